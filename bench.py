@@ -10,12 +10,15 @@ DLT triangulation, frame-to-frame match, motion-only LM pose, local BA (10 KF x 
 10 pose-only).  Keyframes shard across ranks with no data-path collective ("weak" scaling); the only collective is the
 RCCL all-gather of the per-keyframe poses (56 B each) once per step.
 
-`--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under torch.distributed.run with N ranks
+`--gpus N` with N > 1 and no WORLD_SIZE in the environment runs itself again in a child torch.distributed.run with N ranks
 (one per GPU, rendezvous on 127.0.0.1); under a launcher, --gpus must equal WORLD_SIZE.  It refuses to run on fewer GPUs.
 
 Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, timed live with HIP events on
 the launch stream through the library's stage profiler) and `cpu_baseline` (the CPU oracle -- a "port", the reference
 itself is unbuildable here -- timed on this host, rank 0 at N=1, on a bounded sample of the same workload).
+
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (dump_step_outputs); the inputs are rendered from fixed
+seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -71,6 +74,71 @@ def schedule_stats(passes):
             "rule": "all three optimize_map passes start from the same poses and landmarks (run_vslam.cpp:61-64: the first two do not write back) and differ only "
                     "by the landmark flags the previous pass left; a pass that flags nothing new is continued to the last pass's 10 iterations instead of "
                     "being repeated -- bit-identical results (tests/test_gpu_lm.py::test_adaptive_schedule_is_bit_identical; --ba-plain-schedule runs every pass)"}
+
+
+DUMP_SAMPLE_KEYFRAMES = 16        # --dump-outputs: keyframes whose per-keypoint arrays are written (a fixed, seeded choice)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _fields_f64(a):
+    """structured array (KEYPOINT_DTYPE / DMATCH_DTYPE) -> float64 (..., n_fields) in field order; every field is exact in float64"""
+    return np.stack([a[f].astype(np.float64) for f in a.dtype.names], -1)
+
+
+def _first_rows(a, counts):
+    """row i of `a` keeps its first counts[i] slots, the rest are zeroed (slots past a list's count are not part of the result)"""
+    a = a.copy()
+    for i, n in enumerate(counts):
+        a[i, max(int(n), 0):] = 0
+    return a
+
+
+def dump_step_outputs(pipe, out_dir, trajectory=None):
+    """--dump-outputs DIR: what the timed path handed back in its last step -- KeyframePipeline.download(), the host view of the step's device
+    results -- as DIR/<name>.npy, float32 or float64, at most DUMP_MAX_BYTES in all.  Per-keyframe results (counts, pose-stage poses, BA poses and
+    window offsets) are written whole; per-keypoint lists, per-landmark and per-edge arrays for the keyframes (and their BA windows) in
+    sample_keyframes.npy, a fixed seeded choice; structured arrays become (..., fields) float64 in field order."""
+    o = pipe.download()
+    B = pipe.B
+    kf = np.sort(np.random.default_rng(0).choice(B, min(B, DUMP_SAMPLE_KEYFRAMES), replace=False))
+    img = np.concatenate([kf, B + kf])          # their left, then right images
+    d = {"sample_keyframes": kf.astype(np.float64)}
+    for k in ("cnt", "nlr", "nf2f", "pn", "ninl"):
+        d[k] = o[k].astype(np.float64)
+    d["Tpnp"] = o["Tpnp"].astype(np.float64)
+    n_lr, n_f2f, n_pn = o["nlr"][kf], o["nf2f"][kf], o["pn"][kf]
+    d["kps"] = _first_rows(_fields_f64(o["kps"][img]), o["cnt"][img])
+    d["desc"] = _first_rows(o["desc"][img].astype(np.float32), o["cnt"][img])
+    d["lr"] = _first_rows(_fields_f64(o["lr"][kf]), n_lr)
+    d["f2f"] = _first_rows(_fields_f64(o["f2f"][kf]), n_f2f)
+    for k in ("xyz", "valid", "rel"):
+        d[k] = _first_rows(o[k][kf].astype(np.float32), n_lr)
+    for k in ("pxyz", "puv", "inl"):
+        d[k] = _first_rows(o[k][kf].astype(np.float32), n_pn)
+    if pipe.with_ba:
+        d["ba_T"] = o["ba_T"].astype(np.float64)
+        # (ba_chi2 is not written: the step passes no chi2 buffer to the BA)
+        tracks = pipe.ba_windows == "tracks"
+        lo = o["ba_lm_off"] if tracks else pipe.h_lm_off
+        lm = np.concatenate([np.arange(lo[b], lo[b + 1]) for b in kf])
+        d["ba_inl"] = o["ba_inl"][lm].astype(np.float32)
+        if tracks:
+            eo = o["ba_e_off"]
+            e = np.concatenate([np.arange(eo[b], eo[b + 1]) for b in kf])
+            for k in ("ba_lm_off", "ba_e_off", "ba_nkf", "ba_build_status"):
+                d[k] = o[k].astype(np.float64)
+            d["ba_xyz"] = o["ba_xyz"][lm].astype(np.float32); d["ba_rel"] = o["ba_rel"][lm].astype(np.float32)
+            d["ba_kf"] = o["ba_kf"][e].astype(np.float64); d["ba_lm"] = o["ba_lm"][e].astype(np.float64); d["ba_uv"] = o["ba_uv"][e].astype(np.float32)
+    if trajectory is not None:
+        d["trajectory"] = trajectory.detach().cpu().numpy().astype(np.float64)
+    del o
+    total = sum(a.nbytes for a in d.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in d.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": sorted(d), "bytes": int(total), "sample_keyframes": [int(b) for b in kf]}
 
 
 def _sha16(path):
@@ -798,6 +866,9 @@ def main():
     ap.add_argument("--render-workers", type=int, default=-1, help="processes that render the synthetic frames (-1: one per available core up to 32; 0: in-process, "
                                                                      "e.g. under rocprofv3, which would otherwise attach to every worker)")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed repeats, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB: "
+                         "per-keyframe results whole, per-keypoint ones for a fixed sample of keyframes; dump_step_outputs); rank 0's batch")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -814,7 +885,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush(); sys.stderr.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess   # (a child process, not exec: device_count() above has already initialised the HIP runtime in this one)
+        raise SystemExit(subprocess.call(cmd))
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d does not match WORLD_SIZE %d (launch with --nproc-per-node %d, or drop the launcher and let "
@@ -913,6 +985,9 @@ def main():
 
     # the timed repeats run WITHOUT the stage profiler (its hipEvent brackets sit between the kernels) ...
     rep_s = [timed_region(one_step) for _ in range(max(args.repeats, 1))]
+    dumped = None
+    if args.dump_outputs and rank == 0:   # (the last timed step ran on pipeline (k - 1) mod P; the later regions overwrite its buffers)
+        dumped = dump_step_outputs(ring.pipes[(ring.k - 1) % len(ring)], args.dump_outputs, chained[0] if seq_mode else None)
     one_step_serial = lambda: one_step(serial=True)
     serial_s = timed_region(one_step_serial) if n_flight > 1 else None   # the same steps with ONE batch in flight (the figure of the earlier rounds)
     plain_s = None
@@ -1130,6 +1205,8 @@ def main():
         }
         if win_stats is not None:
             res["stats"]["ba_windows"] = win_stats
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         if host_inputs is not None:
             res["inputs_from_host"] = host_inputs
         if seq_mode and chained[0] is not None:

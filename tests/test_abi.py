@@ -25,9 +25,9 @@ def test_header_symbols_exported(pkg):
     assert sorted(pkg.ABI_SYMBOLS) == declared
 
 
-def test_header_is_plain_c():
+def test_header_is_plain_c(tmp_path):
     src = '#include "vslam_hip.h"\nint main(void){ vslam_params p; vslam_default_params(&p); return sizeof(vslam_keypoint)==28 && sizeof(vslam_dmatch)==16 ? 0 : 1; }\n'
-    out = "/tmp/abi_c_check.o"
+    out = str(tmp_path / "abi_c_check.o")
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-c", "-", "-o", out], input=src.encode(), check=True)
 
 

@@ -119,3 +119,35 @@ def test_kitti_root_hook(tmp_path, monkeypatch):
     r = b.kitti_measure(n_frames=50)
     assert r["available"] is True and "error" not in r, r
     assert r["frames"] == 8 and r["keypoints_per_frame_mean"] >= 400 and r["pnp_inliers_min"] >= 10 and r["summary"]
+
+
+def test_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: the last timed step's results as float32 / float64 .npy files under 64 MB; the same arguments give the same files, and
+    they are what one step of a pipeline over the same rendered inputs gives (warmup 1 + 2 timed steps on 2 pipelines: the last ran on pipeline 0)"""
+    import importlib.util
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    from stereo_visual_slam_amd.pipeline import KeyframePipeline
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "16", "--unique-frames", "8", "--no-cpu-baseline", "--inputs", "resident",
+            "--no-reference-pipeline", "--no-config4", "--no-config4-step", "--no-live-dropin", "--no-plain-schedule"]
+    dirs = [tmp_path / "a", tmp_path / "b", tmp_path / "direct"]
+    for d in dirs[:2]:
+        r = _bench(*(args + ["--dump-outputs", str(d)]))
+        assert r["steps"] == 2 and r["dump_outputs"]["bytes"] <= 64 << 20
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and {"Tpnp.npy", "ba_T.npy", "kps.npy", "desc.npy", "lr.npy", "xyz.npy"} <= set(names)
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64 << 20
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    pipe = KeyframePipeline(16, anms_num=1500, n_lm=3000, unique_frames=8, seed=0, ba_windows="tracks")
+    try:
+        pipe.step()
+        b.dump_step_outputs(pipe, str(dirs[2]))
+    finally:
+        pipe.close()
+    assert sorted(os.listdir(dirs[2])) == names
+    for n in names:
+        a = np.load(dirs[0] / n)
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, np.load(dirs[1] / n)) and np.array_equal(a, np.load(dirs[2] / n)), n
+    assert np.load(dirs[0] / "cnt.npy").min() > 100 and np.load(dirs[0] / "Tpnp.npy").shape == (16, 7)
