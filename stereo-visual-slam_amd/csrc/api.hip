@@ -152,6 +152,10 @@ static int orb_status_check(Ctx* c, int B) {
     return VSLAM_OK;
 }
 
+// Images per call from which orb_pyrblur_kernel replaces the separate resize + blur (+ FAST) kernels; Tuning::orb_fuse_min overrides it
+constexpr int kOrbFuseMinDefault = 96;
+static int orb_fuse_min(const Ctx* c) { return c->tune.orb_fuse_min >= 0 ? c->tune.orb_fuse_min : kOrbFuseMinDefault; }
+
 // detect + (ANMS) + (describe) on device-resident images
 static int orb_pipeline(Ctx* c, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, int anms_num, int regroup, bool describe,
                         vslam_keypoint* d_kps, uint8_t* d_desc, int32_t* d_count) {
@@ -163,7 +167,7 @@ static int orb_pipeline(Ctx* c, const uint8_t* d_imgs, size_t img_bytes, int pit
     // dependent launches that each do resize AND blur are slower than seven short resize launches + one blur launch over all levels
     // (0.36 vs 0.43 ms for two images).  [r6] With FAST inside the tile pass and the blur on the matrix cores the fused kernel wins from ~64 images on
     // (128 images: 0.89 vs 0.96 ms, 256: 1.35 vs 1.55; round 5's break-even was ~300).  Tuning::orb_fuse_min overrides the threshold (tests run both paths).
-    const bool fused = describe && B >= (c->tune.orb_fuse_min >= 0 ? c->tune.orb_fuse_min : 96);
+    const bool fused = describe && B >= orb_fuse_min(c);
     if (fused) { // [r6] ... and FAST + NMS of every level from the same staged tile
         if ((rc = launch_orb_pyrblur(c->plan, c->tab, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, c->orb.d_blur, c->p.fast_threshold, c->orb.d_corners,
                                      c->orb.d_corner_cnt, c->orb.d_status, c->stream))) return rc;
@@ -416,7 +420,7 @@ int vslam_orb_compute(vslam_ctx* ctx, const uint8_t* img, int w, int h, int stri
     VS_HIP(hipMemcpyAsync(d_in, kps, sizeof(vslam_keypoint) * n, hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemcpyAsync(d_n, &nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(c->orb.d_status, 0, sizeof(int32_t), c->stream));
-    const bool fused = 1 >= (c->tune.orb_fuse_min >= 0 ? c->tune.orb_fuse_min : 384); // (one image: the separate kernels unless a test forces the fused one)
+    const bool fused = 1 >= orb_fuse_min(c); // (one image: the separate kernels unless a test forces the fused one)
     if (fused) { if ((rc = launch_orb_pyrblur(c->plan, c->tab, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->orb.d_blur, 0, nullptr, nullptr, nullptr, c->stream))) return rc; }
     else {
         if ((rc = launch_orb_pyramid(c->plan, c->tab, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->stream))) return rc;

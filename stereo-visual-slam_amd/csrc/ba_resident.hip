@@ -29,9 +29,7 @@
 
 namespace vslam {
 
-#ifndef VSLAM_RS_MIN_WAVES
-#define VSLAM_RS_MIN_WAVES 2 // waves per SIMD the register allocation must leave room for (2: 256 VGPRs)
-#endif
+constexpr int kRsMinWaves = 2; // waves per SIMD the register allocation must leave room for (2: 256 VGPRs)
 // [r5, second session] 256 lanes per window, TWO windows per CU (the launcher asks for half a CU's LDS): with 512 lanes a window held a whole CU
 // -- all of its registers, 156 KB of LDS -- at 20-27 % VALU activity, and its serial stretches (the 60-pivot factorisation: one or two waves busy
 // for 23 % of the time, barriers, exposed round trips) idled the other waves.  Two windows of four waves each use the same registers and fill each
@@ -103,8 +101,8 @@ __device__ inline long long to_fixed(double v, double scale) { return __double2l
 __device__ inline int rs_blk(int I, int K) { return (I * (I + 1) / 2 + K) * 36; }
 
 template <bool SCHED, int BLOCK>
-__global__ __launch_bounds__(BLOCK, VSLAM_RS_MIN_WAVES) void ba_resident_kernel(RsArgs ra, int iters, int update_poses, int update_lms, int classify, int adaptive) {
-    constexpr int kRsBlock = BLOCK, kRsWaves = BLOCK / 64, kRsMaxRows = 20 * kRsWaves;
+__global__ __launch_bounds__(BLOCK, kRsMinWaves) void ba_resident_kernel(RsArgs ra, int iters, int update_poses, int update_lms, int classify, int adaptive) {
+    constexpr int kRsBlock = BLOCK, kRsWaves = BLOCK / 64;
     constexpr int kRsSub = kRsStreams / kRsWaves; // row streams a wave carries (1 or 2)
     const LmWindowArgs& a = ra.a;
     extern __shared__ __align__(16) unsigned char dyn[];
@@ -156,7 +154,8 @@ __global__ __launch_bounds__(BLOCK, VSLAM_RS_MIN_WAVES) void ba_resident_kernel(
     const CamK ck = make_camk(K);
     const double delta = a.huber_delta;
     const double f2sum = ck.fx2 + ck.fy2;
-    const int slot27 = wave_slot<27>(lane), slot36 = wave_slot<36>(lane), slot33 = wave_slot<33>(lane), slot6 = wave_slot<6>(lane);
+    [[maybe_unused]] const int slot27 = wave_slot<27>(lane); // (never read; dropping it changes the register allocation of the kernel)
+    const int slot36 = wave_slot<36>(lane), slot33 = wave_slot<33>(lane), slot6 = wave_slot<6>(lane);
     int dst21 = 0, dst36 = 0; // where the butterfly sum this lane ends up with goes inside a 6 x 6 block
     if (slot33 >= 0 && slot33 < 21) { int rr = 0, rem = slot33; while (rem >= 6 - rr) { rem -= 6 - rr; ++rr; } dst21 = 6 * (rr + rem) + rr; } // upper (rr, cc) -> lower entry (cc, rr)
     if (slot36 >= 0) { const int rr = slot36 / 6, cc = slot36 - 6 * rr; dst36 = 6 * cc + rr; }

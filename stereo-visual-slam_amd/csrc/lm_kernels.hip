@@ -46,47 +46,21 @@
 
 namespace vslam {
 
-#ifndef VSLAM_LM_BLOCK
-#define VSLAM_LM_BLOCK 512
-#endif
-#ifndef VSLAM_LM_DYNAMIC_ITEMS
-#define VSLAM_LM_DYNAMIC_ITEMS 1
-#endif
-#ifndef VSLAM_LM_ITEM_FIXED
-#define VSLAM_LM_ITEM_FIXED 128 // fixed cost of a Schur work item, in hits (see the item balance)
-#endif
-#ifndef VSLAM_LM_MIN_WAVES
-#define VSLAM_LM_MIN_WAVES 2 // waves per SIMD the register allocation must leave room for
-#endif
-// VSLAM_LM_PRIO = n > 0 (tuning aid): the two waves of a SIMD (wave w and w + 4 of the 8-wave workgroup) alternate their issue
-// priority every n rows of the hot loops, so that the older wave does not finish its share 25-30 % before its partner
-#ifndef VSLAM_LM_PRIO
-#define VSLAM_LM_PRIO 0
-#endif
-#if VSLAM_LM_PRIO > 0
-#define LM_PRIO_TICK(cnt) do { if ((((cnt) / VSLAM_LM_PRIO) ^ (wave >> 2)) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); ++(cnt); } while (0)
-#else
-#define LM_PRIO_TICK(cnt) do {} while (0)
-#endif
-constexpr int kLmBlock = VSLAM_LM_BLOCK;
+constexpr int kLmBlock = 512;
+constexpr int kLmItemFixed = 128; // fixed cost of a Schur work item, in hits (see the item balance)
+constexpr int kLmMinWaves = 2;    // waves per SIMD the register allocation must leave room for
 constexpr int kLmWaves = kLmBlock / 64;
 constexpr int kMaxKf = VSLAM_MAX_KF;
 constexpr int kMaxNp = 6 * kMaxKf;
 constexpr int kMaxPairs = kMaxKf * (kMaxKf + 1) / 2;
 constexpr int kHitsPerEdge = (kMaxKf + 1) / 2 + 1;
-#ifndef VSLAM_LM_DINV_LDS
-#define VSLAM_LM_DINV_LDS 1950
-#endif
-constexpr int kDinvLds = VSLAM_LM_DINV_LDS;  // landmarks whose Dinv stays in LDS (48 B each: the 96 KB the static state leaves free)
+constexpr int kDinvLds = 1950;  // landmarks whose Dinv stays in LDS (48 B each: the 96 KB the static state leaves free)
 constexpr int kLin = 2;        // doubles per edge of linearisation scratch: the Huber weight at the current state / at the trial state
 constexpr int kPoseParts = 3;  // a pose's by-pose edge list is summed by this many waves (parts added in a fixed order)
 constexpr int kCntStride = 80; // per-wave counter row (>= kMaxPairs)
-constexpr int kItemSlots = (kMaxPairs + kLmWaves - 1) / kLmWaves; // Schur work items (keyframe pairs) per wave
-#ifndef VSLAM_LM_SLOTS
-#define VSLAM_LM_SLOTS 5
-#endif
+constexpr int kItemSlots = (kMaxPairs + kLmWaves - 1) / kLmWaves; // item[] holds kLmWaves x kItemSlots >= kMaxPairs Schur work items
 constexpr int kDbgSlots = 24;               // phase cycle counters per window (VSLAM_LM_PROFILE)
-constexpr int kLmSlots = VSLAM_LM_SLOTS;    // observations per landmark kept in the slot table (the rest is reached through the CSR)
+constexpr int kLmSlots = 5;                 // observations per landmark kept in the slot table (the rest is reached through the CSR)
 constexpr int kSchedFinalIters = 10;        // iterations of the schedule's last optimize_map pass (run_vslam.cpp:66)
 constexpr int kRowCap = 512;                // 64-landmark rows with a slot-width entry in LDS (32 768 landmarks per window)
 
@@ -104,7 +78,7 @@ struct alignas(16) LmShared {
     double part[kMaxKf * kPoseParts * 27]; // per (pose, part) partial sums of the pose blocks
     int ptot[kCntStride];                  // hits per keyframe pair
     int cnt[kLmWaves * kCntStride];        // per-wave counters / running offsets of the list builders
-    uint8_t item[kLmWaves * kItemSlots];   // Schur work items (pair << 1 | row half) dealt to waves, 0xFF = none
+    uint8_t item[kLmWaves * kItemSlots];   // Schur work items (pair << 1 | row half), costliest first, 0xFF = none
     uint8_t pk1[kCntStride], pk2[kCntStride];
     int kfp[kMaxKf + 4];                   // kf_ptr (keyframe-major range starts), for the per-edge keyframe lookup
     int rowp[kMaxKf + 4];                  // first 64-edge row of every keyframe's list (rows never straddle keyframes)
@@ -166,35 +140,16 @@ __device__ inline double block_max(double v, double* red) {
     return s;
 }
 
-// v - sum_{kk < 6 nK} a[kk] * b[kk] for two 16-B aligned LDS rows: the operands of block K + 1 are requested before the products
-// of block K are formed, and the sum runs in two independent chains (a dependent f64 FMA issues every 8 cycles).
-__device__ inline double row_dot_sub(double v, const double* a, const double* b, int nK) {
-    const double2* ra2 = reinterpret_cast<const double2*>(a);
-    const double2* rb2 = reinterpret_cast<const double2*>(b);
-    if (nK <= 0) return v;
-    double s0 = 0, s1 = 0;
-    double2 a0 = ra2[0], a1 = ra2[1], a2 = ra2[2], b0 = rb2[0], b1 = rb2[1], b2 = rb2[2];
-    for (int K = 1; K < nK; ++K) {
-        const double2 c0 = ra2[3 * K], c1 = ra2[3 * K + 1], c2 = ra2[3 * K + 2];
-        const double2 d0 = rb2[3 * K], d1 = rb2[3 * K + 1], d2 = rb2[3 * K + 2];
-        s0 = fma(a0.x, b0.x, s0); s1 = fma(a0.y, b0.y, s1); s0 = fma(a1.x, b1.x, s0); s1 = fma(a1.y, b1.y, s1); s0 = fma(a2.x, b2.x, s0); s1 = fma(a2.y, b2.y, s1);
-        a0 = c0; a1 = c1; a2 = c2; b0 = d0; b1 = d1; b2 = d2;
-    }
-    s0 = fma(a0.x, b0.x, s0); s1 = fma(a0.y, b0.y, s1); s0 = fma(a1.x, b1.x, s0); s1 = fma(a1.y, b1.y, s1); s0 = fma(a2.x, b2.x, s0); s1 = fma(a2.y, b2.y, s1);
-    return v - (s0 + s1);
-}
-
 // SCHED: the in-kernel adaptive schedule (below).  A separate instance: the pass loop costs the single-pass code ~5 % in spilled registers, and the
 // single-pass instance is what the host tier's per-call latency and the plain three-launch schedule run.
 template <bool IMPL, bool SCHED = false>
-__global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel(LmKernelArgs ka, int mode, int iters, int update_poses, int update_lms,
+__global__ __launch_bounds__(kLmBlock, kLmMinWaves) void lm_window_kernel(LmKernelArgs ka, int mode, int iters, int update_poses, int update_lms,
                                                             int classify, int reuse_csr) {
     static_assert(!(IMPL && SCHED), "the schedule is a property of the window problems");
     const LmWindowArgs& a = ka.a;
     __shared__ LmShared sm;
     const int w = ka.order ? ka.order[blockIdx.x] : (int)blockIdx.x;
     if (ka.defer && !(ka.defer[w] & 1)) return; // (uniform) ba_resident_kernel has done this window
-    int prio_cnt = 0; (void)prio_cnt;
     // keyframes of this window: a.n_kf slots (the pose stride), of which window w uses the first n_kf_w[w] (a growing map)
     const int nk = (!IMPL && a.n_kf_w) ? min(max(a.n_kf_w[w], 1), a.n_kf) : a.n_kf, np = 6 * nk;
     const size_t Tbase = (size_t)w * a.n_kf * 7;
@@ -546,19 +501,14 @@ __global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel
             if (tid < nitems) {
                 const int a1 = sm.pk1[tid];
                 const int hits_i = a1 == sm.pk2[tid] ? sm.kfp[a1 + 1] - sm.kfp[a1] : (int)sm.ptot[tid];
-                s_work[tid] = hits_i > 0 ? ((hits_i + 63) & ~63) + VSLAM_LM_ITEM_FIXED : 0;
+                s_work[tid] = hits_i > 0 ? ((hits_i + 63) & ~63) + kLmItemFixed : 0;
             }
             __syncthreads();
             if (tid < nitems) {
                 const int mine = s_work[tid];
                 int rank = 0;
                 for (int j = 0; j < nitems; ++j) { const int c = s_work[j]; rank += (c > mine) || (c == mine && j < tid); }
-#if VSLAM_LM_DYNAMIC_ITEMS
                 sm.item[rank] = (uint8_t)tid; // costliest first: the waves draw the items from this list as they become free (below)
-#else
-                const int row = rank / kLmWaves, col = rank % kLmWaves;
-                sm.item[((row & 1) ? kLmWaves - 1 - col : col) * kItemSlots + row] = (uint8_t)tid;
-#endif
             }
         }
     }
@@ -582,10 +532,7 @@ __global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel
     // then the arithmetic -- the per-thread summation order is unchanged.
     const float2* uv2 = reinterpret_cast<const float2*>(uv);
     constexpr int kEvalU = 4;
-#ifndef VSLAM_LM_U
-#define VSLAM_LM_U 2
-#endif
-    constexpr int kLmU = VSLAM_LM_U, kLmE = kLmSlots; // landmark-wise phases: landmarks per batch, observations preloaded per landmark
+    constexpr int kLmU = 2, kLmE = kLmSlots; // landmark-wise phases: landmarks per batch, observations preloaded per landmark
     // Evaluation + linearisation at (Rt, Pcur) in one keyframe-major pass.  The keyframe-major edge lists are cut into rows
     // of 64 edges (a row never straddles two keyframes); every wave owns a contiguous range of rows and streams it through
     // a register queue (landmark ids and observations two rows ahead, landmark positions one row ahead -- a row is ~2000 cycles of issue, deeper queues only cost register moves: the lists come from
@@ -604,7 +551,7 @@ __global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel
     const int nrows = sm.rowp[nk], rows_per_wave = (nrows + kLmWaves - 1) / kLmWaves;
     auto eval = [&](const double* Rt, const double* Pcur, double* dstW, double* Hdst, double* bdst) -> double {
         double part = 0;
-        const long long t_ev = cyc ? clock64() : 0;
+        [[maybe_unused]] const long long t_ev = cyc ? clock64() : 0; // (never read; dropping the clock read changes the kernel's machine code)
         const int ra = min(wave * rows_per_wave, nrows), rb = min(ra + rows_per_wave, nrows);
         if (ra < rb) {
             RowIt cur;
@@ -614,14 +561,8 @@ __global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel
                 cur.k = k; cur.j = sm.kfp[k] + 64 * (ra - sm.rowp[k]); cur.jend = sm.kfp[k + 1];
             }
             RowIt ahead = cur;
-#ifndef VSLAM_LM_EVAL_PD
-#define VSLAM_LM_EVAL_PD 1
-#endif
-#ifndef VSLAM_LM_EVAL_QD
-#define VSLAM_LM_EVAL_QD 2
-#endif
-            constexpr int kPD = VSLAM_LM_EVAL_PD; // rows of landmark positions in flight
-            constexpr int kQD = VSLAM_LM_EVAL_QD; // rows of landmark ids / observations in flight (>= kPD)
+            constexpr int kPD = 1; // rows of landmark positions in flight
+            constexpr int kQD = 2; // rows of landmark ids / observations in flight (>= kPD)
             static_assert(kQD >= kPD && kPD >= 1, "queue depths");
             int lq[kQD];
             float2 zq[kQD];
@@ -653,7 +594,6 @@ __global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel
             // queues are rotated with register moves instead of static indices)
 #pragma unroll 1
             for (int row = ra;; ++row) {
-                LM_PRIO_TICK(prio_cnt);
                 const bool done = row >= rb;
                 if (done || cur.k != kacc) {
                     flush(kacc);
@@ -869,17 +809,12 @@ __global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel
                 // estimated cost left the waves 22-27 % of the pass waiting for the slowest one: the older wave of a SIMD runs faster than its
                 // partner, and an item's fixed cost is not proportional to its hits.)  Which wave computes an item does not change its result: one
                 // wave owns a block and reduces it in a fixed order.
-#if VSLAM_LM_DYNAMIC_ITEMS
                 for (;;) {
                     int slot = 0;
                     if (lane == 0) slot = atomicAdd(&sm.flag[6], 1);
                     slot = __builtin_amdgcn_readfirstlane(slot);
                     if (slot >= npairs) break;
                     const int p = sm.item[slot];
-#else
-                for (int slot = 0; slot < kItemSlots; ++slot) {
-                    const int p = sm.item[wave * kItemSlots + slot];
-#endif
                     if (p == 0xFF) continue; // uniform per wave
                     PH(23); // (item boundary: what came before was the previous item's reduction + store)
                     const int k1 = sm.pk1[p], k2 = sm.pk2[p];
@@ -904,7 +839,6 @@ __global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel
                         double g0 = PC(bl, 0, ln), g1 = PC(bl, 1, ln), g2 = PC(bl, 2, ln);
                         PH(15); // (item prologue: first-row operands requested)
                         for (; j < jend; j += 64) {
-                            LM_PRIO_TICK(prio_cnt);
                             double2 Dan, Dbn, Dcn;
                             loadD_row(lnn, Dan, Dbn, Dcn); // (first: see loadD_row -- nothing of THIS row's prefetch is in flight yet)
                             const int lnnn = kf_lm[min(j + 128, jend - 1)];
@@ -978,7 +912,6 @@ __global__ __launch_bounds__(kLmBlock, VSLAM_LM_MIN_WAVES) void lm_window_kernel
                         loadD(h.y, Da, Db, Dc);
                         PH(15);
                         for (; j < jend; j += 64) {
-                            LM_PRIO_TICK(prio_cnt);
                             double2 Dan, Dbn, Dcn;
                             loadD_row(hn.y, Dan, Dbn, Dcn); // (first: see loadD_row)
                             const int2 hnn = hits[min(j + 128, jend - 1)];
@@ -1911,9 +1844,6 @@ static int carve(LmScratch& g_lm, LmKernelArgs& ka, size_t total_lm, size_t tota
 // whole launch waits for it while 255 CUs idle; in descending order the last ones started are the smallest (longest-processing-time-first list
 // scheduling).  One workgroup sorts (edge count descending, window index ascending) keys in LDS; which workgroup computes a window changes nothing
 // in its result.
-#ifndef VSLAM_LM_LPT
-#define VSLAM_LM_LPT 1
-#endif
 __global__ void lm_fill_kernel(int32_t* __restrict__ p, int n, int v) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = v; }
 constexpr int kOrderCap = 4096;
 __global__ __launch_bounds__(1024) void lm_order_kernel(const int32_t* __restrict__ edge_off, int n, int32_t* __restrict__ order) {
@@ -1965,7 +1895,7 @@ int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, 
     const bool adaptive = !(scratch->tune && scratch->tune->ba_adaptive == 0);
     const bool resident_on = (schedule || mode == 0) && !(scratch->tune && scratch->tune->ba_resident == 0);
     ProfScope prof__(stream, "lm_window_kernel", (schedule ? (adaptive ? 2 : 4) : 1) + (resident_on ? 1 : 0)); // (family name kept from rounds 1-4; the BA schedule's launches)
-    if (VSLAM_LM_LPT && a.n_windows > 1 && a.n_windows <= kOrderCap)
+    if (a.n_windows > 1 && a.n_windows <= kOrderCap)
         hipLaunchKernelGGL(lm_order_kernel, dim3(1), dim3(1024), 0, stream, a.edge_off, a.n_windows, const_cast<int32_t*>(ka.order));
     else ka.order = nullptr;
     // optimize_map passes: ba_resident_kernel takes every window whose landmark state fits the LDS of a CU (Tuning::ba_resident = 0: none) and marks

@@ -33,11 +33,8 @@ __device__ inline int4 expand_half(uint32_t bits16) {
     return make_int4((int)expand_nibble(bits16), (int)expand_nibble(bits16 >> 4), (int)expand_nibble(bits16 >> 8), (int)expand_nibble(bits16 >> 12));
 }
 
-#ifndef VSLAM_MATCH_CT
-#define VSLAM_MATCH_CT 4
-#endif
 constexpr int kMatchBlock = 256;             // 4 waves
-constexpr int kColTiles = VSLAM_MATCH_CT;    // 32-column MFMA tiles per wave held in registers (2: accumulators double-buffered; 4: one A read feeds four tiles -- 0.137 vs 0.148 ms per 256 items of 1500 x 1500, 0.103 vs 0.099 at 1100, 0.046 vs 0.044 at 700)
+constexpr int kColTiles = 4;                 // 32-column MFMA tiles per wave held in registers (2: accumulators double-buffered; 4: one A read feeds four tiles -- 0.137 vs 0.148 ms per 256 items of 1500 x 1500, 0.103 vs 0.099 at 1100, 0.046 vs 0.044 at 700)
 constexpr int kColsPerWave = 32 * kColTiles;
 constexpr int kColsPerBlock = (kMatchBlock / 64) * kColsPerWave;
 constexpr int kQRows = 32;                   // query rows per LDS tile
@@ -136,34 +133,15 @@ __global__ __launch_bounds__(kMatchBlock) void match_train_nearest_kernel(
     int m[kColTiles];
 #pragma unroll
     for (int t = 0; t < kColTiles; ++t) m[t] = INT_MIN;
-    if constexpr (kColTiles <= 2) {
-        // software pipeline: the MFMAs of tile t + 1 are issued before the (VALU) epilogue of tile t (two accumulator sets)
-        v16i accA[kColTiles], accB[kColTiles];
-        mma_tile(0, accA);
-        for (int tile = tile0; tile < tile1; tile += 2) {
-            // ---- stage tile + 1 into buffer 1, issue its MFMAs, then fold tile
-            if (tile + 1 < tile1) { sstore(1, x); if (tile + 2 < tile1) gload(tile + 2, x); }
-            __syncthreads();
-            if (tile + 1 < tile1) mma_tile(1, accB);
-            fold_tile(accA, tile * kQRows + 4 * h, nq, tile * kQRows + kQRows <= nq, m);
-            if (tile + 1 >= tile1) break;
-            // ---- stage tile + 2 into buffer 0, issue its MFMAs, then fold tile + 1
-            if (tile + 2 < tile1) { sstore(0, x); if (tile + 3 < tile1) gload(tile + 3, x); }
-            __syncthreads();
-            if (tile + 2 < tile1) mma_tile(0, accA);
-            fold_tile(accB, (tile + 1) * kQRows + 4 * h, nq, (tile + 1) * kQRows + kQRows <= nq, m);
-        }
-    } else {
-        // four column tiles per wave: one set of accumulators; a query tile read from LDS once feeds 32 MFMAs (half the LDS
-        // traffic per MAC); the other wave of the SIMD fills the MFMA pipe while this one folds
-        v16i acc[kColTiles];
-        for (int tile = tile0; tile < tile1; ++tile) {
-            const int buf = (tile - tile0) & 1;
-            if (tile + 1 < tile1) { sstore(buf ^ 1, x); if (tile + 2 < tile1) gload(tile + 2, x); } // (buffer buf ^ 1 was released by the barrier below)
-            mma_tile(buf, acc);
-            fold_tile(acc, tile * kQRows + 4 * h, nq, tile * kQRows + kQRows <= nq, m);
-            __syncthreads();
-        }
+    // four column tiles per wave: one set of accumulators; a query tile read from LDS once feeds 32 MFMAs (half the LDS
+    // traffic per MAC); the other wave of the SIMD fills the MFMA pipe while this one folds
+    v16i acc[kColTiles];
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int buf = (tile - tile0) & 1;
+        if (tile + 1 < tile1) { sstore(buf ^ 1, x); if (tile + 2 < tile1) gload(tile + 2, x); } // (buffer buf ^ 1 was released by the barrier below)
+        mma_tile(buf, acc);
+        fold_tile(acc, tile * kQRows + 4 * h, nq, tile * kQRows + kQRows <= nq, m);
+        __syncthreads();
     }
 #pragma unroll
     for (int t = 0; t < kColTiles; ++t) m[t] = max(m[t], __shfl_xor(m[t], 32));

@@ -26,11 +26,9 @@
 
 #include "orb_pattern.inc"
 
-#ifndef VSLAM_BLUR_TILE_H
-#define VSLAM_BLUR_TILE_H 64 // rows of a pyramid / blur tile (a wave owns a quarter: 6 halo rows of horizontal passes per wave)
-#endif
-
 namespace vslam {
+
+constexpr int kBlurTileH = 64; // rows of a pyramid / blur tile (a wave owns a quarter: 6 halo rows of horizontal passes per wave)
 
 __device__ __constant__ signed char c_pattern[256 * 4];
 
@@ -96,43 +94,7 @@ __device__ inline LevelView level_view(const LevelTable& T, int l, const uint8_t
     return v;
 }
 
-// Stage a tw x th (tw % 4 == 0) pixel tile with origin (x0, y0) into LDS.  Interior tiles take one unaligned dword load
-// per 4 pixels (global memory tolerates unaligned dwords); tiles that cross the image edge fall back to per-byte loads
-// with reflect-101 (REFLECT) or clamped (!REFLECT) coordinates.
-// SKIP_FAR: dwords that start more than 3 columns / rows beyond the image (a 7-tap filter never reads them) are left unwritten.
-template <bool REFLECT, int NTHREADS, bool SKIP_FAR = false>
-__device__ inline void load_tile_u8(uint8_t* lds, int lds_pitch, const uint8_t* __restrict__ src, int spitch, int W, int H, int x0, int y0,
-                                    int tw, int th) {
-    const int tw4 = tw >> 2;
-    if (x0 >= 0 && y0 >= 0 && x0 + tw <= W && y0 + th <= H) { // uniform
-        for (int i = threadIdx.x; i < th * tw4; i += NTHREADS) {
-            const int r = i / tw4, c4 = (i - r * tw4) << 2;
-            uint32_t v;
-            __builtin_memcpy(&v, src + (size_t)(y0 + r) * spitch + x0 + c4, 4);
-            *reinterpret_cast<uint32_t*>(lds + r * lds_pitch + c4) = v;
-        }
-    } else {
-        for (int i = threadIdx.x; i < th * tw4; i += NTHREADS) {
-            const int r = i / tw4, c4 = (i - r * tw4) << 2;
-            const int xa = x0 + c4;
-            if (SKIP_FAR && (xa >= W + 4 || y0 + r >= H + 3)) continue;
-            const int y = REFLECT ? reflect101(y0 + r, H) : min(max(y0 + r, 0), H - 1);
-            const uint8_t* row = src + (size_t)y * spitch;
-            uint32_t v = 0;
-            if (xa >= 0 && xa + 4 <= W) __builtin_memcpy(&v, row + xa, 4); // only the dwords that straddle the edge go byte by byte
-            else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int x = REFLECT ? reflect101(xa + k, W) : min(max(xa + k, 0), W - 1);
-                    v |= (uint32_t)row[x] << (8 * k);
-                }
-            }
-            *reinterpret_cast<uint32_t*>(lds + r * lds_pitch + c4) = v;
-        }
-    }
-}
-
-// Wide variant for tiles whose rows are CHUNKS x 16 bytes (lds_pitch = 16 * CHUNKS, 16-byte aligned): every thread first ISSUES
+// Stages tiles whose rows are CHUNKS x 16 bytes (lds_pitch = 16 * CHUNKS, 16-byte aligned): every thread first ISSUES
 // all of its 16-byte loads (a tile load is otherwise a chain of dependent round trips, one dword each), then stores them.
 // Chunks nobody reads (more than 3 columns / rows beyond the image) are skipped.  Rows beyond the image come from the reflected
 // (REFLECT) or clamped (!REFLECT) row, as whole rows.  Columns: every chunk is ONE 16-byte load -- a chunk that starts left of the
@@ -202,13 +164,7 @@ __device__ inline void load_tile_b128(uint8_t* lds, const uint8_t* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------- host plan
-#ifndef VSLAM_FAST_TILE_H
-#define VSLAM_FAST_TILE_H 32
-#endif
-#ifndef VSLAM_FAST_TILE_W
-#define VSLAM_FAST_TILE_W 64
-#endif
-constexpr int kTileW = VSLAM_FAST_TILE_W, kTileH = VSLAM_FAST_TILE_H; // FAST output tile per workgroup
+constexpr int kTileW = 64, kTileH = 32; // FAST output tile per workgroup
 static inline int cv_round_host(double v) { return (int)lrint(v); }
 
 int orb_plan_init(OrbPlan* plan, int w, int h, int nfeatures, int kp_capacity) {
@@ -285,14 +241,14 @@ int orb_tables_init(const OrbPlan* plan, OrbTables* t) {
             ibeta[2 * (t->y_off[l] + dy) + 1] = (short)lrintf(fy * 2048.f);
         }
     }
-    // tile ownership of the fused pyramid + blur kernel (256 x VSLAM_BLUR_TILE_H source tiles)
+    // tile ownership of the fused pyramid + blur kernel (256 x kBlurTileH source tiles)
     std::vector<int> tdx, tdy;
     for (int l = 0; l + 1 < kNLevels; ++l) {
         const int sw = plan->lv[l].w, sh = plan->lv[l].h, dw = plan->lv[l + 1].w, dh = plan->lv[l + 1].h;
-        const int ntx = (sw + 255) / 256, nty = (sh + VSLAM_BLUR_TILE_H - 1) / VSLAM_BLUR_TILE_H;
+        const int ntx = (sw + 255) / 256, nty = (sh + kBlurTileH - 1) / kBlurTileH;
         t->tdx_off[l] = (int)tdx.size(); t->tdy_off[l] = (int)tdy.size();
         for (int tx = 0, dx = 0; tx <= ntx; ++tx) { while (dx < dw && xofs[t->x_off[l + 1] + dx] < tx * 256) ++dx; tdx.push_back(tx == ntx ? dw : dx); }
-        for (int ty = 0, dy = 0; ty <= nty; ++ty) { while (dy < dh && yofs[t->y_off[l + 1] + dy] < ty * VSLAM_BLUR_TILE_H) ++dy; tdy.push_back(ty == nty ? dh : dy); }
+        for (int ty = 0, dy = 0; ty <= nty; ++ty) { while (dy < dh && yofs[t->y_off[l + 1] + dy] < ty * kBlurTileH) ++dy; tdy.push_back(ty == nty ? dh : dy); }
     }
     int rc = VSLAM_OK;
     do {
@@ -504,10 +460,6 @@ __global__ __launch_bounds__(256) void orb_fast_kernel(LevelTable T, const uint8
     for (int i = threadIdx.x; i < (kScH * kScW + 3) / 4; i += 256) reinterpret_cast<uint32_t*>(sc)[i] = 0;
     __syncthreads();
     OPH(16);
-#ifndef VSLAM_FAST_DBG
-#define VSLAM_FAST_DBG 0 // tuning aid (timing only): 1 = tile load only, 2 = + pre-test, 3 = + corner score
-#endif
-    if (VSLAM_FAST_DBG == 1) { if (pix[threadIdx.x * 7] == 0xA7 && pix[threadIdx.x] == 0x3C && pix[5] == 1) atomicOr(&d_status[b], 64); return; }
 
     // (a) compass pre-test on the score region (tile + halo 1): a 9-arc always contains two ADJACENT compass pixels (ring
     // positions 0, 4, 8, 12), so a corner needs two adjacent compass pixels all brighter or all darker.  Cheap, and it
@@ -557,7 +509,6 @@ __global__ __launch_bounds__(256) void orb_fast_kernel(LevelTable T, const uint8
     // (b) the survivors' corner score (largest threshold for which the pixel is still a FAST-9/16 corner).  A pixel is a corner at
     // `thr` exactly when that score is >= thr, so the score doubles as the full 16-pixel test: no separate ring-mask pass.
     const int nq = qcount;
-    if (VSLAM_FAST_DBG == 2) { if (nq == 77777 && queue[threadIdx.x] == 9) atomicOr(&d_status[b], 64); return; }
     for (int q = threadIdx.x; q < nq; q += 256) {
         const int i = queue[q];
         const int sy = i / kScW, sx = i - sy * kScW;
@@ -568,7 +519,6 @@ __global__ __launch_bounds__(256) void orb_fast_kernel(LevelTable T, const uint8
     OPH(17);
     const int nc = ccount;
     OPH(18);
-    if (VSLAM_FAST_DBG == 3) { if (nc == 77777 && cqueue[threadIdx.x] == 9) atomicOr(&d_status[b], 64); return; }
     // (d) 3x3 non-max suppression + border cull (edgeThreshold 31): survivors collected in LDS, ONE global atomic per block
     for (int q = threadIdx.x; q < nc; q += 256) {
         const int i = cqueue[q];
@@ -656,7 +606,6 @@ __device__ inline void bitonic_sort_lds_e(K* a, int n) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int C = 64 * E;
     const int g0 = wave * C + lane * E; // this lane's first key
-    const bool mine = g0 < n;           // (n is a power of two: a lane's E keys are all inside or all outside when n >= E)
     K v[E];
     auto load = [&]() {
 #pragma unroll
@@ -972,10 +921,7 @@ __device__ inline bool xcd_image_block(int nb, int B, int& b, int& bx) {
     b = 8 * g + (r & 7); bx = r >> 3;
     return b < B;
 }
-#ifndef VSLAM_ORIENT_BLOCKS
-#define VSLAM_ORIENT_BLOCKS 24
-#endif
-constexpr int kOrientBlocks = VSLAM_ORIENT_BLOCKS, kOrientThreads = 256, kOrientWaves = kOrientThreads / 64;
+constexpr int kOrientBlocks = 24, kOrientThreads = 256, kOrientWaves = kOrientThreads / 64;
 constexpr int kOrientPerWave = 4096 / (kOrientBlocks * kOrientWaves) + 1; // keypoints a wave can be handed, one lane each (kp_capacity <= kOrientPerWave x waves per image, checked at launch)
 static_assert(kOrientPerWave <= 64, "orb_orient_kernel: a lane fetches one keypoint record of its wave's walk");
 // per-lane constants of the patch sums (lane = 8 ry + cx, row slot s): {weights u + 15 | mask} of the lane's four bytes, 0 outside the circular patch
@@ -1254,10 +1200,8 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
         // are binned into a uniform grid (cell lists sorted by rank) and a query walks outward ring by ring until the best
         // distance found is below the distance to the unvisited cells.  Only candidates that cannot be the minimum are
         // skipped and every distance is evaluated exactly as before, so the radii are bit-identical.
-#ifndef VSLAM_ANMS_CELL_MIN
-#define VSLAM_ANMS_CELL_MIN 24 // (32 -> 24: 0.75 -> 0.70 ms per 1024 KITTI-sized images; the grid stays below its 1023 cells: 52 x 16)
-#endif
-        const int csz = max(VSLAM_ANMS_CELL_MIN, (int)ceilf(sqrtf((float)img_w * (float)img_h * (1.f / 900.f))));
+        constexpr int kAnmsCellMin = 24; // (32 -> 24: 0.75 -> 0.70 ms per 1024 KITTI-sized images; the grid stays below its 1023 cells: 52 x 16)
+        const int csz = max(kAnmsCellMin, (int)ceilf(sqrtf((float)img_w * (float)img_h * (1.f / 900.f))));
         const int gx = min(max((img_w + csz - 1) / csz, 1), 1023), gy = max(min((img_h + csz - 1) / csz, 1023 / gx), 1), ncell = gx * gy;
         int* ccnt = reinterpret_cast<int*>(skey);                 // the sort buffer is free until the radius sort
         int* coff = ccnt + 1024;
@@ -1457,7 +1401,7 @@ int launch_anms_flat(int B, const vslam_keypoint* d_in, const int32_t* d_nin, in
 // K6a orb_blur_kernel: GaussianBlur 7x7 sigma 2 (8-bit fixed point, BORDER_REFLECT_101) of every pyramid level into a
 // second pyramid, one launch for all levels.  256 x 64 output tiles: (264 x 70) raw pixels staged in LDS -- the arithmetic of
 // cv::GaussianBlur's 8U path: taps cvRound(k*256) = {18,34,49,55,49,34,18} per pass, (sum + 2^15) >> 16 after the column pass.
-constexpr int kBlurTileW = 256, kBlurTileH = VSLAM_BLUR_TILE_H, kBlurWaveRows = kBlurTileH / 4; // workgroup tile; a wave owns a quarter of the rows, all 256 columns
+constexpr int kBlurTileW = 256, kBlurWaveRows = kBlurTileH / 4; // workgroup tile (x kBlurTileH rows); a wave owns a quarter of the rows, all 256 columns
 constexpr int kBlurRawH = kBlurTileH + 6, kBlurRawChunks = (kBlurTileW + 8 + 15) / 16, kBlurRawPitch = 16 * kBlurRawChunks; // raw tile starts at (x0 - 4, y0 - 3); rows of 17 x 16 B
 
 struct BlurTable {
@@ -1565,17 +1509,15 @@ int launch_orb_blur(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes
 //   (1) the pixels of level l + 1 whose top-left source pixel lies in the tile (cv::resize INTER_LINEAR 8U arithmetic as in
 //       orb_resize_kernel: v_perm picks the source byte pair out of the window, v_dot2_u32_u16 is the horizontal pass; the window now
 //       comes from LDS: three aligned dwords, v_alignbyte), and
-//   (2) the blurred level l (the register-streaming pass of orb_blur_kernel, unchanged).
+//   (2) the blurred level l (the arithmetic of orb_blur_kernel, on the matrix cores: see g_blur_mfma_lane).
 // The tile is staged with reflect-101 coordinates (what the blur needs); the resize clamps its row index itself and its column
 // tables never weight a pixel beyond the image, so the reflected halo is never interpolated.
-#ifndef VSLAM_ORB_BLUR_NT
-#define VSLAM_ORB_BLUR_NT 1 // non-temporal stores of the blurred pyramid (pyramid + blur 1.04 -> 1.02 ms, FAST 0.90 -> 0.89 ms per 512 images)
-#endif
+// The blurred pyramid is stored non-temporally (pyramid + blur 1.04 -> 1.02 ms, FAST 0.90 -> 0.89 ms per 512 images).
 // [r6] (3) FAST-9/16 + 3x3 NMS of level l run on the SAME staged tile (orb_fast_kernel staged every level a second time: 0.54 of its
 // 1.82 ms per 1024 images, and 8 GB of re-reads per step).  The tile carries a halo of 4 rows above / below (the blur needs 3, the ring of a
 // score-halo pixel 3 + 1) and 4 / 12 columns left / right, so every pixel the 256 x 64 tile emits finds its ring and its eight neighbours'
 // rings in LDS.  Structure (per wave, no workgroup barrier until the NMS):
-//   pre-test   a lane owns the 4 columns of an aligned dword and walks 6 centre rows at a time: the dwords of 12 raw rows are widened once to
+//   pre-test   a lane owns the 4 columns of an aligned dword and walks 4 centre rows at a time: the dwords of 10 raw rows are widened once to
 //              packed i16 (even / odd pixels), the compass rule "two adjacent compass pixels both brighter than v + t or both darker than
 //              v - t" costs 12 packed operations per pixel pair, the verdict is the sign of a packed difference shifted into a per-lane mask;
 //   queue      set bits become 16-bit tile positions in a 128-entry per-wave LDS queue (ballot ranks, the count lives in an SGPR);
@@ -1586,17 +1528,14 @@ int launch_orb_blur(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes
 // The workgroup's corner list holds kPfCornerCap entries (7 % of the tile's pixels); a denser tile takes the slow path: every thread scans score dwords.
 constexpr int kPfRawH = kBlurTileH + 8;                       // raw rows: tile rows -4 .. kBlurTileH + 3
 constexpr int kPfScPitch = 264, kPfScH = kBlurTileH + 2;      // score tile: rows -1 .. kBlurTileH, byte column = raw column (tile column + 4)
-#ifndef VSLAM_PF_WAVES
-#define VSLAM_PF_WAVES 8
-#endif
-constexpr int kPfWaves = VSLAM_PF_WAVES;     // waves per tile (4 | 8): the LDS tile allows four workgroups per CU, so 8 waves per tile fill the CU's 32 wave slots
+constexpr int kPfWaves = 8;                  // waves per tile: the LDS tile allows four workgroups per CU, so 8 waves per tile fill the CU's 32 wave slots
 constexpr int kPfQueue = 128;                // per wave: < 64 left over + the <= 64 candidates of one ballot
 constexpr int kPfRawBytes = kPfRawH * kBlurRawPitch, kPfScBytes = kPfScH * kPfScPitch;
 constexpr int kPfCornerCap = (40960 - 32 - kPfRawBytes - kPfScBytes - 2 * kPfQueue * kPfWaves) / 2; // per workgroup: corners (score >= threshold) the tile may emit, before the NMS (what is left of a quarter of the CU's LDS)
 static_assert(kPfCornerCap >= 900, "corner list of orb_pyrblur_kernel");
 static_assert(kBlurTileW == 256 && kBlurRawPitch == 272, "the FAST phase of orb_pyrblur_kernel assumes 64 lanes x 4 columns and 272-byte raw rows");
 static_assert(kPfRawBytes >= 4 * (kBlurTileW * kBlurTileH / 4), "the NMS survivors are collected in the pixel tile's storage");
-// [r6] The 7 x 7 blur of the fused kernel on the MATRIX cores (NW = 8 only): the kernel is bound by the integer VALU rate, the matrix pipe is idle,
+// [r6] The 7 x 7 blur of the fused kernel on the MATRIX cores: the kernel is bound by the integer VALU rate, the matrix pipe is idle,
 // and the separable blur is two banded integer matrix products.  v_mfma_i32_16x16x32_i8 (A, B: 8 bytes per lane, k = 8 (lane >> 4) + byte; D lane l, register v =
 // D[4 (l >> 4) + v][l & 15]; tools/scratch/mfma16_layout.hip).  A wave owns a strip of 32 tile columns, two 16-column tiles, all rows:
 //   row pass     h'(16 raw rows x 16 columns) = (raw ^ 0x80)(16 rows x 32 raw columns) . Bh(32 x 16): the band of the taps; the columns of the window that no output
@@ -1609,12 +1548,6 @@ static_assert(kPfRawBytes >= 4 * (kBlurTileW * kBlurTileH / 4), "the NMS survivo
 //   store        through LDS (the score tile's storage, 272-byte rows): after a barrier every lane stores 16 contiguous bytes of a row -- the round-5 experiment
 //                (32 x 32 tiles, tools/scratch/orb_blur_mfma.hip.txt) stored 16-byte row pieces straight from the accumulator layout and lost its gain there.
 // ~230 VALU instructions per strip instead of ~410.
-#ifndef VSLAM_ORB_BLUR_MFMA
-#define VSLAM_ORB_BLUR_MFMA 1
-#endif
-#ifndef VSLAM_PYRBLUR_DBG
-#define VSLAM_PYRBLUR_DBG 0 // tuning aid (timing only, outputs incomplete): 1 = no blur half, 2 = no resize half, 4 = no FAST, 8 = FAST pre-test without the scores
-#endif
 typedef int bl_v4i __attribute__((ext_vector_type(4)));
 struct BlurMfmaLane { uint32_t bh[64][2], g0[64], g1[64]; };
 constexpr uint32_t blur_tap(int d) { return d == 0 || d == 6 ? 18u : d == 1 || d == 5 ? 34u : d == 2 || d == 4 ? 49u : d == 3 ? 55u : 0u; }
@@ -1655,6 +1588,7 @@ __device__ inline int mbcnt64(unsigned long long m) { return (int)__builtin_amdg
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW, 8) void orb_pyrblur_kernel(PyrBlurArgs a) { // (four tiles per CU: 8 waves per SIMD at NW = 8)
+    static_assert(NW == 8, "the matrix-core blur and the FAST pre-test assume eight waves per tile");
     constexpr int NT = 64 * NW;
     const int b = blockIdx.y;
     const int tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x;
@@ -1672,18 +1606,14 @@ __global__ __launch_bounds__(64 * NW, 8) void orb_pyrblur_kernel(PyrBlurArgs a) 
     // the emitted pixels of this tile (cv::ORB keeps corners >= edgeThreshold from the level border), in image coordinates, inclusive
     const int ex_lo = max(ox, kEdge), ex_hi = min(ox + kBlurTileW, W - kEdge) - 1, ey_lo = max(oy, kEdge), ey_hi = min(oy + kBlurTileH, H - kEdge) - 1;
     const bool do_fast = a.corners != nullptr && ex_lo <= ex_hi && ey_lo <= ey_hi; // uniform
-    constexpr bool kMfmaBlur = NW == 8 && VSLAM_ORB_BLUR_MFMA && !(VSLAM_PYRBLUR_DBG & 1); // (the matrix-core blur stages its output in the score tile and zeroes it afterwards)
-    if (do_fast) {
-        if (!kMfmaBlur)
-            for (int i = threadIdx.x; i < kPfScBytes / 16; i += NT) reinterpret_cast<uint4*>(sc)[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (threadIdx.x == 0) { s_ocount = 0; s_dense = 0; s_ccount = 0; }
-    }
+    // (the score tile is zeroed by the blur, which stages its output there)
+    if (do_fast && threadIdx.x == 0) { s_ocount = 0; s_dense = 0; s_ccount = 0; }
     OPH_INIT();
     load_tile_b128<NT, kBlurRawChunks, kPfRawH, true>(raw, src, a.spitch, W, H, ox - 4, oy - 4);
     __syncthreads();
     OPH(32);
     // ---- (1) level l + 1
-    if (a.dst_base && !(VSLAM_PYRBLUR_DBG & 2)) {
+    if (a.dst_base) {
         const int dx_lo = a.tile_dx[tx], dx_hi = a.tile_dx[tx + 1], dy_lo = a.tile_dy[ty], dy_hi = a.tile_dy[ty + 1]; // uniform
         const int dx0 = (dx_lo & ~3) + 4 * lane; // this lane's aligned quad of output columns
         // [r6] a wave owns a CONTIGUOUS run of output rows: consecutive output rows mostly share a source row (scale 1.2: the lower source row of
@@ -1748,161 +1678,78 @@ __global__ __launch_bounds__(64 * NW, 8) void orb_pyrblur_kernel(PyrBlurArgs a) 
         }
     }
     OPH(33);
-    // ---- (2) blurred level l (see orb_blur_kernel).  NW = 4: a wave owns 16 rows x 256 columns, a lane four pixels.  NW = 8: a wave owns
-    // 16 rows x 128 columns, a lane two pixels (the row pass of the 6 halo rows is repeated per row band, so halving the bands' height would cost more)
-    if (!(VSLAM_PYRBLUR_DBG & 1)) {
+    // ---- (2) blurred level l on the matrix cores (see the comment above g_blur_mfma_lane): a wave owns a strip of 32 tile columns, all rows
+    {
         uint8_t* dstb = a.blur_base + (size_t)b * a.blur_img_stride;
-        constexpr uint32_t W0 = 18u | 34u << 8 | 49u << 16 | 55u << 24, W1 = 49u | 34u << 8 | 18u << 16;
-        constexpr uint32_t V0 = 18u | 34u << 16, V1 = 49u | 55u << 16, V2 = 49u | 34u << 16, V3 = 18u << 16;
         const us2_t lim = {255, 255};
-        if constexpr (NW == 4) {
-            const int row0 = wave * kBlurWaveRows;
-            const int nrows = min(kBlurWaveRows, H - (oy + row0)); // wave-uniform
-            const int x = ox + 4 * lane;
-            if (nrows > 0) {
-                const uint32_t* rp = reinterpret_cast<const uint32_t*>(raw + (row0 + 1) * kBlurRawPitch) + lane; // tile row r reads raw rows r + 1 .. r + 7
-                uint8_t* out = dstb + (size_t)(oy + row0) * a.bpitch + x;
-                uint32_t P[kBlurWaveRows + 6][4], hprev[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (int t = 0; t < kBlurWaveRows + 6; ++t) {
-                    if (t - 6 >= nrows) break; // uniform
-                    const uint32_t A = rp[t * (kBlurRawPitch / 4)], Bw = rp[t * (kBlurRawPitch / 4) + 1], C = rp[t * (kBlurRawPitch / 4) + 2];
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) {
-                        const uint32_t lo = o == 3 ? Bw : __builtin_amdgcn_alignbyte(Bw, A, o + 1), hi = o == 3 ? C : __builtin_amdgcn_alignbyte(C, Bw, o + 1);
-                        const uint32_t h = __builtin_amdgcn_udot4(hi, W1, __builtin_amdgcn_udot4(lo, W0, 0u, false), false);
-                        P[t][o] = hprev[o] | h << 16;
-                        hprev[o] = h;
-                    }
-                    if (t >= 6) {
-                        uint32_t sum[4];
-#pragma unroll
-                        for (int o = 0; o < 4; ++o)
-                            sum[o] = udot2(P[t][o], V3, udot2(P[t - 1][o], V2, udot2(P[t - 3][o], V1, udot2(P[t - 5][o], V0, 1u << 15))));
-                        const us2_t p01 = __builtin_elementwise_min(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(sum[1], sum[0], 0x07060302u)), lim);
-                        const us2_t p23 = __builtin_elementwise_min(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(sum[3], sum[2], 0x07060302u)), lim);
-                        const uint32_t px = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, p23), __builtin_bit_cast(uint32_t, p01), 0x06040200u);
-#if VSLAM_ORB_BLUR_NT
-                        if (x < W) __builtin_nontemporal_store(px, reinterpret_cast<uint32_t*>(out + (size_t)(t - 6) * a.bpitch)); // read again only by the descriptor kernel, five kernels later
-#else
-                        if (x < W) *reinterpret_cast<uint32_t*>(out + (size_t)(t - 6) * a.bpitch) = px;
-#endif
-                    }
-                }
-            }
-        } else if constexpr (!kMfmaBlur) {
-            const int band = wave >> 1, half = wave & 1;
-            const int row0 = band * kBlurWaveRows;
-            const int nrows = min(kBlurWaveRows, H - (oy + row0)); // wave-uniform
-            const int xt = 128 * half + 2 * lane;                  // tile column of this lane's first pixel
-            const int x = ox + xt;
-            if (nrows > 0) {
-                // taps of pixel xt: raw columns xt + 1 .. xt + 7 (raw column = tile column + 4); of pixel xt + 1: xt + 2 .. xt + 8.  Three aligned dwords from
-                // raw column xt & ~3 on hold them; sh = (xt & 3) + 1 = 1 | 3 bytes bring the window's first byte to the front
-                const uint32_t* rp = reinterpret_cast<const uint32_t*>(raw + (row0 + 1) * kBlurRawPitch) + (xt >> 2);
-                const uint32_t sh = (uint32_t)(xt & 3) + 1u;
-                uint8_t* out = dstb + (size_t)(oy + row0) * a.bpitch + x;
-                uint32_t P[kBlurWaveRows + 6][2], hprev[2] = {0, 0};
-#pragma unroll
-                for (int t = 0; t < kBlurWaveRows + 6; ++t) {
-                    if (t - 6 >= nrows) break; // uniform
-                    const uint32_t A = rp[t * (kBlurRawPitch / 4)], Bw = rp[t * (kBlurRawPitch / 4) + 1], C = rp[t * (kBlurRawPitch / 4) + 2];
-                    const uint32_t wl = __builtin_amdgcn_alignbyte(Bw, A, sh), wh = __builtin_amdgcn_alignbyte(C, Bw, sh); // window bytes 0 .. 7
-                    const uint32_t lo1 = __builtin_amdgcn_alignbyte(wh, wl, 1u), hi1 = wh >> 8;
-                    const uint32_t hA = __builtin_amdgcn_udot4(wh, W1, __builtin_amdgcn_udot4(wl, W0, 0u, false), false); // (W1's top byte is 0: window byte 7 does not count)
-                    const uint32_t hB = __builtin_amdgcn_udot4(hi1, W1, __builtin_amdgcn_udot4(lo1, W0, 0u, false), false);
-                    P[t][0] = hprev[0] | hA << 16; hprev[0] = hA;
-                    P[t][1] = hprev[1] | hB << 16; hprev[1] = hB;
-                    if (t >= 6) {
-                        uint32_t sum[2];
-#pragma unroll
-                        for (int o = 0; o < 2; ++o)
-                            sum[o] = udot2(P[t][o], V3, udot2(P[t - 1][o], V2, udot2(P[t - 3][o], V1, udot2(P[t - 5][o], V0, 1u << 15))));
-                        const us2_t p01 = __builtin_elementwise_min(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(sum[1], sum[0], 0x07060302u)), lim);
-                        const uint16_t px = (uint16_t)__builtin_amdgcn_perm(0u, __builtin_bit_cast(uint32_t, p01), 0x0c0c0200u);
-#if VSLAM_ORB_BLUR_NT
-                        if (x < W) __builtin_nontemporal_store(px, reinterpret_cast<uint16_t*>(out + (size_t)(t - 6) * a.bpitch));
-#else
-                        if (x < W) *reinterpret_cast<uint16_t*>(out + (size_t)(t - 6) * a.bpitch) = px;
-#endif
-                    }
-                }
-            }
-        } else {
-            // matrix-core form (see the comment above g_blur_mfma_lane)
-            const int g = lane >> 4, j = lane & 15;
-            const uint2 bh2 = *reinterpret_cast<const uint2*>(g_blur_mfma_lane.bh[lane]);
-            const long Bh = (long)(((unsigned long long)bh2.y << 32) | bh2.x);
-            const long Bv = (long)(((unsigned long long)g_blur_mfma_lane.g1[lane] << 32) | g_blur_mfma_lane.g0[lane]);
-            constexpr int kInit = 257 * (128 + 32768) + 32768; // the offsets of both byte planes (low byte - 128, h' = h - 32768) + the rounding constant
-            const bl_v4i zero4 = {0, 0, 0, 0}, init4 = {kInit, kInit, kInit, kInit};
-            uint8_t* stage = sc; // 64 rows x 272 bytes (kBlurRawPitch)
-            static_assert(kBlurTileH * kBlurRawPitch <= kPfScBytes, "the blurred tile is staged in the score tile's storage");
-            const int rows_left = H - oy; // (uniform) output rows of this tile inside the image
-            if (ox + 32 * wave < W) {     // (uniform) a strip entirely beyond the image computes nothing; its staging chunks are never stored
+        const int g = lane >> 4, j = lane & 15;
+        const uint2 bh2 = *reinterpret_cast<const uint2*>(g_blur_mfma_lane.bh[lane]);
+        const long Bh = (long)(((unsigned long long)bh2.y << 32) | bh2.x);
+        const long Bv = (long)(((unsigned long long)g_blur_mfma_lane.g1[lane] << 32) | g_blur_mfma_lane.g0[lane]);
+        constexpr int kInit = 257 * (128 + 32768) + 32768; // the offsets of both byte planes (low byte - 128, h' = h - 32768) + the rounding constant
+        const bl_v4i zero4 = {0, 0, 0, 0}, init4 = {kInit, kInit, kInit, kInit};
+        uint8_t* stage = sc; // 64 rows x 272 bytes (kBlurRawPitch)
+        static_assert(kBlurTileH * kBlurRawPitch <= kPfScBytes, "the blurred tile is staged in the score tile's storage");
+        const int rows_left = H - oy; // (uniform) output rows of this tile inside the image
+        if (ox + 32 * wave < W) {     // (uniform) a strip entirely beyond the image computes nothing; its staging chunks are never stored
 #pragma unroll 1
-                for (int ct = 0; ct < 2; ++ct) {
-                    const int c0 = 32 * wave + 16 * ct; // first tile column of this 16-column tile = raw column of the window's first byte
-                    if (ox + c0 >= W) break;            // (uniform)
-                    // ---- row pass + byte planes: pl[t] = {low plane of row tile t, high plane}
-                    uint32_t plo[5], phi[5];
+            for (int ct = 0; ct < 2; ++ct) {
+                const int c0 = 32 * wave + 16 * ct; // first tile column of this 16-column tile = raw column of the window's first byte
+                if (ox + c0 >= W) break;            // (uniform)
+                // ---- row pass + byte planes: pl[t] = {low plane of row tile t, high plane}
+                uint32_t plo[5], phi[5];
 #pragma unroll
-                    for (int rt = 0; rt < 5; ++rt) {
-                        unsigned long long araw = 0x0101010101010101ull; // (k-group 3: the centring constant)
-                        if (g < 3) araw = *reinterpret_cast<const unsigned long long*>(raw + (16 * rt + j) * kBlurRawPitch + c0 + 8 * g) ^ 0x8080808080808080ull;
-                        const bl_v4i d = __builtin_amdgcn_mfma_i32_16x16x32_i8((long)araw, Bh, zero4, 0, 0, 0);
-                        const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)d[1], (uint32_t)d[0], 0x05010400u); // lo0 lo1 hi0 hi1
-                        const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)d[3], (uint32_t)d[2], 0x05010400u);
-                        plo[rt] = __builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u;
-                        phi[rt] = __builtin_amdgcn_perm(p23, p01, 0x07060302u);
-                    }
-                    // ---- column pass, output row tile T: k-slots = row tiles T and T + 1
+                for (int rt = 0; rt < 5; ++rt) {
+                    unsigned long long araw = 0x0101010101010101ull; // (k-group 3: the centring constant)
+                    if (g < 3) araw = *reinterpret_cast<const unsigned long long*>(raw + (16 * rt + j) * kBlurRawPitch + c0 + 8 * g) ^ 0x8080808080808080ull;
+                    const bl_v4i d = __builtin_amdgcn_mfma_i32_16x16x32_i8((long)araw, Bh, zero4, 0, 0, 0);
+                    const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)d[1], (uint32_t)d[0], 0x05010400u); // lo0 lo1 hi0 hi1
+                    const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)d[3], (uint32_t)d[2], 0x05010400u);
+                    plo[rt] = __builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u;
+                    phi[rt] = __builtin_amdgcn_perm(p23, p01, 0x07060302u);
+                }
+                // ---- column pass, output row tile T: k-slots = row tiles T and T + 1
 #pragma unroll
-                    for (int T = 0; T < 4; ++T) {
-                        if (16 * T >= rows_left) break; // (uniform)
-                        const long alo = (long)(((unsigned long long)plo[T + 1] << 32) | plo[T]), ahi = (long)(((unsigned long long)phi[T + 1] << 32) | phi[T]);
-                        const bl_v4i v = __builtin_amdgcn_mfma_i32_16x16x32_i8(alo, Bv, init4, 0, 0, 0); // (the constant rides in as the accumulator's initial value)
-                        const bl_v4i w = __builtin_amdgcn_mfma_i32_16x16x32_i8(ahi, Bv, zero4, 0, 0, 0);
-                        uint32_t o[4];
+                for (int T = 0; T < 4; ++T) {
+                    if (16 * T >= rows_left) break; // (uniform)
+                    const long alo = (long)(((unsigned long long)plo[T + 1] << 32) | plo[T]), ahi = (long)(((unsigned long long)phi[T + 1] << 32) | phi[T]);
+                    const bl_v4i v = __builtin_amdgcn_mfma_i32_16x16x32_i8(alo, Bv, init4, 0, 0, 0); // (the constant rides in as the accumulator's initial value)
+                    const bl_v4i w = __builtin_amdgcn_mfma_i32_16x16x32_i8(ahi, Bv, zero4, 0, 0, 0);
+                    uint32_t o[4];
 #pragma unroll
-                        for (int u = 0; u < 4; ++u) o[u] = ((uint32_t)w[u] << 8) + (uint32_t)v[u];
-                        const us2_t p01 = __builtin_elementwise_min(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(o[1], o[0], 0x07060302u)), lim);
-                        const us2_t p23 = __builtin_elementwise_min(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(o[3], o[2], 0x07060302u)), lim);
-                        const uint32_t px = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, p23), __builtin_bit_cast(uint32_t, p01), 0x06040200u);
-                        // lane (n = j, g): output row 16 T + n, columns c0 + 4 g .. + 3
-                        *reinterpret_cast<uint32_t*>(stage + (16 * T + j) * kBlurRawPitch + c0 + 4 * g) = px;
-                    }
+                    for (int u = 0; u < 4; ++u) o[u] = ((uint32_t)w[u] << 8) + (uint32_t)v[u];
+                    const us2_t p01 = __builtin_elementwise_min(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(o[1], o[0], 0x07060302u)), lim);
+                    const us2_t p23 = __builtin_elementwise_min(__builtin_bit_cast(us2_t, __builtin_amdgcn_perm(o[3], o[2], 0x07060302u)), lim);
+                    const uint32_t px = __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, p23), __builtin_bit_cast(uint32_t, p01), 0x06040200u);
+                    // lane (n = j, g): output row 16 T + n, columns c0 + 4 g .. + 3
+                    *reinterpret_cast<uint32_t*>(stage + (16 * T + j) * kBlurRawPitch + c0 + 4 * g) = px;
                 }
             }
-            __syncthreads();
-            // ---- rows of 256 contiguous bytes out of the staged tile; the lane that read a chunk zeroes it (the FAST phase needs a zeroed score tile)
-            const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-            for (int i = 0; i < (kBlurTileH * 16) / NT; ++i) {
-                const int chunk = threadIdx.x + i * NT, r = chunk >> 4, cc = chunk & 15;
-                uint4* sp = reinterpret_cast<uint4*>(stage + r * kBlurRawPitch + 16 * cc);
-                const uint4 px = *sp;
-                *sp = z4;
-                const int x = ox + 16 * cc;
-                if (r < rows_left && x < W) { // (a chunk that starts inside the row ends inside its pitch: the pitch is a multiple of 64)
-                    bl_v4i* q = reinterpret_cast<bl_v4i*>(dstb + (size_t)(oy + r) * a.bpitch + x);
-                    const bl_v4i pv = {(int)px.x, (int)px.y, (int)px.z, (int)px.w};
-#if VSLAM_ORB_BLUR_NT
-                    __builtin_nontemporal_store(pv, q);
-#else
-                    *q = pv;
-#endif
-                }
-            }
-            // the bytes of the score tile no staging chunk covers: the 16 padding bytes of each staged row and the tail
-            if (threadIdx.x < kBlurTileH) *reinterpret_cast<uint4*>(stage + threadIdx.x * kBlurRawPitch + 256) = z4;
-            for (int t = kBlurTileH * kBlurRawPitch + 16 * threadIdx.x; t < kPfScBytes; t += 16 * NT) *reinterpret_cast<uint4*>(sc + t) = z4;
-            __syncthreads();
         }
+        __syncthreads();
+        // ---- rows of 256 contiguous bytes out of the staged tile; the lane that read a chunk zeroes it (the FAST phase needs a zeroed score tile)
+        const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (int i = 0; i < (kBlurTileH * 16) / NT; ++i) {
+            const int chunk = threadIdx.x + i * NT, r = chunk >> 4, cc = chunk & 15;
+            uint4* sp = reinterpret_cast<uint4*>(stage + r * kBlurRawPitch + 16 * cc);
+            const uint4 px = *sp;
+            *sp = z4;
+            const int x = ox + 16 * cc;
+            if (r < rows_left && x < W) { // (a chunk that starts inside the row ends inside its pitch: the pitch is a multiple of 64)
+                bl_v4i* q = reinterpret_cast<bl_v4i*>(dstb + (size_t)(oy + r) * a.bpitch + x);
+                const bl_v4i pv = {(int)px.x, (int)px.y, (int)px.z, (int)px.w};
+                __builtin_nontemporal_store(pv, q);
+            }
+        }
+        // the bytes of the score tile no staging chunk covers: the 16 padding bytes of each staged row and the tail
+        if (threadIdx.x < kBlurTileH) *reinterpret_cast<uint4*>(stage + threadIdx.x * kBlurRawPitch + 256) = z4;
+        for (int t = kBlurTileH * kBlurRawPitch + 16 * threadIdx.x; t < kPfScBytes; t += 16 * NT) *reinterpret_cast<uint4*>(sc + t) = z4;
+        __syncthreads();
     }
     OPH(34);
     // ---- (3) FAST-9/16 of level l
-    if (!do_fast || (VSLAM_PYRBLUR_DBG & 4)) return; // uniform
+    if (!do_fast) return; // uniform
     const int thr = a.thr;
     // score region = emitted pixels dilated by one, in TILE coordinates (column -1 .. 256, row -1 .. kBlurTileH), inclusive
     const int vx_lo = ex_lo - 1 - ox, vx_hi = ex_hi + 1 - ox, vy_lo = ey_lo - 1 - oy, vy_hi = ey_hi + 1 - oy;
@@ -1911,7 +1758,6 @@ __global__ __launch_bounds__(64 * NW, 8) void orb_pyrblur_kernel(PyrBlurArgs a) 
     // position id = raw row << 9 | raw column
     auto score_batch = [&](int first, int cnt) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // the queue entries were written by other lanes of this wave
-        if (VSLAM_PYRBLUR_DBG & 8) { if (lane < cnt && wq[first + lane] == 0xFFFF) sc[lane] = 1; return; } // (timing aid: pre-test only)
         bool corner = false; int id = 0;
         if (lane < cnt) {
             id = wq[first + lane];
@@ -1958,7 +1804,7 @@ __global__ __launch_bounds__(64 * NW, 8) void orb_pyrblur_kernel(PyrBlurArgs a) 
     OPH(35);
     {
         constexpr int kRows = kBlurTileH / NW;                      // centre rows per wave (+ 2 for the last wave)
-        constexpr int kG = NW == 4 ? 6 : 4;                         // centre rows per group: their kG + 6 raw rows are widened once
+        constexpr int kG = 4;                                       // centre rows per group: their kG + 6 raw rows are widened once
         constexpr int kGroups = (kRows + 2 + kG - 1) / kG;
         static_assert(kRows * (NW - 1) + kGroups * kG + 6 <= kPfRawH + 8, "the pre-test reads a few rows past the staged tile (into the score tile), for centre rows it skips");
         const int cb0 = kRows * wave - 1;                                                  // first centre row (tile coordinates) of this wave
@@ -2108,10 +1954,7 @@ constexpr int kDescR = 19, kDescRows = 2 * kDescR + 1, kDescPitch = 40; // |patt
 // tests" is two memory round trips per keypoint, so it is software-pipelined: while the tests of keypoint j run out of LDS the patch
 // dwords of the next keypoint are already in flight to registers and the record of the one after that is being fetched; the
 // lane's four test pairs stay in registers for the whole walk.
-#ifndef VSLAM_DESC_BLOCKS
-#define VSLAM_DESC_BLOCKS 48
-#endif
-constexpr int kDescBlocksPerImage = VSLAM_DESC_BLOCKS; // x 4 waves = 192 waves per image: eight keypoints per wave at N = 1500 (32 / 48 / 64 / 96 / 144 blocks: 0.373 / 0.365 / 0.373 / 0.390 / 0.409 ms per 512 images)
+constexpr int kDescBlocksPerImage = 48; // x 4 waves = 192 waves per image: eight keypoints per wave at N = 1500 (32 / 48 / 64 / 96 / 144 blocks: 0.373 / 0.365 / 0.373 / 0.390 / 0.409 ms per 512 images)
 constexpr int kDescPatchIters = (kDescRows * (kDescPitch / 4) + 63) / 64;
 __global__ __launch_bounds__(kDescWaves * 64) void orb_describe_kernel(BlurTable T, LevelTable LT, const uint8_t* __restrict__ d_imgs,
                                                                       size_t img_bytes, int pitch0, const uint8_t* __restrict__ d_pyr,

@@ -582,7 +582,7 @@ __global__ __launch_bounds__(128) void pnp_ransac_select_kernel(const float* __r
                                                                double cy, float thr2, double* __restrict__ T_out, uint8_t* __restrict__ inlier,
                                                                int32_t* __restrict__ n_inl, int32_t* __restrict__ iters_run) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    __shared__ int s_best, s_good;
+    __shared__ int s_best;
     __shared__ double sR[12];
     const int n = min(max(d_n[b], 0), capacity), nh = nh_of[b];
     if (tid == 0) {
@@ -598,7 +598,7 @@ __global__ __launch_bounds__(128) void pnp_ransac_select_kernel(const float* __r
                 }
             }
         }
-        s_best = best; s_good = max_good;
+        s_best = best;
         if (iters_run) iters_run[b] = it;
         if (n_inl) n_inl[b] = best >= 0 ? max_good : 0;
     }

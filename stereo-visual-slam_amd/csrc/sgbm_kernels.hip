@@ -30,7 +30,6 @@ struct SgbmDims {
     size_t img_bytes;
 };
 
-constexpr int kSgbmMaxCost = 32767;
 constexpr int kTOffset = 8192; // L1+L2+L3 lies in [-7776, 46k]: stored as u16 with this offset
 
 __device__ inline int sat16_dev(int v) { return min(max(v, -32768), 32767); }
@@ -212,18 +211,10 @@ __device__ inline void wta_row16(const SgbmDims& dm, int s0, int s1, int s2, int
     }
 }
 
-#ifndef VSLAM_SGBM_PATH_BLOCK
-#define VSLAM_SGBM_PATH_BLOCK 64
-#endif
-constexpr int kPathBlock = VSLAM_SGBM_PATH_BLOCK, kPathLines = kPathBlock / 16; // lines per workgroup (adjacent lines: one contiguous run of the volume per step)
+constexpr int kPathBlock = 64, kPathLines = kPathBlock / 16; // lines per workgroup (adjacent lines: one contiguous run of the volume per step)
 // Non-temporal loads / stores on the streamed volumes (every byte is touched once per kernel): the two diagonal paths gain 7-12 %
-// (1.90 -> 1.67, 1.74 -> 1.61 ms per 32 pairs), the two horizontal ones lose 3 % -- so NT is a property of the direction.
-#ifndef VSLAM_SGBM_LAST_NT
-#define VSLAM_SGBM_LAST_NT 0
-#endif
-#ifndef VSLAM_SGBM_H_NTST
-#define VSLAM_SGBM_H_NTST 1 // non-temporal STORES (not loads) on the horizontal paths: 1.69 -> 1.65 ms for the left-to-right path
-#endif
+// (1.90 -> 1.67, 1.74 -> 1.61 ms per 32 pairs), the two horizontal ones lose 3 % -- so NT loads are a property of the direction.  NT STORES
+// alone pay on the horizontal paths too (1.69 -> 1.65 ms for the left-to-right path): every path stores non-temporally.
 template <bool NT>
 __device__ inline U3 ld_u3(const void* p) {
     if constexpr (NT) {
@@ -231,18 +222,14 @@ __device__ inline U3 ld_u3(const void* p) {
         return U3{__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1), __builtin_nontemporal_load(q + 2)}; // merged into one dwordx3 nt
     } else return *reinterpret_cast<const U3*>(p);
 }
-template <bool NT>
-__device__ inline void st_u3(void* p, U3 v) {
-    if constexpr (NT) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(p);
-        __builtin_nontemporal_store(v.a, q); __builtin_nontemporal_store(v.b, q + 1); __builtin_nontemporal_store(v.c, q + 2);
-    } else *reinterpret_cast<U3*>(p) = v;
+__device__ inline void st_u3_nt(void* p, U3 v) {
+    uint32_t* q = reinterpret_cast<uint32_t*>(p);
+    __builtin_nontemporal_store(v.a, q); __builtin_nontemporal_store(v.b, q + 1); __builtin_nontemporal_store(v.c, q + 2);
 }
 template <int DX, int DY, int MODE, int kPathPF>
 __global__ __launch_bounds__(kPathBlock) void sgbm_path_kernel(SgbmDims dm, const int16_t* __restrict__ C, uint16_t* T, int nlines, int4* __restrict__ rec) {
     const int b = blockIdx.y;
-    constexpr bool kNT = (DX != 0 && DY != 0) || (MODE == 4 && VSLAM_SGBM_LAST_NT != 0); // loads (and stores) of the diagonal paths; tuning macro for the last path
-    constexpr bool kNTst = kNT || (VSLAM_SGBM_H_NTST != 0); // stores of the horizontal paths (tuning macro)
+    constexpr bool kNT = DX != 0 && DY != 0; // loads of the diagonal paths
     const int line = blockIdx.x * kPathLines + (threadIdx.x >> 4), r = threadIdx.x & 15;
     if (line >= nlines) return; // whole DPP row leaves
     const int W1 = dm.width1, h = dm.h;
@@ -306,7 +293,7 @@ __global__ __launch_bounds__(kPathBlock) void sgbm_path_kernel(SgbmDims dm, cons
                     else // last path: S is complete -- pick the winner here instead of storing it
                         wta_row16(dm, f0, f1, f2, f3, f4, f5, r, ((size_t)b * h + y0) * dm.w + dm.minX1 + x0 + (s + k) * DX, rec, s + k < len);
                 }
-                if (MODE != 4 && s + k < len) st_u3<kNTst>(tp + (ptrdiff_t)(s + k) * step, o);
+                if (MODE != 4 && s + k < len) st_u3_nt(tp + (ptrdiff_t)(s + k) * step, o);
             }
         }
     }
@@ -330,13 +317,7 @@ __global__ __launch_bounds__(kPathBlock) void sgbm_path_kernel(SgbmDims dm, cons
 // blockIdx: HIP does not promise dispatch order), so every lower ticket belongs to a workgroup that is resident or finished -- the lowest
 // unfinished one never waits: no co-residency requirement, no deadlock, whatever shares the device.  A spin limit remains as a backstop
 // against a wedged predecessor: it sets the launch's error word (the API reports VSLAM_ERR_HIP), releases the successors and returns.
-#ifndef VSLAM_SGBM_FW_CHUNK
-#define VSLAM_SGBM_FW_CHUNK 32
-#endif
-#ifndef VSLAM_SGBM_FW_PF
-#define VSLAM_SGBM_FW_PF 4
-#endif
-constexpr int kFwChunk = VSLAM_SGBM_FW_CHUNK, kFwPF = VSLAM_SGBM_FW_PF;
+constexpr int kFwChunk = 32, kFwPF = 4;
 constexpr int kFwRecDw = 16 * 9;                       // boundary record of one pixel: 16 lanes x 3 paths x 3 dwords
 template <int kFwRows>
 struct FwShared {
@@ -344,12 +325,7 @@ struct FwShared {
     uint32_t bnd[2][kFwChunk * kFwRecDw];
     int ctl[2]; // [0] this workgroup's ticket (logical index), [1] abort flag of the spin-limit backstop
 };
-#ifndef VSLAM_SGBM_FW_ACQ
-#define VSLAM_SGBM_FW_ACQ 2
-#endif
-#ifndef VSLAM_SGBM_FW_SPIN_LIMIT
-#define VSLAM_SGBM_FW_SPIN_LIMIT (1 << 26) // polls of ~0.5 us: ~30 s
-#endif
+constexpr int kSgbmFwSpinLimit = 1 << 26; // polls of ~0.5 us: ~30 s
 // The recurrence in packed 16-bit arithmetic (two disparities per register: L in [-P2, Cmax], delta <= Cmax + P2, kSent + P1 < 2^15 --
 // nothing leaves int16).  The vectors arrive packed from the volume and from the row above and leave packed: no unpacking at all.
 struct FwVec { short2v p[3]; }; // disparities (6r, 6r+1), (6r+2, 6r+3), (6r+4, 6r+5)
@@ -398,9 +374,6 @@ __global__ __launch_bounds__(kFwRows * 16) void sgbm_forward_kernel(SgbmDims dm,
     // chained slabs on unrelated XCDs: 2.9 -> 4.3 ms per 32 pairs).  The XCC id only picks the pool tried first -- speed, not correctness:
     // a workgroup whose pool is exhausted takes an index from the next one (there are exactly as many indices as workgroups).
     const int nb = gridDim.x / nslab;
-#if defined(VSLAM_SGBM_FW_NO_TICKET) // A/B aid only: logical index = blockIdx (relies on in-order dispatch)
-    if (tid == 0) { sm.ctl[0] = (int)blockIdx.x; sm.ctl[1] = 0; }
-#else
     if (tid == 0) {
         const int npool = (nb % 8 == 0) ? 8 : 1, ntot = gridDim.x;
         const int xcc = (int)(__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u) % npool; // HW_REG_XCC_ID[3:0]
@@ -420,18 +393,14 @@ __global__ __launch_bounds__(kFwRows * 16) void sgbm_forward_kernel(SgbmDims dm,
             if (cand < ntot) { got = cand; break; }
         }
         sm.ctl[0] = got; sm.ctl[1] = 0;
-#ifdef VSLAM_SGBM_FW_DEBUG
-        printf("fw blk %d xcc %d lid %d t %lld\n", (int)blockIdx.x, xcc, got, (long long)wall_clock64());
-#endif
     }
-#endif
     __syncthreads();
     const int lid = sm.ctl[0];
     const int slab = lid / nb, b = lid - slab * nb;
     const int W1 = dm.width1, h = dm.h;
     const int y = slab * kFwRows + row_l;
     const bool rowok = y < h;
-    const int P1 = dm.P1, P2 = dm.P2;
+    const int P2 = dm.P2;
     const size_t rowbase = (((size_t)b * h + min(y, h - 1)) * W1) * 96 + 6 * r;
     const int16_t* cp = C + rowbase;
     int16_t* sp = S1 + rowbase;
@@ -453,16 +422,11 @@ __global__ __launch_bounds__(kFwRows * 16) void sgbm_forward_kernel(SgbmDims dm,
             int spins = 0;
             while (__hip_atomic_load(flag_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
                 __builtin_amdgcn_s_sleep(16);
-                if (++spins > VSLAM_SGBM_FW_SPIN_LIMIT) { sm.ctl[1] = 1; break; }
+                if (++spins > kSgbmFwSpinLimit) { sm.ctl[1] = 1; break; }
             }
         }
-#if VSLAM_SGBM_FW_ACQ == 2
         if (has_pred && tid < 64) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); // polling wave only: the L1 it invalidates is the CU's
-#endif
         __syncthreads();
-#if VSLAM_SGBM_FW_ACQ == 1
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); // the records published before the flag are visible to the loads below
-#endif
         return sm.ctl[1] == 0;
     };
     auto fw_abort = [&]() { // error word for the host, successors released (their results are void with the word set)
@@ -541,7 +505,7 @@ __global__ __launch_bounds__(kFwRows * 16) void sgbm_forward_kernel(SgbmDims dm,
                     s3.a = fw_u(__builtin_elementwise_add_sat(n10.p[0] + nm.p[0], n01.p[0] + n11.p[0]));
                     s3.b = fw_u(__builtin_elementwise_add_sat(n10.p[1] + nm.p[1], n01.p[1] + n11.p[1]));
                     s3.c = fw_u(__builtin_elementwise_add_sat(n10.p[2] + nm.p[2], n01.p[2] + n11.p[2]));
-                    st_u3<true>(sp + (size_t)x * 96, s3);
+                    st_u3_nt(sp + (size_t)x * 96, s3);
                     if (writer) {
                         uint32_t* wp = bnd_out + (x > 0 ? (size_t)(x - 1) * kFwRecDw : bnd_rec0);
 #pragma unroll
@@ -574,19 +538,8 @@ __global__ __launch_bounds__(kFwRows * 16) void sgbm_forward_kernel(SgbmDims dm,
 // border rules, see sgbm_vsum_kernel); (3) C is stored for the other four paths and consumed on the spot by the vertical path's
 // recurrence, whose L goes out as T.  hsum never exists in memory and C is not re-read: 2 volume writes instead of
 // 1 write (hsum) + 2 reads + 1 write (vsum) + 1 read + 1 write (path 0,1).
-#ifndef VSLAM_SGBM_DN_NT
-#define VSLAM_SGBM_DN_NT 1 // non-temporal stores of C / T in the fused top-down kernel: 2.69 -> 2.38 ms per 32 pairs (the 165 MB per pair it writes are next read a kernel later)
-#endif
-#ifndef VSLAM_SGBM_DN_COLS
-#define VSLAM_SGBM_DN_COLS 24
-#endif
-#ifdef VSLAM_SGBM_PROFILE // tuning aid (tools/build_variant.sh ... -DVSLAM_SGBM_PROFILE): cycles per phase of one workgroup's wave 0
-__device__ long long g_sgbm_dbg[8];
-#define DN_T(slot) do { if (dbg__) { const long long t1__ = clock64(); acc__[slot] += t1__ - t0__; t0__ = t1__; } } while (0)
-#else
-#define DN_T(slot) do {} while (0)
-#endif
-constexpr int kDnCols = VSLAM_SGBM_DN_COLS, kDnThreads = (kDnCols + 8) * 16; // one pixel-cost item per (tile column, 16-lane slot)
+// C / T are stored non-temporally: 2.69 -> 2.38 ms per 32 pairs (the 165 MB per pair it writes are next read a kernel later).
+constexpr int kDnCols = 24, kDnThreads = (kDnCols + 8) * 16; // one pixel-cost item per (tile column, 16-lane slot)
 static_assert(kDnCols % 4 == 0 && 6 * 4 * ((kDnCols + 8 + 97 + 3) / 4 + 1) <= 2 * kDnThreads, "the strip loader issues at most two dword loads per thread");
 constexpr int kStripDw = (kDnCols + 8 + 97 + 3) / 4 + 1;  // dwords per (plane, byte shift) copy of the right-view strip: window starts 0 .. kDnCols + 97, 8 bytes each
 struct DnStage { uint32_t a, b; uint8_t l; };             // one row's share of the operand strips on its way from memory to LDS (raw loads: nothing is
@@ -601,7 +554,7 @@ __global__ __launch_bounds__(kDnThreads) void sgbm_down_kernel(SgbmDims dm, cons
     constexpr int kTilePitch = kDnCols + 8 + 8;
     __shared__ alignas(16) uint8_t tile[2][96 * kTilePitch];
     const int t = threadIdx.x >> 4, r = threadIdx.x & 15, d = 6 * r;
-    const int jj = min(max(j0 - 4 + t, 0), W1 - 1), x = dm.minX1 + jj; // pixel-cost column of this item (clamped to the volume)
+    const int jj = min(max(j0 - 4 + t, 0), W1 - 1); // pixel-cost column of this item (clamped to the volume)
     const uint8_t* Lb = pre + ((size_t)(2 * b) * h * 6) * w;
     const uint8_t* Rb = pre + ((size_t)(2 * b + 1) * h * 6) * w;
     // Operands through LDS.  A workgroup row needs 32 left pixels and a 130-byte strip of the right view per plane; fetched per lane (six byte
@@ -658,14 +611,9 @@ __global__ __launch_bounds__(kDnThreads) void sgbm_down_kernel(SgbmDims dm, cons
     stage(0, in[0]);
     fetch(min(1, h - 1), in[0]);
     __syncthreads();
-#ifdef VSLAM_SGBM_PROFILE
-    const bool dbg__ = blockIdx.x == 7 && blockIdx.y == 0 && threadIdx.x == 0;
-    long long acc__[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0__ = clock64();
-#endif
     for (int i0 = 0; i0 < h + dm.SH2; i0 += 18) {
 #pragma unroll
         for (int step = 0; step < 18; ++step) {
-            constexpr int kDummy = 0; (void)kDummy;
             const int sidx = step % 9;
             DnStage& cur = in[step & 1];       // row i + 1, fetched a step ago: goes to LDS now
             DnStage& nxt = in[(step + 1) & 1]; // row i + 2: requested now
@@ -709,9 +657,7 @@ __global__ __launch_bounds__(kDnThreads) void sgbm_down_kernel(SgbmDims dm, cons
                     tile[i & 1][(d + 2 * k + 1) * kTilePitch + t] = (uint8_t)cost[k].y;
                 }
             }
-            DN_T(0);
             __syncthreads();
-            DN_T(1);
             if (path_lane) {
                 if (i < h) {
                     // (2) hsum(i) of column j: nine tile columns t .. t + 8 (= volume columns j - 4 .. j + 4, clamped)
@@ -744,7 +690,6 @@ __global__ __launch_bounds__(kDnThreads) void sgbm_down_kernel(SgbmDims dm, cons
                         }
                     }
                 }
-                DN_T(2);
                 if (i >= dm.SH2) {
                     // (3) row y = i - SH2: C = acc (frozen over the last SH2 rows: no hsum arrives any more), vertical path, T
                     const int y = i - dm.SH2;
@@ -765,18 +710,14 @@ __global__ __launch_bounds__(kDnThreads) void sgbm_down_kernel(SgbmDims dm, cons
                     if (live) {
                         U3 o;
                         o.a = pack16(n0 + kTOffset, n1 + kTOffset); o.b = pack16(n2 + kTOffset, n3 + kTOffset); o.c = pack16(n4 + kTOffset, n5 + kTOffset);
-                        st_u3<VSLAM_SGBM_DN_NT != 0>(C + vbase + (size_t)y * rstride, c);
-                        st_u3<VSLAM_SGBM_DN_NT != 0>(T + vbase + (size_t)y * rstride, o);
+                        st_u3_nt(C + vbase + (size_t)y * rstride, c);
+                        st_u3_nt(T + vbase + (size_t)y * rstride, o);
                     }
-                    } else if (live) st_u3<VSLAM_SGBM_DN_NT != 0>(C + vbase + (size_t)y * rstride, c);
+                    } else if (live) st_u3_nt(C + vbase + (size_t)y * rstride, c);
                 }
-                DN_T(3);
             }
         }
     }
-#ifdef VSLAM_SGBM_PROFILE
-    if (dbg__) for (int q = 0; q < 4; ++q) g_sgbm_dbg[q] = acc__[q];
-#endif
 }
 
 // stand-alone winner-take-all over a stored S volume (MODE 3): one DPP row per pixel
@@ -976,7 +917,6 @@ int launch_sgbm(const Tuning& tune, const uint8_t* d_left, const uint8_t* d_righ
     uint8_t* pre = base + o_pre; int16_t* hsum = (int16_t*)(base + o_hs); int16_t* C = (int16_t*)(base + o_C);
     uint16_t* T = (uint16_t*)(base + o_T); int4* rec = (int4*)(base + o_rec);
     int16_t* d0 = (int16_t*)(base + o_d0); int16_t* d1 = (int16_t*)(base + o_d1); int* par = (int*)(base + o_par); int* cnt = (int*)(base + o_cnt);
-    const int vblocks = (dm.width1 * dm.D + 255) / 256;
     { ProfScope p(stream, "sgbm_prefilter_kernel"); hipLaunchKernelGGL(sgbm_prefilter_kernel, dim3((w + 255) / 256, h, 2 * B), dim3(256), 0, stream, dm, d_left, d_right, pre); }
     // The fused top-down kernel sweeps the rows sequentially with 48 workgroups per pair: it pays from 8 pairs per call on (2.65 vs 4.08 ms
     // at 32 pairs); below that the three massively parallel kernels it replaces are faster (0.99 vs 1.31 ms for one pair).
@@ -1017,10 +957,6 @@ int launch_sgbm(const Tuning& tune, const uint8_t* d_left, const uint8_t* d_righ
       hipLaunchKernelGGL(sgbm_ccl_count_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, maxDiff, newVal, d1, par, cnt);
       hipLaunchKernelGGL(sgbm_ccl_apply_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, newVal, maxSize, par, cnt, d1, d_disp_f32, d_disp_i16); }
     VS_HIP(hipGetLastError());
-#ifdef VSLAM_SGBM_PROFILE
-    { long long hdbg[8]; (void)hipStreamSynchronize(stream); (void)hipMemcpyFromSymbol(hdbg, HIP_SYMBOL(g_sgbm_dbg), sizeof(hdbg));
-      fprintf(stderr, "[sgbm_down profile] cycles of one wave over %d rows: pixel cost %lld, barrier %lld, hsum+ring %lld, path+stores %lld\n", h, hdbg[0], hdbg[1], hdbg[2], hdbg[3]); }
-#endif
     return VSLAM_OK;
 }
 

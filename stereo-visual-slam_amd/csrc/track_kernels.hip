@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void track_pose_chain_kernel(int B, const doub
 // whose query keypoint owns a valid depth (the compaction of build_pnp_inputs_kernel, geom_kernels.hip, repeated with the same ballot ranks):
 // such a candidate carries the pose stage's inlier flag (the reference erases the outliers of motion_estimation from the frame, :306).  A
 // candidate whose query keypoint has no depth of its own is decided by the walk below (track_rule 1) or never a link (track_rule 0).
-constexpr int kCandDepth = 1 << 20, kCandInlier = 1 << 21, kCandIndex = 0xFFFF; // cand word of slot t: q | flags (kp_capacity <= 65536), -1: no match reaches it
+constexpr int kCandDepth = 1 << 20, kCandInlier = 1 << 21; // cand word of slot t: q (low 16 bits) | flags (kp_capacity <= 65536), -1: no match reaches it
 __global__ __launch_bounds__(256) void track_link_kernel(TrackDims d, const vslam_dmatch* __restrict__ d_f2f, const int32_t* __restrict__ d_nf2f,
                                                         const uint8_t* __restrict__ d_valid, const uint8_t* __restrict__ d_inl,
                                                         const int32_t* __restrict__ kp2lr, int32_t* __restrict__ cand, int32_t* __restrict__ succ) {
