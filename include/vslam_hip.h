@@ -331,6 +331,27 @@ typedef struct vslam_tracks_in {
 int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int lm_capacity, int edge_capacity, vslam_ba_batch* out,
                             int32_t* d_status);
 
+/* vslam_build_windows_dev with a choice of WHICH keyframes each window holds (additive: the ABI version is unchanged).
+ * policy 0, sliding: S_b = [max(0, b - n_kf + 1), b]; the windows are vslam_build_windows_dev's bit for bit; evicted[b] = b - n_kf (-1 while < 0).
+ * policy 1, reference culling (Map::remove_keyframe, map.cpp:48-130): S_0 = {0}; for b >= 1, S' = S_{b-1} + {b}, and when |S'| > n_kf
+ *   d_k = |log(G_k o G_b^-1)|_2 for every k in S' \ {b}, G = the chained pose-stage poses the builder uses for the windows;
+ *   far  = the first k (ascending frames) with d_k > far_d, starting from far_d = 0 (the largest distance, lowest frame on a tie);
+ *   near = the first k (ascending frames) with d_k < near_d, starting from near_d = 1e6 (the smallest, lowest frame on a tie);
+ *   near is evicted if near_d < near_dist (the reference: 0.2), otherwise far.
+ *   Deviations from the reference: ties go to the lowest frame (the reference iterates an unordered_map); the distance is taken on the chained
+ *   pose-stage poses, not on BA-refined ones (windows are independent); if no member qualifies (e.g. every distance is non-finite) the oldest
+ *   member is evicted and bit 1 (value 2) of *d_status is set.  The keyframe gate of insert_key_frame (visual_odometry.cpp:353) is not applied:
+ *   every frame is still a keyframe.
+ * Window b holds the frames of S_b in ascending order in slots 0..|S_b|-1 (T_c_w slot k = G[S_b[k]], edges' kf_idx = slot); its landmarks are
+ * those with at least one observation in a frame of S_b (what clean_map keeps), with position and reliable_depth_ as of frame b (a reliable
+ * update in a culled frame counts), ordered as in vslam_build_windows_dev by observation count inside S_b, then by first observation inside S_b.
+ * d_kf_frame (n_frames x n_kf, device): S_b ascending, -1 in unused slots; d_evicted (n_frames, device): the frame evicted at step b, -1 if none.
+ * Status and capacity behaviour: vslam_build_windows_dev's (bit 0).  Refused with VSLAM_ERR_ARG: policy 1 on a chunk (d_T_abs, d_carry_in or
+ * d_carry_out set: which keyframes survive depends on the whole history), near_dist NaN or negative, a policy other than 0 / 1, n_kf outside
+ * 1..VSLAM_MAX_KF, NULL d_kf_frame / d_evicted. */
+int vslam_build_windows_kf_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int policy, double near_dist, int lm_capacity,
+                               int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status);
+
 /* per-window status of the most recent window launch on this process (VSLAM_OK or VSLAM_ERR_ARG per window) */
 int vslam_ba_status_dev(vslam_ctx* ctx, int n_windows, int32_t* h_status);
 /* optimize_map passes the most recent vslam_ba_batch_dev(schedule = 1) call EXECUTED per window: 3 = all of run_vslam.cpp:61-66; 1 or 2 = the

@@ -224,7 +224,8 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "sgbm_ccl_apply_kernel sgbm_ccl_kernels triangulate_kernel find3d_disparity_kernel gather_uv_kernel build_pnp_inputs_kernel lm_window_kernel pose_only_wave_kernel "
            "lm_window_kernel<pnp> pnp_wave_kernel pnp_inlier_kernel pnp_epnp_kernels epnp_front_kernel epnp_jacobi_kernel epnp_back_kernel pnp_count_inliers_kernel hbm_copy_probe_kernel "
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
-           "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel";
+           "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
+           "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -978,7 +979,8 @@ int vslam_ba_batch_dev(vslam_ctx* ctx, const vslam_ba_batch* b, int schedule, in
     return launch_lm_windows(a, schedule, mode, iters, update_poses, update_lms, &c->lm, c->stream);
 }
 
-int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_status) {
+static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_status,
+                         const KfPolicy& kp) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !in || !out || !d_status || in->n_frames <= 0 || n_kf <= 0 || n_kf > VSLAM_MAX_KF || lm_capacity <= 0 || edge_capacity <= 0 ||
         in->kp_capacity <= 0 || in->lr_capacity <= 0 || in->match_capacity <= 0 || in->pnp_capacity <= 0 || !in->d_kps || !in->d_lr || !in->d_nlr ||
@@ -991,7 +993,7 @@ int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf,
     }
     if (in->kp_capacity > 65536) { set_error("kp_capacity %d exceeds 65536 (the window builder packs a keypoint index into 16 bits)", in->kp_capacity); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    const size_t need = track_scratch_bytes(in->n_frames, in->kp_capacity, lm_capacity);
+    const size_t need = track_scratch_bytes(in->n_frames, in->kp_capacity, lm_capacity, kp.policy);
     if (c->track_bytes < need) {
         VS_HIP(hipStreamSynchronize(c->stream));
         if (c->d_track) { (void)hipFree(c->d_track); c->dev_bytes -= c->track_bytes; }
@@ -1005,7 +1007,25 @@ int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf,
     const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
     return launch_build_windows(*in, n_kf, lm_capacity, edge_capacity, K4, c->p.pnp_reproj_thr, track_rule, c->d_track, const_cast<int32_t*>(out->d_lm_off), const_cast<int32_t*>(out->d_edge_off),
                                 const_cast<int32_t*>(out->d_n_kf), out->d_T_c_w, out->d_xyz, const_cast<uint8_t*>(out->d_reliable), out->d_lm_inlier,
-                                const_cast<int32_t*>(out->d_kf_idx), const_cast<int32_t*>(out->d_lm_idx), const_cast<float*>(out->d_uv), d_status, c->stream);
+                                const_cast<int32_t*>(out->d_kf_idx), const_cast<int32_t*>(out->d_lm_idx), const_cast<float*>(out->d_uv), d_status, kp, c->stream);
+}
+
+int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_status) {
+    const KfPolicy kp = {-1, 0.0, nullptr, nullptr};
+    return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
+}
+
+int vslam_build_windows_kf_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int policy, double near_dist, int lm_capacity, int edge_capacity,
+                               vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status) {
+    if (!ctx || !in || !d_kf_frame || !d_evicted) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 sliding, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
+    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
+    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
+    if (policy == 1 && (in->d_T_abs || in->d_carry_in || in->d_carry_out)) {
+        set_error("keyframe culling needs the whole history: not available on a chunk (d_T_abs / d_carry_in / d_carry_out set)"); return VSLAM_ERR_ARG;
+    }
+    const KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
+    return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
 }
 
 int vslam_edge_jacobians(vslam_ctx* ctx, int n, const float* xyz_w, const float* uv, const double T_c_w[7], const double* K4, double* err, double* J_pose,

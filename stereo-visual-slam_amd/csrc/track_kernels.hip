@@ -10,8 +10,9 @@
 // observed by one of them, positions and reliable_depth_ as of time b.  Poses: the pose stage's relative poses chained from frame 0.
 //
 // Throughput-mode simplifications (stated in DESIGN.md): every frame is a keyframe, windows are independent (is_inlier = 1 on entry:
-// the chi2 classification of window b - 1 does not feed window b), the sliding window replaces the distance-based culling of
-// Map::remove_keyframe (map.cpp:48-130).
+// the chi2 classification of window b - 1 does not feed window b).  Which keyframes window b holds is a policy: the sliding window
+// [b - n_kf + 1, b] (vslam_build_windows_dev), or the distance-based culling of Map::remove_keyframe (map.cpp:48-130) evaluated on the
+// chained poses (vslam_build_windows_kf_dev policy 1: kf_band_kernel + kf_set_kernel below; the window kernels are templated on it).
 //
 // gfx950 mapping: the reference walks std::unordered_map<id, Landmark> with per-landmark observation vectors; here a track is a chain
 // of (frame, keypoint) nodes linked by two flat int32 tables pred / succ (B x kp_capacity) filled by one scatter pass per frame pair,
@@ -232,6 +233,118 @@ __global__ __launch_bounds__(256) void track_info_kernel(TrackDims d, const int3
     info[at] = (node ? 1 : 0) | (p >= 0 ? 2 : 0) | (rem << 8);
 }
 
+// ---- culled windows only: per chain, its last frame and its first node with a reliable depth (-1: none), stored at the chain's ROOT node.  A chain
+// is contiguous in frames from its root (no carry: policy 1 refuses chunks), so root / kp_cap is its first frame; the thread of the chain's last
+// node is the only writer of the record.
+__global__ __launch_bounds__(256) void track_ends_kernel(TrackDims d, const int32_t* __restrict__ succ, const int32_t* __restrict__ root,
+                                                        const int32_t* __restrict__ relsrc, int2* __restrict__ ends) {
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= d.kp_cap) return;
+    const size_t at = (size_t)f * d.kp_cap + i;
+    const int r = root[at];
+    if (r >= 0 && succ[at] < 0) ends[r] = make_int2(f, relsrc[at]);
+}
+
+// ---- the keyframe set of every window under the reference's culling (Map::remove_keyframe, map.cpp:48-130): S_0 = {0}; S_b = S_{b-1} + {b}, and
+// when that holds more than n_kf frames the member k != b with d_k = |log(G_k o G_b^-1)| smallest is evicted if d_k < near_dist, else the one with
+// d_k largest (ties: the lowest frame).  kf_distance is THE distance: the band pass and the chain's fallback both call it on the same G.
+constexpr int kKfBand = 64;   // D[b][j - 1] = d(b - j, b), j = 1 .. kKfBand
+constexpr int kKfRows = 32;   // band rows the serial chain stages in LDS at a time
+__device__ inline double kf_distance(const double* __restrict__ Gk, const double Gb_inv[7]) {
+    double T[7], xi[6];
+    se3::mul(Gk, Gb_inv, T);
+    se3::log(T, xi);
+    return sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2] + xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+}
+
+__global__ __launch_bounds__(256) void kf_band_kernel(int B, const double* __restrict__ G, double* __restrict__ D) {
+    const int t = blockIdx.x * 256 + threadIdx.x, b = t / kKfBand, j = t - b * kKfBand + 1;
+    if (b >= B) return;
+    double v = 0.0;
+    if (b - j >= 0) {
+        double Gi[7];
+        se3::inverse(G + (size_t)b * 7, Gi);
+        v = kf_distance(G + (size_t)(b - j) * 7, Gi);
+    }
+    D[t] = v;
+}
+
+// LDS hand-off inside ONE wave: a wave's LDS operations complete in order, so only the compiler needs fencing -- __syncthreads()' workgroup-scope
+// release would also wait for every global store in flight (the per-step outputs), about a microsecond per step of the chain below
+__device__ inline void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// one wave, serial over the windows: lane k holds member k of S_{b-1} (ascending frames).  Per step: a band lookup per member (an LDS row, staged
+// kKfRows steps at a time), the distance itself for members older than kKfBand, then every lane scans the <= VSLAM_MAX_KF (distance, frame) pairs
+// from LDS in frame order -- the reference's loop, unrolled so that the reads issue together -- and the members shift down over the evicted one.
+__global__ __launch_bounds__(64) void kf_set_kernel(int B, int n_kf, double near_dist, const double* __restrict__ G, const double* __restrict__ D,
+                                                    int32_t* __restrict__ kf_frame, int32_t* __restrict__ evicted, int32_t* __restrict__ flags) {
+    __shared__ double rows[kKfRows][kKfBand];
+    __shared__ double s_d[VSLAM_MAX_KF];
+    __shared__ int s_m[VSLAM_MAX_KF];
+    const int lane = threadIdx.x;
+    int mem = lane == 0 ? 0 : -1, n = 1, flag = 0;
+    if (lane < n_kf) kf_frame[lane] = mem;
+    if (lane == 0) evicted[0] = -1;
+    for (int base = 1; base < B; base += kKfRows) {
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kKfRows; ++r) rows[r][lane] = D[(size_t)min(base + r, B - 1) * kKfBand + lane]; // (clamped, not branched: the loads issue together)
+        __syncthreads();
+        for (int r = 0; r < kKfRows && base + r < B; ++r) {
+            const int b = base + r;
+            int ev = -1;
+            if (n < n_kf) {
+                if (lane == n) mem = b;
+                ++n;
+            } else {
+                const bool act = lane < n;
+                const int j = b - mem;
+                double dk = act && j <= kKfBand ? rows[r][j - 1] : 0.0;
+                if (__any(act && j > kKfBand)) {
+                    double Gi[7];
+                    se3::inverse(G + (size_t)b * 7, Gi);
+                    if (act && j > kKfBand) dk = kf_distance(G + (size_t)mem * 7, Gi);
+                }
+                const int moved = __shfl(mem, min(lane + 1, 63));
+                if (act) { s_d[lane] = dk; s_m[lane] = mem; }
+                wave_lds_sync();
+                int far = -1, near = -1;
+                double far_d = 0.0, near_d = 1e6; // (Map::remove_keyframe's starting values; NaN qualifies for neither)
+#pragma unroll
+                for (int k = 0; k < VSLAM_MAX_KF; ++k) {
+                    const double x = s_d[k];
+                    if (k < n && x > far_d) { far_d = x; far = k; }
+                    if (k < n && x < near_d) { near_d = x; near = k; }
+                }
+                int e;
+                if (near >= 0 && near_d < near_dist) e = near;
+                else if (far >= 0) e = far;
+                else { e = 0; flag |= 2; } // no member qualifies: the oldest goes, and the status says so
+                ev = s_m[e];
+                if (lane >= e && lane < n - 1) mem = moved;
+                if (lane == n - 1) mem = b;
+                wave_lds_sync();
+            }
+            if (lane < n_kf) kf_frame[(size_t)b * n_kf + lane] = lane < n ? mem : -1;
+            if (lane == 0) evicted[b] = ev;
+        }
+    }
+    if (lane == 0) *flags = flag;
+}
+
+// policy 0 through vslam_build_windows_kf_dev: the sliding window's sets written out
+__global__ __launch_bounds__(256) void kf_sliding_kernel(int B, int n_kf, int32_t* __restrict__ kf_frame, int32_t* __restrict__ evicted) {
+    const int t = blockIdx.x * 256 + threadIdx.x, b = t / n_kf, k = t - b * n_kf;
+    if (b >= B) return;
+    const int s = max(0, b - n_kf + 1);
+    kf_frame[t] = s + k <= b ? s + k : -1;
+    if (k == 0) evicted[b] = b >= n_kf ? b - n_kf : -1;
+}
+
 // ---- carry-out for the chunk that starts at frame c of this batch: per keypoint slot of frame c, does a track reach it from frame c - 1, and
 // what is that track's landmark position / reliable flag AS OF ITS NODE IN FRAME c - 1 (the state the next chunk's chain walk would have found upstream)
 __global__ __launch_bounds__(256) void track_carry_out_kernel(TrackDims d, int c, const int32_t* __restrict__ kp2lr, const int32_t* __restrict__ pred,
@@ -258,6 +371,27 @@ __device__ inline int window_head_len(int info, int s, int b, int f) {
     return min((info >> 8) + 1, b - f + 1);
 }
 
+// The same for a window whose keyframes are an arbitrary ascending set kf[0..n) (kf[n - 1] = b): a node in frame kf[k] is a head when its chain
+// has no node in the previous member kf[k - 1] -- chains are contiguous in frames, so when the chain starts after it -- and it has one observation
+// per member in [kf[k], min(last, b)].
+__device__ inline int window_set_head_len(int r, const int2* __restrict__ ends, int kp_cap, const int* kf, int n, int k) {
+    if (r < 0 || (k > 0 && r / kp_cap <= kf[k - 1])) return 0;
+    const int last = ends[r].x;
+    int len = 0;
+    for (int j = k; j < n && kf[j] <= last; ++j) ++len;
+    return len;
+}
+
+// A window's keyframes: the sliding window [s, b], or the culled set of kf_frame (kSet).  Loaded into the workgroup's LDS.
+struct WindowSet { const int32_t* kf_frame; const int2* ends; const int32_t* root; };
+template <bool kSet>
+__device__ inline int window_frames(const TrackDims& d, const WindowSet& ws, int b, int* s_kf) {
+    const int s = max(0, b - d.n_kf + 1), nk = b - s + 1;
+    if (threadIdx.x < nk) s_kf[threadIdx.x] = kSet ? ws.kf_frame[(size_t)b * d.n_kf + threadIdx.x] : s + threadIdx.x;
+    __syncthreads();
+    return nk; // (every set holds min(b + 1, n_kf) frames)
+}
+
 __device__ inline int block_sum_i32(int v, int* red /* 4 */) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     __syncthreads();
@@ -268,18 +402,23 @@ __device__ inline int block_sum_i32(int v, int* red /* 4 */) {
 
 // ---- per window: landmark and edge counts, and the landmarks per observation count (the bins of the emit pass)
 constexpr int kHist = VSLAM_MAX_KF + 1;
+template <bool kSet>
 __global__ __launch_bounds__(256) void window_count_kernel(TrackDims d, const int32_t* __restrict__ info, const int32_t* __restrict__ nkps,
-                                                          int32_t* __restrict__ counts, int32_t* __restrict__ hist) {
+                                                          int32_t* __restrict__ counts, int32_t* __restrict__ hist, WindowSet ws) {
     const int b = blockIdx.x, tid = threadIdx.x, s = max(0, b - d.n_kf + 1);
     __shared__ int red[4];
     __shared__ int h[kHist];
+    __shared__ int s_kf[VSLAM_MAX_KF];
     if (tid < kHist) h[tid] = 0;
-    __syncthreads();
+    const int nk = kSet ? window_frames<true>(d, ws, b, s_kf) : 0;
+    if (!kSet) __syncthreads();
     int nl = 0, ne = 0;
-    for (int f = s; f <= b; ++f) {
+    for (int k = 0; k < (kSet ? nk : b - s + 1); ++k) {
+        const int f = kSet ? s_kf[k] : s + k;
         const int nkp = nkps ? min(max(nkps[f], 0), d.kp_cap) : d.kp_cap; // (slots beyond the frame's keypoints are never nodes)
         for (int i = tid; i < nkp; i += 256) {
-            const int len = window_head_len(info[(size_t)f * d.kp_cap + i], s, b, f);
+            const int len = kSet ? window_set_head_len(ws.root[(size_t)f * d.kp_cap + i], ws.ends, d.kp_cap, s_kf, nk, k)
+                                 : window_head_len(info[(size_t)f * d.kp_cap + i], s, b, f);
             nl += len > 0; ne += len;
             if (len > 0) atomicAdd(&h[min(len, kHist - 1)], 1); // (integer: order-free)
         }
@@ -292,9 +431,10 @@ __global__ __launch_bounds__(256) void window_count_kernel(TrackDims d, const in
 
 // ---- offsets of the concatenated arrays (exclusive scan over the windows; one workgroup).  A window that would run past a capacity, and
 // every window after it, is emitted EMPTY and the status word is set: the caller sized its arrays too small.
+template <bool kSet>
 __global__ __launch_bounds__(256) void window_scan_kernel(TrackDims d, const int32_t* __restrict__ counts, int lm_capacity, int edge_capacity,
                                                          int32_t* __restrict__ lm_off, int32_t* __restrict__ edge_off, int32_t* __restrict__ n_kf_out,
-                                                         int32_t* __restrict__ status) {
+                                                         int32_t* __restrict__ status, const int32_t* __restrict__ set_flags) {
     __shared__ int sl[256], se[256];
     __shared__ int carry_l, carry_e, cut;
     const int tid = threadIdx.x;
@@ -336,7 +476,7 @@ __global__ __launch_bounds__(256) void window_scan_kernel(TrackDims d, const int
                 else { gl = lm_off[b + 1]; ge = edge_off[b + 1]; }
             }
         }
-        *status = cut ? 1 : 0;
+        *status = (cut ? 1 : 0) | (kSet ? *set_flags : 0);
     }
 }
 
@@ -344,28 +484,34 @@ __global__ __launch_bounds__(256) void window_scan_kernel(TrackDims d, const int
 // keypoint)); the head's record goes to head_rec[global landmark index] for the emit pass.  No dependent loads here: one info word per
 // slot, a ballot per count, three barriers per 1024 slots.
 constexpr int kRankBlock = 1024, kRankWaves = kRankBlock / 64;
+template <bool kSet>
 __global__ __launch_bounds__(kRankBlock) void window_rank_kernel(TrackDims d, const double* __restrict__ G, const int32_t* __restrict__ counts,
                                                                 const int32_t* __restrict__ hist, const int32_t* __restrict__ info,
                                                                 const int32_t* __restrict__ nkps, const int32_t* __restrict__ lm_off,
                                                                 const int32_t* __restrict__ edge_off, double* __restrict__ T_out,
-                                                                uint32_t* __restrict__ head_rec) {
+                                                                uint32_t* __restrict__ head_rec, WindowSet ws) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = max(0, b - d.n_kf + 1), nk = b - s + 1;
     __shared__ int s_c[kRankWaves][kHist];
     __shared__ int bin_l[kHist], s_run[kHist];
+    __shared__ int s_kf[VSLAM_MAX_KF];
+    if (kSet) window_frames<true>(d, ws, b, s_kf);
     for (int i = tid; i < d.n_kf * 7; i += kRankBlock) { // poses of the window's keyframes (unused slots: identity)
         const int k = i / 7, c = i - 7 * k;
-        T_out[(size_t)b * d.n_kf * 7 + i] = k < nk ? G[(size_t)(s + k) * 7 + c] : (c == 3 ? 1.0 : 0.0);
+        T_out[(size_t)b * d.n_kf * 7 + i] = k < nk ? G[(size_t)((kSet ? s_kf[k] : s + k)) * 7 + c] : (c == 3 ? 1.0 : 0.0);
     }
     const int l0 = lm_off[b];
     if (lm_off[b + 1] - l0 != counts[2 * b] || edge_off[b + 1] - edge_off[b] != counts[2 * b + 1]) return; // truncated by the capacity check: empty window
     if (tid == 0) { int al = 0; for (int c = 1; c < kHist; ++c) { bin_l[c] = al; al += hist[(size_t)b * kHist + c]; } }
     if (tid < kHist) s_run[tid] = 0;
     __syncthreads();
-    for (int f = s; f <= b; ++f) {
+    for (int k = 0; k < nk; ++k) {
+        const int f = kSet ? s_kf[k] : s + k;
         const int nkp = nkps ? min(max(nkps[f], 0), d.kp_cap) : d.kp_cap;
         for (int base = 0; base < nkp; base += kRankBlock) {
             const int i = base + tid;
-            const int len = i < nkp ? min(window_head_len(info[(size_t)f * d.kp_cap + i], s, b, f), kHist - 1) : 0;
+            const int len = i >= nkp ? 0
+                          : kSet ? min(window_set_head_len(ws.root[(size_t)f * d.kp_cap + i], ws.ends, d.kp_cap, s_kf, nk, k), kHist - 1)
+                                 : min(window_head_len(info[(size_t)f * d.kp_cap + i], s, b, f), kHist - 1);
             int my_rank = 0, my_wave_cnt = 0;
 #pragma unroll
             for (int c = 1; c < kHist; ++c) {
@@ -379,7 +525,7 @@ __global__ __launch_bounds__(kRankBlock) void window_rank_kernel(TrackDims d, co
             if (len > 0) {
                 int before = s_run[len];
                 for (int w = 0; w < wave; ++w) before += s_c[w][len];
-                head_rec[l0 + bin_l[len] + before + my_rank] = (uint32_t)(f - s) | ((uint32_t)i << 4) | ((uint32_t)len << 20);
+                head_rec[l0 + bin_l[len] + before + my_rank] = (uint32_t)k | ((uint32_t)i << 4) | ((uint32_t)len << 20); // (k: the head's slot)
             }
             __syncthreads();
             if (tid < kHist) { int t = 0; for (int w = 0; w < kRankWaves; ++w) t += s_c[w][tid]; s_run[tid] += t; }
@@ -388,7 +534,10 @@ __global__ __launch_bounds__(kRankBlock) void window_rank_kernel(TrackDims d, co
 }
 
 // ---- one thread per landmark of the batch: its edges (chronological) and its position / reliable_depth_ as of its last observation inside
-// the window.  Flat over the concatenated landmark array: the window is found by bisection of lm_off.
+// the window.  Flat over the concatenated landmark array: the window is found by bisection of lm_off.  A culled window (kSet) walks the chain
+// through the frames that are not members and emits at the members; its position is the chain's as of frame b (a reliable update in a culled
+// frame counts), read from the chain's record instead of its node at min(last, b).
+template <bool kSet>
 __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vslam_keypoint* __restrict__ d_kps, const float* __restrict__ d_xyz,
                                                          const int32_t* __restrict__ kp2lr, const int32_t* __restrict__ root,
                                                          const int32_t* __restrict__ relsrc, const int32_t* __restrict__ succ,
@@ -396,43 +545,64 @@ __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vsl
                                                          const uint32_t* __restrict__ head_rec, const int32_t* __restrict__ lm_off,
                                                          const int32_t* __restrict__ edge_off, float* __restrict__ xyz_out,
                                                          uint8_t* __restrict__ rel_out, uint8_t* __restrict__ inl_out, int32_t* __restrict__ kf_out,
-                                                         int32_t* __restrict__ lm_out, float* __restrict__ uv_out) {
+                                                         int32_t* __restrict__ lm_out, float* __restrict__ uv_out, WindowSet ws) {
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= lm_off[d.B]) return;
     int lo = 0, hi = d.B; // largest b with lm_off[b] <= g
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (lm_off[mid] <= g) lo = mid; else hi = mid; }
     const int b = lo, s = max(0, b - d.n_kf + 1), l = g - lm_off[b];
     const uint32_t rec = head_rec[g];
-    const int f = s + (int)(rec & 15u), i = (int)((rec >> 4) & 0xFFFFu), len = (int)(rec >> 20);
+    const int32_t* kfs = ws.kf_frame + (size_t)b * d.n_kf;
+    const int slot = (int)(rec & 15u), f = kSet ? kfs[slot] : s + slot, i = (int)((rec >> 4) & 0xFFFFu), len = (int)(rec >> 20);
     int bl = 0, be = 0; // first landmark / first edge of the landmarks with `len` observations
     for (int c = 1; c < len; ++c) { const int n = hist[(size_t)b * kHist + c]; bl += n; be += n * c; }
     int e = edge_off[b] + be + (l - bl) * len;
     int cf = f, ci = i;
-    for (int k = 0; k < len; ++k) {
-        const vslam_keypoint* kp = d_kps + (size_t)cf * d.kp_cap + ci;
-        kf_out[e] = cf - s; lm_out[e] = l;
-        reinterpret_cast<float2*>(uv_out)[e] = make_float2(kp->x, kp->y);
-        ++e;
-        if (k + 1 < len) { ci = succ[(size_t)cf * d.kp_cap + ci]; ++cf; }
+    if (kSet) {
+        for (int k = 0; k < len; ++k) {
+            const int tf = kfs[slot + k];
+            while (cf < tf) { const int nx = succ[(size_t)cf * d.kp_cap + ci]; ci = nx < 0 ? ci : nx; ++cf; } // (a chain reaches tf: ends[])
+            const vslam_keypoint* kp = d_kps + (size_t)cf * d.kp_cap + ci;
+            kf_out[e] = slot + k; lm_out[e] = l;
+            reinterpret_cast<float2*>(uv_out)[e] = make_float2(kp->x, kp->y);
+            ++e;
+        }
+    } else {
+        for (int k = 0; k < len; ++k) {
+            const vslam_keypoint* kp = d_kps + (size_t)cf * d.kp_cap + ci;
+            kf_out[e] = cf - s; lm_out[e] = l;
+            reinterpret_cast<float2*>(uv_out)[e] = make_float2(kp->x, kp->y);
+            ++e;
+            if (k + 1 < len) { ci = succ[(size_t)cf * d.kp_cap + ci]; ++cf; }
+        }
     }
     const size_t last = (size_t)cf * d.kp_cap + ci;
-    const int rs = relsrc[last];
-    const bool has_rel = rs >= 0 || rs <= kCarryCode;
+    bool has_rel;
     float pos[3];
-    landmark_position(d, has_rel ? rs : root[last], kp2lr, d_xyz, G, carry, pos);
+    if (kSet) { // the chain's first reliable node, if it lies at or before b
+        const int r = root[last], rs = ws.ends[r].y;
+        has_rel = rs >= 0 && rs / d.kp_cap <= b;
+        landmark_position(d, has_rel ? rs : r, kp2lr, d_xyz, G, carry, pos);
+    } else {
+        const int rs = relsrc[last];
+        has_rel = rs >= 0 || rs <= kCarryCode;
+        landmark_position(d, has_rel ? rs : root[last], kp2lr, d_xyz, G, carry, pos);
+    }
     float* o = xyz_out + 3 * (size_t)g;
     o[0] = pos[0]; o[1] = pos[1]; o[2] = pos[2];
     rel_out[g] = has_rel; inl_out[g] = 1;
 }
 
-size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity) {
+size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity, int policy) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return al((size_t)lm_capacity * 4) + 6 * al((size_t)B * kp_cap * 4) + al((size_t)B * 7 * 8) + al((size_t)B * 2 * 4) + al((size_t)B * (VSLAM_MAX_KF + 1) * 4);
+    const size_t base = al((size_t)lm_capacity * 4) + 6 * al((size_t)B * kp_cap * 4) + al((size_t)B * 7 * 8) + al((size_t)B * 2 * 4) + al((size_t)B * (VSLAM_MAX_KF + 1) * 4);
+    // culling: the chain records (int2 per slot), the distance band (B x kKfBand doubles), the set kernel's flags
+    return policy == 1 ? base + al((size_t)B * kp_cap * 8) + al((size_t)B * kKfBand * 8) + 256 : base;
 }
 
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, uint8_t* scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
-                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, hipStream_t stream) {
+                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     TrackDims d;
     d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = n_kf;
@@ -442,6 +612,14 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     double* G = (double*)(scratch + 6 * tab); int32_t* counts = (int32_t*)(scratch + 6 * tab + al((size_t)d.B * 7 * 8));
     int32_t* hist = (int32_t*)((uint8_t*)counts + al((size_t)d.B * 2 * 4));
     uint32_t* head_rec = (uint32_t*)((uint8_t*)hist + al((size_t)d.B * (VSLAM_MAX_KF + 1) * 4));
+    const bool cull = kp.policy == 1;
+    WindowSet ws = {kp.kf_frame, nullptr, root};
+    double* D = nullptr; int32_t* set_flags = nullptr;
+    if (cull) {
+        ws.ends = (const int2*)((uint8_t*)head_rec + al((size_t)lm_capacity * 4));
+        D = (double*)((uint8_t*)ws.ends + al((size_t)d.B * d.kp_cap * 8));
+        set_flags = (int32_t*)((uint8_t*)D + al((size_t)d.B * kKfBand * 8));
+    }
     TrackCam cam;
     cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
     int32_t* cand = info; // (the candidate words live in the info table until track_info_kernel writes it)
@@ -449,6 +627,11 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
     if (in.d_T_abs) VS_HIP(hipMemcpyAsync(G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
     else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(1), dim3(256), 0, stream, d.B, in.d_T_rel, G);
+    if (cull) { // the keyframe sets depend on the poses alone
+        hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D);
+        hipLaunchKernelGGL(kf_set_kernel, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, D, kp.kf_frame, kp.evicted, set_flags);
+    } else if (kp.policy == 0)
+        hipLaunchKernelGGL(kf_sliding_kernel, dim3((d.B * n_kf + 255) / 256), dim3(256), 0, stream, d.B, n_kf, kp.kf_frame, kp.evicted);
     if (d.B > 1) hipLaunchKernelGGL(track_link_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ);
     hipLaunchKernelGGL(track_walk_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ, G,
                        in.d_carry_in, root, relsrc);
@@ -456,11 +639,20 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     if (in.d_carry_out && in.carry_out_frame > 0 && in.carry_out_frame < d.B)
         hipLaunchKernelGGL(track_carry_out_kernel, dim3((d.kp_cap + 255) / 256), dim3(256), 0, stream, d, in.carry_out_frame, kp2lr, pred, root, relsrc, in.d_xyz, G,
                            in.d_carry_in, in.d_carry_out);
-    hipLaunchKernelGGL(window_count_kernel, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist);
-    hipLaunchKernelGGL(window_scan_kernel, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status);
-    hipLaunchKernelGGL(window_rank_kernel, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec);
-    hipLaunchKernelGGL(window_emit_kernel, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist, head_rec,
-                       d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out);
+    if (cull) {
+        hipLaunchKernelGGL(track_ends_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, succ, root, relsrc, const_cast<int2*>(ws.ends));
+        hipLaunchKernelGGL(window_count_kernel<true>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist, ws);
+        hipLaunchKernelGGL(window_scan_kernel<true>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags);
+        hipLaunchKernelGGL(window_rank_kernel<true>, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec, ws);
+        hipLaunchKernelGGL(window_emit_kernel<true>, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist,
+                           head_rec, d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out, ws);
+    } else {
+        hipLaunchKernelGGL(window_count_kernel<false>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist, ws);
+        hipLaunchKernelGGL(window_scan_kernel<false>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags);
+        hipLaunchKernelGGL(window_rank_kernel<false>, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec, ws);
+        hipLaunchKernelGGL(window_emit_kernel<false>, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist,
+                           head_rec, d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out, ws);
+    }
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

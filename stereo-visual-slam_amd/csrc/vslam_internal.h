@@ -264,11 +264,14 @@ size_t pnp_ransac_scratch_bytes(int B, int H);
 int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t* d_n, int capacity, int B, int H, const double K[4], double reproj_err,
                             double confidence, uint8_t* scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream);
 // track_kernels.hip: BA windows of a batch of consecutive keyframes from the front end's device-resident output
-size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity);
+// Which keyframes a window holds (vslam_build_windows_kf_dev): policy -1 = the sliding window with no set outputs (vslam_build_windows_dev),
+// 0 = the sliding window with its sets written to kf_frame / evicted, 1 = the reference's culling (needs the extra scratch of track_scratch_bytes)
+struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evicted; };
+size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity, int policy);
 // K4 = {fx, fy, cx, cy}, reproj_thr (pixels), track_rule: see Tuning::track_rule
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, uint8_t* scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
-                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, hipStream_t stream);
+                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {

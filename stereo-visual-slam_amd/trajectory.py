@@ -1,0 +1,77 @@
+"""The trajectory of a throughput-mode batch: every keyframe's pose as the BA windows left it, in the order the reference writes them.
+
+The reference writes a keyframe's pose when Map::remove_keyframe evicts it (map.cpp:119-121, Map::write_pose :168-197) and, at the end of
+the run, the keyframes the map still holds (run_vslam.cpp:84-86).  Here a frame evicted at step b leaves window b - 1, the last window that
+held it, so its pose is window b - 1's BA result at its slot there; the frames of the last window take theirs from that window.  Pure numpy:
+the inputs are the keyframe sets of vslam_build_windows_kf_dev (or of the sliding window) and the BA-refined window poses.
+"""
+import numpy as np
+
+
+def sliding_keyframes(B, n_kf):
+    """the keyframe sets of the sliding window: kf_frame (B, n_kf) with -1 in unused slots, evicted (B,) = b - n_kf (-1 while negative)"""
+    b = np.arange(B)[:, None]
+    f = np.maximum(b - n_kf + 1, 0) + np.arange(n_kf)[None, :]
+    kf_frame = np.where(f <= b, f, -1).astype(np.int32)
+    evicted = np.where(np.arange(B) >= n_kf, np.arange(B) - n_kf, -1).astype(np.int32)
+    return kf_frame, evicted
+
+
+def assemble_trajectory(kf_frame, evicted, ba_T):
+    """kf_frame (B, n_kf) int: window b's frames ascending (-1 unused); evicted (B,) int: the frame evicted at step b (-1 none);
+    ba_T (B, n_kf, 7): the windows' poses (T_c_w, slot k = kf_frame[b, k]).  Returns (frame_ids, T_c_w): the frames in write order --
+    each evicted frame at its eviction, then the last window's frames ascending -- and (len(frame_ids), 7) their poses, row i for frame_ids[i]."""
+    kf_frame = np.asarray(kf_frame); evicted = np.asarray(evicted); ba_T = np.asarray(ba_T, np.float64)
+    B = kf_frame.shape[0]
+    ids, poses = [], []
+    for b in range(1, B):
+        e = int(evicted[b])
+        if e < 0:
+            continue
+        slot = np.flatnonzero(kf_frame[b - 1] == e)
+        if len(slot) != 1:
+            raise ValueError("frame %d evicted at step %d is not in window %d" % (e, b, b - 1))
+        ids.append(e); poses.append(ba_T[b - 1, int(slot[0])])
+    if B > 0:
+        for k, f in enumerate(kf_frame[B - 1]):
+            if f >= 0:
+                ids.append(int(f)); poses.append(ba_T[B - 1, k])
+    return np.array(ids, np.int64), (np.stack(poses) if poses else np.zeros((0, 7)))
+
+
+def _rotmat(q):
+    x, y, z, w = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def T_w_c_rows(T_c_w):
+    """(N, 7) T_c_w (quaternion x, y, z, w, then translation) -> (N, 12): the row-major 3 x 4 [R | t] of T_w_c = T_c_w^-1"""
+    T_c_w = np.asarray(T_c_w, np.float64).reshape(-1, 7)
+    out = np.zeros((len(T_c_w), 12))
+    for n, T in enumerate(T_c_w):
+        R = _rotmat(T[:4] / np.linalg.norm(T[:4]))
+        Rt = R.T
+        out[n] = np.concatenate([Rt, (-Rt @ T[4:])[:, None]], axis=1).ravel()
+    return out
+
+
+def write_trajectory(path, frame_ids, T_c_w):
+    """one line per frame, the format of Map::write_pose (host/map_host.cpp): the frame id, then the row-major 3 x 4 T_w_c, each number as a C++
+    stream prints a double (6 significant digits)"""
+    rows = T_w_c_rows(T_c_w)
+    with open(path, "w") as fh:
+        for f, r in zip(frame_ids, rows):
+            fh.write("%d %s\n" % (int(f), " ".join("%g" % v for v in r)))
+
+
+def read_trajectory(path):
+    """the inverse of write_trajectory: (frame_ids (N,), T_w_c rows (N, 12))"""
+    ids, rows = [], []
+    with open(path) as fh:
+        for line in fh:
+            v = line.split()
+            if v:
+                ids.append(int(v[0])); rows.append([float(x) for x in v[1:13]])
+    return np.array(ids, np.int64), np.array(rows, np.float64).reshape(-1, 12)
