@@ -340,8 +340,8 @@ int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf,
  *   near is evicted if near_d < near_dist (the reference: 0.2), otherwise far.
  *   Deviations from the reference: ties go to the lowest frame (the reference iterates an unordered_map); the distance is taken on the chained
  *   pose-stage poses, not on BA-refined ones (windows are independent); if no member qualifies (e.g. every distance is non-finite) the oldest
- *   member is evicted and bit 1 (value 2) of *d_status is set.  The keyframe gate of insert_key_frame (visual_odometry.cpp:353) is not applied:
- *   every frame is still a keyframe.
+ *   member is evicted and bit 1 (value 2) of *d_status is set.  This entry point does not apply the keyframe gate of insert_key_frame
+ *   (visual_odometry.cpp:353): every frame is a keyframe.  vslam_build_windows_gated_dev below applies it.
  * Window b holds the frames of S_b in ascending order in slots 0..|S_b|-1 (T_c_w slot k = G[S_b[k]], edges' kf_idx = slot); its landmarks are
  * those with at least one observation in a frame of S_b (what clean_map keeps), with position and reliable_depth_ as of frame b (a reliable
  * update in a culled frame counts), ordered as in vslam_build_windows_dev by observation count inside S_b, then by first observation inside S_b.
@@ -351,6 +351,31 @@ int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf,
  * 1..VSLAM_MAX_KF, NULL d_kf_frame / d_evicted. */
 int vslam_build_windows_kf_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int policy, double near_dist, int lm_capacity,
                                int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status);
+
+/* vslam_build_windows_kf_dev with insert_key_frame's keyframe gate (visual_odometry.cpp:348-424; additive: the ABI version is unchanged).
+ * d_num_inliers (n_frames - 1, device): item i = the pose stage's inlier count (num_inliers_) of frame i + 1.  Per frame the state (d_frame_state,
+ * n_frames, device): frame 0 is 2 (initialization); frame f >= 1 with n = d_num_inliers[f - 1], T = d_T_rel[f - 1] (T_c_l_):
+ *   check = at least 10 inliers and |log T| <= 5 (check_motion_estimation :316-346, frame_gap 1; the arithmetic of vslam_check_motion);
+ *   2 = keyframe: check && !(n >= 80 && angleY(T) < 0.03) (:353, angleY signed); 1 = tracked, not a keyframe; 0 = rejected (check false).
+ * What a non-keyframe changes: its depth-valid keypoints that no track reaches create no landmark (they are not features: a match out of them
+ * continues nothing), it records no observation, and a landmark with an unreliable depth does not take a reliable one from it (:391-401).
+ * Tracked features pass through it, continued exactly as in vslam_build_windows_dev (d_pose_inlier, or track_rule 1's reprojection).
+ * Keyframe sets: S_0 = {0}; at a keyframe step b, S_b = S_prev + {b}, and when that holds more than n_kf frames one member is evicted by the
+ * policy -- 0: the oldest; 1: vslam_build_windows_kf_dev's Map::remove_keyframe rule (near_dist, ties, fallback and status bit 1 as there).  At
+ * any other step S_b = S_{b-1} and d_evicted[b] = -1.  d_kf_frame[b] = S_b for every step (ascending, -1 padded).
+ * Windows: at a keyframe step, window b is the map right after keyframe b is inserted -- vslam_build_windows_kf_dev's window on S_b (landmarks
+ * with an observation in S_b, observations from keyframes only, position and reliable_depth_ as of frame b, the same order and capacity
+ * behaviour).  At any other step the window is EMPTY: lm_off / edge_off do not advance, d_n_kf[b] = 0, T_c_w slot 0 = the frame's chained pose
+ * (the BA reads defined numbers; nothing should read its result), the other slots untouched.
+ * Deviations from the reference: a rejected frame (state 0) is never a keyframe but is otherwise treated like state 1 (tracks and the pose chain
+ * pass through it; the reference re-matches the next frame against the last accepted one) and sets bit 2 (value 4) of *d_status; frame_gap is
+ * always 1; the VO "Lost" state is not modelled; the pose stage's inputs are what the caller computed (after a non-keyframe they are not the
+ * reference's).  With every frame a keyframe, every output is vslam_build_windows_kf_dev's with the same policy, bit for bit.
+ * Refused with VSLAM_ERR_ARG: a chunk (d_T_abs, d_carry_in or d_carry_out set), NULL d_num_inliers when n_frames > 1, NULL d_kf_frame /
+ * d_evicted / d_frame_state, a policy other than 0 / 1, near_dist NaN or negative, n_kf outside 1..VSLAM_MAX_KF. */
+int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int policy, double near_dist, const int32_t* d_num_inliers,
+                                  int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted,
+                                  int32_t* d_frame_state, int32_t* d_status);
 
 /* per-window status of the most recent window launch on this process (VSLAM_OK or VSLAM_ERR_ARG per window) */
 int vslam_ba_status_dev(vslam_ctx* ctx, int n_windows, int32_t* h_status);

@@ -77,7 +77,7 @@ ABI_SYMBOLS = [
     "vslam_dev_free", "vslam_dev_upload", "vslam_dev_download", "vslam_dev_memset", "vslam_build_pnp_inputs_dev",
     "vslam_profile_enable", "vslam_profile_read", "vslam_profile_intervals", "vslam_hbm_copy_probe", "vslam_disparity_map", "vslam_disparity_map_dev", "vslam_pnp_ransac", "vslam_pnp_ransac_models", "vslam_find_3d_disparity_dev",
     "vslam_abi_version", "vslam_hbm_copy_probe_variants", "vslam_hbm_copy_probe_variant", "vslam_sgbm_status_dev", "vslam_set_tuning", "vslam_build_windows_dev", "vslam_pnp_ransac_dev",
-    "vslam_build_windows_kf_dev",
+    "vslam_build_windows_kf_dev", "vslam_build_windows_gated_dev",
 ]
 
 
@@ -143,6 +143,7 @@ def load_library():
     lib.vslam_feature_matching_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, vp, i32, i32, i32, vp, i32, vp]
     lib.vslam_hbm_copy_probe_variant.argtypes = [vp, C.c_size_t, i32, i32, vp, vp]
     lib.vslam_build_windows_kf_dev.argtypes = [vp, vp, i32, i32, dbl, i32, i32, vp, vp, vp, vp]
+    lib.vslam_build_windows_gated_dev.argtypes = [vp, vp, i32, i32, dbl, vp, i32, i32, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -431,6 +432,16 @@ class VO:
         self._chk(self.lib.vslam_build_windows_kf_dev(self.h, C.byref(tracks), int(n_kf), int(policy), C.c_double(near_dist), int(lm_capacity),
                                                       int(edge_capacity), C.byref(batch), _p(d_kf_frame), _p(d_evicted), _p(d_status)),
                   "vslam_build_windows_kf_dev")
+
+    def build_windows_gated_dev(self, tracks, n_kf, policy, near_dist, d_num_inliers, lm_capacity, edge_capacity, batch, d_kf_frame, d_evicted,
+                                d_frame_state, d_status):
+        """build_windows_kf_dev with insert_key_frame's keyframe gate (visual_odometry.cpp:353): d_num_inliers (n_frames - 1 int32, item i = frame
+        i + 1) and the relative poses decide each frame's state (d_frame_state, n_frames int32: 2 keyframe, 1 tracked, 0 rejected); only keyframes
+        create landmarks, record observations and enter the sets (policy 0 oldest evicted, 1 the reference's culling); a non-keyframe step's window
+        is empty.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_build_windows_gated_dev(self.h, C.byref(tracks), int(n_kf), int(policy), C.c_double(near_dist), _p(d_num_inliers),
+                                                         int(lm_capacity), int(edge_capacity), C.byref(batch), _p(d_kf_frame), _p(d_evicted),
+                                                         _p(d_frame_state), _p(d_status)), "vslam_build_windows_gated_dev")
 
     def build_pnp_inputs_dev(self, d_f2f, d_nf2f, match_cap, d_lr, d_nlr, lr_cap, d_xyz_lr, d_valid_lr, d_kps_cur, kp_cap, B, d_kp2lr,
                              d_xyz_out, d_uv_out, d_nout, out_cap):

@@ -225,7 +225,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "lm_window_kernel<pnp> pnp_wave_kernel pnp_inlier_kernel pnp_epnp_kernels epnp_front_kernel epnp_jacobi_kernel epnp_back_kernel pnp_count_inliers_kernel hbm_copy_probe_kernel "
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
-           "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel";
+           "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -662,12 +662,7 @@ int vslam_gather_matched_uv_dev(vslam_ctx* ctx, const vslam_keypoint* d_kpsQ, co
 
 int vslam_check_motion(int num_inliers, const double T_c_l[7], double frame_gap) {
     if (!T_c_l) return 0;
-    if (num_inliers < 10) return 0; // visual_odometry.cpp:319
-    double xi[6];
-    se3::log(T_c_l, xi);            // :327
-    double s = 0;
-    for (int i = 0; i < 6; ++i) s += xi[i] * xi[i];
-    return std::sqrt(s) > 5.0 * frame_gap ? 0 : 1; // :329
+    return check_motion_rule(num_inliers, T_c_l, frame_gap) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------- motion-only pose
@@ -993,7 +988,7 @@ static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, in
     }
     if (in->kp_capacity > 65536) { set_error("kp_capacity %d exceeds 65536 (the window builder packs a keypoint index into 16 bits)", in->kp_capacity); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    const size_t need = track_scratch_bytes(in->n_frames, in->kp_capacity, lm_capacity, kp.policy);
+    const size_t need = track_scratch_bytes(in->n_frames, in->kp_capacity, lm_capacity, kp.policy, kp.gate);
     if (c->track_bytes < need) {
         VS_HIP(hipStreamSynchronize(c->stream));
         if (c->d_track) { (void)hipFree(c->d_track); c->dev_bytes -= c->track_bytes; }
@@ -1025,6 +1020,22 @@ int vslam_build_windows_kf_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_
         set_error("keyframe culling needs the whole history: not available on a chunk (d_T_abs / d_carry_in / d_carry_out set)"); return VSLAM_ERR_ARG;
     }
     const KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
+    return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
+}
+
+int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int policy, double near_dist, const int32_t* d_num_inliers,
+                                  int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_frame_state,
+                                  int32_t* d_status) {
+    if (!ctx || !in || !d_kf_frame || !d_evicted || !d_frame_state) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (in->n_frames > 1 && !d_num_inliers) { set_error("the keyframe gate needs d_num_inliers (n_frames - 1 pose-stage inlier counts)"); return VSLAM_ERR_ARG; }
+    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 oldest evicted, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
+    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
+    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
+    if (in->d_T_abs || in->d_carry_in || in->d_carry_out) {
+        set_error("the keyframe gate needs the whole history: not available on a chunk (d_T_abs / d_carry_in / d_carry_out set)"); return VSLAM_ERR_ARG;
+    }
+    KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
+    kp.gate = true; kp.num_inliers = d_num_inliers; kp.frame_state = d_frame_state;
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
 }
 

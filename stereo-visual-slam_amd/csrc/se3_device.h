@@ -121,4 +121,22 @@ VS_HD double angle_y(const double* T) {
 }
 
 } // namespace se3
+
+// VO::check_motion_estimation (visual_odometry.cpp:316-346): at least 10 inliers and |log T_c_l| <= 5 * frame_gap.  The one definition of the
+// rule: vslam_check_motion (host) and the keyframe gate of vslam_build_windows_gated_dev (device) both call it.
+VS_HD bool check_motion_rule(int num_inliers, const double* T_c_l, double frame_gap) {
+    if (num_inliers < 10) return false; // :319
+    double xi[6];
+    se3::log(T_c_l, xi);                // :327
+    double s = 0;
+    for (int i = 0; i < 6; ++i) s += xi[i] * xi[i];
+    return !(sqrt(s) > 5.0 * frame_gap); // :329
+}
+
+// VO::insert_key_frame's gate (:353) on a frame f >= 1 with frame_gap 1: 2 = keyframe, 1 = tracked but not a keyframe (>= 80 inliers and a
+// signed angleY below 0.03), 0 = rejected by check_motion_estimation
+VS_HD int keyframe_state(int num_inliers, const double* T_c_l) {
+    if (!check_motion_rule(num_inliers, T_c_l, 1.0)) return 0;
+    return (num_inliers >= 80 && se3::angle_y(T_c_l) < 0.03) ? 1 : 2;
+}
 } // namespace vslam

@@ -9,7 +9,8 @@
 // map right after keyframe b was inserted: keyframes [max(0, b - n_kf + 1), b] (Map::num_keyframes_ = 10, map.hpp:22), every landmark
 // observed by one of them, positions and reliable_depth_ as of time b.  Poses: the pose stage's relative poses chained from frame 0.
 //
-// Throughput-mode simplifications (stated in DESIGN.md): every frame is a keyframe, windows are independent (is_inlier = 1 on entry:
+// Throughput-mode simplifications (stated in DESIGN.md): every frame is a keyframe unless the gate of insert_key_frame is applied
+// (vslam_build_windows_gated_dev: kf_gate_kernel, track_walk_kernel<true>, kf_set_kernel<true>), windows are independent (is_inlier = 1 on entry:
 // the chi2 classification of window b - 1 does not feed window b).  Which keyframes window b holds is a policy: the sliding window
 // [b - n_kf + 1, b] (vslam_build_windows_dev), or the distance-based culling of Map::remove_keyframe (map.cpp:48-130) evaluated on the
 // chained poses (vslam_build_windows_kf_dev policy 1: kf_band_kernel + kf_set_kernel below; the window kernels are templated on it).
@@ -167,11 +168,14 @@ __device__ inline bool reprojects_within(const float pos[3], const double* __res
 // first frame from BEFORE the batch.  Such a slot is a feature whatever its own depth, and the chain's root -- and its first reliable node, if the
 // carry says one was seen -- lie upstream: both tables then hold the code  kCarryCode - slot  (< -1), which resolves to the carried position.
 // Sequential per path (its length: a few frames for most, the batch at worst), parallel over the ~B x 1200 paths.
+// kGate (vslam_build_windows_gated_dev): a landmark is created, and takes its first reliable depth, only at a KEYFRAME node (state[f] == 2,
+// insert_key_frame :353-424); a tracked feature passes through a non-keyframe exactly as above.
+template <bool kGate>
 __global__ __launch_bounds__(256) void track_walk_kernel(TrackDims d, TrackCam cam, const vslam_keypoint* __restrict__ d_kps, const float* __restrict__ d_xyz,
                                                         const uint8_t* __restrict__ d_valid, const uint8_t* __restrict__ d_rel, const int32_t* __restrict__ kp2lr,
                                                         const int32_t* __restrict__ cand, int32_t* __restrict__ pred, int32_t* __restrict__ succ,
                                                         const double* __restrict__ G, const float* __restrict__ carry, int32_t* __restrict__ root,
-                                                        int32_t* __restrict__ relsrc) {
+                                                        int32_t* __restrict__ relsrc, const int32_t* __restrict__ state) {
     const int f0 = blockIdx.y, i0 = blockIdx.x * 256 + threadIdx.x;
     if (i0 >= d.kp_cap) return;
     if (f0 > 0 && cand[(size_t)f0 * d.kp_cap + i0] >= 0) return; // some earlier slot's walk passes through here
@@ -187,7 +191,7 @@ __global__ __launch_bounds__(256) void track_walk_kernel(TrackDims d, TrackCam c
         const size_t c = (size_t)cf * d.kp_cap + ci;
         const int node = cf * d.kp_cap + ci;
         const int mm = kp2lr[c];
-        const bool own3d = mm >= 0 && d_valid[(size_t)cf * d.lr_cap + mm] != 0;
+        const bool own3d = mm >= 0 && d_valid[(size_t)cf * d.lr_cap + mm] != 0 && (!kGate || state[cf] == 2);
         if (!feat && own3d) { feat = true; r = node; first = -1; }                                        // :403-418 a landmark is created here
         if (feat && first == -1 && own3d && d_rel[(size_t)cf * d.lr_cap + mm] != 0) first = node;           // :391-401 (or created reliable)
         root[c] = feat ? r : -1; relsrc[c] = feat ? first : -1;
@@ -280,26 +284,44 @@ __device__ inline void wave_lds_sync() {
 // one wave, serial over the windows: lane k holds member k of S_{b-1} (ascending frames).  Per step: a band lookup per member (an LDS row, staged
 // kKfRows steps at a time), the distance itself for members older than kKfBand, then every lane scans the <= VSLAM_MAX_KF (distance, frame) pairs
 // from LDS in frame order -- the reference's loop, unrolled so that the reads issue together -- and the members shift down over the evicted one.
+// kGate (vslam_build_windows_gated_dev): only a step whose frame state is 2 inserts its frame; any other step repeats S_{b-1}, evicts nothing and
+// records 0 members in nmem (its window is empty); a rejected frame (state 0) sets bit 2 of the flags.  policy 0 evicts the oldest member (no band:
+// D = nullptr), policy 1 as above.  nmem[b] = |S_b| at a keyframe step.
+template <bool kGate>
 __global__ __launch_bounds__(64) void kf_set_kernel(int B, int n_kf, double near_dist, const double* __restrict__ G, const double* __restrict__ D,
-                                                    int32_t* __restrict__ kf_frame, int32_t* __restrict__ evicted, int32_t* __restrict__ flags) {
+                                                    int32_t* __restrict__ kf_frame, int32_t* __restrict__ evicted, int32_t* __restrict__ flags,
+                                                    const int32_t* __restrict__ state, int32_t* __restrict__ nmem) {
     __shared__ double rows[kKfRows][kKfBand];
     __shared__ double s_d[VSLAM_MAX_KF];
     __shared__ int s_m[VSLAM_MAX_KF];
+    __shared__ int s_st[kKfRows];
     const int lane = threadIdx.x;
+    const bool band = !kGate || D != nullptr;
     int mem = lane == 0 ? 0 : -1, n = 1, flag = 0;
     if (lane < n_kf) kf_frame[lane] = mem;
     if (lane == 0) evicted[0] = -1;
+    if (kGate && lane == 0) nmem[0] = 1; // (frame 0 is a keyframe: initialization)
     for (int base = 1; base < B; base += kKfRows) {
         __syncthreads();
+        if (band)
 #pragma unroll
-        for (int r = 0; r < kKfRows; ++r) rows[r][lane] = D[(size_t)min(base + r, B - 1) * kKfBand + lane]; // (clamped, not branched: the loads issue together)
+            for (int r = 0; r < kKfRows; ++r) rows[r][lane] = D[(size_t)min(base + r, B - 1) * kKfBand + lane]; // (clamped, not branched: the loads issue together)
+        if (kGate && lane < kKfRows) s_st[lane] = state[min(base + lane, B - 1)];
         __syncthreads();
         for (int r = 0; r < kKfRows && base + r < B; ++r) {
             const int b = base + r;
             int ev = -1;
-            if (n < n_kf) {
+            const int st = kGate ? s_st[r] : 2;
+            if (st != 2) {
+                if (st == 0) flag |= 4;
+            } else if (n < n_kf) {
                 if (lane == n) mem = b;
                 ++n;
+            } else if (!band) { // policy 0: the oldest member goes
+                ev = __shfl(mem, 0);
+                const int moved = __shfl(mem, min(lane + 1, 63));
+                if (lane < n - 1) mem = moved;
+                if (lane == n - 1) mem = b;
             } else {
                 const bool act = lane < n;
                 const int j = b - mem;
@@ -331,9 +353,18 @@ __global__ __launch_bounds__(64) void kf_set_kernel(int B, int n_kf, double near
             }
             if (lane < n_kf) kf_frame[(size_t)b * n_kf + lane] = lane < n ? mem : -1;
             if (lane == 0) evicted[b] = ev;
+            if (kGate && lane == 0) nmem[b] = st == 2 ? n : 0;
         }
     }
     if (lane == 0) *flags = flag;
+}
+
+// ---- insert_key_frame's gate, one thread per frame: frame 0 is a keyframe (initialization), frame f >= 1 gets keyframe_state(num_inliers_,
+// T_c_l_) from the pose stage's outputs of item f - 1
+__global__ __launch_bounds__(256) void kf_gate_kernel(int B, const int32_t* __restrict__ num_inliers, const double* __restrict__ T_rel, int32_t* __restrict__ state) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= B) return;
+    state[f] = f == 0 ? 2 : keyframe_state(num_inliers[f - 1], T_rel + (size_t)(f - 1) * 7);
 }
 
 // policy 0 through vslam_build_windows_kf_dev: the sliding window's sets written out
@@ -382,14 +413,16 @@ __device__ inline int window_set_head_len(int r, const int2* __restrict__ ends, 
     return len;
 }
 
-// A window's keyframes: the sliding window [s, b], or the culled set of kf_frame (kSet).  Loaded into the workgroup's LDS.
-struct WindowSet { const int32_t* kf_frame; const int2* ends; const int32_t* root; };
+// A window's keyframes: the sliding window [s, b], or the culled set of kf_frame (kSet).  Loaded into the workgroup's LDS.  nmem (gated sets
+// only, else nullptr): the member count of every window, 0 for the empty window of a non-keyframe step; without it every set holds
+// min(b + 1, n_kf) frames.
+struct WindowSet { const int32_t* kf_frame; const int2* ends; const int32_t* root; const int32_t* nmem; };
 template <bool kSet>
 __device__ inline int window_frames(const TrackDims& d, const WindowSet& ws, int b, int* s_kf) {
-    const int s = max(0, b - d.n_kf + 1), nk = b - s + 1;
+    const int s = max(0, b - d.n_kf + 1), nk = kSet && ws.nmem ? ws.nmem[b] : b - s + 1;
     if (threadIdx.x < nk) s_kf[threadIdx.x] = kSet ? ws.kf_frame[(size_t)b * d.n_kf + threadIdx.x] : s + threadIdx.x;
     __syncthreads();
-    return nk; // (every set holds min(b + 1, n_kf) frames)
+    return nk;
 }
 
 __device__ inline int block_sum_i32(int v, int* red /* 4 */) {
@@ -434,7 +467,7 @@ __global__ __launch_bounds__(256) void window_count_kernel(TrackDims d, const in
 template <bool kSet>
 __global__ __launch_bounds__(256) void window_scan_kernel(TrackDims d, const int32_t* __restrict__ counts, int lm_capacity, int edge_capacity,
                                                          int32_t* __restrict__ lm_off, int32_t* __restrict__ edge_off, int32_t* __restrict__ n_kf_out,
-                                                         int32_t* __restrict__ status, const int32_t* __restrict__ set_flags) {
+                                                         int32_t* __restrict__ status, const int32_t* __restrict__ set_flags, const int32_t* __restrict__ nmem) {
     __shared__ int sl[256], se[256];
     __shared__ int carry_l, carry_e, cut;
     const int tid = threadIdx.x;
@@ -460,7 +493,7 @@ __global__ __launch_bounds__(256) void window_scan_kernel(TrackDims d, const int
             int ol = il, oe = ie;
             if (over) { ol = -1; oe = -1; }
             lm_off[b + 1] = ol; edge_off[b + 1] = oe;
-            n_kf_out[b] = min(b + 1, d.n_kf);
+            n_kf_out[b] = kSet && nmem ? nmem[b] : min(b + 1, d.n_kf);
         }
         __syncthreads();
         if (tid == 255) { carry_l = il; carry_e = ie; }
@@ -490,11 +523,15 @@ __global__ __launch_bounds__(kRankBlock) void window_rank_kernel(TrackDims d, co
                                                                 const int32_t* __restrict__ nkps, const int32_t* __restrict__ lm_off,
                                                                 const int32_t* __restrict__ edge_off, double* __restrict__ T_out,
                                                                 uint32_t* __restrict__ head_rec, WindowSet ws) {
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = max(0, b - d.n_kf + 1), nk = b - s + 1;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = max(0, b - d.n_kf + 1);
     __shared__ int s_c[kRankWaves][kHist];
     __shared__ int bin_l[kHist], s_run[kHist];
     __shared__ int s_kf[VSLAM_MAX_KF];
-    if (kSet) window_frames<true>(d, ws, b, s_kf);
+    const int nk = kSet ? window_frames<true>(d, ws, b, s_kf) : b - s + 1;
+    if (kSet && nk == 0) { // the empty window of a non-keyframe step (gated sets): slot 0 = its own frame's pose, the other slots untouched
+        if (tid < 7) T_out[(size_t)b * d.n_kf * 7 + tid] = G[(size_t)b * 7 + tid];
+        return;
+    }
     for (int i = tid; i < d.n_kf * 7; i += kRankBlock) { // poses of the window's keyframes (unused slots: identity)
         const int k = i / 7, c = i - 7 * k;
         T_out[(size_t)b * d.n_kf * 7 + i] = k < nk ? G[(size_t)((kSet ? s_kf[k] : s + k)) * 7 + c] : (c == 3 ? 1.0 : 0.0);
@@ -593,11 +630,12 @@ __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vsl
     rel_out[g] = has_rel; inl_out[g] = 1;
 }
 
-size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity, int policy) {
+size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity, int policy, bool gate) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t base = al((size_t)lm_capacity * 4) + 6 * al((size_t)B * kp_cap * 4) + al((size_t)B * 7 * 8) + al((size_t)B * 2 * 4) + al((size_t)B * (VSLAM_MAX_KF + 1) * 4);
-    // culling: the chain records (int2 per slot), the distance band (B x kKfBand doubles), the set kernel's flags
-    return policy == 1 ? base + al((size_t)B * kp_cap * 8) + al((size_t)B * kKfBand * 8) + 256 : base;
+    // culling: the chain records (int2 per slot), the distance band (B x kKfBand doubles), the set kernel's flags; the gate: also the member counts
+    const size_t set = base + al((size_t)B * kp_cap * 8) + al((size_t)B * kKfBand * 8) + 256;
+    return gate ? set + al((size_t)B * 4) : policy == 1 ? set : base;
 }
 
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, uint8_t* scratch,
@@ -612,13 +650,14 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     double* G = (double*)(scratch + 6 * tab); int32_t* counts = (int32_t*)(scratch + 6 * tab + al((size_t)d.B * 7 * 8));
     int32_t* hist = (int32_t*)((uint8_t*)counts + al((size_t)d.B * 2 * 4));
     uint32_t* head_rec = (uint32_t*)((uint8_t*)hist + al((size_t)d.B * (VSLAM_MAX_KF + 1) * 4));
-    const bool cull = kp.policy == 1;
-    WindowSet ws = {kp.kf_frame, nullptr, root};
-    double* D = nullptr; int32_t* set_flags = nullptr;
+    const bool gate = kp.gate, cull = kp.policy == 1 || gate; // (cull: the set-templated window kernels)
+    WindowSet ws = {kp.kf_frame, nullptr, root, nullptr};
+    double* D = nullptr; int32_t* set_flags = nullptr; int32_t* nmem = nullptr;
     if (cull) {
         ws.ends = (const int2*)((uint8_t*)head_rec + al((size_t)lm_capacity * 4));
         D = (double*)((uint8_t*)ws.ends + al((size_t)d.B * d.kp_cap * 8));
         set_flags = (int32_t*)((uint8_t*)D + al((size_t)d.B * kKfBand * 8));
+        if (gate) ws.nmem = nmem = (int32_t*)((uint8_t*)set_flags + 256);
     }
     TrackCam cam;
     cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
@@ -627,14 +666,23 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
     if (in.d_T_abs) VS_HIP(hipMemcpyAsync(G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
     else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(1), dim3(256), 0, stream, d.B, in.d_T_rel, G);
-    if (cull) { // the keyframe sets depend on the poses alone
+    if (gate) { // the states depend on the pose stage's outputs alone, the keyframe sets on the states and the poses
+        hipLaunchKernelGGL(kf_gate_kernel, dim3((d.B + 255) / 256), dim3(256), 0, stream, d.B, kp.num_inliers, in.d_T_rel, kp.frame_state);
+        if (kp.policy == 1) hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D);
+        hipLaunchKernelGGL(kf_set_kernel<true>, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, kp.policy == 1 ? D : nullptr, kp.kf_frame, kp.evicted,
+                           set_flags, kp.frame_state, nmem);
+    } else if (cull) { // the keyframe sets depend on the poses alone
         hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D);
-        hipLaunchKernelGGL(kf_set_kernel, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, D, kp.kf_frame, kp.evicted, set_flags);
+        hipLaunchKernelGGL(kf_set_kernel<false>, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, D, kp.kf_frame, kp.evicted, set_flags, nullptr, nullptr);
     } else if (kp.policy == 0)
         hipLaunchKernelGGL(kf_sliding_kernel, dim3((d.B * n_kf + 255) / 256), dim3(256), 0, stream, d.B, n_kf, kp.kf_frame, kp.evicted);
     if (d.B > 1) hipLaunchKernelGGL(track_link_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ);
-    hipLaunchKernelGGL(track_walk_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ, G,
-                       in.d_carry_in, root, relsrc);
+    if (gate)
+        hipLaunchKernelGGL(track_walk_kernel<true>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
+                           G, in.d_carry_in, root, relsrc, (const int32_t*)kp.frame_state);
+    else
+        hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
+                           G, in.d_carry_in, root, relsrc, nullptr);
     hipLaunchKernelGGL(track_info_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, pred, succ, root, in.d_carry_in, info);
     if (in.d_carry_out && in.carry_out_frame > 0 && in.carry_out_frame < d.B)
         hipLaunchKernelGGL(track_carry_out_kernel, dim3((d.kp_cap + 255) / 256), dim3(256), 0, stream, d, in.carry_out_frame, kp2lr, pred, root, relsrc, in.d_xyz, G,
@@ -642,13 +690,13 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     if (cull) {
         hipLaunchKernelGGL(track_ends_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, succ, root, relsrc, const_cast<int2*>(ws.ends));
         hipLaunchKernelGGL(window_count_kernel<true>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist, ws);
-        hipLaunchKernelGGL(window_scan_kernel<true>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags);
+        hipLaunchKernelGGL(window_scan_kernel<true>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags, nmem);
         hipLaunchKernelGGL(window_rank_kernel<true>, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec, ws);
         hipLaunchKernelGGL(window_emit_kernel<true>, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist,
                            head_rec, d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out, ws);
     } else {
         hipLaunchKernelGGL(window_count_kernel<false>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist, ws);
-        hipLaunchKernelGGL(window_scan_kernel<false>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags);
+        hipLaunchKernelGGL(window_scan_kernel<false>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags, nmem);
         hipLaunchKernelGGL(window_rank_kernel<false>, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec, ws);
         hipLaunchKernelGGL(window_emit_kernel<false>, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist,
                            head_rec, d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out, ws);

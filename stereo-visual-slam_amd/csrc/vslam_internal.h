@@ -265,9 +265,10 @@ int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t
                             double confidence, uint8_t* scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream);
 // track_kernels.hip: BA windows of a batch of consecutive keyframes from the front end's device-resident output
 // Which keyframes a window holds (vslam_build_windows_kf_dev): policy -1 = the sliding window with no set outputs (vslam_build_windows_dev),
-// 0 = the sliding window with its sets written to kf_frame / evicted, 1 = the reference's culling (needs the extra scratch of track_scratch_bytes)
-struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evicted; };
-size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity, int policy);
+// 0 = the sliding window with its sets written to kf_frame / evicted, 1 = the reference's culling (needs the extra scratch of track_scratch_bytes).
+// gate (vslam_build_windows_gated_dev): insert_key_frame's keyframe gate on num_inliers (n_frames - 1) and T_rel, states to frame_state; policy 0 / 1.
+struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evicted; bool gate = false; const int32_t* num_inliers = nullptr; int32_t* frame_state = nullptr; };
+size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity, int policy, bool gate = false);
 // K4 = {fx, fy, cx, cy}, reproj_thr (pixels), track_rule: see Tuning::track_rule
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, uint8_t* scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,

@@ -25,7 +25,8 @@ from .trajectory import assemble_trajectory, sliding_keyframes, write_trajectory
 class KeyframePipeline:
     def __init__(self, B, device=0, anms_num=1500, n_lm=3000, n_kf=10, unique_frames=64, unique_windows=None, seed=0, verbose=False,
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
-                 lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2):
+                 lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
+                 keyframe_gate=False):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
         Inputs: ONE rendered sequence of `unique_frames` consecutive stereo keyframes, laid over the batch as a ping-pong
@@ -35,10 +36,14 @@ class KeyframePipeline:
         chunk [first, last] of an F-frame sequence (frame f shows ping-pong frame f of the SAME rendered scene on every rank).
         window_policy (ba_windows="tracks"): "sliding" -- window b = keyframes [b - n_kf + 1, b] (vslam_build_windows_dev); "reference" -- the
         keyframes Map::remove_keyframe's culling keeps (map.cpp:48-130; vslam_build_windows_kf_dev policy 1, nearest frame evicted when closer than
-        near_dist, else the farthest)."""
+        near_dist, else the farthest).
+        keyframe_gate (ba_windows="tracks"): insert_key_frame's gate (visual_odometry.cpp:353) on the pose stage's inlier counts and poses --
+        only keyframes create landmarks, record observations and enter the windows' keyframe sets (vslam_build_windows_gated_dev; window_policy
+        "sliding" evicts the oldest keyframe, "reference" culls); a non-keyframe step's window is empty.  Not available in sequence mode."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
-        self.window_policy, self.near_dist = window_policy, float(near_dist)
+        assert not keyframe_gate or (ba_windows == "tracks" and frame_range is None), "keyframe_gate needs ba_windows='tracks' and no frame_range"
+        self.window_policy, self.near_dist, self.keyframe_gate = window_policy, float(near_dist), bool(keyframe_gate)
         self.depth = depth
         self.pose = pose   # "lm": north_star motion-only LM; "ransac": the reference's cv::solvePnPRansac(..., 100, 4.0, 0.99) (visual_odometry.cpp:277)
         self.ba_windows = ba_windows
@@ -132,9 +137,11 @@ class KeyframePipeline:
             self.ba_nkf = torch.zeros(B, dtype=torch.int32, device=d)
             self.ba_build_status = torch.zeros(1, dtype=torch.int32, device=d)
             self.ba_chi2 = torch.zeros(1, dtype=torch.float64, device=d)
-            if window_policy == "reference":
+            if window_policy == "reference" or keyframe_gate:
                 self.ba_kf_frame = torch.zeros((B, n_kf), dtype=torch.int32, device=d)
                 self.ba_evicted = torch.zeros(B, dtype=torch.int32, device=d)
+            if keyframe_gate:
+                self.ba_frame_state = torch.zeros(B, dtype=torch.int32, device=d)
             tr = TracksIn()
             tr.n_frames = B; tr.kp_capacity = self.cap; tr.lr_capacity = self.cap; tr.match_capacity = self.cap; tr.pnp_capacity = self.cap
             tr.d_kps = self.d_kps.data_ptr(); tr.d_lr = self.d_lr.data_ptr(); tr.d_nlr = self.d_nlr.data_ptr(); tr.d_xyz = self.d_xyz.data_ptr()
@@ -238,6 +245,11 @@ class KeyframePipeline:
 
     def stage_build_windows(self):
         """optimize_map's graph build (optimization.cpp:127-214) + insert_key_frame's bookkeeping (visual_odometry.cpp:363-424) on the device"""
+        if self.keyframe_gate:   # (d_ninl item i = the inlier count of frame i + 1)
+            self.vo.build_windows_gated_dev(self.tracks, self.n_kf, 1 if self.window_policy == "reference" else 0, self.near_dist, self.d_ninl.data_ptr(),
+                                            self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(), self.ba_evicted.data_ptr(),
+                                            self.ba_frame_state.data_ptr(), self.ba_build_status.data_ptr())
+            return
         if self.window_policy == "reference":
             self.vo.build_windows_kf_dev(self.tracks, self.n_kf, 1, self.near_dist, self.lm_capacity, self.edge_capacity, self.ba_batch,
                                          self.ba_kf_frame.data_ptr(), self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
@@ -315,24 +327,27 @@ class KeyframePipeline:
             for k, t in (("ba_lm_off", self.ba_lm_off), ("ba_e_off", self.ba_e_off), ("ba_nkf", self.ba_nkf), ("ba_xyz", self.ba_xyz), ("ba_rel", self.ba_rel),
                          ("ba_kf", self.ba_kf), ("ba_lm", self.ba_lm), ("ba_uv", self.ba_uv), ("ba_build_status", self.ba_build_status)):
                 out[k] = t.cpu().numpy()
-            if self.window_policy == "reference":
+            if self.window_policy == "reference" or self.keyframe_gate:
                 out["ba_kf_frame"] = self.ba_kf_frame.cpu().numpy(); out["ba_evicted"] = self.ba_evicted.cpu().numpy()
             else:
                 out["ba_kf_frame"], out["ba_evicted"] = sliding_keyframes(B, self.n_kf)
+            if self.keyframe_gate:
+                out["frame_state"] = self.ba_frame_state.cpu().numpy()
         return out
 
     def trajectory(self):
         """(frame_ids, T_c_w): every frame's pose from the BA windows (ba_windows="tracks"), in the order the reference writes them -- a frame when it
         is evicted (from the last window that held it), the last window's frames at the end.  write_trajectory(path, *pipe.trajectory()) writes the
-        file KITTI evaluation reads."""
+        file KITTI evaluation reads.  With keyframe_gate, only keyframes are written, each from the last keyframe window that held it."""
         assert self.with_ba and self.ba_windows == "tracks"
         self.vo.sync()
         torch.cuda.synchronize(self.dev)
-        if self.window_policy == "reference":
+        if self.window_policy == "reference" or self.keyframe_gate:
             kf_frame, evicted = self.ba_kf_frame.cpu().numpy(), self.ba_evicted.cpu().numpy()
         else:
             kf_frame, evicted = sliding_keyframes(self.B, self.n_kf)
-        return assemble_trajectory(kf_frame, evicted, self.ba_T.cpu().numpy())
+        valid = (self.ba_frame_state.cpu().numpy() == 2) if self.keyframe_gate else None
+        return assemble_trajectory(kf_frame, evicted, self.ba_T.cpu().numpy(), window_valid=valid)
 
     def close(self):
         self.vo.close()

@@ -2,8 +2,10 @@
 
 The reference writes a keyframe's pose when Map::remove_keyframe evicts it (map.cpp:119-121, Map::write_pose :168-197) and, at the end of
 the run, the keyframes the map still holds (run_vslam.cpp:84-86).  Here a frame evicted at step b leaves window b - 1, the last window that
-held it, so its pose is window b - 1's BA result at its slot there; the frames of the last window take theirs from that window.  Pure numpy:
-the inputs are the keyframe sets of vslam_build_windows_kf_dev (or of the sliding window) and the BA-refined window poses.
+held it, so its pose is window b - 1's BA result at its slot there; the frames of the last window take theirs from that window.  With the keyframe
+gate (vslam_build_windows_gated_dev) only a keyframe step's window carries BA poses: "the last window that held it" is then the last such window
+before b, and the trajectory holds keyframes only.  Pure numpy: the inputs are the keyframe sets of vslam_build_windows_kf_dev /
+vslam_build_windows_gated_dev (or of the sliding window) and the BA-refined window poses.
 """
 import numpy as np
 
@@ -17,25 +19,33 @@ def sliding_keyframes(B, n_kf):
     return kf_frame, evicted
 
 
-def assemble_trajectory(kf_frame, evicted, ba_T):
+def assemble_trajectory(kf_frame, evicted, ba_T, window_valid=None):
     """kf_frame (B, n_kf) int: window b's frames ascending (-1 unused); evicted (B,) int: the frame evicted at step b (-1 none);
-    ba_T (B, n_kf, 7): the windows' poses (T_c_w, slot k = kf_frame[b, k]).  Returns (frame_ids, T_c_w): the frames in write order --
-    each evicted frame at its eviction, then the last window's frames ascending -- and (len(frame_ids), 7) their poses, row i for frame_ids[i]."""
+    ba_T (B, n_kf, 7): the windows' poses (T_c_w, slot k = kf_frame[b, k]); window_valid (B,) bool or None (every window): whether window b
+    carries BA poses (the gate's keyframe steps).  Returns (frame_ids, T_c_w): the frames in write order -- each evicted frame at its eviction,
+    from the last valid window before it, then the last valid window's frames ascending -- and (len(frame_ids), 7) their poses, row i for
+    frame_ids[i]."""
     kf_frame = np.asarray(kf_frame); evicted = np.asarray(evicted); ba_T = np.asarray(ba_T, np.float64)
     B = kf_frame.shape[0]
+    valid = np.ones(B, bool) if window_valid is None else np.asarray(window_valid, bool)
     ids, poses = [], []
+    last = -1   # the last valid window before step b
     for b in range(1, B):
+        if valid[b - 1]:
+            last = b - 1
         e = int(evicted[b])
         if e < 0:
             continue
-        slot = np.flatnonzero(kf_frame[b - 1] == e)
+        slot = np.flatnonzero(kf_frame[last] == e) if last >= 0 else []
         if len(slot) != 1:
-            raise ValueError("frame %d evicted at step %d is not in window %d" % (e, b, b - 1))
-        ids.append(e); poses.append(ba_T[b - 1, int(slot[0])])
-    if B > 0:
-        for k, f in enumerate(kf_frame[B - 1]):
+            raise ValueError("frame %d evicted at step %d is not in window %d" % (e, b, last))
+        ids.append(e); poses.append(ba_T[last, int(slot[0])])
+    if B > 0 and valid[B - 1]:
+        last = B - 1
+    if last >= 0:
+        for k, f in enumerate(kf_frame[last]):
             if f >= 0:
-                ids.append(int(f)); poses.append(ba_T[B - 1, k])
+                ids.append(int(f)); poses.append(ba_T[last, k])
     return np.array(ids, np.int64), (np.stack(poses) if poses else np.zeros((0, 7)))
 
 
