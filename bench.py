@@ -13,9 +13,12 @@ RCCL all-gather of the per-keyframe poses (56 B each) once per step.
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment runs itself again in a child torch.distributed.run with N ranks
 (one per GPU, rendezvous on 127.0.0.1); under a launcher, --gpus must equal WORLD_SIZE.  It refuses to run on fewer GPUs.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, timed live with HIP events on
-the launch stream through the library's stage profiler) and `cpu_baseline` (the CPU oracle -- a "port", the reference
-itself is unbuildable here -- timed on this host, rank 0 at N=1, on a bounded sample of the same workload).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it sets up, warms up, times the steps and
+prints the contract fields.  `--full` also runs every other measurement and check after the timed steps: `roofline`
+(dominant kernel, timed live with HIP events on the launch stream through the library's stage profiler), `cpu_baseline`
+(the CPU oracle -- a "port", the reference itself is unbuildable here -- timed on this host, rank 0 at N=1, on a bounded
+sample of the same workload), the one-batch-in-flight, plain-BA-schedule and host-input figures, the in-flight overlap and
+bit-identity check, and the extra configurations (reference stages, config-4 BA shape, the C++ drop-in).
 
 `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (dump_step_outputs); the inputs are rendered from fixed
 seeds, so two builds run with the same arguments can be compared output for output.
@@ -364,6 +367,49 @@ def usable_cores():
         except Exception:
             continue
     return max(1, min(n, 128))
+
+
+_SCENES = {}   # (n_frames, seed) -> (trajectory, Scene), per render worker process
+
+
+def _render_lr(job):
+    """SequenceRenderer's pool worker: frames `idx` of the (n_frames, seed) sequence as synth.stereo_sequence renders them, left and right image
+    only (stereo_sequence also returns a float64 depth map, 3.7 MB a frame that no pipeline reads)"""
+    from stereo_visual_slam_amd import synth
+    n_frames, seed, idx = job
+    if (n_frames, seed) not in _SCENES:
+        _SCENES[(n_frames, seed)] = synth._sequence_scene(n_frames, seed)
+    traj, sc = _SCENES[(n_frames, seed)]
+    return [(seed, i, sc.render(traj[i])[0], sc.render(traj[i], x_offset=synth.BASELINE)[0]) for i in idx]
+
+
+class SequenceRenderer:
+    """the rendered sequences of several pipelines (one per seed, n_frames each), all frames in ONE pool of spawned worker processes that starts at
+    once and is collected by get(): the frames are synth.stereo_sequence(n_frames, seed)'s, bit for bit, with depth None"""
+
+    def __init__(self, n_frames, seeds, workers):
+        self.n_frames, self.seeds = n_frames, list(seeds)
+        n_jobs = min(n_frames, 4 * max(workers, 1))   # per sequence; strided frames, as stereo_sequence deals them out
+        self.jobs = [(n_frames, s, list(range(k, n_frames, n_jobs))) for s in self.seeds for k in range(n_jobs)]
+        self.pool = self.pending = None
+        if workers > 1:
+            import multiprocessing as mp
+            self.pool = mp.get_context("spawn").Pool(min(workers, len(self.jobs)))
+            self.pending = self.pool.map_async(_render_lr, self.jobs, chunksize=1)
+
+    def get(self):
+        from stereo_visual_slam_amd import synth
+        try:
+            parts = self.pending.get() if self.pool is not None else [_render_lr(j) for j in self.jobs]
+        finally:
+            if self.pool is not None:
+                self.pool.terminate(); self.pool = None
+        trajs = {s: synth.trajectory(self.n_frames, s) for s in self.seeds}
+        seqs = {s: [None] * self.n_frames for s in self.seeds}
+        for part in parts:
+            for s, i, L, R in part:
+                seqs[s][i] = (L, R, trajs[s][i], None)
+        return [seqs[s] for s in self.seeds]
 
 
 def cpu_baseline_tracks(pipe, out, anms_num, n_single=24, per_core=2):
@@ -839,10 +885,15 @@ def main():
     ap.add_argument("--landmarks", type=int, default=3000)
     ap.add_argument("--unique-frames", type=int, default=0, help="rendered stereo keyframes per pipeline (one sequence, laid over the batch as a ping-pong); 0 = the batch size: "
                                                                   "every keyframe of a batch is a different rendered frame, and every pipeline in flight renders its own sequence")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check (stage profiler and roofline, one batch in flight, plain "
+                         "BA schedule, in-flight overlap and bit-identity, host inputs, window statistics, reference stages, config-4 BA shape, C++ drop-in, "
+                         "CPU baseline); without it the run sets up, warms up, times the steps and prints the headline line.  The --no-* options below "
+                         "and --inputs select among these extras")
     ap.add_argument("--no-config4-step", action="store_true", help="skip the extra timed steps with canned config-4-shaped BA windows (`value_config4_windows`)")
     ap.add_argument("--no-live-dropin", action="store_true", help="skip the C++ host driver run (host/run_vslam on 50 rendered pairs: the drop-in's own frames/s)")
     ap.add_argument("--inputs", choices=["resident", "host"], default="host",
-                    help="host: additionally time the same steps with the images arriving from pinned host memory (ring of 2 batches, "
+                    help="host (with --full): additionally time the same steps with the images arriving from pinned host memory (ring of 2 batches, "
                          "hipMemcpyAsync on a copy stream overlapped with the previous step) and report it under `inputs_from_host`; "
                          "the headline `value` is always the HBM-resident one")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -854,7 +905,7 @@ def main():
                          "keyframes [b-9, b] of the batch); synthetic: B canned windows of the BASELINE config-4 shape (10 KF x --landmarks)")
     ap.add_argument("--ba-plain-schedule", action="store_true",
                     help="run all three optimize_map passes for every window (three launches) instead of continuing a pass that flags nothing new "
-                         "(vslam_set_tuning ba_adaptive = 0); the default run reports this figure beside the headline")
+                         "(vslam_set_tuning ba_adaptive = 0); --full reports this figure beside the headline")
     ap.add_argument("--no-plain-schedule", action="store_true", help="skip the extra timed region with the plain BA schedule (profiling runs: it would mix its launches into the counters)")
     ap.add_argument("--no-config4", action="store_true", help="skip the extra BA-only measurement on the config-4 shape")
     ap.add_argument("--pose", choices=["lm", "ransac"], default="lm",
@@ -895,6 +946,19 @@ def main():
         raise SystemExit("bench.py needs a GPU: the hot path is HIP-only (no CPU fallback)")
     if torch.cuda.device_count() < world:
         raise SystemExit("bench.py: %d ranks but only %d GPU(s) visible" % (world, torch.cuda.device_count()))
+    host_cores = usable_cores()   # (affinity cut by the cgroup quota: a box that shows 256 CPUs may grant 16)
+    render_workers = max(1, min(host_cores // max(world, 1), 32)) if args.render_workers < 0 else args.render_workers
+    B = args.batch
+    seq_mode = args.sequence > 0
+    if args.unique_frames <= 0:
+        args.unique_frames = args.sequence if seq_mode else B
+    n_flight = 1 if seq_mode else max(1, args.in_flight)   # (sequence mode: a step is one pass over THE sequence; kept at one pass in flight)
+    # throughput mode: the frames of every pipeline in flight are rendered up front in one pool, while the rest of the setup runs (the pipelines'
+    # own rendering would run one pool per pipeline, one after the other).  Canned BA windows are seeded per pipeline, so that mode keeps it.
+    renderer = None
+    if not seq_mode and (args.no_ba or args.ba_windows != "synthetic"):
+        n_u = max(2, min(args.unique_frames, B)) if B > 1 else 1     # (as KeyframePipeline sizes its sequence)
+        renderer = SequenceRenderer(n_u, [1000 * rank + 7919 * i for i in range(n_flight)], render_workers)
     dist = None
     if world > 1:
         import torch.distributed as dist
@@ -902,16 +966,9 @@ def main():
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
         assert dist.get_world_size() == args.gpus
-    host_cores = usable_cores()   # (affinity cut by the cgroup quota: a box that shows 256 CPUs may grant 16)
-    render_workers = max(1, min(host_cores // max(world, 1), 32)) if args.render_workers < 0 else args.render_workers
 
     from stereo_visual_slam_amd.pipeline import KeyframePipeline, PipelineRing
     from stereo_visual_slam_amd import sharding
-    B = args.batch
-    seq_mode = args.sequence > 0
-    if args.unique_frames <= 0:
-        args.unique_frames = args.sequence if seq_mode else B
-    n_flight = 1 if seq_mode else max(1, args.in_flight)   # (sequence mode: a step is one pass over THE sequence; kept at one pass in flight)
     ba_windows = args.ba_windows  # (the BA results are not fed back into the gathered trajectory in either mode)
     if seq_mode:  # config 5: this rank's contiguous chunk of ONE sequence, plus its halo: the frame before it for the pose stage, nine frames when the BA
                   # windows are built from the tracks (window b = keyframes [b - 9, b]: with them, and the tracks carried across the chunk boundary, a
@@ -925,9 +982,9 @@ def main():
                             with_ba=not args.no_ba, depth=args.depth, unique_frames=args.unique_frames, frame_range=(h_lo, hi, args.sequence),
                             render_workers=render_workers, ba_windows=ba_windows, pose=args.pose)
     else:
-        ring = PipelineRing(n_flight, B, distinct=True, device=local, anms_num=args.anms, n_lm=args.landmarks, seed=1000 * rank, verbose=args.verbose and rank == 0,
-                            with_ba=not args.no_ba, depth=args.depth, unique_frames=args.unique_frames, render_workers=render_workers,
-                            ba_windows=ba_windows, pose=args.pose)
+        ring = PipelineRing(n_flight, B, distinct=True, sequences=renderer.get() if renderer else None, device=local, anms_num=args.anms, n_lm=args.landmarks,
+                            seed=1000 * rank, verbose=args.verbose and rank == 0, with_ba=not args.no_ba, depth=args.depth, unique_frames=args.unique_frames,
+                            render_workers=render_workers, ba_windows=ba_windows, pose=args.pose)
     pipe = ring.pipes[0]
     dev = pipe.dev
     chained = [None]
@@ -961,8 +1018,10 @@ def main():
     for _ in range(args.warmup):
         one_step()
     torch.cuda.synchronize(dev)
-    copy_probe = pipe.vo.hbm_copy_probe_best(1 << 30, 5) if rank == 0 else {"gbs": 0.0}
-    copy_gbs = copy_probe["gbs"]
+    copy_probe = None
+    if args.full:
+        copy_probe = pipe.vo.hbm_copy_probe_best(1 << 30, 5) if rank == 0 else {"gbs": 0.0}
+    copy_gbs = copy_probe["gbs"] if copy_probe else 0.0
 
     def timed_region(step_fn):
         """EXACTLY `steps` steps between barrier + synchronize brackets; max over ranks"""
@@ -989,55 +1048,52 @@ def main():
     if args.dump_outputs and rank == 0:   # (the last timed step ran on pipeline (k - 1) mod P; the later regions overwrite its buffers)
         dumped = dump_step_outputs(ring.pipes[(ring.k - 1) % len(ring)], args.dump_outputs, chained[0] if seq_mode else None)
     one_step_serial = lambda: one_step(serial=True)
-    serial_s = timed_region(one_step_serial) if n_flight > 1 else None   # the same steps with ONE batch in flight (the figure of the earlier rounds)
-    plain_s = None
-    if pipe.with_ba and not args.ba_plain_schedule and not args.no_plain_schedule:   # ... and with the plain BA schedule (every pass for every window: the schedule of the earlier rounds)
-        for p_ in ring.pipes:
-            p_.vo.set_tuning(ba_adaptive=0)
-        one_step(); one_step()
-        plain_s = timed_region(one_step)
-        for p_ in ring.pipes:
-            p_.vo.set_tuning(ba_adaptive=-1)
-        one_step(); one_step()    # (the state every later measurement sees is the default schedule's again)
-    # ... and one extra, untimed-for-the-headline repeat of the same `steps` steps WITH it, one batch in flight: per-kernel durations from HIP events
-    # on the launch stream (with two batches in flight the kernels of both share the CUs and an event bracket measures the mix)
-    pipe.vo.profile_enable(True)
-    pipe.vo.profile_read()
-    profiled_s = timed_region(one_step_serial)
-    prof = pipe.vo.profile_read()
-    pipe.vo.profile_enable(False)
-    n_prof_steps = args.steps
-    # ... and the attribution of the HEADLINE configuration: the same steps with all pipelines in flight and every pipeline's brackets on ONE time
-    # axis (vslam_profile_intervals): how much of the busy span has two or more kernel families running, and the sum of their durations over the span
-    overlap = None
-    if n_flight > 1 and world == 1:
-        try:
-            overlap = inflight_overlap(ring, args, timed_region, one_step)
-        except Exception as e:
-            overlap = {"error": repr(e)}
-    # the pipelines in flight are handed DIFFERENT frames; that sharing the chip changes nobody's bits is checked by stepping each pipeline once more
-    # alone and comparing with what it produced in flight
-    flight_same = None
-    if n_flight > 1 and world == 1 and not seq_mode:
-        keys = ["kps", "desc", "lr", "f2f", "Tpnp", "inl"] + (["ba_T", "ba_inl"] if pipe.with_ba else [])
-        one_step(); one_step()
-        torch.cuda.synchronize(dev)
-        inflight_out = [p_.download() for p_ in ring.pipes]
-        flight_same = True
-        for p_, o1 in zip(ring.pipes, inflight_out):
-            p_.step(); torch.cuda.synchronize(dev)
-            o2 = p_.download()
-            flight_same = flight_same and all(np.array_equal(o1[k_], o2[k_]) for k_ in keys)
-            del o2
-        del inflight_out
-        if not flight_same:
-            raise SystemExit("bench invalid: a pipeline produced different results in flight beside another one than alone, on the same inputs")
-    host_inputs = None
-    if args.inputs == "host" and not seq_mode and world == 1:
-        try:
-            host_inputs = host_input_region(ring, args, timed_region, torch)
-        except Exception as e:  # the extra measurement must never cost the headline
-            host_inputs = {"error": repr(e)}
+    serial_s = plain_s = profiled_s = prof = overlap = flight_same = host_inputs = None
+    if args.full:
+        serial_s = timed_region(one_step_serial) if n_flight > 1 else None   # the same steps with ONE batch in flight (the figure of the earlier rounds)
+        if pipe.with_ba and not args.ba_plain_schedule and not args.no_plain_schedule:   # ... and with the plain BA schedule (every pass for every window: the schedule of the earlier rounds)
+            for p_ in ring.pipes:
+                p_.vo.set_tuning(ba_adaptive=0)
+            one_step(); one_step()
+            plain_s = timed_region(one_step)
+            for p_ in ring.pipes:
+                p_.vo.set_tuning(ba_adaptive=-1)
+            one_step(); one_step()    # (the state every later measurement sees is the default schedule's again)
+        # ... and one extra, untimed-for-the-headline repeat of the same `steps` steps WITH it, one batch in flight: per-kernel durations from HIP events
+        # on the launch stream (with two batches in flight the kernels of both share the CUs and an event bracket measures the mix)
+        pipe.vo.profile_enable(True)
+        pipe.vo.profile_read()
+        profiled_s = timed_region(one_step_serial)
+        prof = pipe.vo.profile_read()
+        pipe.vo.profile_enable(False)
+        # ... and the attribution of the HEADLINE configuration: the same steps with all pipelines in flight and every pipeline's brackets on ONE time
+        # axis (vslam_profile_intervals): how much of the busy span has two or more kernel families running, and the sum of their durations over the span
+        if n_flight > 1 and world == 1:
+            try:
+                overlap = inflight_overlap(ring, args, timed_region, one_step)
+            except Exception as e:
+                overlap = {"error": repr(e)}
+        # the pipelines in flight are handed DIFFERENT frames; that sharing the chip changes nobody's bits is checked by stepping each pipeline once more
+        # alone and comparing with what it produced in flight
+        if n_flight > 1 and world == 1 and not seq_mode:
+            keys = ["kps", "desc", "lr", "f2f", "Tpnp", "inl"] + (["ba_T", "ba_inl"] if pipe.with_ba else [])
+            one_step(); one_step()
+            torch.cuda.synchronize(dev)
+            inflight_out = [p_.download() for p_ in ring.pipes]
+            flight_same = True
+            for p_, o1 in zip(ring.pipes, inflight_out):
+                p_.step(); torch.cuda.synchronize(dev)
+                o2 = p_.download()
+                flight_same = flight_same and all(np.array_equal(o1[k_], o2[k_]) for k_ in keys)
+                del o2
+            del inflight_out
+            if not flight_same:
+                raise SystemExit("bench invalid: a pipeline produced different results in flight beside another one than alone, on the same inputs")
+        if args.inputs == "host" and not seq_mode and world == 1:
+            try:
+                host_inputs = host_input_region(ring, args, timed_region, torch)
+            except Exception as e:  # the extra measurement must never cost the headline
+                host_inputs = {"error": repr(e)}
     elapsed = float(np.median(rep_s))
     # a step that overflowed an ORB capacity or whose BA windows were rejected must not count as processed keyframes
     n_img = pipe.B if args.depth == "sgbm" else 2 * pipe.B
@@ -1049,97 +1105,15 @@ def main():
         raise SystemExit("bench invalid: %d images overflowed an ORB capacity, %d BA windows were rejected, window builder status %d" % (orb_bad, ba_bad, build_bad))
 
     if rank == 0:
-        out = pipe.download()
-        pipe.ba_passes = pipe.vo.ba_schedule_passes(n_ba_windows) if pipe.with_ba else None
-        other_seqs = [p_.h_seq for p_ in ring.pipes[1:]]
-        for p_ in ring.pipes[1:]:
-            p_.close()
-        pipe.ba_shape = None
-        win_stats = None
-        if pipe.with_ba and pipe.ba_windows == "tracks":
-            nl_w, ne_w = np.diff(out["ba_lm_off"]), np.diff(out["ba_e_off"])
-            pipe.ba_shape = (ne_w[pipe.B - n_ba_windows:], nl_w[pipe.B - n_ba_windows:], out["ba_nkf"][pipe.B - n_ba_windows:])
-            n_l = int(out["ba_lm_off"][-1])
-            win_stats = {"landmarks_per_window_mean": float(nl_w.mean()), "landmarks_per_window_max": int(nl_w.max()), "edges_per_window_mean": float(ne_w.mean()),
-                         "edges_per_window_max": int(ne_w.max()), "reliable_fraction": float(out["ba_rel"][:n_l].mean()) if n_l else 0.0,
-                         "keyframes_per_window": "1..%d for the first %d windows (the growing map), then %d" % (pipe.n_kf, pipe.n_kf - 1, pipe.n_kf),
-                         "full_windows": int((out["ba_nkf"] == pipe.n_kf).sum()), "builder_status": build_bad,
-                         "observations_per_landmark": float(ne_w.sum() / max(nl_w.sum(), 1))}
-            # [r6] the track rule (vslam_build_windows_dev, Tuning::track_rule): the step runs the reference's -- a frame-to-frame match continues a track whenever
-            # its last-frame keypoint is a feature (visual_odometry.cpp:568-599) -- and, outside the timed region, the same front-end results are built once
-            # more under the convention of rounds 4-5 (only keypoints with a depth of their own pass a track on) for the before / after figures
-            if not seq_mode:
-                try:
-                    pipe.vo.set_tuning(track_rule=0)
-                    pipe.stage_build_windows(); pipe.vo.sync(); torch.cuda.synchronize(dev)
-                    lo_ = pipe.ba_lm_off.cpu().numpy(); eo_ = pipe.ba_e_off.cpu().numpy()
-                    pipe.vo.set_tuning(track_rule=-1)
-                    pipe.stage_build_windows(); pipe.vo.sync(); torch.cuda.synchronize(dev)
-                    win_stats["track_rule"] = {
-                        "this_run": "1: the reference's tracking() rule (every feature of the last frame is a query; a feature without its own depth is judged by the pose "
-                                    "stage's 4 px rule on its landmark's map position through the chained pose)",
-                        "pose_inputs_per_frame": float(out["pn"][:max(B - 1, 1)].mean()),
-                        "pose_inputs_note": "inputs of the pose stage = frame-to-frame matches whose last-frame keypoint owns a depth (triangulated in that frame); the same under both rules",
-                        "observations_per_landmark": win_stats["observations_per_landmark"],
-                        "round5_rule": {"landmarks_per_window_mean": float(np.diff(lo_).mean()), "edges_per_window_mean": float(np.diff(eo_).mean()),
-                                        "observations_per_landmark": float(eo_[-1] / max(lo_[-1], 1))}}
-                except Exception as e:
-                    win_stats["track_rule"] = {"error": repr(e)}
         units = args.sequence if seq_mode else world * B   # keyframes all ranks processed per step (halo frames are not counted twice)
         value = units * args.steps / elapsed
-        kern = sorted(prof.items(), key=lambda kv: -kv[1][0])
-        dom, (dom_ms, dom_launches, dom_calls) = kern[0]
-        alg, formula = algorithmic_bytes(dom, pipe, args.anms)
-        alg_plain = None
-        if dom == "lm_window_kernel" and getattr(pipe, "ba_passes", None) is not None:   # the same formula over the plain schedule's 30 linearisations per window
-            keep = pipe.ba_passes; pipe.ba_passes = None
-            alg_plain = algorithmic_bytes(dom, pipe, args.anms)[0]
-            pipe.ba_passes = keep
-        if args.depth == "sgbm" and any(k.startswith("sgbm_") for k, _ in kern):
-            # --depth sgbm: the roofline line is the SGBM FAMILY (one bracket = one vslam_disparity_map_dev call = B pairs): compulsory bytes of a
-            # fully fused design = the (w - 96) x h x 96 x i16 cost volume once + both images in + the f32 map out, per pair
-            fam = [(k, v) for k, v in kern if k.startswith("sgbm_")]
-            dom = "sgbm_* (family: %s)" % ", ".join(k for k, _ in fam)
-            dom_ms = sum(v[0] for _, v in fam); dom_launches = sum(v[1] for _, v in fam); dom_calls = n_prof_steps
-            cv = (pipe.w - 96) * pipe.h * 96 * 2
-            alg = B * (cv + 2 * pipe.w * pipe.h + 4 * pipe.w * pipe.h)
-            formula = "B pairs x ((w-96)*h*96*2 B cost volume once + 2*w*h B images in + 4*w*h B f32 disparity out)"
-        per_bracket_s = dom_ms / 1e3 / max(dom_calls, 1)
-        achieved = alg / per_bracket_s / 1e9 if per_bracket_s > 0 else 0.0
-        # `traffic`: HBM bytes per launch set from rocprofv3 PMC passes made offline (tools/profile_round.sh).  Valid only for the same kernel
-        # SOURCES (sha256 recorded in the file), the same kernel, batch and window kind; otherwise null with the reason in traffic_source.
-        sg = args.depth == "sgbm" and dom.startswith("sgbm_*")
-        tname = "traffic_sgbm.json" if sg else ("traffic_tracks.json" if (pipe.with_ba and pipe.ba_windows == "tracks") else "traffic.json")
-        traffic = None
-        tj, traffic_src = load_counter_json(tname)
-        if tj is not None:
-            if (sg and tj.get("batch") == B) or (tj.get("kernel") == dom and tj.get("batch") == B):
-                traffic = int(tj["hbm_bytes_per_launch_set"])
-            else:
-                traffic_src = "profiles/%s was measured for kernel %s at batch %s, not %s at %d" % (tname, tj.get("kernel"), tj.get("batch"), dom, B)
-        nt = max(B - 1, 1)
-        # the roofline line is named after the kernels that ran inside the dominant stage bracket (the BA schedule's bracket keeps the family name
-        # `lm_window_kernel` of rounds 1-4): vslam_ba_deferred_dev says which windows ba_resident_kernel took
-        dom_kernels = dom; res_deferred = None
-        if dom == "lm_window_kernel" and pipe.with_ba:
-            try:
-                nd = int(pipe.vo.ba_deferred(n_ba_windows).sum())
-            except Exception:
-                nd = n_ba_windows
-            if nd == 0:
-                dom_kernels = "ba_resident_kernel+pose_only_wave_kernel"
-            elif nd == n_ba_windows:
-                dom_kernels = "lm_window_kernel+pose_only_wave_kernel"
-            else:
-                dom_kernels = "ba_resident_kernel+lm_window_kernel+pose_only_wave_kernel"
-            res_deferred = nd
         pose_txt = ("motion-only LM pose (10 its)" if args.pose == "lm" else
                     "solvePnPRansac(100, 4.0, 0.99) pose [the reference's own pose stage; not the BASELINE metric]")
         win_txt = ("BA windows built on the device from this step's own tracks (window b = keyframes [b-9, b]: poses = chained pose-stage estimates, "
                    "landmarks / observations as VO::insert_key_frame records them)" if pipe.ba_windows == "tracks" else
                    "%d canned synthetic windows of 10 KF x %d landmarks (config-4 shape; NOT fed by the front end of the step)" % (pipe.unique_windows, args.landmarks))
         workload = ("stereo keyframe hot path, north_star stages (NOT the reference's SGBM depth / solvePnPRansac pose, which are built and measured "
-                    "under `reference_pipeline`; --depth sgbm / --pose ransac select them here): ORB(3000)->ANMS(%d)->rBRIEF on L+R 1241x376, L/R + "
+                    "under `reference_pipeline` with --full; --depth sgbm / --pose ransac select them here): ORB(3000)->ANMS(%d)->rBRIEF on L+R 1241x376, L/R + "
                     "frame-to-frame BF-Hamming cross-check match, epipolar-gated DLT triangulation, %s, %s, local BA schedule 5+5+10 LM + 10 pose-only "
                     "per window%s%s" % (args.anms, pose_txt, win_txt, "" if not args.no_ba else " [BA disabled]",
                                         " [depth stage swapped for the reference's own: SGBM disparity + find_3d; not the BASELINE metric]" if args.depth == "sgbm" else ""))
@@ -1160,135 +1134,230 @@ def main():
                        "parallelism": ("one %d-frame sequence in %d contiguous chunks with a %d-frame halo, relative poses gathered and chained, track state carried across the "
                                        "chunk boundaries rank by rank, BA on the windows of the owned frames (the unsharded run's windows bit for bit)" % (
                                            args.sequence, world, sharding.WINDOW_HALO if seq_exact_ba else 1))
-                                      if seq_mode else "%d independent replicas, sharded keyframes" % world},
+                                      if seq_mode else "%d independent replicas, sharded keyframes" % world,
+                       "full": bool(args.full)},
             "timing": {"repeats": len(rep_s), "ms_per_step_each": [round(1e3 * x / args.steps, 4) for x in rep_s], "reported": "median",
                        "spread_pct": round(100.0 * (max(rep_s) - min(rep_s)) / elapsed, 2),
                        "in_flight": {"batches": len(ring),
                                      "how": "step k is queued on pipeline k mod %d (own context, HIP stream and buffers) without waiting for step k - 1; every step is "
-                                            "the whole hot path over one batch of %d keyframes; the timed region ends with a device-wide synchronize" % (len(ring), B),
-                                     "one_batch_in_flight": None if serial_s is None else {"ms_per_step": round(1e3 * serial_s / args.steps, 4),
-                                                                                            "value": round(units_per_step(args, seq_mode, world, B) * args.steps / serial_s, 3)},
-                                     "results_identical_in_flight_and_alone": flight_same,
-                                     "overlap": overlap},
-                       "ba_schedule": None if not pipe.with_ba else dict(
-                           schedule_stats(pipe.ba_passes), mode="plain (--ba-plain-schedule)" if args.ba_plain_schedule else "adaptive (default)",
-                           plain_schedule=None if plain_s is None else {"ms_per_step": round(1e3 * plain_s / args.steps, 4),
-                                                                         "value": round(units_per_step(args, seq_mode, world, B) * args.steps / plain_s, 3),
-                                                                         "how": "the same steps, same batches in flight, with every optimize_map pass run for every window "
-                                                                                "(three launches; vslam_set_tuning ba_adaptive = 0)"}),
-                       "stage_profiler": "off in the timed repeats; on in one extra repeat of the same %d steps with ONE batch in flight (%.4f ms/step) that feeds "
-                                         "`roofline` and `kernels_ms_per_step`" % (args.steps, 1e3 * profiled_s / args.steps)},
-            "roofline": {"bound": "hbm", "kernel": dom_kernels, "stage_family": dom,
-                         "windows_left_to_lm_window_kernel": (res_deferred if dom == "lm_window_kernel" and pipe.with_ba else None),
-                         "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src,
-                         "copy_ceiling_gbs": round(copy_gbs, 1), "copy_probe": copy_probe, "copy_ceiling_guide_gbs": 6290.0, "frac_of_copy_ceiling": round(achieved / copy_gbs, 6) if copy_gbs > 0 else None,
-                         "algorithmic_bytes_per_launch_set": int(alg), "formula": formula,
-                         "plain_schedule_equivalent": None if alg_plain is None or per_bracket_s <= 0 else {
-                             "algorithmic_bytes_per_launch_set": int(alg_plain), "achieved": round(alg_plain / per_bracket_s / 1e9, 3),
-                             "frac": round(alg_plain / per_bracket_s / 1e9 / HBM_PEAK_GBS, 6),
-                             "note": "the bytes of the 30 linearisations per window the reference's schedule performs, over the same time: the adaptive schedule delivers "
-                                     "that result with fewer of them; `achieved` / `frac` above count only what was executed"},
-                         "avg_ms_per_launch_set": round(1e3 * per_bracket_s, 4), "kernel_launches_per_set": dom_launches // max(dom_calls, 1),
-                         "launch_set": (("one BA schedule = 3 x lm_window_kernel (optimize_map, 5 + 5 + 10 iterations) + 1 x pose_only_wave_kernel (10 iterations)"
-                                         if args.ba_plain_schedule else
-                                         "one BA schedule (stage-profiler family `lm_window_kernel`) = 1 x ba_resident_kernel (optimize_map passes 5 + 5 + 10 back to back for every "
-                                         "window that fits its LDS budget: all of them here; a pass that flags nothing new is continued as the last one) + 1 x lm_window_kernel (the "
-                                         "windows ba_resident_kernel deferred: none here, its workgroups return at once) + 1 x pose_only_wave_kernel (10 iterations)")
-                                        if dom == "lm_window_kernel" else "one stage bracket")},
-            "kernels_ms_per_step": {k: round(v[0] / n_prof_steps, 4) for k, v in kern},
-            "other_rooflines": other_rooflines(prof, pipe, args, n_prof_steps, copy_gbs),
-            "stats": {"keypoints_per_image": float(out["cnt"].mean()), "lr_matches": float(out["nlr"].mean()), "lr_matches_min": int(out["nlr"].min()),
-                      "f2f_matches": float(out["nf2f"][:nt].mean()), "pnp_points": float(out["pn"][:nt].mean()), "pnp_points_min": int(out["pn"][:nt].min()),
-                      "pnp_inliers": float(out["ninl"][:nt].mean()), "pnp_inliers_min": int(out["ninl"][:nt].min()),
-                      "orb_status_nonzero": orb_bad, "ba_status_nonzero": ba_bad},
+                                            "the whole hot path over one batch of %d keyframes; the timed region ends with a device-wide synchronize" % (len(ring), B)}},
+            "stats": {"orb_status_nonzero": orb_bad, "ba_status_nonzero": ba_bad},
         }
-        if win_stats is not None:
-            res["stats"]["ba_windows"] = win_stats
         if dumped is not None:
             res["dump_outputs"] = dumped
-        if host_inputs is not None:
-            res["inputs_from_host"] = host_inputs
         if seq_mode and chained[0] is not None:
             res["trajectory"] = {"frames": int(len(chained[0])), "final_position": [float(x) for x in sharding.camera_centre(chained[0][-1])]}
-        extras_ok = world == 1 and not args.no_ba and args.depth == "match" and args.pose == "lm" and not seq_mode
-        if extras_ok and pipe.ba_windows == "tracks":
-            pipe.close()    # (host arrays stay; the GPU memory goes back before the next pipeline is built)
-            if not args.no_reference_pipeline:
-                try:
-                    res["reference_pipeline"] = reference_pipeline_measure(args, local, torch, pipe.h_seq)
-                except Exception as e:  # an extra must never cost the headline
-                    res["reference_pipeline"] = {"error": repr(e)}
-            if not args.no_config4:
-                try:
-                    res["ba_config4"] = ba_config4_measure(args, local, torch)
-                except Exception as e:
-                    res["ba_config4"] = {"error": repr(e)}
-            if not args.no_config4_step:
-                try:
-                    res["value_config4_windows"] = config4_step_measure(args, local, torch, [pipe.h_seq] + other_seqs)
-                except Exception as e:
-                    res["value_config4_windows"] = {"error": repr(e)}
-            if not args.no_live_dropin:
-                try:
-                    res["live_dropin"] = live_dropin_measure(with_cpu=not args.no_cpu_baseline)
-                except Exception as e:
-                    res["live_dropin"] = {"error": repr(e)}
-                try:   # real KITTI pairs, when the box has them (KITTI_ROOT); otherwise a one-line "not available"
-                    res["kitti_seq00"] = kitti_measure()
-                except Exception as e:
-                    res["kitti_seq00"] = {"available": None, "error": repr(e)}
-        if extras_ok and not args.no_cpu_baseline:
-            res["cpu_baseline"], res["pose_rmse_vs_oracle"] = (cpu_baseline_tracks if pipe.ba_windows == "tracks" else cpu_baseline)(pipe, out, args.anms)
-            info, have_cv2 = host_info()
-            res["cpu_baseline"]["host"] = info
-            if have_cv2:
-                try:   # ... and, the day a box has OpenCV, the oracle is compared with it (tests/test_reference_libs_pin.py) and the outcome recorded here
-                    sys.path.insert(0, os.path.join(ROOT, "tests"))
-                    import oracle as O
-                    from stereo_visual_slam_amd import synth as S
-                    from test_reference_libs_pin import compare_all
-                    res["cpu_baseline"]["host"]["reference_libs_pin"] = compare_all(O, S, n_images=2)
-                except Exception as e:
-                    res["cpu_baseline"]["host"]["reference_libs_pin"] = "cv2 present but the comparison failed: %r" % (e,)
-                try:
-                    res["cpu_baseline"]["reference_libs_timing"] = reference_lib_timing(pipe, args.anms)
-                except Exception as e:
-                    res["cpu_baseline"]["reference_libs_timing"] = "cv2 present but failed: %r" % (e,)
-            else:
-                res["cpu_baseline"]["reference_libs_timing"] = "unavailable on this host (no cv2 / OpenCV / g2o found at run time)"
-                res["cpu_baseline"]["host"]["reference_libs_pin"] = "skipped: no cv2 on this host (tests/test_reference_libs_pin.py)"
-        # scalars of the extra measurements, repeated inside `config` (a record that keeps only the contract's keys still carries them)
-        def _g(d, *ks):
-            for k_ in ks:
-                d = d.get(k_) if isinstance(d, dict) else None
-            return d
-        # [r6] FLAT scalar keys of `config` (round 5 nested them under config.extras, which a parser that keeps scalar config keys dropped)
-        orb_fam = [r for r in res["other_rooflines"] if r.get("kernel") == "orb_* (family)"]
-        res["config"].update({
-            "one_in_flight_kfps": _g(res, "timing", "in_flight", "one_batch_in_flight", "value"),
-            "plain_ba_schedule_kfps": _g(res, "timing", "ba_schedule", "plain_schedule", "value"),
-            "overlap_share_two_or_more_kernels": _g(res, "timing", "in_flight", "overlap", "overlap_share"),
-            "sum_kernel_ms_over_span_ms": _g(res, "timing", "in_flight", "overlap", "sum_kernel_ms_over_span_ms"),
-            "inputs_from_host_kfps": _g(res, "inputs_from_host", "value"),
-            "value_config4_windows_kfps": _g(res, "value_config4_windows", "value"),
-            "reference_pipeline_kfps": _g(res, "reference_pipeline", "value"),
-            "reference_pipeline_sgbm_ms_per_pair": _g(res, "reference_pipeline", "roofline", "ms_per_pair"),
-            "ba_config4_ms_per_256": _g(res, "ba_config4", "ms_per_schedule_batch"),
-            "ba_built_windows_ms_per_schedule_batch": _g(res, "roofline", "avg_ms_per_launch_set"),
-            "orb_family_ms_per_1024_images": orb_fam[0].get("ms_per_1024_images") if orb_fam else None,
-            "orb_family_traffic_bytes_per_1024_images": orb_fam[0].get("traffic_per_1024_images") if orb_fam else None,
-            "kitti_seq00_available": _g(res, "kitti_seq00", "available"),
-            "live_dropin_fps": _g(res, "live_dropin", "gpu", "frames_per_s"),
-            "live_dropin_kfps": _g(res, "live_dropin", "gpu", "keyframes_per_s"),
-            "live_dropin_cpu_path_fps": _g(res, "live_dropin", "cpu", "frames_per_s"),
-            "pose_rmse_vs_oracle_m": _g(res, "pose_rmse_vs_oracle", "ba_translation_rmse_m"),
-        })
+        if args.full:
+            full_report(res, args, ring, pipe, local, torch, B, seq_mode, world, n_ba_windows, build_bad, serial_s, plain_s, profiled_s, prof, overlap,
+                        flight_same, host_inputs, copy_probe, copy_gbs, dev)
         print(json.dumps(res), flush=True)
     ring.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_report(res, args, ring, pipe, local, torch, B, seq_mode, world, n_ba_windows, build_bad, serial_s, plain_s, profiled_s, prof, overlap,
+                flight_same, host_inputs, copy_probe, copy_gbs, dev):
+    """--full, rank 0: what the extra repeats measured (one batch in flight, plain BA schedule, stage profiler, overlap, host inputs) and the extra
+    configurations, added to the headline line `res`"""
+    out = pipe.download()
+    pipe.ba_passes = pipe.vo.ba_schedule_passes(n_ba_windows) if pipe.with_ba else None
+    other_seqs = [p_.h_seq for p_ in ring.pipes[1:]]
+    for p_ in ring.pipes[1:]:
+        p_.close()
+    pipe.ba_shape = None
+    win_stats = None
+    if pipe.with_ba and pipe.ba_windows == "tracks":
+        nl_w, ne_w = np.diff(out["ba_lm_off"]), np.diff(out["ba_e_off"])
+        pipe.ba_shape = (ne_w[pipe.B - n_ba_windows:], nl_w[pipe.B - n_ba_windows:], out["ba_nkf"][pipe.B - n_ba_windows:])
+        n_l = int(out["ba_lm_off"][-1])
+        win_stats = {"landmarks_per_window_mean": float(nl_w.mean()), "landmarks_per_window_max": int(nl_w.max()), "edges_per_window_mean": float(ne_w.mean()),
+                     "edges_per_window_max": int(ne_w.max()), "reliable_fraction": float(out["ba_rel"][:n_l].mean()) if n_l else 0.0,
+                     "keyframes_per_window": "1..%d for the first %d windows (the growing map), then %d" % (pipe.n_kf, pipe.n_kf - 1, pipe.n_kf),
+                     "full_windows": int((out["ba_nkf"] == pipe.n_kf).sum()), "builder_status": build_bad,
+                     "observations_per_landmark": float(ne_w.sum() / max(nl_w.sum(), 1))}
+        # [r6] the track rule (vslam_build_windows_dev, Tuning::track_rule): the step runs the reference's -- a frame-to-frame match continues a track whenever
+        # its last-frame keypoint is a feature (visual_odometry.cpp:568-599) -- and, outside the timed region, the same front-end results are built once
+        # more under the convention of rounds 4-5 (only keypoints with a depth of their own pass a track on) for the before / after figures
+        if not seq_mode:
+            try:
+                pipe.vo.set_tuning(track_rule=0)
+                pipe.stage_build_windows(); pipe.vo.sync(); torch.cuda.synchronize(dev)
+                lo_ = pipe.ba_lm_off.cpu().numpy(); eo_ = pipe.ba_e_off.cpu().numpy()
+                pipe.vo.set_tuning(track_rule=-1)
+                pipe.stage_build_windows(); pipe.vo.sync(); torch.cuda.synchronize(dev)
+                win_stats["track_rule"] = {
+                    "this_run": "1: the reference's tracking() rule (every feature of the last frame is a query; a feature without its own depth is judged by the pose "
+                                "stage's 4 px rule on its landmark's map position through the chained pose)",
+                    "pose_inputs_per_frame": float(out["pn"][:max(B - 1, 1)].mean()),
+                    "pose_inputs_note": "inputs of the pose stage = frame-to-frame matches whose last-frame keypoint owns a depth (triangulated in that frame); the same under both rules",
+                    "observations_per_landmark": win_stats["observations_per_landmark"],
+                    "round5_rule": {"landmarks_per_window_mean": float(np.diff(lo_).mean()), "edges_per_window_mean": float(np.diff(eo_).mean()),
+                                    "observations_per_landmark": float(eo_[-1] / max(lo_[-1], 1))}}
+            except Exception as e:
+                win_stats["track_rule"] = {"error": repr(e)}
+    n_prof_steps = args.steps
+    kern = sorted(prof.items(), key=lambda kv: -kv[1][0])
+    dom, (dom_ms, dom_launches, dom_calls) = kern[0]
+    alg, formula = algorithmic_bytes(dom, pipe, args.anms)
+    alg_plain = None
+    if dom == "lm_window_kernel" and getattr(pipe, "ba_passes", None) is not None:   # the same formula over the plain schedule's 30 linearisations per window
+        keep = pipe.ba_passes; pipe.ba_passes = None
+        alg_plain = algorithmic_bytes(dom, pipe, args.anms)[0]
+        pipe.ba_passes = keep
+    if args.depth == "sgbm" and any(k.startswith("sgbm_") for k, _ in kern):
+        # --depth sgbm: the roofline line is the SGBM FAMILY (one bracket = one vslam_disparity_map_dev call = B pairs): compulsory bytes of a
+        # fully fused design = the (w - 96) x h x 96 x i16 cost volume once + both images in + the f32 map out, per pair (DESIGN.md section 4)
+        fam = [(k, v) for k, v in kern if k.startswith("sgbm_")]
+        dom = "sgbm_* (family: %s)" % ", ".join(k for k, _ in fam)
+        dom_ms = sum(v[0] for _, v in fam); dom_launches = sum(v[1] for _, v in fam); dom_calls = n_prof_steps
+        cv = (pipe.w - 96) * pipe.h * 96 * 2
+        alg = B * (cv + 2 * pipe.w * pipe.h + 4 * pipe.w * pipe.h)
+        formula = "B pairs x ((w-96)*h*96*2 B cost volume once + 2*w*h B images in + 4*w*h B f32 disparity out)"
+    per_bracket_s = dom_ms / 1e3 / max(dom_calls, 1)
+    achieved = alg / per_bracket_s / 1e9 if per_bracket_s > 0 else 0.0
+    # `traffic`: HBM bytes per launch set from rocprofv3 PMC passes made offline (tools/profile_round.sh).  Valid only for the same kernel
+    # SOURCES (sha256 recorded in the file), the same kernel, batch and window kind; otherwise null with the reason in traffic_source.
+    sg = args.depth == "sgbm" and dom.startswith("sgbm_*")
+    tname = "traffic_sgbm.json" if sg else ("traffic_tracks.json" if (pipe.with_ba and pipe.ba_windows == "tracks") else "traffic.json")
+    traffic = None
+    tj, traffic_src = load_counter_json(tname)
+    if tj is not None:
+        if (sg and tj.get("batch") == B) or (tj.get("kernel") == dom and tj.get("batch") == B):
+            traffic = int(tj["hbm_bytes_per_launch_set"])
+        else:
+            traffic_src = "profiles/%s was measured for kernel %s at batch %s, not %s at %d" % (tname, tj.get("kernel"), tj.get("batch"), dom, B)
+    nt = max(B - 1, 1)
+    # the roofline line is named after the kernels that ran inside the dominant stage bracket (the BA schedule's bracket keeps the family name
+    # `lm_window_kernel` of rounds 1-4): vslam_ba_deferred_dev says which windows ba_resident_kernel took
+    dom_kernels = dom; res_deferred = None
+    if dom == "lm_window_kernel" and pipe.with_ba:
+        try:
+            nd = int(pipe.vo.ba_deferred(n_ba_windows).sum())
+        except Exception:
+            nd = n_ba_windows
+        if nd == 0:
+            dom_kernels = "ba_resident_kernel+pose_only_wave_kernel"
+        elif nd == n_ba_windows:
+            dom_kernels = "lm_window_kernel+pose_only_wave_kernel"
+        else:
+            dom_kernels = "ba_resident_kernel+lm_window_kernel+pose_only_wave_kernel"
+        res_deferred = nd
+    units = args.sequence if seq_mode else world * B
+    tm = res["timing"]
+    tm["in_flight"].update({"one_batch_in_flight": None if serial_s is None else {"ms_per_step": round(1e3 * serial_s / args.steps, 4),
+                                                                                   "value": round(units * args.steps / serial_s, 3)},
+                            "results_identical_in_flight_and_alone": flight_same,
+                            "overlap": overlap})
+    tm["ba_schedule"] = None if not pipe.with_ba else dict(
+        schedule_stats(pipe.ba_passes), mode="plain (--ba-plain-schedule)" if args.ba_plain_schedule else "adaptive (default)",
+        plain_schedule=None if plain_s is None else {"ms_per_step": round(1e3 * plain_s / args.steps, 4),
+                                                      "value": round(units * args.steps / plain_s, 3),
+                                                      "how": "the same steps, same batches in flight, with every optimize_map pass run for every window "
+                                                             "(three launches; vslam_set_tuning ba_adaptive = 0)"})
+    tm["stage_profiler"] = ("off in the timed repeats; on in one extra repeat of the same %d steps with ONE batch in flight (%.4f ms/step) that feeds "
+                            "`roofline` and `kernels_ms_per_step`" % (args.steps, 1e3 * profiled_s / args.steps))
+    res["roofline"] = {"bound": "hbm", "kernel": dom_kernels, "stage_family": dom,
+                       "windows_left_to_lm_window_kernel": (res_deferred if dom == "lm_window_kernel" and pipe.with_ba else None),
+                       "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic, "traffic_source": traffic_src,
+                       "copy_ceiling_gbs": round(copy_gbs, 1), "copy_probe": copy_probe, "copy_ceiling_guide_gbs": 6290.0, "frac_of_copy_ceiling": round(achieved / copy_gbs, 6) if copy_gbs > 0 else None,
+                       "algorithmic_bytes_per_launch_set": int(alg), "formula": formula,
+                       "plain_schedule_equivalent": None if alg_plain is None or per_bracket_s <= 0 else {
+                           "algorithmic_bytes_per_launch_set": int(alg_plain), "achieved": round(alg_plain / per_bracket_s / 1e9, 3),
+                           "frac": round(alg_plain / per_bracket_s / 1e9 / HBM_PEAK_GBS, 6),
+                           "note": "the bytes of the 30 linearisations per window the reference's schedule performs, over the same time: the adaptive schedule delivers "
+                                   "that result with fewer of them; `achieved` / `frac` above count only what was executed"},
+                       "avg_ms_per_launch_set": round(1e3 * per_bracket_s, 4), "kernel_launches_per_set": dom_launches // max(dom_calls, 1),
+                       "launch_set": (("one BA schedule = 3 x lm_window_kernel (optimize_map, 5 + 5 + 10 iterations) + 1 x pose_only_wave_kernel (10 iterations)"
+                                       if args.ba_plain_schedule else
+                                       "one BA schedule (stage-profiler family `lm_window_kernel`) = 1 x ba_resident_kernel (optimize_map passes 5 + 5 + 10 back to back for every "
+                                       "window that fits its LDS budget: all of them here; a pass that flags nothing new is continued as the last one) + 1 x lm_window_kernel (the "
+                                       "windows ba_resident_kernel deferred: none here, its workgroups return at once) + 1 x pose_only_wave_kernel (10 iterations)")
+                                      if dom == "lm_window_kernel" else "one stage bracket")}
+    res["kernels_ms_per_step"] = {k: round(v[0] / n_prof_steps, 4) for k, v in kern}
+    res["other_rooflines"] = other_rooflines(prof, pipe, args, n_prof_steps, copy_gbs)
+    res["stats"].update({"keypoints_per_image": float(out["cnt"].mean()), "lr_matches": float(out["nlr"].mean()), "lr_matches_min": int(out["nlr"].min()),
+                         "f2f_matches": float(out["nf2f"][:nt].mean()), "pnp_points": float(out["pn"][:nt].mean()), "pnp_points_min": int(out["pn"][:nt].min()),
+                         "pnp_inliers": float(out["ninl"][:nt].mean()), "pnp_inliers_min": int(out["ninl"][:nt].min())})
+    if win_stats is not None:
+        res["stats"]["ba_windows"] = win_stats
+    if host_inputs is not None:
+        res["inputs_from_host"] = host_inputs
+    extras_ok = world == 1 and not args.no_ba and args.depth == "match" and args.pose == "lm" and not seq_mode
+    if extras_ok and pipe.ba_windows == "tracks":
+        pipe.close()    # (host arrays stay; the GPU memory goes back before the next pipeline is built)
+        if not args.no_reference_pipeline:
+            try:
+                res["reference_pipeline"] = reference_pipeline_measure(args, local, torch, pipe.h_seq)
+            except Exception as e:  # an extra must never cost the headline
+                res["reference_pipeline"] = {"error": repr(e)}
+        if not args.no_config4:
+            try:
+                res["ba_config4"] = ba_config4_measure(args, local, torch)
+            except Exception as e:
+                res["ba_config4"] = {"error": repr(e)}
+        if not args.no_config4_step:
+            try:
+                res["value_config4_windows"] = config4_step_measure(args, local, torch, [pipe.h_seq] + other_seqs)
+            except Exception as e:
+                res["value_config4_windows"] = {"error": repr(e)}
+        if not args.no_live_dropin:
+            try:
+                res["live_dropin"] = live_dropin_measure(with_cpu=not args.no_cpu_baseline)
+            except Exception as e:
+                res["live_dropin"] = {"error": repr(e)}
+            try:   # real KITTI pairs, when the box has them (KITTI_ROOT); otherwise a one-line "not available"
+                res["kitti_seq00"] = kitti_measure()
+            except Exception as e:
+                res["kitti_seq00"] = {"available": None, "error": repr(e)}
+    if extras_ok and not args.no_cpu_baseline:
+        res["cpu_baseline"], res["pose_rmse_vs_oracle"] = (cpu_baseline_tracks if pipe.ba_windows == "tracks" else cpu_baseline)(pipe, out, args.anms)
+        info, have_cv2 = host_info()
+        res["cpu_baseline"]["host"] = info
+        if have_cv2:
+            try:   # ... and, the day a box has OpenCV, the oracle is compared with it (tests/test_reference_libs_pin.py) and the outcome recorded here
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import oracle as O
+                from stereo_visual_slam_amd import synth as S
+                from test_reference_libs_pin import compare_all
+                res["cpu_baseline"]["host"]["reference_libs_pin"] = compare_all(O, S, n_images=2)
+            except Exception as e:
+                res["cpu_baseline"]["host"]["reference_libs_pin"] = "cv2 present but the comparison failed: %r" % (e,)
+            try:
+                res["cpu_baseline"]["reference_libs_timing"] = reference_lib_timing(pipe, args.anms)
+            except Exception as e:
+                res["cpu_baseline"]["reference_libs_timing"] = "cv2 present but failed: %r" % (e,)
+        else:
+            res["cpu_baseline"]["reference_libs_timing"] = "unavailable on this host (no cv2 / OpenCV / g2o found at run time)"
+            res["cpu_baseline"]["host"]["reference_libs_pin"] = "skipped: no cv2 on this host (tests/test_reference_libs_pin.py)"
+    # scalars of the extra measurements, repeated inside `config` (a record that keeps only the contract's keys still carries them)
+    def _g(d, *ks):
+        for k_ in ks:
+            d = d.get(k_) if isinstance(d, dict) else None
+        return d
+    # [r6] FLAT scalar keys of `config` (round 5 nested them under config.extras, which a parser that keeps scalar config keys dropped)
+    orb_fam = [r for r in res["other_rooflines"] if r.get("kernel") == "orb_* (family)"]
+    res["config"].update({
+        "one_in_flight_kfps": _g(res, "timing", "in_flight", "one_batch_in_flight", "value"),
+        "plain_ba_schedule_kfps": _g(res, "timing", "ba_schedule", "plain_schedule", "value"),
+        "overlap_share_two_or_more_kernels": _g(res, "timing", "in_flight", "overlap", "overlap_share"),
+        "sum_kernel_ms_over_span_ms": _g(res, "timing", "in_flight", "overlap", "sum_kernel_ms_over_span_ms"),
+        "inputs_from_host_kfps": _g(res, "inputs_from_host", "value"),
+        "value_config4_windows_kfps": _g(res, "value_config4_windows", "value"),
+        "reference_pipeline_kfps": _g(res, "reference_pipeline", "value"),
+        "reference_pipeline_sgbm_ms_per_pair": _g(res, "reference_pipeline", "roofline", "ms_per_pair"),
+        "ba_config4_ms_per_256": _g(res, "ba_config4", "ms_per_schedule_batch"),
+        "ba_built_windows_ms_per_schedule_batch": _g(res, "roofline", "avg_ms_per_launch_set"),
+        "orb_family_ms_per_1024_images": orb_fam[0].get("ms_per_1024_images") if orb_fam else None,
+        "orb_family_traffic_bytes_per_1024_images": orb_fam[0].get("traffic_per_1024_images") if orb_fam else None,
+        "kitti_seq00_available": _g(res, "kitti_seq00", "available"),
+        "live_dropin_fps": _g(res, "live_dropin", "gpu", "frames_per_s"),
+        "live_dropin_kfps": _g(res, "live_dropin", "gpu", "keyframes_per_s"),
+        "live_dropin_cpu_path_fps": _g(res, "live_dropin", "cpu", "frames_per_s"),
+        "pose_rmse_vs_oracle_m": _g(res, "pose_rmse_vs_oracle", "ba_translation_rmse_m"),
+    })
 
 
 if __name__ == "__main__":

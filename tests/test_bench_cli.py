@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -31,3 +33,20 @@ def test_gpus_must_match_world_size():
 def test_single_gpu_without_device_fails_loudly():
     r = _run(["--gpus", "1", "--steps", "1", "--warmup", "0"])
     assert r.returncode != 0 and "needs a GPU" in (r.stderr + r.stdout), r.stderr[-400:]
+
+
+def test_prerendered_frames_are_the_pipelines_frames():
+    """bench.py renders the frames of every pipeline in flight up front in one pool (SequenceRenderer): the images and poses
+    synth.stereo_sequence gives the pipelines, bit for bit, in process and over worker processes"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from stereo_visual_slam_amd import synth
+    seeds = [0, 7919]
+    refs = [synth.stereo_sequence(5, seed=s) for s in seeds]
+    for workers in (0, 3):
+        got = bench.SequenceRenderer(5, seeds, workers).get()
+        assert len(got) == len(seeds)
+        for seq, ref in zip(got, refs):
+            assert len(seq) == len(ref)
+            for (L, R, T, _), (L0, R0, T0, _) in zip(seq, ref):
+                assert np.array_equal(L, L0) and np.array_equal(R, R0) and np.array_equal(T, T0)

@@ -1,5 +1,6 @@
-"""GPU: bench.py prints ONE JSON line that carries the driver's contract fields, `roofline` and `cpu_baseline` (small batch so that
-the whole run takes well under a minute); `--depth sgbm` reports the SGBM family as its roofline line."""
+"""GPU: bench.py prints ONE JSON line that carries the driver's contract fields; a plain run stops there, `--full` adds `roofline`,
+`cpu_baseline` and the other measurements (small batch so that the whole run takes well under a minute); `--depth sgbm` reports the SGBM
+family as its roofline line."""
 import json
 import os
 import subprocess
@@ -19,13 +20,29 @@ def _bench(*args):
     return json.loads(lines[0])
 
 
+def test_bench_plain_line():
+    """a plain run: the contract fields, the timed repeats and nothing measured or checked besides them"""
+    r = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16", "--unique-frames", "8")
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in r, k
+    assert r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1 and r["unit"] == "keyframes/s" and r["higher_is_better"] is True and r["dtype"] == "u8+f64"
+    assert abs(r["value"] - 16 * 2 / (r["ms_per_step"] * 2e-3)) / r["value"] < 1e-3
+    assert r["timing"]["repeats"] == 3 and r["timing"]["in_flight"]["batches"] == 2 and r["config"]["full"] is False
+    assert "its own sequence" in r["config"]["unique_inputs"] and "built on the device" in r["config"]["workload"]
+    assert r["stats"] == {"orb_status_nonzero": 0, "ba_status_nonzero": 0}
+    for k in ("roofline", "kernels_ms_per_step", "other_rooflines", "cpu_baseline", "inputs_from_host", "reference_pipeline", "ba_config4",
+              "value_config4_windows", "live_dropin", "kitti_seq00"):
+        assert k not in r, k
+    assert "overlap" not in r["timing"]["in_flight"] and "ba_schedule" not in r["timing"]
+
+
 def test_bench_line_contract():
-    r = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "16", "--unique-frames", "8")
+    r = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "16", "--unique-frames", "8", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in r, k
     assert r["n_gpus"] == 1 and r["world_size"] == 1 and r["steps"] == 2 and r["warmup"] == 1
     assert r["unit"] == "keyframes/s" and r["higher_is_better"] is True and r["scaling"] == "weak" and r["vs_baseline"] is None
-    assert r["data"] == "synthetic" and "workload" in r["config"] and "model" not in r["config"]
+    assert r["data"] == "synthetic" and "workload" in r["config"] and "model" not in r["config"] and r["config"]["full"] is True
     assert abs(r["value"] - 16 * 2 / (r["ms_per_step"] * 2e-3)) / r["value"] < 1e-3           # value = units / time
     rf = r["roofline"]
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
@@ -86,17 +103,19 @@ def test_bench_line_contract():
 def test_bench_synthetic_windows_and_ransac_pose():
     """--ba-windows synthetic keeps the config-4 shape of rounds 1-3; --pose ransac swaps in the reference's pose stage"""
     r = _bench("--ba-windows", "synthetic", "--landmarks", "600", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "8", "--unique-frames", "8",
-               "--no-cpu-baseline", "--inputs", "resident")
+               "--no-cpu-baseline", "--inputs", "resident", "--full")
     assert r["config"]["ba_windows"] == "synthetic" and "ba_windows" not in r["stats"] and "reference_pipeline" not in r
     r1 = _bench("--in-flight", "1", "--ba-windows", "synthetic", "--landmarks", "600", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "8",
-                "--unique-frames", "8", "--no-cpu-baseline", "--inputs", "resident")
+                "--unique-frames", "8", "--no-cpu-baseline", "--inputs", "resident", "--full")
     assert r1["timing"]["in_flight"]["batches"] == 1 and r1["timing"]["in_flight"]["one_batch_in_flight"] is None
-    r = _bench("--pose", "ransac", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "8", "--unique-frames", "8", "--no-cpu-baseline", "--inputs", "resident")
+    r = _bench("--pose", "ransac", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "8", "--unique-frames", "8", "--no-cpu-baseline", "--inputs", "resident",
+               "--full")
     assert "solvePnPRansac" in r["config"]["workload"] and "pnp_epnp_kernels" in r["kernels_ms_per_step"] and r["stats"]["pnp_inliers"] > 10
 
 
 def test_bench_sgbm_depth_line():
-    r = _bench("--depth", "sgbm", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "8", "--unique-frames", "8", "--no-cpu-baseline", "--inputs", "resident")
+    r = _bench("--depth", "sgbm", "--steps", "2", "--warmup", "1", "--repeats", "1", "--batch", "8", "--unique-frames", "8", "--no-cpu-baseline", "--inputs", "resident",
+               "--full")
     assert r["roofline"]["kernel"].startswith("sgbm_* (family") and r["roofline"]["frac"] > 0
     assert "sgbm_down_kernel" in r["kernels_ms_per_step"]        # 8 pairs per call: the fused top-down kernel
     assert "SGBM" in r["config"]["workload"]
