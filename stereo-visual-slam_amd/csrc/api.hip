@@ -8,7 +8,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cfloat>
-#include <cmath>
 #include <vector>
 
 #include "se3_device.h"
@@ -68,10 +67,19 @@ void prof_end(hipStream_t s) {
         prof_set_current(((c)->prof && (c)->prof->on) ? (c)->prof : nullptr);               \
     } while (0)
 
-// simple bump arena over one growable device allocation (host-buffer API only)
+// Staging layout of one host-buffer call: 256-byte-aligned slots bumped over the context's growable device buffer.  With a null
+// base it only measures; in() also queues the host -> device copy of its slot.
 struct Arena {
-    Ctx* c; size_t off;
-    explicit Arena(Ctx* ctx) : c(ctx), off(0) {}
+    struct Upload { void* d; const void* h; size_t bytes; };
+    uint8_t* base; size_t off = 0; std::vector<Upload> uploads;
+    explicit Arena(uint8_t* b) : base(b) {}
+    template <typename T> T* take(size_t n) {
+        off = (off + 255) & ~(size_t)255;
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += n * sizeof(T);
+        return p;
+    }
+    template <typename T> T* in(const T* h, size_t n) { T* d = take<T>(n); if (base) uploads.push_back({d, h, n * sizeof(T)}); return d; }
 };
 static int arena_reserve(Ctx* c, size_t bytes) {
     if (c->stage_bytes >= bytes) return VSLAM_OK;
@@ -83,14 +91,19 @@ static int arena_reserve(Ctx* c, size_t bytes) {
     c->stage_bytes = want; c->dev_bytes += want;
     return VSLAM_OK;
 }
-template <typename T>
-static T* arena_take(Arena& a, size_t n) {
-    a.off = (a.off + 255) & ~(size_t)255;
-    T* p = reinterpret_cast<T*>(a.c->d_stage + a.off);
-    a.off += n * sizeof(T);
-    return p;
+// `layout(Arena&)` states the slots once: it runs against a null base to size the reservation, then carves the staging buffer,
+// whose queued uploads go out on the context stream in take order
+template <typename F>
+static int arena_stage(Ctx* c, F&& layout) {
+    Arena m(nullptr);
+    layout(m);
+    if (int rc = arena_reserve(c, m.off)) return rc;
+    Arena a(c->d_stage);
+    layout(a);
+    if (a.off > c->stage_bytes) { set_error("staging layout uses %zu bytes of %zu reserved", a.off, c->stage_bytes); return VSLAM_ERR_CAPACITY; }
+    for (const Arena::Upload& u : a.uploads) VS_HIP(hipMemcpyAsync(u.d, u.h, u.bytes, hipMemcpyHostToDevice, c->stream));
+    return VSLAM_OK;
 }
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static CamParams cam_of(const Ctx* c) {
     CamParams cam;
@@ -282,6 +295,7 @@ void vslam_destroy(vslam_ctx* ctx) {
     if (c->d_ransac) hipFree(c->d_ransac);
     if (c->h_pinned) hipHostFree(c->h_pinned);
     if (c->lm.buf) hipFree(c->lm.buf);
+    if (c->lm.cyc) hipFree(c->lm.cyc);
     void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad,
                     c->match.d_train_best, c->d_stage};
     for (void* q : ptrs) if (q) hipFree(q);
@@ -310,10 +324,10 @@ size_t vslam_device_bytes(const vslam_ctx* ctx) { return ctx ? reinterpret_cast<
 // Host image -> device image with a 64-byte row pitch.  The rows are repacked on the host into a pinned staging buffer and
 // sent as ONE linear copy: hipMemcpy2DAsync from pageable memory degenerates into a copy per row (measured 2.8 ms for a
 // 1241x376 image against 0.03 ms for the same bytes as one block).  Several images of one call use consecutive slots.
-static int upload_image(Ctx* c, Arena& ar, const uint8_t* img, int w, int h, int stride, uint8_t** d_img, int* pitch, int slot = 0) {
-    *pitch = (w + 63) & ~63;
-    const size_t bytes = (size_t)*pitch * h;
-    *d_img = arena_take<uint8_t>(ar, bytes);
+static int img_pitch(int w) { return (w + 63) & ~63; }
+static int upload_image(Ctx* c, uint8_t* d_img, const uint8_t* img, int w, int h, int stride, int slot = 0) {
+    const int pitch = img_pitch(w);
+    const size_t bytes = (size_t)pitch * h;
     const size_t need = bytes * (size_t)(slot + 1);
     if (c->pinned_bytes < need) {
         VS_HIP(hipStreamSynchronize(c->stream));
@@ -325,10 +339,10 @@ static int upload_image(Ctx* c, Arena& ar, const uint8_t* img, int w, int h, int
     }
     uint8_t* stage = c->h_pinned + bytes * (size_t)slot;
     for (int y = 0; y < h; ++y) {
-        memcpy(stage + (size_t)y * *pitch, img + (size_t)y * stride, (size_t)w);
-        memset(stage + (size_t)y * *pitch + w, 0, (size_t)(*pitch - w)); // deterministic padding
+        memcpy(stage + (size_t)y * pitch, img + (size_t)y * stride, (size_t)w);
+        memset(stage + (size_t)y * pitch + w, 0, (size_t)(pitch - w)); // deterministic padding
     }
-    VS_HIP(hipMemcpyAsync(*d_img, stage, bytes, hipMemcpyHostToDevice, c->stream));
+    VS_HIP(hipMemcpyAsync(d_img, stage, bytes, hipMemcpyHostToDevice, c->stream));
     return VSLAM_OK;
 }
 
@@ -339,15 +353,15 @@ static int orb_host_call(vslam_ctx* ctx, const uint8_t* img, int w, int h, int s
     if (rc) return rc;
     if (!kps || !n_out || cap <= 0 || (describe && !desc)) { set_error("null output"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    const int kc = c->p.kp_capacity;
-    const size_t pitch = (w + 63) & ~63;
-    if ((rc = arena_reserve(c, al256(pitch * h) + al256(sizeof(vslam_keypoint) * kc) + al256((size_t)kc * 32) + 1024))) return rc;
-    Arena ar(c);
-    uint8_t* d_img; int dp;
-    if ((rc = upload_image(c, ar, img, w, h, stride, &d_img, &dp))) return rc;
-    vslam_keypoint* d_kps = arena_take<vslam_keypoint>(ar, kc);
-    uint8_t* d_desc = arena_take<uint8_t>(ar, (size_t)kc * 32);
-    int32_t* d_cnt = arena_take<int32_t>(ar, 1);
+    const int kc = c->p.kp_capacity, dp = img_pitch(w);
+    uint8_t *d_img, *d_desc; vslam_keypoint* d_kps; int32_t* d_cnt;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_img = a.take<uint8_t>((size_t)dp * h);
+             d_kps = a.take<vslam_keypoint>(kc);
+             d_desc = a.take<uint8_t>((size_t)kc * 32);
+             d_cnt = a.take<int32_t>(1);
+         }))) return rc;
+    if ((rc = upload_image(c, d_img, img, w, h, stride))) return rc;
     if ((rc = orb_pipeline(c, d_img, (size_t)dp * h, dp, 1, anms_num, regroup, describe, d_kps, d_desc, d_cnt))) return rc;
     int32_t n = 0;
     VS_HIP(hipMemcpyAsync(&n, d_cnt, sizeof(n), hipMemcpyDeviceToHost, c->stream));
@@ -377,13 +391,14 @@ int vslam_anms(vslam_ctx* ctx, vslam_keypoint* kps, int n, int num, int* n_out) 
     if (n == 0) { *n_out = 0; return VSLAM_OK; }
     VS_ENTER(c);
     int rc;
-    if ((rc = arena_reserve(c, 2 * al256(sizeof(vslam_keypoint) * kMaxRows) + 1024))) return rc;
-    Arena ar(c);
-    vslam_keypoint* d_in = arena_take<vslam_keypoint>(ar, kMaxRows);
-    vslam_keypoint* d_out = arena_take<vslam_keypoint>(ar, kMaxRows);
-    int32_t* d_n = arena_take<int32_t>(ar, 1);
-    int32_t* d_cnt = arena_take<int32_t>(ar, 1);
-    int32_t nn = n;
+    vslam_keypoint *d_in, *d_out; int32_t *d_n, *d_cnt;
+    const int32_t nn = n;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_in = a.take<vslam_keypoint>(kMaxRows);
+             d_out = a.take<vslam_keypoint>(kMaxRows);
+             d_n = a.take<int32_t>(1);
+             d_cnt = a.take<int32_t>(1);
+         }))) return rc;
     VS_HIP(hipMemcpyAsync(d_in, kps, sizeof(vslam_keypoint) * n, hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemcpyAsync(d_n, &nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(c->orb.d_status, 0, sizeof(int32_t), c->stream));
@@ -406,18 +421,18 @@ int vslam_orb_compute(vslam_ctx* ctx, const uint8_t* img, int w, int h, int stri
     for (int i = 0; i < n; ++i)
         if (kps[i].octave < 0 || kps[i].octave >= kNLevels) { set_error("keypoint %d: octave %d out of range", i, kps[i].octave); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    const int kc = c->p.kp_capacity;
-    const size_t pitch = (w + 63) & ~63;
-    if ((rc = arena_reserve(c, al256(pitch * h) + 2 * al256(sizeof(vslam_keypoint) * kc) + al256((size_t)kc * 32) + 1024))) return rc;
-    Arena ar(c);
-    uint8_t* d_img; int dp;
-    if ((rc = upload_image(c, ar, img, w, h, stride, &d_img, &dp))) return rc;
-    vslam_keypoint* d_in = arena_take<vslam_keypoint>(ar, kc);
-    vslam_keypoint* d_kps = arena_take<vslam_keypoint>(ar, kc);
-    uint8_t* d_desc = arena_take<uint8_t>(ar, (size_t)kc * 32);
-    int32_t* d_n = arena_take<int32_t>(ar, 1);
-    int32_t* d_cnt = arena_take<int32_t>(ar, 1);
-    int32_t nn = n;
+    const int kc = c->p.kp_capacity, dp = img_pitch(w);
+    uint8_t *d_img, *d_desc; vslam_keypoint *d_in, *d_kps; int32_t *d_n, *d_cnt;
+    const int32_t nn = n;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_img = a.take<uint8_t>((size_t)dp * h);
+             d_in = a.take<vslam_keypoint>(kc);
+             d_kps = a.take<vslam_keypoint>(kc);
+             d_desc = a.take<uint8_t>((size_t)kc * 32);
+             d_n = a.take<int32_t>(1);
+             d_cnt = a.take<int32_t>(1);
+         }))) return rc;
+    if ((rc = upload_image(c, d_img, img, w, h, stride))) return rc;
     VS_HIP(hipMemcpyAsync(d_in, kps, sizeof(vslam_keypoint) * n, hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemcpyAsync(d_n, &nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(c->orb.d_status, 0, sizeof(int32_t), c->stream));
@@ -495,18 +510,15 @@ int vslam_feature_matching(vslam_ctx* ctx, const uint8_t* q, int nq, const uint8
     VS_ENTER(c);
     int rc;
     const int rows = std::max(nq, nt);
-    if ((rc = arena_reserve(c, 2 * al256((size_t)rows * 32) + al256(sizeof(vslam_dmatch) * nq) + 2048))) return rc;
-    Arena ar(c);
-    uint8_t* d_q = arena_take<uint8_t>(ar, (size_t)nq * 32);
-    uint8_t* d_t = arena_take<uint8_t>(ar, (size_t)nt * 32);
-    vslam_dmatch* d_out = arena_take<vslam_dmatch>(ar, nq);
-    int32_t* d_n = arena_take<int32_t>(ar, 4);
-    double* d_gap = arena_take<double>(ar, 1);
-    int32_t hn[3] = {nq, nt, 0};
-    VS_HIP(hipMemcpyAsync(d_q, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_n, hn, sizeof(hn), hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_gap, &frame_gap, sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const int32_t hn[3] = {nq, nt, 0};
+    uint8_t *d_q, *d_t; vslam_dmatch* d_out; int32_t* d_n; double* d_gap;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_q = a.in(q, (size_t)nq * 32);
+             d_t = a.in(t, (size_t)nt * 32);
+             d_out = a.take<vslam_dmatch>(nq);
+             d_n = a.in(hn, 3);
+             d_gap = a.in(&frame_gap, 1);
+         }))) return rc;
     if ((rc = launch_match(d_q, 0, d_n, d_t, 0, d_n + 1, d_gap, gate, c->p.match_ratio, c->p.match_gap_thr, 1, rows, c->match.d_train_best,
                            d_out, nq, d_n + 2, c->stream))) return rc;
     int32_t m = 0;
@@ -537,14 +549,17 @@ int vslam_disparity_map(vslam_ctx* ctx, const uint8_t* left, const uint8_t* righ
     VS_ENTER(c);
     int rc;
     const size_t npix = (size_t)w * h;
-    if ((rc = arena_reserve(c, 2 * al256((size_t)((w + 63) & ~63) * h) + al256(npix * 4) + 2 * al256(npix * 2) + 1024))) return rc;
-    Arena ar(c);
-    uint8_t *d_l, *d_r; int pl, pr;
-    if ((rc = upload_image(c, ar, left, w, h, stride, &d_l, &pl))) return rc;
-    if ((rc = upload_image(c, ar, right, w, h, stride, &d_r, &pr, 1))) return rc;
-    float* d_f = arena_take<float>(ar, npix);
-    int16_t* d_i = arena_take<int16_t>(ar, npix);
-    int16_t* d_raw = arena_take<int16_t>(ar, npix);
+    const int pl = img_pitch(w);
+    uint8_t *d_l, *d_r; float* d_f; int16_t *d_i, *d_raw;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_l = a.take<uint8_t>((size_t)pl * h);
+             d_r = a.take<uint8_t>((size_t)pl * h);
+             d_f = a.take<float>(npix);
+             d_i = a.take<int16_t>(npix);
+             d_raw = a.take<int16_t>(npix);
+         }))) return rc;
+    if ((rc = upload_image(c, d_l, left, w, h, stride))) return rc;
+    if ((rc = upload_image(c, d_r, right, w, h, stride, 1))) return rc;
     if ((rc = launch_sgbm(c->tune, d_l, d_r, (size_t)pl * h, pl, w, h, 1, d_f, d_i, disp_raw_i16 ? d_raw : nullptr, &c->d_sgbm, &c->sgbm_bytes, &c->dev_bytes,
                           c->stream))) return rc;
     if (disparity) VS_HIP(hipMemcpyAsync(disparity, d_f, npix * 4, hipMemcpyDeviceToHost, c->stream));
@@ -585,17 +600,15 @@ int vslam_find_3d_disparity(vslam_ctx* ctx, const vslam_keypoint* kps, int n, co
     if (n == 0) return VSLAM_OK;
     VS_ENTER(c);
     int rc;
-    if ((rc = arena_reserve(c, al256(sizeof(vslam_keypoint) * n) + al256(sizeof(float) * (size_t)dstride * h) + al256(12 * (size_t)n) + 2 * al256(n) + 1024))) return rc;
-    Arena ar(c);
-    vslam_keypoint* d_k = arena_take<vslam_keypoint>(ar, n);
-    float* d_d = arena_take<float>(ar, (size_t)dstride * h);
-    double* d_T = arena_take<double>(ar, 7);
-    float* d_x = arena_take<float>(ar, 3 * (size_t)n);
-    uint8_t* d_v = arena_take<uint8_t>(ar, n);
-    uint8_t* d_r = arena_take<uint8_t>(ar, n);
-    VS_HIP(hipMemcpyAsync(d_k, kps, sizeof(vslam_keypoint) * n, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_d, disparity, sizeof(float) * (size_t)dstride * h, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_T, T_c_w, sizeof(double) * 7, hipMemcpyHostToDevice, c->stream));
+    vslam_keypoint* d_k; float *d_d, *d_x; double* d_T; uint8_t *d_v, *d_r;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_k = a.in(kps, n);
+             d_d = a.in(disparity, (size_t)dstride * h);
+             d_T = a.in(T_c_w, 7);
+             d_x = a.take<float>(3 * (size_t)n);
+             d_v = a.take<uint8_t>(n);
+             d_r = a.take<uint8_t>(n);
+         }))) return rc;
     if ((rc = launch_find3d_disparity(d_k, n, d_d, w, h, dstride, d_T, cam_of(c), d_x, d_v, d_r, c->stream))) return rc;
     VS_HIP(hipMemcpyAsync(xyz_w, d_x, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipMemcpyAsync(valid, d_v, n, hipMemcpyDeviceToHost, c->stream));
@@ -629,20 +642,17 @@ int vslam_triangulate(vslam_ctx* ctx, const float* uvL, const float* uvR, int n,
     if (n == 0) return VSLAM_OK;
     VS_ENTER(c);
     int rc;
-    if ((rc = arena_reserve(c, 2 * al256(8 * (size_t)n) + al256(12 * (size_t)n) + 2 * al256(n) + 2048))) return rc;
-    Arena ar(c);
-    float* d_l = arena_take<float>(ar, 2 * (size_t)n);
-    float* d_r = arena_take<float>(ar, 2 * (size_t)n);
-    double* d_T = arena_take<double>(ar, 7);
-    int32_t* d_n = arena_take<int32_t>(ar, 1);
-    float* d_x = arena_take<float>(ar, 3 * (size_t)n);
-    uint8_t* d_v = arena_take<uint8_t>(ar, n);
-    uint8_t* d_rel = arena_take<uint8_t>(ar, n);
-    int32_t nn = n;
-    VS_HIP(hipMemcpyAsync(d_l, uvL, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_r, uvR, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_T, T_c_w, 56, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_n, &nn, 4, hipMemcpyHostToDevice, c->stream));
+    const int32_t nn = n;
+    float *d_l, *d_r, *d_x; double* d_T; int32_t* d_n; uint8_t *d_v, *d_rel;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_l = a.in(uvL, 2 * (size_t)n);
+             d_r = a.in(uvR, 2 * (size_t)n);
+             d_T = a.in(T_c_w, 7);
+             d_n = a.in(&nn, 1);
+             d_x = a.take<float>(3 * (size_t)n);
+             d_v = a.take<uint8_t>(n);
+             d_rel = a.take<uint8_t>(n);
+         }))) return rc;
     if ((rc = launch_triangulate(d_l, d_r, d_n, n, 1, d_T, cam_of(c), d_x, d_v, d_rel, c->stream))) return rc;
     VS_HIP(hipMemcpyAsync(xyz_w, d_x, 12 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipMemcpyAsync(valid, d_v, n, hipMemcpyDeviceToHost, c->stream));
@@ -687,18 +697,16 @@ int vslam_pnp_motion_only(vslam_ctx* ctx, const float* xyz_w, const float* uv, i
     if (!c || !xyz_w || !uv || n <= 0 || !T_c_w || iters < 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     int rc;
-    if ((rc = arena_reserve(c, al256(12 * (size_t)n) + al256(8 * (size_t)n) + al256(n) + al256(sizeof(vslam_lm_stats)) + 2048))) return rc;
-    Arena ar(c);
-    float* d_x = arena_take<float>(ar, 3 * (size_t)n);
-    float* d_u = arena_take<float>(ar, 2 * (size_t)n);
-    double* d_T = arena_take<double>(ar, 7);
-    int32_t* d_n = arena_take<int32_t>(ar, 2);
-    uint8_t* d_in = arena_take<uint8_t>(ar, n);
-    vslam_lm_stats* d_st = arena_take<vslam_lm_stats>(ar, 1);
-    int32_t nn = n;
-    VS_HIP(hipMemcpyAsync(d_x, xyz_w, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_u, uv, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_T, T_c_w, 56, hipMemcpyHostToDevice, c->stream));
+    const int32_t nn = n;
+    float *d_x, *d_u; double* d_T; int32_t* d_n; uint8_t* d_in; vslam_lm_stats* d_st;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_x = a.in(xyz_w, 3 * (size_t)n);
+             d_u = a.in(uv, 2 * (size_t)n);
+             d_T = a.in(T_c_w, 7);
+             d_n = a.take<int32_t>(2); // (point count in, inlier count out)
+             d_in = a.take<uint8_t>(n);
+             d_st = a.take<vslam_lm_stats>(1);
+         }))) return rc;
     VS_HIP(hipMemcpyAsync(d_n, &nn, 4, hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(d_st, 0, sizeof(vslam_lm_stats), c->stream));
     PnpArgs p;
@@ -763,20 +771,16 @@ static int pnp_ransac_impl(vslam_ctx* ctx, const float* xyz_w, const float* uv, 
         }
     }
     int rc;
-    if ((rc = arena_reserve(c, al256(hx.size() * 4) + al256(hu.size() * 4) + al256((size_t)H * 96) + al256((size_t)H * 56) + 2 * al256((size_t)H * 4) +
-                                   2 * al256(12 * (size_t)n) + 2 * al256(8 * (size_t)n) + 2 * al256(n) + al256(pnp_epnp_ws_bytes(H)) + 4096))) return rc;
-    Arena ar(c);
-    float* d_hx = arena_take<float>(ar, hx.size()); float* d_hu = arena_take<float>(ar, hu.size());
-    double* d_Rt = arena_take<double>(ar, (size_t)H * 12); double* d_hT = arena_take<double>(ar, (size_t)H * 7);
-    int32_t* d_ok = arena_take<int32_t>(ar, H); int32_t* d_cnt = arena_take<int32_t>(ar, H);
-    float* d_x = arena_take<float>(ar, 3 * (size_t)n); float* d_u = arena_take<float>(ar, 2 * (size_t)n);
-    float* d_ix = arena_take<float>(ar, 3 * (size_t)n); float* d_iu = arena_take<float>(ar, 2 * (size_t)n);
-    uint8_t* d_mask = arena_take<uint8_t>(ar, n); double* d_T = arena_take<double>(ar, 7); int32_t* d_n1 = arena_take<int32_t>(ar, 2);
-    uint8_t* d_ws = arena_take<uint8_t>(ar, pnp_epnp_ws_bytes(H));
-    VS_HIP(hipMemcpyAsync(d_hx, hx.data(), hx.size() * 4, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_hu, hu.data(), hu.size() * 4, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_x, xyz_w, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_u, uv, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    float *d_hx, *d_hu, *d_x, *d_u, *d_ix, *d_iu; double *d_Rt, *d_hT, *d_T; int32_t *d_ok, *d_cnt, *d_n1; uint8_t *d_mask, *d_ws;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_hx = a.in(hx.data(), hx.size()); d_hu = a.in(hu.data(), hu.size());
+             d_Rt = a.take<double>((size_t)H * 12); d_hT = a.take<double>((size_t)H * 7);
+             d_ok = a.take<int32_t>(H); d_cnt = a.take<int32_t>(H);
+             d_x = a.in(xyz_w, 3 * (size_t)n); d_u = a.in(uv, 2 * (size_t)n);
+             d_ix = a.take<float>(3 * (size_t)n); d_iu = a.take<float>(2 * (size_t)n);
+             d_mask = a.take<uint8_t>(n); d_T = a.take<double>(7); d_n1 = a.take<int32_t>(2);
+             d_ws = a.take<uint8_t>(pnp_epnp_ws_bytes(H));
+         }))) return rc;
     // 2. every hypothesis: EPnP on its 5 points (one wave each), then its inlier count over all points
     double K[4];
     fill_K(c, K);
@@ -887,23 +891,20 @@ static int window_host(vslam_ctx* ctx, int mode, int n_kf, double* T_c_w, int n_
     for (int j = 0; j < n_edge; ++j) { const int e = perm[j]; skf[j] = kf_idx[e]; slm[j] = lm_idx[e]; suv[2 * j] = uv[2 * e]; suv[2 * j + 1] = uv[2 * e + 1]; }
     VS_ENTER(c);
     int rc;
-    const size_t need = al256(56 * (size_t)n_kf) + al256(12 * (size_t)n_lm) + al256(n_lm) + 3 * al256(4 * (size_t)n_edge) + al256(8 * (size_t)n_edge) * 2 +
-                        al256(sizeof(vslam_lm_stats)) + 4096;
-    if ((rc = arena_reserve(c, need))) return rc;
-    Arena ar(c);
-    double* d_T = arena_take<double>(ar, 7 * (size_t)n_kf);
-    float* d_xyz = arena_take<float>(ar, 3 * (size_t)n_lm);
-    uint8_t* d_inl = arena_take<uint8_t>(ar, n_lm);
-    int32_t* d_kf = arena_take<int32_t>(ar, n_edge);
-    int32_t* d_lm = arena_take<int32_t>(ar, n_edge);
-    float* d_uv = arena_take<float>(ar, 2 * (size_t)n_edge);
-    double* d_chi = arena_take<double>(ar, n_edge);
-    int32_t* d_off = arena_take<int32_t>(ar, 4);
-    vslam_lm_stats* d_st = arena_take<vslam_lm_stats>(ar, 1);
-    double* d_thr = arena_take<double>(ar, 1);
+    double *d_T, *d_chi, *d_thr; float *d_xyz, *d_uv; uint8_t* d_inl; int32_t *d_kf, *d_lm, *d_off; vslam_lm_stats* d_st;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_T = a.in(T_c_w, 7 * (size_t)n_kf);
+             d_xyz = a.in(xyz, 3 * (size_t)n_lm);
+             d_inl = a.take<uint8_t>(n_lm);
+             d_kf = a.take<int32_t>(n_edge);
+             d_lm = a.take<int32_t>(n_edge);
+             d_uv = a.take<float>(2 * (size_t)n_edge);
+             d_chi = a.take<double>(n_edge);
+             d_off = a.take<int32_t>(4);
+             d_st = a.take<vslam_lm_stats>(1);
+             d_thr = a.take<double>(1);
+         }))) return rc;
     const int32_t off[4] = {0, n_lm, 0, n_edge};
-    VS_HIP(hipMemcpyAsync(d_T, T_c_w, 56 * (size_t)n_kf, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_xyz, xyz, 12 * (size_t)n_lm, hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(d_inl, 1, n_lm, c->stream)); // the caller already filtered the graph (optimization.cpp:160 / :334)
     VS_HIP(hipMemcpyAsync(d_kf, skf.data(), 4 * (size_t)n_edge, hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemcpyAsync(d_lm, slm.data(), 4 * (size_t)n_edge, hipMemcpyHostToDevice, c->stream));
@@ -1045,19 +1046,17 @@ int vslam_edge_jacobians(vslam_ctx* ctx, int n, const float* xyz_w, const float*
     if (!c || n <= 0 || !xyz_w || !uv || !T_c_w) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     int rc;
-    if ((rc = arena_reserve(c, al256(12 * (size_t)n) + al256(8 * (size_t)n) + 256 + al256(16 * (size_t)n) + al256(96 * (size_t)n) + al256(48 * (size_t)n) + 2 * al256(8 * (size_t)n) + 4096))) return rc;
-    Arena ar(c);
-    float* d_xyz = arena_take<float>(ar, 3 * (size_t)n);
-    float* d_uv = arena_take<float>(ar, 2 * (size_t)n);
-    double* d_T = arena_take<double>(ar, 7);
-    double* d_err = arena_take<double>(ar, 2 * (size_t)n);
-    double* d_Jp = arena_take<double>(ar, 12 * (size_t)n);
-    double* d_Jl = arena_take<double>(ar, 6 * (size_t)n);
-    double* d_chi = arena_take<double>(ar, n);
-    double* d_hw = arena_take<double>(ar, n);
-    VS_HIP(hipMemcpyAsync(d_xyz, xyz_w, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_uv, uv, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_T, T_c_w, 56, hipMemcpyHostToDevice, c->stream));
+    float *d_xyz, *d_uv; double *d_T, *d_err, *d_Jp, *d_Jl, *d_chi, *d_hw;
+    if ((rc = arena_stage(c, [&](Arena& a) {
+             d_xyz = a.in(xyz_w, 3 * (size_t)n);
+             d_uv = a.in(uv, 2 * (size_t)n);
+             d_T = a.in(T_c_w, 7);
+             d_err = a.take<double>(2 * (size_t)n);
+             d_Jp = a.take<double>(12 * (size_t)n);
+             d_Jl = a.take<double>(6 * (size_t)n);
+             d_chi = a.take<double>(n);
+             d_hw = a.take<double>(n);
+         }))) return rc;
     double K[4];
     fill_K(c, K);
     if (K4) memcpy(K, K4, sizeof(K));

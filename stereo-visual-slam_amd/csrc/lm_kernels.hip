@@ -1788,7 +1788,7 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
 // (LmScratch, owned by the context and grown on demand, is declared in vslam_internal.h)
 static int ensure(void** p, size_t* have, size_t need) {
     if (*have >= need) return VSLAM_OK;
-    if (*p) hipFree(*p);
+    if (*p) VS_HIP(hipFree(*p));
     *p = nullptr; *have = 0;
     if (hipMalloc(p, need) != hipSuccess) { set_error("LM scratch hipMalloc(%zu) failed", need); return VSLAM_ERR_HIP; }
     *have = need;
@@ -1882,11 +1882,15 @@ int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, 
         VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lm_window_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
         scratch->lds_opt_in = true;
     }
-    static long long* d_cyc = nullptr; static int cyc_n = 0;
     if (getenv("VSLAM_LM_PROFILE")) {
-        if (cyc_n < a.n_windows) { if (d_cyc) hipFree(d_cyc); hipMalloc((void**)&d_cyc, sizeof(long long) * kDbgSlots * a.n_windows); cyc_n = a.n_windows; }
-        hipMemsetAsync(d_cyc, 0, sizeof(long long) * kDbgSlots * a.n_windows, stream);
-        ka.dbg_cycles = d_cyc;
+        const size_t cyc_need = sizeof(long long) * kDbgSlots * a.n_windows;
+        if (scratch->cyc_bytes < cyc_need) {
+            VS_HIP(hipStreamSynchronize(stream));
+            int rc = ensure((void**)&scratch->cyc, &scratch->cyc_bytes, cyc_need);
+            if (rc) return rc;
+        }
+        VS_HIP(hipMemsetAsync(scratch->cyc, 0, cyc_need, stream));
+        ka.dbg_cycles = scratch->cyc;
     }
     int rc = carve(*scratch, ka, total_lm, total_edge, a.n_windows, true, stream);
     if (rc) return rc;

@@ -225,6 +225,7 @@ struct LmScratch {
     int rs_dyn_bytes = -1;   // dynamic LDS a ba_resident_kernel workgroup may use on this context's device (-1: not queried yet)
     int32_t* defer = nullptr; // per window of the most recent launch: 1 = left to lm_window_kernel by ba_resident_kernel
     bool defer_valid = false; // ... written by that launch (it involved ba_resident_kernel)
+    long long* cyc = nullptr; size_t cyc_bytes = 0; // phase clocks of the LM kernels (VSLAM_LM_PROFILE), kDbgSlots per window
 };
 // ba_resident.hip: optimize_map / the BA schedule on windows whose landmark state fits the LDS of one CU (the rest is marked in `defer`)
 struct RsLaunch {

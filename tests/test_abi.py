@@ -25,6 +25,37 @@ def test_header_symbols_exported(pkg):
     assert sorted(pkg.ABI_SYMBOLS) == declared
 
 
+def _prototypes():
+    """{symbol: [parameter declarations]} of include/vslam_hip.h, found the way _declared_symbols() finds the names"""
+    hdr = open(os.path.join(ROOT, "include", "vslam_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    protos = {}
+    for name, params in re.findall(r"\b(vslam_[a-z0-9_]+)\s*\(([^)]*)\)", hdr):
+        decls = [" ".join(p.split()) for p in params.split(",")]
+        protos[name] = [] if decls == ["void"] else decls
+    return protos
+
+
+def test_signature_table_matches_header(pkg):
+    """every ABI function gets restype / argtypes from the one table in load_library(): one argtype per prototype parameter,
+    size_t and double parameters as c_size_t / c_double (never a bare Python int), pointers as pointer types"""
+    import ctypes as C
+    lib = pkg.load_library()
+    protos = _prototypes()
+    assert sorted(protos) == _declared_symbols() == sorted(pkg.SIGNATURES)
+    for name, decls in protos.items():
+        argtypes = getattr(lib, name).argtypes
+        assert argtypes is not None, name
+        assert len(argtypes) == len(decls), (name, argtypes, decls)
+        for decl, t in zip(decls, argtypes):
+            if "*" in decl or decl.endswith("]"):
+                assert t is pkg.Ptr or issubclass(t, (C._Pointer, C.c_char_p)), (name, decl, t)
+                continue
+            ctype = decl.rsplit(" ", 1)[0]  # (drop the parameter name)
+            assert (ctype, t) in (("int", C.c_int), ("size_t", C.c_size_t), ("double", C.c_double)), (name, decl, t)
+
+
 def test_header_is_plain_c(tmp_path):
     src = '#include "vslam_hip.h"\nint main(void){ vslam_params p; vslam_default_params(&p); return sizeof(vslam_keypoint)==28 && sizeof(vslam_dmatch)==16 ? 0 : 1; }\n'
     out = str(tmp_path / "abi_c_check.o")
