@@ -67,40 +67,32 @@ void prof_end(hipStream_t s) {
         prof_set_current(((c)->prof && (c)->prof->on) ? (c)->prof : nullptr);               \
     } while (0)
 
-// Staging layout of one host-buffer call: 256-byte-aligned slots bumped over the context's growable device buffer.  With a null
-// base it only measures; in() also queues the host -> device copy of its slot.
-struct Arena {
-    struct Upload { void* d; const void* h; size_t bytes; };
-    uint8_t* base; size_t off = 0; std::vector<Upload> uploads;
-    explicit Arena(uint8_t* b) : base(b) {}
-    template <typename T> T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += n * sizeof(T);
-        return p;
-    }
-    template <typename T> T* in(const T* h, size_t n) { T* d = take<T>(n); if (base) uploads.push_back({d, h, n * sizeof(T)}); return d; }
-};
-static int arena_reserve(Ctx* c, size_t bytes) {
-    if (c->stage_bytes >= bytes) return VSLAM_OK;
-    VS_HIP(hipStreamSynchronize(c->stream));
-    if (c->d_stage) { hipFree(c->d_stage); c->dev_bytes -= c->stage_bytes; }
-    c->d_stage = nullptr; c->stage_bytes = 0;
-    const size_t want = std::max(bytes, (size_t)1 << 20);
-    VS_HIP(hipMalloc((void**)&c->d_stage, want));
-    c->stage_bytes = want; c->dev_bytes += want;
+int DevBuf::reserve(size_t need, hipStream_t stream) {
+    if (bytes >= need) return VSLAM_OK;
+    VS_HIP(hipStreamSynchronize(stream));
+    release();
+    const size_t want = std::max(need, min_bytes);
+    if (hipMalloc((void**)&p, want) != hipSuccess) { p = nullptr; set_error("%s hipMalloc(%zu) failed", name, want); return VSLAM_ERR_HIP; }
+    bytes = want; *acct += want;
     return VSLAM_OK;
 }
-// `layout(Arena&)` states the slots once: it runs against a null base to size the reservation, then carves the staging buffer,
-// whose queued uploads go out on the context stream in take order
+void DevBuf::release() {
+    if (p) { (void)hipFree(p); *acct -= bytes; }
+    p = nullptr; bytes = 0;
+}
+
+// Staging layout of one host-buffer call over the context's staging buffer: in() also queues the host -> device copy of its slot.
+struct Arena : Layout {
+    struct Upload { void* d; const void* h; size_t bytes; };
+    std::vector<Upload> uploads;
+    explicit Arena(uint8_t* b = nullptr) : Layout(b) {}
+    template <typename T> T* in(const T* h, size_t n) { T* d = take<T>(n); if (base) uploads.push_back({d, h, n * sizeof(T)}); return d; }
+};
+// `layout(Arena&)` carves the staging buffer (carve()); the queued uploads go out on the context stream in take order
 template <typename F>
 static int arena_stage(Ctx* c, F&& layout) {
-    Arena m(nullptr);
-    layout(m);
-    if (int rc = arena_reserve(c, m.off)) return rc;
-    Arena a(c->d_stage);
-    layout(a);
-    if (a.off > c->stage_bytes) { set_error("staging layout uses %zu bytes of %zu reserved", a.off, c->stage_bytes); return VSLAM_ERR_CAPACITY; }
+    Arena a;
+    if (int rc = carve(c->stage, c->stream, a, layout)) return rc;
     for (const Arena::Upload& u : a.uploads) VS_HIP(hipMemcpyAsync(u.d, u.h, u.bytes, hipMemcpyHostToDevice, c->stream));
     return VSLAM_OK;
 }
@@ -266,7 +258,7 @@ int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** ou
     }
     if (getenv("VSLAM_ORB_PROFILE")) orb_debug_enable();
     int rc = orb_plan_init(&c->plan, p->img_w, p->img_h, p->orb_nfeatures, p->kp_capacity);
-    if (rc == VSLAM_OK) rc = orb_tables_init(&c->plan, &c->tab);
+    if (rc == VSLAM_OK) { rc = orb_tables_init(&c->plan, &c->tab); c->dev_bytes += c->tab.bytes; }
     const size_t B = (size_t)p->max_batch;
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_pyr, B * c->plan.pyr_bytes);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_corners, B * c->plan.corner_total);
@@ -290,14 +282,10 @@ void vslam_destroy(vslam_ctx* ctx) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     orb_tables_free(&c->tab);
-    if (c->d_sgbm) hipFree(c->d_sgbm);
-    if (c->d_track) hipFree(c->d_track);
-    if (c->d_ransac) hipFree(c->d_ransac);
+    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc}) b->release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
-    if (c->lm.buf) hipFree(c->lm.buf);
-    if (c->lm.cyc) hipFree(c->lm.cyc);
     void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad,
-                    c->match.d_train_best, c->d_stage};
+                    c->match.d_train_best};
     for (void* q : ptrs) if (q) hipFree(q);
     if (c->prof) {
         if (prof_current() == c->prof) prof_set_current(nullptr);
@@ -538,8 +526,7 @@ int vslam_disparity_map_dev(vslam_ctx* ctx, const uint8_t* d_left, const uint8_t
         (!d_disparity && !d_disp_i16 && !d_disp_raw_i16)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     c->sgbm_unchecked = true; // (asynchronous: the forward sweep's error word is looked at by the next vslam_sync / vslam_sgbm_status_dev)
-    return launch_sgbm(c->tune, d_left, d_right, img_stride_bytes, pitch, w, h, B, d_disparity, d_disp_i16, d_disp_raw_i16, &c->d_sgbm, &c->sgbm_bytes,
-                       &c->dev_bytes, c->stream);
+    return launch_sgbm(c->tune, d_left, d_right, img_stride_bytes, pitch, w, h, B, d_disparity, d_disp_i16, d_disp_raw_i16, c->sgbm, c->stream);
 }
 
 int vslam_disparity_map(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int stride, float* disparity, int16_t* disp_i16,
@@ -560,8 +547,7 @@ int vslam_disparity_map(vslam_ctx* ctx, const uint8_t* left, const uint8_t* righ
          }))) return rc;
     if ((rc = upload_image(c, d_l, left, w, h, stride))) return rc;
     if ((rc = upload_image(c, d_r, right, w, h, stride, 1))) return rc;
-    if ((rc = launch_sgbm(c->tune, d_l, d_r, (size_t)pl * h, pl, w, h, 1, d_f, d_i, disp_raw_i16 ? d_raw : nullptr, &c->d_sgbm, &c->sgbm_bytes, &c->dev_bytes,
-                          c->stream))) return rc;
+    if ((rc = launch_sgbm(c->tune, d_l, d_r, (size_t)pl * h, pl, w, h, 1, d_f, d_i, disp_raw_i16 ? d_raw : nullptr, c->sgbm, c->stream))) return rc;
     if (disparity) VS_HIP(hipMemcpyAsync(disparity, d_f, npix * 4, hipMemcpyDeviceToHost, c->stream));
     if (disp_i16) VS_HIP(hipMemcpyAsync(disp_i16, d_i, npix * 2, hipMemcpyDeviceToHost, c->stream));
     if (disp_raw_i16) VS_HIP(hipMemcpyAsync(disp_raw_i16, d_raw, npix * 2, hipMemcpyDeviceToHost, c->stream));
@@ -584,9 +570,8 @@ int vslam_sgbm_status_dev(vslam_ctx* ctx, int32_t* h_status) {
     VS_ENTER(c);
     *h_status = 0;
     c->sgbm_unchecked = false;
-    if (!c->d_sgbm) { VS_HIP(hipStreamSynchronize(c->stream)); return VSLAM_OK; } // no SGBM launch yet
-    // header of the SGBM scratch: int32 [0..7] ticket pools, [8] error word of the most recent launch (sgbm_kernels.hip, launch_sgbm)
-    VS_HIP(hipMemcpyAsync(h_status, c->d_sgbm + 32, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (!c->sgbm.p) { VS_HIP(hipStreamSynchronize(c->stream)); return VSLAM_OK; } // no SGBM launch yet
+    VS_HIP(hipMemcpyAsync(h_status, reinterpret_cast<const int32_t*>(c->sgbm.p) + kSgbmErrorWord, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipStreamSynchronize(c->stream));
     if (*h_status != 0) { set_error("sgbm_forward_kernel: a slab waited for its predecessor beyond the spin limit; the disparity maps of this call are void"); return VSLAM_ERR_HIP; }
     return VSLAM_OK;
@@ -851,17 +836,9 @@ int vslam_pnp_ransac_dev(vslam_ctx* ctx, const float* d_xyz_w, const float* d_uv
     if (!c || !d_xyz_w || !d_uv || !d_n || !d_T_c_w || capacity <= 0 || B < 0 || max_iters <= 0 || max_iters > 4096 || !(reproj_err > 0)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     if (B == 0) return VSLAM_OK;
-    const size_t need = pnp_ransac_scratch_bytes(B, max_iters);
-    if (c->ransac_bytes < need) {
-        VS_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_ransac) { (void)hipFree(c->d_ransac); c->dev_bytes -= c->ransac_bytes; }
-        c->d_ransac = nullptr; c->ransac_bytes = 0;
-        if (hipMalloc((void**)&c->d_ransac, need) != hipSuccess) { c->d_ransac = nullptr; set_error("RANSAC scratch hipMalloc(%zu) failed", need); return VSLAM_ERR_HIP; }
-        c->ransac_bytes = need; c->dev_bytes += need;
-    }
     double K[4];
     fill_K(c, K);
-    return launch_pnp_ransac_batch(d_xyz_w, d_uv, d_n, capacity, B, max_iters, K, reproj_err, confidence, c->d_ransac, d_T_c_w, d_inlier, d_n_inliers, d_iters_run, c->stream);
+    return launch_pnp_ransac_batch(d_xyz_w, d_uv, d_n, capacity, B, max_iters, K, reproj_err, confidence, c->ransac, d_T_c_w, d_inlier, d_n_inliers, d_iters_run, c->stream);
 }
 
 // diagnostic form: additionally returns every hypothesis model ([R row-major | t], 12 doubles each) and its inlier count (-1: degenerate)
@@ -989,19 +966,11 @@ static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, in
     }
     if (in->kp_capacity > 65536) { set_error("kp_capacity %d exceeds 65536 (the window builder packs a keypoint index into 16 bits)", in->kp_capacity); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    const size_t need = track_scratch_bytes(in->n_frames, in->kp_capacity, lm_capacity, kp.policy, kp.gate);
-    if (c->track_bytes < need) {
-        VS_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_track) { (void)hipFree(c->d_track); c->dev_bytes -= c->track_bytes; }
-        c->d_track = nullptr; c->track_bytes = 0;
-        if (hipMalloc((void**)&c->d_track, need) != hipSuccess) { c->d_track = nullptr; set_error("track scratch hipMalloc(%zu) failed", need); return VSLAM_ERR_HIP; }
-        c->track_bytes = need; c->dev_bytes += need;
-    }
     out->n_windows = in->n_frames; out->n_kf = n_kf; out->total_lm = lm_capacity; out->total_edge = edge_capacity;
     double K4[4];
     fill_K(c, K4);
     const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
-    return launch_build_windows(*in, n_kf, lm_capacity, edge_capacity, K4, c->p.pnp_reproj_thr, track_rule, c->d_track, const_cast<int32_t*>(out->d_lm_off), const_cast<int32_t*>(out->d_edge_off),
+    return launch_build_windows(*in, n_kf, lm_capacity, edge_capacity, K4, c->p.pnp_reproj_thr, track_rule, c->track, const_cast<int32_t*>(out->d_lm_off), const_cast<int32_t*>(out->d_edge_off),
                                 const_cast<int32_t*>(out->d_n_kf), out->d_T_c_w, out->d_xyz, const_cast<uint8_t*>(out->d_reliable), out->d_lm_inlier,
                                 const_cast<int32_t*>(out->d_kf_idx), const_cast<int32_t*>(out->d_lm_idx), const_cast<float*>(out->d_uv), d_status, kp, c->stream);
 }

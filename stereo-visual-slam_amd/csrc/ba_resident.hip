@@ -1337,10 +1337,15 @@ static int rs_lds_per_cu(int device) {
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || v <= 0) v = 64 * 1024;
     return v;
 }
-// dynamic LDS of the narrow form: two windows (workgroups of four waves at 256 VGPRs) share a CU, half of its LDS each
-int rs_dyn_lds_bytes(int device) {
-    const int avail = rs_lds_per_cu(device) / 2 - (int)sizeof(RsShared) - 256;
-    return avail > 0 ? (avail & ~255) : 0;
+// dynamic LDS of the narrow form: two windows (workgroups of four waves at 256 VGPRs) share a CU, half of its LDS each; of the wide form:
+// the whole CU's LDS
+void rs_query_device(int device, LmScratch& s) {
+    const int lds = rs_lds_per_cu(device), narrow = lds / 2 - (int)sizeof(RsShared) - 256, full = lds - (int)sizeof(RsShared) - 256;
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n <= 0) n = 256;
+    s.rs_dyn_bytes = narrow > 0 ? (narrow & ~255) : 0;
+    s.rs_full_bytes = full > 0 ? (full & ~255) : 0;
+    s.rs_cu_count = n;
 }
 
 int launch_ba_resident(const RsLaunch& L, hipStream_t stream) {
@@ -1352,25 +1357,14 @@ int launch_ba_resident(const RsLaunch& L, hipStream_t stream) {
     ra.want_chi2 = L.want_chi2; ra.dense_to_general = L.dense_to_general;
     // width: more windows than CUs -> 256 lanes, two windows per CU (throughput); otherwise 512 lanes and the whole CU's LDS (a window's latency).
     // Both widths give the same bits (see kRsStreams), so the choice may depend on the launch.
-    static int s_cus[16] = {0}, s_full[16] = {0};
-    int dev = 0;
-    VS_HIP(hipGetDevice(&dev));
-    const int di = dev >= 0 && dev < 16 ? dev : 0;
-    if (!s_cus[di]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        const int full = rs_lds_per_cu(dev) - (int)sizeof(RsShared) - 256;
-        s_full[di] = full > 0 ? (full & ~255) : 0;
-        s_cus[di] = n;
-    }
-    const int lanes = L.lanes == 256 || L.lanes == 512 ? L.lanes : (L.a.n_windows <= s_cus[di] ? 512 : 256);
-    const int dyn = lanes == 512 ? s_full[di] : L.dyn_bytes;
+    const int lanes = L.lanes == 256 || L.lanes == 512 ? L.lanes : (L.a.n_windows <= L.cu_count ? 512 : 256);
+    const int dyn = lanes == 512 ? L.full_bytes : L.dyn_bytes;
     ra.dyn_bytes = dyn; ra.dyn_narrow = L.dyn_bytes;
     if (!L.opt_in_done) { // more than 64 KB of dynamic LDS needs the opt-in (once per context, i.e. per device)
         VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, L.dyn_bytes));
         VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<false, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, L.dyn_bytes));
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<true, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, s_full[di]));
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, s_full[di]));
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<true, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, L.full_bytes));
+        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, L.full_bytes));
     }
     if (lanes == 512) {
         if (L.schedule) hipLaunchKernelGGL((ba_resident_kernel<true, 512>), dim3(L.a.n_windows), dim3(512), (size_t)dyn, stream, ra, 5, 0, 0, 1, L.adaptive);

@@ -1785,57 +1785,37 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
 #undef POH
 }
 
-// (LmScratch, owned by the context and grown on demand, is declared in vslam_internal.h)
-static int ensure(void** p, size_t* have, size_t need) {
-    if (*have >= need) return VSLAM_OK;
-    if (*p) VS_HIP(hipFree(*p));
-    *p = nullptr; *have = 0;
-    if (hipMalloc(p, need) != hipSuccess) { set_error("LM scratch hipMalloc(%zu) failed", need); return VSLAM_ERR_HIP; }
-    *have = need;
-    return VSLAM_OK;
-}
-
-static int carve(LmScratch& g_lm, LmKernelArgs& ka, size_t total_lm, size_t total_edge, int n_windows, bool with_lm, hipStream_t stream) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t need = 0;
-    const size_t o_P = need; need += al(total_lm * 3 * 8);
-    const size_t o_Pt = need; need += al(total_lm * 3 * 8);
-    const size_t o_Hll = need; need += al(total_lm * 6 * 8);
-    const size_t o_bl = need; need += al(total_lm * 3 * 8);
-    const size_t o_Di = need; need += al(total_lm * 6 * 8);
-    const size_t o_lin = need; need += al(total_edge * kLin * 8);
-    const size_t o_lmptr = need; need += al((total_lm + n_windows + 1) * 4);
-    const size_t o_kfptr = need; need += al((size_t)n_windows * (kMaxKf + 1) * 4);
-    const size_t o_kfe = need; need += al(total_edge * 4);
-    const size_t o_pp = need; need += al((size_t)n_windows * (kMaxPairs + 1) * 4);
-    const size_t o_hits = need; need += with_lm ? al(total_edge * kHitsPerEdge * 8) : 256;
-    const size_t o_act = need; need += al(total_lm);
-    const size_t o_kpos = need; need += al(total_edge * 4);
-    const size_t o_st = need; need += al((size_t)n_windows * 4);
-    const size_t o_chi = need; need += al(total_edge * 8);
-    const size_t o_chik = need; need += al(total_edge * 8);
-    const size_t o_uvk = need; need += al(total_edge * 8);
-    const size_t o_suv = need; need += with_lm ? al(total_lm * kLmSlots * 8) : 256;
-    const size_t o_skf = need; need += with_lm ? al(total_lm * kLmSlots) : 256;
-    const size_t o_lcnt = need; need += al(total_lm);
-    const size_t o_ord = need; need += al((size_t)n_windows * 4);
-    const size_t o_pass = need; need += al((size_t)n_windows * 4);
-    const size_t o_defer = need; need += al((size_t)n_windows * 4);
-    // hipFree/hipMalloc are synchronising; growth only happens on the first call of a given size
-    if (g_lm.bytes < need) { hipStreamSynchronize(stream); int rc = ensure(&g_lm.buf, &g_lm.bytes, need); if (rc) return rc; }
-    uint8_t* base = (uint8_t*)g_lm.buf;
-    ka.a.P = (double*)(base + o_P); ka.a.Ptrial = (double*)(base + o_Pt); ka.a.Hll = (double*)(base + o_Hll);
-    ka.a.bl = (double*)(base + o_bl); ka.a.Dinv = (double*)(base + o_Di);
-    ka.a.lin = (double*)(base + o_lin); ka.a.lm_ptr = (int32_t*)(base + o_lmptr); ka.a.kf_ptr = (int32_t*)(base + o_kfptr);
-    ka.a.kf_edges = (int32_t*)(base + o_kfe); ka.a.pair_ptr = (int32_t*)(base + o_pp); ka.a.pair_hits = (int32_t*)(base + o_hits);
-    ka.act = base + o_act; ka.kf_pos = (int32_t*)(base + o_kpos); ka.status = (int32_t*)(base + o_st);
-    g_lm.status = ka.status; g_lm.status_n = n_windows;
-    if (!ka.a.chi2) ka.a.chi2 = (double*)(base + o_chi);
-    ka.chi2k = (double*)(base + o_chik); ka.uvk = (float*)(base + o_uvk);
-    ka.slot_uv = (float*)(base + o_suv); ka.slot_kf = base + o_skf; ka.lcnt = base + o_lcnt;
-    ka.order = (const int32_t*)(base + o_ord); // (filled by lm_order_kernel when the launcher wants it; cleared to null otherwise)
-    ka.passes = (int32_t*)(base + o_pass); g_lm.passes = ka.passes;
-    g_lm.defer = (int32_t*)(base + o_defer);
+// the scratch of one LM launch in the context's LmScratch (declared in vslam_internal.h).  Without landmarks (PnP) the landmark-wise
+// tables are 256-byte placeholders.
+static int carve_lm(LmScratch& s, LmKernelArgs& ka, size_t total_lm, size_t total_edge, int n_windows, bool with_lm, hipStream_t stream) {
+    int32_t* defer;
+    if (int rc = carve(s.buf, stream, [&](Layout& L) {
+            ka.a.P = L.take<double>(total_lm * 3);
+            ka.a.Ptrial = L.take<double>(total_lm * 3);
+            ka.a.Hll = L.take<double>(total_lm * 6);
+            ka.a.bl = L.take<double>(total_lm * 3);
+            ka.a.Dinv = L.take<double>(total_lm * 6);
+            ka.a.lin = L.take<double>(total_edge * kLin);
+            ka.a.lm_ptr = L.take<int32_t>(total_lm + n_windows + 1);
+            ka.a.kf_ptr = L.take<int32_t>((size_t)n_windows * (kMaxKf + 1));
+            ka.a.kf_edges = L.take<int32_t>(total_edge);
+            ka.a.pair_ptr = L.take<int32_t>((size_t)n_windows * (kMaxPairs + 1));
+            ka.a.pair_hits = L.take<int32_t>(with_lm ? total_edge * kHitsPerEdge * 2 : 64); // (8 B per hit)
+            ka.act = L.take<uint8_t>(total_lm);
+            ka.kf_pos = L.take<int32_t>(total_edge);
+            ka.status = L.take<int32_t>(n_windows);
+            double* chi2 = L.take<double>(total_edge);
+            if (!ka.a.chi2) ka.a.chi2 = chi2;
+            ka.chi2k = L.take<double>(total_edge);
+            ka.uvk = L.take<float>(total_edge * 2);
+            ka.slot_uv = L.take<float>(with_lm ? total_lm * kLmSlots * 2 : 64);
+            ka.slot_kf = L.take<uint8_t>(with_lm ? total_lm * kLmSlots : 256);
+            ka.lcnt = L.take<uint8_t>(total_lm);
+            ka.order = L.take<int32_t>(n_windows); // (filled by lm_order_kernel when the launcher wants it; cleared to null otherwise)
+            ka.passes = L.take<int32_t>(n_windows);
+            defer = L.take<int32_t>(n_windows);
+        })) return rc;
+    s.status = ka.status; s.status_n = n_windows; s.passes = ka.passes; s.defer = defer;
     return VSLAM_OK;
 }
 
@@ -1884,15 +1864,11 @@ int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, 
     }
     if (getenv("VSLAM_LM_PROFILE")) {
         const size_t cyc_need = sizeof(long long) * kDbgSlots * a.n_windows;
-        if (scratch->cyc_bytes < cyc_need) {
-            VS_HIP(hipStreamSynchronize(stream));
-            int rc = ensure((void**)&scratch->cyc, &scratch->cyc_bytes, cyc_need);
-            if (rc) return rc;
-        }
-        VS_HIP(hipMemsetAsync(scratch->cyc, 0, cyc_need, stream));
-        ka.dbg_cycles = scratch->cyc;
+        if (int rc = scratch->cyc.reserve(cyc_need, stream)) return rc;
+        VS_HIP(hipMemsetAsync(scratch->cyc.p, 0, cyc_need, stream));
+        ka.dbg_cycles = (long long*)scratch->cyc.p;
     }
-    int rc = carve(*scratch, ka, total_lm, total_edge, a.n_windows, true, stream);
+    int rc = carve_lm(*scratch, ka, total_lm, total_edge, a.n_windows, true, stream);
     if (rc) return rc;
     // Tuning::ba_adaptive (default on): ONE launch runs a window's passes back to back, and a pass that flags nothing new is continued to the last pass's
     // 10 iterations instead of being repeated (see the kernel); 0: the three passes as three launches, every one of them for every window
@@ -1907,13 +1883,13 @@ int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, 
     const bool resident = (schedule || mode == 0) && !(scratch->tune && scratch->tune->ba_resident == 0);
     scratch->defer_valid = resident;
     if (resident) {
-        if (scratch->rs_dyn_bytes < 0) { int dev = 0; (void)hipGetDevice(&dev); scratch->rs_dyn_bytes = rs_dyn_lds_bytes(dev); }
+        if (scratch->rs_dyn_bytes < 0) { int dev = 0; VS_HIP(hipGetDevice(&dev)); rs_query_device(dev, *scratch); }
         RsLaunch L;
         memset(&L, 0, sizeof(L));
         L.a = ka.a; L.uv_s = ka.uvk; L.epos = ka.kf_pos; L.tab = ka.a.Hll; L.xin = ka.a.Ptrial; L.Pbak = ka.a.P; L.Dc = ka.a.Dinv; L.blc = ka.a.bl;
         L.status = ka.status; L.passes = ka.passes; L.defer = scratch->defer; L.order = ka.order; L.dbg = getenv("VSLAM_RS_PROFILE") ? ka.dbg_cycles : nullptr;
         L.lanes = (scratch->tune && scratch->tune->ba_lanes > 0) ? scratch->tune->ba_lanes : 0;
-        L.dyn_bytes = scratch->rs_dyn_bytes; L.schedule = schedule; L.adaptive = adaptive ? 1 : 0; L.iters = iters; L.update_poses = update_poses; L.update_lms = update_lms;
+        L.dyn_bytes = scratch->rs_dyn_bytes; L.full_bytes = scratch->rs_full_bytes; L.cu_count = scratch->rs_cu_count; L.schedule = schedule; L.adaptive = adaptive ? 1 : 0; L.iters = iters; L.update_poses = update_poses; L.update_lms = update_lms;
         L.opt_in_done = scratch->rs_opt_in; L.want_chi2 = ka.want_chi2;
         L.dense_to_general = !(scratch->tune && scratch->tune->ba_resident == 1);
         if (schedule && !adaptive) hipLaunchKernelGGL(lm_fill_kernel, dim3((a.n_windows + 255) / 256), dim3(256), 0, stream, ka.passes, a.n_windows, 3);
@@ -1969,7 +1945,7 @@ int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, 
 }
 
 int lm_fetch_deferred(const LmScratch* scratch, int n_windows, int32_t* h_defer, hipStream_t stream) {
-    if (!scratch->buf || !scratch->defer || !h_defer || n_windows > scratch->status_n) return VSLAM_ERR_ARG;
+    if (!scratch->buf.p || !scratch->defer || !h_defer || n_windows > scratch->status_n) return VSLAM_ERR_ARG;
     if (!scratch->defer_valid) { for (int w = 0; w < n_windows; ++w) h_defer[w] = 1; return VSLAM_OK; } // the last launch did not involve ba_resident_kernel: every window on lm_window_kernel
     VS_HIP(hipMemcpyAsync(h_defer, scratch->defer, sizeof(int32_t) * n_windows, hipMemcpyDeviceToHost, stream));
     VS_HIP(hipStreamSynchronize(stream));
@@ -1978,7 +1954,7 @@ int lm_fetch_deferred(const LmScratch* scratch, int n_windows, int32_t* h_defer,
 }
 
 int lm_fetch_passes(const LmScratch* scratch, int n_windows, int32_t* h_passes, hipStream_t stream) {
-    if (!scratch->buf || !scratch->passes || !h_passes || n_windows > scratch->status_n) return VSLAM_ERR_ARG;
+    if (!scratch->buf.p || !scratch->passes || !h_passes || n_windows > scratch->status_n) return VSLAM_ERR_ARG;
     VS_HIP(hipMemcpyAsync(h_passes, scratch->passes, sizeof(int32_t) * n_windows, hipMemcpyDeviceToHost, stream));
     VS_HIP(hipStreamSynchronize(stream));
     return VSLAM_OK;
@@ -1986,8 +1962,8 @@ int lm_fetch_passes(const LmScratch* scratch, int n_windows, int32_t* h_passes, 
 
 int lm_fetch_status(const LmScratch* scratch, int n_windows, int32_t* h_status, hipStream_t stream) {
     const LmScratch& g_lm = *scratch;
-    if (!g_lm.buf || !h_status) return VSLAM_ERR_ARG;
-    // the status words of the most recent launch live at a fixed offset that carve() recorded
+    if (!g_lm.buf.p || !h_status) return VSLAM_ERR_ARG;
+    // the status words of the most recent launch live at a fixed offset that carve_lm() recorded
     VS_HIP(hipMemcpyAsync(h_status, g_lm.status, sizeof(int32_t) * n_windows, hipMemcpyDeviceToHost, stream));
     VS_HIP(hipStreamSynchronize(stream));
     return VSLAM_OK;
@@ -2049,7 +2025,7 @@ int launch_pnp(const PnpArgs& p, LmScratch* scratch, hipStream_t stream) {
     ka.a.huber_delta = p.huber_delta;
     ka.pnp_n = p.n; ka.capacity = p.capacity;
     const size_t tot = (size_t)p.B * p.capacity;
-    int rc = carve(*scratch, ka, tot, tot, p.B, false, stream);
+    int rc = carve_lm(*scratch, ka, tot, tot, p.B, false, stream);
     if (rc) return rc;
     ka.order = nullptr; // (problem b runs on workgroup b)
     ProfScope prof__(stream, "lm_window_kernel<pnp>", 2);

@@ -265,6 +265,7 @@ int orb_tables_init(const OrbPlan* plan, OrbTables* t) {
         hipMemcpy(t->d_ialpha, ialpha, sizeof(short) * 2 * nx, hipMemcpyHostToDevice);
         hipMemcpy(t->d_yofs, yofs, sizeof(int) * ny, hipMemcpyHostToDevice);
         hipMemcpy(t->d_ibeta, ibeta, sizeof(short) * 2 * ny, hipMemcpyHostToDevice);
+        t->bytes = sizeof(int) * (tdx.size() + tdy.size() + nx + ny) + sizeof(short) * 2 * (nx + ny);
     } while (0);
     delete[] xofs; delete[] ialpha; delete[] yofs; delete[] ibeta;
     int dev = 0;

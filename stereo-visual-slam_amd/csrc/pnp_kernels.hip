@@ -621,25 +621,21 @@ __global__ __launch_bounds__(128) void pnp_ransac_select_kernel(const float* __r
         m[i] = i < n ? (nh == 1 ? (uint8_t)1 : (uint8_t)ransac_point_is_inlier(sR, px, pu, i, fx, fy, cx, cy, thr2)) : (uint8_t)0;
 }
 
-size_t pnp_ransac_scratch_bytes(int B, int H) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nh = (size_t)B * H;
-    return al(nh * kMp * 3 * 4) + al(nh * kMp * 2 * 4) + al(nh * 12 * 8) + al(nh * 7 * 8) + 2 * al(nh * 4) + al((size_t)B * 4) + al(pnp_epnp_ws_bytes((int)nh));
-}
-
 int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t* d_n, int capacity, int B, int H, const double K[4], double reproj_err,
-                            double confidence, uint8_t* scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream) {
+                            double confidence, DevBuf& scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream) {
     if (B <= 0) return VSLAM_OK;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t nh = (size_t)B * H;
-    float* hx = (float*)scratch; scratch += al(nh * kMp * 3 * 4);
-    float* hu = (float*)scratch; scratch += al(nh * kMp * 2 * 4);
-    double* Rt = (double*)scratch; scratch += al(nh * 12 * 8);
-    double* hT = (double*)scratch; scratch += al(nh * 7 * 8);
-    int32_t* ok = (int32_t*)scratch; scratch += al(nh * 4);
-    int32_t* cnt = (int32_t*)scratch; scratch += al(nh * 4);
-    int32_t* nh_of = (int32_t*)scratch; scratch += al((size_t)B * 4);
-    double* ws = (double*)scratch;
+    float *hx, *hu; double *Rt, *hT, *ws; int32_t *ok, *cnt, *nh_of;
+    if (int rc = carve(scratch, stream, [&](Layout& L) {
+            hx = L.take<float>(nh * kMp * 3);
+            hu = L.take<float>(nh * kMp * 2);
+            Rt = L.take<double>(nh * 12);
+            hT = L.take<double>(nh * 7);
+            ok = L.take<int32_t>(nh);
+            cnt = L.take<int32_t>(nh);
+            nh_of = L.take<int32_t>(B);
+            ws = (double*)L.take<uint8_t>(pnp_epnp_ws_bytes((int)nh));
+        })) return rc;
     const float thr2 = (float)(reproj_err * reproj_err);
     { ProfScope p(stream, "pnp_ransac_subsets_kernel");
       hipLaunchKernelGGL(pnp_ransac_subsets_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, d_xyz, d_uv, d_n, capacity, B, H, hx, hu, nh_of); }

@@ -878,7 +878,7 @@ __global__ __launch_bounds__(256) void sgbm_ccl_apply_kernel(int w, int h, int n
 
 // ------------------------------------------------------------------------------------------- host driver
 int launch_sgbm(const Tuning& tune, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B, float* d_disp_f32,
-                int16_t* d_disp_i16, int16_t* d_disp_raw, uint8_t** scratch, size_t* scratch_bytes, size_t* dev_bytes, hipStream_t stream) {
+                int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream) {
     if (B <= 0) return VSLAM_OK;
     SgbmDims dm;
     dm.w = w; dm.h = h; dm.D = 96; dm.minX1 = 96; dm.width1 = w - 96; dm.P1 = 8 * 9 * 9; dm.P2 = 32 * 9 * 9; dm.SW2 = 4; dm.SH2 = 4; dm.uniq = 10;
@@ -886,37 +886,28 @@ int launch_sgbm(const Tuning& tune, const uint8_t* d_left, const uint8_t* d_righ
     // width1 <= SW2 is undefined in OpenCV 3.2 (unclamped read of pixel-cost columns 0..SW2), so it is an argument error here.
     if (dm.width1 <= dm.SW2 || h <= 2 * dm.SH2 + 1 || w > 4096) { set_error("image size unsupported (need 100 < w <= 4096, h > 9)"); return VSLAM_ERR_ARG; }
     const size_t vol = (size_t)h * dm.width1 * dm.D, npix = (size_t)w * h;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t need = 256; // header: int32 [0..7] ticket pools of the forward sweep, [8] its error word (vslam_sgbm_status_dev)
-    const size_t o_pre = need; need += al((size_t)2 * B * h * 6 * w);
-    const size_t o_hs = need; need += al((size_t)B * vol * 2);
-    const size_t o_C = need; need += al((size_t)B * vol * 2);
-    const size_t o_T = o_hs; // hsum is dead once C exists: T reuses its storage (the fused top-down pass never materialises hsum at all)
-    const size_t o_rec = need; need += al((size_t)B * npix * 16);
-    const size_t o_d0 = need; need += al((size_t)B * npix * 2);
-    const size_t o_d1 = need; need += al((size_t)B * npix * 2);
-    const size_t o_par = need; need += al((size_t)B * npix * 4);
-    const size_t o_cnt = need; need += al((size_t)B * npix * 4);
     // forward sweep: 32-row slabs (workgroups of 512 threads, two per CU) up to 32 pairs, 64-row slabs above.  The slabs of a pair are a chain
     // of ~2 200 (64 rows) / ~2 600 (32 rows) steps and a step's time is mostly its latency (barrier, LDS mailbox, the dependent minimum ->
     // delta -> update chain), so shorter workgroups win until the chip is full: 16 / 24 / 32 / 40 pairs 2.33 / 2.60 / 2.93 / 3.45 ms with 32
     // rows, 3.01 / 3.06 / 3.19 / 3.35 ms with 64 (48-row slabs: 2.64 / 2.76 / 2.92 / 3.31 -- no better anywhere).  Tuning::sgbm_fw_rows overrides.
     const int fw_rows = tune.sgbm_fw_rows > 0 ? tune.sgbm_fw_rows : (B <= 32 ? 32 : 64);
     const int nslab = (h + fw_rows - 1) / fw_rows;
-    const size_t o_bnd = need; need += al((size_t)B * (nslab > 1 ? nslab - 1 : 1) * ((dm.width1 + kFwChunk - 1) / kFwChunk + 1) * kFwChunk * kFwRecDw * 4);
-    const size_t o_flag = need; need += al((size_t)B * nslab * 4);
-    if (*scratch_bytes < need) {
-        VS_HIP(hipStreamSynchronize(stream));
-        if (*scratch) { (void)hipFree(*scratch); *dev_bytes -= *scratch_bytes; }
-        *scratch = nullptr; *scratch_bytes = 0;
-        if (hipMalloc((void**)scratch, need) != hipSuccess) { *scratch = nullptr; set_error("SGBM scratch hipMalloc(%zu) failed", need); return VSLAM_ERR_HIP; }
-        *scratch_bytes = need; *dev_bytes += need;
-    }
-    uint8_t* base = *scratch;
-    VS_HIP(hipMemsetAsync(base, 0, 64, stream)); // ticket pools + error word of this launch
-    uint8_t* pre = base + o_pre; int16_t* hsum = (int16_t*)(base + o_hs); int16_t* C = (int16_t*)(base + o_C);
-    uint16_t* T = (uint16_t*)(base + o_T); int4* rec = (int4*)(base + o_rec);
-    int16_t* d0 = (int16_t*)(base + o_d0); int16_t* d1 = (int16_t*)(base + o_d1); int* par = (int*)(base + o_par); int* cnt = (int*)(base + o_cnt);
+    int* hdr; uint8_t* pre; int16_t *hsum, *C, *d0, *d1; int4* rec; int *par, *cnt, *flag; uint32_t* bnd;
+    if (int rc = carve(scratch, stream, [&](Layout& L) {
+            hdr = L.take<int>(64); // int32 [0, kSgbmErrorWord): ticket pools of the forward sweep, [kSgbmErrorWord]: its error word
+            pre = L.take<uint8_t>((size_t)2 * B * h * 6 * w);
+            hsum = L.take<int16_t>(B * vol);
+            C = L.take<int16_t>(B * vol);
+            rec = L.take<int4>(B * npix);
+            d0 = L.take<int16_t>(B * npix);
+            d1 = L.take<int16_t>(B * npix);
+            par = L.take<int>(B * npix);
+            cnt = L.take<int>(B * npix);
+            bnd = L.take<uint32_t>((size_t)B * (nslab > 1 ? nslab - 1 : 1) * ((dm.width1 + kFwChunk - 1) / kFwChunk + 1) * kFwChunk * kFwRecDw);
+            flag = L.take<int>((size_t)B * nslab);
+        })) return rc;
+    uint16_t* T = (uint16_t*)hsum; // hsum is dead once C exists: T reuses its storage (the fused top-down pass never materialises hsum at all)
+    VS_HIP(hipMemsetAsync(hdr, 0, 64, stream)); // ticket pools + error word of this launch
     { ProfScope p(stream, "sgbm_prefilter_kernel"); hipLaunchKernelGGL(sgbm_prefilter_kernel, dim3((w + 255) / 256, h, 2 * B), dim3(256), 0, stream, dm, d_left, d_right, pre); }
     // The fused top-down kernel sweeps the rows sequentially with 48 workgroups per pair: it pays from 8 pairs per call on (2.65 vs 4.08 ms
     // at 32 pairs); below that the three massively parallel kernels it replaces are faster (0.99 vs 1.31 ms for one pair).
@@ -928,10 +919,10 @@ int launch_sgbm(const Tuning& tune, const uint8_t* d_left, const uint8_t* d_righ
     if (!unfused && !fwd) { ProfScope p(stream, "sgbm_down_kernel"); hipLaunchKernelGGL(sgbm_down_kernel<true>, dim3((dm.width1 + kDnCols - 1) / kDnCols, B), dim3(kDnThreads), 0, stream, dm, pre, C, T); }
     if (fwd) {
         { ProfScope p(stream, "sgbm_down_kernel"); hipLaunchKernelGGL(sgbm_down_kernel<false>, dim3((dm.width1 + kDnCols - 1) / kDnCols, B), dim3(kDnThreads), 0, stream, dm, pre, C, T); }
-        VS_HIP(hipMemsetAsync(base + o_flag, 0, (size_t)B * nslab * 4, stream));
+        VS_HIP(hipMemsetAsync(flag, 0, (size_t)B * nslab * 4, stream));
         ProfScope p(stream, "sgbm_forward_kernel");
-        if (fw_rows == 64) hipLaunchKernelGGL(sgbm_forward_kernel<64>, dim3(B * nslab), dim3(64 * 16), 0, stream, dm, C, (int16_t*)T, (uint32_t*)(base + o_bnd), (int*)(base + o_flag), (int*)base, nslab);
-        else hipLaunchKernelGGL(sgbm_forward_kernel<32>, dim3(B * nslab), dim3(32 * 16), 0, stream, dm, C, (int16_t*)T, (uint32_t*)(base + o_bnd), (int*)(base + o_flag), (int*)base, nslab);
+        if (fw_rows == 64) hipLaunchKernelGGL(sgbm_forward_kernel<64>, dim3(B * nslab), dim3(64 * 16), 0, stream, dm, C, (int16_t*)T, bnd, flag, hdr, nslab);
+        else hipLaunchKernelGGL(sgbm_forward_kernel<32>, dim3(B * nslab), dim3(32 * 16), 0, stream, dm, C, (int16_t*)T, bnd, flag, hdr, nslab);
     }
     if (unfused) { ProfScope p(stream, "sgbm_hsum_kernel"); hipLaunchKernelGGL(sgbm_hsum_kernel, dim3((dm.width1 + kHsSeg - 1) / kHsSeg, h, B), dim3(kHsBlock), 0, stream, dm, pre, hsum); }
     if (unfused) { ProfScope p(stream, "sgbm_vsum_kernel"); hipLaunchKernelGGL(sgbm_vsum_kernel, dim3((dm.width1 * 12 + 255) / 256, (h + kVsChunk - 1) / kVsChunk, B), dim3(256), 0, stream, dm, hsum, C); }

@@ -630,35 +630,30 @@ __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vsl
     rel_out[g] = has_rel; inl_out[g] = 1;
 }
 
-size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity, int policy, bool gate) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t base = al((size_t)lm_capacity * 4) + 6 * al((size_t)B * kp_cap * 4) + al((size_t)B * 7 * 8) + al((size_t)B * 2 * 4) + al((size_t)B * (VSLAM_MAX_KF + 1) * 4);
-    // culling: the chain records (int2 per slot), the distance band (B x kKfBand doubles), the set kernel's flags; the gate: also the member counts
-    const size_t set = base + al((size_t)B * kp_cap * 8) + al((size_t)B * kKfBand * 8) + 256;
-    return gate ? set + al((size_t)B * 4) : policy == 1 ? set : base;
-}
-
-int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, uint8_t* scratch,
+int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
                          int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     TrackDims d;
     d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = n_kf;
-    const size_t tab = al((size_t)d.B * d.kp_cap * 4);
-    int32_t* kp2lr = (int32_t*)scratch; int32_t* pred = (int32_t*)(scratch + tab); int32_t* succ = (int32_t*)(scratch + 2 * tab);
-    int32_t* root = (int32_t*)(scratch + 3 * tab); int32_t* relsrc = (int32_t*)(scratch + 4 * tab); int32_t* info = (int32_t*)(scratch + 5 * tab);
-    double* G = (double*)(scratch + 6 * tab); int32_t* counts = (int32_t*)(scratch + 6 * tab + al((size_t)d.B * 7 * 8));
-    int32_t* hist = (int32_t*)((uint8_t*)counts + al((size_t)d.B * 2 * 4));
-    uint32_t* head_rec = (uint32_t*)((uint8_t*)hist + al((size_t)d.B * (VSLAM_MAX_KF + 1) * 4));
     const bool gate = kp.gate, cull = kp.policy == 1 || gate; // (cull: the set-templated window kernels)
-    WindowSet ws = {kp.kf_frame, nullptr, root, nullptr};
-    double* D = nullptr; int32_t* set_flags = nullptr; int32_t* nmem = nullptr;
-    if (cull) {
-        ws.ends = (const int2*)((uint8_t*)head_rec + al((size_t)lm_capacity * 4));
-        D = (double*)((uint8_t*)ws.ends + al((size_t)d.B * d.kp_cap * 8));
-        set_flags = (int32_t*)((uint8_t*)D + al((size_t)d.B * kKfBand * 8));
-        if (gate) ws.nmem = nmem = (int32_t*)((uint8_t*)set_flags + 256);
-    }
+    const size_t tab = (size_t)d.B * d.kp_cap;
+    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *info, *counts, *hist; double* G; uint32_t* head_rec;
+    int2* ends = nullptr; double* D = nullptr; int32_t* set_flags = nullptr; int32_t* nmem = nullptr;
+    if (int rc = carve(scratch, stream, [&](Layout& L) {
+            kp2lr = L.take<int32_t>(tab); pred = L.take<int32_t>(tab); succ = L.take<int32_t>(tab);
+            root = L.take<int32_t>(tab); relsrc = L.take<int32_t>(tab); info = L.take<int32_t>(tab);
+            G = L.take<double>((size_t)d.B * 7);
+            counts = L.take<int32_t>((size_t)d.B * 2);
+            hist = L.take<int32_t>((size_t)d.B * (VSLAM_MAX_KF + 1));
+            head_rec = L.take<uint32_t>(lm_capacity);
+            if (cull) { // the chain records, the distance band, the set kernel's flags; the gate: also the member counts
+                ends = L.take<int2>(tab);
+                D = L.take<double>((size_t)d.B * kKfBand);
+                set_flags = L.take<int32_t>(64);
+                if (gate) nmem = L.take<int32_t>(d.B);
+            }
+        })) return rc;
+    const WindowSet ws = {kp.kf_frame, ends, root, nmem};
     TrackCam cam;
     cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
     int32_t* cand = info; // (the candidate words live in the info table until track_info_kernel writes it)
@@ -688,7 +683,7 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
         hipLaunchKernelGGL(track_carry_out_kernel, dim3((d.kp_cap + 255) / 256), dim3(256), 0, stream, d, in.carry_out_frame, kp2lr, pred, root, relsrc, in.d_xyz, G,
                            in.d_carry_in, in.d_carry_out);
     if (cull) {
-        hipLaunchKernelGGL(track_ends_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, succ, root, relsrc, const_cast<int2*>(ws.ends));
+        hipLaunchKernelGGL(track_ends_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, succ, root, relsrc, ends);
         hipLaunchKernelGGL(window_count_kernel<true>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist, ws);
         hipLaunchKernelGGL(window_scan_kernel<true>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags, nmem);
         hipLaunchKernelGGL(window_rank_kernel<true>, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec, ws);

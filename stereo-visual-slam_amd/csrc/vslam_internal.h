@@ -35,6 +35,44 @@ struct ProfScope {
     ~ProfScope() { prof_end(s); }
 };
 
+// ----------------------------------------------------------------------------------------------- device scratch
+// Slots bumped over a device buffer, each a whole number of 256-byte units.  With a null base it only measures.
+struct Layout {
+    uint8_t* base; size_t off = 0;
+    explicit Layout(uint8_t* b = nullptr) : base(b) {}
+    template <typename T> T* take(size_t n) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (n * sizeof(T) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
+// A growable device buffer of a context, accounted to the context's byte counter.  It only grows, on the first call that needs more,
+// after a synchronise of the stream that may still use it.
+struct DevBuf {
+    const char* name;      // for error messages
+    size_t* acct;          // the owning context's dev_bytes
+    size_t min_bytes;      // smallest allocation
+    uint8_t* p = nullptr; size_t bytes = 0;
+    DevBuf(const char* n, size_t* a, size_t min = 0) : name(n), acct(a), min_bytes(min) {}
+    int reserve(size_t need, hipStream_t stream);
+    void release();
+};
+
+// `layout(L&)` states the slots once: it runs against a null base to measure, `buf` grows to fit, and it runs again on `a` to carve `buf`
+template <typename L, typename F>
+int carve(DevBuf& buf, hipStream_t stream, L& a, F&& layout) {
+    L m(nullptr);
+    layout(m);
+    if (int rc = buf.reserve(m.off, stream)) return rc;
+    a.base = buf.p; a.off = 0;
+    layout(a);
+    if (a.off > buf.bytes) { set_error("%s layout uses %zu bytes of %zu reserved", buf.name, a.off, buf.bytes); return VSLAM_ERR_CAPACITY; }
+    return VSLAM_OK;
+}
+template <typename F>
+int carve(DevBuf& buf, hipStream_t stream, F&& layout) { Layout a; return carve(buf, stream, a, layout); }
+
 constexpr int kWave = 64;
 constexpr int kNLevels = VSLAM_ORB_NLEVELS;
 constexpr int kEdge = 31;            // ORB edgeThreshold
@@ -77,6 +115,7 @@ struct OrbTables {
     int* d_tile_dx;
     int* d_tile_dy;
     int tdx_off[kNLevels], tdy_off[kNLevels];
+    size_t bytes;     // device memory of the tables above
 };
 
 void orb_debug_enable();
@@ -190,7 +229,6 @@ struct LmWindowArgs {
     size_t total_lm, total_edge;
 };
 // mode 0 = optimize_map (EdgeProjection + Schur), 1 = optimize_pose_only.
-// sgbm_kernels.hip.  *scratch / *scratch_bytes: caller-owned growable device buffer.
 // Kernel-choice overrides of a context (tuning aid / tests): -1 = the library's batch-size rule.  Seeded ONCE at vslam_create from the
 // VSLAM_* environment variables of the same names (validated there), changed afterwards only through vslam_set_tuning -- no getenv on
 // the call path (it races with a host that mutates its environment).
@@ -210,34 +248,39 @@ struct Tuning {
                               // last-frame keypoint owns a valid depth (kept for before / after measurements)
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
 };
+// scratch: the context's SGBM buffer.  Its first 256-byte slot is a header of int32 words: the forward sweep's ticket pools, then its error word.
+constexpr int kSgbmTicketPools = 8;
+constexpr int kSgbmErrorWord = kSgbmTicketPools; // error word of the most recent launch (vslam_sgbm_status_dev)
 int launch_sgbm(const Tuning& tune, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B, float* d_disp_f32,
-                int16_t* d_disp_i16, int16_t* d_disp_raw, uint8_t** scratch, size_t* scratch_bytes, size_t* dev_bytes, hipStream_t stream);
-size_t sgbm_scratch_bytes(int w, int h, int B);
+                int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream);
 
 // device scratch of the LM kernels: owned by the context (two contexts / streams must not share it), grown on demand
 struct LmScratch {
-    void* buf = nullptr; size_t bytes = 0;
+    DevBuf buf, cyc; // the kernels' scratch; the phase clocks of the LM kernels (VSLAM_LM_PROFILE), kDbgSlots per window
     int32_t* status = nullptr; int status_n = 0;
     int32_t* passes = nullptr; // optimize_map passes executed per window by the most recent schedule (lm_fetch_passes)
     const Tuning* tune = nullptr; // the owning context's overrides
     bool lds_opt_in = false; // the > 64 KB dynamic-LDS attribute of lm_window_kernel has been set on this context's device
     bool rs_opt_in = false;  // ... of ba_resident_kernel
-    int rs_dyn_bytes = -1;   // dynamic LDS a ba_resident_kernel workgroup may use on this context's device (-1: not queried yet)
+    // ba_resident_kernel on this context's device (rs_query_device; rs_dyn_bytes -1: not queried yet): dynamic LDS of a 256-lane workgroup
+    // (two windows per CU) and of a 512-lane one (the whole CU), and the CU count
+    int rs_dyn_bytes = -1, rs_full_bytes = 0, rs_cu_count = 0;
     int32_t* defer = nullptr; // per window of the most recent launch: 1 = left to lm_window_kernel by ba_resident_kernel
     bool defer_valid = false; // ... written by that launch (it involved ba_resident_kernel)
-    long long* cyc = nullptr; size_t cyc_bytes = 0; // phase clocks of the LM kernels (VSLAM_LM_PROFILE), kDbgSlots per window
+    explicit LmScratch(size_t* acct) : buf("LM scratch", acct), cyc("LM clock buffer", acct) {}
 };
 // ba_resident.hip: optimize_map / the BA schedule on windows whose landmark state fits the LDS of one CU (the rest is marked in `defer`)
 struct RsLaunch {
     LmWindowArgs a;
     void* uv_s; int32_t* epos; double* tab; double* xin; double* Pbak; double* Dc; double* blc; // scratch slices (see RsArgs)
     int32_t* status; int32_t* passes; int32_t* defer; const int32_t* order; long long* dbg;
-    int dyn_bytes, schedule, adaptive, iters, update_poses, update_lms, dense_to_general;
-    int want_chi2;           // the CALLER asked for per-edge chi2 (L.a.chi2 is never null here: carve() substitutes scratch)
+    int dyn_bytes, full_bytes, cu_count; // LmScratch::rs_dyn_bytes, rs_full_bytes, rs_cu_count
+    int schedule, adaptive, iters, update_poses, update_lms, dense_to_general;
+    int want_chi2;           // the CALLER asked for per-edge chi2 (L.a.chi2 is never null here: the LM layout substitutes scratch)
     int lanes;               // 256 | 512 forces a width of ba_resident_kernel (Tuning::ba_lanes); 0: by the number of windows in the launch
     bool opt_in_done;
 };
-int rs_dyn_lds_bytes(int device);
+void rs_query_device(int device, LmScratch& s);
 int launch_ba_resident(const RsLaunch& L, hipStream_t stream);
 int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, int update_poses, int update_lms, LmScratch* scratch,
                       hipStream_t stream);
@@ -261,17 +304,15 @@ int launch_pnp_epnp(const float* d_hx, const float* d_hu, int H, const double K[
 int launch_pnp_count_inliers(const float* d_xyz, const float* d_uv, int n, const double* d_Rt, const int32_t* d_ok, int hyp0, int n_hyp, const double K[4],
                              double reproj_thr, int32_t* d_counts, uint8_t* d_mask, hipStream_t stream);
 
-size_t pnp_ransac_scratch_bytes(int B, int H);
 int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t* d_n, int capacity, int B, int H, const double K[4], double reproj_err,
-                            double confidence, uint8_t* scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream);
+                            double confidence, DevBuf& scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream);
 // track_kernels.hip: BA windows of a batch of consecutive keyframes from the front end's device-resident output
 // Which keyframes a window holds (vslam_build_windows_kf_dev): policy -1 = the sliding window with no set outputs (vslam_build_windows_dev),
-// 0 = the sliding window with its sets written to kf_frame / evicted, 1 = the reference's culling (needs the extra scratch of track_scratch_bytes).
+// 0 = the sliding window with its sets written to kf_frame / evicted, 1 = the reference's culling (needs extra scratch).
 // gate (vslam_build_windows_gated_dev): insert_key_frame's keyframe gate on num_inliers (n_frames - 1) and T_rel, states to frame_state; policy 0 / 1.
 struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evicted; bool gate = false; const int32_t* num_inliers = nullptr; int32_t* frame_state = nullptr; };
-size_t track_scratch_bytes(int B, int kp_cap, int lm_capacity, int policy, bool gate = false);
 // K4 = {fx, fy, cx, cy}, reproj_thr (pixels), track_rule: see Tuning::track_rule
-int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, uint8_t* scratch,
+int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
                          int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream);
 
@@ -286,15 +327,13 @@ struct Ctx {
     OrbTables tab;
     OrbBuffers orb;
     MatchBuffers match;
-    // staging for the host-buffer API (sized for one item)
-    uint8_t* d_stage; size_t stage_bytes;
+    DevBuf stage{"staging", &dev_bytes, (size_t)1 << 20}; // staging for the host-buffer API (sized for one item)
     uint8_t* h_pinned; size_t pinned_bytes;
-    // SGBM working set (cost volumes; grown on demand by vslam_disparity_map*)
-    uint8_t* d_sgbm; size_t sgbm_bytes;
+    DevBuf sgbm{"SGBM scratch", &dev_bytes}; // cost volumes of vslam_disparity_map*
     bool sgbm_unchecked;  // an asynchronous SGBM launch whose error word nobody has read yet (vslam_sync / vslam_sgbm_status_dev do)
-    uint8_t* d_ransac; size_t ransac_bytes; // hypothesis tables of vslam_pnp_ransac_dev (grown on demand)
-    uint8_t* d_track; size_t track_bytes; // chain tables of vslam_build_windows_dev (grown on demand)
-    LmScratch lm;
+    DevBuf ransac{"RANSAC scratch", &dev_bytes}; // hypothesis tables of vslam_pnp_ransac_dev
+    DevBuf track{"track scratch", &dev_bytes};   // chain tables of vslam_build_windows_dev
+    LmScratch lm{&dev_bytes};
     Tuning tune;
     Prof* prof;           // stage profiler of this context (vslam_profile_enable); null until first enabled
 };

@@ -198,6 +198,42 @@ def test_schedule_pose_only_wave_vs_window_kernel(pkg, synth):
         ctx.close()
 
 
+def test_device_bytes_count_the_lm_scratch(pkg, synth):
+    """vslam_device_bytes counts the LM scratch: the first vslam_ba_batch_dev on device-resident windows (no staging) grows it, a second
+    call of the same shape reuses it"""
+    import torch
+    wins = [synth.ba_window_fast(n_kf=10, n_lm=500, seed=400 + i) for i in range(2)]
+    lm_off = np.cumsum([0] + [len(w["xyz"]) for w in wins]).astype(np.int32)
+    e_off = np.cumsum([0] + [len(w["kf_idx"]) for w in wins]).astype(np.int32)
+    ctx = pkg.VO(device=0, max_batch=1)
+    try:
+        d = "cuda"
+        T = torch.from_numpy(np.stack([w["T0"] for w in wins])).to(d)
+        xyz = torch.from_numpy(np.concatenate([w["xyz"] for w in wins])).to(d)
+        kf = torch.from_numpy(np.concatenate([w["kf_idx"] for w in wins])).to(d)
+        lm = torch.from_numpy(np.concatenate([w["lm_idx"] for w in wins])).to(d)
+        uv = torch.from_numpy(np.concatenate([w["uv"] for w in wins])).to(d)
+        inl = torch.ones(int(lm_off[-1]), dtype=torch.uint8, device=d)
+        t_lm, t_e = torch.from_numpy(lm_off).to(d), torch.from_numpy(e_off).to(d)
+        bb = pkg.BaBatch()
+        bb.n_windows = 2; bb.n_kf = 10
+        bb.d_lm_off = t_lm.data_ptr(); bb.d_edge_off = t_e.data_ptr(); bb.d_T_c_w = T.data_ptr(); bb.d_xyz = xyz.data_ptr()
+        bb.d_reliable = None; bb.d_lm_inlier = inl.data_ptr(); bb.d_kf_idx = kf.data_ptr(); bb.d_lm_idx = lm.data_ptr(); bb.d_uv = uv.data_ptr()
+        bb.d_chi2 = None; bb.d_stats = None; bb.total_lm = int(lm_off[-1]); bb.total_edge = int(e_off[-1])
+        torch.cuda.synchronize()
+        before = ctx.device_bytes
+        ctx.ba_batch_dev(bb, schedule=1)
+        ctx.sync()
+        assert (ctx.ba_status(2) == 0).all()
+        grown = ctx.device_bytes
+        assert grown > before, (before, grown)
+        ctx.ba_batch_dev(bb, schedule=1)
+        ctx.sync()
+        assert ctx.device_bytes == grown
+    finally:
+        ctx.close()
+
+
 def test_pnp_ransac_dev_batch_parity(pkg, oracle, synth):
     """vslam_pnp_ransac_dev: B problems of different sizes in one call (incl. exactly 5 points, fewer than 5, heavy outliers) against
     oracle/ransac.c problem by problem: iterations run, inlier count and mask identical, the returned model bit-identical up to the quaternion
