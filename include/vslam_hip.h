@@ -377,6 +377,51 @@ int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int
                                   int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted,
                                   int32_t* d_frame_state, int32_t* d_status);
 
+/* ---- Throughput mode, pose inputs against the MAP (additive: the ABI version and vslam_tracks_in are unchanged).
+ * VO::motion_estimation (visual_odometry.cpp:260-277) hands solvePnPRansac every feature of the last frame that the current frame matched, at its
+ * LANDMARK's map position (pt_3d_: the creation point or the first reliable one, :391-401), and erases the outliers from the frame (:306): tracking
+ * is frame-to-map.  With every frame a keyframe, the sequential loop is, for f = 1 .. n_frames - 1:
+ *   1. the query set is the features of frame f - 1 (the tracked inliers plus the landmarks created at f - 1);
+ *   2. the inputs are every frame-to-frame match out of a feature, in match order: xyz_w = the landmark's position as of frame f - 1, uv = the
+ *      current keypoint;
+ *   3. the pose solver gives T_c_w(f) and an inlier mask; the inliers become features of f;
+ *   4. insert_key_frame as in vslam_build_windows_dev: observations, reliable-depth upgrades, landmarks from f's own-depth keypoints that no track
+ *      reaches, at T_c_w(f).
+ * The batch stays parallel: it is computed in REFINEMENT PASSES, each parallel over all frames.  Pass 0 is the pose stage's own result:
+ * G^0 = the chain of d_T_rel, links^0 = the d_pose_inlier flags of the own-depth inputs plus track_rule's judgement of depth-less features.
+ * Pass k >= 1 starts from G^{k-1} (n_frames x 7 absolute T_c_w, frame 0 = the world = identity) and links^{k-1}: walk the tracks (a link holds
+ * only if the previous pass said so; a link out of a slot that is no longer a feature continues nothing), emit every pair's inputs as in step 2
+ * in the world of G^{k-1} (vslam_build_map_pnp_inputs_dev), run the caller's solver on every item at once (LM from the guess G^{k-1}_{i+1};
+ * RANSAC takes no guess), and take G^k (row 0 = identity) and links^k = the inlier flags.  Failure rule: an item with 0 inliers gets
+ * G^k_f = G^{k-1}_{f-1} and no links (stage A: a failed problem gives T_rel = identity).  Windows are built from G^K and links^K
+ * (vslam_build_windows_map_dev).
+ * CONTRACT: after k passes, frames 0..k are exactly the sequential loop's when the solver is a pure function of its inputs -- the inputs of pair
+ * f - 1 -> f depend only on the links into frames <= f - 1 and the poses of frames <= f - 1 (induction on f).  With RANSAC this is exact, so
+ * K >= n_frames - 1 passes reproduce the sequential loop; LM depends on its guess and converges rather than matching exactly. */
+
+/* G_0 = identity, G_f = T_rel[f - 1] o G_{f - 1} (n_frames x 7, device): the chain the window builders use, bit for bit.  Asynchronous. */
+int vslam_chain_poses_dev(vslam_ctx* ctx, int n_frames, const double* d_T_rel, double* d_T_c_w);
+
+/* One refinement pass's pose inputs.  d_T_c_w (n_frames x 7, device): G^{k-1}.  d_input_of_match_prev ((n_frames - 1) x match_capacity, device):
+ * the previous pass's index map, with in->d_pose_inlier that pass's inlier flags ((n_frames - 1) x in->pnp_capacity, in->pnp_capacity = that pass's
+ * out_capacity); NULL: pass-0 links (in->d_pose_inlier in own-depth order as in vslam_build_windows_dev, plus track_rule).  in->d_T_rel is not read.
+ * Outputs per item i (frame pair i -> i + 1): d_xyz_w ((n_frames - 1) x out_capacity x 3 f32) the landmark's position as of frame i -- bit for bit the
+ * position that landmark has in window i of vslam_build_windows_map_dev on the same poses and links; d_uv ((n_frames - 1) x out_capacity x 2) the
+ * train keypoint (x, y); d_n (n_frames - 1) the input count; d_input_of_match ((n_frames - 1) x match_capacity) the input match k became, -1 for
+ * none (entries from d_nf2f[i] on are -1).  *d_status: 0, or bit 0 when out_capacity cut an item's list (the inputs that fit are kept).  The
+ * preconditions of vslam_tracks_in hold (one-to-one d_f2f, kp_capacity <= 65536).  Refused with VSLAM_ERR_ARG: a chunk (d_T_abs, d_carry_in,
+ * d_carry_out or carry_out_frame set), NULL d_T_c_w, out_capacity < 1, a NULL output pointer.  Asynchronous on the context stream. */
+int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
+                                   float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status);
+
+/* vslam_build_windows_kf_dev on the poses d_T_c_w (n_frames x 7, G^K) and the links of d_input_of_match (index map of the pass that produced the flags
+ * in in->d_pose_inlier; NULL: pass-0 links).  in->d_T_rel is not read.  Everything else -- policies 0 and 1, d_kf_frame / d_evicted, capacity and
+ * status behaviour -- is vslam_build_windows_kf_dev's.  CONTRACT: with d_T_c_w = vslam_chain_poses_dev(d_T_rel) and d_input_of_match = NULL its output
+ * equals vslam_build_windows_kf_dev's bit for bit.  Refused with VSLAM_ERR_ARG: a chunk, NULL d_T_c_w, and what vslam_build_windows_kf_dev refuses. */
+int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match, int n_kf,
+                                int policy, double near_dist, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame,
+                                int32_t* d_evicted, int32_t* d_status);
+
 /* per-window status of the most recent window launch on this process (VSLAM_OK or VSLAM_ERR_ARG per window) */
 int vslam_ba_status_dev(vslam_ctx* ctx, int n_windows, int32_t* h_status);
 /* optimize_map passes the most recent vslam_ba_batch_dev(schedule = 1) call EXECUTED per window: 3 = all of run_vslam.cpp:61-66; 1 or 2 = the

@@ -125,6 +125,9 @@ SIGNATURES = {
     "vslam_build_windows_dev": (I, [P, P, I, I, I, P, P]),
     "vslam_build_windows_kf_dev": (I, [P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_build_windows_gated_dev": (I, [P, P, I, I, D, P, I, I, P, P, P, P, P]),
+    "vslam_chain_poses_dev": (I, [P, I, P, P]),
+    "vslam_build_map_pnp_inputs_dev": (I, [P, P, P, P, P, P, P, P, I, P]),
+    "vslam_build_windows_map_dev": (I, [P, P, P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_ba_status_dev": (I, [P, I, P]), "vslam_ba_schedule_passes_dev": (I, [P, I, P]), "vslam_ba_deferred_dev": (I, [P, I, P]),
     "vslam_edge_jacobians": (I, [P, I, P, P, P, P, P, P, P, P, P]),
     "vslam_set_tuning": (I, [P, C.c_char_p, I]), "vslam_sgbm_status_dev": (I, [P, P]), "vslam_orb_status_dev": (I, [P, I, P]),
@@ -439,6 +442,22 @@ class VO:
         is empty.  Semantics in include/vslam_hip.h."""
         self._chk(self.lib.vslam_build_windows_gated_dev(self.h, C.byref(tracks), n_kf, policy, near_dist, d_num_inliers, lm_capacity, edge_capacity,
                                                          C.byref(batch), d_kf_frame, d_evicted, d_frame_state, d_status), "vslam_build_windows_gated_dev")
+
+    def chain_poses_dev(self, n_frames, d_T_rel, d_T_c_w):
+        """G_0 = identity, G_f = T_rel[f - 1] o G_{f - 1} (n_frames x 7 float64): the window builders' chain"""
+        self._chk(self.lib.vslam_chain_poses_dev(self.h, n_frames, d_T_rel, d_T_c_w), "vslam_chain_poses_dev")
+
+    def build_map_pnp_inputs_dev(self, tracks, d_T_c_w, d_input_of_match_prev, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status):
+        """one refinement pass's pose inputs against the map (VO::motion_estimation, visual_odometry.cpp:260-277): every match out of a feature of frame
+        i at its landmark's position in the world of d_T_c_w, links from d_input_of_match_prev (None: pass 0).  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_build_map_pnp_inputs_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match_prev, d_xyz_w, d_uv, d_n, d_input_of_match,
+                                                          out_capacity, d_status), "vslam_build_map_pnp_inputs_dev")
+
+    def build_windows_map_dev(self, tracks, d_T_c_w, d_input_of_match, n_kf, policy, near_dist, lm_capacity, edge_capacity, batch, d_kf_frame, d_evicted,
+                              d_status):
+        """build_windows_kf_dev on the caller's poses and the links of a refinement pass (d_input_of_match None: pass 0).  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_build_windows_map_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match, n_kf, policy, near_dist, lm_capacity,
+                                                       edge_capacity, C.byref(batch), d_kf_frame, d_evicted, d_status), "vslam_build_windows_map_dev")
 
     def build_pnp_inputs_dev(self, d_f2f, d_nf2f, match_cap, d_lr, d_nlr, lr_cap, d_xyz_lr, d_valid_lr, d_kps_cur, kp_cap, B, d_kp2lr,
                              d_xyz_out, d_uv_out, d_nout, out_cap):

@@ -230,7 +230,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "lm_window_kernel<pnp> pnp_wave_kernel pnp_inlier_kernel pnp_epnp_kernels epnp_front_kernel epnp_jacobi_kernel epnp_back_kernel pnp_count_inliers_kernel hbm_copy_probe_kernel "
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
-           "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel";
+           "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -957,7 +957,7 @@ static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, in
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !in || !out || !d_status || in->n_frames <= 0 || n_kf <= 0 || n_kf > VSLAM_MAX_KF || lm_capacity <= 0 || edge_capacity <= 0 ||
         in->kp_capacity <= 0 || in->lr_capacity <= 0 || in->match_capacity <= 0 || in->pnp_capacity <= 0 || !in->d_kps || !in->d_lr || !in->d_nlr ||
-        !in->d_xyz || !in->d_valid || !in->d_reliable || (in->n_frames > 1 && (!in->d_f2f || !in->d_nf2f || !in->d_pose_inlier || !in->d_T_rel)) ||
+        !in->d_xyz || !in->d_valid || !in->d_reliable || (in->n_frames > 1 && (!in->d_f2f || !in->d_nf2f || !in->d_pose_inlier || (!in->d_T_rel && !kp.G))) ||
         !out->d_lm_off || !out->d_edge_off || !out->d_T_c_w || !out->d_xyz || !out->d_reliable || !out->d_lm_inlier || !out->d_kf_idx || !out->d_lm_idx ||
         !out->d_uv || !out->d_n_kf) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if ((long long)in->n_frames * in->kp_capacity > 0x7FFFFFFFll) { set_error("n_frames x kp_capacity exceeds the 31-bit node keys"); return VSLAM_ERR_ARG; }
@@ -1006,6 +1006,53 @@ int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int
     }
     KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
     kp.gate = true; kp.num_inliers = d_num_inliers; kp.frame_state = d_frame_state;
+    return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
+}
+
+int vslam_chain_poses_dev(vslam_ctx* ctx, int n_frames, const double* d_T_rel, double* d_T_c_w) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || n_frames <= 0 || !d_T_c_w || (n_frames > 1 && !d_T_rel)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_chain_poses(n_frames, d_T_rel, d_T_c_w, c->stream);
+}
+
+// the refinement passes (vslam_build_map_pnp_inputs_dev, vslam_build_windows_map_dev): poses from the caller, so no chunk and no NULL pose table
+static int map_refuses(const vslam_tracks_in* in, const double* d_T_c_w) {
+    if (in->d_T_abs || in->d_carry_in || in->d_carry_out || in->carry_out_frame != 0) {
+        set_error("the map pose inputs need the whole history: not available on a chunk (d_T_abs / d_carry_in / d_carry_out set)"); return VSLAM_ERR_ARG;
+    }
+    if (!d_T_c_w) { set_error("d_T_c_w (n_frames x 7 absolute poses) is required"); return VSLAM_ERR_ARG; }
+    return VSLAM_OK;
+}
+
+int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, float* d_xyz_w,
+                                   float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !in) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (int rc = map_refuses(in, d_T_c_w)) return rc;
+    if (out_capacity < 1 || !d_xyz_w || !d_uv || !d_n || !d_input_of_match || !d_status || in->n_frames <= 0 || in->kp_capacity <= 0 ||
+        in->lr_capacity <= 0 || in->match_capacity <= 0 || in->pnp_capacity <= 0 || !in->d_kps || !in->d_lr || !in->d_nlr || !in->d_xyz || !in->d_valid ||
+        !in->d_reliable || (in->n_frames > 1 && (!in->d_f2f || !in->d_nf2f || !in->d_pose_inlier))) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if ((long long)in->n_frames * in->kp_capacity > 0x7FFFFFFFll) { set_error("n_frames x kp_capacity exceeds the 31-bit node keys"); return VSLAM_ERR_ARG; }
+    if (in->kp_capacity > 65536) { set_error("kp_capacity %d exceeds 65536 (the window builder packs a keypoint index into 16 bits)", in->kp_capacity); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    double K4[4];
+    fill_K(c, K4);
+    const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
+    return launch_map_pnp_inputs(*in, d_T_c_w, d_input_of_match_prev, K4, c->p.pnp_reproj_thr, track_rule, c->track, d_xyz_w, d_uv, d_n, d_input_of_match,
+                                 out_capacity, d_status, c->stream);
+}
+
+int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match, int n_kf, int policy,
+                                double near_dist, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted,
+                                int32_t* d_status) {
+    if (!ctx || !in || !d_kf_frame || !d_evicted) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (int rc = map_refuses(in, d_T_c_w)) return rc;
+    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 sliding, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
+    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
+    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
+    KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
+    kp.G = d_T_c_w; kp.in_of_match = d_input_of_match;
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
 }
 

@@ -14,6 +14,8 @@
 // the chi2 classification of window b - 1 does not feed window b).  Which keyframes window b holds is a policy: the sliding window
 // [b - n_kf + 1, b] (vslam_build_windows_dev), or the distance-based culling of Map::remove_keyframe (map.cpp:48-130) evaluated on the
 // chained poses (vslam_build_windows_kf_dev policy 1: kf_band_kernel + kf_set_kernel below; the window kernels are templated on it).
+// Pose inputs against the map (vslam_build_map_pnp_inputs_dev / vslam_build_windows_map_dev): the poses come from the caller (a refinement pass's
+// absolute G) and the links from an index map (track_link_kernel<true>); track_map_inputs_kernel emits every match out of a feature at its landmark's position.
 //
 // gfx950 mapping: the reference walks std::unordered_map<id, Landmark> with per-landmark observation vectors; here a track is a chain
 // of (frame, keypoint) nodes linked by two flat int32 tables pred / succ (B x kp_capacity) filled by one scatter pass per frame pair,
@@ -91,14 +93,29 @@ __global__ __launch_bounds__(256) void track_pose_chain_kernel(int B, const doub
 // whose query keypoint owns a valid depth (the compaction of build_pnp_inputs_kernel, geom_kernels.hip, repeated with the same ballot ranks):
 // such a candidate carries the pose stage's inlier flag (the reference erases the outliers of motion_estimation from the frame, :306).  A
 // candidate whose query keypoint has no depth of its own is decided by the walk below (track_rule 1) or never a link (track_rule 0).
+// kMap (the refinement passes of vslam_build_map_pnp_inputs_dev / vslam_build_windows_map_dev): the pose problem's inputs are indexed by
+// the map in_of_match (match k of item i -> input j, or -1), so every candidate is decided here: it holds when match k was input j and j an inlier.
 constexpr int kCandDepth = 1 << 20, kCandInlier = 1 << 21; // cand word of slot t: q (low 16 bits) | flags (kp_capacity <= 65536), -1: no match reaches it
+template <bool kMap>
 __global__ __launch_bounds__(256) void track_link_kernel(TrackDims d, const vslam_dmatch* __restrict__ d_f2f, const int32_t* __restrict__ d_nf2f,
                                                         const uint8_t* __restrict__ d_valid, const uint8_t* __restrict__ d_inl,
-                                                        const int32_t* __restrict__ kp2lr, int32_t* __restrict__ cand, int32_t* __restrict__ succ) {
+                                                        const int32_t* __restrict__ kp2lr, int32_t* __restrict__ cand, int32_t* __restrict__ succ,
+                                                        const int32_t* __restrict__ in_of_match) {
     const int it = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ int s_tot[4];
     const int nm = min(max(d_nf2f[it], 0), d.match_cap);
     const vslam_dmatch* m = d_f2f + (size_t)it * d.match_cap;
+    if (kMap) {
+        for (int k = tid; k < nm; k += 256) {
+            const int q = m[k].queryIdx, t = m[k].trainIdx;
+            if (q < 0 || q >= d.kp_cap || t < 0 || t >= d.kp_cap) continue;
+            const int j = in_of_match[(size_t)it * d.match_cap + k];
+            const bool inl = j >= 0 && j < d.pnp_cap && d_inl[(size_t)it * d.pnp_cap + j] != 0;
+            cand[(size_t)(it + 1) * d.kp_cap + t] = q | kCandDepth | (inl ? kCandInlier : 0);
+            succ[(size_t)it * d.kp_cap + q] = t;
+        }
+        return;
+    }
     const int32_t* k2 = kp2lr + (size_t)it * d.kp_cap;
     int written = 0;
     for (int base = 0; base < nm; base += 256) {
@@ -394,6 +411,57 @@ __global__ __launch_bounds__(256) void track_carry_out_kernel(TrackDims d, int c
     reinterpret_cast<float4*>(carry_out)[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
 }
 
+// ---- per frame pair (i -> i + 1), after the walk: the pose problem of frame i + 1 against the MAP (VO::motion_estimation, visual_odometry.cpp:260-277):
+// every match out of a feature of frame i (root != -1), in match order, with its landmark's position as of frame i -- the source rule of
+// window_emit_kernel (the first reliable node, else the root), so the point is bit for bit the one window i holds -- and the current keypoint.
+// Compacted with the ballot ranks of track_link_kernel; in_of_match[k] = the input match k became (-1: none, or cut by out_cap: status bit 0).
+__global__ __launch_bounds__(256) void track_map_inputs_kernel(TrackDims d, const vslam_dmatch* __restrict__ d_f2f, const int32_t* __restrict__ d_nf2f,
+                                                              const vslam_keypoint* __restrict__ d_kps, const float* __restrict__ d_xyz,
+                                                              const int32_t* __restrict__ kp2lr, const int32_t* __restrict__ root,
+                                                              const int32_t* __restrict__ relsrc, const double* __restrict__ G, int out_cap,
+                                                              float* __restrict__ xyz_out, float* __restrict__ uv_out, int32_t* __restrict__ n_out,
+                                                              int32_t* __restrict__ in_of_match, int32_t* __restrict__ status) {
+    const int it = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int s_tot[4];
+    const int nm = min(max(d_nf2f[it], 0), d.match_cap);
+    const vslam_dmatch* m = d_f2f + (size_t)it * d.match_cap;
+    int32_t* map = in_of_match + (size_t)it * d.match_cap;
+    int written = 0;
+    for (int base = 0; base < nm; base += 256) {
+        const int k = base + tid;
+        bool ok = false; int q = -1, t = -1;
+        if (k < nm) {
+            q = m[k].queryIdx; t = m[k].trainIdx;
+            ok = q >= 0 && q < d.kp_cap && t >= 0 && t < d.kp_cap && root[(size_t)it * d.kp_cap + q] != -1;
+        }
+        const unsigned long long mask = __ballot(ok);
+        __syncthreads();
+        if (lane == 0) s_tot[wave] = __popcll(mask);
+        __syncthreads();
+        int off = written;
+        for (int w = 0; w < wave; ++w) off += s_tot[w];
+        const int j = off + __popcll(mask & ((1ull << lane) - 1ull));
+        const bool keep = ok && j < out_cap;
+        if (keep) {
+            const size_t c = (size_t)it * d.kp_cap + q;
+            const int rs = relsrc[c];
+            float pos[3];
+            landmark_position(d, rs != -1 ? rs : root[c], kp2lr, d_xyz, G, nullptr, pos);
+            float* o = xyz_out + 3 * ((size_t)it * out_cap + j);
+            o[0] = pos[0]; o[1] = pos[1]; o[2] = pos[2];
+            const vslam_keypoint* kp = d_kps + (size_t)(it + 1) * d.kp_cap + t;
+            reinterpret_cast<float2*>(uv_out)[(size_t)it * out_cap + j] = make_float2(kp->x, kp->y);
+        }
+        if (k < nm) map[k] = keep ? j : -1;
+        written += s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+    }
+    for (int k = nm + tid; k < d.match_cap; k += 256) map[k] = -1;
+    if (tid == 0) {
+        n_out[it] = min(written, out_cap);
+        if (written > out_cap) atomicOr(status, 1);
+    }
+}
+
 // A chain HEAD of window [s, b]: a node in frame s, or a node without predecessor (a landmark created inside the window).  Every
 // landmark observed in the window has exactly one.  Returns the observations it has inside the window (0: not a head) -- from the
 // slot's info word alone (track_chain_kernel), no chain walk.
@@ -659,7 +727,8 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     int32_t* cand = info; // (the candidate words live in the info table until track_info_kernel writes it)
     ProfScope prof__(stream, "build_windows_kernels", 9);
     hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
-    if (in.d_T_abs) VS_HIP(hipMemcpyAsync(G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
+    if (kp.G) VS_HIP(hipMemcpyAsync(G, kp.G, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (the map builder: the caller's poses)
+    else if (in.d_T_abs) VS_HIP(hipMemcpyAsync(G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
     else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(1), dim3(256), 0, stream, d.B, in.d_T_rel, G);
     if (gate) { // the states depend on the pose stage's outputs alone, the keyframe sets on the states and the poses
         hipLaunchKernelGGL(kf_gate_kernel, dim3((d.B + 255) / 256), dim3(256), 0, stream, d.B, kp.num_inliers, in.d_T_rel, kp.frame_state);
@@ -671,7 +740,10 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
         hipLaunchKernelGGL(kf_set_kernel<false>, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, D, kp.kf_frame, kp.evicted, set_flags, nullptr, nullptr);
     } else if (kp.policy == 0)
         hipLaunchKernelGGL(kf_sliding_kernel, dim3((d.B * n_kf + 255) / 256), dim3(256), 0, stream, d.B, n_kf, kp.kf_frame, kp.evicted);
-    if (d.B > 1) hipLaunchKernelGGL(track_link_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ);
+    if (d.B > 1 && kp.in_of_match)
+        hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, kp.in_of_match);
+    else if (d.B > 1)
+        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr);
     if (gate)
         hipLaunchKernelGGL(track_walk_kernel<true>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
                            G, in.d_carry_in, root, relsrc, (const int32_t*)kp.frame_state);
@@ -696,6 +768,46 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
         hipLaunchKernelGGL(window_emit_kernel<false>, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist,
                            head_rec, d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out, ws);
     }
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
+// ---- G[0] = identity, G[f] = T_rel[f - 1] o G[f - 1]: the builders' chain on its own (vslam_chain_poses_dev)
+int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream) {
+    ProfScope prof__(stream, "track_pose_chain_kernel");
+    hipLaunchKernelGGL(track_pose_chain_kernel, dim3(1), dim3(256), 0, stream, n_frames, d_T_rel, d_G);
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
+// ---- one refinement pass's pose inputs (vslam_build_map_pnp_inputs_dev): the walk of the builders on the caller's poses G and the previous pass's
+// links (in_of_match_prev, or the pose stage's own-depth flags and track_rule when it is null), then the map inputs of every frame pair
+int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const double K4[4], double reproj_thr, int track_rule,
+                          DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match, int out_capacity, int32_t* d_status,
+                          hipStream_t stream) {
+    TrackDims d;
+    d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = 1;
+    const size_t tab = (size_t)d.B * d.kp_cap;
+    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *cand;
+    if (int rc = carve(scratch, stream, [&](Layout& L) {
+            kp2lr = L.take<int32_t>(tab); pred = L.take<int32_t>(tab); succ = L.take<int32_t>(tab);
+            root = L.take<int32_t>(tab); relsrc = L.take<int32_t>(tab); cand = L.take<int32_t>(tab);
+        })) return rc;
+    TrackCam cam;
+    cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
+    ProfScope prof__(stream, "map_pnp_inputs_kernels", 4);
+    VS_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t), stream));
+    if (d.B < 2) return VSLAM_OK;
+    hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
+    if (d_in_of_match_prev)
+        hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ,
+                           d_in_of_match_prev);
+    else
+        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr);
+    hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr,
+                       cand, pred, succ, d_G, nullptr, root, relsrc, nullptr);
+    hipLaunchKernelGGL(track_map_inputs_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_kps, in.d_xyz, kp2lr, root, relsrc, d_G,
+                       out_capacity, d_xyz_out, d_uv_out, d_n_out, d_in_of_match, d_status);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

@@ -26,7 +26,7 @@ class KeyframePipeline:
     def __init__(self, B, device=0, anms_num=1500, n_lm=3000, n_kf=10, unique_frames=64, unique_windows=None, seed=0, verbose=False,
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
                  lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
-                 keyframe_gate=False):
+                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
         Inputs: ONE rendered sequence of `unique_frames` consecutive stereo keyframes, laid over the batch as a ping-pong
@@ -39,10 +39,20 @@ class KeyframePipeline:
         near_dist, else the farthest).
         keyframe_gate (ba_windows="tracks"): insert_key_frame's gate (visual_odometry.cpp:353) on the pose stage's inlier counts and poses --
         only keyframes create landmarks, record observations and enter the windows' keyframe sets (vslam_build_windows_gated_dev; window_policy
-        "sliding" evicts the oldest keyframe, "reference" culls); a non-keyframe step's window is empty.  Not available in sequence mode."""
+        "sliding" evicts the oldest keyframe, "reference" culls); a non-keyframe step's window is empty.  Not available in sequence mode.
+        pose_inputs (ba_windows="tracks"): "own_depth" -- the pose stage's inputs are the matches whose last-frame keypoint has a depth of its own, at
+        that camera-frame point, poses relative and chained; "map" -- after that stage, `pose_passes` refinement passes solve every frame against the
+        MAP, as VO::motion_estimation does (visual_odometry.cpp:260-277: every matched feature of the last frame at its landmark's position), each pass
+        parallel over the batch (vslam_build_map_pnp_inputs_dev; after K passes frames 0..K are the sequential loop's), and the windows are built on
+        the last pass's poses and links (vslam_build_windows_map_dev).  Not with keyframe_gate or in sequence mode."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
         assert not keyframe_gate or (ba_windows == "tracks" and frame_range is None), "keyframe_gate needs ba_windows='tracks' and no frame_range"
+        assert pose_inputs in ("own_depth", "map")
+        if pose_inputs == "map":
+            assert with_ba and ba_windows == "tracks" and int(pose_passes) >= 1, "pose_inputs='map' needs ba_windows='tracks' and pose_passes >= 1"
+            assert not keyframe_gate and frame_range is None, "pose_inputs='map' is not available with keyframe_gate or frame_range"
+        self.pose_inputs, self.pose_passes = pose_inputs, int(pose_passes)
         self.window_policy, self.near_dist, self.keyframe_gate = window_policy, float(near_dist), bool(keyframe_gate)
         self.depth = depth
         self.pose = pose   # "lm": north_star motion-only LM; "ransac": the reference's cv::solvePnPRansac(..., 100, 4.0, 0.99) (visual_odometry.cpp:277)
@@ -137,7 +147,7 @@ class KeyframePipeline:
             self.ba_nkf = torch.zeros(B, dtype=torch.int32, device=d)
             self.ba_build_status = torch.zeros(1, dtype=torch.int32, device=d)
             self.ba_chi2 = torch.zeros(1, dtype=torch.float64, device=d)
-            if window_policy == "reference" or keyframe_gate:
+            if window_policy == "reference" or keyframe_gate or pose_inputs == "map":
                 self.ba_kf_frame = torch.zeros((B, n_kf), dtype=torch.int32, device=d)
                 self.ba_evicted = torch.zeros(B, dtype=torch.int32, device=d)
             if keyframe_gate:
@@ -149,6 +159,22 @@ class KeyframePipeline:
             tr.d_nf2f = self.d_nf2f.data_ptr(); tr.d_pose_inlier = self.d_inl.data_ptr(); tr.d_T_rel = self.d_Tpnp.data_ptr()
             tr.d_nkps = self.d_cnt.data_ptr()   # (the first B counts: the left images)
             self.tracks = tr
+            if pose_inputs == "map":
+                # refinement passes: poses G^k (B x 7, double-buffered), the pass's inputs, its index map and inlier flags (double-buffered)
+                self.map_G = [torch.zeros((B, 7), dtype=torch.float64, device=d) for _ in range(2)]
+                self.map_T = torch.zeros((B, 7), dtype=torch.float64, device=d)
+                self.map_xyz = torch.zeros((B, self.cap, 3), dtype=torch.float32, device=d)
+                self.map_uv = torch.zeros((B, self.cap, 2), dtype=torch.float32, device=d)
+                self.map_n = torch.zeros(B, dtype=torch.int32, device=d)
+                self.map_index = [torch.full((B, self.cap), -1, dtype=torch.int32, device=d) for _ in range(2)]
+                self.map_inl = [torch.zeros((B, self.cap), dtype=torch.uint8, device=d) for _ in range(2)]
+                self.map_ninl = torch.zeros(B, dtype=torch.int32, device=d)
+                self.map_status = torch.zeros(1, dtype=torch.int32, device=d)
+                self.map_cur = 0
+                mt = TracksIn()
+                for f_, _ in TracksIn._fields_:
+                    setattr(mt, f_, getattr(tr, f_))
+                self.map_tracks = mt
             bb = BaBatch()
             bb.n_windows = B; bb.n_kf = n_kf
             bb.d_lm_off = self.ba_lm_off.data_ptr(); bb.d_edge_off = self.ba_e_off.data_ptr(); bb.d_T_c_w = self.ba_T.data_ptr()
@@ -234,17 +260,53 @@ class KeyframePipeline:
         vo.build_pnp_inputs_dev(self.d_f2f.data_ptr(), self.d_nf2f.data_ptr(), cap, self.d_lr.data_ptr(), self.d_nlr.data_ptr(), cap,
                                 self.d_xyz.data_ptr(), self.d_valid.data_ptr(), self.d_kps.data_ptr() + cap * 28, cap, n, self.d_kp2lr.data_ptr(),
                                 self.d_pxyz.data_ptr(), self.d_puv.data_ptr(), self.d_pn.data_ptr(), cap)
+        self._solve(self.d_pxyz, self.d_puv, self.d_pn, self.d_Tpnp, self.d_inl, self.d_ninl, self.d_Tident)
+        if self.pose_inputs == "map":
+            self._map_passes()
+
+    def _solve(self, xyz, uv, n_in, T, inl, ninl, guess):
+        """the pose stage on the B - 1 problems (xyz, uv, n_in): T (B x 7) and the inlier flags / counts"""
+        cap, n = self.cap, self.B - 1
         if self.pose == "ransac":   # no pose guess is consumed (useExtrinsicGuess = false)
-            vo.pnp_ransac_dev(self.d_pxyz.data_ptr(), self.d_puv.data_ptr(), self.d_pn.data_ptr(), cap, n, self.d_Tpnp.data_ptr(), 100, 4.0, 0.99,
-                              self.d_inl.data_ptr(), self.d_ninl.data_ptr(), None)
+            self.vo.pnp_ransac_dev(xyz.data_ptr(), uv.data_ptr(), n_in.data_ptr(), cap, n, T.data_ptr(), 100, 4.0, 0.99, inl.data_ptr(), ninl.data_ptr(), None)
             return
         with torch.cuda.stream(self.stream):
-            self.d_Tpnp.copy_(self.d_Tident)
-        vo.motion_estimation_dev(self.d_pxyz.data_ptr(), self.d_puv.data_ptr(), self.d_pn.data_ptr(), cap, n, self.d_Tpnp.data_ptr(), 10,
-                                 self.d_inl.data_ptr(), self.d_ninl.data_ptr())
+            T.copy_(guess)
+        self.vo.motion_estimation_dev(xyz.data_ptr(), uv.data_ptr(), n_in.data_ptr(), cap, n, T.data_ptr(), 10, inl.data_ptr(), ninl.data_ptr())
+
+    def _map_passes(self):
+        """pose_inputs="map": G^0 = the chain of the stage's relative poses, links^0 its flags; pass k solves every frame f against the map of
+        (G^{k-1}, links^{k-1}) -- LM from the guess G^{k-1}_f, RANSAC without one -- and an item with no inlier keeps G^k_f = G^{k-1}_{f-1}"""
+        B, cap, n = self.B, self.cap, self.B - 1
+        mt = self.map_tracks
+        cur = 0
+        self.vo.chain_poses_dev(B, self.d_Tpnp.data_ptr(), self.map_G[cur].data_ptr())
+        prev_index, prev_inl = None, self.d_inl
+        for _ in range(self.pose_passes):
+            nxt = cur ^ 1
+            G, Gn = self.map_G[cur], self.map_G[nxt]
+            mt.d_pose_inlier = prev_inl.data_ptr(); mt.pnp_capacity = cap
+            self.vo.build_map_pnp_inputs_dev(mt, G.data_ptr(), None if prev_index is None else prev_index.data_ptr(), self.map_xyz.data_ptr(),
+                                             self.map_uv.data_ptr(), self.map_n.data_ptr(), self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
+            with torch.cuda.stream(self.stream):
+                guess = torch.cat([G[1:], G[:1]])   # (item i: frame i + 1; the last row is not read)
+            self._solve(self.map_xyz, self.map_uv, self.map_n, self.map_T, self.map_inl[nxt], self.map_ninl, guess)
+            with torch.cuda.stream(self.stream):
+                Gn[0].copy_(self.d_Tident[0])
+                Gn[1:].copy_(torch.where((self.map_ninl[:n] > 0)[:, None], self.map_T[:n], G[:n]))
+            prev_index, prev_inl, cur = self.map_index[nxt], self.map_inl[nxt], nxt
+        self.map_cur = cur
 
     def stage_build_windows(self):
         """optimize_map's graph build (optimization.cpp:127-214) + insert_key_frame's bookkeeping (visual_odometry.cpp:363-424) on the device"""
+        if self.pose_inputs == "map":   # the last pass's poses and links
+            c = self.map_cur
+            mt = self.map_tracks
+            mt.d_pose_inlier = self.map_inl[c].data_ptr(); mt.pnp_capacity = self.cap
+            self.vo.build_windows_map_dev(mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr(), self.n_kf, 1 if self.window_policy == "reference" else 0,
+                                          self.near_dist, self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(),
+                                          self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
+            return
         if self.keyframe_gate:   # (d_ninl item i = the inlier count of frame i + 1)
             self.vo.build_windows_gated_dev(self.tracks, self.n_kf, 1 if self.window_policy == "reference" else 0, self.near_dist, self.d_ninl.data_ptr(),
                                             self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(), self.ba_evicted.data_ptr(),
@@ -333,6 +395,11 @@ class KeyframePipeline:
                 out["ba_kf_frame"], out["ba_evicted"] = sliding_keyframes(B, self.n_kf)
             if self.keyframe_gate:
                 out["frame_state"] = self.ba_frame_state.cpu().numpy()
+        if self.pose_inputs == "map":   # the last refinement pass (item i: frame i + 1); T_c_w = its poses G^K
+            c = self.map_cur
+            out["map_n"] = self.map_n.cpu().numpy(); out["map_xyz"] = self.map_xyz.cpu().numpy(); out["map_uv"] = self.map_uv.cpu().numpy()
+            out["map_index"] = self.map_index[c].cpu().numpy(); out["map_inl"] = self.map_inl[c].cpu().numpy(); out["map_ninl"] = self.map_ninl.cpu().numpy()
+            out["T_c_w"] = self.map_G[c].cpu().numpy()
         return out
 
     def trajectory(self):
