@@ -370,7 +370,8 @@ int vslam_build_windows_kf_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_
  * Deviations from the reference: a rejected frame (state 0) is never a keyframe but is otherwise treated like state 1 (tracks and the pose chain
  * pass through it; the reference re-matches the next frame against the last accepted one) and sets bit 2 (value 4) of *d_status; frame_gap is
  * always 1; the VO "Lost" state is not modelled; the pose stage's inputs are what the caller computed (after a non-keyframe they are not the
- * reference's).  With every frame a keyframe, every output is vslam_build_windows_kf_dev's with the same policy, bit for bit.
+ * reference's; vslam_build_windows_map_gated_dev below runs the gate inside the map passes instead).  With every frame a keyframe, every output is
+ * vslam_build_windows_kf_dev's with the same policy, bit for bit.
  * Refused with VSLAM_ERR_ARG: a chunk (d_T_abs, d_carry_in or d_carry_out set), NULL d_num_inliers when n_frames > 1, NULL d_kf_frame /
  * d_evicted / d_frame_state, a policy other than 0 / 1, near_dist NaN or negative, n_kf outside 1..VSLAM_MAX_KF. */
 int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int policy, double near_dist, const int32_t* d_num_inliers,
@@ -397,7 +398,8 @@ int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int
  * (vslam_build_windows_map_dev).
  * CONTRACT: after k passes, frames 0..k are exactly the sequential loop's when the solver is a pure function of its inputs -- the inputs of pair
  * f - 1 -> f depend only on the links into frames <= f - 1 and the poses of frames <= f - 1 (induction on f).  With RANSAC this is exact, so
- * K >= n_frames - 1 passes reproduce the sequential loop; LM depends on its guess and converges rather than matching exactly. */
+ * K >= n_frames - 1 passes reproduce the sequential loop; LM depends on its guess and converges rather than matching exactly.
+ * These entries run without the keyframe gate (every frame a keyframe); the *_gated_dev entries below run the gate inside the passes. */
 
 /* G_0 = identity, G_f = T_rel[f - 1] o G_{f - 1} (n_frames x 7, device): the chain the window builders use, bit for bit.  Asynchronous. */
 int vslam_chain_poses_dev(vslam_ctx* ctx, int n_frames, const double* d_T_rel, double* d_T_c_w);
@@ -421,6 +423,51 @@ int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, co
 int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match, int n_kf,
                                 int policy, double near_dist, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame,
                                 int32_t* d_evicted, int32_t* d_status);
+
+/* ---- Throughput mode, the keyframe gate INSIDE the refinement passes (additive: the ABI version and vslam_tracks_in are unchanged).
+ * insert_key_frame's gate (visual_odometry.cpp:353) joined with the map inputs.  The sequential loop, for f = 1 .. n_frames - 1:
+ *   1. the query set is the features of frame f - 1: the tracked inliers into f - 1, plus -- if f - 1 is a keyframe (state 2; frame 0 always
+ *      is) -- the landmarks created at f - 1;
+ *   2. the inputs are every frame-to-frame match out of a feature, in match order: xyz_w = the landmark's position as of f - 1 (the creation point,
+ *      or the first reliable one; reliable upgrades happen at keyframes only), uv = the current keypoint;
+ *   3. the solver gives T_c_w(f), an inlier mask and num_inliers(f); with no inlier T_c_w(f) = T_c_w(f - 1) and there are no links;
+ *   4. state(f) = keyframe_state(num_inliers(f), T_c_w(f) o T_c_w(f - 1)^-1) -- the rule of vslam_build_windows_gated_dev (check_motion_estimation,
+ *      then the 80-inlier / angleY test; one definition, se3_device.h);
+ *   5. at state 2 insert_key_frame runs (observations, reliable upgrades, new landmarks at T_c_w(f)) and the keyframe set is updated by the policy
+ *      (0 oldest evicted, 1 culling); at states 0 and 1 the inliers pass through, nothing is recorded and the window is empty -- the rules of
+ *      vslam_build_windows_gated_dev.
+ * Deviations kept from vslam_build_windows_gated_dev: a rejected frame passes through (status bit 2), frame_gap is 1, no Lost state, BA results are
+ * not fed back into tracking, windows are independent, the frame-to-frame matcher's query set is every keypoint of the last frame.
+ * Passes: pass 0 is the pose stage (G^0 = the chain of d_T_rel, links^0 = its flags plus track_rule, states^0 = vslam_gate_states_dev(d_T_rel,
+ * absolute = 0) on its inlier counts); pass k walks the tracks with states^{k-1} on (G^{k-1}, links^{k-1}) (vslam_build_map_pnp_inputs_gated_dev),
+ * solves every item, takes G^k and links^k (the failure rule of step 3), then states^k = vslam_gate_states_dev(G^k, absolute = 1) on the pass's
+ * inlier counts.  Windows: vslam_build_windows_map_gated_dev on (G^K, links^K, states^K).
+ * CONTRACT: when the solver is a pure function of its inputs (RANSAC), after k passes the poses, inlier masks and states of frames 0..k and windows
+ * 0..k equal the sequential loop's; K >= n_frames - 1 passes reproduce it.  LM depends on its guess and converges rather than matching exactly. */
+
+/* d_frame_state (n_frames, device) = insert_key_frame's gate per frame: frame 0 is 2; frame f >= 1 gets keyframe_state(d_num_inliers[f - 1], T_c_l).
+ * absolute = 0: d_T is T_rel ((n_frames - 1) x 7) and T_c_l = d_T[f - 1] -- bit for bit the d_frame_state vslam_build_windows_gated_dev writes;
+ * absolute = 1: d_T is G (n_frames x 7 absolute T_c_w) and T_c_l = G_f o G_{f-1}^-1 (:615), computed on the device.  d_num_inliers: n_frames - 1,
+ * item i = frame i + 1.  Refused with VSLAM_ERR_ARG: absolute outside 0 / 1, NULL d_frame_state, NULL d_T / d_num_inliers when n_frames > 1.
+ * Asynchronous on the context stream. */
+int vslam_gate_states_dev(vslam_ctx* ctx, int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_frame_state);
+
+/* vslam_build_map_pnp_inputs_dev with the gated walk: d_frame_state (n_frames, device) = the previous pass's states; a node whose frame is not a
+ * keyframe (state != 2) creates no landmark and gives no reliable depth, tracked features pass through it.  CONTRACT: with every state 2 the outputs
+ * are vslam_build_map_pnp_inputs_dev's bit for bit.  Refused with VSLAM_ERR_ARG: NULL d_frame_state, and what vslam_build_map_pnp_inputs_dev refuses. */
+int vslam_build_map_pnp_inputs_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
+                                         const int32_t* d_frame_state, float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity,
+                                         int32_t* d_status);
+
+/* vslam_build_windows_map_dev with the frame states d_frame_state (n_frames, device) as an INPUT: the gated windows of vslam_build_windows_gated_dev --
+ * the gated walk, keyframe sets updated at state 2 only (policy 0 oldest evicted, 1 culling), empty windows with d_n_kf[b] = 0 at states 0 and 1,
+ * status bits 0-2 as there -- on the poses d_T_c_w and the links of d_input_of_match (NULL: pass-0 links).  in->d_T_rel is not read.
+ * CONTRACTS, bit for bit: with every state 2 the outputs are vslam_build_windows_map_dev's with the same policy; with d_T_c_w = vslam_chain_poses_dev
+ * (d_T_rel), d_input_of_match = NULL and d_frame_state = vslam_gate_states_dev(d_T_rel, absolute = 0) they are vslam_build_windows_gated_dev's
+ * (windows, d_kf_frame, d_evicted, status).  Refused with VSLAM_ERR_ARG: NULL d_frame_state, and what vslam_build_windows_map_dev refuses. */
+int vslam_build_windows_map_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match,
+                                      const int32_t* d_frame_state, int n_kf, int policy, double near_dist, int lm_capacity, int edge_capacity,
+                                      vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status);
 
 /* per-window status of the most recent window launch on this process (VSLAM_OK or VSLAM_ERR_ARG per window) */
 int vslam_ba_status_dev(vslam_ctx* ctx, int n_windows, int32_t* h_status);

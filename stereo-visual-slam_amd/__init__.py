@@ -128,6 +128,9 @@ SIGNATURES = {
     "vslam_chain_poses_dev": (I, [P, I, P, P]),
     "vslam_build_map_pnp_inputs_dev": (I, [P, P, P, P, P, P, P, P, I, P]),
     "vslam_build_windows_map_dev": (I, [P, P, P, P, I, I, D, I, I, P, P, P, P]),
+    "vslam_gate_states_dev": (I, [P, I, P, I, P, P]),
+    "vslam_build_map_pnp_inputs_gated_dev": (I, [P, P, P, P, P, P, P, P, P, I, P]),
+    "vslam_build_windows_map_gated_dev": (I, [P, P, P, P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_ba_status_dev": (I, [P, I, P]), "vslam_ba_schedule_passes_dev": (I, [P, I, P]), "vslam_ba_deferred_dev": (I, [P, I, P]),
     "vslam_edge_jacobians": (I, [P, I, P, P, P, P, P, P, P, P, P]),
     "vslam_set_tuning": (I, [P, C.c_char_p, I]), "vslam_sgbm_status_dev": (I, [P, P]), "vslam_orb_status_dev": (I, [P, I, P]),
@@ -458,6 +461,24 @@ class VO:
         """build_windows_kf_dev on the caller's poses and the links of a refinement pass (d_input_of_match None: pass 0).  Semantics in include/vslam_hip.h."""
         self._chk(self.lib.vslam_build_windows_map_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match, n_kf, policy, near_dist, lm_capacity,
                                                        edge_capacity, C.byref(batch), d_kf_frame, d_evicted, d_status), "vslam_build_windows_map_dev")
+
+    def gate_states_dev(self, n_frames, d_T, absolute, d_num_inliers, d_frame_state):
+        """insert_key_frame's gate per frame (n_frames int32: 2 keyframe, 1 tracked, 0 rejected) from the inlier counts (item i = frame i + 1) and d_T:
+        absolute 0 -- the relative poses T_rel (the gated builder's states); 1 -- absolute poses G, T_c_l = G_f o G_{f-1}^-1.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_gate_states_dev(self.h, n_frames, d_T, absolute, d_num_inliers, d_frame_state), "vslam_gate_states_dev")
+
+    def build_map_pnp_inputs_gated_dev(self, tracks, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity,
+                                       d_status):
+        """build_map_pnp_inputs_dev with the gated walk on the previous pass's frame states.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_build_map_pnp_inputs_gated_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n,
+                                                                d_input_of_match, out_capacity, d_status), "vslam_build_map_pnp_inputs_gated_dev")
+
+    def build_windows_map_gated_dev(self, tracks, d_T_c_w, d_input_of_match, d_frame_state, n_kf, policy, near_dist, lm_capacity, edge_capacity, batch,
+                                    d_kf_frame, d_evicted, d_status):
+        """build_windows_map_dev with the frame states as an input: the gated windows (empty at a non-keyframe).  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_build_windows_map_gated_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match, d_frame_state, n_kf, policy, near_dist,
+                                                             lm_capacity, edge_capacity, C.byref(batch), d_kf_frame, d_evicted, d_status),
+                  "vslam_build_windows_map_gated_dev")
 
     def build_pnp_inputs_dev(self, d_f2f, d_nf2f, match_cap, d_lr, d_nlr, lr_cap, d_xyz_lr, d_valid_lr, d_kps_cur, kp_cap, B, d_kp2lr,
                              d_xyz_out, d_uv_out, d_nout, out_cap):

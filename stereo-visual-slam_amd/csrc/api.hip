@@ -1025,8 +1025,17 @@ static int map_refuses(const vslam_tracks_in* in, const double* d_T_c_w) {
     return VSLAM_OK;
 }
 
-int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, float* d_xyz_w,
-                                   float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status) {
+int vslam_gate_states_dev(vslam_ctx* ctx, int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_frame_state) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || n_frames <= 0 || !d_frame_state || (n_frames > 1 && (!d_T || !d_num_inliers))) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (absolute != 0 && absolute != 1) { set_error("absolute must be 0 (d_T = T_rel) or 1 (d_T = absolute T_c_w)"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_gate_states(n_frames, d_T, absolute, d_num_inliers, d_frame_state, c->stream);
+}
+
+// d_frame_state: null for the ungated entry, required by the gated one
+static int map_pnp_inputs(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, const int32_t* d_frame_state,
+                          float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !in) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (int rc = map_refuses(in, d_T_c_w)) return rc;
@@ -1039,8 +1048,20 @@ int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, co
     double K4[4];
     fill_K(c, K4);
     const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
-    return launch_map_pnp_inputs(*in, d_T_c_w, d_input_of_match_prev, K4, c->p.pnp_reproj_thr, track_rule, c->track, d_xyz_w, d_uv, d_n, d_input_of_match,
-                                 out_capacity, d_status, c->stream);
+    return launch_map_pnp_inputs(*in, d_T_c_w, d_input_of_match_prev, d_frame_state, K4, c->p.pnp_reproj_thr, track_rule, c->track, d_xyz_w, d_uv, d_n,
+                                 d_input_of_match, out_capacity, d_status, c->stream);
+}
+
+int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, float* d_xyz_w,
+                                   float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status) {
+    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, nullptr, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status);
+}
+
+int vslam_build_map_pnp_inputs_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
+                                         const int32_t* d_frame_state, float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity,
+                                         int32_t* d_status) {
+    if (!d_frame_state) { set_error("the gated walk needs d_frame_state (n_frames states of the previous pass)"); return VSLAM_ERR_ARG; }
+    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status);
 }
 
 int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match, int n_kf, int policy,
@@ -1053,6 +1074,19 @@ int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const
     if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
     KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
     kp.G = d_T_c_w; kp.in_of_match = d_input_of_match;
+    return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
+}
+
+int vslam_build_windows_map_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match,
+                                      const int32_t* d_frame_state, int n_kf, int policy, double near_dist, int lm_capacity, int edge_capacity,
+                                      vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status) {
+    if (!ctx || !in || !d_kf_frame || !d_evicted || !d_frame_state) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (int rc = map_refuses(in, d_T_c_w)) return rc;
+    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 oldest evicted, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
+    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
+    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
+    KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
+    kp.G = d_T_c_w; kp.in_of_match = d_input_of_match; kp.gate = true; kp.state_in = d_frame_state;
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
 }
 

@@ -16,6 +16,8 @@
 // chained poses (vslam_build_windows_kf_dev policy 1: kf_band_kernel + kf_set_kernel below; the window kernels are templated on it).
 // Pose inputs against the map (vslam_build_map_pnp_inputs_dev / vslam_build_windows_map_dev): the poses come from the caller (a refinement pass's
 // absolute G) and the links from an index map (track_link_kernel<true>); track_map_inputs_kernel emits every match out of a feature at its landmark's position.
+// Gated inside the passes (the *_gated_dev map entries): the frame states come from the caller too (kf_gate_kernel<true> on a pass's G), and the
+// walk and the keyframe sets are the gated ones (track_walk_kernel<true>, kf_set_kernel<true>).
 //
 // gfx950 mapping: the reference walks std::unordered_map<id, Landmark> with per-landmark observation vectors; here a track is a chain
 // of (frame, keypoint) nodes linked by two flat int32 tables pred / succ (B x kp_capacity) filled by one scatter pass per frame pair,
@@ -377,11 +379,17 @@ __global__ __launch_bounds__(64) void kf_set_kernel(int B, int n_kf, double near
 }
 
 // ---- insert_key_frame's gate, one thread per frame: frame 0 is a keyframe (initialization), frame f >= 1 gets keyframe_state(num_inliers_,
-// T_c_l_) from the pose stage's outputs of item f - 1
-__global__ __launch_bounds__(256) void kf_gate_kernel(int B, const int32_t* __restrict__ num_inliers, const double* __restrict__ T_rel, int32_t* __restrict__ state) {
+// T_c_l_) from the pose stage's outputs of item f - 1.  T: the relative poses T_rel (n_frames - 1 rows), or -- kAbs, a refinement pass's gate
+// (vslam_gate_states_dev absolute = 1) -- the absolute poses G (n_frames rows), T_c_l_ = G_f o G_{f-1}^-1 as the reference takes it (:615)
+template <bool kAbs>
+__global__ __launch_bounds__(256) void kf_gate_kernel(int B, const int32_t* __restrict__ num_inliers, const double* __restrict__ T, int32_t* __restrict__ state) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= B) return;
-    state[f] = f == 0 ? 2 : keyframe_state(num_inliers[f - 1], T_rel + (size_t)(f - 1) * 7);
+    if (!kAbs || f == 0) { state[f] = f == 0 ? 2 : keyframe_state(num_inliers[f - 1], T + (size_t)(f - 1) * 7); return; }
+    double Gi[7], T_c_l[7];
+    se3::inverse(T + (size_t)(f - 1) * 7, Gi);
+    se3::mul(T + (size_t)f * 7, Gi, T_c_l);
+    state[f] = keyframe_state(num_inliers[f - 1], T_c_l);
 }
 
 // policy 0 through vslam_build_windows_kf_dev: the sliding window's sets written out
@@ -730,11 +738,13 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     if (kp.G) VS_HIP(hipMemcpyAsync(G, kp.G, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (the map builder: the caller's poses)
     else if (in.d_T_abs) VS_HIP(hipMemcpyAsync(G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
     else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(1), dim3(256), 0, stream, d.B, in.d_T_rel, G);
+    const int32_t* state = kp.state_in ? kp.state_in : kp.frame_state; // (the map builder: the caller's states)
     if (gate) { // the states depend on the pose stage's outputs alone, the keyframe sets on the states and the poses
-        hipLaunchKernelGGL(kf_gate_kernel, dim3((d.B + 255) / 256), dim3(256), 0, stream, d.B, kp.num_inliers, in.d_T_rel, kp.frame_state);
+        if (!kp.state_in)
+            hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((d.B + 255) / 256), dim3(256), 0, stream, d.B, kp.num_inliers, in.d_T_rel, kp.frame_state);
         if (kp.policy == 1) hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D);
         hipLaunchKernelGGL(kf_set_kernel<true>, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, kp.policy == 1 ? D : nullptr, kp.kf_frame, kp.evicted,
-                           set_flags, kp.frame_state, nmem);
+                           set_flags, state, nmem);
     } else if (cull) { // the keyframe sets depend on the poses alone
         hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D);
         hipLaunchKernelGGL(kf_set_kernel<false>, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, D, kp.kf_frame, kp.evicted, set_flags, nullptr, nullptr);
@@ -746,7 +756,7 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
         hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr);
     if (gate)
         hipLaunchKernelGGL(track_walk_kernel<true>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
-                           G, in.d_carry_in, root, relsrc, (const int32_t*)kp.frame_state);
+                           G, in.d_carry_in, root, relsrc, state);
     else
         hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
                            G, in.d_carry_in, root, relsrc, nullptr);
@@ -780,11 +790,21 @@ int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStre
     return VSLAM_OK;
 }
 
+// ---- the keyframe gate on its own (vslam_gate_states_dev): on the relative poses (the gated builder's states, bit for bit) or on absolute ones
+int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream) {
+    ProfScope prof__(stream, "kf_gate_kernel");
+    if (absolute) hipLaunchKernelGGL(kf_gate_kernel<true>, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_T, d_state);
+    else hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_T, d_state);
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
 // ---- one refinement pass's pose inputs (vslam_build_map_pnp_inputs_dev): the walk of the builders on the caller's poses G and the previous pass's
-// links (in_of_match_prev, or the pose stage's own-depth flags and track_rule when it is null), then the map inputs of every frame pair
-int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const double K4[4], double reproj_thr, int track_rule,
-                          DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match, int out_capacity, int32_t* d_status,
-                          hipStream_t stream) {
+// links (in_of_match_prev, or the pose stage's own-depth flags and track_rule when it is null), then the map inputs of every frame pair.
+// d_state (vslam_build_map_pnp_inputs_gated_dev; else null): the previous pass's frame states -- the gated walk, a non-keyframe creates nothing
+int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
+                          double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
+                          int out_capacity, int32_t* d_status, hipStream_t stream) {
     TrackDims d;
     d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = 1;
     const size_t tab = (size_t)d.B * d.kp_cap;
@@ -804,8 +824,12 @@ int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const in
                            d_in_of_match_prev);
     else
         hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr);
-    hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr,
-                       cand, pred, succ, d_G, nullptr, root, relsrc, nullptr);
+    if (d_state)
+        hipLaunchKernelGGL(track_walk_kernel<true>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable,
+                           kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, d_state);
+    else
+        hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable,
+                           kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, nullptr);
     hipLaunchKernelGGL(track_map_inputs_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_kps, in.d_xyz, kp2lr, root, relsrc, d_G,
                        out_capacity, d_xyz_out, d_uv_out, d_n_out, d_in_of_match, d_status);
     VS_HIP(hipGetLastError());

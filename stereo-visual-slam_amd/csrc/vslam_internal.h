@@ -312,17 +312,20 @@ int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t
 // gate (vslam_build_windows_gated_dev): insert_key_frame's keyframe gate on num_inliers (n_frames - 1) and T_rel, states to frame_state; policy 0 / 1.
 // map (vslam_build_windows_map_dev): the poses G (n_frames x 7) come from the caller instead of the chain of d_T_rel, and when in_of_match is set
 // ((n_frames - 1) x match_capacity) the links are decided through it: match k of item i holds when in_of_match >= 0 and that input's d_pose_inlier flag is set.
+// gate with state_in (vslam_build_windows_map_gated_dev): the frame states are the caller's (n_frames), not computed from num_inliers / T_rel.
 struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evicted; bool gate = false; const int32_t* num_inliers = nullptr; int32_t* frame_state = nullptr;
-                  const double* G = nullptr; const int32_t* in_of_match = nullptr; };
+                  const double* G = nullptr; const int32_t* in_of_match = nullptr; const int32_t* state_in = nullptr; };
 // K4 = {fx, fy, cx, cy}, reproj_thr (pixels), track_rule: see Tuning::track_rule
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
                          int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream);
 int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream);
-// one refinement pass's pose inputs against the map (vslam_build_map_pnp_inputs_dev)
-int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const double K4[4], double reproj_thr, int track_rule,
-                          DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match, int out_capacity, int32_t* d_status,
-                          hipStream_t stream);
+// insert_key_frame's gate per frame (vslam_gate_states_dev): absolute 0 on T_rel (n_frames - 1 rows), 1 on absolute poses (n_frames rows)
+int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream);
+// one refinement pass's pose inputs against the map (vslam_build_map_pnp_inputs_dev; d_state non-null: the gated walk, *_gated_dev)
+int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
+                          double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
+                          int out_capacity, int32_t* d_status, hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {

@@ -44,16 +44,25 @@ class KeyframePipeline:
         that camera-frame point, poses relative and chained; "map" -- after that stage, `pose_passes` refinement passes solve every frame against the
         MAP, as VO::motion_estimation does (visual_odometry.cpp:260-277: every matched feature of the last frame at its landmark's position), each pass
         parallel over the batch (vslam_build_map_pnp_inputs_dev; after K passes frames 0..K are the sequential loop's), and the windows are built on
-        the last pass's poses and links (vslam_build_windows_map_dev).  Not with keyframe_gate or in sequence mode."""
+        the last pass's poses and links (vslam_build_windows_map_dev).  Not with keyframe_gate=True or in sequence mode.
+        keyframe_gate="per_pass" (pose_inputs="map"): the gate inside the passes -- states^0 from stage A's inlier counts and relative poses, pass k walks
+        the tracks with states^{k-1} (a non-keyframe creates no landmark and takes no reliable depth), solves, and takes states^k from its own inlier
+        counts and poses (vslam_gate_states_dev); the windows are the gated ones on (G^K, links^K, states^K) (vslam_build_windows_map_gated_dev).  After
+        K passes frames 0..K are the gated sequential loop's (include/vslam_hip.h)."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
+        assert keyframe_gate in (False, True, "per_pass"), "keyframe_gate: False, True (on stage A's inputs) or 'per_pass' (inside the map passes)"
+        per_pass = keyframe_gate == "per_pass"
         assert not keyframe_gate or (ba_windows == "tracks" and frame_range is None), "keyframe_gate needs ba_windows='tracks' and no frame_range"
         assert pose_inputs in ("own_depth", "map")
+        assert not per_pass or pose_inputs == "map", "keyframe_gate='per_pass' needs pose_inputs='map'"
         if pose_inputs == "map":
             assert with_ba and ba_windows == "tracks" and int(pose_passes) >= 1, "pose_inputs='map' needs ba_windows='tracks' and pose_passes >= 1"
-            assert not keyframe_gate and frame_range is None, "pose_inputs='map' is not available with keyframe_gate or frame_range"
+            assert (per_pass or not keyframe_gate) and frame_range is None, \
+                "pose_inputs='map' is not available with keyframe_gate=True (keyframe_gate='per_pass' gates inside the passes) or frame_range"
         self.pose_inputs, self.pose_passes = pose_inputs, int(pose_passes)
-        self.window_policy, self.near_dist, self.keyframe_gate = window_policy, float(near_dist), bool(keyframe_gate)
+        self.window_policy, self.near_dist = window_policy, float(near_dist)
+        self.keyframe_gate = "per_pass" if per_pass else bool(keyframe_gate)
         self.depth = depth
         self.pose = pose   # "lm": north_star motion-only LM; "ransac": the reference's cv::solvePnPRansac(..., 100, 4.0, 0.99) (visual_odometry.cpp:277)
         self.ba_windows = ba_windows
@@ -150,7 +159,7 @@ class KeyframePipeline:
             if window_policy == "reference" or keyframe_gate or pose_inputs == "map":
                 self.ba_kf_frame = torch.zeros((B, n_kf), dtype=torch.int32, device=d)
                 self.ba_evicted = torch.zeros(B, dtype=torch.int32, device=d)
-            if keyframe_gate:
+            if keyframe_gate:   # (per_pass: the latest pass's states, updated in place pass by pass)
                 self.ba_frame_state = torch.zeros(B, dtype=torch.int32, device=d)
             tr = TracksIn()
             tr.n_frames = B; tr.kp_capacity = self.cap; tr.lr_capacity = self.cap; tr.match_capacity = self.cap; tr.pnp_capacity = self.cap
@@ -171,6 +180,8 @@ class KeyframePipeline:
                 self.map_ninl = torch.zeros(B, dtype=torch.int32, device=d)
                 self.map_status = torch.zeros(1, dtype=torch.int32, device=d)
                 self.map_cur = 0
+                if per_pass:    # (the states the last pass started from: what it changed is a report)
+                    self.map_state_prev = torch.zeros(B, dtype=torch.int32, device=d)
                 mt = TracksIn()
                 for f_, _ in TracksIn._fields_:
                     setattr(mt, f_, getattr(tr, f_))
@@ -276,24 +287,37 @@ class KeyframePipeline:
 
     def _map_passes(self):
         """pose_inputs="map": G^0 = the chain of the stage's relative poses, links^0 its flags; pass k solves every frame f against the map of
-        (G^{k-1}, links^{k-1}) -- LM from the guess G^{k-1}_f, RANSAC without one -- and an item with no inlier keeps G^k_f = G^{k-1}_{f-1}"""
+        (G^{k-1}, links^{k-1}) -- LM from the guess G^{k-1}_f, RANSAC without one -- and an item with no inlier keeps G^k_f = G^{k-1}_{f-1}.
+        keyframe_gate="per_pass": states^0 = the gate on stage A's counts and T_rel; pass k walks with states^{k-1}, then gates on its counts and G^k"""
         B, cap, n = self.B, self.cap, self.B - 1
         mt = self.map_tracks
         cur = 0
+        gated = self.keyframe_gate == "per_pass"
         self.vo.chain_poses_dev(B, self.d_Tpnp.data_ptr(), self.map_G[cur].data_ptr())
+        if gated:
+            self.vo.gate_states_dev(B, self.d_Tpnp.data_ptr(), 0, self.d_ninl.data_ptr(), self.ba_frame_state.data_ptr())
         prev_index, prev_inl = None, self.d_inl
-        for _ in range(self.pose_passes):
+        for k in range(self.pose_passes):
             nxt = cur ^ 1
             G, Gn = self.map_G[cur], self.map_G[nxt]
             mt.d_pose_inlier = prev_inl.data_ptr(); mt.pnp_capacity = cap
-            self.vo.build_map_pnp_inputs_dev(mt, G.data_ptr(), None if prev_index is None else prev_index.data_ptr(), self.map_xyz.data_ptr(),
-                                             self.map_uv.data_ptr(), self.map_n.data_ptr(), self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
+            prev = None if prev_index is None else prev_index.data_ptr()
+            if gated:
+                self.vo.build_map_pnp_inputs_gated_dev(mt, G.data_ptr(), prev, self.ba_frame_state.data_ptr(), self.map_xyz.data_ptr(), self.map_uv.data_ptr(),
+                                                       self.map_n.data_ptr(), self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
+            else:
+                self.vo.build_map_pnp_inputs_dev(mt, G.data_ptr(), prev, self.map_xyz.data_ptr(), self.map_uv.data_ptr(), self.map_n.data_ptr(),
+                                                 self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
             with torch.cuda.stream(self.stream):
                 guess = torch.cat([G[1:], G[:1]])   # (item i: frame i + 1; the last row is not read)
             self._solve(self.map_xyz, self.map_uv, self.map_n, self.map_T, self.map_inl[nxt], self.map_ninl, guess)
             with torch.cuda.stream(self.stream):
                 Gn[0].copy_(self.d_Tident[0])
                 Gn[1:].copy_(torch.where((self.map_ninl[:n] > 0)[:, None], self.map_T[:n], G[:n]))
+                if gated and k == self.pose_passes - 1:
+                    self.map_state_prev.copy_(self.ba_frame_state)
+            if gated:   # (the inputs of this pass were built from the states before: same stream, so overwriting them here is ordered)
+                self.vo.gate_states_dev(B, Gn.data_ptr(), 1, self.map_ninl.data_ptr(), self.ba_frame_state.data_ptr())
             prev_index, prev_inl, cur = self.map_index[nxt], self.map_inl[nxt], nxt
         self.map_cur = cur
 
@@ -303,6 +327,11 @@ class KeyframePipeline:
             c = self.map_cur
             mt = self.map_tracks
             mt.d_pose_inlier = self.map_inl[c].data_ptr(); mt.pnp_capacity = self.cap
+            if self.keyframe_gate == "per_pass":
+                self.vo.build_windows_map_gated_dev(mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr(), self.ba_frame_state.data_ptr(), self.n_kf,
+                                                    1 if self.window_policy == "reference" else 0, self.near_dist, self.lm_capacity, self.edge_capacity,
+                                                    self.ba_batch, self.ba_kf_frame.data_ptr(), self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
+                return
             self.vo.build_windows_map_dev(mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr(), self.n_kf, 1 if self.window_policy == "reference" else 0,
                                           self.near_dist, self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(),
                                           self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
@@ -393,8 +422,10 @@ class KeyframePipeline:
                 out["ba_kf_frame"] = self.ba_kf_frame.cpu().numpy(); out["ba_evicted"] = self.ba_evicted.cpu().numpy()
             else:
                 out["ba_kf_frame"], out["ba_evicted"] = sliding_keyframes(B, self.n_kf)
-            if self.keyframe_gate:
+            if self.keyframe_gate:   # (per_pass: the last pass's states; frame_state_prev: the states that pass started from)
                 out["frame_state"] = self.ba_frame_state.cpu().numpy()
+                if self.keyframe_gate == "per_pass":
+                    out["frame_state_prev"] = self.map_state_prev.cpu().numpy()
         if self.pose_inputs == "map":   # the last refinement pass (item i: frame i + 1); T_c_w = its poses G^K
             c = self.map_cur
             out["map_n"] = self.map_n.cpu().numpy(); out["map_xyz"] = self.map_xyz.cpu().numpy(); out["map_uv"] = self.map_uv.cpu().numpy()
