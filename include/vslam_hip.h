@@ -140,6 +140,20 @@ int vslam_feature_matching_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stri
                                const double* d_gap, int gate, int B, int max_rows,
                                vslam_dmatch* d_out, int out_capacity, int32_t* d_nout);
 
+/* vslam_feature_matching_dev on a SUBSET of every item's query rows (additive: the ABI version is unchanged).  d_qsel (B x sel_capacity int32, device):
+ * item b's selected query rows, d_qsel[b][0 .. d_nqsel[b]), ASCENDING original row indices; d_nqsel (B, device) their counts.
+ * CONTRACT: the result equals vslam_feature_matching_dev run on the gathered rows Q[d_qsel[b][0 .. n)] with every queryIdx mapped back to the original
+ * row index: trainIdx, distance, the output order (ascending original query index), the gate arithmetic (d_min over the subset's matches), the
+ * out_capacity cut and d_nout are the unmasked entry's.  The first-minimum tie rules are unchanged (ascending selected row = ascending original row,
+ * because the list ascends).  With d_qsel[b] = 0 .. d_nq[b] - 1 the output is vslam_feature_matching_dev's bit for bit; an empty selection gives
+ * d_nout[b] = 0.  The unselected rows are never staged: the cost follows the selection's length, not d_nq.
+ * PRECONDITION (not detected, like the one-to-one d_f2f of vslam_tracks_in): every index lies in [0, min(d_nq[b], max_rows)) and the list is strictly
+ * ascending; otherwise the result is undefined (no access leaves the item's rows).  Refused with VSLAM_ERR_ARG: NULL d_qsel / d_nqsel,
+ * sel_capacity < 1 or > 4096 (the matcher's row limit), and what vslam_feature_matching_dev refuses. */
+int vslam_feature_matching_subset_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq, const int32_t* d_qsel,
+                                      const int32_t* d_nqsel, int sel_capacity, const uint8_t* d_t, size_t t_stride_bytes, const int32_t* d_nt,
+                                      const double* d_gap, int gate, int B, int max_rows, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout);
+
 /* ------------------------------------------------------------------ A6: dense stereo disparity --------- */
 /* Replaces VO::disparity_map (visual_odometry.cpp:159-174): cv::StereoSGBM::create(0, 96, 9, 8*9*9, 32*9*9, 1, 63, 10,
  * 100, 32)->compute(left, right) followed by convertTo(CV_32F, 1/16).  left/right: h x w u8 (row stride in bytes);
@@ -437,7 +451,8 @@ int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const
  *      (0 oldest evicted, 1 culling); at states 0 and 1 the inliers pass through, nothing is recorded and the window is empty -- the rules of
  *      vslam_build_windows_gated_dev.
  * Deviations kept from vslam_build_windows_gated_dev: a rejected frame passes through (status bit 2), frame_gap is 1, no Lost state, BA results are
- * not fed back into tracking, windows are independent, the frame-to-frame matcher's query set is every keypoint of the last frame.
+ * not fed back into tracking, windows are independent, the frame-to-frame matcher's query set is every keypoint of the last frame (this last one is
+ * lifted by vslam_build_map_pnp_inputs_requery_dev below).
  * Passes: pass 0 is the pose stage (G^0 = the chain of d_T_rel, links^0 = its flags plus track_rule, states^0 = vslam_gate_states_dev(d_T_rel,
  * absolute = 0) on its inlier counts); pass k walks the tracks with states^{k-1} on (G^{k-1}, links^{k-1}) (vslam_build_map_pnp_inputs_gated_dev),
  * solves every item, takes G^k and links^k (the failure rule of step 3), then states^k = vslam_gate_states_dev(G^k, absolute = 1) on the pass's
@@ -458,6 +473,37 @@ int vslam_gate_states_dev(vslam_ctx* ctx, int n_frames, const double* d_T, int a
 int vslam_build_map_pnp_inputs_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
                                          const int32_t* d_frame_state, float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity,
                                          int32_t* d_status);
+
+/* ---- The gated passes with the REFERENCE'S QUERY SET (additive: the ABI version and vslam_tracks_in are unchanged).  VO::tracking
+ * (visual_odometry.cpp:568-575) builds descriptors_last from frame_last_.features_ only, and feature_matching runs its cross-check and the
+ * max(match_ratio d_min, match_gap_thr frame_gap) gate on THAT subset.  In the gated sequential loop above, steps 1-2 then read:
+ *   1. the query set is the features of frame f - 1 (as there); the frame-to-frame table of pair f - 1 -> f is the cross-checked, gated match of
+ *      THOSE keypoints' descriptors (ascending keypoint index) against every keypoint of frame f;
+ *   2. the inputs are every match of that table, in match order (every query is a feature by construction).
+ * Frame 0's features are its depth-valid keypoints.  The deviation "the matcher's query set is every keypoint of the last frame" does not apply to
+ * this mode; the others stay (a rejected frame passes through, frame_gap is 1, no Lost state, BA results are not fed back, windows are independent),
+ * and the query order is ascending keypoint index where the reference's is feature order (ties and RANSAC's draw order only).
+ * vslam_build_map_pnp_inputs_requery_dev = vslam_build_map_pnp_inputs_gated_dev, except that
+ *   (a) the walk uses in->d_f2f / in->d_nf2f (the table the previous pass solved on) with that pass's index map and flags, and d_frame_state -- as there;
+ *   (b) per frame f it writes the features of the walk -- d_feat (n_frames x in->kp_capacity int32): the ascending keypoint indices, d_nfeat (n_frames);
+ *   (c) every pair i -> i + 1 is matched again by vslam_feature_matching_subset_dev's kernels: queries = the rows d_feat[i] of frame i's descriptors
+ *       (frame f's block at d_desc + f * desc_stride_bytes, 32 bytes per keypoint), trains = every keypoint of frame i + 1 (in->d_nkps, required),
+ *       frame_gap 1, gate on, the context's match_ratio / match_gap_thr; the table goes to d_f2f_out ((n_frames - 1) x in->match_capacity) /
+ *       d_nf2f_out (n_frames - 1), which must not alias in->d_f2f / in->d_nf2f;
+ *   (d) d_xyz_w, d_uv, d_n, d_input_of_match are emitted ON THE NEW TABLE (d_input_of_match indexes d_f2f_out).
+ * The caller solves, and hands the next pass -- and vslam_build_windows_map_gated_dev -- in->d_f2f = this pass's d_f2f_out with this pass's index map
+ * and flags.  Pass 1 takes the pose stage's all-keypoint table with d_input_of_match_prev = NULL.
+ * CONTRACT: when the solver is a pure function of its inputs, after k passes the tables of pairs 0..k-1 and the poses, masks, states and windows of
+ * frames 0..k equal the sequential loop's with steps 1-2 as above (the features of frame f after pass k are final for f <= k - 1: they depend on the
+ * links into frames <= f and the tables of pairs <= f - 1, final after pass k - 1; pass 1 needs no links for frame 0).  With every keypoint of every
+ * frame a feature the table is vslam_feature_matching_dev's and the inputs are vslam_build_map_pnp_inputs_gated_dev's on it, bit for bit.
+ * n_frames = 1: d_nfeat[0] = 0 and nothing else is written.  Refused with VSLAM_ERR_ARG: what the gated entry refuses; NULL d_desc, d_feat, d_nfeat,
+ * d_f2f_out, d_nf2f_out or in->d_nkps; d_desc / desc_stride_bytes not multiples of 16 or desc_stride_bytes < kp_capacity x 32; kp_capacity > 4096;
+ * n_frames - 1 > max_batch; d_f2f_out overlapping in->d_f2f (or d_nf2f_out == in->d_nf2f). */
+int vslam_build_map_pnp_inputs_requery_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
+                                           const int32_t* d_frame_state, const uint8_t* d_desc, size_t desc_stride_bytes, int32_t* d_feat, int32_t* d_nfeat,
+                                           vslam_dmatch* d_f2f_out, int32_t* d_nf2f_out, float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match,
+                                           int out_capacity, int32_t* d_status);
 
 /* vslam_build_windows_map_dev with the frame states d_frame_state (n_frames, device) as an INPUT: the gated windows of vslam_build_windows_gated_dev --
  * the gated walk, keyframe sets updated at state 2 only (policy 0 oldest evicted, 1 culling), empty windows with d_n_kf[b] = 0 at states 0 and 1,

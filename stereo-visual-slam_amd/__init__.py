@@ -106,6 +106,7 @@ SIGNATURES = {
     "vslam_feature_detection_dev": (I, [P, P, Z, I, I, P, P, P]),
     "vslam_feature_matching": (I, [P, P, I, P, I, D, I, P, P]),
     "vslam_feature_matching_dev": (I, [P, P, Z, P, P, Z, P, P, I, I, I, P, I, P]),
+    "vslam_feature_matching_subset_dev": (I, [P, P, Z, P, P, P, I, P, Z, P, P, I, I, I, P, I, P]),
     "vslam_disparity_map": (I, [P, P, P, I, I, I, P, P, P]),
     "vslam_disparity_map_dev": (I, [P, P, P, Z, I, I, I, I, P, P, P]),
     "vslam_find_3d_disparity": (I, [P, P, I, P, I, I, I, P, P, P, P, P]),
@@ -130,6 +131,7 @@ SIGNATURES = {
     "vslam_build_windows_map_dev": (I, [P, P, P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_gate_states_dev": (I, [P, I, P, I, P, P]),
     "vslam_build_map_pnp_inputs_gated_dev": (I, [P, P, P, P, P, P, P, P, P, I, P]),
+    "vslam_build_map_pnp_inputs_requery_dev": (I, [P, P, P, P, P, P, Z, P, P, P, P, P, P, P, P, I, P]),
     "vslam_build_windows_map_gated_dev": (I, [P, P, P, P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_ba_status_dev": (I, [P, I, P]), "vslam_ba_schedule_passes_dev": (I, [P, I, P]), "vslam_ba_deferred_dev": (I, [P, I, P]),
     "vslam_edge_jacobians": (I, [P, I, P, P, P, P, P, P, P, P, P]),
@@ -297,6 +299,11 @@ class VO:
         out = np.zeros(max(len(q), 1), DMATCH_DTYPE); n = C.c_int()
         self._chk(self.lib.vslam_feature_matching(self.h, q, len(q), t, len(t), frame_gap, gate, out, C.byref(n)), "vslam_feature_matching")
         return out[:n.value].copy()
+
+    def feature_matching_subset_dev(self, d_q, q_stride, d_nq, d_qsel, d_nqsel, sel_cap, d_t, t_stride, d_nt, d_gap, gate, B, max_rows, d_out, out_cap, d_nout):
+        """feature_matching_dev on the query rows d_qsel[b][0 .. d_nqsel[b]) (ascending) of every item; queryIdx = the original row.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_feature_matching_subset_dev(self.h, d_q, q_stride, d_nq, d_qsel, d_nqsel, sel_cap, d_t, t_stride, d_nt, d_gap, gate, B, max_rows,
+                                                             d_out, out_cap, d_nout), "vslam_feature_matching_subset_dev")
 
     def feature_matching_dev(self, d_q, q_stride, d_nq, d_t, t_stride, d_nt, d_gap, gate, B, max_rows, d_out, out_cap, d_nout):
         self._chk(self.lib.vslam_feature_matching_dev(self.h, d_q, q_stride, d_nq, d_t, t_stride, d_nt, d_gap, gate, B, max_rows, d_out, out_cap,
@@ -472,6 +479,14 @@ class VO:
         """build_map_pnp_inputs_dev with the gated walk on the previous pass's frame states.  Semantics in include/vslam_hip.h."""
         self._chk(self.lib.vslam_build_map_pnp_inputs_gated_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n,
                                                                 d_input_of_match, out_capacity, d_status), "vslam_build_map_pnp_inputs_gated_dev")
+
+    def build_map_pnp_inputs_requery_dev(self, tracks, d_T_c_w, d_input_of_match_prev, d_frame_state, d_desc, desc_stride, d_feat, d_nfeat, d_f2f_out,
+                                         d_nf2f_out, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status):
+        """build_map_pnp_inputs_gated_dev with every pair re-matched on the features of its first frame (the reference's query set) between the walk and the
+        emit: writes the feature lists, the new frame-to-frame table and the inputs on that table.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_build_map_pnp_inputs_requery_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match_prev, d_frame_state, d_desc, desc_stride,
+                                                                  d_feat, d_nfeat, d_f2f_out, d_nf2f_out, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity,
+                                                                  d_status), "vslam_build_map_pnp_inputs_requery_dev")
 
     def build_windows_map_gated_dev(self, tracks, d_T_c_w, d_input_of_match, d_frame_state, n_kf, policy, near_dist, lm_capacity, edge_capacity, batch,
                                     d_kf_frame, d_evicted, d_status):

@@ -230,7 +230,8 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "lm_window_kernel<pnp> pnp_wave_kernel pnp_inlier_kernel pnp_epnp_kernels epnp_front_kernel epnp_jacobi_kernel epnp_back_kernel pnp_count_inliers_kernel hbm_copy_probe_kernel "
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
-           "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel";
+           "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
+           "match_train_nearest_sel_kernel track_features_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -486,6 +487,23 @@ int vslam_feature_matching_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stri
     VS_ENTER(c);
     return launch_match(d_q, q_stride_bytes, d_nq, d_t, t_stride_bytes, d_nt, d_gap, gate, c->p.match_ratio, c->p.match_gap_thr, B, max_rows,
                         c->match.d_train_best, d_out, out_capacity, d_nout, c->stream);
+}
+
+int vslam_feature_matching_subset_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq, const int32_t* d_qsel,
+                                      const int32_t* d_nqsel, int sel_capacity, const uint8_t* d_t, size_t t_stride_bytes, const int32_t* d_nt,
+                                      const double* d_gap, int gate, int B, int max_rows, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !d_q || !d_t || !d_nq || !d_nt || !d_gap || !d_out || !d_nout || out_capacity <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!d_qsel || !d_nqsel) { set_error("vslam_feature_matching_subset_dev: d_qsel and d_nqsel are required"); return VSLAM_ERR_ARG; }
+    if (sel_capacity < 1 || sel_capacity > kMaxRows) { set_error("sel_capacity %d outside 1..%d (the matcher's row limit)", sel_capacity, kMaxRows); return VSLAM_ERR_ARG; }
+    if (B > c->p.max_batch) { set_error("batch %d exceeds context max_batch %d", B, c->p.max_batch); return VSLAM_ERR_ARG; }
+    if ((((uintptr_t)d_q | (uintptr_t)d_t | (uintptr_t)q_stride_bytes | (uintptr_t)t_stride_bytes) & 15) != 0) {
+        set_error("vslam_feature_matching_subset_dev: d_q, d_t and both strides must be multiples of 16 bytes (the matcher reads descriptors with 16-byte loads)");
+        return VSLAM_ERR_ARG;
+    }
+    VS_ENTER(c);
+    return launch_match(d_q, q_stride_bytes, d_nq, d_t, t_stride_bytes, d_nt, d_gap, gate, c->p.match_ratio, c->p.match_gap_thr, B, max_rows,
+                        c->match.d_train_best, d_out, out_capacity, d_nout, c->stream, d_qsel, sel_capacity, d_nqsel);
 }
 
 int vslam_feature_matching(vslam_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, double frame_gap, int gate,
@@ -1033,9 +1051,9 @@ int vslam_gate_states_dev(vslam_ctx* ctx, int n_frames, const double* d_T, int a
     return launch_gate_states(n_frames, d_T, absolute, d_num_inliers, d_frame_state, c->stream);
 }
 
-// d_frame_state: null for the ungated entry, required by the gated one
+// d_frame_state: null for the ungated entry, required by the gated ones; rq: the re-match of the requery entry (its scratch is filled in here), else null
 static int map_pnp_inputs(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, const int32_t* d_frame_state,
-                          float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status) {
+                          float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status, MapRequery* rq = nullptr) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !in) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (int rc = map_refuses(in, d_T_c_w)) return rc;
@@ -1044,12 +1062,28 @@ static int map_pnp_inputs(vslam_ctx* ctx, const vslam_tracks_in* in, const doubl
         !in->d_reliable || (in->n_frames > 1 && (!in->d_f2f || !in->d_nf2f || !in->d_pose_inlier))) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if ((long long)in->n_frames * in->kp_capacity > 0x7FFFFFFFll) { set_error("n_frames x kp_capacity exceeds the 31-bit node keys"); return VSLAM_ERR_ARG; }
     if (in->kp_capacity > 65536) { set_error("kp_capacity %d exceeds 65536 (the window builder packs a keypoint index into 16 bits)", in->kp_capacity); return VSLAM_ERR_ARG; }
+    if (rq) {
+        if (!rq->d_desc || !rq->d_feat || !rq->d_nfeat || !rq->d_f2f_out || !rq->d_nf2f_out || !in->d_nkps) {
+            set_error("the re-match needs d_desc, d_feat, d_nfeat, d_f2f_out, d_nf2f_out and in->d_nkps"); return VSLAM_ERR_ARG;
+        }
+        if ((((uintptr_t)rq->d_desc | (uintptr_t)rq->desc_stride) & 15) != 0 || rq->desc_stride < (size_t)in->kp_capacity * 32) {
+            set_error("d_desc and desc_stride_bytes must be multiples of 16 bytes, desc_stride_bytes >= kp_capacity x 32"); return VSLAM_ERR_ARG;
+        }
+        if (in->kp_capacity > kMaxRows) { set_error("kp_capacity %d exceeds the matcher's %d rows", in->kp_capacity, kMaxRows); return VSLAM_ERR_ARG; }
+        if (in->n_frames - 1 > c->p.max_batch) { set_error("%d frame pairs exceed context max_batch %d", in->n_frames - 1, c->p.max_batch); return VSLAM_ERR_ARG; }
+        if (in->n_frames > 1) { // the walk reads in->d_f2f while nothing orders it against the re-match's writes: the two tables must not overlap
+            const size_t bytes = (size_t)(in->n_frames - 1) * in->match_capacity * sizeof(vslam_dmatch);
+            const uintptr_t a = (uintptr_t)in->d_f2f, b = (uintptr_t)rq->d_f2f_out;
+            if ((a < b + bytes && b < a + bytes) || in->d_nf2f == rq->d_nf2f_out) { set_error("d_f2f_out / d_nf2f_out must not alias in->d_f2f / in->d_nf2f"); return VSLAM_ERR_ARG; }
+        }
+        rq->ratio = c->p.match_ratio; rq->gap_thr = c->p.match_gap_thr; rq->d_train_best = c->match.d_train_best;
+    }
     VS_ENTER(c);
     double K4[4];
     fill_K(c, K4);
     const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
     return launch_map_pnp_inputs(*in, d_T_c_w, d_input_of_match_prev, d_frame_state, K4, c->p.pnp_reproj_thr, track_rule, c->track, d_xyz_w, d_uv, d_n,
-                                 d_input_of_match, out_capacity, d_status, c->stream);
+                                 d_input_of_match, out_capacity, d_status, c->stream, rq);
 }
 
 int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, float* d_xyz_w,
@@ -1062,6 +1096,15 @@ int vslam_build_map_pnp_inputs_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* 
                                          int32_t* d_status) {
     if (!d_frame_state) { set_error("the gated walk needs d_frame_state (n_frames states of the previous pass)"); return VSLAM_ERR_ARG; }
     return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status);
+}
+
+int vslam_build_map_pnp_inputs_requery_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
+                                           const int32_t* d_frame_state, const uint8_t* d_desc, size_t desc_stride_bytes, int32_t* d_feat, int32_t* d_nfeat,
+                                           vslam_dmatch* d_f2f_out, int32_t* d_nf2f_out, float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match,
+                                           int out_capacity, int32_t* d_status) {
+    if (!d_frame_state) { set_error("the gated walk needs d_frame_state (n_frames states of the previous pass)"); return VSLAM_ERR_ARG; }
+    MapRequery rq = {d_desc, desc_stride_bytes, d_feat, d_nfeat, d_f2f_out, d_nf2f_out, 0.0, 0.0, nullptr};
+    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status, &rq);
 }
 
 int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match, int n_kf, int policy,

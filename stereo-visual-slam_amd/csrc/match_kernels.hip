@@ -66,12 +66,20 @@ __device__ inline void fold_tile(const v16i (&acc)[kColTiles], int ib, int nq, b
 // Work items are numbered column-block-major (w = (colblock * qsplit + split) * B + item): the items' live column blocks
 // come first in the grid and spread evenly over the XCDs / CUs, the blocks beyond an item's train rows (capacity padding)
 // sit at the end and exit at once.  (With the item as the slow index the live blocks of every item landed on the same few XCDs.)
+// kSel (vslam_feature_matching_subset_dev): the query set of item b is the ascending row list d_qsel[b][0 .. d_nqsel[b]).  The list is COMPACTED on the
+// way into LDS -- staged tile row r is Q[qsel[r]] -- so a selection of n rows costs n / 32 tiles, the MFMA / fold path is untouched (the exact
+// 256 - 2 hamming identity holds) and the packed key carries the row's RANK in the list; match_finalize_kernel maps rank -> row.  The list ascends,
+// so ascending rank = ascending original row and the first-minimum tie rule is the unmasked kernel's.
+template <bool kSel>
 __global__ __launch_bounds__(kMatchBlock) void match_train_nearest_kernel(
     const uint8_t* __restrict__ d_q, size_t q_stride, const int32_t* __restrict__ d_nq, const uint8_t* __restrict__ d_t, size_t t_stride,
-    const int32_t* __restrict__ d_nt, int max_rows, int qsplit, int B, uint32_t* __restrict__ d_train_best) {
+    const int32_t* __restrict__ d_nt, int max_rows, int qsplit, int B, uint32_t* __restrict__ d_train_best, const int32_t* __restrict__ d_qsel,
+    int sel_cap, const int32_t* __restrict__ d_nqsel) {
     const int w = blockIdx.x;
     const int b = w % B, split = (w / B) % qsplit, cb = w / (B * qsplit);
-    const int nq = min(d_nq[b], max_rows), nt = min(d_nt[b], max_rows);
+    const int nrows = min(d_nq[b], max_rows), nt = min(d_nt[b], max_rows);
+    const int nq = kSel ? min(max(d_nqsel[b], 0), min(sel_cap, nrows)) : nrows; // the rows that compete: all of them, or the selection's length
+    const int32_t* sel = kSel ? d_qsel + (size_t)b * sel_cap : nullptr;
     const int c0 = cb * kColsPerBlock;
     if (c0 >= nt || nq <= 0) return;
     // query range of this split, in whole tiles
@@ -104,7 +112,8 @@ __global__ __launch_bounds__(kMatchBlock) void match_train_nearest_kernel(
     // staging: a tile is 32 rows x 8 dwords of raw descriptor = one dword per thread, expanded to 32 operand bytes into LDS
     const int srow = threadIdx.x >> 3, sword = threadIdx.x & 7;
     auto gload = [&](int tile, uint32_t& x) {
-        const int r0 = min(tile * kQRows + srow, nq - 1);
+        int r0 = min(tile * kQRows + srow, nq - 1);
+        if (kSel) r0 = min(max(sel[r0], 0), nrows - 1); // rank -> row (the clamp keeps a list that breaks the precondition inside the item)
         x = reinterpret_cast<const uint32_t*>(Q + (size_t)r0 * 32)[sword];
     };
     auto sstore = [&](int buf, uint32_t x) {
@@ -183,9 +192,12 @@ constexpr int kFinBlock = 1024;
 __global__ __launch_bounds__(kFinBlock) void match_finalize_kernel(
     const int32_t* __restrict__ d_nq, const int32_t* __restrict__ d_nt, const double* __restrict__ d_gap, int gate,
     double ratio, double gap_thr, int max_rows, const uint32_t* __restrict__ d_train_best, vslam_dmatch* __restrict__ d_out,
-    int out_capacity, int32_t* __restrict__ d_nout) {
+    int out_capacity, int32_t* __restrict__ d_nout, const int32_t* __restrict__ d_qsel, int sel_cap, const int32_t* __restrict__ d_nqsel) {
     const int b = blockIdx.x;
-    const int nq = min(d_nq[b], max_rows), nt = min(d_nt[b], max_rows);
+    const int nrows = min(d_nq[b], max_rows), nt = min(d_nt[b], max_rows);
+    // a selection (d_qsel non-null): the keys carry ranks in the list, nq is its length and queryIdx is the list's entry
+    const int32_t* sel = d_qsel ? d_qsel + (size_t)b * sel_cap : nullptr;
+    const int nq = sel ? min(max(d_nqsel[b], 0), min(sel_cap, nrows)) : nrows;
     __shared__ uint32_t qbest[kMaxRows];
     __shared__ int s_wave_tot[kFinBlock / 64];
     __shared__ uint32_t s_min[kFinBlock / 64];
@@ -224,7 +236,7 @@ __global__ __launch_bounds__(kFinBlock) void match_finalize_kernel(
         const int r = block_rank(keep, s_wave_tot, total);
         if (keep && written + r < out_capacity) {
             vslam_dmatch m;
-            m.queryIdx = i; m.trainIdx = (int)(key & 0xFFFFu); m.imgIdx = 0; m.distance = (float)d;
+            m.queryIdx = sel ? sel[i] : i; m.trainIdx = (int)(key & 0xFFFFu); m.imgIdx = 0; m.distance = (float)d;
             out[written + r] = m;
         }
         written += total;
@@ -234,7 +246,8 @@ __global__ __launch_bounds__(kFinBlock) void match_finalize_kernel(
 
 int launch_match(const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, const uint8_t* d_t, size_t t_stride,
                  const int32_t* d_nt, const double* d_gap, int gate, double ratio, double gap_thr, int B, int max_rows,
-                 uint32_t* d_train_best, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout, hipStream_t stream) {
+                 uint32_t* d_train_best, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout, hipStream_t stream, const int32_t* d_qsel, int sel_cap,
+                 const int32_t* d_nqsel) {
     if (B <= 0) return VSLAM_OK;
     if (max_rows > kMaxRows || max_rows <= 0) { set_error("matcher: max_rows %d out of range (<= %d)", max_rows, kMaxRows); return VSLAM_ERR_ARG; }
     // fill the chip: ~>= 1024 workgroups.  Split the query range when the batch is small.
@@ -243,14 +256,18 @@ int launch_match(const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, const
     while (qsplit < 16 && (long)tblocks * qsplit * B < 1024 && max_rows / (qsplit * 2) >= 4 * kQRows) qsplit *= 2;
     // every in-range train row is written exactly once when the query range is not split
     if (qsplit > 1) VS_HIP(hipMemsetAsync(d_train_best, 0xFF, (size_t)B * max_rows * sizeof(uint32_t), stream));
-    {
+    if (d_qsel) {
+        ProfScope prof__(stream, "match_train_nearest_sel_kernel");
+        hipLaunchKernelGGL(match_train_nearest_kernel<true>, dim3(tblocks * qsplit * B), dim3(kMatchBlock), 0, stream, d_q, q_stride, d_nq, d_t, t_stride,
+                           d_nt, max_rows, qsplit, B, d_train_best, d_qsel, sel_cap, d_nqsel);
+    } else {
         ProfScope prof__(stream, "match_train_nearest_kernel");
-        hipLaunchKernelGGL(match_train_nearest_kernel, dim3(tblocks * qsplit * B), dim3(kMatchBlock), 0, stream, d_q, q_stride, d_nq, d_t, t_stride,
-                           d_nt, max_rows, qsplit, B, d_train_best);
+        hipLaunchKernelGGL(match_train_nearest_kernel<false>, dim3(tblocks * qsplit * B), dim3(kMatchBlock), 0, stream, d_q, q_stride, d_nq, d_t, t_stride,
+                           d_nt, max_rows, qsplit, B, d_train_best, nullptr, 0, nullptr);
     }
     ProfScope prof__(stream, "match_finalize_kernel");
     hipLaunchKernelGGL(match_finalize_kernel, dim3(B), dim3(kFinBlock), 0, stream, d_nq, d_nt, d_gap, gate, ratio, gap_thr,
-                       max_rows, d_train_best, d_out, out_capacity, d_nout);
+                       max_rows, d_train_best, d_out, out_capacity, d_nout, d_qsel, sel_cap, d_nqsel);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

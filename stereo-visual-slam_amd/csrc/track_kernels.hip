@@ -18,6 +18,8 @@
 // absolute G) and the links from an index map (track_link_kernel<true>); track_map_inputs_kernel emits every match out of a feature at its landmark's position.
 // Gated inside the passes (the *_gated_dev map entries): the frame states come from the caller too (kf_gate_kernel<true> on a pass's G), and the
 // walk and the keyframe sets are the gated ones (track_walk_kernel<true>, kf_set_kernel<true>).
+// The reference's query set inside those passes (vslam_build_map_pnp_inputs_requery_dev): track_features_kernel lists every frame's features after the
+// walk, the subset matcher (match_kernels.hip) re-matches every pair on them, and track_map_inputs_kernel emits on that table.
 //
 // gfx950 mapping: the reference walks std::unordered_map<id, Landmark> with per-landmark observation vectors; here a track is a chain
 // of (frame, keypoint) nodes linked by two flat int32 tables pred / succ (B x kp_capacity) filled by one scatter pass per frame pair,
@@ -470,6 +472,30 @@ __global__ __launch_bounds__(256) void track_map_inputs_kernel(TrackDims d, cons
     }
 }
 
+// ---- per frame, after the walk (vslam_build_map_pnp_inputs_requery_dev): the frame's FEATURES -- the slots with root != -1, the one definition the
+// kernel above uses -- as an ascending list (the ballot ranks again) and their count: the query set VO::tracking hands feature_matching
+// (visual_odometry.cpp:568-575, descriptors_last = frame_last_.features_).  Also the frame gap of the pair that starts here (1: adjacent frames).
+__global__ __launch_bounds__(256) void track_features_kernel(TrackDims d, const int32_t* __restrict__ root, const int32_t* __restrict__ nkps,
+                                                            int32_t* __restrict__ feat, int32_t* __restrict__ nfeat, double* __restrict__ gap) {
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int s_tot[4];
+    const int n = nkps ? min(max(nkps[f], 0), d.kp_cap) : d.kp_cap;
+    int written = 0;
+    for (int base = 0; base < n; base += 256) {
+        const int i = base + tid;
+        const bool ok = i < n && root[(size_t)f * d.kp_cap + i] != -1;
+        const unsigned long long mask = __ballot(ok);
+        __syncthreads();
+        if (lane == 0) s_tot[wave] = __popcll(mask);
+        __syncthreads();
+        int off = written;
+        for (int w = 0; w < wave; ++w) off += s_tot[w];
+        if (ok) feat[(size_t)f * d.kp_cap + off + __popcll(mask & ((1ull << lane) - 1ull))] = i;
+        written += s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
+    }
+    if (tid == 0) { nfeat[f] = written; if (f + 1 < d.B) gap[f] = 1.0; }
+}
+
 // A chain HEAD of window [s, b]: a node in frame s, or a node without predecessor (a landmark created inside the window).  Every
 // landmark observed in the window has exactly one.  Returns the observations it has inside the window (0: not a head) -- from the
 // slot's info word alone (track_chain_kernel), no chain walk.
@@ -801,23 +827,29 @@ int launch_gate_states(int n_frames, const double* d_T, int absolute, const int3
 
 // ---- one refinement pass's pose inputs (vslam_build_map_pnp_inputs_dev): the walk of the builders on the caller's poses G and the previous pass's
 // links (in_of_match_prev, or the pose stage's own-depth flags and track_rule when it is null), then the map inputs of every frame pair.
-// d_state (vslam_build_map_pnp_inputs_gated_dev; else null): the previous pass's frame states -- the gated walk, a non-keyframe creates nothing
+// d_state (vslam_build_map_pnp_inputs_gated_dev; else null): the previous pass's frame states -- the gated walk, a non-keyframe creates nothing.
+// rq (vslam_build_map_pnp_inputs_requery_dev; else null): between the walk and the emit every pair is RE-MATCHED with the features of its first frame
+// as the query set (track_features_kernel + the subset matcher), and the inputs are emitted on that table instead of in.d_f2f
 int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
                           double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
-                          int out_capacity, int32_t* d_status, hipStream_t stream) {
+                          int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq) {
     TrackDims d;
     d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = 1;
     const size_t tab = (size_t)d.B * d.kp_cap;
-    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *cand;
+    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *cand; double* gap = nullptr;
     if (int rc = carve(scratch, stream, [&](Layout& L) {
             kp2lr = L.take<int32_t>(tab); pred = L.take<int32_t>(tab); succ = L.take<int32_t>(tab);
             root = L.take<int32_t>(tab); relsrc = L.take<int32_t>(tab); cand = L.take<int32_t>(tab);
+            if (rq) gap = L.take<double>(d.B);
         })) return rc;
     TrackCam cam;
     cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
     ProfScope prof__(stream, "map_pnp_inputs_kernels", 4);
     VS_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t), stream));
-    if (d.B < 2) return VSLAM_OK;
+    if (d.B < 2) {
+        if (rq) VS_HIP(hipMemsetAsync(rq->d_nfeat, 0, sizeof(int32_t) * d.B, stream)); // (no pair: no walk, no list)
+        return VSLAM_OK;
+    }
     hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
     if (d_in_of_match_prev)
         hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ,
@@ -830,7 +862,17 @@ int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const in
     else
         hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable,
                            kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, nullptr);
-    hipLaunchKernelGGL(track_map_inputs_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_kps, in.d_xyz, kp2lr, root, relsrc, d_G,
+    const vslam_dmatch* f2f = in.d_f2f; const int32_t* nf2f = in.d_nf2f;
+    if (rq) { // pair i: queries = the features of frame i, trains = every keypoint of frame i + 1, the gate of VO::feature_matching at frame_gap 1
+        hipLaunchKernelGGL(track_features_kernel, dim3(d.B), dim3(256), 0, stream, d, root, in.d_nkps, rq->d_feat, rq->d_nfeat, gap);
+        prof_end(stream); // (the matcher brackets its own kernels: this bracket closes before it ...
+        if (int rc = launch_match(rq->d_desc, rq->desc_stride, in.d_nkps, rq->d_desc + rq->desc_stride, rq->desc_stride, in.d_nkps + 1, gap, 1, rq->ratio,
+                                  rq->gap_thr, d.B - 1, d.kp_cap, rq->d_train_best, rq->d_f2f_out, d.match_cap, rq->d_nf2f_out, stream, rq->d_feat, d.kp_cap,
+                                  rq->d_nfeat)) return rc;
+        prof_begin(stream, "track_map_inputs_kernel", 1); // ... and prof__ closes this one, around the emit)
+        f2f = rq->d_f2f_out; nf2f = rq->d_nf2f_out;
+    }
+    hipLaunchKernelGGL(track_map_inputs_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, f2f, nf2f, in.d_kps, in.d_xyz, kp2lr, root, relsrc, d_G,
                        out_capacity, d_xyz_out, d_uv_out, d_n_out, d_in_of_match, d_status);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;

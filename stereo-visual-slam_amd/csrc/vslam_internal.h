@@ -173,7 +173,8 @@ struct MatchBuffers {
 };
 int launch_match(const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, const uint8_t* d_t, size_t t_stride,
                  const int32_t* d_nt, const double* d_gap, int gate, double ratio, double gap_thr, int B, int max_rows,
-                 uint32_t* d_train_best, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout, hipStream_t stream);
+                 uint32_t* d_train_best, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout, hipStream_t stream,
+                 const int32_t* d_qsel = nullptr, int sel_cap = 0, const int32_t* d_nqsel = nullptr);
 
 // ----------------------------------------------------------------------------------------------- geometry
 struct CamParams { double fx, fy, cx, cy, b, dmin, dmax, drel, row_tol; };
@@ -322,10 +323,15 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
 int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream);
 // insert_key_frame's gate per frame (vslam_gate_states_dev): absolute 0 on T_rel (n_frames - 1 rows), 1 on absolute poses (n_frames rows)
 int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream);
-// one refinement pass's pose inputs against the map (vslam_build_map_pnp_inputs_dev; d_state non-null: the gated walk, *_gated_dev)
+// the re-match of vslam_build_map_pnp_inputs_requery_dev: frame f's descriptors at d_desc + f * desc_stride; outputs the feature lists (n_frames x kp_capacity,
+// n_frames) and the new frame-to-frame table ((n_frames - 1) x match_capacity); the matcher's gate parameters and scratch
+struct MapRequery { const uint8_t* d_desc; size_t desc_stride; int32_t* d_feat; int32_t* d_nfeat; vslam_dmatch* d_f2f_out; int32_t* d_nf2f_out;
+                    double ratio, gap_thr; uint32_t* d_train_best; };
+// one refinement pass's pose inputs against the map (vslam_build_map_pnp_inputs_dev; d_state non-null: the gated walk, *_gated_dev; rq non-null: the
+// pairs are re-matched on their feature sets between the walk and the emit, *_requery_dev)
 int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
                           double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
-                          int out_capacity, int32_t* d_status, hipStream_t stream);
+                          int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq = nullptr);
 
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {

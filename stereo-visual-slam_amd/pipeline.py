@@ -26,7 +26,7 @@ class KeyframePipeline:
     def __init__(self, B, device=0, anms_num=1500, n_lm=3000, n_kf=10, unique_frames=64, unique_windows=None, seed=0, verbose=False,
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
                  lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
-                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1):
+                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all"):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
         Inputs: ONE rendered sequence of `unique_frames` consecutive stereo keyframes, laid over the batch as a ping-pong
@@ -48,7 +48,11 @@ class KeyframePipeline:
         keyframe_gate="per_pass" (pose_inputs="map"): the gate inside the passes -- states^0 from stage A's inlier counts and relative poses, pass k walks
         the tracks with states^{k-1} (a non-keyframe creates no landmark and takes no reliable depth), solves, and takes states^k from its own inlier
         counts and poses (vslam_gate_states_dev); the windows are the gated ones on (G^K, links^K, states^K) (vslam_build_windows_map_gated_dev).  After
-        K passes frames 0..K are the gated sequential loop's (include/vslam_hip.h)."""
+        K passes frames 0..K are the gated sequential loop's (include/vslam_hip.h).
+        f2f_queries: "all" -- the frame-to-frame table is stage A's, every keypoint of the last frame a query; "features" (pose_inputs="map",
+        keyframe_gate="per_pass") -- the reference's query set (visual_odometry.cpp:568-575): pass k re-matches every pair with the features of its
+        first frame, as the walk of (table^{k-1}, links^{k-1}, states^{k-1}) finds them, against every keypoint of the second, and solves on that
+        table (vslam_build_map_pnp_inputs_requery_dev); stage A's table stays untouched, the windows are built on the last pass's table."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
         assert keyframe_gate in (False, True, "per_pass"), "keyframe_gate: False, True (on stage A's inputs) or 'per_pass' (inside the map passes)"
@@ -60,6 +64,9 @@ class KeyframePipeline:
             assert with_ba and ba_windows == "tracks" and int(pose_passes) >= 1, "pose_inputs='map' needs ba_windows='tracks' and pose_passes >= 1"
             assert (per_pass or not keyframe_gate) and frame_range is None, \
                 "pose_inputs='map' is not available with keyframe_gate=True (keyframe_gate='per_pass' gates inside the passes) or frame_range"
+        assert f2f_queries in ("all", "features")
+        assert f2f_queries == "all" or (per_pass and pose_inputs == "map"), "f2f_queries='features' needs pose_inputs='map' and keyframe_gate='per_pass'"
+        self.f2f_queries = f2f_queries
         self.pose_inputs, self.pose_passes = pose_inputs, int(pose_passes)
         self.window_policy, self.near_dist = window_policy, float(near_dist)
         self.keyframe_gate = "per_pass" if per_pass else bool(keyframe_gate)
@@ -186,6 +193,12 @@ class KeyframePipeline:
                 for f_, _ in TracksIn._fields_:
                     setattr(mt, f_, getattr(tr, f_))
                 self.map_tracks = mt
+                if f2f_queries == "features":   # table^k alternates between two buffers (table^0 = stage A's d_f2f); the last pass's feature lists
+                    self.map_f2f = [torch.zeros((B, self.cap, 16), dtype=torch.uint8, device=d) for _ in range(2)]
+                    self.map_nf2f = [torch.zeros(B, dtype=torch.int32, device=d) for _ in range(2)]
+                    self.map_feat = torch.zeros((B, self.cap), dtype=torch.int32, device=d)
+                    self.map_nfeat = torch.zeros(B, dtype=torch.int32, device=d)
+                    self.map_table = None   # (index into map_f2f of the last pass's table)
             bb = BaBatch()
             bb.n_windows = B; bb.n_kf = n_kf
             bb.d_lm_off = self.ba_lm_off.data_ptr(); bb.d_edge_off = self.ba_e_off.data_ptr(); bb.d_T_c_w = self.ba_T.data_ptr()
@@ -297,12 +310,22 @@ class KeyframePipeline:
         if gated:
             self.vo.gate_states_dev(B, self.d_Tpnp.data_ptr(), 0, self.d_ninl.data_ptr(), self.ba_frame_state.data_ptr())
         prev_index, prev_inl = None, self.d_inl
+        requery = self.f2f_queries == "features"
+        mt.d_f2f = self.d_f2f.data_ptr(); mt.d_nf2f = self.d_nf2f.data_ptr()   # (table^0: stage A's)
         for k in range(self.pose_passes):
             nxt = cur ^ 1
             G, Gn = self.map_G[cur], self.map_G[nxt]
             mt.d_pose_inlier = prev_inl.data_ptr(); mt.pnp_capacity = cap
             prev = None if prev_index is None else prev_index.data_ptr()
-            if gated:
+            if requery:   # walk on table^{k-1}, re-match on its features into the other buffer, inputs on that table; the next pass walks on it
+                t = k & 1
+                self.vo.build_map_pnp_inputs_requery_dev(mt, G.data_ptr(), prev, self.ba_frame_state.data_ptr(), self.d_desc.data_ptr(), cap * 32,
+                                                         self.map_feat.data_ptr(), self.map_nfeat.data_ptr(), self.map_f2f[t].data_ptr(),
+                                                         self.map_nf2f[t].data_ptr(), self.map_xyz.data_ptr(), self.map_uv.data_ptr(), self.map_n.data_ptr(),
+                                                         self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
+                mt.d_f2f = self.map_f2f[t].data_ptr(); mt.d_nf2f = self.map_nf2f[t].data_ptr()
+                self.map_table = t
+            elif gated:
                 self.vo.build_map_pnp_inputs_gated_dev(mt, G.data_ptr(), prev, self.ba_frame_state.data_ptr(), self.map_xyz.data_ptr(), self.map_uv.data_ptr(),
                                                        self.map_n.data_ptr(), self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
             else:
@@ -428,6 +451,11 @@ class KeyframePipeline:
                     out["frame_state_prev"] = self.map_state_prev.cpu().numpy()
         if self.pose_inputs == "map":   # the last refinement pass (item i: frame i + 1); T_c_w = its poses G^K
             c = self.map_cur
+            if self.f2f_queries == "features" and self.map_table is not None:   # the table that pass solved on and the feature lists it was matched from
+                t = self.map_table
+                out["map_f2f"] = self.map_f2f[t].cpu().numpy().reshape(B, -1).view(DMATCH_DTYPE).reshape(B, cap)
+                out["map_nf2f"] = self.map_nf2f[t].cpu().numpy()
+                out["map_feat"] = self.map_feat.cpu().numpy(); out["map_nfeat"] = self.map_nfeat.cpu().numpy()
             out["map_n"] = self.map_n.cpu().numpy(); out["map_xyz"] = self.map_xyz.cpu().numpy(); out["map_uv"] = self.map_uv.cpu().numpy()
             out["map_index"] = self.map_index[c].cpu().numpy(); out["map_inl"] = self.map_inl[c].cpu().numpy(); out["map_ninl"] = self.map_ninl.cpu().numpy()
             out["T_c_w"] = self.map_G[c].cpu().numpy()

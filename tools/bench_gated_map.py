@@ -12,7 +12,9 @@ Reports, one JSON line per configuration:
   * state changes from pass K - 1 to pass K (frame_state against frame_state_prev);
   * keyframe-trajectory error against the rendered ground truth: trajectory() after the BA schedule (the keyframes' BA-refined poses, each from
     the last keyframe window that held it) against synth.stereo_sequence's T_c_w, both relative to the batch's first frame.
-Usage: python tools/bench_gated_map.py [--B 1024] [--pose lm ransac] [--passes 1 2 4 -1] [--reps 3]   (-1: B - 1 passes)"""
+--queries all features: the gated passes with stage A's all-keypoint frame-to-frame table ("all") and with every pair re-matched per pass on the
+features of its first frame, the reference's query set (f2f_queries="features"); per record also the mean pose inputs per frame of the last pass.
+Usage: python tools/bench_gated_map.py [--B 1024] [--pose lm ransac] [--passes 1 2 4 -1] [--reps 3] [--queries all features]   (-1: B - 1 passes)"""
 import argparse
 import json
 import os
@@ -57,6 +59,7 @@ def main():
     ap.add_argument("--passes", nargs="+", type=int, default=[1, 2, 4, -1])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--unique-frames", type=int, default=64)
+    ap.add_argument("--queries", nargs="+", default=["all"], choices=["all", "features"])
     args = ap.parse_args()
     from stereo_visual_slam_amd import synth
     from stereo_visual_slam_amd.pipeline import KeyframePipeline
@@ -64,15 +67,18 @@ def main():
     seq = synth.stereo_sequence(min(args.unique_frames, B), seed=0, workers=8)
     for pose in args.pose:
         base_ms, ungated_ms = None, {}
-        configs = [("stage_a", 0)] + [(g, K if K > 0 else B - 1) for K in args.passes for g in ("ungated", "per_pass")]
-        for gate, K in configs:
+        configs = [("stage_a", 0, "all")] + [(g, K if K > 0 else B - 1, qs) for K in args.passes for g in ("ungated", "per_pass")
+                                             for qs in (args.queries if g == "per_pass" else ["all"])]
+        for gate, K, queries in configs:
             kw = dict(keyframe_gate=True) if gate == "stage_a" else dict(pose_inputs="map", pose_passes=K,
                                                                          keyframe_gate="per_pass" if gate == "per_pass" else False)
+            if queries != "all":
+                kw["f2f_queries"] = queries
             p = KeyframePipeline(B, unique_frames=len(seq), sequence=seq, ba_windows="tracks", pose=pose, window_policy="reference", **kw)
             try:
                 p.stage_orb(); p.stage_stereo_match()
                 ms = _track_ms(p, args.reps)
-                rec = dict(pose=pose, gate=gate, passes=K, B=B, stage_track_kernel_ms=round(ms, 3))
+                rec = dict(pose=pose, gate=gate, queries=queries, passes=K, B=B, stage_track_kernel_ms=round(ms, 3))
                 if gate == "stage_a":
                     base_ms = ms
                 else:
@@ -88,6 +94,8 @@ def main():
                     rec["keyframes"] = int((st == 2).sum()); rec["rejected"] = int((st == 0).sum())
                     rec["keyframes_per_1024"] = round(1024.0 * rec["keyframes"] / B, 1)
                     if gate == "per_pass":
+                        rec["inputs_per_frame"] = round(float(out["map_n"][:B - 1].mean()), 1)
+                        rec["inliers_per_frame"] = round(float(out["map_ninl"][:B - 1].mean()), 1)
                         rec["state_changes_last_pass"] = int((st != out["frame_state_prev"]).sum())
                     rec["trajectory_keyframes"] = n
                     rec["kf_trans_err_m"] = dict(mean=round(float(te.mean()), 4), median=round(float(np.median(te)), 4), max=round(float(te.max()), 4))
