@@ -9,59 +9,58 @@
 //   step (ii) : key = d << 16 | j   -> min over {j : i*(j) = i} = smallest d, then smallest j (strict '<').
 //
 // gfx950 mapping.  The all-pairs Hamming table is the one dense contraction of the pipeline: with the descriptor bits
-// recoded as +-1 bytes, <a, b> = 256 - 2 hamming(a, b), so a 32 x 32 block of distances is eight
-// v_mfma_i32_32x32x32_i8 (exact integer arithmetic).  The +-1 form never exists in HBM: `match_train_nearest_kernel` reads the raw
-// 32-B descriptors and expands bits to bytes in registers -- the 64 train columns of a wave once, into the VGPRs that stay resident
-// as MFMA B operands; every 32-row query tile cooperatively (one dword -> 32 bytes per thread) on its way into LDS (row stride
-// 272 B: conflict-free ds_read_b128), shared by the four waves of the workgroup -- and folds the column minima in the
-// accumulator layout (column = lane % 32): per value one v_lshl_add + one v_max on packed keys, with the +256 bias
-// supplied as the MFMA C operand.  The previous v_xor + v_bcnt formulation was bound by v_bcnt_u32_b32 issuing at quarter rate.
+// recoded as +-1, <a, b> = 256 - 2 hamming(a, b).  +-1 is exact in FP4 (e2m1: 0x2 / 0xA), so a 32 x 32 block of distances is four
+// v_mfma_f32_32x32x64_f8f6f4 with FP4 operands (four VGPRs each; 32.5 cycles per instruction, the cycles of v_mfma_i32_32x32x32_i8 at
+// twice the K -- tools/scratch/mfma_fp4_layout.hip), exact in the f32 accumulator.  The +-1 form never exists in HBM:
+// `match_train_nearest_kernel` reads the raw 32-B descriptors and expands bits to nibbles in registers (a shift and a masked merge per operand
+// dword) -- the 128 train columns of a wave once, into the 64 VGPRs that stay resident as MFMA B operands; every 32-row query tile
+// cooperatively (one dword -> 16 bytes per thread) on its way into LDS (row stride 144 B: conflict-free ds_read_b128), shared by the four
+// waves of the workgroup.  The fold needs no key arithmetic: the tie-break enters as the C operand of a tile's first MFMA
+// (C = (31 - local row) * 2^-12), so the accumulator IS the key dot + row fraction (largest dot, then smallest row; exact in f32, see the
+// kernel's comment) and the column maxima are v_max3_f32 over the accumulator registers, two values per instruction.
+// 164 VGPRs, no scratch: three waves per SIMD.  (Before: eight v_mfma_i32_32x32x32_i8 per block on +-1 bytes and v_lshl_add + v_max per value
+// on packed integer keys, 219 VGPRs, 0.50 ms per 1024 items of 1500 x 1500; now 0.20 ms.)
 #include "vslam_internal.h"
 
 namespace vslam {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
 
-// four descriptor bits -> four bytes of +-1 (bit set -> 0xFF = -1, clear -> 0x01 = +1); bit k of the nibble -> byte k
-__device__ inline uint32_t expand_nibble(uint32_t nib) {
-    const uint32_t s = __umul24(nib & 0xFu, 0x204081u) & 0x01010101u;
-    return ((s << 8) - (s << 1)) | 0x01010101u;
+// 32 descriptor bits -> 32 e2m1 nibbles of +-1 (bit clear -> 0x2 = +1, set -> 0xA = -1) = the 16 operand bytes of one lane for one
+// K = 64 step.  Operand dword i, nibble n holds bit 4 n + i: a shift and a masked merge per dword.  (A Hamming dot product does not care
+// which k a bit lands on, only that the query side and the train side agree -- both go through this function.)
+__device__ inline v4i expand32(uint32_t x) {
+    return v4i{(int)(((x << 3) & 0x88888888u) | 0x22222222u), (int)(((x << 2) & 0x88888888u) | 0x22222222u),
+               (int)(((x << 1) & 0x88888888u) | 0x22222222u), (int)((x & 0x88888888u) | 0x22222222u)};
 }
-// 16 descriptor bits -> 16 operand bytes
-__device__ inline int4 expand_half(uint32_t bits16) {
-    return make_int4((int)expand_nibble(bits16), (int)expand_nibble(bits16 >> 4), (int)expand_nibble(bits16 >> 8), (int)expand_nibble(bits16 >> 12));
+// one K = 64 step of a 32 x 32 block: FP4 operands (cbsz = blgp = 4, four VGPRs each).  kBlockScale = 0 on both sides selects the instruction's
+// form without block scales, v_mfma_f32_32x32x64_f8f6f4 (products unscaled; half the encoding and no scale VGPR); 0x7F7F7F7F would be the scaled form
+// with E8M0 127 = 2^0.  tools/scratch/mfma_fp4_layout.hip checks both on the device.
+constexpr int kBlockScale = 0;
+__device__ inline v16f mma_fp4(v4i a, v4i b, v16f c) {
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(v8i{a[0], a[1], a[2], a[3], 0, 0, 0, 0}, v8i{b[0], b[1], b[2], b[3], 0, 0, 0, 0}, c, 4, 4, 0,
+                                                           kBlockScale, 0, kBlockScale);
+}
+
+// threadIdx.x behind a compiler barrier: lane arithmetic that is needed only after (or rarely inside) the tile loop is recomputed from it there
+// instead of staying in registers across the loop -- the loop runs at the 168-VGPR limit of three waves per SIMD
+__device__ inline int fresh_tid() {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
 }
 
 constexpr int kMatchBlock = 256;             // 4 waves
-constexpr int kColTiles = 4;                 // 32-column MFMA tiles per wave held in registers (2: accumulators double-buffered; 4: one A read feeds four tiles -- 0.137 vs 0.148 ms per 256 items of 1500 x 1500, 0.103 vs 0.099 at 1100, 0.046 vs 0.044 at 700)
+constexpr int kColTiles = 4;                 // 32-column MFMA tiles per wave held in registers (one A read from LDS feeds four tiles)
 constexpr int kColsPerWave = 32 * kColTiles;
 constexpr int kColsPerBlock = (kMatchBlock / 64) * kColsPerWave;
 constexpr int kQRows = 32;                   // query rows per LDS tile
-constexpr int kQStride = 272;                // bytes per staged query row (256 + 16: conflict-free 16-B reads)
-
-// epilogue of one 32-row query tile: fold the 16 accumulator slots of this lane (per column tile) into the running maximum of
-// dot << 16 | (0xFFFF - row) (signed compare: largest dot = smallest distance, then smallest row)
-__device__ inline void fold_tile(const v16i (&acc)[kColTiles], int ib, int nq, bool full, int (&m)[kColTiles]) {
-    const int inv = 0xFFFF - ib;
-    if (full) {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int iv = inv - (8 * (v / 4) + (v % 4));
-#pragma unroll
-            for (int t = 0; t < kColTiles; ++t) m[t] = max(m[t], (acc[t][v] << 16) + iv);
-        }
-    } else { // last, partial tile: rows >= nq must not compete
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int off = 8 * (v / 4) + (v % 4);
-            if (ib + off < nq) {
-#pragma unroll
-                for (int t = 0; t < kColTiles; ++t) m[t] = max(m[t], (acc[t][v] << 16) + inv - off);
-            }
-        }
-    }
-}
+constexpr int kQStride = 144;                // bytes per staged query row (128 + 16: conflict-free 16-B reads)
+constexpr float kRowUnit = 1.f / 4096.f;     // one row of tie-break in the f32 key (kMaxRows = 4096 rows fit the 12 fraction bits)
+constexpr float kNoRow = -4194304.f;         // C of a row past nq: dot + kNoRow is exact and below every real key
+static_assert(kMaxRows <= 4096, "the f32 key holds the row in 12 fraction bits");
 
 // Work items are numbered column-block-major (w = (colblock * qsplit + split) * B + item): the items' live column blocks
 // come first in the grid and spread evenly over the XCDs / CUs, the blocks beyond an item's train rows (capacity padding)
@@ -70,8 +69,13 @@ __device__ inline void fold_tile(const v16i (&acc)[kColTiles], int ib, int nq, b
 // way into LDS -- staged tile row r is Q[qsel[r]] -- so a selection of n rows costs n / 32 tiles, the MFMA / fold path is untouched (the exact
 // 256 - 2 hamming identity holds) and the packed key carries the row's RANK in the list; match_finalize_kernel maps rank -> row.  The list ascends,
 // so ascending rank = ascending original row and the first-minimum tie rule is the unmasked kernel's.
+//
+// The f32 key.  Within the tiles tile0 .. tile1 - 1 of this workgroup, row i (of tile T, local row i % 32) competes with
+//   key = dot + (32 (tile1 - T) - 1 - i % 32) * 2^-12 = dot + (32 tile1 - 1 - i) * 2^-12:  largest dot, then smallest row;
+// |dot| <= 256 and the fraction has 12 bits, so every key is exact in f32 and distinct per row.  The MFMA forms it: the first instruction of a
+// tile takes C = (31 - i % 32) * 2^-12 (constant per lane and register), and the running maxima gain 32 * 2^-12 before each tile.
 template <bool kSel>
-__global__ __launch_bounds__(kMatchBlock) void match_train_nearest_kernel(
+__global__ __launch_bounds__(kMatchBlock, 3) void match_train_nearest_kernel(
     const uint8_t* __restrict__ d_q, size_t q_stride, const int32_t* __restrict__ d_nq, const uint8_t* __restrict__ d_t, size_t t_stride,
     const int32_t* __restrict__ d_nt, int max_rows, int qsplit, int B, uint32_t* __restrict__ d_train_best, const int32_t* __restrict__ d_qsel,
     int sel_cap, const int32_t* __restrict__ d_nqsel) {
@@ -88,79 +92,79 @@ __global__ __launch_bounds__(kMatchBlock) void match_train_nearest_kernel(
     if (tile0 >= tile1) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     __shared__ alignas(16) int8_t sq[2][kQRows * kQStride];
-    __shared__ uint2 lut[256]; // descriptor byte -> its eight +-1 operand bytes
-    {
-        const uint32_t v = threadIdx.x;
-        lut[v] = make_uint2(expand_nibble(v), expand_nibble(v >> 4));
-    }
     const uint8_t* Q = d_q + (size_t)b * q_stride;
     const uint8_t* T = d_t + (size_t)b * t_stride;
-    // B operands: this wave's 64 train columns, expanded once and resident for the whole kernel.  Operand slice s of lane
-    // (r, h) holds k = 32 s + 16 h .. + 15, i.e. halfword 2 s + h of the descriptor.
-    v4i breg[kColTiles][8];
+    // B operands: this wave's 128 train columns, expanded once and resident for the whole kernel.  K step s of lane (r, h) holds
+    // dword 4 h + s of the descriptor (one 16-B load per column and lane).
+    v4i breg[kColTiles][4];
 #pragma unroll
     for (int t = 0; t < kColTiles; ++t) {
         const int j = min(c0 + wave * kColsPerWave + 32 * t + r, nt - 1);
-        const uint4 lo = *reinterpret_cast<const uint4*>(T + (size_t)j * 32), hi = *reinterpret_cast<const uint4*>(T + (size_t)j * 32 + 16);
-        const uint32_t wd[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int4 e = expand_half((wd[s] >> (16 * h)) & 0xFFFFu);
-            breg[t][s] = v4i{e.x, e.y, e.z, e.w};
-        }
+        const uint4 d = *reinterpret_cast<const uint4*>(T + (size_t)j * 32 + 16 * h);
+        breg[t][0] = expand32(d.x); breg[t][1] = expand32(d.y); breg[t][2] = expand32(d.z); breg[t][3] = expand32(d.w);
     }
-    // staging: a tile is 32 rows x 8 dwords of raw descriptor = one dword per thread, expanded to 32 operand bytes into LDS
+    // staging: a tile is 32 rows x 8 dwords of raw descriptor = one dword per thread, expanded to 16 operand bytes into LDS
     const int srow = threadIdx.x >> 3, sword = threadIdx.x & 7;
     auto gload = [&](int tile, uint32_t& x) {
         int r0 = min(tile * kQRows + srow, nq - 1);
         if (kSel) r0 = min(max(sel[r0], 0), nrows - 1); // rank -> row (the clamp keeps a list that breaks the precondition inside the item)
-        x = reinterpret_cast<const uint32_t*>(Q + (size_t)r0 * 32)[sword];
+        x = *reinterpret_cast<const uint32_t*>(Q + ((uint32_t)r0 * 32u + (uint32_t)sword * 4u)); // (32-bit offset from the item's base)
     };
-    auto sstore = [&](int buf, uint32_t x) {
-        const uint2 b0 = lut[x & 0xFFu], b1 = lut[(x >> 8) & 0xFFu], b2 = lut[(x >> 16) & 0xFFu], b3 = lut[x >> 24];
-        int4* dst = reinterpret_cast<int4*>(&sq[buf][srow * kQStride + sword * 32]);
-        dst[0] = make_int4((int)b0.x, (int)b0.y, (int)b1.x, (int)b1.y); dst[1] = make_int4((int)b2.x, (int)b2.y, (int)b3.x, (int)b3.y);
-    };
-    auto mma_tile = [&](int buf, v16i (&acc)[kColTiles]) {
-        v4i a[8];
+    auto sstore = [&](int buf, uint32_t x) { *reinterpret_cast<v4i*>(&sq[buf][srow * kQStride + sword * 16]) = expand32(x); };
+    // tie-break C of this lane's 16 accumulator slots (slot v = local row 8 (v / 4) + v % 4 + 4 h)
+    v16f ctie;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) a[s] = *reinterpret_cast<const v4i*>(&sq[buf][r * kQStride + s * 32 + h * 16]);
-        const v16i zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // (the first MFMA of a tile reads C = 0 as an inline constant: no accumulator clears)
-#pragma unroll
-        for (int t = 0; t < kColTiles; ++t) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[0], breg[t][0], zero, 0, 0, 0);
-#pragma unroll
-        for (int s = 1; s < 8; ++s)
-#pragma unroll
-            for (int t = 0; t < kColTiles; ++t) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], breg[t][s], acc[t], 0, 0, 0);
-    };
+    for (int v = 0; v < 16; ++v) ctie[v] = (float)(31 - (8 * (v / 4) + (v % 4) + 4 * h)) * kRowUnit;
     uint32_t x;
     gload(tile0, x);
-    __syncthreads(); // the expansion table is complete
     sstore(0, x);
     if (tile0 + 1 < tile1) gload(tile0 + 1, x);
     __syncthreads();
-    int m[kColTiles];
+    float m[kColTiles];
 #pragma unroll
-    for (int t = 0; t < kColTiles; ++t) m[t] = INT_MIN;
-    // four column tiles per wave: one set of accumulators; a query tile read from LDS once feeds 32 MFMAs (half the LDS
-    // traffic per MAC); the other wave of the SIMD fills the MFMA pipe while this one folds
-    v16i acc[kColTiles];
+    for (int t = 0; t < kColTiles; ++t) m[t] = -INFINITY;
+    // four column tiles per wave: one set of accumulators; a query tile read from LDS once feeds 16 MFMAs; the other waves of the SIMD
+    // fill the MFMA pipe while this one folds
+    v16f acc[kColTiles];
     for (int tile = tile0; tile < tile1; ++tile) {
         const int buf = (tile - tile0) & 1;
         if (tile + 1 < tile1) { sstore(buf ^ 1, x); if (tile + 2 < tile1) gload(tile + 2, x); } // (buffer buf ^ 1 was released by the barrier below)
-        mma_tile(buf, acc);
-        fold_tile(acc, tile * kQRows + 4 * h, nq, tile * kQRows + kQRows <= nq, m);
+        if (tile * kQRows + kQRows > nq) { // the item's last, partial tile (nothing follows it): rows >= nq must not compete
+            const int row0 = tile * kQRows + 4 * ((fresh_tid() >> 5) & 1);
+#pragma unroll
+            for (int v = 0; v < 16; ++v)
+                if (row0 + 8 * (v / 4) + (v % 4) >= nq) ctie[v] = kNoRow;
+        }
+        v4i a[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) a[s] = *reinterpret_cast<const v4i*>(&sq[buf][r * kQStride + (4 * h + s) * 16]);
+#pragma unroll
+        for (int t = 0; t < kColTiles; ++t) acc[t] = mma_fp4(a[0], breg[t][0], ctie);
+#pragma unroll
+        for (int s = 1; s < 4; ++s)
+#pragma unroll
+            for (int t = 0; t < kColTiles; ++t) acc[t] = mma_fp4(a[s], breg[t][s], acc[t]);
+        // fold: the accumulators ARE the keys -- one v_max3_f32 per two values
+#pragma unroll
+        for (int t = 0; t < kColTiles; ++t) {
+            float mm = m[t] + 32.f * kRowUnit;
+#pragma unroll
+            for (int v = 0; v < 16; v += 2) mm = __builtin_fmaxf(__builtin_fmaxf(acc[t][v], acc[t][v + 1]), mm);
+            m[t] = mm;
+        }
         __syncthreads();
     }
 #pragma unroll
-    for (int t = 0; t < kColTiles; ++t) m[t] = max(m[t], __shfl_xor(m[t], 32));
-    if (h == 0) {
+    for (int t = 0; t < kColTiles; ++t) m[t] = __builtin_fmaxf(m[t], __shfl_xor(m[t], 32));
+    const int tid = fresh_tid();
+    if ((tid & 32) == 0) {
 #pragma unroll
         for (int t = 0; t < kColTiles; ++t) {
-            const int mm = m[t];
-            const int j = c0 + wave * kColsPerWave + 32 * t + r;
-            if (j < nt && mm != INT_MIN) {
-                const uint32_t d = (uint32_t)(256 - (mm >> 16)) >> 1, i = 0xFFFFu - ((uint32_t)mm & 0xFFFFu);
+            const float mm = m[t];
+            const int j = c0 + (tid >> 6) * kColsPerWave + 32 * t + (tid & 31);
+            if (j < nt && mm >= -256.f) {
+                const float fl = __builtin_floorf(mm); // = dot; the fraction is (32 tile1 - 1 - row) * 2^-12
+                const uint32_t d = (uint32_t)(256 - (int)fl) >> 1, i = (uint32_t)(32 * tile1 - 1 - (int)((mm - fl) * 4096.f));
                 const uint32_t key = (d << 16) | i;
                 if (qsplit == 1) d_train_best[(size_t)b * max_rows + j] = key;
                 else atomicMin(&d_train_best[(size_t)b * max_rows + j], key);

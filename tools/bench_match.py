@@ -27,6 +27,13 @@ vo.sync(); dt = (time.perf_counter() - t0) / a.reps
 pr = vo.profile_read()
 print("B=%d N=%d  %.3f ms/call  %.2f T pair-distances/s" % (B, N, dt * 1e3, B * N * N / dt / 1e12))
 print({k: round(v[0] / a.reps, 4) for k, v in sorted(pr.items(), key=lambda kv: -kv[1][0])})
+# issue floor of the Hamming table: four v_mfma_f32_32x32x64_f8f6f4 (FP4) per 32 x 32 block at 32.5 cycles each (tools/scratch/mfma_fp4_layout.hip), column
+# tiles in whole workgroups of 512 columns, one matrix pipe per SIMD, nominal 2.4 GHz
+simds = 4 * torch.cuda.get_device_properties(0).multi_processor_count
+floor_ms = B * ((N + 31) // 32) * (16 * ((N + 511) // 512)) * 4 * 32.5 / (simds * 2.4e9) * 1e3
+k_ms = pr.get("match_train_nearest_kernel", (0.0,))[0] / a.reps
+if k_ms > 0:
+    print("match_train_nearest_kernel %.4f ms = %.0f %% of its MFMA issue floor (%.4f ms, FP4 32x32x64)" % (k_ms, 100.0 * floor_ms / k_ms, floor_ms))
 for pct in a.select:
     k = max(0, min(N, int(round(N * pct / 100.0))))
     rs = np.random.default_rng(1)
