@@ -6,7 +6,10 @@ import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
-KINDS = ["match", "sgbm", "orb", "ba", "pnp", "ransac", "windows", "ransac_dev", "ba_schedule", "ba_resident"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import structured_inputs as S  # noqa: E402
+
+KINDS = ["match", "sgbm", "orb", "ba", "pnp", "ransac", "windows", "ransac_dev", "ba_schedule", "ba_resident", "orb_ties", "sgbm_periodic"]
 
 
 class Mismatch(AssertionError):
@@ -60,6 +63,46 @@ def one_case(kind, rng, vo, pkg, O, synth):
                 fail("feature_detection", w=w, h=h, seed=seed, nf=nf, an=an)
         finally:
             ctx.close()
+    elif kind == "orb_ties":
+        # a random generator of tests/structured_inputs.py (tiled patch, mirrored noise, checkerboard, quantised blocks, binary noise, blob lattice) with random
+        # parameters and size: tied FAST scores, Harris responses and ANMS radii.  An image whose oracle counts exceed a device capacity must end in the
+        # capacity error instead.  (Images up to 640 x 360: the CPU oracle and the stage-by-stage capacity count dominate the case.)
+        w, h = int(rng.integers(160, 640)), int(rng.integers(120, 360))
+        gen = str(rng.choice(["tiled", "mirror", "checker", "quant", "binary", "blobs"]))
+        args = {"tiled": dict(t=int(rng.integers(8, 64)), seed=seed, cell=int(rng.integers(2, 4))), "mirror": dict(seed=seed), "checker": dict(s=int(rng.integers(5, 32))),
+                "quant": dict(levels=int(rng.integers(2, 6)), block=int(rng.integers(3, 7)), seed=seed), "binary": dict(seed=seed, block=int(rng.integers(2, 5))),
+                "blobs": dict(pitch=int(rng.integers(12, 40)), half=int(rng.integers(1, 3)))}[gen]
+        img = S.GENERATORS[gen](h, w, **args)
+        nf = int(rng.choice([300, 1000, 3000])); an = int(rng.choice([50, 100, 500, 1500]))
+        bits, cnt = S.device_capacity_bits(O, img, nf, an)
+        ctx = pkg.VO(device=0, max_batch=1, img_w=w, img_h=h, orb_nfeatures=nf, anms_num=an)
+        ctx.set_tuning(orb_fuse_min=int(forced))
+        try:
+            if bits or cnt["unknown"]:
+                try:
+                    ctx.feature_detection(img)
+                    fail("orb_ties: no capacity error", gen=gen, args=args, w=w, h=h, nf=nf, an=an, bits=bits)
+                except pkg.VslamError as e:
+                    if "capacity" not in str(e).lower():
+                        fail("orb_ties: wrong error", gen=gen, args=args, w=w, h=h, nf=nf, an=an, err=str(e))
+            else:
+                k, d = ctx.feature_detection(img); wk, wd = O.feature_detection(img, nf, an)
+                if not (kps_equal(k, wk) and np.array_equal(d, wd)):
+                    fail("orb_ties feature_detection", gen=gen, args=args, w=w, h=h, nf=nf, an=an)
+                det = O.orb_detect(img, nf)
+                if not kps_equal(ctx.adaptive_non_maximal_suppresion(det, an), O.anms(det, an)):
+                    fail("orb_ties anms", gen=gen, args=args, w=w, h=h, nf=nf, an=an)
+        finally:
+            ctx.close()
+    elif kind == "sgbm_periodic":
+        # a pair cut from a horizontally periodic texture: exact cost ties at d, d + p, d + 2p (noise 0) or near-ties (noise > 0); the first minimum wins
+        w, h = int(rng.integers(101, 500)), int(rng.integers(10, 150))
+        p = int(rng.integers(4, 80)); sh = int(rng.integers(0, 96)); noise = int(rng.choice([0, 0, 1, 2, 3, 6]))
+        Lc, R = S.periodic_pair(p, sh, noise, w, h, seed)
+        gf, gi, graw = vo.disparity_map(Lc, R, return_i16=True)
+        wi, wraw = O.sgbm_compute(Lc, R, return_raw=True)
+        if not (np.array_equal(graw, wraw) and np.array_equal(gi, wi)):
+            fail("sgbm_periodic", w=w, h=h, period=p, shift=sh, noise=noise, seed=seed)
     elif kind == "ba":
         nk = int(rng.integers(1, 13)); nl = int(rng.choice([40, 300, 1500, 2600]))
         win = synth.ba_window(n_kf=nk, n_lm=nl, seed=seed, max_obs=min(5, nk), min_obs=min(2, nk))
@@ -221,7 +264,7 @@ def run(seconds=120.0, seed=0, only="", vo=None, max_cases=None, schedule=None):
     i = 0
     try:
         while time.time() < t_end and (max_cases is None or i < max_cases):
-            kind = only or (schedule[i % len(schedule)] if schedule else rng.choice(["match", "match", "sgbm", "orb", "ba", "pnp", "ransac", "windows", "ransac_dev", "ba_schedule", "ba_resident"]))
+            kind = only or (schedule[i % len(schedule)] if schedule else rng.choice(["match", "match", "sgbm", "orb", "ba", "pnp", "ransac", "windows", "ransac_dev", "ba_schedule", "ba_resident", "orb_ties", "sgbm_periodic"]))
             one_case(kind, rng, vo, pkg, O, synth)
             n[kind] += 1
             i += 1

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-RING = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
+from orb_restatements import RING, anms_numpy as _anms_numpy, fast_numpy as _fast_numpy, pattern_from_header as _pattern_from_header
 
 
 def test_layout_known_answers(oracle):
@@ -93,21 +93,6 @@ def test_pyramid_chain_is_level_from_previous_level(oracle, synth):
     assert np.array_equal(lv[0], img)
     for l in range(1, 8):
         assert np.array_equal(lv[l], oracle.resize_linear(lv[l - 1], lv[l].shape[1], lv[l].shape[0]))
-
-
-def _fast_numpy(img, t):
-    """FAST-9/16 from the definition: >= 9 contiguous ring pixels all > v+t or all < v-t; score = largest t' that still passes"""
-    h, w = img.shape
-    I = img.astype(np.int64)
-    ring = np.stack([I[3 + dy:h - 3 + dy, 3 + dx:w - 3 + dx] for dx, dy in RING])  # 16 x (h-6) x (w-6)
-    c = I[3:h - 3, 3:w - 3]
-    d = c[None] - ring
-    ext = np.concatenate([d, d[:8]])
-    mins = np.stack([ext[i:i + 9].min(0) for i in range(16)]).max(0)       # best dark arc: all d >= mins
-    maxs = np.stack([(-ext[i:i + 9]).min(0) for i in range(16)]).max(0)    # best bright arc
-    best = np.maximum(mins, maxs)
-    corner = best > t
-    return corner, np.maximum(best, t) - 1
 
 
 def test_fast_matches_definition(oracle, synth):
@@ -251,24 +236,6 @@ def test_retain_best_keeps_ties(oracle):
     assert len(oracle.retain_best(kps, 10)) == 10 and len(oracle.retain_best(kps, 0)) == 0
 
 
-def _anms_numpy(kps, num):
-    """line-by-line numpy/python restatement of visual_odometry.cpp:96-157"""
-    if len(kps) < num:
-        return kps
-    order = np.argsort(-kps["response"], kind="stable")
-    k = kps[order]
-    rad = np.full(len(k), np.finfo(np.float64).max)
-    for i in range(len(k)):
-        thr = np.float32(k["response"][i]) * np.float32(1.11)
-        j = 0
-        while j < i and k["response"][j] > thr:
-            dx = np.float32(k["x"][i] - k["x"][j]); dy = np.float32(k["y"][i] - k["y"][j])
-            rad[i] = min(rad[i], np.sqrt(np.float64(dx) * np.float64(dx) + np.float64(dy) * np.float64(dy)))
-            j += 1
-    final = np.sort(rad)[::-1][num - 1]
-    return k[rad >= final]
-
-
 def test_anms_matches_reference_restated_in_numpy(oracle, synth):
     img = synth.noise_image(7, 400, 240)
     kps = oracle.orb_detect(img, 800)
@@ -278,13 +245,6 @@ def test_anms_matches_reference_restated_in_numpy(oracle, synth):
         assert len(got) >= num and len(got) == len(want)
         assert np.array_equal(got["x"], want["x"]) and np.array_equal(got["y"], want["y"])
     assert len(oracle.anms(kps, len(kps) + 1)) == len(kps)  # :100 no-op
-
-
-def _pattern_from_header():
-    import os, re
-    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "orb_pattern.h")).read()
-    nums = [int(v) for v in re.findall(r"-?\d+", txt.split("= {", 1)[1])]
-    return np.array(nums[:1024]).reshape(256, 4)
 
 
 def test_pattern_table_first_rows():
