@@ -135,10 +135,10 @@ def retain_best(kps, npoints):
     return kps[:n].copy()
 
 
-def orb_detect(img, nfeatures=3000, cap=8192):
+def orb_detect(img, nfeatures=3000, cap=8192, fast_threshold=20):
     img = _u8img(img)
     out = np.zeros(cap, KEYPOINT_DTYPE)
-    n = lib().vo_orb_detect(_p(img), img.shape[1], img.shape[0], img.strides[0], nfeatures, _p(out), cap)
+    n = lib().vo_orb_detect(_p(img), img.shape[1], img.shape[0], img.strides[0], nfeatures, int(fast_threshold), _p(out), cap)
     assert n >= 0, n
     return out[:n].copy()
 
@@ -158,11 +158,11 @@ def orb_compute(img, kps):
     return kps[:n].copy(), desc[:n].copy()
 
 
-def feature_detection(img, nfeatures=3000, anms_num=500, cap=8192):
+def feature_detection(img, nfeatures=3000, anms_num=500, cap=8192, fast_threshold=20):
     img = _u8img(img)
     kps = np.zeros(cap, KEYPOINT_DTYPE)
     desc = np.zeros((cap, 32), np.uint8)
-    n = lib().vo_feature_detection(_p(img), img.shape[1], img.shape[0], img.strides[0], nfeatures, anms_num,
+    n = lib().vo_feature_detection(_p(img), img.shape[1], img.shape[0], img.strides[0], nfeatures, anms_num, int(fast_threshold),
                                    _p(kps), cap, _p(desc))
     assert n >= 0, n
     return kps[:n].copy(), desc[:n].copy()
@@ -184,10 +184,10 @@ def bf_match_xcheck(q, t):
     return out[:n].copy()
 
 
-def feature_matching(q, t, frame_gap=1.0):
+def feature_matching(q, t, frame_gap=1.0, ratio=2.0, gap_thr=30.0):
     q, t = _desc(q), _desc(t)
     out = np.zeros(max(len(q), 1), DMATCH_DTYPE)
-    n = lib().vo_feature_matching(_p(q), len(q), _p(t), len(t), C.c_double(frame_gap), _p(out))
+    n = lib().vo_feature_matching(_p(q), len(q), _p(t), len(t), C.c_double(frame_gap), C.c_double(ratio), C.c_double(gap_thr), _p(out))
     return out[:n].copy()
 
 
@@ -263,23 +263,24 @@ def se3_angle_y(T):
 
 CAM_KITTI = np.array([718.856, 718.856, 607.1928, 185.2157, 0.573])  # types_def.hpp:53-54
 K_KITTI = CAM_KITTI[:4].copy()
+DEPTH_GATE = (10.0, 400.0, 40.0)  # visual_odometry.cpp:194, :201: valid 10 < Z < 400, reliable Z < 40
 
 
-def find_3d_disparity(kps, disparity, T_c_w, cam=CAM_KITTI):
+def find_3d_disparity(kps, disparity, T_c_w, cam=CAM_KITTI, depth_gate=DEPTH_GATE):
     kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
     disparity = np.ascontiguousarray(disparity, np.float32)
     n = len(kps)
     xyz = np.zeros((n, 3), np.float32); valid = np.zeros(n, np.uint8); rel = np.zeros(n, np.uint8)
     lib().vo_find_3d_disparity(_p(kps), n, _p(disparity), disparity.shape[1], disparity.shape[0], disparity.shape[1],
-                               _p(_d(T_c_w, 7)), _p(_d(cam, 5)), _p(xyz), _p(valid), _p(rel))
+                               _p(_d(T_c_w, 7)), _p(_d(cam, 5)), _p(_d(depth_gate, 3)), _p(xyz), _p(valid), _p(rel))
     return xyz, valid, rel
 
 
-def triangulate_dlt(uvL, uvR, T_c_w, cam=CAM_KITTI, row_tol=2.0):
+def triangulate_dlt(uvL, uvR, T_c_w, cam=CAM_KITTI, row_tol=2.0, depth_gate=DEPTH_GATE):
     uvL = np.ascontiguousarray(uvL, np.float32).reshape(-1, 2); uvR = np.ascontiguousarray(uvR, np.float32).reshape(-1, 2)
     n = len(uvL)
     xyz = np.zeros((n, 3), np.float32); valid = np.zeros(n, np.uint8); rel = np.zeros(n, np.uint8)
-    lib().vo_triangulate_dlt(_p(uvL), _p(uvR), n, _p(_d(T_c_w, 7)), _p(_d(cam, 5)), C.c_double(row_tol), _p(xyz), _p(valid), _p(rel))
+    lib().vo_triangulate_dlt(_p(uvL), _p(uvR), n, _p(_d(T_c_w, 7)), _p(_d(cam, 5)), C.c_double(row_tol), _p(_d(depth_gate, 3)), _p(xyz), _p(valid), _p(rel))
     return xyz, valid, rel
 
 
@@ -336,11 +337,12 @@ def pose_only_window(T, xyz, kf_idx, lm_idx, uv, K=K_KITTI, iters=10, huber_delt
     return T, chi2[:len(kf_idx)], _stats(st)
 
 
-def chi2_classify(chi2, flag_lm, lm_inlier):
+def chi2_classify(chi2, flag_lm, lm_inlier, threshold=5.991):
+    """threshold: the initial chi2 threshold; in the reference it is the variable that is also the Huber delta (optimization.cpp:154, :205)"""
     chi2 = _d(chi2); flag_lm = np.ascontiguousarray(flag_lm, np.int32)
     lm_inlier = np.ascontiguousarray(lm_inlier, np.uint8).copy()
     ni = C.c_int(); no = C.c_int()
-    th = lib().vo_chi2_classify(_p(chi2), len(chi2), _p(flag_lm), _p(lm_inlier), len(lm_inlier), C.byref(ni), C.byref(no))
+    th = lib().vo_chi2_classify(_p(chi2), len(chi2), _p(flag_lm), _p(lm_inlier), len(lm_inlier), C.c_double(threshold), C.byref(ni), C.byref(no))
     return float(th), lm_inlier, ni.value, no.value
 
 

@@ -27,9 +27,9 @@ int main(void) {
     const int cap = 8192;
     vo_keypoint* k0 = (vo_keypoint*)malloc(sizeof(vo_keypoint) * cap); vo_keypoint* k1 = (vo_keypoint*)malloc(sizeof(vo_keypoint) * cap);
     uint8_t* d0 = (uint8_t*)malloc((size_t)cap * 32); uint8_t* d1 = (uint8_t*)malloc((size_t)cap * 32);
-    const int n0 = vo_feature_detection(L, w, h, w, 1000, 200, k0, cap, d0), n1 = vo_feature_detection(R, w, h, w, 1000, 200, k1, cap, d1);
+    const int n0 = vo_feature_detection(L, w, h, w, 1000, 200, 20, k0, cap, d0), n1 = vo_feature_detection(R, w, h, w, 1000, 200, 20, k1, cap, d1);
     vo_dmatch* m = (vo_dmatch*)malloc(sizeof(vo_dmatch) * (size_t)(n0 > 0 ? n0 : 1));
-    const int nm = n0 > 0 && n1 > 0 ? vo_feature_matching(d0, n0, d1, n1, 1.0, m) : 0;
+    const int nm = n0 > 0 && n1 > 0 ? vo_feature_matching(d0, n0, d1, n1, 1.0, 2.0, 30.0, m) : 0;
     printf("orb %d %d keypoints, %d matches\n", n0, n1, nm);
     /* SGBM */
     float* disp = (float*)malloc(sizeof(float) * (size_t)w * h);

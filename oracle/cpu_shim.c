@@ -49,9 +49,6 @@ int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** ou
     (void)device; (void)stream;
     if (!p || !out) { set_error("null argument"); return VSLAM_ERR_ARG; }
     if (p->struct_size != (int32_t)sizeof(vslam_params) || p->abi_version != VSLAM_ABI_VERSION) { set_error("vslam_params from a different ABI"); return VSLAM_ERR_ARG; }
-    /* the oracle hard-codes the constants the reference hard-codes; refuse configurations it cannot honour */
-    if (p->fast_threshold != 20 || p->depth_min != 10 || p->depth_max != 400 || p->depth_reliable != 40 || p->match_ratio != 2.0 ||
-        p->match_gap_thr != 30.0) { set_error("CPU shim: only the reference's constants are supported"); return VSLAM_ERR_ARG; }
     vslam_ctx* c = (vslam_ctx*)calloc(1, sizeof(*c));
     c->p = *p;
     *out = c;
@@ -65,7 +62,7 @@ int vslam_feature_detection(vslam_ctx* c, const uint8_t* img, int w, int h, int 
     const int big = 16384; /* detection produces up to ~3000 (+ ties) keypoints before ANMS */
     vo_keypoint* k = (vo_keypoint*)malloc(sizeof(vo_keypoint) * (size_t)big);
     uint8_t* d = (uint8_t*)malloc((size_t)big * 32);
-    const int n = vo_feature_detection(img, w, h, stride, c->p.orb_nfeatures, c->p.anms_num, k, big, d);
+    const int n = vo_feature_detection(img, w, h, stride, c->p.orb_nfeatures, c->p.anms_num, c->p.fast_threshold, k, big, d);
     int rc = VSLAM_OK;
     if (n < 0 || n > cap) { set_error("capacity"); rc = VSLAM_ERR_CAPACITY; *n_out = 0; }
     else { memcpy(kps, k, sizeof(vo_keypoint) * (size_t)n); memcpy(desc, d, (size_t)n * 32); *n_out = n; }
@@ -83,7 +80,7 @@ int vslam_feature_matching(vslam_ctx* c, const uint8_t* q, int nq, const uint8_t
     if (!c || !n_out || nq < 0 || nt < 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     *n_out = 0;
     if (nq == 0 || nt == 0) return VSLAM_OK;
-    *n_out = gate ? vo_feature_matching(q, nq, t, nt, frame_gap, (vo_dmatch*)out) : vo_bf_match_hamming_xcheck(q, nq, t, nt, (vo_dmatch*)out);
+    *n_out = gate ? vo_feature_matching(q, nq, t, nt, frame_gap, c->p.match_ratio, c->p.match_gap_thr, (vo_dmatch*)out) : vo_bf_match_hamming_xcheck(q, nq, t, nt, (vo_dmatch*)out);
     return VSLAM_OK;
 }
 
@@ -96,7 +93,8 @@ int vslam_disparity_map(vslam_ctx* c, const uint8_t* left, const uint8_t* right,
 int vslam_find_3d_disparity(vslam_ctx* c, const vslam_keypoint* kps, int n, const float* disparity, int w, int h, int dstride, const double T_c_w[7],
                             float* xyz_w, uint8_t* valid, uint8_t* reliable, int* n_valid) {
     if (!c || n < 0 || !disparity || !T_c_w) { set_error("bad argument"); return VSLAM_ERR_ARG; }
-    const int k = n ? vo_find_3d_disparity((const vo_keypoint*)kps, n, disparity, w, h, dstride, T_c_w, c->p.cam, xyz_w, valid, reliable) : 0;
+    const double gate[3] = {c->p.depth_min, c->p.depth_max, c->p.depth_reliable};
+    const int k = n ? vo_find_3d_disparity((const vo_keypoint*)kps, n, disparity, w, h, dstride, T_c_w, c->p.cam, gate, xyz_w, valid, reliable) : 0;
     if (n_valid) *n_valid = k;
     return VSLAM_OK;
 }
@@ -104,7 +102,8 @@ int vslam_find_3d_disparity(vslam_ctx* c, const vslam_keypoint* kps, int n, cons
 int vslam_triangulate(vslam_ctx* c, const float* uvL, const float* uvR, int n, const double T_c_w[7], float* xyz_w, uint8_t* valid, uint8_t* reliable,
                       int* n_valid) {
     if (!c || n < 0 || !T_c_w) { set_error("bad argument"); return VSLAM_ERR_ARG; }
-    const int k = n ? vo_triangulate_dlt(uvL, uvR, n, T_c_w, c->p.cam, c->p.stereo_row_tol, xyz_w, valid, reliable) : 0;
+    const double gate[3] = {c->p.depth_min, c->p.depth_max, c->p.depth_reliable};
+    const int k = n ? vo_triangulate_dlt(uvL, uvR, n, T_c_w, c->p.cam, c->p.stereo_row_tol, gate, xyz_w, valid, reliable) : 0;
     if (n_valid) *n_valid = k;
     return VSLAM_OK;
 }
@@ -141,7 +140,7 @@ static int window(vslam_ctx* c, int pose_only, int n_kf, double* T, int n_lm, fl
                        : vo_local_ba(n_kf, T, n_lm, xyz, n_edge, kf_idx, lm_idx, uv, K, iters, c->p.huber_delta, update_poses, update_lms, chi2, (vo_lm_stats*)stats);
     if (rc) { free(chi2); set_error("oracle rejected the graph (%d)", rc); return VSLAM_ERR_ARG; }
     uint8_t* scratch = lm_inlier ? NULL : (uint8_t*)calloc((size_t)n_lm, 1);
-    const double th = vo_chi2_classify(chi2, n_edge, flag_lm ? flag_lm : lm_idx, lm_inlier ? lm_inlier : scratch, n_lm, NULL, NULL);
+    const double th = vo_chi2_classify(chi2, n_edge, flag_lm ? flag_lm : lm_idx, lm_inlier ? lm_inlier : scratch, n_lm, c->p.huber_delta, NULL, NULL);
     free(scratch);
     if (thr_out) *thr_out = th;
     if (chi2_out) memcpy(chi2_out, chi2, sizeof(double) * (size_t)n_edge);

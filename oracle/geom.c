@@ -138,21 +138,22 @@ double vo_se3_angle_y(const double T[7]) {
 
 /* ------------------------------------------------------------------ A7: depth -> world points ------- */
 
-static void gate_and_store(const double rel[3], const double T_c_w[7], int i, float* xyz_w, uint8_t* valid,
+static void gate_and_store(const double rel[3], const double T_c_w[7], const double gate[3], int i, float* xyz_w, uint8_t* valid,
                            uint8_t* reliable, int* nvalid) {
     double Tinv[7], pw[3];
     vo_se3_inv(T_c_w, Tinv);
     vo_se3_act(Tinv, rel, pw);
-    /* visual_odometry.cpp:194: keep 10 < Z < 400 ; :201 reliable = Z < 40 */
-    int ok = (rel[2] > 10 && rel[2] < 400);
+    /* visual_odometry.cpp:194: keep 10 < Z < 400 ; :201 reliable = Z < 40 (gate = {min, max, reliable}; NULL: those constants) */
+    const double zmin = gate ? gate[0] : 10, zmax = gate ? gate[1] : 400, zrel = gate ? gate[2] : 40;
+    int ok = (rel[2] > zmin && rel[2] < zmax);
     valid[i] = (uint8_t)ok;
-    reliable[i] = (uint8_t)(ok && rel[2] < 40);
+    reliable[i] = (uint8_t)(ok && rel[2] < zrel);
     xyz_w[3 * i] = (float)pw[0]; xyz_w[3 * i + 1] = (float)pw[1]; xyz_w[3 * i + 2] = (float)pw[2]; /* cv::Point3f */
     if (ok) ++*nvalid;
 }
 
 int vo_find_3d_disparity(const vo_keypoint* kps, int n, const float* disparity, int w, int h, int dstride,
-                         const double T_c_w[7], const double cam[5], float* xyz_w, uint8_t* valid,
+                         const double T_c_w[7], const double cam[5], const double depth_gate[3], float* xyz_w, uint8_t* valid,
                          uint8_t* reliable) {
     const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3], b = cam[4];
     int nvalid = 0;
@@ -167,13 +168,13 @@ int vo_find_3d_disparity(const vo_keypoint* kps, int n, const float* disparity, 
         }
         double depth = fx * b / (double)disparity[(size_t)r * dstride + c];
         double rel[3] = {x * depth, y * depth, depth};
-        gate_and_store(rel, T_c_w, i, xyz_w, valid, reliable, &nvalid);
+        gate_and_store(rel, T_c_w, depth_gate, i, xyz_w, valid, reliable, &nvalid);
     }
     return nvalid;
 }
 
 int vo_triangulate_dlt(const float* uvL, const float* uvR, int n, const double T_c_w[7], const double cam[5], double row_tol,
-                       float* xyz_w, uint8_t* valid, uint8_t* reliable) {
+                       const double depth_gate[3], float* xyz_w, uint8_t* valid, uint8_t* reliable) {
     const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3], b = cam[4];
     int nvalid = 0;
     for (int i = 0; i < n; ++i) {
@@ -201,7 +202,7 @@ int vo_triangulate_dlt(const float* uvL, const float* uvR, int n, const double T
          * no descriptor-matched stereo stage (its depth is SGBM, which searches along the row by construction); a cross-checked
          * L/R descriptor match has no such constraint built in, so the stage that replaces SGBM applies it explicitly. */
         if (row_tol >= 0 && (!(fabs((double)uvL[2 * i + 1] - (double)uvR[2 * i + 1]) <= row_tol) || !(uvL[2 * i] > uvR[2 * i]))) { rel[0] = rel[1] = 0; rel[2] = -1; }
-        gate_and_store(rel, T_c_w, i, xyz_w, valid, reliable, &nvalid);
+        gate_and_store(rel, T_c_w, depth_gate, i, xyz_w, valid, reliable, &nvalid);
     }
     return nvalid;
 }

@@ -348,9 +348,9 @@ int vo_pose_only_window(int n_kf, double* T_c_w, int n_lm, const float* xyz, int
     return 0;
 }
 
-double vo_chi2_classify(const double* chi2, int n_edge, const int32_t* flag_lm, uint8_t* lm_inlier, int n_lm,
+double vo_chi2_classify(const double* chi2, int n_edge, const int32_t* flag_lm, uint8_t* lm_inlier, int n_lm, double chi2_th0,
                         int* n_inlier_edges, int* n_outlier_edges) {
-    double chi2_th = 5.991; /* optimization.cpp:154 */
+    double chi2_th = chi2_th0; /* optimization.cpp:154: 5.991, the variable that :205 also hands to the Huber kernel */
     int cnt_outlier = 0, cnt_inlier = 0, iteration = 0;
     while (iteration < 5) { /* :226-252 */
         cnt_outlier = 0; cnt_inlier = 0;

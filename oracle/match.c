@@ -48,7 +48,7 @@ int vo_bf_match_hamming_xcheck(const uint8_t* q, int nq, const uint8_t* t, int n
     return n;
 }
 
-int vo_feature_matching(const uint8_t* q, int nq, const uint8_t* t, int nt, double frame_gap, vo_dmatch* out) {
+int vo_feature_matching(const uint8_t* q, int nq, const uint8_t* t, int nt, double frame_gap, double ratio, double gap_thr, vo_dmatch* out) {
     int cap = nq > 0 ? nq : 1;
     vo_dmatch* m = (vo_dmatch*)malloc(sizeof(vo_dmatch) * (size_t)cap);
     int n = vo_bf_match_hamming_xcheck(q, nq, t, nt, m); /* visual_odometry.cpp:225 */
@@ -58,7 +58,7 @@ int vo_feature_matching(const uint8_t* q, int nq, const uint8_t* t, int nt, doub
     if (n > 0) {
         float dmin = m[0].distance;
         for (int i = 1; i < n; ++i) if (m[i].distance < dmin) dmin = m[i].distance;
-        double a = 2.0 * (double)dmin, b = 30.0 * frame_gap; /* :242 */
+        double a = ratio * (double)dmin, b = gap_thr * frame_gap; /* :242: 2.0, 30.0 */
         double thr = a > b ? a : b;
         for (int i = 0; i < n; ++i)
             if ((double)m[i].distance <= thr) out[k++] = m[i];

@@ -373,8 +373,8 @@ static uint8_t* alloc_levels(const vo_orb_layout* L, int nlevels, uint8_t** lv) 
     return buf;
 }
 
-int vo_orb_detect(const uint8_t* img, int w, int h, int stride, int nfeatures, vo_keypoint* out, int cap) {
-    const int edge = 31, fast_thr = 20;
+int vo_orb_detect(const uint8_t* img, int w, int h, int stride, int nfeatures, int fast_threshold, vo_keypoint* out, int cap) {
+    const int edge = 31, fast_thr = fast_threshold; /* cv::ORB::create's default, which the reference keeps: 20 */
     vo_orb_layout L;
     vo_orb_layout_init(w, h, nfeatures, &L);
     uint8_t* lv[VO_ORB_NLEVELS];
@@ -543,9 +543,9 @@ int vo_orb_compute(const uint8_t* img, int w, int h, int stride, vo_keypoint* kp
     return n;
 }
 
-int vo_feature_detection(const uint8_t* img, int w, int h, int stride, int nfeatures, int anms_num,
+int vo_feature_detection(const uint8_t* img, int w, int h, int stride, int nfeatures, int anms_num, int fast_threshold,
                          vo_keypoint* kps, int cap, uint8_t* desc) {
-    int n = vo_orb_detect(img, w, h, stride, nfeatures, kps, cap); /* visual_odometry.cpp:80 */
+    int n = vo_orb_detect(img, w, h, stride, nfeatures, fast_threshold, kps, cap); /* visual_odometry.cpp:80 */
     if (n < 0) return n;
     n = vo_anms(kps, n, anms_num);                                 /* :82 */
     return vo_orb_compute(img, w, h, stride, kps, n, desc);        /* :85 */

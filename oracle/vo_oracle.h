@@ -96,8 +96,9 @@ float vo_ic_angle(const uint8_t* img, int stride, int x, int y);
 int vo_retain_best(vo_keypoint* kps, int n, int npoints);
 
 /* cv::ORB::create(nfeatures)->detect(img, kps).  Output order: level ascending, raster within a level.
- * reference call site: visual_odometry.cpp:80 (ctor :22).  returns count or <0 on overflow of cap. */
-int vo_orb_detect(const uint8_t* img, int w, int h, int stride, int nfeatures, vo_keypoint* out, int cap);
+ * reference call site: visual_odometry.cpp:80 (ctor :22).  fast_threshold: the FAST threshold of cv::ORB::create (its default, and
+ * the reference's value, is 20).  returns count or <0 on overflow of cap. */
+int vo_orb_detect(const uint8_t* img, int w, int h, int stride, int nfeatures, int fast_threshold, vo_keypoint* out, int cap);
 
 /* VO::adaptive_non_maximal_suppresion (visual_odometry.cpp:96-157).  Stable sort on response ties.
  * In place; returns the new count. */
@@ -110,7 +111,7 @@ int vo_orb_compute(const uint8_t* img, int w, int h, int stride, vo_keypoint* kp
 
 /* VO::feature_detection (visual_odometry.cpp:70-94) without the GUI calls: detect(3000) -> ANMS(anms_num)
  * -> compute. returns count. */
-int vo_feature_detection(const uint8_t* img, int w, int h, int stride, int nfeatures, int anms_num,
+int vo_feature_detection(const uint8_t* img, int w, int h, int stride, int nfeatures, int anms_num, int fast_threshold,
                          vo_keypoint* kps, int cap, uint8_t* desc);
 
 /* ------------------------------------------------------------------ matcher (A5) --------------------- */
@@ -120,8 +121,9 @@ int vo_feature_detection(const uint8_t* img, int w, int h, int stride, int nfeat
  * returns the number of matches (ascending queryIdx). */
 int vo_bf_match_hamming_xcheck(const uint8_t* q, int nq, const uint8_t* t, int nt, vo_dmatch* out);
 
-/* VO::feature_matching (visual_odometry.cpp:219-251): cross-check match + gate d <= max(2*dmin, 30*gap). */
-int vo_feature_matching(const uint8_t* q, int nq, const uint8_t* t, int nt, double frame_gap, vo_dmatch* out);
+/* VO::feature_matching (visual_odometry.cpp:219-251): cross-check match + gate d <= max(ratio*dmin, gap_thr*gap); the reference's
+ * constants (:242) are ratio = 2.0, gap_thr = 30.0. */
+int vo_feature_matching(const uint8_t* q, int nq, const uint8_t* t, int nt, double frame_gap, double ratio, double gap_thr, vo_dmatch* out);
 
 /* ------------------------------------------------------------------ stereo depth (A6) ---------------- */
 
@@ -146,16 +148,17 @@ double vo_se3_angle_y(const double T[7]);                     /* [UPSTREAM Sophu
 
 /* Frame::find_3d + VO::set_ref_3d_position (types_def.cpp:9-18, visual_odometry.cpp:176-217).
  * disparity: f32 h x w map (row stride in elements).  Writes per-keypoint world xyz (f32), valid, reliable.
- * No compaction (caller compacts in order).  returns number valid. */
+ * No compaction (caller compacts in order).  depth_gate = {min, max, reliable} of :194 / :201 in metres of camera-frame depth
+ * (valid: min < Z < max, reliable: valid and Z < reliable); NULL = the reference's 10, 400, 40.  returns number valid. */
 int vo_find_3d_disparity(const vo_keypoint* kps, int n, const float* disparity, int w, int h, int dstride,
-                         const double T_c_w[7], const double cam[5] /*fx,fy,cx,cy,b*/,
+                         const double T_c_w[7], const double cam[5] /*fx,fy,cx,cy,b*/, const double depth_gate[3],
                          float* xyz_w, uint8_t* valid, uint8_t* reliable);
 
 /* north_star stage K8: rectified-stereo inhomogeneous DLT (4 equations, 3 unknowns, normal equations)
  * on matched (uL,vL),(uR,vR), then the same gates/outputs as set_ref_3d_position.  row_tol: epipolar gate
  * |vL - vR| <= row_tol and uL > uR (rectified pair); < 0 disables it. */
 int vo_triangulate_dlt(const float* uvL, const float* uvR, int n, const double T_c_w[7], const double cam[5], double row_tol,
-                       float* xyz_w, uint8_t* valid, uint8_t* reliable);
+                       const double depth_gate[3], float* xyz_w, uint8_t* valid, uint8_t* reliable);
 
 /* VO::check_motion_estimation (visual_odometry.cpp:316-346) */
 int vo_check_motion(int num_inliers, const double T_c_l[7], double frame_gap);
@@ -186,8 +189,10 @@ int vo_pose_only_window(int n_kf, double* T_c_w, int n_lm, const float* xyz, int
 
 /* Adaptive chi2 threshold + inlier flags (optimization.cpp:224-266 / :382-424).  Edges are visited in
  * ascending edge index (defined order; the reference iterates a std::map keyed by pointer).  flag_lm[e] is
- * the landmark whose is_inlier flag edge e writes (reference: feat.landmark_id_).  returns final threshold. */
-double vo_chi2_classify(const double* chi2, int n_edge, const int32_t* flag_lm, uint8_t* lm_inlier, int n_lm,
+ * the landmark whose is_inlier flag edge e writes (reference: feat.landmark_id_).  chi2_th0: the initial threshold -- the reference's
+ * `chi2_th = 5.991` (:154 / :328), ONE variable that is also the Huber delta (:205 / :364), so a caller that changes the Huber width
+ * (vslam_params.huber_delta) passes the same number here.  returns final threshold. */
+double vo_chi2_classify(const double* chi2, int n_edge, const int32_t* flag_lm, uint8_t* lm_inlier, int n_lm, double chi2_th0,
                         int* n_inlier_edges, int* n_outlier_edges);
 
 /* north_star stage K9 (substitute for cv::solvePnPRansac at visual_odometry.cpp:277): motion-only LM on one

@@ -24,6 +24,17 @@ def fast_numpy(img, t):
     return corner, np.maximum(best, t) - 1
 
 
+def fast_nms_numpy(img, t):
+    """FAST-9/16 at threshold t with the 3 x 3 non-maximum suppression of cv::FAST: a corner survives when its score is strictly larger
+    than the scores of its eight neighbours (0 where not a corner).  Returns (keep, score), both image-sized."""
+    corner, score = fast_numpy(img, t)
+    full = np.zeros(img.shape, np.int64); full[3:-3, 3:-3] = np.where(corner, score, 0)
+    isc = np.zeros(img.shape, bool); isc[3:-3, 3:-3] = corner
+    pad = np.pad(full, 1)
+    nb = np.max([pad[1 + dy:pad.shape[0] - 1 + dy, 1 + dx:pad.shape[1] - 1 + dx] for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dy, dx) != (0, 0)], axis=0)
+    return isc & (full > nb), full
+
+
 def anms_numpy(kps, num):
     """line-by-line numpy/python restatement of visual_odometry.cpp:96-157"""
     if len(kps) < num:

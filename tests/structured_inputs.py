@@ -179,7 +179,7 @@ ST_CORNER, ST_CAND, ST_SEL, ST_ANMS, ST_OUT = 1, 2, 4, 8, 16
 CAND_CAP, SEL_CAP, ANMS_CAP = 4096, 1024, 3328
 
 
-def device_capacity_bits(O, img, nfeatures, anms_num, kp_capacity=4096, describe=True):
+def device_capacity_bits(O, img, nfeatures, anms_num, kp_capacity=4096, describe=True, fast_threshold=20):
     """the ORB status bits the device must raise for this image, from the oracle's counts stage by stage: (bits, counts).  A stage behind an
     overflowing one sees a truncated list whose content is not defined; its bit is predicted from the truncated COUNT where that is defined
     (the selection truncates a level to 1024) and left out of `bits` but named in counts["unknown"] where it is not."""
@@ -189,14 +189,14 @@ def device_capacity_bits(O, img, nfeatures, anms_num, kp_capacity=4096, describe
     bits = 0; unknown = 0
     corners, cands = [], []
     for l in range(8):
-        c = O.fast9_16(lv[l], 20, True)
+        c = O.fast9_16(lv[l], fast_threshold, True)
         c = c[(c["x"] >= 31) & (c["x"] < L["w"][l] - 31) & (c["y"] >= 31) & (c["y"] < L["h"][l] - 31)]
         corners.append(len(c)); cands.append(len(O.retain_best(c, 2 * L["nfeat"][l])))
         if len(c) > ((L["w"][l] * L["h"][l] // 16 + 255) & ~255):
             bits |= ST_CORNER; unknown |= ST_CAND | ST_SEL | ST_ANMS | ST_OUT
         if cands[-1] > CAND_CAP:
             bits |= ST_CAND; unknown |= ST_SEL | ST_ANMS | ST_OUT
-    kps = O.orb_detect(img, nfeatures, cap=1 << 16)
+    kps = O.orb_detect(img, nfeatures, cap=1 << 16, fast_threshold=fast_threshold)
     sel = np.bincount(kps["octave"], minlength=8)
     if not unknown & ST_SEL and (sel > SEL_CAP).any():
         bits |= ST_SEL; unknown |= ST_OUT

@@ -169,9 +169,17 @@ def test_chain_is_the_builders(pkg):
 def test_pass_loop_vs_restatement(pkg, seed):
     """passes 1 .. K on random tables with the stand-in solver run on the host between them: every pass's inputs against the restatement's, the
     final windows against its windows; K = F - 1 also against the sequential loop; every input's position is its landmark's in window i, bit for bit"""
+    _pass_loop_vs_restatement(pkg, seed, (4.0, 300.0, 4.0)[seed])
+
+
+def _pass_loop_vs_restatement(pkg, seed, thr, cam=None):
+    """cam (fx, fy, cx, cy, b): the context's camera, its K handed to the restatement (None: the KITTI camera of both).  Returns the number of
+    entries of the first two passes' input lists (counts and index maps) in which the restatement under that camera differs from the restatement
+    under the KITTI camera."""
     rng = np.random.default_rng(4300 + seed)
-    ctx = pkg.VO(device=0, max_batch=1, pnp_reproj_thr=(4.0, 300.0, 4.0)[seed])
-    n_inputs = 0
+    ctx = pkg.VO(device=0, max_batch=1, pnp_reproj_thr=thr, **({} if cam is None else dict(cam=cam)))
+    kw = {} if cam is None else dict(K=np.asarray(cam, np.float64)[:4])
+    n_inputs = n_camera_inputs = 0
     try:
         for case in range(2):
             F = int(rng.integers(10, 14)); cap = int(rng.choice([64, 128])); n_kf = int(rng.integers(2, 11)); policy = case % 2
@@ -181,7 +189,11 @@ def test_pass_loop_vs_restatement(pkg, seed):
             seq = R.sequential(t, R.standin_solver, n_kf=n_kf, policy=policy)
             for K in (1, 2, F - 1):
                 tag = (seed, case, F, cap, K)
-                ref = R.passes(t, R.standin_solver, K, G0=G0, n_kf=n_kf, policy=policy, reproj_thr=ctx.params.pnp_reproj_thr)
+                ref = R.passes(t, R.standin_solver, K, G0=G0, n_kf=n_kf, policy=policy, reproj_thr=ctx.params.pnp_reproj_thr, **kw)
+                if cam is not None and K == 2:
+                    kitti = R.passes(t, R.standin_solver, K, G0=G0, n_kf=n_kf, policy=policy, reproj_thr=ctx.params.pnp_reproj_thr)
+                    n_camera_inputs += sum(abs(a["n"] - b["n"]) + int((a["index"] != b["index"]).sum())
+                                           for k in range(K) for a, b in zip(ref["per_pass"][k]["items"], kitti["per_pass"][k]["items"]))
                 G, index, inl = G0, None, None
                 for k in range(K):
                     d_in = dv.inputs(ctx, G, index, inl)
@@ -214,6 +226,7 @@ def test_pass_loop_vs_restatement(pkg, seed):
         assert n_inputs > 200, n_inputs
     finally:
         ctx.close()
+    return n_camera_inputs
 
 
 def test_inputs_capacity_cut(pkg):

@@ -157,23 +157,36 @@ def _random_tracks(rng, F, cap, n_kp_max):
 def test_build_windows_random_tracks_vs_oracle(pkg, oracle, seed):
     """the builder alone, on random association / match / flag tables (chains of every length, unreliable -> reliable updates mid-chain,
     dropped links, empty frames, n_kf from 1 to 12, capacity overflow), through vslam_build_windows_dev against oracle/windows.c"""
+    _random_tracks_vs_oracle(pkg, oracle, seed)
+
+
+def _random_tracks_vs_oracle(pkg, oracle, seed, thrs=(4.0, 300.0, 1200.0), cam=None):
+    """cam (fx, fy, cx, cy, b): the contexts' camera, its K handed to the oracle (None: the KITTI camera of both).  Returns the number of edges by
+    which the oracle's windows under that camera differ from its windows under the KITTI camera, summed over the cases."""
     import torch
     rng = np.random.default_rng(1000 + seed)
+    K = None if cam is None else np.asarray(cam, np.float64)[:4]
+    kw = {} if cam is None else dict(cam=cam)
+    n_camera_edges = 0
     # [r6] the track rule: seeds 0-3 the reference's (a match continues a track whenever its last-frame keypoint is a feature; one without a depth is judged by
     # reprojecting the landmark's map position), seeds 4-5 the convention of rounds 4-5.  Random geometry rarely reprojects within the product's 4 px, so
     # the cases also run with thresholds of hundreds of pixels: then many depth-less links hold, chains of them, with position updates in between.
     rule = 1 if seed < 4 else 0
-    ctxs = {thr: pkg.VO(device=0, max_batch=1, pnp_reproj_thr=thr) for thr in (4.0, 300.0, 1200.0)}
+    ctxs = {thr: pkg.VO(device=0, max_batch=1, pnp_reproj_thr=thr, **kw) for thr in thrs}
     for c_ in ctxs.values():
         c_.set_tuning(track_rule=rule)
     n_depthless_links = 0
     try:
         for case in range(12):
-            thr = (4.0, 300.0, 1200.0)[case % 3]; ctx = ctxs[thr]
+            thr = thrs[case % len(thrs)]; ctx = ctxs[thr]
             F = int(rng.integers(1, 40)); cap = int(rng.choice([64, 100, 256])); n_kf = int(rng.integers(1, 13))
             kps, lr, nlr, xyz, valid, rel, f2f, nf2f, inl, T_rel, nk = _random_tracks(rng, F, cap, int(rng.integers(1, cap + 1)))
             full = oracle.build_windows(kps, lr, nlr, xyz, valid, rel, f2f, nf2f, inl, T_rel, n_kf=n_kf, lm_capacity=F * cap * (n_kf + 1),
-                                        edge_capacity=2 * F * cap * (n_kf + 1), reproj_thr=thr, track_rule=rule)   # (a landmark is in up to n_kf windows)
+                                        edge_capacity=2 * F * cap * (n_kf + 1), reproj_thr=thr, track_rule=rule, K=K)   # (a landmark is in up to n_kf windows)
+            if K is not None:
+                kitti = oracle.build_windows(kps, lr, nlr, xyz, valid, rel, f2f, nf2f, inl, T_rel, n_kf=n_kf, lm_capacity=F * cap * (n_kf + 1),
+                                             edge_capacity=2 * F * cap * (n_kf + 1), reproj_thr=thr, track_rule=rule)
+                n_camera_edges += abs(int(full["edge_off"][F]) - int(kitti["edge_off"][F]))
             if rule:
                 old = oracle.build_windows(kps, lr, nlr, xyz, valid, rel, f2f, nf2f, inl, T_rel, n_kf=n_kf, lm_capacity=F * cap * (n_kf + 1),
                                            edge_capacity=2 * F * cap * (n_kf + 1), track_rule=0)
@@ -184,7 +197,7 @@ def test_build_windows_random_tracks_vs_oracle(pkg, oracle, seed):
             lm_cap = max(int(nl_tot * rng.uniform(0.3, 0.9)), 1) if shrink else nl_tot + 7
             e_cap = ne_tot + 5
             w = oracle.build_windows(kps, lr, nlr, xyz, valid, rel, f2f, nf2f, inl, T_rel, n_kf=n_kf, lm_capacity=lm_cap, edge_capacity=e_cap, reproj_thr=thr,
-                                     track_rule=rule)
+                                     track_rule=rule, K=K)
             d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
             t_kps, t_lr, t_nlr, t_xyz, t_valid, t_rel, t_nk = d(kps.view(np.uint8)), d(lr.view(np.uint8)), d(nlr), d(xyz), d(valid), d(rel), d(nk)
             t_f2f = d(f2f.view(np.uint8)) if F > 1 else torch.zeros(16, dtype=torch.uint8, device="cuda")
@@ -224,3 +237,4 @@ def test_build_windows_random_tracks_vs_oracle(pkg, oracle, seed):
     finally:
         for c_ in ctxs.values():
             c_.close()
+    return n_camera_edges

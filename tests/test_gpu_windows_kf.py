@@ -181,15 +181,24 @@ def _random_T_rel(rng, F, O):
 def test_random_tracks_vs_oracle(pkg, oracle, seed):
     """random association / match / flag tables and random poses with both eviction branches, both track rules, thresholds 4 / 300 / 1200 px,
     n_kf 1..12, capacity overflow: the sets against the numpy rule, the windows against the oracle's full-history windows restricted to them"""
+    _random_tracks_kf_vs_oracle(pkg, oracle, seed)
+
+
+def _random_tracks_kf_vs_oracle(pkg, oracle, seed, thrs=(4.0, 300.0, 1200.0), cam=None):
+    """cam (fx, fy, cx, cy, b): the contexts' camera, its K handed to the oracle (None: the KITTI camera of both).  Returns the number of edges by
+    which the oracle's full-history windows under that camera differ from those under the KITTI camera, summed over the cases."""
     rng = np.random.default_rng(5000 + seed)
     rule = 1 if seed < 3 else 0
-    ctxs = {thr: pkg.VO(device=0, max_batch=1, pnp_reproj_thr=thr) for thr in (4.0, 300.0, 1200.0)}
+    K = None if cam is None else np.asarray(cam, np.float64)[:4]
+    kw = {} if cam is None else dict(cam=cam)
+    n_camera_edges = 0
+    ctxs = {thr: pkg.VO(device=0, max_batch=1, pnp_reproj_thr=thr, **kw) for thr in thrs}
     for c_ in ctxs.values():
         c_.set_tuning(track_rule=rule)
     n_near = n_far_not_oldest = 0
     try:
         for case in range(10):
-            thr = (4.0, 300.0, 1200.0)[case % 3]; ctx = ctxs[thr]
+            thr = thrs[case % len(thrs)]; ctx = ctxs[thr]
             F = int(rng.integers(1, 40)); cap = int(rng.choice([64, 100, 256])); n_kf = int(rng.integers(1, 13))
             tables = list(_random_tracks(rng, F, cap, int(rng.integers(1, cap + 1))))
             tables[9] = _random_T_rel(rng, F, oracle)
@@ -201,7 +210,11 @@ def test_random_tracks_vs_oracle(pkg, oracle, seed):
                                   < 0.2)
                     n_far_not_oldest += int(ev[b] != kf[b - 1][0])
             full = oracle.build_windows(*tables[:10], n_kf=max(F, 1), lm_capacity=F * cap * (F + 1), edge_capacity=2 * F * cap * (F + 1),
-                                        reproj_thr=thr, track_rule=rule)
+                                        reproj_thr=thr, track_rule=rule, K=K)
+            if K is not None:
+                kitti = oracle.build_windows(*tables[:10], n_kf=max(F, 1), lm_capacity=F * cap * (F + 1), edge_capacity=2 * F * cap * (F + 1),
+                                             reproj_thr=thr, track_rule=rule)
+                n_camera_edges += abs(int(full["edge_off"][F]) - int(kitti["edge_off"][F]))
             wins = _expected_windows(full, kf)
             nl_tot = sum(len(w) for w in wins); ne_tot = sum(sum(len(k) for k in w) for w in wins)
             shrink = rng.random() < 0.3 and nl_tot > 4
@@ -216,6 +229,7 @@ def test_random_tracks_vs_oracle(pkg, oracle, seed):
     finally:
         for c_ in ctxs.values():
             c_.close()
+    return n_camera_edges
 
 
 def test_sliding_equivalence(pkg, oracle):
