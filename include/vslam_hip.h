@@ -159,8 +159,10 @@ int vslam_feature_matching_subset_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t
  * 100, 32)->compute(left, right) followed by convertTo(CV_32F, 1/16).  left/right: h x w u8 (row stride in bytes);
  * disparity: h x w f32, tightly packed (invalid pixels = -1.0, like the reference).  Optional outputs (may be NULL):
  * disp_i16 = the CV_16S fixed-point map after median + speckle filtering, disp_raw_i16 = before them.
- * Sizes: 100 < w <= 4096, h > 9 (VSLAM_ERR_ARG otherwise; OpenCV 3.2's own output is undefined for w - 96 <= 4, where its
- * horizontal box sum reads past the pixel-cost row). */
+ * These two entries are vslam_disparity_map_ex[_dev] with the reference's set (vslam_default_sgbm_params): 96 disparities, a 9 x 9 window,
+ * hence 100 < w <= 4096 and h > 9 (VSLAM_ERR_ARG otherwise; OpenCV 3.2's own output is undefined for w - 96 <= 4, where its
+ * horizontal box sum reads past the pixel-cost row).  A rig with another baseline, lens or image size sets its own range, window
+ * and matching constants through vslam_sgbm_params. */
 int vslam_disparity_map(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int stride,
                         float* disparity, int16_t* disp_i16, int16_t* disp_raw_i16);
 
@@ -168,6 +170,42 @@ int vslam_disparity_map(vslam_ctx* ctx, const uint8_t* left, const uint8_t* righ
  * B x h x w, tightly packed.  The SGBM working set (about 250 MB per 1241x376 pair) is grown on demand and kept. */
 int vslam_disparity_map_dev(vslam_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride_bytes,
                             int pitch, int w, int h, int B, float* d_disparity, int16_t* d_disp_i16, int16_t* d_disp_raw_i16);
+
+/* The arguments of cv::StereoSGBM::create that a caller may set (additive: vslam_params and the ABI version are unchanged).  minDisparity is
+ * 0 and the mode is MODE_SGBM (single pass, five directions): that is all the CPU oracle restates, so it is all this library computes.
+ * Every accepted set gives OpenCV 3.2's map bit for bit; everything outside the accepted domain is VSLAM_ERR_ARG, never a different map. */
+typedef struct vslam_sgbm_params {
+    int32_t num_disparities;       /* 96    a multiple of 16 in [16, 256] (the winner key holds the disparity in 8 bits)            */
+    int32_t block_size;            /* 9     odd, >= 1                                                                               */
+    int32_t P1, P2;                /* 648, 2592 (8 / 32 * block^2)   0 < P1 < P2                                                     */
+    int32_t disp12_max_diff;       /* 1     >= 0                                                                                    */
+    int32_t pre_filter_cap;        /* 63    in [1, 63]; the Sobel channel is clipped to ftzero = max(cap, 15) | 1                    */
+    int32_t uniqueness_ratio;      /* 10    in [0, 100]                                                                             */
+    int32_t speckle_window_size;   /* 100   >= 0; 0 = no speckle filter                                                             */
+    int32_t speckle_range;         /* 32    >= 0                                                                                    */
+    int32_t struct_size;           /* sizeof(vslam_sgbm_params) of the caller's header; set by vslam_default_sgbm_params, checked  */
+} vslam_sgbm_params;
+
+/* the reference's set: (96, 9, 648, 2592, 1, 63, 10, 100, 32) and struct_size */
+void vslam_default_sgbm_params(vslam_sgbm_params* p);
+
+/* Is the set admissible for w x h images?  Host arithmetic only: no context, no GPU.  VSLAM_OK, or VSLAM_ERR_ARG with vslam_last_error()
+ * naming the offending field.  Beyond the field ranges above:
+ *   w - num_disparities > block_size / 2 (below that OpenCV 3.2 reads past its pixel-cost row), h > block_size, w <= 4096, and the
+ *   16-bit range rule  3 * (block_size^2 * (2 * ftzero + 63) + P2) <= 65535:  a block cost is at most Cmax = block_size^2 * (2 * ftzero + 63)
+ *   (Birchfield-Tomasi: 2 * ftzero on the clipped Sobel channel + 255 >> 2 on the raw one), a path value lies in [-P2, Cmax], and the running
+ *   sum of three paths is kept as u16 with the offset 3 * P2.  The same bound keeps every 16-bit cost of OpenCV's own arithmetic from
+ *   wrapping.  It holds P2 = 32 * block^2 up to block 9 at cap 63, and block 11 at cap 31; what lies beyond is refused. */
+int vslam_sgbm_params_check(const vslam_sgbm_params* p, int w, int h);
+
+/* vslam_disparity_map[_dev] with a caller's set (NULL = the reference's).  Same buffers and contracts; vslam_sgbm_params_check runs first, so
+ * nothing is launched for a refused set.  The reference's set runs exactly the kernels of vslam_disparity_map[_dev]; any other set runs the
+ * line-parallel kernels (one per path) at every batch size, on a cost volume of 16 * ceil-to-{2,4,6,8,12,16}(num_disparities / 16) int16 per pixel. */
+int vslam_disparity_map_ex(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int stride,
+                           const vslam_sgbm_params* sgbm, float* disparity, int16_t* disp_i16, int16_t* disp_raw_i16);
+int vslam_disparity_map_ex_dev(vslam_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride_bytes,
+                               int pitch, int w, int h, int B, const vslam_sgbm_params* sgbm, float* d_disparity, int16_t* d_disp_i16,
+                               int16_t* d_disp_raw_i16);
 
 /* ------------------------------------------------------------------ A7: depth -> landmarks ------------ */
 /* Replaces Frame::find_3d (types_def.cpp:9-18) + the gating of VO::set_ref_3d_position

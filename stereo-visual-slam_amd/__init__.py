@@ -34,6 +34,16 @@ class Params(C.Structure):
                 ("struct_size", C.c_int32), ("abi_version", C.c_int32)]
 
 
+class SgbmParams(C.Structure):
+    """vslam_sgbm_params: the cv::StereoSGBM::create arguments a caller may set (minDisparity 0, MODE_SGBM)"""
+    _fields_ = [("num_disparities", C.c_int32), ("block_size", C.c_int32), ("P1", C.c_int32), ("P2", C.c_int32),
+                ("disp12_max_diff", C.c_int32), ("pre_filter_cap", C.c_int32), ("uniqueness_ratio", C.c_int32),
+                ("speckle_window_size", C.c_int32), ("speckle_range", C.c_int32), ("struct_size", C.c_int32)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_[:9])
+
+
 ABI_VERSION = 5  # VSLAM_ABI_VERSION of include/vslam_hip.h this binding was written against
 
 
@@ -109,6 +119,10 @@ SIGNATURES = {
     "vslam_feature_matching_subset_dev": (I, [P, P, Z, P, P, P, I, P, Z, P, P, I, I, I, P, I, P]),
     "vslam_disparity_map": (I, [P, P, P, I, I, I, P, P, P]),
     "vslam_disparity_map_dev": (I, [P, P, P, Z, I, I, I, I, P, P, P]),
+    "vslam_default_sgbm_params": (None, [P]),
+    "vslam_sgbm_params_check": (I, [P, I, I]),
+    "vslam_disparity_map_ex": (I, [P, P, P, I, I, I, P, P, P, P]),
+    "vslam_disparity_map_ex_dev": (I, [P, P, P, Z, I, I, I, I, P, P, P, P]),
     "vslam_find_3d_disparity": (I, [P, P, I, P, I, I, I, P, P, P, P, P]),
     "vslam_triangulate": (I, [P, P, P, I, P, P, P, P, P]),
     "vslam_find_3d_disparity_dev": (I, [P, P, P, I, I, P, I, I, P, P, P, P]),
@@ -195,6 +209,42 @@ def default_params(**kw):
         else:
             setattr(p, k, v)
     return p
+
+
+def default_sgbm_params(**kw):
+    """the reference's StereoSGBM set (96, 9, 648, 2592, 1, 63, 10, 100, 32), fields overridden by keyword"""
+    p = SgbmParams()
+    load_library().vslam_default_sgbm_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _sgbm_params(sgbm):
+    """None (the reference's set), an SgbmParams, a dict of fields, or a tuple (num_disparities, block_size[, P1, P2, ...]) in field
+    order; a tuple without P1 / P2 gets OpenCV's recommended 8 / 32 * block_size^2"""
+    if sgbm is None or isinstance(sgbm, SgbmParams):
+        return sgbm
+    if isinstance(sgbm, dict):
+        return default_sgbm_params(**sgbm)
+    vals = [int(v) for v in sgbm]
+    names = [f for f, _ in SgbmParams._fields_[:9]]
+    assert 2 <= len(vals) <= 9 and len(vals) != 3, "SGBM set: (num_disparities, block_size[, P1, P2, ...])"
+    if len(vals) == 2:
+        vals += [8 * vals[1] ** 2, 32 * vals[1] ** 2]
+    return default_sgbm_params(**dict(zip(names, vals)))
+
+
+def sgbm_params_check(p, w, h):
+    """vslam_sgbm_params_check: is the set admissible for w x h images?  Host arithmetic, needs no GPU.  Raises VslamError naming the field."""
+    lib = load_library()
+    p = _sgbm_params(p)
+    if p is None:
+        p = default_sgbm_params()
+    rc = lib.vslam_sgbm_params_check(C.byref(p), w, h)
+    if rc != VSLAM_OK:
+        raise VslamError("vslam_sgbm_params_check failed (%d): %s" % (rc, lib.vslam_last_error().decode()))
+    return True
 
 
 def _desc(d):
@@ -310,20 +360,28 @@ class VO:
                                                       d_nout), "vslam_feature_matching_dev")
 
     # ------------------------------------------------------------ VO::disparity_map (StereoSGBM + convertTo 1/16)
-    def disparity_map(self, left, right, return_i16=False):
+    def disparity_map(self, left, right, return_i16=False, sgbm=None):
         """visual_odometry.cpp:159-174.  Returns the f32 disparity map (invalid = -1); with return_i16 also the CV_16S
-        map after median/speckle filtering and the raw SGBM output before them."""
+        map after median/speckle filtering and the raw SGBM output before them.  sgbm: the StereoSGBM set (an SgbmParams, a dict of
+        its fields or a tuple in field order); None = the reference's."""
         left = np.ascontiguousarray(left, np.uint8); right = np.ascontiguousarray(right, np.uint8)
         assert left.ndim == 2 and left.shape == right.shape
         h, w = left.shape
         out = np.zeros((h, w), np.float32)
         i16 = np.zeros((h, w), np.int16) if return_i16 else None
         raw = np.zeros((h, w), np.int16) if return_i16 else None
-        self._chk(self.lib.vslam_disparity_map(self.h, left, right, w, h, w, out, i16, raw), "vslam_disparity_map")
+        if sgbm is None:
+            self._chk(self.lib.vslam_disparity_map(self.h, left, right, w, h, w, out, i16, raw), "vslam_disparity_map")
+        else:
+            self._chk(self.lib.vslam_disparity_map_ex(self.h, left, right, w, h, w, C.byref(_sgbm_params(sgbm)), out, i16, raw), "vslam_disparity_map_ex")
         return (out, i16, raw) if return_i16 else out
 
-    def disparity_map_dev(self, d_left, d_right, img_stride_bytes, pitch, w, h, B, d_disp, d_i16=None, d_raw=None):
-        self._chk(self.lib.vslam_disparity_map_dev(self.h, d_left, d_right, img_stride_bytes, pitch, w, h, B, d_disp, d_i16, d_raw), "vslam_disparity_map_dev")
+    def disparity_map_dev(self, d_left, d_right, img_stride_bytes, pitch, w, h, B, d_disp, d_i16=None, d_raw=None, sgbm=None):
+        if sgbm is None:
+            self._chk(self.lib.vslam_disparity_map_dev(self.h, d_left, d_right, img_stride_bytes, pitch, w, h, B, d_disp, d_i16, d_raw), "vslam_disparity_map_dev")
+        else:
+            self._chk(self.lib.vslam_disparity_map_ex_dev(self.h, d_left, d_right, img_stride_bytes, pitch, w, h, B, C.byref(_sgbm_params(sgbm)), d_disp, d_i16, d_raw),
+                      "vslam_disparity_map_ex_dev")
 
     def set_tuning(self, **kw):
         """kernel-choice overrides of this context, e.g. set_tuning(sgbm_fwd_min=1, sgbm_fw_rows=32); -1 = library default"""

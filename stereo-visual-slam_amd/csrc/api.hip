@@ -225,6 +225,7 @@ int vslam_abi_version(void) { return VSLAM_ABI_VERSION; }
 const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tests/test_abi.py checks the list against the sources)
     return "orb_resize_kernel orb_pyrblur_kernel orb_fast_kernel orb_select_kernel orb_anms_kernel orb_orient_kernel orb_blur_kernel orb_describe_kernel "
            "match_train_nearest_kernel match_finalize_kernel sgbm_prefilter_kernel sgbm_down_kernel sgbm_forward_kernel sgbm_hsum_kernel sgbm_vsum_kernel sgbm_path_kernel "
+           "sgbm_hsum_g_kernel sgbm_vsum_g_kernel sgbm_path_g_kernel sgbm_wta_g_kernel "
            "sgbm_wta_kernel sgbm_lrcheck_kernel sgbm_median3_kernel sgbm_ccl_rows_kernel sgbm_ccl_union_kernel sgbm_ccl_count_kernel "
            "sgbm_ccl_apply_kernel sgbm_ccl_kernels triangulate_kernel find3d_disparity_kernel gather_uv_kernel build_pnp_inputs_kernel lm_window_kernel pose_only_wave_kernel "
            "lm_window_kernel<pnp> pnp_wave_kernel pnp_inlier_kernel pnp_epnp_kernels epnp_front_kernel epnp_jacobi_kernel epnp_back_kernel pnp_count_inliers_kernel hbm_copy_probe_kernel "
@@ -537,20 +538,73 @@ int vslam_feature_matching(vslam_ctx* ctx, const uint8_t* q, int nq, const uint8
 
 // ---------------------------------------------------------------------------------------------- geometry
 // ---------------------------------------------------------------------------------------------- SGBM
-int vslam_disparity_map_dev(vslam_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride_bytes, int pitch, int w, int h,
-                            int B, float* d_disparity, int16_t* d_disp_i16, int16_t* d_disp_raw_i16) {
+void vslam_default_sgbm_params(vslam_sgbm_params* p) {
+    if (!p) return;
+    p->num_disparities = 96; p->block_size = 9; p->P1 = 8 * 9 * 9; p->P2 = 32 * 9 * 9; p->disp12_max_diff = 1; p->pre_filter_cap = 63; // visual_odometry.cpp:163-164
+    p->uniqueness_ratio = 10; p->speckle_window_size = 100; p->speckle_range = 32; p->struct_size = (int32_t)sizeof(vslam_sgbm_params);
+}
+
+int vslam_sgbm_params_check(const vslam_sgbm_params* p, int w, int h) {
+    if (!p) { set_error("vslam_sgbm_params: null pointer"); return VSLAM_ERR_ARG; }
+    auto refuse = [](const char* field, long v, const char* rule) { set_error("vslam_sgbm_params.%s = %ld: %s", field, v, rule); return VSLAM_ERR_ARG; };
+    if (p->struct_size != (int32_t)sizeof(vslam_sgbm_params)) return refuse("struct_size", p->struct_size, "not this library's sizeof(vslam_sgbm_params)");
+    if (p->num_disparities < 16 || p->num_disparities > 256 || p->num_disparities % 16) return refuse("num_disparities", p->num_disparities, "need a multiple of 16 in [16, 256]");
+    if (p->block_size < 1 || p->block_size % 2 == 0) return refuse("block_size", p->block_size, "need an odd size >= 1");
+    if (p->P1 <= 0) return refuse("P1", p->P1, "need 0 < P1 < P2");
+    if (p->P2 <= p->P1) return refuse("P2", p->P2, "need 0 < P1 < P2");
+    if (p->disp12_max_diff < 0) return refuse("disp12_max_diff", p->disp12_max_diff, "need >= 0");
+    if (p->pre_filter_cap < 1 || p->pre_filter_cap > 63) return refuse("pre_filter_cap", p->pre_filter_cap, "need a cap in [1, 63]");
+    if (p->uniqueness_ratio < 0 || p->uniqueness_ratio > 100) return refuse("uniqueness_ratio", p->uniqueness_ratio, "need a ratio in [0, 100]");
+    if (p->speckle_window_size < 0) return refuse("speckle_window_size", p->speckle_window_size, "need >= 0");
+    if (p->speckle_range < 0) return refuse("speckle_range", p->speckle_range, "need >= 0");
+    // the 16-bit range rule (include/vslam_hip.h): three path values plus the offset 3 * P2 in a u16
+    const long ftzero = (p->pre_filter_cap > 15 ? p->pre_filter_cap : 15) | 1;
+    const long bs = p->block_size < 255 ? p->block_size : 255; // (255^2 * 93 is far outside already: no overflow for any int32 field)
+    const long cmax = bs * bs * (2 * ftzero + 63);
+    if (3 * (cmax + (long)p->P2) > 65535) {
+        set_error("vslam_sgbm_params: block_size %d, pre_filter_cap %d and P2 %d leave the 16-bit range: need 3 * (block_size^2 * (2 * ftzero + 63) + P2) <= 65535, have %ld",
+                  p->block_size, p->pre_filter_cap, p->P2, 3 * (cmax + (long)p->P2));
+        return VSLAM_ERR_ARG;
+    }
+    if (w > 4096) { set_error("vslam_sgbm_params: image width %d > 4096", w); return VSLAM_ERR_ARG; }
+    if (w - p->num_disparities <= p->block_size / 2) {
+        set_error("vslam_sgbm_params.num_disparities = %d with block_size %d needs an image wider than %d (have %d)", p->num_disparities, p->block_size,
+                  p->num_disparities + p->block_size / 2, w);
+        return VSLAM_ERR_ARG;
+    }
+    if (h <= p->block_size) { set_error("vslam_sgbm_params.block_size = %d needs more than %d image rows (have %d)", p->block_size, p->block_size, h); return VSLAM_ERR_ARG; }
+    return VSLAM_OK;
+}
+
+// NULL = the reference's set; anything else must pass the check before a launch
+static int sgbm_set_of(const vslam_sgbm_params* sgbm, int w, int h, vslam_sgbm_params& sp) {
+    if (sgbm) sp = *sgbm; else vslam_default_sgbm_params(&sp);
+    return vslam_sgbm_params_check(&sp, w, h);
+}
+
+int vslam_disparity_map_ex_dev(vslam_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride_bytes, int pitch, int w, int h,
+                               int B, const vslam_sgbm_params* sgbm, float* d_disparity, int16_t* d_disp_i16, int16_t* d_disp_raw_i16) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !d_left || !d_right || w <= 0 || h <= 0 || pitch < w || B < 0 || img_stride_bytes < (size_t)pitch * h ||
         (!d_disparity && !d_disp_i16 && !d_disp_raw_i16)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    vslam_sgbm_params sp;
+    if (int rc = sgbm_set_of(sgbm, w, h, sp)) return rc;
     VS_ENTER(c);
     c->sgbm_unchecked = true; // (asynchronous: the forward sweep's error word is looked at by the next vslam_sync / vslam_sgbm_status_dev)
-    return launch_sgbm(c->tune, d_left, d_right, img_stride_bytes, pitch, w, h, B, d_disparity, d_disp_i16, d_disp_raw_i16, c->sgbm, c->stream);
+    return launch_sgbm(c->tune, sp, d_left, d_right, img_stride_bytes, pitch, w, h, B, d_disparity, d_disp_i16, d_disp_raw_i16, c->sgbm, c->stream);
 }
 
-int vslam_disparity_map(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int stride, float* disparity, int16_t* disp_i16,
-                        int16_t* disp_raw_i16) {
+int vslam_disparity_map_dev(vslam_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride_bytes, int pitch, int w, int h,
+                            int B, float* d_disparity, int16_t* d_disp_i16, int16_t* d_disp_raw_i16) {
+    return vslam_disparity_map_ex_dev(ctx, d_left, d_right, img_stride_bytes, pitch, w, h, B, nullptr, d_disparity, d_disp_i16, d_disp_raw_i16);
+}
+
+int vslam_disparity_map_ex(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int stride, const vslam_sgbm_params* sgbm,
+                           float* disparity, int16_t* disp_i16, int16_t* disp_raw_i16) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !left || !right || w <= 0 || h <= 0 || stride < w || (!disparity && !disp_i16 && !disp_raw_i16)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    vslam_sgbm_params sp;
+    if (int rc0 = sgbm_set_of(sgbm, w, h, sp)) return rc0;
     VS_ENTER(c);
     int rc;
     const size_t npix = (size_t)w * h;
@@ -565,12 +619,17 @@ int vslam_disparity_map(vslam_ctx* ctx, const uint8_t* left, const uint8_t* righ
          }))) return rc;
     if ((rc = upload_image(c, d_l, left, w, h, stride))) return rc;
     if ((rc = upload_image(c, d_r, right, w, h, stride, 1))) return rc;
-    if ((rc = launch_sgbm(c->tune, d_l, d_r, (size_t)pl * h, pl, w, h, 1, d_f, d_i, disp_raw_i16 ? d_raw : nullptr, c->sgbm, c->stream))) return rc;
+    if ((rc = launch_sgbm(c->tune, sp, d_l, d_r, (size_t)pl * h, pl, w, h, 1, d_f, d_i, disp_raw_i16 ? d_raw : nullptr, c->sgbm, c->stream))) return rc;
     if (disparity) VS_HIP(hipMemcpyAsync(disparity, d_f, npix * 4, hipMemcpyDeviceToHost, c->stream));
     if (disp_i16) VS_HIP(hipMemcpyAsync(disp_i16, d_i, npix * 2, hipMemcpyDeviceToHost, c->stream));
     if (disp_raw_i16) VS_HIP(hipMemcpyAsync(disp_raw_i16, d_raw, npix * 2, hipMemcpyDeviceToHost, c->stream));
     int32_t st = 0;
     return vslam_sgbm_status_dev(ctx, &st); // synchronises; VSLAM_ERR_HIP if the forward sweep's backstop fired
+}
+
+int vslam_disparity_map(vslam_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int stride, float* disparity, int16_t* disp_i16,
+                        int16_t* disp_raw_i16) {
+    return vslam_disparity_map_ex(ctx, left, right, w, h, stride, nullptr, disparity, disp_i16, disp_raw_i16);
 }
 
 int vslam_set_tuning(vslam_ctx* ctx, const char* name, int value) {

@@ -19,6 +19,9 @@
 //   sgbm_lrcheck_kernel       sub-pixel parabola, disp2 bookkeeping, left-right check (workgroup per row)
 //   sgbm_median3_kernel       3x3 median, replicated borders
 //   sgbm_ccl_{rows,union,count,apply}_kernel   speckle filter as connected-component labelling (atomic union-find) + size threshold, /16 -> f32
+// The list above is the reference's set (vslam_disparity_map[_dev]).  A caller's vslam_sgbm_params (vslam_disparity_map_ex[_dev]) runs
+//   sgbm_hsum_g / sgbm_vsum_g / sgbm_path_g<dx,dy,mode,NPL> / sgbm_wta_g   the line-parallel chain with the disparity count, block size, penalties and
+//                                              T offset as runtime values, NPL = 2 / 4 / 6 / 8 / 12 / 16 disparities per lane, at every batch size
 #include "vslam_internal.h"
 
 #include <stdlib.h>
@@ -876,10 +879,305 @@ __global__ __launch_bounds__(256) void sgbm_ccl_apply_kernel(int w, int h, int n
     if (out_f32) out_f32[g] = (float)d * 0.0625f; // convertTo(CV_32F, 1/16): exact
 }
 
+// ------------------------------------------------------------------------------------------- caller-set parameters: the general line-parallel chain
+// Any admissible vslam_sgbm_params other than the reference's runs prefilter -> sgbm_hsum_g -> sgbm_vsum_g -> sgbm_path_g x 5 (-> sgbm_wta_g)
+// -> lrcheck -> median -> CCL at EVERY batch size (the fused top-down / forward sweeps stay specialised for 96 disparities and the 9 x 9
+// window; profiles/sgbm_params.json records what that costs).  The cost volume's per-pixel stride is Dp = 16 * NPL int16, NPL = disparities per
+// lane of the 16-lane DPP row, one of 2 / 4 / 6 / 8 / 12 / 16: the smallest that holds D.  A lane slot with disparity >= D is padding: its
+// path value is forced to kSent after every step, so it behaves as the out-of-range neighbour of D - 1, never lowers the row minimum
+// (kSent > Cmax), never wins and never votes in the uniqueness test.  The running sum of the three downward paths is stored as u16 with the
+// offset 3 * P2 (L >= -P2 per path); vslam_sgbm_params_check's range rule 3 * (Cmax + P2) <= 65535 is what makes that, and kSent, exact.
+struct SgbmGDims { SgbmDims d; int Dp, toff; };
+__global__ __launch_bounds__(kHsBlock) void sgbm_hsum_g_kernel(SgbmGDims gd, const uint8_t* __restrict__ pre, int16_t* __restrict__ hsum) {
+    const SgbmDims& dm = gd.d;
+    const int b = blockIdx.z, y = blockIdx.y, j0 = blockIdx.x * kHsSeg;
+    const int Dp = gd.Dp, D = dm.D, SW2 = dm.SW2, nq = Dp >> 2, ng = Dp >> 3, ncol = kHsSeg + 2 * SW2;
+    extern __shared__ uint4 sgbm_gtile[]; // ncol x Dp bytes
+    uint8_t* tile = reinterpret_cast<uint8_t*>(sgbm_gtile);
+    const uint8_t* L = pre + (((size_t)(2 * b) * dm.h + y) * 6) * dm.w;
+    const uint8_t* R = pre + (((size_t)(2 * b + 1) * dm.h + y) * 6) * dm.w;
+    const int W1 = dm.width1, w = dm.w;
+    for (int it = threadIdx.x; it < ncol * nq; it += kHsBlock) {
+        const int t = it / nq, q = it - t * nq, d = 4 * q;
+        uint32_t out = 0;
+        if (d < D) { // (D is a multiple of 16: the whole quad is inside; x - d - 3 >= minX1 - D + 1 > 0)
+            const int jj = min(max(j0 - SW2 + t, 0), W1 - 1), x = dm.minX1 + jj;
+            uint32_t acc[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const uint8_t* lp = L + 3 * c * w; const uint8_t* rp = R + 3 * c * w;
+                const int u = lp[x], u0 = lp[w + x], u1 = lp[2 * w + x];
+                const uint32_t vv = ld_u32_unaligned(rp + x - d - 3), v0v = ld_u32_unaligned(rp + w + x - d - 3), v1v = ld_u32_unaligned(rp + 2 * w + x - d - 3);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { // disparity d + i <-> byte 3 - i
+                    const int sh = 8 * (3 - i);
+                    const int v = (vv >> sh) & 255, v0 = (v0v >> sh) & 255, v1 = (v1v >> sh) & 255;
+                    const int c0 = max(max(0, u - v1), v0 - u), c1 = max(max(0, v - u1), u0 - v);
+                    acc[i] += (uint32_t)(min(c0, c1) >> (c == 0 ? 0 : 2));
+                }
+            }
+            out = acc[0] | (acc[1] << 8) | (acc[2] << 16) | (acc[3] << 24); // each <= 2 * ftzero + 63 <= 189
+        }
+        *(uint32_t*)(tile + t * Dp + d) = out;
+    }
+    __syncthreads();
+    for (int it = threadIdx.x; it < kHsSeg * ng; it += kHsBlock) {
+        const int t = it / ng, g = it - t * ng;
+        if (j0 + t >= W1) continue;
+        uint32_t e0 = 0, o0 = 0, e1 = 0, o1 = 0; // block_size taps of <= 189: no carry between the packed u16 halves
+        for (int i = 0; i <= 2 * SW2; ++i) {
+            const uint2 v = *(const uint2*)(tile + (t + i) * Dp + 8 * g);
+            e0 += v.x & 0x00FF00FFu; o0 += (v.x >> 8) & 0x00FF00FFu;
+            e1 += v.y & 0x00FF00FFu; o1 += (v.y >> 8) & 0x00FF00FFu;
+        }
+        uint4 o;
+        o.x = (e0 & 0xFFFFu) | (o0 << 16); o.y = (e0 >> 16) | (o0 & 0xFFFF0000u);
+        o.z = (e1 & 0xFFFFu) | (o1 << 16); o.w = (e1 >> 16) | (o1 & 0xFFFF0000u);
+        *(uint4*)(hsum + (((size_t)b * dm.h + y) * W1 + j0 + t) * Dp + 8 * g) = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void sgbm_vsum_g_kernel(SgbmGDims gd, const int16_t* __restrict__ hsum, int16_t* __restrict__ C) {
+    const SgbmDims& dm = gd.d;
+    const int b = blockIdx.z, ya = blockIdx.y * kVsChunk, yb = min(ya + kVsChunk, dm.h), ng = gd.Dp >> 3;
+    const int it = blockIdx.x * 256 + threadIdx.x; // (j, g): 8 disparities
+    if (it >= dm.width1 * ng) return;
+    const int j = it / ng;
+    const size_t rs = (size_t)dm.width1 * gd.Dp; // row stride (elements)
+    const int16_t* hp = hsum + (size_t)b * dm.h * rs + (size_t)it * 8;
+    int16_t* cp = C + (size_t)b * dm.h * rs + (size_t)it * 8;
+    const int ylast = j == 0 ? 0 : dm.h - 1 - dm.SH2; // last row whose window is evaluated
+    const int yy = min(ya, ylast);
+    S8 acc = *(const S8*)(hp + (size_t)max(yy - dm.SH2, 0) * rs);
+    for (int k = yy - dm.SH2 + 1; k <= yy + dm.SH2; ++k) acc = s8_add(acc, *(const S8*)(hp + (size_t)max(k, 0) * rs));
+#pragma unroll 4
+    for (int y = ya; y < yb; ++y) {
+        *(S8*)(cp + (size_t)y * rs) = acc;
+        if (y + 1 <= ylast) acc = s8_sub(s8_add(acc, *(const S8*)(hp + (size_t)(y + 1 + dm.SH2) * rs)), *(const S8*)(hp + (size_t)max(y - dm.SH2, 0) * rs));
+    }
+}
+
+template <int N> struct alignas(4) UV { uint32_t v[N]; };
+template <bool NT, int N>
+__device__ inline UV<N> ld_uv(const void* p) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+    UV<N> r;
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.v[i] = NT ? __builtin_nontemporal_load(q + i) : q[i];
+    return r;
+}
+template <int N>
+__device__ inline void st_uv_nt(void* p, const UV<N>& v) {
+    uint32_t* q = reinterpret_cast<uint32_t*>(p);
+#pragma unroll
+    for (int i = 0; i < N; ++i) __builtin_nontemporal_store(v.v[i], q + i);
+}
+template <int N> __device__ inline int uv_get(const UV<N>& v, int i) { return (i & 1) ? hi16s(v.v[i >> 1]) : lo16s(v.v[i >> 1]); }
+template <int N> __device__ inline int uv_getu(const UV<N>& v, int i) { return (i & 1) ? (int)(v.v[i >> 1] >> 16) : (int)(v.v[i >> 1] & 0xFFFFu); }
+
+// wta_row16 with NPL disparities per lane, of which the first `nlive` are real (disparity < D)
+template <int NPL>
+__device__ inline void wta_row16_g(const SgbmDims& dm, const int (&s)[NPL], int r, int nlive, size_t out_index, int4* __restrict__ rec, bool active) {
+    const int d0 = NPL * r;
+    int best = 0x7FFFFFFF;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) if (i < nlive) best = min(best, ((s[i] + 32768) << 8) | (d0 + i));
+    best = row16_min(best);
+    const int minS = (best >> 8) - 32768, bd = best & 0xFF;
+    const int u = 100 - dm.uniq, lim = __mul24(minS, 100);
+    int bad = 0;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) bad |= (i < nlive && __mul24(s[i], u) < lim && abs(bd - d0 - i) > 1) ? 1 : 0;
+    bad = row16_max(bad);
+    const int sm_in = dpp_mov<0x111>(0, s[NPL - 1]), sp_in = dpp_mov<0x101>(0, s[0]);
+    const int j = bd - d0;
+    if (active && j >= 0 && j < NPL) { // the lane holding the winner
+        int sm = sm_in, sc = s[0], sp = s[1];
+#pragma unroll
+        for (int q = 1; q < NPL; ++q) if (j == q) { sm = s[q - 1]; sc = s[q]; sp = q + 1 < NPL ? s[q + 1 < NPL ? q + 1 : q] : sp_in; }
+        rec[out_index] = make_int4(bad ? -1 : best, (int)pack16(sm, sc), sp, 0);
+    }
+}
+
+template <int DX, int DY, int MODE, int NPL, int kPF>
+__global__ __launch_bounds__(kPathBlock) void sgbm_path_g_kernel(SgbmGDims gd, const int16_t* __restrict__ C, uint16_t* T, int nlines, int4* __restrict__ rec) {
+    const SgbmDims& dm = gd.d;
+    constexpr int NW = NPL / 2, Dp = NPL * 16;
+    static_assert(NPL % 2 == 0, "lane loads must stay dword-aligned");
+    const int b = blockIdx.y;
+    constexpr bool kNT = DX != 0 && DY != 0;
+    const int line = blockIdx.x * kPathLines + (threadIdx.x >> 4), r = threadIdx.x & 15;
+    if (line >= nlines) return; // whole DPP row leaves
+    const int W1 = dm.width1, h = dm.h;
+    int x0, y0, len;
+    if (DY == 0) { y0 = line; x0 = DX > 0 ? 0 : W1 - 1; len = W1; }
+    else if (DX == 0) { x0 = line; y0 = 0; len = h; }
+    else {
+        if (line < W1) { x0 = line; y0 = 0; } else { x0 = DX > 0 ? 0 : W1 - 1; y0 = line - W1 + 1; }
+        len = min(DX > 0 ? W1 - x0 : x0 + 1, h - y0);
+    }
+    const ptrdiff_t step = ((ptrdiff_t)DY * W1 + DX) * Dp;
+    const size_t first = (((size_t)b * h + y0) * W1 + x0) * Dp + NPL * r;
+    const int16_t* cp = C + first;
+    uint16_t* tp = T + first;
+    const int nlive = min(max(dm.D - NPL * r, 0), NPL); // slots of this lane that are disparities of the volume
+    UV<NW> cq[kPF], tq[kPF];
+#pragma unroll
+    for (int k = 0; k < kPF; ++k) {
+        const ptrdiff_t o = (ptrdiff_t)min(k, len - 1) * step;
+        cq[k] = ld_uv<kNT, NW>(cp + o);
+        if (MODE != 0) tq[k] = ld_uv<kNT, NW>(tp + o);
+    }
+    int l[NPL], minPrev = 0;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) l[i] = i < nlive ? 0 : kSent;
+    const int P1 = dm.P1, P2 = dm.P2, toff = gd.toff;
+    for (int s = 0; s < len; s += kPF) {
+#pragma unroll
+        for (int k = 0; k < kPF; ++k) {
+            const UV<NW> c = cq[k];
+            UV<NW> t = {};
+            if (MODE != 0) t = tq[k];
+            {
+                const ptrdiff_t o = (ptrdiff_t)min(s + k + kPF, len - 1) * step;
+                cq[k] = ld_uv<kNT, NW>(cp + o);
+                if (MODE != 0) tq[k] = ld_uv<kNT, NW>(tp + o);
+            }
+            const int lm = dpp_mov<0x111>(kSent, l[NPL - 1]); // row_shr:1 -- lane r-1's last disparity
+            const int lp = dpp_mov<0x101>(kSent, l[0]);       // row_shl:1 -- lane r+1's first disparity
+            const int delta = minPrev + P2;
+            int n[NPL], m = kSent;
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) {
+                const int dn = i > 0 ? l[i > 0 ? i - 1 : 0] : lm, up = i + 1 < NPL ? l[i + 1 < NPL ? i + 1 : i] : lp;
+                const int v = uv_get(c, i) - delta + min(min(l[i], min(dn, up) + P1), delta);
+                n[i] = i < nlive ? v : kSent;
+                m = min(m, n[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) l[i] = n[i];
+            minPrev = row16_min(m);
+            UV<NW> o;
+            if (MODE == 0) {
+#pragma unroll
+                for (int i = 0; i < NW; ++i) o.v[i] = pack16(n[2 * i] + toff, n[2 * i + 1] + toff);
+            } else if (MODE == 1) { // u16 wrap-around add: the true sum (+offset) always fits
+#pragma unroll
+                for (int i = 0; i < NW; ++i) o.v[i] = pack16(uv_getu(t, 2 * i) + n[2 * i], uv_getu(t, 2 * i + 1) + n[2 * i + 1]);
+            } else if (MODE == 2) {
+#pragma unroll
+                for (int i = 0; i < NW; ++i) o.v[i] = pack16(sat16_dev(uv_getu(t, 2 * i) - toff + n[2 * i]), sat16_dev(uv_getu(t, 2 * i + 1) - toff + n[2 * i + 1]));
+            } else {
+                int f[NPL];
+#pragma unroll
+                for (int i = 0; i < NPL; ++i) f[i] = sat16_dev(uv_get(t, i) + n[i]);
+                if (MODE == 3) {
+#pragma unroll
+                    for (int i = 0; i < NW; ++i) o.v[i] = pack16(f[2 * i], f[2 * i + 1]);
+                } else // last path: S is complete -- pick the winner here instead of storing it
+                    wta_row16_g<NPL>(dm, f, r, nlive, ((size_t)b * h + y0) * dm.w + dm.minX1 + x0 + (s + k) * DX, rec, s + k < len);
+            }
+            if (MODE != 4 && s + k < len) st_uv_nt<NW>(tp + (ptrdiff_t)(s + k) * step, o);
+        }
+    }
+}
+
+template <int NPL>
+__global__ __launch_bounds__(256) void sgbm_wta_g_kernel(SgbmGDims gd, const uint16_t* __restrict__ S, int4* __restrict__ rec) {
+    const SgbmDims& dm = gd.d;
+    const int b = blockIdx.y;
+    const size_t pixel = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int r = threadIdx.x & 15;
+    const size_t npx = (size_t)dm.h * dm.width1;
+    if (pixel >= npx) return;
+    const UV<NPL / 2> v = ld_uv<false, NPL / 2>(S + ((size_t)b * npx + pixel) * (NPL * 16) + NPL * r);
+    int s[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) s[i] = uv_get(v, i);
+    const int y = (int)(pixel / dm.width1), x = (int)(pixel - (size_t)y * dm.width1);
+    wta_row16_g<NPL>(dm, s, r, min(max(dm.D - NPL * r, 0), NPL), ((size_t)b * dm.h + y) * dm.w + x + dm.minX1, rec, true);
+}
+
+// the five paths (+ the stand-alone winner-take-all below 4 pairs, as in the default chain) for one lane width
+template <int NPL>
+static void launch_paths_g(const SgbmGDims& gd, int B, const int16_t* C, uint16_t* T, int4* rec, hipStream_t stream) {
+    const SgbmDims& dm = gd.d;
+    constexpr int kPv = NPL <= 8 ? 8 : 4, kPh = NPL <= 6 ? 16 : (NPL <= 8 ? 8 : 4); // prefetch depth: the queues stay in registers at every lane width
+    const int nv = dm.width1, nd = dm.width1 + dm.h - 1, h = dm.h;
+    const dim3 gv((nv + kPathLines - 1) / kPathLines, B), gdg((nd + kPathLines - 1) / kPathLines, B), gh((h + kPathLines - 1) / kPathLines, B);
+    { ProfScope p(stream, "sgbm_path_g_kernel<0,1>"); hipLaunchKernelGGL((sgbm_path_g_kernel<0, 1, 0, NPL, kPv>), gv, dim3(kPathBlock), 0, stream, gd, C, T, nv, (int4*)nullptr); }
+    { ProfScope p(stream, "sgbm_path_g_kernel<1,1>"); hipLaunchKernelGGL((sgbm_path_g_kernel<1, 1, 1, NPL, kPv>), gdg, dim3(kPathBlock), 0, stream, gd, C, T, nd, (int4*)nullptr); }
+    { ProfScope p(stream, "sgbm_path_g_kernel<-1,1>"); hipLaunchKernelGGL((sgbm_path_g_kernel<-1, 1, 1, NPL, kPv>), gdg, dim3(kPathBlock), 0, stream, gd, C, T, nd, (int4*)nullptr); }
+    { ProfScope p(stream, "sgbm_path_g_kernel<1,0>"); hipLaunchKernelGGL((sgbm_path_g_kernel<1, 0, 2, NPL, kPh>), gh, dim3(kPathBlock), 0, stream, gd, C, T, h, (int4*)nullptr); }
+    if (B >= 4) { ProfScope p(stream, "sgbm_path_g_kernel<-1,0>"); hipLaunchKernelGGL((sgbm_path_g_kernel<-1, 0, 4, NPL, kPh>), gh, dim3(kPathBlock), 0, stream, gd, C, T, h, rec); }
+    else {
+        { ProfScope p(stream, "sgbm_path_g_kernel<-1,0>"); hipLaunchKernelGGL((sgbm_path_g_kernel<-1, 0, 3, NPL, kPh>), gh, dim3(kPathBlock), 0, stream, gd, C, T, h, (int4*)nullptr); }
+        { ProfScope p(stream, "sgbm_wta_g_kernel"); hipLaunchKernelGGL(sgbm_wta_g_kernel<NPL>, dim3((unsigned)(((size_t)h * dm.width1 + 15) / 16), B), dim3(256), 0, stream, gd, T, rec); }
+    }
+}
+
 // ------------------------------------------------------------------------------------------- host driver
-int launch_sgbm(const Tuning& tune, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B, float* d_disp_f32,
-                int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream) {
+static int launch_sgbm_general(const vslam_sgbm_params& sp, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B,
+                               float* d_disp_f32, int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream) {
+    SgbmGDims gd;
+    SgbmDims& dm = gd.d;
+    const int D = sp.num_disparities, npl16 = D / 16;
+    const int npl = npl16 <= 2 ? 2 : (npl16 <= 4 ? 4 : (npl16 <= 6 ? 6 : (npl16 <= 8 ? 8 : (npl16 <= 12 ? 12 : 16))));
+    dm.w = w; dm.h = h; dm.D = D; dm.minX1 = D; dm.width1 = w - D; dm.P1 = sp.P1; dm.P2 = sp.P2; dm.SW2 = dm.SH2 = sp.block_size / 2; dm.uniq = sp.uniqueness_ratio;
+    dm.disp12 = sp.disp12_max_diff; dm.ftzero = max(sp.pre_filter_cap, 15) | 1; dm.pitch = pitch; dm.img_bytes = img_bytes;
+    gd.Dp = 16 * npl; gd.toff = 3 * sp.P2;
+    const size_t vol = (size_t)h * dm.width1 * gd.Dp, npix = (size_t)w * h;
+    int* hdr; uint8_t* pre; int16_t *hsum, *C, *d0, *d1; int4* rec; int *par, *cnt;
+    if (int rc = carve(scratch, stream, [&](Layout& L) {
+            hdr = L.take<int>(64); // the header of the default chain: its error word is this launch's too (cleared, never set)
+            pre = L.take<uint8_t>((size_t)2 * B * h * 6 * w);
+            hsum = L.take<int16_t>(B * vol);
+            C = L.take<int16_t>(B * vol);
+            rec = L.take<int4>(B * npix);
+            d0 = L.take<int16_t>(B * npix);
+            d1 = L.take<int16_t>(B * npix);
+            par = L.take<int>(B * npix);
+            cnt = L.take<int>(B * npix);
+        })) return rc;
+    uint16_t* T = (uint16_t*)hsum; // hsum is dead once C exists
+    VS_HIP(hipMemsetAsync(hdr, 0, 64, stream));
+    { ProfScope p(stream, "sgbm_prefilter_kernel"); hipLaunchKernelGGL(sgbm_prefilter_kernel, dim3((w + 255) / 256, h, 2 * B), dim3(256), 0, stream, dm, d_left, d_right, pre); }
+    { ProfScope p(stream, "sgbm_hsum_g_kernel");
+      hipLaunchKernelGGL(sgbm_hsum_g_kernel, dim3((dm.width1 + kHsSeg - 1) / kHsSeg, h, B), dim3(kHsBlock), (size_t)(kHsSeg + 2 * dm.SW2) * gd.Dp, stream, gd, pre, hsum); }
+    { ProfScope p(stream, "sgbm_vsum_g_kernel");
+      hipLaunchKernelGGL(sgbm_vsum_g_kernel, dim3((dm.width1 * (gd.Dp / 8) + 255) / 256, (h + kVsChunk - 1) / kVsChunk, B), dim3(256), 0, stream, gd, hsum, C); }
+    switch (npl) {
+        case 2: launch_paths_g<2>(gd, B, C, T, rec, stream); break;
+        case 4: launch_paths_g<4>(gd, B, C, T, rec, stream); break;
+        case 6: launch_paths_g<6>(gd, B, C, T, rec, stream); break;
+        case 8: launch_paths_g<8>(gd, B, C, T, rec, stream); break;
+        case 12: launch_paths_g<12>(gd, B, C, T, rec, stream); break;
+        default: launch_paths_g<16>(gd, B, C, T, rec, stream); break;
+    }
+    { ProfScope p(stream, "sgbm_lrcheck_kernel");
+      hipLaunchKernelGGL(sgbm_lrcheck_kernel, dim3(h, B), dim3(kLrBlock), (size_t)(w + (w + 1) / 2) * sizeof(int), stream, dm, rec, d0); }
+    if (d_disp_raw) VS_HIP(hipMemcpyAsync(d_disp_raw, d0, (size_t)B * npix * 2, hipMemcpyDeviceToDevice, stream));
+    { ProfScope p(stream, "sgbm_median3_kernel"); hipLaunchKernelGGL(sgbm_median3_kernel, dim3((w + 255) / 256, h, B), dim3(256), 0, stream, w, h, d0, d1); }
+    const int pblocks = (int)((npix + 255) / 256);
+    // speckle_window_size 0 = no filter: a size threshold of 0 removes no component.  Disparities are int16: a range beyond 4096 joins everything.
+    const int newVal = -16, maxDiff = 16 * min(sp.speckle_range, 4096), maxSize = sp.speckle_window_size;
+    { ProfScope p(stream, "sgbm_ccl_kernels", 4);
+      hipLaunchKernelGGL(sgbm_ccl_rows_kernel, dim3(h, B), dim3(kCclBlock), (size_t)2 * w * sizeof(int), stream, w, h, maxDiff, newVal, d1, par, cnt);
+      hipLaunchKernelGGL(sgbm_ccl_union_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, maxDiff, newVal, d1, par);
+      hipLaunchKernelGGL(sgbm_ccl_count_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, maxDiff, newVal, d1, par, cnt);
+      hipLaunchKernelGGL(sgbm_ccl_apply_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, newVal, maxSize, par, cnt, d1, d_disp_f32, d_disp_i16); }
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
+// sp has passed vslam_sgbm_params_check for (w, h) (the API entries run it before anything is launched).  The reference's own set keeps the
+// kernels and the batch-size dispatch it has always had; every other set runs the general chain.
+int launch_sgbm(const Tuning& tune, const vslam_sgbm_params& sp, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B,
+                float* d_disp_f32, int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream) {
     if (B <= 0) return VSLAM_OK;
+    const bool reference_set = sp.num_disparities == 96 && sp.block_size == 9 && sp.P1 == 8 * 9 * 9 && sp.P2 == 32 * 9 * 9 && sp.disp12_max_diff == 1 &&
+                               sp.pre_filter_cap == 63 && sp.uniqueness_ratio == 10 && sp.speckle_window_size == 100 && sp.speckle_range == 32;
+    if (!reference_set) return launch_sgbm_general(sp, d_left, d_right, img_bytes, pitch, w, h, B, d_disp_f32, d_disp_i16, d_disp_raw, scratch, stream);
     SgbmDims dm;
     dm.w = w; dm.h = h; dm.D = 96; dm.minX1 = 96; dm.width1 = w - 96; dm.P1 = 8 * 9 * 9; dm.P2 = 32 * 9 * 9; dm.SW2 = 4; dm.SH2 = 4; dm.uniq = 10;
     dm.disp12 = 1; dm.ftzero = 63; dm.pitch = pitch; dm.img_bytes = img_bytes; // visual_odometry.cpp:163-164

@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import BaBatch, DMATCH_DTYPE, KEYPOINT_DTYPE, TracksIn, VO, default_params
+from . import BaBatch, DMATCH_DTYPE, KEYPOINT_DTYPE, TracksIn, VO, _sgbm_params, default_params, sgbm_params_check
 from . import synth
 from .trajectory import assemble_trajectory, sliding_keyframes, write_trajectory  # noqa: F401  (re-exported)
 
@@ -26,9 +26,11 @@ class KeyframePipeline:
     def __init__(self, B, device=0, anms_num=1500, n_lm=3000, n_kf=10, unique_frames=64, unique_windows=None, seed=0, verbose=False,
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
                  lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
-                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all"):
+                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all", sgbm_params=None):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
+        sgbm_params (depth="sgbm"): the StereoSGBM set of the batched disparity call -- an SgbmParams, a dict of its fields or a tuple
+        (num_disparities, block_size[, P1, P2, ...]); None = the reference's (96, 9, 648, 2592, 1, 63, 10, 100, 32).
         Inputs: ONE rendered sequence of `unique_frames` consecutive stereo keyframes, laid over the batch as a ping-pong
         (0, 1, ..., n-1, n-2, ..., 1, 0, 1, ...), so that every item b >= 1 and its predecessor are adjacent frames of the same
         scene (driving the sequence backwards is as valid a frame-to-frame pair as driving it forwards); `unique_windows` BA
@@ -71,6 +73,8 @@ class KeyframePipeline:
         self.window_policy, self.near_dist = window_policy, float(near_dist)
         self.keyframe_gate = "per_pass" if per_pass else bool(keyframe_gate)
         self.depth = depth
+        assert sgbm_params is None or depth == "sgbm", "sgbm_params needs depth='sgbm'"
+        self.sgbm_params = _sgbm_params(sgbm_params)
         self.pose = pose   # "lm": north_star motion-only LM; "ransac": the reference's cv::solvePnPRansac(..., 100, 4.0, 0.99) (visual_odometry.cpp:277)
         self.ba_windows = ba_windows
         self.B = B
@@ -85,6 +89,8 @@ class KeyframePipeline:
         self.cap = p.kp_capacity
         self.w, self.h = p.img_w, p.img_h
         self.pitch = (self.w + 63) // 64 * 64
+        if self.sgbm_params is not None:
+            sgbm_params_check(self.sgbm_params, self.w, self.h)  # (raises VslamError: a refused set never reaches the batched call)
         self.img_bytes = self.pitch * self.h
         d = self.dev
         # ---- inputs: 2B images [left 0..B-1 | right 0..B-1]; consecutive keyframes of `unique_scenes` short sequences
@@ -258,7 +264,7 @@ class KeyframePipeline:
         if self.depth == "sgbm":
             # VO::disparity_map + Frame::find_3d / gates of set_ref_3d_position on every left keypoint (visual_odometry.cpp:159-217)
             vo.disparity_map_dev(self.d_imgs.data_ptr(), self.d_imgs.data_ptr() + B * self.img_bytes, self.img_bytes, self.pitch, self.w, self.h, B,
-                                 self.d_disp.data_ptr())
+                                 self.d_disp.data_ptr(), sgbm=self.sgbm_params)
             vo.find_3d_disparity_dev(self.d_kps.data_ptr(), self.d_cnt.data_ptr(), cap, B, self.d_disp.data_ptr(), self.w, self.h,
                                      self.d_Tident.data_ptr(), self.d_xyz.data_ptr(), self.d_valid.data_ptr(), self.d_rel.data_ptr())
             with torch.cuda.stream(self.stream):

@@ -1,0 +1,114 @@
+"""Shared by tests/test_sgbm_params.py (CPU) and tests/test_gpu_sgbm_params.py: the StereoSGBM parameter sets, the stereo pairs and the refused
+sets of the caller-set-SGBM tests.  A set is a dict of vslam_sgbm_params fields over the reference's (96, 9, 648, 2592, 1, 63, 10, 100, 32)."""
+import functools
+
+import numpy as np
+
+DEFAULT = dict(num_disparities=96, block_size=9, P1=648, P2=2592, disp12_max_diff=1, pre_filter_cap=63, uniqueness_ratio=10,
+               speckle_window_size=100, speckle_range=32)
+# vslam_sgbm_params field -> keyword of oracle.sgbm_compute
+ORACLE_KW = dict(num_disparities="num_disp", block_size="block", P1="P1", P2="P2", disp12_max_diff="disp12_max_diff", pre_filter_cap="pre_filter_cap",
+                 uniqueness_ratio="uniqueness", speckle_window_size="speckle_window", speckle_range="speckle_range")
+
+
+def _db(D, block, P1, P2, **kw):
+    return dict(num_disparities=D, block_size=block, P1=P1, P2=P2, **kw)
+
+
+# disparity range / window sets: run on the noise pairs and on the rendered pair
+DB_SETS = {
+    "d16_b3": _db(16, 3, 72, 288), "d32_b5": _db(32, 5, 200, 800), "d64_b7": _db(64, 7, 392, 1568), "d80_b5": _db(80, 5, 200, 800),
+    "d128_b9": _db(128, 9, 648, 2592), "d256_b3": _db(256, 3, 72, 288), "d96_b11_cap31": _db(96, 11, 968, 3872, pre_filter_cap=31),
+    "d96_b1": _db(96, 1, 8, 32),
+}
+# matching-constant sets: they change nothing on the rendered pairs, so they run on the noise pairs only
+CONST_SETS = {
+    "uniq0": dict(uniqueness_ratio=0), "uniq40": dict(uniqueness_ratio=40), "uniq100": dict(uniqueness_ratio=100),
+    "disp12_0": dict(disp12_max_diff=0), "disp12_1000": dict(disp12_max_diff=1000),
+    "speckle_off": dict(speckle_window_size=0), "speckle_400_r1": dict(speckle_window_size=400, speckle_range=1),
+    "cap15": dict(pre_filter_cap=15), "p1_100_p2_101": dict(P1=100, P2=101),
+}
+SETS = {**DB_SETS, **CONST_SETS}
+
+
+def full(s):
+    return {**DEFAULT, **s}
+
+
+def oracle_kwargs(s):
+    return {ORACLE_KW[k]: v for k, v in full(s).items()}
+
+
+def min_width_ok(s, w, h):
+    f = full(s)
+    return w - f["num_disparities"] > f["block_size"] // 2 and h > f["block_size"]
+
+
+def noise(synth, w, h, shift, band):
+    """the construction of test_sgbm_noise_pair_with_speckles: a shifted copy of blocky noise with a band of unrelated rows in the right view"""
+    base = synth.noise_image(3, w + shift, h)
+    L = np.ascontiguousarray(base[:, :w]); R = np.ascontiguousarray(base[:, shift:]).copy()
+    R[band[0]:band[1]] = synth.noise_image(4, w, band[1] - band[0])
+    return L, R
+
+
+def rendered(synth, seed, w, h, noise_amp=0):
+    """the rendered pair of test_sgbm_small_sizes"""
+    sc = synth.Scene(seed)
+    T = synth.trajectory(1, seed)[0]
+    L, _ = sc.render(T, w, h)
+    R, _ = sc.render(T, w, h, x_offset=synth.BASELINE)
+    if noise_amp:
+        rng = np.random.default_rng(seed)
+        R = np.clip(R.astype(int) + rng.integers(-noise_amp, noise_amp + 1, R.shape), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(L), np.ascontiguousarray(R)
+
+
+@functools.lru_cache(maxsize=None)
+def _pairs_cached():
+    from stereo_visual_slam_amd import synth
+    return {
+        "noise300": noise(synth, 300, 60, 31, (20, 40)),
+        "noise420": noise(synth, 420, 48, 110, (16, 32)),   # winner at disparity 110: only D >= 128 finds it (lanes above 96)
+        "noise480": noise(synth, 480, 40, 200, (12, 24)),   # winner at disparity 200: D = 256
+        "rendered333": rendered(synth, 7 + 333, 333, 77, 10),
+    }
+
+
+def pairs():
+    return _pairs_cached()
+
+
+def host_cases():
+    """(pair name, set name) of the host-tier test: every set on every noise pair wide enough for it, the D / block sets on the rendered pair too"""
+    out = []
+    for pn, (L, _) in pairs().items():
+        h, w = L.shape
+        for sn, s in SETS.items():
+            if pn == "rendered333" and sn not in DB_SETS:
+                continue
+            if min_width_ok(s, w, h):
+                out.append((pn, sn))
+    return out
+
+
+def saturated_pair():
+    """the 0 / 255 random 50 x 260 pair of test_sgbm_flat_and_saturated: maximum pixel costs"""
+    rng = np.random.default_rng(0)
+    L = (rng.integers(0, 2, (50, 260)) * 255).astype(np.uint8); R = (rng.integers(0, 2, (50, 260)) * 255).astype(np.uint8)
+    return L, R
+
+
+BOUNDARY = _db(96, 9, 6535, 6536)                       # 3 * (81 * 189 + 6536) = 65535: the last admissible P2 at block 9, cap 63
+BEYOND = {"p2_6537": _db(96, 9, 6535, 6537), "b11_cap63": _db(96, 11, 968, 3872)}   # refused or exact, never different
+
+# (name, set, w, h): what vslam_sgbm_params_check must refuse
+REFUSED = [
+    ("D0", dict(num_disparities=0), 300, 60), ("D24", dict(num_disparities=24), 300, 60), ("D272", dict(num_disparities=272), 400, 60),
+    ("block_even", dict(block_size=8), 300, 60), ("P1_0", dict(P1=0), 300, 60), ("P1_eq_P2", dict(P1=2592), 300, 60), ("P1_gt_P2", dict(P1=3000), 300, 60),
+    ("cap0", dict(pre_filter_cap=0), 300, 60), ("cap64", dict(pre_filter_cap=64), 300, 60),
+    ("uniq_neg", dict(uniqueness_ratio=-1), 300, 60), ("uniq101", dict(uniqueness_ratio=101), 300, 60),
+    ("disp12_neg", dict(disp12_max_diff=-1), 300, 60), ("speckle_range_neg", dict(speckle_range=-1), 300, 60),
+    ("too_narrow", dict(), 100, 60), ("too_narrow_d64_b7", _db(64, 7, 392, 1568), 67, 60), ("too_low", dict(), 300, 9),
+    ("too_wide", dict(), 4097, 60), ("struct_size", dict(struct_size=36), 300, 60),
+]
