@@ -19,17 +19,22 @@
 //   sgbm_lrcheck_kernel       sub-pixel parabola, disp2 bookkeeping, left-right check (workgroup per row)
 //   sgbm_median3_kernel       3x3 median, replicated borders
 //   sgbm_ccl_{rows,union,count,apply}_kernel   speckle filter as connected-component labelling (atomic union-find) + size threshold, /16 -> f32
-// The list above is the reference's set (vslam_disparity_map[_dev]).  A caller's vslam_sgbm_params (vslam_disparity_map_ex[_dev]) runs
-//   sgbm_hsum_g / sgbm_vsum_g / sgbm_path_g<dx,dy,mode,NPL> / sgbm_wta_g   the line-parallel chain with the disparity count, block size, penalties and
-//                                              T offset as runtime values, NPL = 2 / 4 / 6 / 8 / 12 / 16 disparities per lane, at every batch size
+// The batch thresholds above are the reference's set (vslam_disparity_map[_dev]).  Any other vslam_sgbm_params (vslam_disparity_map_ex[_dev]) runs
+// the line kernels -- hsum, vsum, one sgbm_path_kernel per path (+ sgbm_wta_kernel) -- at every batch size: they take the disparity count, block
+// size, penalties and T offset from SgbmDims and are instantiated for NPL = 2 / 4 / 6 / 8 / 12 / 16 disparities per lane; the two fused sweeps
+// stay specialised for 96 disparities and the 9 x 9 window.
 #include "vslam_internal.h"
 
 #include <stdlib.h>
 
 namespace vslam {
 
+// The cost volume's per-pixel stride is Dp = 16 * NPL int16, NPL = disparities per lane of the 16-lane DPP row that owns a pixel: the smallest of
+// 2 / 4 / 6 / 8 / 12 / 16 that holds D (lane slots with disparity >= D are padding).  toff: the u16 offset of T, the running sum of the three
+// downward paths (each L >= -P2) -- kTOffset for the reference's set, whose fused sweeps write T with that constant, 3 * P2 for any other;
+// vslam_sgbm_params_check's range rule 3 * (Cmax + P2) <= 65535 is what makes the offset sum, and kSent below, exact.
 struct SgbmDims {
-    int w, h, D, minX1, width1, P1, P2, SW2, SH2, uniq, disp12, ftzero, pitch;
+    int w, h, D, Dp, minX1, width1, P1, P2, toff, SW2, SH2, uniq, disp12, ftzero, pitch;
     size_t img_bytes;
 };
 
@@ -69,60 +74,65 @@ __global__ __launch_bounds__(256) void sgbm_prefilter_kernel(SgbmDims dm, const 
 
 // ------------------------------------------------------------------------------------------- block cost, horizontal part
 // One workgroup = one image row x kHsSeg pixels.  Phase 1 evaluates the Birchfield-Tomasi pixel cost (both channels)
-// once per (pixel, disparity) of the segment plus a 4-pixel halo (columns clamped to the volume, like the reference's
+// once per (pixel, disparity) of the segment plus a block_size / 2 pixel halo (columns clamped to the volume, like the reference's
 // box sums) into an LDS tile, four disparities per work item through unaligned dword loads of the right-view planes.
-// Phase 2 forms the 9-tap horizontal sums, 8 disparities per work item (ds_read_b64, byte lanes accumulated as two
+// Phase 2 forms the block_size-tap horizontal sums, 8 disparities per work item (ds_read_b64, byte lanes accumulated as two
 // packed u16 pairs), and stores them as int16.
+// D_CT / TAPS != 0: num_disparities (then no lane slot is padding: Dp = D) and block_size as compile-time values; 0 = from SgbmDims.
 constexpr int kHsSeg = 64, kHsBlock = 256;
 __device__ inline uint32_t ld_u32_unaligned(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 
+template <int D_CT, int TAPS>
 __global__ __launch_bounds__(kHsBlock) void sgbm_hsum_kernel(SgbmDims dm, const uint8_t* __restrict__ pre, int16_t* __restrict__ hsum) {
     const int b = blockIdx.z, y = blockIdx.y, j0 = blockIdx.x * kHsSeg;
-    __shared__ alignas(16) uint8_t tile[(kHsSeg + 8) * 96];
+    const int Dp = D_CT ? D_CT : dm.Dp, D = D_CT ? D_CT : dm.D, SW2 = TAPS ? TAPS / 2 : dm.SW2, nq = Dp >> 2, ng = Dp >> 3, ncol = kHsSeg + 2 * SW2;
+    extern __shared__ uint4 sgbm_hs_tile[]; // ncol x Dp bytes
+    uint8_t* tile = reinterpret_cast<uint8_t*>(sgbm_hs_tile);
     const uint8_t* L = pre + (((size_t)(2 * b) * dm.h + y) * 6) * dm.w;
     const uint8_t* R = pre + (((size_t)(2 * b + 1) * dm.h + y) * 6) * dm.w;
     const int W1 = dm.width1, w = dm.w;
-    for (int it = threadIdx.x; it < (kHsSeg + 8) * 24; it += kHsBlock) {
-        const int t = it / 24, q = it - t * 24, d = 4 * q;
-        const int jj = min(max(j0 - 4 + t, 0), W1 - 1), x = dm.minX1 + jj;
+    for (int it = threadIdx.x; it < ncol * nq; it += kHsBlock) {
+        const int t = it / nq, q = it - t * nq, d = 4 * q;
         uint32_t out = 0;
-        uint32_t acc[4] = {0, 0, 0, 0};
+        if (d < D) { // (D is a multiple of 16: the whole quad is inside; x - d - 3 >= minX1 - D + 1 > 0)
+            const int jj = min(max(j0 - SW2 + t, 0), W1 - 1), x = dm.minX1 + jj;
+            uint32_t acc[4] = {0, 0, 0, 0};
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const uint8_t* lp = L + 3 * c * w; const uint8_t* rp = R + 3 * c * w;
-            const int u = lp[x], u0 = lp[w + x], u1 = lp[2 * w + x];
-            const uint32_t vv = ld_u32_unaligned(rp + x - d - 3), v0v = ld_u32_unaligned(rp + w + x - d - 3), v1v = ld_u32_unaligned(rp + 2 * w + x - d - 3);
+            for (int c = 0; c < 2; ++c) {
+                const uint8_t* lp = L + 3 * c * w; const uint8_t* rp = R + 3 * c * w;
+                const int u = lp[x], u0 = lp[w + x], u1 = lp[2 * w + x];
+                const uint32_t vv = ld_u32_unaligned(rp + x - d - 3), v0v = ld_u32_unaligned(rp + w + x - d - 3), v1v = ld_u32_unaligned(rp + 2 * w + x - d - 3);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { // disparity d + i <-> byte 3 - i
-                const int sh = 8 * (3 - i);
-                const int v = (vv >> sh) & 255, v0 = (v0v >> sh) & 255, v1 = (v1v >> sh) & 255;
-                const int c0 = max(max(0, u - v1), v0 - u), c1 = max(max(0, v - u1), u0 - v);
-                acc[i] += (uint32_t)(min(c0, c1) >> (c == 0 ? 0 : 2));
+                for (int i = 0; i < 4; ++i) { // disparity d + i <-> byte 3 - i
+                    const int sh = 8 * (3 - i);
+                    const int v = (vv >> sh) & 255, v0 = (v0v >> sh) & 255, v1 = (v1v >> sh) & 255;
+                    const int c0 = max(max(0, u - v1), v0 - u), c1 = max(max(0, v - u1), u0 - v);
+                    acc[i] += (uint32_t)(min(c0, c1) >> (c == 0 ? 0 : 2));
+                }
             }
+            out = acc[0] | (acc[1] << 8) | (acc[2] << 16) | (acc[3] << 24); // each <= 2 * ftzero + 63 <= 189
         }
-        out = acc[0] | (acc[1] << 8) | (acc[2] << 16) | (acc[3] << 24); // each <= 126 + 63
-        *(uint32_t*)(tile + t * 96 + d) = out;
+        *(uint32_t*)(tile + t * Dp + d) = out;
     }
     __syncthreads();
-    for (int it = threadIdx.x; it < kHsSeg * 12; it += kHsBlock) {
-        const int t = it / 12, g = it - t * 12;
+    for (int it = threadIdx.x; it < kHsSeg * ng; it += kHsBlock) {
+        const int t = it / ng, g = it - t * ng;
         if (j0 + t >= W1) continue;
-        uint32_t e0 = 0, o0 = 0, e1 = 0, o1 = 0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-            const uint2 v = *(const uint2*)(tile + (t + i) * 96 + 8 * g);
+        uint32_t e0 = 0, o0 = 0, e1 = 0, o1 = 0; // block_size taps of <= 189: no carry between the packed u16 halves
+        for (int i = 0; i <= 2 * SW2; ++i) {
+            const uint2 v = *(const uint2*)(tile + (t + i) * Dp + 8 * g);
             e0 += v.x & 0x00FF00FFu; o0 += (v.x >> 8) & 0x00FF00FFu;
             e1 += v.y & 0x00FF00FFu; o1 += (v.y >> 8) & 0x00FF00FFu;
         }
         uint4 o;
         o.x = (e0 & 0xFFFFu) | (o0 << 16); o.y = (e0 >> 16) | (o0 & 0xFFFF0000u);
         o.z = (e1 & 0xFFFFu) | (o1 << 16); o.w = (e1 >> 16) | (o1 & 0xFFFF0000u);
-        *(uint4*)(hsum + (((size_t)b * dm.h + y) * W1 + j0 + t) * 96 + 8 * g) = o;
+        *(uint4*)(hsum + (((size_t)b * dm.h + y) * W1 + j0 + t) * Dp + 8 * g) = o;
     }
 }
 
 // ------------------------------------------------------------------------------------------- block cost, vertical part
-// C(y) = sum of hsum over rows y-4..y+4 (rows above the image replicate row 0); the reference stops sliding SH2 rows
+// C(y) = sum of hsum over rows y-SH2..y+SH2 (rows above the image replicate row 0); the reference stops sliding SH2 rows
 // above the bottom (the last rows repeat C(h-1-SH2)) and never updates column 0 after the first row.  Each work item owns
 // (column, 8 disparities) and slides down a chunk of rows with packed int16 adds: 2 loads + 1 store per row.
 typedef short short2v __attribute__((ext_vector_type(2)));
@@ -132,11 +142,11 @@ __device__ inline S8 s8_sub(S8 p, S8 q) { return S8{p.a - q.a, p.b - q.b, p.c - 
 constexpr int kVsChunk = 47;
 
 __global__ __launch_bounds__(256) void sgbm_vsum_kernel(SgbmDims dm, const int16_t* __restrict__ hsum, int16_t* __restrict__ C) {
-    const int b = blockIdx.z, ya = blockIdx.y * kVsChunk, yb = min(ya + kVsChunk, dm.h);
+    const int b = blockIdx.z, ya = blockIdx.y * kVsChunk, yb = min(ya + kVsChunk, dm.h), ng = dm.Dp >> 3;
     const int it = blockIdx.x * 256 + threadIdx.x; // (j, g): 8 disparities
-    if (it >= dm.width1 * 12) return;
-    const int j = it / 12;
-    const size_t rs = (size_t)dm.width1 * 96; // row stride (elements)
+    if (it >= dm.width1 * ng) return;
+    const int j = it / ng;
+    const size_t rs = (size_t)dm.width1 * dm.Dp; // row stride (elements)
     const int16_t* hp = hsum + (size_t)b * dm.h * rs + (size_t)it * 8;
     int16_t* cp = C + (size_t)b * dm.h * rs + (size_t)it * 8;
     const int ylast = j == 0 ? 0 : dm.h - 1 - dm.SH2; // last row whose window is evaluated
@@ -154,17 +164,19 @@ __global__ __launch_bounds__(256) void sgbm_vsum_kernel(SgbmDims dm, const int16
 // The five SGM paths of MODE_SGBM's single pass are independent 1-D recurrences along image lines:
 //   L_r(p, d) = C(p, d) + min(L_r(p-r, d), L_r(p-r, d-1) + P1, L_r(p-r, d+1) + P1, min_k L_r(p-r, k) + P2) - (min_k L_r(p-r, k) + P2)
 // with L_r = 0 (and its minimum 0) outside the cost volume.  One 16-lane DPP row owns one line and walks it with the
-// previous L in registers (6 disparities per lane, D = 96): neighbour disparities come from row_shr/row_shl, the
-// per-pixel minimum from a 4-step quad_perm/row_mirror reduction -- no LDS, no barriers, loads prefetched kPathPF steps ahead.
+// previous L in registers (NPL disparities per lane; 6 for D = 96): neighbour disparities come from row_shr/row_shl, the
+// per-pixel minimum from a 4-step quad_perm/row_mirror reduction -- no LDS, no barriers, loads prefetched kPF steps ahead.
+// A lane slot with disparity >= D is padding: its path value is forced to kSent after every step, so it behaves as the out-of-range
+// neighbour of D - 1, never lowers the row minimum (kSent > Cmax), never wins and never votes in the uniqueness test.  FULL = no slot is
+// padding (D = 16 * NPL, the reference's set among them): the selects fold away.
 // Accumulation keeps the reference's saturation order S = sat16(sat16(L0 + L1 + L2 + L3) + L4):
-//   MODE 0: T  = L + kTOffset           (first of the three paths from the previous row; u16, wrap-safe)
+//   MODE 0: T  = L + toff               (first of the three paths from the previous row; u16, wrap-safe)
 //   MODE 1: T += L                      (the other two)
-//   MODE 2: S1 = sat16(L + T - kTOffset)     (left -> right, in place)
+//   MODE 2: S1 = sat16(L + T - toff)         (left -> right, in place)
 //   MODE 3: S  = sat16(S1 + L)               (right -> left, in place; winner-take-all in its own kernel: small batches,
 //                                              where the extra instructions on the sequential chain cost more than the traffic)
 //   MODE 4: same, but S is consumed on the spot by the winner-take-all and never stored (large batches, HBM-bound)
 constexpr int kSent = 30000; // out-of-range disparity neighbour: any value with kSent + P1 > max(delta) behaves like SHRT_MAX
-struct alignas(4) U3 { uint32_t a, b, c; };
 
 template <int CTRL>
 __device__ inline int dpp_mov(int old, int src) { return __builtin_amdgcn_update_dpp(old, src, CTRL, 0xF, 0xF, false); }
@@ -186,30 +198,47 @@ __device__ inline int lo16s(uint32_t v) { return (int)(int16_t)(v & 0xFFFFu); }
 __device__ inline int hi16s(uint32_t v) { return (int)v >> 16; }
 __device__ inline uint32_t pack16(int lo, int hi) { return ((uint32_t)lo & 0xFFFFu) | ((uint32_t)hi << 16); }
 
-// winner-take-all for one pixel held by a DPP row (6 disparities per lane): first minimum and the uniqueness test.
+template <int N> struct alignas(4) UV { uint32_t v[N]; };
+template <bool NT, int N>
+__device__ inline UV<N> ld_uv(const void* p) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+    UV<N> r;
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.v[i] = NT ? __builtin_nontemporal_load(q + i) : q[i];
+    return r;
+}
+template <int N>
+__device__ inline void st_uv_nt(void* p, const UV<N>& v) {
+    uint32_t* q = reinterpret_cast<uint32_t*>(p);
+#pragma unroll
+    for (int i = 0; i < N; ++i) __builtin_nontemporal_store(v.v[i], q + i);
+}
+template <int N> __device__ inline int uv_get(const UV<N>& v, int i) { return (i & 1) ? hi16s(v.v[i >> 1]) : lo16s(v.v[i >> 1]); }
+template <int N> __device__ inline int uv_getu(const UV<N>& v, int i) { return (i & 1) ? (int)(v.v[i >> 1] >> 16) : (int)(v.v[i >> 1] & 0xFFFFu); }
+
+// winner-take-all for one pixel held by a DPP row (NPL disparities per lane, of which the first `nlive` are disparities of the volume): first
+// minimum and the uniqueness test.
 // The lane holding the winner writes rec = {(minS + 32768) << 8 | d  (or -1 when not unique), S[d-1] | S[d] << 16, S[d+1]};
 // the parabola sub-pixel step (an integer division) is left to the left-right kernel, off this sequential chain.
-__device__ inline void wta_row16(const SgbmDims& dm, int s0, int s1, int s2, int s3, int s4, int s5, int r, size_t out_index,
-                                 int4* __restrict__ rec, bool active) {
-    const int d0 = 6 * r;
-    int best = ((s0 + 32768) << 8) | d0;
-    best = min(best, ((s1 + 32768) << 8) | (d0 + 1)); best = min(best, ((s2 + 32768) << 8) | (d0 + 2));
-    best = min(best, ((s3 + 32768) << 8) | (d0 + 3)); best = min(best, ((s4 + 32768) << 8) | (d0 + 4));
-    best = min(best, ((s5 + 32768) << 8) | (d0 + 5));
+template <int NPL>
+__device__ inline void wta_row16(const SgbmDims& dm, const int (&s)[NPL], int r, int nlive, size_t out_index, int4* __restrict__ rec, bool active) {
+    const int d0 = NPL * r;
+    int best = 0x7FFFFFFF;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) if (i < nlive) best = min(best, ((s[i] + 32768) << 8) | (d0 + i));
     best = row16_min(best);
     const int minS = (best >> 8) - 32768, bd = best & 0xFF;
     const int u = 100 - dm.uniq, lim = __mul24(minS, 100); // |S| < 2^15: 24-bit multiplies are exact (and full rate)
-    int bad = ((__mul24(s0, u) < lim && abs(bd - d0) > 1) || (__mul24(s1, u) < lim && abs(bd - d0 - 1) > 1) ||
-               (__mul24(s2, u) < lim && abs(bd - d0 - 2) > 1) || (__mul24(s3, u) < lim && abs(bd - d0 - 3) > 1) ||
-               (__mul24(s4, u) < lim && abs(bd - d0 - 4) > 1) || (__mul24(s5, u) < lim && abs(bd - d0 - 5) > 1)) ? 1 : 0;
-    bad = row16_max(bad);
-    const int sm_in = dpp_mov<0x111>(0, s5), sp_in = dpp_mov<0x101>(0, s0);
-    const int j = bd - d0;
-    if (active && j >= 0 && j < 6) { // the lane holding the winner
-        const int a[8] = {sm_in, s0, s1, s2, s3, s4, s5, sp_in};
-        int sm = a[0], sc = a[1], sp = a[2];
+    int bad = 0;
 #pragma unroll
-        for (int q = 1; q < 6; ++q) if (j == q) { sm = a[q]; sc = a[q + 1]; sp = a[q + 2]; }
+    for (int i = 0; i < NPL; ++i) bad |= (i < nlive && __mul24(s[i], u) < lim && abs(bd - d0 - i) > 1) ? 1 : 0;
+    bad = row16_max(bad);
+    const int sm_in = dpp_mov<0x111>(0, s[NPL - 1]), sp_in = dpp_mov<0x101>(0, s[0]);
+    const int j = bd - d0;
+    if (active && j >= 0 && j < NPL) { // the lane holding the winner
+        int sm = sm_in, sc = s[0], sp = s[1];
+#pragma unroll
+        for (int q = 1; q < NPL; ++q) if (j == q) { sm = s[q - 1]; sc = s[q]; sp = q + 1 < NPL ? s[q + 1 < NPL ? q + 1 : q] : sp_in; }
         rec[out_index] = make_int4(bad ? -1 : best, (int)pack16(sm, sc), sp, 0);
     }
 }
@@ -218,19 +247,10 @@ constexpr int kPathBlock = 64, kPathLines = kPathBlock / 16; // lines per workgr
 // Non-temporal loads / stores on the streamed volumes (every byte is touched once per kernel): the two diagonal paths gain 7-12 %
 // (1.90 -> 1.67, 1.74 -> 1.61 ms per 32 pairs), the two horizontal ones lose 3 % -- so NT loads are a property of the direction.  NT STORES
 // alone pay on the horizontal paths too (1.69 -> 1.65 ms for the left-to-right path): every path stores non-temporally.
-template <bool NT>
-__device__ inline U3 ld_u3(const void* p) {
-    if constexpr (NT) {
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-        return U3{__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + 1), __builtin_nontemporal_load(q + 2)}; // merged into one dwordx3 nt
-    } else return *reinterpret_cast<const U3*>(p);
-}
-__device__ inline void st_u3_nt(void* p, U3 v) {
-    uint32_t* q = reinterpret_cast<uint32_t*>(p);
-    __builtin_nontemporal_store(v.a, q); __builtin_nontemporal_store(v.b, q + 1); __builtin_nontemporal_store(v.c, q + 2);
-}
-template <int DX, int DY, int MODE, int kPathPF>
+template <int DX, int DY, int MODE, int NPL, int kPF, bool FULL>
 __global__ __launch_bounds__(kPathBlock) void sgbm_path_kernel(SgbmDims dm, const int16_t* __restrict__ C, uint16_t* T, int nlines, int4* __restrict__ rec) {
+    constexpr int NW = NPL / 2, Dp = NPL * 16;
+    static_assert(NPL % 2 == 0, "lane loads must stay dword-aligned");
     const int b = blockIdx.y;
     constexpr bool kNT = DX != 0 && DY != 0; // loads of the diagonal paths
     const int line = blockIdx.x * kPathLines + (threadIdx.x >> 4), r = threadIdx.x & 15;
@@ -243,61 +263,69 @@ __global__ __launch_bounds__(kPathBlock) void sgbm_path_kernel(SgbmDims dm, cons
         if (line < W1) { x0 = line; y0 = 0; } else { x0 = DX > 0 ? 0 : W1 - 1; y0 = line - W1 + 1; }
         len = min(DX > 0 ? W1 - x0 : x0 + 1, h - y0);
     }
-    const ptrdiff_t step = ((ptrdiff_t)DY * W1 + DX) * 96;
-    const size_t first = (((size_t)b * h + y0) * W1 + x0) * 96 + 6 * r;
+    const ptrdiff_t step = ((ptrdiff_t)DY * W1 + DX) * Dp;
+    const size_t first = (((size_t)b * h + y0) * W1 + x0) * Dp + NPL * r;
     const int16_t* cp = C + first;
     uint16_t* tp = T + first;
+    const int nlive = FULL ? NPL : min(max(dm.D - NPL * r, 0), NPL); // slots of this lane that are disparities of the volume
     // prefetch queue: loads are unconditional (indices clamped to the line) so that no wait is forced at the load site
-    U3 cq[kPathPF], tq[kPathPF];
+    UV<NW> cq[kPF], tq[kPF];
 #pragma unroll
-    for (int k = 0; k < kPathPF; ++k) {
+    for (int k = 0; k < kPF; ++k) {
         const ptrdiff_t o = (ptrdiff_t)min(k, len - 1) * step;
-        cq[k] = ld_u3<kNT>(cp + o);
-        tq[k] = MODE != 0 ? ld_u3<kNT>(tp + o) : U3{0, 0, 0};
+        cq[k] = ld_uv<kNT, NW>(cp + o);
+        if (MODE != 0) tq[k] = ld_uv<kNT, NW>(tp + o);
     }
-    int l0 = 0, l1 = 0, l2 = 0, l3 = 0, l4 = 0, l5 = 0, minPrev = 0;
-    const int P1 = dm.P1, P2 = dm.P2;
-    for (int s = 0; s < len; s += kPathPF) {
+    int l[NPL], minPrev = 0;
 #pragma unroll
-        for (int k = 0; k < kPathPF; ++k) {
+    for (int i = 0; i < NPL; ++i) l[i] = i < nlive ? 0 : kSent;
+    const int P1 = dm.P1, P2 = dm.P2, toff = dm.toff;
+    for (int s = 0; s < len; s += kPF) {
+#pragma unroll
+        for (int k = 0; k < kPF; ++k) {
+            const UV<NW> c = cq[k];
+            UV<NW> t = {};
+            if (MODE != 0) t = tq[k];
             {
-                const U3 c = cq[k], t = tq[k];
-                {
-                    const ptrdiff_t o = (ptrdiff_t)min(s + k + kPathPF, len - 1) * step;
-                    cq[k] = ld_u3<kNT>(cp + o);
-                    if (MODE != 0) tq[k] = ld_u3<kNT>(tp + o);
-                }
-                const int lm = dpp_mov<0x111>(kSent, l5); // row_shr:1 -- lane r-1's last disparity (d0 - 1)
-                const int lp = dpp_mov<0x101>(kSent, l0); // row_shl:1 -- lane r+1's first disparity (d5 + 1)
-                const int delta = minPrev + P2;
-                const int n0 = lo16s(c.a) - delta + min(min(l0, min(lm, l1) + P1), delta);
-                const int n1 = hi16s(c.a) - delta + min(min(l1, min(l0, l2) + P1), delta);
-                const int n2 = lo16s(c.b) - delta + min(min(l2, min(l1, l3) + P1), delta);
-                const int n3 = hi16s(c.b) - delta + min(min(l3, min(l2, l4) + P1), delta);
-                const int n4 = lo16s(c.c) - delta + min(min(l4, min(l3, l5) + P1), delta);
-                const int n5 = hi16s(c.c) - delta + min(min(l5, min(l4, lp) + P1), delta);
-                l0 = n0; l1 = n1; l2 = n2; l3 = n3; l4 = n4; l5 = n5;
-                minPrev = row16_min(min(min(min(n0, n1), min(n2, n3)), min(n4, n5)));
-                U3 o;
-                if (MODE == 0) {
-                    o.a = pack16(n0 + kTOffset, n1 + kTOffset); o.b = pack16(n2 + kTOffset, n3 + kTOffset); o.c = pack16(n4 + kTOffset, n5 + kTOffset);
-                } else if (MODE == 1) { // u16 wrap-around add: the true sum (+offset) always fits
-                    o.a = pack16((int)(t.a & 0xFFFFu) + n0, (int)(t.a >> 16) + n1);
-                    o.b = pack16((int)(t.b & 0xFFFFu) + n2, (int)(t.b >> 16) + n3);
-                    o.c = pack16((int)(t.c & 0xFFFFu) + n4, (int)(t.c >> 16) + n5);
-                } else if (MODE == 2) {
-                    o.a = pack16(sat16_dev((int)(t.a & 0xFFFFu) - kTOffset + n0), sat16_dev((int)(t.a >> 16) - kTOffset + n1));
-                    o.b = pack16(sat16_dev((int)(t.b & 0xFFFFu) - kTOffset + n2), sat16_dev((int)(t.b >> 16) - kTOffset + n3));
-                    o.c = pack16(sat16_dev((int)(t.c & 0xFFFFu) - kTOffset + n4), sat16_dev((int)(t.c >> 16) - kTOffset + n5));
-                } else {
-                    const int f0 = sat16_dev(lo16s(t.a) + n0), f1 = sat16_dev(hi16s(t.a) + n1), f2 = sat16_dev(lo16s(t.b) + n2);
-                    const int f3 = sat16_dev(hi16s(t.b) + n3), f4 = sat16_dev(lo16s(t.c) + n4), f5 = sat16_dev(hi16s(t.c) + n5);
-                    if (MODE == 3) { o.a = pack16(f0, f1); o.b = pack16(f2, f3); o.c = pack16(f4, f5); }
-                    else // last path: S is complete -- pick the winner here instead of storing it
-                        wta_row16(dm, f0, f1, f2, f3, f4, f5, r, ((size_t)b * h + y0) * dm.w + dm.minX1 + x0 + (s + k) * DX, rec, s + k < len);
-                }
-                if (MODE != 4 && s + k < len) st_u3_nt(tp + (ptrdiff_t)(s + k) * step, o);
+                const ptrdiff_t o = (ptrdiff_t)min(s + k + kPF, len - 1) * step;
+                cq[k] = ld_uv<kNT, NW>(cp + o);
+                if (MODE != 0) tq[k] = ld_uv<kNT, NW>(tp + o);
             }
+            const int lm = dpp_mov<0x111>(kSent, l[NPL - 1]); // row_shr:1 -- lane r-1's last disparity
+            const int lp = dpp_mov<0x101>(kSent, l[0]);       // row_shl:1 -- lane r+1's first disparity
+            const int delta = minPrev + P2;
+            int n[NPL], m = kSent;
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) {
+                const int dn = i > 0 ? l[i > 0 ? i - 1 : 0] : lm, up = i + 1 < NPL ? l[i + 1 < NPL ? i + 1 : i] : lp;
+                const int v = uv_get(c, i) - delta + min(min(l[i], min(dn, up) + P1), delta);
+                n[i] = i < nlive ? v : kSent;
+                m = min(m, n[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) l[i] = n[i];
+            minPrev = row16_min(m);
+            UV<NW> o;
+            if (MODE == 0) {
+#pragma unroll
+                for (int i = 0; i < NW; ++i) o.v[i] = pack16(n[2 * i] + toff, n[2 * i + 1] + toff);
+            } else if (MODE == 1) { // u16 wrap-around add: the true sum (+offset) always fits
+#pragma unroll
+                for (int i = 0; i < NW; ++i) o.v[i] = pack16(uv_getu(t, 2 * i) + n[2 * i], uv_getu(t, 2 * i + 1) + n[2 * i + 1]);
+            } else if (MODE == 2) {
+#pragma unroll
+                for (int i = 0; i < NW; ++i) o.v[i] = pack16(sat16_dev(uv_getu(t, 2 * i) - toff + n[2 * i]), sat16_dev(uv_getu(t, 2 * i + 1) - toff + n[2 * i + 1]));
+            } else {
+                int f[NPL];
+#pragma unroll
+                for (int i = 0; i < NPL; ++i) f[i] = sat16_dev(uv_get(t, i) + n[i]);
+                if (MODE == 3) {
+#pragma unroll
+                    for (int i = 0; i < NW; ++i) o.v[i] = pack16(f[2 * i], f[2 * i + 1]);
+                } else // last path: S is complete -- pick the winner here instead of storing it
+                    wta_row16<NPL>(dm, f, r, nlive, ((size_t)b * h + y0) * dm.w + dm.minX1 + x0 + (s + k) * DX, rec, s + k < len);
+            }
+            if (MODE != 4 && s + k < len) st_uv_nt<NW>(tp + (ptrdiff_t)(s + k) * step, o);
         }
     }
 }
@@ -460,9 +488,9 @@ __global__ __launch_bounds__(kFwRows * 16) void sgbm_forward_kernel(SgbmDims dm,
     stage_load(1);
     stage_store(0);
     __syncthreads();
-    U3 cq[kFwPF];
+    UV<3> cq[kFwPF];
 #pragma unroll
-    for (int k = 0; k < kFwPF; ++k) cq[k] = ld_u3<true>(cp + (size_t)min(max(k - 2 * row_l, 0), W1 - 1) * 96);
+    for (int k = 0; k < kFwPF; ++k) cq[k] = ld_uv<true, 3>(cp + (size_t)min(max(k - 2 * row_l, 0), W1 - 1) * 96);
     FwVec l10 = {{short2v{0, 0}, short2v{0, 0}, short2v{0, 0}}};
     const short2v P1v = {(short)dm.P1, (short)dm.P1};
     uint32_t nb_lo = (uint32_t)kSent | ((uint32_t)kSent << 16), nb_hi = nb_lo;
@@ -484,14 +512,14 @@ __global__ __launch_bounds__(kFwRows * 16) void sgbm_forward_kernel(SgbmDims dm,
             for (int k = 0; k < kFwPF; ++k) {
                 const int t = t0 + u0 + k, x = t - 2 * row_l;
                 const bool act = rowok && x >= 0 && x < W1;
-                const U3 c3 = cq[k];
-                cq[k] = ld_u3<true>(cp + (size_t)min(max(x + kFwPF, 0), W1 - 1) * 96);
+                const UV<3> c3 = cq[k];
+                cq[k] = ld_uv<true, 3>(cp + (size_t)min(max(x + kFwPF, 0), W1 - 1) * 96);
                 // what the row above left behind one step ago: its L of pixel x + 1
                 const uint32_t* src = row_l == 0 ? &sm.bnd[chunk & 1][(t & (kFwChunk - 1)) * kFwRecDw + r * 9] : &sm.slot[(t + 1) & 1][row_l - 1][r * 9];
                 uint32_t a[9];
 #pragma unroll
                 for (int q = 0; q < 9; ++q) a[q] = src[q];
-                const FwVec cv = fw_vec(c3.a, c3.b, c3.c);
+                const FwVec cv = fw_vec(c3.v[0], c3.v[1], c3.v[2]);
                 FwVec n10 = fw_path(l10, cv, P1v, P2, nb_lo, nb_hi);
                 const FwVec nm = fw_path(fw_vec(a[0], a[1], a[2]), cv, P1v, P2, nb_lo, nb_hi);           // (-1, 1): from (x + 1, y - 1), one step old
                 const FwVec n01 = fw_path(fw_vec(h01[0], h01[1], h01[2]), cv, P1v, P2, nb_lo, nb_hi);    // (0, 1):  from (x, y - 1), two steps old
@@ -504,11 +532,11 @@ __global__ __launch_bounds__(kFwRows * 16) void sgbm_forward_kernel(SgbmDims dm,
                     for (int q = 0; q < 3; ++q) { dst[q] = fw_u(nm.p[q]); dst[3 + q] = fw_u(n01.p[q]); dst[6 + q] = fw_u(n11.p[q]); }
                     l10 = n10;
                     // sat16 of the four-term sum: the two pair sums cannot overflow int16 (|L| < 2^14), one saturating add finishes
-                    U3 s3;
-                    s3.a = fw_u(__builtin_elementwise_add_sat(n10.p[0] + nm.p[0], n01.p[0] + n11.p[0]));
-                    s3.b = fw_u(__builtin_elementwise_add_sat(n10.p[1] + nm.p[1], n01.p[1] + n11.p[1]));
-                    s3.c = fw_u(__builtin_elementwise_add_sat(n10.p[2] + nm.p[2], n01.p[2] + n11.p[2]));
-                    st_u3_nt(sp + (size_t)x * 96, s3);
+                    UV<3> s3;
+                    s3.v[0] = fw_u(__builtin_elementwise_add_sat(n10.p[0] + nm.p[0], n01.p[0] + n11.p[0]));
+                    s3.v[1] = fw_u(__builtin_elementwise_add_sat(n10.p[1] + nm.p[1], n01.p[1] + n11.p[1]));
+                    s3.v[2] = fw_u(__builtin_elementwise_add_sat(n10.p[2] + nm.p[2], n01.p[2] + n11.p[2]));
+                    st_uv_nt<3>(sp + (size_t)x * 96, s3);
                     if (writer) {
                         uint32_t* wp = bnd_out + (x > 0 ? (size_t)(x - 1) * kFwRecDw : bnd_rec0);
 #pragma unroll
@@ -696,27 +724,27 @@ __global__ __launch_bounds__(kDnThreads) void sgbm_down_kernel(SgbmDims dm, cons
                 if (i >= dm.SH2) {
                     // (3) row y = i - SH2: C = acc (frozen over the last SH2 rows: no hsum arrives any more), vertical path, T
                     const int y = i - dm.SH2;
-                    U3 c;
-                    c.a = __builtin_bit_cast(uint32_t, acc[0]); c.b = __builtin_bit_cast(uint32_t, acc[1]); c.c = __builtin_bit_cast(uint32_t, acc[2]);
+                    UV<3> c;
+                    c.v[0] = __builtin_bit_cast(uint32_t, acc[0]); c.v[1] = __builtin_bit_cast(uint32_t, acc[1]); c.v[2] = __builtin_bit_cast(uint32_t, acc[2]);
                     if constexpr (WITH_PATH) {
                     const int lm = dpp_mov<0x111>(kSent, l5);
                     const int lp = dpp_mov<0x101>(kSent, l0);
                     const int delta = minPrev + P2;
-                    const int n0 = lo16s(c.a) - delta + min(min(l0, min(lm, l1) + P1), delta);
-                    const int n1 = hi16s(c.a) - delta + min(min(l1, min(l0, l2) + P1), delta);
-                    const int n2 = lo16s(c.b) - delta + min(min(l2, min(l1, l3) + P1), delta);
-                    const int n3 = hi16s(c.b) - delta + min(min(l3, min(l2, l4) + P1), delta);
-                    const int n4 = lo16s(c.c) - delta + min(min(l4, min(l3, l5) + P1), delta);
-                    const int n5 = hi16s(c.c) - delta + min(min(l5, min(l4, lp) + P1), delta);
+                    const int n0 = lo16s(c.v[0]) - delta + min(min(l0, min(lm, l1) + P1), delta);
+                    const int n1 = hi16s(c.v[0]) - delta + min(min(l1, min(l0, l2) + P1), delta);
+                    const int n2 = lo16s(c.v[1]) - delta + min(min(l2, min(l1, l3) + P1), delta);
+                    const int n3 = hi16s(c.v[1]) - delta + min(min(l3, min(l2, l4) + P1), delta);
+                    const int n4 = lo16s(c.v[2]) - delta + min(min(l4, min(l3, l5) + P1), delta);
+                    const int n5 = hi16s(c.v[2]) - delta + min(min(l5, min(l4, lp) + P1), delta);
                     l0 = n0; l1 = n1; l2 = n2; l3 = n3; l4 = n4; l5 = n5;
                     minPrev = row16_min(min(min(min(n0, n1), min(n2, n3)), min(n4, n5)));
                     if (live) {
-                        U3 o;
-                        o.a = pack16(n0 + kTOffset, n1 + kTOffset); o.b = pack16(n2 + kTOffset, n3 + kTOffset); o.c = pack16(n4 + kTOffset, n5 + kTOffset);
-                        st_u3_nt(C + vbase + (size_t)y * rstride, c);
-                        st_u3_nt(T + vbase + (size_t)y * rstride, o);
+                        UV<3> o;
+                        o.v[0] = pack16(n0 + kTOffset, n1 + kTOffset); o.v[1] = pack16(n2 + kTOffset, n3 + kTOffset); o.v[2] = pack16(n4 + kTOffset, n5 + kTOffset);
+                        st_uv_nt<3>(C + vbase + (size_t)y * rstride, c);
+                        st_uv_nt<3>(T + vbase + (size_t)y * rstride, o);
                     }
-                    } else if (live) st_u3_nt(C + vbase + (size_t)y * rstride, c);
+                    } else if (live) st_uv_nt<3>(C + vbase + (size_t)y * rstride, c);
                 }
             }
         }
@@ -724,15 +752,19 @@ __global__ __launch_bounds__(kDnThreads) void sgbm_down_kernel(SgbmDims dm, cons
 }
 
 // stand-alone winner-take-all over a stored S volume (MODE 3): one DPP row per pixel
+template <int NPL, bool FULL>
 __global__ __launch_bounds__(256) void sgbm_wta_kernel(SgbmDims dm, const uint16_t* __restrict__ S, int4* __restrict__ rec) {
     const int b = blockIdx.y;
     const size_t pixel = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int r = threadIdx.x & 15;
     const size_t npx = (size_t)dm.h * dm.width1;
     if (pixel >= npx) return;
-    const U3 v = *(const U3*)(S + ((size_t)b * npx + pixel) * 96 + 6 * r);
+    const UV<NPL / 2> v = ld_uv<false, NPL / 2>(S + ((size_t)b * npx + pixel) * (NPL * 16) + NPL * r);
+    int s[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) s[i] = uv_get(v, i);
     const int y = (int)(pixel / dm.width1), x = (int)(pixel - (size_t)y * dm.width1);
-    wta_row16(dm, lo16s(v.a), hi16s(v.a), lo16s(v.b), hi16s(v.b), lo16s(v.c), hi16s(v.c), r, ((size_t)b * dm.h + y) * dm.w + x + dm.minX1, rec, true);
+    wta_row16<NPL>(dm, s, r, FULL ? NPL : min(max(dm.D - NPL * r, 0), NPL), ((size_t)b * dm.h + y) * dm.w + x + dm.minX1, rec, true);
 }
 
 // ------------------------------------------------------------------------------------------- left-right check
@@ -879,318 +911,63 @@ __global__ __launch_bounds__(256) void sgbm_ccl_apply_kernel(int w, int h, int n
     if (out_f32) out_f32[g] = (float)d * 0.0625f; // convertTo(CV_32F, 1/16): exact
 }
 
-// ------------------------------------------------------------------------------------------- caller-set parameters: the general line-parallel chain
-// Any admissible vslam_sgbm_params other than the reference's runs prefilter -> sgbm_hsum_g -> sgbm_vsum_g -> sgbm_path_g x 5 (-> sgbm_wta_g)
-// -> lrcheck -> median -> CCL at EVERY batch size (the fused top-down / forward sweeps stay specialised for 96 disparities and the 9 x 9
-// window; profiles/sgbm_params.json records what that costs).  The cost volume's per-pixel stride is Dp = 16 * NPL int16, NPL = disparities per
-// lane of the 16-lane DPP row, one of 2 / 4 / 6 / 8 / 12 / 16: the smallest that holds D.  A lane slot with disparity >= D is padding: its
-// path value is forced to kSent after every step, so it behaves as the out-of-range neighbour of D - 1, never lowers the row minimum
-// (kSent > Cmax), never wins and never votes in the uniqueness test.  The running sum of the three downward paths is stored as u16 with the
-// offset 3 * P2 (L >= -P2 per path); vslam_sgbm_params_check's range rule 3 * (Cmax + P2) <= 65535 is what makes that, and kSent, exact.
-struct SgbmGDims { SgbmDims d; int Dp, toff; };
-__global__ __launch_bounds__(kHsBlock) void sgbm_hsum_g_kernel(SgbmGDims gd, const uint8_t* __restrict__ pre, int16_t* __restrict__ hsum) {
-    const SgbmDims& dm = gd.d;
-    const int b = blockIdx.z, y = blockIdx.y, j0 = blockIdx.x * kHsSeg;
-    const int Dp = gd.Dp, D = dm.D, SW2 = dm.SW2, nq = Dp >> 2, ng = Dp >> 3, ncol = kHsSeg + 2 * SW2;
-    extern __shared__ uint4 sgbm_gtile[]; // ncol x Dp bytes
-    uint8_t* tile = reinterpret_cast<uint8_t*>(sgbm_gtile);
-    const uint8_t* L = pre + (((size_t)(2 * b) * dm.h + y) * 6) * dm.w;
-    const uint8_t* R = pre + (((size_t)(2 * b + 1) * dm.h + y) * 6) * dm.w;
-    const int W1 = dm.width1, w = dm.w;
-    for (int it = threadIdx.x; it < ncol * nq; it += kHsBlock) {
-        const int t = it / nq, q = it - t * nq, d = 4 * q;
-        uint32_t out = 0;
-        if (d < D) { // (D is a multiple of 16: the whole quad is inside; x - d - 3 >= minX1 - D + 1 > 0)
-            const int jj = min(max(j0 - SW2 + t, 0), W1 - 1), x = dm.minX1 + jj;
-            uint32_t acc[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                const uint8_t* lp = L + 3 * c * w; const uint8_t* rp = R + 3 * c * w;
-                const int u = lp[x], u0 = lp[w + x], u1 = lp[2 * w + x];
-                const uint32_t vv = ld_u32_unaligned(rp + x - d - 3), v0v = ld_u32_unaligned(rp + w + x - d - 3), v1v = ld_u32_unaligned(rp + 2 * w + x - d - 3);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { // disparity d + i <-> byte 3 - i
-                    const int sh = 8 * (3 - i);
-                    const int v = (vv >> sh) & 255, v0 = (v0v >> sh) & 255, v1 = (v1v >> sh) & 255;
-                    const int c0 = max(max(0, u - v1), v0 - u), c1 = max(max(0, v - u1), u0 - v);
-                    acc[i] += (uint32_t)(min(c0, c1) >> (c == 0 ? 0 : 2));
-                }
-            }
-            out = acc[0] | (acc[1] << 8) | (acc[2] << 16) | (acc[3] << 24); // each <= 2 * ftzero + 63 <= 189
-        }
-        *(uint32_t*)(tile + t * Dp + d) = out;
-    }
-    __syncthreads();
-    for (int it = threadIdx.x; it < kHsSeg * ng; it += kHsBlock) {
-        const int t = it / ng, g = it - t * ng;
-        if (j0 + t >= W1) continue;
-        uint32_t e0 = 0, o0 = 0, e1 = 0, o1 = 0; // block_size taps of <= 189: no carry between the packed u16 halves
-        for (int i = 0; i <= 2 * SW2; ++i) {
-            const uint2 v = *(const uint2*)(tile + (t + i) * Dp + 8 * g);
-            e0 += v.x & 0x00FF00FFu; o0 += (v.x >> 8) & 0x00FF00FFu;
-            e1 += v.y & 0x00FF00FFu; o1 += (v.y >> 8) & 0x00FF00FFu;
-        }
-        uint4 o;
-        o.x = (e0 & 0xFFFFu) | (o0 << 16); o.y = (e0 >> 16) | (o0 & 0xFFFF0000u);
-        o.z = (e1 & 0xFFFFu) | (o1 << 16); o.w = (e1 >> 16) | (o1 & 0xFFFF0000u);
-        *(uint4*)(hsum + (((size_t)b * dm.h + y) * W1 + j0 + t) * Dp + 8 * g) = o;
-    }
-}
-
-__global__ __launch_bounds__(256) void sgbm_vsum_g_kernel(SgbmGDims gd, const int16_t* __restrict__ hsum, int16_t* __restrict__ C) {
-    const SgbmDims& dm = gd.d;
-    const int b = blockIdx.z, ya = blockIdx.y * kVsChunk, yb = min(ya + kVsChunk, dm.h), ng = gd.Dp >> 3;
-    const int it = blockIdx.x * 256 + threadIdx.x; // (j, g): 8 disparities
-    if (it >= dm.width1 * ng) return;
-    const int j = it / ng;
-    const size_t rs = (size_t)dm.width1 * gd.Dp; // row stride (elements)
-    const int16_t* hp = hsum + (size_t)b * dm.h * rs + (size_t)it * 8;
-    int16_t* cp = C + (size_t)b * dm.h * rs + (size_t)it * 8;
-    const int ylast = j == 0 ? 0 : dm.h - 1 - dm.SH2; // last row whose window is evaluated
-    const int yy = min(ya, ylast);
-    S8 acc = *(const S8*)(hp + (size_t)max(yy - dm.SH2, 0) * rs);
-    for (int k = yy - dm.SH2 + 1; k <= yy + dm.SH2; ++k) acc = s8_add(acc, *(const S8*)(hp + (size_t)max(k, 0) * rs));
-#pragma unroll 4
-    for (int y = ya; y < yb; ++y) {
-        *(S8*)(cp + (size_t)y * rs) = acc;
-        if (y + 1 <= ylast) acc = s8_sub(s8_add(acc, *(const S8*)(hp + (size_t)(y + 1 + dm.SH2) * rs)), *(const S8*)(hp + (size_t)max(y - dm.SH2, 0) * rs));
-    }
-}
-
-template <int N> struct alignas(4) UV { uint32_t v[N]; };
-template <bool NT, int N>
-__device__ inline UV<N> ld_uv(const void* p) {
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    UV<N> r;
-#pragma unroll
-    for (int i = 0; i < N; ++i) r.v[i] = NT ? __builtin_nontemporal_load(q + i) : q[i];
-    return r;
-}
-template <int N>
-__device__ inline void st_uv_nt(void* p, const UV<N>& v) {
-    uint32_t* q = reinterpret_cast<uint32_t*>(p);
-#pragma unroll
-    for (int i = 0; i < N; ++i) __builtin_nontemporal_store(v.v[i], q + i);
-}
-template <int N> __device__ inline int uv_get(const UV<N>& v, int i) { return (i & 1) ? hi16s(v.v[i >> 1]) : lo16s(v.v[i >> 1]); }
-template <int N> __device__ inline int uv_getu(const UV<N>& v, int i) { return (i & 1) ? (int)(v.v[i >> 1] >> 16) : (int)(v.v[i >> 1] & 0xFFFFu); }
-
-// wta_row16 with NPL disparities per lane, of which the first `nlive` are real (disparity < D)
-template <int NPL>
-__device__ inline void wta_row16_g(const SgbmDims& dm, const int (&s)[NPL], int r, int nlive, size_t out_index, int4* __restrict__ rec, bool active) {
-    const int d0 = NPL * r;
-    int best = 0x7FFFFFFF;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) if (i < nlive) best = min(best, ((s[i] + 32768) << 8) | (d0 + i));
-    best = row16_min(best);
-    const int minS = (best >> 8) - 32768, bd = best & 0xFF;
-    const int u = 100 - dm.uniq, lim = __mul24(minS, 100);
-    int bad = 0;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) bad |= (i < nlive && __mul24(s[i], u) < lim && abs(bd - d0 - i) > 1) ? 1 : 0;
-    bad = row16_max(bad);
-    const int sm_in = dpp_mov<0x111>(0, s[NPL - 1]), sp_in = dpp_mov<0x101>(0, s[0]);
-    const int j = bd - d0;
-    if (active && j >= 0 && j < NPL) { // the lane holding the winner
-        int sm = sm_in, sc = s[0], sp = s[1];
-#pragma unroll
-        for (int q = 1; q < NPL; ++q) if (j == q) { sm = s[q - 1]; sc = s[q]; sp = q + 1 < NPL ? s[q + 1 < NPL ? q + 1 : q] : sp_in; }
-        rec[out_index] = make_int4(bad ? -1 : best, (int)pack16(sm, sc), sp, 0);
-    }
-}
-
-template <int DX, int DY, int MODE, int NPL, int kPF>
-__global__ __launch_bounds__(kPathBlock) void sgbm_path_g_kernel(SgbmGDims gd, const int16_t* __restrict__ C, uint16_t* T, int nlines, int4* __restrict__ rec) {
-    const SgbmDims& dm = gd.d;
-    constexpr int NW = NPL / 2, Dp = NPL * 16;
-    static_assert(NPL % 2 == 0, "lane loads must stay dword-aligned");
-    const int b = blockIdx.y;
-    constexpr bool kNT = DX != 0 && DY != 0;
-    const int line = blockIdx.x * kPathLines + (threadIdx.x >> 4), r = threadIdx.x & 15;
-    if (line >= nlines) return; // whole DPP row leaves
-    const int W1 = dm.width1, h = dm.h;
-    int x0, y0, len;
-    if (DY == 0) { y0 = line; x0 = DX > 0 ? 0 : W1 - 1; len = W1; }
-    else if (DX == 0) { x0 = line; y0 = 0; len = h; }
-    else {
-        if (line < W1) { x0 = line; y0 = 0; } else { x0 = DX > 0 ? 0 : W1 - 1; y0 = line - W1 + 1; }
-        len = min(DX > 0 ? W1 - x0 : x0 + 1, h - y0);
-    }
-    const ptrdiff_t step = ((ptrdiff_t)DY * W1 + DX) * Dp;
-    const size_t first = (((size_t)b * h + y0) * W1 + x0) * Dp + NPL * r;
-    const int16_t* cp = C + first;
-    uint16_t* tp = T + first;
-    const int nlive = min(max(dm.D - NPL * r, 0), NPL); // slots of this lane that are disparities of the volume
-    UV<NW> cq[kPF], tq[kPF];
-#pragma unroll
-    for (int k = 0; k < kPF; ++k) {
-        const ptrdiff_t o = (ptrdiff_t)min(k, len - 1) * step;
-        cq[k] = ld_uv<kNT, NW>(cp + o);
-        if (MODE != 0) tq[k] = ld_uv<kNT, NW>(tp + o);
-    }
-    int l[NPL], minPrev = 0;
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) l[i] = i < nlive ? 0 : kSent;
-    const int P1 = dm.P1, P2 = dm.P2, toff = gd.toff;
-    for (int s = 0; s < len; s += kPF) {
-#pragma unroll
-        for (int k = 0; k < kPF; ++k) {
-            const UV<NW> c = cq[k];
-            UV<NW> t = {};
-            if (MODE != 0) t = tq[k];
-            {
-                const ptrdiff_t o = (ptrdiff_t)min(s + k + kPF, len - 1) * step;
-                cq[k] = ld_uv<kNT, NW>(cp + o);
-                if (MODE != 0) tq[k] = ld_uv<kNT, NW>(tp + o);
-            }
-            const int lm = dpp_mov<0x111>(kSent, l[NPL - 1]); // row_shr:1 -- lane r-1's last disparity
-            const int lp = dpp_mov<0x101>(kSent, l[0]);       // row_shl:1 -- lane r+1's first disparity
-            const int delta = minPrev + P2;
-            int n[NPL], m = kSent;
-#pragma unroll
-            for (int i = 0; i < NPL; ++i) {
-                const int dn = i > 0 ? l[i > 0 ? i - 1 : 0] : lm, up = i + 1 < NPL ? l[i + 1 < NPL ? i + 1 : i] : lp;
-                const int v = uv_get(c, i) - delta + min(min(l[i], min(dn, up) + P1), delta);
-                n[i] = i < nlive ? v : kSent;
-                m = min(m, n[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < NPL; ++i) l[i] = n[i];
-            minPrev = row16_min(m);
-            UV<NW> o;
-            if (MODE == 0) {
-#pragma unroll
-                for (int i = 0; i < NW; ++i) o.v[i] = pack16(n[2 * i] + toff, n[2 * i + 1] + toff);
-            } else if (MODE == 1) { // u16 wrap-around add: the true sum (+offset) always fits
-#pragma unroll
-                for (int i = 0; i < NW; ++i) o.v[i] = pack16(uv_getu(t, 2 * i) + n[2 * i], uv_getu(t, 2 * i + 1) + n[2 * i + 1]);
-            } else if (MODE == 2) {
-#pragma unroll
-                for (int i = 0; i < NW; ++i) o.v[i] = pack16(sat16_dev(uv_getu(t, 2 * i) - toff + n[2 * i]), sat16_dev(uv_getu(t, 2 * i + 1) - toff + n[2 * i + 1]));
-            } else {
-                int f[NPL];
-#pragma unroll
-                for (int i = 0; i < NPL; ++i) f[i] = sat16_dev(uv_get(t, i) + n[i]);
-                if (MODE == 3) {
-#pragma unroll
-                    for (int i = 0; i < NW; ++i) o.v[i] = pack16(f[2 * i], f[2 * i + 1]);
-                } else // last path: S is complete -- pick the winner here instead of storing it
-                    wta_row16_g<NPL>(dm, f, r, nlive, ((size_t)b * h + y0) * dm.w + dm.minX1 + x0 + (s + k) * DX, rec, s + k < len);
-            }
-            if (MODE != 4 && s + k < len) st_uv_nt<NW>(tp + (ptrdiff_t)(s + k) * step, o);
-        }
-    }
-}
-
-template <int NPL>
-__global__ __launch_bounds__(256) void sgbm_wta_g_kernel(SgbmGDims gd, const uint16_t* __restrict__ S, int4* __restrict__ rec) {
-    const SgbmDims& dm = gd.d;
-    const int b = blockIdx.y;
-    const size_t pixel = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-    const int r = threadIdx.x & 15;
-    const size_t npx = (size_t)dm.h * dm.width1;
-    if (pixel >= npx) return;
-    const UV<NPL / 2> v = ld_uv<false, NPL / 2>(S + ((size_t)b * npx + pixel) * (NPL * 16) + NPL * r);
-    int s[NPL];
-#pragma unroll
-    for (int i = 0; i < NPL; ++i) s[i] = uv_get(v, i);
-    const int y = (int)(pixel / dm.width1), x = (int)(pixel - (size_t)y * dm.width1);
-    wta_row16_g<NPL>(dm, s, r, min(max(dm.D - NPL * r, 0), NPL), ((size_t)b * dm.h + y) * dm.w + x + dm.minX1, rec, true);
-}
-
-// the five paths (+ the stand-alone winner-take-all below 4 pairs, as in the default chain) for one lane width
-template <int NPL>
-static void launch_paths_g(const SgbmGDims& gd, int B, const int16_t* C, uint16_t* T, int4* rec, hipStream_t stream) {
-    const SgbmDims& dm = gd.d;
+// ------------------------------------------------------------------------------------------- host driver
+// the line kernels' paths from number `first` on -- (0,1), (1,1), (-1,1), (1,0), (-1,0); a fused sweep has done the ones before -- and, below 4
+// pairs, the stand-alone winner-take-all, for one lane width
+template <int NPL, bool FULL>
+static void launch_paths(const SgbmDims& dm, int first, int B, const int16_t* C, uint16_t* T, int4* rec, hipStream_t stream) {
     constexpr int kPv = NPL <= 8 ? 8 : 4, kPh = NPL <= 6 ? 16 : (NPL <= 8 ? 8 : 4); // prefetch depth: the queues stay in registers at every lane width
     const int nv = dm.width1, nd = dm.width1 + dm.h - 1, h = dm.h;
     const dim3 gv((nv + kPathLines - 1) / kPathLines, B), gdg((nd + kPathLines - 1) / kPathLines, B), gh((h + kPathLines - 1) / kPathLines, B);
-    { ProfScope p(stream, "sgbm_path_g_kernel<0,1>"); hipLaunchKernelGGL((sgbm_path_g_kernel<0, 1, 0, NPL, kPv>), gv, dim3(kPathBlock), 0, stream, gd, C, T, nv, (int4*)nullptr); }
-    { ProfScope p(stream, "sgbm_path_g_kernel<1,1>"); hipLaunchKernelGGL((sgbm_path_g_kernel<1, 1, 1, NPL, kPv>), gdg, dim3(kPathBlock), 0, stream, gd, C, T, nd, (int4*)nullptr); }
-    { ProfScope p(stream, "sgbm_path_g_kernel<-1,1>"); hipLaunchKernelGGL((sgbm_path_g_kernel<-1, 1, 1, NPL, kPv>), gdg, dim3(kPathBlock), 0, stream, gd, C, T, nd, (int4*)nullptr); }
-    { ProfScope p(stream, "sgbm_path_g_kernel<1,0>"); hipLaunchKernelGGL((sgbm_path_g_kernel<1, 0, 2, NPL, kPh>), gh, dim3(kPathBlock), 0, stream, gd, C, T, h, (int4*)nullptr); }
-    if (B >= 4) { ProfScope p(stream, "sgbm_path_g_kernel<-1,0>"); hipLaunchKernelGGL((sgbm_path_g_kernel<-1, 0, 4, NPL, kPh>), gh, dim3(kPathBlock), 0, stream, gd, C, T, h, rec); }
+    if (first <= 0) { ProfScope p(stream, "sgbm_path_kernel<0,1>"); hipLaunchKernelGGL((sgbm_path_kernel<0, 1, 0, NPL, kPv, FULL>), gv, dim3(kPathBlock), 0, stream, dm, C, T, nv, (int4*)nullptr); }
+    if (first <= 1) { ProfScope p(stream, "sgbm_path_kernel<1,1>"); hipLaunchKernelGGL((sgbm_path_kernel<1, 1, 1, NPL, kPv, FULL>), gdg, dim3(kPathBlock), 0, stream, dm, C, T, nd, (int4*)nullptr); }
+    if (first <= 2) { ProfScope p(stream, "sgbm_path_kernel<-1,1>"); hipLaunchKernelGGL((sgbm_path_kernel<-1, 1, 1, NPL, kPv, FULL>), gdg, dim3(kPathBlock), 0, stream, dm, C, T, nd, (int4*)nullptr); }
+    if (first <= 3) { ProfScope p(stream, "sgbm_path_kernel<1,0>"); hipLaunchKernelGGL((sgbm_path_kernel<1, 0, 2, NPL, kPh, FULL>), gh, dim3(kPathBlock), 0, stream, dm, C, T, h, (int4*)nullptr); }
+    if (B >= 4) { ProfScope p(stream, "sgbm_path_kernel<-1,0>"); hipLaunchKernelGGL((sgbm_path_kernel<-1, 0, 4, NPL, kPh, FULL>), gh, dim3(kPathBlock), 0, stream, dm, C, T, h, rec); }
     else {
-        { ProfScope p(stream, "sgbm_path_g_kernel<-1,0>"); hipLaunchKernelGGL((sgbm_path_g_kernel<-1, 0, 3, NPL, kPh>), gh, dim3(kPathBlock), 0, stream, gd, C, T, h, (int4*)nullptr); }
-        { ProfScope p(stream, "sgbm_wta_g_kernel"); hipLaunchKernelGGL(sgbm_wta_g_kernel<NPL>, dim3((unsigned)(((size_t)h * dm.width1 + 15) / 16), B), dim3(256), 0, stream, gd, T, rec); }
+        { ProfScope p(stream, "sgbm_path_kernel<-1,0>"); hipLaunchKernelGGL((sgbm_path_kernel<-1, 0, 3, NPL, kPh, FULL>), gh, dim3(kPathBlock), 0, stream, dm, C, T, h, (int4*)nullptr); }
+        { ProfScope p(stream, "sgbm_wta_kernel"); hipLaunchKernelGGL((sgbm_wta_kernel<NPL, FULL>), dim3((unsigned)(((size_t)h * dm.width1 + 15) / 16), B), dim3(256), 0, stream, dm, T, rec); }
     }
 }
-
-// ------------------------------------------------------------------------------------------- host driver
-static int launch_sgbm_general(const vslam_sgbm_params& sp, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B,
-                               float* d_disp_f32, int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream) {
-    SgbmGDims gd;
-    SgbmDims& dm = gd.d;
-    const int D = sp.num_disparities, npl16 = D / 16;
-    const int npl = npl16 <= 2 ? 2 : (npl16 <= 4 ? 4 : (npl16 <= 6 ? 6 : (npl16 <= 8 ? 8 : (npl16 <= 12 ? 12 : 16))));
-    dm.w = w; dm.h = h; dm.D = D; dm.minX1 = D; dm.width1 = w - D; dm.P1 = sp.P1; dm.P2 = sp.P2; dm.SW2 = dm.SH2 = sp.block_size / 2; dm.uniq = sp.uniqueness_ratio;
-    dm.disp12 = sp.disp12_max_diff; dm.ftzero = max(sp.pre_filter_cap, 15) | 1; dm.pitch = pitch; dm.img_bytes = img_bytes;
-    gd.Dp = 16 * npl; gd.toff = 3 * sp.P2;
-    const size_t vol = (size_t)h * dm.width1 * gd.Dp, npix = (size_t)w * h;
-    int* hdr; uint8_t* pre; int16_t *hsum, *C, *d0, *d1; int4* rec; int *par, *cnt;
-    if (int rc = carve(scratch, stream, [&](Layout& L) {
-            hdr = L.take<int>(64); // the header of the default chain: its error word is this launch's too (cleared, never set)
-            pre = L.take<uint8_t>((size_t)2 * B * h * 6 * w);
-            hsum = L.take<int16_t>(B * vol);
-            C = L.take<int16_t>(B * vol);
-            rec = L.take<int4>(B * npix);
-            d0 = L.take<int16_t>(B * npix);
-            d1 = L.take<int16_t>(B * npix);
-            par = L.take<int>(B * npix);
-            cnt = L.take<int>(B * npix);
-        })) return rc;
-    uint16_t* T = (uint16_t*)hsum; // hsum is dead once C exists
-    VS_HIP(hipMemsetAsync(hdr, 0, 64, stream));
-    { ProfScope p(stream, "sgbm_prefilter_kernel"); hipLaunchKernelGGL(sgbm_prefilter_kernel, dim3((w + 255) / 256, h, 2 * B), dim3(256), 0, stream, dm, d_left, d_right, pre); }
-    { ProfScope p(stream, "sgbm_hsum_g_kernel");
-      hipLaunchKernelGGL(sgbm_hsum_g_kernel, dim3((dm.width1 + kHsSeg - 1) / kHsSeg, h, B), dim3(kHsBlock), (size_t)(kHsSeg + 2 * dm.SW2) * gd.Dp, stream, gd, pre, hsum); }
-    { ProfScope p(stream, "sgbm_vsum_g_kernel");
-      hipLaunchKernelGGL(sgbm_vsum_g_kernel, dim3((dm.width1 * (gd.Dp / 8) + 255) / 256, (h + kVsChunk - 1) / kVsChunk, B), dim3(256), 0, stream, gd, hsum, C); }
-    switch (npl) {
-        case 2: launch_paths_g<2>(gd, B, C, T, rec, stream); break;
-        case 4: launch_paths_g<4>(gd, B, C, T, rec, stream); break;
-        case 6: launch_paths_g<6>(gd, B, C, T, rec, stream); break;
-        case 8: launch_paths_g<8>(gd, B, C, T, rec, stream); break;
-        case 12: launch_paths_g<12>(gd, B, C, T, rec, stream); break;
-        default: launch_paths_g<16>(gd, B, C, T, rec, stream); break;
-    }
-    { ProfScope p(stream, "sgbm_lrcheck_kernel");
-      hipLaunchKernelGGL(sgbm_lrcheck_kernel, dim3(h, B), dim3(kLrBlock), (size_t)(w + (w + 1) / 2) * sizeof(int), stream, dm, rec, d0); }
-    if (d_disp_raw) VS_HIP(hipMemcpyAsync(d_disp_raw, d0, (size_t)B * npix * 2, hipMemcpyDeviceToDevice, stream));
-    { ProfScope p(stream, "sgbm_median3_kernel"); hipLaunchKernelGGL(sgbm_median3_kernel, dim3((w + 255) / 256, h, B), dim3(256), 0, stream, w, h, d0, d1); }
-    const int pblocks = (int)((npix + 255) / 256);
-    // speckle_window_size 0 = no filter: a size threshold of 0 removes no component.  Disparities are int16: a range beyond 4096 joins everything.
-    const int newVal = -16, maxDiff = 16 * min(sp.speckle_range, 4096), maxSize = sp.speckle_window_size;
-    { ProfScope p(stream, "sgbm_ccl_kernels", 4);
-      hipLaunchKernelGGL(sgbm_ccl_rows_kernel, dim3(h, B), dim3(kCclBlock), (size_t)2 * w * sizeof(int), stream, w, h, maxDiff, newVal, d1, par, cnt);
-      hipLaunchKernelGGL(sgbm_ccl_union_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, maxDiff, newVal, d1, par);
-      hipLaunchKernelGGL(sgbm_ccl_count_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, maxDiff, newVal, d1, par, cnt);
-      hipLaunchKernelGGL(sgbm_ccl_apply_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, newVal, maxSize, par, cnt, d1, d_disp_f32, d_disp_i16); }
-    VS_HIP(hipGetLastError());
-    return VSLAM_OK;
+template <int NPL>
+static void launch_paths(const SgbmDims& dm, int first, int B, const int16_t* C, uint16_t* T, int4* rec, hipStream_t stream) {
+    if (dm.D == 16 * NPL) launch_paths<NPL, true>(dm, first, B, C, T, rec, stream);
+    else launch_paths<NPL, false>(dm, first, B, C, T, rec, stream);
 }
 
-// sp has passed vslam_sgbm_params_check for (w, h) (the API entries run it before anything is launched).  The reference's own set keeps the
-// kernels and the batch-size dispatch it has always had; every other set runs the general chain.
+static SgbmDims sgbm_dims(const vslam_sgbm_params& sp, bool reference_set, int w, int h, int pitch, size_t img_bytes) {
+    const int D = sp.num_disparities, n16 = D / 16;
+    const int npl = n16 <= 2 ? 2 : (n16 <= 4 ? 4 : (n16 <= 6 ? 6 : (n16 <= 8 ? 8 : (n16 <= 12 ? 12 : 16))));
+    SgbmDims dm;
+    dm.w = w; dm.h = h; dm.D = D; dm.Dp = 16 * npl; dm.minX1 = D; dm.width1 = w - D; dm.P1 = sp.P1; dm.P2 = sp.P2; dm.toff = reference_set ? kTOffset : 3 * sp.P2;
+    dm.SW2 = dm.SH2 = sp.block_size / 2; dm.uniq = sp.uniqueness_ratio; dm.disp12 = sp.disp12_max_diff; dm.ftzero = max(sp.pre_filter_cap, 15) | 1;
+    dm.pitch = pitch; dm.img_bytes = img_bytes;
+    return dm;
+}
+
+// sp has passed vslam_sgbm_params_check for (w, h) (the API entries run it before anything is launched).  The reference's own set
+// (visual_odometry.cpp:163-164) keeps the batch-size dispatch it has always had; every other set runs the line kernels at every batch size.
 int launch_sgbm(const Tuning& tune, const vslam_sgbm_params& sp, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B,
                 float* d_disp_f32, int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream) {
     if (B <= 0) return VSLAM_OK;
     const bool reference_set = sp.num_disparities == 96 && sp.block_size == 9 && sp.P1 == 8 * 9 * 9 && sp.P2 == 32 * 9 * 9 && sp.disp12_max_diff == 1 &&
                                sp.pre_filter_cap == 63 && sp.uniqueness_ratio == 10 && sp.speckle_window_size == 100 && sp.speckle_range == 32;
-    if (!reference_set) return launch_sgbm_general(sp, d_left, d_right, img_bytes, pitch, w, h, B, d_disp_f32, d_disp_i16, d_disp_raw, scratch, stream);
-    SgbmDims dm;
-    dm.w = w; dm.h = h; dm.D = 96; dm.minX1 = 96; dm.width1 = w - 96; dm.P1 = 8 * 9 * 9; dm.P2 = 32 * 9 * 9; dm.SW2 = 4; dm.SH2 = 4; dm.uniq = 10;
-    dm.disp12 = 1; dm.ftzero = 63; dm.pitch = pitch; dm.img_bytes = img_bytes; // visual_odometry.cpp:163-164
-    // width1 <= SW2 is undefined in OpenCV 3.2 (unclamped read of pixel-cost columns 0..SW2), so it is an argument error here.
-    if (dm.width1 <= dm.SW2 || h <= 2 * dm.SH2 + 1 || w > 4096) { set_error("image size unsupported (need 100 < w <= 4096, h > 9)"); return VSLAM_ERR_ARG; }
-    const size_t vol = (size_t)h * dm.width1 * dm.D, npix = (size_t)w * h;
+    const SgbmDims dm = sgbm_dims(sp, reference_set, w, h, pitch, img_bytes);
+    const size_t vol = (size_t)h * dm.width1 * dm.Dp, npix = (size_t)w * h;
+    // The fused top-down kernel sweeps the rows sequentially with 48 workgroups per pair: it pays from 8 pairs per call on (2.65 vs 4.08 ms
+    // at 32 pairs); below that the three massively parallel kernels it replaces are faster (0.99 vs 1.31 ms for one pair).
+    // Tuning::sgbm_fuse_min overrides the threshold (tests run both paths).
+    const bool fused = reference_set && B >= (tune.sgbm_fuse_min >= 0 ? tune.sgbm_fuse_min : 8);
+    // ... and from there on the four forward paths run as one wavefront sweep (sgbm_forward_kernel) instead of one kernel per path.
+    // The slabs of a pair are a chain (about 2200 sequential steps): it pays from 16 pairs per call on.  Tuning::sgbm_fwd_min overrides.
+    const bool fwd = fused && B >= (tune.sgbm_fwd_min >= 0 ? tune.sgbm_fwd_min : 16);
     // forward sweep: 32-row slabs (workgroups of 512 threads, two per CU) up to 32 pairs, 64-row slabs above.  The slabs of a pair are a chain
     // of ~2 200 (64 rows) / ~2 600 (32 rows) steps and a step's time is mostly its latency (barrier, LDS mailbox, the dependent minimum ->
     // delta -> update chain), so shorter workgroups win until the chip is full: 16 / 24 / 32 / 40 pairs 2.33 / 2.60 / 2.93 / 3.45 ms with 32
     // rows, 3.01 / 3.06 / 3.19 / 3.35 ms with 64 (48-row slabs: 2.64 / 2.76 / 2.92 / 3.31 -- no better anywhere).  Tuning::sgbm_fw_rows overrides.
     const int fw_rows = tune.sgbm_fw_rows > 0 ? tune.sgbm_fw_rows : (B <= 32 ? 32 : 64);
     const int nslab = (h + fw_rows - 1) / fw_rows;
-    int* hdr; uint8_t* pre; int16_t *hsum, *C, *d0, *d1; int4* rec; int *par, *cnt, *flag; uint32_t* bnd;
+    int* hdr; uint8_t* pre; int16_t *hsum, *C, *d0, *d1; int4* rec; int *par, *cnt, *flag = nullptr; uint32_t* bnd = nullptr;
     if (int rc = carve(scratch, stream, [&](Layout& L) {
             hdr = L.take<int>(64); // int32 [0, kSgbmErrorWord): ticket pools of the forward sweep, [kSgbmErrorWord]: its error word
             pre = L.take<uint8_t>((size_t)2 * B * h * 6 * w);
@@ -1201,45 +978,49 @@ int launch_sgbm(const Tuning& tune, const vslam_sgbm_params& sp, const uint8_t* 
             d1 = L.take<int16_t>(B * npix);
             par = L.take<int>(B * npix);
             cnt = L.take<int>(B * npix);
-            bnd = L.take<uint32_t>((size_t)B * (nslab > 1 ? nslab - 1 : 1) * ((dm.width1 + kFwChunk - 1) / kFwChunk + 1) * kFwChunk * kFwRecDw);
-            flag = L.take<int>((size_t)B * nslab);
+            if (fwd) {
+                bnd = L.take<uint32_t>((size_t)B * (nslab > 1 ? nslab - 1 : 1) * ((dm.width1 + kFwChunk - 1) / kFwChunk + 1) * kFwChunk * kFwRecDw);
+                flag = L.take<int>((size_t)B * nslab);
+            }
         })) return rc;
     uint16_t* T = (uint16_t*)hsum; // hsum is dead once C exists: T reuses its storage (the fused top-down pass never materialises hsum at all)
     VS_HIP(hipMemsetAsync(hdr, 0, 64, stream)); // ticket pools + error word of this launch
     { ProfScope p(stream, "sgbm_prefilter_kernel"); hipLaunchKernelGGL(sgbm_prefilter_kernel, dim3((w + 255) / 256, h, 2 * B), dim3(256), 0, stream, dm, d_left, d_right, pre); }
-    // The fused top-down kernel sweeps the rows sequentially with 48 workgroups per pair: it pays from 8 pairs per call on (2.65 vs 4.08 ms
-    // at 32 pairs); below that the three massively parallel kernels it replaces are faster (0.99 vs 1.31 ms for one pair).
-    // Tuning::sgbm_fuse_min overrides the threshold (tests run both paths).
-    const bool unfused = B < (tune.sgbm_fuse_min >= 0 ? tune.sgbm_fuse_min : 8);
-    // ... and from there on the four forward paths run as one wavefront sweep (sgbm_forward_kernel) instead of one kernel per path.
-    // The slabs of a pair are a chain (about 2200 sequential steps): it pays from 16 pairs per call on.  Tuning::sgbm_fwd_min overrides.
-    const bool fwd = !unfused && B >= (tune.sgbm_fwd_min >= 0 ? tune.sgbm_fwd_min : 16);
-    if (!unfused && !fwd) { ProfScope p(stream, "sgbm_down_kernel"); hipLaunchKernelGGL(sgbm_down_kernel<true>, dim3((dm.width1 + kDnCols - 1) / kDnCols, B), dim3(kDnThreads), 0, stream, dm, pre, C, T); }
+    int first = 0; // paths the fused sweeps have done
     if (fwd) {
         { ProfScope p(stream, "sgbm_down_kernel"); hipLaunchKernelGGL(sgbm_down_kernel<false>, dim3((dm.width1 + kDnCols - 1) / kDnCols, B), dim3(kDnThreads), 0, stream, dm, pre, C, T); }
         VS_HIP(hipMemsetAsync(flag, 0, (size_t)B * nslab * 4, stream));
         ProfScope p(stream, "sgbm_forward_kernel");
         if (fw_rows == 64) hipLaunchKernelGGL(sgbm_forward_kernel<64>, dim3(B * nslab), dim3(64 * 16), 0, stream, dm, C, (int16_t*)T, bnd, flag, hdr, nslab);
         else hipLaunchKernelGGL(sgbm_forward_kernel<32>, dim3(B * nslab), dim3(32 * 16), 0, stream, dm, C, (int16_t*)T, bnd, flag, hdr, nslab);
+        first = 4;
+    } else if (fused) {
+        ProfScope p(stream, "sgbm_down_kernel"); hipLaunchKernelGGL(sgbm_down_kernel<true>, dim3((dm.width1 + kDnCols - 1) / kDnCols, B), dim3(kDnThreads), 0, stream, dm, pre, C, T);
+        first = 1;
+    } else {
+        const dim3 ghs((dm.width1 + kHsSeg - 1) / kHsSeg, h, B);
+        const size_t tile_bytes = (size_t)(kHsSeg + 2 * dm.SW2) * dm.Dp;
+        { ProfScope p(stream, "sgbm_hsum_kernel");
+          if (dm.D == 96 && dm.SW2 == 4) hipLaunchKernelGGL((sgbm_hsum_kernel<96, 9>), ghs, dim3(kHsBlock), tile_bytes, stream, dm, pre, hsum);
+          else hipLaunchKernelGGL((sgbm_hsum_kernel<0, 0>), ghs, dim3(kHsBlock), tile_bytes, stream, dm, pre, hsum); }
+        { ProfScope p(stream, "sgbm_vsum_kernel");
+          hipLaunchKernelGGL(sgbm_vsum_kernel, dim3((dm.width1 * (dm.Dp / 8) + 255) / 256, (h + kVsChunk - 1) / kVsChunk, B), dim3(256), 0, stream, dm, hsum, C); }
     }
-    if (unfused) { ProfScope p(stream, "sgbm_hsum_kernel"); hipLaunchKernelGGL(sgbm_hsum_kernel, dim3((dm.width1 + kHsSeg - 1) / kHsSeg, h, B), dim3(kHsBlock), 0, stream, dm, pre, hsum); }
-    if (unfused) { ProfScope p(stream, "sgbm_vsum_kernel"); hipLaunchKernelGGL(sgbm_vsum_kernel, dim3((dm.width1 * 12 + 255) / 256, (h + kVsChunk - 1) / kVsChunk, B), dim3(256), 0, stream, dm, hsum, C); }
-    { const int nv = dm.width1, nd = dm.width1 + h - 1;
-      if (unfused) { ProfScope p(stream, "sgbm_path_kernel<0,1>"); hipLaunchKernelGGL((sgbm_path_kernel<0, 1, 0, 8>), dim3((nv + kPathLines - 1) / kPathLines, B), dim3(kPathBlock), 0, stream, dm, C, T, nv, (int4*)nullptr); }
-      if (!fwd) { ProfScope p(stream, "sgbm_path_kernel<1,1>"); hipLaunchKernelGGL((sgbm_path_kernel<1, 1, 1, 8>), dim3((nd + kPathLines - 1) / kPathLines, B), dim3(kPathBlock), 0, stream, dm, C, T, nd, (int4*)nullptr); }
-      if (!fwd) { ProfScope p(stream, "sgbm_path_kernel<-1,1>"); hipLaunchKernelGGL((sgbm_path_kernel<-1, 1, 1, 8>), dim3((nd + kPathLines - 1) / kPathLines, B), dim3(kPathBlock), 0, stream, dm, C, T, nd, (int4*)nullptr); }
-      if (!fwd) { ProfScope p(stream, "sgbm_path_kernel<1,0>"); hipLaunchKernelGGL((sgbm_path_kernel<1, 0, 2, 16>), dim3((h + kPathLines - 1) / kPathLines, B), dim3(kPathBlock), 0, stream, dm, C, T, h, (int4*)nullptr); }
-      if (B >= 4) { ProfScope p(stream, "sgbm_path_kernel<-1,0>"); hipLaunchKernelGGL((sgbm_path_kernel<-1, 0, 4, 16>), dim3((h + kPathLines - 1) / kPathLines, B), dim3(kPathBlock), 0, stream, dm, C, T, h, rec); }
-      else {
-        { ProfScope p(stream, "sgbm_path_kernel<-1,0>"); hipLaunchKernelGGL((sgbm_path_kernel<-1, 0, 3, 16>), dim3((h + kPathLines - 1) / kPathLines, B), dim3(kPathBlock), 0, stream, dm, C, T, h, (int4*)nullptr); }
-        { ProfScope p(stream, "sgbm_wta_kernel"); hipLaunchKernelGGL(sgbm_wta_kernel, dim3((unsigned)(((size_t)h * dm.width1 + 15) / 16), B), dim3(256), 0, stream, dm, T, rec); }
-      } }
+    switch (dm.Dp / 16) {
+        case 2: launch_paths<2>(dm, first, B, C, T, rec, stream); break;
+        case 4: launch_paths<4>(dm, first, B, C, T, rec, stream); break;
+        case 6: launch_paths<6>(dm, first, B, C, T, rec, stream); break;
+        case 8: launch_paths<8>(dm, first, B, C, T, rec, stream); break;
+        case 12: launch_paths<12>(dm, first, B, C, T, rec, stream); break;
+        default: launch_paths<16>(dm, first, B, C, T, rec, stream); break;
+    }
     { ProfScope p(stream, "sgbm_lrcheck_kernel");
       hipLaunchKernelGGL(sgbm_lrcheck_kernel, dim3(h, B), dim3(kLrBlock), (size_t)(w + (w + 1) / 2) * sizeof(int), stream, dm, rec, d0); }
     if (d_disp_raw) VS_HIP(hipMemcpyAsync(d_disp_raw, d0, (size_t)B * npix * 2, hipMemcpyDeviceToDevice, stream));
     { ProfScope p(stream, "sgbm_median3_kernel"); hipLaunchKernelGGL(sgbm_median3_kernel, dim3((w + 255) / 256, h, B), dim3(256), 0, stream, w, h, d0, d1); }
     const int pblocks = (int)((npix + 255) / 256);
-    const int newVal = -16, maxDiff = 16 * 32, maxSize = 100; // speckleWindowSize 100, speckleRange 32
+    // speckle_window_size 0 = no filter: a size threshold of 0 removes no component.  Disparities are int16: a range beyond 4096 joins everything.
+    const int newVal = -16, maxDiff = 16 * min(sp.speckle_range, 4096), maxSize = sp.speckle_window_size;
     { ProfScope p(stream, "sgbm_ccl_kernels", 4);
       hipLaunchKernelGGL(sgbm_ccl_rows_kernel, dim3(h, B), dim3(kCclBlock), (size_t)2 * w * sizeof(int), stream, w, h, maxDiff, newVal, d1, par, cnt);
       hipLaunchKernelGGL(sgbm_ccl_union_kernel, dim3(pblocks, B), dim3(256), 0, stream, w, h, maxDiff, newVal, d1, par);

@@ -252,7 +252,7 @@ struct Tuning {
 // scratch: the context's SGBM buffer.  Its first 256-byte slot is a header of int32 words: the forward sweep's ticket pools, then its error word.
 constexpr int kSgbmTicketPools = 8;
 constexpr int kSgbmErrorWord = kSgbmTicketPools; // error word of the most recent launch (vslam_sgbm_status_dev)
-// sp: a set that vslam_sgbm_params_check accepts for (w, h).  The reference's set runs the kernels specialised for it, any other the general chain.
+// sp: a set that vslam_sgbm_params_check accepts for (w, h).  The reference's set keeps its batch-size dispatch (fused sweeps), any other runs the line kernels at every batch size.
 int launch_sgbm(const Tuning& tune, const vslam_sgbm_params& sp, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B,
                 float* d_disp_f32, int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream);
 

@@ -99,6 +99,29 @@ def saturated_pair():
     return L, R
 
 
+def batch(synth, B, w, h, pitch):
+    """B different pairs of the device-tier test (each its own noise, shift and band of unrelated rows) and their (2, B, h, pitch) upload buffer"""
+    out = []
+    for b in range(B):
+        shift = 9 + (13 * b) % 100
+        base = synth.noise_image(10 + b, w + shift, h)
+        L = np.ascontiguousarray(base[:, :w]); R = np.ascontiguousarray(base[:, shift:]).copy()
+        r0 = (7 * b) % (h - 12)
+        R[r0:r0 + 12] = synth.noise_image(100 + b, w, 12)
+        out.append((L, R))
+    buf = np.zeros((2, B, h, pitch), np.uint8)
+    for b, (L, R) in enumerate(out):
+        buf[0, b, :, :w] = L; buf[1, b, :, :w] = R
+    return out, buf
+
+
+# (B, set name) of the device-tier test on the 300 x 60 batch: two exact-fit lane widths across the default chain's fused-WTA (4), top-down (8) and
+# forward-sweep (16) thresholds; a padded lane width (D = 80 in 6 disparities per lane) and a D = 96 set that is not the reference's (block 1,
+# T offset 3 * P2) with the winner-take-all folded into the last path (B >= 4)
+DEVICE_B5_SETS = ("d80_b5", "d96_b1")
+DEVICE_CASES = [(B, sn) for sn in ("d64_b7", "d128_b9") for B in (5, 9, 17)] + [(5, sn) for sn in DEVICE_B5_SETS]
+
+
 BOUNDARY = _db(96, 9, 6535, 6536)                       # 3 * (81 * 189 + 6536) = 65535: the last admissible P2 at block 9, cap 63
 BEYOND = {"p2_6537": _db(96, 9, 6535, 6537), "b11_cap63": _db(96, 11, 968, 3872)}   # refused or exact, never different
 

@@ -45,21 +45,6 @@ def test_beyond_the_range_rule_refused_or_exact(vo, pkg, oracle, name):
 
 
 # ------------------------------------------------------------------------------------------------ 3. device tier
-def _batch(synth, B, w, h, pitch):
-    pairs = []
-    for b in range(B):   # every pair different: its own noise, shift and band of unrelated rows
-        shift = 9 + (13 * b) % 100
-        base = synth.noise_image(10 + b, w + shift, h)
-        L = np.ascontiguousarray(base[:, :w]); R = np.ascontiguousarray(base[:, shift:]).copy()
-        r0 = (7 * b) % (h - 12)
-        R[r0:r0 + 12] = synth.noise_image(100 + b, w, 12)
-        pairs.append((L, R))
-    buf = np.zeros((2, B, h, pitch), np.uint8)
-    for b, (L, R) in enumerate(pairs):
-        buf[0, b, :, :w] = L; buf[1, b, :, :w] = R
-    return pairs, buf
-
-
 def _run_dev(ctx, buf, w, h, pitch, sgbm):
     import torch
     B = buf.shape[1]
@@ -73,16 +58,18 @@ def _run_dev(ctx, buf, w, h, pitch, sgbm):
 
 @pytest.fixture(scope="module")
 def batch17(synth):
-    return _batch(synth, 17, 300, 60, 320)
+    return cases.batch(synth, 17, 300, 60, 320)
 
 
 @pytest.fixture(scope="module")
 def batch17_oracle(oracle, batch17):
-    return {sn: [_oracle(oracle, L, R, cases.SETS[sn]) for L, R in batch17[0]] for sn in ("d64_b7", "d128_b9")}
+    nb = {}
+    for B, sn in cases.DEVICE_CASES:
+        nb[sn] = max(nb.get(sn, 0), B)
+    return {sn: [_oracle(oracle, L, R, cases.SETS[sn]) for L, R in batch17[0][:n]] for sn, n in nb.items()}
 
 
-@pytest.mark.parametrize("sn", ["d64_b7", "d128_b9"])
-@pytest.mark.parametrize("B", [5, 9, 17])   # across the default chain's fused-WTA (4), top-down (8) and forward-sweep (16) thresholds
+@pytest.mark.parametrize("B,sn", cases.DEVICE_CASES, ids=["%d-%s" % c for c in cases.DEVICE_CASES])
 def test_device_tier_batches_and_tuning_keys(pkg, batch17, batch17_oracle, B, sn):
     w, h, pitch = 300, 60, 320
     buf = np.ascontiguousarray(batch17[1][:, :B])

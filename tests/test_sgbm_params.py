@@ -84,6 +84,14 @@ def test_oracle_guard_host_cases(oracle, default_maps, pn, sn):
     assert not np.array_equal(disp, default_maps[pn][0]), "this set's map equals the reference set's on this pair: the GPU case would prove nothing"
 
 
+@pytest.mark.parametrize("sn", cases.DEVICE_B5_SETS)
+def test_oracle_guard_device_b5_sets(oracle, synth, sn):
+    pairs, _ = cases.batch(synth, 5, 300, 60, 320)
+    kw = cases.oracle_kwargs(cases.SETS[sn])
+    differs = [not np.array_equal(oracle.sgbm_compute(L, R, **kw), oracle.sgbm_compute(L, R)) for L, R in pairs]
+    assert any(differs), "this set's maps equal the reference set's on all five pairs: the GPU case would prove nothing"
+
+
 def test_oracle_guard_boundary(oracle):
     L, R = cases.saturated_pair()
     ref = oracle.sgbm_compute(L, R)

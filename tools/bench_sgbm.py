@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """micro-benchmark: SGBM disparity stage only (B stereo pairs, device-resident), for kernel tuning.
 Without any of the StereoSGBM options the call is the reference's fixed entry (the old code path); with one, the set goes through
-vslam_disparity_map_ex_dev.  --json appends one result line to a file."""
-import argparse, json, os, sys, time
+vslam_disparity_map_ex_dev.  --json appends one result line to a file.
+--windows N is the end-to-end protocol of profiles/sgbm_params.json: 3 warm-up calls, then N timed windows of --reps calls each with the stage
+profiler off, host clock around calls that end in a synchronise; every window, their median and a checksum of the output are printed and stored."""
+import argparse, hashlib, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -17,6 +19,7 @@ for f, opt in FIELDS:
     ap.add_argument(opt, dest=f, type=int, default=None)
 ap.add_argument("--json", default=None, help="append the result as one JSON line to this file")
 ap.add_argument("--label", default="")
+ap.add_argument("--windows", type=int, default=0, help="N timed windows of --reps calls each, profiler off (0 = one profiled window)")
 a = ap.parse_args()
 given = {f: getattr(a, f) for f, _ in FIELDS if getattr(a, f) is not None}
 sgbm = None
@@ -38,6 +41,24 @@ if sgbm is None:
     run = lambda: vo.disparity_map_dev(d[0].data_ptr(), d[1].data_ptr(), h * pitch, pitch, w, h, a.batch, out.data_ptr())
 else:
     run = lambda: vo.disparity_map_dev(d[0].data_ptr(), d[1].data_ptr(), h * pitch, pitch, w, h, a.batch, out.data_ptr(), sgbm=sgbm)
+if a.windows > 0:
+    for _ in range(3): run()
+    vo.sync()
+    win = []
+    for _ in range(a.windows):
+        t0 = time.perf_counter()
+        for _ in range(a.reps): run()
+        vo.sync(); win.append(round((time.perf_counter() - t0) / a.reps * 1e3, 4))
+    med = statistics.median(win)
+    digest = hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()[:16]
+    print("B=%d  windows ms %s  median %.4f ms  %.5f ms/pair  device MB %.0f  output %s" % (a.batch, win, med, med / a.batch, vo.device_bytes / 1e6, digest))
+    if a.json:
+        rec = dict(label=a.label, batch=a.batch, reps=a.reps, sgbm=list(sgbm.as_tuple()) if sgbm is not None else "reference set, fixed entry",
+                   windows_ms=win, ms_per_call=med, ms_per_pair=round(med / a.batch, 5), device_mb=round(vo.device_bytes / 1e6, 1), output_sha256_16=digest)
+        with open(a.json, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+    vo.close()
+    sys.exit(0)
 run(); vo.sync()
 vo.profile_enable(True); vo.profile_read()
 t0 = time.perf_counter()
