@@ -154,6 +154,20 @@ int vslam_feature_matching_subset_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t
                                       const int32_t* d_nqsel, int sel_capacity, const uint8_t* d_t, size_t t_stride_bytes, const int32_t* d_nt,
                                       const double* d_gap, int gate, int B, int max_rows, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout);
 
+/* vslam_feature_matching_subset_dev with the QUERY side of item b taken from another block (additive: the ABI version is unchanged).  d_qitem (B int32,
+ * device): item b's query descriptor block (d_q + d_qitem[b] * q_stride_bytes), its d_nq entry, its d_qsel row and its d_nqsel entry are those of block
+ * d_qitem[b]; the query side holds n_qitems blocks (d_nq / d_nqsel: n_qitems entries, d_qsel: n_qitems x sel_capacity).  The train side, d_gap[b] and
+ * the outputs stay item b's.  d_qitem[b] outside [0, n_qitems) (-1 by convention: the item has no query frame) gives d_nout[b] = 0.  Several items
+ * may name the same block.  This is how a frame is matched against its last ACCEPTED predecessor at the pair's real frame gap (VO::tracking after a
+ * rejected frame, visual_odometry.cpp:630-637 and :239-242; vslam_build_map_pnp_inputs_recover_dev below).
+ * CONTRACT: with d_qitem[b] = b (and n_qitems >= B) the output is vslam_feature_matching_subset_dev's bit for bit; in general item b equals that entry
+ * run on the gathered blocks.  Same kernels: one index load ahead of the address arithmetic.  Refused with VSLAM_ERR_ARG: NULL d_qitem, n_qitems < 1,
+ * and what vslam_feature_matching_subset_dev refuses (B counts items, so B <= max_batch; n_qitems is not bounded by it). */
+int vslam_feature_matching_pairs_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq, const int32_t* d_qsel,
+                                     const int32_t* d_nqsel, int sel_capacity, const int32_t* d_qitem, int n_qitems, const uint8_t* d_t, size_t t_stride_bytes,
+                                     const int32_t* d_nt, const double* d_gap, int gate, int B, int max_rows, vslam_dmatch* d_out, int out_capacity,
+                                     int32_t* d_nout);
+
 /* ------------------------------------------------------------------ A6: dense stereo disparity --------- */
 /* Replaces VO::disparity_map (visual_odometry.cpp:159-174): cv::StereoSGBM::create(0, 96, 9, 8*9*9, 32*9*9, 1, 63, 10,
  * 100, 32)->compute(left, right) followed by convertTo(CV_32F, 1/16).  left/right: h x w u8 (row stride in bytes);
@@ -552,6 +566,80 @@ int vslam_build_map_pnp_inputs_requery_dev(vslam_ctx* ctx, const vslam_tracks_in
 int vslam_build_windows_map_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match,
                                       const int32_t* d_frame_state, int n_kf, int policy, double near_dist, int lm_capacity, int edge_capacity,
                                       vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status);
+
+/* ---- The gated passes with the REFERENCE'S FAILURE HANDLING (additive: the ABI version, vslam_tracks_in and vslam_params are unchanged).  When
+ * check_motion_estimation fails, VO::tracking does not call move_frame() (visual_odometry.cpp:630-637): the rejected frame and its features are dropped,
+ * the next frame is matched against the features of the LAST ACCEPTED frame with frame_gap = the difference of their frame ids, which widens the
+ * matcher's gate to max(match_ratio d_min, match_gap_thr frame_gap) (:239-242) and the motion check to 5 frame_gap (:328-329); after more than ten
+ * consecutive rejections the state is Lost and the node loop ends (:673-693, run_vslam.cpp:78-81).  The sequential loop (conventions of
+ * vslam_build_map_pnp_inputs_requery_dev unless stated; frame 0 is a keyframe, state 2), with last = 0 and lost_run = 0, for f = 1 .. n_frames - 1:
+ *   1. if lost_run > 10 the VO is Lost: state(f) = 3, no table, no input, G_f = G_last, an empty window; Lost is absorbing (every later frame is 3);
+ *   2. l = last, gap = f - l: the table of frame f is the cross-checked, gated match of the FEATURES OF FRAME l (ascending keypoint indices, as that
+ *      frame was accepted) against every keypoint of frame f, with frame_gap = gap;
+ *   3. every match of that table is an input, in match order: xyz_w = the landmark's map position as it stands after frame l (rejected frames change
+ *      nothing in the map), uv = the keypoint of f;
+ *   4. the solver gives T_c_w(f), a mask and num_inliers; with no inlier G_f = G_l and there are no links;
+ *   5. T_c_l = G_f o G_l^-1; state(f) = 0 if !check_motion_rule(num_inliers, T_c_l, gap), else 1 if num_inliers >= 80 && angleY < 0.03, else 2;
+ *   6. state 0: lost_run++, the frame's features are dropped (nothing is ever matched out of it), it records nothing, its window is empty, last stays;
+ *   7. state 1 or 2: lost_run = 0, the inliers become the frame's features, at state 2 insert_key_frame runs and the keyframe set is updated by the
+ *      policy exactly as in vslam_build_windows_map_gated_dev, last = f.
+ * The remaining deviations of this mode from the reference: BA results are not fed back into tracking, and windows are independent (what sharding a
+ * sequence into independent windows means); the query order is ascending keypoint index (ties and RANSAC's draw order only).
+ * Passes: pass 0 is the pose stage on adjacent frames (states^0 = vslam_gate_states_dev(d_T_rel, absolute = 0), pred^{-1}(f) = f - 1).  Pass k >= 1
+ * derives pred^{k-1} / gap from states^{k-1} (vslam_frame_pairs_dev's rule), walks the tracks on (G^{k-1}, table^{k-1}, links^{k-1}) -- table^{k-1}
+ * was built on pred^{k-2} --, re-matches every frame f with pred^{k-1}(f) >= 0 from the features of pred^{k-1}(f) at gap f - pred^{k-1}(f), emits the
+ * inputs on that table with positions as of frame pred^{k-1}(f) (vslam_build_map_pnp_inputs_recover_dev), solves every item (no inlier:
+ * G^k_f = G^{k-1}_{pred(f)}; the LM guess stays G^{k-1}_f), and takes states^k = vslam_gate_states_pairs_dev(G^k, pred^{k-1}) on the pass's inlier
+ * counts.  Windows: vslam_build_windows_map_recover_dev on (G^K, table^K, its pairing pred^{K-1}, links^K, states^K).
+ * WALK RULE: only frames of state 1 or 2 (and frame 0) have features.  A link of item f - 1 holds only when the previous pass's mask kept it, its
+ * query slot is a feature of pred_prev(f), frame f is accepted under the current states AND pred_prev(f) == pred(f): a table built on a pairing the
+ * current states no longer give continues nothing this pass.  Frames of state 0 or 3 have an empty feature list.  The honoured links therefore join
+ * consecutive accepted frames: tracks are disjoint paths, contiguous in accepted-frame rank, and every walk steps to the next accepted frame, which
+ * lies strictly later, so it terminates on any input.
+ * CONTRACT (A): with no state 0 (and so no 3) in any state vector involved, every output of vslam_build_map_pnp_inputs_recover_dev,
+ * vslam_gate_states_pairs_dev and vslam_build_windows_map_recover_dev equals that of its sibling -- vslam_build_map_pnp_inputs_requery_dev,
+ * vslam_gate_states_dev(absolute = 1), vslam_build_windows_map_gated_dev -- bit for bit (pred(f) = f - 1, every gap 1.0).
+ * CONTRACT (B): with a solver that is a pure function of its inputs, after k passes everything that belongs to frames 0..k -- tables and feature lists,
+ * inputs and masks, poses and states, pred / gap, windows -- equals the sequential loop above; K = n_frames - 1 reproduces it everywhere.  (Induction:
+ * pred(f) read from states^{k-1} and from states^{k-2} agree for f <= k, so the links of final frames are always honoured.)
+ * DEVICE SAFETY: every index read from a caller's array (d_pred_prev / d_pred of the windows entry, d_qitem, the states) is range-checked before it
+ * addresses memory; an entry of d_pred_prev outside [-1, f) empties the item's links and sets bit 4 (value 16) of *d_status, as does a state outside
+ * 0..3 (treated as rejected). */
+
+/* The pairing: d_pred[f] (n_frames int32) = the last frame j < f with d_frame_state[j] in {1, 2} (frame 0 always counts); -1 for frame 0 and for a frame
+ * that is Lost under these states -- a run of 11 or more frames of any other state ends directly before it, or an earlier frame is Lost.
+ * d_gap[f - 1] (n_frames - 1 doubles) = f - d_pred[f], or 1.0 where d_pred[f] is -1.  One small scan kernel.  Refused with VSLAM_ERR_ARG: n_frames < 1,
+ * NULL d_frame_state / d_pred, NULL d_gap when n_frames > 1.  Asynchronous on the context stream. */
+int vslam_frame_pairs_dev(vslam_ctx* ctx, int n_frames, const int32_t* d_frame_state, int32_t* d_pred, double* d_gap);
+
+/* vslam_gate_states_dev(absolute = 1) against the pairing d_pred (n_frames, the pairing the pass's items were built on): frame 0 is 2; frame f >= 1 with
+ * p = d_pred[f] in [0, f) gets the gate on T_c_l = G_f o G_p^-1 with frame_gap = f - p in check_motion_rule; a frame with any other d_pred[f] had no
+ * item in this pass and gets the raw state 0.  Then the Lost scan of vslam_frame_pairs_dev runs over the raw states in frame order and writes 3 from the
+ * first Lost frame on.  CONTRACT: with d_pred[f] = f - 1 everywhere and no run of 11 zeros the output is vslam_gate_states_dev(absolute = 1)'s bit for
+ * bit.  Refused with VSLAM_ERR_ARG: NULL d_pred / d_frame_state, NULL d_T_c_w / d_num_inliers when n_frames > 1, n_frames < 1. */
+int vslam_gate_states_pairs_dev(vslam_ctx* ctx, int n_frames, const double* d_T_c_w, const int32_t* d_pred, const int32_t* d_num_inliers,
+                                int32_t* d_frame_state);
+
+/* vslam_build_map_pnp_inputs_requery_dev with the pairing.  d_pred_prev (n_frames, device): the pairing the table in in->d_f2f was built on; NULL means
+ * f - 1 (the pose stage's table).  d_pred (n_frames) / d_gap (n_frames - 1): OUTPUTS, derived from d_frame_state as in vslam_frame_pairs_dev.  Item i is
+ * frame i + 1, as everywhere.  The walk follows the WALK RULE above; d_feat / d_nfeat hold every frame's features (d_nfeat = 0 at states 0 and 3).  For
+ * each f >= 1 with d_pred[f] >= 0 the feature list of frame d_pred[f] is matched against every keypoint of f at gap f - d_pred[f]
+ * (vslam_feature_matching_pairs_dev's path), and the inputs are emitted on that table with positions as of frame d_pred[f].  A Lost frame gets
+ * d_n = 0, d_nf2f_out = 0 and an index map of -1.  *d_status: bits 0-2 as in the sibling, bit 3 (value 8) when any frame is Lost, bit 4 (value 16) for
+ * an out-of-range d_pred_prev entry or state.  n_frames = 1: d_pred[0] = -1, d_nfeat[0] = 0, nothing else is written.
+ * Refused with VSLAM_ERR_ARG: what vslam_build_map_pnp_inputs_requery_dev refuses (a chunk included), NULL d_pred or d_gap. */
+int vslam_build_map_pnp_inputs_recover_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
+                                           const int32_t* d_pred_prev, const int32_t* d_frame_state, const uint8_t* d_desc, size_t desc_stride_bytes,
+                                           int32_t* d_feat, int32_t* d_nfeat, vslam_dmatch* d_f2f_out, int32_t* d_nf2f_out, float* d_xyz_w, float* d_uv, int32_t* d_n,
+                                           int32_t* d_input_of_match, int out_capacity, int32_t* d_pred, double* d_gap, int32_t* d_status);
+
+/* vslam_build_windows_map_gated_dev with the pairing d_pred (n_frames, device) of the table passed in in->d_f2f (a pass's d_pred output).  The walk
+ * follows the WALK RULE above with the pairing of d_frame_state; observations, landmark creation and reliable upgrades happen at state 2 only; states
+ * 0, 1 and 3 give empty windows; the keyframe sets are vslam_build_windows_map_gated_dev's.  *d_status: bits 0-2 as there, bit 3 when a frame is Lost,
+ * bit 4 for an out-of-range d_pred entry or state.  Refused with VSLAM_ERR_ARG: NULL d_pred, and what vslam_build_windows_map_gated_dev refuses. */
+int vslam_build_windows_map_recover_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match,
+                                        const int32_t* d_pred, const int32_t* d_frame_state, int n_kf, int policy, double near_dist, int lm_capacity,
+                                        int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status);
 
 /* per-window status of the most recent window launch on this process (VSLAM_OK or VSLAM_ERR_ARG per window) */
 int vslam_ba_status_dev(vslam_ctx* ctx, int n_windows, int32_t* h_status);

@@ -117,6 +117,7 @@ SIGNATURES = {
     "vslam_feature_matching": (I, [P, P, I, P, I, D, I, P, P]),
     "vslam_feature_matching_dev": (I, [P, P, Z, P, P, Z, P, P, I, I, I, P, I, P]),
     "vslam_feature_matching_subset_dev": (I, [P, P, Z, P, P, P, I, P, Z, P, P, I, I, I, P, I, P]),
+    "vslam_feature_matching_pairs_dev": (I, [P, P, Z, P, P, P, I, P, I, P, Z, P, P, I, I, I, P, I, P]),
     "vslam_disparity_map": (I, [P, P, P, I, I, I, P, P, P]),
     "vslam_disparity_map_dev": (I, [P, P, P, Z, I, I, I, I, P, P, P]),
     "vslam_default_sgbm_params": (None, [P]),
@@ -147,6 +148,10 @@ SIGNATURES = {
     "vslam_build_map_pnp_inputs_gated_dev": (I, [P, P, P, P, P, P, P, P, P, I, P]),
     "vslam_build_map_pnp_inputs_requery_dev": (I, [P, P, P, P, P, P, Z, P, P, P, P, P, P, P, P, I, P]),
     "vslam_build_windows_map_gated_dev": (I, [P, P, P, P, P, I, I, D, I, I, P, P, P, P]),
+    "vslam_frame_pairs_dev": (I, [P, I, P, P, P]),
+    "vslam_gate_states_pairs_dev": (I, [P, I, P, P, P, P]),
+    "vslam_build_map_pnp_inputs_recover_dev": (I, [P, P, P, P, P, P, P, Z, P, P, P, P, P, P, P, P, I, P, P, P]),
+    "vslam_build_windows_map_recover_dev": (I, [P, P, P, P, P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_ba_status_dev": (I, [P, I, P]), "vslam_ba_schedule_passes_dev": (I, [P, I, P]), "vslam_ba_deferred_dev": (I, [P, I, P]),
     "vslam_edge_jacobians": (I, [P, I, P, P, P, P, P, P, P, P, P]),
     "vslam_set_tuning": (I, [P, C.c_char_p, I]), "vslam_sgbm_status_dev": (I, [P, P]), "vslam_orb_status_dev": (I, [P, I, P]),
@@ -355,6 +360,12 @@ class VO:
         self._chk(self.lib.vslam_feature_matching_subset_dev(self.h, d_q, q_stride, d_nq, d_qsel, d_nqsel, sel_cap, d_t, t_stride, d_nt, d_gap, gate, B, max_rows,
                                                              d_out, out_cap, d_nout), "vslam_feature_matching_subset_dev")
 
+    def feature_matching_pairs_dev(self, d_q, q_stride, d_nq, d_qsel, d_nqsel, sel_cap, d_qitem, n_qitems, d_t, t_stride, d_nt, d_gap, gate, B, max_rows, d_out,
+                                   out_cap, d_nout):
+        """feature_matching_subset_dev with item b's query side taken from block d_qitem[b] of n_qitems (< 0: no match for the item).  include/vslam_hip.h."""
+        self._chk(self.lib.vslam_feature_matching_pairs_dev(self.h, d_q, q_stride, d_nq, d_qsel, d_nqsel, sel_cap, d_qitem, n_qitems, d_t, t_stride, d_nt, d_gap,
+                                                            gate, B, max_rows, d_out, out_cap, d_nout), "vslam_feature_matching_pairs_dev")
+
     def feature_matching_dev(self, d_q, q_stride, d_nq, d_t, t_stride, d_nt, d_gap, gate, B, max_rows, d_out, out_cap, d_nout):
         self._chk(self.lib.vslam_feature_matching_dev(self.h, d_q, q_stride, d_nq, d_t, t_stride, d_nt, d_gap, gate, B, max_rows, d_out, out_cap,
                                                       d_nout), "vslam_feature_matching_dev")
@@ -552,6 +563,29 @@ class VO:
         self._chk(self.lib.vslam_build_windows_map_gated_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match, d_frame_state, n_kf, policy, near_dist,
                                                              lm_capacity, edge_capacity, C.byref(batch), d_kf_frame, d_evicted, d_status),
                   "vslam_build_windows_map_gated_dev")
+
+    def frame_pairs_dev(self, n_frames, d_frame_state, d_pred, d_gap):
+        """every frame's last accepted predecessor (-1: frame 0, or Lost) and the gap to it, from the frame states.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_frame_pairs_dev(self.h, n_frames, d_frame_state, d_pred, d_gap), "vslam_frame_pairs_dev")
+
+    def gate_states_pairs_dev(self, n_frames, d_T_c_w, d_pred, d_num_inliers, d_frame_state):
+        """gate_states_dev(absolute=1) against the pairing d_pred at the pairs' real gaps, then the Lost scan (state 3).  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_gate_states_pairs_dev(self.h, n_frames, d_T_c_w, d_pred, d_num_inliers, d_frame_state), "vslam_gate_states_pairs_dev")
+
+    def build_map_pnp_inputs_recover_dev(self, tracks, d_T_c_w, d_input_of_match_prev, d_pred_prev, d_frame_state, d_desc, desc_stride, d_feat, d_nfeat,
+                                         d_f2f_out, d_nf2f_out, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_pred, d_gap, d_status):
+        """build_map_pnp_inputs_requery_dev with every frame re-matched from its last accepted predecessor (the reference's failure handling): also
+        writes the pairing d_pred / d_gap.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_build_map_pnp_inputs_recover_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match_prev, d_pred_prev, d_frame_state, d_desc,
+                                                                  desc_stride, d_feat, d_nfeat, d_f2f_out, d_nf2f_out, d_xyz_w, d_uv, d_n, d_input_of_match,
+                                                                  out_capacity, d_pred, d_gap, d_status), "vslam_build_map_pnp_inputs_recover_dev")
+
+    def build_windows_map_recover_dev(self, tracks, d_T_c_w, d_input_of_match, d_pred, d_frame_state, n_kf, policy, near_dist, lm_capacity, edge_capacity,
+                                      batch, d_kf_frame, d_evicted, d_status):
+        """build_windows_map_gated_dev on a table built on the pairing d_pred: rejected and Lost frames are dropped.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_build_windows_map_recover_dev(self.h, C.byref(tracks), d_T_c_w, d_input_of_match, d_pred, d_frame_state, n_kf, policy,
+                                                               near_dist, lm_capacity, edge_capacity, C.byref(batch), d_kf_frame, d_evicted, d_status),
+                  "vslam_build_windows_map_recover_dev")
 
     def build_pnp_inputs_dev(self, d_f2f, d_nf2f, match_cap, d_lr, d_nlr, lr_cap, d_xyz_lr, d_valid_lr, d_kps_cur, kp_cap, B, d_kp2lr,
                              d_xyz_out, d_uv_out, d_nout, out_cap):

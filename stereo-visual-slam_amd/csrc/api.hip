@@ -231,7 +231,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
-           "match_train_nearest_sel_kernel track_features_kernel";
+           "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -504,6 +504,25 @@ int vslam_feature_matching_subset_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t
     VS_ENTER(c);
     return launch_match(d_q, q_stride_bytes, d_nq, d_t, t_stride_bytes, d_nt, d_gap, gate, c->p.match_ratio, c->p.match_gap_thr, B, max_rows,
                         c->match.d_train_best, d_out, out_capacity, d_nout, c->stream, d_qsel, sel_capacity, d_nqsel);
+}
+
+int vslam_feature_matching_pairs_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq, const int32_t* d_qsel,
+                                     const int32_t* d_nqsel, int sel_capacity, const int32_t* d_qitem, int n_qitems, const uint8_t* d_t, size_t t_stride_bytes,
+                                     const int32_t* d_nt, const double* d_gap, int gate, int B, int max_rows, vslam_dmatch* d_out, int out_capacity,
+                                     int32_t* d_nout) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !d_q || !d_t || !d_nq || !d_nt || !d_gap || !d_out || !d_nout || out_capacity <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!d_qsel || !d_nqsel) { set_error("vslam_feature_matching_pairs_dev: d_qsel and d_nqsel are required"); return VSLAM_ERR_ARG; }
+    if (!d_qitem || n_qitems < 1) { set_error("vslam_feature_matching_pairs_dev: d_qitem (B query-block indices) and n_qitems >= 1 are required"); return VSLAM_ERR_ARG; }
+    if (sel_capacity < 1 || sel_capacity > kMaxRows) { set_error("sel_capacity %d outside 1..%d (the matcher's row limit)", sel_capacity, kMaxRows); return VSLAM_ERR_ARG; }
+    if (B > c->p.max_batch) { set_error("batch %d exceeds context max_batch %d", B, c->p.max_batch); return VSLAM_ERR_ARG; }
+    if ((((uintptr_t)d_q | (uintptr_t)d_t | (uintptr_t)q_stride_bytes | (uintptr_t)t_stride_bytes) & 15) != 0) {
+        set_error("vslam_feature_matching_pairs_dev: d_q, d_t and both strides must be multiples of 16 bytes (the matcher reads descriptors with 16-byte loads)");
+        return VSLAM_ERR_ARG;
+    }
+    VS_ENTER(c);
+    return launch_match(d_q, q_stride_bytes, d_nq, d_t, t_stride_bytes, d_nt, d_gap, gate, c->p.match_ratio, c->p.match_gap_thr, B, max_rows,
+                        c->match.d_train_best, d_out, out_capacity, d_nout, c->stream, d_qsel, sel_capacity, d_nqsel, d_qitem, n_qitems);
 }
 
 int vslam_feature_matching(vslam_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, double frame_gap, int gate,
@@ -1109,9 +1128,25 @@ int vslam_gate_states_dev(vslam_ctx* ctx, int n_frames, const double* d_T, int a
     return launch_gate_states(n_frames, d_T, absolute, d_num_inliers, d_frame_state, c->stream);
 }
 
-// d_frame_state: null for the ungated entry, required by the gated ones; rq: the re-match of the requery entry (its scratch is filled in here), else null
+int vslam_frame_pairs_dev(vslam_ctx* ctx, int n_frames, const int32_t* d_frame_state, int32_t* d_pred, double* d_gap) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || n_frames <= 0 || !d_frame_state || !d_pred || (n_frames > 1 && !d_gap)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_frame_pairs(n_frames, d_frame_state, d_pred, d_gap, c->stream);
+}
+
+int vslam_gate_states_pairs_dev(vslam_ctx* ctx, int n_frames, const double* d_T_c_w, const int32_t* d_pred, const int32_t* d_num_inliers,
+                                int32_t* d_frame_state) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || n_frames <= 0 || !d_frame_state || !d_pred || (n_frames > 1 && (!d_T_c_w || !d_num_inliers))) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_gate_states_pairs(n_frames, d_T_c_w, d_pred, d_num_inliers, d_frame_state, c->track, c->stream);
+}
+
+// d_frame_state: null for the ungated entry, required by the gated ones; rq: the re-match of the requery entry (its scratch is filled in here), else null;
+// rv: the pairing of the recover entry (with rq), else null
 static int map_pnp_inputs(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, const int32_t* d_frame_state,
-                          float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status, MapRequery* rq = nullptr) {
+                          float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status, MapRequery* rq = nullptr, const MapRecover* rv = nullptr) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !in) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (int rc = map_refuses(in, d_T_c_w)) return rc;
@@ -1141,7 +1176,7 @@ static int map_pnp_inputs(vslam_ctx* ctx, const vslam_tracks_in* in, const doubl
     fill_K(c, K4);
     const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
     return launch_map_pnp_inputs(*in, d_T_c_w, d_input_of_match_prev, d_frame_state, K4, c->p.pnp_reproj_thr, track_rule, c->track, d_xyz_w, d_uv, d_n,
-                                 d_input_of_match, out_capacity, d_status, c->stream, rq);
+                                 d_input_of_match, out_capacity, d_status, c->stream, rq, rv);
 }
 
 int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, float* d_xyz_w,
@@ -1163,6 +1198,17 @@ int vslam_build_map_pnp_inputs_requery_dev(vslam_ctx* ctx, const vslam_tracks_in
     if (!d_frame_state) { set_error("the gated walk needs d_frame_state (n_frames states of the previous pass)"); return VSLAM_ERR_ARG; }
     MapRequery rq = {d_desc, desc_stride_bytes, d_feat, d_nfeat, d_f2f_out, d_nf2f_out, 0.0, 0.0, nullptr};
     return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status, &rq);
+}
+
+int vslam_build_map_pnp_inputs_recover_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
+                                           const int32_t* d_pred_prev, const int32_t* d_frame_state, const uint8_t* d_desc, size_t desc_stride_bytes,
+                                           int32_t* d_feat, int32_t* d_nfeat, vslam_dmatch* d_f2f_out, int32_t* d_nf2f_out, float* d_xyz_w, float* d_uv, int32_t* d_n,
+                                           int32_t* d_input_of_match, int out_capacity, int32_t* d_pred, double* d_gap, int32_t* d_status) {
+    if (!d_frame_state) { set_error("the gated walk needs d_frame_state (n_frames states of the previous pass)"); return VSLAM_ERR_ARG; }
+    if (!d_pred || !d_gap) { set_error("the recover entry writes the pairing: d_pred (n_frames) and d_gap (n_frames - 1) are required"); return VSLAM_ERR_ARG; }
+    MapRequery rq = {d_desc, desc_stride_bytes, d_feat, d_nfeat, d_f2f_out, d_nf2f_out, 0.0, 0.0, nullptr};
+    const MapRecover rv = {d_pred_prev, d_pred, d_gap};
+    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status, &rq, &rv);
 }
 
 int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match, int n_kf, int policy,
@@ -1188,6 +1234,20 @@ int vslam_build_windows_map_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in,
     if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
     KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
     kp.G = d_T_c_w; kp.in_of_match = d_input_of_match; kp.gate = true; kp.state_in = d_frame_state;
+    return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
+}
+
+int vslam_build_windows_map_recover_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match,
+                                        const int32_t* d_pred, const int32_t* d_frame_state, int n_kf, int policy, double near_dist, int lm_capacity,
+                                        int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status) {
+    if (!ctx || !in || !d_kf_frame || !d_evicted || !d_frame_state) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!d_pred) { set_error("d_pred (n_frames: the pairing in->d_f2f was built on) is required"); return VSLAM_ERR_ARG; }
+    if (int rc = map_refuses(in, d_T_c_w)) return rc;
+    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 oldest evicted, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
+    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
+    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
+    KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
+    kp.G = d_T_c_w; kp.in_of_match = d_input_of_match; kp.gate = true; kp.state_in = d_frame_state; kp.recover = true; kp.pred_table = d_pred;
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
 }
 

@@ -69,6 +69,9 @@ static_assert(kMaxRows <= 4096, "the f32 key holds the row in 12 fraction bits")
 // way into LDS -- staged tile row r is Q[qsel[r]] -- so a selection of n rows costs n / 32 tiles, the MFMA / fold path is untouched (the exact
 // 256 - 2 hamming identity holds) and the packed key carries the row's RANK in the list; match_finalize_kernel maps rank -> row.  The list ascends,
 // so ascending rank = ascending original row and the first-minimum tie rule is the unmasked kernel's.
+// d_qitem (vslam_feature_matching_pairs_dev; null: item b's own block): the QUERY side of item b -- descriptor block, d_nq entry, d_qsel row and
+// d_nqsel entry -- is block d_qitem[b] of n_qitems; the train side, d_gap and the outputs stay item b's.  An index outside [0, n_qitems) empties the
+// item.  One uniform load ahead of the address arithmetic: the resident operands, the tile pipeline and the register budget are untouched.
 //
 // The f32 key.  Within the tiles tile0 .. tile1 - 1 of this workgroup, row i (of tile T, local row i % 32) competes with
 //   key = dot + (32 (tile1 - T) - 1 - i % 32) * 2^-12 = dot + (32 tile1 - 1 - i) * 2^-12:  largest dot, then smallest row;
@@ -78,12 +81,14 @@ template <bool kSel>
 __global__ __launch_bounds__(kMatchBlock, 3) void match_train_nearest_kernel(
     const uint8_t* __restrict__ d_q, size_t q_stride, const int32_t* __restrict__ d_nq, const uint8_t* __restrict__ d_t, size_t t_stride,
     const int32_t* __restrict__ d_nt, int max_rows, int qsplit, int B, uint32_t* __restrict__ d_train_best, const int32_t* __restrict__ d_qsel,
-    int sel_cap, const int32_t* __restrict__ d_nqsel) {
+    int sel_cap, const int32_t* __restrict__ d_nqsel, const int32_t* __restrict__ d_qitem, int n_qitems) {
     const int w = blockIdx.x;
     const int b = w % B, split = (w / B) % qsplit, cb = w / (B * qsplit);
-    const int nrows = min(d_nq[b], max_rows), nt = min(d_nt[b], max_rows);
-    const int nq = kSel ? min(max(d_nqsel[b], 0), min(sel_cap, nrows)) : nrows; // the rows that compete: all of them, or the selection's length
-    const int32_t* sel = kSel ? d_qsel + (size_t)b * sel_cap : nullptr;
+    const int qb = d_qitem ? d_qitem[b] : b; // the block the query side comes from
+    if (d_qitem && (qb < 0 || qb >= n_qitems)) return;
+    const int nrows = min(d_nq[qb], max_rows), nt = min(d_nt[b], max_rows);
+    const int nq = kSel ? min(max(d_nqsel[qb], 0), min(sel_cap, nrows)) : nrows; // the rows that compete: all of them, or the selection's length
+    const int32_t* sel = kSel ? d_qsel + (size_t)qb * sel_cap : nullptr;
     const int c0 = cb * kColsPerBlock;
     if (c0 >= nt || nq <= 0) return;
     // query range of this split, in whole tiles
@@ -92,7 +97,7 @@ __global__ __launch_bounds__(kMatchBlock, 3) void match_train_nearest_kernel(
     if (tile0 >= tile1) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     __shared__ alignas(16) int8_t sq[2][kQRows * kQStride];
-    const uint8_t* Q = d_q + (size_t)b * q_stride;
+    const uint8_t* Q = d_q + (size_t)qb * q_stride;
     const uint8_t* T = d_t + (size_t)b * t_stride;
     // B operands: this wave's 128 train columns, expanded once and resident for the whole kernel.  K step s of lane (r, h) holds
     // dword 4 h + s of the descriptor (one 16-B load per column and lane).
@@ -196,12 +201,16 @@ constexpr int kFinBlock = 1024;
 __global__ __launch_bounds__(kFinBlock) void match_finalize_kernel(
     const int32_t* __restrict__ d_nq, const int32_t* __restrict__ d_nt, const double* __restrict__ d_gap, int gate,
     double ratio, double gap_thr, int max_rows, const uint32_t* __restrict__ d_train_best, vslam_dmatch* __restrict__ d_out,
-    int out_capacity, int32_t* __restrict__ d_nout, const int32_t* __restrict__ d_qsel, int sel_cap, const int32_t* __restrict__ d_nqsel) {
+    int out_capacity, int32_t* __restrict__ d_nout, const int32_t* __restrict__ d_qsel, int sel_cap, const int32_t* __restrict__ d_nqsel,
+    const int32_t* __restrict__ d_qitem, int n_qitems) {
     const int b = blockIdx.x;
-    const int nrows = min(d_nq[b], max_rows), nt = min(d_nt[b], max_rows);
+    const int qraw = d_qitem ? d_qitem[b] : b;
+    const bool live = !d_qitem || (qraw >= 0 && qraw < n_qitems); // (an item without a query block: nq = 0, d_nout[b] = 0)
+    const int qb = live ? qraw : 0;
+    const int nrows = live ? min(d_nq[qb], max_rows) : 0, nt = min(d_nt[b], max_rows);
     // a selection (d_qsel non-null): the keys carry ranks in the list, nq is its length and queryIdx is the list's entry
-    const int32_t* sel = d_qsel ? d_qsel + (size_t)b * sel_cap : nullptr;
-    const int nq = sel ? min(max(d_nqsel[b], 0), min(sel_cap, nrows)) : nrows;
+    const int32_t* sel = d_qsel ? d_qsel + (size_t)qb * sel_cap : nullptr;
+    const int nq = sel ? min(max(d_nqsel[qb], 0), min(sel_cap, nrows)) : nrows;
     __shared__ uint32_t qbest[kMaxRows];
     __shared__ int s_wave_tot[kFinBlock / 64];
     __shared__ uint32_t s_min[kFinBlock / 64];
@@ -251,7 +260,7 @@ __global__ __launch_bounds__(kFinBlock) void match_finalize_kernel(
 int launch_match(const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, const uint8_t* d_t, size_t t_stride,
                  const int32_t* d_nt, const double* d_gap, int gate, double ratio, double gap_thr, int B, int max_rows,
                  uint32_t* d_train_best, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout, hipStream_t stream, const int32_t* d_qsel, int sel_cap,
-                 const int32_t* d_nqsel) {
+                 const int32_t* d_nqsel, const int32_t* d_qitem, int n_qitems) {
     if (B <= 0) return VSLAM_OK;
     if (max_rows > kMaxRows || max_rows <= 0) { set_error("matcher: max_rows %d out of range (<= %d)", max_rows, kMaxRows); return VSLAM_ERR_ARG; }
     // fill the chip: ~>= 1024 workgroups.  Split the query range when the batch is small.
@@ -263,15 +272,15 @@ int launch_match(const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, const
     if (d_qsel) {
         ProfScope prof__(stream, "match_train_nearest_sel_kernel");
         hipLaunchKernelGGL(match_train_nearest_kernel<true>, dim3(tblocks * qsplit * B), dim3(kMatchBlock), 0, stream, d_q, q_stride, d_nq, d_t, t_stride,
-                           d_nt, max_rows, qsplit, B, d_train_best, d_qsel, sel_cap, d_nqsel);
+                           d_nt, max_rows, qsplit, B, d_train_best, d_qsel, sel_cap, d_nqsel, d_qitem, n_qitems);
     } else {
         ProfScope prof__(stream, "match_train_nearest_kernel");
         hipLaunchKernelGGL(match_train_nearest_kernel<false>, dim3(tblocks * qsplit * B), dim3(kMatchBlock), 0, stream, d_q, q_stride, d_nq, d_t, t_stride,
-                           d_nt, max_rows, qsplit, B, d_train_best, nullptr, 0, nullptr);
+                           d_nt, max_rows, qsplit, B, d_train_best, nullptr, 0, nullptr, d_qitem, n_qitems);
     }
     ProfScope prof__(stream, "match_finalize_kernel");
     hipLaunchKernelGGL(match_finalize_kernel, dim3(B), dim3(kFinBlock), 0, stream, d_nq, d_nt, d_gap, gate, ratio, gap_thr,
-                       max_rows, d_train_best, d_out, out_capacity, d_nout, d_qsel, sel_cap, d_nqsel);
+                       max_rows, d_train_best, d_out, out_capacity, d_nout, d_qsel, sel_cap, d_nqsel, d_qitem, n_qitems);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

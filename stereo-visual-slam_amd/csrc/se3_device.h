@@ -133,10 +133,12 @@ VS_HD bool check_motion_rule(int num_inliers, const double* T_c_l, double frame_
     return !(sqrt(s) > 5.0 * frame_gap); // :329
 }
 
-// VO::insert_key_frame's gate (:353) on a frame f >= 1 with frame_gap 1: 2 = keyframe, 1 = tracked but not a keyframe (>= 80 inliers and a
+// VO::insert_key_frame's gate (:353) on a frame f >= 1 (keyframe_state: frame_gap 1; keyframe_state_gap: the frame's gap to the last accepted
+// frame, visual_odometry.cpp:328-329): 2 = keyframe, 1 = tracked but not a keyframe (>= 80 inliers and a
 // signed angleY below 0.03), 0 = rejected by check_motion_estimation
-VS_HD int keyframe_state(int num_inliers, const double* T_c_l) {
-    if (!check_motion_rule(num_inliers, T_c_l, 1.0)) return 0;
+VS_HD int keyframe_state_gap(int num_inliers, const double* T_c_l, double frame_gap) {
+    if (!check_motion_rule(num_inliers, T_c_l, frame_gap)) return 0;
     return (num_inliers >= 80 && se3::angle_y(T_c_l) < 0.03) ? 1 : 2;
 }
+VS_HD int keyframe_state(int num_inliers, const double* T_c_l) { return keyframe_state_gap(num_inliers, T_c_l, 1.0); }
 } // namespace vslam

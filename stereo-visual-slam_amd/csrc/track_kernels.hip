@@ -20,6 +20,9 @@
 // walk and the keyframe sets are the gated ones (track_walk_kernel<true>, kf_set_kernel<true>).
 // The reference's query set inside those passes (vslam_build_map_pnp_inputs_requery_dev): track_features_kernel lists every frame's features after the
 // walk, the subset matcher (match_kernels.hip) re-matches every pair on them, and track_map_inputs_kernel emits on that table.
+// The reference's failure handling inside those passes (the *_recover_dev entries): frame_pairs_kernel pairs every frame with its last ACCEPTED
+// predecessor (state 1 or 2) and finds the Lost frames; the links of a pair are honoured only when the table was built on that pairing, so the
+// tracks are paths through consecutive accepted frames and the walk / emit kernels step through `nxt` (the next accepted frame) instead of f + 1.
 //
 // gfx950 mapping: the reference walks std::unordered_map<id, Landmark> with per-landmark observation vectors; here a track is a chain
 // of (frame, keypoint) nodes linked by two flat int32 tables pred / succ (B x kp_capacity) filled by one scatter pass per frame pair,
@@ -104,9 +107,12 @@ template <bool kMap>
 __global__ __launch_bounds__(256) void track_link_kernel(TrackDims d, const vslam_dmatch* __restrict__ d_f2f, const int32_t* __restrict__ d_nf2f,
                                                         const uint8_t* __restrict__ d_valid, const uint8_t* __restrict__ d_inl,
                                                         const int32_t* __restrict__ kp2lr, int32_t* __restrict__ cand, int32_t* __restrict__ succ,
-                                                        const int32_t* __restrict__ in_of_match) {
+                                                        const int32_t* __restrict__ in_of_match, const int32_t* __restrict__ lfrm) {
     const int it = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ int s_tot[4];
+    // lfrm (the recover entries; null: adjacent frames): the query frame of item `it` when its links are honoured, -1 when they are not (uniform exit)
+    const int l = lfrm ? lfrm[it] : it;
+    if (l < 0) return;
     const int nm = min(max(d_nf2f[it], 0), d.match_cap);
     const vslam_dmatch* m = d_f2f + (size_t)it * d.match_cap;
     if (kMap) {
@@ -116,11 +122,11 @@ __global__ __launch_bounds__(256) void track_link_kernel(TrackDims d, const vsla
             const int j = in_of_match[(size_t)it * d.match_cap + k];
             const bool inl = j >= 0 && j < d.pnp_cap && d_inl[(size_t)it * d.pnp_cap + j] != 0;
             cand[(size_t)(it + 1) * d.kp_cap + t] = q | kCandDepth | (inl ? kCandInlier : 0);
-            succ[(size_t)it * d.kp_cap + q] = t;
+            succ[(size_t)l * d.kp_cap + q] = t;
         }
         return;
     }
-    const int32_t* k2 = kp2lr + (size_t)it * d.kp_cap;
+    const int32_t* k2 = kp2lr + (size_t)l * d.kp_cap;
     int written = 0;
     for (int base = 0; base < nm; base += 256) {
         const int k = base + tid;
@@ -128,7 +134,7 @@ __global__ __launch_bounds__(256) void track_link_kernel(TrackDims d, const vsla
         if (k < nm) {
             q = m[k].queryIdx; t = m[k].trainIdx;
             in_range = q >= 0 && q < d.kp_cap && t >= 0 && t < d.kp_cap;
-            if (in_range) { const int li = k2[q]; ok = li >= 0 && d_valid[(size_t)it * d.lr_cap + li] != 0; }
+            if (in_range) { const int li = k2[q]; ok = li >= 0 && d_valid[(size_t)l * d.lr_cap + li] != 0; }
         }
         const unsigned long long mask = __ballot(ok);
         __syncthreads();
@@ -140,7 +146,7 @@ __global__ __launch_bounds__(256) void track_link_kernel(TrackDims d, const vsla
         if (in_range) { // (matches are one-to-one in query and train index: the matcher's cross-check)
             const bool inl = ok && j < d.pnp_cap && d_inl[(size_t)it * d.pnp_cap + j] != 0;
             cand[(size_t)(it + 1) * d.kp_cap + t] = q | (ok ? kCandDepth : 0) | (inl ? kCandInlier : 0);
-            succ[(size_t)it * d.kp_cap + q] = t;
+            succ[(size_t)l * d.kp_cap + q] = t;
         }
         written += s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
     }
@@ -191,12 +197,14 @@ __device__ inline bool reprojects_within(const float pos[3], const double* __res
 // Sequential per path (its length: a few frames for most, the batch at worst), parallel over the ~B x 1200 paths.
 // kGate (vslam_build_windows_gated_dev): a landmark is created, and takes its first reliable depth, only at a KEYFRAME node (state[f] == 2,
 // insert_key_frame :353-424); a tracked feature passes through a non-keyframe exactly as above.
+// nxt (the recover entries; null: f + 1): the frame a path continues in after frame f -- the next accepted frame, -1 for none.  nxt[f] > f, so the
+// walk advances strictly in frame index and ends.
 template <bool kGate>
 __global__ __launch_bounds__(256) void track_walk_kernel(TrackDims d, TrackCam cam, const vslam_keypoint* __restrict__ d_kps, const float* __restrict__ d_xyz,
                                                         const uint8_t* __restrict__ d_valid, const uint8_t* __restrict__ d_rel, const int32_t* __restrict__ kp2lr,
                                                         const int32_t* __restrict__ cand, int32_t* __restrict__ pred, int32_t* __restrict__ succ,
                                                         const double* __restrict__ G, const float* __restrict__ carry, int32_t* __restrict__ root,
-                                                        int32_t* __restrict__ relsrc, const int32_t* __restrict__ state) {
+                                                        int32_t* __restrict__ relsrc, const int32_t* __restrict__ state, const int32_t* __restrict__ nxt) {
     const int f0 = blockIdx.y, i0 = blockIdx.x * 256 + threadIdx.x;
     if (i0 >= d.kp_cap) return;
     if (f0 > 0 && cand[(size_t)f0 * d.kp_cap + i0] >= 0) return; // some earlier slot's walk passes through here
@@ -216,10 +224,11 @@ __global__ __launch_bounds__(256) void track_walk_kernel(TrackDims d, TrackCam c
         if (!feat && own3d) { feat = true; r = node; first = -1; }                                        // :403-418 a landmark is created here
         if (feat && first == -1 && own3d && d_rel[(size_t)cf * d.lr_cap + mm] != 0) first = node;           // :391-401 (or created reliable)
         root[c] = feat ? r : -1; relsrc[c] = feat ? first : -1;
-        if (cf + 1 >= d.B) break;
+        const int nf = nxt ? nxt[cf] : cf + 1;
+        if (nf <= cf || nf >= d.B) break;
         const int t = succ[c]; // (candidate)
         if (t < 0) break;
-        const size_t cn = (size_t)(cf + 1) * d.kp_cap + t;
+        const size_t cn = (size_t)nf * d.kp_cap + t;
         const int cd = cand[cn];
         bool holds = false;
         if (feat) {
@@ -227,12 +236,12 @@ __global__ __launch_bounds__(256) void track_walk_kernel(TrackDims d, TrackCam c
             else if (cam.track_rule) {
                 const int src = first != -1 ? first : r;
                 if (src != pos_src) { landmark_position(d, src, kp2lr, d_xyz, G, carry, pos); pos_src = src; }
-                holds = reprojects_within(pos, G + (size_t)(cf + 1) * 7, d_kps + cn, cam);
+                holds = reprojects_within(pos, G + (size_t)nf * 7, d_kps + cn, cam);
             }
         }
         if (holds) pred[cn] = ci;
         else { succ[c] = -1; feat = false; r = -1; first = -1; }
-        ++cf; ci = t;
+        cf = nf; ci = t;
     }
 }
 
@@ -394,6 +403,89 @@ __global__ __launch_bounds__(256) void kf_gate_kernel(int B, const int32_t* __re
     state[f] = keyframe_state(num_inliers[f - 1], T_c_l);
 }
 
+// the same gate against the last ACCEPTED frame (vslam_gate_states_pairs_dev): T_c_l_ = G_f o G_pred(f)^-1 and frame_gap = f - pred(f) widens
+// check_motion_estimation (visual_odometry.cpp:328-329).  A frame without a predecessor (pred outside [0, f)) had no item in the pass: raw state 0.
+// With pred(f) = f - 1 the arithmetic is kf_gate_kernel<true>'s.
+__global__ __launch_bounds__(256) void kf_gate_pairs_kernel(int B, const int32_t* __restrict__ num_inliers, const double* __restrict__ G,
+                                                           const int32_t* __restrict__ pred, int32_t* __restrict__ state) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= B) return;
+    if (f == 0) { state[0] = 2; return; }
+    const int p = pred[f];
+    if (p < 0 || p >= f) { state[f] = 0; return; }
+    double Gi[7], T_c_l[7];
+    se3::inverse(G + (size_t)p * 7, Gi);
+    se3::mul(G + (size_t)f * 7, Gi, T_c_l);
+    state[f] = keyframe_state_gap(num_inliers[f - 1], T_c_l, (double)(f - p));
+}
+
+// ---- the pairing of VO::tracking's failure handling (visual_odometry.cpp:630-637, :673-693), one workgroup: pred[f] = the last frame j < f with state
+// 1 or 2 (frame 0 always counts) as an exclusive max-scan in chunks of 256 frames; a frame is Lost when 11 or more rejected frames lie between it and
+// that predecessor (f - pred > 11: lost_run > 10) or an earlier frame is Lost: pred = -1 from the first such frame on.  gap[f - 1] = f - pred[f] (1.0
+// without a predecessor).  Optional outputs: state_out (may alias state; the EFFECTIVE states: 3 from the first Lost frame on, 0 for a state outside
+// 0..3, else the state itself -- what the walk and the keyframe sets of the recover entries run on), nxt (the next accepted frame of
+// every frame, -1 for none: nxt[pred[f]] = f for every accepted f, distinct predecessors), lfrm (item f - 1's query frame pred[f] when frame f is
+// accepted and the table of pred_prev -- null: f - 1 -- was built on that same pairing, else -1), flags (bit 3: a Lost frame; bit 4: a state outside
+// 0..3 or a pred_prev[f] outside [-1, f), whose item is emptied).  Thread tid owns the frames tid + 256 k in both phases.
+constexpr int kLostGap = 11; // f - pred(f) above this: more than ten consecutive rejections (:673)
+__global__ __launch_bounds__(256) void frame_pairs_kernel(int B, const int32_t* state, int32_t* state_out, int32_t* __restrict__ pred, double* __restrict__ gap,
+                                                         int32_t* __restrict__ nxt, const int32_t* __restrict__ pred_prev, int32_t* __restrict__ lfrm,
+                                                         int32_t* __restrict__ flags) {
+    __shared__ int s[256];
+    __shared__ int carry, first_lost;
+    const int tid = threadIdx.x;
+    if (tid == 0) { carry = -1; first_lost = B; }
+    __syncthreads();
+    int flag = 0;
+    for (int base = 0; base < B; base += 256) {
+        const int f = base + tid;
+        const int st = f < B ? state[f] : 0;
+        if (f > 0 && f < B && (st < 0 || st > 3)) flag |= 16;
+        s[tid] = f < B && (f == 0 || st == 1 || st == 2) ? f : -1;
+        __syncthreads();
+        for (int dd = 1; dd < 256; dd <<= 1) {
+            const int a = tid >= dd ? s[tid - dd] : -1;
+            __syncthreads();
+            s[tid] = max(s[tid], a);
+            __syncthreads();
+        }
+        const int incl = max(carry, s[tid]), excl = max(carry, tid > 0 ? s[tid - 1] : -1);
+        if (f < B) {
+            pred[f] = f == 0 ? -1 : excl;
+            if (f > 0 && f - excl > kLostGap) atomicMin(&first_lost, f);
+        }
+        __syncthreads();
+        if (tid == 255) carry = incl;
+        __syncthreads();
+    }
+    const int L = first_lost;
+    if (nxt) {
+        for (int f = tid; f < B; f += 256) nxt[f] = -1;
+        __syncthreads();
+    }
+    for (int f = tid; f < B; f += 256) {
+        const int st = state[f];
+        const bool lost = f >= L;
+        int p = pred[f];
+        if (lost) { p = -1; pred[f] = -1; }
+        if (state_out) state_out[f] = f == 0 ? 2 : lost ? 3 : (st < 0 || st > 3) ? 0 : st;
+        const bool acc = f > 0 && !lost && (st == 1 || st == 2);
+        if (f > 0) gap[f - 1] = p >= 0 ? (double)(f - p) : 1.0;
+        if (nxt && acc) nxt[p] = f;
+        if (lfrm && f > 0) {
+            const int pp = pred_prev ? pred_prev[f] : f - 1;
+            const bool bad = pp < -1 || pp >= f;
+            if (bad) flag |= 16;
+            lfrm[f - 1] = acc && !bad && pp == p ? p : -1;
+        }
+    }
+    if (L < B) flag |= 8;
+    if (flags && flag) atomicOr(flags, flag);
+}
+
+// the pairing's flags joined to a builder's status word (after window_scan_kernel wrote it)
+__global__ void status_or_kernel(int32_t* __restrict__ status, const int32_t* __restrict__ flags) { *status |= *flags; }
+
 // policy 0 through vslam_build_windows_kf_dev: the sliding window's sets written out
 __global__ __launch_bounds__(256) void kf_sliding_kernel(int B, int n_kf, int32_t* __restrict__ kf_frame, int32_t* __restrict__ evicted) {
     const int t = blockIdx.x * 256 + threadIdx.x, b = t / n_kf, k = t - b * n_kf;
@@ -430,10 +522,13 @@ __global__ __launch_bounds__(256) void track_map_inputs_kernel(TrackDims d, cons
                                                               const int32_t* __restrict__ kp2lr, const int32_t* __restrict__ root,
                                                               const int32_t* __restrict__ relsrc, const double* __restrict__ G, int out_cap,
                                                               float* __restrict__ xyz_out, float* __restrict__ uv_out, int32_t* __restrict__ n_out,
-                                                              int32_t* __restrict__ in_of_match, int32_t* __restrict__ status) {
+                                                              int32_t* __restrict__ in_of_match, int32_t* __restrict__ status, const int32_t* __restrict__ qfrm) {
     const int it = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ int s_tot[4];
-    const int nm = min(max(d_nf2f[it], 0), d.match_cap);
+    // qfrm (the recover entries; null: frame `it`): the frame the queries of item `it` live in, frame it + 1's last accepted predecessor (in [0, it]
+    // by construction, frame_pairs_kernel); -1: the frame is Lost, no input and an index map of -1
+    const int l = qfrm ? qfrm[it] : it;
+    const int nm = l < 0 ? 0 : min(max(d_nf2f[it], 0), d.match_cap);
     const vslam_dmatch* m = d_f2f + (size_t)it * d.match_cap;
     int32_t* map = in_of_match + (size_t)it * d.match_cap;
     int written = 0;
@@ -442,7 +537,7 @@ __global__ __launch_bounds__(256) void track_map_inputs_kernel(TrackDims d, cons
         bool ok = false; int q = -1, t = -1;
         if (k < nm) {
             q = m[k].queryIdx; t = m[k].trainIdx;
-            ok = q >= 0 && q < d.kp_cap && t >= 0 && t < d.kp_cap && root[(size_t)it * d.kp_cap + q] != -1;
+            ok = q >= 0 && q < d.kp_cap && t >= 0 && t < d.kp_cap && root[(size_t)l * d.kp_cap + q] != -1;
         }
         const unsigned long long mask = __ballot(ok);
         __syncthreads();
@@ -453,7 +548,7 @@ __global__ __launch_bounds__(256) void track_map_inputs_kernel(TrackDims d, cons
         const int j = off + __popcll(mask & ((1ull << lane) - 1ull));
         const bool keep = ok && j < out_cap;
         if (keep) {
-            const size_t c = (size_t)it * d.kp_cap + q;
+            const size_t c = (size_t)l * d.kp_cap + q;
             const int rs = relsrc[c];
             float pos[3];
             landmark_position(d, rs != -1 ? rs : root[c], kp2lr, d_xyz, G, nullptr, pos);
@@ -493,7 +588,7 @@ __global__ __launch_bounds__(256) void track_features_kernel(TrackDims d, const 
         if (ok) feat[(size_t)f * d.kp_cap + off + __popcll(mask & ((1ull << lane) - 1ull))] = i;
         written += s_tot[0] + s_tot[1] + s_tot[2] + s_tot[3];
     }
-    if (tid == 0) { nfeat[f] = written; if (f + 1 < d.B) gap[f] = 1.0; }
+    if (tid == 0) { nfeat[f] = written; if (gap && f + 1 < d.B) gap[f] = 1.0; } // (gap null: the recover entry's pairing wrote the gaps)
 }
 
 // A chain HEAD of window [s, b]: a node in frame s, or a node without predecessor (a landmark created inside the window).  Every
@@ -518,7 +613,7 @@ __device__ inline int window_set_head_len(int r, const int2* __restrict__ ends, 
 // A window's keyframes: the sliding window [s, b], or the culled set of kf_frame (kSet).  Loaded into the workgroup's LDS.  nmem (gated sets
 // only, else nullptr): the member count of every window, 0 for the empty window of a non-keyframe step; without it every set holds
 // min(b + 1, n_kf) frames.
-struct WindowSet { const int32_t* kf_frame; const int2* ends; const int32_t* root; const int32_t* nmem; };
+struct WindowSet { const int32_t* kf_frame; const int2* ends; const int32_t* root; const int32_t* nmem; const int32_t* nxt = nullptr; }; // nxt: see track_walk_kernel
 template <bool kSet>
 __device__ inline int window_frames(const TrackDims& d, const WindowSet& ws, int b, int* s_kf) {
     const int s = max(0, b - d.n_kf + 1), nk = kSet && ws.nmem ? ws.nmem[b] : b - s + 1;
@@ -700,7 +795,11 @@ __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vsl
     if (kSet) {
         for (int k = 0; k < len; ++k) {
             const int tf = kfs[slot + k];
-            while (cf < tf) { const int nx = succ[(size_t)cf * d.kp_cap + ci]; ci = nx < 0 ? ci : nx; ++cf; } // (a chain reaches tf: ends[])
+            while (cf < tf) { // (a chain reaches tf: ends[]; it steps through the frames, or -- ws.nxt -- through the accepted ones)
+                const int nx = succ[(size_t)cf * d.kp_cap + ci], nf = ws.nxt ? ws.nxt[cf] : cf + 1;
+                if (nf <= cf || nf > tf) break;
+                ci = nx < 0 ? ci : nx; cf = nf;
+            }
             const vslam_keypoint* kp = d_kps + (size_t)cf * d.kp_cap + ci;
             kf_out[e] = slot + k; lm_out[e] = l;
             reinterpret_cast<float2*>(uv_out)[e] = make_float2(kp->x, kp->y);
@@ -741,6 +840,7 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     const size_t tab = (size_t)d.B * d.kp_cap;
     int32_t *kp2lr, *pred, *succ, *root, *relsrc, *info, *counts, *hist; double* G; uint32_t* head_rec;
     int2* ends = nullptr; double* D = nullptr; int32_t* set_flags = nullptr; int32_t* nmem = nullptr;
+    int32_t *r_pred = nullptr, *nxt = nullptr, *lfrm = nullptr, *r_flags = nullptr, *r_state = nullptr; double* r_gap = nullptr; // (kp.recover: the pairing of the states)
     if (int rc = carve(scratch, stream, [&](Layout& L) {
             kp2lr = L.take<int32_t>(tab); pred = L.take<int32_t>(tab); succ = L.take<int32_t>(tab);
             root = L.take<int32_t>(tab); relsrc = L.take<int32_t>(tab); info = L.take<int32_t>(tab);
@@ -754,17 +854,26 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
                 set_flags = L.take<int32_t>(64);
                 if (gate) nmem = L.take<int32_t>(d.B);
             }
+            if (kp.recover) {
+                r_pred = L.take<int32_t>(d.B); nxt = L.take<int32_t>(d.B); lfrm = L.take<int32_t>(d.B); r_flags = L.take<int32_t>(64); r_state = L.take<int32_t>(d.B);
+                r_gap = L.take<double>(d.B);
+            }
         })) return rc;
-    const WindowSet ws = {kp.kf_frame, ends, root, nmem};
+    WindowSet ws = {kp.kf_frame, ends, root, nmem};
+    ws.nxt = nxt;
     TrackCam cam;
     cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
     int32_t* cand = info; // (the candidate words live in the info table until track_info_kernel writes it)
     ProfScope prof__(stream, "build_windows_kernels", 9);
+    if (kp.recover) { // which frame every frame continues from under the caller's states, and which items' links that honours (table built on kp.pred_table)
+        VS_HIP(hipMemsetAsync(r_flags, 0, sizeof(int32_t), stream));
+        hipLaunchKernelGGL(frame_pairs_kernel, dim3(1), dim3(256), 0, stream, d.B, kp.state_in, r_state, r_pred, r_gap, nxt, kp.pred_table, lfrm, r_flags);
+    }
     hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
     if (kp.G) VS_HIP(hipMemcpyAsync(G, kp.G, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (the map builder: the caller's poses)
     else if (in.d_T_abs) VS_HIP(hipMemcpyAsync(G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
     else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(1), dim3(256), 0, stream, d.B, in.d_T_rel, G);
-    const int32_t* state = kp.state_in ? kp.state_in : kp.frame_state; // (the map builder: the caller's states)
+    const int32_t* state = kp.recover ? r_state : kp.state_in ? kp.state_in : kp.frame_state; // (the map builder: the caller's states; recover: with the Lost frames marked)
     if (gate) { // the states depend on the pose stage's outputs alone, the keyframe sets on the states and the poses
         if (!kp.state_in)
             hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((d.B + 255) / 256), dim3(256), 0, stream, d.B, kp.num_inliers, in.d_T_rel, kp.frame_state);
@@ -777,16 +886,17 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     } else if (kp.policy == 0)
         hipLaunchKernelGGL(kf_sliding_kernel, dim3((d.B * n_kf + 255) / 256), dim3(256), 0, stream, d.B, n_kf, kp.kf_frame, kp.evicted);
     if (d.B > 1 && kp.in_of_match)
-        hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, kp.in_of_match);
+        hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, kp.in_of_match, lfrm);
     else if (d.B > 1)
-        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr);
+        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr, lfrm);
     if (gate)
         hipLaunchKernelGGL(track_walk_kernel<true>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
-                           G, in.d_carry_in, root, relsrc, state);
+                           G, in.d_carry_in, root, relsrc, state, nxt);
     else
         hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
-                           G, in.d_carry_in, root, relsrc, nullptr);
-    hipLaunchKernelGGL(track_info_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, pred, succ, root, in.d_carry_in, info);
+                           G, in.d_carry_in, root, relsrc, nullptr, nullptr);
+    if (!kp.recover) // (the info words serve the sliding windows; the recovered windows are set windows, which read root / ends)
+        hipLaunchKernelGGL(track_info_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, pred, succ, root, in.d_carry_in, info);
     if (in.d_carry_out && in.carry_out_frame > 0 && in.carry_out_frame < d.B)
         hipLaunchKernelGGL(track_carry_out_kernel, dim3((d.kp_cap + 255) / 256), dim3(256), 0, stream, d, in.carry_out_frame, kp2lr, pred, root, relsrc, in.d_xyz, G,
                            in.d_carry_in, in.d_carry_out);
@@ -797,6 +907,7 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
         hipLaunchKernelGGL(window_rank_kernel<true>, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec, ws);
         hipLaunchKernelGGL(window_emit_kernel<true>, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist,
                            head_rec, d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out, ws);
+        if (kp.recover) hipLaunchKernelGGL(status_or_kernel, dim3(1), dim3(1), 0, stream, d_status, r_flags);
     } else {
         hipLaunchKernelGGL(window_count_kernel<false>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist, ws);
         hipLaunchKernelGGL(window_scan_kernel<false>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags, nmem);
@@ -825,22 +936,48 @@ int launch_gate_states(int n_frames, const double* d_T, int absolute, const int3
     return VSLAM_OK;
 }
 
+// ---- the pairing on its own (vslam_frame_pairs_dev) and the gate against it (vslam_gate_states_pairs_dev: raw states, then the Lost scan in place;
+// the scan's pred / gap go to scratch)
+int launch_frame_pairs(int n_frames, const int32_t* d_state, int32_t* d_pred, double* d_gap, hipStream_t stream) {
+    ProfScope prof__(stream, "frame_pairs_kernel");
+    hipLaunchKernelGGL(frame_pairs_kernel, dim3(1), dim3(256), 0, stream, n_frames, d_state, (int32_t*)nullptr, d_pred, d_gap, (int32_t*)nullptr,
+                       (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
+int launch_gate_states_pairs(int n_frames, const double* d_G, const int32_t* d_pred, const int32_t* d_num_inliers, int32_t* d_state, DevBuf& scratch,
+                             hipStream_t stream) {
+    int32_t* s_pred; double* s_gap;
+    if (int rc = carve(scratch, stream, [&](Layout& L) { s_pred = L.take<int32_t>(n_frames); s_gap = L.take<double>(n_frames); })) return rc;
+    ProfScope prof__(stream, "kf_gate_pairs_kernel", 2);
+    hipLaunchKernelGGL(kf_gate_pairs_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_G, d_pred, d_state);
+    hipLaunchKernelGGL(frame_pairs_kernel, dim3(1), dim3(256), 0, stream, n_frames, d_state, d_state, s_pred, s_gap, (int32_t*)nullptr, (const int32_t*)nullptr,
+                       (int32_t*)nullptr, (int32_t*)nullptr);
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
 // ---- one refinement pass's pose inputs (vslam_build_map_pnp_inputs_dev): the walk of the builders on the caller's poses G and the previous pass's
 // links (in_of_match_prev, or the pose stage's own-depth flags and track_rule when it is null), then the map inputs of every frame pair.
 // d_state (vslam_build_map_pnp_inputs_gated_dev; else null): the previous pass's frame states -- the gated walk, a non-keyframe creates nothing.
 // rq (vslam_build_map_pnp_inputs_requery_dev; else null): between the walk and the emit every pair is RE-MATCHED with the features of its first frame
 // as the query set (track_features_kernel + the subset matcher), and the inputs are emitted on that table instead of in.d_f2f
+// rv (vslam_build_map_pnp_inputs_recover_dev, with rq; else null): d_state also gives the pairing -- every frame against its last accepted predecessor,
+// Lost frames without one (frame_pairs_kernel: rv->d_pred, rv->d_gap) --, the walk honours a pair's links only when in.d_f2f was built on that pairing
+// (rv->d_pred_prev) and steps through the accepted frames, and pair f - 1 is re-matched from the features of pred(f) at gap f - pred(f)
 int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
                           double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
-                          int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq) {
+                          int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq, const MapRecover* rv) {
     TrackDims d;
     d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = 1;
     const size_t tab = (size_t)d.B * d.kp_cap;
-    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *cand; double* gap = nullptr;
+    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *cand; double* gap = nullptr; int32_t *nxt = nullptr, *lfrm = nullptr, *r_state = nullptr;
     if (int rc = carve(scratch, stream, [&](Layout& L) {
             kp2lr = L.take<int32_t>(tab); pred = L.take<int32_t>(tab); succ = L.take<int32_t>(tab);
             root = L.take<int32_t>(tab); relsrc = L.take<int32_t>(tab); cand = L.take<int32_t>(tab);
-            if (rq) gap = L.take<double>(d.B);
+            if (rq && !rv) gap = L.take<double>(d.B);
+            if (rv) { nxt = L.take<int32_t>(d.B); lfrm = L.take<int32_t>(d.B); r_state = L.take<int32_t>(d.B); }
         })) return rc;
     TrackCam cam;
     cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
@@ -848,32 +985,36 @@ int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const in
     VS_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t), stream));
     if (d.B < 2) {
         if (rq) VS_HIP(hipMemsetAsync(rq->d_nfeat, 0, sizeof(int32_t) * d.B, stream)); // (no pair: no walk, no list)
+        if (rv) VS_HIP(hipMemsetAsync(rv->d_pred, 0xFF, sizeof(int32_t) * d.B, stream)); // (frame 0 has no predecessor; no gap entry)
         return VSLAM_OK;
     }
+    if (rv) // (the flags -- a Lost frame, an out-of-range state or d_pred_prev entry -- go straight into the status word cleared above)
+        hipLaunchKernelGGL(frame_pairs_kernel, dim3(1), dim3(256), 0, stream, d.B, d_state, r_state, rv->d_pred, rv->d_gap, nxt, rv->d_pred_prev, lfrm, d_status);
     hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
     if (d_in_of_match_prev)
         hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ,
-                           d_in_of_match_prev);
+                           d_in_of_match_prev, lfrm);
     else
-        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr);
+        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr, lfrm);
     if (d_state)
         hipLaunchKernelGGL(track_walk_kernel<true>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable,
-                           kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, d_state);
+                           kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, rv ? r_state : d_state, nxt);
     else
         hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable,
-                           kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, nullptr);
+                           kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, nullptr, nullptr);
     const vslam_dmatch* f2f = in.d_f2f; const int32_t* nf2f = in.d_nf2f;
     if (rq) { // pair i: queries = the features of frame i, trains = every keypoint of frame i + 1, the gate of VO::feature_matching at frame_gap 1
         hipLaunchKernelGGL(track_features_kernel, dim3(d.B), dim3(256), 0, stream, d, root, in.d_nkps, rq->d_feat, rq->d_nfeat, gap);
         prof_end(stream); // (the matcher brackets its own kernels: this bracket closes before it ...
-        if (int rc = launch_match(rq->d_desc, rq->desc_stride, in.d_nkps, rq->d_desc + rq->desc_stride, rq->desc_stride, in.d_nkps + 1, gap, 1, rq->ratio,
-                                  rq->gap_thr, d.B - 1, d.kp_cap, rq->d_train_best, rq->d_f2f_out, d.match_cap, rq->d_nf2f_out, stream, rq->d_feat, d.kp_cap,
-                                  rq->d_nfeat)) return rc;
+        // (rv: item i's query block is frame pred(i + 1) -- the d_qitem path, block indices = frame indices -- at the pairing's gaps)
+        if (int rc = launch_match(rq->d_desc, rq->desc_stride, in.d_nkps, rq->d_desc + rq->desc_stride, rq->desc_stride, in.d_nkps + 1, rv ? rv->d_gap : gap, 1,
+                                  rq->ratio, rq->gap_thr, d.B - 1, d.kp_cap, rq->d_train_best, rq->d_f2f_out, d.match_cap, rq->d_nf2f_out, stream, rq->d_feat,
+                                  d.kp_cap, rq->d_nfeat, rv ? rv->d_pred + 1 : nullptr, rv ? d.B : 0)) return rc;
         prof_begin(stream, "track_map_inputs_kernel", 1); // ... and prof__ closes this one, around the emit)
         f2f = rq->d_f2f_out; nf2f = rq->d_nf2f_out;
     }
     hipLaunchKernelGGL(track_map_inputs_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, f2f, nf2f, in.d_kps, in.d_xyz, kp2lr, root, relsrc, d_G,
-                       out_capacity, d_xyz_out, d_uv_out, d_n_out, d_in_of_match, d_status);
+                       out_capacity, d_xyz_out, d_uv_out, d_n_out, d_in_of_match, d_status, rv ? rv->d_pred + 1 : nullptr);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

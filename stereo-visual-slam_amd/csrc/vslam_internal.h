@@ -174,7 +174,7 @@ struct MatchBuffers {
 int launch_match(const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, const uint8_t* d_t, size_t t_stride,
                  const int32_t* d_nt, const double* d_gap, int gate, double ratio, double gap_thr, int B, int max_rows,
                  uint32_t* d_train_best, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout, hipStream_t stream,
-                 const int32_t* d_qsel = nullptr, int sel_cap = 0, const int32_t* d_nqsel = nullptr);
+                 const int32_t* d_qsel = nullptr, int sel_cap = 0, const int32_t* d_nqsel = nullptr, const int32_t* d_qitem = nullptr, int n_qitems = 0);
 
 // ----------------------------------------------------------------------------------------------- geometry
 struct CamParams { double fx, fy, cx, cy, b, dmin, dmax, drel, row_tol; };
@@ -316,7 +316,10 @@ int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t
 // ((n_frames - 1) x match_capacity) the links are decided through it: match k of item i holds when in_of_match >= 0 and that input's d_pose_inlier flag is set.
 // gate with state_in (vslam_build_windows_map_gated_dev): the frame states are the caller's (n_frames), not computed from num_inliers / T_rel.
 struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evicted; bool gate = false; const int32_t* num_inliers = nullptr; int32_t* frame_state = nullptr;
-                  const double* G = nullptr; const int32_t* in_of_match = nullptr; const int32_t* state_in = nullptr; };
+                  const double* G = nullptr; const int32_t* in_of_match = nullptr; const int32_t* state_in = nullptr;
+                  // recover (vslam_build_windows_map_recover_dev; with gate, G, state_in): the states also give the pairing of every frame with its last
+                  // accepted predecessor; pred_table (n_frames) is the pairing in.d_f2f was built on -- a pair's links hold only where the two agree
+                  bool recover = false; const int32_t* pred_table = nullptr; };
 // K4 = {fx, fy, cx, cy}, reproj_thr (pixels), track_rule: see Tuning::track_rule
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
@@ -324,6 +327,13 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
 int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream);
 // insert_key_frame's gate per frame (vslam_gate_states_dev): absolute 0 on T_rel (n_frames - 1 rows), 1 on absolute poses (n_frames rows)
 int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream);
+// the reference's failure handling: every frame's last accepted predecessor / gap / Lost from the states (vslam_frame_pairs_dev), and the gate taken
+// against that predecessor at that gap followed by the Lost scan (vslam_gate_states_pairs_dev)
+int launch_frame_pairs(int n_frames, const int32_t* d_state, int32_t* d_pred, double* d_gap, hipStream_t stream);
+int launch_gate_states_pairs(int n_frames, const double* d_G, const int32_t* d_pred, const int32_t* d_num_inliers, int32_t* d_state, DevBuf& scratch,
+                             hipStream_t stream);
+// vslam_build_map_pnp_inputs_recover_dev: the pairing in.d_f2f was built on (null: adjacent frames) and the outputs of this pass's pairing
+struct MapRecover { const int32_t* d_pred_prev; int32_t* d_pred; double* d_gap; };
 // the re-match of vslam_build_map_pnp_inputs_requery_dev: frame f's descriptors at d_desc + f * desc_stride; outputs the feature lists (n_frames x kp_capacity,
 // n_frames) and the new frame-to-frame table ((n_frames - 1) x match_capacity); the matcher's gate parameters and scratch
 struct MapRequery { const uint8_t* d_desc; size_t desc_stride; int32_t* d_feat; int32_t* d_nfeat; vslam_dmatch* d_f2f_out; int32_t* d_nf2f_out;
@@ -332,7 +342,7 @@ struct MapRequery { const uint8_t* d_desc; size_t desc_stride; int32_t* d_feat; 
 // pairs are re-matched on their feature sets between the walk and the emit, *_requery_dev)
 int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
                           double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
-                          int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq = nullptr);
+                          int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq = nullptr, const MapRecover* rv = nullptr);
 
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {

@@ -26,7 +26,7 @@ class KeyframePipeline:
     def __init__(self, B, device=0, anms_num=1500, n_lm=3000, n_kf=10, unique_frames=64, unique_windows=None, seed=0, verbose=False,
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
                  lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
-                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all", sgbm_params=None):
+                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all", sgbm_params=None, rejected_frames="pass_through"):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
         sgbm_params (depth="sgbm"): the StereoSGBM set of the batched disparity call -- an SgbmParams, a dict of its fields or a tuple
@@ -54,7 +54,12 @@ class KeyframePipeline:
         f2f_queries: "all" -- the frame-to-frame table is stage A's, every keypoint of the last frame a query; "features" (pose_inputs="map",
         keyframe_gate="per_pass") -- the reference's query set (visual_odometry.cpp:568-575): pass k re-matches every pair with the features of its
         first frame, as the walk of (table^{k-1}, links^{k-1}, states^{k-1}) finds them, against every keypoint of the second, and solves on that
-        table (vslam_build_map_pnp_inputs_requery_dev); stage A's table stays untouched, the windows are built on the last pass's table."""
+        table (vslam_build_map_pnp_inputs_requery_dev); stage A's table stays untouched, the windows are built on the last pass's table.
+        rejected_frames: "pass_through" -- a frame that check_motion_estimation rejects is treated like a tracked one (tracks run through it, every pair
+        is matched at frame_gap 1); "recover" (pose_inputs="map", keyframe_gate="per_pass", f2f_queries="features") -- the reference's failure handling
+        (visual_odometry.cpp:630-637, :673-693): a rejected frame and its features are dropped, the next frame is matched against the features of the last
+        ACCEPTED frame at their real frame gap, more than ten rejections in a row end in the Lost state 3 (vslam_build_map_pnp_inputs_recover_dev,
+        vslam_gate_states_pairs_dev, vslam_build_windows_map_recover_dev); download() adds the last pass's pairing map_pred / map_gap."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
         assert keyframe_gate in (False, True, "per_pass"), "keyframe_gate: False, True (on stage A's inputs) or 'per_pass' (inside the map passes)"
@@ -68,7 +73,11 @@ class KeyframePipeline:
                 "pose_inputs='map' is not available with keyframe_gate=True (keyframe_gate='per_pass' gates inside the passes) or frame_range"
         assert f2f_queries in ("all", "features")
         assert f2f_queries == "all" or (per_pass and pose_inputs == "map"), "f2f_queries='features' needs pose_inputs='map' and keyframe_gate='per_pass'"
+        assert rejected_frames in ("pass_through", "recover")
+        assert rejected_frames == "pass_through" or (per_pass and pose_inputs == "map" and f2f_queries == "features"), \
+            "rejected_frames='recover' needs pose_inputs='map', keyframe_gate='per_pass' and f2f_queries='features'"
         self.f2f_queries = f2f_queries
+        self.rejected_frames = rejected_frames
         self.pose_inputs, self.pose_passes = pose_inputs, int(pose_passes)
         self.window_policy, self.near_dist = window_policy, float(near_dist)
         self.keyframe_gate = "per_pass" if per_pass else bool(keyframe_gate)
@@ -205,6 +214,9 @@ class KeyframePipeline:
                     self.map_feat = torch.zeros((B, self.cap), dtype=torch.int32, device=d)
                     self.map_nfeat = torch.zeros(B, dtype=torch.int32, device=d)
                     self.map_table = None   # (index into map_f2f of the last pass's table)
+                if rejected_frames == "recover":   # pred^k alternates like the tables (a pass reads the pairing its table was built on); the last pass's gaps
+                    self.map_pred = [torch.full((B,), -1, dtype=torch.int32, device=d) for _ in range(2)]
+                    self.map_gap = torch.ones(B, dtype=torch.float64, device=d)
             bb = BaBatch()
             bb.n_windows = B; bb.n_kf = n_kf
             bb.d_lm_off = self.ba_lm_off.data_ptr(); bb.d_edge_off = self.ba_e_off.data_ptr(); bb.d_T_c_w = self.ba_T.data_ptr()
@@ -317,13 +329,25 @@ class KeyframePipeline:
             self.vo.gate_states_dev(B, self.d_Tpnp.data_ptr(), 0, self.d_ninl.data_ptr(), self.ba_frame_state.data_ptr())
         prev_index, prev_inl = None, self.d_inl
         requery = self.f2f_queries == "features"
+        recover = self.rejected_frames == "recover"
+        pred_prev = None   # (stage A's table: adjacent frames)
         mt.d_f2f = self.d_f2f.data_ptr(); mt.d_nf2f = self.d_nf2f.data_ptr()   # (table^0: stage A's)
         for k in range(self.pose_passes):
             nxt = cur ^ 1
             G, Gn = self.map_G[cur], self.map_G[nxt]
             mt.d_pose_inlier = prev_inl.data_ptr(); mt.pnp_capacity = cap
             prev = None if prev_index is None else prev_index.data_ptr()
-            if requery:   # walk on table^{k-1}, re-match on its features into the other buffer, inputs on that table; the next pass walks on it
+            if recover:   # the requery pass below with every frame matched from its last accepted predecessor; pred^{k-1} / gap are outputs
+                t = k & 1
+                pred = self.map_pred[t]
+                self.vo.build_map_pnp_inputs_recover_dev(mt, G.data_ptr(), prev, None if pred_prev is None else pred_prev.data_ptr(),
+                                                         self.ba_frame_state.data_ptr(), self.d_desc.data_ptr(), cap * 32, self.map_feat.data_ptr(),
+                                                         self.map_nfeat.data_ptr(), self.map_f2f[t].data_ptr(), self.map_nf2f[t].data_ptr(),
+                                                         self.map_xyz.data_ptr(), self.map_uv.data_ptr(), self.map_n.data_ptr(), self.map_index[nxt].data_ptr(),
+                                                         cap, pred.data_ptr(), self.map_gap.data_ptr(), self.map_status.data_ptr())
+                mt.d_f2f = self.map_f2f[t].data_ptr(); mt.d_nf2f = self.map_nf2f[t].data_ptr()
+                self.map_table = t
+            elif requery:   # walk on table^{k-1}, re-match on its features into the other buffer, inputs on that table; the next pass walks on it
                 t = k & 1
                 self.vo.build_map_pnp_inputs_requery_dev(mt, G.data_ptr(), prev, self.ba_frame_state.data_ptr(), self.d_desc.data_ptr(), cap * 32,
                                                          self.map_feat.data_ptr(), self.map_nfeat.data_ptr(), self.map_f2f[t].data_ptr(),
@@ -342,10 +366,17 @@ class KeyframePipeline:
             self._solve(self.map_xyz, self.map_uv, self.map_n, self.map_T, self.map_inl[nxt], self.map_ninl, guess)
             with torch.cuda.stream(self.stream):
                 Gn[0].copy_(self.d_Tident[0])
-                Gn[1:].copy_(torch.where((self.map_ninl[:n] > 0)[:, None], self.map_T[:n], G[:n]))
+                if recover:   # no inlier: the pose of the frame matched against (a Lost frame: of the last accepted frame before the run)
+                    keep = torch.cummax(pred, 0).values.clamp(min=0)[1:].long()
+                    Gn[1:].copy_(torch.where((self.map_ninl[:n] > 0)[:, None], self.map_T[:n], G[keep]))
+                else:
+                    Gn[1:].copy_(torch.where((self.map_ninl[:n] > 0)[:, None], self.map_T[:n], G[:n]))
                 if gated and k == self.pose_passes - 1:
                     self.map_state_prev.copy_(self.ba_frame_state)
-            if gated:   # (the inputs of this pass were built from the states before: same stream, so overwriting them here is ordered)
+            if recover:   # the gate against the frame matched against, at the pair's gap, then the Lost scan
+                self.vo.gate_states_pairs_dev(B, Gn.data_ptr(), pred.data_ptr(), self.map_ninl.data_ptr(), self.ba_frame_state.data_ptr())
+                pred_prev = pred
+            elif gated:   # (the inputs of this pass were built from the states before: same stream, so overwriting them here is ordered)
                 self.vo.gate_states_dev(B, Gn.data_ptr(), 1, self.map_ninl.data_ptr(), self.ba_frame_state.data_ptr())
             prev_index, prev_inl, cur = self.map_index[nxt], self.map_inl[nxt], nxt
         self.map_cur = cur
@@ -356,6 +387,12 @@ class KeyframePipeline:
             c = self.map_cur
             mt = self.map_tracks
             mt.d_pose_inlier = self.map_inl[c].data_ptr(); mt.pnp_capacity = self.cap
+            if self.rejected_frames == "recover":   # (map_table also names the pairing the last pass's table was built on)
+                self.vo.build_windows_map_recover_dev(mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr(), self.map_pred[self.map_table].data_ptr(),
+                                                      self.ba_frame_state.data_ptr(), self.n_kf, 1 if self.window_policy == "reference" else 0, self.near_dist,
+                                                      self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(),
+                                                      self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
+                return
             if self.keyframe_gate == "per_pass":
                 self.vo.build_windows_map_gated_dev(mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr(), self.ba_frame_state.data_ptr(), self.n_kf,
                                                     1 if self.window_policy == "reference" else 0, self.near_dist, self.lm_capacity, self.edge_capacity,
@@ -462,6 +499,8 @@ class KeyframePipeline:
                 out["map_f2f"] = self.map_f2f[t].cpu().numpy().reshape(B, -1).view(DMATCH_DTYPE).reshape(B, cap)
                 out["map_nf2f"] = self.map_nf2f[t].cpu().numpy()
                 out["map_feat"] = self.map_feat.cpu().numpy(); out["map_nfeat"] = self.map_nfeat.cpu().numpy()
+                if self.rejected_frames == "recover":   # the pairing that table was built on (frame f against map_pred[f], -1: none) and its gaps
+                    out["map_pred"] = self.map_pred[t].cpu().numpy(); out["map_gap"] = self.map_gap.cpu().numpy()
             out["map_n"] = self.map_n.cpu().numpy(); out["map_xyz"] = self.map_xyz.cpu().numpy(); out["map_uv"] = self.map_uv.cpu().numpy()
             out["map_index"] = self.map_index[c].cpu().numpy(); out["map_inl"] = self.map_inl[c].cpu().numpy(); out["map_ninl"] = self.map_ninl.cpu().numpy()
             out["T_c_w"] = self.map_G[c].cpu().numpy()
