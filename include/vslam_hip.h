@@ -92,7 +92,8 @@ typedef struct vslam_ctx vslam_ctx;
 
 /* ------------------------------------------------------------------ context --------------------------- */
 void vslam_default_params(vslam_params* p);
-/* stream: a hipStream_t (as void*) to run on, or NULL to create a private one. */
+/* stream: a hipStream_t (as void*) to run on, or NULL to create a private one.  img_w, img_h in [64, 4095]; a context with a smaller image (each side
+ * >= 2) serves the rectification stage and the entry points that take no context-sized image, and its ORB entry points return VSLAM_ERR_ARG. */
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out);
 void vslam_destroy(vslam_ctx* ctx);
 const char* vslam_last_error(void);
@@ -103,6 +104,71 @@ int vslam_sync(vslam_ctx* ctx);
 size_t vslam_device_bytes(const vslam_ctx* ctx);
 /* name of the GPU kernel families, for profiling cross-reference (NUL separated list not needed: static string) */
 const char* vslam_kernel_names(void);
+
+/* ------------------------------------------------------------------ rectification: raw pairs -> rectified pairs --- */
+/* Every stage below assumes a rectified, undistorted stereo pair (SGBM searches along the row, the L/R matcher gates on |vL - vR|, vslam_triangulate
+ * is the rectified-stereo DLT, find_3d is z = fx b / d).  The reference can assume it because KITTI odometry ships rectified images
+ * and it reads them as they are; a rig that is not KITTI delivers raw images.  This stage has no counterpart in the
+ * reference: it is the published arithmetic of OpenCV's initUndistortRectifyMap(K, D, R, P, size, CV_16SC2) followed by
+ * remap(INTER_LINEAR, BORDER_CONSTANT, 0) on 8-bit gray images, restated -- PARITY UNPINNED like the rest of the tree (no OpenCV to compare with;
+ * the tests' yardstick is the numpy restatement tests/rectify_ref.py).  Additive: vslam_params and the ABI version are unchanged.
+ * Map, per camera and destination pixel (x, y), in double:
+ *   P3 = [[fx', 0, cx'], [0, fy', cy'], [0, 0, 1]], M = (P3 R)^-1, (X, Y, W) = M (x, y, 1), xn = X / W, yn = Y / W, r2 = xn^2 + yn^2,
+ *   kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2),
+ *   xd = xn kr + 2 p1 xn yn + p2 (r2 + 2 xn^2), yd = yn kr + p1 (r2 + 2 yn^2) + 2 p2 xn yn, u = fx xd + cx, v = fy yd + cy,
+ *   iu = rint(32 u), iv = rint(32 v) (half to even; clipped to +-2^40 first), sx = iu >> 5 (arithmetic), ax = iu & 31, likewise sy, ay;
+ *   sx, sy saturate to int16; a non-finite u or v makes the entry "outside": sx = sy = -32768, ax = ay = 0.
+ *   Stored as xy (h x w x 2 int16: sx, sy) and frac (h x w uint16: ay * 32 + ax) -- the CV_16SC2 + CV_16UC1 pair.
+ * Remap: dst(x, y) = (w00 S(sx, sy) + w10 S(sx + 1, sy) + w01 S(sx, sy + 1) + w11 S(sx + 1, sy + 1) + 512) >> 10 with w00 = (32 - ax)(32 - ay),
+ *   w10 = ax (32 - ay), w01 = (32 - ax) ay, w11 = ax ay; S reads 0 for any tap outside [0, src_w) x [0, src_h), per tap; integers throughout. */
+typedef struct vslam_rectify_cam {
+    double K[4];                   /* fx fy cx cy of the RAW camera                                                          */
+    double D[8];                   /* k1 k2 p1 p2 k3 k4 k5 k6: OpenCV's order of the rational distortion model (zeros = none) */
+    double R[9];                   /* rectifying rotation, row-major (cv::stereoRectify's R1 / R2); identity = undistort only */
+    double P[4];                   /* fx' fy' cx' cy' of the RECTIFIED camera (the left 3 x 3 of P1 / P2)                     */
+} vslam_rectify_cam;
+typedef struct vslam_rectify_params {
+    int32_t src_w, src_h;          /* raw image size, each in [2, 4096]                                                       */
+    vslam_rectify_cam cam[2];      /* 0 = left, 1 = right                                                                     */
+    int32_t struct_size;           /* sizeof(vslam_rectify_params) of the caller's header; set by vslam_default_rectify_params, checked */
+} vslam_rectify_params;
+
+/* the identity rig at the KITTI camera and 1241 x 376: D = 0, R = I, P = K = vslam_default_params' cam -- its map is the identity */
+void vslam_default_rectify_params(vslam_rectify_params* p);
+
+/* Is the rig admissible for dst_w x dst_h rectified images?  Host arithmetic only: no context, no GPU.  VSLAM_OK, or VSLAM_ERR_ARG with
+ * vslam_last_error() naming the offending field: struct_size mismatch; src_w, src_h, dst_w or dst_h outside [2, 4096]; a non-finite entry
+ * anywhere; fx, fy, fx' or fy' <= 0; R not a rotation (max |R R^T - I| > 1e-6 or det R <= 0). */
+int vslam_rectify_params_check(const vslam_rectify_params* p, int dst_w, int dst_h);
+
+/* The map of camera `cam` (0 | 1) for dst_w x dst_h rectified images, in host memory: xy dst_h x dst_w x 2 int16, frac dst_h x dst_w uint16, tightly
+ * packed.  Host arithmetic in double, no context, no GPU; vslam_rectify_params_check runs first.  Once per rig: not a hot path. */
+int vslam_rectify_build_maps(const vslam_rectify_params* p, int cam, int dst_w, int dst_h, int16_t* xy, uint16_t* frac);
+
+/* Check, build both maps for the context's img_w x img_h and upload them.  The two maps are context state (8 bytes per destination pixel and
+ * camera, counted by vslam_device_bytes, not part of the growable scratch).  A refused rig launches nothing and leaves maps already set in place.
+ * Synchronises the context stream (a launch may still read the maps it replaces). */
+int vslam_rectify_set(vslam_ctx* ctx, const vslam_rectify_params* p);
+
+/* A caller's own maps for camera `cam` (e.g. cv::initUndistortRectifyMap's CV_16SC2 output for another lens model): xy img_h x img_w x 2 int16, frac
+ * img_h x img_w uint16 (< 1024), host memory, for src_w x src_h raw images (each in [2, 4096]).  Any int16 coordinates are valid (taps outside the
+ * source read 0).  Refused with VSLAM_ERR_ARG: cam outside 0 | 1, a null pointer, a source size out of range, a frac entry >= 1024. */
+int vslam_rectify_set_maps(vslam_ctx* ctx, int cam, const int16_t* xy, const uint16_t* frac, int src_w, int src_h);
+
+/* One raw image of camera `cam` (host, src_h rows of src_stride bytes) -> the rectified image (host, img_h rows of dst_stride bytes, img_w bytes
+ * written per row).  Synchronous; the same kernel as the batched call.  VSLAM_ERR_ARG before that camera's map is set. */
+int vslam_rectify(vslam_ctx* ctx, int cam, const uint8_t* src, int src_stride, uint8_t* dst, int dst_stride);
+
+/* Batched, device-resident: B raw pairs, image b of a side at d_src_* + b * src_img_bytes (src_h rows of src_pitch bytes), to B rectified pairs at
+ * d_dst_* + b * dst_img_bytes (img_h rows of dst_pitch bytes; the padding bytes from img_w to dst_pitch are written as 0, so the output can go
+ * straight into vslam_feature_detection_dev / vslam_disparity_map_dev).  Either side's pair of pointers may be NULL: that camera is skipped.
+ * One launch for both sides; asynchronous on the context stream.  A lane applies its decoded map entries to a group of images of the batch, so
+ * the cost per image falls with B up to a few groups per CU.  Destinations whose base, dst_pitch and dst_img_bytes are multiples of 4 are written
+ * with dword stores, anything else byte by byte (same result, slower).
+ * Refused with VSLAM_ERR_ARG: a side given before its map is set, both sides NULL, one pointer of a side NULL and the other not, B < 1 or
+ * B > max_batch, src_pitch < src_w, dst_pitch < img_w, src_img_bytes < src_pitch x src_h (or >= 4 GiB), dst_img_bytes < dst_pitch x img_h. */
+int vslam_rectify_dev(vslam_ctx* ctx, const uint8_t* d_src_left, const uint8_t* d_src_right, size_t src_img_bytes, int src_pitch, int B,
+                      uint8_t* d_dst_left, uint8_t* d_dst_right, size_t dst_img_bytes, int dst_pitch);
 
 /* ------------------------------------------------------------------ A1+A2+A3: VO::feature_detection --- */
 /* Replaces the body of VO::feature_detection (visual_odometry.cpp:70-94) minus the GUI calls:
@@ -662,7 +728,7 @@ int vslam_ba_deferred_dev(vslam_ctx* ctx, int n_windows, int32_t* h_deferred);
 int vslam_edge_jacobians(vslam_ctx* ctx, int n, const float* xyz_w, const float* uv, const double T_c_w[7], const double* K4,
                          double* err, double* J_pose, double* J_point, double* chi2, double* huber_w);
 /* Kernel-choice overrides of a context (tuning aid, and how the tests force every kernel path): name in {"orb_fuse_min", "sgbm_fuse_min",
- * "sgbm_fwd_min" (items per call from which the fused kernel is used), "sgbm_fw_rows" (32 | 64), "pose_only_window", "pnp_window", "ba_adaptive" (0 | 1), "ba_lanes" (256 | 512: lanes per window of the
+ * "sgbm_fwd_min" (items per call from which the fused kernel is used), "sgbm_fw_rows" (32 | 64), "pose_only_window", "pnp_window", "ba_adaptive" (0 | 1), "rectify_form" (0 | 1: source side of the rectification kernel, direct gathers | source boxes staged in LDS; same bytes), "ba_lanes" (256 | 512: lanes per window of the
  * LDS-resident optimize_map kernel; default by the number of windows in the call; the results do not depend on it), "track_rule" (0 | 1: see
  * vslam_build_windows_dev; this one changes RESULTS, it is the before / after switch of round 6)};
  * value -1 = the library's batch-size rule.  vslam_create seeds them once from the environment variables VSLAM_<NAME> (an unparsable

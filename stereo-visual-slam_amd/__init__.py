@@ -44,6 +44,17 @@ class SgbmParams(C.Structure):
         return tuple(getattr(self, f) for f, _ in self._fields_[:9])
 
 
+class RectifyCam(C.Structure):
+    """vslam_rectify_cam: one camera of a raw stereo rig -- K (fx fy cx cy, raw), D (k1 k2 p1 p2 k3 k4 k5 k6), R (rectifying rotation,
+    row-major), P (fx' fy' cx' cy', rectified)"""
+    _fields_ = [("K", C.c_double * 4), ("D", C.c_double * 8), ("R", C.c_double * 9), ("P", C.c_double * 4)]
+
+
+class RectifyParams(C.Structure):
+    """vslam_rectify_params: the raw image size and the two cameras (0 = left, 1 = right)"""
+    _fields_ = [("src_w", C.c_int32), ("src_h", C.c_int32), ("cam", RectifyCam * 2), ("struct_size", C.c_int32)]
+
+
 ABI_VERSION = 5  # VSLAM_ABI_VERSION of include/vslam_hip.h this binding was written against
 
 
@@ -109,6 +120,13 @@ SIGNATURES = {
     "vslam_destroy": (None, [P]),
     "vslam_last_error": (C.c_char_p, []), "vslam_version": (C.c_char_p, []), "vslam_abi_version": (I, []), "vslam_sync": (I, [P]),
     "vslam_device_bytes": (Z, [P]), "vslam_kernel_names": (C.c_char_p, []),
+    "vslam_default_rectify_params": (None, [P]),
+    "vslam_rectify_params_check": (I, [P, I, I]),
+    "vslam_rectify_build_maps": (I, [P, I, I, I, P, P]),
+    "vslam_rectify_set": (I, [P, P]),
+    "vslam_rectify_set_maps": (I, [P, I, P, P, I, I]),
+    "vslam_rectify": (I, [P, I, P, I, P, I]),
+    "vslam_rectify_dev": (I, [P, P, P, Z, I, I, P, P, Z, I]),
     "vslam_feature_detection": (I, [P, P, I, I, I, P, P, I, P]),
     "vslam_orb_detect": (I, [P, P, I, I, I, P, I, P]),
     "vslam_anms": (I, [P, P, I, I, P]),
@@ -252,6 +270,44 @@ def sgbm_params_check(p, w, h):
     return True
 
 
+def default_rectify_params(src_w=None, src_h=None, cams=None):
+    """the identity rig at the KITTI camera and 1241 x 376 (its map is the identity), fields overridden: src_w / src_h, and cams = two dicts
+    with any of K (4), D (up to 8), R (3 x 3 or 9) and P (4)"""
+    p = RectifyParams()
+    load_library().vslam_default_rectify_params(C.byref(p))
+    if src_w is not None:
+        p.src_w = int(src_w)
+    if src_h is not None:
+        p.src_h = int(src_h)
+    for s, cam in enumerate(cams or ()):
+        for name, vals in cam.items():
+            arr = getattr(p.cam[s], name)
+            vals = np.asarray(vals, np.float64).ravel()
+            assert len(vals) <= len(arr), (name, len(vals))
+            for i in range(len(arr)):
+                arr[i] = float(vals[i]) if i < len(vals) else 0.0
+    return p
+
+
+def rectify_params_check(p, w, h):
+    """vslam_rectify_params_check: is the rig admissible for w x h rectified images?  Host arithmetic, needs no GPU.  Raises VslamError naming the field."""
+    lib = load_library()
+    rc = lib.vslam_rectify_params_check(C.byref(p), w, h)
+    if rc != VSLAM_OK:
+        raise VslamError("vslam_rectify_params_check failed (%d): %s" % (rc, lib.vslam_last_error().decode()))
+    return True
+
+
+def rectify_build_maps(p, cam, w, h):
+    """vslam_rectify_build_maps: (xy (h, w, 2) int16, frac (h, w) uint16) of camera `cam` for w x h rectified images.  Host arithmetic, needs no GPU."""
+    lib = load_library()
+    xy = np.zeros((max(h, 0), max(w, 0), 2), np.int16); frac = np.zeros((max(h, 0), max(w, 0)), np.uint16)
+    rc = lib.vslam_rectify_build_maps(C.byref(p), cam, w, h, xy, frac)
+    if rc != VSLAM_OK:
+        raise VslamError("vslam_rectify_build_maps failed (%d): %s" % (rc, lib.vslam_last_error().decode()))
+    return xy, frac
+
+
 def _desc(d):
     d = np.ascontiguousarray(d, np.uint8)
     if d.size == 0:
@@ -393,6 +449,29 @@ class VO:
         else:
             self._chk(self.lib.vslam_disparity_map_ex_dev(self.h, d_left, d_right, img_stride_bytes, pitch, w, h, B, C.byref(_sgbm_params(sgbm)), d_disp, d_i16, d_raw),
                       "vslam_disparity_map_ex_dev")
+
+    # ------------------------------------------------------------ rectification: raw pairs -> rectified pairs (no counterpart in the reference)
+    def rectify_set(self, params):
+        """check the rig, build both maps for the context's image size and upload them (vslam_rectify_set)"""
+        self._chk(self.lib.vslam_rectify_set(self.h, C.byref(params)), "vslam_rectify_set")
+
+    def rectify_set_maps(self, cam, xy, frac, src_w, src_h):
+        """a caller's own maps for camera `cam`: xy (img_h, img_w, 2) int16, frac (img_h, img_w) uint16, for src_w x src_h raw images"""
+        xy = np.ascontiguousarray(xy, np.int16); frac = np.ascontiguousarray(frac, np.uint16)
+        assert xy.shape == (self.params.img_h, self.params.img_w, 2) and frac.shape == xy.shape[:2], (xy.shape, frac.shape)
+        self._chk(self.lib.vslam_rectify_set_maps(self.h, cam, xy, frac, src_w, src_h), "vslam_rectify_set_maps")
+
+    def rectify(self, img, cam):
+        """one raw image of camera `cam` -> the rectified img_h x img_w image (host buffers; the batched call's kernel)"""
+        img = self._img(img)
+        out = np.zeros((self.params.img_h, self.params.img_w), np.uint8)
+        self._chk(self.lib.vslam_rectify(self.h, cam, img, img.strides[0], out, out.strides[0]), "vslam_rectify")
+        return out
+
+    def rectify_dev(self, d_src_left, d_src_right, src_img_bytes, src_pitch, B, d_dst_left, d_dst_right, dst_img_bytes, dst_pitch):
+        """B raw pairs -> B rectified pairs, device-resident, asynchronous; a side whose two pointers are None is skipped (include/vslam_hip.h)"""
+        self._chk(self.lib.vslam_rectify_dev(self.h, d_src_left, d_src_right, src_img_bytes, src_pitch, B, d_dst_left, d_dst_right, dst_img_bytes, dst_pitch),
+                  "vslam_rectify_dev")
 
     def set_tuning(self, **kw):
         """kernel-choice overrides of this context, e.g. set_tuning(sgbm_fwd_min=1, sgbm_fw_rows=32); -1 = library default"""

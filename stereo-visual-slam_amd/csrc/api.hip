@@ -124,6 +124,7 @@ static const TuneKey kTuneKeys[] = {
     {"ba_adaptive", "VSLAM_BA_ADAPTIVE", &Tuning::ba_adaptive, 0, 1},
     {"ba_lanes", "VSLAM_BA_LANES", &Tuning::ba_lanes, 256, 512},
     {"track_rule", "VSLAM_TRACK_RULE", &Tuning::track_rule, 0, 1},
+    {"rectify_form", "VSLAM_RECTIFY_FORM", &Tuning::rectify_form, 0, 1},
 };
 static int tune_set(Tuning& t, const TuneKey& k, long v) {
     if (v == -1) { t.*(k.field) = -1; return VSLAM_OK; } // back to the library's rule
@@ -198,6 +199,7 @@ static int orb_pipeline(Ctx* c, const uint8_t* d_imgs, size_t img_bytes, int pit
 
 static int check_img(Ctx* c, const void* img, int w, int h, int stride) {
     if (!c || !img) { set_error("null context or image"); return VSLAM_ERR_ARG; }
+    if (!c->orb_ok) { set_error("the context's %dx%d image is below ORB's 64x64: it serves the rectification stage and the image-free entry points only", c->p.img_w, c->p.img_h); return VSLAM_ERR_ARG; }
     if (w != c->p.img_w || h != c->p.img_h || stride < w) { set_error("image %dx%d (stride %d) does not match the context's %dx%d", w, h, stride, c->p.img_w, c->p.img_h); return VSLAM_ERR_ARG; }
     return VSLAM_OK;
 }
@@ -231,7 +233,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
-           "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel";
+           "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -258,7 +260,11 @@ int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** ou
         c->own_stream = true;
     }
     if (getenv("VSLAM_ORB_PROFILE")) orb_debug_enable();
-    int rc = orb_plan_init(&c->plan, p->img_w, p->img_h, p->orb_nfeatures, p->kp_capacity);
+    // An image below ORB's 64 x 64 (a small rectification target): the ORB plan and buffers are laid out for the 64 x 64 minimum so that every
+    // pointer of the context exists, and the ORB entry points refuse the context (check_img, vslam_feature_detection_dev, vslam_orb_level).
+    c->orb_ok = p->img_w >= 64 && p->img_h >= 64;
+    if (p->img_w < 2 || p->img_h < 2) { set_error("image size %dx%d unsupported (2..4095; ORB needs 64..4095)", p->img_w, p->img_h); vslam_destroy(reinterpret_cast<vslam_ctx*>(c)); return VSLAM_ERR_ARG; }
+    int rc = orb_plan_init(&c->plan, std::max(p->img_w, 64), std::max(p->img_h, 64), p->orb_nfeatures, p->kp_capacity);
     if (rc == VSLAM_OK) { rc = orb_tables_init(&c->plan, &c->tab); c->dev_bytes += c->tab.bytes; }
     const size_t B = (size_t)p->max_batch;
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_pyr, B * c->plan.pyr_bytes);
@@ -286,7 +292,7 @@ void vslam_destroy(vslam_ctx* ctx) {
     for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc}) b->release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
     void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad,
-                    c->match.d_train_best};
+                    c->match.d_train_best, c->rect.d_map[0], c->rect.d_map[1], c->rect.d_tiles[0], c->rect.d_tiles[1]};
     for (void* q : ptrs) if (q) hipFree(q);
     if (c->prof) {
         if (prof_current() == c->prof) prof_set_current(nullptr);
@@ -445,7 +451,7 @@ int vslam_orb_compute(vslam_ctx* ctx, const uint8_t* img, int w, int h, int stri
 int vslam_feature_detection_dev(vslam_ctx* ctx, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, vslam_keypoint* d_kps,
                                 uint8_t* d_desc, int32_t* d_count) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !d_imgs || !d_kps || !d_desc || !d_count || pitch < c->p.img_w || img_bytes < (size_t)pitch * c->p.img_h) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!c || !d_imgs || !d_kps || !d_desc || !d_count || pitch < c->p.img_w || img_bytes < (size_t)pitch * c->p.img_h || !c->orb_ok) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     return orb_pipeline(c, d_imgs, img_bytes, pitch, B, c->p.anms_num, 1, true, d_kps, d_desc, d_count);
 }
@@ -461,7 +467,7 @@ int vslam_orb_status_dev(vslam_ctx* ctx, int B, int32_t* h_status) {
 
 int vslam_orb_level(vslam_ctx* ctx, int item, int level, int blurred, uint8_t* out, int out_stride, int out_rows, int* w, int* h) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !out || !w || !h || item < 0 || item >= c->p.max_batch || level < 0 || level >= kNLevels || (level == 0 && !blurred)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!c || !out || !w || !h || item < 0 || item >= c->p.max_batch || level < 0 || level >= kNLevels || (level == 0 && !blurred) || !c->orb_ok) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     const OrbLevel& L = c->plan.lv[level];
     if (out_stride < L.w || out_rows < L.h) { set_error("vslam_orb_level: level %d is %d x %d", level, L.w, L.h); return VSLAM_ERR_CAPACITY; }
@@ -669,6 +675,160 @@ int vslam_sgbm_status_dev(vslam_ctx* ctx, int32_t* h_status) {
     VS_HIP(hipMemcpyAsync(h_status, reinterpret_cast<const int32_t*>(c->sgbm.p) + kSgbmErrorWord, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipStreamSynchronize(c->stream));
     if (*h_status != 0) { set_error("sgbm_forward_kernel: a slab waited for its predecessor beyond the spin limit; the disparity maps of this call are void"); return VSLAM_ERR_HIP; }
+    return VSLAM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- rectification
+void vslam_default_rectify_params(vslam_rectify_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->src_w = 1241; p->src_h = 376;
+    for (vslam_rectify_cam& c : p->cam) {
+        c.K[0] = c.P[0] = 718.856; c.K[1] = c.P[1] = 718.856; c.K[2] = c.P[2] = 607.1928; c.K[3] = c.P[3] = 185.2157; // vslam_default_params' cam
+        c.R[0] = c.R[4] = c.R[8] = 1.0;
+    }
+    p->struct_size = (int32_t)sizeof(vslam_rectify_params);
+}
+
+int vslam_rectify_params_check(const vslam_rectify_params* p, int dst_w, int dst_h) {
+    if (!p) { set_error("vslam_rectify_params: null pointer"); return VSLAM_ERR_ARG; }
+    if (p->struct_size != (int32_t)sizeof(vslam_rectify_params)) {
+        set_error("vslam_rectify_params.struct_size = %d: not this library's sizeof(vslam_rectify_params) = %d", p->struct_size, (int)sizeof(vslam_rectify_params));
+        return VSLAM_ERR_ARG;
+    }
+    auto size_ok = [](const char* field, int v) {
+        if (v >= 2 && v <= 4096) return true;
+        set_error("vslam_rectify_params: %s = %d outside [2, 4096]", field, v);
+        return false;
+    };
+    if (!size_ok("src_w", p->src_w) || !size_ok("src_h", p->src_h) || !size_ok("dst_w", dst_w) || !size_ok("dst_h", dst_h)) return VSLAM_ERR_ARG;
+    for (int s = 0; s < 2; ++s) {
+        const vslam_rectify_cam& c = p->cam[s];
+        const struct { const char* name; const double* v; int n; } arrays[] = {{"K", c.K, 4}, {"D", c.D, 8}, {"R", c.R, 9}, {"P", c.P, 4}};
+        for (const auto& a : arrays)
+            for (int i = 0; i < a.n; ++i)
+                if (!std::isfinite(a.v[i])) { set_error("vslam_rectify_params.cam[%d].%s[%d] is not finite", s, a.name, i); return VSLAM_ERR_ARG; }
+        for (int i = 0; i < 2; ++i) {
+            if (!(c.K[i] > 0)) { set_error("vslam_rectify_params.cam[%d].K[%d] = %g: the focal length must be > 0", s, i, c.K[i]); return VSLAM_ERR_ARG; }
+            if (!(c.P[i] > 0)) { set_error("vslam_rectify_params.cam[%d].P[%d] = %g: the rectified focal length must be > 0", s, i, c.P[i]); return VSLAM_ERR_ARG; }
+        }
+        double err, det;
+        rectify_rotation_error(c.R, &err, &det);
+        if (err > 1e-6 || !(det > 0)) {
+            set_error("vslam_rectify_params.cam[%d].R is not a rotation: max |R R^T - I| = %g (need <= 1e-6), det = %g (need > 0)", s, err, det);
+            return VSLAM_ERR_ARG;
+        }
+    }
+    return VSLAM_OK;
+}
+
+int vslam_rectify_build_maps(const vslam_rectify_params* p, int cam, int dst_w, int dst_h, int16_t* xy, uint16_t* frac) {
+    if (int rc = vslam_rectify_params_check(p, dst_w, dst_h)) return rc;
+    if ((cam != 0 && cam != 1) || !xy || !frac) { set_error("vslam_rectify_build_maps: cam must be 0 or 1, xy and frac non-null"); return VSLAM_ERR_ARG; }
+    rectify_build_map(p->cam[cam], dst_w, dst_h, xy, frac);
+    return VSLAM_OK;
+}
+
+// Source side of rectify_kernel: 0 = direct gathers, 1 = LDS-staged boxes (0.93 vs 2.87 ms per 1024 raw pairs; tiles without a box and
+// unaligned sources gather); Tuning::rectify_form overrides it (tests and tools/bench_rectify.py run both)
+constexpr int kRectifyFormDefault = 1;
+static int rectify_form(const Ctx* c) { return c->tune.rectify_form >= 0 ? c->tune.rectify_form : kRectifyFormDefault; }
+
+// pack + upload one camera's map (allocates the context's slot on first use; the stream is idle when the old entries are overwritten)
+static int rectify_upload(Ctx* c, int cam, const std::vector<uint2>& packed, int src_w, int src_h) {
+    std::vector<int4> tiles((size_t)rectify_tiles_x(c->p.img_w) * ((c->p.img_h + 3) / 4));
+    rectify_tile_boxes(packed.data(), c->p.img_w, c->p.img_h, tiles.data());
+    VS_HIP(hipStreamSynchronize(c->stream));
+    if (!c->rect.d_map[cam]) { int rc = dev_alloc(c, &c->rect.d_map[cam], packed.size()); if (rc) return rc; }
+    if (!c->rect.d_tiles[cam]) { int rc = dev_alloc(c, &c->rect.d_tiles[cam], tiles.size()); if (rc) return rc; }
+    VS_HIP(hipMemcpy(c->rect.d_map[cam], packed.data(), packed.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    VS_HIP(hipMemcpy(c->rect.d_tiles[cam], tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice));
+    c->rect.src_w[cam] = src_w; c->rect.src_h[cam] = src_h;
+    return VSLAM_OK;
+}
+
+int vslam_rectify_set(vslam_ctx* ctx, const vslam_rectify_params* p) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("null context"); return VSLAM_ERR_ARG; }
+    const int w = c->p.img_w, h = c->p.img_h;
+    if (int rc = vslam_rectify_params_check(p, w, h)) return rc;
+    VS_ENTER(c);
+    std::vector<uint2> packed[2];
+    std::vector<int16_t> xy((size_t)w * h * 2);
+    std::vector<uint16_t> frac((size_t)w * h);
+    for (int s = 0; s < 2; ++s) { // (both maps exist on the host before the first one replaces anything on the device)
+        rectify_build_map(p->cam[s], w, h, xy.data(), frac.data());
+        packed[s].resize((size_t)rectify_map_pitch(w) * h);
+        rectify_pack_map(xy.data(), frac.data(), w, h, p->src_w, p->src_h, packed[s].data());
+    }
+    for (int s = 0; s < 2; ++s)
+        if (int rc = rectify_upload(c, s, packed[s], p->src_w, p->src_h)) return rc;
+    return VSLAM_OK;
+}
+
+int vslam_rectify_set_maps(vslam_ctx* ctx, int cam, const int16_t* xy, const uint16_t* frac, int src_w, int src_h) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !xy || !frac || (cam != 0 && cam != 1)) { set_error("vslam_rectify_set_maps: null argument or cam outside 0 | 1"); return VSLAM_ERR_ARG; }
+    if (src_w < 2 || src_w > 4096 || src_h < 2 || src_h > 4096) { set_error("vslam_rectify_set_maps: source size %d x %d outside [2, 4096]", src_w, src_h); return VSLAM_ERR_ARG; }
+    const int w = c->p.img_w, h = c->p.img_h;
+    for (size_t i = 0; i < (size_t)w * h; ++i)
+        if (frac[i] >= 1024) { set_error("vslam_rectify_set_maps: frac[%zu] = %d is not ay * 32 + ax with ax, ay < 32", i, (int)frac[i]); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    std::vector<uint2> packed((size_t)rectify_map_pitch(w) * h);
+    rectify_pack_map(xy, frac, w, h, src_w, src_h, packed.data());
+    return rectify_upload(c, cam, packed, src_w, src_h);
+}
+
+int vslam_rectify_dev(vslam_ctx* ctx, const uint8_t* d_src_left, const uint8_t* d_src_right, size_t src_img_bytes, int src_pitch, int B,
+                      uint8_t* d_dst_left, uint8_t* d_dst_right, size_t dst_img_bytes, int dst_pitch) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("null context"); return VSLAM_ERR_ARG; }
+    const uint8_t* src[2] = {d_src_left, d_src_right};
+    uint8_t* dst[2] = {d_dst_left, d_dst_right};
+    if ((!src[0] != !dst[0]) || (!src[1] != !dst[1]) || (!src[0] && !src[1])) {
+        set_error("vslam_rectify_dev: a side is its source AND its destination pointer (both NULL = skipped), and at least one side is needed"); return VSLAM_ERR_ARG;
+    }
+    if (B < 1 || B > c->p.max_batch) { set_error("batch %d outside 1..max_batch %d", B, c->p.max_batch); return VSLAM_ERR_ARG; }
+    RectifyLaunch L{};
+    for (int s = 0; s < 2; ++s) {
+        if (!src[s]) continue;
+        if (!c->rect.d_map[s]) { set_error("vslam_rectify_dev: no map set for camera %d (vslam_rectify_set / vslam_rectify_set_maps)", s); return VSLAM_ERR_ARG; }
+        if (src_pitch < c->rect.src_w[s] || src_img_bytes < (size_t)src_pitch * c->rect.src_h[s] || (uint64_t)src_pitch * c->rect.src_h[s] > 0xFFFFFFFFull) {
+            set_error("vslam_rectify_dev: src_pitch %d / src_img_bytes %zu do not hold camera %d's %d x %d source", src_pitch, src_img_bytes, s, c->rect.src_w[s], c->rect.src_h[s]);
+            return VSLAM_ERR_ARG;
+        }
+        L.map[s] = c->rect.d_map[s]; L.tiles[s] = c->rect.d_tiles[s]; L.src[s] = src[s]; L.dst[s] = dst[s];
+    }
+    if (dst_pitch < c->p.img_w || dst_img_bytes < (size_t)dst_pitch * c->p.img_h) {
+        set_error("vslam_rectify_dev: dst_pitch %d / dst_img_bytes %zu do not hold the context's %d x %d image", dst_pitch, dst_img_bytes, c->p.img_w, c->p.img_h);
+        return VSLAM_ERR_ARG;
+    }
+    VS_ENTER(c);
+    L.form = rectify_form(c);
+    L.w = c->p.img_w; L.h = c->p.img_h; L.B = B; L.src_pitch = src_pitch; L.dst_pitch = dst_pitch; L.src_img_bytes = src_img_bytes; L.dst_img_bytes = dst_img_bytes;
+    return launch_rectify(L, c->stream);
+}
+
+int vslam_rectify(vslam_ctx* ctx, int cam, const uint8_t* src, int src_stride, uint8_t* dst, int dst_stride) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !src || !dst || (cam != 0 && cam != 1)) { set_error("vslam_rectify: null argument or cam outside 0 | 1"); return VSLAM_ERR_ARG; }
+    if (!c->rect.d_map[cam]) { set_error("vslam_rectify: no map set for camera %d (vslam_rectify_set / vslam_rectify_set_maps)", cam); return VSLAM_ERR_ARG; }
+    const int sw = c->rect.src_w[cam], sh = c->rect.src_h[cam], w = c->p.img_w, h = c->p.img_h;
+    if (src_stride < sw || dst_stride < w) { set_error("vslam_rectify: src_stride %d < %d or dst_stride %d < %d", src_stride, sw, dst_stride, w); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    int rc;
+    const int sp = img_pitch(sw), dp = img_pitch(w);
+    uint8_t *d_s, *d_d;
+    if ((rc = arena_stage(c, [&](Arena& a) { d_s = a.take<uint8_t>((size_t)sp * sh); d_d = a.take<uint8_t>((size_t)dp * h); }))) return rc;
+    if ((rc = upload_image(c, d_s, src, sw, sh, src_stride))) return rc;
+    RectifyLaunch L{};
+    L.map[cam] = c->rect.d_map[cam]; L.tiles[cam] = c->rect.d_tiles[cam]; L.src[cam] = d_s; L.dst[cam] = d_d; L.form = rectify_form(c);
+    L.w = w; L.h = h; L.B = 1; L.src_pitch = sp; L.dst_pitch = dp; L.src_img_bytes = (size_t)sp * sh; L.dst_img_bytes = (size_t)dp * h;
+    if ((rc = launch_rectify(L, c->stream))) return rc;
+    std::vector<uint8_t> out((size_t)dp * h);
+    VS_HIP(hipMemcpyAsync(out.data(), d_d, out.size(), hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    for (int y = 0; y < h; ++y) memcpy(dst + (size_t)y * dst_stride, out.data() + (size_t)y * dp, (size_t)w);
     return VSLAM_OK;
 }
 

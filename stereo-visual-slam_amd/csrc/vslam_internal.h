@@ -247,6 +247,7 @@ struct Tuning {
                               // (visual_odometry.cpp:568-599): whenever the last-frame keypoint is a feature -- created there or tracked into it; one without a depth of its own
                               // is judged by the pose stage's inlier rule on its landmark's map position (:260-270, :277).  0 = the convention of rounds 4-5: only when the
                               // last-frame keypoint owns a valid depth (kept for before / after measurements)
+    int rectify_form = -1;    // VSLAM_RECTIFY_FORM: source side of rectify_kernel -- 0 = direct byte gathers, 1 = each tile's source box staged in LDS (default 1; tiles whose box does not pay gather either way)
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
 };
 // scratch: the context's SGBM buffer.  Its first 256-byte slot is a header of int32 words: the forward sweep's ticket pools, then its error word.
@@ -344,6 +345,22 @@ int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const in
                           double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
                           int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq = nullptr, const MapRecover* rv = nullptr);
 
+// ----------------------------------------------------------------------------------------------- rectification
+// rectify_kernels.hip: the map builder (host, double, once per rig), the device entry format and the gather kernel
+constexpr int kRectifyGroup = 8;   // images of the batch one lane applies its decoded map entries to
+void rectify_rotation_error(const double R[9], double* ortho_err, double* det);
+void rectify_build_map(const vslam_rectify_cam& cam, int dst_w, int dst_h, int16_t* xy, uint16_t* frac);
+int rectify_map_pitch(int dst_w);  // entries per row of a device map: dst_w rounded up to 4
+void rectify_pack_map(const int16_t* xy, const uint16_t* frac, int dst_w, int dst_h, int src_w, int src_h, uint2* out);
+int rectify_tiles_x(int dst_w);    // 256 x 4 destination tiles per tile row
+void rectify_tile_boxes(const uint2* packed, int dst_w, int dst_h, int4* tiles); // per tile the source box to stage in LDS, or zeros: gather directly
+// side s (0 left, 1 right) is skipped when any of its three pointers is null; w x h: the destination size the maps were built for
+// form: 0 = direct gathers, 1 = the tiles' source boxes staged in LDS (tiles[s] required; falls back to 0 for sources that are not 16-byte aligned)
+struct RectifyLaunch { const uint2* map[2]; const int4* tiles[2]; const uint8_t* src[2]; uint8_t* dst[2]; int w, h, B, src_pitch, dst_pitch, form;
+                       size_t src_img_bytes, dst_img_bytes; };
+int launch_rectify(const RectifyLaunch& L, hipStream_t stream);
+struct RectifyState { uint2* d_map[2]; int4* d_tiles[2]; int src_w[2], src_h[2]; };  // the two maps of a context (null until set), counted in dev_bytes
+
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {
     vslam_params p;
@@ -364,6 +381,8 @@ struct Ctx {
     LmScratch lm{&dev_bytes};
     Tuning tune;
     Prof* prof;           // stage profiler of this context (vslam_profile_enable); null until first enabled
+    RectifyState rect;    // vslam_rectify_set / vslam_rectify_set_maps
+    bool orb_ok;          // img_w, img_h >= 64: the ORB entry points serve this context (a smaller one is a rectification target only)
 };
 
 } // namespace vslam

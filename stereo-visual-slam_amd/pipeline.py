@@ -26,7 +26,8 @@ class KeyframePipeline:
     def __init__(self, B, device=0, anms_num=1500, n_lm=3000, n_kf=10, unique_frames=64, unique_windows=None, seed=0, verbose=False,
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
                  lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
-                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all", sgbm_params=None, rejected_frames="pass_through"):
+                 keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all", sgbm_params=None, rejected_frames="pass_through",
+                 rectify=None, raw_images=None):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
         sgbm_params (depth="sgbm"): the StereoSGBM set of the batched disparity call -- an SgbmParams, a dict of its fields or a tuple
@@ -59,7 +60,11 @@ class KeyframePipeline:
         is matched at frame_gap 1); "recover" (pose_inputs="map", keyframe_gate="per_pass", f2f_queries="features") -- the reference's failure handling
         (visual_odometry.cpp:630-637, :673-693): a rejected frame and its features are dropped, the next frame is matched against the features of the last
         ACCEPTED frame at their real frame gap, more than ten rejections in a row end in the Lost state 3 (vslam_build_map_pnp_inputs_recover_dev,
-        vslam_gate_states_pairs_dev, vslam_build_windows_map_recover_dev); download() adds the last pass's pairing map_pred / map_gap."""
+        vslam_gate_states_pairs_dev, vslam_build_windows_map_recover_dev); download() adds the last pass's pairing map_pred / map_gap.
+        rectify: a RectifyParams -- the rig delivers RAW images: they live in their own device buffer, and stage_rectify() (the first stage of step())
+        fills the batch's images from them through the rig's two maps (vslam_rectify_set / vslam_rectify_dev) on the pipeline's stream.  raw_images:
+        the (2B, src_h, src_w) uint8 raw images [left 0..B-1 | right 0..B-1]; absent, the rendered frames serve as the raw images (a rig whose
+        source size equals the image size).  None: the images are the rendered frames, as before, and stage_rectify is never called."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
         assert keyframe_gate in (False, True, "per_pass"), "keyframe_gate: False, True (on stage A's inputs) or 'per_pass' (inside the map passes)"
@@ -125,7 +130,24 @@ class KeyframePipeline:
         self.h_imgs = imgs
         self.h_imgs_unique_left = np.stack([np.pad(f[0], ((0, 0), (0, self.pitch - self.w))) for f in seq])
         self.h_imgs_unique_right = np.stack([np.pad(f[1], ((0, 0), (0, self.pitch - self.w))) for f in seq])
-        self.d_imgs = torch.from_numpy(imgs).to(d)
+        self.rectify = rectify
+        if rectify is None:
+            assert raw_images is None, "raw_images needs rectify"
+            self.d_imgs = torch.from_numpy(imgs).to(d)
+        else:
+            self.src_w, self.src_h = int(rectify.src_w), int(rectify.src_h)
+            if raw_images is None:
+                assert (self.src_w, self.src_h) == (self.w, self.h), "rendered frames as raw images need a rig whose source size is the image size"
+                raw_images = imgs[:, :, :self.w]
+            raw_images = np.asarray(raw_images, np.uint8)
+            assert raw_images.shape == (2 * B, self.src_h, self.src_w), (raw_images.shape, (2 * B, self.src_h, self.src_w))
+            self.src_pitch = (self.src_w + 63) // 64 * 64
+            self.src_img_bytes = self.src_pitch * self.src_h
+            raw = np.zeros((2 * B, self.src_h, self.src_pitch), np.uint8)
+            raw[:, :, :self.src_w] = raw_images
+            self.vo.rectify_set(rectify)   # (raises VslamError naming the field: a refused rig never reaches the batched call)
+            self.d_raw = torch.from_numpy(raw).to(d)
+            self.d_imgs = torch.zeros((2 * B, self.h, self.pitch), dtype=torch.uint8, device=d)   # filled by stage_rectify()
         # ---- ORB outputs
         self.d_kps = torch.zeros((2 * B, self.cap, 28), dtype=torch.uint8, device=d)
         self.d_desc = torch.zeros((2 * B, self.cap, 32), dtype=torch.uint8, device=d)
@@ -265,6 +287,12 @@ class KeyframePipeline:
         torch.cuda.synchronize(self.dev)
 
     # ------------------------------------------------------------------ stages
+    def stage_rectify(self):
+        """raw pairs -> the batch's rectified images (rectify set): one launch for both cameras"""
+        B = self.B
+        self.vo.rectify_dev(self.d_raw.data_ptr(), self.d_raw.data_ptr() + B * self.src_img_bytes, self.src_img_bytes, self.src_pitch, B,
+                            self.d_imgs.data_ptr(), self.d_imgs.data_ptr() + B * self.img_bytes, self.img_bytes, self.pitch)
+
     def stage_orb(self):
         n_img = self.B if self.depth == "sgbm" else 2 * self.B  # the reference never detects on the right image
         self.vo.feature_detection_dev(self.d_imgs.data_ptr(), self.img_bytes, self.pitch, n_img, self.d_kps.data_ptr(),
@@ -460,6 +488,8 @@ class KeyframePipeline:
         self.vo.ba_batch_dev(self.ba_batch, schedule=1)
 
     def step(self):
+        if self.rectify is not None:
+            self.stage_rectify()
         self.stage_orb()
         self.stage_stereo_match()
         self.stage_track()
