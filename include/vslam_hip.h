@@ -727,7 +727,7 @@ int vslam_ba_deferred_dev(vslam_ctx* ctx, int n_windows, int32_t* h_deferred);
  * params.huber_delta).  n observations of n world points through ONE pose; host buffers, synchronous; any output may be NULL. */
 int vslam_edge_jacobians(vslam_ctx* ctx, int n, const float* xyz_w, const float* uv, const double T_c_w[7], const double* K4,
                          double* err, double* J_pose, double* J_point, double* chi2, double* huber_w);
-/* Kernel-choice overrides of a context (tuning aid, and how the tests force every kernel path): name in {"orb_fuse_min", "sgbm_fuse_min",
+/* Kernel-choice overrides of a context (tuning aid, and how the tests force every kernel path): name in {"orb_fuse_min", "anms_cap" (pixels at which the ANMS radius walk stops early, 0 = never; same output either way, see vslam_orb_anms_path_dev), "sgbm_fuse_min",
  * "sgbm_fwd_min" (items per call from which the fused kernel is used), "sgbm_fw_rows" (32 | 64), "pose_only_window", "pnp_window", "ba_adaptive" (0 | 1), "rectify_form" (0 | 1: source side of the rectification kernel, direct gathers | source boxes staged in LDS; same bytes), "ba_lanes" (256 | 512: lanes per window of the
  * LDS-resident optimize_map kernel; default by the number of windows in the call; the results do not depend on it), "track_rule" (0 | 1: see
  * vslam_build_windows_dev; this one changes RESULTS, it is the before / after switch of round 6)};
@@ -740,6 +740,15 @@ int vslam_set_tuning(vslam_ctx* ctx, const char* name, int value);
 int vslam_sgbm_status_dev(vslam_ctx* ctx, int32_t* h_status);
 /* per-image ORB capacity flags of the most recent ORB launch (0 = ok) */
 int vslam_orb_status_dev(vslam_ctx* ctx, int B, int32_t* h_status);
+/* Which way each image of the most recent ANMS launch (vslam_feature_detection[_dev], vslam_anms, vslam_orb_compute) went through orb_anms_kernel.
+ * The kernel's suppression-radius walk stops once it has cleared "anms_cap" pixels (vslam_set_tuning; default one cell of its grid) and takes the
+ * selection from such radii only when that is provably the selection of VO::adaptive_non_maximal_suppresion (visual_odometry.cpp:124-153);
+ * otherwise it finishes the stopped walks and selects again.  The output never depends on it.  Synchronises the context stream. */
+#define VSLAM_ANMS_PATH_NONE 0     /* no ANMS: anms_num <= 0 or fewer keypoints than anms_num (:100) */
+#define VSLAM_ANMS_PATH_SHORTCUT 1 /* capped walk, selection accepted */
+#define VSLAM_ANMS_PATH_FALLBACK 2 /* capped walk, check failed: stopped walks finished, selection redone */
+#define VSLAM_ANMS_PATH_UNCAPPED 3 /* "anms_cap" = 0: every walk runs to its end */
+int vslam_orb_anms_path_dev(vslam_ctx* ctx, int B, int32_t* h_path);
 /* Diagnostic (rows A1 / A3): one level of the scale pyramid (blurred = 0: cv::resize INTER_LINEAR of the level above, what cv::ORB::detect runs
  * FAST / Harris / the IC angle on; level 0 is the caller's image and is not kept) or of the GaussianBlur 7x7 sigma 2 pyramid (blurred = 1: what
  * cv::ORB::compute samples) of image `item` of the most recent ORB launch of this context (vslam_feature_detection[_dev], vslam_orb_compute:

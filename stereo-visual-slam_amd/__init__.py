@@ -172,7 +172,7 @@ SIGNATURES = {
     "vslam_build_windows_map_recover_dev": (I, [P, P, P, P, P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_ba_status_dev": (I, [P, I, P]), "vslam_ba_schedule_passes_dev": (I, [P, I, P]), "vslam_ba_deferred_dev": (I, [P, I, P]),
     "vslam_edge_jacobians": (I, [P, I, P, P, P, P, P, P, P, P, P]),
-    "vslam_set_tuning": (I, [P, C.c_char_p, I]), "vslam_sgbm_status_dev": (I, [P, P]), "vslam_orb_status_dev": (I, [P, I, P]),
+    "vslam_set_tuning": (I, [P, C.c_char_p, I]), "vslam_sgbm_status_dev": (I, [P, P]), "vslam_orb_status_dev": (I, [P, I, P]), "vslam_orb_anms_path_dev": (I, [P, I, P]),
     "vslam_orb_level": (I, [P, I, I, I, P, I, I, P, P]),
     "vslam_build_pnp_inputs_dev": (I, [P, P, P, I, P, P, I, P, P, P, I, I, P, P, P, P, I]),
     "vslam_profile_enable": (I, [P, I]), "vslam_profile_read": (I, [P, P, I, P]), "vslam_profile_intervals": (I, [P, P, I, P]),
@@ -402,6 +402,13 @@ class VO:
     def orb_status(self, B):
         st = np.zeros(B, np.int32)
         self._chk(self.lib.vslam_orb_status_dev(self.h, B, st), "vslam_orb_status_dev")
+        return st
+
+    def orb_anms_path(self, B):
+        """per image of the last ANMS launch: 0 = no ANMS, 1 = capped radius walk accepted, 2 = its check failed and the stopped walks were finished,
+        3 = uncapped walk (set_tuning(anms_cap=0))"""
+        st = np.zeros(B, np.int32)
+        self._chk(self.lib.vslam_orb_anms_path_dev(self.h, B, st), "vslam_orb_anms_path_dev")
         return st
 
     # ------------------------------------------------------------ VO::feature_matching (visual_odometry.cpp:219-251)

@@ -115,6 +115,7 @@ static int dev_alloc(Ctx* c, T** p, size_t n) {
 struct TuneKey { const char* name; const char* env; int Tuning::*field; int lo, hi; };
 static const TuneKey kTuneKeys[] = {
     {"orb_fuse_min", "VSLAM_ORB_FUSE_MIN", &Tuning::orb_fuse_min, 0, 1 << 30},
+    {"anms_cap", "VSLAM_ANMS_CAP", &Tuning::anms_cap, 0, 1 << 30},
     {"sgbm_fuse_min", "VSLAM_SGBM_FUSE_MIN", &Tuning::sgbm_fuse_min, 0, 1 << 30},
     {"sgbm_fwd_min", "VSLAM_SGBM_FWD_MIN", &Tuning::sgbm_fwd_min, 0, 1 << 30},
     {"sgbm_fw_rows", "VSLAM_SGBM_FW_ROWS", &Tuning::sgbm_fw_rows, 32, 64},
@@ -185,7 +186,7 @@ static int orb_pipeline(Ctx* c, const uint8_t* d_imgs, size_t img_bytes, int pit
     if ((rc = launch_orb_select(c->plan, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel,
                                 c->orb.d_sel_cnt, c->orb.d_status, c->stream))) return rc;
     if ((rc = launch_orb_anms(c->plan, B, c->orb.d_sel, c->orb.d_sel_cnt, c->plan.sel_cap, anms_num, regroup, d_kps, nullptr, c->orb.d_order, c->p.kp_capacity,
-                              d_count, c->orb.d_status, c->orb.d_rad, c->stream))) return rc;
+                              d_count, c->orb.d_status, c->orb.d_rad, c->tune.anms_cap, c->orb.d_anms_path, c->stream))) return rc;
     // orientation (and the rBRIEF rotation) only for the keypoints the ANMS kept
     if ((rc = launch_orb_orient(c->plan, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, d_kps, c->orb.d_cs, c->orb.d_order, c->p.kp_capacity, d_count, c->stream))) return rc;
     if (describe) {
@@ -277,6 +278,7 @@ int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** ou
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_cs, B * (size_t)p->kp_capacity);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_order, B * (size_t)p->kp_capacity);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_rad, B * (size_t)kMaxRows);
+    if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_anms_path, B);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->match.d_train_best, B * kMaxRows);
     if (rc != VSLAM_OK) { vslam_destroy(reinterpret_cast<vslam_ctx*>(c)); return rc; }
     *out = reinterpret_cast<vslam_ctx*>(c);
@@ -291,7 +293,7 @@ void vslam_destroy(vslam_ctx* ctx) {
     orb_tables_free(&c->tab);
     for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc}) b->release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
-    void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad,
+    void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad, c->orb.d_anms_path,
                     c->match.d_train_best, c->rect.d_map[0], c->rect.d_map[1], c->rect.d_tiles[0], c->rect.d_tiles[1]};
     for (void* q : ptrs) if (q) hipFree(q);
     if (c->prof) {
@@ -397,7 +399,7 @@ int vslam_anms(vslam_ctx* ctx, vslam_keypoint* kps, int n, int num, int* n_out) 
     VS_HIP(hipMemcpyAsync(d_in, kps, sizeof(vslam_keypoint) * n, hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemcpyAsync(d_n, &nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(c->orb.d_status, 0, sizeof(int32_t), c->stream));
-    if ((rc = launch_anms_flat(1, d_in, d_n, kMaxRows, num, 0, c->p.img_w, c->p.img_h, d_out, nullptr, nullptr, kMaxRows, d_cnt, c->orb.d_status, c->orb.d_rad, c->stream))) return rc;
+    if ((rc = launch_anms_flat(1, d_in, d_n, kMaxRows, num, 0, c->p.img_w, c->p.img_h, d_out, nullptr, nullptr, kMaxRows, d_cnt, c->orb.d_status, c->orb.d_rad, c->tune.anms_cap, c->orb.d_anms_path, c->stream))) return rc;
     int32_t m = 0;
     VS_HIP(hipMemcpyAsync(&m, d_cnt, sizeof(m), hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipStreamSynchronize(c->stream));
@@ -437,7 +439,7 @@ int vslam_orb_compute(vslam_ctx* ctx, const uint8_t* img, int w, int h, int stri
         if ((rc = launch_orb_pyramid(c->plan, c->tab, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->stream))) return rc;
         if ((rc = launch_orb_blur(c->plan, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->orb.d_blur, c->stream))) return rc;
     }
-    if ((rc = launch_anms_flat(1, d_in, d_n, kc, 0, 1, w, h, d_kps, c->orb.d_cs, nullptr, kc, d_cnt, c->orb.d_status, c->orb.d_rad, c->stream))) return rc;
+    if ((rc = launch_anms_flat(1, d_in, d_n, kc, 0, 1, w, h, d_kps, c->orb.d_cs, nullptr, kc, d_cnt, c->orb.d_status, c->orb.d_rad, c->tune.anms_cap, c->orb.d_anms_path, c->stream))) return rc;
     if ((rc = launch_orb_describe(c->plan, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->orb.d_blur, d_kps, c->orb.d_cs, nullptr, kc, d_cnt, d_desc, c->stream))) return rc;
     int32_t m = 0;
     VS_HIP(hipMemcpyAsync(&m, d_cnt, sizeof(m), hipMemcpyDeviceToHost, c->stream));
@@ -461,6 +463,15 @@ int vslam_orb_status_dev(vslam_ctx* ctx, int B, int32_t* h_status) {
     if (!c || !h_status || B <= 0 || B > c->p.max_batch) return VSLAM_ERR_ARG;
     VS_ENTER(c);
     VS_HIP(hipMemcpyAsync(h_status, c->orb.d_status, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return VSLAM_OK;
+}
+
+int vslam_orb_anms_path_dev(vslam_ctx* ctx, int B, int32_t* h_path) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !h_path || B <= 0 || B > c->p.max_batch) return VSLAM_ERR_ARG;
+    VS_ENTER(c);
+    VS_HIP(hipMemcpyAsync(h_path, c->orb.d_anms_path, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipStreamSynchronize(c->stream));
     return VSLAM_OK;
 }

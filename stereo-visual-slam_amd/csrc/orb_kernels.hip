@@ -13,7 +13,8 @@
 //   orb_select_kernel       one workgroup per (image, level): 256-bin histogram cut on the FAST score (retainBest(2n) with ties), Harris 7 x 7, 4-pass radix
 //                           select on the f32 response (retainBest(n) with ties), raster-order bitonic sort in LDS
 //   orb_anms_kernel         one workgroup per image: register-blocked bitonic sort by response, suppression radii by a grid-accelerated nearest-stronger search
-//                           (exact f64 distances), second sort for the num-th radius, ordered compaction, cv::ORB::compute's border cull + regroup by octave
+//                           (exact f64 distances) that stops at a cap wherever the selection cannot depend on the exact radius, 8-pass radix select of the num-th
+//                           radius, ordered compaction, cv::ORB::compute's border cull + regroup by octave
 //   orb_orient_kernel       intensity-centroid angle of the keypoints the ANMS kept: a wave per keypoint, 8 rows x 32 bytes per load instruction, v_dot4 moments
 //   orb_describe_kernel     a wave per keypoint, software-pipelined: the 39 x 40 patch of the BLURRED level staged in LDS, 256 rotated tests, 4 bits per lane
 // Float expressions that must round like the CPU (no FMA contraction) use explicit __f*_rn intrinsics; the file is
@@ -57,7 +58,7 @@ void orb_debug_dump(hipStream_t stream) {
     static const char* names[64] = {"sel: hist+cut", "sel: harris", "sel: radix select", "sel: compact+sort", "sel: angle+out", nullptr, nullptr, nullptr,
                                     "desc: patch load", "desc: row blur", "desc: col blur", "desc: sincos+tests", nullptr, nullptr, nullptr, nullptr,
                                     "fast: tile load", "fast: corner test", "fast: score", "fast: nms+append", nullptr, nullptr, nullptr, nullptr,
-                                    "anms: gather+sort", "anms: radii", "anms: radius sort", "anms: compact+regroup+out", nullptr, nullptr, nullptr, nullptr,
+                                    "anms: gather+sort", "anms: radii", "anms: radius select", "anms: compact+regroup+out", nullptr, nullptr, nullptr, nullptr,
                                     "pyrfast: tile load", "pyrfast: resize", "pyrfast: blur", "pyrfast: edge columns", "pyrfast: pre-test", "pyrfast: queue pushes", "pyrfast: scores",
                                     "pyrfast: flush + barrier", "pyrfast: nms", "pyrfast: output"};
     for (int i = 0; i < 64; ++i) if (names[i] && h[i]) fprintf(stderr, "  [orb profile] %-28s %14lld block-cycles (sum over blocks)\n", names[i], h[i]);
@@ -909,6 +910,9 @@ int launch_orb_select(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_byt
 // ------------------------------------------------------------------------------------------- K5 ANMS
 constexpr int kAnmsBlock = 1024;
 constexpr int kAnmsBrute = 160; // at most this many stronger keypoints: scanning them beats walking the grid
+// which way an image went through orb_anms_kernel (vslam_orb_anms_path_dev)
+constexpr int kAnmsPathNone = VSLAM_ANMS_PATH_NONE, kAnmsPathShortcut = VSLAM_ANMS_PATH_SHORTCUT, kAnmsPathFallback = VSLAM_ANMS_PATH_FALLBACK,
+              kAnmsPathUncapped = VSLAM_ANMS_PATH_UNCAPPED;
 
 // K3b orb_orient_kernel: intensity-centroid orientation of the keypoints that survived the ANMS, and the (cos, sin) of the rBRIEF
 // rotation.  A 16-lane group per keypoint (four per wave); a fixed set of groups per image walks the list.  The level
@@ -1116,7 +1120,8 @@ template <int CAP, bool WITH_CS>
 __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_keypoint* __restrict__ d_in, const int32_t* __restrict__ d_nin,
                                                              int nlists, int in_capacity, int anms_num, int regroup, int img_w,
                                                              int img_h, vslam_keypoint* __restrict__ d_kps, float2* __restrict__ d_cs, int32_t* __restrict__ d_order, int kp_capacity,
-                                                             int32_t* __restrict__ d_count, int32_t* __restrict__ d_status, double* __restrict__ d_rad) {
+                                                             int32_t* __restrict__ d_count, int32_t* __restrict__ d_status, double* __restrict__ d_rad, int anms_cap,
+                                                             int32_t* __restrict__ d_path) {
     const int b = blockIdx.x;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* skey = reinterpret_cast<unsigned long long*>(smem);                  // kMaxRows u64 (sort buffer; grid lists during the radius phase)
@@ -1129,6 +1134,9 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
     unsigned long long& s_final = *reinterpret_cast<unsigned long long*>(tail);
     int* s_wave_tot = reinterpret_cast<int*>(tail + 16);                                     // kAnmsBlock / 64
     int* s_off = s_wave_tot + kAnmsBlock / 64;                                               // kNLevels + 1
+    unsigned long long& s_farmin = *reinterpret_cast<unsigned long long*>(tail + 8);         // capped walk: least lower bound of the far keypoints (f64 bits)
+    int& s_nfar = s_off[kNLevels + 1];                                                       // ... their number
+    int& s_ngt = s_off[kNLevels + 2];                                                        // ... and how many stored radii exceed that bound
 
     OPH_INIT();
     // ---- gather (lists in order): flat index g -> (list, i)
@@ -1178,6 +1186,7 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
     };
     const bool do_anms = anms_num > 0 && N >= anms_num; // visual_odometry.cpp:100
     int M = N; // count after ANMS
+    int path = kAnmsPathNone;
     if (do_anms) {
         // ---- sort by response, strongest first; ties by input index (stable)
         int np2 = 1;
@@ -1204,7 +1213,7 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
         constexpr int kAnmsCellMin = 24; // (32 -> 24: 0.75 -> 0.70 ms per 1024 KITTI-sized images; the grid stays below its 1023 cells: 52 x 16)
         const int csz = max(kAnmsCellMin, (int)ceilf(sqrtf((float)img_w * (float)img_h * (1.f / 900.f))));
         const int gx = min(max((img_w + csz - 1) / csz, 1), 1023), gy = max(min((img_h + csz - 1) / csz, 1023 / gx), 1), ncell = gx * gy;
-        int* ccnt = reinterpret_cast<int*>(skey);                 // the sort buffer is free until the radius sort
+        int* ccnt = reinterpret_cast<int*>(skey);                 // the sort buffer is free until the regroup sort (the radius select puts its 256 bins here)
         int* coff = ccnt + 1024;
         uint16_t* tmpl = reinterpret_cast<uint16_t*>(coff + 1024); // ranks per cell, arrival order
         uint16_t* clist = tmpl + kMaxRows;                          // ranks per cell, ascending
@@ -1213,6 +1222,17 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
             const int cx = min(max((int)(x / (float)csz), 0), gx - 1), cy = min(max((int)(y / (float)csz), 0), gy - 1);
             return cy * gx + cx;
         };
+        // Capped walk.  A radius is never an output: the selection below needs the num-th largest radius (`final_radius`) and, per
+        // keypoint, whether its radius reaches it.  So a walk also stops once the distance it has cleared (`bnd`) reaches `cap` pixels
+        // with the nearest stronger keypoint still unproven: that keypoint is FAR, its radius is known to be >= bnd, and it is stored as
+        // DBL_MAX like the keypoints without any stronger one.  The few far keypoints are what a wave used to wait for, ring after
+        // ring, while its other lanes were done after the 3 x 3 block.  The selection from such radii is taken only when it is
+        // provably the selection from the true ones (the check after the walk); otherwise pass 1 finishes the far walks without a
+        // cap, so the cap changes the speed and never the result.
+        // cap: Tuning::anms_cap; -1 = one cell (every walk ends after the 3 x 3 block at the latest), 0 = never stop early.
+        double cap = anms_cap < 0 ? (double)csz * (1.0 - 1e-6) : (double)anms_cap; // (a cell shrunk like bnd: a keypoint ON a cell edge stops after 3 x 3 too)
+        path = cap > 0 ? kAnmsPathShortcut : kAnmsPathUncapped;
+        if (threadIdx.x == 0) { s_nfar = 0; s_ngt = 0; s_farmin = ~0ull; }
         for (int c = threadIdx.x; c <= ncell; c += kAnmsBlock) ccnt[c] = 0;
         __syncthreads();
         for (int r = threadIdx.x; r < N; r += kAnmsBlock) { const int c = cell_of(sxy[r].x, sxy[r].y); cof[r] = (uint16_t)c; atomicAdd(&ccnt[c], 1); }
@@ -1239,11 +1259,14 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
             clist[o0 + pos] = (uint16_t)r;
         }
         __syncthreads();
+#pragma unroll 1
+        for (int pass = 0;; ++pass) { // (uniform; pass 1 only after a failed check)
         for (int i = threadIdx.x; i < N; i += kAnmsBlock) {
             const float thr = __fmul_rn(sr[i], 1.11f);
             // first j in [0, i) with !(sr[j] > thr); sr is non-increasing
             int lo = 0, hi = i;
             while (lo < hi) { const int mid = (lo + hi) >> 1; if (sr[mid] > thr) lo = mid + 1; else hi = mid; }
+            if (pass > 0 && !(lo > 0 && srad[i] == 1.7976931348623157e308)) continue; // pass 1: the far keypoints only (this lane stored srad[i])
             const float xi = sxy[i].x, yi = sxy[i].y;
             double best = 1.7976931348623157e308;
             auto visit = [&](int j) {
@@ -1258,7 +1281,9 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
                 const float dx = __fsub_rn(xi, pj.x), dy = __fsub_rn(yi, pj.y);
                 best = fmin(best, __fma_rn((double)dx, (double)dx, __dmul_rn((double)dy, (double)dy)));
             };
-            if (lo <= kAnmsBrute) {
+            // With the cap on, every keypoint that has a stronger one walks the capped grid: the top ranks have few stronger keypoints, far
+            // apart, and are done (far) after the 3 x 3 block instead of scanning up to kAnmsBrute candidates.
+            if (lo <= kAnmsBrute && (lo == 0 || !(cap > 0))) {
                 int j = 0;
                 for (; j + 4 <= lo; j += 4) {
                     const float2 p0 = sxy[j], p1 = sxy[j + 1], p2 = sxy[j + 2], p3 = sxy[j + 3];
@@ -1274,6 +1299,11 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
                         const double by = fmin((double)yi - (double)((cyi - k + 1) * csz), (double)((cyi + k) * csz) - (double)yi);
                         const double bnd = fmin(bx, by) * (1.0 - 1e-6); // (margin: the reference's dx, dy are f32-rounded differences)
                         if (bnd > 0 && best <= bnd * bnd) break;
+                        if (cap > 0 && bnd >= cap) { // far: stored as DBL_MAX, like lo == 0 (cap > 0, so bnd > 0: its bits order like an integer)
+                            atomicAdd(&s_nfar, 1); atomicMin(&s_farmin, (unsigned long long)__double_as_longlong(bnd));
+                            lo = 0;
+                            break;
+                        }
                     }
                     const int y0 = cyi - k, y1 = cyi + k, x0 = cxi - k, x1 = cxi + k;
                     for (int cy = max(y0, 0); cy <= min(y1, gy - 1); ++cy) {
@@ -1300,13 +1330,81 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
             srad[i] = lo > 0 ? sqrt(best) : 1.7976931348623157e308;
         }
         __syncthreads();
+        if (pass > 0 || s_nfar == 0) break;
+        // ---- do these radii give the selection the true ones give?  Yes exactly when the num-th largest of them (final_radius, below) is
+        // finite and no far keypoint's lower bound is below it: then every far radius is >= its bound >= final_radius, so putting the
+        // true values back moves nothing across final_radius -- the num-th largest radius and the kept set stay, and ties at final_radius
+        // are among exact radii.  With m = the least of the bounds that is: FEWER THAN num stored radii exceed m (the DBL_MAX ones do), which
+        // needs no sort and is asked here, while the grid lists still stand.
+        // In floating point: a far keypoint's squared distance d2 to any stronger keypoint exceeds fl(bnd * bnd) (the visited ones failed the
+        // exit test; the unvisited ones lie beyond the cleared square by the walk's own (1 - 1e-6) margin), sqrt is correctly rounded and
+        // monotone, and fl(sqrt(fl(x * x))) == x in binary64, so its radius fl(sqrt(d2)) >= bnd: comparing the stored radii with the shrunk
+        // bnd itself is the conservative side, and sqrt rounding cannot flip it.
+        {
+            const double m = __longlong_as_double((long long)s_farmin);
+            int above = 0;
+            for (int i = threadIdx.x; i < N; i += kAnmsBlock) above += srad[i] > m; // (this lane stored srad[i])
+            for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o);
+            if ((threadIdx.x & 63) == 0 && above) atomicAdd(&s_ngt, above);
+        }
+        __syncthreads();
+        if (s_ngt < anms_num) break;
+        // ---- the check failed: the far keypoints finish their walk without a cap, and the image goes on exactly as without the shortcut
+        path = kAnmsPathFallback; cap = 0.0;
+        }
         OPH(25);
-        // ---- the num-th largest radius (:141-146): sort the radii descending
-        for (int g = threadIdx.x; g < np2; g += kAnmsBlock) skey[g] = g < N ? ~(unsigned long long)__double_as_longlong(srad[g]) : ~0ull;
-        __syncthreads();
-        bitonic_sort_lds(skey, np2);
-        if (threadIdx.x == 0) s_final = ~skey[anms_num - 1];
-        __syncthreads();
+        // ---- the num-th largest radius (:141-146).  Only that one element of the sorted radii is ever read, so it is SELECTED: the bits of
+        // a non-negative double order like an integer, and eight passes over their 8-bit digits, most significant first, each keep the bin
+        // that holds the wanted rank among the keys that share the digits chosen so far (find_rank_bin's suffix scan, on words of this
+        // kernel's own LDS).  A lane holds its keys in registers; the 256 bins stand where the grid lists, dead by now, were.
+        {
+            constexpr int kPer = (CAP + kAnmsBlock - 1) / kAnmsBlock;
+            int* hist = reinterpret_cast<int*>(skey);
+            int& s_bin = s_nfar; int& s_above = s_ngt; // (free since the check above)
+            unsigned long long kv[kPer];
+#pragma unroll
+            for (int q = 0; q < kPer; ++q) { const int g = q * kAnmsBlock + threadIdx.x; kv[q] = g < N ? (unsigned long long)__double_as_longlong(srad[g]) : 0ull; }
+            const int lane = threadIdx.x & 63;
+            unsigned long long prefix = 0; // the digits chosen so far
+            int rank = anms_num;           // the wanted key is the rank-th largest of the keys that start with them
+#pragma unroll 1
+            for (int shift = 56; shift >= 0; shift -= 8) {
+                if (threadIdx.x < 256) hist[threadIdx.x] = 0;
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < kPer; ++q) {
+                    const bool act = q * kAnmsBlock + (int)threadIdx.x < N && (shift == 56 || (kv[q] >> (shift + 8)) == prefix);
+                    const int digit = (int)(kv[q] >> shift) & 255;
+                    // the leading digits are the same for nearly all radii: the lanes that share the first active lane's digit add as one
+                    const unsigned long long m = __ballot(act);
+                    if (m) { // (wave-uniform)
+                        const int lead = __ffsll((long long)m) - 1, d0 = __shfl(digit, lead);
+                        const unsigned long long same = __ballot(act && digit == d0);
+                        if (lane == lead) atomicAdd(&hist[d0], __popcll(same));
+                        else if (act && digit != d0) atomicAdd(&hist[digit], 1);
+                    }
+                }
+                __syncthreads();
+                if (threadIdx.x < 64) { // largest bin d with at least `rank` keys in the bins >= d, and the number of keys above it
+                    const int b0 = 252 - 4 * lane; // this lane owns bins b0 + 3 .. b0 (descending); lane 0 owns 255 .. 252
+                    const int h3 = hist[b0 + 3], h2 = hist[b0 + 2], h1 = hist[b0 + 1], h0 = hist[b0];
+                    const int mine = h3 + h2 + h1 + h0;
+                    int incl = mine; // keys in the bins >= b0
+                    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+                    const int before = incl - mine;
+                    if (before < rank && incl >= rank) { // (exactly one lane: at least `rank` keys take part in every pass)
+                        int acc = before, d = b0 + 3;
+                        if (acc + h3 < rank) { acc += h3; d = b0 + 2; if (acc + h2 < rank) { acc += h2; d = b0 + 1; if (acc + h1 < rank) { acc += h1; d = b0; } } }
+                        s_bin = d; s_above = acc;
+                    }
+                }
+                __syncthreads();
+                prefix = (prefix << 8) | (unsigned long long)s_bin;
+                rank -= s_above;
+            }
+            if (threadIdx.x == 0) s_final = prefix;
+            __syncthreads();
+        }
         OPH(26);
         const double final_radius = __longlong_as_double((long long)s_final);
         // ---- keep rad >= final radius, in response order (:147-153)
@@ -1325,6 +1423,7 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
         for (int g = threadIdx.x; g < N; g += kAnmsBlock) sord[g] = (uint16_t)g;
         __syncthreads();
     }
+    if (threadIdx.x == 0) d_path[b] = path;
     // ---- cv::ORB::compute prologue: border cull in level-0 coordinates, stable regroup by octave
     if (regroup) {
         int np2 = 1;
@@ -1363,7 +1462,7 @@ __global__ __launch_bounds__(kAnmsBlock, 8) void orb_anms_kernel(const vslam_key
 template <int CAP>
 static int launch_anms_t(int B, const vslam_keypoint* d_in, const int32_t* d_nin, int nlists, int in_capacity, int anms_num,
                          int regroup, int img_w, int img_h, vslam_keypoint* d_kps, float2* d_cs, int32_t* d_order, int kp_capacity, int32_t* d_count,
-                         int32_t* d_status, double* d_rad, hipStream_t stream) {
+                         int32_t* d_status, double* d_rad, int anms_cap, int32_t* d_path, hipStream_t stream) {
     constexpr size_t smem = anms_lds_bytes(CAP);
     static bool attr_set[16] = {false}; // per device: the > 64 KB dynamic-LDS opt-in is a per-device function attribute
     int dev = 0;
@@ -1376,26 +1475,26 @@ static int launch_anms_t(int B, const vslam_keypoint* d_in, const int32_t* d_nin
     ProfScope prof__(stream, "orb_anms_kernel");
     if (d_cs)
         hipLaunchKernelGGL((orb_anms_kernel<CAP, true>), dim3(B), dim3(kAnmsBlock), smem, stream, d_in, d_nin, nlists, in_capacity, anms_num, regroup,
-                           img_w, img_h, d_kps, d_cs, d_order, kp_capacity, d_count, d_status, d_rad);
+                           img_w, img_h, d_kps, d_cs, d_order, kp_capacity, d_count, d_status, d_rad, anms_cap, d_path);
     else
         hipLaunchKernelGGL((orb_anms_kernel<CAP, false>), dim3(B), dim3(kAnmsBlock), smem, stream, d_in, d_nin, nlists, in_capacity, anms_num, regroup,
-                           img_w, img_h, d_kps, d_cs, d_order, kp_capacity, d_count, d_status, d_rad);
+                           img_w, img_h, d_kps, d_cs, d_order, kp_capacity, d_count, d_status, d_rad, anms_cap, d_path);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }
 
 int launch_orb_anms(const OrbPlan& plan, int B, const vslam_keypoint* d_sel, const int32_t* d_sel_cnt, int sel_cap, int anms_num,
                     int regroup, vslam_keypoint* d_kps, float2* d_cs, int32_t* d_order, int kp_capacity, int32_t* d_count, int32_t* d_status, double* d_rad,
-                    hipStream_t stream) {
+                    int anms_cap, int32_t* d_path, hipStream_t stream) {
     return launch_anms_t<kAnmsCapPipe>(B, d_sel, d_sel_cnt, kNLevels, sel_cap, anms_num, regroup, plan.w, plan.h, d_kps, d_cs, d_order, kp_capacity, d_count,
-                                       d_status, d_rad, stream);
+                                       d_status, d_rad, anms_cap, d_path, stream);
 }
 
 int launch_anms_flat(int B, const vslam_keypoint* d_in, const int32_t* d_nin, int in_capacity, int anms_num, int regroup, int img_w,
                      int img_h, vslam_keypoint* d_kps, float2* d_cs, int32_t* d_order, int kp_capacity, int32_t* d_count, int32_t* d_status, double* d_rad,
-                     hipStream_t stream) {
+                     int anms_cap, int32_t* d_path, hipStream_t stream) {
     return launch_anms_t<kMaxRows>(B, d_in, d_nin, 1, in_capacity, anms_num, regroup, img_w, img_h, d_kps, d_cs, d_order, kp_capacity, d_count, d_status, d_rad,
-                                   stream);
+                                   anms_cap, d_path, stream);
 }
 
 // ------------------------------------------------------------------------------------------- K6 blur + rBRIEF

@@ -136,6 +136,7 @@ struct OrbBuffers {
     float2* d_cs;          // B x kp_capacity: per-keypoint (cos, sin) of the rBRIEF rotation
     int32_t* d_order;      // B x kp_capacity: the output slots in (octave, raster) order -- the walk order of orient / describe
     double* d_rad;         // B x kMaxRows: ANMS suppression radii (f64)
+    int32_t* d_anms_path;  // B: VSLAM_ANMS_PATH_* of the most recent orb_anms_kernel launch
 };
 
 // launches (all asynchronous on `stream`)
@@ -152,13 +153,14 @@ int launch_orb_select(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_byt
                       int32_t* d_status, hipStream_t stream);
 // gather per-level lists (level asc) -> ANMS(num) -> regroup by octave -> d_kps (B x kp_capacity), d_count
 // anms_num <= 0: no ANMS (detect order).  regroup: apply cv::ORB::compute's border cull + octave regrouping.
+// anms_cap: Tuning::anms_cap as it stands (-1 = one grid cell).  d_path[b]: which way image b went (VSLAM_ANMS_PATH_*).
 int launch_orb_anms(const OrbPlan& plan, int B, const vslam_keypoint* d_sel, const int32_t* d_sel_cnt, int sel_cap,
                     int anms_num, int regroup, vslam_keypoint* d_kps, float2* d_cs, int32_t* d_order, int kp_capacity, int32_t* d_count, int32_t* d_status,
-                    double* d_rad, hipStream_t stream);
+                    double* d_rad, int anms_cap, int32_t* d_path, hipStream_t stream);
 // same ANMS kernel on a flat list per image (d_in: B x in_capacity, d_nin[b]) for the stand-alone vslam_anms call
 int launch_anms_flat(int B, const vslam_keypoint* d_in, const int32_t* d_nin, int in_capacity, int anms_num, int regroup,
                      int img_w, int img_h, vslam_keypoint* d_kps, float2* d_cs, int32_t* d_order, int kp_capacity, int32_t* d_count, int32_t* d_status,
-                     double* d_rad, hipStream_t stream);
+                     double* d_rad, int anms_cap, int32_t* d_path, hipStream_t stream);
 int launch_orb_blur(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr, uint8_t* d_blur,
                     hipStream_t stream);
 int launch_orb_orient(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr, vslam_keypoint* d_kps,
@@ -235,6 +237,8 @@ struct LmWindowArgs {
 // the call path (it races with a host that mutates its environment).
 struct Tuning {
     int orb_fuse_min = -1;    // VSLAM_ORB_FUSE_MIN: images per call from which orb_pyrblur_kernel replaces resize + blur
+    int anms_cap = -1;        // VSLAM_ANMS_CAP: pixels of cleared distance at which orb_anms_kernel's radius walk stops early (0 = never: the full walk;
+                              // default: one cell of its grid).  Same bits either way: a selection the cap could have changed is redone without it
     int sgbm_fuse_min = -1;   // VSLAM_SGBM_FUSE_MIN: pairs per call from which sgbm_down_kernel replaces hsum / vsum / path<0,1>
     int sgbm_fwd_min = -1;    // VSLAM_SGBM_FWD_MIN: pairs per call from which sgbm_forward_kernel replaces three path kernels
     int sgbm_fw_rows = -1;    // VSLAM_SGBM_FW_ROWS: 32 or 64 image rows per slab of the forward sweep
