@@ -728,7 +728,7 @@ int vslam_ba_deferred_dev(vslam_ctx* ctx, int n_windows, int32_t* h_deferred);
 int vslam_edge_jacobians(vslam_ctx* ctx, int n, const float* xyz_w, const float* uv, const double T_c_w[7], const double* K4,
                          double* err, double* J_pose, double* J_point, double* chi2, double* huber_w);
 /* Kernel-choice overrides of a context (tuning aid, and how the tests force every kernel path): name in {"orb_fuse_min", "anms_cap" (pixels at which the ANMS radius walk stops early, 0 = never; same output either way, see vslam_orb_anms_path_dev), "sgbm_fuse_min",
- * "sgbm_fwd_min" (items per call from which the fused kernel is used), "sgbm_fw_rows" (32 | 64), "pose_only_window", "pnp_window", "ba_adaptive" (0 | 1), "rectify_form" (0 | 1: source side of the rectification kernel, direct gathers | source boxes staged in LDS; same bytes), "ba_lanes" (256 | 512: lanes per window of the
+ * "sgbm_fwd_min" (items per call from which the fused kernel is used), "sgbm_fw_rows" (32 | 64), "pose_only_window", "pose_only_waves" (0 = automatic | 12 | 4: waves per window of the schedule's pose-only kernel; default by the number of windows in the call; same bits either way), "pnp_window", "ba_adaptive" (0 | 1), "rectify_form" (0 | 1: source side of the rectification kernel, direct gathers | source boxes staged in LDS; same bytes), "ba_lanes" (256 | 512: lanes per window of the
  * LDS-resident optimize_map kernel; default by the number of windows in the call; the results do not depend on it), "track_rule" (0 | 1: see
  * vslam_build_windows_dev; this one changes RESULTS, it is the before / after switch of round 6)};
  * value -1 = the library's batch-size rule.  vslam_create seeds them once from the environment variables VSLAM_<NAME> (an unparsable

@@ -120,6 +120,7 @@ static const TuneKey kTuneKeys[] = {
     {"sgbm_fwd_min", "VSLAM_SGBM_FWD_MIN", &Tuning::sgbm_fwd_min, 0, 1 << 30},
     {"sgbm_fw_rows", "VSLAM_SGBM_FW_ROWS", &Tuning::sgbm_fw_rows, 32, 64},
     {"pose_only_window", "VSLAM_POSE_ONLY_WINDOW", &Tuning::pose_only_window, 0, 1},
+    {"pose_only_waves", "VSLAM_POSE_ONLY_WAVES", &Tuning::pose_only_waves, 0, VSLAM_MAX_KF},
     {"ba_resident", "VSLAM_BA_RESIDENT", &Tuning::ba_resident, 0, 1},
     {"pnp_window", "VSLAM_PNP_WINDOW", &Tuning::pnp_window, 0, 1},
     {"ba_adaptive", "VSLAM_BA_ADAPTIVE", &Tuning::ba_adaptive, 0, 1},
@@ -129,7 +130,8 @@ static const TuneKey kTuneKeys[] = {
 };
 static int tune_set(Tuning& t, const TuneKey& k, long v) {
     if (v == -1) { t.*(k.field) = -1; return VSLAM_OK; } // back to the library's rule
-    if (v < k.lo || v > k.hi || (k.field == &Tuning::sgbm_fw_rows && v != 32 && v != 64) || (k.field == &Tuning::ba_lanes && v != 256 && v != 512)) {
+    if (v < k.lo || v > k.hi || (k.field == &Tuning::sgbm_fw_rows && v != 32 && v != 64) || (k.field == &Tuning::ba_lanes && v != 256 && v != 512) ||
+        (k.field == &Tuning::pose_only_waves && v != 0 && v != VSLAM_MAX_KF && v != kPoseOnlyNarrowWaves)) {
         set_error("tuning value %s = %ld out of range (%d..%d%s, or -1 = default)", k.name, v, k.lo, k.hi, k.field == &Tuning::sgbm_fw_rows ? ", 32 or 64" : "");
         return VSLAM_ERR_ARG;
     }

@@ -1472,17 +1472,27 @@ __global__ __launch_bounds__(64) void pnp_wave_kernel(const float* __restrict__ 
 // scale partials, summed in keyframe order by every wave.  Then the chi2 classification (:224-266) -- at the state of the last EVALUATED
 // trial, g2o's quirk, like the window kernel.  Runs only behind the three optimize_map passes of a schedule: they have validated the graph
 // (status word) and nothing here needs the landmark CSR.
-constexpr int kPoBlock = 64 * kMaxKf;
+// W waves per window.  W = kMaxKf is one keyframe per wave: a window's own latency, what a launch of at most one window per CU waits for.  At 168
+// registers per lane its 12 waves fill a CU, so nothing covers a window's serial phases (setup scans, the barrier behind the fattest keyframe,
+// the 6x6 solve + se3::exp chain of every trial).  The narrow form (kPoseOnlyNarrowWaves = 4 waves, two per SIMD: no register cap, nothing spills)
+// runs two windows per CU: a wave then owns a LIST of keyframes and runs every per-keyframe phase over it, one keyframe after the other.  Keyframes
+// are dealt to waves by active edge count, longest first, so the barriers wait for balanced sums.  A keyframe's arithmetic does not depend on the
+// wave that runs it (its edges go to the 64 lanes of that wave as j = kb + 64 u + lane, its 27 sums through the same butterfly, sums over keyframes
+// in keyframe order): both forms give the same bits (tests/test_gpu_pose_only_forms.py).  Sweep and figures: DESIGN.md 5.1, profiles/pose_only_forms.json.
 struct PoShared {
     double H[2][kMaxKf][36], g[2][kMaxKf][6];
     double part[2][kMaxKf], spart[2][kMaxKf];
+    double x[kMaxKf][6];
     int cnt[kMaxKf][kMaxKf];
     int kbeg[kMaxKf + 1];
     int flag[2];
     int cin[2][kMaxKf], cout[2][kMaxKf];
     double T[2][kMaxKf][7], R[3][kMaxKf][12];
 };
-__global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs ka, int iters, int update_poses) {
+template <int W, int kMinWaves>
+__global__ __launch_bounds__(64 * W, kMinWaves) void pose_only_wave_kernel(LmKernelArgs ka, int iters, int update_poses) {
+    static_assert(W == kMaxKf || (W >= 1 && W <= 8), "the keyframe deal takes its minimum over eight lanes"); // (kMinWaves: waves per SIMD the registers are budgeted for)
+    constexpr int kBlock = 64 * W;
     const LmWindowArgs& a = ka.a;
     __shared__ PoShared sm;
     const int w = ka.order ? ka.order[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -1507,7 +1517,7 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
     const double delta = a.huber_delta;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     // ---- setup: per-keyframe runs of the active edges (ascending edge id inside a keyframe), two ballot scans over this wave's chunk
-    const int per = (((ne + kMaxKf - 1) / kMaxKf) + 63) & ~63;
+    const int per = (((ne + W - 1) / W) + 63) & ~63;
     const int c0 = min(wave * per, ne), c1 = min(c0 + per, ne);
     {
         int cnt[kMaxKf];
@@ -1542,7 +1552,7 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
         for (int k = 0; k < kMaxKf; ++k) {
             int before = 0, tot = 0;
 #pragma unroll
-            for (int c = 0; c < kMaxKf; ++c) { const int v = sm.cnt[c][k]; tot += v; if (c < wave) before += v; }
+            for (int c = 0; c < W; ++c) { const int v = sm.cnt[c][k]; tot += v; if (c < wave) before += v; }
             off[k] = run + before;
             if (tid == 0) sm.kbeg[k] = run;
             run += tot;
@@ -1575,28 +1585,51 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
     }
     __syncthreads();
     POH(0);
-    const int ntot = sm.kbeg[kMaxKf];
-    const bool mine = wave < nk;                          // this wave owns keyframe `wave`
-    const int kb = mine ? sm.kbeg[wave] : 0, ke = mine ? sm.kbeg[wave + 1] : 0;
+    // ---- this wave's keyframes: `held` packs them four bits each, nheld of them.  The narrow forms deal by longest-processing-time-first (keyframes
+    // by descending active edge count, ties by keyframe index, each to the wave with the least load so far, ties by wave index); every wave runs the
+    // same deal from sm.kbeg -- lane k holds keyframe k's count and rank, lane v wave v's load -- and keeps what falls to it
+    unsigned long long held = 0;
+    int nheld = 0;
+    if constexpr (W == kMaxKf) { held = (unsigned long long)wave; nheld = wave < nk ? 1 : 0; }
+    else {
+        const int kl = min(lane, kMaxKf - 1);
+        const int mycnt = lane < nk ? sm.kbeg[kl + 1] - sm.kbeg[kl] : -1;
+        int rank = 0;
+        for (int j = 0; j < nk; ++j) { const int cj = sm.kbeg[j + 1] - sm.kbeg[j]; rank += (cj > mycnt || (cj == mycnt && j < lane)) ? 1 : 0; }
+        int load = 0;
+        for (int r = 0; r < nk; ++r) {
+            const int k = __builtin_amdgcn_readfirstlane(__ffsll((long long)__ballot(lane < nk && rank == r)) - 1);
+            const int cr = __shfl(mycnt, k);
+            int key = lane < W ? load * 16 + lane : 0x7fffffff;
+            key = min(key, __shfl_xor(key, 1)); key = min(key, __shfl_xor(key, 2)); key = min(key, __shfl_xor(key, 4));
+            const int v = __builtin_amdgcn_readfirstlane(key) & 15;
+            if (lane == v) load += cr;
+            if (v == wave) { held |= (unsigned long long)k << (4 * nheld); ++nheld; }
+        }
+    }
+    auto kf_at = [&](int q) -> int { return (int)((held >> (4 * q)) & 15ull); };
     // poses live in LDS (current / trial / last evaluated trial per keyframe) and reach the evaluation loop through scalar registers:
-    // held in VGPRs next to the 27 accumulators they spilled (168 registers per lane at 12 waves per workgroup)
-    {
+    // held in VGPRs next to the 27 accumulators they spilled (168 registers per lane at three waves per SIMD)
+#pragma unroll 1
+    for (int q = 0; q < nheld; ++q) {
+        const int k = kf_at(q);
         double T[7], Rt[12];
 #pragma unroll
-        for (int i = 0; i < 7; ++i) T[i] = a.T[((size_t)w * a.n_kf + min(wave, nk - 1)) * 7 + i];
+        for (int i = 0; i < 7; ++i) T[i] = a.T[((size_t)w * a.n_kf + k) * 7 + i];
         expand_pose(T, Rt);
         if (lane == 0) {
 #pragma unroll
-            for (int i = 0; i < 7; ++i) sm.T[0][wave][i] = T[i];
+            for (int i = 0; i < 7; ++i) sm.T[0][k][i] = T[i];
 #pragma unroll
-            for (int i = 0; i < 12; ++i) { sm.R[0][wave][i] = Rt[i]; sm.R[2][wave][i] = Rt[i]; }
+            for (int i = 0; i < 12; ++i) { sm.R[0][k][i] = Rt[i]; sm.R[2][k][i] = Rt[i]; }
         }
-        __builtin_amdgcn_wave_barrier();
     }
+    __builtin_amdgcn_wave_barrier();
     const int slot27 = wave_slot<27>(lane);
-    // robust cost of this keyframe's edges at pose R; LIN: its 6x6 block and right-hand side into sm.H[buf][wave], sm.g[buf][wave];
+    // robust cost of keyframe k's edges at pose R; LIN: its 6x6 block and right-hand side into sm.H[buf][k], sm.g[buf][k];
     // CHI: chi2 per edge into chik (keyframe-major)
-    auto evaluate = [&](const double* Rlds, bool lin, int buf, bool store_chi) -> double {
+    auto evaluate = [&](const double* Rlds, bool lin, int buf, bool store_chi, int k) -> double {
+        const int kb = __builtin_amdgcn_readfirstlane(sm.kbeg[k]), ke = __builtin_amdgcn_readfirstlane(sm.kbeg[k + 1]);
         double R[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) R[i] = uniform_f64(Rlds[i]);
@@ -1639,14 +1672,14 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
             for (int u = 0; u < 2; ++u) { pp[u] = pn[u]; zz[u] = zn[u]; }
         }
         const double total = wave_sum(part);
-        if (lin && mine) {
+        if (lin) {
             wave_reduce_scatter<27>(acc, lane);
             if (slot27 >= 0 && slot27 < 21) {
                 int r = 0, rem = slot27;
                 while (rem >= 6 - r) { rem -= 6 - r; ++r; }
                 const int cc = r + rem;
-                sm.H[buf][wave][6 * r + cc] = acc[0]; sm.H[buf][wave][6 * cc + r] = acc[0];
-            } else if (slot27 >= 21) sm.g[buf][wave][slot27 - 21] = acc[0];
+                sm.H[buf][k][6 * r + cc] = acc[0]; sm.H[buf][k][6 * cc + r] = acc[0];
+            } else if (slot27 >= 21) sm.g[buf][k][slot27 - 21] = acc[0];
         }
         return total;
     };
@@ -1660,8 +1693,12 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
     int pc = 0; // which of sm.T / sm.R [0], [1] holds the current pose; sm.R[2] = the last evaluated trial (g2o's edge errors reflect it)
     int cur = 0, it = 0, total_trials = 0, pb = 0, fb = 0;
     if (iters > 0) { // the initial state goes through the same evaluation + linearisation
-        const double c = evaluate(sm.R[pc][wave], true, cur, false);
-        if (lane == 0 && mine) sm.part[pb][wave] = c;
+#pragma unroll 1
+        for (int q = 0; q < nheld; ++q) {
+            const int k = kf_at(q);
+            const double c = evaluate(sm.R[pc][k], true, cur, false, k);
+            if (lane == 0) sm.part[pb][k] = c;
+        }
         __syncthreads();
         currentChi = sum_kf(sm.part[pb]);
         pb ^= 1;
@@ -1678,14 +1715,24 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
         int qmax = 0;
         bool again = true;
         while (again) {
-            double x[6] = {0, 0, 0, 0, 0, 0};
-            if (mine) {
-                double Hk[36], gk[6];
+            // the steps of this wave's keyframes, computed in every lane; a list of them is parked in sm.x until the window knows that every factorisation went through
+            double xw[6] = {0, 0, 0, 0, 0, 0}; // (one keyframe per wave: the step stays in registers)
+#pragma unroll 1
+            for (int q = 0; q < nheld; ++q) {
+                const int k = kf_at(q);
+                double Hk[36], gk[6], x[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
-                for (int i = 0; i < 36; ++i) Hk[i] = sm.H[cur][wave][i];
+                for (int i = 0; i < 36; ++i) Hk[i] = sm.H[cur][k][i];
 #pragma unroll
-                for (int i = 0; i < 6; ++i) gk[i] = sm.g[cur][wave][i];
+                for (int i = 0; i < 6; ++i) gk[i] = sm.g[cur][k][i];
                 if (!chol6_solve(Hk, lambda, gk, x) && lane == 0) sm.flag[fb] = 1;
+                if constexpr (W == kMaxKf) {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) xw[i] = x[i];
+                } else if (lane == 0) {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) sm.x[k][i] = x[i];
+                }
             }
             POH(2);
             __syncthreads();
@@ -1693,35 +1740,35 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
             const bool ok2 = sm.flag[fb] == 0;
             if (tid == 0) sm.flag[fb ^ 1] = 0; // (last read before the previous trial's second barrier, next written after this trial's)
             fb ^= 1;
-            if (!ok2) {
+#pragma unroll 1
+            for (int q = 0; q < nheld; ++q) {
+                const int k = kf_at(q);
+                double sc = 0;
+                {
+                    double x[6], E[7], Tc[7], Tt[7], Rtt[12];
 #pragma unroll
-                for (int i = 0; i < 6; ++i) x[i] = 0;
-            }
-            {
-                double E[7], Tc[7], Tt[7], Rtt[12];
+                    for (int i = 0; i < 6; ++i) x[i] = !ok2 ? 0.0 : W == kMaxKf ? xw[i] : sm.x[k][i];
 #pragma unroll
-                for (int i = 0; i < 7; ++i) Tc[i] = sm.T[pc][wave][i];
-                se3::exp(x, E);
-                se3::mul(E, Tc, Tt);
-                expand_pose(Tt, Rtt);
-                __builtin_amdgcn_wave_barrier();
-                if (lane == 0) {
+                    for (int i = 0; i < 6; ++i) sc += x[i] * (lambda * x[i] + sm.g[cur][k][i]);
 #pragma unroll
-                    for (int i = 0; i < 7; ++i) sm.T[pc ^ 1][wave][i] = Tt[i];
+                    for (int i = 0; i < 7; ++i) Tc[i] = sm.T[pc][k][i];
+                    se3::exp(x, E);
+                    se3::mul(E, Tc, Tt);
+                    expand_pose(Tt, Rtt);
+                    __builtin_amdgcn_wave_barrier();
+                    if (lane == 0) {
 #pragma unroll
-                    for (int i = 0; i < 12; ++i) { sm.R[pc ^ 1][wave][i] = Rtt[i]; sm.R[2][wave][i] = Rtt[i]; }
+                        for (int i = 0; i < 7; ++i) sm.T[pc ^ 1][k][i] = Tt[i];
+#pragma unroll
+                        for (int i = 0; i < 12; ++i) { sm.R[pc ^ 1][k][i] = Rtt[i]; sm.R[2][k][i] = Rtt[i]; }
+                    }
+                    __builtin_amdgcn_wave_barrier();
                 }
-                __builtin_amdgcn_wave_barrier();
+                POH(4);
+                const double c = evaluate(sm.R[pc ^ 1][k], true, cur ^ 1, false, k);
+                POH(5);
+                if (lane == 0) { sm.part[pb][k] = c; sm.spart[pb][k] = sc; }
             }
-            POH(4);
-            const double c = evaluate(sm.R[pc ^ 1][wave], true, cur ^ 1, false);
-            POH(5);
-            double sc = 0;
-            if (mine) {
-#pragma unroll
-                for (int i = 0; i < 6; ++i) sc += x[i] * (lambda * x[i] + sm.g[cur][wave][i]);
-            }
-            if (lane == 0 && mine) { sm.part[pb][wave] = c; sm.spart[pb][wave] = sc; }
             __syncthreads();
             POH(6);
             double tempChi = sum_kf(sm.part[pb]);
@@ -1751,14 +1798,19 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
     if (st && tid == 0) { st->iterations = it; st->total_trials = total_trials; st->chi2_final = currentChi; st->lambda_final = lambda; }
     POH(7);
     // ---- chi2 of every active edge at the last evaluated state, then the adaptive threshold (optimization.cpp:224-252)
-    evaluate(sm.R[2][wave], false, 0, true);
+#pragma unroll 1
+    for (int q = 0; q < nheld; ++q) { const int k = kf_at(q); evaluate(sm.R[2][k], false, 0, true, k); }
     double th = delta; // :154: chi2_th is both the Huber delta and the initial classification threshold
     int cb = 0;
     for (int iteration = 0; iteration < 5; ++iteration) {
-        int cin = 0, cout = 0;
-        for (int j = kb + lane; j < ke; j += 64) { if (chik[j] > th) ++cout; else ++cin; }
-        for (int o = 32; o > 0; o >>= 1) { cin += __shfl_xor(cin, o); cout += __shfl_xor(cout, o); }
-        if (lane == 0) { sm.cin[cb][wave] = mine ? cin : 0; sm.cout[cb][wave] = mine ? cout : 0; }
+#pragma unroll 1
+        for (int q = 0; q < nheld; ++q) {
+            const int k = kf_at(q), kb = sm.kbeg[k], ke = sm.kbeg[k + 1];
+            int cin = 0, cout = 0;
+            for (int j = kb + lane; j < ke; j += 64) { if (chik[j] > th) ++cout; else ++cin; }
+            for (int o = 32; o > 0; o >>= 1) { cin += __shfl_xor(cin, o); cout += __shfl_xor(cout, o); }
+            if (lane == 0) { sm.cin[cb][k] = cin; sm.cout[cb][k] = cout; }
+        }
         __syncthreads();
         int tin = 0, tout = 0;
         for (int k = 0; k < nk; ++k) { tin += sm.cin[cb][k]; tout += sm.cout[cb][k]; }
@@ -1769,19 +1821,26 @@ __global__ __launch_bounds__(kPoBlock) void pose_only_wave_kernel(LmKernelArgs k
     }
     if (ka.want_chi2) { // chi2 in the caller's edge order, 0 for the edges of excluded landmarks (the flags are still the pass's input here)
         double* chi2 = a.chi2 + e0;
-        for (int e = tid; e < ne; e += kPoBlock) if (!inl[lmi[e]]) chi2[e] = 0.0;
-        for (int j = kb + lane; j < ke; j += 64) chi2[list[j]] = chik[j];
+        for (int e = tid; e < ne; e += kBlock) if (!inl[lmi[e]]) chi2[e] = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < nheld; ++q) {
+            const int k = kf_at(q), kb = sm.kbeg[k], ke = sm.kbeg[k + 1];
+            for (int j = kb + lane; j < ke; j += 64) chi2[list[j]] = chik[j];
+        }
     }
     __syncthreads();
     // the last edge of a landmark decides its flag (:254-266, ascending edge order; the edges are sorted by landmark)
-    for (int j = kb + lane; j < ke; j += 64) {
-        const int e = list[j];
-        if (e == ne - 1 || lmi[e + 1] != lmi[e]) inl[lmi[e]] = !(chik[j] > th);
+#pragma unroll 1
+    for (int q = 0; q < nheld; ++q) {
+        const int k = kf_at(q), kb = sm.kbeg[k], ke = sm.kbeg[k + 1];
+        for (int j = kb + lane; j < ke; j += 64) {
+            const int e = list[j];
+            if (e == ne - 1 || lmi[e + 1] != lmi[e]) inl[lmi[e]] = !(chik[j] > th);
+        }
+        if (update_poses && lane < 7) a.T[((size_t)w * a.n_kf + k) * 7 + lane] = sm.T[pc][k][lane];
     }
     if (tid == 0 && a.chi2_thr) a.chi2_thr[w] = th;
-    if (update_poses && mine && lane < 7) a.T[((size_t)w * a.n_kf + wave) * 7 + lane] = sm.T[pc][wave][lane];
     POH(8);
-    (void)ntot;
 #undef POH
 }
 
@@ -1919,13 +1978,22 @@ int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, 
             hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, 0, 5, 0, 0, 1, 1); // (the landmark CSR of the first launch is still valid)
             hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, 0, kSchedFinalIters, 1, 0, 1, 1);
         }
-        // the pose-only pass: one wave per keyframe (pose_only_wave_kernel); Tuning::pose_only_window = 1 (tuning aid / cross-check test) keeps the window kernel
+        // the pose-only pass: pose_only_wave_kernel; Tuning::pose_only_window = 1 (tuning aid / cross-check test) keeps the window kernel
         ka.defer = nullptr; // (every window)
         const bool po_window = scratch->tune && scratch->tune->pose_only_window > 0;
         if (po_window) hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, 1, 10, 1, 0, 1, resident ? 0 : 1); // (the landmark CSR exists only where lm_window_kernel ran the passes)
         else {
             if (ka.dbg_cycles && getenv("VSLAM_PO_PROFILE")) hipMemsetAsync(ka.dbg_cycles, 0, sizeof(long long) * kDbgSlots * a.n_windows, stream); // show only this pass
-            hipLaunchKernelGGL(pose_only_wave_kernel, dim3(a.n_windows), dim3(kPoBlock), 0, stream, ka, 10, 1);
+            // W = kMaxKf where a window's own latency counts (at most one window per CU: sequence mode, small batches), the narrow form beyond -- the rule of
+            // launch_ba_resident; Tuning::pose_only_waves forces either
+            if (scratch->rs_dyn_bytes < 0) { int dev = 0; VS_HIP(hipGetDevice(&dev)); rs_query_device(dev, *scratch); }
+            const int forced = scratch->tune ? scratch->tune->pose_only_waves : -1;
+            const int waves = forced > 0 ? forced : (a.n_windows <= scratch->rs_cu_count ? kMaxKf : kPoseOnlyNarrowWaves);
+            switch (waves) {
+            case kMaxKf: hipLaunchKernelGGL((pose_only_wave_kernel<kMaxKf, 3>), dim3(a.n_windows), dim3(64 * kMaxKf), 0, stream, ka, 10, 1); break;
+            case kPoseOnlyNarrowWaves: hipLaunchKernelGGL((pose_only_wave_kernel<kPoseOnlyNarrowWaves, 2>), dim3(a.n_windows), dim3(64 * kPoseOnlyNarrowWaves), 0, stream, ka, 10, 1); break;
+            default: set_error("pose_only_waves %d is not built", waves); return VSLAM_ERR_ARG;
+            }
         }
     } else {
         hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, mode, iters, update_poses, update_lms, 1, 0);

@@ -235,6 +235,7 @@ struct LmWindowArgs {
 // Kernel-choice overrides of a context (tuning aid / tests): -1 = the library's batch-size rule.  Seeded ONCE at vslam_create from the
 // VSLAM_* environment variables of the same names (validated there), changed afterwards only through vslam_set_tuning -- no getenv on
 // the call path (it races with a host that mutates its environment).
+constexpr int kPoseOnlyNarrowWaves = 4; // the narrow form of pose_only_wave_kernel that the library builds next to VSLAM_MAX_KF waves per window
 struct Tuning {
     int orb_fuse_min = -1;    // VSLAM_ORB_FUSE_MIN: images per call from which orb_pyrblur_kernel replaces resize + blur
     int anms_cap = -1;        // VSLAM_ANMS_CAP: pixels of cleared distance at which orb_anms_kernel's radius walk stops early (0 = never: the full walk;
@@ -243,6 +244,8 @@ struct Tuning {
     int sgbm_fwd_min = -1;    // VSLAM_SGBM_FWD_MIN: pairs per call from which sgbm_forward_kernel replaces three path kernels
     int sgbm_fw_rows = -1;    // VSLAM_SGBM_FW_ROWS: 32 or 64 image rows per slab of the forward sweep
     int pose_only_window = -1; // VSLAM_POSE_ONLY_WINDOW: 1 = the schedule's pose-only pass on lm_window_kernel instead of pose_only_wave_kernel
+    int pose_only_waves = -1; // VSLAM_POSE_ONLY_WAVES: waves per window of pose_only_wave_kernel -- VSLAM_MAX_KF (one keyframe per wave) or kPoseOnlyNarrowWaves (a wave runs a list of
+                              // keyframes, two windows share a CU); 0 = default: VSLAM_MAX_KF when a launch has at most as many windows as the device has CUs, else the narrow form; same bits either way
     int pnp_window = -1;      // VSLAM_PNP_WINDOW: 1 = single-pose problems on lm_window_kernel<pnp> instead of pnp_wave_kernel
     int ba_lanes = -1;        // VSLAM_BA_LANES: 256 | 512 = lanes per window of ba_resident_kernel (default: 512 when a launch has at most as many windows as the device has CUs, else 256 -- two windows per CU; same bits either way)
     int ba_resident = -1;     // VSLAM_BA_RESIDENT: 0 = optimize_map windows always on lm_window_kernel; 1 = on ba_resident_kernel whenever they fit its LDS budget;
