@@ -533,6 +533,34 @@ int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int
  * K >= n_frames - 1 passes reproduce the sequential loop; LM depends on its guess and converges rather than matching exactly.
  * These entries run without the keyframe gate (every frame a keyframe); the *_gated_dev entries below run the gate inside the passes. */
 
+/* ---- Several independent sequences in one batch.  The entries of this section take "a batch of consecutive frames"; a context may instead declare
+ * the batch as n_seg SEGMENTS laid back to back: segment k covers frames [first[k], first[k + 1]) and is a sequence of its own -- its first frame is an
+ * initialisation frame and nothing crosses a boundary.  first: a HOST array of n_seg + 1 strictly ascending ints with first[0] = 0; n_seg = 0 with NULL
+ * clears the table.  The table is context state like the rectification maps: uploaded once, expanded on the device to start(f) = the first frame of
+ * f's segment, counted in vslam_device_bytes; the call synchronises the stream.
+ * CONTRACT: for every segment, every output of every entry below is bit for bit what the same entry gives for a batch that holds that segment alone
+ * (frame indices and offsets rebased).  Without a table every entry launches what it always launched, with the same bits.
+ * A "boundary item" is item i of a per-pair array ((n_frames - 1) rows) whose frame i + 1 is a segment's first frame.  The rules:
+ *   1. Boundary items are empty, whatever the caller's tables hold: no link, no pose input (d_n = 0, index map -1), no honoured match.  Tracks are
+ *      paths over links, so no track crosses a boundary.  The *_requery_dev / *_recover_dev entries give such an item an empty re-matched table
+ *      (d_nf2f_out = 0) without running the matcher on it.
+ *   2. The pose chain restarts at every segment's first frame: G[start] = identity (vslam_chain_poses_dev and the builders' own chain, grouped per segment
+ *      as for a batch that begins there), and a segment's landmark positions live in the world of its first frame.  The entries that take the
+ *      caller's d_T_c_w expect row first[k] to be identity for every k; this is not checked.
+ *   3. Frame states and pairings restart: state[start] = 2, pred[start] = -1, the boundary item's gap is 1.0, no pairing leaves a segment, and the
+ *      Lost scan restarts -- a segment that ends Lost leaves the next one untouched.
+ *   4. Keyframe sets and windows restart: the sliding window of frame b is [max(start(b), b - n_kf + 1), b] with d_n_kf[b] = min(b - start(b) + 1, n_kf);
+ *      the culled and gated sets restart at S = {start}.
+ *   5. Indices and status stay batch-wide: d_kf_frame / d_evicted / d_pred hold batch frame indices, offsets are those of the concatenated arrays, the
+ *      status bits are ORs over the batch, and the capacity rule is unchanged (windows from the first one that does not fit, in batch order, are empty).
+ * Honoured by vslam_build_windows_dev / _kf_dev / _gated_dev / _map_dev / _map_gated_dev / _map_recover_dev, vslam_build_map_pnp_inputs_dev / _gated_dev /
+ * _requery_dev / _recover_dev, vslam_chain_poses_dev, vslam_gate_states_dev, vslam_gate_states_pairs_dev, vslam_frame_pairs_dev and
+ * vslam_build_pnp_inputs_dev (B items = the pairs of B + 1 frames).
+ * VSLAM_ERR_ARG, with vslam_last_error() naming the cause and nothing launched: a malformed table (the previous one stays in place); while a table
+ * is set, one of those calls whose n_frames (or items + 1) differs from first[n_seg], or which carries a chunk input (d_T_abs, d_carry_in,
+ * d_carry_out): a sequence sharded across ranks stays single-sequence. */
+int vslam_set_segments(vslam_ctx* ctx, int n_seg, const int32_t* first);
+
 /* G_0 = identity, G_f = T_rel[f - 1] o G_{f - 1} (n_frames x 7, device): the chain the window builders use, bit for bit.  Asynchronous. */
 int vslam_chain_poses_dev(vslam_ctx* ctx, int n_frames, const double* d_T_rel, double* d_T_c_w);
 

@@ -159,6 +159,7 @@ SIGNATURES = {
     "vslam_build_windows_dev": (I, [P, P, I, I, I, P, P]),
     "vslam_build_windows_kf_dev": (I, [P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_build_windows_gated_dev": (I, [P, P, I, I, D, P, I, I, P, P, P, P, P]),
+    "vslam_set_segments": (I, [P, I, P]),
     "vslam_chain_poses_dev": (I, [P, I, P, P]),
     "vslam_build_map_pnp_inputs_dev": (I, [P, P, P, P, P, P, P, P, I, P]),
     "vslam_build_windows_map_dev": (I, [P, P, P, P, I, I, D, I, I, P, P, P, P]),
@@ -607,6 +608,16 @@ class VO:
         is empty.  Semantics in include/vslam_hip.h."""
         self._chk(self.lib.vslam_build_windows_gated_dev(self.h, C.byref(tracks), n_kf, policy, near_dist, d_num_inliers, lm_capacity, edge_capacity,
                                                          C.byref(batch), d_kf_frame, d_evicted, d_frame_state, d_status), "vslam_build_windows_gated_dev")
+
+    def set_segments(self, first):
+        """declare every following batch of the consecutive-frame entries as independent sequences laid back to back: first = [0, ..., n_frames],
+        strictly ascending, segment k = frames [first[k], first[k + 1]) (the rules: include/vslam_hip.h).  None or an empty list clears the table."""
+        if first is None or len(first) == 0:
+            self._chk(self.lib.vslam_set_segments(self.h, 0, None), "vslam_set_segments")
+            return
+        first = np.ascontiguousarray(first, np.int32)
+        assert first.ndim == 1 and first.size >= 2, first.shape
+        self._chk(self.lib.vslam_set_segments(self.h, int(first.size) - 1, first), "vslam_set_segments")
 
     def chain_poses_dev(self, n_frames, d_T_rel, d_T_c_w):
         """G_0 = identity, G_f = T_rel[f - 1] o G_{f - 1} (n_frames x 7 float64): the window builders' chain"""

@@ -293,7 +293,7 @@ void vslam_destroy(vslam_ctx* ctx) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     orb_tables_free(&c->tab);
-    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc}) b->release();
+    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc, &c->segbuf}) b->release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
     void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad, c->orb.d_anms_path,
                     c->match.d_train_best, c->rect.d_map[0], c->rect.d_map[1], c->rect.d_tiles[0], c->rect.d_tiles[1]};
@@ -1220,6 +1220,38 @@ int vslam_ba_batch_dev(vslam_ctx* ctx, const vslam_ba_batch* b, int schedule, in
     return launch_lm_windows(a, schedule, mode, iters, update_poses, update_lms, &c->lm, c->stream);
 }
 
+// ---- several independent sequences in one batch (the rules: include/vslam_hip.h)
+int vslam_set_segments(vslam_ctx* ctx, int n_seg, const int32_t* first) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("null context"); return VSLAM_ERR_ARG; }
+    if (n_seg < 0 || (n_seg == 0) != (first == nullptr)) { set_error("vslam_set_segments: n_seg >= 1 with first (n_seg + 1 entries), or 0 with NULL to clear the table"); return VSLAM_ERR_ARG; }
+    if (n_seg > 0) {
+        if (first[0] != 0) { set_error("vslam_set_segments: first[0] = %d, must be 0", first[0]); return VSLAM_ERR_ARG; }
+        for (int k = 0; k < n_seg; ++k)
+            if (first[k + 1] <= first[k]) { set_error("vslam_set_segments: first[%d] = %d does not ascend past first[%d] = %d", k + 1, first[k + 1], k, first[k]); return VSLAM_ERR_ARG; }
+    }
+    VS_ENTER(c);
+    VS_HIP(hipStreamSynchronize(c->stream)); // (launches in flight may still read the old table)
+    if (n_seg == 0) { c->seg = SegView(); c->seg_frames = 0; return VSLAM_OK; }
+    const int n_frames = first[n_seg];
+    int32_t *d_first, *d_start, *d_qitem;
+    c->seg = SegView(); c->seg_frames = 0; // (a failed upload leaves no half-written table in place)
+    if (int rc = carve(c->segbuf, c->stream, [&](Layout& L) { d_first = L.take<int32_t>((size_t)n_seg + 1); d_start = L.take<int32_t>(n_frames); d_qitem = L.take<int32_t>(n_frames); })) return rc;
+    VS_HIP(hipMemcpyAsync(d_first, first, sizeof(int32_t) * ((size_t)n_seg + 1), hipMemcpyHostToDevice, c->stream));
+    if (int rc = launch_seg_expand(n_frames, n_seg, d_first, d_start, d_qitem, c->stream)) return rc;
+    VS_HIP(hipStreamSynchronize(c->stream)); // (`first` is the caller's again on return)
+    c->seg.first = d_first; c->seg.start = d_start; c->seg.qitem = d_qitem; c->seg.n_seg = n_seg; c->seg_frames = n_frames;
+    return VSLAM_OK;
+}
+
+// a table is in place: the call must cover exactly its frames, and a chunk of a longer sequence (sequence mode across ranks) stays single-sequence
+static int seg_refuses(const Ctx* c, int n_frames, bool chunk) {
+    if (!c->seg.first) return VSLAM_OK;
+    if (n_frames != c->seg_frames) { set_error("the segment table covers %d frames, this call has %d (vslam_set_segments(ctx, 0, NULL) clears the table)", c->seg_frames, n_frames); return VSLAM_ERR_ARG; }
+    if (chunk) { set_error("a segment table is set: chunk inputs (d_T_abs / d_carry_in / d_carry_out) are not available, sequence mode across ranks is single-sequence"); return VSLAM_ERR_ARG; }
+    return VSLAM_OK;
+}
+
 static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_status,
                          const KfPolicy& kp) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
@@ -1233,6 +1265,7 @@ static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, in
         if (in->d_carry_out || in->carry_out_frame != 0) { set_error("carry_out_frame %d needs d_carry_out and 1 <= carry_out_frame < n_frames (%d)", in->carry_out_frame, in->n_frames); return VSLAM_ERR_ARG; }
     }
     if (in->kp_capacity > 65536) { set_error("kp_capacity %d exceeds 65536 (the window builder packs a keypoint index into 16 bits)", in->kp_capacity); return VSLAM_ERR_ARG; }
+    if (int rc = seg_refuses(c, in->n_frames, in->d_T_abs || in->d_carry_in || in->d_carry_out)) return rc;
     VS_ENTER(c);
     out->n_windows = in->n_frames; out->n_kf = n_kf; out->total_lm = lm_capacity; out->total_edge = edge_capacity;
     double K4[4];
@@ -1240,7 +1273,7 @@ static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, in
     const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
     return launch_build_windows(*in, n_kf, lm_capacity, edge_capacity, K4, c->p.pnp_reproj_thr, track_rule, c->track, const_cast<int32_t*>(out->d_lm_off), const_cast<int32_t*>(out->d_edge_off),
                                 const_cast<int32_t*>(out->d_n_kf), out->d_T_c_w, out->d_xyz, const_cast<uint8_t*>(out->d_reliable), out->d_lm_inlier,
-                                const_cast<int32_t*>(out->d_kf_idx), const_cast<int32_t*>(out->d_lm_idx), const_cast<float*>(out->d_uv), d_status, kp, c->stream);
+                                const_cast<int32_t*>(out->d_kf_idx), const_cast<int32_t*>(out->d_lm_idx), const_cast<float*>(out->d_uv), d_status, kp, c->stream, c->seg);
 }
 
 int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_status) {
@@ -1280,8 +1313,9 @@ int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int
 int vslam_chain_poses_dev(vslam_ctx* ctx, int n_frames, const double* d_T_rel, double* d_T_c_w) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || n_frames <= 0 || !d_T_c_w || (n_frames > 1 && !d_T_rel)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (int rc = seg_refuses(c, n_frames, false)) return rc;
     VS_ENTER(c);
-    return launch_chain_poses(n_frames, d_T_rel, d_T_c_w, c->stream);
+    return launch_chain_poses(n_frames, d_T_rel, d_T_c_w, c->stream, c->seg);
 }
 
 // the refinement passes (vslam_build_map_pnp_inputs_dev, vslam_build_windows_map_dev): poses from the caller, so no chunk and no NULL pose table
@@ -1297,23 +1331,26 @@ int vslam_gate_states_dev(vslam_ctx* ctx, int n_frames, const double* d_T, int a
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || n_frames <= 0 || !d_frame_state || (n_frames > 1 && (!d_T || !d_num_inliers))) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (absolute != 0 && absolute != 1) { set_error("absolute must be 0 (d_T = T_rel) or 1 (d_T = absolute T_c_w)"); return VSLAM_ERR_ARG; }
+    if (int rc = seg_refuses(c, n_frames, false)) return rc;
     VS_ENTER(c);
-    return launch_gate_states(n_frames, d_T, absolute, d_num_inliers, d_frame_state, c->stream);
+    return launch_gate_states(n_frames, d_T, absolute, d_num_inliers, d_frame_state, c->stream, c->seg);
 }
 
 int vslam_frame_pairs_dev(vslam_ctx* ctx, int n_frames, const int32_t* d_frame_state, int32_t* d_pred, double* d_gap) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || n_frames <= 0 || !d_frame_state || !d_pred || (n_frames > 1 && !d_gap)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (int rc = seg_refuses(c, n_frames, false)) return rc;
     VS_ENTER(c);
-    return launch_frame_pairs(n_frames, d_frame_state, d_pred, d_gap, c->stream);
+    return launch_frame_pairs(n_frames, d_frame_state, d_pred, d_gap, c->stream, c->seg);
 }
 
 int vslam_gate_states_pairs_dev(vslam_ctx* ctx, int n_frames, const double* d_T_c_w, const int32_t* d_pred, const int32_t* d_num_inliers,
                                 int32_t* d_frame_state) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || n_frames <= 0 || !d_frame_state || !d_pred || (n_frames > 1 && (!d_T_c_w || !d_num_inliers))) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (int rc = seg_refuses(c, n_frames, false)) return rc;
     VS_ENTER(c);
-    return launch_gate_states_pairs(n_frames, d_T_c_w, d_pred, d_num_inliers, d_frame_state, c->track, c->stream);
+    return launch_gate_states_pairs(n_frames, d_T_c_w, d_pred, d_num_inliers, d_frame_state, c->track, c->stream, c->seg);
 }
 
 // d_frame_state: null for the ungated entry, required by the gated ones; rq: the re-match of the requery entry (its scratch is filled in here), else null;
@@ -1344,12 +1381,13 @@ static int map_pnp_inputs(vslam_ctx* ctx, const vslam_tracks_in* in, const doubl
         }
         rq->ratio = c->p.match_ratio; rq->gap_thr = c->p.match_gap_thr; rq->d_train_best = c->match.d_train_best;
     }
+    if (int rc = seg_refuses(c, in->n_frames, false)) return rc; // (map_refuses above turned every chunk away)
     VS_ENTER(c);
     double K4[4];
     fill_K(c, K4);
     const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
     return launch_map_pnp_inputs(*in, d_T_c_w, d_input_of_match_prev, d_frame_state, K4, c->p.pnp_reproj_thr, track_rule, c->track, d_xyz_w, d_uv, d_n,
-                                 d_input_of_match, out_capacity, d_status, c->stream, rq, rv);
+                                 d_input_of_match, out_capacity, d_status, c->stream, c->seg, rq, rv);
 }
 
 int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, float* d_xyz_w,
@@ -1559,9 +1597,10 @@ int vslam_build_pnp_inputs_dev(vslam_ctx* ctx, const vslam_dmatch* d_f2f, const 
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !d_f2f || !d_nf2f || !d_lr || !d_nlr || !d_xyz_lr || !d_valid_lr || !d_kps_cur || !d_kp2lr || !d_xyz_out || !d_uv_out || !d_nout ||
         match_capacity <= 0 || lr_capacity <= 0 || kp_capacity <= 0 || out_capacity <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (int rc = seg_refuses(c, B + 1, false)) return rc; // (B items = the pairs of B + 1 consecutive frames)
     VS_ENTER(c);
     return launch_build_pnp_inputs(d_f2f, d_nf2f, match_capacity, d_lr, d_nlr, lr_capacity, d_xyz_lr, d_valid_lr, d_kps_cur, kp_capacity, B,
-                                   d_kp2lr, d_xyz_out, d_uv_out, d_nout, out_capacity, c->stream);
+                                   d_kp2lr, d_xyz_out, d_uv_out, d_nout, out_capacity, c->stream, c->seg.start);
 }
 
 // float4 streaming copy of `bytes` (src -> dst, both allocated here), `reps` timed launches after one warm-up, hipEvents on the

@@ -124,7 +124,8 @@ __global__ __launch_bounds__(256) void build_pnp_inputs_kernel(const vslam_dmatc
                                                               const float* __restrict__ d_xyz_lr, const uint8_t* __restrict__ d_valid_lr,
                                                               const vslam_keypoint* __restrict__ d_kpsT, int kp_capacity,
                                                               int32_t* __restrict__ d_kp2lr, float* __restrict__ d_xyz_out,
-                                                              float* __restrict__ d_uv_out, int32_t* __restrict__ d_nout, int out_capacity) {
+                                                              float* __restrict__ d_uv_out, int32_t* __restrict__ d_nout, int out_capacity,
+                                                              const int32_t* __restrict__ seg_start) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ int s_tot[4];
     int32_t* kp2lr = d_kp2lr + (size_t)b * kp_capacity;
@@ -137,7 +138,8 @@ __global__ __launch_bounds__(256) void build_pnp_inputs_kernel(const vslam_dmatc
         if (q >= 0 && q < kp_capacity) kp2lr[q] = i;
     }
     __syncthreads();
-    const int nm = min(d_nm[b], match_capacity);
+    // seg_start (vslam_set_segments; null: one sequence): frame b + 1 opens a new sequence, the item carries no pose input whatever d_m holds
+    const int nm = seg_start && seg_start[b + 1] == b + 1 ? 0 : min(d_nm[b], match_capacity);
     const vslam_dmatch* m = d_m + (size_t)b * match_capacity;
     int written = 0;
     for (int base = 0; base < nm; base += 256) {
@@ -169,11 +171,11 @@ __global__ __launch_bounds__(256) void build_pnp_inputs_kernel(const vslam_dmatc
 int launch_build_pnp_inputs(const vslam_dmatch* d_m, const int32_t* d_nm, int match_capacity, const vslam_dmatch* d_lr,
                             const int32_t* d_nlr, int lr_capacity, const float* d_xyz_lr, const uint8_t* d_valid_lr,
                             const vslam_keypoint* d_kpsT, int kp_capacity, int B, int32_t* d_kp2lr, float* d_xyz_out, float* d_uv_out,
-                            int32_t* d_nout, int out_capacity, hipStream_t stream) {
+                            int32_t* d_nout, int out_capacity, hipStream_t stream, const int32_t* d_seg_start) {
     if (B <= 0) return VSLAM_OK;
     ProfScope prof__(stream, "build_pnp_inputs_kernel");
     hipLaunchKernelGGL(build_pnp_inputs_kernel, dim3(B), dim3(256), 0, stream, d_m, d_nm, match_capacity, d_lr, d_nlr, lr_capacity, d_xyz_lr,
-                       d_valid_lr, d_kpsT, kp_capacity, d_kp2lr, d_xyz_out, d_uv_out, d_nout, out_capacity);
+                       d_valid_lr, d_kpsT, kp_capacity, d_kp2lr, d_xyz_out, d_uv_out, d_nout, out_capacity, d_seg_start);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

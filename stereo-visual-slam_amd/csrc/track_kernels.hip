@@ -38,7 +38,27 @@
 
 namespace vslam {
 
-struct TrackDims { int B, kp_cap, lr_cap, match_cap, pnp_cap, n_kf; };
+// start / first / n_seg (vslam_set_segments; null, null, 0: the batch is one sequence): the batch holds n_seg independent sequences laid back to back,
+// segment k = frames [first[k], first[k + 1]), start[f] = the first frame of f's segment.  Every kernel below that pairs frame f with f - 1, or treats
+// frame 0 as THE initialisation, does so per segment; indices stay batch-wide.  A null test is all a one-sequence batch pays.
+struct TrackDims { int B, kp_cap, lr_cap, match_cap, pnp_cap, n_kf; const int32_t* start = nullptr; const int32_t* first = nullptr; int n_seg = 0; };
+__device__ inline int seg_start(const int32_t* __restrict__ start, int f) { return start ? start[f] : 0; }
+// item `it` (the pair it -> it + 1) straddles two segments: it is empty whatever the caller's tables hold
+__device__ inline bool seg_boundary_item(const int32_t* __restrict__ start, int it) { return start && start[it + 1] == it + 1; }
+// the frames [lo, hi) workgroup blockIdx.x of a one-workgroup-per-segment kernel owns (first null: the whole batch)
+__device__ inline void seg_slice(const int32_t* __restrict__ first, int B, int& lo, int& hi) {
+    lo = first ? first[blockIdx.x] : 0; hi = first ? first[blockIdx.x + 1] : B;
+}
+
+// vslam_set_segments: start[f] by bisection of first, and the matcher's query block of every item (the item itself; -1 empties a boundary item)
+__global__ __launch_bounds__(256) void seg_expand_kernel(int B, int n_seg, const int32_t* __restrict__ first, int32_t* __restrict__ start, int32_t* __restrict__ qitem) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= B) return;
+    int lo = 0, hi = n_seg; // largest k with first[k] <= f
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (first[mid] <= f) lo = mid; else hi = mid; }
+    start[f] = first[lo];
+    if (f > 0) qitem[f - 1] = first[lo] == f ? -1 : f - 1;
+}
 
 // ---- per frame: keypoint -> L/R match table; chain tables cleared
 __global__ __launch_bounds__(256) void track_init_kernel(TrackDims d, const vslam_dmatch* __restrict__ d_lr, const int32_t* __restrict__ d_nlr,
@@ -57,15 +77,19 @@ __global__ __launch_bounds__(256) void track_init_kernel(TrackDims d, const vsla
 
 // ---- global poses: G[0] = identity, G[f] = T_rel[f - 1] o G[f - 1]; inclusive scan of SE3 products (Hillis-Steele in LDS, chunks of 256
 // frames chained through a carry).  SE3 composition is associative; the scan's grouping differs from a sequential chain only in rounding.
-__global__ __launch_bounds__(256) void track_pose_chain_kernel(int B, const double* __restrict__ T_rel, double* __restrict__ G) {
+// Segments: one workgroup per segment runs the same chunk loop on its slice, so a segment's products are grouped as in a batch that begins at its
+// first frame and G[first[k]] = identity.
+__global__ __launch_bounds__(256) void track_pose_chain_kernel(int B_all, const double* __restrict__ T_rel, double* __restrict__ G, const int32_t* __restrict__ first) {
     __shared__ double buf[2][256][7];
     __shared__ double carry[7];
     const int tid = threadIdx.x;
+    int f_lo, B;
+    seg_slice(first, B_all, f_lo, B);
     if (tid == 0) { carry[0] = carry[1] = carry[2] = 0; carry[3] = 1; carry[4] = carry[5] = carry[6] = 0; }
-    for (int base = 0; base < B; base += 256) {
+    for (int base = f_lo; base < B; base += 256) {
         const int f = base + tid;
         double X[7] = {0, 0, 0, 1, 0, 0, 0};
-        if (f > 0 && f < B)
+        if (f > f_lo && f < B)
 #pragma unroll
             for (int i = 0; i < 7; ++i) X[i] = T_rel[(size_t)(f - 1) * 7 + i];
         int cur = 0;
@@ -112,7 +136,7 @@ __global__ __launch_bounds__(256) void track_link_kernel(TrackDims d, const vsla
     __shared__ int s_tot[4];
     // lfrm (the recover entries; null: adjacent frames): the query frame of item `it` when its links are honoured, -1 when they are not (uniform exit)
     const int l = lfrm ? lfrm[it] : it;
-    if (l < 0) return;
+    if (l < 0 || seg_boundary_item(d.start, it)) return; // (no link crosses a segment boundary: the tracks are paths over these links)
     const int nm = min(max(d_nf2f[it], 0), d.match_cap);
     const vslam_dmatch* m = d_f2f + (size_t)it * d.match_cap;
     if (kMap) {
@@ -291,11 +315,11 @@ __device__ inline double kf_distance(const double* __restrict__ Gk, const double
     return sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2] + xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
 }
 
-__global__ __launch_bounds__(256) void kf_band_kernel(int B, const double* __restrict__ G, double* __restrict__ D) {
+__global__ __launch_bounds__(256) void kf_band_kernel(int B, const double* __restrict__ G, double* __restrict__ D, const int32_t* __restrict__ start) {
     const int t = blockIdx.x * 256 + threadIdx.x, b = t / kKfBand, j = t - b * kKfBand + 1;
     if (b >= B) return;
     double v = 0.0;
-    if (b - j >= 0) {
+    if (b - j >= seg_start(start, b)) {
         double Gi[7];
         se3::inverse(G + (size_t)b * 7, Gi);
         v = kf_distance(G + (size_t)(b - j) * 7, Gi);
@@ -318,20 +342,22 @@ __device__ inline void wave_lds_sync() {
 // records 0 members in nmem (its window is empty); a rejected frame (state 0) sets bit 2 of the flags.  policy 0 evicts the oldest member (no band:
 // D = nullptr), policy 1 as above.  nmem[b] = |S_b| at a keyframe step.
 template <bool kGate>
-__global__ __launch_bounds__(64) void kf_set_kernel(int B, int n_kf, double near_dist, const double* __restrict__ G, const double* __restrict__ D,
+__global__ __launch_bounds__(64) void kf_set_kernel(int B_all, int n_kf, double near_dist, const double* __restrict__ G, const double* __restrict__ D,
                                                     int32_t* __restrict__ kf_frame, int32_t* __restrict__ evicted, int32_t* __restrict__ flags,
-                                                    const int32_t* __restrict__ state, int32_t* __restrict__ nmem) {
+                                                    const int32_t* __restrict__ state, int32_t* __restrict__ nmem, const int32_t* __restrict__ first) {
     __shared__ double rows[kKfRows][kKfBand];
     __shared__ double s_d[VSLAM_MAX_KF];
     __shared__ int s_m[VSLAM_MAX_KF];
     __shared__ int s_st[kKfRows];
     const int lane = threadIdx.x;
     const bool band = !kGate || D != nullptr;
-    int mem = lane == 0 ? 0 : -1, n = 1, flag = 0;
-    if (lane < n_kf) kf_frame[lane] = mem;
-    if (lane == 0) evicted[0] = -1;
-    if (kGate && lane == 0) nmem[0] = 1; // (frame 0 is a keyframe: initialization)
-    for (int base = 1; base < B; base += kKfRows) {
+    int f_lo, B; // (segments: one wave per segment, S restarts at {first[k]}; the chains are independent, the staging is relative to the slice)
+    seg_slice(first, B_all, f_lo, B);
+    int mem = lane == 0 ? f_lo : -1, n = 1, flag = 0;
+    if (lane < n_kf) kf_frame[(size_t)f_lo * n_kf + lane] = mem;
+    if (lane == 0) evicted[f_lo] = -1;
+    if (kGate && lane == 0) nmem[f_lo] = 1; // (a segment's first frame is a keyframe: initialization)
+    for (int base = f_lo + 1; base < B; base += kKfRows) {
         __syncthreads();
         if (band)
 #pragma unroll
@@ -386,17 +412,19 @@ __global__ __launch_bounds__(64) void kf_set_kernel(int B, int n_kf, double near
             if (kGate && lane == 0) nmem[b] = st == 2 ? n : 0;
         }
     }
-    if (lane == 0) *flags = flag;
+    if (lane == 0) { if (first) { if (flag) atomicOr(flags, flag); } else *flags = flag; } // (segments: the launcher cleared the word)
 }
 
 // ---- insert_key_frame's gate, one thread per frame: frame 0 is a keyframe (initialization), frame f >= 1 gets keyframe_state(num_inliers_,
 // T_c_l_) from the pose stage's outputs of item f - 1.  T: the relative poses T_rel (n_frames - 1 rows), or -- kAbs, a refinement pass's gate
 // (vslam_gate_states_dev absolute = 1) -- the absolute poses G (n_frames rows), T_c_l_ = G_f o G_{f-1}^-1 as the reference takes it (:615)
 template <bool kAbs>
-__global__ __launch_bounds__(256) void kf_gate_kernel(int B, const int32_t* __restrict__ num_inliers, const double* __restrict__ T, int32_t* __restrict__ state) {
+__global__ __launch_bounds__(256) void kf_gate_kernel(int B, const int32_t* __restrict__ num_inliers, const double* __restrict__ T, int32_t* __restrict__ state,
+                                                       const int32_t* __restrict__ start) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= B) return;
-    if (!kAbs || f == 0) { state[f] = f == 0 ? 2 : keyframe_state(num_inliers[f - 1], T + (size_t)(f - 1) * 7); return; }
+    const bool init = f == seg_start(start, f); // (a segment's first frame)
+    if (!kAbs || init) { state[f] = init ? 2 : keyframe_state(num_inliers[f - 1], T + (size_t)(f - 1) * 7); return; }
     double Gi[7], T_c_l[7];
     se3::inverse(T + (size_t)(f - 1) * 7, Gi);
     se3::mul(T + (size_t)f * 7, Gi, T_c_l);
@@ -407,12 +435,13 @@ __global__ __launch_bounds__(256) void kf_gate_kernel(int B, const int32_t* __re
 // check_motion_estimation (visual_odometry.cpp:328-329).  A frame without a predecessor (pred outside [0, f)) had no item in the pass: raw state 0.
 // With pred(f) = f - 1 the arithmetic is kf_gate_kernel<true>'s.
 __global__ __launch_bounds__(256) void kf_gate_pairs_kernel(int B, const int32_t* __restrict__ num_inliers, const double* __restrict__ G,
-                                                           const int32_t* __restrict__ pred, int32_t* __restrict__ state) {
+                                                           const int32_t* __restrict__ pred, int32_t* __restrict__ state, const int32_t* __restrict__ start) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= B) return;
-    if (f == 0) { state[0] = 2; return; }
+    const int f_lo = seg_start(start, f);
+    if (f == f_lo) { state[f] = 2; return; }
     const int p = pred[f];
-    if (p < 0 || p >= f) { state[f] = 0; return; }
+    if (p < f_lo || p >= f) { state[f] = 0; return; }
     double Gi[7], T_c_l[7];
     se3::inverse(G + (size_t)p * 7, Gi);
     se3::mul(G + (size_t)f * 7, Gi, T_c_l);
@@ -428,20 +457,24 @@ __global__ __launch_bounds__(256) void kf_gate_pairs_kernel(int B, const int32_t
 // accepted and the table of pred_prev -- null: f - 1 -- was built on that same pairing, else -1), flags (bit 3: a Lost frame; bit 4: a state outside
 // 0..3 or a pred_prev[f] outside [-1, f), whose item is emptied).  Thread tid owns the frames tid + 256 k in both phases.
 constexpr int kLostGap = 11; // f - pred(f) above this: more than ten consecutive rejections (:673)
-__global__ __launch_bounds__(256) void frame_pairs_kernel(int B, const int32_t* state, int32_t* state_out, int32_t* __restrict__ pred, double* __restrict__ gap,
+// Segments: one workgroup per segment on its slice [f_lo, B) -- the scan, the Lost frames and nxt restart there, a segment's first frame always counts
+// and has pred -1; the boundary item before it gets gap 1.0 and lfrm -1; a pred_prev entry that points into an earlier segment is out of range.
+__global__ __launch_bounds__(256) void frame_pairs_kernel(int B_all, const int32_t* state, int32_t* state_out, int32_t* __restrict__ pred, double* __restrict__ gap,
                                                          int32_t* __restrict__ nxt, const int32_t* __restrict__ pred_prev, int32_t* __restrict__ lfrm,
-                                                         int32_t* __restrict__ flags) {
+                                                         int32_t* __restrict__ flags, const int32_t* __restrict__ first) {
     __shared__ int s[256];
     __shared__ int carry, first_lost;
     const int tid = threadIdx.x;
+    int f_lo, B;
+    seg_slice(first, B_all, f_lo, B);
     if (tid == 0) { carry = -1; first_lost = B; }
     __syncthreads();
     int flag = 0;
-    for (int base = 0; base < B; base += 256) {
+    for (int base = f_lo; base < B; base += 256) {
         const int f = base + tid;
         const int st = f < B ? state[f] : 0;
-        if (f > 0 && f < B && (st < 0 || st > 3)) flag |= 16;
-        s[tid] = f < B && (f == 0 || st == 1 || st == 2) ? f : -1;
+        if (f > f_lo && f < B && (st < 0 || st > 3)) flag |= 16;
+        s[tid] = f < B && (f == f_lo || st == 1 || st == 2) ? f : -1;
         __syncthreads();
         for (int dd = 1; dd < 256; dd <<= 1) {
             const int a = tid >= dd ? s[tid - dd] : -1;
@@ -451,8 +484,8 @@ __global__ __launch_bounds__(256) void frame_pairs_kernel(int B, const int32_t* 
         }
         const int incl = max(carry, s[tid]), excl = max(carry, tid > 0 ? s[tid - 1] : -1);
         if (f < B) {
-            pred[f] = f == 0 ? -1 : excl;
-            if (f > 0 && f - excl > kLostGap) atomicMin(&first_lost, f);
+            pred[f] = f == f_lo ? -1 : excl;
+            if (f > f_lo && f - excl > kLostGap) atomicMin(&first_lost, f);
         }
         __syncthreads();
         if (tid == 255) carry = incl;
@@ -460,24 +493,24 @@ __global__ __launch_bounds__(256) void frame_pairs_kernel(int B, const int32_t* 
     }
     const int L = first_lost;
     if (nxt) {
-        for (int f = tid; f < B; f += 256) nxt[f] = -1;
+        for (int f = f_lo + tid; f < B; f += 256) nxt[f] = -1;
         __syncthreads();
     }
-    for (int f = tid; f < B; f += 256) {
+    for (int f = f_lo + tid; f < B; f += 256) {
         const int st = state[f];
         const bool lost = f >= L;
         int p = pred[f];
         if (lost) { p = -1; pred[f] = -1; }
-        if (state_out) state_out[f] = f == 0 ? 2 : lost ? 3 : (st < 0 || st > 3) ? 0 : st;
-        const bool acc = f > 0 && !lost && (st == 1 || st == 2);
-        if (f > 0) gap[f - 1] = p >= 0 ? (double)(f - p) : 1.0;
+        if (state_out) state_out[f] = f == f_lo ? 2 : lost ? 3 : (st < 0 || st > 3) ? 0 : st;
+        const bool acc = f > f_lo && !lost && (st == 1 || st == 2);
+        if (f > 0) gap[f - 1] = p >= 0 ? (double)(f - p) : 1.0; // (p = -1 at a segment's first frame: the boundary item's gap is 1.0)
         if (nxt && acc) nxt[p] = f;
-        if (lfrm && f > 0) {
+        if (lfrm && f > f_lo) {
             const int pp = pred_prev ? pred_prev[f] : f - 1;
-            const bool bad = pp < -1 || pp >= f;
+            const bool bad = pp < -1 || pp >= f || (pp >= 0 && pp < f_lo);
             if (bad) flag |= 16;
             lfrm[f - 1] = acc && !bad && pp == p ? p : -1;
-        }
+        } else if (lfrm && f > 0) lfrm[f - 1] = -1;
     }
     if (L < B) flag |= 8;
     if (flags && flag) atomicOr(flags, flag);
@@ -487,12 +520,12 @@ __global__ __launch_bounds__(256) void frame_pairs_kernel(int B, const int32_t* 
 __global__ void status_or_kernel(int32_t* __restrict__ status, const int32_t* __restrict__ flags) { *status |= *flags; }
 
 // policy 0 through vslam_build_windows_kf_dev: the sliding window's sets written out
-__global__ __launch_bounds__(256) void kf_sliding_kernel(int B, int n_kf, int32_t* __restrict__ kf_frame, int32_t* __restrict__ evicted) {
+__global__ __launch_bounds__(256) void kf_sliding_kernel(int B, int n_kf, int32_t* __restrict__ kf_frame, int32_t* __restrict__ evicted, const int32_t* __restrict__ start) {
     const int t = blockIdx.x * 256 + threadIdx.x, b = t / n_kf, k = t - b * n_kf;
     if (b >= B) return;
-    const int s = max(0, b - n_kf + 1);
+    const int f_lo = seg_start(start, b), s = max(f_lo, b - n_kf + 1);
     kf_frame[t] = s + k <= b ? s + k : -1;
-    if (k == 0) evicted[b] = b >= n_kf ? b - n_kf : -1;
+    if (k == 0) evicted[b] = b - f_lo >= n_kf ? b - n_kf : -1;
 }
 
 // ---- carry-out for the chunk that starts at frame c of this batch: per keypoint slot of frame c, does a track reach it from frame c - 1, and
@@ -527,7 +560,7 @@ __global__ __launch_bounds__(256) void track_map_inputs_kernel(TrackDims d, cons
     __shared__ int s_tot[4];
     // qfrm (the recover entries; null: frame `it`): the frame the queries of item `it` live in, frame it + 1's last accepted predecessor (in [0, it]
     // by construction, frame_pairs_kernel); -1: the frame is Lost, no input and an index map of -1
-    const int l = qfrm ? qfrm[it] : it;
+    const int l = seg_boundary_item(d.start, it) ? -1 : qfrm ? qfrm[it] : it; // (a boundary item carries no pose input)
     const int nm = l < 0 ? 0 : min(max(d_nf2f[it], 0), d.match_cap);
     const vslam_dmatch* m = d_f2f + (size_t)it * d.match_cap;
     int32_t* map = in_of_match + (size_t)it * d.match_cap;
@@ -574,7 +607,9 @@ __global__ __launch_bounds__(256) void track_features_kernel(TrackDims d, const 
                                                             int32_t* __restrict__ feat, int32_t* __restrict__ nfeat, double* __restrict__ gap) {
     const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ int s_tot[4];
-    const int n = nkps ? min(max(nkps[f], 0), d.kp_cap) : d.kp_cap;
+    // (a one-frame segment has no pair: like a one-frame batch, which runs no walk, it lists nothing)
+    const bool lone = d.start && d.start[f] == f && (f + 1 >= d.B || d.start[f + 1] == f + 1);
+    const int n = lone ? 0 : nkps ? min(max(nkps[f], 0), d.kp_cap) : d.kp_cap;
     int written = 0;
     for (int base = 0; base < n; base += 256) {
         const int i = base + tid;
@@ -590,6 +625,9 @@ __global__ __launch_bounds__(256) void track_features_kernel(TrackDims d, const 
     }
     if (tid == 0) { nfeat[f] = written; if (gap && f + 1 < d.B) gap[f] = 1.0; } // (gap null: the recover entry's pairing wrote the gaps)
 }
+
+// first frame of sliding window b: the window never reaches before its segment
+__device__ inline int window_first(const TrackDims& d, int b) { return max(seg_start(d.start, b), b - d.n_kf + 1); }
 
 // A chain HEAD of window [s, b]: a node in frame s, or a node without predecessor (a landmark created inside the window).  Every
 // landmark observed in the window has exactly one.  Returns the observations it has inside the window (0: not a head) -- from the
@@ -616,7 +654,7 @@ __device__ inline int window_set_head_len(int r, const int2* __restrict__ ends, 
 struct WindowSet { const int32_t* kf_frame; const int2* ends; const int32_t* root; const int32_t* nmem; const int32_t* nxt = nullptr; }; // nxt: see track_walk_kernel
 template <bool kSet>
 __device__ inline int window_frames(const TrackDims& d, const WindowSet& ws, int b, int* s_kf) {
-    const int s = max(0, b - d.n_kf + 1), nk = kSet && ws.nmem ? ws.nmem[b] : b - s + 1;
+    const int s = window_first(d, b), nk = kSet && ws.nmem ? ws.nmem[b] : b - s + 1;
     if (threadIdx.x < nk) s_kf[threadIdx.x] = kSet ? ws.kf_frame[(size_t)b * d.n_kf + threadIdx.x] : s + threadIdx.x;
     __syncthreads();
     return nk;
@@ -635,7 +673,7 @@ constexpr int kHist = VSLAM_MAX_KF + 1;
 template <bool kSet>
 __global__ __launch_bounds__(256) void window_count_kernel(TrackDims d, const int32_t* __restrict__ info, const int32_t* __restrict__ nkps,
                                                           int32_t* __restrict__ counts, int32_t* __restrict__ hist, WindowSet ws) {
-    const int b = blockIdx.x, tid = threadIdx.x, s = max(0, b - d.n_kf + 1);
+    const int b = blockIdx.x, tid = threadIdx.x, s = window_first(d, b);
     __shared__ int red[4];
     __shared__ int h[kHist];
     __shared__ int s_kf[VSLAM_MAX_KF];
@@ -690,7 +728,7 @@ __global__ __launch_bounds__(256) void window_scan_kernel(TrackDims d, const int
             int ol = il, oe = ie;
             if (over) { ol = -1; oe = -1; }
             lm_off[b + 1] = ol; edge_off[b + 1] = oe;
-            n_kf_out[b] = kSet && nmem ? nmem[b] : min(b + 1, d.n_kf);
+            n_kf_out[b] = kSet && nmem ? nmem[b] : min(b - seg_start(d.start, b) + 1, d.n_kf);
         }
         __syncthreads();
         if (tid == 255) { carry_l = il; carry_e = ie; }
@@ -720,7 +758,7 @@ __global__ __launch_bounds__(kRankBlock) void window_rank_kernel(TrackDims d, co
                                                                 const int32_t* __restrict__ nkps, const int32_t* __restrict__ lm_off,
                                                                 const int32_t* __restrict__ edge_off, double* __restrict__ T_out,
                                                                 uint32_t* __restrict__ head_rec, WindowSet ws) {
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = max(0, b - d.n_kf + 1);
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, s = window_first(d, b);
     __shared__ int s_c[kRankWaves][kHist];
     __shared__ int bin_l[kHist], s_run[kHist];
     __shared__ int s_kf[VSLAM_MAX_KF];
@@ -784,7 +822,7 @@ __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vsl
     if (g >= lm_off[d.B]) return;
     int lo = 0, hi = d.B; // largest b with lm_off[b] <= g
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (lm_off[mid] <= g) lo = mid; else hi = mid; }
-    const int b = lo, s = max(0, b - d.n_kf + 1), l = g - lm_off[b];
+    const int b = lo, s = window_first(d, b), l = g - lm_off[b];
     const uint32_t rec = head_rec[g];
     const int32_t* kfs = ws.kf_frame + (size_t)b * d.n_kf;
     const int slot = (int)(rec & 15u), f = kSet ? kfs[slot] : s + slot, i = (int)((rec >> 4) & 0xFFFFu), len = (int)(rec >> 20);
@@ -833,9 +871,11 @@ __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vsl
 
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
-                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream) {
+                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream, const SegView& seg) {
     TrackDims d;
     d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = n_kf;
+    d.start = seg.start; d.first = seg.first; d.n_seg = seg.n_seg;
+    const int seg_grid = seg.first ? seg.n_seg : 1; // the per-sequence kernels: one workgroup per segment
     const bool gate = kp.gate, cull = kp.policy == 1 || gate; // (cull: the set-templated window kernels)
     const size_t tab = (size_t)d.B * d.kp_cap;
     int32_t *kp2lr, *pred, *succ, *root, *relsrc, *info, *counts, *hist; double* G; uint32_t* head_rec;
@@ -867,24 +907,26 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
     ProfScope prof__(stream, "build_windows_kernels", 9);
     if (kp.recover) { // which frame every frame continues from under the caller's states, and which items' links that honours (table built on kp.pred_table)
         VS_HIP(hipMemsetAsync(r_flags, 0, sizeof(int32_t), stream));
-        hipLaunchKernelGGL(frame_pairs_kernel, dim3(1), dim3(256), 0, stream, d.B, kp.state_in, r_state, r_pred, r_gap, nxt, kp.pred_table, lfrm, r_flags);
+        hipLaunchKernelGGL(frame_pairs_kernel, dim3(seg_grid), dim3(256), 0, stream, d.B, kp.state_in, r_state, r_pred, r_gap, nxt, kp.pred_table, lfrm, r_flags, seg.first);
     }
     hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
     if (kp.G) VS_HIP(hipMemcpyAsync(G, kp.G, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (the map builder: the caller's poses)
     else if (in.d_T_abs) VS_HIP(hipMemcpyAsync(G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
-    else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(1), dim3(256), 0, stream, d.B, in.d_T_rel, G);
+    else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(seg_grid), dim3(256), 0, stream, d.B, in.d_T_rel, G, seg.first);
     const int32_t* state = kp.recover ? r_state : kp.state_in ? kp.state_in : kp.frame_state; // (the map builder: the caller's states; recover: with the Lost frames marked)
+    if (cull && seg.first) VS_HIP(hipMemsetAsync(set_flags, 0, sizeof(int32_t), stream)); // (the segments' waves OR their flags into the word)
     if (gate) { // the states depend on the pose stage's outputs alone, the keyframe sets on the states and the poses
         if (!kp.state_in)
-            hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((d.B + 255) / 256), dim3(256), 0, stream, d.B, kp.num_inliers, in.d_T_rel, kp.frame_state);
-        if (kp.policy == 1) hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D);
-        hipLaunchKernelGGL(kf_set_kernel<true>, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, kp.policy == 1 ? D : nullptr, kp.kf_frame, kp.evicted,
-                           set_flags, state, nmem);
+            hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((d.B + 255) / 256), dim3(256), 0, stream, d.B, kp.num_inliers, in.d_T_rel, kp.frame_state, seg.start);
+        if (kp.policy == 1) hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D, seg.start);
+        hipLaunchKernelGGL(kf_set_kernel<true>, dim3(seg_grid), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, kp.policy == 1 ? D : nullptr, kp.kf_frame, kp.evicted,
+                           set_flags, state, nmem, seg.first);
     } else if (cull) { // the keyframe sets depend on the poses alone
-        hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D);
-        hipLaunchKernelGGL(kf_set_kernel<false>, dim3(1), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, D, kp.kf_frame, kp.evicted, set_flags, nullptr, nullptr);
+        hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D, seg.start);
+        hipLaunchKernelGGL(kf_set_kernel<false>, dim3(seg_grid), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, D, kp.kf_frame, kp.evicted, set_flags, nullptr, nullptr,
+                           seg.first);
     } else if (kp.policy == 0)
-        hipLaunchKernelGGL(kf_sliding_kernel, dim3((d.B * n_kf + 255) / 256), dim3(256), 0, stream, d.B, n_kf, kp.kf_frame, kp.evicted);
+        hipLaunchKernelGGL(kf_sliding_kernel, dim3((d.B * n_kf + 255) / 256), dim3(256), 0, stream, d.B, n_kf, kp.kf_frame, kp.evicted, seg.start);
     if (d.B > 1 && kp.in_of_match)
         hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, kp.in_of_match, lfrm);
     else if (d.B > 1)
@@ -920,40 +962,40 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
 }
 
 // ---- G[0] = identity, G[f] = T_rel[f - 1] o G[f - 1]: the builders' chain on its own (vslam_chain_poses_dev)
-int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream) {
+int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream, const SegView& seg) {
     ProfScope prof__(stream, "track_pose_chain_kernel");
-    hipLaunchKernelGGL(track_pose_chain_kernel, dim3(1), dim3(256), 0, stream, n_frames, d_T_rel, d_G);
+    hipLaunchKernelGGL(track_pose_chain_kernel, dim3(seg.first ? seg.n_seg : 1), dim3(256), 0, stream, n_frames, d_T_rel, d_G, seg.first);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }
 
 // ---- the keyframe gate on its own (vslam_gate_states_dev): on the relative poses (the gated builder's states, bit for bit) or on absolute ones
-int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream) {
+int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream, const SegView& seg) {
     ProfScope prof__(stream, "kf_gate_kernel");
-    if (absolute) hipLaunchKernelGGL(kf_gate_kernel<true>, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_T, d_state);
-    else hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_T, d_state);
+    if (absolute) hipLaunchKernelGGL(kf_gate_kernel<true>, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_T, d_state, seg.start);
+    else hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_T, d_state, seg.start);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }
 
 // ---- the pairing on its own (vslam_frame_pairs_dev) and the gate against it (vslam_gate_states_pairs_dev: raw states, then the Lost scan in place;
 // the scan's pred / gap go to scratch)
-int launch_frame_pairs(int n_frames, const int32_t* d_state, int32_t* d_pred, double* d_gap, hipStream_t stream) {
+int launch_frame_pairs(int n_frames, const int32_t* d_state, int32_t* d_pred, double* d_gap, hipStream_t stream, const SegView& seg) {
     ProfScope prof__(stream, "frame_pairs_kernel");
-    hipLaunchKernelGGL(frame_pairs_kernel, dim3(1), dim3(256), 0, stream, n_frames, d_state, (int32_t*)nullptr, d_pred, d_gap, (int32_t*)nullptr,
-                       (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(frame_pairs_kernel, dim3(seg.first ? seg.n_seg : 1), dim3(256), 0, stream, n_frames, d_state, (int32_t*)nullptr, d_pred, d_gap, (int32_t*)nullptr,
+                       (const int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, seg.first);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }
 
 int launch_gate_states_pairs(int n_frames, const double* d_G, const int32_t* d_pred, const int32_t* d_num_inliers, int32_t* d_state, DevBuf& scratch,
-                             hipStream_t stream) {
+                             hipStream_t stream, const SegView& seg) {
     int32_t* s_pred; double* s_gap;
     if (int rc = carve(scratch, stream, [&](Layout& L) { s_pred = L.take<int32_t>(n_frames); s_gap = L.take<double>(n_frames); })) return rc;
     ProfScope prof__(stream, "kf_gate_pairs_kernel", 2);
-    hipLaunchKernelGGL(kf_gate_pairs_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_G, d_pred, d_state);
-    hipLaunchKernelGGL(frame_pairs_kernel, dim3(1), dim3(256), 0, stream, n_frames, d_state, d_state, s_pred, s_gap, (int32_t*)nullptr, (const int32_t*)nullptr,
-                       (int32_t*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(kf_gate_pairs_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, d_num_inliers, d_G, d_pred, d_state, seg.start);
+    hipLaunchKernelGGL(frame_pairs_kernel, dim3(seg.first ? seg.n_seg : 1), dim3(256), 0, stream, n_frames, d_state, d_state, s_pred, s_gap, (int32_t*)nullptr, (const int32_t*)nullptr,
+                       (int32_t*)nullptr, (int32_t*)nullptr, seg.first);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }
@@ -966,11 +1008,18 @@ int launch_gate_states_pairs(int n_frames, const double* d_G, const int32_t* d_p
 // rv (vslam_build_map_pnp_inputs_recover_dev, with rq; else null): d_state also gives the pairing -- every frame against its last accepted predecessor,
 // Lost frames without one (frame_pairs_kernel: rv->d_pred, rv->d_gap) --, the walk honours a pair's links only when in.d_f2f was built on that pairing
 // (rv->d_pred_prev) and steps through the accepted frames, and pair f - 1 is re-matched from the features of pred(f) at gap f - pred(f)
+int launch_seg_expand(int n_frames, int n_seg, const int32_t* d_first, int32_t* d_start, int32_t* d_qitem, hipStream_t stream) {
+    hipLaunchKernelGGL(seg_expand_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, n_seg, d_first, d_start, d_qitem);
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
 int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
                           double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
-                          int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq, const MapRecover* rv) {
+                          int out_capacity, int32_t* d_status, hipStream_t stream, const SegView& seg, const MapRequery* rq, const MapRecover* rv) {
     TrackDims d;
     d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = 1;
+    d.start = seg.start; d.first = seg.first; d.n_seg = seg.n_seg;
     const size_t tab = (size_t)d.B * d.kp_cap;
     int32_t *kp2lr, *pred, *succ, *root, *relsrc, *cand; double* gap = nullptr; int32_t *nxt = nullptr, *lfrm = nullptr, *r_state = nullptr;
     if (int rc = carve(scratch, stream, [&](Layout& L) {
@@ -989,7 +1038,8 @@ int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const in
         return VSLAM_OK;
     }
     if (rv) // (the flags -- a Lost frame, an out-of-range state or d_pred_prev entry -- go straight into the status word cleared above)
-        hipLaunchKernelGGL(frame_pairs_kernel, dim3(1), dim3(256), 0, stream, d.B, d_state, r_state, rv->d_pred, rv->d_gap, nxt, rv->d_pred_prev, lfrm, d_status);
+        hipLaunchKernelGGL(frame_pairs_kernel, dim3(seg.first ? seg.n_seg : 1), dim3(256), 0, stream, d.B, d_state, r_state, rv->d_pred, rv->d_gap, nxt, rv->d_pred_prev, lfrm,
+                           d_status, seg.first);
     hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
     if (d_in_of_match_prev)
         hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ,
@@ -1006,10 +1056,11 @@ int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const in
     if (rq) { // pair i: queries = the features of frame i, trains = every keypoint of frame i + 1, the gate of VO::feature_matching at frame_gap 1
         hipLaunchKernelGGL(track_features_kernel, dim3(d.B), dim3(256), 0, stream, d, root, in.d_nkps, rq->d_feat, rq->d_nfeat, gap);
         prof_end(stream); // (the matcher brackets its own kernels: this bracket closes before it ...
-        // (rv: item i's query block is frame pred(i + 1) -- the d_qitem path, block indices = frame indices -- at the pairing's gaps)
+        // (rv: item i's query block is frame pred(i + 1) -- the d_qitem path, block indices = frame indices -- at the pairing's gaps; segments: the same
+        // path with block i for item i and -1 for a boundary item, which the matcher leaves empty without running on it.  pred = -1 at a segment's first frame)
         if (int rc = launch_match(rq->d_desc, rq->desc_stride, in.d_nkps, rq->d_desc + rq->desc_stride, rq->desc_stride, in.d_nkps + 1, rv ? rv->d_gap : gap, 1,
                                   rq->ratio, rq->gap_thr, d.B - 1, d.kp_cap, rq->d_train_best, rq->d_f2f_out, d.match_cap, rq->d_nf2f_out, stream, rq->d_feat,
-                                  d.kp_cap, rq->d_nfeat, rv ? rv->d_pred + 1 : nullptr, rv ? d.B : 0)) return rc;
+                                  d.kp_cap, rq->d_nfeat, rv ? rv->d_pred + 1 : seg.qitem, rv || seg.qitem ? d.B : 0)) return rc;
         prof_begin(stream, "track_map_inputs_kernel", 1); // ... and prof__ closes this one, around the emit)
         f2f = rq->d_f2f_out; nf2f = rq->d_nf2f_out;
     }

@@ -190,7 +190,7 @@ int launch_triangulate(const float* d_uvL, const float* d_uvR, const int32_t* d_
 int launch_build_pnp_inputs(const vslam_dmatch* d_m, const int32_t* d_nm, int match_capacity, const vslam_dmatch* d_lr,
                             const int32_t* d_nlr, int lr_capacity, const float* d_xyz_lr, const uint8_t* d_valid_lr,
                             const vslam_keypoint* d_kpsT, int kp_capacity, int B, int32_t* d_kp2lr, float* d_xyz_out, float* d_uv_out,
-                            int32_t* d_nout, int out_capacity, hipStream_t stream);
+                            int32_t* d_nout, int out_capacity, hipStream_t stream, const int32_t* d_seg_start = nullptr);
 int launch_gather_uv(const vslam_keypoint* d_kpsQ, const vslam_keypoint* d_kpsT, int kp_capacity, const vslam_dmatch* d_m,
                      const int32_t* d_nm, int match_capacity, int B, float* d_uvQ, float* d_uvT, hipStream_t stream);
 
@@ -328,18 +328,22 @@ struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evic
                   // recover (vslam_build_windows_map_recover_dev; with gate, G, state_in): the states also give the pairing of every frame with its last
                   // accepted predecessor; pred_table (n_frames) is the pairing in.d_f2f was built on -- a pair's links hold only where the two agree
                   bool recover = false; const int32_t* pred_table = nullptr; };
+// The segment table of a context as the launchers see it (vslam_set_segments; all null / 0: the batch is one sequence): start[f] = first frame of
+// f's segment (n_frames), first (n_seg + 1), qitem[i] = i, or -1 for the item before a segment's first frame (n_frames - 1).
+struct SegView { const int32_t* start = nullptr; const int32_t* first = nullptr; const int32_t* qitem = nullptr; int n_seg = 0; };
+int launch_seg_expand(int n_frames, int n_seg, const int32_t* d_first, int32_t* d_start, int32_t* d_qitem, hipStream_t stream);
 // K4 = {fx, fy, cx, cy}, reproj_thr (pixels), track_rule: see Tuning::track_rule
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
                          int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
-                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream);
-int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream);
+                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream, const SegView& seg);
+int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream, const SegView& seg);
 // insert_key_frame's gate per frame (vslam_gate_states_dev): absolute 0 on T_rel (n_frames - 1 rows), 1 on absolute poses (n_frames rows)
-int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream);
+int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream, const SegView& seg);
 // the reference's failure handling: every frame's last accepted predecessor / gap / Lost from the states (vslam_frame_pairs_dev), and the gate taken
 // against that predecessor at that gap followed by the Lost scan (vslam_gate_states_pairs_dev)
-int launch_frame_pairs(int n_frames, const int32_t* d_state, int32_t* d_pred, double* d_gap, hipStream_t stream);
+int launch_frame_pairs(int n_frames, const int32_t* d_state, int32_t* d_pred, double* d_gap, hipStream_t stream, const SegView& seg);
 int launch_gate_states_pairs(int n_frames, const double* d_G, const int32_t* d_pred, const int32_t* d_num_inliers, int32_t* d_state, DevBuf& scratch,
-                             hipStream_t stream);
+                             hipStream_t stream, const SegView& seg);
 // vslam_build_map_pnp_inputs_recover_dev: the pairing in.d_f2f was built on (null: adjacent frames) and the outputs of this pass's pairing
 struct MapRecover { const int32_t* d_pred_prev; int32_t* d_pred; double* d_gap; };
 // the re-match of vslam_build_map_pnp_inputs_requery_dev: frame f's descriptors at d_desc + f * desc_stride; outputs the feature lists (n_frames x kp_capacity,
@@ -350,7 +354,7 @@ struct MapRequery { const uint8_t* d_desc; size_t desc_stride; int32_t* d_feat; 
 // pairs are re-matched on their feature sets between the walk and the emit, *_requery_dev)
 int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
                           double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
-                          int out_capacity, int32_t* d_status, hipStream_t stream, const MapRequery* rq = nullptr, const MapRecover* rv = nullptr);
+                          int out_capacity, int32_t* d_status, hipStream_t stream, const SegView& seg, const MapRequery* rq = nullptr, const MapRecover* rv = nullptr);
 
 // ----------------------------------------------------------------------------------------------- rectification
 // rectify_kernels.hip: the map builder (host, double, once per rig), the device entry format and the gather kernel
@@ -389,6 +393,9 @@ struct Ctx {
     Tuning tune;
     Prof* prof;           // stage profiler of this context (vslam_profile_enable); null until first enabled
     RectifyState rect;    // vslam_rectify_set / vslam_rectify_set_maps
+    DevBuf segbuf{"segment table", &dev_bytes}; // vslam_set_segments: first, start, qitem
+    SegView seg;          // ... as the launchers take it (all null: no table)
+    int seg_frames;       // first[n_seg] of the table in place (0: none)
     bool orb_ok;          // img_w, img_h >= 64: the ORB entry points serve this context (a smaller one is a rectification target only)
 };
 

@@ -19,7 +19,7 @@ import torch
 
 from . import BaBatch, DMATCH_DTYPE, KEYPOINT_DTYPE, TracksIn, VO, _sgbm_params, default_params, sgbm_params_check
 from . import synth
-from .trajectory import assemble_trajectory, sliding_keyframes, write_trajectory  # noqa: F401  (re-exported)
+from .trajectory import assemble_trajectories, assemble_trajectory, sliding_keyframes, write_trajectory  # noqa: F401  (re-exported)
 
 
 class KeyframePipeline:
@@ -27,7 +27,7 @@ class KeyframePipeline:
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
                  lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
                  keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all", sgbm_params=None, rejected_frames="pass_through",
-                 rectify=None, raw_images=None):
+                 rectify=None, raw_images=None, segments=None, segment_sequences=None):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
         sgbm_params (depth="sgbm"): the StereoSGBM set of the batched disparity call -- an SgbmParams, a dict of its fields or a tuple
@@ -64,7 +64,14 @@ class KeyframePipeline:
         rectify: a RectifyParams -- the rig delivers RAW images: they live in their own device buffer, and stage_rectify() (the first stage of step())
         fills the batch's images from them through the rig's two maps (vslam_rectify_set / vslam_rectify_dev) on the pipeline's stream.  raw_images:
         the (2B, src_h, src_w) uint8 raw images [left 0..B-1 | right 0..B-1]; absent, the rendered frames serve as the raw images (a rig whose
-        source size equals the image size).  None: the images are the rendered frames, as before, and stage_rectify is never called."""
+        source size equals the image size).  None: the images are the rendered frames, as before, and stage_rectify is never called.
+        segments = [n_0, n_1, ...] (lengths >= 1 that sum to B; ba_windows="tracks", no frame_range): the batch holds that many INDEPENDENT sequences
+        laid back to back (vslam_set_segments; the rules are in include/vslam_hip.h): every segment's first frame is an initialisation frame, and
+        tracks, the pose chain, frame states and pairings, keyframe sets and windows all restart there, so every output of segment s is bit for bit
+        that of KeyframePipeline(B=n_s, sequence=segment_sequences[s]) with the same options.  Segment s shows the frames that pipeline shows;
+        segment_sequences = None renders them with seed + 7919 s (PipelineRing's convention).  pose_passes = K gives the sequential loop for frames
+        0..K of EVERY segment, so K = max(n_s) - 1 is exact for the whole batch.  Frame indices in download() stay batch-wide; download() adds
+        seg_first, trajectories() returns one trajectory per segment."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
         assert keyframe_gate in (False, True, "per_pass"), "keyframe_gate: False, True (on stage A's inputs) or 'per_pass' (inside the map passes)"
@@ -81,6 +88,16 @@ class KeyframePipeline:
         assert rejected_frames in ("pass_through", "recover")
         assert rejected_frames == "pass_through" or (per_pass and pose_inputs == "map" and f2f_queries == "features"), \
             "rejected_frames='recover' needs pose_inputs='map', keyframe_gate='per_pass' and f2f_queries='features'"
+        self.seg_first = None
+        if segments is not None:
+            segments = [int(n_) for n_ in segments]
+            assert len(segments) >= 1 and min(segments) >= 1 and sum(segments) == B, "segments: lengths >= 1 that sum to B"
+            assert with_ba and ba_windows == "tracks" and frame_range is None, "segments need ba_windows='tracks' and no frame_range"
+            assert sequence is None, "a segmented pipeline takes segment_sequences (one rendered sequence per segment), not sequence"
+            assert segment_sequences is None or len(segment_sequences) == len(segments)
+            self.seg_first = np.concatenate([[0], np.cumsum(segments)]).astype(np.int32)
+        else:
+            assert segment_sequences is None, "segment_sequences needs segments"
         self.f2f_queries = f2f_queries
         self.rejected_frames = rejected_frames
         self.pose_inputs, self.pose_passes = pose_inputs, int(pose_passes)
@@ -109,23 +126,37 @@ class KeyframePipeline:
         d = self.dev
         # ---- inputs: 2B images [left 0..B-1 | right 0..B-1]; consecutive keyframes of `unique_scenes` short sequences
         imgs = np.zeros((2 * B, self.h, self.pitch), np.uint8)
-        n_u = max(2, min(unique_frames, B if frame_range is None else int(frame_range[2]))) if (B > 1 or frame_range is not None) else 1
-        # `sequence`: an already rendered synth.stereo_sequence(n_u, seed) (tests that build several pipelines over the same frames)
-        seq = sequence if sequence is not None else synth.stereo_sequence(n_u, seed=seed, w=self.w, h=self.h, workers=render_workers)
-        assert len(seq) == n_u, (len(seq), n_u)
-        if verbose:
-            print("rendered %d stereo keyframes" % n_u, flush=True)
-        period = max(2 * (n_u - 1), 1)
-        f0 = 0
-        if frame_range is not None:
-            f0 = int(frame_range[0])
-            assert int(frame_range[1]) - f0 == B
-        self.frame_of = [(t if t < n_u else period - t) for t in ((f0 + b) % period for b in range(B))]
+        if self.seg_first is None:
+            n_u = max(2, min(unique_frames, B if frame_range is None else int(frame_range[2]))) if (B > 1 or frame_range is not None) else 1
+            # `sequence`: an already rendered synth.stereo_sequence(n_u, seed) (tests that build several pipelines over the same frames)
+            seq = sequence if sequence is not None else synth.stereo_sequence(n_u, seed=seed, w=self.w, h=self.h, workers=render_workers)
+            assert len(seq) == n_u, (len(seq), n_u)
+            if verbose:
+                print("rendered %d stereo keyframes" % n_u, flush=True)
+            period = max(2 * (n_u - 1), 1)
+            f0 = 0
+            if frame_range is not None:
+                f0 = int(frame_range[0])
+                assert int(frame_range[1]) - f0 == B
+            self.frame_of = [(t if t < n_u else period - t) for t in ((f0 + b) % period for b in range(B))]
+            self.unique_frames = n_u
+        else:   # every segment laid out as the pipeline of its length alone lays out its batch; frame_of indexes the sequences joined end to end
+            self.h_seqs, self.frame_of, seq = [], [], []
+            for s_, n_s in enumerate(segments):
+                n_u = max(2, min(unique_frames, n_s)) if n_s > 1 else 1
+                sq = segment_sequences[s_] if segment_sequences is not None else \
+                    synth.stereo_sequence(n_u, seed=seed + 7919 * s_, w=self.w, h=self.h, workers=render_workers)
+                assert len(sq) == n_u, (s_, len(sq), n_u)
+                period = max(2 * (n_u - 1), 1)
+                self.frame_of += [len(seq) + (t if t < n_u else period - t) for t in (b % period for b in range(n_s))]
+                self.h_seqs.append(sq); seq = seq + list(sq)
+            if verbose:
+                print("rendered %d stereo keyframes in %d segments" % (len(seq), len(segments)), flush=True)
+            self.unique_frames = unique_frames   # (the per-segment cap, as given: PipelineRing hands it to its other pipelines)
         for b in range(B):
             L, R, _, _ = seq[self.frame_of[b]]
             imgs[b, :, :self.w] = L
             imgs[B + b, :, :self.w] = R
-        self.unique_frames = n_u
         self.h_seq = seq   # (kept: a second pipeline over the same frames needs no second rendering)
         self.h_imgs = imgs
         self.h_imgs_unique_left = np.stack([np.pad(f[0], ((0, 0), (0, self.pitch - self.w))) for f in seq])
@@ -248,6 +279,12 @@ class KeyframePipeline:
             bb.total_lm = self.lm_capacity; bb.total_edge = self.edge_capacity
             self.ba_batch = bb
             self.unique_windows = B
+            if self.seg_first is not None:   # the table is context state: every consecutive-frame entry of this context honours it from here on
+                self.vo.set_segments(self.seg_first)
+                ft = torch.from_numpy(self.seg_first.astype(np.int64)).to(d)
+                self.seg_starts = ft[:-1]            # the segments' first frames
+                self.seg_boundary = ft[1:-1] - 1     # the items (pairs) that straddle two segments
+                self.seg_start_of = torch.repeat_interleave(ft[:-1], ft[1:] - ft[:-1])   # start(f) per frame
         # ---- canned local-BA windows
         if with_ba and ba_windows == "synthetic":
             unique_windows = B if unique_windows is None else max(1, min(unique_windows, B))
@@ -322,11 +359,16 @@ class KeyframePipeline:
         """keyframe b-1 -> keyframe b for b = 1..B-1 (the first keyframe of the batch has no predecessor in the batch)"""
         B, cap = self.B, self.cap
         if B < 2:
+            if self.pose_inputs == "map":   # one frame, no pair: the passes leave G = identity, state 2 and empty tables
+                self._map_passes()
             return
         vo, n = self.vo, B - 1
         # query = left descriptors of keyframe b-1 (item i = b-1), train = left descriptors of keyframe b
         vo.feature_matching_dev(self.d_desc.data_ptr(), cap * 32, self.d_cnt.data_ptr(), self.d_desc.data_ptr() + cap * 32, cap * 32,
                                 self.d_cnt.data_ptr() + 4, self.d_gap.data_ptr(), 1, n, cap, self.d_f2f.data_ptr(), cap, self.d_nf2f.data_ptr())
+        if self.seg_first is not None and len(self.seg_boundary):   # the matcher pairs every frame with the next one: a pair across two segments is no pair
+            with torch.cuda.stream(self.stream):
+                self.d_nf2f[self.seg_boundary] = 0
         vo.build_pnp_inputs_dev(self.d_f2f.data_ptr(), self.d_nf2f.data_ptr(), cap, self.d_lr.data_ptr(), self.d_nlr.data_ptr(), cap,
                                 self.d_xyz.data_ptr(), self.d_valid.data_ptr(), self.d_kps.data_ptr() + cap * 28, cap, n, self.d_kp2lr.data_ptr(),
                                 self.d_pxyz.data_ptr(), self.d_puv.data_ptr(), self.d_pn.data_ptr(), cap)
@@ -337,6 +379,8 @@ class KeyframePipeline:
     def _solve(self, xyz, uv, n_in, T, inl, ninl, guess):
         """the pose stage on the B - 1 problems (xyz, uv, n_in): T (B x 7) and the inlier flags / counts"""
         cap, n = self.cap, self.B - 1
+        if n == 0:
+            return
         if self.pose == "ransac":   # no pose guess is consumed (useExtrinsicGuess = false)
             self.vo.pnp_ransac_dev(xyz.data_ptr(), uv.data_ptr(), n_in.data_ptr(), cap, n, T.data_ptr(), 100, 4.0, 0.99, inl.data_ptr(), ninl.data_ptr(), None)
             return
@@ -395,10 +439,15 @@ class KeyframePipeline:
             with torch.cuda.stream(self.stream):
                 Gn[0].copy_(self.d_Tident[0])
                 if recover:   # no inlier: the pose of the frame matched against (a Lost frame: of the last accepted frame before the run)
-                    keep = torch.cummax(pred, 0).values.clamp(min=0)[1:].long()
+                    keep = torch.cummax(pred, 0).values.clamp(min=0)
+                    if self.seg_first is not None:   # (... of its own segment: never earlier than the segment's first frame)
+                        keep = torch.maximum(keep, self.seg_start_of)
+                    keep = keep[1:].long()
                     Gn[1:].copy_(torch.where((self.map_ninl[:n] > 0)[:, None], self.map_T[:n], G[keep]))
                 else:
                     Gn[1:].copy_(torch.where((self.map_ninl[:n] > 0)[:, None], self.map_T[:n], G[:n]))
+                if self.seg_first is not None:   # every segment's first frame is its world: the boundary items' solutions and fallbacks are dropped
+                    Gn[self.seg_starts] = self.d_Tident[0]
                 if gated and k == self.pose_passes - 1:
                     self.map_state_prev.copy_(self.ba_frame_state)
             if recover:   # the gate against the frame matched against, at the pair's gap, then the Lost scan
@@ -517,7 +566,9 @@ class KeyframePipeline:
             if self.window_policy == "reference" or self.keyframe_gate:
                 out["ba_kf_frame"] = self.ba_kf_frame.cpu().numpy(); out["ba_evicted"] = self.ba_evicted.cpu().numpy()
             else:
-                out["ba_kf_frame"], out["ba_evicted"] = sliding_keyframes(B, self.n_kf)
+                out["ba_kf_frame"], out["ba_evicted"] = self._sliding_keyframes()
+            if self.seg_first is not None:
+                out["seg_first"] = self.seg_first.copy()
             if self.keyframe_gate:   # (per_pass: the last pass's states; frame_state_prev: the states that pass started from)
                 out["frame_state"] = self.ba_frame_state.cpu().numpy()
                 if self.keyframe_gate == "per_pass":
@@ -536,19 +587,41 @@ class KeyframePipeline:
             out["T_c_w"] = self.map_G[c].cpu().numpy()
         return out
 
-    def trajectory(self):
-        """(frame_ids, T_c_w): every frame's pose from the BA windows (ba_windows="tracks"), in the order the reference writes them -- a frame when it
-        is evicted (from the last window that held it), the last window's frames at the end.  write_trajectory(path, *pipe.trajectory()) writes the
-        file KITTI evaluation reads.  With keyframe_gate, only keyframes are written, each from the last keyframe window that held it."""
+    def _sliding_keyframes(self):
+        """the sliding windows' sets on the host, per segment when the batch is segmented (batch frame indices)"""
+        if self.seg_first is None:
+            return sliding_keyframes(self.B, self.n_kf)
+        parts = [sliding_keyframes(int(hi - lo), self.n_kf) for lo, hi in zip(self.seg_first[:-1], self.seg_first[1:])]
+        kf = np.concatenate([np.where(k >= 0, k + lo, -1) for (k, _), lo in zip(parts, self.seg_first)]).astype(np.int32)
+        ev = np.concatenate([np.where(e >= 0, e + lo, -1) for (_, e), lo in zip(parts, self.seg_first)]).astype(np.int32)
+        return kf, ev
+
+    def _trajectory_inputs(self):
         assert self.with_ba and self.ba_windows == "tracks"
         self.vo.sync()
         torch.cuda.synchronize(self.dev)
         if self.window_policy == "reference" or self.keyframe_gate:
             kf_frame, evicted = self.ba_kf_frame.cpu().numpy(), self.ba_evicted.cpu().numpy()
         else:
-            kf_frame, evicted = sliding_keyframes(self.B, self.n_kf)
+            kf_frame, evicted = self._sliding_keyframes()
         valid = (self.ba_frame_state.cpu().numpy() == 2) if self.keyframe_gate else None
-        return assemble_trajectory(kf_frame, evicted, self.ba_T.cpu().numpy(), window_valid=valid)
+        return kf_frame, evicted, self.ba_T.cpu().numpy(), valid
+
+    def trajectories(self):
+        """a segmented pipeline's trajectories: one (frame_ids, T_c_w) per segment as trajectory() gives it for that segment's pipeline alone, the ids
+        local to the segment.  An unsegmented pipeline has one segment."""
+        kf_frame, evicted, ba_T, valid = self._trajectory_inputs()
+        first = self.seg_first if self.seg_first is not None else np.array([0, self.B])
+        return assemble_trajectories(kf_frame, evicted, ba_T, first, window_valid=valid)
+
+    def trajectory(self):
+        """(frame_ids, T_c_w): every frame's pose from the BA windows (ba_windows="tracks"), in the order the reference writes them -- a frame when it
+        is evicted (from the last window that held it), the last window's frames at the end.  write_trajectory(path, *pipe.trajectory()) writes the
+        file KITTI evaluation reads.  With keyframe_gate, only keyframes are written, each from the last keyframe window that held it.
+        A segmented pipeline holds several trajectories: trajectories()."""
+        assert self.seg_first is None, "a segmented pipeline has one trajectory per segment: use trajectories()"
+        kf_frame, evicted, ba_T, valid = self._trajectory_inputs()
+        return assemble_trajectory(kf_frame, evicted, ba_T, window_valid=valid)
 
     def close(self):
         self.vo.close()
@@ -569,8 +642,10 @@ class PipelineRing:
         together are different data; otherwise all pipelines show the first one's frames (tests compare their results bit for bit)"""
         assert P >= 1
         kw0 = dict(kw)
+        segmented = kw.get("segments") is not None   # (segments / segment_sequences pass through; `sequences[i]` is then pipeline i's segment_sequences)
+        seq_key = "segment_sequences" if segmented else "sequence"
         if sequences is not None:
-            kw0["sequence"] = sequences[0]
+            kw0[seq_key] = sequences[0]
         first = KeyframePipeline(B, **kw0)
         self.pipes = [first]
         for i in range(1, P):
@@ -578,11 +653,11 @@ class PipelineRing:
             kw2["unique_frames"] = first.unique_frames
             kw2["verbose"] = False
             if sequences is not None and i < len(sequences):
-                kw2["sequence"] = sequences[i]; kw2["render_workers"] = 0
-            elif distinct:
-                kw2["seed"] = kw.get("seed", 0) + 7919 * i
+                kw2[seq_key] = sequences[i]; kw2["render_workers"] = 0
+            elif distinct:   # (a segmented pipeline uses seed + 7919 s for its segments: the next pipeline's seeds start after them)
+                kw2["seed"] = kw.get("seed", 0) + 7919 * i * (len(kw["segments"]) if segmented else 1)
             else:
-                kw2["sequence"] = first.h_seq          # the other pipelines show the same rendered frames: no second rendering
+                kw2[seq_key] = first.h_seqs if segmented else first.h_seq   # the other pipelines show the same rendered frames: no second rendering
                 kw2["render_workers"] = 0
             self.pipes.append(KeyframePipeline(B, **kw2))
         self.distinct = distinct or (sequences is not None and len(sequences) > 1)

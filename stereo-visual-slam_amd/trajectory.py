@@ -49,6 +49,24 @@ def assemble_trajectory(kf_frame, evicted, ba_T, window_valid=None):
     return np.array(ids, np.int64), (np.stack(poses) if poses else np.zeros((0, 7)))
 
 
+def assemble_trajectories(kf_frame, evicted, ba_T, first, window_valid=None):
+    """assemble_trajectory for a batch of independent sequences laid back to back (vslam_set_segments): first = [0, ..., B], segment s = frames
+    [first[s], first[s + 1]); kf_frame / evicted hold batch frame indices, as the segmented builders write them.  Returns one (frame_ids, T_c_w)
+    per segment, the ids local to the segment (frame first[s] is 0): what assemble_trajectory gives for that segment's batch alone."""
+    kf_frame = np.asarray(kf_frame); evicted = np.asarray(evicted); ba_T = np.asarray(ba_T, np.float64)
+    first = np.asarray(first, np.int64)
+    if first.ndim != 1 or first.size < 2 or first[0] != 0 or first[-1] != kf_frame.shape[0] or (np.diff(first) <= 0).any():
+        raise ValueError("first must ascend strictly from 0 to the number of windows (%d): %r" % (kf_frame.shape[0], first.tolist()))
+    out = []
+    for lo, hi in zip(first[:-1], first[1:]):
+        kf, ev = kf_frame[lo:hi], evicted[lo:hi]
+        if ((kf >= 0) & ((kf < lo) | (kf >= hi))).any() or ((ev >= 0) & ((ev < lo) | (ev >= hi))).any():
+            raise ValueError("the keyframe sets of segment [%d, %d) reach outside it" % (lo, hi))
+        out.append(assemble_trajectory(np.where(kf >= 0, kf - lo, -1), np.where(ev >= 0, ev - lo, -1), ba_T[lo:hi],
+                                       None if window_valid is None else np.asarray(window_valid, bool)[lo:hi]))
+    return out
+
+
 def _rotmat(q):
     x, y, z, w = q
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
