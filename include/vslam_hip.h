@@ -735,6 +735,49 @@ int vslam_build_windows_map_recover_dev(vslam_ctx* ctx, const vslam_tracks_in* i
                                         const int32_t* d_pred, const int32_t* d_frame_state, int n_kf, int policy, double near_dist, int lm_capacity,
                                         int edge_capacity, vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status);
 
+/* ---- Throughput mode, CHAINED BA windows (additive: vslam_ba_batch, vslam_params and the ABI version are unchanged).  vslam_ba_batch_dev treats the
+ * windows of a batch as independent: is_inlier is 1 on entry to every window, a keyframe enters window b at its pose-stage pose, and the BA runs from
+ * the first keyframe.  The reference carries the is_inlier flags from one optimize_map to the next keyframe's graph (optimization.cpp:160), passes every
+ * keyframe through up to ten successive schedules, each from the poses the one before wrote (:272-278), and starts at keyframes_.size() >= 10
+ * (run_vslam.cpp:58).  optimize_map is only ever called with if_update_landmark = false and the new keyframe's pose comes from solvePnPRansac without
+ * a guess (visual_odometry.cpp:268-290), so what one window hands to the next is (a) the poses of the keyframes they share and (b) one is_inlier flag per
+ * landmark.  A keyframe's identity is its batch frame index; a landmark's is the root of its track, below.
+ *
+ * Landmark identities.  d_lm_id (capacity int32, device) is context state like the segment table; NULL / 0 clears it.  While it is set, every
+ * vslam_build_windows*_dev entry also writes d_lm_id[l] for each landmark l of the concatenated landmark array: frame x kp_capacity + keypoint of the
+ * keypoint that CREATED the landmark (batch frame index).  Two landmarks of a batch's windows are the same map landmark exactly when their ids are
+ * equal; inside a window the ids are distinct.  With no buffer set every builder launches exactly what it launches without this entry.
+ * Refused with VSLAM_ERR_ARG while a buffer is set: a builder call whose lm_capacity exceeds `capacity`; a chunk call (d_T_abs / d_carry_in /
+ * d_carry_out), because a root from before the batch has no frame index.  The call itself refuses capacity < 0 and NULL with capacity != 0 (or the reverse). */
+int vslam_set_window_ids(vslam_ctx* ctx, int32_t* d_lm_id, int capacity);
+
+/* The chained BA.  `batch`: what a builder filled for the whole batch (n_windows = frames); d_lm_id: the ids that builder wrote (total_lm entries);
+ * d_kf_frame: the builder's keyframe sets, or NULL for the sliding window [max(start(w), w - n_kf + 1), w].  The segment table says which windows form a
+ * sequence; without one the batch is one sequence.  Step j = 0, 1, ... runs the schedule of vslam_ba_batch_dev(schedule = 1) -- same kernels, same
+ * tuning keys -- on the j-th window of every sequence that has one, all of them in one launch.  Window w = first[s] + j at step j:
+ *   1. entry state: slot k holds frame g = d_kf_frame[w][k]; for g == w the slot keeps the builder's pose, for g != w it takes the pose the chain holds
+ *      for g (the latest value an earlier window of the sequence left for it; the builder's if there is none); lm_inlier[l] = the chain's flag of
+ *      d_lm_id[l], 1 until some window has written it;
+ *   2. the window is ACTIVE when d_n_kf[w] >= min_kf (min_kf = 10: the reference's keyframes_.size() >= 10; 1: every non-empty window); a window with
+ *      d_n_kf[w] = 0 (the gate's non-keyframe steps) never is;
+ *   3. an active window runs the schedule from that state; its poses, flags, chi2 and stats go to the caller's arrays at window w and into the chain
+ *      state; d_ran[w] = 1;
+ *   4. an inactive window with d_n_kf[w] > 0: the carried poses and flags of 1 are written to the caller's arrays at w, its own pose enters the chain
+ *      state, d_ran[w] = 0 -- so the last window that held a frame always has that frame's final pose;
+ *   5. an inactive window with d_n_kf[w] = 0 is left as built; d_ran[w] = 0.
+ * COMPOSITION of step j (the result is bit for bit vslam_ba_batch_dev(schedule = 1) on this batch): one window slot per sequence with more than j
+ * frames, ascending; n_kf, total_lm, total_edge and K4 the caller's; an active window's landmarks and edges packed in slot order; an inactive window
+ * EMPTY (offsets do not advance, d_n_kf = 0, the builder's poses) -- the shape the gated builders emit.  Nothing between two steps waits for the device:
+ * no synchronisation, no device-to-host copy.  State (a pose per frame, a byte per n_frames x kp_capacity root) and the staging batch (sized by the
+ * caller's totals) live in a growable scratch of the context, counted by vslam_device_bytes.
+ * Afterwards vslam_ba_status_dev(ctx, n_windows, h) returns, per window of the CALLER's batch, the status word of the step that ran it (0 for an
+ * inactive window); vslam_ba_schedule_passes_dev / vslam_ba_deferred_dev describe single launches and return VSLAM_ERR_ARG until the next one.
+ * d_chi2 / d_stats / d_reliable / d_n_kf of the batch and d_ran are optional.  Device safety: every offset, id and frame index read from the caller's
+ * arrays is range-checked; a window whose offsets leave the arrays is treated as inactive.
+ * Refused with VSLAM_ERR_ARG: NULL d_lm_id, min_kf outside 1..batch->n_kf, batch->n_windows different from the segment table's frame count when a
+ * table is set, and what vslam_ba_batch_dev refuses.  Asynchronous on the context stream. */
+int vslam_ba_chain_dev(vslam_ctx* ctx, const vslam_ba_batch* batch, const int32_t* d_lm_id, const int32_t* d_kf_frame, int min_kf, int32_t* d_ran);
+
 /* per-window status of the most recent window launch on this process (VSLAM_OK or VSLAM_ERR_ARG per window) */
 int vslam_ba_status_dev(vslam_ctx* ctx, int n_windows, int32_t* h_status);
 /* optimize_map passes the most recent vslam_ba_batch_dev(schedule = 1) call EXECUTED per window: 3 = all of run_vslam.cpp:61-66; 1 or 2 = the

@@ -156,6 +156,8 @@ SIGNATURES = {
     "vslam_local_ba": (I, [P, I, P, I, P, I, P, P, P, P, P, I, I, I, P, P, P, P]),
     "vslam_pose_only_window": (I, [P, I, P, I, P, I, P, P, P, P, P, I, I, P, P, P, P]),
     "vslam_ba_batch_dev": (I, [P, P, I, I, I, I, I]),
+    "vslam_set_window_ids": (I, [P, P, I]),
+    "vslam_ba_chain_dev": (I, [P, P, P, P, I, P]),
     "vslam_build_windows_dev": (I, [P, P, I, I, I, P, P]),
     "vslam_build_windows_kf_dev": (I, [P, P, I, I, D, I, I, P, P, P, P]),
     "vslam_build_windows_gated_dev": (I, [P, P, I, I, D, P, I, I, P, P, P, P, P]),
@@ -586,6 +588,20 @@ class VO:
 
     def ba_batch_dev(self, batch, schedule=1, mode=0, iters=10, update_poses=1, update_lms=0):
         self._chk(self.lib.vslam_ba_batch_dev(self.h, C.byref(batch), schedule, mode, iters, update_poses, update_lms), "vslam_ba_batch_dev")
+
+    def set_window_ids(self, d_lm_id, capacity=0):
+        """context state: while set, every build_windows*_dev entry also writes each landmark's identity (creating frame x kp_capacity + creating
+        keypoint) to d_lm_id (capacity int32, device).  None clears it.  Semantics in include/vslam_hip.h."""
+        if d_lm_id is None:
+            self._chk(self.lib.vslam_set_window_ids(self.h, None, 0), "vslam_set_window_ids")
+            return
+        self._chk(self.lib.vslam_set_window_ids(self.h, d_lm_id, capacity), "vslam_set_window_ids")
+
+    def ba_chain_dev(self, batch, d_lm_id, d_kf_frame=None, min_kf=None, d_ran=None):
+        """the BA schedule with the windows of every sequence run in order, each from the poses and is_inlier flags the previous one left; the
+        sequences of the segment table side by side.  d_kf_frame None: sliding windows; min_kf None: batch.n_kf.  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_ba_chain_dev(self.h, C.byref(batch), d_lm_id, d_kf_frame, batch.n_kf if min_kf is None else int(min_kf), d_ran),
+                  "vslam_ba_chain_dev")
 
     def build_windows_dev(self, tracks, n_kf, lm_capacity, edge_capacity, batch, d_status):
         """optimize_map's graph build on the device (optimization.cpp:127-214 + visual_odometry.cpp:363-424) for a batch of consecutive

@@ -236,7 +236,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
-           "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel";
+           "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -293,7 +293,7 @@ void vslam_destroy(vslam_ctx* ctx) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     orb_tables_free(&c->tab);
-    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc, &c->segbuf}) b->release();
+    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc, &c->segbuf, &c->chain}) b->release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
     void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad, c->orb.d_anms_path,
                     c->match.d_train_best, c->rect.d_map[0], c->rect.d_map[1], c->rect.d_tiles[0], c->rect.d_tiles[1]};
@@ -1220,6 +1220,80 @@ int vslam_ba_batch_dev(vslam_ctx* ctx, const vslam_ba_batch* b, int schedule, in
     return launch_lm_windows(a, schedule, mode, iters, update_poses, update_lms, &c->lm, c->stream);
 }
 
+// ---- landmark identities out of the window builders, and the chained BA on them (the contract: include/vslam_hip.h)
+static int seg_refuses(const Ctx* c, int n_frames, bool chunk);
+int vslam_set_window_ids(vslam_ctx* ctx, int32_t* d_lm_id, int capacity) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c) { set_error("null context"); return VSLAM_ERR_ARG; }
+    if (capacity < 0 || (capacity == 0) != (d_lm_id == nullptr)) { set_error("vslam_set_window_ids: a buffer with capacity >= 1, or NULL with 0 to clear it"); return VSLAM_ERR_ARG; }
+    c->ids = d_lm_id; c->ids_cap = capacity;
+    return VSLAM_OK;
+}
+
+int vslam_ba_chain_dev(vslam_ctx* ctx, const vslam_ba_batch* b, const int32_t* d_lm_id, const int32_t* d_kf_frame, int min_kf, int32_t* d_ran) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !b || b->n_windows <= 0 || !b->d_lm_off || !b->d_edge_off || !b->d_T_c_w || !b->d_xyz || !b->d_lm_inlier || !b->d_kf_idx ||
+        !b->d_lm_idx || !b->d_uv || b->total_lm <= 0 || b->total_edge <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!d_lm_id) { set_error("vslam_ba_chain_dev: d_lm_id is required (the landmark ids a window builder wrote, vslam_set_window_ids)"); return VSLAM_ERR_ARG; }
+    if (b->n_kf < 1 || b->n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", b->n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
+    if (min_kf < 1 || min_kf > b->n_kf) { set_error("vslam_ba_chain_dev: min_kf %d outside 1..n_kf (%d)", min_kf, b->n_kf); return VSLAM_ERR_ARG; }
+    if (int rc = seg_refuses(c, b->n_windows, false)) return rc;
+    VS_ENTER(c);
+    // the sequences: the segment table, or the whole batch.  The host knows their lengths, so the loop below never waits for the device.
+    const int n_win = b->n_windows, n_seg = c->seg.first ? c->seg.n_seg : 1;
+    int n_steps = 0;
+    std::vector<int> longer; // longer[j] = sequences with more than j frames = window slots of step j
+    {
+        std::vector<int> hist(n_win + 2, 0);
+        for (int s = 0; s < n_seg; ++s) { const int len = c->seg.first ? c->seg_first_h[s + 1] - c->seg_first_h[s] : n_win; hist[len]++; n_steps = std::max(n_steps, len); }
+        longer.assign(n_steps, 0);
+        for (int j = n_steps - 1, acc = 0; j >= 0; --j) { acc += hist[j + 1]; longer[j] = acc; }
+    }
+    const int kp_cap = std::max(c->p.kp_capacity, c->ids_kp_cap);
+    ChainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_windows = n_win; a.n_kf = b->n_kf; a.min_kf = min_kf; a.total_lm = b->total_lm; a.total_edge = b->total_edge;
+    a.lm_off = b->d_lm_off; a.edge_off = b->d_edge_off; a.n_kf_w = b->d_n_kf; a.T = b->d_T_c_w; a.xyz = b->d_xyz; a.reliable = b->d_reliable;
+    a.lm_inlier = b->d_lm_inlier; a.kf_idx = b->d_kf_idx; a.lm_idx = b->d_lm_idx; a.uv = b->d_uv; a.chi2 = b->d_chi2; a.stats = b->d_stats;
+    a.lm_id = d_lm_id; a.kf_frame = d_kf_frame; a.ran = d_ran; a.first = c->seg.first; a.n_seg = n_seg;
+    a.n_roots = (long long)n_win * kp_cap;
+    const size_t tl = (size_t)b->total_lm, te = (size_t)b->total_edge;
+    int32_t* head; size_t head_words = 0;
+    if (int rc = carve(c->chain, c->stream, [&](Layout& L) {
+            a.pose = L.take<double>((size_t)n_win * 7); a.pose_set = L.take<uint8_t>(n_win); a.bit = L.take<uint8_t>((size_t)a.n_roots); a.status = L.take<int32_t>(n_win);
+            const size_t h0 = L.off;
+            a.s_lm_off = L.take<int32_t>((size_t)n_seg + 1); a.s_edge_off = L.take<int32_t>((size_t)n_seg + 1); a.s_n_kf = L.take<int32_t>(n_seg); a.s_win = L.take<int32_t>(n_seg);
+            head = a.s_lm_off; head_words = (L.off - h0) / sizeof(int32_t);
+            a.s_T = L.take<double>((size_t)n_seg * b->n_kf * 7); a.s_xyz = L.take<float>(tl * 3); a.s_rel = L.take<uint8_t>(tl); a.s_inl = L.take<uint8_t>(tl);
+            a.s_kf = L.take<int32_t>(te); a.s_lm = L.take<int32_t>(te); a.s_uv = L.take<float>(te * 2);
+            a.s_chi2 = L.take<double>(b->d_chi2 ? te : 0); a.s_stats = L.take<vslam_lm_stats>(b->d_stats ? n_seg : 0);
+        })) return rc;
+    if (!b->d_reliable) a.s_rel = nullptr;
+    if (!b->d_chi2) a.s_chi2 = nullptr;
+    if (!b->d_stats) a.s_stats = nullptr;
+    VS_HIP(hipMemsetAsync(a.pose_set, 0, n_win, c->stream));
+    VS_HIP(hipMemsetAsync(a.bit, 1, (size_t)a.n_roots, c->stream)); // is_inlier = 1 until some window has written it
+    VS_HIP(hipMemsetAsync(a.status, 0, sizeof(int32_t) * n_win, c->stream));
+    VS_HIP(hipMemsetAsync(head, 0, sizeof(int32_t) * head_words, c->stream));
+    LmWindowArgs w;
+    memset(&w, 0, sizeof(w));
+    w.n_kf = b->n_kf; w.n_kf_w = a.s_n_kf; w.lm_off = a.s_lm_off; w.edge_off = a.s_edge_off; w.T = a.s_T; w.xyz = a.s_xyz; w.reliable = a.s_rel; w.lm_inlier = a.s_inl;
+    w.kf_idx = a.s_kf; w.lm_idx = a.s_lm; w.uv = a.s_uv; w.chi2 = a.s_chi2; w.stats = a.s_stats; w.chi2_thr = nullptr;
+    fill_K(c, w.K); w.huber_delta = c->p.huber_delta; w.total_lm = tl; w.total_edge = te;
+    if (b->K4) memcpy(w.K, b->K4, sizeof(w.K));
+    for (int j = 0; j < n_steps; ++j) {
+        const int n_slots = longer[j];
+        w.n_windows = n_slots;
+        if (int rc = launch_chain_stage(a, j, n_slots, c->stream)) return rc;
+        if (int rc = launch_lm_windows(w, 1, 0, 10, 1, 0, &c->lm, c->stream)) return rc; // (the schedule of vslam_ba_batch_dev(schedule = 1))
+        if (int rc = launch_chain_scatter(a, n_slots, c->lm.status, c->stream)) return rc;
+    }
+    // vslam_ba_status_dev: per window of the caller's batch, the status word of the step that ran it
+    c->lm.status = a.status; c->lm.status_n = n_win;
+    c->lm.passes = nullptr; c->lm.defer = nullptr; c->lm.defer_valid = false; // (the per-launch diagnostics describe single steps: not available after a chain)
+    return VSLAM_OK;
+}
+
 // ---- several independent sequences in one batch (the rules: include/vslam_hip.h)
 int vslam_set_segments(vslam_ctx* ctx, int n_seg, const int32_t* first) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
@@ -1232,15 +1306,16 @@ int vslam_set_segments(vslam_ctx* ctx, int n_seg, const int32_t* first) {
     }
     VS_ENTER(c);
     VS_HIP(hipStreamSynchronize(c->stream)); // (launches in flight may still read the old table)
-    if (n_seg == 0) { c->seg = SegView(); c->seg_frames = 0; return VSLAM_OK; }
+    if (n_seg == 0) { c->seg = SegView(); c->seg_frames = 0; c->seg_first_h.clear(); return VSLAM_OK; }
     const int n_frames = first[n_seg];
     int32_t *d_first, *d_start, *d_qitem;
-    c->seg = SegView(); c->seg_frames = 0; // (a failed upload leaves no half-written table in place)
+    c->seg = SegView(); c->seg_frames = 0; c->seg_first_h.clear(); // (a failed upload leaves no half-written table in place)
     if (int rc = carve(c->segbuf, c->stream, [&](Layout& L) { d_first = L.take<int32_t>((size_t)n_seg + 1); d_start = L.take<int32_t>(n_frames); d_qitem = L.take<int32_t>(n_frames); })) return rc;
     VS_HIP(hipMemcpyAsync(d_first, first, sizeof(int32_t) * ((size_t)n_seg + 1), hipMemcpyHostToDevice, c->stream));
     if (int rc = launch_seg_expand(n_frames, n_seg, d_first, d_start, d_qitem, c->stream)) return rc;
     VS_HIP(hipStreamSynchronize(c->stream)); // (`first` is the caller's again on return)
     c->seg.first = d_first; c->seg.start = d_start; c->seg.qitem = d_qitem; c->seg.n_seg = n_seg; c->seg_frames = n_frames;
+    c->seg_first_h.assign(first, first + n_seg + 1);
     return VSLAM_OK;
 }
 
@@ -1266,6 +1341,14 @@ static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, in
     }
     if (in->kp_capacity > 65536) { set_error("kp_capacity %d exceeds 65536 (the window builder packs a keypoint index into 16 bits)", in->kp_capacity); return VSLAM_ERR_ARG; }
     if (int rc = seg_refuses(c, in->n_frames, in->d_T_abs || in->d_carry_in || in->d_carry_out)) return rc;
+    KfPolicy kpi = kp;
+    if (c->ids) { // vslam_set_window_ids: the builder also writes every landmark's root
+        if (lm_capacity > c->ids_cap) { set_error("lm_capacity %d exceeds the window-id buffer's capacity %d (vslam_set_window_ids)", lm_capacity, c->ids_cap); return VSLAM_ERR_ARG; }
+        if (in->d_T_abs || in->d_carry_in || in->d_carry_out) {
+            set_error("window ids are set: chunk inputs (d_T_abs / d_carry_in / d_carry_out) are not available, a root from before the batch has no frame index"); return VSLAM_ERR_ARG;
+        }
+        kpi.lm_id = c->ids; c->ids_kp_cap = in->kp_capacity;
+    }
     VS_ENTER(c);
     out->n_windows = in->n_frames; out->n_kf = n_kf; out->total_lm = lm_capacity; out->total_edge = edge_capacity;
     double K4[4];
@@ -1273,7 +1356,7 @@ static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, in
     const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
     return launch_build_windows(*in, n_kf, lm_capacity, edge_capacity, K4, c->p.pnp_reproj_thr, track_rule, c->track, const_cast<int32_t*>(out->d_lm_off), const_cast<int32_t*>(out->d_edge_off),
                                 const_cast<int32_t*>(out->d_n_kf), out->d_T_c_w, out->d_xyz, const_cast<uint8_t*>(out->d_reliable), out->d_lm_inlier,
-                                const_cast<int32_t*>(out->d_kf_idx), const_cast<int32_t*>(out->d_lm_idx), const_cast<float*>(out->d_uv), d_status, kp, c->stream, c->seg);
+                                const_cast<int32_t*>(out->d_kf_idx), const_cast<int32_t*>(out->d_lm_idx), const_cast<float*>(out->d_uv), d_status, kpi, c->stream, c->seg);
 }
 
 int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_status) {

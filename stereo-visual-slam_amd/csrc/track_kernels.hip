@@ -651,7 +651,8 @@ __device__ inline int window_set_head_len(int r, const int2* __restrict__ ends, 
 // A window's keyframes: the sliding window [s, b], or the culled set of kf_frame (kSet).  Loaded into the workgroup's LDS.  nmem (gated sets
 // only, else nullptr): the member count of every window, 0 for the empty window of a non-keyframe step; without it every set holds
 // min(b + 1, n_kf) frames.
-struct WindowSet { const int32_t* kf_frame; const int2* ends; const int32_t* root; const int32_t* nmem; const int32_t* nxt = nullptr; }; // nxt: see track_walk_kernel
+struct WindowSet { const int32_t* kf_frame; const int2* ends; const int32_t* root; const int32_t* nmem; const int32_t* nxt = nullptr; // nxt: see track_walk_kernel
+                   int32_t* lm_id = nullptr; }; // lm_id: vslam_set_window_ids (window_emit_kernel writes every landmark's root there)
 template <bool kSet>
 __device__ inline int window_frames(const TrackDims& d, const WindowSet& ws, int b, int* s_kf) {
     const int s = window_first(d, b), nk = kSet && ws.nmem ? ws.nmem[b] : b - s + 1;
@@ -867,6 +868,7 @@ __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vsl
     float* o = xyz_out + 3 * (size_t)g;
     o[0] = pos[0]; o[1] = pos[1]; o[2] = pos[2];
     rel_out[g] = has_rel; inl_out[g] = 1;
+    if (ws.lm_id) ws.lm_id[g] = root[last]; // the landmark's identity across windows: its creating frame x kp_cap + its creating keypoint
 }
 
 int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
@@ -900,7 +902,7 @@ int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, i
             }
         })) return rc;
     WindowSet ws = {kp.kf_frame, ends, root, nmem};
-    ws.nxt = nxt;
+    ws.nxt = nxt; ws.lm_id = kp.lm_id;
     TrackCam cam;
     cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
     int32_t* cand = info; // (the candidate words live in the info table until track_info_kernel writes it)

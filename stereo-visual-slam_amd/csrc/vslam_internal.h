@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/vslam_hip.h"
 
 namespace vslam {
@@ -327,7 +329,9 @@ struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evic
                   const double* G = nullptr; const int32_t* in_of_match = nullptr; const int32_t* state_in = nullptr;
                   // recover (vslam_build_windows_map_recover_dev; with gate, G, state_in): the states also give the pairing of every frame with its last
                   // accepted predecessor; pred_table (n_frames) is the pairing in.d_f2f was built on -- a pair's links hold only where the two agree
-                  bool recover = false; const int32_t* pred_table = nullptr; };
+                  bool recover = false; const int32_t* pred_table = nullptr;
+                  // vslam_set_window_ids: per landmark of the concatenated array, the root node of its track (frame x kp_capacity + keypoint); null: not written
+                  int32_t* lm_id = nullptr; };
 // The segment table of a context as the launchers see it (vslam_set_segments; all null / 0: the batch is one sequence): start[f] = first frame of
 // f's segment (n_frames), first (n_seg + 1), qitem[i] = i, or -1 for the item before a segment's first frame (n_frames - 1).
 struct SegView { const int32_t* start = nullptr; const int32_t* first = nullptr; const int32_t* qitem = nullptr; int n_seg = 0; };
@@ -355,6 +359,25 @@ struct MapRequery { const uint8_t* d_desc; size_t desc_stride; int32_t* d_feat; 
 int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
                           double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
                           int out_capacity, int32_t* d_status, hipStream_t stream, const SegView& seg, const MapRequery* rq = nullptr, const MapRecover* rv = nullptr);
+
+// chain_kernels.hip: the chained BA of vslam_ba_chain_dev.  Step j stages the j-th window of every sequence that has one into a batch of its own
+// (offsets, then gather with the carried poses and flags substituted), the schedule runs on it, and scatter takes the results back to the caller's
+// arrays and into the chain state.  Every index read from a caller's array is range-checked before it addresses memory.
+struct ChainArgs {
+    int n_windows, n_kf, min_kf; long long total_lm, total_edge;   // the caller's batch
+    const int32_t* lm_off; const int32_t* edge_off; const int32_t* n_kf_w; // (n_kf_w null: every window holds n_kf keyframes)
+    double* T; const float* xyz; const uint8_t* reliable; uint8_t* lm_inlier; const int32_t* kf_idx; const int32_t* lm_idx; const float* uv;
+    double* chi2; vslam_lm_stats* stats;                             // (null: not wanted)
+    const int32_t* lm_id; const int32_t* kf_frame; int32_t* ran;     // (kf_frame null: the sliding window; ran null: not wanted)
+    const int32_t* first; int n_seg;                                 // the segment table (first null: one sequence, n_seg = 1)
+    // chain state: pose per frame (x 7) with its "some window left one" byte, the is_inlier byte per root, the status word per caller window
+    double* pose; uint8_t* pose_set; uint8_t* bit; long long n_roots; int32_t* status;
+    // the staging batch of one step (at most n_seg windows; landmark / edge arrays sized by the caller's totals) and slot -> caller window
+    int32_t* s_lm_off; int32_t* s_edge_off; int32_t* s_n_kf; int32_t* s_win;
+    double* s_T; float* s_xyz; uint8_t* s_rel; uint8_t* s_inl; int32_t* s_kf; int32_t* s_lm; float* s_uv; double* s_chi2; vslam_lm_stats* s_stats;
+};
+int launch_chain_stage(const ChainArgs& a, int step, int n_slots, hipStream_t stream);
+int launch_chain_scatter(const ChainArgs& a, int n_slots, const int32_t* step_status, hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- rectification
 // rectify_kernels.hip: the map builder (host, double, once per rig), the device entry format and the gather kernel
@@ -396,6 +419,10 @@ struct Ctx {
     DevBuf segbuf{"segment table", &dev_bytes}; // vslam_set_segments: first, start, qitem
     SegView seg;          // ... as the launchers take it (all null: no table)
     int seg_frames;       // first[n_seg] of the table in place (0: none)
+    std::vector<int32_t> seg_first_h; // ... and its `first` on the host (vslam_ba_chain_dev walks the sequences step by step)
+    int32_t* ids; int ids_cap;  // vslam_set_window_ids: the caller's landmark-id buffer the window builders also fill (null: none)
+    int ids_kp_cap;       // kp_capacity of the most recent builder call that wrote ids (the stride of the ids' frame index)
+    DevBuf chain{"chain scratch", &dev_bytes};   // state and staging batch of vslam_ba_chain_dev
     bool orb_ok;          // img_w, img_h >= 64: the ORB entry points serve this context (a smaller one is a rectification target only)
 };
 

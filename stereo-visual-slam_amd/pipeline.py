@@ -27,7 +27,7 @@ class KeyframePipeline:
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
                  lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
                  keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all", sgbm_params=None, rejected_frames="pass_through",
-                 rectify=None, raw_images=None, segments=None, segment_sequences=None):
+                 rectify=None, raw_images=None, segments=None, segment_sequences=None, ba_chain=False, ba_chain_min_kf=None):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
         sgbm_params (depth="sgbm"): the StereoSGBM set of the batched disparity call -- an SgbmParams, a dict of its fields or a tuple
@@ -71,7 +71,11 @@ class KeyframePipeline:
         that of KeyframePipeline(B=n_s, sequence=segment_sequences[s]) with the same options.  Segment s shows the frames that pipeline shows;
         segment_sequences = None renders them with seed + 7919 s (PipelineRing's convention).  pose_passes = K gives the sequential loop for frames
         0..K of EVERY segment, so K = max(n_s) - 1 is exact for the whole batch.  Frame indices in download() stay batch-wide; download() adds
-        seg_first, trajectories() returns one trajectory per segment."""
+        seg_first, trajectories() returns one trajectory per segment.
+        ba_chain (ba_windows="tracks", no frame_range): the windows of a sequence run in order, each from the poses and is_inlier flags the previous one
+        left (vslam_ba_chain_dev: the reference's carried flags, optimization.cpp:160, and successive schedules, :272-278); the segments run side by side.
+        ba_chain_min_kf: the BA runs on windows with at least that many keyframes (None = n_kf: run_vslam.cpp:58's keyframes_.size() >= 10; 1 = every
+        non-empty window); a smaller window passes the carried state through.  download() adds ba_lm_id (the landmarks' identities) and ba_ran."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
         assert keyframe_gate in (False, True, "per_pass"), "keyframe_gate: False, True (on stage A's inputs) or 'per_pass' (inside the map passes)"
@@ -98,6 +102,13 @@ class KeyframePipeline:
             self.seg_first = np.concatenate([[0], np.cumsum(segments)]).astype(np.int32)
         else:
             assert segment_sequences is None, "segment_sequences needs segments"
+        self.ba_chain = bool(ba_chain)
+        if self.ba_chain:
+            assert with_ba and ba_windows == "tracks" and frame_range is None, "ba_chain needs ba_windows='tracks' and no frame_range"
+            self.ba_chain_min_kf = n_kf if ba_chain_min_kf is None else int(ba_chain_min_kf)
+            assert 1 <= self.ba_chain_min_kf <= n_kf, "ba_chain_min_kf: 1..n_kf"
+        else:
+            assert ba_chain_min_kf is None, "ba_chain_min_kf needs ba_chain"
         self.f2f_queries = f2f_queries
         self.rejected_frames = rejected_frames
         self.pose_inputs, self.pose_passes = pose_inputs, int(pose_passes)
@@ -236,6 +247,9 @@ class KeyframePipeline:
                 self.ba_evicted = torch.zeros(B, dtype=torch.int32, device=d)
             if keyframe_gate:   # (per_pass: the latest pass's states, updated in place pass by pass)
                 self.ba_frame_state = torch.zeros(B, dtype=torch.int32, device=d)
+            if self.ba_chain:   # the landmarks' identities (written by the builder) and which windows the chain ran
+                self.ba_lm_id = torch.zeros(self.lm_capacity, dtype=torch.int32, device=d)
+                self.ba_ran = torch.zeros(B, dtype=torch.int32, device=d)
             tr = TracksIn()
             tr.n_frames = B; tr.kp_capacity = self.cap; tr.lr_capacity = self.cap; tr.match_capacity = self.cap; tr.pnp_capacity = self.cap
             tr.d_kps = self.d_kps.data_ptr(); tr.d_lr = self.d_lr.data_ptr(); tr.d_nlr = self.d_nlr.data_ptr(); tr.d_xyz = self.d_xyz.data_ptr()
@@ -279,6 +293,8 @@ class KeyframePipeline:
             bb.total_lm = self.lm_capacity; bb.total_edge = self.edge_capacity
             self.ba_batch = bb
             self.unique_windows = B
+            if self.ba_chain:   # context state, like the segment table: every builder of this context writes the ids from here on
+                self.vo.set_window_ids(self.ba_lm_id.data_ptr(), self.lm_capacity)
             if self.seg_first is not None:   # the table is context state: every consecutive-frame entry of this context honours it from here on
                 self.vo.set_segments(self.seg_first)
                 ft = torch.from_numpy(self.seg_first.astype(np.int64)).to(d)
@@ -529,12 +545,21 @@ class KeyframePipeline:
             return
         if self.ba_windows == "tracks":
             self.stage_build_windows()
-            self.vo.ba_batch_dev(self.ba_batch, schedule=1)
+            if self.ba_chain:
+                self.vo.ba_chain_dev(self.ba_batch, self.ba_lm_id.data_ptr(), self._chain_kf_frame(), self.ba_chain_min_kf, self.ba_ran.data_ptr())
+            else:
+                self.vo.ba_batch_dev(self.ba_batch, schedule=1)
             return
         with torch.cuda.stream(self.stream):
             self.ba_T.copy_(self.ba_T0)
             self.ba_inl.fill_(1)
         self.vo.ba_batch_dev(self.ba_batch, schedule=1)
+
+    def _chain_kf_frame(self):
+        """the keyframe sets the last builder call wrote (None: it was the plain sliding builder, which writes none)"""
+        if self.window_policy == "reference" or self.keyframe_gate or self.pose_inputs == "map":
+            return self.ba_kf_frame.data_ptr()
+        return None
 
     def step(self):
         if self.rectify is not None:
@@ -569,6 +594,8 @@ class KeyframePipeline:
                 out["ba_kf_frame"], out["ba_evicted"] = self._sliding_keyframes()
             if self.seg_first is not None:
                 out["seg_first"] = self.seg_first.copy()
+            if self.ba_chain:
+                out["ba_lm_id"] = self.ba_lm_id.cpu().numpy(); out["ba_ran"] = self.ba_ran.cpu().numpy()
             if self.keyframe_gate:   # (per_pass: the last pass's states; frame_state_prev: the states that pass started from)
                 out["frame_state"] = self.ba_frame_state.cpu().numpy()
                 if self.keyframe_gate == "per_pass":
