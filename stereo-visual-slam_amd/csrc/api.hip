@@ -1117,6 +1117,22 @@ int vslam_pnp_ransac_models(vslam_ctx* ctx, const float* xyz_w, const float* uv,
 }
 
 // ---------------------------------------------------------------------------------------------- window optimisation
+// the arrays every entry that optimises a vslam_ba_batch needs
+static bool ba_batch_ok(const vslam_ba_batch* b) {
+    return b && b->n_windows > 0 && b->d_lm_off && b->d_edge_off && b->d_T_c_w && b->d_xyz && b->d_lm_inlier && b->d_kf_idx && b->d_lm_idx && b->d_uv && b->total_lm > 0 &&
+           b->total_edge > 0;
+}
+// the kernels' view of a batch: its arrays and totals, the context's intrinsics unless the batch brings its own K4, the context's Huber delta
+static LmWindowArgs lm_args_of(const Ctx* c, const vslam_ba_batch& b) {
+    LmWindowArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_windows = b.n_windows; a.n_kf = b.n_kf; a.n_kf_w = b.d_n_kf; a.lm_off = b.d_lm_off; a.edge_off = b.d_edge_off; a.T = b.d_T_c_w; a.xyz = b.d_xyz;
+    a.reliable = b.d_reliable; a.lm_inlier = b.d_lm_inlier; a.kf_idx = b.d_kf_idx; a.lm_idx = b.d_lm_idx; a.uv = b.d_uv; a.chi2 = b.d_chi2; a.stats = b.d_stats;
+    fill_K(c, a.K); a.huber_delta = c->p.huber_delta; a.total_lm = b.total_lm; a.total_edge = b.total_edge;
+    if (b.K4) memcpy(a.K, b.K4, sizeof(a.K));
+    return a;
+}
+
 // Shared host wrapper of optimize_map / optimize_pose_only: stable-sorts the caller's edges by landmark (the
 // kernel's CSR contract), runs one pass on the GPU, un-permutes chi2 and applies the chi2 classification of
 // optimization.cpp:224-266 on the host with the caller's flag_lm (quirk Q1 lives in the caller's edge list).
@@ -1157,12 +1173,9 @@ static int window_host(vslam_ctx* ctx, int mode, int n_kf, double* T_c_w, int n_
     VS_HIP(hipMemcpyAsync(d_off, off, sizeof(off), hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(d_st, 0, sizeof(vslam_lm_stats), c->stream));
     VS_HIP(hipMemsetAsync(d_chi, 0, 8 * (size_t)n_edge, c->stream));
-    LmWindowArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_windows = 1; a.n_kf = n_kf; a.lm_off = d_off; a.edge_off = d_off + 2; a.T = d_T; a.xyz = d_xyz; a.reliable = nullptr;
-    a.lm_inlier = d_inl; a.kf_idx = d_kf; a.lm_idx = d_lm; a.uv = d_uv; a.chi2 = d_chi; a.stats = d_st; a.chi2_thr = d_thr;
-    fill_K(c, a.K); a.huber_delta = c->p.huber_delta; a.total_lm = n_lm; a.total_edge = n_edge;
-    if (K4) memcpy(a.K, K4, sizeof(a.K)); // the caller's `const cv::Mat& K` (optimization.hpp:137-139)
+    const vslam_ba_batch b = {1, n_kf, d_off, d_off + 2, d_T, d_xyz, nullptr, d_inl, d_kf, d_lm, d_uv, d_chi, d_st, n_lm, n_edge, K4, nullptr}; // (K4: the caller's `const cv::Mat& K`, optimization.hpp:137-139)
+    LmWindowArgs a = lm_args_of(c, b);
+    a.chi2_thr = d_thr;
     if ((rc = launch_lm_windows(a, 0, mode, iters, update_poses, update_lms, &c->lm, c->stream))) return rc;
     int32_t status = 0;
     if ((rc = lm_fetch_status(&c->lm, 1, &status, c->stream))) return rc;
@@ -1207,21 +1220,20 @@ int vslam_pose_only_window(vslam_ctx* ctx, int n_kf, double* T_c_w, int n_lm, co
 
 int vslam_ba_batch_dev(vslam_ctx* ctx, const vslam_ba_batch* b, int schedule, int mode, int iters, int update_poses, int update_lms) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !b || b->n_windows <= 0 || !b->d_lm_off || !b->d_edge_off || !b->d_T_c_w || !b->d_xyz || !b->d_lm_inlier || !b->d_kf_idx ||
-        !b->d_lm_idx || !b->d_uv || b->total_lm <= 0 || b->total_edge <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!c || !ba_batch_ok(b)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    LmWindowArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_windows = b->n_windows; a.n_kf = b->n_kf; a.n_kf_w = b->d_n_kf; a.lm_off = b->d_lm_off; a.edge_off = b->d_edge_off; a.T = b->d_T_c_w; a.xyz = b->d_xyz;
-    a.reliable = b->d_reliable; a.lm_inlier = b->d_lm_inlier; a.kf_idx = b->d_kf_idx; a.lm_idx = b->d_lm_idx; a.uv = b->d_uv;
-    a.chi2 = b->d_chi2; a.stats = b->d_stats; a.chi2_thr = nullptr;
-    fill_K(c, a.K); a.huber_delta = c->p.huber_delta; a.total_lm = b->total_lm; a.total_edge = b->total_edge;
-    if (b->K4) memcpy(a.K, b->K4, sizeof(a.K));
-    return launch_lm_windows(a, schedule, mode, iters, update_poses, update_lms, &c->lm, c->stream);
+    return launch_lm_windows(lm_args_of(c, *b), schedule, mode, iters, update_poses, update_lms, &c->lm, c->stream);
+}
+
+// a table is in place: the call must cover exactly its frames, and a chunk of a longer sequence (sequence mode across ranks) stays single-sequence
+static int seg_refuses(const Ctx* c, int n_frames, bool chunk) {
+    if (!c->seg.first) return VSLAM_OK;
+    if (n_frames != c->seg_frames) { set_error("the segment table covers %d frames, this call has %d (vslam_set_segments(ctx, 0, NULL) clears the table)", c->seg_frames, n_frames); return VSLAM_ERR_ARG; }
+    if (chunk) { set_error("a segment table is set: chunk inputs (d_T_abs / d_carry_in / d_carry_out) are not available, sequence mode across ranks is single-sequence"); return VSLAM_ERR_ARG; }
+    return VSLAM_OK;
 }
 
 // ---- landmark identities out of the window builders, and the chained BA on them (the contract: include/vslam_hip.h)
-static int seg_refuses(const Ctx* c, int n_frames, bool chunk);
 int vslam_set_window_ids(vslam_ctx* ctx, int32_t* d_lm_id, int capacity) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c) { set_error("null context"); return VSLAM_ERR_ARG; }
@@ -1232,8 +1244,7 @@ int vslam_set_window_ids(vslam_ctx* ctx, int32_t* d_lm_id, int capacity) {
 
 int vslam_ba_chain_dev(vslam_ctx* ctx, const vslam_ba_batch* b, const int32_t* d_lm_id, const int32_t* d_kf_frame, int min_kf, int32_t* d_ran) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !b || b->n_windows <= 0 || !b->d_lm_off || !b->d_edge_off || !b->d_T_c_w || !b->d_xyz || !b->d_lm_inlier || !b->d_kf_idx ||
-        !b->d_lm_idx || !b->d_uv || b->total_lm <= 0 || b->total_edge <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!c || !ba_batch_ok(b)) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (!d_lm_id) { set_error("vslam_ba_chain_dev: d_lm_id is required (the landmark ids a window builder wrote, vslam_set_window_ids)"); return VSLAM_ERR_ARG; }
     if (b->n_kf < 1 || b->n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", b->n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
     if (min_kf < 1 || min_kf > b->n_kf) { set_error("vslam_ba_chain_dev: min_kf %d outside 1..n_kf (%d)", min_kf, b->n_kf); return VSLAM_ERR_ARG; }
@@ -1275,12 +1286,9 @@ int vslam_ba_chain_dev(vslam_ctx* ctx, const vslam_ba_batch* b, const int32_t* d
     VS_HIP(hipMemsetAsync(a.bit, 1, (size_t)a.n_roots, c->stream)); // is_inlier = 1 until some window has written it
     VS_HIP(hipMemsetAsync(a.status, 0, sizeof(int32_t) * n_win, c->stream));
     VS_HIP(hipMemsetAsync(head, 0, sizeof(int32_t) * head_words, c->stream));
-    LmWindowArgs w;
-    memset(&w, 0, sizeof(w));
-    w.n_kf = b->n_kf; w.n_kf_w = a.s_n_kf; w.lm_off = a.s_lm_off; w.edge_off = a.s_edge_off; w.T = a.s_T; w.xyz = a.s_xyz; w.reliable = a.s_rel; w.lm_inlier = a.s_inl;
-    w.kf_idx = a.s_kf; w.lm_idx = a.s_lm; w.uv = a.s_uv; w.chi2 = a.s_chi2; w.stats = a.s_stats; w.chi2_thr = nullptr;
-    fill_K(c, w.K); w.huber_delta = c->p.huber_delta; w.total_lm = tl; w.total_edge = te;
-    if (b->K4) memcpy(w.K, b->K4, sizeof(w.K));
+    const vslam_ba_batch staged = {0, b->n_kf, a.s_lm_off, a.s_edge_off, a.s_T, a.s_xyz, a.s_rel, a.s_inl, a.s_kf, a.s_lm, a.s_uv, a.s_chi2, a.s_stats, b->total_lm, b->total_edge,
+                                   b->K4, a.s_n_kf}; // (n_windows: per step, below)
+    LmWindowArgs w = lm_args_of(c, staged);
     for (int j = 0; j < n_steps; ++j) {
         const int n_slots = longer[j];
         w.n_windows = n_slots;
@@ -1319,11 +1327,25 @@ int vslam_set_segments(vslam_ctx* ctx, int n_seg, const int32_t* first) {
     return VSLAM_OK;
 }
 
-// a table is in place: the call must cover exactly its frames, and a chunk of a longer sequence (sequence mode across ranks) stays single-sequence
-static int seg_refuses(const Ctx* c, int n_frames, bool chunk) {
-    if (!c->seg.first) return VSLAM_OK;
-    if (n_frames != c->seg_frames) { set_error("the segment table covers %d frames, this call has %d (vslam_set_segments(ctx, 0, NULL) clears the table)", c->seg_frames, n_frames); return VSLAM_ERR_ARG; }
-    if (chunk) { set_error("a segment table is set: chunk inputs (d_T_abs / d_carry_in / d_carry_out) are not available, sequence mode across ranks is single-sequence"); return VSLAM_ERR_ARG; }
+// what the builders' walk takes from the context (the default track_rule is resolved here)
+static TrackParams track_params_of(const Ctx* c) {
+    TrackParams tp;
+    fill_K(c, tp.K4); tp.reproj_thr = c->p.pnp_reproj_thr; tp.track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
+    return tp;
+}
+
+// a chunk of a longer sequence (sequence mode across ranks), and the refusal of the entries that need the whole history; who: "<the entry's mode> need(s)"
+static bool is_chunk(const vslam_tracks_in* in) { return in->d_T_abs || in->d_carry_in || in->d_carry_out; }
+static int chunk_refused(const char* who) {
+    set_error("%s the whole history: not available on a chunk (d_T_abs / d_carry_in / d_carry_out set)", who); return VSLAM_ERR_ARG;
+}
+
+// the keyframe-policy arguments of the five entries that write the keyframe sets; policy0: the entry's own name for policy 0.  Every such entry checks
+// in this order: its required pointers, what only it needs (d_num_inliers / d_pred / map_refuses), this, its chunk refusal, then build_windows' own
+static int kf_policy_refuses(int policy, const char* policy0, int n_kf, double near_dist) {
+    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 %s, 1 reference culling)", policy, policy0); return VSLAM_ERR_ARG; }
+    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
+    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
     return VSLAM_OK;
 }
 
@@ -1340,23 +1362,18 @@ static int build_windows(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, in
         if (in->d_carry_out || in->carry_out_frame != 0) { set_error("carry_out_frame %d needs d_carry_out and 1 <= carry_out_frame < n_frames (%d)", in->carry_out_frame, in->n_frames); return VSLAM_ERR_ARG; }
     }
     if (in->kp_capacity > 65536) { set_error("kp_capacity %d exceeds 65536 (the window builder packs a keypoint index into 16 bits)", in->kp_capacity); return VSLAM_ERR_ARG; }
-    if (int rc = seg_refuses(c, in->n_frames, in->d_T_abs || in->d_carry_in || in->d_carry_out)) return rc;
+    if (int rc = seg_refuses(c, in->n_frames, is_chunk(in))) return rc;
     KfPolicy kpi = kp;
     if (c->ids) { // vslam_set_window_ids: the builder also writes every landmark's root
         if (lm_capacity > c->ids_cap) { set_error("lm_capacity %d exceeds the window-id buffer's capacity %d (vslam_set_window_ids)", lm_capacity, c->ids_cap); return VSLAM_ERR_ARG; }
-        if (in->d_T_abs || in->d_carry_in || in->d_carry_out) {
+        if (is_chunk(in)) {
             set_error("window ids are set: chunk inputs (d_T_abs / d_carry_in / d_carry_out) are not available, a root from before the batch has no frame index"); return VSLAM_ERR_ARG;
         }
         kpi.lm_id = c->ids; c->ids_kp_cap = in->kp_capacity;
     }
     VS_ENTER(c);
     out->n_windows = in->n_frames; out->n_kf = n_kf; out->total_lm = lm_capacity; out->total_edge = edge_capacity;
-    double K4[4];
-    fill_K(c, K4);
-    const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
-    return launch_build_windows(*in, n_kf, lm_capacity, edge_capacity, K4, c->p.pnp_reproj_thr, track_rule, c->track, const_cast<int32_t*>(out->d_lm_off), const_cast<int32_t*>(out->d_edge_off),
-                                const_cast<int32_t*>(out->d_n_kf), out->d_T_c_w, out->d_xyz, const_cast<uint8_t*>(out->d_reliable), out->d_lm_inlier,
-                                const_cast<int32_t*>(out->d_kf_idx), const_cast<int32_t*>(out->d_lm_idx), const_cast<float*>(out->d_uv), d_status, kpi, c->stream, c->seg);
+    return launch_build_windows(*in, *out, d_status, track_params_of(c), kpi, c->track, c->stream, c->seg);
 }
 
 int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int lm_capacity, int edge_capacity, vslam_ba_batch* out, int32_t* d_status) {
@@ -1367,12 +1384,8 @@ int vslam_build_windows_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf,
 int vslam_build_windows_kf_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int n_kf, int policy, double near_dist, int lm_capacity, int edge_capacity,
                                vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status) {
     if (!ctx || !in || !d_kf_frame || !d_evicted) { set_error("bad argument"); return VSLAM_ERR_ARG; }
-    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 sliding, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
-    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
-    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
-    if (policy == 1 && (in->d_T_abs || in->d_carry_in || in->d_carry_out)) {
-        set_error("keyframe culling needs the whole history: not available on a chunk (d_T_abs / d_carry_in / d_carry_out set)"); return VSLAM_ERR_ARG;
-    }
+    if (int rc = kf_policy_refuses(policy, "sliding", n_kf, near_dist)) return rc;
+    if (policy == 1 && is_chunk(in)) return chunk_refused("keyframe culling needs");
     const KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
 }
@@ -1382,12 +1395,8 @@ int vslam_build_windows_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, int
                                   int32_t* d_status) {
     if (!ctx || !in || !d_kf_frame || !d_evicted || !d_frame_state) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (in->n_frames > 1 && !d_num_inliers) { set_error("the keyframe gate needs d_num_inliers (n_frames - 1 pose-stage inlier counts)"); return VSLAM_ERR_ARG; }
-    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 oldest evicted, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
-    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
-    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
-    if (in->d_T_abs || in->d_carry_in || in->d_carry_out) {
-        set_error("the keyframe gate needs the whole history: not available on a chunk (d_T_abs / d_carry_in / d_carry_out set)"); return VSLAM_ERR_ARG;
-    }
+    if (int rc = kf_policy_refuses(policy, "oldest evicted", n_kf, near_dist)) return rc;
+    if (is_chunk(in)) return chunk_refused("the keyframe gate needs");
     KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
     kp.gate = true; kp.num_inliers = d_num_inliers; kp.frame_state = d_frame_state;
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
@@ -1403,9 +1412,7 @@ int vslam_chain_poses_dev(vslam_ctx* ctx, int n_frames, const double* d_T_rel, d
 
 // the refinement passes (vslam_build_map_pnp_inputs_dev, vslam_build_windows_map_dev): poses from the caller, so no chunk and no NULL pose table
 static int map_refuses(const vslam_tracks_in* in, const double* d_T_c_w) {
-    if (in->d_T_abs || in->d_carry_in || in->d_carry_out || in->carry_out_frame != 0) {
-        set_error("the map pose inputs need the whole history: not available on a chunk (d_T_abs / d_carry_in / d_carry_out set)"); return VSLAM_ERR_ARG;
-    }
+    if (is_chunk(in) || in->carry_out_frame != 0) return chunk_refused("the map pose inputs need");
     if (!d_T_c_w) { set_error("d_T_c_w (n_frames x 7 absolute poses) is required"); return VSLAM_ERR_ARG; }
     return VSLAM_OK;
 }
@@ -1439,11 +1446,11 @@ int vslam_gate_states_pairs_dev(vslam_ctx* ctx, int n_frames, const double* d_T_
 // d_frame_state: null for the ungated entry, required by the gated ones; rq: the re-match of the requery entry (its scratch is filled in here), else null;
 // rv: the pairing of the recover entry (with rq), else null
 static int map_pnp_inputs(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, const int32_t* d_frame_state,
-                          float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status, MapRequery* rq = nullptr, const MapRecover* rv = nullptr) {
+                          const MapInputsOut& out, MapRequery* rq, const MapRecover* rv) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !in) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (int rc = map_refuses(in, d_T_c_w)) return rc;
-    if (out_capacity < 1 || !d_xyz_w || !d_uv || !d_n || !d_input_of_match || !d_status || in->n_frames <= 0 || in->kp_capacity <= 0 ||
+    if (out.capacity < 1 || !out.xyz || !out.uv || !out.n || !out.in_of_match || !out.status || in->n_frames <= 0 || in->kp_capacity <= 0 ||
         in->lr_capacity <= 0 || in->match_capacity <= 0 || in->pnp_capacity <= 0 || !in->d_kps || !in->d_lr || !in->d_nlr || !in->d_xyz || !in->d_valid ||
         !in->d_reliable || (in->n_frames > 1 && (!in->d_f2f || !in->d_nf2f || !in->d_pose_inlier))) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if ((long long)in->n_frames * in->kp_capacity > 0x7FFFFFFFll) { set_error("n_frames x kp_capacity exceeds the 31-bit node keys"); return VSLAM_ERR_ARG; }
@@ -1466,23 +1473,19 @@ static int map_pnp_inputs(vslam_ctx* ctx, const vslam_tracks_in* in, const doubl
     }
     if (int rc = seg_refuses(c, in->n_frames, false)) return rc; // (map_refuses above turned every chunk away)
     VS_ENTER(c);
-    double K4[4];
-    fill_K(c, K4);
-    const int track_rule = c->tune.track_rule >= 0 ? c->tune.track_rule : 1;
-    return launch_map_pnp_inputs(*in, d_T_c_w, d_input_of_match_prev, d_frame_state, K4, c->p.pnp_reproj_thr, track_rule, c->track, d_xyz_w, d_uv, d_n,
-                                 d_input_of_match, out_capacity, d_status, c->stream, c->seg, rq, rv);
+    return launch_map_pnp_inputs(*in, d_T_c_w, d_input_of_match_prev, d_frame_state, track_params_of(c), out, rq, rv, c->track, c->stream, c->seg);
 }
 
 int vslam_build_map_pnp_inputs_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev, float* d_xyz_w,
                                    float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity, int32_t* d_status) {
-    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, nullptr, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status);
+    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, nullptr, {d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status}, nullptr, nullptr);
 }
 
 int vslam_build_map_pnp_inputs_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
                                          const int32_t* d_frame_state, float* d_xyz_w, float* d_uv, int32_t* d_n, int32_t* d_input_of_match, int out_capacity,
                                          int32_t* d_status) {
     if (!d_frame_state) { set_error("the gated walk needs d_frame_state (n_frames states of the previous pass)"); return VSLAM_ERR_ARG; }
-    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status);
+    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, {d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status}, nullptr, nullptr);
 }
 
 int vslam_build_map_pnp_inputs_requery_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
@@ -1491,7 +1494,7 @@ int vslam_build_map_pnp_inputs_requery_dev(vslam_ctx* ctx, const vslam_tracks_in
                                            int out_capacity, int32_t* d_status) {
     if (!d_frame_state) { set_error("the gated walk needs d_frame_state (n_frames states of the previous pass)"); return VSLAM_ERR_ARG; }
     MapRequery rq = {d_desc, desc_stride_bytes, d_feat, d_nfeat, d_f2f_out, d_nf2f_out, 0.0, 0.0, nullptr};
-    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status, &rq);
+    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, {d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status}, &rq, nullptr);
 }
 
 int vslam_build_map_pnp_inputs_recover_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match_prev,
@@ -1502,7 +1505,7 @@ int vslam_build_map_pnp_inputs_recover_dev(vslam_ctx* ctx, const vslam_tracks_in
     if (!d_pred || !d_gap) { set_error("the recover entry writes the pairing: d_pred (n_frames) and d_gap (n_frames - 1) are required"); return VSLAM_ERR_ARG; }
     MapRequery rq = {d_desc, desc_stride_bytes, d_feat, d_nfeat, d_f2f_out, d_nf2f_out, 0.0, 0.0, nullptr};
     const MapRecover rv = {d_pred_prev, d_pred, d_gap};
-    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status, &rq, &rv);
+    return map_pnp_inputs(ctx, in, d_T_c_w, d_input_of_match_prev, d_frame_state, {d_xyz_w, d_uv, d_n, d_input_of_match, out_capacity, d_status}, &rq, &rv);
 }
 
 int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const double* d_T_c_w, const int32_t* d_input_of_match, int n_kf, int policy,
@@ -1510,9 +1513,7 @@ int vslam_build_windows_map_dev(vslam_ctx* ctx, const vslam_tracks_in* in, const
                                 int32_t* d_status) {
     if (!ctx || !in || !d_kf_frame || !d_evicted) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (int rc = map_refuses(in, d_T_c_w)) return rc;
-    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 sliding, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
-    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
-    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
+    if (int rc = kf_policy_refuses(policy, "sliding", n_kf, near_dist)) return rc;
     KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
     kp.G = d_T_c_w; kp.in_of_match = d_input_of_match;
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
@@ -1523,9 +1524,7 @@ int vslam_build_windows_map_gated_dev(vslam_ctx* ctx, const vslam_tracks_in* in,
                                       vslam_ba_batch* out, int32_t* d_kf_frame, int32_t* d_evicted, int32_t* d_status) {
     if (!ctx || !in || !d_kf_frame || !d_evicted || !d_frame_state) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (int rc = map_refuses(in, d_T_c_w)) return rc;
-    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 oldest evicted, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
-    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
-    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
+    if (int rc = kf_policy_refuses(policy, "oldest evicted", n_kf, near_dist)) return rc;
     KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
     kp.G = d_T_c_w; kp.in_of_match = d_input_of_match; kp.gate = true; kp.state_in = d_frame_state;
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);
@@ -1537,9 +1536,7 @@ int vslam_build_windows_map_recover_dev(vslam_ctx* ctx, const vslam_tracks_in* i
     if (!ctx || !in || !d_kf_frame || !d_evicted || !d_frame_state) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     if (!d_pred) { set_error("d_pred (n_frames: the pairing in->d_f2f was built on) is required"); return VSLAM_ERR_ARG; }
     if (int rc = map_refuses(in, d_T_c_w)) return rc;
-    if (policy != 0 && policy != 1) { set_error("unknown keyframe policy %d (0 oldest evicted, 1 reference culling)", policy); return VSLAM_ERR_ARG; }
-    if (n_kf < 1 || n_kf > VSLAM_MAX_KF) { set_error("n_kf %d outside 1..%d", n_kf, VSLAM_MAX_KF); return VSLAM_ERR_ARG; }
-    if (!(near_dist >= 0.0)) { set_error("near_dist must be a number >= 0"); return VSLAM_ERR_ARG; }
+    if (int rc = kf_policy_refuses(policy, "oldest evicted", n_kf, near_dist)) return rc;
     KfPolicy kp = {policy, near_dist, d_kf_frame, d_evicted};
     kp.G = d_T_c_w; kp.in_of_match = d_input_of_match; kp.gate = true; kp.state_in = d_frame_state; kp.recover = true; kp.pred_table = d_pred;
     return build_windows(ctx, in, n_kf, lm_capacity, edge_capacity, out, d_status, kp);

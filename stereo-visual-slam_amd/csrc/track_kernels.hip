@@ -871,94 +871,129 @@ __global__ __launch_bounds__(256) void window_emit_kernel(TrackDims d, const vsl
     if (ws.lm_id) ws.lm_id[g] = root[last]; // the landmark's identity across windows: its creating frame x kp_cap + its creating keypoint
 }
 
-int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
-                         int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
-                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream, const SegView& seg) {
-    TrackDims d;
-    d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = n_kf;
-    d.start = seg.start; d.first = seg.first; d.n_seg = seg.n_seg;
-    const int seg_grid = seg.first ? seg.n_seg : 1; // the per-sequence kernels: one workgroup per segment
-    const bool gate = kp.gate, cull = kp.policy == 1 || gate; // (cull: the set-templated window kernels)
-    const size_t tab = (size_t)d.B * d.kp_cap;
-    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *info, *counts, *hist; double* G; uint32_t* head_rec;
-    int2* ends = nullptr; double* D = nullptr; int32_t* set_flags = nullptr; int32_t* nmem = nullptr;
-    int32_t *r_pred = nullptr, *nxt = nullptr, *lfrm = nullptr, *r_flags = nullptr, *r_state = nullptr; double* r_gap = nullptr; // (kp.recover: the pairing of the states)
-    if (int rc = carve(scratch, stream, [&](Layout& L) {
-            kp2lr = L.take<int32_t>(tab); pred = L.take<int32_t>(tab); succ = L.take<int32_t>(tab);
-            root = L.take<int32_t>(tab); relsrc = L.take<int32_t>(tab); info = L.take<int32_t>(tab);
-            G = L.take<double>((size_t)d.B * 7);
-            counts = L.take<int32_t>((size_t)d.B * 2);
-            hist = L.take<int32_t>((size_t)d.B * (VSLAM_MAX_KF + 1));
-            head_rec = L.take<uint32_t>(lm_capacity);
-            if (cull) { // the chain records, the distance band, the set kernel's flags; the gate: also the member counts
-                ends = L.take<int2>(tab);
-                D = L.take<double>((size_t)d.B * kKfBand);
-                set_flags = L.take<int32_t>(64);
-                if (gate) nmem = L.take<int32_t>(d.B);
-            }
-            if (kp.recover) {
-                r_pred = L.take<int32_t>(d.B); nxt = L.take<int32_t>(d.B); lfrm = L.take<int32_t>(d.B); r_flags = L.take<int32_t>(64); r_state = L.take<int32_t>(d.B);
-                r_gap = L.take<double>(d.B);
-            }
-        })) return rc;
-    WindowSet ws = {kp.kf_frame, ends, root, nmem};
-    ws.nxt = nxt; ws.lm_id = kp.lm_id;
-    TrackCam cam;
-    cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
-    int32_t* cand = info; // (the candidate words live in the info table until track_info_kernel writes it)
-    ProfScope prof__(stream, "build_windows_kernels", 9);
-    if (kp.recover) { // which frame every frame continues from under the caller's states, and which items' links that honours (table built on kp.pred_table)
-        VS_HIP(hipMemsetAsync(r_flags, 0, sizeof(int32_t), stream));
-        hipLaunchKernelGGL(frame_pairs_kernel, dim3(seg_grid), dim3(256), 0, stream, d.B, kp.state_in, r_state, r_pred, r_gap, nxt, kp.pred_table, lfrm, r_flags, seg.first);
-    }
-    hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
-    if (kp.G) VS_HIP(hipMemcpyAsync(G, kp.G, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (the map builder: the caller's poses)
-    else if (in.d_T_abs) VS_HIP(hipMemcpyAsync(G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
-    else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(seg_grid), dim3(256), 0, stream, d.B, in.d_T_rel, G, seg.first);
-    const int32_t* state = kp.recover ? r_state : kp.state_in ? kp.state_in : kp.frame_state; // (the map builder: the caller's states; recover: with the Lost frames marked)
-    if (cull && seg.first) VS_HIP(hipMemsetAsync(set_flags, 0, sizeof(int32_t), stream)); // (the segments' waves OR their flags into the word)
-    if (gate) { // the states depend on the pose stage's outputs alone, the keyframe sets on the states and the poses
+struct WindowTables { double* G; int32_t *counts, *hist; uint32_t* head_rec; int2* ends = nullptr; double* D = nullptr; int32_t *set_flags = nullptr, *nmem = nullptr; }; // the window builder's own scratch
+
+// ---- which keyframes every window holds: the gate's states (unless they are the caller's) and the sets on them, the culled sets, or the sliding sets
+static void launch_kf_sets(int B, int n_kf, const vslam_tracks_in& in, const KfPolicy& kp, const WindowTables& w, const int32_t* state, int seg_grid, const SegView& seg, hipStream_t stream) {
+    if (kp.gate) { // the states depend on the pose stage's outputs alone, the keyframe sets on the states and the poses
         if (!kp.state_in)
-            hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((d.B + 255) / 256), dim3(256), 0, stream, d.B, kp.num_inliers, in.d_T_rel, kp.frame_state, seg.start);
-        if (kp.policy == 1) hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D, seg.start);
-        hipLaunchKernelGGL(kf_set_kernel<true>, dim3(seg_grid), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, kp.policy == 1 ? D : nullptr, kp.kf_frame, kp.evicted,
-                           set_flags, state, nmem, seg.first);
-    } else if (cull) { // the keyframe sets depend on the poses alone
-        hipLaunchKernelGGL(kf_band_kernel, dim3((d.B * kKfBand + 255) / 256), dim3(256), 0, stream, d.B, G, D, seg.start);
-        hipLaunchKernelGGL(kf_set_kernel<false>, dim3(seg_grid), dim3(64), 0, stream, d.B, n_kf, kp.near_dist, G, D, kp.kf_frame, kp.evicted, set_flags, nullptr, nullptr,
-                           seg.first);
+            hipLaunchKernelGGL(kf_gate_kernel<false>, dim3((B + 255) / 256), dim3(256), 0, stream, B, kp.num_inliers, in.d_T_rel, kp.frame_state, seg.start);
+        if (kp.policy == 1) hipLaunchKernelGGL(kf_band_kernel, dim3((B * kKfBand + 255) / 256), dim3(256), 0, stream, B, w.G, w.D, seg.start);
+        hipLaunchKernelGGL(kf_set_kernel<true>, dim3(seg_grid), dim3(64), 0, stream, B, n_kf, kp.near_dist, w.G, kp.policy == 1 ? w.D : nullptr, kp.kf_frame, kp.evicted, w.set_flags,
+                           state, w.nmem, seg.first);
+    } else if (kp.policy == 1) { // the keyframe sets depend on the poses alone
+        hipLaunchKernelGGL(kf_band_kernel, dim3((B * kKfBand + 255) / 256), dim3(256), 0, stream, B, w.G, w.D, seg.start);
+        hipLaunchKernelGGL(kf_set_kernel<false>, dim3(seg_grid), dim3(64), 0, stream, B, n_kf, kp.near_dist, w.G, w.D, kp.kf_frame, kp.evicted, w.set_flags, nullptr, nullptr, seg.first);
     } else if (kp.policy == 0)
-        hipLaunchKernelGGL(kf_sliding_kernel, dim3((d.B * n_kf + 255) / 256), dim3(256), 0, stream, d.B, n_kf, kp.kf_frame, kp.evicted, seg.start);
-    if (d.B > 1 && kp.in_of_match)
-        hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, kp.in_of_match, lfrm);
+        hipLaunchKernelGGL(kf_sliding_kernel, dim3((B * n_kf + 255) / 256), dim3(256), 0, stream, B, n_kf, kp.kf_frame, kp.evicted, seg.start);
+}
+
+// ---- the front half both builders share: the dims (with the segment table), the camera, the six n_frames x kp_capacity node tables, and the
+// launches from the optional pairing to the walk.  A launcher carves its scratch ONCE (a second carve may grow the buffer and free the first
+// one's memory), so the tables come out of the launcher's own layout: take().
+struct TrackTables {
+    TrackDims d; TrackCam cam;
+    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *cand;
+    int32_t *nxt = nullptr, *lfrm = nullptr, *r_state = nullptr; // recover: the pairing's next accepted frame / link frame, the states with the Lost frames marked
+    TrackTables(const vslam_tracks_in& in, int n_kf, const TrackParams& tp, const SegView& seg) {
+        d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = n_kf;
+        d.start = seg.start; d.first = seg.first; d.n_seg = seg.n_seg;
+        cam.fx = tp.K4[0]; cam.fy = tp.K4[1]; cam.cx = tp.K4[2]; cam.cy = tp.K4[3]; cam.thr2 = tp.reproj_thr * tp.reproj_thr; cam.track_rule = tp.track_rule;
+    }
+    size_t tab() const { return (size_t)d.B * d.kp_cap; }
+    int seg_grid() const { return d.first ? d.n_seg : 1; } // the per-sequence kernels: one workgroup per segment
+    void take(Layout& L, bool recover) {
+        kp2lr = L.take<int32_t>(tab()); pred = L.take<int32_t>(tab()); succ = L.take<int32_t>(tab());
+        root = L.take<int32_t>(tab()); relsrc = L.take<int32_t>(tab()); cand = L.take<int32_t>(tab());
+        if (recover) { nxt = L.take<int32_t>(d.B); lfrm = L.take<int32_t>(d.B); r_state = L.take<int32_t>(d.B); }
+    }
+};
+
+// the tables' initial state; before it, rv non-null (recover): the pairing of `state` (rv->d_pred / d_gap; rv->d_pred_prev: the one in.d_f2f was built on), flags ORed into *flags
+static void launch_track_init(const TrackTables& t, const vslam_tracks_in& in, const MapRecover* rv, const int32_t* state, int32_t* flags, hipStream_t stream) {
+    if (rv)
+        hipLaunchKernelGGL(frame_pairs_kernel, dim3(t.seg_grid()), dim3(256), 0, stream, t.d.B, state, t.r_state, rv->d_pred, rv->d_gap, t.nxt, rv->d_pred_prev, t.lfrm, flags, t.d.first);
+    hipLaunchKernelGGL(track_init_kernel, dim3(t.d.B), dim3(256), 0, stream, t.d, in.d_lr, in.d_nlr, t.kp2lr, t.pred, t.succ, t.cand);
+}
+
+// the links (through in_of_match when it is set, else by the pose stage's own-depth flags and track_rule) and the walk on the poses G; state non-null: the gated walk
+static void launch_track_walk(const TrackTables& t, const vslam_tracks_in& in, const int32_t* in_of_match, const double* G, const float* carry_in, const int32_t* state,
+                              hipStream_t stream) {
+    const TrackDims& d = t.d;
+    if (d.B > 1 && in_of_match)
+        hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, t.kp2lr, t.cand, t.succ, in_of_match, t.lfrm);
     else if (d.B > 1)
-        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr, lfrm);
-    if (gate)
-        hipLaunchKernelGGL(track_walk_kernel<true>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
-                           G, in.d_carry_in, root, relsrc, state, nxt);
+        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, t.kp2lr, t.cand, t.succ, nullptr, t.lfrm);
+    const dim3 grid((d.kp_cap + 255) / 256, d.B);
+    if (state)
+        hipLaunchKernelGGL(track_walk_kernel<true>, grid, dim3(256), 0, stream, d, t.cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, t.kp2lr, t.cand, t.pred, t.succ, G, carry_in,
+                           t.root, t.relsrc, state, t.nxt);
     else
-        hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, kp2lr, cand, pred, succ,
-                           G, in.d_carry_in, root, relsrc, nullptr, nullptr);
+        hipLaunchKernelGGL(track_walk_kernel<false>, grid, dim3(256), 0, stream, d, t.cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable, t.kp2lr, t.cand, t.pred, t.succ, G, carry_in,
+                           t.root, t.relsrc, nullptr, nullptr);
+}
+
+// ---- count / scan / rank / emit on the sliding windows (info words) or on the keyframe sets (kSet: chain records) into the caller's batch o, whose total_lm /
+// total_edge are its capacities.  The builder WRITES the arrays that the optimiser's view of the struct declares const: the casts live here.
+template <bool kSet>
+static void launch_window_kernels(const TrackTables& t, const vslam_tracks_in& in, const WindowTables& w, const WindowSet& ws, const vslam_ba_batch& o, int32_t* d_status,
+                                  hipStream_t stream) {
+    const TrackDims& d = t.d;
+    const int32_t* info = t.cand; // (the candidate words live in the info table until track_info_kernel writes it)
+    hipLaunchKernelGGL(window_count_kernel<kSet>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, w.counts, w.hist, ws);
+    hipLaunchKernelGGL(window_scan_kernel<kSet>, dim3(1), dim3(256), 0, stream, d, w.counts, o.total_lm, o.total_edge, const_cast<int32_t*>(o.d_lm_off),
+                       const_cast<int32_t*>(o.d_edge_off), const_cast<int32_t*>(o.d_n_kf), d_status, w.set_flags, w.nmem);
+    hipLaunchKernelGGL(window_rank_kernel<kSet>, dim3(d.B), dim3(kRankBlock), 0, stream, d, w.G, w.counts, w.hist, info, in.d_nkps, o.d_lm_off, o.d_edge_off, o.d_T_c_w, w.head_rec, ws);
+    hipLaunchKernelGGL(window_emit_kernel<kSet>, dim3((o.total_lm + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, t.kp2lr, t.root, t.relsrc, t.succ, w.G, in.d_carry_in, w.hist,
+                       w.head_rec, o.d_lm_off, o.d_edge_off, o.d_xyz, const_cast<uint8_t*>(o.d_reliable), o.d_lm_inlier, const_cast<int32_t*>(o.d_kf_idx),
+                       const_cast<int32_t*>(o.d_lm_idx), const_cast<float*>(o.d_uv), ws);
+}
+
+int launch_build_windows(const vslam_tracks_in& in, const vslam_ba_batch& out, int32_t* d_status, const TrackParams& tp, const KfPolicy& kp, DevBuf& scratch, hipStream_t stream,
+                         const SegView& seg) {
+    TrackTables t(in, out.n_kf, tp, seg);
+    const TrackDims& d = t.d;
+    const bool cull = kp.policy == 1 || kp.gate; // (cull: the set-templated window kernels)
+    WindowTables w;
+    MapRecover rv = {kp.pred_table, nullptr, nullptr}; int32_t* r_flags = nullptr; // (kp.recover: the pairing of the states, built on kp.pred_table)
+    if (int rc = carve(scratch, stream, [&](Layout& L) {
+            t.take(L, kp.recover);
+            w.G = L.take<double>((size_t)d.B * 7);
+            w.counts = L.take<int32_t>((size_t)d.B * 2);
+            w.hist = L.take<int32_t>((size_t)d.B * (VSLAM_MAX_KF + 1));
+            w.head_rec = L.take<uint32_t>(out.total_lm);
+            if (cull) { // the chain records, the distance band, the set kernel's flags; the gate: also the member counts
+                w.ends = L.take<int2>(t.tab());
+                w.D = L.take<double>((size_t)d.B * kKfBand);
+                w.set_flags = L.take<int32_t>(64);
+                if (kp.gate) w.nmem = L.take<int32_t>(d.B);
+            }
+            if (kp.recover) { rv.d_pred = L.take<int32_t>(d.B); rv.d_gap = L.take<double>(d.B); r_flags = L.take<int32_t>(64); }
+        })) return rc;
+    WindowSet ws = {kp.kf_frame, w.ends, t.root, w.nmem};
+    ws.nxt = t.nxt; ws.lm_id = kp.lm_id;
+    ProfScope prof__(stream, "build_windows_kernels", 9);
+    if (kp.recover) VS_HIP(hipMemsetAsync(r_flags, 0, sizeof(int32_t), stream)); // (the pairing's flags reach d_status at the end)
+    launch_track_init(t, in, kp.recover ? &rv : nullptr, kp.state_in, r_flags, stream);
+    if (kp.G) VS_HIP(hipMemcpyAsync(w.G, kp.G, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (the map builder: the caller's poses)
+    else if (in.d_T_abs) VS_HIP(hipMemcpyAsync(w.G, in.d_T_abs, sizeof(double) * 7 * (size_t)d.B, hipMemcpyDeviceToDevice, stream)); // (a chunk: poses in the sequence's world)
+    else hipLaunchKernelGGL(track_pose_chain_kernel, dim3(t.seg_grid()), dim3(256), 0, stream, d.B, in.d_T_rel, w.G, seg.first);
+    const int32_t* state = kp.recover ? t.r_state : kp.state_in ? kp.state_in : kp.frame_state; // (the map builder: the caller's states; recover: with the Lost frames marked)
+    if (cull && seg.first) VS_HIP(hipMemsetAsync(w.set_flags, 0, sizeof(int32_t), stream)); // (the segments' waves OR their flags into the word)
+    launch_kf_sets(d.B, out.n_kf, in, kp, w, state, t.seg_grid(), seg, stream);
+    launch_track_walk(t, in, kp.in_of_match, w.G, in.d_carry_in, kp.gate ? state : nullptr, stream);
+    const dim3 node_grid((d.kp_cap + 255) / 256, d.B);
     if (!kp.recover) // (the info words serve the sliding windows; the recovered windows are set windows, which read root / ends)
-        hipLaunchKernelGGL(track_info_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, pred, succ, root, in.d_carry_in, info);
+        hipLaunchKernelGGL(track_info_kernel, node_grid, dim3(256), 0, stream, d, t.pred, t.succ, t.root, in.d_carry_in, t.cand);
     if (in.d_carry_out && in.carry_out_frame > 0 && in.carry_out_frame < d.B)
-        hipLaunchKernelGGL(track_carry_out_kernel, dim3((d.kp_cap + 255) / 256), dim3(256), 0, stream, d, in.carry_out_frame, kp2lr, pred, root, relsrc, in.d_xyz, G,
+        hipLaunchKernelGGL(track_carry_out_kernel, dim3((d.kp_cap + 255) / 256), dim3(256), 0, stream, d, in.carry_out_frame, t.kp2lr, t.pred, t.root, t.relsrc, in.d_xyz, w.G,
                            in.d_carry_in, in.d_carry_out);
     if (cull) {
-        hipLaunchKernelGGL(track_ends_kernel, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, succ, root, relsrc, ends);
-        hipLaunchKernelGGL(window_count_kernel<true>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist, ws);
-        hipLaunchKernelGGL(window_scan_kernel<true>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags, nmem);
-        hipLaunchKernelGGL(window_rank_kernel<true>, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec, ws);
-        hipLaunchKernelGGL(window_emit_kernel<true>, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist,
-                           head_rec, d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out, ws);
+        hipLaunchKernelGGL(track_ends_kernel, node_grid, dim3(256), 0, stream, d, t.succ, t.root, t.relsrc, w.ends);
+        launch_window_kernels<true>(t, in, w, ws, out, d_status, stream);
         if (kp.recover) hipLaunchKernelGGL(status_or_kernel, dim3(1), dim3(1), 0, stream, d_status, r_flags);
-    } else {
-        hipLaunchKernelGGL(window_count_kernel<false>, dim3(d.B), dim3(256), 0, stream, d, info, in.d_nkps, counts, hist, ws);
-        hipLaunchKernelGGL(window_scan_kernel<false>, dim3(1), dim3(256), 0, stream, d, counts, lm_capacity, edge_capacity, d_lm_off, d_edge_off, d_n_kf, d_status, set_flags, nmem);
-        hipLaunchKernelGGL(window_rank_kernel<false>, dim3(d.B), dim3(kRankBlock), 0, stream, d, G, counts, hist, info, in.d_nkps, d_lm_off, d_edge_off, d_T, head_rec, ws);
-        hipLaunchKernelGGL(window_emit_kernel<false>, dim3((lm_capacity + 255) / 256), dim3(256), 0, stream, d, in.d_kps, in.d_xyz, kp2lr, root, relsrc, succ, G, in.d_carry_in, hist,
-                           head_rec, d_lm_off, d_edge_off, d_xyz_out, d_rel_out, d_inl_out, d_kf_out, d_lm_out, d_uv_out, ws);
-    }
+    } else
+        launch_window_kernels<false>(t, in, w, ws, out, d_status, stream);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }
@@ -1002,6 +1037,12 @@ int launch_gate_states_pairs(int n_frames, const double* d_G, const int32_t* d_p
     return VSLAM_OK;
 }
 
+int launch_seg_expand(int n_frames, int n_seg, const int32_t* d_first, int32_t* d_start, int32_t* d_qitem, hipStream_t stream) {
+    hipLaunchKernelGGL(seg_expand_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, n_seg, d_first, d_start, d_qitem);
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
 // ---- one refinement pass's pose inputs (vslam_build_map_pnp_inputs_dev): the walk of the builders on the caller's poses G and the previous pass's
 // links (in_of_match_prev, or the pose stage's own-depth flags and track_rule when it is null), then the map inputs of every frame pair.
 // d_state (vslam_build_map_pnp_inputs_gated_dev; else null): the previous pass's frame states -- the gated walk, a non-keyframe creates nothing.
@@ -1010,53 +1051,27 @@ int launch_gate_states_pairs(int n_frames, const double* d_G, const int32_t* d_p
 // rv (vslam_build_map_pnp_inputs_recover_dev, with rq; else null): d_state also gives the pairing -- every frame against its last accepted predecessor,
 // Lost frames without one (frame_pairs_kernel: rv->d_pred, rv->d_gap) --, the walk honours a pair's links only when in.d_f2f was built on that pairing
 // (rv->d_pred_prev) and steps through the accepted frames, and pair f - 1 is re-matched from the features of pred(f) at gap f - pred(f)
-int launch_seg_expand(int n_frames, int n_seg, const int32_t* d_first, int32_t* d_start, int32_t* d_qitem, hipStream_t stream) {
-    hipLaunchKernelGGL(seg_expand_kernel, dim3((n_frames + 255) / 256), dim3(256), 0, stream, n_frames, n_seg, d_first, d_start, d_qitem);
-    VS_HIP(hipGetLastError());
-    return VSLAM_OK;
-}
-
-int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
-                          double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
-                          int out_capacity, int32_t* d_status, hipStream_t stream, const SegView& seg, const MapRequery* rq, const MapRecover* rv) {
-    TrackDims d;
-    d.B = in.n_frames; d.kp_cap = in.kp_capacity; d.lr_cap = in.lr_capacity; d.match_cap = in.match_capacity; d.pnp_cap = in.pnp_capacity; d.n_kf = 1;
-    d.start = seg.start; d.first = seg.first; d.n_seg = seg.n_seg;
-    const size_t tab = (size_t)d.B * d.kp_cap;
-    int32_t *kp2lr, *pred, *succ, *root, *relsrc, *cand; double* gap = nullptr; int32_t *nxt = nullptr, *lfrm = nullptr, *r_state = nullptr;
+int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const TrackParams& tp, const MapInputsOut& out,
+                          const MapRequery* rq, const MapRecover* rv, DevBuf& scratch, hipStream_t stream, const SegView& seg) {
+    TrackTables t(in, 1, tp, seg);
+    const TrackDims& d = t.d;
+    double* gap = nullptr;
     if (int rc = carve(scratch, stream, [&](Layout& L) {
-            kp2lr = L.take<int32_t>(tab); pred = L.take<int32_t>(tab); succ = L.take<int32_t>(tab);
-            root = L.take<int32_t>(tab); relsrc = L.take<int32_t>(tab); cand = L.take<int32_t>(tab);
+            t.take(L, rv != nullptr);
             if (rq && !rv) gap = L.take<double>(d.B);
-            if (rv) { nxt = L.take<int32_t>(d.B); lfrm = L.take<int32_t>(d.B); r_state = L.take<int32_t>(d.B); }
         })) return rc;
-    TrackCam cam;
-    cam.fx = K4[0]; cam.fy = K4[1]; cam.cx = K4[2]; cam.cy = K4[3]; cam.thr2 = reproj_thr * reproj_thr; cam.track_rule = track_rule;
     ProfScope prof__(stream, "map_pnp_inputs_kernels", 4);
-    VS_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t), stream));
+    VS_HIP(hipMemsetAsync(out.status, 0, sizeof(int32_t), stream));
     if (d.B < 2) {
         if (rq) VS_HIP(hipMemsetAsync(rq->d_nfeat, 0, sizeof(int32_t) * d.B, stream)); // (no pair: no walk, no list)
         if (rv) VS_HIP(hipMemsetAsync(rv->d_pred, 0xFF, sizeof(int32_t) * d.B, stream)); // (frame 0 has no predecessor; no gap entry)
         return VSLAM_OK;
     }
-    if (rv) // (the flags -- a Lost frame, an out-of-range state or d_pred_prev entry -- go straight into the status word cleared above)
-        hipLaunchKernelGGL(frame_pairs_kernel, dim3(seg.first ? seg.n_seg : 1), dim3(256), 0, stream, d.B, d_state, r_state, rv->d_pred, rv->d_gap, nxt, rv->d_pred_prev, lfrm,
-                           d_status, seg.first);
-    hipLaunchKernelGGL(track_init_kernel, dim3(d.B), dim3(256), 0, stream, d, in.d_lr, in.d_nlr, kp2lr, pred, succ, cand);
-    if (d_in_of_match_prev)
-        hipLaunchKernelGGL(track_link_kernel<true>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ,
-                           d_in_of_match_prev, lfrm);
-    else
-        hipLaunchKernelGGL(track_link_kernel<false>, dim3(d.B - 1), dim3(256), 0, stream, d, in.d_f2f, in.d_nf2f, in.d_valid, in.d_pose_inlier, kp2lr, cand, succ, nullptr, lfrm);
-    if (d_state)
-        hipLaunchKernelGGL(track_walk_kernel<true>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable,
-                           kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, rv ? r_state : d_state, nxt);
-    else
-        hipLaunchKernelGGL(track_walk_kernel<false>, dim3((d.kp_cap + 255) / 256, d.B), dim3(256), 0, stream, d, cam, in.d_kps, in.d_xyz, in.d_valid, in.d_reliable,
-                           kp2lr, cand, pred, succ, d_G, nullptr, root, relsrc, nullptr, nullptr);
+    launch_track_init(t, in, rv, d_state, out.status, stream); // (rv: the flags -- a Lost frame, an out-of-range state or d_pred_prev entry -- go straight into the status word)
+    launch_track_walk(t, in, d_in_of_match_prev, d_G, nullptr, d_state && rv ? t.r_state : d_state, stream);
     const vslam_dmatch* f2f = in.d_f2f; const int32_t* nf2f = in.d_nf2f;
     if (rq) { // pair i: queries = the features of frame i, trains = every keypoint of frame i + 1, the gate of VO::feature_matching at frame_gap 1
-        hipLaunchKernelGGL(track_features_kernel, dim3(d.B), dim3(256), 0, stream, d, root, in.d_nkps, rq->d_feat, rq->d_nfeat, gap);
+        hipLaunchKernelGGL(track_features_kernel, dim3(d.B), dim3(256), 0, stream, d, t.root, in.d_nkps, rq->d_feat, rq->d_nfeat, gap);
         prof_end(stream); // (the matcher brackets its own kernels: this bracket closes before it ...
         // (rv: item i's query block is frame pred(i + 1) -- the d_qitem path, block indices = frame indices -- at the pairing's gaps; segments: the same
         // path with block i for item i and -1 for a boundary item, which the matcher leaves empty without running on it.  pred = -1 at a segment's first frame)
@@ -1066,8 +1081,8 @@ int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const in
         prof_begin(stream, "track_map_inputs_kernel", 1); // ... and prof__ closes this one, around the emit)
         f2f = rq->d_f2f_out; nf2f = rq->d_nf2f_out;
     }
-    hipLaunchKernelGGL(track_map_inputs_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, f2f, nf2f, in.d_kps, in.d_xyz, kp2lr, root, relsrc, d_G,
-                       out_capacity, d_xyz_out, d_uv_out, d_n_out, d_in_of_match, d_status, rv ? rv->d_pred + 1 : nullptr);
+    hipLaunchKernelGGL(track_map_inputs_kernel, dim3(d.B - 1), dim3(256), 0, stream, d, f2f, nf2f, in.d_kps, in.d_xyz, t.kp2lr, t.root, t.relsrc, d_G,
+                       out.capacity, out.xyz, out.uv, out.n, out.in_of_match, out.status, rv ? rv->d_pred + 1 : nullptr);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

@@ -318,7 +318,8 @@ int launch_pnp_count_inliers(const float* d_xyz, const float* d_uv, int n, const
 
 int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t* d_n, int capacity, int B, int H, const double K[4], double reproj_err,
                             double confidence, DevBuf& scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream);
-// track_kernels.hip: BA windows of a batch of consecutive keyframes from the front end's device-resident output
+// track_kernels.hip: BA windows of a batch of consecutive keyframes from the front end's device-resident output.  launch_build_windows and
+// launch_map_pnp_inputs share one front half (dims, node tables, pairing, init, link, walk); KfPolicy says what the window builder adds to it.
 // Which keyframes a window holds (vslam_build_windows_kf_dev): policy -1 = the sliding window with no set outputs (vslam_build_windows_dev),
 // 0 = the sliding window with its sets written to kf_frame / evicted, 1 = the reference's culling (needs extra scratch).
 // gate (vslam_build_windows_gated_dev): insert_key_frame's keyframe gate on num_inliers (n_frames - 1) and T_rel, states to frame_state; policy 0 / 1.
@@ -336,10 +337,11 @@ struct KfPolicy { int policy; double near_dist; int32_t* kf_frame; int32_t* evic
 // f's segment (n_frames), first (n_seg + 1), qitem[i] = i, or -1 for the item before a segment's first frame (n_frames - 1).
 struct SegView { const int32_t* start = nullptr; const int32_t* first = nullptr; const int32_t* qitem = nullptr; int n_seg = 0; };
 int launch_seg_expand(int n_frames, int n_seg, const int32_t* d_first, int32_t* d_start, int32_t* d_qitem, hipStream_t stream);
-// K4 = {fx, fy, cx, cy}, reproj_thr (pixels), track_rule: see Tuning::track_rule
-int launch_build_windows(const vslam_tracks_in& in, int n_kf, int lm_capacity, int edge_capacity, const double K4[4], double reproj_thr, int track_rule, DevBuf& scratch,
-                         int32_t* d_lm_off, int32_t* d_edge_off, int32_t* d_n_kf, double* d_T, float* d_xyz_out, uint8_t* d_rel_out, uint8_t* d_inl_out,
-                         int32_t* d_kf_out, int32_t* d_lm_out, float* d_uv_out, int32_t* d_status, const KfPolicy& kp, hipStream_t stream, const SegView& seg);
+// What both builders' walk takes from the context: K4 = {fx, fy, cx, cy}, reproj_thr (pixels), track_rule resolved to 0 / 1 (see Tuning::track_rule)
+struct TrackParams { double K4[4]; double reproj_thr; int track_rule; };
+// out: the caller's batch -- n_kf the pose stride, total_lm / total_edge the capacities of its arrays, every array written -- and its status word
+int launch_build_windows(const vslam_tracks_in& in, const vslam_ba_batch& out, int32_t* d_status, const TrackParams& tp, const KfPolicy& kp, DevBuf& scratch, hipStream_t stream,
+                         const SegView& seg);
 int launch_chain_poses(int n_frames, const double* d_T_rel, double* d_G, hipStream_t stream, const SegView& seg);
 // insert_key_frame's gate per frame (vslam_gate_states_dev): absolute 0 on T_rel (n_frames - 1 rows), 1 on absolute poses (n_frames rows)
 int launch_gate_states(int n_frames, const double* d_T, int absolute, const int32_t* d_num_inliers, int32_t* d_state, hipStream_t stream, const SegView& seg);
@@ -348,17 +350,20 @@ int launch_gate_states(int n_frames, const double* d_T, int absolute, const int3
 int launch_frame_pairs(int n_frames, const int32_t* d_state, int32_t* d_pred, double* d_gap, hipStream_t stream, const SegView& seg);
 int launch_gate_states_pairs(int n_frames, const double* d_G, const int32_t* d_pred, const int32_t* d_num_inliers, int32_t* d_state, DevBuf& scratch,
                              hipStream_t stream, const SegView& seg);
-// vslam_build_map_pnp_inputs_recover_dev: the pairing in.d_f2f was built on (null: adjacent frames) and the outputs of this pass's pairing
+// the recover entries: the pairing in.d_f2f was built on (null: adjacent frames) and where the pairing of this call's states goes (the caller's
+// arrays in vslam_build_map_pnp_inputs_recover_dev, scratch in the window builder)
 struct MapRecover { const int32_t* d_pred_prev; int32_t* d_pred; double* d_gap; };
 // the re-match of vslam_build_map_pnp_inputs_requery_dev: frame f's descriptors at d_desc + f * desc_stride; outputs the feature lists (n_frames x kp_capacity,
 // n_frames) and the new frame-to-frame table ((n_frames - 1) x match_capacity); the matcher's gate parameters and scratch
 struct MapRequery { const uint8_t* d_desc; size_t desc_stride; int32_t* d_feat; int32_t* d_nfeat; vslam_dmatch* d_f2f_out; int32_t* d_nf2f_out;
                     double ratio, gap_thr; uint32_t* d_train_best; };
-// one refinement pass's pose inputs against the map (vslam_build_map_pnp_inputs_dev; d_state non-null: the gated walk, *_gated_dev; rq non-null: the
-// pairs are re-matched on their feature sets between the walk and the emit, *_requery_dev)
-int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const double K4[4],
-                          double reproj_thr, int track_rule, DevBuf& scratch, float* d_xyz_out, float* d_uv_out, int32_t* d_n_out, int32_t* d_in_of_match,
-                          int out_capacity, int32_t* d_status, hipStream_t stream, const SegView& seg, const MapRequery* rq = nullptr, const MapRecover* rv = nullptr);
+// the inputs of every frame pair (xyz / uv: (n_frames - 1) x capacity, n), the input index of every match and the status word
+struct MapInputsOut { float* xyz; float* uv; int32_t* n; int32_t* in_of_match; int capacity; int32_t* status; };
+// one refinement pass's pose inputs against the map (vslam_build_map_pnp_inputs_dev): the builders' walk on the caller's poses d_G and the previous
+// pass's links.  d_state non-null: the gated walk (*_gated_dev); rq non-null: the pairs are re-matched on their feature sets between the walk and
+// the emit (*_requery_dev); rv non-null (with rq and d_state): the pairing of the states decides who is matched against whom (*_recover_dev)
+int launch_map_pnp_inputs(const vslam_tracks_in& in, const double* d_G, const int32_t* d_in_of_match_prev, const int32_t* d_state, const TrackParams& tp, const MapInputsOut& out,
+                          const MapRequery* rq, const MapRecover* rv, DevBuf& scratch, hipStream_t stream, const SegView& seg);
 
 // chain_kernels.hip: the chained BA of vslam_ba_chain_dev.  Step j stages the j-th window of every sequence that has one into a batch of its own
 // (offsets, then gather with the carried poses and flags substituted), the schedule runs on it, and scatter takes the results back to the caller's

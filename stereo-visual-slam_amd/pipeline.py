@@ -22,6 +22,11 @@ from . import synth
 from .trajectory import assemble_trajectories, assemble_trajectory, sliding_keyframes, write_trajectory  # noqa: F401  (re-exported)
 
 
+def _copy_struct(st):
+    """a ctypes struct with the same field values (pointers included)"""
+    return type(st).from_buffer_copy(st)
+
+
 class KeyframePipeline:
     def __init__(self, B, device=0, anms_num=1500, n_lm=3000, n_kf=10, unique_frames=64, unique_windows=None, seed=0, verbose=False,
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
@@ -242,7 +247,7 @@ class KeyframePipeline:
             self.ba_nkf = torch.zeros(B, dtype=torch.int32, device=d)
             self.ba_build_status = torch.zeros(1, dtype=torch.int32, device=d)
             self.ba_chi2 = torch.zeros(1, dtype=torch.float64, device=d)
-            if window_policy == "reference" or keyframe_gate or pose_inputs == "map":
+            if self._builder_writes_kf:
                 self.ba_kf_frame = torch.zeros((B, n_kf), dtype=torch.int32, device=d)
                 self.ba_evicted = torch.zeros(B, dtype=torch.int32, device=d)
             if keyframe_gate:   # (per_pass: the latest pass's states, updated in place pass by pass)
@@ -271,10 +276,7 @@ class KeyframePipeline:
                 self.map_cur = 0
                 if per_pass:    # (the states the last pass started from: what it changed is a report)
                     self.map_state_prev = torch.zeros(B, dtype=torch.int32, device=d)
-                mt = TracksIn()
-                for f_, _ in TracksIn._fields_:
-                    setattr(mt, f_, getattr(tr, f_))
-                self.map_tracks = mt
+                self.map_tracks = _copy_struct(tr)
                 if f2f_queries == "features":   # table^k alternates between two buffers (table^0 = stage A's d_f2f); the last pass's feature lists
                     self.map_f2f = [torch.zeros((B, self.cap, 16), dtype=torch.uint8, device=d) for _ in range(2)]
                     self.map_nf2f = [torch.zeros(B, dtype=torch.int32, device=d) for _ in range(2)]
@@ -284,14 +286,7 @@ class KeyframePipeline:
                 if rejected_frames == "recover":   # pred^k alternates like the tables (a pass reads the pairing its table was built on); the last pass's gaps
                     self.map_pred = [torch.full((B,), -1, dtype=torch.int32, device=d) for _ in range(2)]
                     self.map_gap = torch.ones(B, dtype=torch.float64, device=d)
-            bb = BaBatch()
-            bb.n_windows = B; bb.n_kf = n_kf
-            bb.d_lm_off = self.ba_lm_off.data_ptr(); bb.d_edge_off = self.ba_e_off.data_ptr(); bb.d_T_c_w = self.ba_T.data_ptr()
-            bb.d_xyz = self.ba_xyz.data_ptr(); bb.d_reliable = self.ba_rel.data_ptr(); bb.d_lm_inlier = self.ba_inl.data_ptr()
-            bb.d_kf_idx = self.ba_kf.data_ptr(); bb.d_lm_idx = self.ba_lm.data_ptr(); bb.d_uv = self.ba_uv.data_ptr()
-            bb.d_chi2 = None; bb.d_stats = None; bb.K4 = None; bb.d_n_kf = self.ba_nkf.data_ptr()
-            bb.total_lm = self.lm_capacity; bb.total_edge = self.edge_capacity
-            self.ba_batch = bb
+            self.ba_batch = self._make_ba_batch(self.lm_capacity, self.edge_capacity, self.ba_rel, self.ba_nkf)
             self.unique_windows = B
             if self.ba_chain:   # context state, like the segment table: every builder of this context writes the ids from here on
                 self.vo.set_window_ids(self.ba_lm_id.data_ptr(), self.lm_capacity)
@@ -329,15 +324,41 @@ class KeyframePipeline:
             self.h_lm_off = np.array(lm_off, np.int64)
             self.edges_per_window = e_off[-1] / B
             self.lms_per_window = lm_off[-1] / B
-            bb = BaBatch()
-            bb.n_windows = B; bb.n_kf = n_kf
-            bb.d_lm_off = self.ba_lm_off.data_ptr(); bb.d_edge_off = self.ba_e_off.data_ptr(); bb.d_T_c_w = self.ba_T.data_ptr()
-            bb.d_xyz = self.ba_xyz.data_ptr(); bb.d_reliable = None; bb.d_lm_inlier = self.ba_inl.data_ptr()
-            bb.d_kf_idx = self.ba_kf.data_ptr(); bb.d_lm_idx = self.ba_lm.data_ptr(); bb.d_uv = self.ba_uv.data_ptr()
-            bb.d_chi2 = None; bb.d_stats = None  # per-edge chi2 is internal to optimize_map, not one of its outputs
-            bb.total_lm = self.total_lm; bb.total_edge = self.total_edge
-            self.ba_batch = bb
+            self.ba_batch = self._make_ba_batch(self.total_lm, self.total_edge)
         torch.cuda.synchronize(self.dev)
+
+    def _make_ba_batch(self, total_lm, total_edge, rel=None, nkf=None):
+        """the BaBatch over the pipeline's window tensors; rel / nkf: the reliable flags and per-window keyframe counts a builder writes (None: all
+        reliable, n_kf keyframes each).  Per-edge chi2 is internal to optimize_map, not one of its outputs; the intrinsics are the context's."""
+        bb = BaBatch()
+        bb.n_windows = self.B; bb.n_kf = self.n_kf
+        bb.d_lm_off = self.ba_lm_off.data_ptr(); bb.d_edge_off = self.ba_e_off.data_ptr(); bb.d_T_c_w = self.ba_T.data_ptr()
+        bb.d_xyz = self.ba_xyz.data_ptr(); bb.d_reliable = None if rel is None else rel.data_ptr(); bb.d_lm_inlier = self.ba_inl.data_ptr()
+        bb.d_kf_idx = self.ba_kf.data_ptr(); bb.d_lm_idx = self.ba_lm.data_ptr(); bb.d_uv = self.ba_uv.data_ptr()
+        bb.d_chi2 = None; bb.d_stats = None; bb.K4 = None; bb.d_n_kf = None if nkf is None else nkf.data_ptr()
+        bb.total_lm = total_lm; bb.total_edge = total_edge
+        return bb
+
+    # ------------------------------------------------------------------ which entries the options select (tools re-assign options on a live pipeline)
+    @property
+    def _map_flavour(self):
+        """the refinement passes' entry: "recover" / "requery" / "gated" / "plain" (None: pose_inputs="own_depth")"""
+        if self.pose_inputs != "map":
+            return None
+        return "recover" if self.rejected_frames == "recover" else "requery" if self.f2f_queries == "features" else \
+            "gated" if self.keyframe_gate == "per_pass" else "plain"
+
+    @property
+    def _window_builder(self):
+        """the window builder's entry: "map_recover" / "map_gated" / "map" on the passes' output, else "gated" / "kf" / "sliding" on stage A's"""
+        if self.pose_inputs == "map":
+            return "map_recover" if self.rejected_frames == "recover" else "map_gated" if self.keyframe_gate == "per_pass" else "map"
+        return "gated" if self.keyframe_gate else "kf" if self.window_policy == "reference" else "sliding"
+
+    @property
+    def _builder_writes_kf(self):
+        """the builder writes the keyframe sets ba_kf_frame / ba_evicted (every entry but the plain sliding one)"""
+        return self._window_builder != "sliding"
 
     # ------------------------------------------------------------------ stages
     def stage_rectify(self):
@@ -409,46 +430,38 @@ class KeyframePipeline:
         (G^{k-1}, links^{k-1}) -- LM from the guess G^{k-1}_f, RANSAC without one -- and an item with no inlier keeps G^k_f = G^{k-1}_{f-1}.
         keyframe_gate="per_pass": states^0 = the gate on stage A's counts and T_rel; pass k walks with states^{k-1}, then gates on its counts and G^k"""
         B, cap, n = self.B, self.cap, self.B - 1
-        mt = self.map_tracks
-        cur = 0
-        gated = self.keyframe_gate == "per_pass"
+        mt, cur = self.map_tracks, 0
+        flavour = self._map_flavour
+        gated, rematch, recover = flavour != "plain", flavour in ("requery", "recover"), flavour == "recover"
         self.vo.chain_poses_dev(B, self.d_Tpnp.data_ptr(), self.map_G[cur].data_ptr())
         if gated:
             self.vo.gate_states_dev(B, self.d_Tpnp.data_ptr(), 0, self.d_ninl.data_ptr(), self.ba_frame_state.data_ptr())
-        prev_index, prev_inl = None, self.d_inl
-        requery = self.f2f_queries == "features"
-        recover = self.rejected_frames == "recover"
-        pred_prev = None   # (stage A's table: adjacent frames)
+        state = self.ba_frame_state.data_ptr() if gated else None
+        prev_index, prev_inl, pred_prev = None, self.d_inl, None   # (no pairing: stage A's table is on adjacent frames)
         mt.d_f2f = self.d_f2f.data_ptr(); mt.d_nf2f = self.d_nf2f.data_ptr()   # (table^0: stage A's)
         for k in range(self.pose_passes):
             nxt = cur ^ 1
             G, Gn = self.map_G[cur], self.map_G[nxt]
             mt.d_pose_inlier = prev_inl.data_ptr(); mt.pnp_capacity = cap
-            prev = None if prev_index is None else prev_index.data_ptr()
-            if recover:   # the requery pass below with every frame matched from its last accepted predecessor; pred^{k-1} / gap are outputs
+            head = (mt, G.data_ptr(), None if prev_index is None else prev_index.data_ptr())
+            out = (self.map_xyz.data_ptr(), self.map_uv.data_ptr(), self.map_n.data_ptr(), self.map_index[nxt].data_ptr(), cap)
+            status = self.map_status.data_ptr()
+            if rematch:   # walk on table^{k-1}, re-match on its features into the other buffer, inputs on that table; the next pass walks on it
                 t = k & 1
+                rq = (self.d_desc.data_ptr(), cap * 32, self.map_feat.data_ptr(), self.map_nfeat.data_ptr(), self.map_f2f[t].data_ptr(), self.map_nf2f[t].data_ptr())
+            if recover:   # ... with every frame matched from its last accepted predecessor; pred^k / gap are outputs, pred^{k-1} the pairing of table^{k-1}
                 pred = self.map_pred[t]
-                self.vo.build_map_pnp_inputs_recover_dev(mt, G.data_ptr(), prev, None if pred_prev is None else pred_prev.data_ptr(),
-                                                         self.ba_frame_state.data_ptr(), self.d_desc.data_ptr(), cap * 32, self.map_feat.data_ptr(),
-                                                         self.map_nfeat.data_ptr(), self.map_f2f[t].data_ptr(), self.map_nf2f[t].data_ptr(),
-                                                         self.map_xyz.data_ptr(), self.map_uv.data_ptr(), self.map_n.data_ptr(), self.map_index[nxt].data_ptr(),
-                                                         cap, pred.data_ptr(), self.map_gap.data_ptr(), self.map_status.data_ptr())
-                mt.d_f2f = self.map_f2f[t].data_ptr(); mt.d_nf2f = self.map_nf2f[t].data_ptr()
-                self.map_table = t
-            elif requery:   # walk on table^{k-1}, re-match on its features into the other buffer, inputs on that table; the next pass walks on it
-                t = k & 1
-                self.vo.build_map_pnp_inputs_requery_dev(mt, G.data_ptr(), prev, self.ba_frame_state.data_ptr(), self.d_desc.data_ptr(), cap * 32,
-                                                         self.map_feat.data_ptr(), self.map_nfeat.data_ptr(), self.map_f2f[t].data_ptr(),
-                                                         self.map_nf2f[t].data_ptr(), self.map_xyz.data_ptr(), self.map_uv.data_ptr(), self.map_n.data_ptr(),
-                                                         self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
-                mt.d_f2f = self.map_f2f[t].data_ptr(); mt.d_nf2f = self.map_nf2f[t].data_ptr()
-                self.map_table = t
+                self.vo.build_map_pnp_inputs_recover_dev(*head, None if pred_prev is None else pred_prev.data_ptr(), state, *rq, *out, pred.data_ptr(),
+                                                         self.map_gap.data_ptr(), status)
+            elif rematch:
+                self.vo.build_map_pnp_inputs_requery_dev(*head, state, *rq, *out, status)
             elif gated:
-                self.vo.build_map_pnp_inputs_gated_dev(mt, G.data_ptr(), prev, self.ba_frame_state.data_ptr(), self.map_xyz.data_ptr(), self.map_uv.data_ptr(),
-                                                       self.map_n.data_ptr(), self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
+                self.vo.build_map_pnp_inputs_gated_dev(*head, state, *out, status)
             else:
-                self.vo.build_map_pnp_inputs_dev(mt, G.data_ptr(), prev, self.map_xyz.data_ptr(), self.map_uv.data_ptr(), self.map_n.data_ptr(),
-                                                 self.map_index[nxt].data_ptr(), cap, self.map_status.data_ptr())
+                self.vo.build_map_pnp_inputs_dev(*head, *out, status)
+            if rematch:
+                mt.d_f2f = self.map_f2f[t].data_ptr(); mt.d_nf2f = self.map_nf2f[t].data_ptr()
+                self.map_table = t
             with torch.cuda.stream(self.stream):
                 guess = torch.cat([G[1:], G[:1]])   # (item i: frame i + 1; the last row is not read)
             self._solve(self.map_xyz, self.map_uv, self.map_n, self.map_T, self.map_inl[nxt], self.map_ninl, guess)
@@ -476,35 +489,25 @@ class KeyframePipeline:
 
     def stage_build_windows(self):
         """optimize_map's graph build (optimization.cpp:127-214) + insert_key_frame's bookkeeping (visual_odometry.cpp:363-424) on the device"""
-        if self.pose_inputs == "map":   # the last pass's poses and links
-            c = self.map_cur
-            mt = self.map_tracks
+        builder, status = self._window_builder, self.ba_build_status.data_ptr()
+        if builder == "sliding":
+            return self.vo.build_windows_dev(self.tracks, self.n_kf, self.lm_capacity, self.edge_capacity, self.ba_batch, status)
+        policy = (self.n_kf, 1 if self.window_policy == "reference" else 0, self.near_dist)
+        outs = (self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(), self.ba_evicted.data_ptr())
+        if builder == "kf":
+            self.vo.build_windows_kf_dev(self.tracks, *policy, *outs, status)
+        elif builder == "gated":   # (d_ninl item i = the inlier count of frame i + 1)
+            self.vo.build_windows_gated_dev(self.tracks, *policy, self.d_ninl.data_ptr(), *outs, self.ba_frame_state.data_ptr(), status)
+        else:   # the last pass's poses and links
+            c, mt = self.map_cur, self.map_tracks
             mt.d_pose_inlier = self.map_inl[c].data_ptr(); mt.pnp_capacity = self.cap
-            if self.rejected_frames == "recover":   # (map_table also names the pairing the last pass's table was built on)
-                self.vo.build_windows_map_recover_dev(mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr(), self.map_pred[self.map_table].data_ptr(),
-                                                      self.ba_frame_state.data_ptr(), self.n_kf, 1 if self.window_policy == "reference" else 0, self.near_dist,
-                                                      self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(),
-                                                      self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
-                return
-            if self.keyframe_gate == "per_pass":
-                self.vo.build_windows_map_gated_dev(mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr(), self.ba_frame_state.data_ptr(), self.n_kf,
-                                                    1 if self.window_policy == "reference" else 0, self.near_dist, self.lm_capacity, self.edge_capacity,
-                                                    self.ba_batch, self.ba_kf_frame.data_ptr(), self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
-                return
-            self.vo.build_windows_map_dev(mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr(), self.n_kf, 1 if self.window_policy == "reference" else 0,
-                                          self.near_dist, self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(),
-                                          self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
-            return
-        if self.keyframe_gate:   # (d_ninl item i = the inlier count of frame i + 1)
-            self.vo.build_windows_gated_dev(self.tracks, self.n_kf, 1 if self.window_policy == "reference" else 0, self.near_dist, self.d_ninl.data_ptr(),
-                                            self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_kf_frame.data_ptr(), self.ba_evicted.data_ptr(),
-                                            self.ba_frame_state.data_ptr(), self.ba_build_status.data_ptr())
-            return
-        if self.window_policy == "reference":
-            self.vo.build_windows_kf_dev(self.tracks, self.n_kf, 1, self.near_dist, self.lm_capacity, self.edge_capacity, self.ba_batch,
-                                         self.ba_kf_frame.data_ptr(), self.ba_evicted.data_ptr(), self.ba_build_status.data_ptr())
-            return
-        self.vo.build_windows_dev(self.tracks, self.n_kf, self.lm_capacity, self.edge_capacity, self.ba_batch, self.ba_build_status.data_ptr())
+            head = (mt, self.map_G[c].data_ptr(), self.map_index[c].data_ptr())
+            if builder == "map_recover":   # (map_table also names the pairing the last pass's table was built on)
+                self.vo.build_windows_map_recover_dev(*head, self.map_pred[self.map_table].data_ptr(), self.ba_frame_state.data_ptr(), *policy, *outs, status)
+            elif builder == "map_gated":
+                self.vo.build_windows_map_gated_dev(*head, self.ba_frame_state.data_ptr(), *policy, *outs, status)
+            else:
+                self.vo.build_windows_map_dev(*head, *policy, *outs, status)
 
     def stage_build_windows_chunk(self, T_abs, carry_in=None, carry_out_frame=0):
         """sequence mode: this batch is the chunk [first, last] of a longer sequence.  T_abs (B, 7): the poses of its frames in the SEQUENCE's world (gathered
@@ -530,10 +533,7 @@ class KeyframePipeline:
 
     def ba_schedule_from(self, first):
         """the BA schedule on the built windows [first, B) only (sequence mode: the windows of the frames this rank OWNS; the ones before belong to its halo)"""
-        from . import BaBatch
-        b = BaBatch()
-        for f_, _ in BaBatch._fields_:
-            setattr(b, f_, getattr(self.ba_batch, f_))
+        b = _copy_struct(self.ba_batch)
         b.n_windows = self.B - first
         b.d_lm_off = self.ba_lm_off[first:].data_ptr(); b.d_edge_off = self.ba_e_off[first:].data_ptr()
         b.d_T_c_w = self.ba_T[first:].data_ptr(); b.d_n_kf = self.ba_nkf[first:].data_ptr()
@@ -557,9 +557,7 @@ class KeyframePipeline:
 
     def _chain_kf_frame(self):
         """the keyframe sets the last builder call wrote (None: it was the plain sliding builder, which writes none)"""
-        if self.window_policy == "reference" or self.keyframe_gate or self.pose_inputs == "map":
-            return self.ba_kf_frame.data_ptr()
-        return None
+        return self.ba_kf_frame.data_ptr() if self._builder_writes_kf else None
 
     def step(self):
         if self.rectify is not None:
@@ -588,10 +586,7 @@ class KeyframePipeline:
             for k, t in (("ba_lm_off", self.ba_lm_off), ("ba_e_off", self.ba_e_off), ("ba_nkf", self.ba_nkf), ("ba_xyz", self.ba_xyz), ("ba_rel", self.ba_rel),
                          ("ba_kf", self.ba_kf), ("ba_lm", self.ba_lm), ("ba_uv", self.ba_uv), ("ba_build_status", self.ba_build_status)):
                 out[k] = t.cpu().numpy()
-            if self.window_policy == "reference" or self.keyframe_gate:
-                out["ba_kf_frame"] = self.ba_kf_frame.cpu().numpy(); out["ba_evicted"] = self.ba_evicted.cpu().numpy()
-            else:
-                out["ba_kf_frame"], out["ba_evicted"] = self._sliding_keyframes()
+            out["ba_kf_frame"], out["ba_evicted"] = self._keyframe_sets()
             if self.seg_first is not None:
                 out["seg_first"] = self.seg_first.copy()
             if self.ba_chain:
@@ -614,6 +609,13 @@ class KeyframePipeline:
             out["T_c_w"] = self.map_G[c].cpu().numpy()
         return out
 
+    def _keyframe_sets(self):
+        """(kf_frame, evicted) of the built windows on the host.  Deliberate: pose_inputs="map" with a sliding, ungated window reports the host-side
+        sliding sets, although its builder wrote the device arrays too"""
+        if self.window_policy == "reference" or self.keyframe_gate:
+            return self.ba_kf_frame.cpu().numpy(), self.ba_evicted.cpu().numpy()
+        return self._sliding_keyframes()
+
     def _sliding_keyframes(self):
         """the sliding windows' sets on the host, per segment when the batch is segmented (batch frame indices)"""
         if self.seg_first is None:
@@ -627,10 +629,7 @@ class KeyframePipeline:
         assert self.with_ba and self.ba_windows == "tracks"
         self.vo.sync()
         torch.cuda.synchronize(self.dev)
-        if self.window_policy == "reference" or self.keyframe_gate:
-            kf_frame, evicted = self.ba_kf_frame.cpu().numpy(), self.ba_evicted.cpu().numpy()
-        else:
-            kf_frame, evicted = self._sliding_keyframes()
+        kf_frame, evicted = self._keyframe_sets()
         valid = (self.ba_frame_state.cpu().numpy() == 2) if self.keyframe_gate else None
         return kf_frame, evicted, self.ba_T.cpu().numpy(), valid
 
