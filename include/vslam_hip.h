@@ -799,7 +799,7 @@ int vslam_ba_deferred_dev(vslam_ctx* ctx, int n_windows, int32_t* h_deferred);
 int vslam_edge_jacobians(vslam_ctx* ctx, int n, const float* xyz_w, const float* uv, const double T_c_w[7], const double* K4,
                          double* err, double* J_pose, double* J_point, double* chi2, double* huber_w);
 /* Kernel-choice overrides of a context (tuning aid, and how the tests force every kernel path): name in {"orb_fuse_min", "anms_cap" (pixels at which the ANMS radius walk stops early, 0 = never; same output either way, see vslam_orb_anms_path_dev), "sgbm_fuse_min",
- * "sgbm_fwd_min" (items per call from which the fused kernel is used), "sgbm_fw_rows" (32 | 64), "pose_only_window", "pose_only_waves" (0 = automatic | 12 | 4: waves per window of the schedule's pose-only kernel; default by the number of windows in the call; same bits either way), "pnp_window", "ba_adaptive" (0 | 1), "rectify_form" (0 | 1: source side of the rectification kernel, direct gathers | source boxes staged in LDS; same bytes), "ba_lanes" (256 | 512: lanes per window of the
+ * "sgbm_fwd_min" (items per call from which the fused kernel is used), "sgbm_fw_rows" (32 | 64), "pose_only_window", "pose_only_waves" (0 = automatic | 12 | 4: waves per window of the schedule's pose-only kernel; default by the number of windows in the call; same bits either way), "pnp_window", "ba_adaptive" (0 | 1), "rectify_form" (0 | 1: source side of the rectification kernel, direct gathers | source boxes staged in LDS; same bytes), "voxel_form" (0 | 1: vslam_voxel_fuse_disparity_dev inserts every point directly | sums each image tile in LDS first; same table), "ba_lanes" (256 | 512: lanes per window of the
  * LDS-resident optimize_map kernel; default by the number of windows in the call; the results do not depend on it), "track_rule" (0 | 1: see
  * vslam_build_windows_dev; this one changes RESULTS, it is the before / after switch of round 6)};
  * value -1 = the library's batch-size rule.  vslam_create seeds them once from the environment variables VSLAM_<NAME> (an unparsable
@@ -865,6 +865,74 @@ int vslam_hbm_copy_probe(vslam_ctx* ctx, size_t bytes, int reps, double* gbs_out
  * name_out (>= 64 bytes, may be NULL) receives its description.  vslam_hbm_copy_probe reports the best of them. */
 int vslam_hbm_copy_probe_variants(void);
 int vslam_hbm_copy_probe_variant(vslam_ctx* ctx, size_t bytes, int reps, int variant, double* gbs_out, char* name_out);
+
+/* ------------------------------------------------------------------ dense map: disparities fused into a voxel grid --- */
+/* The SGBM stage computes a disparity for every pixel of every keyframe; this stage turns them, at the keyframes' poses, into a MAP: a sparse
+ * voxel grid in a device hash table.  A point list is no product at batch size (1024 keyframes hold 4.8e8 pixels), a fused, bounded structure is.
+ * Every voxel holds integers only -- a point count, the sums of the points' sub-voxel offsets (1/256 voxel) and of their 8-bit intensities -- so
+ * the table is bit-reproducible under any arrival order.  The reference has no dense map (it publishes its landmark cloud, visualization.cpp:19-74).
+ * Additive: vslam_params and the ABI version are unchanged; the host mirror (host/) does not call the stage.
+ *
+ * KEY of a point (x, y, z) in map `map_id`, with vs = (float)voxel_size and inv = 1.0f / vs, per axis in f32:
+ *   t = x * inv (rounded to f32 before anything else uses it), c = floorf(t), i = (int)c, o = min((int)((t - c) * 256.0f), 255).
+ * A point with a non-finite t, or an i outside [-2^17, 2^17), is dropped and counted (n_dropped_range).
+ *   key = map_id << 54 | (ix + 2^17) << 36 | (iy + 2^17) << 18 | (iz + 2^17),  map_id in [0, 1022] (all-ones is the empty slot).
+ * VOXEL: count, sum_ox, sum_oy, sum_oz, sum_intensity, all uint32: exact while count < 2^24 (255 * 2^24 < 2^32); an extraction that meets a larger
+ * count sets status bit 1 and that voxel's sums are void.
+ * TABLE: 2^log2_capacity slots of 32 bytes (key 8, the five sums 20, 4 unused), open addressing with linear probing over at most 128 slots.  A point
+ * that finds no slot is dropped and counted (n_dropped_full, status bit 0); which points are lost then depends on the arrival order, but
+ * sum of counts + n_dropped_full + n_dropped_range = valid points offered always holds.  Size the table for a load factor below one half. */
+typedef struct vslam_voxel_map vslam_voxel_map;
+struct vslam_voxel_stats {
+    uint64_t n_occupied;       /* occupied slots                                   */
+    uint64_t n_points;         /* points accumulated (the sum of the voxels' counts) */
+    uint64_t n_dropped_range;  /* points dropped for range                         */
+    uint64_t n_dropped_full;   /* points dropped because the table was full        */
+    uint32_t status;           /* bit 0: table full; bit 1: a voxel count reached 2^24 */
+    int32_t struct_size;       /* sizeof(struct vslam_voxel_stats) of the caller's header: set by the caller, checked */
+};
+typedef struct vslam_voxel {   /* one extracted voxel (32 bytes) */
+    int32_t ix, iy, iz;        /* voxel index per axis */
+    uint32_t count;
+    float x, y, z;             /* centroid: ((double)ix + ((double)sum_ox / count + 0.5) / 256.0) * (double)vs, cast to float; y, z likewise */
+    float intensity;           /* (float)((double)sum_intensity / count) */
+} vslam_voxel;
+
+/* A table of 2^log2_capacity slots (log2_capacity in [10, 28]) for voxels of voxel_size (finite, > 0), empty.  Its 32 << log2_capacity bytes are
+ * counted in vslam_device_bytes while the handle lives.  A map belongs to its context and is destroyed before it.  Synchronous. */
+int vslam_voxel_create(vslam_ctx* ctx, double voxel_size, int log2_capacity, vslam_voxel_map** out);
+void vslam_voxel_destroy(vslam_voxel_map* vm);
+/* empties the table and zeroes the counters and the status; asynchronous on the context stream */
+int vslam_voxel_clear(vslam_voxel_map* vm);
+/* the counters so far (host->struct_size set by the caller); synchronises the context stream */
+int vslam_voxel_stats(vslam_voxel_map* vm, struct vslam_voxel_stats* host);
+
+/* Every entry below is asynchronous on the context stream and refuses with VSLAM_ERR_ARG before it launches anything: a null pointer where one is
+ * required, B < 1 or B > max_batch, step < 1, z_min >= z_max (or either not finite), a map_id outside [0, 1022] (extraction: [-1, 1022]),
+ * w or h < 1, a pitch below w, a voxel map of another context.
+ *
+ * vslam_reproject_dev: every pixel (c, r) with c % step == 0 and r % step == 0 of B disparity maps (B x h x w f32, tightly packed) through
+ * Frame::find_3d's arithmetic for a keypoint at ((float)c, (float)r) (types_def.cpp:9-18: f64 math, f32 at rest) and the inverse of the item's pose
+ * d_T_c_w + 7 b, as vslam_find_3d_disparity_dev does; valid = z_min < Z < z_max.  Outputs B x ceil(h / step) x ceil(w / step): d_xyz f32 x 3,
+ * d_valid uint8.  The fused entry below runs the same device function: same bits. */
+int vslam_reproject_dev(vslam_ctx* ctx, const float* d_disparity, int w, int h, int B, const double* d_T_c_w, double z_min, double z_max, int step,
+                        float* d_xyz, uint8_t* d_valid);
+/* n f32 points into map map_id; d_valid (n uint8, NULL: all valid) masks points out, d_intensity (n uint8, NULL: 0) is summed per voxel.  Also the
+ * way to map the landmarks of the BA windows (vslam_ba_batch positions). */
+int vslam_voxel_insert_points_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const float* d_xyz, const uint8_t* d_valid, const uint8_t* d_intensity, size_t n,
+                                  int map_id);
+/* Reprojection and insertion in one pass, no point ever written to memory: item b's valid points (vslam_reproject_dev's) go into map d_map_id[b]
+ * (B int32; an item whose id is negative or above 1022 is skipped), their intensity the pixel of d_gray + b * img_bytes (rows of `pitch` bytes;
+ * NULL: 0).  Two forms, same table (vslam_set_tuning "voxel_form"): 0 = every point straight into the table; 1 = a workgroup sums its image tile in
+ * an LDS hash table first and adds each distinct voxel of the tile to the table once (in both, a lane first merges equal keys among its own four
+ * adjacent pixels). */
+int vslam_voxel_fuse_disparity_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
+                                   int w, int h, int B, const double* d_T_c_w, const int32_t* d_map_id, double z_min, double z_max, int step);
+/* The occupied slots with count >= min_count of map map_id (-1: every map), compacted into d_out (`capacity` vslam_voxel) and, when given, their
+ * map ids into d_map_out (`capacity` int32); *d_n_out (uint64, device) = the full count even when it exceeds `capacity`.  The order is unspecified
+ * (Map::landmarks_ is an unordered_map too): sort by (map, ix, iy, iz) to compare. */
+int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int min_count, vslam_voxel* d_out, int32_t* d_map_out, size_t capacity,
+                            uint64_t* d_n_out);
 
 /* ------------------------------------------------------------------ raw device memory helpers ---------- */
 /* For hosts without their own device allocator (the C++ mirror in host/); bench.py passes torch tensors. */

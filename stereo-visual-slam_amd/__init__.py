@@ -87,6 +87,21 @@ class TracksIn(C.Structure):
                 ("d_T_abs", C.c_void_p), ("d_carry_in", C.c_void_p), ("d_carry_out", C.c_void_p), ("carry_out_frame", C.c_int32)]
 
 
+class VoxelStats(C.Structure):
+    """struct vslam_voxel_stats: the counters of a voxel map (status bit 0: table full, bit 1: a voxel count reached 2^24)"""
+    _fields_ = [("n_occupied", C.c_uint64), ("n_points", C.c_uint64), ("n_dropped_range", C.c_uint64), ("n_dropped_full", C.c_uint64),
+                ("status", C.c_uint32), ("struct_size", C.c_int32)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_[:5]}
+
+
+# vslam_voxel (32 bytes) and the form VoxelMap.extract() returns it in: the map id in front, sorted by (map, ix, iy, iz)
+VOXEL_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("count", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4")])
+VOXEL_MAP_DTYPE = np.dtype([("map", "<i4")] + VOXEL_DTYPE.descr)
+VOXEL_MAX_MAP = 1022
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("launches", C.c_int32), ("calls", C.c_int32)]
 
@@ -180,6 +195,12 @@ SIGNATURES = {
     "vslam_build_pnp_inputs_dev": (I, [P, P, P, I, P, P, I, P, P, P, I, I, P, P, P, P, I]),
     "vslam_profile_enable": (I, [P, I]), "vslam_profile_read": (I, [P, P, I, P]), "vslam_profile_intervals": (I, [P, P, I, P]),
     "vslam_hbm_copy_probe": (I, [P, Z, I, P]), "vslam_hbm_copy_probe_variants": (I, []), "vslam_hbm_copy_probe_variant": (I, [P, Z, I, I, P, P]),
+    "vslam_voxel_create": (I, [P, D, I, C.POINTER(C.c_void_p)]), "vslam_voxel_destroy": (None, [P]), "vslam_voxel_clear": (I, [P]),
+    "vslam_voxel_stats": (I, [P, C.POINTER(VoxelStats)]),
+    "vslam_reproject_dev": (I, [P, P, I, I, I, P, D, D, I, P, P]),
+    "vslam_voxel_insert_points_dev": (I, [P, P, P, P, P, Z, I]),
+    "vslam_voxel_fuse_disparity_dev": (I, [P, P, P, P, Z, I, I, I, I, P, P, D, D, I]),
+    "vslam_voxel_extract_dev": (I, [P, P, I, I, P, P, Z, P]),
     "vslam_dev_alloc": (I, [P, Z]), "vslam_dev_free": (I, [P]), "vslam_dev_upload": (I, [P, P, P, Z]), "vslam_dev_download": (I, [P, P, P, Z]),
     "vslam_dev_memset": (I, [P, P, I, Z]),
 }
@@ -337,6 +358,8 @@ class VO:
 
     def close(self):
         if getattr(self, "h", None):
+            for vm in list(getattr(self, "_voxel_maps", ())):   # (a voxel map belongs to its context and goes first)
+                vm.close()
             self.lib.vslam_destroy(self.h)
             self.h = None
 
@@ -705,6 +728,29 @@ class VO:
         self._chk(self.lib.vslam_build_pnp_inputs_dev(self.h, d_f2f, d_nf2f, match_cap, d_lr, d_nlr, lr_cap, d_xyz_lr, d_valid_lr, d_kps_cur, kp_cap, B,
                                                       d_kp2lr, d_xyz_out, d_uv_out, d_nout, out_cap), "vslam_build_pnp_inputs_dev")
 
+    # ------------------------------------------------------------ dense map: disparities fused into a voxel grid (no counterpart in the reference)
+    def voxel_map(self, voxel_size=0.2, log2_capacity=22):
+        """an empty VoxelMap of this context: 2^log2_capacity slots of 32 bytes for voxels of voxel_size metres"""
+        return VoxelMap(self, voxel_size, log2_capacity)
+
+    def reproject_dev(self, d_disp, w, h, B, d_T, z_min, z_max, step, d_xyz, d_valid):
+        """every step-th pixel of B disparity maps through Frame::find_3d at the items' poses: B x ceil(h / step) x ceil(w / step) points and
+        their depth-gate flags (z_min < Z < z_max).  Semantics in include/vslam_hip.h."""
+        self._chk(self.lib.vslam_reproject_dev(self.h, d_disp, w, h, B, d_T, z_min, z_max, step, d_xyz, d_valid), "vslam_reproject_dev")
+
+    def voxel_insert_points_dev(self, vm, d_xyz, d_valid, d_intensity, n, map_id=0):
+        """n f32 points (d_valid / d_intensity uint8 or None) into map map_id of the VoxelMap vm"""
+        self._chk(self.lib.vslam_voxel_insert_points_dev(self.h, vm.h, d_xyz, d_valid, d_intensity, n, map_id), "vslam_voxel_insert_points_dev")
+
+    def voxel_fuse_disparity_dev(self, vm, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step=1):
+        """reproject_dev + voxel_insert_points_dev in one pass: item b's valid points into map d_map_id[b] (< 0: skipped), intensity from d_gray (None: 0)"""
+        self._chk(self.lib.vslam_voxel_fuse_disparity_dev(self.h, vm.h, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step),
+                  "vslam_voxel_fuse_disparity_dev")
+
+    def voxel_extract_dev(self, vm, map_id, min_count, d_out, d_map_out, capacity, d_n_out):
+        """the occupied voxels with count >= min_count of map map_id (-1: all) into d_out (capacity x 32 bytes) / d_map_out; d_n_out (uint64): the full count"""
+        self._chk(self.lib.vslam_voxel_extract_dev(self.h, vm.h, map_id, min_count, d_out, d_map_out, capacity, d_n_out), "vslam_voxel_extract_dev")
+
     def profile_enable(self, on=True):
         self._chk(self.lib.vslam_profile_enable(self.h, on), "vslam_profile_enable")
 
@@ -763,3 +809,58 @@ class VO:
         st = np.zeros(n_windows, np.int32)
         self._chk(self.lib.vslam_ba_schedule_passes_dev(self.h, n_windows, st), "vslam_ba_schedule_passes_dev")
         return st
+
+
+class VoxelMap:
+    """A sparse voxel grid in a device hash table (include/vslam_hip.h "dense map"): per voxel a point count, the sums of the points' sub-voxel
+    offsets and of their intensities, all integers, so the table does not depend on the order its points arrived in.  Filled through
+    VO.voxel_insert_points_dev / VO.voxel_fuse_disparity_dev (or KeyframePipeline.dense_map); belongs to the VO it was created on."""
+
+    def __init__(self, vo, voxel_size=0.2, log2_capacity=22):
+        self.vo, self.voxel_size, self.log2_capacity = vo, float(voxel_size), int(log2_capacity)
+        h = C.c_void_p()
+        vo._chk(vo.lib.vslam_voxel_create(vo.h, voxel_size, log2_capacity, C.byref(h)), "vslam_voxel_create")
+        self.h = h
+        if not hasattr(vo, "_voxel_maps"):
+            vo._voxel_maps = []
+        vo._voxel_maps.append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.vo.lib.vslam_voxel_destroy(self.h)
+            self.h = None
+            self.vo._voxel_maps.remove(self)
+
+    def clear(self):
+        """empty table, zero counters; asynchronous on the context stream"""
+        self.vo._chk(self.vo.lib.vslam_voxel_clear(self.h), "vslam_voxel_clear")
+
+    def stats(self):
+        """{n_occupied, n_points, n_dropped_range, n_dropped_full, status}; synchronises"""
+        st = VoxelStats(); st.struct_size = C.sizeof(VoxelStats)
+        self.vo._chk(self.vo.lib.vslam_voxel_stats(self.h, C.byref(st)), "vslam_voxel_stats")
+        return st.as_dict()
+
+    def extract(self, map_id=-1, min_count=1, capacity=None, sort=True):
+        """the voxels with count >= min_count of map map_id (-1: every map) as a VOXEL_MAP_DTYPE array sorted by (map, ix, iy, iz) -- the canonical
+        form for comparisons.  capacity: rows of the device buffer (None: the occupied slots); the call returns at most that many, in the table's
+        order when the count exceeds it (self.last_count holds the full count)."""
+        import torch
+        vo = self.vo
+        if capacity is None:
+            capacity = max(self.stats()["n_occupied"], 1)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_out = torch.zeros((capacity, 32), dtype=torch.uint8, device=dev)
+        d_map = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
+        vo.voxel_extract_dev(self, map_id, min_count, d_out.data_ptr(), d_map.data_ptr(), capacity, d_n.data_ptr())
+        vo.sync()
+        self.last_count = int(d_n.cpu()[0])
+        n = min(self.last_count, capacity)
+        v = d_out[:n].cpu().numpy().reshape(-1).view(VOXEL_DTYPE)
+        out = np.zeros(n, VOXEL_MAP_DTYPE)
+        out["map"] = d_map[:n].cpu().numpy()
+        for f in VOXEL_DTYPE.names:
+            out[f] = v[f]
+        return out[np.lexsort((out["iz"], out["iy"], out["ix"], out["map"]))] if sort else out

@@ -127,6 +127,7 @@ static const TuneKey kTuneKeys[] = {
     {"ba_lanes", "VSLAM_BA_LANES", &Tuning::ba_lanes, 256, 512},
     {"track_rule", "VSLAM_TRACK_RULE", &Tuning::track_rule, 0, 1},
     {"rectify_form", "VSLAM_RECTIFY_FORM", &Tuning::rectify_form, 0, 1},
+    {"voxel_form", "VSLAM_VOXEL_FORM", &Tuning::voxel_form, 0, 1},
 };
 static int tune_set(Tuning& t, const TuneKey& k, long v) {
     if (v == -1) { t.*(k.field) = -1; return VSLAM_OK; } // back to the library's rule
@@ -236,7 +237,8 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
-           "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels";
+           "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
+           "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -1681,6 +1683,129 @@ int vslam_build_pnp_inputs_dev(vslam_ctx* ctx, const vslam_dmatch* d_f2f, const 
     VS_ENTER(c);
     return launch_build_pnp_inputs(d_f2f, d_nf2f, match_capacity, d_lr, d_nlr, lr_capacity, d_xyz_lr, d_valid_lr, d_kps_cur, kp_capacity, B,
                                    d_kp2lr, d_xyz_out, d_uv_out, d_nout, out_capacity, c->stream, c->seg.start);
+}
+
+// ---------------------------------------------------------------------------------------------- dense map
+// Form of voxel_fuse_kernel: 0 = every point straight into the global table, 1 = tile sums in LDS first; Tuning::voxel_form overrides
+// it (tests and tools/bench_voxel.py run both)
+constexpr int kVoxelFormDefault = 1;
+static int voxel_form(const Ctx* c) { return c->tune.voxel_form >= 0 ? c->tune.voxel_form : kVoxelFormDefault; }
+
+int vslam_voxel_create(vslam_ctx* ctx, double voxel_size, int log2_capacity, vslam_voxel_map** out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !out) { set_error("vslam_voxel_create: null argument"); return VSLAM_ERR_ARG; }
+    *out = nullptr;
+    const float vs = (float)voxel_size;
+    if (!std::isfinite(voxel_size) || !(voxel_size > 0) || !std::isfinite(vs) || !(vs > 0.f) || !std::isfinite(1.0f / vs)) {
+        set_error("vslam_voxel_create: voxel_size %g is not a finite positive float", voxel_size); return VSLAM_ERR_ARG;
+    }
+    if (log2_capacity < 10 || log2_capacity > 28) { set_error("vslam_voxel_create: log2_capacity %d outside [10, 28]", log2_capacity); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    VoxelMap* m = new VoxelMap();
+    m->ctx = c; m->bytes = ((size_t)32 << log2_capacity) + sizeof(unsigned long long) * kVoxelCounters;
+    m->t.log2_capacity = log2_capacity; m->t.vs = vs; m->t.inv = 1.0f / vs;
+    if (hipMalloc((void**)&m->t.slots, m->bytes) != hipSuccess) { set_error("vslam_voxel_create: hipMalloc(%zu) failed", m->bytes); delete m; return VSLAM_ERR_HIP; }
+    m->t.counters = reinterpret_cast<unsigned long long*>(m->t.slots + ((size_t)32 << log2_capacity));
+    c->dev_bytes += m->bytes;
+    int rc = launch_voxel_clear(m->t, c->stream);
+    if (rc == VSLAM_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("vslam_voxel_create: clearing the table failed"); rc = VSLAM_ERR_HIP; }
+    if (rc) { vslam_voxel_destroy(reinterpret_cast<vslam_voxel_map*>(m)); return rc; }
+    *out = reinterpret_cast<vslam_voxel_map*>(m);
+    return VSLAM_OK;
+}
+
+void vslam_voxel_destroy(vslam_voxel_map* vm) {
+    VoxelMap* m = reinterpret_cast<VoxelMap*>(vm);
+    if (!m) return;
+    hipSetDevice(m->ctx->device);
+    hipStreamSynchronize(m->ctx->stream);
+    hipFree(m->t.slots);
+    m->ctx->dev_bytes -= m->bytes;
+    delete m;
+}
+
+int vslam_voxel_clear(vslam_voxel_map* vm) {
+    VoxelMap* m = reinterpret_cast<VoxelMap*>(vm);
+    if (!m) { set_error("vslam_voxel_clear: null map"); return VSLAM_ERR_ARG; }
+    VS_ENTER(m->ctx);
+    return launch_voxel_clear(m->t, m->ctx->stream);
+}
+
+int vslam_voxel_stats(vslam_voxel_map* vm, struct vslam_voxel_stats* host) {
+    VoxelMap* m = reinterpret_cast<VoxelMap*>(vm);
+    if (!m || !host || host->struct_size != (int32_t)sizeof(struct vslam_voxel_stats)) { set_error("vslam_voxel_stats: null argument or struct_size mismatch"); return VSLAM_ERR_ARG; }
+    VS_ENTER(m->ctx);
+    unsigned long long w[kVoxelCounters];
+    VS_HIP(hipMemcpyAsync(w, m->t.counters, sizeof(w), hipMemcpyDeviceToHost, m->ctx->stream));
+    VS_HIP(hipStreamSynchronize(m->ctx->stream));
+    host->n_occupied = w[0]; host->n_points = w[1]; host->n_dropped_range = w[2]; host->n_dropped_full = w[3]; host->status = (uint32_t)w[4];
+    return VSLAM_OK;
+}
+
+// the checks the image entries share; fills `a` from the context's camera
+static int voxel_images(const Ctx* c, const char* who, const float* d_disparity, int w, int h, int B, const double* d_T_c_w, double z_min, double z_max, int step,
+                        VoxelImages& a) {
+    if (!d_disparity || !d_T_c_w) { set_error("%s: null pointer", who); return VSLAM_ERR_ARG; }
+    if (B < 1 || B > c->p.max_batch || B > 65535) { set_error("%s: batch %d outside 1..max_batch %d", who, B, c->p.max_batch); return VSLAM_ERR_ARG; }
+    if (w < 1 || h < 1 || step < 1) { set_error("%s: w %d, h %d and step %d must be >= 1", who, w, h, step); return VSLAM_ERR_ARG; }
+    if (!std::isfinite(z_min) || !std::isfinite(z_max) || !(z_min < z_max)) { set_error("%s: the depth gate needs finite z_min < z_max (%g, %g)", who, z_min, z_max); return VSLAM_ERR_ARG; }
+    if (((size_t)h + step - 1) / step / 16 + 1 > 65535) { set_error("%s: %d rows exceed the launch grid", who, h); return VSLAM_ERR_ARG; }
+    a.disp = d_disparity; a.w = w; a.h = h; a.B = B; a.step = step; a.T = d_T_c_w; a.z_min = z_min; a.z_max = z_max;
+    a.fx = c->p.cam[0]; a.fy = c->p.cam[1]; a.cx = c->p.cam[2]; a.cy = c->p.cam[3]; a.b = c->p.cam[4];
+    return VSLAM_OK;
+}
+
+int vslam_reproject_dev(vslam_ctx* ctx, const float* d_disparity, int w, int h, int B, const double* d_T_c_w, double z_min, double z_max, int step,
+                        float* d_xyz, uint8_t* d_valid) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !d_xyz || !d_valid) { set_error("vslam_reproject_dev: null argument"); return VSLAM_ERR_ARG; }
+    VoxelImages a;
+    if (int rc = voxel_images(c, "vslam_reproject_dev", d_disparity, w, h, B, d_T_c_w, z_min, z_max, step, a)) return rc;
+    VS_ENTER(c);
+    return launch_reproject(a, d_xyz, d_valid, c->stream);
+}
+
+static VoxelMap* voxel_map_of(const Ctx* c, vslam_voxel_map* vm, const char* who) {
+    VoxelMap* m = reinterpret_cast<VoxelMap*>(vm);
+    if (!c || !m || m->ctx != c) { set_error("%s: null context or map, or a map of another context", who); return nullptr; }
+    return m;
+}
+
+int vslam_voxel_insert_points_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const float* d_xyz, const uint8_t* d_valid, const uint8_t* d_intensity, size_t n,
+                                  int map_id) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    VoxelMap* m = voxel_map_of(c, vm, "vslam_voxel_insert_points_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (n > 0 && !d_xyz) { set_error("vslam_voxel_insert_points_dev: null d_xyz"); return VSLAM_ERR_ARG; }
+    if (map_id < 0 || map_id > kVoxelMaxMap) { set_error("vslam_voxel_insert_points_dev: map_id %d outside [0, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_voxel_insert_points(m->t, d_xyz, d_valid, d_intensity, n, map_id, c->stream);
+}
+
+int vslam_voxel_fuse_disparity_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
+                                   int w, int h, int B, const double* d_T_c_w, const int32_t* d_map_id, double z_min, double z_max, int step) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    VoxelMap* m = voxel_map_of(c, vm, "vslam_voxel_fuse_disparity_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!d_map_id) { set_error("vslam_voxel_fuse_disparity_dev: null d_map_id"); return VSLAM_ERR_ARG; }
+    VoxelImages a;
+    if (int rc = voxel_images(c, "vslam_voxel_fuse_disparity_dev", d_disparity, w, h, B, d_T_c_w, z_min, z_max, step, a)) return rc;
+    if (d_gray && (pitch < w || img_bytes < (size_t)pitch * h)) {
+        set_error("vslam_voxel_fuse_disparity_dev: pitch %d / img_bytes %zu do not hold a %d x %d image", pitch, img_bytes, w, h); return VSLAM_ERR_ARG;
+    }
+    VS_ENTER(c);
+    return launch_voxel_fuse(m->t, a, d_gray, img_bytes, pitch, d_map_id, voxel_form(c), c->stream);
+}
+
+int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int min_count, vslam_voxel* d_out, int32_t* d_map_out, size_t capacity,
+                            uint64_t* d_n_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    VoxelMap* m = voxel_map_of(c, vm, "vslam_voxel_extract_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!d_n_out || (capacity > 0 && !d_out)) { set_error("vslam_voxel_extract_dev: null d_n_out, or null d_out with a capacity"); return VSLAM_ERR_ARG; }
+    if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_voxel_extract_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_voxel_extract(m->t, map_id, min_count, d_out, d_map_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
 }
 
 // float4 streaming copy of `bytes` (src -> dst, both allocated here), `reps` timed launches after one warm-up, hipEvents on the

@@ -257,6 +257,7 @@ struct Tuning {
                               // is judged by the pose stage's inlier rule on its landmark's map position (:260-270, :277).  0 = the convention of rounds 4-5: only when the
                               // last-frame keypoint owns a valid depth (kept for before / after measurements)
     int rectify_form = -1;    // VSLAM_RECTIFY_FORM: source side of rectify_kernel -- 0 = direct byte gathers, 1 = each tile's source box staged in LDS (default 1; tiles whose box does not pay gather either way)
+    int voxel_form = -1;      // VSLAM_VOXEL_FORM: voxel_fuse_kernel -- 0 = every point straight into the global table, 1 = a workgroup sums its image tile in an LDS hash table first (same table either way)
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
 };
 // scratch: the context's SGBM buffer.  Its first 256-byte slot is a header of int32 words: the forward sweep's ticket pools, then its error word.
@@ -399,6 +400,24 @@ struct RectifyLaunch { const uint2* map[2]; const int4* tiles[2]; const uint8_t*
                        size_t src_img_bytes, dst_img_bytes; };
 int launch_rectify(const RectifyLaunch& L, hipStream_t stream);
 struct RectifyState { uint2* d_map[2]; int4* d_tiles[2]; int src_w[2], src_h[2]; };  // the two maps of a context (null until set), counted in dev_bytes
+
+// ----------------------------------------------------------------------------------------------- dense map
+// voxel_kernels.hip: disparity maps reprojected at their keyframes' poses and summed into a sparse voxel grid (include/vslam_hip.h "dense map").
+// A slot is 32 bytes: the key, then count / sum_ox / sum_oy / sum_oz / sum_intensity as uint32 and 4 unused bytes.
+constexpr int kVoxelMaxMap = 1022;       // map ids 0 .. 1022: the key's top ten bits, all-ones left to the empty slot
+constexpr int kVoxelCounters = 8;        // uint64 words behind a table: occupied, points, dropped for range, dropped full, status (the rest unused)
+struct VoxelTable { uint8_t* slots; unsigned long long* counters; int log2_capacity; float vs, inv; };
+struct VoxelMap { Ctx* ctx; VoxelTable t; size_t bytes; };
+// B disparity maps (B x h x w f32, tightly packed), their poses (B x 7) and the pixels wanted: every step-th column and row, depth gate (z_min, z_max)
+struct VoxelImages { const float* disp; int w, h, B, step; const double* T; double z_min, z_max, fx, fy, cx, cy, b; };
+int launch_voxel_clear(const VoxelTable& t, hipStream_t stream);
+int launch_reproject(const VoxelImages& a, float* d_xyz, uint8_t* d_valid, hipStream_t stream);
+int launch_voxel_insert_points(const VoxelTable& t, const float* d_xyz, const uint8_t* d_valid, const uint8_t* d_intensity, size_t n, int map_id, hipStream_t stream);
+// form: 0 = direct insertion, 1 = tile sums in LDS first
+int launch_voxel_fuse(const VoxelTable& t, const VoxelImages& a, const uint8_t* d_gray, size_t img_bytes, int pitch, const int32_t* d_map_id, int form,
+                      hipStream_t stream);
+int launch_voxel_extract(const VoxelTable& t, int map_id, int min_count, vslam_voxel* d_out, int32_t* d_map_out, size_t capacity, unsigned long long* d_n_out,
+                         hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {

@@ -19,6 +19,7 @@ import torch
 
 from . import BaBatch, DMATCH_DTYPE, KEYPOINT_DTYPE, TracksIn, VO, _sgbm_params, default_params, sgbm_params_check
 from . import synth
+from .dense import write_ply  # noqa: F401  (re-exported)
 from .trajectory import assemble_trajectories, assemble_trajectory, sliding_keyframes, write_trajectory  # noqa: F401  (re-exported)
 
 
@@ -648,6 +649,40 @@ class KeyframePipeline:
         assert self.seg_first is None, "a segmented pipeline has one trajectory per segment: use trajectories()"
         kf_frame, evicted, ba_T, valid = self._trajectory_inputs()
         return assemble_trajectory(kf_frame, evicted, ba_T, window_valid=valid)
+
+    def dense_map_inputs(self):
+        """what dense_map() fuses: (T_c_w (B, 7) float64, map_id (B,) int32) -- every frame of trajectories() at its BA-refined pose with its segment's
+        index (0 without a segment table) as map id; a frame outside the trajectories has map id -1 and the identity pose"""
+        trajs = self.trajectories()
+        assert len(trajs) <= 1023, "a voxel map holds at most 1023 maps (segments)"
+        first = self.seg_first if self.seg_first is not None else np.array([0, self.B])
+        T = np.tile(np.array([0, 0, 0, 1, 0, 0, 0], np.float64), (self.B, 1))
+        map_id = np.full(self.B, -1, np.int32)
+        for s_, (ids, Ts) in enumerate(trajs):
+            T[first[s_] + ids] = Ts
+            map_id[first[s_] + ids] = s_
+        return T, map_id
+
+    def dense_map(self, voxel_size=0.2, log2_capacity=22, z_min=None, z_max=None, step=1, voxel_map=None):
+        """The dense map of the last step (depth="sgbm", ba_windows="tracks"): the SGBM disparity and the left image of every frame trajectories()
+        returns, reprojected at that frame's BA-refined pose and fused into a VoxelMap (vslam_voxel_fuse_disparity_dev) -- map id = the segment index.
+        z_min / z_max default to the context's depth_min / depth_reliable (the reference trusts stereo depth below 40 m only); every step-th pixel.
+        voxel_map: a VoxelMap of this pipeline's context to accumulate into over several steps (voxel_size / log2_capacity then go unused); otherwise
+        a new one.  Returns the map: .extract() / .stats() read it, write_ply(path, vm.extract()) writes it."""
+        assert self.depth == "sgbm", "dense_map needs depth='sgbm': it fuses the SGBM disparity maps"
+        assert self.with_ba and self.ba_windows == "tracks", "dense_map needs ba_windows='tracks': the poses are the BA windows'"
+        T, map_id = self.dense_map_inputs()   # (synchronises: the step is complete)
+        p = self.vo.params
+        z_min = p.depth_min if z_min is None else float(z_min)
+        z_max = p.depth_reliable if z_max is None else float(z_max)
+        vm = voxel_map if voxel_map is not None else self.vo.voxel_map(voxel_size, log2_capacity)
+        assert vm.vo is self.vo, "voxel_map belongs to another context"
+        with torch.cuda.stream(self.stream):
+            self.dense_T = torch.from_numpy(T).to(self.dev)
+            self.dense_map_id = torch.from_numpy(map_id).to(self.dev)
+        self.vo.voxel_fuse_disparity_dev(vm, self.d_disp.data_ptr(), self.d_imgs.data_ptr(), self.img_bytes, self.pitch, self.w, self.h, self.B,
+                                         self.dense_T.data_ptr(), self.dense_map_id.data_ptr(), z_min, z_max, int(step))
+        return vm
 
     def close(self):
         self.vo.close()
