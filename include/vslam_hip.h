@@ -934,6 +934,72 @@ int vslam_voxel_fuse_disparity_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const fl
 int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int min_count, vslam_voxel* d_out, int32_t* d_map_out, size_t capacity,
                             uint64_t* d_n_out);
 
+/* ------------------------------------------------------------------ place database: loop-closure candidates and verified edges --- */
+/* Noticing that the camera is back at a place it has seen: keyframe descriptor blocks are kept in a database that outlives the steps (loops close
+ * over thousands of frames, a batch holds max_batch), every query entry is scored against every earlier entry of its sequence by brute force over the
+ * raw descriptors on the matrix cores -- no vocabulary, nothing trained -- and the best candidates are verified with the library's own matcher and
+ * RANSAC pose stage, which also yields the relative pose a pose-graph back end wants.  The reference has no loop closure.  Additive: vslam_params and
+ * the ABI version are unchanged; the host mirror (host/) does not call the stage.
+ *
+ * SCORE of query entry i (descriptor rows D_i, n_i of them) against entry j, all integer, hence exact and independent of arrival order:
+ *   score(i, j) = #{ r < n_i : min_c hamming(D_i[r], D_j[c]) <= tau }      (asymmetric; 0 when n_j = 0)
+ * The pair is ELIGIBLE when seq_j == seq_i and frame_j <= frame_i - min_gap; a pair that is not eligible scores -1 and costs no matrix work.
+ * ENTRY: rows_per_entry R <= 4096 (the matcher's row limit); its first min(n, R) descriptor rows at a stride of R rounded up to 32 rows (every block
+ * 16-byte aligned, the matcher's contract), seq, frame and, with geometry, per keypoint row the pixel (x, y of vslam_keypoint), the camera-frame point,
+ * its valid flag, and the ascending list of the rows that own a valid point (the d_qsel / d_nqsel of vslam_feature_matching_pairs_dev).  Entry ids are
+ * dense and ascending in the order of the adds. */
+typedef struct vslam_place_db vslam_place_db;
+struct vslam_place_stats {
+    int32_t n_entries;         /* entries held                                      */
+    int32_t capacity;          /* entries the database can hold                     */
+    int32_t rows_per_entry;    /* R                                                 */
+    int32_t with_geometry;     /* 1 when pixels / points / valid rows are kept      */
+    uint64_t n_refused;        /* vslam_place_add_dev calls refused for lack of room */
+    int32_t struct_size;       /* sizeof(struct vslam_place_stats) of the caller's header: set by the caller, checked */
+};
+/* An empty database of capacity_entries (>= 1) entries of rows_per_entry (1 .. 4096) rows.  Its bytes are counted in vslam_device_bytes while the
+ * handle lives.  A database belongs to its context and is destroyed before it.  Synchronous. */
+int vslam_place_create(vslam_ctx* ctx, int rows_per_entry, int capacity_entries, int with_geometry, vslam_place_db** out);
+void vslam_place_destroy(vslam_place_db* db);
+/* forgets every entry and zeroes the refusal counter (host bookkeeping only: nothing on the device is read before it is written again) */
+int vslam_place_clear(vslam_place_db* db);
+int vslam_place_stats(vslam_place_db* db, struct vslam_place_stats* host);
+/* Entry `entry` as the database holds it, into host buffers (diagnostic, and the way to persist a database; synchronises the context stream):
+ * meta[4] = {n, seq, frame, valid rows (0 without geometry)}; desc (R x 32 bytes; rows at or past n are zero); with geometry also xy (R x 2 f32),
+ * xyz (R x 3 f32), valid (R uint8) and qsel (R int32, the first meta[3] defined).  Every buffer but meta may be NULL: not wanted. */
+int vslam_place_read_entry(vslam_place_db* db, int entry, int32_t* meta, uint8_t* desc, float* xy, float* xyz, uint8_t* valid, int32_t* qsel);
+/* n, seq and frame (count int32 each, host; any may be NULL) of entries [first, first + count); synchronises the context stream */
+int vslam_place_read_meta(vslam_place_db* db, int first, int count, int32_t* n, int32_t* seq, int32_t* frame);
+
+/* Every entry below refuses with VSLAM_ERR_ARG and a message before it launches anything: a null pointer where one is required, a range outside the
+ * entries held, ld below the number of entries, a database of another context.
+ *
+ * vslam_place_add_dev: appends item b of a batch (B >= 1) when d_add[b] != 0 (d_add NULL: every item), in ascending b: the first min(d_n[b], R) rows of
+ * d_desc + b * desc_stride_bytes (both multiples of 16 bytes), d_seq[b] and d_frame[b]; with geometry also d_kps / d_xyz (x 3) / d_valid at
+ * [b * kp_capacity, ...), all required then (rows at or past kp_capacity own no point).  *first_entry (may be NULL) = the id of the first entry added
+ * (the entry count when none was).  An add that does not fit adds NOTHING: VSLAM_ERR_CAPACITY, counted in n_refused.  The call reads d_add on the host
+ * (it synchronises the context stream); the copies are asynchronous on it. */
+int vslam_place_add_dev(vslam_ctx* ctx, vslam_place_db* db, const uint8_t* d_desc, size_t desc_stride_bytes, const int32_t* d_n, const int32_t* d_add,
+                        const int32_t* d_seq, const int32_t* d_frame, const vslam_keypoint* d_kps, const float* d_xyz, const uint8_t* d_valid, int kp_capacity,
+                        int B, int* first_entry);
+/* d_score (nq x ld int32, ld >= the entry count; columns at or past the entry count are not touched): the score of query entries [q0, q0 + nq),
+ * nq in 1 .. 65535, against every entry, tau in [0, 255].  Asynchronous; the same call twice writes the same bytes. */
+int vslam_place_score_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, int tau, int min_gap, int32_t* d_score, int ld);
+/* Per query of a score table the K (1 .. 8) eligible entries with the highest score that reach min_score, into d_cand / d_cand_score (nq x K int32):
+ * descending score, ties to the smaller entry id; unused slots -1 / 0. */
+int vslam_place_select_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, const int32_t* d_score, int ld, int K, int min_score, int32_t* d_cand,
+                           int32_t* d_cand_score);
+/* Geometric verification of query b's (entry q0 + b, nq <= max_batch) rank-`rank` candidate c = d_cand[b * K + rank] on a database with geometry:
+ * (1) vslam_feature_matching_pairs_dev with entry c's block and its valid rows as the query side (d_qitem[b] = c), entry q0 + b's descriptors as the
+ * train side, gate = 1 at gap 1.0; (2) a gather, in match order, of (point of c at queryIdx, pixel of entry q0 + b at trainIdx); (3)
+ * vslam_pnp_ransac_dev with the context's pnp_reproj_thr, 100 iterations, confidence 0.99 (visual_odometry.cpp:277).  d_T_q_c (nq x 7) is that call's
+ * T_c_w with "world" = candidate c's camera: the relative pose of a loop edge.  d_n_matches / d_n_inliers (nq int32).  An edge is ACCEPTED when
+ * n_inliers >= min_inliers (>= 0; 10 is VO::check_motion_estimation's minimum, visual_odometry.cpp:319; its relative-motion limit does not apply to a
+ * loop edge).  A query without a candidate (-1) gives identity / 0 / 0; one with fewer matches than min_inliers cannot be accepted and is not handed
+ * to RANSAC: identity, its match count, 0 inliers.  Asynchronous; uses the context's matcher and RANSAC scratch. */
+int vslam_place_verify_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, const int32_t* d_cand, int K, int rank, int min_inliers, double* d_T_q_c,
+                           int32_t* d_n_matches, int32_t* d_n_inliers);
+
 /* ------------------------------------------------------------------ raw device memory helpers ---------- */
 /* For hosts without their own device allocator (the C++ mirror in host/); bench.py passes torch tensors. */
 int vslam_dev_alloc(void** p, size_t bytes);

@@ -102,6 +102,20 @@ VOXEL_MAP_DTYPE = np.dtype([("map", "<i4")] + VOXEL_DTYPE.descr)
 VOXEL_MAX_MAP = 1022
 
 
+class PlaceStats(C.Structure):
+    """struct vslam_place_stats: entries held, capacity, rows per entry, geometry flag and the adds refused for lack of room"""
+    _fields_ = [("n_entries", C.c_int32), ("capacity", C.c_int32), ("rows_per_entry", C.c_int32), ("with_geometry", C.c_int32),
+                ("n_refused", C.c_uint64), ("struct_size", C.c_int32)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_[:5]}
+
+
+# the rows KeyframePipeline.loop_closures returns: one per (query entry, candidate)
+LOOP_EDGE_DTYPE = np.dtype([("entry_q", "<i4"), ("entry_c", "<i4"), ("seq", "<i4"), ("frame_q", "<i4"), ("frame_c", "<i4"), ("score", "<i4"),
+                            ("n_matches", "<i4"), ("n_inliers", "<i4"), ("accepted", "?"), ("T_q_c", "<f8", (7,))])
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("launches", C.c_int32), ("calls", C.c_int32)]
 
@@ -201,6 +215,14 @@ SIGNATURES = {
     "vslam_voxel_insert_points_dev": (I, [P, P, P, P, P, Z, I]),
     "vslam_voxel_fuse_disparity_dev": (I, [P, P, P, P, Z, I, I, I, I, P, P, D, D, I]),
     "vslam_voxel_extract_dev": (I, [P, P, I, I, P, P, Z, P]),
+    "vslam_place_create": (I, [P, I, I, I, C.POINTER(C.c_void_p)]), "vslam_place_destroy": (None, [P]), "vslam_place_clear": (I, [P]),
+    "vslam_place_stats": (I, [P, C.POINTER(PlaceStats)]),
+    "vslam_place_read_entry": (I, [P, I, P, P, P, P, P, P]),
+    "vslam_place_read_meta": (I, [P, I, I, P, P, P]),
+    "vslam_place_add_dev": (I, [P, P, P, Z, P, P, P, P, P, P, P, I, I, P]),
+    "vslam_place_score_dev": (I, [P, P, I, I, I, I, P, I]),
+    "vslam_place_select_dev": (I, [P, P, I, I, P, I, I, I, P, P]),
+    "vslam_place_verify_dev": (I, [P, P, I, I, P, I, I, I, P, P, P]),
     "vslam_dev_alloc": (I, [P, Z]), "vslam_dev_free": (I, [P]), "vslam_dev_upload": (I, [P, P, P, Z]), "vslam_dev_download": (I, [P, P, P, Z]),
     "vslam_dev_memset": (I, [P, P, I, Z]),
 }
@@ -358,7 +380,7 @@ class VO:
 
     def close(self):
         if getattr(self, "h", None):
-            for vm in list(getattr(self, "_voxel_maps", ())):   # (a voxel map belongs to its context and goes first)
+            for vm in list(getattr(self, "_voxel_maps", ())) + list(getattr(self, "_place_dbs", ())):   # (they belong to the context and go first)
                 vm.close()
             self.lib.vslam_destroy(self.h)
             self.h = None
@@ -751,6 +773,31 @@ class VO:
         """the occupied voxels with count >= min_count of map map_id (-1: all) into d_out (capacity x 32 bytes) / d_map_out; d_n_out (uint64): the full count"""
         self._chk(self.lib.vslam_voxel_extract_dev(self.h, vm.h, map_id, min_count, d_out, d_map_out, capacity, d_n_out), "vslam_voxel_extract_dev")
 
+    # ------------------------------------------------------------ loop closure: place database, score, candidates, verified edges (no counterpart in the reference)
+    def place_db(self, rows=None, capacity=4096, with_geometry=True):
+        """an empty PlaceDB of this context: `capacity` entries of `rows` descriptor rows (None: the context's anms_num)"""
+        return PlaceDB(self, int(self.params.anms_num if rows is None else rows), capacity, with_geometry)
+
+    def place_add_dev(self, db, d_desc, desc_stride, d_n, d_add, d_seq, d_frame, d_kps, d_xyz, d_valid, kp_capacity, B):
+        """append the items of a batch whose d_add is non-zero (None: all); returns the id of the first entry added.  Semantics in include/vslam_hip.h."""
+        first = C.c_int(-1)
+        self._chk(self.lib.vslam_place_add_dev(self.h, db.h, d_desc, desc_stride, d_n, d_add, d_seq, d_frame, d_kps, d_xyz, d_valid, kp_capacity, B,
+                                               C.byref(first)), "vslam_place_add_dev")
+        return first.value
+
+    def place_score_dev(self, db, q0, nq, tau, min_gap, d_score, ld):
+        """the nq x n_entries place-score table (int32, row stride ld) of query entries [q0, q0 + nq): -1 where the pair is not eligible"""
+        self._chk(self.lib.vslam_place_score_dev(self.h, db.h, q0, nq, tau, min_gap, d_score, ld), "vslam_place_score_dev")
+
+    def place_select_dev(self, db, q0, nq, d_score, ld, K, min_score, d_cand, d_cand_score):
+        """per query the K best eligible entries that reach min_score (descending score, ties to the smaller id; -1 / 0 unused)"""
+        self._chk(self.lib.vslam_place_select_dev(self.h, db.h, q0, nq, d_score, ld, K, min_score, d_cand, d_cand_score), "vslam_place_select_dev")
+
+    def place_verify_dev(self, db, q0, nq, d_cand, K, rank, min_inliers, d_T_q_c, d_n_matches, d_n_inliers):
+        """matcher + gather + RANSAC pose of every query's rank-`rank` candidate: relative pose, match and inlier counts"""
+        self._chk(self.lib.vslam_place_verify_dev(self.h, db.h, q0, nq, d_cand, K, rank, min_inliers, d_T_q_c, d_n_matches, d_n_inliers),
+                  "vslam_place_verify_dev")
+
     def profile_enable(self, on=True):
         self._chk(self.lib.vslam_profile_enable(self.h, on), "vslam_profile_enable")
 
@@ -864,3 +911,87 @@ class VoxelMap:
         for f in VOXEL_DTYPE.names:
             out[f] = v[f]
         return out[np.lexsort((out["iz"], out["iy"], out["ix"], out["map"]))] if sort else out
+
+
+class PlaceDB:
+    """A database of keyframe descriptor blocks that outlives the steps (include/vslam_hip.h "place database"): entries are appended by
+    VO.place_add_dev, scored against each other by brute force on the matrix cores (VO.place_score_dev), and the best candidates verified with the
+    matcher and the RANSAC pose stage (VO.place_verify_dev).  KeyframePipeline.loop_closures drives all of it; belongs to the VO it was created on."""
+
+    def __init__(self, vo, rows, capacity=4096, with_geometry=True):
+        self.vo, self.rows, self.capacity, self.with_geometry = vo, int(rows), int(capacity), bool(with_geometry)
+        h = C.c_void_p()
+        vo._chk(vo.lib.vslam_place_create(vo.h, self.rows, self.capacity, int(self.with_geometry), C.byref(h)), "vslam_place_create")
+        self.h = h
+        if not hasattr(vo, "_place_dbs"):
+            vo._place_dbs = []
+        vo._place_dbs.append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.vo.lib.vslam_place_destroy(self.h)
+            self.h = None
+            self.vo._place_dbs.remove(self)
+
+    def clear(self):
+        """forget every entry and zero the refusal counter"""
+        self.vo._chk(self.vo.lib.vslam_place_clear(self.h), "vslam_place_clear")
+
+    def stats(self):
+        """{n_entries, capacity, rows_per_entry, with_geometry, n_refused}"""
+        st = PlaceStats(); st.struct_size = C.sizeof(PlaceStats)
+        self.vo._chk(self.vo.lib.vslam_place_stats(self.h, C.byref(st)), "vslam_place_stats")
+        return st.as_dict()
+
+    def __len__(self):
+        return self.stats()["n_entries"]
+
+    def meta(self, first=0, count=None):
+        """(n, seq, frame) int32 arrays of entries [first, first + count) (count None: to the last entry); synchronises"""
+        count = len(self) - first if count is None else count
+        n = np.zeros(count, np.int32); seq = np.zeros(count, np.int32); frame = np.zeros(count, np.int32)
+        self.vo._chk(self.vo.lib.vslam_place_read_meta(self.h, first, count, n, seq, frame), "vslam_place_read_meta")
+        return n, seq, frame
+
+    def entry(self, e):
+        """entry e as the database holds it: dict(n, seq, frame, desc (n, 32)) and, with geometry, xy (n, 2), xyz (n, 3), valid (n,), qsel (ascending
+        rows that own a valid point); synchronises"""
+        R = self.rows
+        meta = np.zeros(4, np.int32); desc = np.zeros((R, 32), np.uint8)
+        g = self.with_geometry
+        xy = np.zeros((R, 2), np.float32) if g else None; xyz = np.zeros((R, 3), np.float32) if g else None
+        valid = np.zeros(R, np.uint8) if g else None; qsel = np.zeros(R, np.int32) if g else None
+        self.vo._chk(self.vo.lib.vslam_place_read_entry(self.h, e, meta, desc, xy, xyz, valid, qsel), "vslam_place_read_entry")
+        n = int(meta[0])
+        out = dict(n=n, seq=int(meta[1]), frame=int(meta[2]), desc=desc[:n], desc_tail=desc[n:])
+        if g:
+            out.update(xy=xy[:n], xyz=xyz[:n], valid=valid[:n], qsel=qsel[:int(meta[3])])
+        return out
+
+    def score(self, q0, nq, tau, min_gap):
+        """the (nq, n_entries) int32 score table of query entries [q0, q0 + nq) as a torch tensor on the device (asynchronous on the context stream)"""
+        import torch
+        n = len(self)
+        d_score = torch.empty((nq, max(n, 1)), dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
+        torch.cuda.synchronize()   # (the buffer is ready before the context stream writes it)
+        self.vo.place_score_dev(self, q0, nq, tau, min_gap, d_score.data_ptr(), d_score.shape[1])
+        return d_score
+
+    def select(self, q0, d_score, K, min_score):
+        """(candidates, scores), each (nq, K) int32 on the device, of a table score() returned"""
+        import torch
+        nq = d_score.shape[0]
+        d_cand = torch.empty((nq, K), dtype=torch.int32, device=d_score.device); d_cs = torch.empty_like(d_cand)
+        torch.cuda.synchronize()
+        self.vo.place_select_dev(self, q0, nq, d_score.data_ptr(), d_score.shape[1], K, min_score, d_cand.data_ptr(), d_cs.data_ptr())
+        return d_cand, d_cs
+
+    def verify(self, q0, d_cand, rank, min_inliers=10):
+        """(T_q_c (nq, 7) float64, n_matches, n_inliers (nq,) int32), on the device, of every query's rank-`rank` candidate"""
+        import torch
+        nq, K = d_cand.shape
+        d_T = torch.empty((nq, 7), dtype=torch.float64, device=d_cand.device)
+        d_nm = torch.empty(nq, dtype=torch.int32, device=d_cand.device); d_ni = torch.empty_like(d_nm)
+        torch.cuda.synchronize()
+        self.vo.place_verify_dev(self, q0, nq, d_cand.data_ptr(), K, rank, min_inliers, d_T.data_ptr(), d_nm.data_ptr(), d_ni.data_ptr())
+        return d_T, d_nm, d_ni

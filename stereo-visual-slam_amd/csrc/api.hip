@@ -238,7 +238,8 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
            "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
-           "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel";
+           "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel "
+           "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -1806,6 +1807,203 @@ int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int
     if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_voxel_extract_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     return launch_voxel_extract(m->t, map_id, min_count, d_out, d_map_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
+}
+
+// ---------------------------------------------------------------------------------------------- place database
+int vslam_place_create(vslam_ctx* ctx, int rows_per_entry, int capacity_entries, int with_geometry, vslam_place_db** out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !out) { set_error("vslam_place_create: null argument"); return VSLAM_ERR_ARG; }
+    *out = nullptr;
+    if (rows_per_entry < 1 || rows_per_entry > kMaxRows) { set_error("vslam_place_create: rows_per_entry %d outside 1..%d (the matcher's row limit)", rows_per_entry, kMaxRows); return VSLAM_ERR_ARG; }
+    if (capacity_entries < 1) { set_error("vslam_place_create: capacity_entries %d must be >= 1", capacity_entries); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    PlaceDb* d = new PlaceDb(&c->dev_bytes);
+    d->ctx = c; d->n_refused = 0; d->block = nullptr;
+    const size_t R = (size_t)rows_per_entry, Rs = (R + 31) & ~(size_t)31, cap = (size_t)capacity_entries;
+    d->v = PlaceView{};
+    d->v.rows = rows_per_entry; d->v.stride_rows = (int)Rs; d->v.capacity = capacity_entries; d->v.n_entries = 0;
+    PlaceView& v = d->v;
+    auto layout = [&](Layout& a) {
+        v.desc = a.take<uint8_t>(cap * Rs * 32); v.n = a.take<int32_t>(cap); v.seq = a.take<int32_t>(cap); v.frame = a.take<int32_t>(cap);
+        if (with_geometry) {
+            v.xy = a.take<float2>(cap * R); v.xyz = a.take<float>(cap * R * 3); v.valid = a.take<uint8_t>(cap * R); v.qsel = a.take<int32_t>(cap * R);
+            v.nqsel = a.take<int32_t>(cap);
+        }
+    };
+    Layout m(nullptr);
+    layout(m);
+    d->bytes = m.off;
+    if (hipMalloc((void**)&d->block, d->bytes) != hipSuccess) { set_error("vslam_place_create: hipMalloc(%zu) failed", d->bytes); delete d; return VSLAM_ERR_HIP; }
+    c->dev_bytes += d->bytes;
+    Layout a(d->block);
+    layout(a);
+    *out = reinterpret_cast<vslam_place_db*>(d);
+    return VSLAM_OK;
+}
+
+void vslam_place_destroy(vslam_place_db* db) {
+    PlaceDb* d = reinterpret_cast<PlaceDb*>(db);
+    if (!d) return;
+    hipSetDevice(d->ctx->device);
+    hipStreamSynchronize(d->ctx->stream);
+    hipFree(d->block);
+    d->ctx->dev_bytes -= d->bytes;
+    d->dst.release(); d->work.release();
+    delete d;
+}
+
+int vslam_place_clear(vslam_place_db* db) {
+    PlaceDb* d = reinterpret_cast<PlaceDb*>(db);
+    if (!d) { set_error("vslam_place_clear: null database"); return VSLAM_ERR_ARG; }
+    d->v.n_entries = 0; d->n_refused = 0;
+    return VSLAM_OK;
+}
+
+int vslam_place_stats(vslam_place_db* db, struct vslam_place_stats* host) {
+    PlaceDb* d = reinterpret_cast<PlaceDb*>(db);
+    if (!d || !host || host->struct_size != (int32_t)sizeof(struct vslam_place_stats)) { set_error("vslam_place_stats: null argument or struct_size mismatch"); return VSLAM_ERR_ARG; }
+    host->n_entries = d->v.n_entries; host->capacity = d->v.capacity; host->rows_per_entry = d->v.rows; host->with_geometry = d->v.xy ? 1 : 0;
+    host->n_refused = d->n_refused;
+    return VSLAM_OK;
+}
+
+int vslam_place_read_entry(vslam_place_db* db, int entry, int32_t* meta, uint8_t* desc, float* xy, float* xyz, uint8_t* valid, int32_t* qsel) {
+    PlaceDb* d = reinterpret_cast<PlaceDb*>(db);
+    if (!d || !meta) { set_error("vslam_place_read_entry: null database or meta"); return VSLAM_ERR_ARG; }
+    if (entry < 0 || entry >= d->v.n_entries) { set_error("vslam_place_read_entry: entry %d is not among the %d entries held", entry, d->v.n_entries); return VSLAM_ERR_ARG; }
+    Ctx* c = d->ctx;
+    VS_ENTER(c);
+    const PlaceView& v = d->v;
+    const size_t e = (size_t)entry, R = (size_t)v.rows;
+    hipStream_t st = c->stream;
+    meta[3] = 0;
+    VS_HIP(hipMemcpyAsync(&meta[0], v.n + e, 4, hipMemcpyDeviceToHost, st));
+    VS_HIP(hipMemcpyAsync(&meta[1], v.seq + e, 4, hipMemcpyDeviceToHost, st));
+    VS_HIP(hipMemcpyAsync(&meta[2], v.frame + e, 4, hipMemcpyDeviceToHost, st));
+    if (desc) VS_HIP(hipMemcpyAsync(desc, v.desc + e * v.stride_rows * 32, R * 32, hipMemcpyDeviceToHost, st));
+    if (v.xy) {
+        VS_HIP(hipMemcpyAsync(&meta[3], v.nqsel + e, 4, hipMemcpyDeviceToHost, st));
+        if (xy) VS_HIP(hipMemcpyAsync(xy, v.xy + e * R, R * 8, hipMemcpyDeviceToHost, st));
+        if (xyz) VS_HIP(hipMemcpyAsync(xyz, v.xyz + e * R * 3, R * 12, hipMemcpyDeviceToHost, st));
+        if (valid) VS_HIP(hipMemcpyAsync(valid, v.valid + e * R, R, hipMemcpyDeviceToHost, st));
+        if (qsel) VS_HIP(hipMemcpyAsync(qsel, v.qsel + e * R, R * 4, hipMemcpyDeviceToHost, st));
+    }
+    VS_HIP(hipStreamSynchronize(st));
+    return VSLAM_OK;
+}
+
+int vslam_place_read_meta(vslam_place_db* db, int first, int count, int32_t* n, int32_t* seq, int32_t* frame) {
+    PlaceDb* d = reinterpret_cast<PlaceDb*>(db);
+    if (!d) { set_error("vslam_place_read_meta: null database"); return VSLAM_ERR_ARG; }
+    if (first < 0 || count < 0 || first > d->v.n_entries - count) { set_error("vslam_place_read_meta: entries [%d, %d + %d) are not among the %d held", first, first, count, d->v.n_entries); return VSLAM_ERR_ARG; }
+    Ctx* c = d->ctx;
+    VS_ENTER(c);
+    if (count == 0) return VSLAM_OK;
+    const size_t bytes = sizeof(int32_t) * (size_t)count;
+    if (n) VS_HIP(hipMemcpyAsync(n, d->v.n + first, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (seq) VS_HIP(hipMemcpyAsync(seq, d->v.seq + first, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (frame) VS_HIP(hipMemcpyAsync(frame, d->v.frame + first, bytes, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return VSLAM_OK;
+}
+
+static PlaceDb* place_db_of(const Ctx* c, vslam_place_db* db, const char* who) {
+    PlaceDb* d = reinterpret_cast<PlaceDb*>(db);
+    if (!c || !d || d->ctx != c) { set_error("%s: null context or database, or a database of another context", who); return nullptr; }
+    return d;
+}
+// the query range of the score / select / verify entries
+static int place_range(const PlaceDb* d, const char* who, int q0, int nq, int nq_max) {
+    if (nq < 1 || nq > nq_max) { set_error("%s: nq %d outside 1..%d", who, nq, nq_max); return VSLAM_ERR_ARG; }
+    if (q0 < 0 || q0 > d->v.n_entries - nq) { set_error("%s: queries [%d, %d + %d) are not among the %d entries held", who, q0, q0, nq, d->v.n_entries); return VSLAM_ERR_ARG; }
+    return VSLAM_OK;
+}
+
+int vslam_place_add_dev(vslam_ctx* ctx, vslam_place_db* db, const uint8_t* d_desc, size_t desc_stride_bytes, const int32_t* d_n, const int32_t* d_add,
+                        const int32_t* d_seq, const int32_t* d_frame, const vslam_keypoint* d_kps, const float* d_xyz, const uint8_t* d_valid, int kp_capacity,
+                        int B, int* first_entry) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    PlaceDb* d = place_db_of(c, db, "vslam_place_add_dev");
+    if (!d) return VSLAM_ERR_ARG;
+    if (!d_desc || !d_n || !d_seq || !d_frame) { set_error("vslam_place_add_dev: null d_desc, d_n, d_seq or d_frame"); return VSLAM_ERR_ARG; }
+    if (B < 1) { set_error("vslam_place_add_dev: batch %d must be >= 1", B); return VSLAM_ERR_ARG; }
+    if ((((uintptr_t)d_desc | (uintptr_t)desc_stride_bytes) & 15) != 0) { set_error("vslam_place_add_dev: d_desc and desc_stride_bytes must be multiples of 16 bytes"); return VSLAM_ERR_ARG; }
+    if (d->v.xy && (!d_kps || !d_xyz || !d_valid || kp_capacity < 1)) { set_error("vslam_place_add_dev: a database with geometry needs d_kps, d_xyz, d_valid and kp_capacity >= 1"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    // which items are added, and where: decided on the host so that an add that does not fit adds nothing
+    std::vector<int32_t> dst((size_t)B, 1);
+    if (d_add) {
+        VS_HIP(hipMemcpyAsync(dst.data(), d_add, sizeof(int32_t) * B, hipMemcpyDeviceToHost, c->stream));
+        VS_HIP(hipStreamSynchronize(c->stream));
+    }
+    const int first = d->v.n_entries;
+    long long n_add = 0;
+    for (int b = 0; b < B; ++b) dst[b] = dst[b] != 0 ? first + (int)(n_add++) : -1;
+    if (first_entry) *first_entry = first;
+    if (n_add > (long long)d->v.capacity - first) {
+        ++d->n_refused;
+        set_error("vslam_place_add_dev: %lld entries do not fit (%d of %d held): nothing added", n_add, first, d->v.capacity);
+        return VSLAM_ERR_CAPACITY;
+    }
+    if (n_add == 0) return VSLAM_OK;
+    if (int rc = d->dst.reserve(sizeof(int32_t) * B, c->stream)) return rc;
+    VS_HIP(hipMemcpyAsync(d->dst.p, dst.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));   // (dst is a local)
+    if (int rc = launch_place_add(d->v, reinterpret_cast<const int32_t*>(d->dst.p), d_desc, desc_stride_bytes, d_n, d_seq, d_frame, d_kps, d_xyz, d_valid,
+                                  kp_capacity, B, c->stream)) return rc;
+    d->v.n_entries = first + (int)n_add;
+    return VSLAM_OK;
+}
+
+int vslam_place_score_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, int tau, int min_gap, int32_t* d_score, int ld) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    PlaceDb* d = place_db_of(c, db, "vslam_place_score_dev");
+    if (!d) return VSLAM_ERR_ARG;
+    if (!d_score) { set_error("vslam_place_score_dev: null d_score"); return VSLAM_ERR_ARG; }
+    if (int rc = place_range(d, "vslam_place_score_dev", q0, nq, 65535)) return rc;
+    if (tau < 0 || tau > 255) { set_error("vslam_place_score_dev: tau %d outside [0, 255]", tau); return VSLAM_ERR_ARG; }
+    if (ld < d->v.n_entries) { set_error("vslam_place_score_dev: ld %d is below the %d entries held", ld, d->v.n_entries); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_place_score(d->v, q0, nq, tau, min_gap, d_score, ld, c->stream);
+}
+
+int vslam_place_select_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, const int32_t* d_score, int ld, int K, int min_score, int32_t* d_cand,
+                           int32_t* d_cand_score) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    PlaceDb* d = place_db_of(c, db, "vslam_place_select_dev");
+    if (!d) return VSLAM_ERR_ARG;
+    if (!d_score || !d_cand || !d_cand_score) { set_error("vslam_place_select_dev: null d_score, d_cand or d_cand_score"); return VSLAM_ERR_ARG; }
+    if (int rc = place_range(d, "vslam_place_select_dev", q0, nq, 1 << 30)) return rc;
+    if (K < 1 || K > 8) { set_error("vslam_place_select_dev: K %d outside 1..8", K); return VSLAM_ERR_ARG; }
+    if (ld < d->v.n_entries) { set_error("vslam_place_select_dev: ld %d is below the %d entries held", ld, d->v.n_entries); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_place_select(d->v, nq, d_score, ld, K, min_score, d_cand, d_cand_score, c->stream);
+}
+
+int vslam_place_verify_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, const int32_t* d_cand, int K, int rank, int min_inliers, double* d_T_q_c,
+                           int32_t* d_n_matches, int32_t* d_n_inliers) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    PlaceDb* d = place_db_of(c, db, "vslam_place_verify_dev");
+    if (!d) return VSLAM_ERR_ARG;
+    if (!d_cand || !d_T_q_c || !d_n_matches || !d_n_inliers) { set_error("vslam_place_verify_dev: null d_cand, d_T_q_c, d_n_matches or d_n_inliers"); return VSLAM_ERR_ARG; }
+    if (!d->v.xy) { set_error("vslam_place_verify_dev: the database was created without geometry"); return VSLAM_ERR_ARG; }
+    if (int rc = place_range(d, "vslam_place_verify_dev", q0, nq, c->p.max_batch)) return rc;
+    if (K < 1 || K > 8 || rank < 0 || rank >= K) { set_error("vslam_place_verify_dev: K %d outside 1..8 or rank %d outside [0, K)", K, rank); return VSLAM_ERR_ARG; }
+    if (min_inliers < 0) { set_error("vslam_place_verify_dev: min_inliers %d must be >= 0", min_inliers); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    const PlaceView& v = d->v;
+    const size_t R = (size_t)v.rows, n = (size_t)nq;
+    int32_t *d_qitem, *d_nm, *d_np; double* d_gap; vslam_dmatch* d_m; float *d_xyz, *d_uv;
+    if (int rc = carve(d->work, c->stream, [&](Layout& a) {
+            d_qitem = a.take<int32_t>(n); d_nm = a.take<int32_t>(n); d_np = a.take<int32_t>(n); d_gap = a.take<double>(n);
+            d_m = a.take<vslam_dmatch>(n * R); d_xyz = a.take<float>(n * R * 3); d_uv = a.take<float>(n * R * 2);
+        })) return rc;
+    if (int rc = launch_place_verify_prep(v, nq, d_cand, K, rank, d_qitem, d_gap, c->stream)) return rc;
+    const size_t stride = (size_t)v.stride_rows * 32;
+    if (int rc = vslam_feature_matching_pairs_dev(ctx, v.desc, stride, v.n, v.qsel, v.nqsel, v.rows, d_qitem, v.n_entries, v.desc + (size_t)q0 * stride, stride,
+                                                  v.n + q0, d_gap, 1, nq, v.rows, d_m, v.rows, d_nm)) return rc;
+    if (int rc = launch_place_gather(v, q0, nq, d_qitem, d_m, d_nm, min_inliers, d_xyz, d_uv, d_np, d_n_matches, c->stream)) return rc;
+    return vslam_pnp_ransac_dev(ctx, d_xyz, d_uv, d_np, v.rows, nq, d_T_q_c, 100, c->p.pnp_reproj_thr, 0.99, nullptr, d_n_inliers, nullptr);
 }
 
 // float4 streaming copy of `bytes` (src -> dst, both allocated here), `reps` timed launches after one warm-up, hipEvents on the

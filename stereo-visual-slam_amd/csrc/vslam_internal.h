@@ -419,6 +419,24 @@ int launch_voxel_fuse(const VoxelTable& t, const VoxelImages& a, const uint8_t* 
 int launch_voxel_extract(const VoxelTable& t, int map_id, int min_count, vslam_voxel* d_out, int32_t* d_map_out, size_t capacity, unsigned long long* d_n_out,
                          hipStream_t stream);
 
+// ----------------------------------------------------------------------------------------------- place database
+// place_kernels.hip: keyframe descriptor blocks kept across steps and the place score between them (include/vslam_hip.h "place database").
+// Entry e owns stride_rows x 32 bytes of descriptors (stride_rows = rows rounded up to 32: every block 16-byte aligned, the tail zeroed), n / seq / frame
+// and, with geometry (xy non-null), `rows` slots of pixel, camera-frame point, valid flag and the ascending list qsel[0 .. nqsel) of the valid rows.
+struct PlaceView { uint8_t* desc; int32_t* n; int32_t* seq; int32_t* frame; float2* xy; float* xyz; uint8_t* valid; int32_t* qsel; int32_t* nqsel;
+                   int rows, stride_rows, capacity, n_entries; };
+struct PlaceDb { Ctx* ctx; PlaceView v; uint8_t* block; size_t bytes; unsigned long long n_refused; DevBuf dst, work;
+                 PlaceDb(size_t* acct) : dst("place add table", acct), work("place verify scratch", acct) {} };
+int launch_place_add(const PlaceView& v, const int32_t* d_dst, const uint8_t* d_desc, size_t desc_stride, const int32_t* d_n, const int32_t* d_seq,
+                     const int32_t* d_frame, const vslam_keypoint* d_kps, const float* d_xyz, const uint8_t* d_valid, int kp_capacity, int B, hipStream_t stream);
+// d_score (nq x ld int32): -1 / the count of section "place database" for queries [q0, q0 + nq) against every entry
+int launch_place_score(const PlaceView& v, int q0, int nq, int tau, int min_gap, int32_t* d_score, int ld, hipStream_t stream);
+int launch_place_select(const PlaceView& v, int nq, const int32_t* d_score, int ld, int K, int min_score, int32_t* d_cand, int32_t* d_cand_score,
+                        hipStream_t stream);
+int launch_place_verify_prep(const PlaceView& v, int nq, const int32_t* d_cand, int K, int rank, int32_t* d_qitem, double* d_gap, hipStream_t stream);
+int launch_place_gather(const PlaceView& v, int q0, int nq, const int32_t* d_qitem, const vslam_dmatch* d_m, const int32_t* d_nm, int min_inliers, float* d_xyz,
+                        float* d_uv, int32_t* d_n, int32_t* d_n_matches, hipStream_t stream);
+
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {
     vslam_params p;

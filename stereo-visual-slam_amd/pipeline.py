@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import BaBatch, DMATCH_DTYPE, KEYPOINT_DTYPE, TracksIn, VO, _sgbm_params, default_params, sgbm_params_check
+from . import BaBatch, DMATCH_DTYPE, KEYPOINT_DTYPE, LOOP_EDGE_DTYPE, TracksIn, VO, _sgbm_params, default_params, sgbm_params_check
 from . import synth
 from .dense import write_ply  # noqa: F401  (re-exported)
 from .trajectory import assemble_trajectories, assemble_trajectory, sliding_keyframes, write_trajectory  # noqa: F401  (re-exported)
@@ -683,6 +683,97 @@ class KeyframePipeline:
         self.vo.voxel_fuse_disparity_dev(vm, self.d_disp.data_ptr(), self.d_imgs.data_ptr(), self.img_bytes, self.pitch, self.w, self.h, self.B,
                                          self.dense_T.data_ptr(), self.dense_map_id.data_ptr(), z_min, z_max, int(step))
         return vm
+
+    # ------------------------------------------------------------------ loop closure (nothing here runs unless loop_closures is called)
+    def show_sequence(self, sequence):
+        """lay another rendered sequence of the same length over the batch (an unsegmented pipeline without a rig): the next step() sees its frames.
+        This is how one pipeline is driven over the successive chunks of a longer drive."""
+        assert self.seg_first is None and self.rectify is None, "show_sequence: an unsegmented pipeline without rectify"
+        assert len(sequence) == len(self.h_seq), (len(sequence), len(self.h_seq))
+        B = self.B
+        imgs = np.zeros((2 * B, self.h, self.pitch), np.uint8)
+        for b in range(B):
+            L, R, _, _ = sequence[self.frame_of[b]]
+            imgs[b, :, :self.w] = L; imgs[B + b, :, :self.w] = R
+        self.h_seq, self.h_imgs = sequence, imgs
+        self.vo.sync()
+        with torch.cuda.stream(self.stream):
+            self.d_imgs.copy_(torch.from_numpy(imgs).to(self.dev))
+        self.stream.synchronize()
+
+    def _points_per_keypoint(self):
+        """(xyz (B, cap, 3) f32, valid (B, cap) uint8) laid out per LEFT KEYPOINT: depth="sgbm" has them so; depth="match" holds them per L/R match and
+        they are scattered through the L/R table (queryIdx = the left keypoint)"""
+        if self.depth == "sgbm":
+            return self.d_xyz, self.d_valid
+        B, cap = self.B, self.cap
+        with torch.cuda.stream(self.stream):
+            kp = self.d_lr.view(torch.int32).reshape(B, cap, 4)[:, :, 0].long().clamp(0, cap - 1)
+            live = torch.arange(cap, device=self.dev)[None, :] < self.d_nlr[:, None]
+            # a dead slot is sent to a spare column that is cut off again
+            tgt = torch.where(live, kp, torch.full_like(kp, cap))
+            xyz = torch.zeros((B, cap + 1, 3), dtype=torch.float32, device=self.dev).scatter_(1, tgt[:, :, None].expand(B, cap, 3), self.d_xyz)
+            valid = torch.zeros((B, cap + 1), dtype=torch.uint8, device=self.dev).scatter_(1, tgt, self.d_valid)
+            xyz, valid = xyz[:, :cap].contiguous(), valid[:, :cap].contiguous()
+        return xyz, valid
+
+    def loop_closures(self, place_db=None, rows=None, tau=None, min_gap=None, K=3, min_score=None, min_inliers=10, frame_offset=0, seq_ids=None):
+        """Loop-closure edges of the last step (include/vslam_hip.h "place database").  The step's frames -- all of them, or with keyframe_gate the
+        keyframes (the frames trajectories() returns) -- are appended to `place_db` with seq = the segment index (seq_ids: a sequence id per segment
+        instead) and frame = the batch-wide frame index + frame_offset (an int: what earlier steps of the same drive have consumed).  Each new entry
+        is scored against every entry of its sequence at least min_gap frames older, the K best that reach min_score are verified with the matcher
+        and the RANSAC pose stage, and one row per (query, candidate) comes back: a LOOP_EDGE_DTYPE array (entry_q, entry_c, seq, frame_q, frame_c,
+        score, n_matches, n_inliers, accepted = n_inliers >= min_inliers, T_q_c = the pose of candidate c's camera frame in query q's: p_q = T_q_c p_c).
+        place_db: a PlaceDB of this pipeline's context (vo.place_db(...)) kept by the caller -- handing the same one to every step finds loops into
+        earlier batches, which is the point of it; None: a database of this pipeline's own, emptied first, so only loops inside the step are found.
+        rows: descriptor rows kept per entry of a new database (None: anms_num).  tau: None = (int)match_gap_thr = 30, the distance the reference's
+        matcher gate trusts at frame gap 1.  min_gap and min_score have no derivable default and must be given: on the project's renderer at 500
+        keypoints and tau 30, a revisit within half a metre and 0.03 rad scored 83..148, the best other frame at most 54, a foreign scene at most 2
+        (DESIGN.md 5.9); min_gap should exceed the frames over which consecutive views still overlap."""
+        assert min_gap is not None and min_score is not None, "loop_closures: min_gap and min_score must be given (no derivable default; see the docstring)"
+        assert 1 <= int(K) <= 8 and int(min_inliers) >= 0
+        vo, B, cap = self.vo, self.B, self.cap
+        tau = int(vo.params.match_gap_thr) if tau is None else int(tau)
+        if place_db is None:
+            if getattr(self, "_own_place_db", None) is None:
+                self._own_place_db = vo.place_db(rows=rows, capacity=max(B, 1), with_geometry=True)
+            place_db = self._own_place_db
+            place_db.clear()
+        assert place_db.vo is vo and place_db.with_geometry, "place_db: a PlaceDB with geometry of this pipeline's context"
+        vo.sync()
+        torch.cuda.synchronize(self.dev)
+        first_of = self.seg_first if self.seg_first is not None else np.array([0, B])
+        seg_of = np.repeat(np.arange(len(first_of) - 1), np.diff(first_of))
+        seq = seg_of if seq_ids is None else np.asarray(seq_ids, np.int64)[seg_of]
+        frame = np.arange(B) + int(frame_offset)
+        xyz, valid = self._points_per_keypoint()
+        with torch.cuda.stream(self.stream):
+            d_seq = torch.from_numpy(seq.astype(np.int32)).to(self.dev); d_frame = torch.from_numpy(frame.astype(np.int32)).to(self.dev)
+            d_add = (self.ba_frame_state == 2).to(torch.int32) if self.keyframe_gate else None
+        self.stream.synchronize()
+        q0 = vo.place_add_dev(place_db, self.d_desc.data_ptr(), cap * 32, self.d_cnt.data_ptr(), None if d_add is None else d_add.data_ptr(), d_seq.data_ptr(),
+                              d_frame.data_ptr(), self.d_kps.data_ptr(), xyz.data_ptr(), valid.data_ptr(), cap, B)
+        n_total = len(place_db)
+        _, e_seq, e_frame = place_db.meta()
+        rows_out = []
+        chunk = int(vo.params.max_batch)
+        for c0 in range(q0, n_total, chunk):
+            nq = min(chunk, n_total - c0)
+            d_score = place_db.score(c0, nq, tau, int(min_gap))
+            d_cand, d_cs = place_db.select(c0, d_score, int(K), int(min_score))
+            ver = [place_db.verify(c0, d_cand, r, int(min_inliers)) for r in range(int(K))]
+            vo.sync()
+            cand, cs = d_cand.cpu().numpy(), d_cs.cpu().numpy()
+            for r, (dT, dnm, dni) in enumerate(ver):
+                T, nm, ni = dT.cpu().numpy(), dnm.cpu().numpy(), dni.cpu().numpy()
+                for b in np.flatnonzero(cand[:, r] >= 0):
+                    e, c = c0 + int(b), int(cand[b, r])
+                    rows_out.append((e, r, (e, c, e_seq[e], e_frame[e], e_frame[c], cs[b, r], nm[b], ni[b], bool(ni[b] >= min_inliers), T[b])))
+        rows_out.sort(key=lambda t: (t[0], t[1]))
+        out = np.zeros(len(rows_out), LOOP_EDGE_DTYPE)
+        for i, (_, _, row) in enumerate(rows_out):
+            out[i] = row
+        return out
 
     def close(self):
         self.vo.close()
