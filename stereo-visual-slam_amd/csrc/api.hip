@@ -7,7 +7,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cfloat>
 #include <vector>
 
 #include "se3_device.h"
@@ -102,6 +101,16 @@ static CamParams cam_of(const Ctx* c) {
     cam.fx = c->p.cam[0]; cam.fy = c->p.cam[1]; cam.cx = c->p.cam[2]; cam.cy = c->p.cam[3]; cam.b = c->p.cam[4];
     cam.dmin = c->p.depth_min; cam.dmax = c->p.depth_max; cam.drel = c->p.depth_reliable; cam.row_tol = c->p.stereo_row_tol;
     return cam;
+}
+static void fill_K(const Ctx* c, double K[4]) { K[0] = c->p.cam[0]; K[1] = c->p.cam[1]; K[2] = c->p.cam[2]; K[3] = c->p.cam[3]; }
+// launch_pnp's view of B single-pose problems under the context's intrinsics, Huber delta and inlier threshold; no outputs besides the poses and
+// no n_hint until the caller sets them
+static PnpArgs pnp_args_of(const Ctx* c, const float* d_xyz, const float* d_uv, const int32_t* d_n, int capacity, int B, double* d_T, int iters) {
+    PnpArgs p;
+    memset(&p, 0, sizeof(p));
+    p.xyz = d_xyz; p.uv = d_uv; p.n = d_n; p.capacity = capacity; p.B = B; p.T = d_T; p.iters = iters;
+    fill_K(c, p.K); p.huber_delta = c->p.huber_delta; p.reproj_thr = c->p.pnp_reproj_thr;
+    return p;
 }
 
 template <typename T>
@@ -233,7 +242,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "match_train_nearest_kernel match_finalize_kernel sgbm_prefilter_kernel sgbm_down_kernel sgbm_forward_kernel sgbm_hsum_kernel sgbm_vsum_kernel sgbm_path_kernel "
            "sgbm_wta_kernel sgbm_lrcheck_kernel sgbm_median3_kernel sgbm_ccl_rows_kernel sgbm_ccl_union_kernel sgbm_ccl_count_kernel "
            "sgbm_ccl_apply_kernel sgbm_ccl_kernels triangulate_kernel find3d_disparity_kernel gather_uv_kernel build_pnp_inputs_kernel lm_window_kernel pose_only_wave_kernel "
-           "lm_window_kernel<pnp> pnp_wave_kernel pnp_inlier_kernel pnp_epnp_kernels epnp_front_kernel epnp_jacobi_kernel epnp_back_kernel pnp_count_inliers_kernel hbm_copy_probe_kernel "
+           "lm_window_kernel<pnp> pnp_wave_kernel pnp_inlier_kernel pnp_epnp_kernels epnp_front_kernel epnp_jacobi_kernel epnp_back_kernel hbm_copy_probe_kernel "
            "pnp_ransac_subsets_kernel pnp_ransac_count_kernel pnp_ransac_select_kernel "
            "build_windows_kernels track_init_kernel track_pose_chain_kernel track_link_kernel track_chain_kernel window_count_kernel window_scan_kernel window_rank_kernel window_emit_kernel "
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
@@ -496,55 +505,47 @@ int vslam_orb_level(vslam_ctx* ctx, int item, int level, int blurred, uint8_t* o
 }
 
 // ---------------------------------------------------------------------------------------------- matcher
-int vslam_feature_matching_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq, const uint8_t* d_t,
-                               size_t t_stride_bytes, const int32_t* d_nt, const double* d_gap, int gate, int B, int max_rows,
-                               vslam_dmatch* d_out, int out_capacity, int32_t* d_nout) {
+// vslam_feature_matching{,_subset,_pairs}_dev: the three entries' argument checks in their one order, then the launch.  subset: the entry takes
+// d_qsel / d_nqsel / sel_capacity; pairs: it also takes d_qitem / n_qitems (an entry that lacks them passes null / 0, the launch's defaults)
+static int feature_matching_dev(const char* entry, bool subset, bool pairs, vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq,
+                                const int32_t* d_qsel, const int32_t* d_nqsel, int sel_capacity, const int32_t* d_qitem, int n_qitems, const uint8_t* d_t,
+                                size_t t_stride_bytes, const int32_t* d_nt, const double* d_gap, int gate, int B, int max_rows, vslam_dmatch* d_out,
+                                int out_capacity, int32_t* d_nout) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !d_q || !d_t || !d_nq || !d_nt || !d_gap || !d_out || !d_nout || out_capacity <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (subset && (!d_qsel || !d_nqsel)) { set_error("%s: d_qsel and d_nqsel are required", entry); return VSLAM_ERR_ARG; }
+    if (pairs && (!d_qitem || n_qitems < 1)) { set_error("%s: d_qitem (B query-block indices) and n_qitems >= 1 are required", entry); return VSLAM_ERR_ARG; }
+    if (subset && (sel_capacity < 1 || sel_capacity > kMaxRows)) { set_error("sel_capacity %d outside 1..%d (the matcher's row limit)", sel_capacity, kMaxRows); return VSLAM_ERR_ARG; }
     if (B > c->p.max_batch) { set_error("batch %d exceeds context max_batch %d", B, c->p.max_batch); return VSLAM_ERR_ARG; }
     if ((((uintptr_t)d_q | (uintptr_t)d_t | (uintptr_t)q_stride_bytes | (uintptr_t)t_stride_bytes) & 15) != 0) {
-        set_error("vslam_feature_matching_dev: d_q, d_t and both strides must be multiples of 16 bytes (the matcher reads descriptors with 16-byte loads)");
+        set_error("%s: d_q, d_t and both strides must be multiples of 16 bytes (the matcher reads descriptors with 16-byte loads)", entry);
         return VSLAM_ERR_ARG;
     }
     VS_ENTER(c);
     return launch_match(d_q, q_stride_bytes, d_nq, d_t, t_stride_bytes, d_nt, d_gap, gate, c->p.match_ratio, c->p.match_gap_thr, B, max_rows,
-                        c->match.d_train_best, d_out, out_capacity, d_nout, c->stream);
+                        c->match.d_train_best, d_out, out_capacity, d_nout, c->stream, d_qsel, sel_capacity, d_nqsel, d_qitem, n_qitems);
+}
+
+int vslam_feature_matching_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq, const uint8_t* d_t,
+                               size_t t_stride_bytes, const int32_t* d_nt, const double* d_gap, int gate, int B, int max_rows,
+                               vslam_dmatch* d_out, int out_capacity, int32_t* d_nout) {
+    return feature_matching_dev("vslam_feature_matching_dev", false, false, ctx, d_q, q_stride_bytes, d_nq, nullptr, nullptr, 0, nullptr, 0, d_t, t_stride_bytes, d_nt,
+                                d_gap, gate, B, max_rows, d_out, out_capacity, d_nout);
 }
 
 int vslam_feature_matching_subset_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq, const int32_t* d_qsel,
                                       const int32_t* d_nqsel, int sel_capacity, const uint8_t* d_t, size_t t_stride_bytes, const int32_t* d_nt,
                                       const double* d_gap, int gate, int B, int max_rows, vslam_dmatch* d_out, int out_capacity, int32_t* d_nout) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !d_q || !d_t || !d_nq || !d_nt || !d_gap || !d_out || !d_nout || out_capacity <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
-    if (!d_qsel || !d_nqsel) { set_error("vslam_feature_matching_subset_dev: d_qsel and d_nqsel are required"); return VSLAM_ERR_ARG; }
-    if (sel_capacity < 1 || sel_capacity > kMaxRows) { set_error("sel_capacity %d outside 1..%d (the matcher's row limit)", sel_capacity, kMaxRows); return VSLAM_ERR_ARG; }
-    if (B > c->p.max_batch) { set_error("batch %d exceeds context max_batch %d", B, c->p.max_batch); return VSLAM_ERR_ARG; }
-    if ((((uintptr_t)d_q | (uintptr_t)d_t | (uintptr_t)q_stride_bytes | (uintptr_t)t_stride_bytes) & 15) != 0) {
-        set_error("vslam_feature_matching_subset_dev: d_q, d_t and both strides must be multiples of 16 bytes (the matcher reads descriptors with 16-byte loads)");
-        return VSLAM_ERR_ARG;
-    }
-    VS_ENTER(c);
-    return launch_match(d_q, q_stride_bytes, d_nq, d_t, t_stride_bytes, d_nt, d_gap, gate, c->p.match_ratio, c->p.match_gap_thr, B, max_rows,
-                        c->match.d_train_best, d_out, out_capacity, d_nout, c->stream, d_qsel, sel_capacity, d_nqsel);
+    return feature_matching_dev("vslam_feature_matching_subset_dev", true, false, ctx, d_q, q_stride_bytes, d_nq, d_qsel, d_nqsel, sel_capacity, nullptr, 0, d_t,
+                                t_stride_bytes, d_nt, d_gap, gate, B, max_rows, d_out, out_capacity, d_nout);
 }
 
 int vslam_feature_matching_pairs_dev(vslam_ctx* ctx, const uint8_t* d_q, size_t q_stride_bytes, const int32_t* d_nq, const int32_t* d_qsel,
                                      const int32_t* d_nqsel, int sel_capacity, const int32_t* d_qitem, int n_qitems, const uint8_t* d_t, size_t t_stride_bytes,
                                      const int32_t* d_nt, const double* d_gap, int gate, int B, int max_rows, vslam_dmatch* d_out, int out_capacity,
                                      int32_t* d_nout) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || !d_q || !d_t || !d_nq || !d_nt || !d_gap || !d_out || !d_nout || out_capacity <= 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
-    if (!d_qsel || !d_nqsel) { set_error("vslam_feature_matching_pairs_dev: d_qsel and d_nqsel are required"); return VSLAM_ERR_ARG; }
-    if (!d_qitem || n_qitems < 1) { set_error("vslam_feature_matching_pairs_dev: d_qitem (B query-block indices) and n_qitems >= 1 are required"); return VSLAM_ERR_ARG; }
-    if (sel_capacity < 1 || sel_capacity > kMaxRows) { set_error("sel_capacity %d outside 1..%d (the matcher's row limit)", sel_capacity, kMaxRows); return VSLAM_ERR_ARG; }
-    if (B > c->p.max_batch) { set_error("batch %d exceeds context max_batch %d", B, c->p.max_batch); return VSLAM_ERR_ARG; }
-    if ((((uintptr_t)d_q | (uintptr_t)d_t | (uintptr_t)q_stride_bytes | (uintptr_t)t_stride_bytes) & 15) != 0) {
-        set_error("vslam_feature_matching_pairs_dev: d_q, d_t and both strides must be multiples of 16 bytes (the matcher reads descriptors with 16-byte loads)");
-        return VSLAM_ERR_ARG;
-    }
-    VS_ENTER(c);
-    return launch_match(d_q, q_stride_bytes, d_nq, d_t, t_stride_bytes, d_nt, d_gap, gate, c->p.match_ratio, c->p.match_gap_thr, B, max_rows,
-                        c->match.d_train_best, d_out, out_capacity, d_nout, c->stream, d_qsel, sel_capacity, d_nqsel, d_qitem, n_qitems);
+    return feature_matching_dev("vslam_feature_matching_pairs_dev", true, true, ctx, d_q, q_stride_bytes, d_nq, d_qsel, d_nqsel, sel_capacity, d_qitem, n_qitems, d_t,
+                                t_stride_bytes, d_nt, d_gap, gate, B, max_rows, d_out, out_capacity, d_nout);
 }
 
 int vslam_feature_matching(vslam_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, double frame_gap, int gate,
@@ -856,16 +857,18 @@ int vslam_find_3d_disparity(vslam_ctx* ctx, const vslam_keypoint* kps, int n, co
     if (n == 0) return VSLAM_OK;
     VS_ENTER(c);
     int rc;
-    vslam_keypoint* d_k; float *d_d, *d_x; double* d_T; uint8_t *d_v, *d_r;
+    const int32_t nn = n;
+    vslam_keypoint* d_k; float *d_d, *d_x; double* d_T; int32_t* d_n; uint8_t *d_v, *d_r;
     if ((rc = arena_stage(c, [&](Arena& a) {
              d_k = a.in(kps, n);
              d_d = a.in(disparity, (size_t)dstride * h);
              d_T = a.in(T_c_w, 7);
+             d_n = a.in(&nn, 1);
              d_x = a.take<float>(3 * (size_t)n);
              d_v = a.take<uint8_t>(n);
              d_r = a.take<uint8_t>(n);
          }))) return rc;
-    if ((rc = launch_find3d_disparity(d_k, n, d_d, w, h, dstride, d_T, cam_of(c), d_x, d_v, d_r, c->stream))) return rc;
+    if ((rc = launch_find3d_disparity_batch(d_k, d_n, n, 1, d_d, w, h, dstride, (size_t)dstride * h, d_T, cam_of(c), d_x, d_v, d_r, c->stream))) return rc;
     VS_HIP(hipMemcpyAsync(xyz_w, d_x, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipMemcpyAsync(valid, d_v, n, hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipMemcpyAsync(reliable, d_r, n, hipMemcpyDeviceToHost, c->stream));
@@ -879,7 +882,7 @@ int vslam_find_3d_disparity_dev(vslam_ctx* ctx, const vslam_keypoint* d_kps, con
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !d_kps || !d_n || !d_disparity || !d_T_c_w || !d_xyz_w || !d_valid || !d_reliable || kp_capacity <= 0 || w <= 0 || h <= 0 || B < 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    return launch_find3d_disparity_batch(d_kps, d_n, kp_capacity, B, d_disparity, w, h, d_T_c_w, cam_of(c), d_xyz_w, d_valid, d_reliable, c->stream);
+    return launch_find3d_disparity_batch(d_kps, d_n, kp_capacity, B, d_disparity, w, h, w, (size_t)w * h, d_T_c_w, cam_of(c), d_xyz_w, d_valid, d_reliable, c->stream);
 }
 
 int vslam_triangulate_dev(vslam_ctx* ctx, const float* d_uvL, const float* d_uvR, const int32_t* d_n, int capacity, int B,
@@ -932,18 +935,13 @@ int vslam_check_motion(int num_inliers, const double T_c_l[7], double frame_gap)
 }
 
 // ---------------------------------------------------------------------------------------------- motion-only pose
-static void fill_K(const Ctx* c, double K[4]) { K[0] = c->p.cam[0]; K[1] = c->p.cam[1]; K[2] = c->p.cam[2]; K[3] = c->p.cam[3]; }
-
 int vslam_pnp_motion_only_dev(vslam_ctx* ctx, const float* d_xyz_w, const float* d_uv, const int32_t* d_n, int capacity, int B,
                               double* d_T_c_w, int iters, uint8_t* d_inlier, int32_t* d_n_inliers) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !d_xyz_w || !d_uv || !d_n || !d_T_c_w || capacity <= 0 || iters < 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    PnpArgs p;
-    memset(&p, 0, sizeof(p));
-    p.xyz = d_xyz_w; p.uv = d_uv; p.n = d_n; p.capacity = capacity; p.B = B; p.T = d_T_c_w; p.iters = iters;
-    fill_K(c, p.K); p.huber_delta = c->p.huber_delta; p.reproj_thr = c->p.pnp_reproj_thr;
-    p.inlier = d_inlier; p.n_inliers = d_n_inliers; p.stats = nullptr;
+    PnpArgs p = pnp_args_of(c, d_xyz_w, d_uv, d_n, capacity, B, d_T_c_w, iters);
+    p.inlier = d_inlier; p.n_inliers = d_n_inliers;
     return launch_pnp(p, &c->lm, c->stream);
 }
 
@@ -965,10 +963,7 @@ int vslam_pnp_motion_only(vslam_ctx* ctx, const float* xyz_w, const float* uv, i
          }))) return rc;
     VS_HIP(hipMemcpyAsync(d_n, &nn, 4, hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(d_st, 0, sizeof(vslam_lm_stats), c->stream));
-    PnpArgs p;
-    memset(&p, 0, sizeof(p));
-    p.xyz = d_x; p.uv = d_u; p.n = d_n; p.capacity = n; p.B = 1; p.T = d_T; p.iters = iters;
-    fill_K(c, p.K); p.huber_delta = c->p.huber_delta; p.reproj_thr = c->p.pnp_reproj_thr;
+    PnpArgs p = pnp_args_of(c, d_x, d_u, d_n, n, 1, d_T, iters);
     p.inlier = d_in; p.n_inliers = d_n + 1; p.stats = d_st; p.n_hint = n;
     if ((rc = launch_pnp(p, &c->lm, c->stream))) return rc;
     int32_t ni = 0;
@@ -981,19 +976,8 @@ int vslam_pnp_motion_only(vslam_ctx* ctx, const float* xyz_w, const float* uv, i
     return VSLAM_OK;
 }
 
-// RANSAC wrapper (see include/vslam_hip.h and oracle/ransac.c for the restated control flow)
-static unsigned cv_rng_next(uint64_t& state) {
-    state = (uint64_t)(unsigned)state * 4164903690ULL + (unsigned)(state >> 32);
-    return (unsigned)state;
-}
-static int ransac_update_num_iters(double p, double ep, int model_points, int max_iters) { // cv::RANSACUpdateNumIters
-    p = std::min(std::max(p, 0.), 1.); ep = std::min(std::max(ep, 0.), 1.);
-    double num = std::max(1. - p, DBL_MIN), denom = 1. - std::pow(1. - ep, model_points);
-    if (denom < DBL_MIN) return 0;
-    num = std::log(num); denom = std::log(denom);
-    return denom >= 0 || -num >= max_iters * (-denom) ? max_iters : (int)std::lrint(num / denom);
-}
-
+// Host-buffer RANSAC (include/vslam_hip.h): stages the caller's points and runs the batched launch at B = 1.  The subset draw, EPnP, the scoring
+// and the acceptance replay are launch_pnp_ransac_batch's (pnp_kernels.hip); the only other restatement of that control flow is oracle/ransac.c
 static int pnp_ransac_impl(vslam_ctx* ctx, const float* xyz_w, const float* uv, int n, double T_c_w[7], int max_iters, double reproj_err,
                            double confidence, int lm_iters, uint8_t* inlier, int* n_inliers, int* iters_run, double* models_Rt, int32_t* models_count) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
@@ -1004,93 +988,54 @@ static int pnp_ransac_impl(vslam_ctx* ctx, const float* xyz_w, const float* uv, 
     const int mp = 5;
     if (n < mp || max_iters == 0) return VSLAM_OK;
     VS_ENTER(c);
-    const bool single = n == mp;          // ptsetreg.cpp: count == modelPoints -> one model from all points, every point an inlier
-    const int H = single ? 1 : max_iters;
-    // 1. the subset sequence (host: a few hundred RNG draws)
-    std::vector<float> hx((size_t)H * mp * 3), hu((size_t)H * mp * 2);
-    uint64_t state = 0xFFFFFFFFFFFFFFFFULL;
-    for (int it = 0; it < H; ++it) {
-        int idx[5];
-        for (int i = 0; i < mp; ++i) {
-            if (single) { idx[i] = i; continue; }
-            for (;;) {
-                const int v = (int)(cv_rng_next(state) % (unsigned)n);
-                int j = 0;
-                for (; j < i; ++j) if (idx[j] == v) break;
-                idx[i] = v;
-                if (j == i) break;
-            }
-        }
-        for (int i = 0; i < mp; ++i) {
-            memcpy(&hx[((size_t)it * mp + i) * 3], xyz_w + 3 * (size_t)idx[i], 12);
-            memcpy(&hu[((size_t)it * mp + i) * 2], uv + 2 * (size_t)idx[i], 8);
-        }
-    }
     int rc;
-    float *d_hx, *d_hu, *d_x, *d_u, *d_ix, *d_iu; double *d_Rt, *d_hT, *d_T; int32_t *d_ok, *d_cnt, *d_n1; uint8_t *d_mask, *d_ws;
+    const int32_t nn = n;
+    float *d_x, *d_u, *d_ix, *d_iu; double* d_T; int32_t *d_n, *d_res; uint8_t* d_mask;
     if ((rc = arena_stage(c, [&](Arena& a) {
-             d_hx = a.in(hx.data(), hx.size()); d_hu = a.in(hu.data(), hu.size());
-             d_Rt = a.take<double>((size_t)H * 12); d_hT = a.take<double>((size_t)H * 7);
-             d_ok = a.take<int32_t>(H); d_cnt = a.take<int32_t>(H);
              d_x = a.in(xyz_w, 3 * (size_t)n); d_u = a.in(uv, 2 * (size_t)n);
+             d_n = a.in(&nn, 1);
+             d_T = a.take<double>(7); d_mask = a.take<uint8_t>(n);
+             d_res = a.take<int32_t>(3); // inlier count and iterations run out; [2]: the refinement's point count in
              d_ix = a.take<float>(3 * (size_t)n); d_iu = a.take<float>(2 * (size_t)n);
-             d_mask = a.take<uint8_t>(n); d_T = a.take<double>(7); d_n1 = a.take<int32_t>(2);
-             d_ws = a.take<uint8_t>(pnp_epnp_ws_bytes(H));
          }))) return rc;
-    // 2. every hypothesis: EPnP on its 5 points (one wave each), then its inlier count over all points
     double K[4];
     fill_K(c, K);
-    if ((rc = launch_pnp_epnp(d_hx, d_hu, H, K, d_Rt, d_hT, d_ok, d_ws, c->stream))) return rc;
+    RansacTables tab;
+    if ((rc = launch_pnp_ransac_batch(d_x, d_u, d_n, n, 1, max_iters, K, reproj_err, confidence, c->ransac, d_T, d_mask, d_res, d_res + 1, c->stream, &tab))) return rc;
+    const bool single = n == mp; // ptsetreg.cpp: count == modelPoints -> one model from all points, every point an inlier
+    const int H = single ? 1 : max_iters;
+    double T[7]; int32_t res[2];
+    std::vector<uint8_t> mask(n);
     std::vector<int32_t> cnt(H), okv(H);
-    if (!single && (rc = launch_pnp_count_inliers(d_x, d_u, n, d_Rt, d_ok, 0, H, K, reproj_err, d_cnt, nullptr, c->stream))) return rc;
-    if (!single) VS_HIP(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)H * 4, hipMemcpyDeviceToHost, c->stream));
-    VS_HIP(hipMemcpyAsync(okv.data(), d_ok, (size_t)H * 4, hipMemcpyDeviceToHost, c->stream));
-    if (models_Rt) VS_HIP(hipMemcpyAsync(models_Rt, d_Rt, (size_t)H * 96, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipMemcpyAsync(T, d_T, 56, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipMemcpyAsync(mask.data(), d_mask, n, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipMemcpyAsync(res, d_res, 8, hipMemcpyDeviceToHost, c->stream));
+    if (models_Rt) {
+        VS_HIP(hipMemcpyAsync(models_Rt, tab.Rt, (size_t)H * 96, hipMemcpyDeviceToHost, c->stream));
+        VS_HIP(hipMemcpyAsync(okv.data(), tab.ok, (size_t)H * 4, hipMemcpyDeviceToHost, c->stream));
+        VS_HIP(hipMemcpyAsync(cnt.data(), tab.counts, (size_t)H * 4, hipMemcpyDeviceToHost, c->stream));
+    }
     VS_HIP(hipStreamSynchronize(c->stream));
     if (models_count) for (int i = 0; i < H; ++i) models_count[i] = okv[i] ? (single ? n : cnt[i]) : -1;
-    // 3. replay of the sequential loop over the counts (ptsetreg.cpp: strict improvement, adaptive iteration count)
-    int best = -1, max_good = 0, it = 0;
-    if (single) { if (okv[0]) { best = 0; max_good = n; } }
-    else {
-        int niters = H;
-        for (it = 0; it < niters; ++it)
-            if (okv[it] && cnt[it] > std::max(max_good, mp - 1)) {
-                best = it; max_good = cnt[it];
-                niters = ransac_update_num_iters(confidence, (double)(n - max_good) / n, mp, niters);
-            }
-    }
-    if (iters_run) *iters_run = it;
-    if (best < 0) return VSLAM_OK;
-    // 4. mask of the best model; lm_iters > 0: refinement on its inliers (solvePnP on the inliers; deviation R2 of oracle/ransac.c)
-    std::vector<uint8_t> mask(n, 1);
-    if (!single) {
-        if ((rc = launch_pnp_count_inliers(d_x, d_u, n, d_Rt, d_ok, best, 1, K, reproj_err, nullptr, d_mask, c->stream))) return rc;
-        VS_HIP(hipMemcpyAsync(mask.data(), d_mask, n, hipMemcpyDeviceToHost, c->stream));
-        VS_HIP(hipStreamSynchronize(c->stream));
-    }
+    if (iters_run) *iters_run = res[1];
+    const int max_good = res[0];
+    if (max_good <= 0) return VSLAM_OK; // no model accepted: T_c_w stays as the caller left it
+    // lm_iters > 0: refinement on the best model's inliers (solvePnP on the inliers; deviation R2 of oracle/ransac.c)
     std::vector<float> ix, iu;
     for (int i = 0; i < n; ++i) if (mask[i]) { ix.insert(ix.end(), xyz_w + 3 * (size_t)i, xyz_w + 3 * (size_t)i + 3); iu.insert(iu.end(), uv + 2 * (size_t)i, uv + 2 * (size_t)i + 2); }
-    const int m = (int)(iu.size() / 2);
+    const int32_t m = (int32_t)(iu.size() / 2);
     if (m != max_good) { set_error("RANSAC inlier recount mismatch (%d vs %d)", m, max_good); return VSLAM_ERR_HIP; }
-    if (lm_iters <= 0) { // OpenCV 3.2.0: solvePnPRansac assigns _local_model (the best RANSAC model) to rvec / tvec; the refined pose is discarded
-        VS_HIP(hipMemcpyAsync(T_c_w, d_hT + 7 * (size_t)best, 56, hipMemcpyDeviceToHost, c->stream));
+    if (lm_iters > 0) { // (0 = OpenCV 3.2.0: solvePnPRansac assigns _local_model, the best RANSAC model, to rvec / tvec; the refined pose is discarded)
+        VS_HIP(hipMemcpyAsync(d_ix, ix.data(), ix.size() * 4, hipMemcpyHostToDevice, c->stream));
+        VS_HIP(hipMemcpyAsync(d_iu, iu.data(), iu.size() * 4, hipMemcpyHostToDevice, c->stream));
+        VS_HIP(hipMemcpyAsync(d_res + 2, &m, 4, hipMemcpyHostToDevice, c->stream));
+        PnpArgs p = pnp_args_of(c, d_ix, d_iu, d_res + 2, m, 1, d_T, lm_iters); // (d_T holds the best model: the seed)
+        p.huber_delta = 1e300; p.reproj_thr = reproj_err; p.n_hint = m;
+        if ((rc = launch_pnp(p, &c->lm, c->stream))) return rc;
+        VS_HIP(hipMemcpyAsync(T, d_T, 56, hipMemcpyDeviceToHost, c->stream));
         VS_HIP(hipStreamSynchronize(c->stream));
-        if (inlier) memcpy(inlier, mask.data(), n);
-        if (n_inliers) *n_inliers = max_good;
-        return VSLAM_OK;
     }
-    VS_HIP(hipMemcpyAsync(d_ix, ix.data(), ix.size() * 4, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_iu, iu.data(), iu.size() * 4, hipMemcpyHostToDevice, c->stream));
-    VS_HIP(hipMemcpyAsync(d_T, d_hT + 7 * (size_t)best, 56, hipMemcpyDeviceToDevice, c->stream));
-    int32_t nn = m;
-    VS_HIP(hipMemcpyAsync(d_n1, &nn, 4, hipMemcpyHostToDevice, c->stream));
-    PnpArgs p;
-    memset(&p, 0, sizeof(p));
-    p.xyz = d_ix; p.uv = d_iu; p.n = d_n1; p.capacity = m; p.B = 1; p.T = d_T; p.iters = lm_iters;
-    fill_K(c, p.K); p.huber_delta = 1e300; p.reproj_thr = reproj_err; p.n_hint = m;
-    if ((rc = launch_pnp(p, &c->lm, c->stream))) return rc;
-    VS_HIP(hipMemcpyAsync(T_c_w, d_T, 56, hipMemcpyDeviceToHost, c->stream));
-    VS_HIP(hipStreamSynchronize(c->stream));
+    memcpy(T_c_w, T, 56);
     if (inlier) memcpy(inlier, mask.data(), n);
     if (n_inliers) *n_inliers = max_good;
     return VSLAM_OK;

@@ -34,37 +34,21 @@ __device__ inline void inverse_pose(const double* T, double Rinv[9], double tinv
     for (int a = 0; a < 3; ++a) tinv[a] = -(Rinv[3 * a] * T[4] + Rinv[3 * a + 1] * T[5] + Rinv[3 * a + 2] * T[6]);
 }
 
-__global__ __launch_bounds__(256) void find3d_disparity_kernel(const vslam_keypoint* __restrict__ kps, int n, const float* __restrict__ disp,
-                                                              int w, int h, int dstride, const double* __restrict__ T, CamParams cam,
+// item b has d_n[b] keypoints at kps + b * kp_capacity, its own pose and its own disparity map at disp + b * item_stride (rows dstride elements apart)
+__global__ __launch_bounds__(256) void find3d_disparity_kernel(const vslam_keypoint* __restrict__ kps, const int32_t* __restrict__ d_n,
+                                                              int kp_capacity, const float* __restrict__ disp, int w, int h, int dstride,
+                                                              size_t item_stride, const double* __restrict__ d_T, CamParams cam,
                                                               float* __restrict__ xyz, uint8_t* __restrict__ valid, uint8_t* __restrict__ rel) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    double Rinv[9], tinv[3];
-    inverse_pose(T, Rinv, tinv);
-    const float u = kps[i].x, v = kps[i].y;
-    const int r = (int)v, c = (int)u; // at<float>(kp.pt.y, kp.pt.x): float -> int truncation (quirk Q3)
-    if (r < 0 || r >= h || c < 0 || c >= w) { valid[i] = 0; rel[i] = 0; xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = 0.f; return; }
-    const double x = ((double)u - cam.cx) / cam.fx, y = ((double)v - cam.cy) / cam.fy;
-    const double depth = cam.fx * cam.b / (double)disp[(size_t)r * dstride + c];
-    const double p[3] = {x * depth, y * depth, depth};
-    gate_store(p, Rinv, tinv, cam, i, xyz, valid, rel);
-}
-
-// batched form: item b has d_n[b] keypoints at kps + b * kp_capacity and its own disparity map and pose
-__global__ __launch_bounds__(256) void find3d_disparity_batch_kernel(const vslam_keypoint* __restrict__ kps, const int32_t* __restrict__ d_n,
-                                                                    int kp_capacity, const float* __restrict__ disp, int w, int h,
-                                                                    const double* __restrict__ d_T, CamParams cam, float* __restrict__ xyz,
-                                                                    uint8_t* __restrict__ valid, uint8_t* __restrict__ rel) {
     const int b = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
     if (k >= min(d_n[b], kp_capacity)) return;
     const size_t i = (size_t)b * kp_capacity + k;
     double Rinv[9], tinv[3];
     inverse_pose(d_T + 7 * b, Rinv, tinv);
     const float u = kps[i].x, v = kps[i].y;
-    const int r = (int)v, c = (int)u; // quirk Q3: truncation
+    const int r = (int)v, c = (int)u; // at<float>(kp.pt.y, kp.pt.x): float -> int truncation (quirk Q3)
     if (r < 0 || r >= h || c < 0 || c >= w) { valid[i] = 0; rel[i] = 0; xyz[3 * i] = xyz[3 * i + 1] = xyz[3 * i + 2] = 0.f; return; }
     const double x = ((double)u - cam.cx) / cam.fx, y = ((double)v - cam.cy) / cam.fy;
-    const double depth = cam.fx * cam.b / (double)disp[((size_t)b * h + r) * w + c];
+    const double depth = cam.fx * cam.b / (double)disp[b * item_stride + (size_t)r * dstride + c];
     const double p[3] = {x * depth, y * depth, depth};
     gate_store(p, Rinv, tinv, cam, i, xyz, valid, rel);
 }
@@ -180,21 +164,13 @@ int launch_build_pnp_inputs(const vslam_dmatch* d_m, const int32_t* d_nm, int ma
     return VSLAM_OK;
 }
 
-int launch_find3d_disparity(const vslam_keypoint* d_kps, int n, const float* d_disp, int w, int h, int dstride, const double* d_T,
-                            CamParams cam, float* d_xyz, uint8_t* d_valid, uint8_t* d_rel, hipStream_t stream) {
-    if (n <= 0) return VSLAM_OK;
-    hipLaunchKernelGGL(find3d_disparity_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_kps, n, d_disp, w, h, dstride, d_T, cam,
-                       d_xyz, d_valid, d_rel);
-    VS_HIP(hipGetLastError());
-    return VSLAM_OK;
-}
-
 int launch_find3d_disparity_batch(const vslam_keypoint* d_kps, const int32_t* d_n, int kp_capacity, int B, const float* d_disp, int w, int h,
-                                  const double* d_T, CamParams cam, float* d_xyz, uint8_t* d_valid, uint8_t* d_rel, hipStream_t stream) {
+                                  int dstride, size_t item_stride, const double* d_T, CamParams cam, float* d_xyz, uint8_t* d_valid, uint8_t* d_rel,
+                                  hipStream_t stream) {
     if (B <= 0) return VSLAM_OK;
     ProfScope prof__(stream, "find3d_disparity_kernel");
-    hipLaunchKernelGGL(find3d_disparity_batch_kernel, dim3((kp_capacity + 255) / 256, B), dim3(256), 0, stream, d_kps, d_n, kp_capacity, d_disp, w, h,
-                       d_T, cam, d_xyz, d_valid, d_rel);
+    hipLaunchKernelGGL(find3d_disparity_kernel, dim3((kp_capacity + 255) / 256, B), dim3(256), 0, stream, d_kps, d_n, kp_capacity, d_disp, w, h,
+                       dstride, item_stride, d_T, cam, d_xyz, d_valid, d_rel);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

@@ -426,7 +426,7 @@ __global__ __launch_bounds__(64) void epnp_back_kernel(int H, int Hs, double fu,
     ok_out[h] = fin ? 1 : 0;
 }
 
-size_t pnp_epnp_ws_bytes(int H) { return (size_t)kWsFields * (size_t)((H + 63) & ~63) * sizeof(double); }
+static size_t pnp_epnp_ws_bytes(int H) { return (size_t)kWsFields * (size_t)((H + 63) & ~63) * sizeof(double); }
 
 // the three launches for H hypotheses (ws: pnp_epnp_ws_bytes(H) bytes)
 static void launch_epnp_stages(const float* d_hx, const float* d_hu, int H, const double K[4], double* ws, double* d_Rt, double* d_T, int32_t* d_ok,
@@ -437,54 +437,11 @@ static void launch_epnp_stages(const float* d_hx, const float* d_hu, int H, cons
     hipLaunchKernelGGL(epnp_back_kernel, dim3(Hs / 64), dim3(64), 0, stream, H, Hs, K[0], K[1], K[2], K[3], (const double*)ws, d_Rt, d_T, d_ok);
 }
 
-// PnPRansacCallback::computeError + findInliers: inliers of every hypothesis over the shared point set (block = hypothesis);
-// mask (optional) receives the per-point flags of hypothesis `mask_hyp`
-__global__ __launch_bounds__(256) void pnp_count_inliers_kernel(const float* __restrict__ xyz, const float* __restrict__ uv, int n, const double* __restrict__ Rt,
-                                                               const int32_t* __restrict__ ok, double fx, double fy, double cx, double cy, float thr2,
-                                                               int32_t* __restrict__ counts, int hyp0, uint8_t* __restrict__ mask) {
-    const int hyp = hyp0 + blockIdx.x;
-    __shared__ double sR[12];
-    __shared__ int cnt;
-    if (threadIdx.x < 12) sR[threadIdx.x] = Rt[(size_t)hyp * 12 + threadIdx.x];
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    int mine = 0;
-    if (ok[hyp])
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const double X = xyz[3 * i], Y = xyz[3 * i + 1], Z = xyz[3 * i + 2];
-            double x = sR[0] * X + sR[1] * Y + sR[2] * Z + sR[9];
-            double y = sR[3] * X + sR[4] * Y + sR[5] * Z + sR[10];
-            double z = sR[6] * X + sR[7] * Y + sR[8] * Z + sR[11];
-            z = z ? 1. / z : 1;
-            x *= z; y *= z;
-            const float pu = (float)(x * fx + cx), pv = (float)(y * fy + cy);
-            const float du = uv[2 * i] - pu, dv = uv[2 * i + 1] - pv;
-            float err = 0.f;
-            err += du * du;
-            err += dv * dv;
-            const bool in = err <= thr2;
-            if (mask) mask[i] = in;
-            mine += in;
-        }
-    else if (mask)
-        for (int i = threadIdx.x; i < n; i += 256) mask[i] = 0;
-    atomicAdd(&cnt, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && counts) counts[hyp] = cnt;
-}
-
-int launch_pnp_epnp(const float* d_hx, const float* d_hu, int H, const double K[4], double* d_Rt, double* d_T, int32_t* d_ok, uint8_t* ws, hipStream_t stream) {
-    if (H <= 0) return VSLAM_OK;
-    ProfScope prof__(stream, "pnp_epnp_kernels", 3);
-    launch_epnp_stages(d_hx, d_hu, H, K, (double*)ws, d_Rt, d_T, d_ok, nullptr, 1, stream);
-    VS_HIP(hipGetLastError());
-    return VSLAM_OK;
-}
-
-// ------------------------------------------------------------------------------------------- batched RANSAC pose (vslam_pnp_ransac_dev)
+// ------------------------------------------------------------------------------------------- RANSAC pose (vslam_pnp_ransac[_models | _dev])
 // cv::solvePnPRansac(..., useExtrinsicGuess = false, 100, 4.0, 0.99) of VO::motion_estimation (visual_odometry.cpp:277) for B independent
-// problems whose points are already in device memory -- the reference's own pose stage in throughput mode.  Same restatement as the host
-// tier (api.hip pnp_ransac_impl, oracle/ransac.c): every problem draws the SAME cv::RNG sequence (seed -1) of 5-point subsets modulo its
+// problems whose points are in device memory -- the reference's own pose stage in throughput mode, and at B = 1 the host-buffer entries
+// (api.hip pnp_ransac_impl stages its arguments and calls this launch).  The library's one restatement of the control flow, next to the
+// oracle's (oracle/ransac.c): every problem draws the SAME cv::RNG sequence (seed -1) of 5-point subsets modulo its
 // own point count, all B x max_iters hypotheses are solved (EPnP, one wave each) and scored at once, and the sequential acceptance rule
 // with its adaptive stopping (RANSACUpdateNumIters) is replayed per problem over the counts.  Returns the best RANSAC model itself (OpenCV
 // 3.2.0, the reference's pinned version: the refined pose is discarded) and its inlier mask.
@@ -528,8 +485,8 @@ __global__ __launch_bounds__(64) void pnp_ransac_subsets_kernel(const float* __r
     }
 }
 
-// PnPRansacCallback::computeError of one point under one model: f64 projection with one reciprocal, f32 squared error (the arithmetic of
-// pnp_count_inliers_kernel above, shared by the two batched kernels below)
+// PnPRansacCallback::computeError + findInliers for one point under one model: f64 projection with one reciprocal, f32 squared error
+// against (float)(reproj_err^2) -- the library's only copy of the rule; the count and the select kernel below both call it
 __device__ inline bool ransac_point_is_inlier(const double* sR, const float* xyz, const float* uv, int i, double fx, double fy, double cx, double cy, float thr2) {
     const double X = xyz[3 * i], Y = xyz[3 * i + 1], Z = xyz[3 * i + 2];
     double x = sR[0] * X + sR[1] * Y + sR[2] * Z + sR[9];
@@ -622,7 +579,8 @@ __global__ __launch_bounds__(128) void pnp_ransac_select_kernel(const float* __r
 }
 
 int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t* d_n, int capacity, int B, int H, const double K[4], double reproj_err,
-                            double confidence, DevBuf& scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream) {
+                            double confidence, DevBuf& scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream,
+                            RansacTables* tables) {
     if (B <= 0) return VSLAM_OK;
     const size_t nh = (size_t)B * H;
     float *hx, *hu; double *Rt, *hT, *ws; int32_t *ok, *cnt, *nh_of;
@@ -647,16 +605,7 @@ int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t
       hipLaunchKernelGGL(pnp_ransac_select_kernel, dim3(B), dim3(128), 0, stream, d_xyz, d_uv, d_n, capacity, H, Rt, hT, ok, cnt, nh_of, confidence, K[0], K[1], K[2],
                          K[3], thr2, d_T, d_inlier, d_n_inl, d_iters); }
     VS_HIP(hipGetLastError());
-    return VSLAM_OK;
-}
-
-int launch_pnp_count_inliers(const float* d_xyz, const float* d_uv, int n, const double* d_Rt, const int32_t* d_ok, int hyp0, int n_hyp, const double K[4],
-                             double reproj_thr, int32_t* d_counts, uint8_t* d_mask, hipStream_t stream) {
-    if (n_hyp <= 0) return VSLAM_OK;
-    ProfScope prof__(stream, "pnp_count_inliers_kernel");
-    hipLaunchKernelGGL(pnp_count_inliers_kernel, dim3(n_hyp), dim3(256), 0, stream, d_xyz, d_uv, n, d_Rt, d_ok, K[0], K[1], K[2], K[3],
-                       (float)(reproj_thr * reproj_thr), d_counts, hyp0, d_mask);
-    VS_HIP(hipGetLastError());
+    if (tables) *tables = {Rt, ok, cnt};
     return VSLAM_OK;
 }
 

@@ -182,10 +182,10 @@ int launch_match(const uint8_t* d_q, size_t q_stride, const int32_t* d_nq, const
 
 // ----------------------------------------------------------------------------------------------- geometry
 struct CamParams { double fx, fy, cx, cy, b, dmin, dmax, drel, row_tol; };
-int launch_find3d_disparity(const vslam_keypoint* d_kps, int n, const float* d_disp, int w, int h, int dstride,
-                            const double* d_T, CamParams cam, float* d_xyz, uint8_t* d_valid, uint8_t* d_rel, hipStream_t stream);
+// item b's disparity map starts at d_disp + b * item_stride, its rows are dstride elements apart
 int launch_find3d_disparity_batch(const vslam_keypoint* d_kps, const int32_t* d_n, int kp_capacity, int B, const float* d_disp, int w, int h,
-                                  const double* d_T, CamParams cam, float* d_xyz, uint8_t* d_valid, uint8_t* d_rel, hipStream_t stream);
+                                  int dstride, size_t item_stride, const double* d_T, CamParams cam, float* d_xyz, uint8_t* d_valid, uint8_t* d_rel,
+                                  hipStream_t stream);
 int launch_triangulate(const float* d_uvL, const float* d_uvR, const int32_t* d_n, int capacity, int B, const double* d_T,
                        CamParams cam, float* d_xyz, uint8_t* d_valid, uint8_t* d_rel, hipStream_t stream);
 // f2f matches + per-keypoint 3-D points of the query frame -> compact (xyz, uv) PnP inputs (ordered, valid only)
@@ -311,14 +311,13 @@ struct PnpArgs {
 int launch_pnp(const PnpArgs& a, LmScratch* scratch, hipStream_t stream);
 int launch_edge_jacobians(int n, const float* d_xyz, const float* d_uv, const double* d_T, const double K[4], double delta, double* d_err, double* d_Jp, double* d_Jl,
                           double* d_chi2, double* d_hw, hipStream_t stream);
-// pnp_kernels.hip: EPnP of H 5-point subsets (one wave each) -> R|t (H x 12), pose (H x 7), ok flag; f32 inlier scoring of hypotheses
-size_t pnp_epnp_ws_bytes(int H);
-int launch_pnp_epnp(const float* d_hx, const float* d_hu, int H, const double K[4], double* d_Rt, double* d_T, int32_t* d_ok, uint8_t* ws, hipStream_t stream);
-int launch_pnp_count_inliers(const float* d_xyz, const float* d_uv, int n, const double* d_Rt, const int32_t* d_ok, int hyp0, int n_hyp, const double K[4],
-                             double reproj_thr, int32_t* d_counts, uint8_t* d_mask, hipStream_t stream);
-
+// pnp_kernels.hip: cv::solvePnPRansac for B problems of up to `capacity` points -- H 5-point subsets each, EPnP per subset (one wave each), f32 inlier
+// scoring, the sequential acceptance rule replayed per problem.  tables (optional): where the B x H hypothesis tables lie in `scratch` -- [R | t]
+// (12 doubles), ok flag, inlier count (0 where ok == 0) -- valid until the next launch on that scratch
+struct RansacTables { const double* Rt; const int32_t* ok; const int32_t* counts; };
 int launch_pnp_ransac_batch(const float* d_xyz, const float* d_uv, const int32_t* d_n, int capacity, int B, int H, const double K[4], double reproj_err,
-                            double confidence, DevBuf& scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream);
+                            double confidence, DevBuf& scratch, double* d_T, uint8_t* d_inlier, int32_t* d_n_inl, int32_t* d_iters, hipStream_t stream,
+                            RansacTables* tables = nullptr);
 // track_kernels.hip: BA windows of a batch of consecutive keyframes from the front end's device-resident output.  launch_build_windows and
 // launch_map_pnp_inputs share one front half (dims, node tables, pairing, init, link, walk); KfPolicy says what the window builder adds to it.
 // Which keyframes a window holds (vslam_build_windows_kf_dev): policy -1 = the sliding window with no set outputs (vslam_build_windows_dev),

@@ -136,6 +136,46 @@ def test_pnp_ransac_too_few_points(vo, synth):
     assert n == 0 and it == 0 and np.array_equal(T, p["T0"])
 
 
+def test_pnp_ransac_no_model_accepted(vo, oracle, synth):
+    """n >= 6 and no hypothesis with 5 inliers: no inliers, the oracle's iteration count, and T_c_w (output only) left as the caller passed it"""
+    p = synth.pnp_problem(M=8, seed=1, outlier_frac=0.0, sigma_px=0.4)
+    rng = np.random.default_rng(1001)
+    uv = np.stack([rng.uniform(40, 1200, 8), rng.uniform(40, 330, 8)], 1).astype(np.float32)   # pixels unrelated to the points
+    wT, winl, wn, wit = oracle.pnp_ransac(p["xyz"], uv)
+    assert wn == 0 and not winl.any()   # (the input does what it is here for)
+    T, inl, n, it = vo.motion_estimation_ransac(p["xyz"], uv, p["T0"])
+    assert n == 0 and not inl.any() and it == wit
+    assert np.array_equal(T, p["T0"])
+
+
+def test_pnp_ransac_zero_iterations(vo, synth):
+    p = synth.pnp_problem(M=50, seed=2)
+    T, inl, n, it = vo.motion_estimation_ransac(p["xyz"], p["uv"], p["T0"], max_iters=0)
+    assert n == 0 and it == 0 and not inl.any() and np.array_equal(T, p["T0"])
+
+
+def test_pnp_ransac_models_short_hypothesis_table(vo, oracle, synth):
+    """a hypothesis count that is neither 100 nor a multiple of the wave width: 7 models of 9 clean points, bit-equal to the oracle's"""
+    p = synth.pnp_problem(M=9, seed=21, outlier_frac=0.0, sigma_px=0.4)
+    T, inl, n, it, models, counts = vo.motion_estimation_ransac_models(p["xyz"], p["uv"], max_iters=7)
+    subs = oracle.ransac_subsets(9, 7)
+    assert models.shape == (7, 12) and counts.shape == (7,)
+    for h in range(7):
+        m = oracle.epnp_subset(p["xyz"], p["uv"], subs[h])
+        assert m is not None and np.array_equal(m, models[h]), h
+        assert oracle.pnp_ransac_hypothesis(p["xyz"], p["uv"], h)[1] == counts[h]
+
+
+def test_pnp_ransac_models_exactly_five_points(vo, oracle, synth):
+    """count == modelPoints (ptsetreg.cpp): one model from all five points, every point an inlier, no iteration; only entry 0 of the tables is written"""
+    p = synth.pnp_problem(M=5, seed=22, outlier_frac=0.0, sigma_px=0.4)
+    T, inl, n, it, models, counts = vo.motion_estimation_ransac_models(p["xyz"], p["uv"])
+    m = oracle.epnp_subset(p["xyz"], p["uv"], (0, 1, 2, 3, 4))
+    assert m is not None and np.array_equal(m, models[0])
+    assert counts[0] == 5 and n == 5 and it == 0 and inl.all() and len(inl) == 5
+    assert not models[1:].any() and not counts[1:].any()
+
+
 def test_pnp_wave_vs_window_kernel_around_crossover(pkg, oracle, synth):
     """the single-pose problem has two implementations (pnp_wave_kernel up to 1024 points, lm_window_kernel<pnp> above) with
     different summation orders: cross-check them on the SAME inputs around the crossover, both against the oracle."""
