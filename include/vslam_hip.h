@@ -363,6 +363,7 @@ int vslam_check_motion(int num_inliers, const double T_c_l[7], double frame_gap)
  * flag_lm[e]: landmark whose is_inlier flag edge e writes (reference: feat.landmark_id_, :258-264; quirk Q1),
  * or NULL for flag_lm = lm_idx.  lm_inlier: n_lm flags, in/out (:224-266, edges visited in ascending index).
  * update_poses / update_lms: if_update_map / if_update_landmark (:272-287).  chi2_out (n_edge) optional.
+ * n_edge = 0 (a window whose landmarks were all classified out) is VSLAM_OK: poses, landmarks and flags stay, the statistics are zero.
  * K4 = {fx, fy, cx, cy}: the `const cv::Mat& K` argument of optimize_map / optimize_pose_only (optimization.hpp:137-139,
  * :150-152), passed per call; NULL = the context's intrinsics (vslam_params.cam). */
 int vslam_local_ba(vslam_ctx* ctx, int n_kf, double* T_c_w, int n_lm, float* xyz, int n_edge,

@@ -1088,7 +1088,12 @@ static int window_host(vslam_ctx* ctx, int mode, int n_kf, double* T_c_w, int n_
                        const int32_t* lm_idx, const float* uv, const double* K4, const int32_t* flag_lm, int iters, int update_poses, int update_lms,
                        uint8_t* lm_inlier, double* chi2_out, double* thr_out, vslam_lm_stats* stats) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!c || n_kf <= 0 || n_kf > VSLAM_MAX_KF || !T_c_w || n_lm <= 0 || !xyz || n_edge <= 0 || !kf_idx || !lm_idx || !uv || iters < 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (!c || n_kf <= 0 || n_kf > VSLAM_MAX_KF || !T_c_w || n_lm <= 0 || !xyz || n_edge < 0 || (n_edge > 0 && (!kf_idx || !lm_idx || !uv)) || iters < 0) { set_error("bad argument"); return VSLAM_ERR_ARG; }
+    if (n_edge == 0) { // a graph without edges (every landmark of the window classified out): nothing to optimise and no flag to write; poses and landmarks stay
+        if (stats) memset(stats, 0, sizeof(*stats));
+        if (thr_out) { double th = c->p.huber_delta; for (int iteration = 0; iteration < 5; ++iteration) th *= 2; *thr_out = th; } // (:226-252: a ratio of 0 / 0 is never > 0.5)
+        return VSLAM_OK;
+    }
     for (int e = 0; e < n_edge; ++e)
         if (kf_idx[e] < 0 || kf_idx[e] >= n_kf || lm_idx[e] < 0 || lm_idx[e] >= n_lm || (flag_lm && (flag_lm[e] < -1 || flag_lm[e] >= n_lm))) { set_error("edge %d: index out of range", e); return VSLAM_ERR_ARG; }
     // counting sort by landmark (stable)
