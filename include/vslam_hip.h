@@ -939,7 +939,7 @@ int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int
 /* Noticing that the camera is back at a place it has seen: keyframe descriptor blocks are kept in a database that outlives the steps (loops close
  * over thousands of frames, a batch holds max_batch), every query entry is scored against every earlier entry of its sequence by brute force over the
  * raw descriptors on the matrix cores -- no vocabulary, nothing trained -- and the best candidates are verified with the library's own matcher and
- * RANSAC pose stage, which also yields the relative pose a pose-graph back end wants.  The reference has no loop closure.  Additive: vslam_params and
+ * RANSAC pose stage, which also yields the relative pose the pose-graph stage below consumes.  The reference has no loop closure.  Additive: vslam_params and
  * the ABI version are unchanged; the host mirror (host/) does not call the stage.
  *
  * SCORE of query entry i (descriptor rows D_i, n_i of them) against entry j, all integer, hence exact and independent of arrival order:
@@ -1000,6 +1000,73 @@ int vslam_place_select_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, c
  * to RANSAC: identity, its match count, 0 inliers.  Asynchronous; uses the context's matcher and RANSAC scratch. */
 int vslam_place_verify_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, const int32_t* d_cand, int K, int rank, int min_inliers, double* d_T_q_c,
                            int32_t* d_n_matches, int32_t* d_n_inliers);
+
+/* ------------------------------------------------------------------ pose-graph optimisation: loop edges correct the trajectory --- */
+/* What consumes the edges of the place database: a batch of n_graphs independent pose graphs, laid back to back (graph g owns nodes
+ * [node_off[g], node_off[g+1]) and edges [edge_off[g], edge_off[g+1])), each optimised by one persistent workgroup through all its Levenberg-Marquardt
+ * iterations.  The reference has no pose graph.  Additive: vslam_params and the ABI version are unchanged; the host mirror (host/) does not call it.
+ *
+ * PROBLEM.  Node k holds T_k = T_c_w (7 doubles, quaternion x, y, z, w then translation).  An edge is (i, j, Z, w[6]) with GRAPH-LOCAL node ids
+ * i != j: Z measures T_i o T_j^-1 (p_i = Z p_j: the T_q_c of a loop edge with i = q, j = c), w is a diagonal information in tangent order
+ * [upsilon; omega], finite and >= 0.  Residual r = log(Z^-1 o T_i o T_j^-1), cost = sum r' diag(w) r over the ACTIVE edges.  Update T <- exp(delta) o T.
+ * With E = Z^-1 T_i T_j^-1 and A = I - ad(r)/2 + ad(r)^2/12:  dr/d delta_i = A Ad(Z^-1),  dr/d delta_j = -A Ad(E).
+ * GAUGE.  d_fixed[k] != 0 holds node k; NULL holds node 0 of every graph.  A node without an active edge is held too (its block of H is zero).
+ * LM.  (H + lambda diag(H)) delta = -g from lambda_init; a step is accepted when the cost falls, then lambda <- max(lambda / 10, 1e-12); a rejected
+ * step gives lambda <- 10 lambda.  Stops at |delta| < step_tol, at lambda > 1e12, or at max_iters.  All arithmetic is f64.
+ * SOLVER.  Preconditioned conjugate gradients, matrix-free over the edges, to |r| <= pcg_tol |b| or pcg_max_iters.  Two preconditioners
+ * (vslam_set_tuning "pg_precond"): 0 = block-Jacobi (the 6 x 6 diagonal blocks); 1 = chain: the block-tridiagonal part of H + lambda diag(H), i.e. the
+ * diagonal blocks and the blocks of the edges with |i - j| = 1, factorised and applied by a sequential block LDL' sweep; -1 = the library's rule
+ * (DESIGN.md 5.10).  Nodes should therefore be numbered along the odometry chain.
+ * DETERMINISM.  Node sums run over a per-node incidence list in ascending edge order, dot products in an order that depends on the graph's own node
+ * and edge counts only, no floating-point atomics: the same call twice writes the same bytes, and a graph's output in a batch is bit for bit its
+ * output alone.
+ * SAFETY.  Every offset and node id is range-checked on the device.  A graph whose offsets are out of range or out of order is skipped entirely
+ * (only its status word is written); one with a bad node id (outside [0, N) or i == j) or a non-finite pose, measurement or weight (or a negative
+ * weight) has its poses copied through and its status bit set.  Degenerate graphs (0 or 1 node, no edges, every node held, a broken chain, a
+ * component that reaches no held node) are results, not errors: finite output, status 0. */
+#define VSLAM_PG_BAD_INDEX 1    /* an offset or node id out of range: graph skipped                              */
+#define VSLAM_PG_NONFINITE 2    /* a non-finite pose / measurement / weight or a negative weight: graph skipped   */
+#define VSLAM_PG_PCG_CAP 4      /* PCG reached pcg_max_iters in some step (the step is still a descent candidate) */
+#define VSLAM_PG_LAMBDA 8       /* stopped because lambda exceeded 1e12                                           */
+#define VSLAM_PG_SINGULAR 16    /* a diagonal block was not positive definite (zero weights): pivot replaced by 1 */
+typedef struct vslam_pose_graph {
+    int32_t struct_size;          /* sizeof(vslam_pose_graph): set by the caller, checked */
+    int32_t n_graphs;
+    int32_t total_nodes, total_edges;
+    const int32_t* d_node_off;    /* n_graphs + 1 */
+    const int32_t* d_edge_off;    /* n_graphs + 1 */
+    const double* d_T;            /* total_nodes x 7, in */
+    const uint8_t* d_fixed;       /* total_nodes, or NULL: node 0 of every graph */
+    const int32_t* d_edge_i;      /* total_edges, graph-local */
+    const int32_t* d_edge_j;      /* total_edges, graph-local */
+    const double* d_edge_Z;       /* total_edges x 7 */
+    const double* d_edge_w;       /* total_edges x 6 */
+    const uint8_t* d_edge_active; /* total_edges, or NULL: all active */
+    double* d_edge_chi2;          /* total_edges, out: r' diag(w) r of EVERY edge (inactive ones too) at the output poses; NULL = not wanted */
+} vslam_pose_graph;
+typedef struct vslam_pose_graph_params {
+    int32_t struct_size;          /* sizeof(vslam_pose_graph_params) */
+    int32_t max_iters;            /* LM iterations; 0 = evaluate only */
+    int32_t pcg_max_iters;
+    int32_t reserved;
+    double pcg_tol;               /* relative residual */
+    double step_tol;
+    double lambda_init;
+} vslam_pose_graph_params;
+typedef struct vslam_pose_graph_stats {
+    double chi2_init, chi2_final, lambda;
+    int32_t lm_iters, pcg_iters, n_free, status;
+} vslam_pose_graph_stats;
+/* max_iters 50, pcg_max_iters 4000, pcg_tol 1e-10, step_tol 1e-9, lambda_init 1e-4 */
+void vslam_pose_graph_default_params(vslam_pose_graph_params* p);
+/* Optimises every graph of the batch: d_T_out (total_nodes x 7; may be d_T itself) and, when not NULL, d_stats (n_graphs) and graph->d_edge_chi2.
+ * params NULL = the defaults.  max_iters = 0 evaluates only: chi2_init and the edge chi2 are written and the poses copied.  Refuses with
+ * VSLAM_ERR_ARG and a message before it launches anything: a null where a pointer is required, negative counts, a wrong struct_size, parameters out
+ * of range.  Asynchronous on the context stream; the state lives in a growable buffer of the context counted in vslam_device_bytes. */
+int vslam_pose_graph_dev(vslam_ctx* ctx, const vslam_pose_graph* graph, const vslam_pose_graph_params* params, double* d_T_out,
+                         vslam_pose_graph_stats* d_stats);
+/* the status words of the n_graphs graphs of the most recent vslam_pose_graph_dev call, into h_status (host); synchronises the context stream */
+int vslam_pose_graph_status_dev(vslam_ctx* ctx, int n_graphs, int32_t* h_status);
 
 /* ------------------------------------------------------------------ raw device memory helpers ---------- */
 /* For hosts without their own device allocator (the C++ mirror in host/); bench.py passes torch tensors. */

@@ -116,6 +116,24 @@ LOOP_EDGE_DTYPE = np.dtype([("entry_q", "<i4"), ("entry_c", "<i4"), ("seq", "<i4
                             ("n_matches", "<i4"), ("n_inliers", "<i4"), ("accepted", "?"), ("T_q_c", "<f8", (7,))])
 
 
+class PoseGraphBatch(C.Structure):
+    """vslam_pose_graph: a batch of independent pose graphs laid back to back (device pointers); struct_size is filled in by VO.pose_graph_dev"""
+    _fields_ = [("struct_size", C.c_int32), ("n_graphs", C.c_int32), ("total_nodes", C.c_int32), ("total_edges", C.c_int32),
+                ("d_node_off", C.c_void_p), ("d_edge_off", C.c_void_p), ("d_T", C.c_void_p), ("d_fixed", C.c_void_p), ("d_edge_i", C.c_void_p),
+                ("d_edge_j", C.c_void_p), ("d_edge_Z", C.c_void_p), ("d_edge_w", C.c_void_p), ("d_edge_active", C.c_void_p), ("d_edge_chi2", C.c_void_p)]
+
+
+class PoseGraphParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("max_iters", C.c_int32), ("pcg_max_iters", C.c_int32), ("reserved", C.c_int32),
+                ("pcg_tol", C.c_double), ("step_tol", C.c_double), ("lambda_init", C.c_double)]
+
+
+# vslam_pose_graph_stats, one per graph
+POSE_GRAPH_STATS_DTYPE = np.dtype([("chi2_init", "<f8"), ("chi2_final", "<f8"), ("lambda", "<f8"), ("lm_iters", "<i4"), ("pcg_iters", "<i4"),
+                                   ("n_free", "<i4"), ("status", "<i4")])
+PG_BAD_INDEX, PG_NONFINITE, PG_PCG_CAP, PG_LAMBDA, PG_SINGULAR = 1, 2, 4, 8, 16
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("launches", C.c_int32), ("calls", C.c_int32)]
 
@@ -223,6 +241,9 @@ SIGNATURES = {
     "vslam_place_score_dev": (I, [P, P, I, I, I, I, P, I]),
     "vslam_place_select_dev": (I, [P, P, I, I, P, I, I, I, P, P]),
     "vslam_place_verify_dev": (I, [P, P, I, I, P, I, I, I, P, P, P]),
+    "vslam_pose_graph_default_params": (None, [C.POINTER(PoseGraphParams)]),
+    "vslam_pose_graph_dev": (I, [P, C.POINTER(PoseGraphBatch), C.POINTER(PoseGraphParams), P, P]),
+    "vslam_pose_graph_status_dev": (I, [P, I, P]),
     "vslam_dev_alloc": (I, [P, Z]), "vslam_dev_free": (I, [P]), "vslam_dev_upload": (I, [P, P, P, Z]), "vslam_dev_download": (I, [P, P, P, Z]),
     "vslam_dev_memset": (I, [P, P, I, Z]),
 }
@@ -352,6 +373,15 @@ def rectify_build_maps(p, cam, w, h):
     if rc != VSLAM_OK:
         raise VslamError("vslam_rectify_build_maps failed (%d): %s" % (rc, lib.vslam_last_error().decode()))
     return xy, frac
+
+
+def default_pose_graph_params(**kw):
+    """vslam_pose_graph_default_params (max_iters 50, pcg_max_iters 4000, pcg_tol 1e-10, step_tol 1e-9, lambda_init 1e-4), fields overridden by keyword"""
+    p = PoseGraphParams()
+    load_library().vslam_pose_graph_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
 
 
 def _desc(d):
@@ -797,6 +827,51 @@ class VO:
         """matcher + gather + RANSAC pose of every query's rank-`rank` candidate: relative pose, match and inlier counts"""
         self._chk(self.lib.vslam_place_verify_dev(self.h, db.h, q0, nq, d_cand, K, rank, min_inliers, d_T_q_c, d_n_matches, d_n_inliers),
                   "vslam_place_verify_dev")
+
+    # ------------------------------------------------------------ pose-graph optimisation (no counterpart in the reference)
+    def pose_graph_dev(self, graph, params=None, d_T_out=None, d_stats=None):
+        """vslam_pose_graph_dev on a PoseGraphBatch of device pointers: the optimised poses into d_T_out (total_nodes x 7 doubles; may be graph.d_T), the
+        per-graph vslam_pose_graph_stats into d_stats (or None).  Asynchronous.  Semantics in include/vslam_hip.h."""
+        graph.struct_size = C.sizeof(PoseGraphBatch)
+        self._chk(self.lib.vslam_pose_graph_dev(self.h, C.byref(graph), None if params is None else C.byref(params), d_T_out, d_stats), "vslam_pose_graph_dev")
+
+    def pose_graph_status(self, n_graphs):
+        """the status words (PG_* bits) of the graphs of the most recent pose_graph_dev call; synchronises"""
+        st = np.zeros(n_graphs, np.int32)
+        self._chk(self.lib.vslam_pose_graph_status_dev(self.h, n_graphs, st), "vslam_pose_graph_status_dev")
+        return st
+
+    def optimize_pose_graph(self, T, node_off, edges, fixed=None, active=None, params=None, **kw):
+        """A batch of pose graphs from numpy arrays: T (total_nodes, 7) poses T_c_w, node_off (G + 1), edges = dict(off (G + 1), i, j (graph-local
+        node ids), Z (E, 7), w (E, 6)); fixed (total_nodes) and active (E) optional byte masks; params a PoseGraphParams, or its fields by keyword.
+        Uploads, runs, downloads.  Returns dict(T (total_nodes, 7), stats (G records of POSE_GRAPH_STATS_DTYPE), edge_chi2 (E))."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        T = np.ascontiguousarray(T, np.float64).reshape(-1, 7)
+        node_off = np.ascontiguousarray(node_off, np.int32); edge_off = np.ascontiguousarray(edges["off"], np.int32)
+        ei = np.ascontiguousarray(edges["i"], np.int32); ej = np.ascontiguousarray(edges["j"], np.int32)
+        Z = np.ascontiguousarray(edges["Z"], np.float64).reshape(-1, 7); w = np.ascontiguousarray(edges["w"], np.float64).reshape(-1, 6)
+        G, N, E = len(node_off) - 1, len(T), len(ei)
+        assert G >= 0 and len(edge_off) == G + 1 and len(ej) == E and len(Z) == E and len(w) == E
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        t = dict(node_off=up(node_off), edge_off=up(edge_off), T=up(T), ei=up(ei), ej=up(ej), Z=up(Z), w=up(w),
+                 out=torch.zeros((N, 7), dtype=torch.float64, device=dev), chi2=torch.zeros(E, dtype=torch.float64, device=dev),
+                 stats=torch.zeros(max(G, 1) * POSE_GRAPH_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev))
+        if fixed is not None:
+            t["fixed"] = up(np.ascontiguousarray(fixed, np.uint8)); assert len(t["fixed"]) == N
+        if active is not None:
+            t["active"] = up(np.ascontiguousarray(active, np.uint8)); assert len(t["active"]) == E
+        ptr = lambda k: t[k].data_ptr() if k in t and t[k].numel() else None
+        g = PoseGraphBatch(n_graphs=G, total_nodes=N, total_edges=E, d_node_off=t["node_off"].data_ptr(), d_edge_off=t["edge_off"].data_ptr(), d_T=ptr("T"),
+                      d_fixed=ptr("fixed"), d_edge_i=ptr("ei"), d_edge_j=ptr("ej"), d_edge_Z=ptr("Z"), d_edge_w=ptr("w"), d_edge_active=ptr("active"),
+                      d_edge_chi2=ptr("chi2"))
+        if params is None and kw:
+            params = default_pose_graph_params(**kw)
+        torch.cuda.synchronize()   # (the uploads are done before the context stream reads them)
+        self.pose_graph_dev(g, params, ptr("out"), t["stats"].data_ptr())
+        self.sync()
+        stats = t["stats"].cpu().numpy().view(POSE_GRAPH_STATS_DTYPE)[:G].copy()
+        return dict(T=t["out"].cpu().numpy(), stats=stats, edge_chi2=t["chi2"].cpu().numpy())
 
     def profile_enable(self, on=True):
         self._chk(self.lib.vslam_profile_enable(self.h, on), "vslam_profile_enable")

@@ -137,6 +137,7 @@ static const TuneKey kTuneKeys[] = {
     {"track_rule", "VSLAM_TRACK_RULE", &Tuning::track_rule, 0, 1},
     {"rectify_form", "VSLAM_RECTIFY_FORM", &Tuning::rectify_form, 0, 1},
     {"voxel_form", "VSLAM_VOXEL_FORM", &Tuning::voxel_form, 0, 1},
+    {"pg_precond", "VSLAM_PG_PRECOND", &Tuning::pg_precond, 0, 1},
 };
 static int tune_set(Tuning& t, const TuneKey& k, long v) {
     if (v == -1) { t.*(k.field) = -1; return VSLAM_OK; } // back to the library's rule
@@ -248,7 +249,8 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
            "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
            "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel "
-           "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel";
+           "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel "
+           "pose_graph_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -305,7 +307,7 @@ void vslam_destroy(vslam_ctx* ctx) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     orb_tables_free(&c->tab);
-    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc, &c->segbuf, &c->chain}) b->release();
+    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc, &c->segbuf, &c->chain, &c->pgraph}) b->release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
     void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad, c->orb.d_anms_path,
                     c->match.d_train_best, c->rect.d_map[0], c->rect.d_map[1], c->rect.d_tiles[0], c->rect.d_tiles[1]};
@@ -1954,6 +1956,53 @@ int vslam_place_verify_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, c
                                                   v.n + q0, d_gap, 1, nq, v.rows, d_m, v.rows, d_nm)) return rc;
     if (int rc = launch_place_gather(v, q0, nq, d_qitem, d_m, d_nm, min_inliers, d_xyz, d_uv, d_np, d_n_matches, c->stream)) return rc;
     return vslam_pnp_ransac_dev(ctx, d_xyz, d_uv, d_np, v.rows, nq, d_T_q_c, 100, c->p.pnp_reproj_thr, 0.99, nullptr, d_n_inliers, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------- pose graph
+void vslam_pose_graph_default_params(vslam_pose_graph_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(vslam_pose_graph_params);
+    p->max_iters = 50; p->pcg_max_iters = 4000; p->pcg_tol = 1e-10; p->step_tol = 1e-9; p->lambda_init = 1e-4;
+}
+
+// (the checks on the structs come before the one on the context: they need no device)
+int vslam_pose_graph_dev(vslam_ctx* ctx, const vslam_pose_graph* graph, const vslam_pose_graph_params* params, double* d_T_out,
+                         vslam_pose_graph_stats* d_stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!graph) { set_error("vslam_pose_graph_dev: null graph"); return VSLAM_ERR_ARG; }
+    if (graph->struct_size != (int32_t)sizeof(vslam_pose_graph)) { set_error("vslam_pose_graph_dev: vslam_pose_graph struct_size %d, the library has %d", graph->struct_size, (int)sizeof(vslam_pose_graph)); return VSLAM_ERR_ARG; }
+    vslam_pose_graph_params p;
+    vslam_pose_graph_default_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(vslam_pose_graph_params)) { set_error("vslam_pose_graph_dev: vslam_pose_graph_params struct_size %d, the library has %d", params->struct_size, (int)sizeof(vslam_pose_graph_params)); return VSLAM_ERR_ARG; }
+        p = *params;
+    }
+    if (p.max_iters < 0 || p.pcg_max_iters < 1 || !(p.pcg_tol >= 0) || !(p.step_tol >= 0) || !(p.lambda_init > 0) || !(p.lambda_init <= 1e12)) {
+        set_error("vslam_pose_graph_dev: parameters out of range (max_iters >= 0, pcg_max_iters >= 1, pcg_tol >= 0, step_tol >= 0, 0 < lambda_init <= 1e12)");
+        return VSLAM_ERR_ARG;
+    }
+    if (graph->n_graphs < 0 || graph->total_nodes < 0 || graph->total_edges < 0) { set_error("vslam_pose_graph_dev: negative count (n_graphs %d, total_nodes %d, total_edges %d)", graph->n_graphs, graph->total_nodes, graph->total_edges); return VSLAM_ERR_ARG; }
+    if (!graph->d_node_off || !graph->d_edge_off) { set_error("vslam_pose_graph_dev: null d_node_off or d_edge_off"); return VSLAM_ERR_ARG; }
+    if (graph->total_nodes > 0 && (!graph->d_T || !d_T_out)) { set_error("vslam_pose_graph_dev: null d_T or d_T_out"); return VSLAM_ERR_ARG; }
+    if (graph->total_edges > 0 && (!graph->d_edge_i || !graph->d_edge_j || !graph->d_edge_Z || !graph->d_edge_w)) { set_error("vslam_pose_graph_dev: null d_edge_i, d_edge_j, d_edge_Z or d_edge_w"); return VSLAM_ERR_ARG; }
+    if (!c) { set_error("vslam_pose_graph_dev: null context"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    if (int rc = launch_pose_graph(*graph, p, c->tune.pg_precond, d_T_out, d_stats, c->pgraph, c->stream)) return rc;
+    c->pgraph_n = graph->n_graphs;
+    return VSLAM_OK;
+}
+
+int vslam_pose_graph_status_dev(vslam_ctx* ctx, int n_graphs, int32_t* h_status) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!h_status) { set_error("vslam_pose_graph_status_dev: null h_status"); return VSLAM_ERR_ARG; }
+    if (n_graphs < 0) { set_error("vslam_pose_graph_status_dev: negative n_graphs %d", n_graphs); return VSLAM_ERR_ARG; }
+    if (!c) { set_error("vslam_pose_graph_status_dev: null context"); return VSLAM_ERR_ARG; }
+    if (n_graphs > c->pgraph_n) { set_error("vslam_pose_graph_status_dev: %d graphs asked for, the most recent vslam_pose_graph_dev call had %d", n_graphs, c->pgraph_n); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    if (n_graphs > 0) VS_HIP(hipMemcpyAsync(h_status, c->pgraph.p, sizeof(int32_t) * (size_t)n_graphs, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return VSLAM_OK;
 }
 
 // float4 streaming copy of `bytes` (src -> dst, both allocated here), `reps` timed launches after one warm-up, hipEvents on the

@@ -257,6 +257,7 @@ struct Tuning {
                               // is judged by the pose stage's inlier rule on its landmark's map position (:260-270, :277).  0 = the convention of rounds 4-5: only when the
                               // last-frame keypoint owns a valid depth (kept for before / after measurements)
     int rectify_form = -1;    // VSLAM_RECTIFY_FORM: source side of rectify_kernel -- 0 = direct byte gathers, 1 = each tile's source box staged in LDS (default 1; tiles whose box does not pay gather either way)
+    int pg_precond = -1;      // VSLAM_PG_PRECOND: preconditioner of pose_graph_kernel's conjugate gradients -- 0 = block-Jacobi, 1 = chain (block-tridiagonal); default: the rule of DESIGN.md 5.10
     int voxel_form = -1;      // VSLAM_VOXEL_FORM: voxel_fuse_kernel -- 0 = every point straight into the global table, 1 = a workgroup sums its image tile in an LDS hash table first (same table either way)
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
 };
@@ -436,6 +437,12 @@ int launch_place_verify_prep(const PlaceView& v, int nq, const int32_t* d_cand, 
 int launch_place_gather(const PlaceView& v, int q0, int nq, const int32_t* d_qitem, const vslam_dmatch* d_m, const int32_t* d_nm, int min_inliers, float* d_xyz,
                         float* d_uv, int32_t* d_n, int32_t* d_n_matches, hipStream_t stream);
 
+// ----------------------------------------------------------------------------------------------- pose graph
+// posegraph_kernels.hip: one persistent workgroup per graph through all LM iterations (include/vslam_hip.h "pose-graph optimisation").  The per-graph
+// state is carved from `buf`; d_status (n_graphs words, the library's own copy for vslam_pose_graph_status_dev) is its first slot.  precond: -1 / 0 / 1.
+int launch_pose_graph(const vslam_pose_graph& g, const vslam_pose_graph_params& p, int precond, double* d_T_out, vslam_pose_graph_stats* d_stats, DevBuf& buf,
+                      hipStream_t stream);
+
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {
     vslam_params p;
@@ -464,6 +471,8 @@ struct Ctx {
     int32_t* ids; int ids_cap;  // vslam_set_window_ids: the caller's landmark-id buffer the window builders also fill (null: none)
     int ids_kp_cap;       // kp_capacity of the most recent builder call that wrote ids (the stride of the ids' frame index)
     DevBuf chain{"chain scratch", &dev_bytes};   // state and staging batch of vslam_ba_chain_dev
+    DevBuf pgraph{"pose-graph state", &dev_bytes}; // status words and per-graph state of vslam_pose_graph_dev
+    int pgraph_n;         // graphs of the most recent vslam_pose_graph_dev call (0: none yet)
     bool orb_ok;          // img_w, img_h >= 64: the ORB entry points serve this context (a smaller one is a rectification target only)
 };
 

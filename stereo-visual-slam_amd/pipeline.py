@@ -650,10 +650,12 @@ class KeyframePipeline:
         kf_frame, evicted, ba_T, valid = self._trajectory_inputs()
         return assemble_trajectory(kf_frame, evicted, ba_T, window_valid=valid)
 
-    def dense_map_inputs(self):
+    def dense_map_inputs(self, poses=None):
         """what dense_map() fuses: (T_c_w (B, 7) float64, map_id (B,) int32) -- every frame of trajectories() at its BA-refined pose with its segment's
-        index (0 without a segment table) as map id; a frame outside the trajectories has map id -1 and the identity pose"""
-        trajs = self.trajectories()
+        index (0 without a segment table) as map id; a frame outside the trajectories has map id -1 and the identity pose.  poses: one
+        (frame_ids, T_c_w) per segment to use instead of trajectories(), e.g. what close_loops() returned"""
+        trajs = self.trajectories() if poses is None else poses
+        assert len(trajs) == (len(self.seg_first) - 1 if self.seg_first is not None else 1), "poses: one (frame_ids, T_c_w) per segment"
         assert len(trajs) <= 1023, "a voxel map holds at most 1023 maps (segments)"
         first = self.seg_first if self.seg_first is not None else np.array([0, self.B])
         T = np.tile(np.array([0, 0, 0, 1, 0, 0, 0], np.float64), (self.B, 1))
@@ -663,15 +665,19 @@ class KeyframePipeline:
             map_id[first[s_] + ids] = s_
         return T, map_id
 
-    def dense_map(self, voxel_size=0.2, log2_capacity=22, z_min=None, z_max=None, step=1, voxel_map=None):
+    def dense_map(self, voxel_size=0.2, log2_capacity=22, z_min=None, z_max=None, step=1, voxel_map=None, poses=None):
         """The dense map of the last step (depth="sgbm", ba_windows="tracks"): the SGBM disparity and the left image of every frame trajectories()
         returns, reprojected at that frame's BA-refined pose and fused into a VoxelMap (vslam_voxel_fuse_disparity_dev) -- map id = the segment index.
         z_min / z_max default to the context's depth_min / depth_reliable (the reference trusts stereo depth below 40 m only); every step-th pixel.
         voxel_map: a VoxelMap of this pipeline's context to accumulate into over several steps (voxel_size / log2_capacity then go unused); otherwise
-        a new one.  Returns the map: .extract() / .stats() read it, write_ply(path, vm.extract()) writes it."""
+        a new one.  poses: the corrected trajectories close_loops() returned, in place of the BA poses (None: the BA poses).
+        Returns the map: .extract() / .stats() read it, write_ply(path, vm.extract()) writes it."""
         assert self.depth == "sgbm", "dense_map needs depth='sgbm': it fuses the SGBM disparity maps"
         assert self.with_ba and self.ba_windows == "tracks", "dense_map needs ba_windows='tracks': the poses are the BA windows'"
-        T, map_id = self.dense_map_inputs()   # (synchronises: the step is complete)
+        if poses is not None:
+            self.vo.sync()
+            torch.cuda.synchronize(self.dev)
+        T, map_id = self.dense_map_inputs() if poses is None else self.dense_map_inputs(poses)   # (synchronises: the step is complete)
         p = self.vo.params
         z_min = p.depth_min if z_min is None else float(z_min)
         z_max = p.depth_reliable if z_max is None else float(z_max)
@@ -774,6 +780,29 @@ class KeyframePipeline:
         for i, (_, _, row) in enumerate(rows_out):
             out[i] = row
         return out
+
+    def close_loops(self, edges, frame_offset=0, w_odo=(1.0, 1.0), w_loop=(1.0, 1.0), reject_chi2=None, params=None, motion_limit=5.0):
+        """The last step's trajectories corrected by loop-closure edges (include/vslam_hip.h "pose-graph optimisation"): a PoseGraph with one graph
+        per segment -- nodes = the frames trajectories() returns, odometry edges between consecutive ones from the BA poses, one loop edge per
+        accepted row of `edges` (what loop_closures() returned, with the same frame_offset) -- optimised in one call, all segments side by side.
+        A row belongs to the segment its frames lie in (its `seq` is not consulted: loop_closures may have given several segments one sequence id);
+        rows that are not accepted, or whose frames are not both nodes of one segment -- frames of another step, of two segments, or ones the keyframe
+        gate dropped -- are counted in .pose_graph.report, not dropped silently, and so are the odometry edges that exceed the motion limit
+        (PoseGraph: a pose tracked across a cut in the recording is not a measurement).  w_odo, w_loop, motion_limit, reject_chi2, params: PoseGraph and
+        PoseGraph.optimize (no measured default for the weights exists).  Returns what trajectories() returns, corrected; dense_map(poses=...) takes
+        it.  The BA landmarks are not moved, and the frames of other steps are out of reach: each step starts a world of its own."""
+        from .posegraph import PoseGraph
+        first = np.asarray(self.seg_first if self.seg_first is not None else [0, self.B], np.int64)
+        pg = PoseGraph(w_odo=w_odo, w_loop=w_loop, motion_limit=motion_limit)
+        for s_, (ids, Ts) in enumerate(self.trajectories()):
+            pg.add_trajectory(s_, np.asarray(ids, np.int64) + int(first[s_]) + int(frame_offset), Ts)
+        rows = np.array(edges, copy=True)
+        seg = np.searchsorted(first, rows["frame_q"].astype(np.int64) - int(frame_offset), side="right") - 1
+        rows["seq"] = np.where((seg >= 0) & (seg < len(first) - 1), seg, -1)
+        pg.add_loop_edges(rows)
+        self.pose_graph = pg
+        out = pg.optimize(self.vo, reject_chi2=reject_chi2, params=params)
+        return [(ids - int(first[s_]) - int(frame_offset), Ts) for s_, (ids, Ts) in enumerate(out)]
 
     def close(self):
         self.vo.close()
