@@ -799,7 +799,7 @@ int vslam_ba_deferred_dev(vslam_ctx* ctx, int n_windows, int32_t* h_deferred);
  * params.huber_delta).  n observations of n world points through ONE pose; host buffers, synchronous; any output may be NULL. */
 int vslam_edge_jacobians(vslam_ctx* ctx, int n, const float* xyz_w, const float* uv, const double T_c_w[7], const double* K4,
                          double* err, double* J_pose, double* J_point, double* chi2, double* huber_w);
-/* Kernel-choice overrides of a context (tuning aid, and how the tests force every kernel path): name in {"orb_fuse_min", "anms_cap" (pixels at which the ANMS radius walk stops early, 0 = never; same output either way, see vslam_orb_anms_path_dev), "sgbm_fuse_min",
+/* Kernel-choice overrides of a context (tuning aid, and how the tests force every kernel path): name in {"orb_fuse_min", "orb_tiled" (0 | 1: the fused ORB kernel writes the levels that the orientation and descriptor kernels sample row-major | as 16 x 8 pixel tiles of one cache line each; default 1; same bits either way), "anms_cap" (pixels at which the ANMS radius walk stops early, 0 = never; same output either way, see vslam_orb_anms_path_dev), "sgbm_fuse_min",
  * "sgbm_fwd_min" (items per call from which the fused kernel is used), "sgbm_fw_rows" (32 | 64), "pose_only_window", "pose_only_waves" (0 = automatic | 12 | 4: waves per window of the schedule's pose-only kernel; default by the number of windows in the call; same bits either way), "pnp_window", "ba_adaptive" (0 | 1), "rectify_form" (0 | 1: source side of the rectification kernel, direct gathers | source boxes staged in LDS; same bytes), "voxel_form" (0 | 1: vslam_voxel_fuse_disparity_dev inserts every point directly | sums each image tile in LDS first; same table), "ba_lanes" (256 | 512: lanes per window of the
  * LDS-resident optimize_map kernel; default by the number of windows in the call; the results do not depend on it), "track_rule" (0 | 1: see
  * vslam_build_windows_dev; this one changes RESULTS, it is the before / after switch of round 6)};

@@ -124,6 +124,7 @@ static int dev_alloc(Ctx* c, T** p, size_t n) {
 struct TuneKey { const char* name; const char* env; int Tuning::*field; int lo, hi; };
 static const TuneKey kTuneKeys[] = {
     {"orb_fuse_min", "VSLAM_ORB_FUSE_MIN", &Tuning::orb_fuse_min, 0, 1 << 30},
+    {"orb_tiled", "VSLAM_ORB_TILED", &Tuning::orb_tiled, 0, 1},
     {"anms_cap", "VSLAM_ANMS_CAP", &Tuning::anms_cap, 0, 1 << 30},
     {"sgbm_fuse_min", "VSLAM_SGBM_FUSE_MIN", &Tuning::sgbm_fuse_min, 0, 1 << 30},
     {"sgbm_fwd_min", "VSLAM_SGBM_FWD_MIN", &Tuning::sgbm_fwd_min, 0, 1 << 30},
@@ -175,6 +176,8 @@ static int orb_status_check(Ctx* c, int B) {
 // Images per call from which orb_pyrblur_kernel replaces the separate resize + blur (+ FAST) kernels; Tuning::orb_fuse_min overrides it
 constexpr int kOrbFuseMinDefault = 96;
 static int orb_fuse_min(const Ctx* c) { return c->tune.orb_fuse_min >= 0 ? c->tune.orb_fuse_min : kOrbFuseMinDefault; }
+// The fused kernel writes the blurred pyramid line-tiled for orb_describe_kernel<true> unless Tuning::orb_tiled = 0; the separate blur kernel is row-major always
+static bool orb_tiled(const Ctx* c, bool fused) { return fused && c->tune.orb_tiled != 0; }
 
 // detect + (ANMS) + (describe) on device-resident images
 static int orb_pipeline(Ctx* c, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, int anms_num, int regroup, bool describe,
@@ -188,8 +191,9 @@ static int orb_pipeline(Ctx* c, const uint8_t* d_imgs, size_t img_bytes, int pit
     // (0.36 vs 0.43 ms for two images).  [r6] With FAST inside the tile pass and the blur on the matrix cores the fused kernel wins from ~64 images on
     // (128 images: 0.89 vs 0.96 ms, 256: 1.35 vs 1.55; round 5's break-even was ~300).  Tuning::orb_fuse_min overrides the threshold (tests run both paths).
     const bool fused = describe && B >= orb_fuse_min(c);
+    if (describe) c->orb.blur_tiled = orb_tiled(c, fused);
     if (fused) { // [r6] ... and FAST + NMS of every level from the same staged tile
-        if ((rc = launch_orb_pyrblur(c->plan, c->tab, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, c->orb.d_blur, c->p.fast_threshold, c->orb.d_corners,
+        if ((rc = launch_orb_pyrblur(c->plan, c->tab, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, c->orb.d_blur, c->orb.blur_tiled, c->orb.d_rawt, c->p.fast_threshold, c->orb.d_corners,
                                      c->orb.d_corner_cnt, c->orb.d_status, c->stream))) return rc;
     } else {
         if ((rc = launch_orb_pyramid(c->plan, c->tab, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, c->stream))) return rc;
@@ -201,11 +205,12 @@ static int orb_pipeline(Ctx* c, const uint8_t* d_imgs, size_t img_bytes, int pit
     if ((rc = launch_orb_anms(c->plan, B, c->orb.d_sel, c->orb.d_sel_cnt, c->plan.sel_cap, anms_num, regroup, d_kps, nullptr, c->orb.d_order, c->p.kp_capacity,
                               d_count, c->orb.d_status, c->orb.d_rad, c->tune.anms_cap, c->orb.d_anms_path, c->stream))) return rc;
     // orientation (and the rBRIEF rotation) only for the keypoints the ANMS kept
-    if ((rc = launch_orb_orient(c->plan, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, d_kps, c->orb.d_cs, c->orb.d_order, c->p.kp_capacity, d_count, c->stream))) return rc;
+    if ((rc = launch_orb_orient(c->plan, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, d_kps, c->orb.d_cs, c->orb.d_order, c->p.kp_capacity, d_count,
+                                fused && c->orb.blur_tiled ? c->orb.d_rawt : nullptr, c->stream))) return rc; // (the tiled raw copy exists when this call's fused kernel wrote it)
     if (describe) {
         if (!fused && (rc = launch_orb_blur(c->plan, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, c->orb.d_blur, c->stream))) return rc;
         if ((rc = launch_orb_describe(c->plan, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, c->orb.d_blur, d_kps, c->orb.d_cs, c->orb.d_order, c->p.kp_capacity, d_count,
-                                      d_desc, c->stream))) return rc;
+                                      d_desc, c->orb.blur_tiled, c->stream))) return rc;
     }
     if (getenv("VSLAM_ORB_PROFILE")) orb_debug_dump(c->stream);
     return VSLAM_OK;
@@ -291,6 +296,7 @@ int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** ou
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_sel_cnt, B * kNLevels);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_status, B);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_blur, B * c->plan.blur_bytes);
+    if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_rawt, B * c->plan.blur_bytes);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_cs, B * (size_t)p->kp_capacity);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_order, B * (size_t)p->kp_capacity);
     if (rc == VSLAM_OK) rc = dev_alloc(c, &c->orb.d_rad, B * (size_t)kMaxRows);
@@ -309,7 +315,7 @@ void vslam_destroy(vslam_ctx* ctx) {
     orb_tables_free(&c->tab);
     for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc, &c->segbuf, &c->chain, &c->pgraph}) b->release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
-    void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_cs, c->orb.d_order, c->orb.d_rad, c->orb.d_anms_path,
+    void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_rawt, c->orb.d_cs, c->orb.d_order, c->orb.d_rad, c->orb.d_anms_path,
                     c->match.d_train_best, c->rect.d_map[0], c->rect.d_map[1], c->rect.d_tiles[0], c->rect.d_tiles[1]};
     for (void* q : ptrs) if (q) hipFree(q);
     if (c->prof) {
@@ -450,13 +456,14 @@ int vslam_orb_compute(vslam_ctx* ctx, const uint8_t* img, int w, int h, int stri
     VS_HIP(hipMemcpyAsync(d_n, &nn, sizeof(nn), hipMemcpyHostToDevice, c->stream));
     VS_HIP(hipMemsetAsync(c->orb.d_status, 0, sizeof(int32_t), c->stream));
     const bool fused = 1 >= orb_fuse_min(c); // (one image: the separate kernels unless a test forces the fused one)
-    if (fused) { if ((rc = launch_orb_pyrblur(c->plan, c->tab, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->orb.d_blur, 0, nullptr, nullptr, nullptr, c->stream))) return rc; }
+    c->orb.blur_tiled = orb_tiled(c, fused);
+    if (fused) { if ((rc = launch_orb_pyrblur(c->plan, c->tab, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->orb.d_blur, c->orb.blur_tiled, nullptr, 0, nullptr, nullptr, nullptr, c->stream))) return rc; }
     else {
         if ((rc = launch_orb_pyramid(c->plan, c->tab, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->stream))) return rc;
         if ((rc = launch_orb_blur(c->plan, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->orb.d_blur, c->stream))) return rc;
     }
     if ((rc = launch_anms_flat(1, d_in, d_n, kc, 0, 1, w, h, d_kps, c->orb.d_cs, nullptr, kc, d_cnt, c->orb.d_status, c->orb.d_rad, c->tune.anms_cap, c->orb.d_anms_path, c->stream))) return rc;
-    if ((rc = launch_orb_describe(c->plan, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->orb.d_blur, d_kps, c->orb.d_cs, nullptr, kc, d_cnt, d_desc, c->stream))) return rc;
+    if ((rc = launch_orb_describe(c->plan, d_img, (size_t)dp * h, dp, 1, c->orb.d_pyr, c->orb.d_blur, d_kps, c->orb.d_cs, nullptr, kc, d_cnt, d_desc, c->orb.blur_tiled, c->stream))) return rc;
     int32_t m = 0;
     VS_HIP(hipMemcpyAsync(&m, d_cnt, sizeof(m), hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipStreamSynchronize(c->stream));
@@ -501,6 +508,15 @@ int vslam_orb_level(vslam_ctx* ctx, int item, int level, int blurred, uint8_t* o
     const uint8_t* src = blurred ? c->orb.d_blur + (size_t)item * c->plan.blur_bytes + c->plan.blur_off[level]
                                  : c->orb.d_pyr + (size_t)item * c->plan.pyr_bytes + L.pyr_off;
     VS_HIP(hipStreamSynchronize(c->stream));
+    if (blurred && c->orb.blur_tiled) { // the last producer wrote the level line-tiled: fetch it as it lies and de-tile here (a diagnostic: no kernel for it)
+        const int pitch = (L.w + 63) & ~63;
+        std::vector<uint8_t> lv((size_t)pitch * tiled_rows(L.h));
+        VS_HIP(hipMemcpy(lv.data(), src, lv.size(), hipMemcpyDeviceToHost));
+        for (int y = 0; y < L.h; ++y)
+            for (int x = 0; x < L.w; ++x) out[(size_t)y * out_stride + x] = lv[tiled_offset(x, y, pitch / kTileCols)];
+        *w = L.w; *h = L.h;
+        return VSLAM_OK;
+    }
     VS_HIP(hipMemcpy2D(out, (size_t)out_stride, src, (size_t)((L.w + 63) & ~63), (size_t)L.w, (size_t)L.h, hipMemcpyDeviceToHost));
     *w = L.w; *h = L.h;
     return VSLAM_OK;

@@ -17,12 +17,16 @@
 //                           radius, ordered compaction, cv::ORB::compute's border cull + regroup by octave
 //   orb_orient_kernel       intensity-centroid angle of the keypoints the ANMS kept: a wave per keypoint, 8 rows x 32 bytes per load instruction, v_dot4 moments
 //   orb_describe_kernel     a wave per keypoint, software-pipelined: the 39 x 40 patch of the BLURRED level staged in LDS, 256 rotated tests, 4 bits per lane
+//   line-tiled levels       behind the fused kernel (Tuning::orb_tiled) the blurred pyramid and a copy of the raw levels are stored as 16 x 8 pixel tiles of one
+//                           128-byte line each (tiled_offset, vslam_internal.h); orb_orient_kernel<true> / orb_describe_kernel<true> fetch whole lines: a third of the
+//                           lines per patch of the row-major gathers.  The <false> instances and the separate kernels read row-major levels as before
 // Float expressions that must round like the CPU (no FMA contraction) use explicit __f*_rn intrinsics; the file is
 // also compiled with -ffp-contract=off.
 #include "vslam_internal.h"
 
 #include <math.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "orb_pattern.inc"
@@ -193,7 +197,8 @@ int orb_plan_init(OrbPlan* plan, int w, int h, int nfeatures, int kp_capacity) {
         L.tab_off = tab; tab += L.w;
     }
     int blur = 0;
-    for (int l = 0; l < kNLevels; ++l) { plan->blur_off[l] = blur; blur += ((plan->lv[l].w + 63) & ~63) * plan->lv[l].h; }
+    // (whole tile rows: the level's bytes in the line-tiled layout, see tiled_offset; the row-major layout leaves the padding rows untouched)
+    for (int l = 0; l < kNLevels; ++l) { plan->blur_off[l] = blur; blur += ((plan->lv[l].w + 63) & ~63) * tiled_rows(plan->lv[l].h); }
     plan->blur_bytes = (blur + 255) & ~255;
     plan->pyr_bytes = (pyr + 255) & ~255;
     plan->corner_total = corners;
@@ -956,10 +961,21 @@ __device__ const IcLaneTable g_ic_lane = make_ic_lane_table();
 // mask |u| <= umax[|v|] and the weights u + 15 are per-lane constants, so a keypoint is 8 v_dot4_u32_u8 + 4 multiply-adds per lane (exact integers).  Two
 // keypoints per trip; their four moments are summed over the wave with a halving butterfly (7 exchanges instead of 24).  The angle, its store and the f64 cos /
 // sin of the rBRIEF rotation are done after the walk, one lane per keypoint.
+// TILED: the patches come from the line-tiled raw copy (d_rawt: tiled_offset, the plan of the blurred pyramid).  The 31 x 31 patch whose corner sits at
+// (x mod 16, y mod 8) of its first tile spans at most 3 x 5 tiles = 120 chunks of 16 bytes: two 16-byte loads per lane, lanes 8 k .. 8 k + 7 on the eight rows
+// of one tile -- about 14 whole lines per keypoint where the row-major gather touches about 38.  The tiles are re-staged in LDS (48 bytes x 40 rows per keypoint, four
+// keypoints per wave) and read back in the lane layout above: two aligned dwords and one v_alignbyte with a wave-uniform shift per row slot, so the weight table, the
+// dot products and the butterfly are the same.  Tiles of the 3 x 5 block without a pixel of the patch are not loaded (they may lie beyond the level), nor is anything
+// for a keypoint without a patch; byte 31 of a row slot (weight 0) may come from such a tile.
+constexpr int kOriTilesX = 3, kOriTilesY = 5, kOriTPitch = kTileCols * kOriTilesX, kOriTRows = kTileRows * kOriTilesY, kOriTBytes = kOriTPitch * kOriTRows;
+static_assert(kTileCols - 1 + 31 <= kOriTPitch && kTileRows - 1 + 31 <= kOriTRows && 4 * ((kTileCols - 1) / 4 + 7) + 8 <= kOriTPitch, "patch and read-back window fit the staged tiles at every alignment");
+struct RawTiledTable { int off[kNLevels]; };
+template <bool TILED>
 __global__ __launch_bounds__(kOrientThreads) void orb_orient_kernel(LevelTable T, const uint8_t* __restrict__ d_imgs, size_t img_bytes, int pitch0,
                                                                   const uint8_t* __restrict__ d_pyr, size_t pyr_bytes,
                                                                   vslam_keypoint* __restrict__ d_kps, float2* __restrict__ d_cs, const int32_t* __restrict__ d_order,
-                                                                  int kp_capacity, const int32_t* __restrict__ d_count, int nb, int B) {
+                                                                  int kp_capacity, const int32_t* __restrict__ d_count, int nb, int B,
+                                                                  const uint8_t* __restrict__ d_rawt, size_t rawt_bytes, RawTiledTable RT) {
     int b, bx;
     if (!xcd_image_block(nb, B, b, bx)) return; // (uniform)
     const int n = min(d_count[b], kp_capacity);
@@ -1045,7 +1061,65 @@ __global__ __launch_bounds__(kOrientThreads) void orb_orient_kernel(LevelTable T
             if (k0 + u < cnt) { if (lane & 4) s_m01[at] = r; else s_m10[at] = r; }
         }
     };
-    if (cnt > 0) {
+    if constexpr (TILED) {
+        __shared__ __attribute__((aligned(16))) uint8_t s_tiles[kOrientWaves][4][kOriTBytes];
+        uint8_t* const wt_lds = &s_tiles[wave][0][0];
+        const uint8_t* rawt0 = d_rawt + (size_t)b * rawt_bytes;
+        // this lane's chunks: row tr of tile t = (lane >> 3) + 8 it of the block (t < 15), tile column t % 3, tile row t / 3
+        const int tr = lane & 7;
+        int ttx[2], tty[2];
+#pragma unroll
+        for (int it = 0; it < 2; ++it) { const int t = (lane >> 3) + 8 * it; tty[it] = t / kOriTilesX; ttx[it] = t - kOriTilesX * tty[it]; }
+        auto request_t = [&](int k0, uint4 (&tv)[4][2]) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int x0 = __builtin_amdgcn_readlane(my_x, k0 + u) - 15, y0 = __builtin_amdgcn_readlane(my_y, k0 + u) - 15, l = __builtin_amdgcn_readlane(my_l, k0 + u);
+                const bool live = __builtin_amdgcn_readlane(my_ok, k0 + u) != 0; // (uniform) a patch inside the level: see tiled_offset
+                const int tpr = T.pitch[l] >> 4;
+                const int ntx = live ? ((x0 & 15) + 30) >> 4 : -1, nty = ((y0 & 7) + 30) >> 3; // last tile column / row that holds a pixel of the patch
+                const uint8_t* org = rawt0 + RT.off[l] + (size_t)tiled_offset(x0 & ~15, y0 & ~7, tpr);
+#pragma unroll
+                for (int it = 0; it < 2; ++it) {
+                    tv[u][it] = make_uint4(0u, 0u, 0u, 0u);
+                    if (ttx[it] <= ntx && tty[it] <= nty) // (tile 15 of the second load: tty = 5 > nty)
+                        tv[u][it] = *reinterpret_cast<const uint4*>(org + (__umul24((uint32_t)tty[it], (uint32_t)tpr) + (uint32_t)ttx[it]) * kTileBytes + 16 * tr);
+                }
+            }
+        };
+        auto stage_t = [&](const uint4 (&tv)[4][2]) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int it = 0; it < 2; ++it)
+                    if (tty[it] < kOriTilesY) *reinterpret_cast<uint4*>(wt_lds + u * kOriTBytes + (kTileRows * tty[it] + tr) * kOriTPitch + kTileCols * ttx[it]) = tv[u][it];
+        };
+        auto readback_t = [&](int k0, uint32_t (&px)[4][4]) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int xo = (__builtin_amdgcn_readlane(my_x, k0 + u) - 15) & 15, yo = (__builtin_amdgcn_readlane(my_y, k0 + u) - 15) & 7; // uniform
+                const uint32_t* base = reinterpret_cast<const uint32_t*>(wt_lds + u * kOriTBytes + yo * kOriTPitch) + (xo >> 2) + cx;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const uint32_t lo = base[rsel[s] * (kOriTPitch / 4)], hi = base[rsel[s] * (kOriTPitch / 4) + 1];
+                    px[u][s] = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)(xo & 3));
+                }
+            }
+        };
+        if (cnt > 0) {
+            uint4 tv[4][2];
+            request_t(0, tv);
+            for (int k0 = 0; k0 < cnt; k0 += 4) { // (uniform)
+                stage_t(tv);
+                if (k0 + 4 < cnt) request_t(k0 + 4, tv); // the next four keypoints' tiles are in flight while these four are summed
+                __builtin_amdgcn_wave_barrier(); // LDS traffic of one wave is ordered; this only pins the compiler
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                uint32_t px[4][4];
+                readback_t(k0, px);
+                reduce_store(k0, px);
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+    } else if (cnt > 0) {
         uint32_t pa[4][4], pb[4][4];
         request(0, pa);
         for (int k0 = 0; k0 < cnt; k0 += 8) { // (uniform)
@@ -1072,13 +1146,20 @@ __global__ __launch_bounds__(kOrientThreads) void orb_orient_kernel(LevelTable T
 }
 
 int launch_orb_orient(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr, vslam_keypoint* d_kps,
-                      float2* d_cs, const int32_t* d_order, int kp_capacity, const int32_t* d_count, hipStream_t stream) {
+                      float2* d_cs, const int32_t* d_order, int kp_capacity, const int32_t* d_count, const uint8_t* d_rawt, hipStream_t stream) {
     LevelTable T;
     fill_level_table(plan, &T);
+    RawTiledTable RT;
+    for (int l = 0; l < kNLevels; ++l) RT.off[l] = plan.blur_off[l];
     if (kp_capacity > kOrientPerWave * kOrientBlocks * kOrientWaves) { set_error("kp_capacity %d exceeds the orientation walk (%d)", kp_capacity, kOrientPerWave * kOrientBlocks * kOrientWaves); return VSLAM_ERR_ARG; }
     ProfScope prof__(stream, "orb_orient_kernel");
-    hipLaunchKernelGGL(orb_orient_kernel, dim3(kOrientBlocks * ((B + 7) / 8 * 8)), dim3(kOrientThreads), 0, stream, T, d_imgs, img_bytes, pitch, d_pyr,
-                       (size_t)plan.pyr_bytes, d_kps, d_cs, d_order, kp_capacity, d_count, kOrientBlocks, B);
+    // (d_rawt: the line-tiled raw copy orb_pyrblur_kernel wrote in this call; nullptr: the row-major pyramid)
+    if (d_rawt)
+        hipLaunchKernelGGL(orb_orient_kernel<true>, dim3(kOrientBlocks * ((B + 7) / 8 * 8)), dim3(kOrientThreads), 0, stream, T, d_imgs, img_bytes, pitch, d_pyr,
+                           (size_t)plan.pyr_bytes, d_kps, d_cs, d_order, kp_capacity, d_count, kOrientBlocks, B, d_rawt, (size_t)plan.blur_bytes, RT);
+    else
+        hipLaunchKernelGGL(orb_orient_kernel<false>, dim3(kOrientBlocks * ((B + 7) / 8 * 8)), dim3(kOrientThreads), 0, stream, T, d_imgs, img_bytes, pitch, d_pyr,
+                           (size_t)plan.pyr_bytes, d_kps, d_cs, d_order, kp_capacity, d_count, kOrientBlocks, B, d_rawt, (size_t)plan.blur_bytes, RT);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }
@@ -1677,6 +1758,8 @@ __device__ const BlurMfmaLane g_blur_mfma_lane = make_blur_mfma_lane();
 struct PyrBlurArgs {
     const uint8_t* src_base; size_t src_img_stride; int spitch, sw, sh;      // level l (raw)
     uint8_t* blur_base; size_t blur_img_stride; int bpitch;                  // blurred level l
+    int blur_tiled;                                                          // ... stored line-tiled (tiled_offset) instead of row-major
+    uint8_t* rawt_base; size_t rawt_img_stride;                              // line-tiled copy of the raw level l for orb_orient_kernel<true> (pitch bpitch; nullptr: none)
     uint8_t* dst_base; size_t dst_img_stride; int dpitch, dw, dh;            // level l + 1 (nullptr at the last level)
     const int* xofs; const short* ialpha; const int* yofs; const short* ibeta; // resize tables of level l + 1
     const int* tile_dx; const int* tile_dy;                                  // output ownership per tile column / row
@@ -1827,19 +1910,32 @@ __global__ __launch_bounds__(64 * NW, 8) void orb_pyrblur_kernel(PyrBlurArgs a) 
             }
         }
         __syncthreads();
-        // ---- rows of 256 contiguous bytes out of the staged tile; the lane that read a chunk zeroes it (the FAST phase needs a zeroed score tile)
+        // ---- 16-byte chunks (16 columns of one row) out of the staged tile; the lane that read a chunk zeroes it (the FAST phase needs a zeroed score tile).
+        // Row-major: 16 consecutive lanes store the 256 contiguous bytes of a row.  Line-tiled (a.blur_tiled, uniform): eight consecutive lanes store the eight
+        // rows of ONE 16 x 8 tile of the level, a whole 128-byte line (ox and oy are multiples of the tile size); the next eight lanes take the tile eight
+        // to the right, so that the sixteen LDS reads of a pass, 272 r + 16 cc, fall into sixteen different 16-byte bank groups.
+        // The line-tiled copy of the RAW level (a.rawt_base, uniform; only with a.blur_tiled) leaves with the same chunk map and the same offsets: the staged raw
+        // tile is intact until the NMS.  Its pixel columns start at byte 4 of a staged row, so a chunk is four dword reads; columns past W are reflected pixels: padding.
         const uint4 z4 = make_uint4(0u, 0u, 0u, 0u);
+        const int tpr = a.bpitch >> 4;
+        uint8_t* dstr = a.rawt_base ? a.rawt_base + (size_t)b * a.rawt_img_stride : nullptr;
 #pragma unroll
         for (int i = 0; i < (kBlurTileH * 16) / NT; ++i) {
-            const int chunk = threadIdx.x + i * NT, r = chunk >> 4, cc = chunk & 15;
+            const int chunk = threadIdx.x + i * NT;
+            const int r = a.blur_tiled ? (chunk & 7) + 8 * (chunk >> 7) : chunk >> 4, cc = a.blur_tiled ? (chunk & 8) + ((chunk >> 4) & 7) : chunk & 15;
             uint4* sp = reinterpret_cast<uint4*>(stage + r * kBlurRawPitch + 16 * cc);
             const uint4 px = *sp;
             *sp = z4;
             const int x = ox + 16 * cc;
-            if (r < rows_left && x < W) { // (a chunk that starts inside the row ends inside its pitch: the pitch is a multiple of 64)
-                bl_v4i* q = reinterpret_cast<bl_v4i*>(dstb + (size_t)(oy + r) * a.bpitch + x);
+            if (r < rows_left && x < W) { // (a chunk that starts inside the row ends inside its pitch: the pitch is a multiple of 64; tiled: see tiled_offset)
+                const size_t off = a.blur_tiled ? (size_t)tiled_offset(x, oy + r, tpr) : (size_t)(oy + r) * a.bpitch + x;
                 const bl_v4i pv = {(int)px.x, (int)px.y, (int)px.z, (int)px.w};
-                __builtin_nontemporal_store(pv, q);
+                __builtin_nontemporal_store(pv, reinterpret_cast<bl_v4i*>(dstb + off));
+                if (dstr) { // uniform
+                    const uint32_t* rp = reinterpret_cast<const uint32_t*>(raw + (r + 4) * kBlurRawPitch + 4 + 16 * cc);
+                    const bl_v4i rv = {(int)rp[0], (int)rp[1], (int)rp[2], (int)rp[3]};
+                    __builtin_nontemporal_store(rv, reinterpret_cast<bl_v4i*>(dstr + off));
+                }
             }
         }
         // the bytes of the score tile no staging chunk covers: the 16 padding bytes of each staged row and the tail
@@ -2010,7 +2106,7 @@ __global__ __launch_bounds__(64 * NW, 8) void orb_pyrblur_kernel(PyrBlurArgs a) 
 // d_corners == nullptr: pyramid + blur only (the descriptor-only entry point); else the level's FAST corners are appended to d_corners /
 // d_corner_cnt (zeroed here, like d_status) exactly as launch_orb_fast would
 int launch_orb_pyrblur(const OrbPlan& plan, const OrbTables& tab, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, uint8_t* d_pyr,
-                       uint8_t* d_blur, int fast_thr, uint32_t* d_corners, int32_t* d_corner_cnt, int32_t* d_status, hipStream_t stream) {
+                       uint8_t* d_blur, bool tiled, uint8_t* d_rawt, int fast_thr, uint32_t* d_corners, int32_t* d_corner_cnt, int32_t* d_status, hipStream_t stream) {
     if (d_corners) {
         VS_HIP(hipMemsetAsync(d_corner_cnt, 0, sizeof(int32_t) * B * kNLevels, stream));
         VS_HIP(hipMemsetAsync(d_status, 0, sizeof(int32_t) * B, stream));
@@ -2024,7 +2120,8 @@ int launch_orb_pyrblur(const OrbPlan& plan, const OrbTables& tab, const uint8_t*
         a.src_img_stride = l == 0 ? img_bytes : (size_t)plan.pyr_bytes;
         a.spitch = l == 0 ? pitch : ((S.w + 63) & ~63);
         a.sw = S.w; a.sh = S.h;
-        a.blur_base = d_blur + plan.blur_off[l]; a.blur_img_stride = (size_t)plan.blur_bytes; a.bpitch = (S.w + 63) & ~63;
+        a.blur_base = d_blur + plan.blur_off[l]; a.blur_img_stride = (size_t)plan.blur_bytes; a.bpitch = (S.w + 63) & ~63; a.blur_tiled = tiled ? 1 : 0;
+        if (tiled && d_rawt) { a.rawt_base = d_rawt + plan.blur_off[l]; a.rawt_img_stride = (size_t)plan.blur_bytes; } // (the raw copy has the blurred pyramid's plan)
         a.tiles_x = (S.w + kBlurTileW - 1) / kBlurTileW;
         const int tiles_y = (S.h + kBlurTileH - 1) / kBlurTileH;
         if (l + 1 < kNLevels) {
@@ -2056,6 +2153,15 @@ constexpr int kDescR = 19, kDescRows = 2 * kDescR + 1, kDescPitch = 40; // |patt
 // lane's four test pairs stay in registers for the whole walk.
 constexpr int kDescBlocksPerImage = 48; // x 4 waves = 192 waves per image: eight keypoints per wave at N = 1500 (32 / 48 / 64 / 96 / 144 blocks: 0.373 / 0.365 / 0.373 / 0.390 / 0.409 ms per 512 images)
 constexpr int kDescPatchIters = (kDescRows * (kDescPitch / 4) + 63) / 64;
+// TILED: the blurred level lies line-tiled (tiled_offset: 16 x 8 pixel tiles, one 128-byte line each).  The 39 x 39 neighbourhood whose corner sits at
+// (x mod 16, y mod 8) of its first tile spans at most 4 x 6 tiles = 192 chunks of 16 bytes: three 16-byte loads per lane, lanes 8 k .. 8 k + 7 on the eight rows
+// of one tile, so every instruction fetches whole lines -- about 19 lines per keypoint where the row-major gather touches about 50 (39 rows of 40 bytes).  The tiles
+// are staged as a 64-byte-wide, 48-row image per wave; the tests index it as before, the corner's offset inside its first tile folded into the wave-uniform base.
+// Tiles of the 4 x 6 block that hold no pixel of the neighbourhood are not loaded (they may lie beyond the level): the lanes keep zeros for them.
+constexpr int kDescTilesX = 4, kDescTilesY = 6, kDescTPitch = kTileCols * kDescTilesX, kDescTRows = kTileRows * kDescTilesY, kDescTIters = kDescTilesX * kDescTilesY * kTileRows / 64;
+static_assert(kTileCols - 1 + kDescRows <= kDescTPitch && kTileRows - 1 + kDescRows <= kDescTRows, "the neighbourhood fits the staged tiles at every alignment");
+static_assert(kDescTIters * 64 == kDescTilesX * kDescTilesY * kTileRows && 64 / kTileRows == 2 * kDescTilesX, "a load instruction covers two rows of the tile block");
+template <bool TILED>
 __global__ __launch_bounds__(kDescWaves * 64) void orb_describe_kernel(BlurTable T, LevelTable LT, const uint8_t* __restrict__ d_imgs,
                                                                       size_t img_bytes, int pitch0, const uint8_t* __restrict__ d_pyr,
                                                                       size_t pyr_bytes, const uint8_t* __restrict__ d_blur, size_t blur_bytes,
@@ -2081,7 +2187,9 @@ __global__ __launch_bounds__(kDescWaves * 64) void orb_describe_kernel(BlurTable
     int j = __builtin_amdgcn_readlane(slots, 0);
     const vslam_keypoint* kps = d_kps + (size_t)b * kp_capacity;
     const float2* css = d_cs + (size_t)b * kp_capacity;
-    __shared__ __attribute__((aligned(16))) uint8_t patch[kDescWaves][kDescRows * kDescPitch];
+    constexpr int kPitch = TILED ? kDescTPitch : kDescPitch, kPv = TILED ? kDescTIters : kDescPatchIters;
+    using pv_t = typename std::conditional<TILED, uint4, uint32_t>::type; // what a lane holds of a patch in flight: 16-byte chunks or dwords
+    __shared__ __attribute__((aligned(16))) uint8_t patch[kDescWaves][TILED ? kDescTRows * kDescTPitch : kDescRows * kDescPitch];
     uint8_t* pl = patch[wave];
     float px0[4], py0[4], px1[4], py1[4]; // this lane's four test pairs
 #pragma unroll
@@ -2096,6 +2204,8 @@ __global__ __launch_bounds__(kDescWaves * 64) void orb_describe_kernel(BlurTable
         const int i = lane + 64 * it;
         prow[it] = i / (kDescPitch / 4); pcol[it] = 4 * (i - prow[it] * (kDescPitch / 4));
     }
+    // TILED: this lane's chunks are row tr of tile (ttx, 2 it + tty) of the block, it = 0 .. 2
+    const int tr = lane & 7, ttx = (lane >> 3) & 3, tty = lane >> 5;
     struct Geo { int cx, cy, l, W, H, bpitch; bool inside; const uint8_t* blur; };
     auto geometry = [&](const vslam_keypoint& kp) -> Geo {
         Geo g;
@@ -2113,17 +2223,31 @@ __global__ __launch_bounds__(kDescWaves * 64) void orb_describe_kernel(BlurTable
         g.inside = g.cx - kDescR >= 0 && g.cx + kDescR + 1 < g.W && g.cy - kDescR >= 0 && g.cy + kDescR < g.H; // uniform per wave
         return g;
     };
-    auto patch_fetch = [&](const Geo& g, uint32_t (&pv)[kDescPatchIters]) {
+    auto patch_fetch = [&](const Geo& g, pv_t (&pv)[kPv]) {
         if (!g.inside) return;
-        const uint8_t* org = g.blur + (size_t)(g.cy - kDescR) * g.bpitch + (g.cx - kDescR); // wave-uniform
+        if constexpr (TILED) {
+            const int x0 = g.cx - kDescR, y0 = g.cy - kDescR, tpr = g.bpitch >> 4;                      // wave-uniform
+            const int ntx = ((x0 & 15) + kDescRows - 1) >> 4, nty = ((y0 & 7) + kDescRows - 1) >> 3;      // last tile column / row of the block that holds a pixel
+            const uint8_t* org = g.blur + (size_t)tiled_offset(x0 & ~15, y0 & ~7, tpr);                 // the block's first tile
+            const uint32_t rowb = (uint32_t)tpr * kTileBytes;
 #pragma unroll
-        for (int it = 0; it < kDescPatchIters; ++it) // (24-bit multiply: full rate; rows < 39, pitch < 4160)
-            if (prow[it] < kDescRows) __builtin_memcpy(&pv[it], org + (__umul24((uint32_t)prow[it], (uint32_t)g.bpitch) + (uint32_t)pcol[it]), 4);
+            for (int it = 0; it < kDescTIters; ++it) {
+                uint4 v = make_uint4(0u, 0u, 0u, 0u);
+                if (ttx <= ntx && 2 * it + tty <= nty) // (these tiles hold a pixel of the neighbourhood, which lies inside the level: see tiled_offset)
+                    v = *reinterpret_cast<const uint4*>(org + (__umul24((uint32_t)(2 * it + tty), rowb) + (uint32_t)(ttx * kTileBytes + 16 * tr)));
+                pv[it] = v;
+            }
+        } else {
+            const uint8_t* org = g.blur + (size_t)(g.cy - kDescR) * g.bpitch + (g.cx - kDescR); // wave-uniform
+#pragma unroll
+            for (int it = 0; it < kDescPatchIters; ++it) // (24-bit multiply: full rate; rows < 39, pitch < 4160)
+                if (prow[it] < kDescRows) __builtin_memcpy(&pv[it], org + (__umul24((uint32_t)prow[it], (uint32_t)g.bpitch) + (uint32_t)pcol[it]), 4);
+        }
     };
     vslam_keypoint kp = kps[j];
     float2 cs = css[j];
     Geo g = geometry(kp);
-    uint32_t pv[kDescPatchIters];
+    pv_t pv[kPv];
     patch_fetch(g, pv);
     auto slot_of = [&](int v) -> int { return v < nvisit ? __builtin_amdgcn_readlane(slots, v) : -1; }; // v is wave-uniform
     int j1 = slot_of(1);                           // next keypoint: record in flight
@@ -2132,13 +2256,19 @@ __global__ __launch_bounds__(kDescWaves * 64) void orb_describe_kernel(BlurTable
     for (;;) {
         // patch of keypoint j: registers -> LDS
         if (g.inside) {
+            if constexpr (TILED) {
 #pragma unroll
-            for (int it = 0; it < kDescPatchIters; ++it)
-                if (prow[it] < kDescRows) *reinterpret_cast<uint32_t*>(pl + prow[it] * kDescPitch + pcol[it]) = pv[it];
+                for (int it = 0; it < kDescTIters; ++it)
+                    *reinterpret_cast<uint4*>(pl + (kTileRows * (2 * it + tty) + tr) * kDescTPitch + kTileCols * ttx) = pv[it];
+            } else {
+#pragma unroll
+                for (int it = 0; it < kDescPatchIters; ++it)
+                    if (prow[it] < kDescRows) *reinterpret_cast<uint32_t*>(pl + prow[it] * kDescPitch + pcol[it]) = pv[it];
+            }
         }
         // keypoint j1: its patch goes in flight now; keypoint j2: its record
         const Geo g1 = geometry(kp1);
-        uint32_t pv1[kDescPatchIters];
+        pv_t pv1[kPv];
         if (j1 >= 0) patch_fetch(g1, pv1);
         const int j2 = slot_of(visit + 2);
         const vslam_keypoint kp2 = kps[max(j2, 0)];
@@ -2147,23 +2277,27 @@ __global__ __launch_bounds__(kDescWaves * 64) void orb_describe_kernel(BlurTable
         const float ca = cs.x, sa = cs.y;
         int nib = 0;
         if (g.inside) {
+            // the staged image's byte of the keypoint's centre (TILED: the neighbourhood's corner sits at (x mod 16, y mod 8) of the first tile); wave-uniform
+            const uint8_t* pc = pl + kDescR * kPitch + kDescR + (TILED ? ((g.cy - kDescR) & 7) * kPitch + ((g.cx - kDescR) & 15) : 0);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int ix0 = __float2int_rn(__fsub_rn(__fmul_rn(px0[k], ca), __fmul_rn(py0[k], sa)));
                 const int iy0 = __float2int_rn(__fadd_rn(__fmul_rn(px0[k], sa), __fmul_rn(py0[k], ca)));
                 const int ix1 = __float2int_rn(__fsub_rn(__fmul_rn(px1[k], ca), __fmul_rn(py1[k], sa)));
                 const int iy1 = __float2int_rn(__fadd_rn(__fmul_rn(px1[k], sa), __fmul_rn(py1[k], ca)));
-                const int t0 = pl[(iy0 + kDescR) * kDescPitch + ix0 + kDescR], t1 = pl[(iy1 + kDescR) * kDescPitch + ix1 + kDescR];
+                const int t0 = pc[iy0 * kPitch + ix0], t1 = pc[iy1 * kPitch + ix1];
                 nib |= (t0 < t1) << k;
             }
         } else {
             const uint8_t* rawp = g.l == 0 ? d_imgs + (size_t)b * img_bytes : d_pyr + (size_t)b * pyr_bytes + T.pyr_off[g.l];
             const int rpitch = g.l == 0 ? pitch0 : T.pitch[g.l];
+            // (TILED: the level's size comes from the table again, so that the pipeline does not carry it in scalar registers for this rare path)
+            const int W = TILED ? T.w[g.l] : g.W, H = TILED ? T.h[g.l] : g.H;
             auto sample = [&](int ix, int iy) -> int {
                 const int x = g.cx + ix, y = g.cy + iy;
-                if (x >= 0 && x < g.W && y >= 0 && y < g.H) return g.blur[(size_t)y * g.bpitch + x];
+                if (x >= 0 && x < W && y >= 0 && y < H) return g.blur[TILED ? (size_t)tiled_offset(x, y, g.bpitch >> 4) : (size_t)y * g.bpitch + x];
                 // outside the level the reference reads the UNBLURRED reflect-101 border of its pyramid buffer
-                return rawp[(size_t)reflect101(y, g.H) * rpitch + reflect101(x, g.W)];
+                return rawp[(size_t)reflect101(y, H) * rpitch + reflect101(x, W)];
             };
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -2181,13 +2315,13 @@ __global__ __launch_bounds__(kDescWaves * 64) void orb_describe_kernel(BlurTable
         ++visit;
         j = j1; j1 = j2; g = g1; cs = cs1; kp1 = kp2; cs1 = cs2;
 #pragma unroll
-        for (int it = 0; it < kDescPatchIters; ++it) pv[it] = pv1[it];
+        for (int it = 0; it < kPv; ++it) pv[it] = pv1[it];
     }
 }
 
 int launch_orb_describe(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr,
                         const uint8_t* d_blur, const vslam_keypoint* d_kps, const float2* d_cs, const int32_t* d_order, int kp_capacity, const int32_t* d_count,
-                        uint8_t* d_desc, hipStream_t stream) {
+                        uint8_t* d_desc, bool tiled, hipStream_t stream) {
     BlurTable T;
     fill_blur_table(plan, &T);
     LevelTable LT;
@@ -2196,8 +2330,13 @@ int launch_orb_describe(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_b
     const int max_kp = min(kp_capacity, kMaxRows);
     const int blocks = min(kDescBlocksPerImage, (max_kp + kDescWaves - 1) / kDescWaves);
     ProfScope prof__(stream, "orb_describe_kernel");
-    hipLaunchKernelGGL(orb_describe_kernel, dim3(blocks * ((B + 7) / 8 * 8)), dim3(kDescWaves * 64), 0, stream, T, LT, d_imgs,
-                       img_bytes, pitch, d_pyr, (size_t)plan.pyr_bytes, d_blur, (size_t)plan.blur_bytes, d_kps, d_cs, d_order, kp_capacity, d_count, d_desc, blocks, B);
+    // (tiled: d_blur as orb_pyrblur_kernel wrote it under blur_tiled; a missing instance cannot happen: both are built here)
+    if (tiled)
+        hipLaunchKernelGGL(orb_describe_kernel<true>, dim3(blocks * ((B + 7) / 8 * 8)), dim3(kDescWaves * 64), 0, stream, T, LT, d_imgs,
+                           img_bytes, pitch, d_pyr, (size_t)plan.pyr_bytes, d_blur, (size_t)plan.blur_bytes, d_kps, d_cs, d_order, kp_capacity, d_count, d_desc, blocks, B);
+    else
+        hipLaunchKernelGGL(orb_describe_kernel<false>, dim3(blocks * ((B + 7) / 8 * 8)), dim3(kDescWaves * 64), 0, stream, T, LT, d_imgs,
+                           img_bytes, pitch, d_pyr, (size_t)plan.pyr_bytes, d_blur, (size_t)plan.blur_bytes, d_kps, d_cs, d_order, kp_capacity, d_count, d_desc, blocks, B);
     VS_HIP(hipGetLastError());
     return VSLAM_OK;
 }

@@ -99,9 +99,24 @@ struct OrbPlan {
     int corner_total;     // per image
     int total_tiles;      // FAST tiles per image, all levels
     int sel_cap;          // per (image, level) capacity of the selected keypoint staging list
-    int blur_off[kNLevels]; // byte offset of each level inside one image's blurred pyramid (level 0 included)
+    int blur_off[kNLevels]; // byte offset of each level inside one image's blurred pyramid (level 0 included); a level holds pitch x tiled_rows(h) bytes
     int blur_bytes;       // per image
 };
+
+// Line-tiled level layout (the blurred pyramid as orb_pyrblur_kernel writes it for orb_describe_kernel<true>): the level is cut into tiles of
+// 16 columns x 8 rows, tile (tx, ty) is the 128 contiguous bytes -- one cache line -- at (ty * tiles_per_row + tx) * 128, row r of it the 16 bytes at
+// 16 * (r & 7).  tiles_per_row = pitch / 16 (pitches are multiples of 64), and there are ceil(h / 8) tile rows: a level occupies
+// pitch * tiled_rows(h) bytes in EITHER layout, so one plan serves both.
+// No tiled access leaves the level's allocation: x < pitch and y < tiled_rows(h) give tx < tiles_per_row and ty < tiled_rows(h) / 8, i.e. an offset
+// below pitch * tiled_rows(h) -- the last, partial tile row is allocated in full.  The producer stores 16-byte chunks that start at a pixel (x, y)
+// of the level (x < w <= pitch, y < h); the consumers read whole chunks of tiles that hold a pixel of a patch which passed the kernel's `inside`
+// test, i.e. lies inside the level, or single pixels inside the level.  Bytes of a tile beyond the level's width or height (padding) are
+// never written by anyone and may hold anything: no result depends on them.
+constexpr int kTileCols = 16, kTileRows = 8, kTileBytes = kTileCols * kTileRows;
+__host__ __device__ inline int tiled_rows(int h) { return (h + kTileRows - 1) & ~(kTileRows - 1); }
+__host__ __device__ inline uint32_t tiled_offset(int x, int y, int tiles_per_row) {
+    return (uint32_t)(((y >> 3) * tiles_per_row + (x >> 4)) * kTileBytes + ((y & 7) << 4) + (x & 15));
+}
 
 struct Ctx;
 
@@ -135,6 +150,8 @@ struct OrbBuffers {
     int32_t* d_status;     // B  (bit flags: overflow conditions)
     vslam_keypoint* d_det; // B x kp_capacity: detect output (level asc, raster) when ANMS is run as a separate call
     uint8_t* d_blur;       // B x blur_bytes: Gaussian-blurred pyramid (rBRIEF samples these)
+    uint8_t* d_rawt;       // B x blur_bytes: line-tiled copy of the raw levels 0..7 (orb_orient_kernel<true> samples these); written only together with a tiled d_blur
+    bool blur_tiled;       // layout of d_blur as its most recent producer wrote it: line-tiled (orb_pyrblur_kernel under Tuning::orb_tiled) or row-major
     float2* d_cs;          // B x kp_capacity: per-keypoint (cos, sin) of the rBRIEF rotation
     int32_t* d_order;      // B x kp_capacity: the output slots in (octave, raster) order -- the walk order of orient / describe
     double* d_rad;         // B x kMaxRows: ANMS suppression radii (f64)
@@ -146,8 +163,10 @@ int launch_orb_pyramid(const OrbPlan& plan, const OrbTables& tab, const uint8_t*
                        int B, uint8_t* d_pyr, hipStream_t stream);
 // pyramid level l + 1 AND the blurred level l from ONE staging of the level-l tile (8 launches: the levels depend on each other)
 // [r6] ... and, with d_corners != nullptr, FAST + NMS of level l from the same tile (then launch_orb_fast is not called)
+// tiled: the blurred levels are written line-tiled (tiled_offset) instead of row-major; launch_orb_describe must be told the same.
+// tiled and d_rawt != nullptr: a line-tiled copy of raw levels 0..7 goes to d_rawt as well (B x blur_bytes, the blurred pyramid's plan), for launch_orb_orient
 int launch_orb_pyrblur(const OrbPlan& plan, const OrbTables& tab, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, uint8_t* d_pyr,
-                       uint8_t* d_blur, int fast_thr, uint32_t* d_corners, int32_t* d_corner_cnt, int32_t* d_status, hipStream_t stream);
+                       uint8_t* d_blur, bool tiled, uint8_t* d_rawt, int fast_thr, uint32_t* d_corners, int32_t* d_corner_cnt, int32_t* d_status, hipStream_t stream);
 int launch_orb_fast(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr,
                     int fast_thr, uint32_t* d_corners, int32_t* d_corner_cnt, int32_t* d_status, hipStream_t stream);
 int launch_orb_select(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr,
@@ -166,10 +185,10 @@ int launch_anms_flat(int B, const vslam_keypoint* d_in, const int32_t* d_nin, in
 int launch_orb_blur(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr, uint8_t* d_blur,
                     hipStream_t stream);
 int launch_orb_orient(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr, vslam_keypoint* d_kps,
-                      float2* d_cs, const int32_t* d_order, int kp_capacity, const int32_t* d_count, hipStream_t stream);
+                      float2* d_cs, const int32_t* d_order, int kp_capacity, const int32_t* d_count, const uint8_t* d_rawt, hipStream_t stream);
 int launch_orb_describe(const OrbPlan& plan, const uint8_t* d_imgs, size_t img_bytes, int pitch, int B, const uint8_t* d_pyr,
                         const uint8_t* d_blur, const vslam_keypoint* d_kps, const float2* d_cs, const int32_t* d_order, int kp_capacity, const int32_t* d_count,
-                        uint8_t* d_desc, hipStream_t stream);
+                        uint8_t* d_desc, bool tiled, hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- matcher
 struct MatchBuffers {
@@ -240,6 +259,8 @@ struct LmWindowArgs {
 constexpr int kPoseOnlyNarrowWaves = 4; // the narrow form of pose_only_wave_kernel that the library builds next to VSLAM_MAX_KF waves per window
 struct Tuning {
     int orb_fuse_min = -1;    // VSLAM_ORB_FUSE_MIN: images per call from which orb_pyrblur_kernel replaces resize + blur
+    int orb_tiled = -1;       // VSLAM_ORB_TILED: 0 = orb_pyrblur_kernel writes the blurred pyramid row-major and orb_describe_kernel gathers rows (the form before the
+                              // line-tiled layout, kept for before / after measurements); default / 1: line-tiled whenever the fused kernel runs.  Same bits either way
     int anms_cap = -1;        // VSLAM_ANMS_CAP: pixels of cleared distance at which orb_anms_kernel's radius walk stops early (0 = never: the full walk;
                               // default: one cell of its grid).  Same bits either way: a selection the cap could have changed is redone without it
     int sgbm_fuse_min = -1;   // VSLAM_SGBM_FUSE_MIN: pairs per call from which sgbm_down_kernel replaces hsum / vsum / path<0,1>
