@@ -212,7 +212,7 @@ static int orb_pipeline(Ctx* c, const uint8_t* d_imgs, size_t img_bytes, int pit
         if ((rc = launch_orb_describe(c->plan, d_imgs, img_bytes, pitch, B, c->orb.d_pyr, c->orb.d_blur, d_kps, c->orb.d_cs, c->orb.d_order, c->p.kp_capacity, d_count,
                                       d_desc, c->orb.blur_tiled, c->stream))) return rc;
     }
-    if (getenv("VSLAM_ORB_PROFILE")) orb_debug_dump(c->stream);
+    if (c->prof_orb) orb_debug_dump(c->stream);
     return VSLAM_OK;
 }
 
@@ -274,14 +274,16 @@ int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** ou
     VS_HIP(hipSetDevice(device));
     Ctx* c = new Ctx(); // (value-initialised: zeroes, then the members' default initialisers -- Tuning's -1, LmScratch's)
     c->p = *p; c->device = device;
-    c->lm.tune = &c->tune;
     { int rc_t = tune_from_env(c->tune); if (rc_t) { delete c; return rc_t; } }
+    // the profile switches (tuning aids) are read here as well, once: nothing below vslam_create calls getenv
+    c->prof_orb = getenv("VSLAM_ORB_PROFILE") != nullptr;
+    c->lm.prof_lm = getenv("VSLAM_LM_PROFILE") != nullptr; c->lm.prof_rs = getenv("VSLAM_RS_PROFILE") != nullptr; c->lm.prof_po = getenv("VSLAM_PO_PROFILE") != nullptr;
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
     else {
         if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); delete c; return VSLAM_ERR_HIP; }
         c->own_stream = true;
     }
-    if (getenv("VSLAM_ORB_PROFILE")) orb_debug_enable();
+    if (c->prof_orb) orb_debug_enable();
     // An image below ORB's 64 x 64 (a small rectification target): the ORB plan and buffers are laid out for the 64 x 64 minimum so that every
     // pointer of the context exists, and the ORB entry points refuse the context (check_img, vslam_feature_detection_dev, vslam_orb_level).
     c->orb_ok = p->img_w >= 64 && p->img_h >= 64;
@@ -1265,11 +1267,10 @@ int vslam_ba_chain_dev(vslam_ctx* ctx, const vslam_ba_batch* b, const int32_t* d
         w.n_windows = n_slots;
         if (int rc = launch_chain_stage(a, j, n_slots, c->stream)) return rc;
         if (int rc = launch_lm_windows(w, 1, 0, 10, 1, 0, &c->lm, c->stream)) return rc; // (the schedule of vslam_ba_batch_dev(schedule = 1))
-        if (int rc = launch_chain_scatter(a, n_slots, c->lm.status, c->stream)) return rc;
+        if (int rc = launch_chain_scatter(a, n_slots, c->lm.last.status, c->stream)) return rc;
     }
     // vslam_ba_status_dev: per window of the caller's batch, the status word of the step that ran it
-    c->lm.status = a.status; c->lm.status_n = n_win;
-    c->lm.passes = nullptr; c->lm.defer = nullptr; c->lm.defer_valid = false; // (the per-launch diagnostics describe single steps: not available after a chain)
+    c->lm.last = LmLast::of_chain(a.status, n_win);
     return VSLAM_OK;
 }
 

@@ -74,27 +74,6 @@ struct alignas(16) RsShared {
     unsigned char itempair[kRsHitItems];           // pair of work item i of the hit-major phase
 };
 
-struct RsArgs {
-    LmWindowArgs a;
-    float2* uv_s;          // total_edge: observations, slot-major per window: slot q of sorted landmark s at [slotoff[q] + s]
-    int32_t* epos;         // total_edge: caller's edge id (window-local) at the same position
-    double* tab;           // 6 x total_lm doubles of scratch; window slice [6 lm0, 6 (lm0 + nl)) holds, as u16: perm[nl] (sorted position ->
-                           // landmark id, window-local), mstat[nl] (keyframe set (12 bits) | slot of the landmark's last edge << 12, sorted order)
-    double* xin;           // 3 x total_lm doubles of scratch; window slice holds, as f32, the input positions in sorted order (3 nl floats)
-    double* Pbak;          // 3 x total_lm: the accepted positions while a trial sits in LDS
-    double* Dc;            // 6 x total_lm: D^-1 = (H_ll + lambda I)^-1 of the multi-observation landmarks, sorted order, 48 B records (hit-major phase)
-    double* blc;           // 3 x total_lm: their b_l, 24 B records
-    int32_t* status;
-    int32_t* passes;
-    int32_t* defer;        // n_windows: 1 = window left to lm_window_kernel
-    const int32_t* order;
-    long long* dbg;
-    int dyn_bytes;
-    int dyn_narrow;        // the dynamic LDS of the 256-lane form: WHICH windows the kernel takes and on which path (hit-major / row-wise) is decided against it in both widths, so that a window's bits do not depend on the width
-    int want_chi2;
-    int dense_to_general;  // 1: windows with more than 2.2 observations per landmark are left to lm_window_kernel (Tuning::ba_resident = 1 forces them here)
-};
-
 __device__ inline long long to_fixed(double v, double scale) { return __double2ll_rn(v * scale); }
 
 // lower block (I >= K) of the packed reduced system
@@ -1332,46 +1311,33 @@ __global__ __launch_bounds__(BLOCK, kRsMinWaves) void ba_resident_kernel(RsArgs 
 }
 
 // ------------------------------------------------------------------------------------------------------------- launcher
-static int rs_lds_per_cu(int device) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || v <= 0) v = 64 * 1024;
-    return v;
-}
-// dynamic LDS of the narrow form: two windows (workgroups of four waves at 256 VGPRs) share a CU, half of its LDS each; of the wide form:
-// the whole CU's LDS
-void rs_query_device(int device, LmScratch& s) {
-    const int lds = rs_lds_per_cu(device), narrow = lds / 2 - (int)sizeof(RsShared) - 256, full = lds - (int)sizeof(RsShared) - 256;
-    int n = 0;
+// The device facts ba_resident_kernel is launched by -- its dynamic LDS in the narrow form (two workgroups of four waves at 256 VGPRs share a CU, half
+// of its LDS each) and in the wide form (the whole CU's LDS), the CU count -- and the opt-in that more than 64 KB of dynamic LDS needs, for all four instances
+int rs_device_ready(int device, LmScratch& s) {
+    int lds = 0, n = 0;
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || lds <= 0) lds = 64 * 1024;
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n <= 0) n = 256;
-    s.rs_dyn_bytes = narrow > 0 ? (narrow & ~255) : 0;
+    const int narrow = lds / 2 - (int)sizeof(RsShared) - 256, full = lds - (int)sizeof(RsShared) - 256;
+    s.rs_narrow_bytes = narrow > 0 ? (narrow & ~255) : 0;
     s.rs_full_bytes = full > 0 ? (full & ~255) : 0;
-    s.rs_cu_count = n;
+    s.cu_count = n;
+    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, s.rs_narrow_bytes));
+    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<false, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, s.rs_narrow_bytes));
+    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<true, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, s.rs_full_bytes));
+    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, s.rs_full_bytes));
+    return VSLAM_OK;
 }
 
-int launch_ba_resident(const RsLaunch& L, hipStream_t stream) {
-    RsArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.a = L.a;
-    ra.uv_s = reinterpret_cast<float2*>(L.uv_s); ra.epos = L.epos; ra.tab = L.tab; ra.xin = L.xin; ra.Pbak = L.Pbak; ra.Dc = L.Dc; ra.blc = L.blc;
-    ra.status = L.status; ra.passes = L.passes; ra.defer = L.defer; ra.order = L.order; ra.dbg = L.dbg;
-    ra.want_chi2 = L.want_chi2; ra.dense_to_general = L.dense_to_general;
-    // width: more windows than CUs -> 256 lanes, two windows per CU (throughput); otherwise 512 lanes and the whole CU's LDS (a window's latency).
-    // Both widths give the same bits (see kRsStreams), so the choice may depend on the launch.
-    const int lanes = L.lanes == 256 || L.lanes == 512 ? L.lanes : (L.a.n_windows <= L.cu_count ? 512 : 256);
-    const int dyn = lanes == 512 ? L.full_bytes : L.dyn_bytes;
-    ra.dyn_bytes = dyn; ra.dyn_narrow = L.dyn_bytes;
-    if (!L.opt_in_done) { // more than 64 KB of dynamic LDS needs the opt-in (once per context, i.e. per device)
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<true, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, L.dyn_bytes));
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<false, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, L.dyn_bytes));
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<true, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, L.full_bytes));
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&ba_resident_kernel<false, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, L.full_bytes));
-    }
-    if (lanes == 512) {
-        if (L.schedule) hipLaunchKernelGGL((ba_resident_kernel<true, 512>), dim3(L.a.n_windows), dim3(512), (size_t)dyn, stream, ra, 5, 0, 0, 1, L.adaptive);
-        else hipLaunchKernelGGL((ba_resident_kernel<false, 512>), dim3(L.a.n_windows), dim3(512), (size_t)dyn, stream, ra, L.iters, L.update_poses, L.update_lms, 1, 0);
+// ra.dyn_bytes is the dynamic LDS of the width plan.ba_lanes
+int launch_ba_resident(const RsArgs& ra, const LmPlan& plan, int iters, int update_poses, int update_lms, hipStream_t stream) {
+    const dim3 grid(ra.a.n_windows);
+    const size_t dyn = (size_t)ra.dyn_bytes;
+    if (plan.ba_lanes == 512) {
+        if (plan.schedule) hipLaunchKernelGGL((ba_resident_kernel<true, 512>), grid, dim3(512), dyn, stream, ra, 5, 0, 0, 1, plan.adaptive ? 1 : 0);
+        else hipLaunchKernelGGL((ba_resident_kernel<false, 512>), grid, dim3(512), dyn, stream, ra, iters, update_poses, update_lms, 1, 0);
     } else {
-        if (L.schedule) hipLaunchKernelGGL((ba_resident_kernel<true, 256>), dim3(L.a.n_windows), dim3(256), (size_t)dyn, stream, ra, 5, 0, 0, 1, L.adaptive);
-        else hipLaunchKernelGGL((ba_resident_kernel<false, 256>), dim3(L.a.n_windows), dim3(256), (size_t)dyn, stream, ra, L.iters, L.update_poses, L.update_lms, 1, 0);
+        if (plan.schedule) hipLaunchKernelGGL((ba_resident_kernel<true, 256>), grid, dim3(256), dyn, stream, ra, 5, 0, 0, 1, plan.adaptive ? 1 : 0);
+        else hipLaunchKernelGGL((ba_resident_kernel<false, 256>), grid, dim3(256), dyn, stream, ra, iters, update_poses, update_lms, 1, 0);
     }
     VS_HIP(hipGetLastError());
     return VSLAM_OK;

@@ -64,8 +64,6 @@ constexpr int kLmSlots = 5;                 // observations per landmark kept in
 constexpr int kSchedFinalIters = 10;        // iterations of the schedule's last optimize_map pass (run_vslam.cpp:66)
 constexpr int kRowCap = 512;                // 64-landmark rows with a slot-width entry in LDS (32 768 landmarks per window)
 
-size_t lm_hits_per_edge() { return kHitsPerEdge; }
-
 struct alignas(16) LmShared {
     double S[kMaxNp * kMaxNp];
     double Hpp[kMaxKf * 36], HppT[kMaxKf * 36]; // pose blocks at the current state / at the state of the latest trial
@@ -1845,10 +1843,9 @@ __global__ __launch_bounds__(64 * W, kMinWaves) void pose_only_wave_kernel(LmKer
 }
 
 // the scratch of one LM launch in the context's LmScratch (declared in vslam_internal.h).  Without landmarks (PnP) the landmark-wise
-// tables are 256-byte placeholders.
-static int carve_lm(LmScratch& s, LmKernelArgs& ka, size_t total_lm, size_t total_edge, int n_windows, bool with_lm, hipStream_t stream) {
-    int32_t* defer;
-    if (int rc = carve(s.buf, stream, [&](Layout& L) {
+// tables are 256-byte placeholders.  defer: the slot ba_resident_kernel writes (ka.defer stays null: lm_window_kernel reads it only behind that kernel).
+static int carve_lm(LmScratch& s, LmKernelArgs& ka, int32_t*& defer, size_t total_lm, size_t total_edge, int n_windows, bool with_lm, hipStream_t stream) {
+    return carve(s.buf, stream, [&](Layout& L) {
             ka.a.P = L.take<double>(total_lm * 3);
             ka.a.Ptrial = L.take<double>(total_lm * 3);
             ka.a.Hll = L.take<double>(total_lm * 6);
@@ -1873,9 +1870,7 @@ static int carve_lm(LmScratch& s, LmKernelArgs& ka, size_t total_lm, size_t tota
             ka.order = L.take<int32_t>(n_windows); // (filled by lm_order_kernel when the launcher wants it; cleared to null otherwise)
             ka.passes = L.take<int32_t>(n_windows);
             defer = L.take<int32_t>(n_windows);
-        })) return rc;
-    s.status = ka.status; s.status_n = n_windows; s.passes = ka.passes; s.defer = defer;
-    return VSLAM_OK;
+        });
 }
 
 // Largest window first.  A batch has more windows than the chip has CUs (one workgroup per CU), a window's time grows with its edge count, and
@@ -1905,136 +1900,153 @@ __global__ __launch_bounds__(1024) void lm_order_kernel(const int32_t* __restric
     for (int i = threadIdx.x; i < n; i += 1024) order[i] = (int32_t)(key[i] & 0xFFFFFFFFu);
 }
 
+constexpr size_t kLmDynLds = (size_t)kDinvLds * 6 * sizeof(double); // dynamic LDS of lm_window_kernel with landmarks: D^-1 of the first kDinvLds
+
+// Makes this context's device ready for the LM kernels: the opt-in that more than 64 KB of dynamic LDS needs, for every instance of lm_window_kernel
+// that is launched with any (lm_window_kernel<true>, the single-pose form, takes none) here and of ba_resident_kernel in rs_device_ready, which also stores
+// that kernel's LDS budgets and the CU count.  Once per context, on its first LM launch: a context that never runs BA or a pose stage does not pay
+// for it at vslam_create.
+static int lm_device_ready(LmScratch& s) {
+    if (s.dev_ready) return VSLAM_OK;
+    int dev = 0;
+    VS_HIP(hipGetDevice(&dev));
+    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lm_window_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLmDynLds));
+    VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lm_window_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLmDynLds));
+    if (int rc = rs_device_ready(dev, s)) return rc;
+    s.dev_ready = true;
+    return VSLAM_OK;
+}
+
+// the rules of LmPlan (vslam_internal.h), each stated once
+static LmPlan plan_lm_windows(int n_windows, int schedule, int mode, const Tuning& t, int cu_count) {
+    LmPlan p;
+    p.schedule = schedule != 0;
+    p.resident = (schedule || mode == 0) && t.ba_resident != 0;
+    p.adaptive = t.ba_adaptive != 0;
+    p.dense_to_general = t.ba_resident != 1;
+    p.order = n_windows > 1 && n_windows <= kOrderCap;
+    p.po_window = t.pose_only_window > 0;
+    p.po_waves = t.pose_only_waves > 0 ? t.pose_only_waves : (n_windows <= cu_count ? kMaxKf : kPoseOnlyNarrowWaves);
+    p.ba_lanes = t.ba_lanes == 256 || t.ba_lanes == 512 ? t.ba_lanes : (n_windows <= cu_count ? 512 : 256);
+    p.launches = (p.schedule ? (p.adaptive ? 2 : 4) : 1) + (p.resident ? 1 : 0);
+    return p;
+}
+
+// tuning aid: the phase clocks of one launch set (thread 0 of every window, rows of `stride` slots) to stderr, as the mean of every named slot over
+// the windows; the slots in total_mask add up to the total
+static void dump_phase_clocks(const char* tag, const char* const* names, int n_slots, int stride, uint32_t total_mask, const long long* d_cycles, int n_windows,
+                              hipStream_t stream) {
+    hipStreamSynchronize(stream);
+    std::vector<long long> h(kDbgSlots * (size_t)n_windows);
+    hipMemcpy(h.data(), d_cycles, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
+    double tot = 0;
+    for (int i = 0; i < n_slots; ++i) {
+        double sum = 0;
+        for (int w = 0; w < n_windows; ++w) sum += (double)h[stride * (size_t)w + i];
+        sum /= n_windows;
+        if ((total_mask >> i) & 1) tot += sum;
+        fprintf(stderr, "  [%s profile] %-32s %10.0f ticks/window\n", tag, names[i], sum);
+    }
+    fprintf(stderr, "  [%s profile] total %.0f (clock64 ticks = shader clock, thread 0 of every window)\n", tag, tot);
+}
+
 int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, int update_poses, int update_lms, LmScratch* scratch,
                       hipStream_t stream) {
-    const size_t total_lm = a.total_lm, total_edge = a.total_edge;
     if (a.n_windows <= 0) return VSLAM_OK;
     if (a.n_kf <= 0 || a.n_kf > kMaxKf) { set_error("n_kf %d out of range (1..%d)", a.n_kf, kMaxKf); return VSLAM_ERR_ARG; }
+    if (int rc = lm_device_ready(*scratch)) return rc;
+    const LmPlan plan = plan_lm_windows(a.n_windows, schedule, mode, *scratch->tune, scratch->cu_count);
+    const dim3 grid(a.n_windows), block(kLmBlock);
+    const size_t cyc_bytes = sizeof(long long) * kDbgSlots * a.n_windows;
     LmKernelArgs ka;
     memset(&ka, 0, sizeof(ka));
     ka.a = a;
     ka.want_chi2 = a.chi2 != nullptr;
     ka.dinv_lds = kDinvLds;
-    const size_t dyn_lds = (size_t)kDinvLds * 6 * sizeof(double);
-    if (!scratch->lds_opt_in) { // more than 64 KB of dynamic LDS needs the opt-in (once per context, i.e. per device)
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lm_window_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
-        VS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lm_window_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
-        scratch->lds_opt_in = true;
-    }
-    if (getenv("VSLAM_LM_PROFILE")) {
-        const size_t cyc_need = sizeof(long long) * kDbgSlots * a.n_windows;
-        if (int rc = scratch->cyc.reserve(cyc_need, stream)) return rc;
-        VS_HIP(hipMemsetAsync(scratch->cyc.p, 0, cyc_need, stream));
+    if (scratch->prof_lm) {
+        if (int rc = scratch->cyc.reserve(cyc_bytes, stream)) return rc;
+        VS_HIP(hipMemsetAsync(scratch->cyc.p, 0, cyc_bytes, stream));
         ka.dbg_cycles = (long long*)scratch->cyc.p;
     }
-    int rc = carve_lm(*scratch, ka, total_lm, total_edge, a.n_windows, true, stream);
-    if (rc) return rc;
-    // Tuning::ba_adaptive (default on): ONE launch runs a window's passes back to back, and a pass that flags nothing new is continued to the last pass's
-    // 10 iterations instead of being repeated (see the kernel); 0: the three passes as three launches, every one of them for every window
-    const bool adaptive = !(scratch->tune && scratch->tune->ba_adaptive == 0);
-    const bool resident_on = (schedule || mode == 0) && !(scratch->tune && scratch->tune->ba_resident == 0);
-    ProfScope prof__(stream, "lm_window_kernel", (schedule ? (adaptive ? 2 : 4) : 1) + (resident_on ? 1 : 0)); // (family name kept from rounds 1-4; the BA schedule's launches)
-    if (a.n_windows > 1 && a.n_windows <= kOrderCap)
-        hipLaunchKernelGGL(lm_order_kernel, dim3(1), dim3(1024), 0, stream, a.edge_off, a.n_windows, const_cast<int32_t*>(ka.order));
+    int32_t* defer;
+    if (int rc = carve_lm(*scratch, ka, defer, a.total_lm, a.total_edge, a.n_windows, true, stream)) return rc;
+    scratch->last = LmLast{ka.status, a.n_windows, ka.passes, defer, plan.resident};
+    ProfScope prof__(stream, "lm_window_kernel", plan.launches); // (family name kept from rounds 1-4; the BA schedule's launches)
+    if (plan.order) hipLaunchKernelGGL(lm_order_kernel, dim3(1), dim3(1024), 0, stream, a.edge_off, a.n_windows, const_cast<int32_t*>(ka.order));
     else ka.order = nullptr;
-    // optimize_map passes: ba_resident_kernel takes every window whose landmark state fits the LDS of a CU (Tuning::ba_resident = 0: none) and marks
-    // the others in `defer`; lm_window_kernel then runs with that list and returns at once for the windows that are done
-    const bool resident = (schedule || mode == 0) && !(scratch->tune && scratch->tune->ba_resident == 0);
-    scratch->defer_valid = resident;
-    if (resident) {
-        if (scratch->rs_dyn_bytes < 0) { int dev = 0; VS_HIP(hipGetDevice(&dev)); rs_query_device(dev, *scratch); }
-        RsLaunch L;
-        memset(&L, 0, sizeof(L));
-        L.a = ka.a; L.uv_s = ka.uvk; L.epos = ka.kf_pos; L.tab = ka.a.Hll; L.xin = ka.a.Ptrial; L.Pbak = ka.a.P; L.Dc = ka.a.Dinv; L.blc = ka.a.bl;
-        L.status = ka.status; L.passes = ka.passes; L.defer = scratch->defer; L.order = ka.order; L.dbg = getenv("VSLAM_RS_PROFILE") ? ka.dbg_cycles : nullptr;
-        L.lanes = (scratch->tune && scratch->tune->ba_lanes > 0) ? scratch->tune->ba_lanes : 0;
-        L.dyn_bytes = scratch->rs_dyn_bytes; L.full_bytes = scratch->rs_full_bytes; L.cu_count = scratch->rs_cu_count; L.schedule = schedule; L.adaptive = adaptive ? 1 : 0; L.iters = iters; L.update_poses = update_poses; L.update_lms = update_lms;
-        L.opt_in_done = scratch->rs_opt_in; L.want_chi2 = ka.want_chi2;
-        L.dense_to_general = !(scratch->tune && scratch->tune->ba_resident == 1);
-        if (schedule && !adaptive) hipLaunchKernelGGL(lm_fill_kernel, dim3((a.n_windows + 255) / 256), dim3(256), 0, stream, ka.passes, a.n_windows, 3);
-        rc = launch_ba_resident(L, stream);
-        if (rc) return rc;
-        scratch->rs_opt_in = true;
-        ka.defer = scratch->defer;
-        if (L.dbg) { // tuning aid (VSLAM_LM_PROFILE=1 VSLAM_RS_PROFILE=1): phase clocks of ba_resident_kernel, thread 0 of every window
-            hipStreamSynchronize(stream);
-            std::vector<long long> h(kDbgSlots * (size_t)a.n_windows);
-            hipMemcpy(h.data(), ka.dbg_cycles, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
+    if (plan.schedule && !plan.adaptive) hipLaunchKernelGGL(lm_fill_kernel, dim3((a.n_windows + 255) / 256), dim3(256), 0, stream, ka.passes, a.n_windows, 3);
+    if (plan.resident) { // the optimize_map passes of the windows that fit it; lm_window_kernel then runs with `defer` and returns at once for the windows that are done
+        RsArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.a = ka.a; // (the scratch slices: see the aliasing table at RsArgs)
+        ra.uv_s = reinterpret_cast<float2*>(ka.uvk); ra.epos = ka.kf_pos; ra.tab = ka.a.Hll; ra.xin = ka.a.Ptrial; ra.Pbak = ka.a.P; ra.Dc = ka.a.Dinv; ra.blc = ka.a.bl;
+        ra.status = ka.status; ra.passes = ka.passes; ra.defer = defer; ra.order = ka.order; ra.dbg = scratch->prof_rs ? ka.dbg_cycles : nullptr;
+        ra.dyn_bytes = plan.ba_lanes == 512 ? scratch->rs_full_bytes : scratch->rs_narrow_bytes; ra.dyn_narrow = scratch->rs_narrow_bytes;
+        ra.want_chi2 = ka.want_chi2; // (the CALLER asked for per-edge chi2: ka.a.chi2 is never null here, carve_lm substitutes scratch)
+        ra.dense_to_general = plan.dense_to_general;
+        if (int rc = launch_ba_resident(ra, plan, iters, update_poses, update_lms, stream)) return rc;
+        ka.defer = defer;
+        if (ra.dbg) { // (VSLAM_LM_PROFILE=1 VSLAM_RS_PROFILE=1) ba_resident_kernel's clocks, then cleared for lm_window_kernel's
             static const char* rs_names[16] = {"setup", "pass init", "boot evaluation", "lambda-init pass", "linearise", "convert+cholesky+solve", "pose update+backsub+trial eval",
                                                "(loop tail)", "classification", "write-back", "lin: row open", "lin: landmark blocks", "lin: diag pair (row-wise)", "lin: off-diag pairs (row-wise)", "lin: singles chunks", "(classification: row loop)"};
-            double tot = 0;
-            for (int i = 0; i < 16; ++i) { double sum = 0; for (int w = 0; w < a.n_windows; ++w) sum += (double)h[16 * (size_t)w + i]; sum /= a.n_windows; if (i < 10) tot += sum; fprintf(stderr, "  [rs profile] %-32s %10.0f ticks/window\n", rs_names[i], sum); }
-            fprintf(stderr, "  [rs profile] total %.0f (clock64 ticks)\n", tot);
-            hipMemsetAsync(ka.dbg_cycles, 0, sizeof(long long) * kDbgSlots * a.n_windows, stream);
+            dump_phase_clocks("rs", rs_names, 16, 16, 0x3FF, ka.dbg_cycles, a.n_windows, stream);
+            hipMemsetAsync(ka.dbg_cycles, 0, cyc_bytes, stream);
         }
     }
-    if (schedule) {
+    if (plan.schedule) {
         // run_vslam.cpp:58-71: optimize_map(5) x2 without write-back, optimize_map(10) writing poses, optimize_pose_only(10)
-        if (adaptive) {
-            hipLaunchKernelGGL((lm_window_kernel<false, true>), dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, 0, 5, 0, 0, 1, 0);
+        if (plan.adaptive) {
+            hipLaunchKernelGGL((lm_window_kernel<false, true>), grid, block, kLmDynLds, stream, ka, 0, 5, 0, 0, 1, 0);
         } else {
-            if (!resident) hipLaunchKernelGGL(lm_fill_kernel, dim3((a.n_windows + 255) / 256), dim3(256), 0, stream, ka.passes, a.n_windows, 3);
-            hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, 0, 5, 0, 0, 1, 0);
-            hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, 0, 5, 0, 0, 1, 1); // (the landmark CSR of the first launch is still valid)
-            hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, 0, kSchedFinalIters, 1, 0, 1, 1);
+            hipLaunchKernelGGL(lm_window_kernel<false>, grid, block, kLmDynLds, stream, ka, 0, 5, 0, 0, 1, 0);
+            hipLaunchKernelGGL(lm_window_kernel<false>, grid, block, kLmDynLds, stream, ka, 0, 5, 0, 0, 1, 1); // (the landmark CSR of the first launch is still valid)
+            hipLaunchKernelGGL(lm_window_kernel<false>, grid, block, kLmDynLds, stream, ka, 0, kSchedFinalIters, 1, 0, 1, 1);
         }
-        // the pose-only pass: pose_only_wave_kernel; Tuning::pose_only_window = 1 (tuning aid / cross-check test) keeps the window kernel
-        ka.defer = nullptr; // (every window)
-        const bool po_window = scratch->tune && scratch->tune->pose_only_window > 0;
-        if (po_window) hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, 1, 10, 1, 0, 1, resident ? 0 : 1); // (the landmark CSR exists only where lm_window_kernel ran the passes)
+        ka.defer = nullptr; // the pose-only pass takes every window
+        if (plan.po_window) hipLaunchKernelGGL(lm_window_kernel<false>, grid, block, kLmDynLds, stream, ka, 1, 10, 1, 0, 1, plan.resident ? 0 : 1); // (the landmark CSR exists only where lm_window_kernel ran the passes)
         else {
-            if (ka.dbg_cycles && getenv("VSLAM_PO_PROFILE")) hipMemsetAsync(ka.dbg_cycles, 0, sizeof(long long) * kDbgSlots * a.n_windows, stream); // show only this pass
-            // W = kMaxKf where a window's own latency counts (at most one window per CU: sequence mode, small batches), the narrow form beyond -- the rule of
-            // launch_ba_resident; Tuning::pose_only_waves forces either
-            if (scratch->rs_dyn_bytes < 0) { int dev = 0; VS_HIP(hipGetDevice(&dev)); rs_query_device(dev, *scratch); }
-            const int forced = scratch->tune ? scratch->tune->pose_only_waves : -1;
-            const int waves = forced > 0 ? forced : (a.n_windows <= scratch->rs_cu_count ? kMaxKf : kPoseOnlyNarrowWaves);
-            switch (waves) {
-            case kMaxKf: hipLaunchKernelGGL((pose_only_wave_kernel<kMaxKf, 3>), dim3(a.n_windows), dim3(64 * kMaxKf), 0, stream, ka, 10, 1); break;
-            case kPoseOnlyNarrowWaves: hipLaunchKernelGGL((pose_only_wave_kernel<kPoseOnlyNarrowWaves, 2>), dim3(a.n_windows), dim3(64 * kPoseOnlyNarrowWaves), 0, stream, ka, 10, 1); break;
-            default: set_error("pose_only_waves %d is not built", waves); return VSLAM_ERR_ARG;
+            if (ka.dbg_cycles && scratch->prof_po) hipMemsetAsync(ka.dbg_cycles, 0, cyc_bytes, stream); // show only this pass
+            switch (plan.po_waves) {
+            case kMaxKf: hipLaunchKernelGGL((pose_only_wave_kernel<kMaxKf, 3>), grid, dim3(64 * kMaxKf), 0, stream, ka, 10, 1); break;
+            case kPoseOnlyNarrowWaves: hipLaunchKernelGGL((pose_only_wave_kernel<kPoseOnlyNarrowWaves, 2>), grid, dim3(64 * kPoseOnlyNarrowWaves), 0, stream, ka, 10, 1); break;
+            default: set_error("pose_only_waves %d is not built", plan.po_waves); return VSLAM_ERR_ARG;
             }
         }
     } else {
-        hipLaunchKernelGGL(lm_window_kernel<false>, dim3(a.n_windows), dim3(kLmBlock), dyn_lds, stream, ka, mode, iters, update_poses, update_lms, 1, 0);
+        hipLaunchKernelGGL(lm_window_kernel<false>, grid, block, kLmDynLds, stream, ka, mode, iters, update_poses, update_lms, 1, 0);
     }
     VS_HIP(hipGetLastError());
-    if (ka.dbg_cycles) {
-        hipStreamSynchronize(stream);
-        std::vector<long long> h(kDbgSlots * (size_t)a.n_windows);
-        hipMemcpy(h.data(), ka.dbg_cycles, sizeof(long long) * h.size(), hipMemcpyDeviceToHost);
+    if (ka.dbg_cycles) { // (the setup sub-splits, slots 13..15, are not in the total)
         static const char* names[kDbgSlots] = {"setup", "eval+lin", "lm blocks", "pose blocks", "lambda/Dinv", "bs", "schur", "cholesky (rest)", "solve (rest)", "update+scale", "eval trial", "loop tail", "classify+wb", "(setup: csr)", "(setup: kf-major)", "schur: item prologue",
                                                "chol: diag+rows", "chol: barrier 1", "chol: trailing update", "chol: barrier 2", "solve: barrier", "solve: back-subst", "schur: rows", "schur: reduce+store"};
-        double tot = 0;
-        for (int i = 0; i < kDbgSlots; ++i) { double s = 0; for (int w = 0; w < a.n_windows; ++w) s += (double)h[kDbgSlots * (size_t)w + i]; s /= a.n_windows; if (i < 13 || i >= 16) tot += s; fprintf(stderr, "  [lm profile] %-20s %10.0f ticks/window\n", names[i], s); }
-        fprintf(stderr, "  [lm profile] total %.0f cycles (clock64 = shader clock, thread 0 of every window; setup sub-splits not included)\n", tot);
+        dump_phase_clocks("lm", names, kDbgSlots, kDbgSlots, 0xFF1FFF, ka.dbg_cycles, a.n_windows, stream);
     }
     return VSLAM_OK;
 }
 
-int lm_fetch_deferred(const LmScratch* scratch, int n_windows, int32_t* h_defer, hipStream_t stream) {
-    if (!scratch->buf.p || !scratch->defer || !h_defer || n_windows > scratch->status_n) return VSLAM_ERR_ARG;
-    if (!scratch->defer_valid) { for (int w = 0; w < n_windows; ++w) h_defer[w] = 1; return VSLAM_OK; } // the last launch did not involve ba_resident_kernel: every window on lm_window_kernel
-    VS_HIP(hipMemcpyAsync(h_defer, scratch->defer, sizeof(int32_t) * n_windows, hipMemcpyDeviceToHost, stream));
+// the fetchers of LmScratch::last (what each accepts: see their declarations)
+static bool last_has(const LmScratch& s, const int32_t* d_words, const int32_t* h) { return s.buf.p && d_words && h; }
+static int fetch_words(const int32_t* d_words, int n, int32_t* h, hipStream_t stream) {
+    VS_HIP(hipMemcpyAsync(h, d_words, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
     VS_HIP(hipStreamSynchronize(stream));
+    return VSLAM_OK;
+}
+int lm_fetch_deferred(const LmScratch* scratch, int n_windows, int32_t* h_defer, hipStream_t stream) {
+    const LmLast& l = scratch->last;
+    if (!last_has(*scratch, l.defer, h_defer) || n_windows > l.n) return VSLAM_ERR_ARG;
+    if (!l.defer_valid) { for (int w = 0; w < n_windows; ++w) h_defer[w] = 1; return VSLAM_OK; }
+    if (int rc = fetch_words(l.defer, n_windows, h_defer, stream)) return rc;
     for (int w = 0; w < n_windows; ++w) h_defer[w] &= 1;
     return VSLAM_OK;
 }
-
 int lm_fetch_passes(const LmScratch* scratch, int n_windows, int32_t* h_passes, hipStream_t stream) {
-    if (!scratch->buf.p || !scratch->passes || !h_passes || n_windows > scratch->status_n) return VSLAM_ERR_ARG;
-    VS_HIP(hipMemcpyAsync(h_passes, scratch->passes, sizeof(int32_t) * n_windows, hipMemcpyDeviceToHost, stream));
-    VS_HIP(hipStreamSynchronize(stream));
-    return VSLAM_OK;
+    const LmLast& l = scratch->last;
+    if (!last_has(*scratch, l.passes, h_passes) || n_windows > l.n) return VSLAM_ERR_ARG;
+    return fetch_words(l.passes, n_windows, h_passes, stream);
 }
-
 int lm_fetch_status(const LmScratch* scratch, int n_windows, int32_t* h_status, hipStream_t stream) {
-    const LmScratch& g_lm = *scratch;
-    if (!g_lm.buf.p || !h_status) return VSLAM_ERR_ARG;
-    // the status words of the most recent launch live at a fixed offset that carve_lm() recorded
-    VS_HIP(hipMemcpyAsync(h_status, g_lm.status, sizeof(int32_t) * n_windows, hipMemcpyDeviceToHost, stream));
-    VS_HIP(hipStreamSynchronize(stream));
-    return VSLAM_OK;
+    if (!last_has(*scratch, scratch->last.status, h_status)) return VSLAM_ERR_ARG;
+    return fetch_words(scratch->last.status, n_windows, h_status, stream);
 }
 
 // diagnostic of rows A10 / A11: one lane per observation runs the device functions every LM kernel linearises with (cam_norm, eval_obs,
@@ -2075,9 +2087,10 @@ int launch_edge_jacobians(int n, const float* d_xyz, const float* d_uv, const do
 
 int launch_pnp(const PnpArgs& p, LmScratch* scratch, hipStream_t stream) {
     if (p.B <= 0) return VSLAM_OK;
+    if (int rc = lm_device_ready(*scratch)) return rc;
     // one wave per problem unless the caller knows the problems are large (n_hint points: the window kernel's 512 lanes pay from ~1000
     // points on); Tuning::pnp_window = 1 (tuning aid / cross-check test) forces the window kernel
-    const bool force_window = scratch->tune && scratch->tune->pnp_window > 0;
+    const bool force_window = scratch->tune->pnp_window > 0;
     if (!force_window && p.n_hint <= 1024) {
         ProfScope prof__(stream, "pnp_wave_kernel");
         hipLaunchKernelGGL(pnp_wave_kernel, dim3(p.B), dim3(64), 0, stream, p.xyz, p.uv, p.n, p.capacity, p.T, p.iters, p.K[0], p.K[1], p.K[2], p.K[3],
@@ -2093,8 +2106,9 @@ int launch_pnp(const PnpArgs& p, LmScratch* scratch, hipStream_t stream) {
     ka.a.huber_delta = p.huber_delta;
     ka.pnp_n = p.n; ka.capacity = p.capacity;
     const size_t tot = (size_t)p.B * p.capacity;
-    int rc = carve_lm(*scratch, ka, tot, tot, p.B, false, stream);
-    if (rc) return rc;
+    int32_t* defer;
+    if (int rc = carve_lm(*scratch, ka, defer, tot, tot, p.B, false, stream)) return rc;
+    scratch->last = LmLast{ka.status, p.B, ka.passes, defer, false};
     ka.order = nullptr; // (problem b runs on workgroup b)
     ProfScope prof__(stream, "lm_window_kernel<pnp>", 2);
     hipLaunchKernelGGL(lm_window_kernel<true>, dim3(p.B), dim3(kLmBlock), 0, stream, ka, 1, p.iters, 1, 0, 0, 0);

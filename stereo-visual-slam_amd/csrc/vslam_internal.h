@@ -246,7 +246,7 @@ struct LmWindowArgs {
     int32_t* kf_edges; // total_edge: landmark id of the edge stored at keyframe-major position j
     int32_t* pair_ptr; // n_windows x (NPAIR + 1)
     int32_t* pair_hits;// Schur hit records of the off-diagonal keyframe pairs: {pos1 | pos2 << 16, landmark} (8 B each)
-    int32_t hit_capacity_per_edge; // hits of a window <= n_edges_w * hit_capacity_per_edge
+    int32_t hit_capacity_per_edge; // UNUSED (nobody sets or reads it): kept because the kernels take this struct by value
     double K[4];
     double huber_delta;
     double* chi2_thr; // n_windows: final adaptive threshold of the last pass
@@ -289,37 +289,87 @@ constexpr int kSgbmErrorWord = kSgbmTicketPools; // error word of the most recen
 int launch_sgbm(const Tuning& tune, const vslam_sgbm_params& sp, const uint8_t* d_left, const uint8_t* d_right, size_t img_bytes, int pitch, int w, int h, int B,
                 float* d_disp_f32, int16_t* d_disp_i16, int16_t* d_disp_raw, DevBuf& scratch, hipStream_t stream);
 
+// ba_resident_kernel's arguments (ba_resident.hip: optimize_map / the BA schedule on windows whose landmark state fits the LDS of one CU; the rest is
+// marked in `defer`).  launch_lm_windows fills them: the scratch pointers are slices of lm_window_kernel's own scratch (carve_lm), so that both kernels
+// run in one launch set on one buffer.  ba_resident_kernel's slice <- lm_window_kernel's, and who owns it when:
+//   tab   <- Hll     (6 x total_lm doubles)  ba_resident_kernel: perm / mstat / working positions;  lm_window_kernel: H_ll of the first trial
+//   xin   <- Ptrial  (3 x total_lm doubles)  input positions as f32, sorted;                        trial landmark estimates
+//   Pbak  <- P       (3 x total_lm doubles)  accepted positions while a trial sits in LDS;          current landmark estimates
+//   Dc    <- Dinv    (6 x total_lm doubles)  D^-1 of the multi-observation landmarks;               D^-1 of every landmark
+//   blc   <- bl      (3 x total_lm doubles)  their b_l;                                             b_l of every landmark
+//   uv_s  <- uvk     (2 x total_edge floats) observations slot-major;                               observations keyframe-major
+//   epos  <- kf_pos  (total_edge int32)      caller's edge id per slot-major position;              keyframe-major position per edge
+// Sharing is safe because every one of them is cut into PER-WINDOW slices (by lm_off / edge_off) that only the workgroup of that window touches, and
+// within a launch set a window's optimize_map passes run on exactly one of the two kernels: ba_resident_kernel comes first on the stream and writes
+// defer[w]; lm_window_kernel returns at once for defer[w] == 0 and, for a window left to it (even one given up half-way), rebuilds its slices from the
+// caller's arrays.  The schedule's pose-only pass, after both, takes every window and also reads nothing that the passes left in scratch.
+struct RsArgs {
+    LmWindowArgs a;
+    float2* uv_s;          // total_edge: observations, slot-major per window: slot q of sorted landmark s at [slotoff[q] + s]
+    int32_t* epos;         // total_edge: caller's edge id (window-local) at the same position
+    double* tab;           // 6 x total_lm doubles of scratch; window slice [6 lm0, 6 (lm0 + nl)) holds, as u16: perm[nl] (sorted position ->
+                           // landmark id, window-local), mstat[nl] (keyframe set (12 bits) | slot of the landmark's last edge << 12, sorted order)
+    double* xin;           // 3 x total_lm doubles of scratch; window slice holds, as f32, the input positions in sorted order (3 nl floats)
+    double* Pbak;          // 3 x total_lm: the accepted positions while a trial sits in LDS
+    double* Dc;            // 6 x total_lm: D^-1 = (H_ll + lambda I)^-1 of the multi-observation landmarks, sorted order, 48 B records (hit-major phase)
+    double* blc;           // 3 x total_lm: their b_l, 24 B records
+    int32_t* status;
+    int32_t* passes;
+    int32_t* defer;        // n_windows: 1 = window left to lm_window_kernel
+    const int32_t* order;
+    long long* dbg;
+    int dyn_bytes;
+    int dyn_narrow;        // the dynamic LDS of the 256-lane form: WHICH windows the kernel takes and on which path (hit-major / row-wise) is decided against it in both widths, so that a window's bits do not depend on the width
+    int want_chi2;
+    int dense_to_general;  // 1: windows with more than 2.2 observations per landmark are left to lm_window_kernel (Tuning::ba_resident = 1 forces them here)
+};
+
+// Every decision of one launch_lm_windows call, taken once (plan_lm_windows, lm_kernels.hip) from the call's shape, the context's Tuning and the
+// device's CU count; the launchers only execute it.  The reasons for the rules stand at the Tuning fields.
+struct LmPlan {
+    bool schedule;         // the BA schedule of run_vslam.cpp:58-71 (else one pass of the caller's mode)
+    bool resident;         // ba_resident_kernel runs first and takes the optimize_map passes of the windows it does not mark in `defer`
+    bool adaptive;         // schedule: one launch per kernel runs a window's passes back to back (else three launches, every pass for every window)
+    bool dense_to_general; // resident: windows above 2.2 observations per landmark are deferred too
+    bool order;            // lm_order_kernel deals the windows largest first
+    bool po_window;        // schedule: the pose-only pass on lm_window_kernel, else on pose_only_wave_kernel ...
+    int po_waves;          // ... with this many waves per window
+    int ba_lanes;          // resident: 256 | 512 lanes per window
+    int launches;          // what the stage profiler is told: 1, 2 (adaptive) or 4 (plain schedule), + resident; lm_order_kernel and lm_fill_kernel are not counted
+};
+
+// What the most recent launch on a context's LmScratch left for vslam_ba_status_dev / _schedule_passes_dev / _deferred_dev.  Replaced whole by
+// every launcher that carves the scratch (launch_lm_windows, launch_pnp's window form) and by vslam_ba_chain_dev, never field by field.
+struct LmLast {
+    int32_t* status = nullptr; int n = 0; // per window: VSLAM_OK or why the kernel rejected its graph; windows of that launch
+    int32_t* passes = nullptr;  // optimize_map passes executed per window -- written by a schedule only: after any other launch the slot holds whatever it held
+    int32_t* defer = nullptr;   // per window: 1 = left to lm_window_kernel by ba_resident_kernel ...
+    bool defer_valid = false;   // ... written by that launch (it involved ba_resident_kernel); false: every window ran on lm_window_kernel
+    // after a chain: the caller's windows with the status of the step that ran each; the per-launch diagnostics describe single steps and are not available
+    static LmLast of_chain(int32_t* status, int n) { LmLast l; l.status = status; l.n = n; return l; }
+};
 // device scratch of the LM kernels: owned by the context (two contexts / streams must not share it), grown on demand
 struct LmScratch {
     DevBuf buf, cyc; // the kernels' scratch; the phase clocks of the LM kernels (VSLAM_LM_PROFILE), kDbgSlots per window
-    int32_t* status = nullptr; int status_n = 0;
-    int32_t* passes = nullptr; // optimize_map passes executed per window by the most recent schedule (lm_fetch_passes)
-    const Tuning* tune = nullptr; // the owning context's overrides
-    bool lds_opt_in = false; // the > 64 KB dynamic-LDS attribute of lm_window_kernel has been set on this context's device
-    bool rs_opt_in = false;  // ... of ba_resident_kernel
-    // ba_resident_kernel on this context's device (rs_query_device; rs_dyn_bytes -1: not queried yet): dynamic LDS of a 256-lane workgroup
-    // (two windows per CU) and of a 512-lane one (the whole CU), and the CU count
-    int rs_dyn_bytes = -1, rs_full_bytes = 0, rs_cu_count = 0;
-    int32_t* defer = nullptr; // per window of the most recent launch: 1 = left to lm_window_kernel by ba_resident_kernel
-    bool defer_valid = false; // ... written by that launch (it involved ba_resident_kernel)
-    explicit LmScratch(size_t* acct) : buf("LM scratch", acct), cyc("LM clock buffer", acct) {}
+    const Tuning* tune; // the owning context's overrides
+    // tuning aids, read from the environment ONCE by vslam_create: VSLAM_LM_PROFILE (phase clocks of the window kernels to stderr), with it
+    // VSLAM_RS_PROFILE (those of ba_resident_kernel first) and VSLAM_PO_PROFILE (the clocks are cleared before the pose-only pass: only that pass shows)
+    bool prof_lm = false, prof_rs = false, prof_po = false;
+    // lm_device_ready, on the first LM launch of the context: every instance of lm_window_kernel and ba_resident_kernel may use more than 64 KB of
+    // dynamic LDS on this context's device; ba_resident_kernel's dynamic LDS at 256 lanes (two windows per CU) and at 512 (the whole CU); the CU count
+    bool dev_ready = false;
+    int rs_narrow_bytes = 0, rs_full_bytes = 0, cu_count = 0;
+    LmLast last;
+    LmScratch(size_t* acct, const Tuning* t) : buf("LM scratch", acct), cyc("LM clock buffer", acct), tune(t) {}
 };
-// ba_resident.hip: optimize_map / the BA schedule on windows whose landmark state fits the LDS of one CU (the rest is marked in `defer`)
-struct RsLaunch {
-    LmWindowArgs a;
-    void* uv_s; int32_t* epos; double* tab; double* xin; double* Pbak; double* Dc; double* blc; // scratch slices (see RsArgs)
-    int32_t* status; int32_t* passes; int32_t* defer; const int32_t* order; long long* dbg;
-    int dyn_bytes, full_bytes, cu_count; // LmScratch::rs_dyn_bytes, rs_full_bytes, rs_cu_count
-    int schedule, adaptive, iters, update_poses, update_lms, dense_to_general;
-    int want_chi2;           // the CALLER asked for per-edge chi2 (L.a.chi2 is never null here: the LM layout substitutes scratch)
-    int lanes;               // 256 | 512 forces a width of ba_resident_kernel (Tuning::ba_lanes); 0: by the number of windows in the launch
-    bool opt_in_done;
-};
-void rs_query_device(int device, LmScratch& s);
-int launch_ba_resident(const RsLaunch& L, hipStream_t stream);
+int rs_device_ready(int device, LmScratch& s); // ba_resident.hip's half of lm_device_ready
+// iters / update_poses / update_lms: of a single pass (plan.schedule false)
+int launch_ba_resident(const RsArgs& ra, const LmPlan& plan, int iters, int update_poses, int update_lms, hipStream_t stream);
 int launch_lm_windows(const LmWindowArgs& a, int schedule, int mode, int iters, int update_poses, int update_lms, LmScratch* scratch,
                       hipStream_t stream);
-size_t lm_hits_per_edge();
+// The fetchers synchronise the stream.  Kept as they were (bench.py relies on them): lm_fetch_status does NOT compare n_windows with the last launch's
+// count (asking for more reads past the status words), the other two refuse n_windows beyond it; lm_fetch_passes after a launch that was no schedule
+// returns whatever the slot holds; lm_fetch_deferred after a launch without ba_resident_kernel returns all 1.
 int lm_fetch_status(const LmScratch* scratch, int n_windows, int32_t* h_status, hipStream_t stream);
 int lm_fetch_passes(const LmScratch* scratch, int n_windows, int32_t* h_passes, hipStream_t stream);
 int lm_fetch_deferred(const LmScratch* scratch, int n_windows, int32_t* h_defer, hipStream_t stream);
@@ -481,9 +531,10 @@ struct Ctx {
     bool sgbm_unchecked;  // an asynchronous SGBM launch whose error word nobody has read yet (vslam_sync / vslam_sgbm_status_dev do)
     DevBuf ransac{"RANSAC scratch", &dev_bytes}; // hypothesis tables of vslam_pnp_ransac_dev
     DevBuf track{"track scratch", &dev_bytes};   // chain tables of vslam_build_windows_dev
-    LmScratch lm{&dev_bytes};
     Tuning tune;
+    LmScratch lm{&dev_bytes, &tune};
     Prof* prof;           // stage profiler of this context (vslam_profile_enable); null until first enabled
+    bool prof_orb;        // VSLAM_ORB_PROFILE was set when the context was created: every ORB call dumps the phase clocks of its kernels
     RectifyState rect;    // vslam_rectify_set / vslam_rectify_set_maps
     DevBuf segbuf{"segment table", &dev_bytes}; // vslam_set_segments: first, start, qitem
     SegView seg;          // ... as the launchers take it (all null: no table)
