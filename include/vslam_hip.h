@@ -1068,6 +1068,100 @@ int vslam_pose_graph_dev(vslam_ctx* ctx, const vslam_pose_graph* graph, const vs
 /* the status words of the n_graphs graphs of the most recent vslam_pose_graph_dev call, into h_status (host); synchronises the context stream */
 int vslam_pose_graph_status_dev(vslam_ctx* ctx, int n_graphs, int32_t* h_status);
 
+/* ------------------------------------------------------------------ full bundle adjustment: loop closing moves the map too -------- */
+/* What follows the pose graph: all keyframes and all landmarks of a sequence over all their observations, with the loop edges as relative-pose
+ * factors.  A batch of n_problems independent problems laid back to back (problem p owns keyframes [kf_off[p], kf_off[p+1]), landmarks
+ * [lm_off[p], lm_off[p+1]), observations [obs_off[p], obs_off[p+1]) and edges [edge_off[p], edge_off[p+1])), each optimised by one persistent
+ * workgroup through all its Levenberg-Marquardt iterations.  The reference has no such stage (its optimize_map sees ten keyframes).  Additive:
+ * vslam_params and the ABI version are unchanged; the host mirror (host/) does not call it.
+ *
+ * PROBLEM.  Keyframe k holds T_k = T_c_w (7 doubles), landmark l holds X_l (3 doubles, world).  An observation is (kf, lm, uv, disp) with
+ * PROBLEM-LOCAL ids, sorted by landmark inside a problem (non-decreasing lm: the rule of vslam_ba_batch).  With P = R_k X_l + t_k its residual is
+ * e = [u - (fx Px / Pz + cx), v - (fy Py / Pz + cy)] (vo_projection_residual) and, when disp is valid, a third row d - bf / Pz.  disp is the stereo
+ * disparity measured at that keypoint (fx b / Z of the keypoint's own stereo depth); a negative or NaN disp marks a left-image-only observation,
+ * d_obs_disp NULL makes every observation one.  The stereo rows fix the scale: with them and one held keyframe the minimum is unique.
+ * With A = de/dP = [[-fx/Pz, 0, fx Px/Pz^2], [0, -fy/Pz, fy Py/Pz^2], [0, 0, bf/Pz^2]]:  de/d delta_k = A [I, -P^],  de/dX_l = A R_k.
+ * ROBUST KERNEL.  Huber on s = e'e of width huber_delta: rho = s for s <= delta^2, else 2 sqrt(s) delta - delta^2; the weight rho' multiplies
+ * J'J and J'e (g2o's rule).  huber_delta = 0: none.
+ * EDGES.  (i, j, Z, w[6]) between keyframes i != j: residual, Jacobians and meaning exactly those of vslam_pose_graph.  total_edges = 0 is allowed.
+ * COST.  sum rho(e'e) over the ACTIVE observations + sum r' diag(w) r over the ACTIVE edges.  UPDATE.  T <- exp(delta) o T, X <- X + dX.
+ * HELD.  d_fixed[k] != 0 holds keyframe k; NULL holds keyframe 0 of every problem.  A keyframe without an active observation and without an active
+ * edge is held too.  A landmark without an active observation is copied through.
+ * BEHIND THE CAMERA.  An active observation whose point has Pz <= 0 at the input state is inactive for this call and counted (n_obs_dropped,
+ * VSLAM_FBA_DROPPED).  A trial state in which an active observation has Pz <= 0 costs infinity: the step is rejected.
+ * LM.  The pose graph's rule: (H + lambda diag(H)) on the full system, before the elimination, from lambda_init; a step that lowers the cost is
+ * accepted, then lambda <- max(lambda / 10, 1e-12); a rejected step gives lambda <- 10 lambda.  Stops at |delta| < step_tol (poses and points
+ * together), at lambda > 1e12 or at max_iters.  All arithmetic is f64.
+ * SOLVER.  The landmarks are eliminated (3 x 3 blocks V_l, closed-form inverse); the reduced camera system S = U + edges - W V^-1 W' is solved by
+ * preconditioned conjugate gradients that never form it, to |r| <= pcg_tol |b| or pcg_max_iters; the preconditioner is block-Jacobi, the 6 x 6
+ * blocks U_k + edges - sum_o W_o V^-1 W_o' (the diagonal blocks of S when no keyframe observes a landmark twice); then the landmarks are
+ * back-substituted.  A damped V_l that is not positive definite holds that landmark for the iteration (VSLAM_FBA_SINGULAR); so does a diagonal
+ * block of the preconditioner, whose pivot is replaced by 1.
+ * DETERMINISM.  As the pose graph: keyframe sums walk a per-keyframe incidence list in ascending observation order, landmark sums their
+ * observations in ascending order, dot products in an order that depends on the problem's own counts only, no floating-point atomics.  The same
+ * call twice writes the same bytes, and a problem's output in a batch is bit for bit its output alone.
+ * SAFETY.  Every offset is checked on the device for range, order and disjointness, every keyframe and landmark id for range, the landmark order
+ * of the observations, and every pose, point, measurement and weight for finiteness (a +inf disp is non-finite; weights must be >= 0).  A problem
+ * with a bad offset is skipped entirely (only its status word is written); one with a bad id, a broken landmark order or a non-finite value has
+ * its poses and points copied through and its status bit set.  Its neighbours are untouched.  Degenerate problems (no observations, one keyframe,
+ * every keyframe held, a keyframe without observations, a landmark seen once) are results: finite output. */
+#define VSLAM_FBA_BAD_INDEX 1   /* an offset, a keyframe / landmark id out of range, or observations not sorted by landmark: problem skipped */
+#define VSLAM_FBA_NONFINITE 2   /* a non-finite pose / point / measurement / weight or a negative weight: problem passed through              */
+#define VSLAM_FBA_PCG_CAP 4     /* PCG reached pcg_max_iters in some step (the step is still a descent candidate)                             */
+#define VSLAM_FBA_LAMBDA 8      /* stopped because lambda exceeded 1e12                                                                       */
+#define VSLAM_FBA_SINGULAR 16   /* a damped landmark block or a preconditioner block was not positive definite in some iteration              */
+#define VSLAM_FBA_DROPPED 32    /* observations behind the camera at the input state were left out (n_obs_dropped)                            */
+typedef struct vslam_full_ba {
+    int32_t struct_size;          /* sizeof(vslam_full_ba): set by the caller, checked */
+    int32_t n_problems;
+    int32_t total_kfs, total_lms, total_obs, total_edges;
+    const int32_t* d_kf_off;      /* n_problems + 1 */
+    const int32_t* d_lm_off;      /* n_problems + 1 */
+    const int32_t* d_obs_off;     /* n_problems + 1 */
+    const int32_t* d_edge_off;    /* n_problems + 1 */
+    const double* d_T;            /* total_kfs x 7, in */
+    const uint8_t* d_fixed;       /* total_kfs, or NULL: keyframe 0 of every problem */
+    const double* d_xyz;          /* total_lms x 3, in */
+    const int32_t* d_obs_kf;      /* total_obs, problem-local */
+    const int32_t* d_obs_lm;      /* total_obs, problem-local, non-decreasing inside a problem */
+    const float* d_obs_uv;        /* total_obs x 2 */
+    const float* d_obs_disp;      /* total_obs, or NULL: all mono; negative or NaN = mono */
+    const uint8_t* d_obs_active;  /* total_obs, or NULL: all active */
+    double* d_obs_chi2;           /* total_obs, out: e'e of EVERY observation (inactive ones too) at the output state; NULL = not wanted */
+    const int32_t* d_edge_i;      /* total_edges, problem-local */
+    const int32_t* d_edge_j;      /* total_edges, problem-local */
+    const double* d_edge_Z;       /* total_edges x 7 */
+    const double* d_edge_w;       /* total_edges x 6 */
+    const uint8_t* d_edge_active; /* total_edges, or NULL: all active */
+    double K4[4];                 /* fx, fy, cx, cy */
+    double bf;                    /* fx x baseline */
+    double huber_delta;           /* 0 = no robust kernel */
+} vslam_full_ba;
+typedef struct vslam_full_ba_params {
+    int32_t struct_size;          /* sizeof(vslam_full_ba_params) */
+    int32_t max_iters;            /* LM iterations; 0 = evaluate only */
+    int32_t pcg_max_iters;
+    int32_t reserved;
+    double pcg_tol;               /* relative residual */
+    double step_tol;
+    double lambda_init;
+} vslam_full_ba_params;
+typedef struct vslam_full_ba_stats {
+    double chi2_init, chi2_final, lambda;
+    int32_t lm_iters, pcg_iters, n_free, n_obs_dropped, status, reserved;
+} vslam_full_ba_stats;
+/* max_iters 50, pcg_max_iters 4000, pcg_tol 1e-10, step_tol 1e-9, lambda_init 1e-4 (the pose graph's; DESIGN.md 5.11 for the iteration counts) */
+void vslam_full_ba_default_params(vslam_full_ba_params* p);
+/* Optimises every problem of the batch: d_T_out (total_kfs x 7; may be d_T itself), d_xyz_out (total_lms x 3; may be d_xyz itself) and, when
+ * not NULL, d_stats (n_problems) and ba->d_obs_chi2.  params NULL = the defaults.  max_iters = 0 evaluates only: chi2_init and the observation chi2
+ * are written, poses and points copied.  Refuses with VSLAM_ERR_ARG and a message before it launches anything: a null where a pointer is
+ * required, negative counts, a wrong struct_size, parameters or camera out of range.  Asynchronous on the context stream; the state lives in a
+ * growable buffer of the context counted in vslam_device_bytes. */
+int vslam_full_ba_dev(vslam_ctx* ctx, const vslam_full_ba* ba, const vslam_full_ba_params* params, double* d_T_out, double* d_xyz_out,
+                      vslam_full_ba_stats* d_stats);
+/* the status words of the n_problems problems of the most recent vslam_full_ba_dev call, into h_status (host); synchronises the context stream */
+int vslam_full_ba_status_dev(vslam_ctx* ctx, int n_problems, int32_t* h_status);
+
 /* ------------------------------------------------------------------ raw device memory helpers ---------- */
 /* For hosts without their own device allocator (the C++ mirror in host/); bench.py passes torch tensors. */
 int vslam_dev_alloc(void** p, size_t bytes);

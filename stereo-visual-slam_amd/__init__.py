@@ -134,6 +134,28 @@ POSE_GRAPH_STATS_DTYPE = np.dtype([("chi2_init", "<f8"), ("chi2_final", "<f8"), 
 PG_BAD_INDEX, PG_NONFINITE, PG_PCG_CAP, PG_LAMBDA, PG_SINGULAR = 1, 2, 4, 8, 16
 
 
+class FullBABatch(C.Structure):
+    """vslam_full_ba: a batch of independent full bundle adjustment problems laid back to back (device pointers, the camera by value); struct_size is
+    filled in by VO.full_ba_dev"""
+    _fields_ = [("struct_size", C.c_int32), ("n_problems", C.c_int32), ("total_kfs", C.c_int32), ("total_lms", C.c_int32), ("total_obs", C.c_int32),
+                ("total_edges", C.c_int32), ("d_kf_off", C.c_void_p), ("d_lm_off", C.c_void_p), ("d_obs_off", C.c_void_p), ("d_edge_off", C.c_void_p),
+                ("d_T", C.c_void_p), ("d_fixed", C.c_void_p), ("d_xyz", C.c_void_p), ("d_obs_kf", C.c_void_p), ("d_obs_lm", C.c_void_p),
+                ("d_obs_uv", C.c_void_p), ("d_obs_disp", C.c_void_p), ("d_obs_active", C.c_void_p), ("d_obs_chi2", C.c_void_p), ("d_edge_i", C.c_void_p),
+                ("d_edge_j", C.c_void_p), ("d_edge_Z", C.c_void_p), ("d_edge_w", C.c_void_p), ("d_edge_active", C.c_void_p), ("K4", C.c_double * 4),
+                ("bf", C.c_double), ("huber_delta", C.c_double)]
+
+
+class FullBAParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("max_iters", C.c_int32), ("pcg_max_iters", C.c_int32), ("reserved", C.c_int32),
+                ("pcg_tol", C.c_double), ("step_tol", C.c_double), ("lambda_init", C.c_double)]
+
+
+# vslam_full_ba_stats, one per problem
+FULL_BA_STATS_DTYPE = np.dtype([("chi2_init", "<f8"), ("chi2_final", "<f8"), ("lambda", "<f8"), ("lm_iters", "<i4"), ("pcg_iters", "<i4"), ("n_free", "<i4"),
+                                ("n_obs_dropped", "<i4"), ("status", "<i4"), ("reserved", "<i4")])
+FBA_BAD_INDEX, FBA_NONFINITE, FBA_PCG_CAP, FBA_LAMBDA, FBA_SINGULAR, FBA_DROPPED = 1, 2, 4, 8, 16, 32
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("launches", C.c_int32), ("calls", C.c_int32)]
 
@@ -244,6 +266,9 @@ SIGNATURES = {
     "vslam_pose_graph_default_params": (None, [C.POINTER(PoseGraphParams)]),
     "vslam_pose_graph_dev": (I, [P, C.POINTER(PoseGraphBatch), C.POINTER(PoseGraphParams), P, P]),
     "vslam_pose_graph_status_dev": (I, [P, I, P]),
+    "vslam_full_ba_default_params": (None, [C.POINTER(FullBAParams)]),
+    "vslam_full_ba_dev": (I, [P, C.POINTER(FullBABatch), C.POINTER(FullBAParams), P, P, P]),
+    "vslam_full_ba_status_dev": (I, [P, I, P]),
     "vslam_dev_alloc": (I, [P, Z]), "vslam_dev_free": (I, [P]), "vslam_dev_upload": (I, [P, P, P, Z]), "vslam_dev_download": (I, [P, P, P, Z]),
     "vslam_dev_memset": (I, [P, P, I, Z]),
 }
@@ -379,6 +404,15 @@ def default_pose_graph_params(**kw):
     """vslam_pose_graph_default_params (max_iters 50, pcg_max_iters 4000, pcg_tol 1e-10, step_tol 1e-9, lambda_init 1e-4), fields overridden by keyword"""
     p = PoseGraphParams()
     load_library().vslam_pose_graph_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_full_ba_params(**kw):
+    """vslam_full_ba_default_params (max_iters 50, pcg_max_iters 4000, pcg_tol 1e-10, step_tol 1e-9, lambda_init 1e-4), fields overridden by keyword"""
+    p = FullBAParams()
+    load_library().vslam_full_ba_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -872,6 +906,66 @@ class VO:
         self.sync()
         stats = t["stats"].cpu().numpy().view(POSE_GRAPH_STATS_DTYPE)[:G].copy()
         return dict(T=t["out"].cpu().numpy(), stats=stats, edge_chi2=t["chi2"].cpu().numpy())
+
+    # ------------------------------------------------------------ full bundle adjustment (no counterpart in the reference)
+    def full_ba_dev(self, ba, params=None, d_T_out=None, d_xyz_out=None, d_stats=None):
+        """vslam_full_ba_dev on a FullBABatch of device pointers: the optimised poses into d_T_out (total_kfs x 7 doubles; may be ba.d_T), the points into
+        d_xyz_out (total_lms x 3 doubles; may be ba.d_xyz), the per-problem vslam_full_ba_stats into d_stats (or None).  Asynchronous.  Semantics in
+        include/vslam_hip.h."""
+        ba.struct_size = C.sizeof(FullBABatch)
+        self._chk(self.lib.vslam_full_ba_dev(self.h, C.byref(ba), None if params is None else C.byref(params), d_T_out, d_xyz_out, d_stats), "vslam_full_ba_dev")
+
+    def full_ba_status(self, n_problems):
+        """the status words (FBA_* bits) of the problems of the most recent full_ba_dev call; synchronises"""
+        st = np.zeros(n_problems, np.int32)
+        self._chk(self.lib.vslam_full_ba_status_dev(self.h, n_problems, st), "vslam_full_ba_status_dev")
+        return st
+
+    def full_ba(self, T, xyz, offsets, obs, edges=None, fixed=None, K4=None, bf=None, huber_delta=0.0, params=None, **kw):
+        """A batch of full bundle adjustment problems from numpy arrays: T (total_kfs, 7) poses T_c_w, xyz (total_lms, 3), offsets = dict(kf, lm, obs,
+        edge: G + 1 each), obs = dict(kf, lm (problem-local ids, sorted by landmark inside a problem), uv (O, 2), disp (O) or None, active (O) or
+        None), edges = dict(i, j, Z (E, 7), w (E, 6), active or None) or None; fixed (total_kfs) optional; K4 = (fx, fy, cx, cy) and bf default to
+        the context's camera; params a FullBAParams, or its fields by keyword.  Uploads, runs, downloads.  Returns dict(T, xyz, stats (G records
+        of FULL_BA_STATS_DTYPE), obs_chi2 (O))."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        T = np.ascontiguousarray(T, np.float64).reshape(-1, 7); xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        off = {k: np.ascontiguousarray(offsets[k], np.int32) for k in ("kf", "lm", "obs", "edge")}
+        G = len(off["kf"]) - 1
+        assert G >= 0 and all(len(v) == G + 1 for v in off.values())
+        okf = np.ascontiguousarray(obs["kf"], np.int32); olm = np.ascontiguousarray(obs["lm"], np.int32)
+        uv = np.ascontiguousarray(obs["uv"], np.float32).reshape(-1, 2)
+        N, M, O = len(T), len(xyz), len(okf)
+        assert len(olm) == O and len(uv) == O
+        e = edges if edges is not None else dict(i=np.zeros(0, np.int32), j=np.zeros(0, np.int32), Z=np.zeros((0, 7)), w=np.zeros((0, 6)))
+        ei = np.ascontiguousarray(e["i"], np.int32); ej = np.ascontiguousarray(e["j"], np.int32)
+        Z = np.ascontiguousarray(e["Z"], np.float64).reshape(-1, 7); w = np.ascontiguousarray(e["w"], np.float64).reshape(-1, 6)
+        E = len(ei)
+        assert len(ej) == E and len(Z) == E and len(w) == E
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        t = dict(kf_off=up(off["kf"]), lm_off=up(off["lm"]), obs_off=up(off["obs"]), edge_off=up(off["edge"]), T=up(T), xyz=up(xyz), okf=up(okf), olm=up(olm),
+                 uv=up(uv), ei=up(ei), ej=up(ej), Z=up(Z), w=up(w), T_out=torch.zeros((N, 7), dtype=torch.float64, device=dev),
+                 xyz_out=torch.zeros((M, 3), dtype=torch.float64, device=dev), chi2=torch.zeros(O, dtype=torch.float64, device=dev),
+                 stats=torch.zeros(max(G, 1) * FULL_BA_STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev))
+        for key, src, n, dt in (("disp", obs.get("disp"), O, np.float32), ("oact", obs.get("active"), O, np.uint8), ("eact", e.get("active"), E, np.uint8),
+                                ("fixed", fixed, N, np.uint8)):
+            if src is not None:
+                t[key] = up(np.ascontiguousarray(src, dt)); assert len(t[key]) == n, key
+        ptr = lambda k: t[k].data_ptr() if k in t and t[k].numel() else None
+        cam = list(self.params.cam)
+        K4 = cam[:4] if K4 is None else [float(v) for v in K4]
+        ba = FullBABatch(n_problems=G, total_kfs=N, total_lms=M, total_obs=O, total_edges=E, d_kf_off=t["kf_off"].data_ptr(), d_lm_off=t["lm_off"].data_ptr(),
+                         d_obs_off=t["obs_off"].data_ptr(), d_edge_off=t["edge_off"].data_ptr(), d_T=ptr("T"), d_fixed=ptr("fixed"), d_xyz=ptr("xyz"),
+                         d_obs_kf=ptr("okf"), d_obs_lm=ptr("olm"), d_obs_uv=ptr("uv"), d_obs_disp=ptr("disp"), d_obs_active=ptr("oact"), d_obs_chi2=ptr("chi2"),
+                         d_edge_i=ptr("ei"), d_edge_j=ptr("ej"), d_edge_Z=ptr("Z"), d_edge_w=ptr("w"), d_edge_active=ptr("eact"),
+                         K4=(C.c_double * 4)(*K4), bf=float(cam[0] * cam[4] if bf is None else bf), huber_delta=float(huber_delta))
+        if params is None and kw:
+            params = default_full_ba_params(**kw)
+        torch.cuda.synchronize()   # (the uploads are done before the context stream reads them)
+        self.full_ba_dev(ba, params, ptr("T_out"), ptr("xyz_out"), t["stats"].data_ptr())
+        self.sync()
+        stats = t["stats"].cpu().numpy().view(FULL_BA_STATS_DTYPE)[:G].copy()
+        return dict(T=t["T_out"].cpu().numpy(), xyz=t["xyz_out"].cpu().numpy(), stats=stats, obs_chi2=t["chi2"].cpu().numpy())
 
     def profile_enable(self, on=True):
         self._chk(self.lib.vslam_profile_enable(self.h, on), "vslam_profile_enable")

@@ -139,6 +139,7 @@ static const TuneKey kTuneKeys[] = {
     {"rectify_form", "VSLAM_RECTIFY_FORM", &Tuning::rectify_form, 0, 1},
     {"voxel_form", "VSLAM_VOXEL_FORM", &Tuning::voxel_form, 0, 1},
     {"pg_precond", "VSLAM_PG_PRECOND", &Tuning::pg_precond, 0, 1},
+    {"fba_store", "VSLAM_FBA_STORE", &Tuning::fba_store, 0, 1},
 };
 static int tune_set(Tuning& t, const TuneKey& k, long v) {
     if (v == -1) { t.*(k.field) = -1; return VSLAM_OK; } // back to the library's rule
@@ -255,7 +256,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
            "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel "
            "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel "
-           "pose_graph_kernel";
+           "pose_graph_kernel full_ba_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -315,7 +316,7 @@ void vslam_destroy(vslam_ctx* ctx) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     orb_tables_free(&c->tab);
-    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc, &c->segbuf, &c->chain, &c->pgraph}) b->release();
+    for (DevBuf* b : {&c->stage, &c->sgbm, &c->ransac, &c->track, &c->lm.buf, &c->lm.cyc, &c->segbuf, &c->chain, &c->pgraph, &c->fullba}) b->release();
     if (c->h_pinned) hipHostFree(c->h_pinned);
     void* ptrs[] = {c->orb.d_pyr, c->orb.d_corners, c->orb.d_corner_cnt, c->orb.d_sel, c->orb.d_sel_cnt, c->orb.d_status, c->orb.d_det, c->orb.d_blur, c->orb.d_rawt, c->orb.d_cs, c->orb.d_order, c->orb.d_rad, c->orb.d_anms_path,
                     c->match.d_train_best, c->rect.d_map[0], c->rect.d_map[1], c->rect.d_tiles[0], c->rect.d_tiles[1]};
@@ -2018,6 +2019,66 @@ int vslam_pose_graph_status_dev(vslam_ctx* ctx, int n_graphs, int32_t* h_status)
     if (n_graphs > c->pgraph_n) { set_error("vslam_pose_graph_status_dev: %d graphs asked for, the most recent vslam_pose_graph_dev call had %d", n_graphs, c->pgraph_n); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     if (n_graphs > 0) VS_HIP(hipMemcpyAsync(h_status, c->pgraph.p, sizeof(int32_t) * (size_t)n_graphs, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return VSLAM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- full bundle adjustment
+void vslam_full_ba_default_params(vslam_full_ba_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(vslam_full_ba_params);
+    p->max_iters = 50; p->pcg_max_iters = 4000; p->pcg_tol = 1e-10; p->step_tol = 1e-9; p->lambda_init = 1e-4;
+}
+
+// (the checks on the structs come before the one on the context: they need no device)
+int vslam_full_ba_dev(vslam_ctx* ctx, const vslam_full_ba* ba, const vslam_full_ba_params* params, double* d_T_out, double* d_xyz_out,
+                      vslam_full_ba_stats* d_stats) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!ba) { set_error("vslam_full_ba_dev: null problem"); return VSLAM_ERR_ARG; }
+    if (ba->struct_size != (int32_t)sizeof(vslam_full_ba)) { set_error("vslam_full_ba_dev: vslam_full_ba struct_size %d, the library has %d", ba->struct_size, (int)sizeof(vslam_full_ba)); return VSLAM_ERR_ARG; }
+    vslam_full_ba_params p;
+    vslam_full_ba_default_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(vslam_full_ba_params)) { set_error("vslam_full_ba_dev: vslam_full_ba_params struct_size %d, the library has %d", params->struct_size, (int)sizeof(vslam_full_ba_params)); return VSLAM_ERR_ARG; }
+        p = *params;
+    }
+    if (p.max_iters < 0 || p.pcg_max_iters < 1 || !(p.pcg_tol >= 0) || !(p.step_tol >= 0) || !(p.lambda_init > 0) || !(p.lambda_init <= 1e12)) {
+        set_error("vslam_full_ba_dev: parameters out of range (max_iters >= 0, pcg_max_iters >= 1, pcg_tol >= 0, step_tol >= 0, 0 < lambda_init <= 1e12)");
+        return VSLAM_ERR_ARG;
+    }
+    const double big = 1.7976931348623157e308;
+    if (!(ba->K4[0] > 0) || !(ba->K4[0] <= big) || !(ba->K4[1] > 0) || !(ba->K4[1] <= big) || !(fabs(ba->K4[2]) <= big) || !(fabs(ba->K4[3]) <= big) || !(ba->bf >= 0) ||
+        !(ba->bf <= big) || !(ba->huber_delta >= 0) || !(ba->huber_delta <= big)) {
+        set_error("vslam_full_ba_dev: camera out of range (fx, fy > 0, cx, cy finite, bf >= 0, huber_delta >= 0, all finite)");
+        return VSLAM_ERR_ARG;
+    }
+    if (ba->n_problems < 0 || ba->total_kfs < 0 || ba->total_lms < 0 || ba->total_obs < 0 || ba->total_edges < 0) {
+        set_error("vslam_full_ba_dev: negative count (n_problems %d, total_kfs %d, total_lms %d, total_obs %d, total_edges %d)", ba->n_problems, ba->total_kfs, ba->total_lms, ba->total_obs, ba->total_edges);
+        return VSLAM_ERR_ARG;
+    }
+    if (!ba->d_kf_off || !ba->d_lm_off || !ba->d_obs_off || !ba->d_edge_off) { set_error("vslam_full_ba_dev: null d_kf_off, d_lm_off, d_obs_off or d_edge_off"); return VSLAM_ERR_ARG; }
+    if (ba->total_kfs > 0 && (!ba->d_T || !d_T_out)) { set_error("vslam_full_ba_dev: null d_T or d_T_out"); return VSLAM_ERR_ARG; }
+    if (ba->total_lms > 0 && (!ba->d_xyz || !d_xyz_out)) { set_error("vslam_full_ba_dev: null d_xyz or d_xyz_out"); return VSLAM_ERR_ARG; }
+    if (ba->total_obs > 0 && (!ba->d_obs_kf || !ba->d_obs_lm || !ba->d_obs_uv)) { set_error("vslam_full_ba_dev: null d_obs_kf, d_obs_lm or d_obs_uv"); return VSLAM_ERR_ARG; }
+    if (ba->total_edges > 0 && (!ba->d_edge_i || !ba->d_edge_j || !ba->d_edge_Z || !ba->d_edge_w)) { set_error("vslam_full_ba_dev: null d_edge_i, d_edge_j, d_edge_Z or d_edge_w"); return VSLAM_ERR_ARG; }
+    if (!c) { set_error("vslam_full_ba_dev: null context"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    // the library's choice (profiles/full_ba.json): stored observations
+    const int store = c->tune.fba_store >= 0 ? c->tune.fba_store : 1;
+    if (int rc = launch_full_ba(*ba, p, store, d_T_out, d_xyz_out, d_stats, c->fullba, c->stream)) return rc;
+    c->fullba_n = ba->n_problems;
+    return VSLAM_OK;
+}
+
+int vslam_full_ba_status_dev(vslam_ctx* ctx, int n_problems, int32_t* h_status) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!h_status) { set_error("vslam_full_ba_status_dev: null h_status"); return VSLAM_ERR_ARG; }
+    if (n_problems < 0) { set_error("vslam_full_ba_status_dev: negative n_problems %d", n_problems); return VSLAM_ERR_ARG; }
+    if (!c) { set_error("vslam_full_ba_status_dev: null context"); return VSLAM_ERR_ARG; }
+    if (n_problems > c->fullba_n) { set_error("vslam_full_ba_status_dev: %d problems asked for, the most recent vslam_full_ba_dev call had %d", n_problems, c->fullba_n); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    if (n_problems > 0) VS_HIP(hipMemcpyAsync(h_status, c->fullba.p, sizeof(int32_t) * (size_t)n_problems, hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipStreamSynchronize(c->stream));
     return VSLAM_OK;
 }

@@ -281,6 +281,7 @@ struct Tuning {
     int pg_precond = -1;      // VSLAM_PG_PRECOND: preconditioner of pose_graph_kernel's conjugate gradients -- 0 = block-Jacobi, 1 = chain (block-tridiagonal); default: the rule of DESIGN.md 5.10
     int voxel_form = -1;      // VSLAM_VOXEL_FORM: voxel_fuse_kernel -- 0 = every point straight into the global table, 1 = a workgroup sums its image tile in an LDS hash table first (same table either way)
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
+    int fba_store = -1;       // VSLAM_FBA_STORE: 1 = full_ba_kernel keeps (P, B) of every observation from the linearisation (default), 0 = recomputes them in every conjugate-gradient phase
 };
 // scratch: the context's SGBM buffer.  Its first 256-byte slot is a header of int32 words: the forward sweep's ticket pools, then its error word.
 constexpr int kSgbmTicketPools = 8;
@@ -514,6 +515,13 @@ int launch_place_gather(const PlaceView& v, int q0, int nq, const int32_t* d_qit
 int launch_pose_graph(const vslam_pose_graph& g, const vslam_pose_graph_params& p, int precond, double* d_T_out, vslam_pose_graph_stats* d_stats, DevBuf& buf,
                       hipStream_t stream);
 
+// ----------------------------------------------------------------------------------------------- full bundle adjustment
+// fullba_kernels.hip: one persistent workgroup per problem through all LM iterations (include/vslam_hip.h "full bundle adjustment").  The state is
+// carved from `buf`; the status words (n_problems, the library's own copy for vslam_full_ba_status_dev) are its first slot.  store: 1 = the observations'
+// (P, B) are kept from the linearisation, 0 = recomputed in every conjugate-gradient phase.
+int launch_full_ba(const vslam_full_ba& b, const vslam_full_ba_params& p, int store, double* d_T_out, double* d_xyz_out, vslam_full_ba_stats* d_stats,
+                   DevBuf& buf, hipStream_t stream);
+
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {
     vslam_params p;
@@ -546,6 +554,8 @@ struct Ctx {
     DevBuf pgraph{"pose-graph state", &dev_bytes}; // status words and per-graph state of vslam_pose_graph_dev
     int pgraph_n;         // graphs of the most recent vslam_pose_graph_dev call (0: none yet)
     bool orb_ok;          // img_w, img_h >= 64: the ORB entry points serve this context (a smaller one is a rectification target only)
+    DevBuf fullba{"full-BA state", &dev_bytes};    // status words and per-problem state of vslam_full_ba_dev
+    int fullba_n;         // problems of the most recent vslam_full_ba_dev call (0: none yet)
 };
 
 } // namespace vslam

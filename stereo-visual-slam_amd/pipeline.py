@@ -33,7 +33,7 @@ class KeyframePipeline:
                  with_ba=True, depth="match", frame_range=None, render_workers=0, sequence=None, ba_windows="synthetic",
                  lm_per_window=None, edges_per_window=None, pose="lm", window_policy="sliding", near_dist=0.2,
                  keyframe_gate=False, pose_inputs="own_depth", pose_passes=1, f2f_queries="all", sgbm_params=None, rejected_frames="pass_through",
-                 rectify=None, raw_images=None, segments=None, segment_sequences=None, ba_chain=False, ba_chain_min_kf=None):
+                 rectify=None, raw_images=None, segments=None, segment_sequences=None, ba_chain=False, ba_chain_min_kf=None, landmark_ids=False):
         """depth = "match": north_star stage (right-image ORB, L/R match, DLT); "sgbm": the reference's own depth path
         (VO::disparity_map + Frame::find_3d on the left keypoints; the right image is only consumed by SGBM).
         sgbm_params (depth="sgbm"): the StereoSGBM set of the batched disparity call -- an SgbmParams, a dict of its fields or a tuple
@@ -81,7 +81,9 @@ class KeyframePipeline:
         ba_chain (ba_windows="tracks", no frame_range): the windows of a sequence run in order, each from the poses and is_inlier flags the previous one
         left (vslam_ba_chain_dev: the reference's carried flags, optimization.cpp:160, and successive schedules, :272-278); the segments run side by side.
         ba_chain_min_kf: the BA runs on windows with at least that many keyframes (None = n_kf: run_vslam.cpp:58's keyframes_.size() >= 10; 1 = every
-        non-empty window); a smaller window passes the carried state through.  download() adds ba_lm_id (the landmarks' identities) and ba_ran."""
+        non-empty window); a smaller window passes the carried state through.  download() adds ba_lm_id (the landmarks' identities) and ba_ran.
+        landmark_ids (ba_windows="tracks", no frame_range): the window builders also write every landmark's identity (vslam_set_window_ids), which
+        full_ba() needs; ba_chain implies it.  False: no buffer is allocated and the builders launch what they always launched."""
         assert depth in ("match", "sgbm") and ba_windows in ("synthetic", "tracks") and pose in ("lm", "ransac")
         assert window_policy in ("sliding", "reference") and near_dist >= 0
         assert keyframe_gate in (False, True, "per_pass"), "keyframe_gate: False, True (on stage A's inputs) or 'per_pass' (inside the map passes)"
@@ -115,6 +117,8 @@ class KeyframePipeline:
             assert 1 <= self.ba_chain_min_kf <= n_kf, "ba_chain_min_kf: 1..n_kf"
         else:
             assert ba_chain_min_kf is None, "ba_chain_min_kf needs ba_chain"
+        self.landmark_ids = bool(landmark_ids) or self.ba_chain
+        assert not self.landmark_ids or (with_ba and ba_windows == "tracks" and frame_range is None), "landmark_ids needs ba_windows='tracks' and no frame_range"
         self.f2f_queries = f2f_queries
         self.rejected_frames = rejected_frames
         self.pose_inputs, self.pose_passes = pose_inputs, int(pose_passes)
@@ -253,8 +257,9 @@ class KeyframePipeline:
                 self.ba_evicted = torch.zeros(B, dtype=torch.int32, device=d)
             if keyframe_gate:   # (per_pass: the latest pass's states, updated in place pass by pass)
                 self.ba_frame_state = torch.zeros(B, dtype=torch.int32, device=d)
-            if self.ba_chain:   # the landmarks' identities (written by the builder) and which windows the chain ran
+            if self.landmark_ids:   # the landmarks' identities (written by the builder)
                 self.ba_lm_id = torch.zeros(self.lm_capacity, dtype=torch.int32, device=d)
+            if self.ba_chain:   # which windows the chain ran
                 self.ba_ran = torch.zeros(B, dtype=torch.int32, device=d)
             tr = TracksIn()
             tr.n_frames = B; tr.kp_capacity = self.cap; tr.lr_capacity = self.cap; tr.match_capacity = self.cap; tr.pnp_capacity = self.cap
@@ -289,7 +294,7 @@ class KeyframePipeline:
                     self.map_gap = torch.ones(B, dtype=torch.float64, device=d)
             self.ba_batch = self._make_ba_batch(self.lm_capacity, self.edge_capacity, self.ba_rel, self.ba_nkf)
             self.unique_windows = B
-            if self.ba_chain:   # context state, like the segment table: every builder of this context writes the ids from here on
+            if self.landmark_ids:   # context state, like the segment table: every builder of this context writes the ids from here on
                 self.vo.set_window_ids(self.ba_lm_id.data_ptr(), self.lm_capacity)
             if self.seg_first is not None:   # the table is context state: every consecutive-frame entry of this context honours it from here on
                 self.vo.set_segments(self.seg_first)
@@ -590,8 +595,10 @@ class KeyframePipeline:
             out["ba_kf_frame"], out["ba_evicted"] = self._keyframe_sets()
             if self.seg_first is not None:
                 out["seg_first"] = self.seg_first.copy()
+            if self.landmark_ids:
+                out["ba_lm_id"] = self.ba_lm_id.cpu().numpy()
             if self.ba_chain:
-                out["ba_lm_id"] = self.ba_lm_id.cpu().numpy(); out["ba_ran"] = self.ba_ran.cpu().numpy()
+                out["ba_ran"] = self.ba_ran.cpu().numpy()
             if self.keyframe_gate:   # (per_pass: the last pass's states; frame_state_prev: the states that pass started from)
                 out["frame_state"] = self.ba_frame_state.cpu().numpy()
                 if self.keyframe_gate == "per_pass":
@@ -790,7 +797,7 @@ class KeyframePipeline:
         gate dropped -- are counted in .pose_graph.report, not dropped silently, and so are the odometry edges that exceed the motion limit
         (PoseGraph: a pose tracked across a cut in the recording is not a measurement).  w_odo, w_loop, motion_limit, reject_chi2, params: PoseGraph and
         PoseGraph.optimize (no measured default for the weights exists).  Returns what trajectories() returns, corrected; dense_map(poses=...) takes
-        it.  The BA landmarks are not moved, and the frames of other steps are out of reach: each step starts a world of its own."""
+        it.  The BA landmarks are not moved (full_ba() does that), and the frames of other steps are out of reach: each step starts a world of its own."""
         from .posegraph import PoseGraph
         first = np.asarray(self.seg_first if self.seg_first is not None else [0, self.B], np.int64)
         pg = PoseGraph(w_odo=w_odo, w_loop=w_loop, motion_limit=motion_limit)
@@ -803,6 +810,57 @@ class KeyframePipeline:
         self.pose_graph = pg
         out = pg.optimize(self.vo, reject_chi2=reject_chi2, params=params)
         return [(ids - int(first[s_]) - int(frame_offset), Ts) for s_, (ids, Ts) in enumerate(out)]
+
+    def window_landmark_ids(self):
+        """the identities (creating frame x kp_capacity + creating keypoint) of the landmarks of the built windows, window after window (landmark_ids=True)"""
+        assert self.landmark_ids, "window_landmark_ids needs landmark_ids=True (or ba_chain=True)"
+        self.vo.sync()
+        torch.cuda.synchronize(self.dev)
+        return self.ba_lm_id.cpu().numpy()[:int(self.ba_lm_off.cpu().numpy()[-1])]
+
+    def full_ba(self, edges=None, poses=None, w_loop=(1.0, 1.0), huber_delta=None, params=None, frame_offset=0):
+        """Full bundle adjustment of the last step (include/vslam_hip.h "full bundle adjustment"): per segment all keyframes of trajectories() and all
+        landmarks of the BA windows over all their observations, the accepted rows of `edges` (what loop_closures() returned, with the same
+        frame_offset) as pose-pose factors of information w_loop, all segments in one call.  poses: the initial poses in place of trajectories(),
+        e.g. what close_loops() returned -- the landmarks are then first carried along by their creating keyframe's correction.  huber_delta: None =
+        the context's (the width the library's other BA passes use), 0 = no robust kernel.  params: a FullBAParams.  FullBA (fullba.py) says how the
+        problem is formed and what is left out; that is counted in .full_ba_result["report"].  Returns what trajectories() returns, refined;
+        dense_map(poses=...) takes it.  .full_ba_result keeps report and, per segment, dict(lm_id, xyz (every landmark of the windows at its new
+        position, float64: vo.voxel_insert_points_dev takes them as float32), in_problem, problem, xyz_problem, stats, obs_chi2).
+        Needs landmark_ids=True (or ba_chain=True).  The result is not fed back into tracking, and frames of other steps are out of reach."""
+        if not getattr(self, "landmark_ids", False):
+            raise ValueError("full_ba needs the landmarks' identities: build the pipeline with landmark_ids=True (or ba_chain=True)")
+        from .fullba import FullBA
+        trajs = self.trajectories()   # (synchronises: the step is complete)
+        if poses is not None:
+            assert len(poses) == len(trajs), "poses: one (frame_ids, T_c_w) per segment"
+        first = np.asarray(self.seg_first if self.seg_first is not None else [0, self.B], np.int64)
+        cam = list(self.vo.params.cam)
+        fb = FullBA(cam[:4], cam[0] * cam[4], self.cap, w_loop=w_loop, huber_delta=self.vo.params.huber_delta if huber_delta is None else huber_delta)
+        kf_frame, _ = self._keyframe_sets()
+        lm_off, e_off = self.ba_lm_off.cpu().numpy().astype(np.int64), self.ba_e_off.cpu().numpy().astype(np.int64)
+        n_lm, n_e = int(lm_off[-1]), int(e_off[-1])
+        ba_kf, ba_lm, ba_uv = self.ba_kf.cpu().numpy()[:n_e], self.ba_lm.cpu().numpy()[:n_e], self.ba_uv.cpu().numpy()[:n_e]
+        lm_id, lm_xyz = self.ba_lm_id.cpu().numpy()[:n_lm].astype(np.int64), self.ba_xyz.cpu().numpy()[:n_lm].astype(np.float64)
+        win_of_e = np.repeat(np.arange(self.B), np.diff(e_off)); win_of_lm = np.repeat(np.arange(self.B), np.diff(lm_off))
+        e_frame = kf_frame[win_of_e, ba_kf].astype(np.int64)
+        e_id = lm_id[lm_off[win_of_e] + ba_lm]
+        kp_xyz, kp_valid = self._points_per_keypoint()
+        self.stream.synchronize()
+        kp_xyz, kp_valid = kp_xyz.cpu().numpy(), kp_valid.cpu().numpy()
+        for s_, (ids, Ts) in enumerate(trajs):
+            T_new = None
+            if poses is not None:
+                ids_p, T_p = poses[s_]
+                assert np.array_equal(np.asarray(ids_p), np.asarray(ids)), "poses: the frame ids of trajectories(), segment %d" % s_
+                T_new = T_p
+            we = (win_of_e >= first[s_]) & (win_of_e < first[s_ + 1]); wl = (win_of_lm >= first[s_]) & (win_of_lm < first[s_ + 1])
+            fb.add_segment(first[s_], ids, Ts, e_frame[we], e_id[we], ba_uv[we], lm_id[wl], lm_xyz[wl], kp_xyz, kp_valid, T_new=T_new)
+        if edges is not None:
+            fb.add_loop_edges(edges, frame_offset=frame_offset)
+        out = fb.optimize(self.vo, params=params)
+        self.full_ba_result = dict(report=fb.report, segments=fb.last)
+        return out
 
     def close(self):
         self.vo.close()

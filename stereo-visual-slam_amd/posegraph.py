@@ -58,7 +58,7 @@ class PoseGraph:
     the RANSAC pose stage's covariance has been measured.  A caller who knows them should pass their inverses.
 
     Limits: one workgroup per graph, so a single 4096-node graph uses one compute unit.  Steps of one drive shown through show_sequence each start a
-    world of their own; a graph across steps needs poses the caller has put into one world.  BA landmarks are not moved."""
+    world of their own; a graph across steps needs poses the caller has put into one world.  BA landmarks are not moved (fullba.FullBA does that)."""
 
     def __init__(self, w_odo=(1.0, 1.0), w_loop=(1.0, 1.0), motion_limit=5.0):
         self.w_odo = np.repeat(np.asarray(w_odo, np.float64), 3); self.w_loop = np.repeat(np.asarray(w_loop, np.float64), 3)
