@@ -1162,6 +1162,85 @@ int vslam_full_ba_dev(vslam_ctx* ctx, const vslam_full_ba* ba, const vslam_full_
 /* the status words of the n_problems problems of the most recent vslam_full_ba_dev call, into h_status (host); synchronises the context stream */
 int vslam_full_ba_status_dev(vslam_ctx* ctx, int n_problems, int32_t* h_status);
 
+/* ------------------------------------------------------------------ match by projection: re-observed and fused landmarks -------- */
+/* Search by projection: the landmarks of neighbouring keyframes (or of the other end of a loop) are projected into a keyframe at its estimated
+ * pose, and each looks for its descriptor among the keypoints inside a small pixel window round the projection.  Additive: vslam_params and the
+ * ABI version are unchanged; the host mirror (host/) does not call it.
+ *
+ * ITEMS.  A batch of n_items items laid back to back: item m owns landmarks [lm_off[m], lm_off[m+1]), names a target image item_img[m] in [0, B)
+ * and carries a pose item_T[m] (7 doubles qx qy qz qw tx ty tz, T_c_w).  The target image indexes d_kps and d_n at stride kp_capacity and d_desc at
+ * desc_stride_bytes (0 = kp_capacity x 32): the layout vslam_place_add_dev takes.  Sort the items by image: neighbours then share the descriptors
+ * in the cache.
+ * LANDMARKS.  A world point lm_xyz (3 doubles) and a descriptor row lm_desc_row into d_src_desc (n_src_rows rows of 32 bytes; it may be d_desc
+ * itself: a landmark's identity frame x kp_capacity + keypoint is then its row).
+ * CAMERA.  K4 = fx fy cx cy, a HOST pointer read during the call, or NULL for the context's camera; w and h are the context's img_w and img_h.
+ * THE RULE, per landmark, in f64 without contraction:
+ *   1. R from the quaternion as it stands (no normalisation): R00 = 1 - 2 (yy + zz), R01 = 2 (xy - zw), R02 = 2 (xz + yw), R10 = 2 (xy + zw),
+ *      R11 = 1 - 2 (xx + zz), R12 = 2 (yz - xw), R20 = 2 (xz - yw), R21 = 2 (yz + xw), R22 = 1 - 2 (xx + yy);  P = ((Ri0 X + Ri1 Y) + Ri2 Z) + ti.
+ *      Not z_min <= Pz <= z_max: BEHIND.
+ *   2. u = (fx Px) / Pz + cx, v = (fy Py) / Pz + cy.  Not (0 <= u <= w - 1 and 0 <= v <= h - 1): OUTSIDE.
+ *   3. The candidates are the keypoints j < min(d_n[img], kp_capacity) with |(double)x_j - u| <= r and |(double)y_j - v| <= r, r = (double)radius_px.
+ *      None: NO_CANDIDATE.
+ *   4. d_j = hamming(descriptor of the landmark, descriptor of j).  The best candidate minimises (d_j, j); second = the smallest d over the other
+ *      candidates.  d_best > tau: TOO_FAR.  ratio_pct > 0, a second candidate exists and 100 d_best > ratio_pct x second: AMBIGUOUS.
+ *   5. Among the landmarks of ONE ITEM that passed 4 with the same keypoint j the one with the smallest (d_best, index inside the item) keeps it:
+ *      MATCHED; the others: CONTESTED.  (Two items on one image do not contest each other.)
+ * OUTPUTS, per landmark: d_match = the keypoint when MATCHED, else -1; d_dist = d_best whenever there was a candidate (TOO_FAR, AMBIGUOUS,
+ * CONTESTED and MATCHED), else -1; d_n_cand (may be NULL) = the candidate count (0 before step 3); d_status = one of the codes below.
+ * INVALID INPUT.  A non-finite point, a descriptor row outside [0, n_src_rows): that landmark is INVALID (-1, -1, 0).  A non-finite pose or an
+ * image outside [0, B): every landmark of the item.  Offsets: with pm = max(0, lm_off[0..m-1]) item m WRITES exactly the landmarks
+ * [max(lm_off[m], pm), min(lm_off[m+1], n_landmarks)) -- ranges that cannot overlap whatever lm_off holds -- and is sound when
+ * pm <= lm_off[m] <= lm_off[m+1] <= n_landmarks; an item that is not writes INVALID there.  Nothing is read or written out of range.
+ * DETERMINISM.  Every reduction is a minimum over integer keys or a count: the same call twice writes the same bytes, and an item's output in a
+ * batch is its output alone.
+ * LIMIT.  One workgroup holds an image's keypoint grid (32 x 32 px cells, img_w, img_h <= 4095: at most 128 x 128), pixel coordinates, cell lists and
+ * claims in LDS: 4 bytes per cell and 18 per keypoint slot, so kp_capacity <= VSLAM_PROJECT_MATCH_MAX_KP.  (vslam_set_tuning "pm_stage" = 1 also
+ * stages the image's descriptors there, 32 bytes per slot more, where two workgroups still fit a CU; the outputs are the same bytes.) */
+#define VSLAM_PROJECT_MATCH_MAX_KP 4096
+#define VSLAM_PM_MATCHED 0
+#define VSLAM_PM_BEHIND 1
+#define VSLAM_PM_OUTSIDE 2
+#define VSLAM_PM_NO_CANDIDATE 3
+#define VSLAM_PM_TOO_FAR 4
+#define VSLAM_PM_AMBIGUOUS 5
+#define VSLAM_PM_CONTESTED 6
+#define VSLAM_PM_INVALID 7
+typedef struct vslam_project_match {
+    int32_t struct_size;            /* sizeof(vslam_project_match): set by the caller, checked */
+    int32_t n_items, n_landmarks;
+    int32_t B, kp_capacity, n_src_rows;
+    const int32_t* d_lm_off;        /* n_items + 1 */
+    const int32_t* d_item_img;      /* n_items */
+    const double* d_item_T;         /* n_items x 7 */
+    const double* d_lm_xyz;         /* n_landmarks x 3 */
+    const int32_t* d_lm_desc_row;   /* n_landmarks */
+    const uint8_t* d_src_desc;      /* n_src_rows x 32, 16-byte aligned */
+    const vslam_keypoint* d_kps;    /* B x kp_capacity */
+    const uint8_t* d_desc;          /* B x desc_stride_bytes, 16-byte aligned */
+    size_t desc_stride_bytes;       /* a multiple of 16, >= kp_capacity x 32; 0 = kp_capacity x 32 */
+    const int32_t* d_n;             /* B */
+    const double* K4;               /* host, 4 doubles, or NULL: the context's camera */
+    int32_t* d_match;               /* n_landmarks, out */
+    int32_t* d_dist;                /* n_landmarks, out */
+    int32_t* d_n_cand;              /* n_landmarks, out, or NULL */
+    uint8_t* d_status;              /* n_landmarks, out */
+} vslam_project_match;
+typedef struct vslam_project_match_params {
+    int32_t struct_size;            /* sizeof(vslam_project_match_params) */
+    float radius_px;                /* > 0, finite */
+    int32_t tau;                    /* 0 .. 255 */
+    int32_t ratio_pct;              /* 0 .. 100; 0 = no ratio test */
+    double z_min, z_max;            /* depth gate, neither NaN */
+} vslam_project_match_params;
+/* radius_px 15, tau 50, ratio_pct 80, z_min 0.1, z_max 1e4 */
+void vslam_project_match_default_params(vslam_project_match_params* p);
+/* One launch for the whole batch, asynchronous on the context stream.  p NULL = the defaults.  Refuses with VSLAM_ERR_ARG and a message before it
+ * launches anything: a null where a pointer is required (the landmark and output arrays only when n_landmarks > 0), n_items or B < 1, n_landmarks
+ * or n_src_rows < 0, a wrong struct_size, radius_px not positive and finite, tau or ratio_pct out of range, a NaN gate, a camera with fx or
+ * fy <= 0 or a non-finite entry, kp_capacity outside [1, VSLAM_PROJECT_MATCH_MAX_KP], d_src_desc or d_desc not 16-byte aligned, a
+ * desc_stride_bytes that is no multiple of 16 or below kp_capacity x 32. */
+int vslam_project_match_dev(vslam_ctx* ctx, const vslam_project_match* in, const vslam_project_match_params* p);
+
 /* ------------------------------------------------------------------ raw device memory helpers ---------- */
 /* For hosts without their own device allocator (the C++ mirror in host/); bench.py passes torch tensors. */
 int vslam_dev_alloc(void** p, size_t bytes);

@@ -156,6 +156,25 @@ FULL_BA_STATS_DTYPE = np.dtype([("chi2_init", "<f8"), ("chi2_final", "<f8"), ("l
 FBA_BAD_INDEX, FBA_NONFINITE, FBA_PCG_CAP, FBA_LAMBDA, FBA_SINGULAR, FBA_DROPPED = 1, 2, 4, 8, 16, 32
 
 
+class ProjectMatchBatch(C.Structure):
+    """vslam_project_match: a batch of match-by-projection items laid back to back (device pointers; K4 a HOST pointer or None); struct_size is filled in
+    by VO.project_match_dev"""
+    _fields_ = [("struct_size", C.c_int32), ("n_items", C.c_int32), ("n_landmarks", C.c_int32), ("B", C.c_int32), ("kp_capacity", C.c_int32),
+                ("n_src_rows", C.c_int32), ("d_lm_off", C.c_void_p), ("d_item_img", C.c_void_p), ("d_item_T", C.c_void_p), ("d_lm_xyz", C.c_void_p),
+                ("d_lm_desc_row", C.c_void_p), ("d_src_desc", C.c_void_p), ("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("desc_stride_bytes", C.c_size_t),
+                ("d_n", C.c_void_p), ("K4", C.POINTER(C.c_double)), ("d_match", C.c_void_p), ("d_dist", C.c_void_p), ("d_n_cand", C.c_void_p),
+                ("d_status", C.c_void_p)]
+
+
+class ProjectMatchParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("radius_px", C.c_float), ("tau", C.c_int32), ("ratio_pct", C.c_int32), ("z_min", C.c_double),
+                ("z_max", C.c_double)]
+
+
+PM_MATCHED, PM_BEHIND, PM_OUTSIDE, PM_NO_CANDIDATE, PM_TOO_FAR, PM_AMBIGUOUS, PM_CONTESTED, PM_INVALID = range(8)
+PROJECT_MATCH_MAX_KP = 4096
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("total_ms", C.c_double), ("launches", C.c_int32), ("calls", C.c_int32)]
 
@@ -269,6 +288,8 @@ SIGNATURES = {
     "vslam_full_ba_default_params": (None, [C.POINTER(FullBAParams)]),
     "vslam_full_ba_dev": (I, [P, C.POINTER(FullBABatch), C.POINTER(FullBAParams), P, P, P]),
     "vslam_full_ba_status_dev": (I, [P, I, P]),
+    "vslam_project_match_default_params": (None, [C.POINTER(ProjectMatchParams)]),
+    "vslam_project_match_dev": (I, [P, C.POINTER(ProjectMatchBatch), C.POINTER(ProjectMatchParams)]),
     "vslam_dev_alloc": (I, [P, Z]), "vslam_dev_free": (I, [P]), "vslam_dev_upload": (I, [P, P, P, Z]), "vslam_dev_download": (I, [P, P, P, Z]),
     "vslam_dev_memset": (I, [P, P, I, Z]),
 }
@@ -413,6 +434,15 @@ def default_full_ba_params(**kw):
     """vslam_full_ba_default_params (max_iters 50, pcg_max_iters 4000, pcg_tol 1e-10, step_tol 1e-9, lambda_init 1e-4), fields overridden by keyword"""
     p = FullBAParams()
     load_library().vslam_full_ba_default_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_project_match_params(**kw):
+    """vslam_project_match_default_params (radius_px 15, tau 50, ratio_pct 80, z_min 0.1, z_max 1e4), fields overridden by keyword"""
+    p = ProjectMatchParams()
+    load_library().vslam_project_match_default_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -966,6 +996,57 @@ class VO:
         self.sync()
         stats = t["stats"].cpu().numpy().view(FULL_BA_STATS_DTYPE)[:G].copy()
         return dict(T=t["T_out"].cpu().numpy(), xyz=t["xyz_out"].cpu().numpy(), stats=stats, obs_chi2=t["chi2"].cpu().numpy())
+
+    # ------------------------------------------------------------ match by projection (re-observed and fused landmarks)
+    def project_match_dev(self, batch, params=None, n_cand=True, fill=None):
+        """vslam_project_match_dev on a ProjectMatchBatch of device pointers (inputs; K4 None = the context's camera, else four numbers).  The outputs are
+        allocated here on the current device, sentinel-free, and returned as torch tensors: dict(match int32, dist int32, status uint8, n_cand int32 or
+        None), n_landmarks each; pointers already set in the batch's output fields are used instead and come back as None.  params a
+        ProjectMatchParams or None for the defaults; fill = a value the allocated outputs hold before the call (what no item writes keeps it).
+        Asynchronous on the context stream.  Semantics in include/vslam_hip.h."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        L = max(int(batch.n_landmarks), 0)
+        out = {}
+        for field, key, dt in (("d_match", "match", torch.int32), ("d_dist", "dist", torch.int32), ("d_status", "status", torch.uint8), ("d_n_cand", "n_cand", torch.int32)):
+            out[key] = None
+            if getattr(batch, field) is None and (key != "n_cand" or n_cand):
+                out[key] = (torch.empty(max(L, 1), dtype=dt, device=dev) if fill is None else torch.full((max(L, 1),), fill, dtype=dt, device=dev))[:L]
+                setattr(batch, field, out[key].data_ptr())
+        batch.struct_size = C.sizeof(ProjectMatchBatch)
+        if any(v is not None for v in out.values()):
+            torch.cuda.current_stream().synchronize()   # (the allocations exist before the context stream writes them)
+        self._chk(self.lib.vslam_project_match_dev(self.h, C.byref(batch), None if params is None else C.byref(params)), "vslam_project_match_dev")
+        return out
+
+    def project_match(self, lm_off, item_img, item_T, lm_xyz, lm_desc_row, src_desc, kps, desc, n, K4=None, params=None, fill=None, **kw):
+        """Match by projection from numpy arrays: lm_off (n_items + 1), item_img (n_items), item_T (n_items, 7), lm_xyz (L, 3), lm_desc_row (L), src_desc
+        (rows, 32) uint8 or None for desc itself, kps (B, kp_capacity) KEYPOINT_DTYPE, desc (B, kp_capacity, 32) uint8, n (B).  params a
+        ProjectMatchParams, or its fields by keyword.  Uploads, runs, downloads: dict(match, dist, n_cand, status) numpy arrays."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE); desc = np.ascontiguousarray(desc, np.uint8)
+        B, cap = kps.shape
+        assert desc.shape == (B, cap, 32)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        pad = lambda t: t if t.numel() else torch.zeros(16, dtype=t.dtype, device=dev)
+        t = dict(off=up(np.asarray(lm_off, np.int32)), img=up(np.asarray(item_img, np.int32)), T=up(np.asarray(item_T, np.float64).reshape(-1, 7)),
+                 xyz=pad(up(np.asarray(lm_xyz, np.float64).reshape(-1, 3))), row=pad(up(np.asarray(lm_desc_row, np.int32))), kps=up(kps.view(np.uint8)), desc=up(desc),
+                 n=up(np.asarray(n, np.int32)))
+        t["src"] = t["desc"] if src_desc is None else pad(up(np.ascontiguousarray(src_desc, np.uint8).reshape(-1, 32)))
+        L = len(np.asarray(lm_desc_row))
+        rows = B * cap if src_desc is None else len(np.asarray(src_desc).reshape(-1, 32))
+        k4 = None if K4 is None else (C.c_double * 4)(*[float(v) for v in K4])
+        batch = ProjectMatchBatch(n_items=len(t["img"]), n_landmarks=L, B=B, kp_capacity=cap, n_src_rows=rows, d_lm_off=t["off"].data_ptr(),
+                                  d_item_img=t["img"].data_ptr(), d_item_T=t["T"].data_ptr(), d_lm_xyz=t["xyz"].data_ptr(), d_lm_desc_row=t["row"].data_ptr(),
+                                  d_src_desc=t["src"].data_ptr(), d_kps=t["kps"].data_ptr(), d_desc=t["desc"].data_ptr(), desc_stride_bytes=0, d_n=t["n"].data_ptr(),
+                                  K4=None if k4 is None else C.cast(k4, C.POINTER(C.c_double)))
+        if params is None and kw:
+            params = default_project_match_params(**kw)
+        torch.cuda.synchronize()   # (the uploads are done before the context stream reads them)
+        out = self.project_match_dev(batch, params, fill=fill)
+        self.sync()
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     def profile_enable(self, on=True):
         self._chk(self.lib.vslam_profile_enable(self.h, on), "vslam_profile_enable")

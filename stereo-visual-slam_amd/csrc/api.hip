@@ -140,6 +140,7 @@ static const TuneKey kTuneKeys[] = {
     {"voxel_form", "VSLAM_VOXEL_FORM", &Tuning::voxel_form, 0, 1},
     {"pg_precond", "VSLAM_PG_PRECOND", &Tuning::pg_precond, 0, 1},
     {"fba_store", "VSLAM_FBA_STORE", &Tuning::fba_store, 0, 1},
+    {"pm_stage", "VSLAM_PM_STAGE", &Tuning::pm_stage, 0, 1},
 };
 static int tune_set(Tuning& t, const TuneKey& k, long v) {
     if (v == -1) { t.*(k.field) = -1; return VSLAM_OK; } // back to the library's rule
@@ -256,7 +257,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
            "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel "
            "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel "
-           "pose_graph_kernel full_ba_kernel";
+           "pose_graph_kernel full_ba_kernel project_match_kernel";
 }
 
 int vslam_create(const vslam_params* p, int device, void* stream, vslam_ctx** out) {
@@ -2081,6 +2082,63 @@ int vslam_full_ba_status_dev(vslam_ctx* ctx, int n_problems, int32_t* h_status) 
     if (n_problems > 0) VS_HIP(hipMemcpyAsync(h_status, c->fullba.p, sizeof(int32_t) * (size_t)n_problems, hipMemcpyDeviceToHost, c->stream));
     VS_HIP(hipStreamSynchronize(c->stream));
     return VSLAM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- match by projection
+void vslam_project_match_default_params(vslam_project_match_params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(vslam_project_match_params);
+    p->radius_px = 15.f; p->tau = 50; p->ratio_pct = 80; p->z_min = 0.1; p->z_max = 1e4;
+}
+
+// (the checks on the structs come before the one on the context: they need no device)
+int vslam_project_match_dev(vslam_ctx* ctx, const vslam_project_match* in, const vslam_project_match_params* params) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    const char* me = "vslam_project_match_dev";
+    if (!in) { set_error("%s: null batch", me); return VSLAM_ERR_ARG; }
+    if (in->struct_size != (int32_t)sizeof(vslam_project_match)) { set_error("%s: vslam_project_match struct_size %d, the library has %d", me, in->struct_size, (int)sizeof(vslam_project_match)); return VSLAM_ERR_ARG; }
+    vslam_project_match_params p;
+    vslam_project_match_default_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(vslam_project_match_params)) { set_error("%s: vslam_project_match_params struct_size %d, the library has %d", me, params->struct_size, (int)sizeof(vslam_project_match_params)); return VSLAM_ERR_ARG; }
+        p = *params;
+    }
+    if (!(p.radius_px > 0.f) || !std::isfinite(p.radius_px)) { set_error("%s: radius_px %g is not positive and finite", me, (double)p.radius_px); return VSLAM_ERR_ARG; }
+    if (p.tau < 0 || p.tau > 255) { set_error("%s: tau %d outside [0, 255]", me, p.tau); return VSLAM_ERR_ARG; }
+    if (p.ratio_pct < 0 || p.ratio_pct > 100) { set_error("%s: ratio_pct %d outside [0, 100]", me, p.ratio_pct); return VSLAM_ERR_ARG; }
+    if (p.z_min != p.z_min || p.z_max != p.z_max) { set_error("%s: a NaN depth gate", me); return VSLAM_ERR_ARG; }
+    if (in->n_items < 1 || in->B < 1 || in->n_landmarks < 0 || in->n_src_rows < 0) {
+        set_error("%s: counts out of range (n_items %d and B %d >= 1, n_landmarks %d and n_src_rows %d >= 0)", me, in->n_items, in->B, in->n_landmarks, in->n_src_rows);
+        return VSLAM_ERR_ARG;
+    }
+    if (in->kp_capacity < 1 || in->kp_capacity > VSLAM_PROJECT_MATCH_MAX_KP) {
+        set_error("%s: kp_capacity %d outside [1, %d] (the keypoint grid, pixels, lists and claims of an image live in LDS)", me, in->kp_capacity, VSLAM_PROJECT_MATCH_MAX_KP);
+        return VSLAM_ERR_ARG;
+    }
+    if (!in->d_lm_off || !in->d_item_img || !in->d_item_T || !in->d_kps || !in->d_desc || !in->d_n) { set_error("%s: null d_lm_off, d_item_img, d_item_T, d_kps, d_desc or d_n", me); return VSLAM_ERR_ARG; }
+    if (in->n_landmarks > 0 && (!in->d_lm_xyz || !in->d_lm_desc_row || !in->d_src_desc || !in->d_match || !in->d_dist || !in->d_status)) {
+        set_error("%s: null d_lm_xyz, d_lm_desc_row, d_src_desc, d_match, d_dist or d_status", me);
+        return VSLAM_ERR_ARG;
+    }
+    if (((uintptr_t)in->d_src_desc & 15) || ((uintptr_t)in->d_desc & 15)) { set_error("%s: d_src_desc and d_desc must be 16-byte aligned", me); return VSLAM_ERR_ARG; }
+    if (in->desc_stride_bytes && ((in->desc_stride_bytes & 15) || in->desc_stride_bytes < (size_t)in->kp_capacity * 32)) {
+        set_error("%s: desc_stride_bytes %zu is no multiple of 16 or below kp_capacity x 32 = %zu", me, in->desc_stride_bytes, (size_t)in->kp_capacity * 32);
+        return VSLAM_ERR_ARG;
+    }
+    if (in->K4) {
+        const double big = 1.7976931348623157e308;
+        if (!(in->K4[0] > 0) || !(in->K4[0] <= big) || !(in->K4[1] > 0) || !(in->K4[1] <= big) || !(fabs(in->K4[2]) <= big) || !(fabs(in->K4[3]) <= big)) {
+            set_error("%s: camera out of range (fx, fy > 0, all finite)", me);
+            return VSLAM_ERR_ARG;
+        }
+    }
+    if (!c) { set_error("%s: null context", me); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    double K[4];
+    if (in->K4) memcpy(K, in->K4, sizeof(K)); else fill_K(c, K);
+    const int stage = c->tune.pm_stage >= 0 ? c->tune.pm_stage : 0;
+    return launch_project_match(*in, p, K, c->p.img_w, c->p.img_h, stage, c->stream);
 }
 
 // float4 streaming copy of `bytes` (src -> dst, both allocated here), `reps` timed launches after one warm-up, hipEvents on the

@@ -281,6 +281,7 @@ struct Tuning {
     int pg_precond = -1;      // VSLAM_PG_PRECOND: preconditioner of pose_graph_kernel's conjugate gradients -- 0 = block-Jacobi, 1 = chain (block-tridiagonal); default: the rule of DESIGN.md 5.10
     int voxel_form = -1;      // VSLAM_VOXEL_FORM: voxel_fuse_kernel -- 0 = every point straight into the global table, 1 = a workgroup sums its image tile in an LDS hash table first (same table either way)
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
+    int pm_stage = -1;        // VSLAM_PM_STAGE: project_match_kernel -- 1 = the target image's descriptors staged in LDS (where two workgroups per CU still fit), 0 = read from L2; default: DESIGN.md 5.12
     int fba_store = -1;       // VSLAM_FBA_STORE: 1 = full_ba_kernel keeps (P, B) of every observation from the linearisation (default), 0 = recomputes them in every conjugate-gradient phase
 };
 // scratch: the context's SGBM buffer.  Its first 256-byte slot is a header of int32 words: the forward sweep's ticket pools, then its error word.
@@ -521,6 +522,13 @@ int launch_pose_graph(const vslam_pose_graph& g, const vslam_pose_graph_params& 
 // (P, B) are kept from the linearisation, 0 = recomputed in every conjugate-gradient phase.
 int launch_full_ba(const vslam_full_ba& b, const vslam_full_ba_params& p, int store, double* d_T_out, double* d_xyz_out, vslam_full_ba_stats* d_stats,
                    DevBuf& buf, hipStream_t stream);
+
+// ----------------------------------------------------------------------------------------------- match by projection
+// projmatch_kernels.hip: one workgroup per item (include/vslam_hip.h "match by projection").  K4 = the call's camera, img_w x img_h the context's image.
+// stage: 1 = the image's descriptors are staged in LDS where that leaves two workgroups per CU, 0 = the candidates read them from L2.
+size_t project_match_lds_bytes(int cap, int gw, int gh, bool stage);
+int launch_project_match(const vslam_project_match& in, const vslam_project_match_params& p, const double K4[4], int img_w, int img_h, int stage,
+                         hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- context
 struct Ctx {

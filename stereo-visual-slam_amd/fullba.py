@@ -41,12 +41,26 @@ class FullBA:
                            landmarks_seen=0, landmarks=0, landmarks_dropped=0, landmarks_without_stereo=0, edges_added=0, edges_not_accepted=0,
                            edges_unknown_seq=0, edges_unknown_frame=0)
 
-    def add_segment(self, first_frame, frame_ids, T_old, obs_frame, obs_lm_id, obs_uv, lm_id, lm_xyz, kp_xyz, kp_valid, T_new=None):
+    def add_segment(self, first_frame, frame_ids, T_old, obs_frame, obs_lm_id, obs_uv, lm_id, lm_xyz, kp_xyz, kp_valid, T_new=None, merge=None):
         """first_frame: the batch frame index of the segment's frame 0; frame_ids (segment-local, as trajectories() returns them) with their poses
         T_old; the windows' observations as (batch frame, landmark id, uv) and their landmarks as (id, world position), duplicates included, in window
         order; kp_xyz (B, cap, 3) / kp_valid (B, cap): the step's camera-frame stereo points per left keypoint; T_new: the initial poses in place of
-        T_old."""
+        T_old.  merge = (ids, canonical), what reobserve() found: landmarks fused into classes.  The creating observation's disparity is computed
+        from the ORIGINAL id, then the ids are remapped to the canonical one, the observations de-duplicated again by (frame, canonical id) -- a stereo
+        row wins over a mono one -- and the class takes the canonical landmark's position: a merged class keeps every member's stereo row.  None
+        leaves every array as it was before the argument existed."""
         rep = self.report
+        canon = None
+        if merge is not None:
+            m_ids, m_can = (np.asarray(a, np.int64).reshape(-1) for a in merge)
+            assert len(m_ids) == len(m_can)
+            mo = np.argsort(m_ids, kind="stable"); m_ids, m_can = m_ids[mo], m_can[mo]
+
+            def canon(a):
+                if not len(m_ids) or not len(a):
+                    return a
+                k = np.minimum(np.searchsorted(m_ids, a), len(m_ids) - 1)
+                return np.where(m_ids[k] == a, m_can[k], a)
         ids = np.asarray(frame_ids, np.int64); order = np.argsort(ids, kind="stable")
         ids = ids[order]; T_old = np.asarray(T_old, np.float64).reshape(-1, 7)[order]
         assert len(np.unique(ids)) == len(ids)
@@ -54,6 +68,10 @@ class FullBA:
         N = len(ids)
         obs_frame = np.asarray(obs_frame, np.int64); obs_lm_id = np.asarray(obs_lm_id, np.int64); obs_uv = np.asarray(obs_uv, np.float32).reshape(-1, 2)
         lm_id = np.asarray(lm_id, np.int64); lm_xyz = np.asarray(lm_xyz, np.float64).reshape(-1, 3)
+        if canon is not None:   # the canonical landmark stands for its class
+            is_canon = canon(lm_id) == lm_id
+            rep["landmarks_merged"] = rep.get("landmarks_merged", 0) + len(np.unique(lm_id[~is_canon]))
+            lm_id, lm_xyz = lm_id[is_canon], lm_xyz[is_canon]
         rep["observations_seen"] += len(obs_frame)
         # landmarks: one per id, at the position the last window left
         uid, last = np.unique(lm_id[::-1], return_index=True)
@@ -77,6 +95,13 @@ class FullBA:
             z = kp_xyz[np.clip(cf, 0, len(kp_xyz) - 1), ck, 2].astype(np.float64)
             ok = creating & (cf >= 0) & (cf < len(kp_xyz)) & (kp_valid[np.clip(cf, 0, len(kp_xyz) - 1), ck] != 0) & (z > 0)
             disp[ok] = (self.bf / z[ok]).astype(np.float32)
+        if canon is not None:   # the ids to canonical, then one observation per (frame, class): the first stereo one, else the first
+            ol = canon(ol)
+            o2 = np.lexsort((np.arange(len(ol)), disp < 0, ol, of))
+            new = np.ones(len(o2), bool); new[1:] = (of[o2][1:] != of[o2][:-1]) | (ol[o2][1:] != ol[o2][:-1])
+            pick = np.sort(o2[new])
+            rep["observations_merged_duplicate"] = rep.get("observations_merged_duplicate", 0) + len(ol) - len(pick)
+            of, ol, ouv, node, disp = of[pick], ol[pick], ouv[pick], node[pick], disp[pick]
         # a landmark left with a single mono observation is not part of the problem
         lidx = np.searchsorted(uid, ol)
         n_obs = np.bincount(lidx, minlength=len(uid)); n_st = np.bincount(lidx[disp >= 0], minlength=len(uid))

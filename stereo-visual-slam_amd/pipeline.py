@@ -818,7 +818,76 @@ class KeyframePipeline:
         torch.cuda.synchronize(self.dev)
         return self.ba_lm_id.cpu().numpy()[:int(self.ba_lm_off.cpu().numpy()[-1])]
 
-    def full_ba(self, edges=None, poses=None, w_loop=(1.0, 1.0), huber_delta=None, params=None, frame_offset=0):
+    def _window_observations(self):
+        """the built windows on the host: (kf_frame, e_frame, e_id, ba_uv, lm_id, lm_xyz, win_of_e, win_of_lm) -- every observation as (batch frame,
+        landmark id, uv) and every landmark as (id, world position), duplicates included, in window order"""
+        kf_frame, _ = self._keyframe_sets()
+        lm_off, e_off = self.ba_lm_off.cpu().numpy().astype(np.int64), self.ba_e_off.cpu().numpy().astype(np.int64)
+        n_lm, n_e = int(lm_off[-1]), int(e_off[-1])
+        ba_kf, ba_lm, ba_uv = self.ba_kf.cpu().numpy()[:n_e], self.ba_lm.cpu().numpy()[:n_e], self.ba_uv.cpu().numpy()[:n_e]
+        lm_id, lm_xyz = self.ba_lm_id.cpu().numpy()[:n_lm].astype(np.int64), self.ba_xyz.cpu().numpy()[:n_lm].astype(np.float64)
+        win_of_e = np.repeat(np.arange(self.B), np.diff(e_off)); win_of_lm = np.repeat(np.arange(self.B), np.diff(lm_off))
+        e_frame = kf_frame[win_of_e, ba_kf].astype(np.int64)
+        e_id = lm_id[lm_off[win_of_e] + ba_lm]
+        return kf_frame, e_frame, e_id, ba_uv, lm_id, lm_xyz, win_of_e, win_of_lm
+
+    def project_matcher(self, radius=15.0, tau=50, ratio_pct=80, z_min=0.1, z_max=1e4):
+        """the callable reobserve() hands its batch to: one vslam_project_match_dev call on the step's resident left keypoints and descriptors (the
+        landmarks' descriptor rows index the same array).  .project_match_batch keeps the last batch, .project_match_result its result, .project_match_ms the call's wall time."""
+        import time
+        from . import ProjectMatchBatch, default_project_match_params, PROJECT_MATCH_MAX_KP
+        assert self.cap <= PROJECT_MATCH_MAX_KP, "kp_capacity %d exceeds vslam_project_match_dev's limit %d" % (self.cap, PROJECT_MATCH_MAX_KP)
+        params = default_project_match_params(radius_px=float(radius), tau=int(tau), ratio_pct=int(ratio_pct), z_min=float(z_min), z_max=float(z_max))
+
+        def matcher(b):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+            t = dict(off=up(b["lm_off"]), img=up(b["item_img"]), T=up(b["item_T"]), xyz=up(b["lm_xyz"]), row=up(b["lm_desc_row"]))
+            batch = ProjectMatchBatch(n_items=len(b["item_img"]), n_landmarks=len(b["lm_desc_row"]), B=self.B, kp_capacity=self.cap, n_src_rows=self.B * self.cap,
+                                      d_lm_off=t["off"].data_ptr(), d_item_img=t["img"].data_ptr(), d_item_T=t["T"].data_ptr(), d_lm_xyz=t["xyz"].data_ptr(),
+                                      d_lm_desc_row=t["row"].data_ptr(), d_src_desc=self.d_desc.data_ptr(), d_kps=self.d_kps.data_ptr(), d_desc=self.d_desc.data_ptr(),
+                                      desc_stride_bytes=self.cap * 32, d_n=self.d_cnt.data_ptr())
+            torch.cuda.synchronize(self.dev)
+            t0 = time.perf_counter()
+            out = self.vo.project_match_dev(batch, params)
+            self.vo.sync()
+            self.project_match_ms = (time.perf_counter() - t0) * 1e3
+            self.project_match_batch = b
+            self.project_match_result = {k: v.cpu().numpy() for k, v in out.items()}
+            return self.project_match_result
+        return matcher
+
+    def reobserve(self, edges=None, neighbours=10, loop_neighbours=2, radius=15.0, tau=50, ratio_pct=80, frame_offset=0, matcher=None):
+        """Match by projection over the last step (include/vslam_hip.h "match by projection"; reobserve.py says how the items are formed and how the
+        matches are applied): the landmarks of the neighbouring keyframes -- and, for the accepted rows of `edges` (what loop_closures() returned, with
+        the same frame_offset), of the other end of the loop -- are projected into each keyframe at its estimated pose and looked for among its
+        keypoints, all items in one device call.  Returns dict(observations (REOBS_DTYPE rows: frame, lm_id, kp, u, v, dist, kind local | loop),
+        merge = (ids, canonical), report); full_ba(reobserved=...) takes it.  matcher: a callable in place of the device call (the yardstick in
+        tests).  The depth gate is the context's depth_min .. depth_max, the one stereo points are created under, and merges pass reobserve.py's
+        merge gate at the search radius.  Needs landmark_ids=True (or
+        ba_chain=True).  Nothing is fed back into the BA windows or into tracking."""
+        if not getattr(self, "landmark_ids", False):
+            raise ValueError("reobserve needs the landmarks' identities: build the pipeline with landmark_ids=True (or ba_chain=True)")
+        from .reobserve import reobserve
+        trajs = self.trajectories()   # (synchronises: the step is complete)
+        first = np.asarray(self.seg_first if self.seg_first is not None else [0, self.B], np.int64)
+        _, e_frame, e_id, ba_uv, lm_id, lm_xyz, win_of_e, win_of_lm = self._window_observations()
+        segs = []
+        for s_, (ids, Ts) in enumerate(trajs):
+            we = (win_of_e >= first[s_]) & (win_of_e < first[s_ + 1]); wl = (win_of_lm >= first[s_]) & (win_of_lm < first[s_ + 1])
+            segs.append((first[s_], ids, Ts, e_frame[we], e_id[we], ba_uv[we], lm_id[wl], lm_xyz[wl]))
+        kps = self.d_kps[:self.B].cpu().numpy().view(np.float32).reshape(self.B, self.cap, 7)[:, :, :2].copy()
+        n = self.d_cnt.cpu().numpy()[:self.B]
+        if matcher is None:
+            # the depth gate is the one that creates landmarks: where no stereo point may be made, none is re-observed either (a landmark passing
+            # beside the camera projects anywhere)
+            matcher = self.project_matcher(radius=radius, tau=tau, ratio_pct=ratio_pct, z_min=self.vo.params.depth_min, z_max=self.vo.params.depth_max)
+        cam = list(self.vo.params.cam)
+        out = reobserve(segs, edges, self.cap, matcher, kps, n, neighbours=neighbours, loop_neighbours=loop_neighbours, frame_offset=frame_offset,
+                        merge_gate=dict(K4=cam[:4], bf=cam[0] * cam[4], radius=radius))
+        self.reobserve_result = out
+        return out
+
+    def full_ba(self, edges=None, poses=None, w_loop=(1.0, 1.0), huber_delta=None, params=None, frame_offset=0, reobserved=None):
         """Full bundle adjustment of the last step (include/vslam_hip.h "full bundle adjustment"): per segment all keyframes of trajectories() and all
         landmarks of the BA windows over all their observations, the accepted rows of `edges` (what loop_closures() returned, with the same
         frame_offset) as pose-pose factors of information w_loop, all segments in one call.  poses: the initial poses in place of trajectories(),
@@ -827,6 +896,8 @@ class KeyframePipeline:
         problem is formed and what is left out; that is counted in .full_ba_result["report"].  Returns what trajectories() returns, refined;
         dense_map(poses=...) takes it.  .full_ba_result keeps report and, per segment, dict(lm_id, xyz (every landmark of the windows at its new
         position, float64: vo.voxel_insert_points_dev takes them as float32), in_problem, problem, xyz_problem, stats, obs_chi2).
+        reobserved: what reobserve() returned -- its observations are appended to the windows' and its merged landmark classes become one landmark
+        each (FullBA.add_segment's merge); the report then counts observations_reobserved, landmarks_merged and observations_merged_duplicate.
         Needs landmark_ids=True (or ba_chain=True).  The result is not fed back into tracking, and frames of other steps are out of reach."""
         if not getattr(self, "landmark_ids", False):
             raise ValueError("full_ba needs the landmarks' identities: build the pipeline with landmark_ids=True (or ba_chain=True)")
@@ -837,14 +908,7 @@ class KeyframePipeline:
         first = np.asarray(self.seg_first if self.seg_first is not None else [0, self.B], np.int64)
         cam = list(self.vo.params.cam)
         fb = FullBA(cam[:4], cam[0] * cam[4], self.cap, w_loop=w_loop, huber_delta=self.vo.params.huber_delta if huber_delta is None else huber_delta)
-        kf_frame, _ = self._keyframe_sets()
-        lm_off, e_off = self.ba_lm_off.cpu().numpy().astype(np.int64), self.ba_e_off.cpu().numpy().astype(np.int64)
-        n_lm, n_e = int(lm_off[-1]), int(e_off[-1])
-        ba_kf, ba_lm, ba_uv = self.ba_kf.cpu().numpy()[:n_e], self.ba_lm.cpu().numpy()[:n_e], self.ba_uv.cpu().numpy()[:n_e]
-        lm_id, lm_xyz = self.ba_lm_id.cpu().numpy()[:n_lm].astype(np.int64), self.ba_xyz.cpu().numpy()[:n_lm].astype(np.float64)
-        win_of_e = np.repeat(np.arange(self.B), np.diff(e_off)); win_of_lm = np.repeat(np.arange(self.B), np.diff(lm_off))
-        e_frame = kf_frame[win_of_e, ba_kf].astype(np.int64)
-        e_id = lm_id[lm_off[win_of_e] + ba_lm]
+        _, e_frame, e_id, ba_uv, lm_id, lm_xyz, win_of_e, win_of_lm = self._window_observations()
         kp_xyz, kp_valid = self._points_per_keypoint()
         self.stream.synchronize()
         kp_xyz, kp_valid = kp_xyz.cpu().numpy(), kp_valid.cpu().numpy()
@@ -855,7 +919,15 @@ class KeyframePipeline:
                 assert np.array_equal(np.asarray(ids_p), np.asarray(ids)), "poses: the frame ids of trajectories(), segment %d" % s_
                 T_new = T_p
             we = (win_of_e >= first[s_]) & (win_of_e < first[s_ + 1]); wl = (win_of_lm >= first[s_]) & (win_of_lm < first[s_ + 1])
-            fb.add_segment(first[s_], ids, Ts, e_frame[we], e_id[we], ba_uv[we], lm_id[wl], lm_xyz[wl], kp_xyz, kp_valid, T_new=T_new)
+            if reobserved is None:
+                fb.add_segment(first[s_], ids, Ts, e_frame[we], e_id[we], ba_uv[we], lm_id[wl], lm_xyz[wl], kp_xyz, kp_valid, T_new=T_new)
+                continue
+            ro = reobserved["observations"]
+            mine = (ro["frame"] >= first[s_]) & (ro["frame"] < first[s_ + 1])
+            fb.report["observations_reobserved"] = fb.report.get("observations_reobserved", 0) + int(mine.sum())
+            fb.add_segment(first[s_], ids, Ts, np.concatenate([e_frame[we], ro["frame"][mine].astype(np.int64)]), np.concatenate([e_id[we], ro["lm_id"][mine]]),
+                           np.concatenate([ba_uv[we].reshape(-1, 2), np.stack([ro["u"][mine], ro["v"][mine]], 1)]), lm_id[wl], lm_xyz[wl], kp_xyz, kp_valid,
+                           T_new=T_new, merge=reobserved["merge"])
         if edges is not None:
             fb.add_loop_edges(edges, frame_offset=frame_offset)
         out = fb.optimize(self.vo, params=params)
