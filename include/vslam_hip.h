@@ -310,7 +310,9 @@ int vslam_triangulate_dev(vslam_ctx* ctx, const float* d_uvL, const float* d_uvR
                           const double* d_T_c_w, float* d_xyz_w, uint8_t* d_valid, uint8_t* d_reliable);
 
 /* Gather matched keypoint coordinates (device glue between matcher and triangulation / PnP):
- * uvQ[b][i] = kpsQ[b][match.queryIdx].pt, uvT[b][i] = kpsT[b][match.trainIdx].pt */
+ * uvQ[b][i] = kpsQ[b][match.queryIdx].pt, uvT[b][i] = kpsT[b][match.trainIdx].pt for i < min(d_nmatch[b], match_capacity); a count
+ * <= 0 writes nothing, and rows at or past the count are left as they were.  An index outside [0, kp_capacity) is CLAMPED to that range (the
+ * row is still written, with the pixel of keypoint 0 or kp_capacity - 1): the caller's tables decide what such a row means. */
 int vslam_gather_matched_uv_dev(vslam_ctx* ctx, const vslam_keypoint* d_kpsQ, const vslam_keypoint* d_kpsT, int kp_capacity,
                                 const vslam_dmatch* d_matches, const int32_t* d_nmatch, int match_capacity, int B,
                                 float* d_uvQ, float* d_uvT);
@@ -832,7 +834,12 @@ int vslam_orb_level(vslam_ctx* ctx, int item, int level, int blurred, uint8_t* o
  * VO::motion_estimation, visual_odometry.cpp:260-270): for every frame-to-frame match (query = previous frame,
  * train = current frame) whose query keypoint owns a valid triangulated point (found through the previous frame's
  * L/R matches d_lr, whose queryIdx is the left keypoint), emit (xyz, current pixel), in match order.
- * d_kp2lr: B x kp_capacity int32 scratch.  Outputs: B x out_capacity. */
+ * d_kp2lr: B x kp_capacity int32 scratch.  Outputs: B x out_capacity.
+ * The rule, as a sequential loop per item: d_kp2lr = -1; for i < min(d_nlr, lr_capacity) in order, an in-range queryIdx q sets d_kp2lr[q] = i, so
+ * of two L/R matches with the same queryIdx the LAST one wins (the largest i, independent of the launch); the frame-to-frame matches
+ * i < min(d_nf2f, match_capacity) are walked in order, one survives when both of its indices are inside [0, kp_capacity), d_kp2lr[queryIdx] >= 0
+ * and d_valid_lr of that L/R match is non-zero (an out-of-range index drops the match; nothing is clamped here); survivor number s is written
+ * only if s < out_capacity and d_nout = min(survivors, out_capacity).  Rows at or past d_nout are left as they were; a count <= 0 gives 0. */
 int vslam_build_pnp_inputs_dev(vslam_ctx* ctx, const vslam_dmatch* d_f2f, const int32_t* d_nf2f, int match_capacity,
                                const vslam_dmatch* d_lr, const int32_t* d_nlr, int lr_capacity, const float* d_xyz_lr,
                                const uint8_t* d_valid_lr, const vslam_keypoint* d_kps_cur, int kp_capacity, int B,

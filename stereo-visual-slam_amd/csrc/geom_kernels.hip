@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void gather_uv_kernel(const vslam_keypoint* __
     reinterpret_cast<float2*>(uvT)[i] = make_float2(t->x, t->y);
 }
 
-// One workgroup per item.  Phase 1: kp2lr[queryIdx of L/R match] = L/R match index (or -1).  Phase 2: walk the
+// One workgroup per item.  Phase 1: kp2lr[queryIdx of L/R match] = the largest L/R match index with that queryIdx (or -1).  Phase 2: walk the
 // frame-to-frame matches in order; a match whose query keypoint has a valid triangulated point contributes
 // (xyz of that point, pixel of the train keypoint).  Ordered compaction via ballot ranks.
 __global__ __launch_bounds__(256) void build_pnp_inputs_kernel(const vslam_dmatch* __restrict__ d_m, const int32_t* __restrict__ d_nm,
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void build_pnp_inputs_kernel(const vslam_dmatc
     const vslam_dmatch* lr = d_lr + (size_t)b * lr_capacity;
     for (int i = tid; i < nlr; i += 256) {
         const int q = lr[i].queryIdx;
-        if (q >= 0 && q < kp_capacity) kp2lr[q] = i;
+        if (q >= 0 && q < kp_capacity) atomicMax(&kp2lr[q], i); // a queryIdx that occurs twice: the later L/R match, whatever the lane order
     }
     __syncthreads();
     // seg_start (vslam_set_segments; null: one sequence): frame b + 1 opens a new sequence, the item carries no pose input whatever d_m holds
