@@ -942,6 +942,86 @@ int vslam_voxel_fuse_disparity_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const fl
 int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int min_count, vslam_voxel* d_out, int32_t* d_map_out, size_t capacity,
                             uint64_t* d_n_out);
 
+/* ------------------------------------------------------------------ surface map: disparities fused into a TSDF, free space carved --- */
+/* The dense map above counts the points that fell into a voxel.  This stage keeps, per voxel, the truncated signed distance to the observed surface
+ * averaged over every view that sees the voxel (a TSDF): views that look THROUGH a voxel vote "free" and carve what a wrong disparity or a passing
+ * car left there, and the surface is the field's zero crossing, read back as one oriented point (surfel) per crossing voxel edge.  Every sum is an
+ * integer and every voxel is written by one lane, so the map is bit-reproducible whatever order frames and blocks arrive in.  The reference has no
+ * such map.  Additive: vslam_params and the ABI version are unchanged; the host mirror (host/) does not call the stage.
+ *
+ * CONSTANTS: vs = (double)(float)voxel_size and inv = 1.0f / (float)voxel_size (the dense map's two numbers), J = trunc_voxels in [1, 8],
+ * tau = (double)J * vs, kq = 1024.0 / tau.  All f64 arithmetic below runs in the written order, no contraction.
+ * BLOCKS: 8 x 8 x 8 voxels; block coordinate per axis = i >> 3 (arithmetic) of the voxel index i in [-2^17, 2^17);
+ *   key = map_id << 45 | (bx + 2^14) << 30 | (by + 2^14) << 15 | (bz + 2^14),  map_id in [0, 1022] (all-ones is the empty slot).
+ * A block is 512 voxels of four uint32 (W, Sq, Wc, I), voxel (ix, iy, iz) at (iz & 7) << 6 | (iy & 7) << 3 | (ix & 7): 8 KiB.  The pool holds
+ * 2^log2_blocks blocks and is its own hash table (slot s owns block s): open addressing, linear probing over at most 128 slots.
+ * ALLOCATION.  A frame b takes part when d_map_id[b] is in 0 .. 1022 and its pose is finite (its seven numbers, the rotation matrix and the inverse
+ * translation formed from them).  Of such a frame every pixel (c, r) with c % step == 0 and r % step == 0: depth = fx * b / (double)d, kept when
+ * z_min < depth < z_max (vslam_reproject_dev's gate: NaN, 0 and negative disparities fail it); for j = -J .. J, Zj = depth + (double)j * vs, skipped
+ * when Zj <= 0; the world point is vslam_reproject_dev's expression with Zj in place of the depth (X = x * Zj, Y = y * Zj, f32 at rest); its voxel
+ * index per axis is the dense map's floorf(p * inv), an axis out of range drops the sample (n_dropped_range); the block that holds it is claimed,
+ * all zero, if no slot holds it yet.  A sample that finds no slot is dropped (n_dropped_full, status bit 0); which blocks are lost then depends on
+ * the arrival order, what the claimed ones hold does not.
+ * INTEGRATION, after the call's allocation is complete: every claimed block whose map id equals d_map_id[b] -- blocks of earlier calls included,
+ * that is what carves them; a block a LATER call claims does not receive this call's frames -- with every voxel (ix, iy, iz) of it, for every frame b
+ * of the call that takes part:
+ *   Xw = ((double)i + 0.5) * vs per axis;  P = R Xw + t with R = the rotation matrix of T_c_w[b] (P[a] = R[3a] X0 + R[3a+1] X1 + R[3a+2] X2 + t[a])
+ *   skip unless P[2] > vs
+ *   u = fx * (P[0] / P[2]) + cx;  v = fy * (P[1] / P[2]) + cy;  c = floor(u + 0.5), r = floor(v + 0.5);  skip unless 0 <= c < w and 0 <= r < h
+ *   z = fx * b / (double)disparity[b][r][c];  skip unless z_min < z < z_max
+ *   sdf = z - P[2];  skip if sdf < -tau   (behind the surface: no information)
+ *   q = (int)rint(fmin(sdf, tau) * kq), in [-1024, 1024]
+ *   W += 1;  Sq += q + 1024;  if (sdf <= tau) { Wc += 1;  I += gray[b][r * pitch + c]; }
+ * `step` thins the allocation only.  The sums are exact while W < 2^20; an extraction that meets a larger W sets status bit 1 and skips the voxel.
+ * EXTRACTION: num(v) = (int64)Sq - 1024 * W, D(v) = (double)num / (double)W; good(v): v lies in a claimed block, max(min_weight, 1) <= W < 2^20 and
+ * Wc >= 1.  For a good voxel a and each axis e, with b = a + e (in whichever block): the edge crosses when b is good and (num_a > 0) != (num_b > 0).
+ *   t = D_a / (D_a - D_b);  position along e = ((double)i_a + 0.5 + t) * vs, the other two axes ((double)i + 0.5) * vs
+ *   gradient: g_e = D_b - D_a;  for each other axis f, g_f = the mean over c in {a, b} (in this order, summed from 0) of (D(c + f) - D(c - f)) / 2
+ *   over those c whose two f-neighbours are good, 0 if there are none;  normal = g / sqrt(gx * gx + gy * gy + gz * gz): it points into free space
+ *   intensity = ((double)I_a + (double)I_b) / ((double)Wc_a + (double)Wc_b);  weight = min(W_a, W_b);  every float is f64 arithmetic cast once.
+ * These are the vertices marching cubes places; triangles are not built. */
+typedef struct vslam_tsdf_map vslam_tsdf_map;
+struct vslam_tsdf_stats {
+    uint64_t n_blocks;          /* claimed blocks                                                     */
+    uint64_t n_samples;         /* allocation samples that found or claimed their block               */
+    uint64_t n_dropped_range;   /* samples dropped for range                                          */
+    uint64_t n_dropped_full;    /* samples dropped because no slot was left                           */
+    uint64_t n_frames_skipped;  /* frames with a map id whose pose was not finite                     */
+    uint64_t n_pairs_visited;   /* (block, frame) pairs of equal map id the integration has looked at */
+    uint64_t n_pairs_kept;      /* ... of which the cull kept                                         */
+    uint32_t status;            /* bit 0: pool full; bit 1: a weight reached 2^20; bit 2: a frame was skipped for its pose */
+    int32_t struct_size;        /* sizeof(struct vslam_tsdf_stats) of the caller's header: set by the caller, checked */
+};
+typedef struct vslam_surfel {   /* one zero-crossing voxel edge (48 bytes) */
+    int32_t ix, iy, iz;         /* the edge's lower voxel a */
+    uint32_t axis;              /* 0, 1, 2: the edge runs from a to a + 1 along x, y, z */
+    uint32_t weight;
+    float x, y, z, nx, ny, nz, intensity;
+} vslam_surfel;
+
+/* An empty map of 2^log2_blocks blocks (log2_blocks in [6, 22]) of voxels of voxel_size (finite, > 0), truncation trunc_voxels in [1, 8].  Its
+ * bytes -- 8 KiB + 12 + 8 * ceil(max_batch / 64) per block, 128 per frame of max_batch -- are counted in vslam_device_bytes while the handle lives.
+ * A map belongs to its context and is destroyed before it.  Synchronous. */
+int vslam_tsdf_create(vslam_ctx* ctx, double voxel_size, int trunc_voxels, int log2_blocks, vslam_tsdf_map** out);
+void vslam_tsdf_destroy(vslam_tsdf_map* tm);
+/* every slot empty, every voxel and counter zero; asynchronous on the context stream */
+int vslam_tsdf_clear(vslam_tsdf_map* tm);
+/* the counters so far (host->struct_size set by the caller); synchronises the context stream */
+int vslam_tsdf_stats(vslam_tsdf_map* tm, struct vslam_tsdf_stats* host);
+/* Allocation and integration of B frames as above (the arguments and refusals of vslam_voxel_fuse_disparity_dev; d_gray NULL: I stays 0).
+ * Two forms, same sums (vslam_set_tuning "tsdf_form"): 0 = every block walks all frames of the call; 1 = a cull kernel writes a frame mask per block
+ * first.  Either skips a (block, frame) pair only when no voxel of the block can pass the rule. */
+int vslam_tsdf_integrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
+                             int w, int h, int B, const double* d_T_c_w, const int32_t* d_map_id, double z_min, double z_max, int step);
+/* The crossing edges of map map_id (-1: every map) into d_out (`capacity` vslam_surfel, 16-byte aligned) and, when given, their map ids into
+ * d_map_out; *d_n_out (uint64, device) = the full count even when it exceeds `capacity`.  The order is unspecified: sort by (map, ix, iy, iz, axis). */
+int vslam_tsdf_extract_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_weight, vslam_surfel* d_out, int32_t* d_map_out, size_t capacity,
+                           uint64_t* d_n_out);
+/* The claimed blocks of map map_id (-1: every map), raw: (map, bx, by, bz) into d_block_out (`capacity` x 4 int32) and the block's 512 x 4 uint32 into
+ * d_voxels_out (both 16-byte aligned); *d_n_out as above.  For tests and tools. */
+int vslam_tsdf_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int32_t* d_block_out, uint32_t* d_voxels_out, size_t capacity,
+                          uint64_t* d_n_out);
+
 /* ------------------------------------------------------------------ place database: loop-closure candidates and verified edges --- */
 /* Noticing that the camera is back at a place it has seen: keyframe descriptor blocks are kept in a database that outlives the steps (loops close
  * over thousands of frames, a batch holds max_batch), every query entry is scored against every earlier entry of its sequence by brute force over the

@@ -102,6 +102,21 @@ VOXEL_MAP_DTYPE = np.dtype([("map", "<i4")] + VOXEL_DTYPE.descr)
 VOXEL_MAX_MAP = 1022
 
 
+class TsdfStats(C.Structure):
+    """struct vslam_tsdf_stats: the counters of a surface map (status bit 0: pool full, bit 1: a weight reached 2^20, bit 2: a frame skipped for its pose)"""
+    _fields_ = [("n_blocks", C.c_uint64), ("n_samples", C.c_uint64), ("n_dropped_range", C.c_uint64), ("n_dropped_full", C.c_uint64),
+                ("n_frames_skipped", C.c_uint64), ("n_pairs_visited", C.c_uint64), ("n_pairs_kept", C.c_uint64), ("status", C.c_uint32), ("struct_size", C.c_int32)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_[:8]}
+
+
+# vslam_surfel (48 bytes) and the form TsdfMap.extract() returns it in: the map id in front, sorted by (map, ix, iy, iz, axis)
+SURFEL_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("axis", "<u4"), ("weight", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
+                         ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("intensity", "<f4")])
+SURFEL_MAP_DTYPE = np.dtype([("map", "<i4")] + SURFEL_DTYPE.descr)
+
+
 class PlaceStats(C.Structure):
     """struct vslam_place_stats: entries held, capacity, rows per entry, geometry flag and the adds refused for lack of room"""
     _fields_ = [("n_entries", C.c_int32), ("capacity", C.c_int32), ("rows_per_entry", C.c_int32), ("with_geometry", C.c_int32),
@@ -274,6 +289,11 @@ SIGNATURES = {
     "vslam_voxel_insert_points_dev": (I, [P, P, P, P, P, Z, I]),
     "vslam_voxel_fuse_disparity_dev": (I, [P, P, P, P, Z, I, I, I, I, P, P, D, D, I]),
     "vslam_voxel_extract_dev": (I, [P, P, I, I, P, P, Z, P]),
+    "vslam_tsdf_create": (I, [P, D, I, I, C.POINTER(C.c_void_p)]), "vslam_tsdf_destroy": (None, [P]), "vslam_tsdf_clear": (I, [P]),
+    "vslam_tsdf_stats": (I, [P, C.POINTER(TsdfStats)]),
+    "vslam_tsdf_integrate_dev": (I, [P, P, P, P, Z, I, I, I, I, P, P, D, D, I]),
+    "vslam_tsdf_extract_dev": (I, [P, P, I, I, P, P, Z, P]),
+    "vslam_tsdf_blocks_dev": (I, [P, P, I, P, P, Z, P]),
     "vslam_place_create": (I, [P, I, I, I, C.POINTER(C.c_void_p)]), "vslam_place_destroy": (None, [P]), "vslam_place_clear": (I, [P]),
     "vslam_place_stats": (I, [P, C.POINTER(PlaceStats)]),
     "vslam_place_read_entry": (I, [P, I, P, P, P, P, P, P]),
@@ -474,7 +494,7 @@ class VO:
 
     def close(self):
         if getattr(self, "h", None):
-            for vm in list(getattr(self, "_voxel_maps", ())) + list(getattr(self, "_place_dbs", ())):   # (they belong to the context and go first)
+            for vm in list(getattr(self, "_voxel_maps", ())) + list(getattr(self, "_tsdf_maps", ())) + list(getattr(self, "_place_dbs", ())):   # (they belong to the context and go first)
                 vm.close()
             self.lib.vslam_destroy(self.h)
             self.h = None
@@ -863,6 +883,16 @@ class VO:
         self._chk(self.lib.vslam_voxel_fuse_disparity_dev(self.h, vm.h, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step),
                   "vslam_voxel_fuse_disparity_dev")
 
+    # ------------------------------------------------------------ surface map: disparities fused into a TSDF (no counterpart in the reference)
+    def tsdf_map(self, voxel_size=0.2, trunc_voxels=4, log2_blocks=16):
+        """an empty TsdfMap of this context: 2^log2_blocks blocks of 8 x 8 x 8 voxels of voxel_size metres (8 KiB each), truncation trunc_voxels voxels"""
+        return TsdfMap(self, voxel_size, trunc_voxels, log2_blocks)
+
+    def tsdf_integrate_dev(self, tm, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step=1):
+        """allocation and integration of B frames into the TsdfMap tm: item b into map d_map_id[b] (< 0: skipped), intensity from d_gray (None: 0)"""
+        self._chk(self.lib.vslam_tsdf_integrate_dev(self.h, tm.h, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step),
+                  "vslam_tsdf_integrate_dev")
+
     def voxel_extract_dev(self, vm, map_id, min_count, d_out, d_map_out, capacity, d_n_out):
         """the occupied voxels with count >= min_count of map map_id (-1: all) into d_out (capacity x 32 bytes) / d_map_out; d_n_out (uint64): the full count"""
         self._chk(self.lib.vslam_voxel_extract_dev(self.h, vm.h, map_id, min_count, d_out, d_map_out, capacity, d_n_out), "vslam_voxel_extract_dev")
@@ -1161,6 +1191,91 @@ class VoxelMap:
         for f in VOXEL_DTYPE.names:
             out[f] = v[f]
         return out[np.lexsort((out["iz"], out["iy"], out["ix"], out["map"]))] if sort else out
+
+
+class TsdfMap:
+    """A truncated signed distance field over 8 x 8 x 8 voxel blocks in a device pool (include/vslam_hip.h "surface map"): per voxel the integer sums
+    of the quantised distance to the surface, of the views that saw it and of their intensities.  Views that look through a voxel carve it.  Filled
+    through integrate_dev (or KeyframePipeline.surface_map); extract() reads the surface as surfels; belongs to the VO it was created on."""
+
+    def __init__(self, vo, voxel_size=0.2, trunc_voxels=4, log2_blocks=16):
+        self.vo, self.voxel_size, self.trunc_voxels, self.log2_blocks = vo, float(voxel_size), int(trunc_voxels), int(log2_blocks)
+        h = C.c_void_p()
+        vo._chk(vo.lib.vslam_tsdf_create(vo.h, voxel_size, trunc_voxels, log2_blocks, C.byref(h)), "vslam_tsdf_create")
+        self.h = h
+        if not hasattr(vo, "_tsdf_maps"):
+            vo._tsdf_maps = []
+        vo._tsdf_maps.append(self)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.vo.lib.vslam_tsdf_destroy(self.h)
+            self.h = None
+            self.vo._tsdf_maps.remove(self)
+
+    def clear(self):
+        """every block released, zero counters; asynchronous on the context stream"""
+        self.vo._chk(self.vo.lib.vslam_tsdf_clear(self.h), "vslam_tsdf_clear")
+
+    def stats(self):
+        """{n_blocks, n_samples, n_dropped_range, n_dropped_full, n_frames_skipped, n_pairs_visited, n_pairs_kept, status}; synchronises"""
+        st = TsdfStats(); st.struct_size = C.sizeof(TsdfStats)
+        self.vo._chk(self.vo.lib.vslam_tsdf_stats(self.h, C.byref(st)), "vslam_tsdf_stats")
+        return st.as_dict()
+
+    def integrate_dev(self, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step=1):
+        """VO.tsdf_integrate_dev into this map"""
+        self.vo.tsdf_integrate_dev(self, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step)
+
+    def _buffers(self, capacity, row_bytes):
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_out = torch.zeros((capacity, row_bytes), dtype=torch.uint8, device=dev)
+        d_n = torch.zeros(1, dtype=torch.int64, device=dev)
+        return dev, d_out, d_n
+
+    def extract(self, map_id=-1, min_weight=1, capacity=None, sort=True):
+        """the zero-crossing voxel edges of map map_id (-1: every map) between voxels of weight >= min_weight, as a SURFEL_MAP_DTYPE array sorted
+        by (map, ix, iy, iz, axis) -- the canonical form for comparisons.  capacity: rows of the device buffer (None: counted by a first pass);
+        the call returns at most that many (self.last_count holds the full count)."""
+        import torch
+        vo = self.vo
+        if capacity is None:
+            dev, d_out, d_n = self._buffers(1, 48)
+            torch.cuda.synchronize(dev)
+            vo._chk(vo.lib.vslam_tsdf_extract_dev(vo.h, self.h, map_id, min_weight, None, None, 0, d_n.data_ptr()), "vslam_tsdf_extract_dev")
+            vo.sync()
+            capacity = max(int(d_n.cpu()[0]), 1)
+        dev, d_out, d_n = self._buffers(capacity, 48)
+        d_map = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
+        vo._chk(vo.lib.vslam_tsdf_extract_dev(vo.h, self.h, map_id, min_weight, d_out.data_ptr(), d_map.data_ptr(), capacity, d_n.data_ptr()), "vslam_tsdf_extract_dev")
+        vo.sync()
+        self.last_count = int(d_n.cpu()[0])
+        n = min(self.last_count, capacity)
+        v = d_out[:n].cpu().numpy().reshape(-1).view(SURFEL_DTYPE)
+        out = np.zeros(n, SURFEL_MAP_DTYPE)
+        out["map"] = d_map[:n].cpu().numpy()
+        for f in SURFEL_DTYPE.names:
+            out[f] = v[f]
+        return out[np.lexsort((out["axis"], out["iz"], out["iy"], out["ix"], out["map"]))] if sort else out
+
+    def blocks(self, map_id=-1):
+        """the claimed blocks of map map_id (-1: every map), raw: (ids (n, 4) int32 of (map, bx, by, bz), voxels (n, 512, 4) uint32 of (W, Sq, Wc, I)
+        with voxel (ix, iy, iz) at (iz & 7) << 6 | (iy & 7) << 3 | (ix & 7)), sorted by (map, bx, by, bz)"""
+        import torch
+        vo = self.vo
+        capacity = max(self.stats()["n_blocks"], 1)
+        dev, d_vox, d_n = self._buffers(capacity, 8192)
+        d_ids = torch.zeros((capacity, 4), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        vo._chk(vo.lib.vslam_tsdf_blocks_dev(vo.h, self.h, map_id, d_ids.data_ptr(), d_vox.data_ptr(), capacity, d_n.data_ptr()), "vslam_tsdf_blocks_dev")
+        vo.sync()
+        n = min(int(d_n.cpu()[0]), capacity)
+        ids = d_ids[:n].cpu().numpy()
+        vox = d_vox[:n].cpu().numpy().view(np.uint32).reshape(n, 512, 4)
+        order = np.lexsort((ids[:, 3], ids[:, 2], ids[:, 1], ids[:, 0]))
+        return ids[order], vox[order]
 
 
 class PlaceDB:

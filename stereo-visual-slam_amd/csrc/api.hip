@@ -138,6 +138,7 @@ static const TuneKey kTuneKeys[] = {
     {"track_rule", "VSLAM_TRACK_RULE", &Tuning::track_rule, 0, 1},
     {"rectify_form", "VSLAM_RECTIFY_FORM", &Tuning::rectify_form, 0, 1},
     {"voxel_form", "VSLAM_VOXEL_FORM", &Tuning::voxel_form, 0, 1},
+    {"tsdf_form", "VSLAM_TSDF_FORM", &Tuning::tsdf_form, 0, 1},
     {"pg_precond", "VSLAM_PG_PRECOND", &Tuning::pg_precond, 0, 1},
     {"fba_store", "VSLAM_FBA_STORE", &Tuning::fba_store, 0, 1},
     {"pm_stage", "VSLAM_PM_STAGE", &Tuning::pm_stage, 0, 1},
@@ -256,6 +257,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
            "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
            "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel "
+           "tsdf_clear_kernel tsdf_frames_kernel tsdf_alloc_kernel tsdf_cull_kernel tsdf_integrate_kernel tsdf_extract_kernel tsdf_blocks_kernel "
            "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel "
            "pose_graph_kernel full_ba_kernel project_match_kernel";
 }
@@ -1778,6 +1780,118 @@ int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int
     if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_voxel_extract_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     return launch_voxel_extract(m->t, map_id, min_count, d_out, d_map_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
+}
+
+// ---------------------------------------------------------------------------------------------- surface map
+// Form of the integration: 0 = every block walks all frames of the call, 1 = tsdf_cull_kernel writes a frame mask per block first;
+// Tuning::tsdf_form overrides it (tests and tools/bench_tsdf.py run both)
+constexpr int kTsdfFormDefault = 1;
+static int tsdf_form(const Ctx* c) { return c->tune.tsdf_form >= 0 ? c->tune.tsdf_form : kTsdfFormDefault; }
+
+int vslam_tsdf_create(vslam_ctx* ctx, double voxel_size, int trunc_voxels, int log2_blocks, vslam_tsdf_map** out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    if (!c || !out) { set_error("vslam_tsdf_create: null argument"); return VSLAM_ERR_ARG; }
+    *out = nullptr;
+    const float vs = (float)voxel_size;
+    if (!std::isfinite(voxel_size) || !(voxel_size > 0) || !std::isfinite(vs) || !(vs > 0.f) || !std::isfinite(1.0f / vs)) {
+        set_error("vslam_tsdf_create: voxel_size %g is not a finite positive float", voxel_size); return VSLAM_ERR_ARG;
+    }
+    if (trunc_voxels < 1 || trunc_voxels > 8) { set_error("vslam_tsdf_create: trunc_voxels %d outside [1, 8]", trunc_voxels); return VSLAM_ERR_ARG; }
+    if (log2_blocks < 6 || log2_blocks > 22) { set_error("vslam_tsdf_create: log2_blocks %d outside [6, 22]", log2_blocks); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    TsdfMap* m = new TsdfMap();
+    TsdfTable& t = m->t;
+    const size_t n = (size_t)1 << log2_blocks, words = ((size_t)c->p.max_batch + 63) / 64;
+    // one allocation: pool | keys | frame masks | frame table | counters | list (every part a multiple of 8 bytes, the pool 16-byte aligned)
+    const size_t pool_b = n * 8192, keys_b = n * 8, pairs_b = n * words * 8, frames_b = (size_t)c->p.max_batch * kTsdfFrameDoubles * 8, cnt_b = 8 * kTsdfCounters;
+    m->ctx = c; m->bytes = pool_b + keys_b + pairs_b + frames_b + cnt_b + n * 4;
+    t.log2_blocks = log2_blocks; t.J = trunc_voxels; t.frame_words = (int)words; t.vs = vs; t.inv = 1.0f / vs;
+    if (hipMalloc(&m->base, m->bytes) != hipSuccess) { set_error("vslam_tsdf_create: hipMalloc(%zu) failed", m->bytes); delete m; return VSLAM_ERR_HIP; }
+    uint8_t* p = reinterpret_cast<uint8_t*>(m->base);
+    t.pool = reinterpret_cast<uint4*>(p); p += pool_b;
+    t.keys = reinterpret_cast<unsigned long long*>(p); p += keys_b;
+    t.pairs = reinterpret_cast<unsigned long long*>(p); p += pairs_b;
+    t.frames = reinterpret_cast<double*>(p); p += frames_b;
+    t.counters = reinterpret_cast<unsigned long long*>(p); p += cnt_b;
+    t.list = reinterpret_cast<uint32_t*>(p);
+    c->dev_bytes += m->bytes;
+    int rc = launch_tsdf_clear(t, c->stream);
+    if (rc == VSLAM_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("vslam_tsdf_create: clearing the pool failed"); rc = VSLAM_ERR_HIP; }
+    if (rc) { vslam_tsdf_destroy(reinterpret_cast<vslam_tsdf_map*>(m)); return rc; }
+    *out = reinterpret_cast<vslam_tsdf_map*>(m);
+    return VSLAM_OK;
+}
+
+void vslam_tsdf_destroy(vslam_tsdf_map* tm) {
+    TsdfMap* m = reinterpret_cast<TsdfMap*>(tm);
+    if (!m) return;
+    hipSetDevice(m->ctx->device);
+    hipStreamSynchronize(m->ctx->stream);
+    hipFree(m->base);
+    m->ctx->dev_bytes -= m->bytes;
+    delete m;
+}
+
+int vslam_tsdf_clear(vslam_tsdf_map* tm) {
+    TsdfMap* m = reinterpret_cast<TsdfMap*>(tm);
+    if (!m) { set_error("vslam_tsdf_clear: null map"); return VSLAM_ERR_ARG; }
+    VS_ENTER(m->ctx);
+    return launch_tsdf_clear(m->t, m->ctx->stream);
+}
+
+int vslam_tsdf_stats(vslam_tsdf_map* tm, struct vslam_tsdf_stats* host) {
+    TsdfMap* m = reinterpret_cast<TsdfMap*>(tm);
+    if (!m || !host || host->struct_size != (int32_t)sizeof(struct vslam_tsdf_stats)) { set_error("vslam_tsdf_stats: null argument or struct_size mismatch"); return VSLAM_ERR_ARG; }
+    VS_ENTER(m->ctx);
+    unsigned long long w[kTsdfCounters];
+    VS_HIP(hipMemcpyAsync(w, m->t.counters, sizeof(w), hipMemcpyDeviceToHost, m->ctx->stream));
+    VS_HIP(hipStreamSynchronize(m->ctx->stream));
+    host->n_blocks = w[0]; host->n_samples = w[1]; host->n_dropped_range = w[2]; host->n_dropped_full = w[3]; host->status = (uint32_t)w[4];
+    host->n_frames_skipped = w[5]; host->n_pairs_visited = w[6]; host->n_pairs_kept = w[7];
+    return VSLAM_OK;
+}
+
+static TsdfMap* tsdf_map_of(const Ctx* c, vslam_tsdf_map* tm, const char* who) {
+    TsdfMap* m = reinterpret_cast<TsdfMap*>(tm);
+    if (!c || !m || m->ctx != c) { set_error("%s: null context or map, or a map of another context", who); return nullptr; }
+    return m;
+}
+
+int vslam_tsdf_integrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
+                             int w, int h, int B, const double* d_T_c_w, const int32_t* d_map_id, double z_min, double z_max, int step) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_integrate_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!d_map_id) { set_error("vslam_tsdf_integrate_dev: null d_map_id"); return VSLAM_ERR_ARG; }
+    VoxelImages a;
+    if (int rc = voxel_images(c, "vslam_tsdf_integrate_dev", d_disparity, w, h, B, d_T_c_w, z_min, z_max, step, a)) return rc;
+    if (d_gray && (pitch < w || img_bytes < (size_t)pitch * h)) {
+        set_error("vslam_tsdf_integrate_dev: pitch %d / img_bytes %zu do not hold a %d x %d image", pitch, img_bytes, w, h); return VSLAM_ERR_ARG;
+    }
+    VS_ENTER(c);
+    return launch_tsdf_integrate(m->t, a, d_gray, img_bytes, pitch, d_map_id, tsdf_form(c), c->stream);
+}
+
+int vslam_tsdf_extract_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_weight, vslam_surfel* d_out, int32_t* d_map_out, size_t capacity,
+                           uint64_t* d_n_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_extract_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!d_n_out || (capacity > 0 && !d_out)) { set_error("vslam_tsdf_extract_dev: null d_n_out, or null d_out with a capacity"); return VSLAM_ERR_ARG; }
+    if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_tsdf_extract_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_tsdf_extract(m->t, map_id, min_weight, d_out, d_map_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
+}
+
+int vslam_tsdf_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int32_t* d_block_out, uint32_t* d_voxels_out, size_t capacity,
+                          uint64_t* d_n_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_blocks_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!d_n_out || (capacity > 0 && (!d_block_out || !d_voxels_out))) { set_error("vslam_tsdf_blocks_dev: null d_n_out, or a null output with a capacity"); return VSLAM_ERR_ARG; }
+    if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_tsdf_blocks_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    return launch_tsdf_blocks(m->t, map_id, d_block_out, d_voxels_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
 }
 
 // ---------------------------------------------------------------------------------------------- place database

@@ -280,6 +280,7 @@ struct Tuning {
     int rectify_form = -1;    // VSLAM_RECTIFY_FORM: source side of rectify_kernel -- 0 = direct byte gathers, 1 = each tile's source box staged in LDS (default 1; tiles whose box does not pay gather either way)
     int pg_precond = -1;      // VSLAM_PG_PRECOND: preconditioner of pose_graph_kernel's conjugate gradients -- 0 = block-Jacobi, 1 = chain (block-tridiagonal); default: the rule of DESIGN.md 5.10
     int voxel_form = -1;      // VSLAM_VOXEL_FORM: voxel_fuse_kernel -- 0 = every point straight into the global table, 1 = a workgroup sums its image tile in an LDS hash table first (same table either way)
+    int tsdf_form = -1;       // VSLAM_TSDF_FORM: tsdf_integrate_kernel -- 0 = every block walks all frames of the call, 1 = tsdf_cull_kernel writes a frame mask per block first (same sums either way); default: DESIGN.md 5.13
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
     int pm_stage = -1;        // VSLAM_PM_STAGE: project_match_kernel -- 1 = the target image's descriptors staged in LDS (where two workgroups per CU still fit), 0 = read from L2; default: DESIGN.md 5.12
     int fba_store = -1;       // VSLAM_FBA_STORE: 1 = full_ba_kernel keeps (P, B) of every observation from the linearisation (default), 0 = recomputes them in every conjugate-gradient phase
@@ -491,6 +492,24 @@ int launch_voxel_fuse(const VoxelTable& t, const VoxelImages& a, const uint8_t* 
                       hipStream_t stream);
 int launch_voxel_extract(const VoxelTable& t, int map_id, int min_count, vslam_voxel* d_out, int32_t* d_map_out, size_t capacity, unsigned long long* d_n_out,
                          hipStream_t stream);
+
+// ----------------------------------------------------------------------------------------------- surface map
+// tsdf_kernels.hip: disparity maps fused into a truncated signed distance field over 8 x 8 x 8 voxel blocks (include/vslam_hip.h "surface map").
+// The hash slot IS the storage: slot s of `keys` owns block s of `pool` (512 voxels of W, Sq, Wc, I as one uint4 each; voxel (x, y, z) of a block
+// at (z & 7) << 6 | (y & 7) << 3 | (x & 7)).  `list` holds the claimed slots in the order they were claimed, counters[0] of them.
+constexpr int kTsdfCounters = 8;         // uint64 words: blocks, samples, dropped for range, dropped full, status, frames skipped, pairs visited, pairs kept
+constexpr int kTsdfFrameDoubles = 16;    // a frame of the frame table: R (9), t (3), the inverse pose's translation (3), the map id (-1: takes no part)
+struct TsdfTable { unsigned long long* keys; uint32_t* list; uint4* pool; unsigned long long* counters; double* frames; unsigned long long* pairs;
+                   int log2_blocks, J, frame_words; float vs, inv; };
+struct TsdfMap { Ctx* ctx; TsdfTable t; size_t bytes; void* base; };
+int launch_tsdf_clear(const TsdfTable& t, hipStream_t stream);
+// form: 0 = every block walks all frames, 1 = a cull kernel writes a frame mask per block first
+int launch_tsdf_integrate(const TsdfTable& t, const VoxelImages& a, const uint8_t* d_gray, size_t img_bytes, int pitch, const int32_t* d_map_id, int form,
+                          hipStream_t stream);
+int launch_tsdf_extract(const TsdfTable& t, int map_id, int min_weight, vslam_surfel* d_out, int32_t* d_map_out, size_t capacity, unsigned long long* d_n_out,
+                        hipStream_t stream);
+int launch_tsdf_blocks(const TsdfTable& t, int map_id, int32_t* d_block_out, uint32_t* d_voxels_out, size_t capacity, unsigned long long* d_n_out,
+                       hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- place database
 // place_kernels.hip: keyframe descriptor blocks kept across steps and the place score between them (include/vslam_hip.h "place database").

@@ -697,6 +697,31 @@ class KeyframePipeline:
                                          self.dense_T.data_ptr(), self.dense_map_id.data_ptr(), z_min, z_max, int(step))
         return vm
 
+    def surface_map(self, voxel_size=0.2, trunc_voxels=4, log2_blocks=16, z_min=None, z_max=None, step=1, tsdf_map=None, poses=None):
+        """The surface map of the last step (depth="sgbm", ba_windows="tracks"): what dense_map() fuses -- the SGBM disparity and the left image of every
+        frame of dense_map_inputs(poses), same default gates depth_min .. depth_reliable -- integrated into a TsdfMap (vslam_tsdf_integrate_dev), map
+        id = the segment index.  step thins the allocation only.  tsdf_map: a TsdfMap of this pipeline's context to accumulate into over several
+        steps (a step's frames also carve the blocks earlier steps claimed; voxel_size / trunc_voxels / log2_blocks then go unused); otherwise a new
+        one.  poses: what close_loops() or full_ba() returned, in place of the BA poses.
+        Returns the map: .extract() reads the surfels, write_surfel_ply(path, tm.extract()) writes them."""
+        assert self.depth == "sgbm", "surface_map needs depth='sgbm': it fuses the SGBM disparity maps"
+        assert self.with_ba and self.ba_windows == "tracks", "surface_map needs ba_windows='tracks': the poses are the BA windows'"
+        if poses is not None:
+            self.vo.sync()
+            torch.cuda.synchronize(self.dev)
+        T, map_id = self.dense_map_inputs() if poses is None else self.dense_map_inputs(poses)   # (synchronises: the step is complete)
+        p = self.vo.params
+        z_min = p.depth_min if z_min is None else float(z_min)
+        z_max = p.depth_reliable if z_max is None else float(z_max)
+        tm = tsdf_map if tsdf_map is not None else self.vo.tsdf_map(voxel_size, trunc_voxels, log2_blocks)
+        assert tm.vo is self.vo, "tsdf_map belongs to another context"
+        with torch.cuda.stream(self.stream):
+            self.dense_T = torch.from_numpy(T).to(self.dev)
+            self.dense_map_id = torch.from_numpy(map_id).to(self.dev)
+        tm.integrate_dev(self.d_disp.data_ptr(), self.d_imgs.data_ptr(), self.img_bytes, self.pitch, self.w, self.h, self.B,
+                         self.dense_T.data_ptr(), self.dense_map_id.data_ptr(), z_min, z_max, int(step))
+        return tm
+
     # ------------------------------------------------------------------ loop closure (nothing here runs unless loop_closures is called)
     def show_sequence(self, sequence):
         """lay another rendered sequence of the same length over the batch (an unsegmented pipeline without a rig): the next step() sees its frames.
