@@ -979,7 +979,21 @@ int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int
  *   gradient: g_e = D_b - D_a;  for each other axis f, g_f = the mean over c in {a, b} (in this order, summed from 0) of (D(c + f) - D(c - f)) / 2
  *   over those c whose two f-neighbours are good, 0 if there are none;  normal = g / sqrt(gx * gx + gy * gy + gz * gz): it points into free space
  *   intensity = ((double)I_a + (double)I_b) / ((double)Wc_a + (double)Wc_b);  weight = min(W_a, W_b);  every float is f64 arithmetic cast once.
- * These are the vertices marching cubes places; triangles are not built. */
+ * These are the vertices marching cubes places; vslam_tsdf_mesh_dev connects them:
+ * MESH.  The cell of voxel c = (ix, iy, iz) has the corners c + (dx, dy, dz), numbered dx + 2 dy + 4 dz.  It is meshable when all eight corners are good
+ * (the predicate above, with the call's min_weight); cube = the sum of 2^corner over the corners with num > 0.  A cell that is not meshable emits nothing.
+ *   Cube edge k = 4 e + p + 2 q (e the axis, f = (e + 1) % 3, g = (e + 2) % 3) runs from corner p f^ + q g^ along e^.  It crosses when its two corners
+ *   differ in sign; its vertex is then EXTRACTION's surfel (c + p f^ + q g^, axis e): no new arithmetic.
+ *   Segments: on each of the six faces 0, 2 or 4 edges cross.  Two: one segment joins them.  Four (two positive corners on a diagonal): two segments,
+ *   each joining the two face edges that meet at one positive corner -- the positive corners are cut apart, the negative ones stay joined.  A segment
+ *   A -> B is directed so that n . ((m_B - m_A) x (P - m_A)) > 0, n the face's outward normal, m the edge midpoints, P a positive corner of the face on
+ *   the segment's side (with two crossings any positive corner of the face, with four the one it cuts off).  The rule reads the face's own four signs
+ *   only, so the two cells that share a face draw the same segments and the mesh has no cracks.
+ *   Loops: every crossing edge now has one successor, so the crossing edges fall into loops.  A loop is rotated to start at its lowest-numbered member
+ *   from which no fan diagonal joins two edges of one cube face (a triangle flat in a face would coincide with a neighbour's); loops are ordered by
+ *   their smallest member; each is fanned (l0, l_i, l_i+1).  Triangles are counter-clockwise seen from free space: (v1 - v0) x (v2 - v0) points towards
+ *   growing D, as the surfel normals do.  Degenerate triangles (a vertex at t = 0 or 1) are kept.  256 rows, at most 5 triangles each, 820 in all;
+ *   row 1 is (0, 8, 4), row 254 is (0, 4, 8).  tools/gen_mc_table.py derives the table (csrc/mc_table.inc) from this paragraph. */
 typedef struct vslam_tsdf_map vslam_tsdf_map;
 struct vslam_tsdf_stats {
     uint64_t n_blocks;          /* claimed blocks                                                     */
@@ -1021,6 +1035,21 @@ int vslam_tsdf_extract_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int m
  * d_voxels_out (both 16-byte aligned); *d_n_out as above.  For tests and tools. */
 int vslam_tsdf_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int32_t* d_block_out, uint32_t* d_voxels_out, size_t capacity,
                           uint64_t* d_n_out);
+/* The mesh of map map_id (-1: every map) by the MESH rule.  The vertices are exactly the surfels vslam_tsdf_extract_dev returns for the same arguments
+ * (same set, same bytes, order unspecified) into d_vertices (`vertex_capacity` vslam_surfel, 16-byte aligned) and, when given, their map ids into
+ * d_vertex_map; the triangles into d_triangles (`triangle_capacity` x 3 int32 indices into this call's vertex array).  d_counts (two uint64, device) =
+ * the full vertex and triangle counts even when they exceed the capacities; nothing is stored at or beyond a capacity; NULL buffers with capacity 0
+ * make a counting call.  Triangle indices are meaningful when counts[0] <= vertex_capacity.  The first call on a map grows the map's vertex-id table
+ * -- (1536 * claimed blocks + 2^log2_blocks) * 4 bytes, counted in vslam_device_bytes -- for which the call reads the block count (one synchronise of
+ * the context stream); the kernels are asynchronous on the context stream.  A min_weight below 1 counts as 1, as in the extraction. */
+typedef struct vslam_triangle { int32_t v[3]; } vslam_triangle;   /* 12 bytes: indices into the call's vertex array */
+int vslam_tsdf_mesh_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_weight, vslam_surfel* d_vertices, int32_t* d_vertex_map,
+                        size_t vertex_capacity, vslam_triangle* d_triangles, size_t triangle_capacity, uint64_t* d_counts);
+/* The inverse of vslam_tsdf_blocks_dev: each of the n listed blocks (d_block_ids n x 4 int32 of (map, bx, by, bz), d_voxels n x 512 x 4 uint32, both
+ * 16-byte aligned) is claimed if it is absent and its 512 voxels are replaced.  An id outside map 0 .. 1022 or coordinates [-2^14, 2^14) is refused
+ * per block: it counts in n_dropped_range and nothing is written for it.  A block that finds no slot counts in n_dropped_full and sets status bit 0.
+ * The ids of one call must be distinct (with duplicates, which copy stays is unspecified).  Asynchronous on the context stream. */
+int vslam_tsdf_load_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const int32_t* d_block_ids, const uint32_t* d_voxels, size_t n);
 
 /* ------------------------------------------------------------------ place database: loop-closure candidates and verified edges --- */
 /* Noticing that the camera is back at a place it has seen: keyframe descriptor blocks are kept in a database that outlives the steps (loops close

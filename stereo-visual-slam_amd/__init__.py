@@ -294,6 +294,8 @@ SIGNATURES = {
     "vslam_tsdf_integrate_dev": (I, [P, P, P, P, Z, I, I, I, I, P, P, D, D, I]),
     "vslam_tsdf_extract_dev": (I, [P, P, I, I, P, P, Z, P]),
     "vslam_tsdf_blocks_dev": (I, [P, P, I, P, P, Z, P]),
+    "vslam_tsdf_mesh_dev": (I, [P, P, I, I, P, P, Z, P, Z, P]),
+    "vslam_tsdf_load_blocks_dev": (I, [P, P, P, P, Z]),
     "vslam_place_create": (I, [P, I, I, I, C.POINTER(C.c_void_p)]), "vslam_place_destroy": (None, [P]), "vslam_place_clear": (I, [P]),
     "vslam_place_stats": (I, [P, C.POINTER(PlaceStats)]),
     "vslam_place_read_entry": (I, [P, I, P, P, P, P, P, P]),
@@ -1193,10 +1195,24 @@ class VoxelMap:
         return out[np.lexsort((out["iz"], out["iy"], out["ix"], out["map"]))] if sort else out
 
 
+def canonical_mesh(vertices, triangles):
+    """the canonical form of a mesh for comparisons: vertices sorted by (map, ix, iy, iz, axis), triangle indices remapped (an index outside the vertex
+    array stays as it is), every triangle's corner order kept, triangle rows sorted lexicographically"""
+    order = np.lexsort((vertices["axis"], vertices["iz"], vertices["iy"], vertices["ix"], vertices["map"]))
+    rank = np.empty(len(order), np.int32)
+    rank[order] = np.arange(len(order), dtype=np.int32)
+    tris = np.asarray(triangles, np.int32).reshape(-1, 3)
+    inside = (tris >= 0) & (tris < len(order))
+    tris = np.where(inside, rank[np.where(inside, tris, 0)] if len(order) else tris, tris).astype(np.int32)
+    tris = tris[np.lexsort((tris[:, 2], tris[:, 1], tris[:, 0]))]
+    return vertices[order], tris
+
+
 class TsdfMap:
     """A truncated signed distance field over 8 x 8 x 8 voxel blocks in a device pool (include/vslam_hip.h "surface map"): per voxel the integer sums
     of the quantised distance to the surface, of the views that saw it and of their intensities.  Views that look through a voxel carve it.  Filled
-    through integrate_dev (or KeyframePipeline.surface_map); extract() reads the surface as surfels; belongs to the VO it was created on."""
+    through integrate_dev (or KeyframePipeline.surface_map) or load_blocks; extract() reads the surface as surfels, mesh() as indexed triangles over
+    the same surfels; belongs to the VO it was created on."""
 
     def __init__(self, vo, voxel_size=0.2, trunc_voxels=4, log2_blocks=16):
         self.vo, self.voxel_size, self.trunc_voxels, self.log2_blocks = vo, float(voxel_size), int(trunc_voxels), int(log2_blocks)
@@ -1276,6 +1292,57 @@ class TsdfMap:
         vox = d_vox[:n].cpu().numpy().view(np.uint32).reshape(n, 512, 4)
         order = np.lexsort((ids[:, 3], ids[:, 2], ids[:, 1], ids[:, 0]))
         return ids[order], vox[order]
+
+    def load_blocks(self, ids, voxels):
+        """the inverse of blocks(): every listed block (ids (n, 4) of (map, bx, by, bz), voxels (n, 512, 4) uint32) is claimed if it is absent and its
+        voxels are replaced.  An id out of range counts in stats()["n_dropped_range"], a block that finds no slot in n_dropped_full; the ids of
+        one call must be distinct."""
+        import torch
+        vo = self.vo
+        ids = np.array(ids, np.int32).reshape(-1, 4)                  # (copies: the caller's arrays may be read-only)
+        voxels = np.array(voxels, np.uint32).reshape(-1, 512, 4)
+        assert len(ids) == len(voxels), (ids.shape, voxels.shape)
+        if not len(ids):
+            return
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_ids = torch.from_numpy(ids).to(dev)
+        d_vox = torch.from_numpy(voxels.view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        vo._chk(vo.lib.vslam_tsdf_load_blocks_dev(vo.h, self.h, d_ids.data_ptr(), d_vox.data_ptr(), len(ids)), "vslam_tsdf_load_blocks_dev")
+        vo.sync()
+
+    def mesh(self, map_id=-1, min_weight=1, sort=True):
+        """the triangle mesh of map map_id (-1: every map) over voxels of weight >= min_weight (include/vslam_hip.h "MESH"): (vertices, triangles) --
+        the surfels of extract() with the same arguments as a SURFEL_MAP_DTYPE array, and (n, 3) int32 indices into it, counter-clockwise seen from
+        free space.  sort: the canonical form -- vertices sorted by (map, ix, iy, iz, axis), the indices remapped, every triangle's corner order kept
+        as emitted, the rows sorted lexicographically; otherwise the device's order.  A first call counts, as extract() does; self.last_counts
+        holds the device's two counts."""
+        import torch
+        vo = self.vo
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_n = torch.zeros(2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        vo._chk(vo.lib.vslam_tsdf_mesh_dev(vo.h, self.h, map_id, min_weight, None, None, 0, None, 0, d_n.data_ptr()), "vslam_tsdf_mesh_dev")
+        vo.sync()
+        vcap, tcap = (int(c) for c in d_n.cpu().tolist())
+        d_v = torch.zeros((max(vcap, 1), 48), dtype=torch.uint8, device=dev)
+        d_map = torch.zeros(max(vcap, 1), dtype=torch.int32, device=dev)
+        d_t = torch.full((max(tcap, 1), 3), -1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
+        vo._chk(vo.lib.vslam_tsdf_mesh_dev(vo.h, self.h, map_id, min_weight, d_v.data_ptr(), d_map.data_ptr(), vcap, d_t.data_ptr(), tcap, d_n.data_ptr()),
+                "vslam_tsdf_mesh_dev")
+        vo.sync()
+        self.last_counts = tuple(int(c) for c in d_n.cpu().tolist())
+        nv, nt = min(self.last_counts[0], vcap), min(self.last_counts[1], tcap)
+        v = d_v[:nv].cpu().numpy().reshape(-1).view(SURFEL_DTYPE)
+        verts = np.zeros(nv, SURFEL_MAP_DTYPE)
+        verts["map"] = d_map[:nv].cpu().numpy()
+        for f in SURFEL_DTYPE.names:
+            verts[f] = v[f]
+        tris = d_t[:nt].cpu().numpy().reshape(-1, 3)
+        if not sort:
+            return verts, tris
+        return canonical_mesh(verts, tris)
 
 
 class PlaceDB:

@@ -257,7 +257,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "track_ends_kernel kf_band_kernel kf_set_kernel kf_sliding_kernel kf_gate_kernel map_pnp_inputs_kernels track_map_inputs_kernel "
            "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
            "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel "
-           "tsdf_clear_kernel tsdf_frames_kernel tsdf_alloc_kernel tsdf_cull_kernel tsdf_integrate_kernel tsdf_extract_kernel tsdf_blocks_kernel "
+           "tsdf_clear_kernel tsdf_frames_kernel tsdf_alloc_kernel tsdf_cull_kernel tsdf_integrate_kernel tsdf_extract_kernel tsdf_blocks_kernel tsdf_mesh_vertex_kernel tsdf_mesh_tri_kernel tsdf_load_kernel "
            "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel "
            "pose_graph_kernel full_ba_kernel project_match_kernel";
 }
@@ -1799,7 +1799,7 @@ int vslam_tsdf_create(vslam_ctx* ctx, double voxel_size, int trunc_voxels, int l
     if (trunc_voxels < 1 || trunc_voxels > 8) { set_error("vslam_tsdf_create: trunc_voxels %d outside [1, 8]", trunc_voxels); return VSLAM_ERR_ARG; }
     if (log2_blocks < 6 || log2_blocks > 22) { set_error("vslam_tsdf_create: log2_blocks %d outside [6, 22]", log2_blocks); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
-    TsdfMap* m = new TsdfMap();
+    TsdfMap* m = new TsdfMap(&c->dev_bytes);
     TsdfTable& t = m->t;
     const size_t n = (size_t)1 << log2_blocks, words = ((size_t)c->p.max_batch + 63) / 64;
     // one allocation: pool | keys | frame masks | frame table | counters | list (every part a multiple of 8 bytes, the pool 16-byte aligned)
@@ -1829,6 +1829,7 @@ void vslam_tsdf_destroy(vslam_tsdf_map* tm) {
     hipStreamSynchronize(m->ctx->stream);
     hipFree(m->base);
     m->ctx->dev_bytes -= m->bytes;
+    m->mesh.release();
     delete m;
 }
 
@@ -1892,6 +1893,48 @@ int vslam_tsdf_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int32_
     if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_tsdf_blocks_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     return launch_tsdf_blocks(m->t, map_id, d_block_out, d_voxels_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
+}
+
+int vslam_tsdf_mesh_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_weight, vslam_surfel* d_vertices, int32_t* d_vertex_map, size_t vertex_capacity,
+                        vslam_triangle* d_triangles, size_t triangle_capacity, uint64_t* d_counts) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_mesh_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!d_counts || (vertex_capacity > 0 && !d_vertices) || (triangle_capacity > 0 && !d_triangles)) {
+        set_error("vslam_tsdf_mesh_dev: null d_counts, or a null output with a capacity"); return VSLAM_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(d_vertices) % 16 || reinterpret_cast<uintptr_t>(d_vertex_map) % 4 || reinterpret_cast<uintptr_t>(d_triangles) % 4 ||
+        reinterpret_cast<uintptr_t>(d_counts) % 8) {
+        set_error("vslam_tsdf_mesh_dev: d_vertices must be 16-byte, d_counts 8-byte, d_vertex_map and d_triangles 4-byte aligned"); return VSLAM_ERR_ARG;
+    }
+    if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_tsdf_mesh_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    // the vertex-id table holds every block claimed so far: the count is read here, after everything queued before this call
+    unsigned long long n_blocks = 0;
+    VS_HIP(hipMemcpyAsync(&n_blocks, m->t.counters, sizeof(n_blocks), hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    const size_t n_slots = (size_t)1 << m->t.log2_blocks, blocks = std::max<size_t>(std::min<size_t>((size_t)n_blocks, n_slots), 1);
+    const size_t have = m->mesh.bytes >= n_slots * 4 ? (m->mesh.bytes - n_slots * 4) / (1536 * 4) : 0;
+    if (have < blocks) {
+        if (int rc = m->mesh.reserve((1536 * blocks + n_slots) * 4, c->stream)) return rc;
+    }
+    const size_t vid_blocks = (m->mesh.bytes - n_slots * 4) / (1536 * 4);
+    uint32_t* pos_of_slot = reinterpret_cast<uint32_t*>(m->mesh.p);
+    int32_t* vid = reinterpret_cast<int32_t*>(m->mesh.p + n_slots * 4);
+    return launch_tsdf_mesh(m->t, vid, pos_of_slot, vid_blocks, map_id, min_weight, d_vertices, d_vertex_map, vertex_capacity, d_triangles, triangle_capacity,
+                            reinterpret_cast<unsigned long long*>(d_counts), c->stream);
+}
+
+int vslam_tsdf_load_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const int32_t* d_block_ids, const uint32_t* d_voxels, size_t n) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_load_blocks_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (n > 0 && (!d_block_ids || !d_voxels)) { set_error("vslam_tsdf_load_blocks_dev: a null input with n > 0"); return VSLAM_ERR_ARG; }
+    if (reinterpret_cast<uintptr_t>(d_block_ids) % 16 || reinterpret_cast<uintptr_t>(d_voxels) % 16) {
+        set_error("vslam_tsdf_load_blocks_dev: d_block_ids and d_voxels must be 16-byte aligned"); return VSLAM_ERR_ARG;
+    }
+    VS_ENTER(c);
+    return launch_tsdf_load(m->t, d_block_ids, d_voxels, n, c->stream);
 }
 
 // ---------------------------------------------------------------------------------------------- place database

@@ -501,7 +501,9 @@ constexpr int kTsdfCounters = 8;         // uint64 words: blocks, samples, dropp
 constexpr int kTsdfFrameDoubles = 16;    // a frame of the frame table: R (9), t (3), the inverse pose's translation (3), the map id (-1: takes no part)
 struct TsdfTable { unsigned long long* keys; uint32_t* list; uint4* pool; unsigned long long* counters; double* frames; unsigned long long* pairs;
                    int log2_blocks, J, frame_words; float vs, inv; };
-struct TsdfMap { Ctx* ctx; TsdfTable t; size_t bytes; void* base; };
+struct TsdfMap { Ctx* ctx; TsdfTable t; size_t bytes; void* base;
+                 DevBuf mesh; // the vertex-id table of vslam_tsdf_mesh_dev: vid (3 x 512 int32 per claimed block) | pos_of_slot (one uint32 per slot); grown by the first mesh call
+                 TsdfMap(size_t* acct) : mesh("mesh vertex-id table", acct) {} };
 int launch_tsdf_clear(const TsdfTable& t, hipStream_t stream);
 // form: 0 = every block walks all frames, 1 = a cull kernel writes a frame mask per block first
 int launch_tsdf_integrate(const TsdfTable& t, const VoxelImages& a, const uint8_t* d_gray, size_t img_bytes, int pitch, const int32_t* d_map_id, int form,
@@ -510,6 +512,11 @@ int launch_tsdf_extract(const TsdfTable& t, int map_id, int min_weight, vslam_su
                         hipStream_t stream);
 int launch_tsdf_blocks(const TsdfTable& t, int map_id, int32_t* d_block_out, uint32_t* d_voxels_out, size_t capacity, unsigned long long* d_n_out,
                        hipStream_t stream);
+// tsdf_mesh_kernels.hip: the triangle mesh of the field (include/vslam_hip.h "MESH") and the block loader
+int launch_tsdf_mesh(const TsdfTable& t, int32_t* d_vid, uint32_t* d_pos_of_slot, size_t vid_blocks, int map_id, int min_weight, vslam_surfel* d_vertices,
+                     int32_t* d_vertex_map, size_t vertex_capacity, vslam_triangle* d_triangles, size_t triangle_capacity, unsigned long long* d_counts,
+                     hipStream_t stream);
+int launch_tsdf_load(const TsdfTable& t, const int32_t* d_block_ids, const uint32_t* d_voxels, size_t n, hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- place database
 // place_kernels.hip: keyframe descriptor blocks kept across steps and the place score between them (include/vslam_hip.h "place database").

@@ -58,3 +58,43 @@ def read_surfel_ply(path):
     props = [tuple(ln.split()[1:]) for ln in head if ln.startswith("property")]
     assert props == [(_PLY_TYPES[_SURFEL_PLY_DTYPE[name].str], name) for name in _SURFEL_PLY_DTYPE.names], props
     return np.frombuffer(data[end:], _SURFEL_PLY_DTYPE, count=n).copy()
+
+
+_FACE_PLY_DTYPE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def write_mesh_ply(path, vertices, triangles):
+    """(vertices, triangles) of TsdfMap.mesh() -> a binary little-endian PLY: the vertex properties of write_surfel_ply, then one face per triangle
+    (`property list uchar int vertex_indices`, corner order kept: counter-clockwise seen from free space)"""
+    triangles = np.asarray(triangles, np.int32).reshape(-1, 3)
+    assert len(triangles) == 0 or (triangles.min() >= 0 and triangles.max() < len(vertices)), "triangle indices outside the vertex array"
+    v = np.zeros(len(vertices), _SURFEL_PLY_DTYPE)
+    for name in _SURFEL_PLY_DTYPE.names:
+        v[name] = vertices[name]
+    f3 = np.zeros(len(triangles), _FACE_PLY_DTYPE)
+    f3["n"] = 3
+    f3["v"] = triangles
+    head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v)]
+    head += ["property %s %s" % (_PLY_TYPES[_SURFEL_PLY_DTYPE[name].str], name) for name in _SURFEL_PLY_DTYPE.names]
+    head += ["element face %d" % len(f3), "property list uchar int vertex_indices"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head + ["end_header"]) + "\n").encode("ascii"))
+        f.write(v.tobytes())
+        f.write(f3.tobytes())
+
+
+def read_mesh_ply(path):
+    """(vertices, triangles) of a file write_mesh_ply wrote: a structured array (x, y, z, nx, ny, nz, intensity, weight) and (n, 3) int32"""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    head = data[:end].decode("ascii").split("\n")
+    assert head[:2] == ["ply", "format binary_little_endian 1.0"], head[:2]
+    n = int(next(ln for ln in head if ln.startswith("element vertex")).split()[2])
+    nf = int(next(ln for ln in head if ln.startswith("element face")).split()[2])
+    props = [tuple(ln.split()[1:]) for ln in head if ln.startswith("property")]
+    assert props == [(_PLY_TYPES[_SURFEL_PLY_DTYPE[name].str], name) for name in _SURFEL_PLY_DTYPE.names] + [("list", "uchar", "int", "vertex_indices")], props
+    v = np.frombuffer(data[end:], _SURFEL_PLY_DTYPE, count=n).copy()
+    f3 = np.frombuffer(data[end + v.nbytes:], _FACE_PLY_DTYPE, count=nf)
+    assert (f3["n"] == 3).all()
+    return v, f3["v"].astype(np.int32)

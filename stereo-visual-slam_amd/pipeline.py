@@ -703,7 +703,8 @@ class KeyframePipeline:
         id = the segment index.  step thins the allocation only.  tsdf_map: a TsdfMap of this pipeline's context to accumulate into over several
         steps (a step's frames also carve the blocks earlier steps claimed; voxel_size / trunc_voxels / log2_blocks then go unused); otherwise a new
         one.  poses: what close_loops() or full_ba() returned, in place of the BA poses.
-        Returns the map: .extract() reads the surfels, write_surfel_ply(path, tm.extract()) writes them."""
+        Returns the map: .extract() reads the surfels, write_surfel_ply(path, tm.extract()) writes them; .mesh() connects them into triangles,
+        write_mesh_ply(path, *tm.mesh()) writes the mesh."""
         assert self.depth == "sgbm", "surface_map needs depth='sgbm': it fuses the SGBM disparity maps"
         assert self.with_ba and self.ba_windows == "tracks", "surface_map needs ba_windows='tracks': the poses are the BA windows'"
         if poses is not None:

@@ -5,13 +5,19 @@ profiler's split of one call into its kernels, and the library's own streaming c
 the neighbour figure.
 
     python tools/bench_tsdf.py [--batches 256,1024] [--voxel 0.2] [--trunc 4] [--z-min 10] [--z-max 40] [--windows 5] [--out profiles/tsdf.json]
+                               [--mesh-out profiles/tsdf_mesh.json] [--mesh-only]
 
 The inputs are one KeyframePipeline(depth="sgbm", ba_windows="tracks", anms_num=500) step at each batch size: its disparity maps, left images and
 BA-refined poses (KeyframePipeline.dense_map_inputs).  A figure is the median of `--windows` timed windows, each a host clock around enough
 back-to-back calls to last >= 0.2 s, ending in a synchronise; the profiler is off (it is on for the one call of the kernel split only).
 "fresh" = into a map cleared before every call (the clear's own time, measured the same way, taken off): every block is claimed; "warm" = into the
 map the previous call filled: no block is claimed, every sum is read and written.  Before anything is timed, the first two frames go through both
-forms into a small map and are compared with the numpy restatement tests/tsdf_ref.py: the block set, every sum, every surfel."""
+forms into a small map and are compared with the numpy restatement tests/tsdf_ref.py: the block set, every sum, every surfel.
+
+--mesh-out adds the mesh on the same maps: ms per call of vslam_tsdf_mesh_dev next to vslam_tsdf_extract_dev with the same
+arguments, the split of one mesh call into its two kernels, and the copy probe on the mesh's compulsory bytes (8 KiB read per block, 48 + 4 B
+written per vertex, 12 B per triangle) and on those plus the vertex-id table's traffic (6 KiB written per block, 12 B read per triangle).  The mesh
+of the small map is compared with tests/tsdf_mesh_ref.py before anything is timed.  --mesh-only skips the integration and dense-map figures."""
 import argparse
 import json
 import os
@@ -25,9 +31,47 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import tsdf_mesh_ref as MR  # noqa: E402
 import tsdf_ref as TR  # noqa: E402
 from bench_voxel import timed  # noqa: E402
 from stereo_visual_slam_amd.pipeline import KeyframePipeline  # noqa: E402
+
+
+def mesh_case(vo, tm, dev, windows, case):
+    """the mesh call and the extract call on the filled map tm (min_weight 2, every map), by the method of the figures above"""
+    import torch
+    sync = vo.sync
+    d_n = torch.zeros(2, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    mesh = lambda v, m, vcap, t, tcap: vo._chk(vo.lib.vslam_tsdf_mesh_dev(vo.h, tm.h, -1, 2, v, m, vcap, t, tcap, d_n.data_ptr()), "vslam_tsdf_mesh_dev")
+    mesh(None, None, 0, None, 0); sync()
+    nv, nt = (int(c) for c in d_n.cpu().tolist())
+    d_v = torch.zeros((max(nv, 1), 48), dtype=torch.uint8, device=dev)
+    d_m = torch.zeros(max(nv, 1), dtype=torch.int32, device=dev)
+    d_t = torch.zeros((max(nt, 1), 3), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    full = lambda: mesh(d_v.data_ptr(), d_m.data_ptr(), nv, d_t.data_ptr(), nt)
+    mesh_ms, mw, n = timed(full, sync, windows)
+    count_ms, _, _ = timed(lambda: mesh(None, None, 0, None, 0), sync, windows)
+    ext = lambda: vo._chk(vo.lib.vslam_tsdf_extract_dev(vo.h, tm.h, -1, 2, d_v.data_ptr(), d_m.data_ptr(), nv, d_n.data_ptr()), "vslam_tsdf_extract_dev")
+    ext_ms, ew, _ = timed(ext, sync, windows)
+    full(); sync()
+    assert [int(c) for c in d_n.cpu().tolist()] == [nv, nt] and int(d_t.min()) >= 0 and int(d_t.max()) < nv
+    vo.profile_enable(True); vo.profile_read()
+    full(); sync()
+    prof = {k: round(ms, 4) for k, (ms, _, _) in vo.profile_read().items() if k.startswith("tsdf_mesh")}
+    vo.profile_enable(False)
+    blocks = tm.stats()["n_blocks"]
+    compulsory = 8192 * blocks + 52 * nv + 12 * nt
+    with_vid = compulsory + 6144 * blocks + 12 * nt
+    gbs = vo.hbm_copy_probe(max(compulsory // 2, 1 << 20), 20)
+    gbs2 = vo.hbm_copy_probe(max(with_vid // 2, 1 << 20), 20)
+    case.update(vertices_min_weight_2=nv, triangles_min_weight_2=nt, mesh_ms=round(mesh_ms, 4), mesh_windows=mw, calls_per_window=n, mesh_count_only_ms=round(count_ms, 4),
+                extract_ms=round(ext_ms, 4), extract_windows=ew, ratio_mesh_over_extract=round(mesh_ms / ext_ms, 2), kernels_ms_one_call=prof,
+                compulsory_bytes=compulsory, copy_probe_gbs=round(gbs, 1), copy_probe_ms_compulsory=round(compulsory / gbs * 1e-6, 4),
+                bytes_with_vertex_ids=with_vid, copy_probe_ms_with_vertex_ids=round(with_vid / gbs2 * 1e-6, 4),
+                ratio_mesh_over_copy=round(mesh_ms / (compulsory / gbs * 1e-6), 2))
+    return case
 
 
 def main():
@@ -40,11 +84,14 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--unique-frames", type=int, default=16)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mesh-out", default=None)
+    ap.add_argument("--mesh-only", action="store_true")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_tsdf: no GPU visible (there is nothing to measure without one)")
     res = dict(voxel_size=a.voxel, trunc_voxels=a.trunc, z_min=a.z_min, z_max=a.z_max, windows=a.windows, device=torch.cuda.get_device_name(0), cases=[])
+    mres = dict(res, cases=[])
     seq = None
     for B in [int(b) for b in a.batches.split(",")]:
         p = KeyframePipeline(B, anms_num=500, unique_frames=a.unique_frames, seed=0, ba_windows="tracks", depth="sgbm", sequence=seq, render_workers=8)
@@ -71,6 +118,11 @@ def main():
                 ids, vox = small.blocks()
                 assert np.array_equal(ids, want_ids) and np.array_equal(vox, want_vox) and small.stats()["n_dropped_full"] == 0, "the surface map differs from the restatement (form %d)" % form
                 assert small.extract().tobytes() == want.tobytes(), "the surfels differ from the restatement (form %d)" % form
+            if a.mesh_out:
+                for mw in (1, 2):
+                    gv, gt = small.mesh(min_weight=mw)
+                    wv, wt = MR.mesh(want_ids, want_vox, a.voxel, mw)
+                    assert gv.tobytes() == wv.tobytes() and np.array_equal(gt, wt) and len(wt) > 0, "the mesh differs from the yardstick (min_weight %d)" % mw
             small.close()
             # ---- the pool: a load factor below one half
             probe = vo.tsdf_map(a.voxel, a.trunc, 19)
@@ -83,6 +135,18 @@ def main():
             sync = vo.sync
             case = dict(B=B, log2_blocks=log2, pixels=B * h * w, blocks=st["n_blocks"], alloc_samples=st["n_samples"], dropped_range=st["n_dropped_range"],
                         load_factor=round(st["n_blocks"] / (1 << log2), 3))
+            if a.mesh_out:
+                integrate(tm); sync()
+                mcase = mesh_case(vo, tm, p.dev, a.windows, dict(case))
+                mres["cases"].append(mcase)
+                print(json.dumps(mcase), flush=True)
+                with open(a.mesh_out, "w") as f:
+                    json.dump(mres, f, indent=1)
+                    f.write("\n")
+                tm.clear(); sync()
+            if a.mesh_only:
+                tm.close()
+                continue
             clear_ms, _, _ = timed(tm.clear, sync, a.windows)
             case["clear_ms"] = round(clear_ms, 4)
             for form, name in ((0, "walk_all"), (1, "masks")):
