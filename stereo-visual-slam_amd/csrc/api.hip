@@ -226,6 +226,41 @@ static int check_img(Ctx* c, const void* img, int w, int h, int stride) {
     return VSLAM_OK;
 }
 
+// ---- the two LM / PCG solvers (pose graph, full BA): their parameter structs have the same fields, and both leave a status word per problem at the
+// front of their state buffer
+template <class Params>
+static void solver_default_params(Params* p) {
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(Params);
+    p->max_iters = 50; p->pcg_max_iters = 4000; p->pcg_tol = 1e-10; p->step_tol = 1e-9; p->lambda_init = 1e-4;
+}
+// p = the caller's parameters, or the defaults without any, checked (`me` is the entry's name, `type` the struct's)
+template <class Params>
+static int solver_params(const char* me, const char* type, const Params* params, Params& p) {
+    solver_default_params(&p);
+    if (params) {
+        if (params->struct_size != (int32_t)sizeof(Params)) { set_error("%s: %s struct_size %d, the library has %d", me, type, params->struct_size, (int)sizeof(Params)); return VSLAM_ERR_ARG; }
+        p = *params;
+    }
+    if (p.max_iters < 0 || p.pcg_max_iters < 1 || !(p.pcg_tol >= 0) || !(p.step_tol >= 0) || !(p.lambda_init > 0) || !(p.lambda_init <= 1e12)) {
+        set_error("%s: parameters out of range (max_iters >= 0, pcg_max_iters >= 1, pcg_tol >= 0, step_tol >= 0, 0 < lambda_init <= 1e12)", me);
+        return VSLAM_ERR_ARG;
+    }
+    return VSLAM_OK;
+}
+// the first n status words of buf, where the most recent call of entry `solver` left `last_n` of them (`what`: graphs / problems)
+static int solver_status(Ctx* c, const char* me, const char* what, const char* solver, const DevBuf Ctx::*buf, const int Ctx::*last_n, int n, int32_t* h_status) {
+    if (!h_status) { set_error("%s: null h_status", me); return VSLAM_ERR_ARG; }
+    if (n < 0) { set_error("%s: negative n_%s %d", me, what, n); return VSLAM_ERR_ARG; }
+    if (!c) { set_error("%s: null context", me); return VSLAM_ERR_ARG; }
+    if (n > c->*last_n) { set_error("%s: %d %s asked for, the most recent %s call had %d", me, n, what, solver, c->*last_n); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    if (n > 0) VS_HIP(hipMemcpyAsync(h_status, (c->*buf).p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return VSLAM_OK;
+}
+
 } // namespace vslam
 
 using namespace vslam;
@@ -2135,12 +2170,7 @@ int vslam_place_verify_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, c
 }
 
 // ---------------------------------------------------------------------------------------------- pose graph
-void vslam_pose_graph_default_params(vslam_pose_graph_params* p) {
-    if (!p) return;
-    memset(p, 0, sizeof(*p));
-    p->struct_size = (int32_t)sizeof(vslam_pose_graph_params);
-    p->max_iters = 50; p->pcg_max_iters = 4000; p->pcg_tol = 1e-10; p->step_tol = 1e-9; p->lambda_init = 1e-4;
-}
+void vslam_pose_graph_default_params(vslam_pose_graph_params* p) { solver_default_params(p); }
 
 // (the checks on the structs come before the one on the context: they need no device)
 int vslam_pose_graph_dev(vslam_ctx* ctx, const vslam_pose_graph* graph, const vslam_pose_graph_params* params, double* d_T_out,
@@ -2149,15 +2179,7 @@ int vslam_pose_graph_dev(vslam_ctx* ctx, const vslam_pose_graph* graph, const vs
     if (!graph) { set_error("vslam_pose_graph_dev: null graph"); return VSLAM_ERR_ARG; }
     if (graph->struct_size != (int32_t)sizeof(vslam_pose_graph)) { set_error("vslam_pose_graph_dev: vslam_pose_graph struct_size %d, the library has %d", graph->struct_size, (int)sizeof(vslam_pose_graph)); return VSLAM_ERR_ARG; }
     vslam_pose_graph_params p;
-    vslam_pose_graph_default_params(&p);
-    if (params) {
-        if (params->struct_size != (int32_t)sizeof(vslam_pose_graph_params)) { set_error("vslam_pose_graph_dev: vslam_pose_graph_params struct_size %d, the library has %d", params->struct_size, (int)sizeof(vslam_pose_graph_params)); return VSLAM_ERR_ARG; }
-        p = *params;
-    }
-    if (p.max_iters < 0 || p.pcg_max_iters < 1 || !(p.pcg_tol >= 0) || !(p.step_tol >= 0) || !(p.lambda_init > 0) || !(p.lambda_init <= 1e12)) {
-        set_error("vslam_pose_graph_dev: parameters out of range (max_iters >= 0, pcg_max_iters >= 1, pcg_tol >= 0, step_tol >= 0, 0 < lambda_init <= 1e12)");
-        return VSLAM_ERR_ARG;
-    }
+    if (int rc = solver_params("vslam_pose_graph_dev", "vslam_pose_graph_params", params, p)) return rc;
     if (graph->n_graphs < 0 || graph->total_nodes < 0 || graph->total_edges < 0) { set_error("vslam_pose_graph_dev: negative count (n_graphs %d, total_nodes %d, total_edges %d)", graph->n_graphs, graph->total_nodes, graph->total_edges); return VSLAM_ERR_ARG; }
     if (!graph->d_node_off || !graph->d_edge_off) { set_error("vslam_pose_graph_dev: null d_node_off or d_edge_off"); return VSLAM_ERR_ARG; }
     if (graph->total_nodes > 0 && (!graph->d_T || !d_T_out)) { set_error("vslam_pose_graph_dev: null d_T or d_T_out"); return VSLAM_ERR_ARG; }
@@ -2170,24 +2192,11 @@ int vslam_pose_graph_dev(vslam_ctx* ctx, const vslam_pose_graph* graph, const vs
 }
 
 int vslam_pose_graph_status_dev(vslam_ctx* ctx, int n_graphs, int32_t* h_status) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!h_status) { set_error("vslam_pose_graph_status_dev: null h_status"); return VSLAM_ERR_ARG; }
-    if (n_graphs < 0) { set_error("vslam_pose_graph_status_dev: negative n_graphs %d", n_graphs); return VSLAM_ERR_ARG; }
-    if (!c) { set_error("vslam_pose_graph_status_dev: null context"); return VSLAM_ERR_ARG; }
-    if (n_graphs > c->pgraph_n) { set_error("vslam_pose_graph_status_dev: %d graphs asked for, the most recent vslam_pose_graph_dev call had %d", n_graphs, c->pgraph_n); return VSLAM_ERR_ARG; }
-    VS_ENTER(c);
-    if (n_graphs > 0) VS_HIP(hipMemcpyAsync(h_status, c->pgraph.p, sizeof(int32_t) * (size_t)n_graphs, hipMemcpyDeviceToHost, c->stream));
-    VS_HIP(hipStreamSynchronize(c->stream));
-    return VSLAM_OK;
+    return solver_status(reinterpret_cast<Ctx*>(ctx), "vslam_pose_graph_status_dev", "graphs", "vslam_pose_graph_dev", &Ctx::pgraph, &Ctx::pgraph_n, n_graphs, h_status);
 }
 
 // ---------------------------------------------------------------------------------------------- full bundle adjustment
-void vslam_full_ba_default_params(vslam_full_ba_params* p) {
-    if (!p) return;
-    memset(p, 0, sizeof(*p));
-    p->struct_size = (int32_t)sizeof(vslam_full_ba_params);
-    p->max_iters = 50; p->pcg_max_iters = 4000; p->pcg_tol = 1e-10; p->step_tol = 1e-9; p->lambda_init = 1e-4;
-}
+void vslam_full_ba_default_params(vslam_full_ba_params* p) { solver_default_params(p); }
 
 // (the checks on the structs come before the one on the context: they need no device)
 int vslam_full_ba_dev(vslam_ctx* ctx, const vslam_full_ba* ba, const vslam_full_ba_params* params, double* d_T_out, double* d_xyz_out,
@@ -2196,15 +2205,7 @@ int vslam_full_ba_dev(vslam_ctx* ctx, const vslam_full_ba* ba, const vslam_full_
     if (!ba) { set_error("vslam_full_ba_dev: null problem"); return VSLAM_ERR_ARG; }
     if (ba->struct_size != (int32_t)sizeof(vslam_full_ba)) { set_error("vslam_full_ba_dev: vslam_full_ba struct_size %d, the library has %d", ba->struct_size, (int)sizeof(vslam_full_ba)); return VSLAM_ERR_ARG; }
     vslam_full_ba_params p;
-    vslam_full_ba_default_params(&p);
-    if (params) {
-        if (params->struct_size != (int32_t)sizeof(vslam_full_ba_params)) { set_error("vslam_full_ba_dev: vslam_full_ba_params struct_size %d, the library has %d", params->struct_size, (int)sizeof(vslam_full_ba_params)); return VSLAM_ERR_ARG; }
-        p = *params;
-    }
-    if (p.max_iters < 0 || p.pcg_max_iters < 1 || !(p.pcg_tol >= 0) || !(p.step_tol >= 0) || !(p.lambda_init > 0) || !(p.lambda_init <= 1e12)) {
-        set_error("vslam_full_ba_dev: parameters out of range (max_iters >= 0, pcg_max_iters >= 1, pcg_tol >= 0, step_tol >= 0, 0 < lambda_init <= 1e12)");
-        return VSLAM_ERR_ARG;
-    }
+    if (int rc = solver_params("vslam_full_ba_dev", "vslam_full_ba_params", params, p)) return rc;
     const double big = 1.7976931348623157e308;
     if (!(ba->K4[0] > 0) || !(ba->K4[0] <= big) || !(ba->K4[1] > 0) || !(ba->K4[1] <= big) || !(fabs(ba->K4[2]) <= big) || !(fabs(ba->K4[3]) <= big) || !(ba->bf >= 0) ||
         !(ba->bf <= big) || !(ba->huber_delta >= 0) || !(ba->huber_delta <= big)) {
@@ -2230,15 +2231,7 @@ int vslam_full_ba_dev(vslam_ctx* ctx, const vslam_full_ba* ba, const vslam_full_
 }
 
 int vslam_full_ba_status_dev(vslam_ctx* ctx, int n_problems, int32_t* h_status) {
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    if (!h_status) { set_error("vslam_full_ba_status_dev: null h_status"); return VSLAM_ERR_ARG; }
-    if (n_problems < 0) { set_error("vslam_full_ba_status_dev: negative n_problems %d", n_problems); return VSLAM_ERR_ARG; }
-    if (!c) { set_error("vslam_full_ba_status_dev: null context"); return VSLAM_ERR_ARG; }
-    if (n_problems > c->fullba_n) { set_error("vslam_full_ba_status_dev: %d problems asked for, the most recent vslam_full_ba_dev call had %d", n_problems, c->fullba_n); return VSLAM_ERR_ARG; }
-    VS_ENTER(c);
-    if (n_problems > 0) VS_HIP(hipMemcpyAsync(h_status, c->fullba.p, sizeof(int32_t) * (size_t)n_problems, hipMemcpyDeviceToHost, c->stream));
-    VS_HIP(hipStreamSynchronize(c->stream));
-    return VSLAM_OK;
+    return solver_status(reinterpret_cast<Ctx*>(ctx), "vslam_full_ba_status_dev", "problems", "vslam_full_ba_dev", &Ctx::fullba, &Ctx::fullba_n, n_problems, h_status);
 }
 
 // ---------------------------------------------------------------------------------------------- match by projection

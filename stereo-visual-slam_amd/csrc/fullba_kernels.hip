@@ -1,7 +1,7 @@
 // fullba_kernels.hip -- full bundle adjustment (include/vslam_hip.h "full bundle adjustment").
 //
-// One persistent workgroup per problem runs every Levenberg-Marquardt iteration of its problem, the design of posegraph_kernels.hip: linearise the
-// observations and edges, eliminate the landmarks, solve the reduced camera system S = U + edges - W V^-1 W' by preconditioned conjugate gradients
+// One persistent workgroup per problem runs every Levenberg-Marquardt iteration of its problem, the design of posegraph_kernels.hip (the set-up
+// phases and the edge cost pass the two solvers share are in pg_solver.h): linearise the observations and edges, eliminate the landmarks, solve the reduced camera system S = U + edges - W V^-1 W' by preconditioned conjugate gradients
 // that never form it, back-substitute, try the step, accept or reject.  No grid-wide synchronisation, no host round trip.
 //
 // An observation's Jacobians factor through A = de/dP (3 x 3, P the point in the camera): Jp = A [I, -P^], Jl = A R.  With B = rho' A'A (symmetric,
@@ -19,7 +19,7 @@
 // order, integer atomics only.  None of it depends on the workgroup width or on the other problems of the batch.
 #include <algorithm>
 
-#include "pg_device.h"
+#include "pg_solver.h"
 #include "se3_device.h"
 #include "vslam_internal.h"
 
@@ -151,22 +151,17 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
     __shared__ int sh_scan[T];
     __shared__ int sh_cnt[8];   // free keyframes, singular flag, observations dropped, active observations
 
-    // ---- the problem's ranges: in range, in order, and disjoint from every other problem's
+    // ---- the problem's ranges
     const int G = a.b.n_problems;
     const int n0 = a.b.d_kf_off[g], n1 = a.b.d_kf_off[g + 1], m0 = a.b.d_lm_off[g], m1 = a.b.d_lm_off[g + 1];
     const int o0 = a.b.d_obs_off[g], o1 = a.b.d_obs_off[g + 1], e0 = a.b.d_edge_off[g], e1 = a.b.d_edge_off[g + 1];
-    int ok = n0 >= 0 && n1 >= n0 && n1 <= a.b.total_kfs && m0 >= 0 && m1 >= m0 && m1 <= a.b.total_lms && o0 >= 0 && o1 >= o0 && o1 <= a.b.total_obs &&
-             e0 >= 0 && e1 >= e0 && e1 <= a.b.total_edges;
-    for (int k = tid; k <= G; k += T) {
-        const int no = a.b.d_kf_off[k], mo = a.b.d_lm_off[k], oo = a.b.d_obs_off[k], eo = a.b.d_edge_off[k];
-        if (k <= g ? (no > n0 || mo > m0 || oo > o0 || eo > e0) : (no < n1 || mo < m1 || oo < o1 || eo < e1)) ok = 0;
-    }
-    ok = __syncthreads_and(ok);
+    const int ok = __syncthreads_and(pg_own_range<T>(a.b.d_kf_off, G, g, a.b.total_kfs, tid) & pg_own_range<T>(a.b.d_lm_off, G, g, a.b.total_lms, tid) &
+                                     pg_own_range<T>(a.b.d_obs_off, G, g, a.b.total_obs, tid) & pg_own_range<T>(a.b.d_edge_off, G, g, a.b.total_edges, tid));
     vslam_full_ba_stats st;
     st.chi2_init = st.chi2_final = 0; st.lambda = a.p.lambda_init; st.lm_iters = st.pcg_iters = st.n_free = st.n_obs_dropped = 0; st.status = 0; st.reserved = 0;
     if (!ok) {
         st.status = VSLAM_FBA_BAD_INDEX;
-        if (tid == 0) { s.status[g] = st.status; if (a.stats) a.stats[g] = st; }
+        pg_write_stats(st, s.status, a.stats, g, tid);
         return;
     }
     const int N = n1 - n0, M = m1 - m0, O = o1 - o0, E = e1 - e0;
@@ -174,9 +169,8 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
     const int32_t* okf = a.b.d_obs_kf + o0; const int32_t* olm = a.b.d_obs_lm + o0;
     const float* ouv = a.b.d_obs_uv + (size_t)o0 * 2; const float* odisp = a.b.d_obs_disp ? a.b.d_obs_disp + o0 : nullptr;
     const uint8_t* oin = a.b.d_obs_active ? a.b.d_obs_active + o0 : nullptr;
-    const int32_t* ei = a.b.d_edge_i + e0; const int32_t* ej = a.b.d_edge_j + e0;
-    const double* Zs = a.b.d_edge_Z + (size_t)e0 * 7; const double* ws = a.b.d_edge_w + (size_t)e0 * 6;
-    const uint8_t* act = a.b.d_edge_active ? a.b.d_edge_active + e0 : nullptr;
+    const PgEdges ed = {E, a.b.d_edge_i + e0, a.b.d_edge_j + e0, a.b.d_edge_Z + (size_t)e0 * 7, a.b.d_edge_w + (size_t)e0 * 6,
+                        a.b.d_edge_active ? a.b.d_edge_active + e0 : nullptr, s.PQ + (size_t)e0 * 36, s.res + (size_t)e0 * 6};
     const double* Tin = a.b.d_T + (size_t)n0 * 7; const double* Xin = a.b.d_xyz + (size_t)m0 * 3;
     double* To = a.T_out + (size_t)n0 * 7; double* Xo = a.X_out + (size_t)m0 * 3;
     double* lin = s.lin + (size_t)o0 * kFbaLin; double* cq = s.cq + (size_t)o0 * 6;
@@ -189,11 +183,11 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
     double* vz = s.z + (size_t)n0 * 6; double* vp = s.p + (size_t)n0 * 6; double* vy = s.y + (size_t)n0 * 6; double* vD = s.D + (size_t)n0 * 6;
     double* Tn = s.Tnew + (size_t)n0 * 7;
     int32_t* held = s.held + n0; int32_t* kstart = s.kstart + n0 + g; int32_t* estart = s.estart + n0 + g; int32_t* kcur = s.kcur + n0; int32_t* ecur = s.ecur + n0;
-    double* PQ = s.PQ + (size_t)e0 * 36; double* res = s.res + (size_t)e0 * 6; double* te = s.te + (size_t)e0 * 12;
+    double* te = s.te + (size_t)e0 * 12;
     int32_t* einc = s.einc + (size_t)e0 * 2; int32_t* etmp = s.etmp + (size_t)e0 * 2;
     double* pk0 = s.pk0 + (n0 >> 6) + g; double* pk1 = s.pk1 + (n0 >> 6) + g; double* pk2 = s.pk2 + (n0 >> 6) + g;
     double* po = s.po + (o0 >> 6) + g; double* pe = s.pe + (e0 >> 6) + g; double* pl = s.pl + (m0 >> 6) + g;
-    const int Nr = (N + 63) & ~63, Mr = (M + 63) & ~63, Or = (O + 63) & ~63, Er = (E + 63) & ~63;
+    const int Nr = (N + 63) & ~63, Mr = (M + 63) & ~63, Or = (O + 63) & ~63;
 
     // ---- the caller's ids and values; poses and points are copied through
     int bad = 0, nonfinite = 0;
@@ -203,19 +197,8 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
         if (!pg_finite(ouv[(size_t)o * 2]) || !pg_finite(ouv[(size_t)o * 2 + 1])) nonfinite = 1;
         if (odisp && odisp[o] > 3.4028234e38f) nonfinite = 1;   // (+inf; a NaN or a negative value marks a mono observation)
     }
-    for (int e = tid; e < E; e += T) {
-        const int i = ei[e], j = ej[e];
-        if (i < 0 || i >= N || j < 0 || j >= N || i == j) bad = 1;
-        for (int q = 0; q < 7; ++q) if (!pg_finite(Zs[(size_t)e * 7 + q])) nonfinite = 1;
-        for (int q = 0; q < 6; ++q) { const double w = ws[(size_t)e * 6 + q]; if (!pg_finite(w) || w < 0) nonfinite = 1; }
-    }
-    for (int k = tid; k < N; k += T) {
-        for (int q = 0; q < 7; ++q) {
-            const double v = Tin[(size_t)k * 7 + q];
-            if (!pg_finite(v)) nonfinite = 1;
-            To[(size_t)k * 7 + q] = v;   // (the same lane owns keyframe k in every keyframe loop below)
-        }
-    }
+    pg_check_edges<T>(ed, N, tid, bad, nonfinite);
+    pg_copy_poses<T>(Tin, To, N, tid, nonfinite);
     for (int l = tid; l < M; l += T) {
         for (int q = 0; q < 3; ++q) {
             const double v = Xin[(size_t)l * 3 + q];
@@ -227,7 +210,7 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
     nonfinite = __syncthreads_or(nonfinite);
     if (bad || nonfinite) {
         st.status = (bad ? VSLAM_FBA_BAD_INDEX : 0) | (nonfinite ? VSLAM_FBA_NONFINITE : 0);
-        if (tid == 0) { s.status[g] = st.status; if (a.stats) a.stats[g] = st; }
+        pg_write_stats(st, s.status, a.stats, g, tid);
         return;
     }
 
@@ -257,56 +240,24 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
         if (dropped) atomicAdd(&sh_cnt[2], dropped);
         if (nact) atomicAdd(&sh_cnt[3], nact);
         for (int e = tid; e < E; e += T) {
-            if (act && !act[e]) continue;
-            atomicAdd(&ecur[ei[e]], 1); atomicAdd(&ecur[ej[e]], 1);
+            if (!ed.on(e)) continue;
+            atomicAdd(&ecur[ed.i[e]], 1); atomicAdd(&ecur[ed.j[e]], 1);
         }
     }
     __syncthreads();
-    // counts -> offsets; the cursors restart at the offsets
-    auto scan = [&](int32_t* cnt, int32_t* start) {
-        const int chunk = (N + T - 1) / T, k0 = min(N, tid * chunk), k1 = min(N, k0 + chunk);
-        int sum = 0;
-        for (int k = k0; k < k1; ++k) sum += cnt[k];
-        sh_scan[tid] = sum;
-        __syncthreads();
-        int base = 0;
-        for (int t = 0; t < tid; ++t) base += sh_scan[t];
-        for (int k = k0; k < k1; ++k) { const int d = cnt[k]; start[k] = base; cnt[k] = base; base += d; }
-        if (tid == T - 1) start[N] = base;
-        __syncthreads();
-    };
-    {
-        int nfree = 0;
-        for (int k = tid; k < N; k += T) {
-            if (kcur[k] == 0 && ecur[k] == 0) held[k] = 1;
-            nfree += !held[k];
-        }
-        if (nfree) atomicAdd(&sh_cnt[0], nfree);
-    }
+    pg_hold_isolated<T>(held, N, tid, &sh_cnt[0], [&](int k) { return kcur[k] == 0 && ecur[k] == 0; });
     __syncthreads();
-    scan(kcur, kstart);
-    scan(ecur, estart);
+    pg_counts_to_offsets<T>(kcur, kstart, N, sh_scan, tid);
+    pg_counts_to_offsets<T>(ecur, estart, N, sh_scan, tid);
     for (int o = tid; o < O; o += T) if (oact[o]) ktmp[atomicAdd(&kcur[okf[o]], 1)] = o;
     for (int e = tid; e < E; e += T) {
-        if (act && !act[e]) continue;
-        etmp[atomicAdd(&ecur[ei[e]], 1)] = 2 * e;
-        etmp[atomicAdd(&ecur[ej[e]], 1)] = 2 * e + 1;
+        if (!ed.on(e)) continue;
+        etmp[atomicAdd(&ecur[ed.i[e]], 1)] = 2 * e;
+        etmp[atomicAdd(&ecur[ed.j[e]], 1)] = 2 * e + 1;
     }
     __syncthreads();
-    // every list sorted by rank: a wave per list, a lane per entry, the entries are distinct
-    auto rank_sort = [&](const int32_t* start, const int32_t* tmp, int32_t* out) {
-        for (int k = tid >> 6; k < N; k += T >> 6) {
-            const int b0 = start[k], n = start[k + 1] - b0;
-            for (int i = lane; i < n; i += 64) {
-                const int v = tmp[b0 + i];
-                int r = 0;
-                for (int j = 0; j < n; ++j) r += tmp[b0 + j] < v;
-                out[b0 + r] = v;
-            }
-        }
-    };
-    rank_sort(kstart, ktmp, kinc);
-    rank_sort(estart, etmp, einc);
+    pg_sort_lists_by_wave<T>(kstart, ktmp, kinc, N, tid);
+    pg_sort_lists_by_wave<T>(estart, etmp, einc, N, tid);
     for (int k = tid; k < N; k += T) {
         for (int q = 0; q < 6; ++q) {
             const size_t o = (size_t)k * 6 + q;
@@ -367,41 +318,7 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
             c = pg_wave_sum(c);
             if (lane == 0) po[o >> 6] = c;
         }
-        for (int e = tid; e < Er; e += T) {
-            double c = 0;
-            if (e < E && !(act && !act[e])) {
-                const int i = ei[e], j = ej[e];
-                double Ti[7], Tj[7], Z[7], w[6], r[6], Ee[7], Zi[7];
-#pragma unroll
-                for (int q = 0; q < 7; ++q) { Ti[q] = Tp[(size_t)i * 7 + q]; Tj[q] = Tp[(size_t)j * 7 + q]; Z[q] = Zs[(size_t)e * 7 + q]; }
-#pragma unroll
-                for (int q = 0; q < 6; ++q) w[q] = ws[(size_t)e * 6 + q];
-                pg_residual(Ti, Tj, Z, r, Ee, Zi);
-                c = pg_chi2(r, w);
-                if (keep) {
-                    double Om[9], U[9], Om2[9], OU[9], UO[9], am[9], bm[9], P[9], Qm[9];
-                    pg_hat(r + 3, Om); pg_hat(r, U);
-                    pg_mm3(Om, Om, Om2); pg_mm3(Om, U, OU); pg_mm3(U, Om, UO);
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) {
-                        am[q] = -0.5 * Om[q] + Om2[q] * (1.0 / 12.0);
-                        bm[q] = -0.5 * U[q] + (OU[q] + UO[q]) * (1.0 / 12.0);
-                    }
-                    am[0] += 1.0; am[4] += 1.0; am[8] += 1.0;
-                    double* pq = PQ + (size_t)e * 36;
-                    pg_jac(am, bm, Zi, 1.0, P, Qm);
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) { pq[q] = P[q]; pq[9 + q] = Qm[q]; }
-                    pg_jac(am, bm, Ee, -1.0, P, Qm);
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) { pq[18 + q] = P[q]; pq[27 + q] = Qm[q]; }
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) res[(size_t)e * 6 + q] = r[q];
-                }
-            }
-            c = pg_wave_sum(c);
-            if (lane == 0) pe[e >> 6] = c;
-        }
+        pg_edge_cost_pass<T>(ed, Tp, keep, pe, tid);
         if (keep) {
             for (int k = tid; k < N; k += T) {
                 double R[9];
@@ -520,12 +437,12 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
                     }
                     for (int q = estart[k]; q < estart[k + 1]; ++q) {
                         const int e = einc[q] >> 1, side = einc[q] & 1;
-                        const double* pq = PQ + (size_t)e * 36;
+                        const double* pq = ed.PQ + (size_t)e * 36;
                         double Pa[9], Qa[9], w[6], wr[6], o6[6];
 #pragma unroll
                         for (int m = 0; m < 9; ++m) { Pa[m] = pq[side * 18 + m]; Qa[m] = pq[side * 18 + 9 + m]; }
 #pragma unroll
-                        for (int m = 0; m < 6; ++m) { w[m] = ws[(size_t)e * 6 + m]; wr[m] = w[m] * res[(size_t)e * 6 + m]; }
+                        for (int m = 0; m < 6; ++m) { w[m] = ed.w[(size_t)e * 6 + m]; wr[m] = w[m] * ed.res[(size_t)e * 6 + m]; }
                         pg_JT(Pa, Qa, wr, o6);
 #pragma unroll
                         for (int m = 0; m < 6; ++m) bk[m] -= o6[m];
@@ -677,9 +594,9 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
             }
             // edges: per side the other side's W J p
             for (int e = tid; e < E; e += T) {
-                if (act && !act[e]) continue;
-                const int i = ei[e], j = ej[e];
-                const double* pq = PQ + (size_t)e * 36;
+                if (!ed.on(e)) continue;
+                const int i = ed.i[e], j = ed.j[e];
+                const double* pq = ed.PQ + (size_t)e * 36;
                 double Pm[9], Qm[9], v[6], t1[6], t2[6];
 #pragma unroll
                 for (int m = 0; m < 9; ++m) { Pm[m] = pq[m]; Qm[m] = pq[9 + m]; }
@@ -692,7 +609,7 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
                 for (int m = 0; m < 6; ++m) v[m] = vp[(size_t)j * 6 + m];
                 pg_J(Pm, Qm, v, t2);
 #pragma unroll
-                for (int m = 0; m < 6; ++m) { const double w = ws[(size_t)e * 6 + m]; te[(size_t)e * 12 + m] = w * t2[m]; te[(size_t)e * 12 + 6 + m] = w * t1[m]; }
+                for (int m = 0; m < 6; ++m) { const double w = ed.w[(size_t)e * 6 + m]; te[(size_t)e * 12 + m] = w * t2[m]; te[(size_t)e * 12 + 6 + m] = w * t1[m]; }
             }
             __syncthreads();
             // keyframes: y_k = (H_kk + lambda D_k) p_k - sum c_q + sum J_side' te, and the block sums of p.y
@@ -715,7 +632,7 @@ __global__ __launch_bounds__(T) void full_ba_kernel(FbaArgs a) {
                     }
                     for (int q = estart[k]; q < estart[k + 1]; ++q) {
                         const int e = einc[q] >> 1, side = einc[q] & 1;
-                        const double* pq = PQ + (size_t)e * 36 + side * 18;
+                        const double* pq = ed.PQ + (size_t)e * 36 + side * 18;
                         double Pm[9], Qm[9], t[6], o6[6];
 #pragma unroll
                         for (int m = 0; m < 9; ++m) { Pm[m] = pq[m]; Qm[m] = pq[9 + m]; }

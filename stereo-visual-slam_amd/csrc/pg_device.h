@@ -1,6 +1,7 @@
 // pg_device.h -- device helpers shared by the persistent-workgroup solvers (posegraph_kernels.hip, fullba_kernels.hip): the deterministic sums
 // (an xor butterfly per aligned block of 64 indices, block sums added in ascending order), the pose-pose edge residual and its Jacobian factors
-// (include/vslam_hip.h "pose-graph optimisation"), and the 6 x 6 inverses.
+// (include/vslam_hip.h "pose-graph optimisation"), and the 6 x 6 inverses.  What one lane computes is here; the phases a whole workgroup runs with
+// them (checks, scans, edge cost, PCG and LM drivers) are in pg_solver.h.
 #pragma once
 #include "se3_device.h"
 #include "vslam_internal.h"

@@ -3,6 +3,7 @@
 // One persistent workgroup of 256 lanes per graph runs every Levenberg-Marquardt iteration of its graph: linearise the edges, build the gradient and
 // the diagonal blocks, solve (H + lambda diag(H)) delta = -g by preconditioned conjugate gradients that never form H (edge phase t_e = W (J_i p_i +
 // J_j p_j), node phase y_n = sum J' t_e + lambda D p_n), try the step, accept or reject.  No grid-wide synchronisation, no host round trip.
+// The set-up phases and the edge cost pass this solver shares with full BA are in pg_solver.h.
 //
 // A Jacobian A Ad(T) has the block form [[P, Q], [0, P]] (A = [[a, b], [0, a]], Ad = [[R, t^R], [0, R]]), so an edge stores 4 x 9 doubles, not 2 x 36.
 //
@@ -16,7 +17,7 @@
 // arithmetic of a step depends on the step before it).
 #include <algorithm>
 
-#include "pg_device.h"
+#include "pg_solver.h"
 #include "se3_device.h"
 #include "vslam_internal.h"
 
@@ -52,29 +53,23 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
     __shared__ int sh_scan[T];
     __shared__ int sh_cnt[4];   // free nodes, edges off the chain, singular flag, spare
 
-    // ---- the graph's ranges: in range, in order, and disjoint from every other graph's (so that a bad neighbour cannot alias this one)
+    // ---- the graph's ranges
     const int G = a.g.n_graphs;
     const int n0 = a.g.d_node_off[g], n1 = a.g.d_node_off[g + 1], e0 = a.g.d_edge_off[g], e1 = a.g.d_edge_off[g + 1];
-    int ok = n0 >= 0 && n1 >= n0 && n1 <= a.g.total_nodes && e0 >= 0 && e1 >= e0 && e1 <= a.g.total_edges;
-    for (int k = tid; k <= G; k += T) {
-        const int no = a.g.d_node_off[k], eo = a.g.d_edge_off[k];
-        if (k <= g ? (no > n0 || eo > e0) : (no < n1 || eo < e1)) ok = 0;
-    }
-    ok = __syncthreads_and(ok);
+    const int ok = __syncthreads_and(pg_own_range<T>(a.g.d_node_off, G, g, a.g.total_nodes, tid) & pg_own_range<T>(a.g.d_edge_off, G, g, a.g.total_edges, tid));
     vslam_pose_graph_stats st;
     st.chi2_init = st.chi2_final = 0; st.lambda = a.p.lambda_init; st.lm_iters = st.pcg_iters = st.n_free = 0; st.status = 0;
     if (!ok) {
         st.status = VSLAM_PG_BAD_INDEX;
-        if (tid == 0) { s.status[g] = st.status; if (a.stats) a.stats[g] = st; }
+        pg_write_stats(st, s.status, a.stats, g, tid);
         return;
     }
     const int N = n1 - n0, E = e1 - e0;
-    const int32_t* ei = a.g.d_edge_i + e0; const int32_t* ej = a.g.d_edge_j + e0;
-    const double* Zs = a.g.d_edge_Z + (size_t)e0 * 7; const double* ws = a.g.d_edge_w + (size_t)e0 * 6;
-    const uint8_t* act = a.g.d_edge_active ? a.g.d_edge_active + e0 : nullptr;
+    const PgEdges ed = {E, a.g.d_edge_i + e0, a.g.d_edge_j + e0, a.g.d_edge_Z + (size_t)e0 * 7, a.g.d_edge_w + (size_t)e0 * 6,
+                        a.g.d_edge_active ? a.g.d_edge_active + e0 : nullptr, s.PQ + (size_t)e0 * 36, s.res + (size_t)e0 * 6};
     const double* Tin = a.g.d_T + (size_t)n0 * 7;
     double* To = a.T_out + (size_t)n0 * 7;
-    double* PQ = s.PQ + (size_t)e0 * 36; double* res = s.res + (size_t)e0 * 6; double* te = s.te + (size_t)e0 * 6;
+    double* te = s.te + (size_t)e0 * 6;
     double* Hd = s.H + (size_t)n0 * 36; double* Od = s.O + (size_t)n0 * 36; double* Fd = s.F + (size_t)n0 * 36; double* Wd = s.W + (size_t)n0 * 36;
     double* vb = s.b + (size_t)n0 * 6; double* vx = s.x + (size_t)n0 * 6; double* vr = s.r + (size_t)n0 * 6; double* vz = s.z + (size_t)n0 * 6;
     double* vp = s.p + (size_t)n0 * 6; double* vy = s.y + (size_t)n0 * 6; double* vu = s.u + (size_t)n0 * 6; double* vD = s.D + (size_t)n0 * 6;
@@ -82,28 +77,17 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
     int32_t* held = s.held + n0; int32_t* start = s.start + n0 + g; int32_t* cursor = s.cursor + n0; int32_t* inc = s.inc + (size_t)e0 * 2;
     double* part0 = s.part0 + (n0 >> 6) + g; double* part1 = s.part1 + (n0 >> 6) + g; double* part2 = s.part2 + (n0 >> 6) + g;
     double* parte = s.parte + (e0 >> 6) + g;
-    const int Nr = (N + 63) & ~63, Er = (E + 63) & ~63;
+    const int Nr = (N + 63) & ~63;
 
-    // ---- the caller's ids and values
+    // ---- the caller's ids and values; poses are copied through
     int bad = 0, nonfinite = 0;
-    for (int e = tid; e < E; e += T) {
-        const int i = ei[e], j = ej[e];
-        if (i < 0 || i >= N || j < 0 || j >= N || i == j) bad = 1;
-        for (int q = 0; q < 7; ++q) if (!pg_finite(Zs[(size_t)e * 7 + q])) nonfinite = 1;
-        for (int q = 0; q < 6; ++q) { const double w = ws[(size_t)e * 6 + q]; if (!pg_finite(w) || w < 0) nonfinite = 1; }
-    }
-    for (int k = tid; k < N; k += T) {
-        for (int q = 0; q < 7; ++q) {
-            const double v = Tin[(size_t)k * 7 + q];
-            if (!pg_finite(v)) nonfinite = 1;
-            To[(size_t)k * 7 + q] = v;   // (the same lane owns node k in every node loop below)
-        }
-    }
+    pg_check_edges<T>(ed, N, tid, bad, nonfinite);
+    pg_copy_poses<T>(Tin, To, N, tid, nonfinite);
     bad = __syncthreads_or(bad);
     nonfinite = __syncthreads_or(nonfinite);
     if (bad || nonfinite) {
         st.status = (bad ? VSLAM_PG_BAD_INDEX : 0) | (nonfinite ? VSLAM_PG_NONFINITE : 0);
-        if (tid == 0) { s.status[g] = st.status; if (a.stats) a.stats[g] = st; }
+        pg_write_stats(st, s.status, a.stats, g, tid);
         return;
     }
 
@@ -114,46 +98,24 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
     {
         int off_chain = 0;
         for (int e = tid; e < E; e += T) {
-            if (act && !act[e]) continue;
-            atomicAdd(&cursor[ei[e]], 1); atomicAdd(&cursor[ej[e]], 1);
-            const int d = ei[e] - ej[e];
+            if (!ed.on(e)) continue;
+            atomicAdd(&cursor[ed.i[e]], 1); atomicAdd(&cursor[ed.j[e]], 1);
+            const int d = ed.i[e] - ed.j[e];
             off_chain += (d != 1 && d != -1);
         }
         if (off_chain) atomicAdd(&sh_cnt[1], off_chain);
     }
     __syncthreads();
-    {
-        const int chunk = (N + T - 1) / T, k0 = min(N, tid * chunk), k1 = min(N, k0 + chunk);
-        int sum = 0, nfree = 0;
-        for (int k = k0; k < k1; ++k) {
-            const int d = cursor[k];
-            if (d == 0) held[k] = 1;
-            nfree += !held[k];
-            sum += d;
-        }
-        sh_scan[tid] = sum;
-        if (nfree) atomicAdd(&sh_cnt[0], nfree);
-        __syncthreads();
-        int base = 0;
-        for (int t = 0; t < tid; ++t) base += sh_scan[t];
-        for (int k = k0; k < k1; ++k) { const int d = cursor[k]; start[k] = base; cursor[k] = base; base += d; }
-        if (tid == T - 1) start[N] = base;
-    }
-    __syncthreads();
+    pg_hold_isolated<T>(held, N, tid, &sh_cnt[0], [&](int k) { return cursor[k] == 0; });
+    pg_counts_to_offsets<T>(cursor, start, N, sh_scan, tid);
     for (int e = tid; e < E; e += T) {
-        if (act && !act[e]) continue;
-        inc[atomicAdd(&cursor[ei[e]], 1)] = 2 * e;
-        inc[atomicAdd(&cursor[ej[e]], 1)] = 2 * e + 1;
+        if (!ed.on(e)) continue;
+        inc[atomicAdd(&cursor[ed.i[e]], 1)] = 2 * e;
+        inc[atomicAdd(&cursor[ed.j[e]], 1)] = 2 * e + 1;
     }
     __syncthreads();
+    pg_sort_lists_by_lane<T>(start, inc, N, tid);
     for (int k = tid; k < N; k += T) {
-        const int b0 = start[k], b1 = start[k + 1];
-        for (int q = b0 + 1; q < b1; ++q) {   // insertion sort: the lists are short
-            const int v = inc[q];
-            int m = q - 1;
-            while (m >= b0 && inc[m] > v) { inc[m + 1] = inc[m]; --m; }
-            inc[m + 1] = v;
-        }
         for (int q = 0; q < 6; ++q) {
             const size_t o = (size_t)k * 6 + q;
             vb[o] = vx[o] = vr[o] = vz[o] = vp[o] = vy[o] = vu[o] = vD[o] = 0.0;
@@ -168,41 +130,7 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
 
     // the cost of the active edges at poses Tp; with `lin` the residuals and Jacobians are kept for the solver
     auto cost_of = [&](const double* Tp, bool lin) -> double {
-        for (int e = tid; e < Er; e += T) {
-            double c = 0;
-            if (e < E && !(act && !act[e])) {
-                const int i = ei[e], j = ej[e];
-                double Ti[7], Tj[7], Z[7], w[6], r[6], Ee[7], Zi[7];
-#pragma unroll
-                for (int q = 0; q < 7; ++q) { Ti[q] = Tp[(size_t)i * 7 + q]; Tj[q] = Tp[(size_t)j * 7 + q]; Z[q] = Zs[(size_t)e * 7 + q]; }
-#pragma unroll
-                for (int q = 0; q < 6; ++q) w[q] = ws[(size_t)e * 6 + q];
-                pg_residual(Ti, Tj, Z, r, Ee, Zi);
-                c = pg_chi2(r, w);
-                if (lin) {
-                    double Om[9], U[9], Om2[9], OU[9], UO[9], am[9], bm[9], P[9], Q[9];
-                    pg_hat(r + 3, Om); pg_hat(r, U);
-                    pg_mm3(Om, Om, Om2); pg_mm3(Om, U, OU); pg_mm3(U, Om, UO);
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) {
-                        am[q] = -0.5 * Om[q] + Om2[q] * (1.0 / 12.0);
-                        bm[q] = -0.5 * U[q] + (OU[q] + UO[q]) * (1.0 / 12.0);
-                    }
-                    am[0] += 1.0; am[4] += 1.0; am[8] += 1.0;
-                    double* pq = PQ + (size_t)e * 36;
-                    pg_jac(am, bm, Zi, 1.0, P, Q);
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) { pq[q] = P[q]; pq[9 + q] = Q[q]; }
-                    pg_jac(am, bm, Ee, -1.0, P, Q);
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) { pq[18 + q] = P[q]; pq[27 + q] = Q[q]; }
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) res[(size_t)e * 6 + q] = r[q];
-                }
-            }
-            c = pg_wave_sum(c);
-            if (lane == 0) parte[e >> 6] = c;
-        }
+        pg_edge_cost_pass<T>(ed, Tp, lin, parte, tid);
         __syncthreads();
         const double total = pg_sum_parts(parte, E);
         __syncthreads();   // (parte is free again)
@@ -231,17 +159,17 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
                     const bool next_free = k + 1 < N && !held[k + 1];
                     for (int q = start[k]; q < start[k + 1]; ++q) {
                         const int e = inc[q] >> 1, side = inc[q] & 1;
-                        const double* pq = PQ + (size_t)e * 36;
+                        const double* pq = ed.PQ + (size_t)e * 36;
                         double Pa[9], Qa[9], w[6], wr[6], o[6];
 #pragma unroll
                         for (int m = 0; m < 9; ++m) { Pa[m] = pq[side * 18 + m]; Qa[m] = pq[side * 18 + 9 + m]; }
 #pragma unroll
-                        for (int m = 0; m < 6; ++m) { w[m] = ws[(size_t)e * 6 + m]; wr[m] = w[m] * res[(size_t)e * 6 + m]; }
+                        for (int m = 0; m < 6; ++m) { w[m] = ed.w[(size_t)e * 6 + m]; wr[m] = w[m] * ed.res[(size_t)e * 6 + m]; }
                         pg_JT(Pa, Qa, wr, o);
 #pragma unroll
                         for (int m = 0; m < 6; ++m) bk[m] -= o[m];
                         pg_JtWJ(Pa, Qa, Pa, Qa, w, Hk);
-                        const int other = side ? ei[e] : ej[e];
+                        const int other = side ? ed.i[e] : ed.j[e];
                         if (next_free && other == k + 1) {
                             double Pb[9], Qb[9];
 #pragma unroll
@@ -430,9 +358,9 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
             if (cg >= a.p.pcg_max_iters) { status |= VSLAM_PG_PCG_CAP; break; }
             // edge phase: t_e = W (J_i p_i + J_j p_j)
             for (int e = tid; e < E; e += T) {
-                if (act && !act[e]) continue;
-                const int i = ei[e], j = ej[e];
-                const double* pq = PQ + (size_t)e * 36;
+                if (!ed.on(e)) continue;
+                const int i = ed.i[e], j = ed.j[e];
+                const double* pq = ed.PQ + (size_t)e * 36;
                 double Pm[9], Qm[9], v[6], t1[6], t2[6];
 #pragma unroll
                 for (int m = 0; m < 9; ++m) { Pm[m] = pq[m]; Qm[m] = pq[9 + m]; }
@@ -445,7 +373,7 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
                 for (int m = 0; m < 6; ++m) v[m] = vp[(size_t)j * 6 + m];
                 pg_J(Pm, Qm, v, t2);
 #pragma unroll
-                for (int m = 0; m < 6; ++m) te[(size_t)e * 6 + m] = ws[(size_t)e * 6 + m] * (t1[m] + t2[m]);
+                for (int m = 0; m < 6; ++m) te[(size_t)e * 6 + m] = ed.w[(size_t)e * 6 + m] * (t1[m] + t2[m]);
             }
             __syncthreads();
             // node phase: y_n = sum J' t_e + lambda D p_n, and the block sums of p.y
@@ -457,7 +385,7 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
                     for (int q = 0; q < 6; ++q) yk[q] = lambda * vD[(size_t)k * 6 + q] * vp[(size_t)k * 6 + q];
                     for (int q = start[k]; q < start[k + 1]; ++q) {
                         const int e = inc[q] >> 1, side = inc[q] & 1;
-                        const double* pq = PQ + (size_t)e * 36 + side * 18;
+                        const double* pq = ed.PQ + (size_t)e * 36 + side * 18;
                         double Pm[9], Qm[9], t[6], o[6];
 #pragma unroll
                         for (int m = 0; m < 9; ++m) { Pm[m] = pq[m]; Qm[m] = pq[9 + m]; }
@@ -499,6 +427,7 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
             __syncthreads();
         }
         st.pcg_iters += cg;
+        __syncthreads();   // (a lane that left the loop early has read its block sums)
 
         // ---- the candidate T' = exp(x) T and |x|
         for (int k = tid; k < Nr; k += T) {
@@ -546,12 +475,12 @@ __global__ __launch_bounds__(kPgThreads) void pose_graph_kernel(PgArgs a) {
     // ---- per-edge chi2 of every edge at the output poses
     if (a.g.d_edge_chi2) {
         for (int e = tid; e < E; e += T) {
-            const int i = ei[e], j = ej[e];
+            const int i = ed.i[e], j = ed.j[e];
             double Ti[7], Tj[7], Z[7], w[6], r[6], Ee[7], Zi[7];
 #pragma unroll
-            for (int q = 0; q < 7; ++q) { Ti[q] = To[(size_t)i * 7 + q]; Tj[q] = To[(size_t)j * 7 + q]; Z[q] = Zs[(size_t)e * 7 + q]; }
+            for (int q = 0; q < 7; ++q) { Ti[q] = To[(size_t)i * 7 + q]; Tj[q] = To[(size_t)j * 7 + q]; Z[q] = ed.Z[(size_t)e * 7 + q]; }
 #pragma unroll
-            for (int q = 0; q < 6; ++q) w[q] = ws[(size_t)e * 6 + q];
+            for (int q = 0; q < 6; ++q) w[q] = ed.w[(size_t)e * 6 + q];
             pg_residual(Ti, Tj, Z, r, Ee, Zi);
             a.g.d_edge_chi2[e0 + e] = pg_chi2(r, w);
         }
