@@ -10,7 +10,8 @@ departures from "3 - 8 keyframes per landmark", each forced by the case guard of
   * N = 65 with M <= 65: at 3 - 8 keyframes per landmark a keyframe would see five landmarks on average and some fewer than three; the run length
     is raised until a keyframe sees twelve on average (RUN_TARGET).
 TRIMMED cases cut a problem to an exact observation count on both sides of 256 (the kernel's workgroup width: where a lane-strided loop takes its
-second trip) and of 512 (its third)."""
+second trip) and of 512 (its third).
+input_cases() varies what a problem may say besides its size: held keyframes, the observation mask, and the mask, weights and direction of edges."""
 import functools
 
 import numpy as np
@@ -211,6 +212,93 @@ def reference(name):
         if isinstance(v, np.ndarray):
             v.setflags(write=False)
     return p, ref
+
+
+# ------------------------------------------------------------------------------------------ the input space: masks, held keyframes, edge weights, directions
+OBS_MASK = dict(kf_off=5, lm_off=20, lm_behind=7)
+
+
+def _obs_mask_case():
+    """arc(12, 63) under an observation mask: keyframe kf_off and landmark lm_off have every observation off (both are then held / copied through);
+    holes at the first, a middle and the last position of other landmarks' ranges, four of each, taken only where the landmark keeps three active
+    observations of which one is stereo (a landmark left with mono views only has no unique minimum); landmark lm_behind stands behind its observers
+    at the input, as in degenerate(), and one of its observations is masked off too, so that n_obs_dropped counts the others only."""
+    p = arc(12, 63)
+    kf, lm = p["kf"], p["lm"]
+    O = len(kf)
+    stereo = R.stereo_mask(p)
+    act = np.ones(O, bool)
+    act[kf == OBS_MASK["kf_off"]] = False
+    act[lm == OBS_MASK["lm_off"]] = False
+    o7 = np.nonzero(lm == OBS_MASK["lm_behind"])[0]
+    X = p["X"].copy()
+    Tk = PG.inverse(p["T"][kf[o7[0]]])
+    X[OBS_MASK["lm_behind"]] = PG.rotmat(Tk) @ np.array([0.3, 0.1, -4.0]) + Tk[4:]
+    act[o7[len(o7) // 2]] = False
+    holes = {"first": [], "middle": [], "last": []}
+    for l in range(len(X)):
+        kind = min(holes, key=lambda k: len(holes[k]))
+        o = np.nonzero(lm == l)[0]
+        if l in (OBS_MASK["lm_off"], OBS_MASK["lm_behind"]) or len(holes[kind]) >= 4:
+            continue
+        at = {"first": o[0], "middle": o[len(o) // 2], "last": o[-1]}[kind]
+        rest = o[(o != at) & act[o]]
+        if act[at] and len(rest) >= 3 and stereo[rest].any():
+            act[at] = False
+            holes[kind].append(int(at))
+    assert all(len(v) == 4 for v in holes.values())
+    return dict(p, X=X, obs_active=act.astype(np.uint8)), holes
+
+
+def reverse_edges(p, which):
+    """a copy whose edges `which` (indices) are stored the other way round, (j, i, Z^-1)"""
+    ei, ej, Z = p["ei"].copy(), p["ej"].copy(), p["Z"].copy()
+    ei[which], ej[which] = p["ej"][which], p["ei"][which]
+    Z[which] = PG.inverse(p["Z"][which])
+    return dict(p, ei=ei, ej=ej, Z=Z)
+
+
+def held(N, kfs):
+    f = np.zeros(N, np.uint8); f[list(kfs)] = 1
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def input_cases():
+    """{name: problem} of the cases that vary what parity_cases() leaves alone: which keyframes are held, the observation mask, and on the edges of
+    ring_5 the mask, weights per edge and axis, and the direction"""
+    a, r5 = arc(12, 63), ring(L=5)
+    rng = np.random.default_rng(2121)
+    out = {}
+    out["held_01"] = dict(a, fixed=held(12, [0, 1]))
+    out["held_mid"] = dict(a, fixed=held(12, [6]))          # keyframe 0 is free
+    out["obs_mask"] = _obs_mask_case()[0]
+    out["edge_mask"] = dict(r5, edge_active=np.array([1, 0, 1, 0, 1], np.uint8))
+    out["edge_weights"] = dict(r5, w=r5["w"] * np.exp(rng.uniform(np.log(0.2), np.log(5.0), (5, 6))))
+    out["edge_reversed"] = reverse_edges(r5, [0, 2])
+    for p in out.values():
+        for v in p.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+    return out
+
+
+INPUT_NAMES = ["held_01", "held_mid", "obs_mask", "edge_mask", "edge_weights", "edge_reversed"]
+
+
+@functools.lru_cache(maxsize=None)
+def input_reference(name):
+    """(problem, the yardstick's converged result): computed once, shared by the CPU guard and the GPU tests, never modified"""
+    p = input_cases()[name]
+    ref = R.solve(p, **CONVERGED)
+    ref["T"].setflags(write=False); ref["X"].setflags(write=False)
+    return p, ref
+
+
+def seen_landmarks(p):
+    """the landmarks with an active observation in the call: the others are copied through"""
+    seen = np.zeros(len(p["X"]), bool); seen[p["lm"][R.input_active(p)[0]]] = True
+    return seen
 
 
 def gradient_norm(p, T, X):

@@ -1,5 +1,6 @@
 """Seeded pose graphs for the pose-graph tests: rings with drift and loop edges, and the degenerate graphs the entry must take as results.
-A graph is dict(T (N, 7), ei, ej (E), Z (E, 7), w (E, 6), fixed (N uint8 or None), active (E uint8 or None)); pack() lays several back to back."""
+A graph is dict(T (N, 7), ei, ej (E), Z (E, 7), w (E, 6), fixed (N uint8 or None), active (E uint8 or None)); pack() lays several back to back.
+The rings vary the size; input_cases() varies what a graph may say besides: held nodes, the mask, weights, edge direction and order, quaternion signs."""
 import functools
 
 import numpy as np
@@ -100,3 +101,128 @@ def ring_reference(N, L):
 
 def gradient_norm(g, T):
     return float(np.linalg.norm(R.cost_and_gradient(T, g["ei"], g["ej"], g["Z"], g["w"], g["fixed"], g["active"])[1]))
+
+
+# ------------------------------------------------------------------------------------------ the input space: masks, held nodes, weights, directions
+def held(N, nodes):
+    f = np.zeros(N, np.uint8); f[list(nodes)] = 1
+    return f
+
+
+def reverse_edges(g, which):
+    """a copy whose edges `which` (a mask over the edges) are stored the other way round, (j, i, Z^-1): the same measurement"""
+    which = np.asarray(which, bool)
+    ei, ej, Z = g["ei"].copy(), g["ej"].copy(), g["Z"].copy()
+    ei[which], ej[which] = g["ej"][which], g["ei"][which]
+    Z[which] = R.inverse(g["Z"][which])
+    return dict(g, ei=ei, ej=ej, Z=Z)
+
+
+def swap_ends(g, which):
+    """what a reader that ignores the direction makes of it: the edges `which` with i and j exchanged and Z as it stands"""
+    which = np.asarray(which, bool)
+    ei, ej = g["ei"].copy(), g["ej"].copy()
+    ei[which], ej[which] = g["ej"][which], g["ei"][which]
+    return dict(g, ei=ei, ej=ej)
+
+
+def swap_weight_columns(g):
+    """what a reader that takes the information as [omega; upsilon] makes of it"""
+    return dict(g, w=np.concatenate([g["w"][:, 3:], g["w"][:, :3]], -1))
+
+
+def without_edges_at(g, node):
+    """a copy with every edge at `node` switched off through the mask (the node is then held)"""
+    act = R._active(len(g["ei"]), g["active"]) & (g["ei"] != node) & (g["ej"] != node)
+    return dict(g, active=act.astype(np.uint8))
+
+
+def flip_quaternions(g, seed):
+    """-q on about half of the poses and half of the measurements: the same rotations on the other sheet of the double cover"""
+    rng = np.random.default_rng(seed)
+    T, Z = g["T"].copy(), g["Z"].copy()
+    nt, nz = rng.random(len(T)) < 0.5, rng.random(len(Z)) < 0.5
+    nt[1], nz[0] = True, True
+    T[nt, :4] *= -1.0; Z[nz, :4] *= -1.0
+    return dict(g, T=T, Z=Z)
+
+
+ZERO_WEIGHT_NODE = 6
+
+
+@functools.lru_cache(maxsize=None)
+def input_cases():
+    """{name: graph} of the cases that vary what the rings leave alone: which nodes are held, the edge mask, weights per edge and component, the
+    direction and order of the edges, the sign of the quaternions, the size of the residuals.  Every one is well posed but zero_weight_node, whose
+    node ZERO_WEIGHT_NODE is free yet has no information (the library's VSLAM_PG_SINGULAR); input_reference() says what it is compared with."""
+    base = ring(12, 5)
+    E = len(base["ei"])
+    rng = np.random.default_rng(4242)
+    out = {}
+    out["gauge_mid"] = dict(base, fixed=held(12, [6]))                     # node 0 is free
+    out["gauge_three"] = dict(ring(65, 5), fixed=held(65, [0, 31, 64]))    # held nodes in mid-chain and at its end
+    out["weights"] = dict(base, w=np.exp(rng.uniform(np.log(0.25), np.log(400.0), (E, 6))))
+    rev = rng.random(E) < 0.5
+    rev[[0, 3, 11]] = True; rev[[1, 12]] = False                           # (chain and loop edges on both sides, whatever the draw)
+    out["reversed"] = reverse_edges(base, rev)
+    # 65-node ring with one loop edge, 40 more edges at node 0, node 64 held, the edges in random order
+    hub = ring(65, 1)
+    hq = np.sort(rng.choice(np.arange(2, 65), 40, replace=False))
+    Zh = R.mul(_noise(rng, 40, 0.004, 0.002), R.mul(hub["T_true"][hq], R.inverse(hub["T_true"][np.zeros(40, np.int64)])))
+    hub = dict(hub, ei=np.concatenate([hub["ei"], hq]).astype(np.int32), ej=np.concatenate([hub["ej"], np.zeros(40)]).astype(np.int32),
+               Z=np.concatenate([hub["Z"], Zh]), w=np.concatenate([hub["w"], np.ones((40, 6))]), fixed=held(65, [64]))
+    order = rng.permutation(len(hub["ei"]))
+    out["shuffled_hub"] = dict(hub, ei=hub["ei"][order], ej=hub["ej"][order], Z=hub["Z"][order], w=hub["w"][order])
+    out["quat_signs"] = flip_quaternions(base, 17)
+    w = base["w"].copy(); w[11:, 3:] = 0.0                                  # the loop edges measure no rotation; the chain keeps the graph well posed
+    out["partial_zero_w"] = dict(base, w=w)
+    act = np.ones(E, np.uint8); act[[4, 11, 15]] = 0                        # chain edge (5, 4) and two loop edges; loop edge (7, 0) spans the break
+    out["masked"] = dict(base, active=act)
+    out["large_residuals"] = ring(12, 5, s_t=0.1, s_r=0.15)
+    # one loop edge on 130 nodes, every second chain edge stored the other way round: the chain preconditioner must still see them all
+    lc = ring(130, 1)
+    every_second = np.zeros(len(lc["ei"]), bool); every_second[0:129:2] = True
+    out["long_chain_reversed"] = reverse_edges(lc, every_second)
+    w = base["w"].copy(); w[(base["ei"] == ZERO_WEIGHT_NODE) | (base["ej"] == ZERO_WEIGHT_NODE)] = 0.0
+    out["zero_weight_node"] = dict(base, w=w)
+    for g in out.values():
+        for v in g.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+    return out
+
+
+WELL_POSED_INPUT_NAMES = ["gauge_mid", "gauge_three", "weights", "reversed", "shuffled_hub", "quat_signs", "partial_zero_w", "masked", "large_residuals",
+                          "long_chain_reversed"]
+INPUT_NAMES = WELL_POSED_INPUT_NAMES + ["zero_weight_node"]
+
+
+def yardstick_graph(name):
+    """the graph the yardstick solves for a case: the case itself, but for zero_weight_node the graph without that node's edges (a singular H has no
+    dense solve; the library leaves the node where it is, which is what holding it does)"""
+    g = input_cases()[name]
+    return without_edges_at(g, ZERO_WEIGHT_NODE) if name == "zero_weight_node" else g
+
+
+@functools.lru_cache(maxsize=None)
+def input_reference(name):
+    """(graph, the yardstick's converged result on yardstick_graph(name)): computed once, shared by the CPU guard and the GPU tests, never modified"""
+    g, y = input_cases()[name], yardstick_graph(name)
+    ref = R.solve(y["T"], y["ei"], y["ej"], y["Z"], y["w"], y["fixed"], y["active"], **CONVERGED)
+    ref["T"].setflags(write=False)
+    return g, ref
+
+
+@functools.lru_cache(maxsize=None)
+def chain_counts():
+    """(c0, c1): the yardstick's PCG iteration totals on long_chain_reversed at the library's defaults, under block-Jacobi and under the chain"""
+    g = input_cases()["long_chain_reversed"]
+    return tuple(solve_case(g, mode="pcg", precond=p)["pcg_iters"] for p in (0, 1))
+
+
+def solve_case(g, **kw):
+    return R.solve(g["T"], g["ei"], g["ej"], g["Z"], g["w"], g["fixed"], g["active"], **kw)
+
+
+def held_of(g):
+    return R.held_nodes(len(g["T"]), g["ei"], g["ej"], g["fixed"], R._active(len(g["ei"]), g["active"]))

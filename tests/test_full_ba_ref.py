@@ -123,6 +123,86 @@ def test_the_inputs_matter():
     assert far(R.solve(Cs.without(p, disp=None), **Cs.CONVERGED), ref)
 
 
+@pytest.mark.parametrize("name", Cs.INPUT_NAMES)
+def test_input_case_guard(name):
+    """every input case (tests/test_gpu_full_ba_inputs.py), the yardstick alone, with the margins of test_case_guard.  What the case holds by
+    construction -- held keyframes, landmarks without an active observation -- is compared with the input: perturbed() moves the start of such a
+    landmark, so the difference between the two starts means nothing there."""
+    p, ref = Cs.input_reference(name)
+    hold, seen = R.held_keyframes(p), Cs.seen_landmarks(p)
+    two = R.solve(Cs.perturbed(p, seed=7), **Cs.CONVERGED)
+    pcg = R.solve(p, mode="pcg")
+    g0 = Cs.gradient_norm(p, p["T"], p["X"])
+    gn = Cs.gradient_norm(p, pcg["T"], pcg["X"])
+    print("%s: %d free keyframes, %d landmarks seen, %d observations dropped; two starts %.2e apart; pcg mode %.2e from converged, gradient %.2e of initial, %d LM / %d PCG iterations"
+          % (name, ref["n_free"], seen.sum(), ref["n_obs_dropped"], max(np.abs(two["T"] - ref["T"]).max(), np.abs(two["X"] - ref["X"])[seen].max()),
+             max(np.abs(pcg["T"] - ref["T"]).max(), np.abs(pcg["X"] - ref["X"]).max()), gn / g0, pcg["lm_iters"], pcg["pcg_iters"]))
+    for r in (ref, pcg):
+        assert np.array_equal(r["T"][hold], p["T"][hold]) and np.array_equal(r["X"][~seen], p["X"][~seen])
+    assert ref["n_free"] == int((~hold).sum())
+    assert _within_a_tenth(dict(T=two["T"], X=two["X"][seen]), dict(T=ref["T"], X=ref["X"][seen]))
+    assert _within_a_tenth(pcg, ref)
+    dropped = R.FBA_DROPPED if name == "obs_mask" else 0
+    assert gn <= 1e-7 * g0 and pcg["status"] == dropped and ref["status"] == dropped
+    assert pcg["chi2_final"] < pcg["chi2_init"]
+    assert pcg["pcg_iters"] < R.DEFAULTS["pcg_max_iters"] and pcg["lm_iters"] < R.DEFAULTS["max_iters"]
+
+
+def test_the_observation_mask_has_every_kind_of_hole():
+    p, holes = Cs._obs_mask_case()
+    on = np.asarray(p["obs_active"], bool)
+    lm, kf = p["lm"], p["kf"]
+    first = np.concatenate([[True], lm[1:] != lm[:-1]]); last = np.concatenate([lm[1:] != lm[:-1], [True]])
+    assert all(first[o] and not on[o] for o in holes["first"]) and all(last[o] and not on[o] for o in holes["last"])
+    assert all(not first[o] and not last[o] and not on[o] for o in holes["middle"]) and all(len(v) == 4 for v in holes.values())
+    assert not on[kf == Cs.OBS_MASK["kf_off"]].any() and (kf == Cs.OBS_MASK["kf_off"]).sum() > 10
+    assert not on[lm == Cs.OBS_MASK["lm_off"]].any() and (lm == Cs.OBS_MASK["lm_off"]).sum() >= 3
+    # behind the camera: the observations of that landmark which the mask left on, and no others
+    behind = R.camera_points(p["T"], p["X"], p)[:, 2] <= 0
+    assert np.array_equal(np.unique(lm[behind]), [Cs.OBS_MASK["lm_behind"]]) and (behind & ~on).sum() >= 1
+    act, dropped = R.input_active(p)
+    assert dropped == (behind & on).sum() >= 2 and dropped < behind.sum()
+    seen = Cs.seen_landmarks(p)
+    assert list(np.nonzero(~seen)[0]) == sorted([Cs.OBS_MASK["lm_behind"], Cs.OBS_MASK["lm_off"]])
+    assert list(np.nonzero(R.held_keyframes(p))[0]) == [0, Cs.OBS_MASK["kf_off"]]
+
+
+def test_the_input_cases_matter():
+    """For every input case the yardstick with that input IGNORED ends farther from the case's reference than the GPU parity tolerance, so a device
+    that ignored it could not pass tests/test_gpu_full_ba_inputs.py."""
+    far = lambda a, b: not (np.allclose(a["T"], b["T"], rtol=1e-4, atol=1e-6) and np.allclose(a["X"], b["X"], rtol=1e-4, atol=1e-6))
+    conv = lambda p: R.solve(p, **Cs.CONVERGED)
+    # fixed dropped: keyframe 1 moves
+    p, ref = Cs.input_reference("held_01")
+    r = conv(Cs.without(p, fixed=None))
+    assert far(r, ref) and not np.allclose(r["T"][1], p["T"][1], rtol=1e-4, atol=1e-6) and np.array_equal(ref["T"][:2], p["T"][:2])
+    # held_mid differs from the default by the gauge alone (T_k G, G^-1 X), so there the held keyframe carries the check: the reference leaves
+    # keyframe 6 at its input and moves keyframe 0, the run without `fixed` does the opposite
+    p, ref = Cs.input_reference("held_mid")
+    r = conv(Cs.without(p, fixed=None))
+    assert far(r, ref) and np.array_equal(ref["T"][6], p["T"][6]) and not np.allclose(ref["T"][0], p["T"][0], rtol=1e-4, atol=1e-6)
+    assert not np.allclose(r["T"][6], p["T"][6], rtol=1e-4, atol=1e-6)
+    G = PG.mul(PG.inverse(r["T"][6]), p["T"][6])
+    Gi = PG.inverse(G)
+    aligned = dict(T=PG.mul(r["T"], np.broadcast_to(G, r["T"].shape)), X=r["X"] @ PG.rotmat(Gi).T + Gi[4:])
+    assert np.allclose(aligned["T"], ref["T"], rtol=0, atol=1e-7) and np.allclose(aligned["X"], ref["X"], rtol=0, atol=1e-6)   # (the gauge and nothing else)
+    # the masks dropped
+    p, ref = Cs.input_reference("obs_mask")
+    assert far(conv(Cs.without(p, obs_active=None)), ref)
+    p, ref = Cs.input_reference("edge_mask")
+    assert far(conv(Cs.without(p, edge_active=None)), ref)
+    # the weight columns taken as [omega; upsilon]
+    p, ref = Cs.input_reference("edge_weights")
+    assert far(conv(Cs.without(p, w=np.concatenate([p["w"][:, 3:], p["w"][:, :3]], -1))), ref)
+    assert far(Cs.reference("ring_5")[1], ref)   # (and the weights are not the uniform ones)
+    # the direction of an edge ignored
+    p, ref = Cs.input_reference("edge_reversed")
+    assert far(conv(Cs.without(p, ei=p["ej"], ej=p["ei"])), ref)
+    swapped = Cs.without(p, ei=np.where([1, 0, 1, 0, 0], p["ej"], p["ei"]), ej=np.where([1, 0, 1, 0, 0], p["ei"], p["ej"]))
+    assert far(conv(swapped), ref)
+    assert set(Cs.INPUT_NAMES) == set(Cs.input_cases())
+
+
 def test_degenerate_problems_are_results():
     for name, (p, n_free, status, dropped) in Cs.degenerate().items():
         r = R.solve(p)
