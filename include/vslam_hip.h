@@ -1050,6 +1050,49 @@ int vslam_tsdf_mesh_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_
  * per block: it counts in n_dropped_range and nothing is written for it.  A block that finds no slot counts in n_dropped_full and sets status bit 0.
  * The ids of one call must be distinct (with duplicates, which copy stays is unspecified).  Asynchronous on the context stream. */
 int vslam_tsdf_load_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const int32_t* d_block_ids, const uint32_t* d_voxels, size_t n);
+/* RENDER.  What a camera at a given pose sees of the field: a depth image and, per pixel, the surface normal and intensity, ray-cast on the device.
+ * All arithmetic is f64 in the written order, no contraction, and every float is cast once at the end.  The call carries a camera fx, fy, cx, cy and
+ * an image size w, h of its own (not the context's: a caller renders at any scale), z_min < z_max, march and min_weight.  vs as above, hs = march * vs,
+ * K = the smallest non-negative integer with z_min + (double)K * hs >= z_max (the host computes it with exactly that expression), sample k of 0 .. K-1
+ * lies at Z_k = z_min + (double)k * hs.  A view v takes part when d_map_id[v] is in 0 .. 1022 and its pose is finite (ALLOCATION's test: the seven
+ * numbers, the rotation matrix, the inverse translation); every pixel of a view that does not take part is a miss.
+ *   The ray of pixel (c, r): x = ((double)c - cx) / fx, y = ((double)r - cy) / fy; like INTEGRATION's distance it is parametrised by the camera's z.
+ *   The sample at depth Z: P = (x * Z, y * Z, Z); Xw[a] = Rinv[3a] * P0 + Rinv[3a+1] * P1 + Rinv[3a+2] * P2 + tinv[a] with Rinv = the transposed rotation
+ *   matrix and tinv[a] = -(Rinv[3a] * t0 + Rinv[3a+1] * t1 + Rinv[3a+2] * t2) (vslam_reproject_dev's inverse pose); g[a] = Xw[a] / vs - 0.5,
+ *   i[a] = floor(g[a]), f[a] = g[a] - (double)i[a].  The sample is UNKNOWN unless every axis has -2^17 <= i[a] and i[a] + 1 < 2^17 and all eight voxels
+ *   i + (dx, dy, dz) of the view's map are good (EXTRACTION's predicate with the call's min_weight: a weight at 2^20 is not good, a min_weight below 1
+ *   counts as 1).  Otherwise, with lerp(a, b, t) = a + t * (b - a) and D(dx, dy, dz) EXTRACTION's D of the corner:
+ *     Dx[dy][dz] = lerp(D(0, dy, dz), D(1, dy, dz), f0);  Dy[dz] = lerp(Dx[0][dz], Dx[1][dz], f1);  D = lerp(Dy[0], Dy[1], f2)
+ *     gradient, the analytic one of that interpolant -- the corner differences along an axis, lerped over the other two axes in the order x, y, z:
+ *       gx = lerp(lerp(X00, X10, f1), lerp(X01, X11, f1), f2) with Xyz = D(1, y, z) - D(0, y, z)
+ *       gy = lerp(lerp(Y00, Y10, f0), lerp(Y01, Y11, f0), f2) with Yxz = D(x, 1, z) - D(x, 0, z)
+ *       gz = lerp(lerp(Z00, Z10, f0), lerp(Z01, Z11, f0), f1) with Zxy = D(x, y, 1) - D(x, y, 0)
+ *     intensity: D's trilinear form over the corners' (double)I / (double)Wc.
+ *   The march walks k = 0, 1, ... and keeps prev = "sample k-1 was known and had D > 0" with its D_prev.  An unknown sample clears prev; a known sample
+ *   with D > 0 sets it; the first known sample with D <= 0 ends the ray (an exact zero counts as not positive, as in the mesh): a HIT if prev is set,
+ *   otherwise a miss -- a back face, or a surface entered from unobserved space, is not rendered.  A ray that reaches K without ending is a miss.
+ *   Hit: s = D_prev / (D_prev - D);  Z* = (z_min + (double)(k - 1) * hs) + s * hs;  depth = (float)Z*.  The attributes come from one more sample at Z*,
+ *   or from sample k if that one is unknown: n = gradient / sqrt(gx * gx + gy * gy + gz * gz), in the world frame, pointing into free space as the surfel
+ *   normals do, (0, 0, 0) if the norm is zero or not finite; the intensity of the same sample.  Stored: (float)nx, (float)ny, (float)nz, (float)intensity.
+ *   Miss: the depth is 0.0f and the attributes are four 0.0f.
+ * Two forms, same bytes (vslam_set_tuning "tsdf_render_form"): 0 = every ray walks all K samples; 1 = a range kernel first projects a sphere around every
+ * claimed block onto the view's 16 x 16 pixel tiles and narrows each tile's walk to the samples that can be known.  d_counts, when given, receives the
+ * rays that hit and the samples the march evaluated (the second depends on the form; attribute samples are not counted). */
+struct vslam_tsdf_render_params {
+    int32_t struct_size;   /* sizeof(struct vslam_tsdf_render_params) of the caller's header: set by the caller, checked */
+    int32_t w, h;
+    double fx, fy, cx, cy, z_min, z_max, march;
+    int32_t min_weight, reserved;
+};
+/* V views of the map by the RENDER rule: d_T_c_w V x 7 poses, d_map_id V map ids (outside 0 .. 1022: the view is all misses), d_depth V x h x w floats,
+ * d_attr V x h x w x 4 floats of (nx, ny, nz, intensity), 16-byte aligned, or NULL, d_counts NULL or two uint64 (8-byte aligned).  Every pixel of every
+ * view is written, nothing beyond V * h * w (4 V h w) floats.  Asynchronous on the context stream; V == 0 is a no-op that succeeds; a call that needs
+ * larger view / range tables than the map holds (128 bytes per view, with form 1 eight more per view and tile; counted in vslam_device_bytes) grows them
+ * first, which synchronises the context stream.  VSLAM_ERR_ARG: a null map or a map of another context, a wrong struct_size, w or h below 1, V < 0,
+ * V * h * w >= 2^31, fx or fy not finite or <= 0, cx or cy not finite, z_min not finite or <= 0, z_max not finite or <= z_min, march not finite or
+ * outside [1/8, 1], K > 8192, a null d_T_c_w, d_map_id or d_depth with V > 0, a misaligned pointer. */
+int vslam_tsdf_render_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const struct vslam_tsdf_render_params* params, int V, const double* d_T_c_w,
+                          const int32_t* d_map_id, float* d_depth, float* d_attr, uint64_t* d_counts);
 
 /* ------------------------------------------------------------------ place database: loop-closure candidates and verified edges --- */
 /* Noticing that the camera is back at a place it has seen: keyframe descriptor blocks are kept in a database that outlives the steps (loops close

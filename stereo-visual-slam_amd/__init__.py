@@ -117,6 +117,12 @@ SURFEL_DTYPE = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("iz", "<i4"), ("axis", "
 SURFEL_MAP_DTYPE = np.dtype([("map", "<i4")] + SURFEL_DTYPE.descr)
 
 
+class TsdfRenderParams(C.Structure):
+    """struct vslam_tsdf_render_params: the camera, image size, depth range, step (in voxels) and weight gate of one vslam_tsdf_render_dev call"""
+    _fields_ = [("struct_size", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("march", C.c_double), ("min_weight", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PlaceStats(C.Structure):
     """struct vslam_place_stats: entries held, capacity, rows per entry, geometry flag and the adds refused for lack of room"""
     _fields_ = [("n_entries", C.c_int32), ("capacity", C.c_int32), ("rows_per_entry", C.c_int32), ("with_geometry", C.c_int32),
@@ -296,6 +302,7 @@ SIGNATURES = {
     "vslam_tsdf_blocks_dev": (I, [P, P, I, P, P, Z, P]),
     "vslam_tsdf_mesh_dev": (I, [P, P, I, I, P, P, Z, P, Z, P]),
     "vslam_tsdf_load_blocks_dev": (I, [P, P, P, P, Z]),
+    "vslam_tsdf_render_dev": (I, [P, P, C.POINTER(TsdfRenderParams), I, P, P, P, P, P]),
     "vslam_place_create": (I, [P, I, I, I, C.POINTER(C.c_void_p)]), "vslam_place_destroy": (None, [P]), "vslam_place_clear": (I, [P]),
     "vslam_place_stats": (I, [P, C.POINTER(PlaceStats)]),
     "vslam_place_read_entry": (I, [P, I, P, P, P, P, P, P]),
@@ -895,6 +902,12 @@ class VO:
         self._chk(self.lib.vslam_tsdf_integrate_dev(self.h, tm.h, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step),
                   "vslam_tsdf_integrate_dev")
 
+    def tsdf_render_dev(self, tm, params, V, d_T, d_map_id, d_depth, d_attr=None, d_counts=None):
+        """V views of the TsdfMap tm ray-cast by the RENDER rule of include/vslam_hip.h: params a TsdfRenderParams (struct_size is set here), d_depth
+        V x h x w f32, d_attr V x h x w x 4 f32 of (nx, ny, nz, intensity) or None, d_counts two uint64 (rays that hit, samples evaluated) or None"""
+        params.struct_size = C.sizeof(TsdfRenderParams)
+        self._chk(self.lib.vslam_tsdf_render_dev(self.h, tm.h, C.byref(params), V, d_T, d_map_id, d_depth, d_attr, d_counts), "vslam_tsdf_render_dev")
+
     def voxel_extract_dev(self, vm, map_id, min_count, d_out, d_map_out, capacity, d_n_out):
         """the occupied voxels with count >= min_count of map map_id (-1: all) into d_out (capacity x 32 bytes) / d_map_out; d_n_out (uint64): the full count"""
         self._chk(self.lib.vslam_voxel_extract_dev(self.h, vm.h, map_id, min_count, d_out, d_map_out, capacity, d_n_out), "vslam_voxel_extract_dev")
@@ -1343,6 +1356,35 @@ class TsdfMap:
         if not sort:
             return verts, tris
         return canonical_mesh(verts, tris)
+
+    def render(self, T_c_w, map_id=0, K4=None, size=None, z_min=None, z_max=None, march=0.5, min_weight=1, attrs=True):
+        """what cameras at the poses T_c_w (V, 7) see of the map (include/vslam_hip.h "RENDER"): dict(depth (V, h, w) f32 -- the camera's z of the
+        surface, 0 where the ray misses --, normal (V, h, w, 3) f32 in the world frame pointing into free space, intensity (V, h, w) f32,
+        counts = (rays that hit, samples evaluated)); normal and intensity are None with attrs=False.  map_id: one id for every view or one
+        per view (outside 0 .. 1022: all misses).  K4 = (fx, fy, cx, cy), size = (w, h) and the depth range default to the context's camera, image
+        size and depth_min .. depth_reliable; march: the step between samples in voxels, in [1/8, 1]; min_weight as in extract()."""
+        import torch
+        vo = self.vo
+        p = vo.params
+        T = np.ascontiguousarray(T_c_w, np.float64).reshape(-1, 7)
+        V = len(T)
+        ids = np.array(np.broadcast_to(np.asarray(map_id, np.int32), (V,)))                 # (a copy: the caller's array may be read-only)
+        fx, fy, cx, cy = (float(v) for v in (p.cam[:4] if K4 is None else K4))
+        w, h = (int(p.img_w), int(p.img_h)) if size is None else (int(size[0]), int(size[1]))
+        rp = TsdfRenderParams(w=w, h=h, fx=fx, fy=fy, cx=cx, cy=cy, z_min=float(p.depth_min if z_min is None else z_min),
+                              z_max=float(p.depth_reliable if z_max is None else z_max), march=float(march), min_weight=int(min_weight))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_T = torch.from_numpy(T).to(dev)
+        d_ids = torch.from_numpy(ids).to(dev)
+        d_depth = torch.zeros((V, max(h, 0), max(w, 0)), dtype=torch.float32, device=dev)
+        d_attr = torch.zeros((V, max(h, 0), max(w, 0), 4), dtype=torch.float32, device=dev) if attrs else None
+        d_counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
+        vo.tsdf_render_dev(self, rp, V, d_T.data_ptr(), d_ids.data_ptr(), d_depth.data_ptr(), d_attr.data_ptr() if attrs else None, d_counts.data_ptr())
+        vo.sync()
+        attr = d_attr.cpu().numpy() if attrs else None
+        return dict(depth=d_depth.cpu().numpy(), normal=attr[..., :3] if attrs else None, intensity=attr[..., 3] if attrs else None,
+                    counts=tuple(int(c) for c in d_counts.cpu().tolist()))
 
 
 class PlaceDB:

@@ -139,6 +139,7 @@ static const TuneKey kTuneKeys[] = {
     {"rectify_form", "VSLAM_RECTIFY_FORM", &Tuning::rectify_form, 0, 1},
     {"voxel_form", "VSLAM_VOXEL_FORM", &Tuning::voxel_form, 0, 1},
     {"tsdf_form", "VSLAM_TSDF_FORM", &Tuning::tsdf_form, 0, 1},
+    {"tsdf_render_form", "VSLAM_TSDF_RENDER_FORM", &Tuning::tsdf_render_form, 0, 1},
     {"pg_precond", "VSLAM_PG_PRECOND", &Tuning::pg_precond, 0, 1},
     {"fba_store", "VSLAM_FBA_STORE", &Tuning::fba_store, 0, 1},
     {"pm_stage", "VSLAM_PM_STAGE", &Tuning::pm_stage, 0, 1},
@@ -293,6 +294,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
            "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel "
            "tsdf_clear_kernel tsdf_frames_kernel tsdf_alloc_kernel tsdf_cull_kernel tsdf_integrate_kernel tsdf_extract_kernel tsdf_blocks_kernel tsdf_mesh_vertex_kernel tsdf_mesh_tri_kernel tsdf_load_kernel "
+           "tsdf_views_kernel tsdf_range_init_kernel tsdf_ray_range_kernel tsdf_render_kernel "
            "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel "
            "pose_graph_kernel full_ba_kernel project_match_kernel";
 }
@@ -1865,6 +1867,7 @@ void vslam_tsdf_destroy(vslam_tsdf_map* tm) {
     hipFree(m->base);
     m->ctx->dev_bytes -= m->bytes;
     m->mesh.release();
+    m->render.release();
     delete m;
 }
 
@@ -1970,6 +1973,48 @@ int vslam_tsdf_load_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const int32_t
     }
     VS_ENTER(c);
     return launch_tsdf_load(m->t, d_block_ids, d_voxels, n, c->stream);
+}
+
+// Form of the render: 0 = every ray walks all K samples, 1 = tsdf_ray_range_kernel narrows each tile's sample range first;
+// Tuning::tsdf_render_form overrides it (tests and tools/bench_tsdf.py run both)
+constexpr int kTsdfRenderFormDefault = 1;
+constexpr int kTsdfRenderMaxSamples = 8192;
+
+int vslam_tsdf_render_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const struct vslam_tsdf_render_params* rp, int V, const double* d_T_c_w, const int32_t* d_map_id,
+                          float* d_depth, float* d_attr, uint64_t* d_counts) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_render_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!rp || rp->struct_size != (int32_t)sizeof(struct vslam_tsdf_render_params)) { set_error("vslam_tsdf_render_dev: null params or struct_size mismatch"); return VSLAM_ERR_ARG; }
+    if (rp->w < 1 || rp->h < 1 || V < 0) { set_error("vslam_tsdf_render_dev: w %d, h %d below 1 or V %d below 0", rp->w, rp->h, V); return VSLAM_ERR_ARG; }
+    if ((unsigned long long)V * (unsigned long long)rp->h * (unsigned long long)rp->w >= (1ull << 31)) {
+        set_error("vslam_tsdf_render_dev: V * h * w = %d * %d * %d is not below 2^31", V, rp->h, rp->w); return VSLAM_ERR_ARG;
+    }
+    if (!std::isfinite(rp->fx) || !(rp->fx > 0) || !std::isfinite(rp->fy) || !(rp->fy > 0) || !std::isfinite(rp->cx) || !std::isfinite(rp->cy)) {
+        set_error("vslam_tsdf_render_dev: camera (%g, %g, %g, %g) is not finite with positive focal lengths", rp->fx, rp->fy, rp->cx, rp->cy); return VSLAM_ERR_ARG;
+    }
+    if (!std::isfinite(rp->z_min) || !(rp->z_min > 0) || !std::isfinite(rp->z_max) || !(rp->z_max > rp->z_min)) {
+        set_error("vslam_tsdf_render_dev: depth range (%g, %g) is not finite with 0 < z_min < z_max", rp->z_min, rp->z_max); return VSLAM_ERR_ARG;
+    }
+    if (!std::isfinite(rp->march) || !(rp->march >= 0.125 && rp->march <= 1.0)) { set_error("vslam_tsdf_render_dev: march %g outside [1/8, 1]", rp->march); return VSLAM_ERR_ARG; }
+    // K: the smallest non-negative integer with z_min + (double)K * hs >= z_max
+    const double hs = rp->march * (double)m->t.vs, guess = (rp->z_max - rp->z_min) / hs;
+    long long K = guess < (double)(kTsdfRenderMaxSamples + 4) ? std::max<long long>((long long)std::floor(guess) - 2, 0) : kTsdfRenderMaxSamples + 1;
+    while (K <= kTsdfRenderMaxSamples && !(rp->z_min + (double)K * hs >= rp->z_max)) ++K;
+    if (K > kTsdfRenderMaxSamples) { set_error("vslam_tsdf_render_dev: (%g, %g) in steps of %g takes more than %d samples", rp->z_min, rp->z_max, hs, kTsdfRenderMaxSamples); return VSLAM_ERR_ARG; }
+    if (V > 0 && (!d_T_c_w || !d_map_id || !d_depth)) { set_error("vslam_tsdf_render_dev: null d_T_c_w, d_map_id or d_depth with V > 0"); return VSLAM_ERR_ARG; }
+    if (reinterpret_cast<uintptr_t>(d_attr) % 16 || reinterpret_cast<uintptr_t>(d_counts) % 8 || reinterpret_cast<uintptr_t>(d_depth) % 4) {
+        set_error("vslam_tsdf_render_dev: d_attr must be 16-byte, d_counts 8-byte, d_depth 4-byte aligned"); return VSLAM_ERR_ARG;
+    }
+    if (V == 0) return VSLAM_OK;
+    VS_ENTER(c);
+    const int form = c->tune.tsdf_render_form >= 0 ? c->tune.tsdf_render_form : kTsdfRenderFormDefault;
+    if (int rc = m->render.reserve(tsdf_render_table_bytes(V, rp->w, rp->h, form), c->stream)) return rc;
+    TsdfRenderCall call;
+    call.w = rp->w; call.h = rp->h; call.V = V; call.K = (int)K; call.min_weight = rp->min_weight;
+    call.fx = rp->fx; call.fy = rp->fy; call.cx = rp->cx; call.cy = rp->cy; call.z_min = rp->z_min; call.hs = hs;
+    call.d_T = d_T_c_w; call.d_map_id = d_map_id; call.d_depth = d_depth; call.d_attr = d_attr; call.d_counts = reinterpret_cast<unsigned long long*>(d_counts);
+    return launch_tsdf_render(m->t, call, m->render.p, form, c->stream);
 }
 
 // ---------------------------------------------------------------------------------------------- place database

@@ -280,6 +280,7 @@ struct Tuning {
     int rectify_form = -1;    // VSLAM_RECTIFY_FORM: source side of rectify_kernel -- 0 = direct byte gathers, 1 = each tile's source box staged in LDS (default 1; tiles whose box does not pay gather either way)
     int pg_precond = -1;      // VSLAM_PG_PRECOND: preconditioner of pose_graph_kernel's conjugate gradients -- 0 = block-Jacobi, 1 = chain (block-tridiagonal); default: the rule of DESIGN.md 5.10
     int voxel_form = -1;      // VSLAM_VOXEL_FORM: voxel_fuse_kernel -- 0 = every point straight into the global table, 1 = a workgroup sums its image tile in an LDS hash table first (same table either way)
+    int tsdf_render_form = -1; // VSLAM_TSDF_RENDER_FORM: vslam_tsdf_render_dev -- 0 = every ray walks all K samples, 1 = tsdf_ray_range_kernel narrows each tile's sample range first (same bytes either way); default: DESIGN.md 5.15
     int tsdf_form = -1;       // VSLAM_TSDF_FORM: tsdf_integrate_kernel -- 0 = every block walks all frames of the call, 1 = tsdf_cull_kernel writes a frame mask per block first (same sums either way); default: DESIGN.md 5.13
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
     int pm_stage = -1;        // VSLAM_PM_STAGE: project_match_kernel -- 1 = the target image's descriptors staged in LDS (where two workgroups per CU still fit), 0 = read from L2; default: DESIGN.md 5.12
@@ -503,7 +504,8 @@ struct TsdfTable { unsigned long long* keys; uint32_t* list; uint4* pool; unsign
                    int log2_blocks, J, frame_words; float vs, inv; };
 struct TsdfMap { Ctx* ctx; TsdfTable t; size_t bytes; void* base;
                  DevBuf mesh; // the vertex-id table of vslam_tsdf_mesh_dev: vid (3 x 512 int32 per claimed block) | pos_of_slot (one uint32 per slot); grown by the first mesh call
-                 TsdfMap(size_t* acct) : mesh("mesh vertex-id table", acct) {} };
+                 DevBuf render; // the tables of vslam_tsdf_render_dev: the view table (16 doubles per view) | (form 1) one (k_lo, k_hi) per view and 16 x 16 tile; grown on demand
+                 TsdfMap(size_t* acct) : mesh("mesh vertex-id table", acct), render("render view and range tables", acct) {} };
 int launch_tsdf_clear(const TsdfTable& t, hipStream_t stream);
 // form: 0 = every block walks all frames, 1 = a cull kernel writes a frame mask per block first
 int launch_tsdf_integrate(const TsdfTable& t, const VoxelImages& a, const uint8_t* d_gray, size_t img_bytes, int pitch, const int32_t* d_map_id, int form,
@@ -517,6 +519,12 @@ int launch_tsdf_mesh(const TsdfTable& t, int32_t* d_vid, uint32_t* d_pos_of_slot
                      int32_t* d_vertex_map, size_t vertex_capacity, vslam_triangle* d_triangles, size_t triangle_capacity, unsigned long long* d_counts,
                      hipStream_t stream);
 int launch_tsdf_load(const TsdfTable& t, const int32_t* d_block_ids, const uint32_t* d_voxels, size_t n, hipStream_t stream);
+// tsdf_render_kernels.hip: depth, normal and intensity views ray-cast from the field (include/vslam_hip.h "RENDER")
+struct TsdfRenderCall { int w, h, V, K, min_weight; double fx, fy, cx, cy, z_min, hs; const double* d_T; const int32_t* d_map_id;
+                        float* d_depth; float* d_attr; unsigned long long* d_counts; };  // (d_attr, d_counts null: not wanted)
+size_t tsdf_render_table_bytes(int V, int w, int h, int form);
+// form: 0 = every ray walks all K samples, 1 = a range kernel narrows each 16 x 16 tile's samples to those near a claimed block first (same bytes)
+int launch_tsdf_render(const TsdfTable& t, const TsdfRenderCall& rc, uint8_t* d_tables, int form, hipStream_t stream);
 
 // ----------------------------------------------------------------------------------------------- place database
 // place_kernels.hip: keyframe descriptor blocks kept across steps and the place score between them (include/vslam_hip.h "place database").

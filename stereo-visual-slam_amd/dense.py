@@ -98,3 +98,25 @@ def read_mesh_ply(path):
     f3 = np.frombuffer(data[end + v.nbytes:], _FACE_PLY_DTYPE, count=nf)
     assert (f3["n"] == 3).all()
     return v, f3["v"].astype(np.int32)
+
+
+def write_depth_pgm(path, depth, z_max):
+    """one depth view of TsdfMap.render() (h, w) -> a binary 16-bit PGM any image viewer opens: 0 = the ray missed, otherwise
+    1 .. 65535 = round(depth / z_max * 65535) (a hit nearer than z_max / 65535 / 2 is stored as 1, one beyond z_max as 65535)"""
+    depth = np.asarray(depth, np.float64)
+    assert depth.ndim == 2 and z_max > 0, (depth.shape, z_max)
+    v = np.where(depth > 0, np.clip(np.rint(depth / z_max * 65535.0), 1, 65535), 0).astype(">u2")
+    with open(path, "wb") as f:
+        f.write(("P5\n%d %d\n65535\n" % (depth.shape[1], depth.shape[0])).encode("ascii"))
+        f.write(v.tobytes())
+
+
+def read_depth_pgm(path, z_max):
+    """the (h, w) float64 depth of a file write_depth_pgm wrote with the same z_max: 0 where the ray missed, otherwise within z_max / 131070 of the
+    depth written"""
+    with open(path, "rb") as f:
+        data = f.read()
+    magic, size, peak, rest = data.split(b"\n", 3)
+    assert magic == b"P5" and peak == b"65535", (magic, peak)
+    w, h = (int(s) for s in size.split())
+    return np.frombuffer(rest, ">u2", count=w * h).reshape(h, w).astype(np.float64) * (z_max / 65535.0)

@@ -721,7 +721,34 @@ class KeyframePipeline:
             self.dense_map_id = torch.from_numpy(map_id).to(self.dev)
         tm.integrate_dev(self.d_disp.data_ptr(), self.d_imgs.data_ptr(), self.img_bytes, self.pitch, self.w, self.h, self.B,
                          self.dense_T.data_ptr(), self.dense_map_id.data_ptr(), z_min, z_max, int(step))
+        self.last_surface_map = tm
         return tm
+
+    def surface_views(self, tsdf_map=None, poses=None, scale=1.0, march=0.5, min_weight=1, disparity=False):
+        """What the surface map shows from every frame of dense_map_inputs(poses), each at its own pose and map id (TsdfMap.render): the carved,
+        multi-view counterpart of the frames' single-view SGBM maps, or -- with poses= what close_loops() or full_ba() returned -- the map seen from
+        where the corrected trajectory puts the cameras.  tsdf_map: a TsdfMap of this pipeline's context (None: the one the last surface_map()
+        returned).  The context's camera and image size are multiplied by `scale`; the depth range is depth_min .. depth_reliable.
+        Returns TsdfMap.render's dict (depth (B, h, w), normal, intensity, counts) with T_c_w and map_id added and, with disparity=True,
+        disparity = fx * b / depth at the scaled fx (0 where the ray misses)."""
+        tm = tsdf_map if tsdf_map is not None else getattr(self, "last_surface_map", None)
+        assert tm is not None and getattr(tm, "h", None), "surface_views needs a TsdfMap: call surface_map() first or pass tsdf_map="
+        assert tm.vo is self.vo, "tsdf_map belongs to another context"
+        assert scale > 0
+        if poses is not None:
+            self.vo.sync()
+            torch.cuda.synchronize(self.dev)
+        T, map_id = self.dense_map_inputs() if poses is None else self.dense_map_inputs(poses)
+        fx, fy, cx, cy, b = (float(v) for v in self.vo.params.cam)
+        K4 = (fx * scale, fy * scale, cx * scale, cy * scale)
+        size = (max(int(round(self.w * scale)), 1), max(int(round(self.h * scale)), 1))
+        out = tm.render(T, map_id, K4=K4, size=size, march=march, min_weight=min_weight)
+        out.update(T_c_w=T, map_id=map_id, K4=K4)
+        if disparity:
+            depth = out["depth"].astype(np.float64)
+            with np.errstate(divide="ignore"):
+                out["disparity"] = np.where(depth > 0, K4[0] * b / depth, 0.0).astype(np.float32)
+        return out
 
     # ------------------------------------------------------------------ loop closure (nothing here runs unless loop_closures is called)
     def show_sequence(self, sequence):

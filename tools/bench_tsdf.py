@@ -5,7 +5,7 @@ profiler's split of one call into its kernels, and the library's own streaming c
 the neighbour figure.
 
     python tools/bench_tsdf.py [--batches 256,1024] [--voxel 0.2] [--trunc 4] [--z-min 10] [--z-max 40] [--windows 5] [--out profiles/tsdf.json]
-                               [--mesh-out profiles/tsdf_mesh.json] [--mesh-only]
+                               [--mesh-out profiles/tsdf_mesh.json] [--mesh-only] [--render] [--render-out profiles/tsdf_render.json]
 
 The inputs are one KeyframePipeline(depth="sgbm", ba_windows="tracks", anms_num=500) step at each batch size: its disparity maps, left images and
 BA-refined poses (KeyframePipeline.dense_map_inputs).  A figure is the median of `--windows` timed windows, each a host clock around enough
@@ -17,7 +17,12 @@ forms into a small map and are compared with the numpy restatement tests/tsdf_re
 --mesh-out adds the mesh on the same maps: ms per call of vslam_tsdf_mesh_dev next to vslam_tsdf_extract_dev with the same
 arguments, the split of one mesh call into its two kernels, and the copy probe on the mesh's compulsory bytes (8 KiB read per block, 48 + 4 B
 written per vertex, 12 B per triangle) and on those plus the vertex-id table's traffic (6 KiB written per block, 12 B read per triangle).  The mesh
-of the small map is compared with tests/tsdf_mesh_ref.py before anything is timed.  --mesh-only skips the integration and dense-map figures."""
+of the small map is compared with tests/tsdf_mesh_ref.py before anything is timed.  --mesh-only skips the integration and dense-map figures.
+
+--render measures the ray-cast views on the same maps instead: vslam_tsdf_render_dev for 64 views at the map's first 64 keyframe
+poses, at the full image size and at half of it, in both forms, at march 0.5 and 1, over the context's depth range: ms per call, rays/s, evaluated
+samples/s, the share of rays that hit, the split of one call into its kernels, and the copy probe on the output bytes (20 B per pixel).  Two views of
+the small map at an eighth of the size are compared with tests/tsdf_render_ref.py, in both forms, before anything is timed."""
 import argparse
 import json
 import os
@@ -33,6 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import tsdf_mesh_ref as MR  # noqa: E402
 import tsdf_ref as TR  # noqa: E402
+import tsdf_render_ref as RR  # noqa: E402
 from bench_voxel import timed  # noqa: E402
 from stereo_visual_slam_amd.pipeline import KeyframePipeline  # noqa: E402
 
@@ -74,6 +80,53 @@ def mesh_case(vo, tm, dev, windows, case):
     return case
 
 
+def render_case(vo, pkg, tm, dev, windows, T, map_id, w, h, case):
+    """vslam_tsdf_render_dev on the filled map tm: V views at the poses T, two sizes x two forms x two marches, by the method of the figures above"""
+    import ctypes as C
+
+    import torch
+    sync = vo.sync
+    V = len(T)
+    p = vo.params
+    d_T = torch.from_numpy(np.ascontiguousarray(T)).to(dev); d_id = torch.from_numpy(np.ascontiguousarray(map_id, np.int32)).to(dev)
+    d_counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    case.update(views=V, z_min=float(p.depth_min), z_max=float(p.depth_reliable), runs=[])
+    for scale in (1.0, 0.5):
+        ws, hs = int(round(w * scale)), int(round(h * scale))
+        d_depth = torch.zeros((V, hs, ws), dtype=torch.float32, device=dev)
+        d_attr = torch.zeros((V, hs, ws, 4), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        out_bytes = 20 * V * hs * ws
+        gbs = vo.hbm_copy_probe(max(out_bytes // 2, 1 << 20), 20)   # a copy of out_bytes / 2 moves out_bytes
+        for march in (0.5, 1.0):
+            rp = pkg.TsdfRenderParams(w=ws, h=hs, fx=p.cam[0] * scale, fy=p.cam[1] * scale, cx=p.cam[2] * scale, cy=p.cam[3] * scale, z_min=p.depth_min,
+                                      z_max=p.depth_reliable, march=march, min_weight=1)
+            call = lambda counts=None: vo.tsdf_render_dev(tm, rp, V, d_T.data_ptr(), d_id.data_ptr(), d_depth.data_ptr(), d_attr.data_ptr(), counts)
+            kept = None
+            for form in (0, 1):
+                vo.set_tuning(tsdf_render_form=form)
+                call(d_counts.data_ptr()); sync()
+                hits, samples = (int(c) for c in d_counts.cpu().tolist())
+                bits = (d_depth.view(torch.int32).sum(dtype=torch.int64).item(), d_attr.view(torch.int32).sum(dtype=torch.int64).item())
+                assert kept is None or kept == (hits, bits), "the two forms differ"
+                kept = (hits, bits)
+                ms, win, n = timed(call, sync, windows)
+                vo.profile_enable(True); vo.profile_read()
+                call(); sync()
+                prof = {k: round(t, 4) for k, (t, _, _) in vo.profile_read().items() if k.startswith("tsdf_")}
+                vo.profile_enable(False)
+                rays = V * hs * ws
+                run = dict(w=ws, h=hs, march=march, form=form, ms=round(ms, 4), windows_ms=win, calls_per_window=n, rays=rays, rays_per_s=round(rays / ms * 1e3, 0),
+                           samples=samples, samples_per_s=round(samples / ms * 1e3, 0), samples_per_ray=round(samples / rays, 2), hit_share=round(hits / rays, 4),
+                           kernels_ms_one_call=prof, output_bytes=out_bytes, copy_probe_gbs=round(gbs, 1), copy_probe_ms_output_bytes=round(out_bytes / gbs * 1e-6, 4),
+                           ratio_over_copy=round(ms / (out_bytes / gbs * 1e-6), 1))
+                case["runs"].append(run)
+                print(json.dumps(run), flush=True)
+            vo.set_tuning(tsdf_render_form=-1)
+        del d_depth, d_attr
+    return case
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="256,1024")
@@ -86,12 +139,15 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--mesh-out", default=None)
     ap.add_argument("--mesh-only", action="store_true")
+    ap.add_argument("--render", action="store_true")
+    ap.add_argument("--render-out", default=os.path.join(ROOT, "profiles", "tsdf_render.json"))
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_tsdf: no GPU visible (there is nothing to measure without one)")
     res = dict(voxel_size=a.voxel, trunc_voxels=a.trunc, z_min=a.z_min, z_max=a.z_max, windows=a.windows, device=torch.cuda.get_device_name(0), cases=[])
     mres = dict(res, cases=[])
+    rres = dict(res, cases=[])
     seq = None
     for B in [int(b) for b in a.batches.split(",")]:
         p = KeyframePipeline(B, anms_num=500, unique_frames=a.unique_frames, seed=0, ba_windows="tracks", depth="sgbm", sequence=seq, render_workers=8)
@@ -123,6 +179,18 @@ def main():
                     gv, gt = small.mesh(min_weight=mw)
                     wv, wt = MR.mesh(want_ids, want_vox, a.voxel, mw)
                     assert gv.tobytes() == wv.tobytes() and np.array_equal(gt, wt) and len(wt) > 0, "the mesh differs from the yardstick (min_weight %d)" % mw
+            if a.render:   # two views of the small map at an eighth of the size, both forms, against the yardstick
+                import stereo_visual_slam_amd as pkg
+                K4, size = tuple(float(v) / 8 for v in vo.params.cam[:4]), (w // 8, h // 8)
+                rwant = RR.render(want_ids, want_vox, a.voxel, T[:2], map_id[:2], K4, size, a.z_min / 2, a.z_max, 0.5, 1)
+                assert rwant["hits"] > 100, rwant["hits"]
+                for form in (0, 1):
+                    vo.set_tuning(tsdf_render_form=form)
+                    got = small.render(T[:2], map_id[:2], K4=K4, size=size, z_min=a.z_min / 2, z_max=a.z_max)
+                    gattr = np.concatenate([got["normal"], got["intensity"][..., None]], -1)
+                    assert got["depth"].tobytes() == rwant["depth"].tobytes() and gattr.tobytes() == rwant["attr"].tobytes() and got["counts"][0] == rwant["hits"], \
+                        "the views differ from the yardstick (form %d)" % form
+                vo.set_tuning(tsdf_render_form=-1)
             small.close()
             # ---- the pool: a load factor below one half
             probe = vo.tsdf_map(a.voxel, a.trunc, 19)
@@ -144,7 +212,14 @@ def main():
                     json.dump(mres, f, indent=1)
                     f.write("\n")
                 tm.clear(); sync()
-            if a.mesh_only:
+            if a.render:
+                integrate(tm); sync()
+                rcase = render_case(vo, pkg, tm, p.dev, a.windows, T[:64], map_id[:64], w, h, dict(case))
+                rres["cases"].append(rcase)
+                with open(a.render_out, "w") as f:
+                    json.dump(rres, f, indent=1)
+                    f.write("\n")
+            if a.mesh_only or a.render:
                 tm.close()
                 continue
             clear_ms, _, _ = timed(tm.clear, sync, a.windows)
