@@ -19,13 +19,16 @@
 //     and the result is still bit-reproducible -- the property the adaptive schedule's "continue instead of repeat" argument needs.
 //   * the back-substitution re-derives D^-1 and b_l from the landmark's own observations, updates the position IN PLACE in LDS and
 //     evaluates the trial cost in the same visit; a rejected step restores the positions from the backup (rare).
-// Reduced system: blocked right-looking Cholesky as in lm_kernels.hip, on a block-packed lower triangle (nk (nk + 1) / 2 blocks of 36).
+// Reduced system: reduced_solve of lm_solver.h (blocked right-looking Cholesky, backward substitution by wave 0 -- the code lm_window_kernel runs on
+// dense rows) on a block-packed lower triangle (nk (nk + 1) / 2 blocks of 36).  The damping rule, the statistics, the trial pose and the threshold
+// rule of the classification (here over five precomputed tallies) are lm_solver.h's too.
 // Windows that do not fit (multi-observation rows x 1536 B + 2 B per landmark + blocks beyond the LDS budget, > 5120 landmarks) are marked deferred and taken by
 // lm_window_kernel in the same launch set.  Same LM rules (g2o Levenberg, Huber 5.991, <= 10 trials), same chi2 classification, same
 // statistics as lm_kernels.hip; sums differ from it in rounding only.
 #include "vslam_internal.h"
 
 #include "lm_device.h"
+#include "lm_solver.h"
 
 namespace vslam {
 
@@ -1030,13 +1033,9 @@ __global__ __launch_bounds__(BLOCK, kRsMinWaves) void ba_resident_kernel(RsArgs 
                 for (int ww = 0; ww < kRsWaves; ++ww)
 #pragma unroll
                     for (int i = 0; i < 6; ++i) tot[i] += sm.redi[8 * ww + i];
-                int ti = 0;
-                for (int iteration = 0; iteration < 5; ++iteration) {
-                    const double out = (double)tot[iteration], in = (double)(tot[5] - tot[iteration]);
-                    const double ratio = in / (in + out);
-                    if (ratio > 0.5) break;
-                    th *= 2; ++ti;
-                }
+                const int ti = chi2_threshold(th, [&](double, int i, double& in, double& out) { // the tallies at the five thresholds are there
+                    out = (double)tot[i]; in = (double)(tot[5] - tot[i]);
+                });
                 for (int j = 0; wave + kRsWaves * j < nrows; ++j) {
                     const int s = 64 * (wave + kRsWaves * j) + lane;
                     const unsigned lv = live[s];
@@ -1062,7 +1061,8 @@ __global__ __launch_bounds__(BLOCK, kRsMinWaves) void ba_resident_kernel(RsArgs 
         pass_init(pass == 0 ? 0 : 1);
         RPH(1);
 
-        double lambda = 0, ni = 2, currentChi = 0, Bcur = 0;
+        LmDamping lm;
+        double currentChi = 0, Bcur = 0;
         int it = 0, total_trials = 0;
         bool p_is_trial = false, need_backup = true, last_trial_is_current = true;
         currentChi = chi_pass(sm.Rt, Bcur);
@@ -1071,8 +1071,7 @@ __global__ __launch_bounds__(BLOCK, kRsMinWaves) void ba_resident_kernel(RsArgs 
         for (;;) { // (at most twice: a continued pass re-enters the loop where it left it)
         for (; it < bound; ++it) {
             if (it == 0 && st && tid == 0) st->chi2_init = currentChi;
-            double rho_gain = 0;
-            int qmax = 0;
+            lm.begin_iteration();
             bool again = true;
             while (again) {
                 if (p_is_trial) { restore_positions(); p_is_trial = false; }
@@ -1081,22 +1080,21 @@ __global__ __launch_bounds__(BLOCK, kRsMinWaves) void ba_resident_kernel(RsArgs 
                 (void)frexp(2.0 * Bcur, &ex);
                 const double scale = ldexp(1.0, 60 - ex), inv_scale = ldexp(1.0, ex - 60);
                 bool ok2 = isfinite(Bcur);
-                if (it == 0 && qmax == 0) { // computeLambdaInit: tau * max |H_jj| over every vertex
+                if (it == 0 && lm.qmax == 0) { // computeLambdaInit: tau * max |H_jj| over every vertex
                     for (int i = tid; i < np; i += kRsBlock) sm.hdq[i] = 0;
                     if (tid == 0) sm.flag[6] = 0;
                     __syncthreads();
                     double md = linearise(0.0, scale, true);
                     __syncthreads();
                     if (tid < np) md = fmax(md, fabs((double)sm.hdq[tid] * inv_scale));
-                    lambda = 1e-5 * block_max1(md);
-                    ni = 2;
+                    lm.init(block_max1(md));
                     RPH(3);
                 }
                 for (int i = tid; i < nblk * 36; i += kRsBlock) Sq[i] = 0;
                 for (int i = tid; i < np; i += kRsBlock) { sm.bpq[i] = 0; sm.bsq[i] = 0; }
                 if (tid == 0) { sm.flag[6] = 0; sm.flag[10] = 0; }
                 __syncthreads();
-                linearise(lambda, scale, false);
+                linearise(lm.lambda, scale, false);
                 __syncthreads();
                 RPH(4);
                 // fixed point -> f64, lambda on the diagonal
@@ -1106,151 +1104,24 @@ __global__ __launch_bounds__(BLOCK, kRsMinWaves) void ba_resident_kernel(RsArgs 
                     while ((I + 1) * (I + 2) / 2 <= b) ++I;
                     const bool diagblk = (b - I * (I + 1) / 2) == I;
                     double v = (double)Sq[i] * inv_scale;
-                    if (diagblk && rr == cc) v += lambda;
+                    if (diagblk && rr == cc) v += lm.lambda;
                     Sb[i] = v;
                 }
                 if (tid < np) { sm.bp[tid] = (double)sm.bpq[tid] * inv_scale; sm.bs[tid] = (double)sm.bsq[tid] * inv_scale; }
                 __syncthreads();
                 if (sm.flag[1]) ok2 = false;
-                // Cholesky S = L L^T, right-looking over 6x6 block columns, the right-hand side as one more row (see lm_kernels.hip)
-                for (int J = 0; J < nk && ok2; ++J) {
-                    const int m = nk - J - 1, nrw = m * 6;
-                    const bool rhs_row = tid == kRsBlock - 1;
-                    if (tid < nrw || tid == 0 || rhs_row) {
-                        double D[21];
-                        const double* dj = &Sb[rs_blk(J, J)];
-#pragma unroll
-                        for (int i = 0; i < 6; ++i)
-#pragma unroll
-                            for (int j = 0; j <= i; ++j) D[i * (i + 1) / 2 + j] = dj[6 * i + j];
-                        bool good = true;
-                        double rd[6];
-#pragma unroll
-                        for (int j = 0; j < 6; ++j) {
-                            double d = D[j * (j + 1) / 2 + j];
-#pragma unroll
-                            for (int kk = 0; kk < j; ++kk) d -= D[j * (j + 1) / 2 + kk] * D[j * (j + 1) / 2 + kk];
-                            if (!(d > 0.0) || !isfinite(d)) good = false;
-                            rd[j] = rsqrt_nr(d);
-                            D[j * (j + 1) / 2 + j] = d * rd[j];
-#pragma unroll
-                            for (int i = j + 1; i < 6; ++i) {
-                                double v = D[i * (i + 1) / 2 + j];
-#pragma unroll
-                                for (int kk = 0; kk < j; ++kk) v -= D[i * (i + 1) / 2 + kk] * D[j * (j + 1) / 2 + kk];
-                                D[i * (i + 1) / 2 + j] = v * rd[j];
-                            }
-                        }
-                        if (tid < nrw || rhs_row) {
-                            double* rowv = rhs_row ? &sm.bs[6 * J] : &Sb[rs_blk(J + 1 + tid / 6, J) + 6 * (tid % 6)];
-                            double x[6];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) {
-                                double v = rowv[c];
-#pragma unroll
-                                for (int kk = 0; kk < c; ++kk) v -= x[kk] * D[c * (c + 1) / 2 + kk];
-                                x[c] = v * rd[c];
-                            }
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) rowv[c] = x[c];
-                        }
-                        if (tid == 0) {
-                            if (!good) sm.flag[1] = 1;
-#pragma unroll
-                            for (int i = 0; i < 21; ++i) sm.Ld[24 * J + i] = D[i];
-#pragma unroll
-                            for (int i = 0; i < 6; ++i) sm.rdiag[6 * J + i] = rd[i];
-                        }
-                    }
-                    __syncthreads();
-                    if (sm.flag[1]) { ok2 = false; break; }
-                    const int npair = m * (m + 1) / 2, nitem = npair * 6 + m;
-                    for (int t = tid; t < nitem; t += kRsBlock) {
-                        const double* xi; double* out; int Kb;
-                        if (t < npair * 6) {
-                            const int pr = t / 6, rr = t - 6 * pr;
-                            int aa = 0, rem = pr;
-                            while (rem > aa) { rem -= aa + 1; ++aa; }
-                            const int Ib = J + 1 + aa; Kb = J + 1 + rem;
-                            xi = &Sb[rs_blk(Ib, J) + 6 * rr]; out = &Sb[rs_blk(Ib, Kb) + 6 * rr];
-                        } else { Kb = J + 1 + (t - npair * 6); xi = &sm.bs[6 * J]; out = &sm.bs[6 * Kb]; }
-                        const double2* xi2 = reinterpret_cast<const double2*>(xi);
-                        const double2 a0 = xi2[0], a1 = xi2[1], a2 = xi2[2];
-                        double2* o2 = reinterpret_cast<double2*>(out);
-                        double2 o[3] = {o2[0], o2[1], o2[2]};
-                        double v[6] = {o[0].x, o[0].y, o[1].x, o[1].y, o[2].x, o[2].y};
-                        const double* kb = &Sb[rs_blk(Kb, J)];
-#pragma unroll
-                        for (int c = 0; c < 6; ++c) {
-                            const double2* xk = reinterpret_cast<const double2*>(kb + 6 * c);
-                            const double2 b0 = xk[0], b1 = xk[1], b2 = xk[2];
-                            v[c] -= (a0.x * b0.x + a0.y * b0.y) + (a1.x * b1.x + a1.y * b1.y) + (a2.x * b2.x + a2.y * b2.y);
-                        }
-                        o2[0] = make_double2(v[0], v[1]); o2[1] = make_double2(v[2], v[3]); o2[2] = make_double2(v[4], v[5]);
-                    }
-                    __syncthreads();
-                }
-                if (sm.flag[1]) ok2 = false;
-                __syncthreads();
-                if (tid == 0) sm.flag[1] = 0;
-                if (ok2) {
-                    if (wave == 0) { // backward substitution L^T x = y, block by block from the last (see lm_kernels.hip)
-                        double u0 = lane < np ? sm.bs[lane] : 0.0, u1 = lane + 64 < np ? sm.bs[lane + 64] : 0.0;
-                        for (int J = nk - 1; J >= 0; --J) {
-                            double Lr0[6], Lr1[6], Ld[21], rdj[6], t[6], x[6];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) {
-                                Lr0[c] = lane < 6 * J ? Sb[rs_blk(J, lane / 6) + 6 * c + lane % 6] : 0.0;
-                                Lr1[c] = (6 * J > 64 && lane + 64 < 6 * J) ? Sb[rs_blk(J, (lane + 64) / 6) + 6 * c + (lane + 64) % 6] : 0.0;
-                                rdj[c] = sm.rdiag[6 * J + c];
-                            }
-#pragma unroll
-                            for (int i = 0; i < 21; ++i) Ld[i] = sm.Ld[24 * J + i];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) {
-                                const int rr = 6 * J + c;
-                                t[c] = rr >= 64 ? readlane_f64(u1, rr - 64) : readlane_f64(u0, rr);
-                            }
-#pragma unroll
-                            for (int c = 5; c >= 0; --c) {
-                                double v = t[c];
-#pragma unroll
-                                for (int k = c + 1; k < 6; ++k) v -= Ld[k * (k + 1) / 2 + c] * x[k];
-                                x[c] = v * rdj[c];
-                            }
-                            if (lane == 0)
-#pragma unroll
-                                for (int c = 0; c < 6; ++c) sm.xp[6 * J + c] = x[c];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) { u0 = fma(-Lr0[c], x[c], u0); u1 = fma(-Lr1[c], x[c], u1); }
-                        }
-                    }
-                } else {
-                    for (int i = tid; i < np; i += kRsBlock) sm.xp[i] = 0;
-                }
-                __syncthreads();
+                // Cholesky of S on the block-packed lower triangle, the right-hand side as one more row, and the backward substitution (lm_solver.h)
+                ok2 = reduced_solve<kRsBlock>(PackedBlocks<6>{Sb}, sm.bs, sm.Ld, sm.rdiag, sm.xp, &sm.flag[1], nk, tid, lane, wave, ok2, NoClock{});
                 RPH(5);
-                if (tid < nk) {
-                    double E[7];
-                    se3::exp(&sm.xp[6 * tid], E);
-                    se3::mul(E, &sm.T[7 * tid], &sm.TT[7 * tid]);
-                    expand_pose(&sm.TT[7 * tid], &sm.RtT[12 * tid]);
-                }
+                if (tid < nk) trial_pose(&sm.xp[6 * tid], &sm.T[7 * tid], &sm.TT[7 * tid], &sm.RtT[12 * tid]);
                 __syncthreads();
                 double scale_gain = 1.0, Btrial = 0;
-                double tempChi = backsub_pass(lambda, need_backup, scale_gain, Btrial);
+                const double tempChi = backsub_pass(lm.lambda, need_backup, scale_gain, Btrial);
                 need_backup = false;
                 p_is_trial = true;
                 last_trial_is_current = false;
                 RPH(6);
-                if (!ok2) tempChi = 1.7976931348623157e308;
-                rho_gain = (currentChi - tempChi) / scale_gain;
-                const bool accept = rho_gain > 0 && isfinite(tempChi);
-                if (accept) {
-                    double alpha = 1. - pow(2 * rho_gain - 1, 3);
-                    alpha = fmin(alpha, 2. / 3.);
-                    lambda *= fmax(1. / 3., alpha);
-                    ni = 2;
+                if (lm.step(currentChi, tempChi, scale_gain, ok2)) {
                     currentChi = tempChi;
                     Bcur = Btrial;
                     __syncthreads();
@@ -1258,18 +1129,14 @@ __global__ __launch_bounds__(BLOCK, kRsMinWaves) void ba_resident_kernel(RsArgs 
                     for (int i = tid; i < nk * 12; i += kRsBlock) sm.Rt[i] = sm.RtT[i];
                     __syncthreads();
                     p_is_trial = false; need_backup = true; last_trial_is_current = true;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
                 }
-                ++qmax;
-                again = (rho_gain < 0) && qmax < 10;
+                again = lm.again();
             }
-            total_trials += qmax;
-            if (st && tid == 0 && it < VSLAM_LM_MAX_ITERS) { st->chi2_iter[it] = currentChi; st->lambda_iter[it] = lambda; st->trials_iter[it] = qmax; }
-            if (qmax == 10 || rho_gain == 0) { ++it; bound = 0; break; }
+            total_trials += lm.qmax;
+            if (tid == 0) lm_stats_iter(st, it, currentChi, lm);
+            if (lm.iteration_ends()) { ++it; bound = 0; break; }
         }
-        if (st && tid == 0) { st->iterations = it; st->total_trials = total_trials; st->chi2_final = currentChi; st->lambda_final = lambda; }
+        if (tid == 0) lm_stats_final(st, it, total_trials, currentChi, lm);
         RPH(7);
 
         // ---- landmark write-back (:272-287): the ACCEPTED positions of this pass's graph (before the classification clears live words); while a

@@ -25,9 +25,15 @@
 //                                                 are re-derived), diagonal pairs stream the keyframe's own list and
 //                                                 also produce the reduced right-hand side; single owner per block
 //   - wave reductions                           : halving butterfly (N sums cost ~N shuffles and end one per lane)
-//   - reduced system                            : blocked left-looking Cholesky in LDS, the right-hand side rides along as an extra
+//   - reduced system                            : blocked right-looking Cholesky in LDS, the right-hand side rides along as an extra
 //                                                 row (forward substitution for free), backward substitution with the unknowns
-//                                                 in the lanes of one wave (readlane + FMA per unknown)
+//                                                 in the lanes of one wave (readlane + FMA per unknown): reduced_solve of lm_solver.h
+//                                                 on dense rows (ba_resident.hip runs the same code on packed blocks)
+// The solver around the per-observation maths (lm_device.h) is lm_solver.h's, once for lm_window_kernel, pose_only_wave_kernel and
+// ba_resident_kernel: the reduced solve, the trial pose exp(x) T and the adaptive chi2 threshold; g2o's damping rule (LmDamping) with the
+// vslam_lm_stats writes for pose_only_wave_kernel and ba_resident_kernel.  What a kernel does on acceptance (swapping buffers, copying
+// poses) and how it counts inliers stays with the kernel.  lm_window_kernel keeps the damping rule and the statistics written out, and
+// pnp_wave_kernel the trial pose as well: see the notes at their loops.
 // Landmarks and pixels are f32 at rest (quirk Q4); poses, accumulators and the LM state are f64.
 // No MFMA: the largest dense object is the 72x72 reduced system (and f64 MFMA has the vector rate on gfx950).  Bound: f64 VALU
 // issue at two waves per SIMD (256 VGPRs: the Schur accumulators), the serial reduced-system phases and, first of all, the bytes
@@ -43,6 +49,7 @@
 
 #include "se3_device.h"
 #include "lm_device.h"
+#include "lm_solver.h"
 
 namespace vslam {
 
@@ -521,6 +528,8 @@ __global__ __launch_bounds__(kLmBlock, kLmMinWaves) void lm_window_kernel(LmKern
 
     PH(0);
     // ------------------------------------------------------------------ LM iterations
+    // g2o's damping rule and the statistics stay written out in this kernel (lambda, ni, rho_gain, qmax as plain locals), not LmDamping's: with the
+    // shared form the schedule on 1024 dense windows ran 0.6 % slower (14.51 against 14.42 ms, outside the spread of the parent's windows); same bits
     double lambda = 0, ni = 2, currentChi = 0;
     int it = 0, total_trials = 0;
     vslam_lm_stats* st = a.stats ? a.stats + w : nullptr;
@@ -957,142 +966,12 @@ __global__ __launch_bounds__(kLmBlock, kLmMinWaves) void lm_window_kernel(LmKern
                 }
                 __syncthreads();
                 PH(6);
-                // Cholesky S = L L^T, RIGHT-looking over 6x6 block columns (np = 6 nk), two barriers per block column:
-                //   P1  every lane that owns a row of the panel below block (J, J) factors the 6x6 diagonal block in registers (redundantly:
-                //       cheaper than one lane + a broadcast) and solves its row against it, in place; the right-hand side rides along as one
-                //       more row (L y = b is solved by the factorisation itself: only the backward substitution is left afterwards)
-                //   P2  the trailing blocks (I, K), J < K <= I, take  -= X_I X_K^T  with one lane per block ROW: 6 outputs from 6 + 36 operands.
-                // The left-looking form it replaces recomputed every element of a block column as a dot product over all earlier columns with one
-                // lane per ELEMENT: 2 LDS operands per FMA, and its column update was bound by LDS bandwidth (in-kernel clocks, per block column:
-                // update 1.84 k cycles, diagonal + rows 2.4 k, barriers 0.55 k).  L_JJ goes to a side array (Ld): nothing reads it before the solve.
-                for (int J = 0; J < nk && ok2; ++J) {
-                    const int m = nk - J - 1, nrows = m * 6;
-                    const bool rhs_row = tid == kLmBlock - 1;
-                    if (tid < nrows || tid == 0 || rhs_row) {
-                        double D[21]; // lower triangle, row-major: (i,j) -> i*(i+1)/2 + j
-#pragma unroll
-                        for (int i = 0; i < 6; ++i)
-#pragma unroll
-                            for (int j = 0; j <= i; ++j) D[i * (i + 1) / 2 + j] = sm.S[(6 * J + i) * np + 6 * J + j];
-                        bool good = true;
-                        double rd[6];
-#pragma unroll
-                        for (int j = 0; j < 6; ++j) {
-                            double d = D[j * (j + 1) / 2 + j];
-#pragma unroll
-                            for (int kk = 0; kk < j; ++kk) d -= D[j * (j + 1) / 2 + kk] * D[j * (j + 1) / 2 + kk];
-                            if (!(d > 0.0) || !isfinite(d)) good = false;
-                            rd[j] = rsqrt_nr(d); // the dependent chain of the factorisation: no IEEE sqrt / division on it
-                            D[j * (j + 1) / 2 + j] = d * rd[j];
-#pragma unroll
-                            for (int i = j + 1; i < 6; ++i) {
-                                double v = D[i * (i + 1) / 2 + j];
-#pragma unroll
-                                for (int kk = 0; kk < j; ++kk) v -= D[i * (i + 1) / 2 + kk] * D[j * (j + 1) / 2 + kk];
-                                D[i * (i + 1) / 2 + j] = v * rd[j];
-                            }
-                        }
-                        if (tid < nrows || rhs_row) {
-                            double* rowv = rhs_row ? &sm.bs[6 * J] : &sm.S[(6 * (J + 1) + tid) * np + 6 * J];
-                            double x[6];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) {
-                                double v = rowv[c];
-#pragma unroll
-                                for (int kk = 0; kk < c; ++kk) v -= x[kk] * D[c * (c + 1) / 2 + kk];
-                                x[c] = v * rd[c];
-                            }
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) rowv[c] = x[c];
-                        }
-                        if (tid == 0) {
-                            if (!good) sm.flag[1] = 1;
-#pragma unroll
-                            for (int i = 0; i < 21; ++i) sm.Ld[24 * J + i] = D[i];
-#pragma unroll
-                            for (int i = 0; i < 6; ++i) sm.rdiag[6 * J + i] = rd[i];
-                        }
-                    }
-                    PH(16);
-                    __syncthreads();
-                    PH(17);
-                    if (sm.flag[1]) { ok2 = false; break; } // uniform
-                    // P2: trailing update.  Items: (block pair (a, b), a >= b, of the m block rows below; row r) and, for the right-hand side, one
-                    // item per block b
-                    const int npair = m * (m + 1) / 2, nitem = npair * 6 + m;
-                    for (int t = tid; t < nitem; t += kLmBlock) {
-                        const double* xi; double* out; int Kb;
-                        if (t < npair * 6) {
-                            const int pr = t / 6, r = t - 6 * pr;
-                            int a = 0, rem = pr;
-                            while (rem > a) { rem -= a + 1; ++a; }
-                            const int Ib = J + 1 + a; Kb = J + 1 + rem;
-                            xi = &sm.S[(6 * Ib + r) * np + 6 * J]; out = &sm.S[(6 * Ib + r) * np + 6 * Kb];
-                        } else { Kb = J + 1 + (t - npair * 6); xi = &sm.bs[6 * J]; out = &sm.bs[6 * Kb]; }
-                        const double2* xi2 = reinterpret_cast<const double2*>(xi);
-                        const double2 a0 = xi2[0], a1 = xi2[1], a2 = xi2[2];
-                        double2* o2 = reinterpret_cast<double2*>(out);
-                        double2 o[3] = {o2[0], o2[1], o2[2]};
-                        double v[6] = {o[0].x, o[0].y, o[1].x, o[1].y, o[2].x, o[2].y};
-#pragma unroll
-                        for (int c = 0; c < 6; ++c) {
-                            const double2* xk = reinterpret_cast<const double2*>(&sm.S[(6 * Kb + c) * np + 6 * J]);
-                            const double2 b0 = xk[0], b1 = xk[1], b2 = xk[2];
-                            v[c] -= (a0.x * b0.x + a0.y * b0.y) + (a1.x * b1.x + a1.y * b1.y) + (a2.x * b2.x + a2.y * b2.y);
-                        }
-                        o2[0] = make_double2(v[0], v[1]); o2[1] = make_double2(v[2], v[3]); o2[2] = make_double2(v[4], v[5]);
-                    }
-                    PH(18);
-                    __syncthreads();
-                    PH(19);
-                }
-                PH(7);
-                if (sm.flag[1]) ok2 = false;
-                __syncthreads();
-                PH(20);
-                if (tid == 0) sm.flag[1] = 0;
-                if (ok2) {
-                    // backward substitution L^T x = y by wave 0, block by block from the last: lane i carries t_i = y_i - sum over the finished
-                    // unknowns (and t_{i+64}: np <= 128).  Per block: its six right-hand sides go to every lane (readlane), every lane solves the
-                    // 6x6 triangle L_JJ^T x = t redundantly (L_JJ from the side array, wave-uniform reads), and the unknowns below take
-                    // t_i -= sum_c L[6J+c][i] x_c with the six rows of L read along i (consecutive lanes, consecutive addresses).
-                    if (wave == 0) {
-                        double u0 = lane < np ? sm.bs[lane] : 0.0, u1 = lane + 64 < np ? sm.bs[lane + 64] : 0.0;
-                        for (int J = nk - 1; J >= 0; --J) {
-                            double Lr0[6], Lr1[6], Ld[21], rdj[6], t[6], x[6];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) {
-                                const int r = 6 * J + c;
-                                Lr0[c] = lane < 6 * J ? sm.S[r * np + lane] : 0.0;
-                                Lr1[c] = (6 * J > 64 && lane + 64 < 6 * J) ? sm.S[r * np + lane + 64] : 0.0;
-                                rdj[c] = sm.rdiag[r];
-                            }
-#pragma unroll
-                            for (int i = 0; i < 21; ++i) Ld[i] = sm.Ld[24 * J + i];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) {
-                                const int r = 6 * J + c; // wave-uniform
-                                t[c] = r >= 64 ? readlane_f64(u1, r - 64) : readlane_f64(u0, r);
-                            }
-#pragma unroll
-                            for (int c = 5; c >= 0; --c) {
-                                double v = t[c];
-#pragma unroll
-                                for (int k = c + 1; k < 6; ++k) v -= Ld[k * (k + 1) / 2 + c] * x[k];
-                                x[c] = v * rdj[c];
-                            }
-                            if (lane == 0)
-#pragma unroll
-                                for (int c = 0; c < 6; ++c) sm.xp[6 * J + c] = x[c];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) { u0 = fma(-Lr0[c], x[c], u0); u1 = fma(-Lr1[c], x[c], u1); }
-                        }
-                    }
-                    PH(21);
-                } else {
-                    for (int i = tid; i < np; i += kLmBlock) sm.xp[i] = 0;
-                }
-                __syncthreads();
+                // Cholesky of S on dense rows with the right-hand side riding along, then the backward substitution by wave 0: reduced_solve
+                // (lm_solver.h).  Its clock instants are the phases 16-19 (per block column), 7, 20 and 21.
+                ok2 = reduced_solve<kLmBlock>(DenseRows<6>{sm.S, np}, sm.bs, sm.Ld, sm.rdiag, sm.xp, &sm.flag[1], nk, tid, lane, wave, ok2, [&](int i) {
+                    constexpr int ph[7] = {16, 17, 18, 19, 7, 20, 21};
+                    PH(ph[i]);
+                });
             } else {
                 // pose-only: block-diagonal system, one thread per pose
                 if (tid < nk) {
@@ -1177,12 +1056,7 @@ __global__ __launch_bounds__(kLmBlock, kLmMinWaves) void lm_window_kernel(LmKern
                 }
             }
             if (tid < np) scale_part += sm.xp[tid] * (lambda * sm.xp[tid] + sm.bp[tid]);
-            if (tid < nk) {
-                double E[7];
-                se3::exp(&sm.xp[6 * tid], E);
-                se3::mul(E, &sm.T[7 * tid], &sm.TTrial[7 * tid]);
-                expand_pose(&sm.TTrial[7 * tid], &sm.RtTrial[12 * tid]);
-            }
+            if (tid < nk) trial_pose(&sm.xp[6 * tid], &sm.T[7 * tid], &sm.TTrial[7 * tid], &sm.RtTrial[12 * tid]);
             scale = block_sum(scale_part, sm.red) + 1e-3;
             } // !boot
             PH(9);
@@ -1228,17 +1102,14 @@ __global__ __launch_bounds__(kLmBlock, kLmMinWaves) void lm_window_kernel(LmKern
     int newly_flagged = 0;   // this thread cleared the flag of a landmark that entered the pass flagged in
     if (classify && !IMPL) {
         double th = delta; // optimization.cpp:154: chi2_th is both the Huber delta and the initial classification threshold
-        for (int iteration = 0; iteration < 5; ++iteration) {
-            double out = 0, in = 0;
+        chi2_threshold(th, [&](double t, int, double& in, double& out) { // recounts
+            out = 0; in = 0;
             for (int j = tid; j < ntot; j += kLmBlock) {
-                if (chi2k[j] > th) out += 1; else in += 1;
+                if (chi2k[j] > t) out += 1; else in += 1;
             }
             out = block_sum(out, sm.red);
             in = block_sum(in, sm.red);
-            const double ratio = in / (in + out);
-            if (ratio > 0.5) break;
-            th *= 2;
-        }
+        });
         // last edge of the landmark wins (ascending edge order).  lm_ptr -> kf_pos -> chi2 is a chain of three dependent loads: four
         // landmarks per lane per trip, level by level (a strided loop is left serial: one round trip per load per landmark)
         for (int l0 = tid; l0 < nl; l0 += 4 * kLmBlock) {
@@ -1388,6 +1259,9 @@ __global__ __launch_bounds__(64) void pnp_wave_kernel(const float* __restrict__ 
         }
         return total;
     };
+    // This loop keeps g2o's damping rule, the statistics and the trial pose written out instead of calling lm_solver.h: with LmDamping the compiler
+    // ordered the sums of the loop differently, and with trial_pose alone it fused other products of exp(x) T -- either way the poses moved in the last
+    // bits (up to 2.7e-9, other trial counts at convergence) on 4 of 6 problems below 1024 points.
     double H[36], g[6], lambda = 0, ni = 2, currentChi = 0;
     int it = 0, total_trials = 0;
     for (it = 0; it < iters; ++it) {
@@ -1687,7 +1561,8 @@ __global__ __launch_bounds__(64 * W, kMinWaves) void pose_only_wave_kernel(LmKer
         return t;
     };
     vslam_lm_stats* st = a.stats ? a.stats + w : nullptr;
-    double lambda = 0, ni = 2, currentChi = 0;
+    LmDamping lm;
+    double currentChi = 0;
     int pc = 0; // which of sm.T / sm.R [0], [1] holds the current pose; sm.R[2] = the last evaluated trial (g2o's edge errors reflect it)
     int cur = 0, it = 0, total_trials = 0, pb = 0, fb = 0;
     if (iters > 0) { // the initial state goes through the same evaluation + linearisation
@@ -1704,13 +1579,12 @@ __global__ __launch_bounds__(64 * W, kMinWaves) void pose_only_wave_kernel(LmKer
         for (int k = 0; k < nk; ++k)
 #pragma unroll
             for (int d = 0; d < 6; ++d) md = fmax(md, fabs(sm.H[cur][k][7 * d]));
-        lambda = 1e-5 * md;
+        lm.init(md);
         if (st && tid == 0) st->chi2_init = currentChi;
     }
     POH(1);
     for (it = 0; it < iters; ++it) {
-        double rho_gain = 0;
-        int qmax = 0;
+        lm.begin_iteration();
         bool again = true;
         while (again) {
             // the steps of this wave's keyframes, computed in every lane; a list of them is parked in sm.x until the window knows that every factorisation went through
@@ -1723,7 +1597,7 @@ __global__ __launch_bounds__(64 * W, kMinWaves) void pose_only_wave_kernel(LmKer
                 for (int i = 0; i < 36; ++i) Hk[i] = sm.H[cur][k][i];
 #pragma unroll
                 for (int i = 0; i < 6; ++i) gk[i] = sm.g[cur][k][i];
-                if (!chol6_solve(Hk, lambda, gk, x) && lane == 0) sm.flag[fb] = 1;
+                if (!chol6_solve(Hk, lm.lambda, gk, x) && lane == 0) sm.flag[fb] = 1;
                 if constexpr (W == kMaxKf) {
 #pragma unroll
                     for (int i = 0; i < 6; ++i) xw[i] = x[i];
@@ -1743,16 +1617,14 @@ __global__ __launch_bounds__(64 * W, kMinWaves) void pose_only_wave_kernel(LmKer
                 const int k = kf_at(q);
                 double sc = 0;
                 {
-                    double x[6], E[7], Tc[7], Tt[7], Rtt[12];
+                    double x[6], Tc[7], Tt[7], Rtt[12];
 #pragma unroll
                     for (int i = 0; i < 6; ++i) x[i] = !ok2 ? 0.0 : W == kMaxKf ? xw[i] : sm.x[k][i];
 #pragma unroll
-                    for (int i = 0; i < 6; ++i) sc += x[i] * (lambda * x[i] + sm.g[cur][k][i]);
+                    for (int i = 0; i < 6; ++i) sc += x[i] * (lm.lambda * x[i] + sm.g[cur][k][i]);
 #pragma unroll
                     for (int i = 0; i < 7; ++i) Tc[i] = sm.T[pc][k][i];
-                    se3::exp(x, E);
-                    se3::mul(E, Tc, Tt);
-                    expand_pose(Tt, Rtt);
+                    trial_pose(x, Tc, Tt, Rtt);
                     __builtin_amdgcn_wave_barrier();
                     if (lane == 0) {
 #pragma unroll
@@ -1769,43 +1641,33 @@ __global__ __launch_bounds__(64 * W, kMinWaves) void pose_only_wave_kernel(LmKer
             }
             __syncthreads();
             POH(6);
-            double tempChi = sum_kf(sm.part[pb]);
+            const double tempChi = sum_kf(sm.part[pb]);
             const double scale = sum_kf(sm.spart[pb]) + 1e-3;
             pb ^= 1;
-            if (!ok2) tempChi = 1.7976931348623157e308;
-            rho_gain = (currentChi - tempChi) / scale;
-            if (rho_gain > 0 && isfinite(tempChi)) {
-                double alpha = 1. - pow(2 * rho_gain - 1, 3);
-                alpha = fmin(alpha, 2. / 3.);
-                lambda *= fmax(1. / 3., alpha);
-                ni = 2;
+            if (lm.step(currentChi, tempChi, scale, ok2)) {
                 currentChi = tempChi;
                 pc ^= 1;
                 cur ^= 1;
-            } else {
-                lambda *= ni;
-                ni *= 2;
             }
-            ++qmax;
-            again = (rho_gain < 0) && qmax < 10;
+            again = lm.again();
         }
-        total_trials += qmax;
-        if (st && tid == 0 && it < VSLAM_LM_MAX_ITERS) { st->chi2_iter[it] = currentChi; st->lambda_iter[it] = lambda; st->trials_iter[it] = qmax; }
-        if (qmax == 10 || rho_gain == 0) { ++it; break; }
+        total_trials += lm.qmax;
+        if (tid == 0) lm_stats_iter(st, it, currentChi, lm);
+        if (lm.iteration_ends()) { ++it; break; }
     }
-    if (st && tid == 0) { st->iterations = it; st->total_trials = total_trials; st->chi2_final = currentChi; st->lambda_final = lambda; }
+    if (tid == 0) lm_stats_final(st, it, total_trials, currentChi, lm);
     POH(7);
     // ---- chi2 of every active edge at the last evaluated state, then the adaptive threshold (optimization.cpp:224-252)
 #pragma unroll 1
     for (int q = 0; q < nheld; ++q) { const int k = kf_at(q); evaluate(sm.R[2][k], false, 0, true, k); }
     double th = delta; // :154: chi2_th is both the Huber delta and the initial classification threshold
     int cb = 0;
-    for (int iteration = 0; iteration < 5; ++iteration) {
+    chi2_threshold(th, [&](double t, int, double& in, double& out) { // sums the per-keyframe counts
 #pragma unroll 1
         for (int q = 0; q < nheld; ++q) {
             const int k = kf_at(q), kb = sm.kbeg[k], ke = sm.kbeg[k + 1];
             int cin = 0, cout = 0;
-            for (int j = kb + lane; j < ke; j += 64) { if (chik[j] > th) ++cout; else ++cin; }
+            for (int j = kb + lane; j < ke; j += 64) { if (chik[j] > t) ++cout; else ++cin; }
             for (int o = 32; o > 0; o >>= 1) { cin += __shfl_xor(cin, o); cout += __shfl_xor(cout, o); }
             if (lane == 0) { sm.cin[cb][k] = cin; sm.cout[cb][k] = cout; }
         }
@@ -1813,10 +1675,8 @@ __global__ __launch_bounds__(64 * W, kMinWaves) void pose_only_wave_kernel(LmKer
         int tin = 0, tout = 0;
         for (int k = 0; k < nk; ++k) { tin += sm.cin[cb][k]; tout += sm.cout[cb][k]; }
         cb ^= 1;
-        const double ratio = (double)tin / (double)(tin + tout);
-        if (ratio > 0.5) break; // uniform
-        th *= 2;
-    }
+        in = (double)tin; out = (double)tout;
+    });
     if (ka.want_chi2) { // chi2 in the caller's edge order, 0 for the edges of excluded landmarks (the flags are still the pass's input here)
         double* chi2 = a.chi2 + e0;
         for (int e = tid; e < ne; e += kBlock) if (!inl[lmi[e]]) chi2[e] = 0.0;

@@ -20,15 +20,22 @@ def vo_res(pkg):
     ctx.close()
 
 
+# rows of the table below, by (n_lm, seed), that do not fit the kernel's LDS budget (too many rows of multi-observation landmarks): the kernel hands
+# them to the general kernel; every other row must run on the resident kernel
+DEFERRED_ROWS = {(3000, 7), (2500, 5)}
+
+
 @pytest.mark.parametrize("n_kf,n_lm,seed,iters,min_obs,max_obs", [(10, 300, 2, 5, 2, 5), (10, 3000, 7, 10, 2, 5), (10, 1000, 9, 10, 1, 3), (12, 800, 21, 8, 2, 5),
-                                                                   (3, 120, 21, 8, 2, 3), (1, 60, 21, 8, 1, 1), (10, 2500, 5, 10, 1, 10)])
+                                                                   (11, 400, 21, 8, 2, 5), (3, 120, 21, 8, 2, 3), (1, 60, 21, 8, 1, 1), (10, 2500, 5, 10, 1, 10)])
 def test_resident_local_ba_parity(vo_res, oracle, synth, n_kf, n_lm, seed, iters, min_obs, max_obs):
     """one optimize_map call (host tier): LM trajectory, poses, landmarks, per-edge chi2, threshold and flags vs the oracle; shuffled edge order;
-    windows with single-observation landmarks (the Woodbury path), 12 keyframes, one keyframe, tracks through the whole window"""
+    windows with single-observation landmarks (the Woodbury path), 12 keyframes, one keyframe, tracks through the whole window.  The keyframe counts
+    reach both edges of the shared backward substitution: 11 (the unknowns cross 64 lanes) and 12 (rows of L are read past lane 64 as well)"""
     w = synth.ba_window(n_kf=n_kf, n_lm=n_lm, seed=seed, min_obs=min_obs, max_obs=min(max_obs, n_kf))
     perm = np.random.default_rng(seed).permutation(len(w["kf_idx"]))
     kf, lm, uv = w["kf_idx"][perm], w["lm_idx"][perm], w["uv"][perm]
     r = vo_res.optimize_map(w["T0"], w["xyz"], kf, lm, uv, True, True, iters)
+    assert vo_res.ba_deferred(1)[0] == int((n_lm, seed) in DEFERRED_ROWS), "which kernel ran the window"
     T, xyz, chi2, st = oracle.local_ba(w["T0"], w["xyz"], kf, lm, uv, iters=iters, update_poses=True, update_lms=True)
     _stats_close(r["stats"], st)
     assert np.allclose(r["T"], T, rtol=RTOL, atol=1e-6)
