@@ -973,6 +973,24 @@ int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int
  *   q = (int)rint(fmin(sdf, tau) * kq), in [-1024, 1024]
  *   W += 1;  Sq += q + 1024;  if (sdf <= tau) { Wc += 1;  I += gray[b][r * pitch + c]; }
  * `step` thins the allocation only.  The sums are exact while W < 2^20; an extraction that meets a larger W sets status bit 1 and skips the voxel.
+ * RE-INTEGRATION (vslam_tsdf_reintegrate_dev): a frame taken out of the field at the pose it went in with and put in at a corrected one.  The sums above
+ * are plain integer sums -- no running average, no clamp, no weight cap at integration time -- so taking a frame out is INTEGRATION's rule subtracted,
+ * exactly.  A frame may only be subtracted from the blocks it was added to.  Blocks enter the block list in claim order, so the blocks a call's frames
+ * reached are the list positions [0, n) with n the claimed-block count after that call's allocation: the frame's REACH (vslam_tsdf_reach_dev after the
+ * integrate call).  A frame b takes part when d_map_id[b] is in 0 .. 1022; its OLD side takes part when T_old[b] is finite by ALLOCATION's test, its NEW
+ * side when T_new[b] is.  An all-NaN old pose makes the frame a plain integration, an all-NaN new pose a removal; a pose that is not finite is how a side
+ * is switched off: it does not count in n_frames_skipped and does not set status bit 2.  With n0 the claimed-block count before the call:
+ *   Allocation: ALLOCATION's rule over the NEW sides only (same disparity, gates and step).
+ *   Accumulation, for every claimed block of the frame's map -- those this call just claimed included -- and every voxel: add = the sum of INTEGRATION's
+ *   four contributions over the NEW sides, operation for operation as INTEGRATION evaluates them, at T_new; sub = the same sum over the OLD sides at
+ *   T_old, counting only frames with (list position of the block) < min(reach[b], n0).
+ *   Update: if every one of the four stored sums is >= its component of sub, the voxel becomes stored + add - sub (one read-modify-write per voxel and
+ *   call).  Otherwise the voxel keeps its stored value -- neither side is applied -- and status bit 3 is set: the call was given a disparity, pose,
+ *   gate or reach that is not the one the frame went in with.
+ * What follows: the caller passes the same disparity, gray image, z_min, z_max and old pose BYTES the frame was integrated with; `step` thins the
+ * allocation only and need not match.  Blocks whose voxels all return to zero stay claimed (linear probing has no deletion here); no voxel of them is
+ * good, so extraction, mesh and render do not see them.  After vslam_tsdf_load_blocks_dev the reach of frames integrated before the dump is not
+ * recoverable (the loader's claim order is its own).  The 2^20 weight limit applies to the sums as stored after the update.
  * EXTRACTION: num(v) = (int64)Sq - 1024 * W, D(v) = (double)num / (double)W; good(v): v lies in a claimed block, max(min_weight, 1) <= W < 2^20 and
  * Wc >= 1.  For a good voxel a and each axis e, with b = a + e (in whichever block): the edge crosses when b is good and (num_a > 0) != (num_b > 0).
  *   t = D_a / (D_a - D_b);  position along e = ((double)i_a + 0.5 + t) * vs, the other two axes ((double)i + 0.5) * vs
@@ -1003,7 +1021,7 @@ struct vslam_tsdf_stats {
     uint64_t n_frames_skipped;  /* frames with a map id whose pose was not finite                     */
     uint64_t n_pairs_visited;   /* (block, frame) pairs of equal map id the integration has looked at */
     uint64_t n_pairs_kept;      /* ... of which the cull kept                                         */
-    uint32_t status;            /* bit 0: pool full; bit 1: a weight reached 2^20; bit 2: a frame was skipped for its pose */
+    uint32_t status;            /* bit 0: pool full; bit 1: a weight reached 2^20; bit 2: a frame was skipped for its pose; bit 3: a re-integration met a sum below what it was to take out */
     int32_t struct_size;        /* sizeof(struct vslam_tsdf_stats) of the caller's header: set by the caller, checked */
 };
 typedef struct vslam_surfel {   /* one zero-crossing voxel edge (48 bytes) */
@@ -1027,6 +1045,18 @@ int vslam_tsdf_stats(vslam_tsdf_map* tm, struct vslam_tsdf_stats* host);
  * first.  Either skips a (block, frame) pair only when no voxel of the block can pass the rule. */
 int vslam_tsdf_integrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
                              int w, int h, int B, const double* d_T_c_w, const int32_t* d_map_id, double z_min, double z_max, int step);
+/* The number of blocks claimed so far into *d_out (uint32, device, 4-byte aligned), asynchronously on the context stream: called after an integrate or
+ * re-integrate call it yields that call's reach (RE-INTEGRATION) without a host round trip. */
+int vslam_tsdf_reach_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, uint32_t* d_out);
+/* RE-INTEGRATION of B frames: the arguments and refusals of vslam_tsdf_integrate_dev with two pose arrays (B x 7 each) and d_reach (B uint32: the reach
+ * each frame went in with; a value above the list length counts as n0).  A null d_T_old, d_T_new or d_reach with B > 0 is refused; B == 0 is a no-op
+ * that succeeds.  Both forms of "tsdf_form" give the same sums: 0 walks the old sides, then the new sides per block; 1 writes two frame masks per block
+ * first, the old one with the reach test folded in.  n_pairs_visited / n_pairs_kept count both sides (an old side is visited where its reach admits the
+ * block).  The first call on a map grows the old sides' tables -- 128 bytes per frame of max_batch and 8 * ceil(max_batch / 64) per block, counted in
+ * vslam_device_bytes -- which synchronises the context stream; the kernels are asynchronous on it. */
+int vslam_tsdf_reintegrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
+                               int w, int h, int B, const double* d_T_old, const double* d_T_new, const int32_t* d_map_id,
+                               const uint32_t* d_reach, double z_min, double z_max, int step);
 /* The crossing edges of map map_id (-1: every map) into d_out (`capacity` vslam_surfel, 16-byte aligned) and, when given, their map ids into
  * d_map_out; *d_n_out (uint64, device) = the full count even when it exceeds `capacity`.  The order is unspecified: sort by (map, ix, iy, iz, axis). */
 int vslam_tsdf_extract_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_weight, vslam_surfel* d_out, int32_t* d_map_out, size_t capacity,

@@ -103,7 +103,8 @@ VOXEL_MAX_MAP = 1022
 
 
 class TsdfStats(C.Structure):
-    """struct vslam_tsdf_stats: the counters of a surface map (status bit 0: pool full, bit 1: a weight reached 2^20, bit 2: a frame skipped for its pose)"""
+    """struct vslam_tsdf_stats: the counters of a surface map (status bit 0: pool full, bit 1: a weight reached 2^20, bit 2: a frame skipped for its pose,
+    bit 3: a re-integration met a sum below what it was to take out)"""
     _fields_ = [("n_blocks", C.c_uint64), ("n_samples", C.c_uint64), ("n_dropped_range", C.c_uint64), ("n_dropped_full", C.c_uint64),
                 ("n_frames_skipped", C.c_uint64), ("n_pairs_visited", C.c_uint64), ("n_pairs_kept", C.c_uint64), ("status", C.c_uint32), ("struct_size", C.c_int32)]
 
@@ -298,6 +299,8 @@ SIGNATURES = {
     "vslam_tsdf_create": (I, [P, D, I, I, C.POINTER(C.c_void_p)]), "vslam_tsdf_destroy": (None, [P]), "vslam_tsdf_clear": (I, [P]),
     "vslam_tsdf_stats": (I, [P, C.POINTER(TsdfStats)]),
     "vslam_tsdf_integrate_dev": (I, [P, P, P, P, Z, I, I, I, I, P, P, D, D, I]),
+    "vslam_tsdf_reach_dev": (I, [P, P, P]),
+    "vslam_tsdf_reintegrate_dev": (I, [P, P, P, P, Z, I, I, I, I, P, P, P, P, D, D, I]),
     "vslam_tsdf_extract_dev": (I, [P, P, I, I, P, P, Z, P]),
     "vslam_tsdf_blocks_dev": (I, [P, P, I, P, P, Z, P]),
     "vslam_tsdf_mesh_dev": (I, [P, P, I, I, P, P, Z, P, Z, P]),
@@ -1255,6 +1258,60 @@ class TsdfMap:
     def integrate_dev(self, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step=1):
         """VO.tsdf_integrate_dev into this map"""
         self.vo.tsdf_integrate_dev(self, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step)
+
+    def reach_dev(self, d_out):
+        """the number of blocks claimed so far into the device uint32 at d_out, asynchronously on the context stream: after an integrate call, the
+        reach of that call's frames (include/vslam_hip.h "RE-INTEGRATION")"""
+        self.vo._chk(self.vo.lib.vslam_tsdf_reach_dev(self.vo.h, self.h, d_out), "vslam_tsdf_reach_dev")
+
+    def reach(self):
+        """reach_dev() read back: an int; synchronises"""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d = torch.zeros(1, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.reach_dev(d.data_ptr())
+        self.vo.sync()
+        return int(d.cpu()[0]) & 0xFFFFFFFF
+
+    def reintegrate_dev(self, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T_old, d_T_new, d_map_id, d_reach, z_min, z_max, step=1):
+        """vslam_tsdf_reintegrate_dev on this map: B frames taken out at d_T_old within their d_reach and put in at d_T_new (a pose that is not
+        finite switches its side off); asynchronous on the context stream"""
+        self.vo._chk(self.vo.lib.vslam_tsdf_reintegrate_dev(self.vo.h, self.h, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T_old, d_T_new, d_map_id, d_reach,
+                                                            z_min, z_max, step), "vslam_tsdf_reintegrate_dev")
+
+    def reintegrate(self, disp, gray, T_old, T_new, map_id, reach, z_min, z_max, step=1):
+        """reintegrate_dev on host or torch arrays, for callers who keep disparities across steps: disp (B, h, w) float32, gray (B, h, pitch >= w) uint8
+        or None, T_old / T_new (B, 7) (None: all NaN, that side switched off), map_id (B,) or one id, reach (B,) or one value -- what reach() gave
+        after the call that integrated the frame.  The disparity, image, gates and old pose must be the ones the frame went in with.  Synchronises;
+        returns the reach of this call's new sides."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        def put(a, dtype, shape=None):
+            if isinstance(a, torch.Tensor):
+                a = a.to(device=dev, dtype=dtype)
+                return (a.expand(shape) if shape is not None else a).contiguous()
+            a = np.asarray(a)
+            return torch.from_numpy(np.array(np.broadcast_to(a, shape) if shape is not None else a)).to(device=dev, dtype=dtype)   # (a copy: the caller's array may be read-only)
+
+        d_disp = put(disp, torch.float32)
+        assert d_disp.dim() == 3, "disp: (B, h, w)"
+        B, h, w = (int(v) for v in d_disp.shape)
+        d_gray = None if gray is None else put(gray, torch.uint8)
+        assert d_gray is None or (d_gray.dim() == 3 and d_gray.shape[0] == B and d_gray.shape[1] == h and d_gray.shape[2] >= w), "gray: (B, h, pitch >= w)"
+        pitch = 0 if d_gray is None else int(d_gray.shape[2])
+        nan = np.full((B, 7), np.nan)
+        d_old = put(nan if T_old is None else T_old, torch.float64, (B, 7))
+        d_new = put(nan if T_new is None else T_new, torch.float64, (B, 7))
+        d_ids = put(map_id, torch.int32, (B,))
+        r = reach.detach().cpu().numpy() if isinstance(reach, torch.Tensor) else np.asarray(reach)
+        r = np.clip(np.broadcast_to(r.astype(np.int64), (B,)), 0, 0xFFFFFFFF).astype(np.uint32)   # (B numbers: the host is the simplest place to make them uint32)
+        d_reach = torch.from_numpy(r.view(np.int32).copy()).to(dev)
+        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream reads them)
+        self.reintegrate_dev(d_disp.data_ptr(), None if d_gray is None else d_gray.data_ptr(), h * pitch, pitch, w, h, B, d_old.data_ptr(), d_new.data_ptr(),
+                             d_ids.data_ptr(), d_reach.data_ptr(), float(z_min), float(z_max), int(step))
+        return self.reach()
 
     def _buffers(self, capacity, row_bytes):
         import torch

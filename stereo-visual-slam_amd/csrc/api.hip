@@ -294,6 +294,7 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "match_train_nearest_sel_kernel track_features_kernel frame_pairs_kernel kf_gate_pairs_kernel rectify_kernel ba_chain_kernels "
            "voxel_clear_kernel reproject_kernel voxel_insert_points_kernel voxel_fuse_kernel voxel_extract_kernel "
            "tsdf_clear_kernel tsdf_frames_kernel tsdf_alloc_kernel tsdf_cull_kernel tsdf_integrate_kernel tsdf_extract_kernel tsdf_blocks_kernel tsdf_mesh_vertex_kernel tsdf_mesh_tri_kernel tsdf_load_kernel "
+           "tsdf_reint_frames_kernel tsdf_reint_cull_kernel tsdf_reint_kernel "
            "tsdf_views_kernel tsdf_range_init_kernel tsdf_ray_range_kernel tsdf_render_kernel "
            "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel "
            "pose_graph_kernel full_ba_kernel project_match_kernel";
@@ -1868,6 +1869,7 @@ void vslam_tsdf_destroy(vslam_tsdf_map* tm) {
     m->ctx->dev_bytes -= m->bytes;
     m->mesh.release();
     m->render.release();
+    m->reint.release();
     delete m;
 }
 
@@ -1909,6 +1911,36 @@ int vslam_tsdf_integrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* d_
     }
     VS_ENTER(c);
     return launch_tsdf_integrate(m->t, a, d_gray, img_bytes, pitch, d_map_id, tsdf_form(c), c->stream);
+}
+
+int vslam_tsdf_reach_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, uint32_t* d_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_reach_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 4) { set_error("vslam_tsdf_reach_dev: d_out is null or not 4-byte aligned"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    // the block counter never exceeds 2^log2_blocks <= 2^22: its low word is the count
+    VS_HIP(hipMemcpyAsync(d_out, m->t.counters, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    return VSLAM_OK;
+}
+
+int vslam_tsdf_reintegrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
+                               int w, int h, int B, const double* d_T_old, const double* d_T_new, const int32_t* d_map_id,
+                               const uint32_t* d_reach, double z_min, double z_max, int step) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_reintegrate_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (B == 0) return VSLAM_OK;
+    if (!d_map_id || !d_T_old || !d_T_new || !d_reach) { set_error("vslam_tsdf_reintegrate_dev: null d_map_id, d_T_old, d_T_new or d_reach"); return VSLAM_ERR_ARG; }
+    VoxelImages a;
+    if (int rc = voxel_images(c, "vslam_tsdf_reintegrate_dev", d_disparity, w, h, B, d_T_new, z_min, z_max, step, a)) return rc;
+    if (d_gray && (pitch < w || img_bytes < (size_t)pitch * h)) {
+        set_error("vslam_tsdf_reintegrate_dev: pitch %d / img_bytes %zu do not hold a %d x %d image", pitch, img_bytes, w, h); return VSLAM_ERR_ARG;
+    }
+    VS_ENTER(c);
+    if (int rc = m->reint.reserve(tsdf_reint_table_bytes(m->t, c->p.max_batch), c->stream)) return rc;
+    const TsdfReint r = tsdf_reint_tables(m->t, c->p.max_batch, m->reint.p, d_reach);
+    return launch_tsdf_reintegrate(m->t, r, a, d_gray, img_bytes, pitch, d_T_old, d_map_id, tsdf_form(c), c->stream);
 }
 
 int vslam_tsdf_extract_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_weight, vslam_surfel* d_out, int32_t* d_map_out, size_t capacity,

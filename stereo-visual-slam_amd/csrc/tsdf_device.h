@@ -1,6 +1,7 @@
 // tsdf_device.h -- what the surface map's two files share (tsdf_kernels.hip: allocation, integration, extraction; tsdf_mesh_kernels.hip: mesh and
 // block loader): the block key, the claim and the lookup in the pool's hash table, the voxel predicates of EXTRACTION and the surfel of a crossing
 // edge.  One definition each, so an extracted surfel and a mesh vertex are the same bits.  Include it from a file compiled with FMA contraction off.
+// Also the frame row, the cull and the per-sample rule of INTEGRATION, which tsdf_kernels.hip adds with and tsdf_reint_kernels.hip adds and subtracts with.
 #pragma once
 #include "vslam_internal.h"
 
@@ -107,6 +108,76 @@ __device__ __forceinline__ void tsdf_surfel(const TsdfTable& t, const uint4* lv,
     o[0] = make_uint4((uint32_t)ia[0], (uint32_t)ia[1], (uint32_t)ia[2], (uint32_t)e);
     o[1] = make_uint4(va.x < vb.x ? va.x : vb.x, __float_as_uint(x), __float_as_uint(y), __float_as_uint(z));
     o[2] = make_uint4(__float_as_uint((float)(g0 / norm)), __float_as_uint((float)(g1 / norm)), __float_as_uint((float)(g2 / norm)), __float_as_uint(inten));
+}
+
+// One row of a frame table (kTsdfFrameDoubles doubles: R, t, the inverse translation, the map id or -1) from a pose and a map id; true when the pose
+// is finite by ALLOCATION's test: its seven numbers, the rotation matrix and the inverse translation formed from them
+__device__ __forceinline__ bool tsdf_frame_row(const double* Tb, int m, double* f) {
+    double R[9], Rinv[9], tinv[3];
+    se3::rotmat(Tb, R);
+    voxel_inverse_pose(Tb, Rinv, tinv);
+    bool fin = true;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) fin = fin && isfinite(Tb[i]);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) fin = fin && isfinite(R[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) fin = fin && isfinite(tinv[i]);
+    const bool mapped = m >= 0 && m <= kVoxelMaxMap;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) f[i] = R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { f[9 + i] = Tb[4 + i]; f[12 + i] = tinv[i]; }
+    f[15] = (mapped && fin) ? (double)m : -1.0;
+    return fin;
+}
+
+// what the cull needs of the camera: the slopes of the image rectangle grown by half a pixel and the lengths of the four side planes' normals
+struct TsdfCull { double al, ar, at, ab, nl, nr, nt, nb, rad; };
+
+// the cull of a call's camera (fx or fy <= 0: rad is infinite and nothing is culled)
+static inline TsdfCull tsdf_cull_of(const TsdfTable& t, const VoxelImages& a) {
+    TsdfCull cu;
+    cu.al = (-0.5 - a.cx) / a.fx; cu.ar = ((double)a.w - 0.5 - a.cx) / a.fx; cu.at = (-0.5 - a.cy) / a.fy; cu.ab = ((double)a.h - 0.5 - a.cy) / a.fy;
+    cu.nl = sqrt(1.0 + cu.al * cu.al); cu.nr = sqrt(1.0 + cu.ar * cu.ar); cu.nt = sqrt(1.0 + cu.at * cu.at); cu.nb = sqrt(1.0 + cu.ab * cu.ab);
+    cu.rad = (a.fx > 0 && a.fy > 0) ? 7.0 * (double)t.vs : (double)INFINITY;
+    return cu;
+}
+
+// The cull, an optimisation only: false when NO voxel of the block can pass the rule in frame f.  Every voxel centre lies within 3.5 sqrt(3) < 6.07
+// voxels of the block's centre C; cu.rad is 7 voxels.  A voxel passes only with P[2] > vs and -0.5 <= u < w - 0.5, that is x >= al z and x < ar z
+// for z > 0 (fx > 0), likewise in y: a sphere wholly on the outer side of one of these five planes holds no such voxel.  (With fx or fy <= 0 the
+// launcher sets rad to infinity and nothing is culled.)
+__device__ __forceinline__ bool tsdf_may_pass(const double* __restrict__ f, const TsdfBlockId& b, double vs, const TsdfCull& cu) {
+    const double C0 = ((double)(8 * b.bx) + 4.0) * vs, C1 = ((double)(8 * b.by) + 4.0) * vs, C2 = ((double)(8 * b.bz) + 4.0) * vs;
+    const double P0 = f[0] * C0 + f[1] * C1 + f[2] * C2 + f[9], P1 = f[3] * C0 + f[4] * C1 + f[5] * C2 + f[10], P2 = f[6] * C0 + f[7] * C1 + f[8] * C2 + f[11];
+    if (!(P2 + cu.rad > vs)) return false;
+    if (P0 - cu.al * P2 < -cu.rad * cu.nl) return false;
+    if (cu.ar * P2 - P0 < -cu.rad * cu.nr) return false;
+    if (P1 - cu.at * P2 < -cu.rad * cu.nt) return false;
+    if (cu.ab * P2 - P1 < -cu.rad * cu.nb) return false;
+    return true;
+}
+
+struct TsdfSums { uint32_t W = 0, Sq = 0, Wc = 0, I = 0; };
+
+// one voxel (centre X in the world) in one frame: the rule of include/vslam_hip.h, f64 in the written order
+__device__ __forceinline__ void tsdf_sample(const double* __restrict__ f, int b, double X0, double X1, double X2, const VoxelImages& a, const uint8_t* __restrict__ gray,
+                                            size_t img_bytes, int pitch, double vs, double tau, double kq, TsdfSums& v) {
+#pragma clang fp contract(off)
+    const double P0 = f[0] * X0 + f[1] * X1 + f[2] * X2 + f[9], P1 = f[3] * X0 + f[4] * X1 + f[5] * X2 + f[10], P2 = f[6] * X0 + f[7] * X1 + f[8] * X2 + f[11];
+    if (!(P2 > vs)) return;
+    const double u = a.fx * (P0 / P2) + a.cx, w = a.fy * (P1 / P2) + a.cy;
+    const double cf = floor(u + 0.5), rf = floor(w + 0.5);
+    if (!(cf >= 0.0 && cf < (double)a.w && rf >= 0.0 && rf < (double)a.h)) return;
+    const int c = (int)cf, r = (int)rf;
+    const double z = a.fx * a.b / (double)a.disp[((size_t)b * a.h + r) * a.w + c];
+    if (!(z > a.z_min && z < a.z_max)) return;
+    const double sdf = z - P2;
+    if (sdf < -tau) return;
+    const int q = (int)rint(fmin(sdf, tau) * kq);
+    v.W += 1u; v.Sq += (uint32_t)(q + 1024);
+    if (sdf <= tau) { v.Wc += 1u; v.I += gray ? (uint32_t)gray[(size_t)b * img_bytes + (size_t)r * pitch + c] : 0u; }
 }
 
 static unsigned tsdf_list_grid(const TsdfTable& t) { // a kernel that walks the block list: no more workgroups than there are slots

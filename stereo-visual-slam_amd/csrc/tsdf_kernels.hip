@@ -14,16 +14,14 @@
 // waits for another to publish an index: claiming is a relaxed key load, a 64-bit compare-and-swap only on "empty", linear probing over at most
 // kTsdfMaxProbe slots.  A sample that finds no slot is dropped and counted.
 // Compiled with FMA contraction off (the Makefile's default): every sum is bit-exact against tests/tsdf_ref.py.
-// The key, the claim, the lookup, the voxel predicates and the surfel arithmetic are in tsdf_device.h, shared with tsdf_mesh_kernels.hip.
+// The key, the claim, the lookup, the voxel predicates and the surfel arithmetic are in tsdf_device.h, shared with tsdf_mesh_kernels.hip; the frame
+// row, the cull and the per-sample rule of INTEGRATION lie there too, shared with tsdf_reint_kernels.hip.
 #include "vslam_internal.h"
 
 #include "se3_device.h"
 #include "tsdf_device.h"
 
 namespace vslam {
-
-// what the cull needs of the camera: the slopes of the image rectangle grown by half a pixel and the lengths of the four side planes' normals
-struct TsdfCull { double al, ar, at, ab, nl, nr, nt, nb, rad; };
 
 __global__ __launch_bounds__(kVoxelBlock) void tsdf_clear_kernel(TsdfTable t) {
     const size_t n_slots = (size_t)1 << t.log2_blocks, n_vox = n_slots * kTsdfLanes, stride = (size_t)gridDim.x * kVoxelBlock;
@@ -39,25 +37,9 @@ __global__ __launch_bounds__(kVoxelBlock) void tsdf_frames_kernel(TsdfTable t, c
     uint32_t skipped = 0u;
     for (int b = threadIdx.x; b < B; b += kVoxelBlock) {
         const double* Tb = T + 7 * (size_t)b;
-        double R[9], Rinv[9], tinv[3];
-        se3::rotmat(Tb, R);
-        voxel_inverse_pose(Tb, Rinv, tinv);
-        bool fin = true;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) fin = fin && isfinite(Tb[i]);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) fin = fin && isfinite(R[i]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) fin = fin && isfinite(tinv[i]);
         const int m = map_ids[b];
-        const bool mapped = m >= 0 && m <= kVoxelMaxMap;
-        skipped += (mapped && !fin) ? 1u : 0u;
-        double* f = t.frames + (size_t)kTsdfFrameDoubles * b;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) f[i] = R[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { f[9 + i] = Tb[4 + i]; f[12 + i] = tinv[i]; }
-        f[15] = (mapped && fin) ? (double)m : -1.0;
+        const bool fin = tsdf_frame_row(Tb, m, t.frames + (size_t)kTsdfFrameDoubles * b);
+        skipped += (m >= 0 && m <= kVoxelMaxMap && !fin) ? 1u : 0u;
     }
     if (skipped) { atomicAdd(&t.counters[5], (u64)skipped); atomicOr(&t.counters[4], 4ull); }
 }
@@ -109,21 +91,6 @@ __global__ __launch_bounds__(kVoxelBlock) __attribute__((amdgpu_num_sgpr(72))) v
 }
 
 // ------------------------------------------------------------------------------------------------------------------- integration
-// The cull, an optimisation only: false when NO voxel of the block can pass the rule in frame f.  Every voxel centre lies within 3.5 sqrt(3) < 6.07
-// voxels of the block's centre C; cu.rad is 7 voxels.  A voxel passes only with P[2] > vs and -0.5 <= u < w - 0.5, that is x >= al z and x < ar z
-// for z > 0 (fx > 0), likewise in y: a sphere wholly on the outer side of one of these five planes holds no such voxel.  (With fx or fy <= 0 the
-// launcher sets rad to infinity and nothing is culled.)
-__device__ __forceinline__ bool tsdf_may_pass(const double* __restrict__ f, const TsdfBlockId& b, double vs, const TsdfCull& cu) {
-    const double C0 = ((double)(8 * b.bx) + 4.0) * vs, C1 = ((double)(8 * b.by) + 4.0) * vs, C2 = ((double)(8 * b.bz) + 4.0) * vs;
-    const double P0 = f[0] * C0 + f[1] * C1 + f[2] * C2 + f[9], P1 = f[3] * C0 + f[4] * C1 + f[5] * C2 + f[10], P2 = f[6] * C0 + f[7] * C1 + f[8] * C2 + f[11];
-    if (!(P2 + cu.rad > vs)) return false;
-    if (P0 - cu.al * P2 < -cu.rad * cu.nl) return false;
-    if (cu.ar * P2 - P0 < -cu.rad * cu.nr) return false;
-    if (P1 - cu.at * P2 < -cu.rad * cu.nt) return false;
-    if (cu.ab * P2 - P1 < -cu.rad * cu.nb) return false;
-    return true;
-}
-
 // (form 1) one wave per (list entry, word of 64 frames), one lane per frame: the frames whose map is the block's and that the cull keeps
 __global__ __launch_bounds__(kVoxelBlock) void tsdf_cull_kernel(TsdfTable t, TsdfCull cu, int B) {
     const u64 n_list = t.counters[0];
@@ -146,27 +113,6 @@ __global__ __launch_bounds__(kVoxelBlock) void tsdf_cull_kernel(TsdfTable t, Tsd
         if (lane == 0) t.pairs[(size_t)s * t.frame_words + wd] = m;
     }
     if (lane == 0 && visited) { atomicAdd(&t.counters[6], (u64)visited); atomicAdd(&t.counters[7], (u64)kept); }
-}
-
-struct TsdfSums { uint32_t W = 0, Sq = 0, Wc = 0, I = 0; };
-
-// one voxel (centre X in the world) in one frame: the rule of include/vslam_hip.h, f64 in the written order
-__device__ __forceinline__ void tsdf_sample(const double* __restrict__ f, int b, double X0, double X1, double X2, const VoxelImages& a, const uint8_t* __restrict__ gray,
-                                            size_t img_bytes, int pitch, double vs, double tau, double kq, TsdfSums& v) {
-#pragma clang fp contract(off)
-    const double P0 = f[0] * X0 + f[1] * X1 + f[2] * X2 + f[9], P1 = f[3] * X0 + f[4] * X1 + f[5] * X2 + f[10], P2 = f[6] * X0 + f[7] * X1 + f[8] * X2 + f[11];
-    if (!(P2 > vs)) return;
-    const double u = a.fx * (P0 / P2) + a.cx, w = a.fy * (P1 / P2) + a.cy;
-    const double cf = floor(u + 0.5), rf = floor(w + 0.5);
-    if (!(cf >= 0.0 && cf < (double)a.w && rf >= 0.0 && rf < (double)a.h)) return;
-    const int c = (int)cf, r = (int)rf;
-    const double z = a.fx * a.b / (double)a.disp[((size_t)b * a.h + r) * a.w + c];
-    if (!(z > a.z_min && z < a.z_max)) return;
-    const double sdf = z - P2;
-    if (sdf < -tau) return;
-    const int q = (int)rint(fmin(sdf, tau) * kq);
-    v.W += 1u; v.Sq += (uint32_t)(q + 1024);
-    if (sdf <= tau) { v.Wc += 1u; v.I += gray ? (uint32_t)gray[(size_t)b * img_bytes + (size_t)r * pitch + c] : 0u; }
 }
 
 template <bool kMasks>
@@ -280,6 +226,16 @@ int launch_tsdf_clear(const TsdfTable& t, hipStream_t stream) {
     return VSLAM_OK;
 }
 
+// ALLOCATION of the frames of t.frames (a.T is not read: the poses are the table's)
+int launch_tsdf_alloc(const TsdfTable& t, const VoxelImages& a, hipStream_t stream) {
+    const int vec = voxel_vec(a), hs = (a.h + a.step - 1) / a.step;
+    const dim3 grid(voxel_tiles_x(a, vec), (hs + kVoxelTileRows - 1) / kVoxelTileRows, a.B);
+    ProfScope ps(stream, "tsdf_alloc_kernel");
+    hipLaunchKernelGGL(tsdf_alloc_kernel, grid, dim3(kVoxelBlock), 0, stream, t, a, vec);
+    VS_HIP(hipGetLastError());
+    return VSLAM_OK;
+}
+
 int launch_tsdf_integrate(const TsdfTable& t, const VoxelImages& a, const uint8_t* d_gray, size_t img_bytes, int pitch, const int32_t* d_map_id, int form,
                           hipStream_t stream) {
     {
@@ -287,17 +243,8 @@ int launch_tsdf_integrate(const TsdfTable& t, const VoxelImages& a, const uint8_
         hipLaunchKernelGGL(tsdf_frames_kernel, dim3(1), dim3(kVoxelBlock), 0, stream, t, a.T, d_map_id, a.B);
         VS_HIP(hipGetLastError());
     }
-    {
-        const int vec = voxel_vec(a), hs = (a.h + a.step - 1) / a.step;
-        const dim3 grid(voxel_tiles_x(a, vec), (hs + kVoxelTileRows - 1) / kVoxelTileRows, a.B);
-        ProfScope ps(stream, "tsdf_alloc_kernel");
-        hipLaunchKernelGGL(tsdf_alloc_kernel, grid, dim3(kVoxelBlock), 0, stream, t, a, vec);
-        VS_HIP(hipGetLastError());
-    }
-    TsdfCull cu;
-    cu.al = (-0.5 - a.cx) / a.fx; cu.ar = ((double)a.w - 0.5 - a.cx) / a.fx; cu.at = (-0.5 - a.cy) / a.fy; cu.ab = ((double)a.h - 0.5 - a.cy) / a.fy;
-    cu.nl = sqrt(1.0 + cu.al * cu.al); cu.nr = sqrt(1.0 + cu.ar * cu.ar); cu.nt = sqrt(1.0 + cu.at * cu.at); cu.nb = sqrt(1.0 + cu.ab * cu.ab);
-    cu.rad = (a.fx > 0 && a.fy > 0) ? 7.0 * (double)t.vs : (double)INFINITY;
+    if (int rc = launch_tsdf_alloc(t, a, stream)) return rc;
+    const TsdfCull cu = tsdf_cull_of(t, a);
     if (form == 1) {
         ProfScope ps(stream, "tsdf_cull_kernel");
         hipLaunchKernelGGL(tsdf_cull_kernel, dim3(tsdf_list_grid(t)), dim3(kVoxelBlock), 0, stream, t, cu, a.B);

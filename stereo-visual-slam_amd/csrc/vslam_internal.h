@@ -505,8 +505,10 @@ struct TsdfTable { unsigned long long* keys; uint32_t* list; uint4* pool; unsign
 struct TsdfMap { Ctx* ctx; TsdfTable t; size_t bytes; void* base;
                  DevBuf mesh; // the vertex-id table of vslam_tsdf_mesh_dev: vid (3 x 512 int32 per claimed block) | pos_of_slot (one uint32 per slot); grown by the first mesh call
                  DevBuf render; // the tables of vslam_tsdf_render_dev: the view table (16 doubles per view) | (form 1) one (k_lo, k_hi) per view and 16 x 16 tile; grown on demand
-                 TsdfMap(size_t* acct) : mesh("mesh vertex-id table", acct), render("render view and range tables", acct) {} };
+                 DevBuf reint; // the old sides of vslam_tsdf_reintegrate_dev: a second frame table | a second frame mask per slot | n0; grown by the first such call
+                 TsdfMap(size_t* acct) : mesh("mesh vertex-id table", acct), render("render view and range tables", acct), reint("re-integration tables", acct) {} };
 int launch_tsdf_clear(const TsdfTable& t, hipStream_t stream);
+int launch_tsdf_alloc(const TsdfTable& t, const VoxelImages& a, hipStream_t stream); // ALLOCATION of the frames of t.frames
 // form: 0 = every block walks all frames, 1 = a cull kernel writes a frame mask per block first
 int launch_tsdf_integrate(const TsdfTable& t, const VoxelImages& a, const uint8_t* d_gray, size_t img_bytes, int pitch, const int32_t* d_map_id, int form,
                           hipStream_t stream);
@@ -514,6 +516,14 @@ int launch_tsdf_extract(const TsdfTable& t, int map_id, int min_weight, vslam_su
                         hipStream_t stream);
 int launch_tsdf_blocks(const TsdfTable& t, int map_id, int32_t* d_block_out, uint32_t* d_voxels_out, size_t capacity, unsigned long long* d_n_out,
                        hipStream_t stream);
+// tsdf_reint_kernels.hip: frames taken out at their old poses and put in at their new ones (include/vslam_hip.h "RE-INTEGRATION").  The new sides use
+// the map's own frame table and masks (t.frames, t.pairs); the old sides the tables of TsdfMap::reint, laid out alike.  n0 = the blocks claimed before the call.
+struct TsdfReint { double* frames_old; unsigned long long* pairs_old; uint32_t* n0; const uint32_t* reach; };
+size_t tsdf_reint_table_bytes(const TsdfTable& t, int max_batch);
+TsdfReint tsdf_reint_tables(const TsdfTable& t, int max_batch, uint8_t* base, const uint32_t* d_reach);
+// a.T: the new poses; form as launch_tsdf_integrate
+int launch_tsdf_reintegrate(const TsdfTable& t, const TsdfReint& r, const VoxelImages& a, const uint8_t* d_gray, size_t img_bytes, int pitch, const double* d_T_old,
+                            const int32_t* d_map_id, int form, hipStream_t stream);
 // tsdf_mesh_kernels.hip: the triangle mesh of the field (include/vslam_hip.h "MESH") and the block loader
 int launch_tsdf_mesh(const TsdfTable& t, int32_t* d_vid, uint32_t* d_pos_of_slot, size_t vid_blocks, int map_id, int min_weight, vslam_surfel* d_vertices,
                      int32_t* d_vertex_map, size_t vertex_capacity, vslam_triangle* d_triangles, size_t triangle_capacity, unsigned long long* d_counts,

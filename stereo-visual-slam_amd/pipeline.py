@@ -704,7 +704,8 @@ class KeyframePipeline:
         steps (a step's frames also carve the blocks earlier steps claimed; voxel_size / trunc_voxels / log2_blocks then go unused); otherwise a new
         one.  poses: what close_loops() or full_ba() returned, in place of the BA poses.
         Returns the map: .extract() reads the surfels, write_surfel_ply(path, tm.extract()) writes them; .mesh() connects them into triangles,
-        write_mesh_ply(path, *tm.mesh()) writes the mesh."""
+        write_mesh_ply(path, *tm.mesh()) writes the mesh.  self.surface_frames remembers what was integrated (poses, map ids, gates, the call's
+        reach) for surface_remap()."""
         assert self.depth == "sgbm", "surface_map needs depth='sgbm': it fuses the SGBM disparity maps"
         assert self.with_ba and self.ba_windows == "tracks", "surface_map needs ba_windows='tracks': the poses are the BA windows'"
         if poses is not None:
@@ -722,7 +723,59 @@ class KeyframePipeline:
         tm.integrate_dev(self.d_disp.data_ptr(), self.d_imgs.data_ptr(), self.img_bytes, self.pitch, self.w, self.h, self.B,
                          self.dense_T.data_ptr(), self.dense_map_id.data_ptr(), z_min, z_max, int(step))
         self.last_surface_map = tm
+        # what surface_remap() needs to take these frames out again: the poses and map ids they went in with, the gates, and the call's reach (the
+        # block count after its allocation, read on the device: a 4-byte copy on the context stream -- the pipeline's own --, no kernel, no host round trip)
+        with torch.cuda.stream(self.stream):
+            reach = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        tm.reach_dev(reach.data_ptr())
+        self.surface_frames = dict(tsdf_map=tm, T=T.copy(), map_id=map_id.copy(), z_min=z_min, z_max=z_max, step=int(step), reach=reach.expand(self.B))
         return tm
+
+    def surface_remap(self, poses, tsdf_map=None, min_shift=0.0, min_turn=0.0):
+        """The last step's frames taken out of the surface map at the poses surface_map() (or the last surface_remap()) put them in with and
+        re-integrated at `poses` -- what close_loops() or full_ba() returned -- in one pass over the map (vslam_tsdf_reintegrate_dev), from the step's
+        disparities and images still on the device.  Only frames whose camera centre moved more than min_shift metres or whose rotation changed by more
+        than min_turn radians are re-integrated; the others stay as they are (map id -1 in the call).  A frame that left the trajectories is removed,
+        one that entered them is added.  tsdf_map: the map surface_map() filled (None: that one).  The remembered poses and reach are updated, so
+        a later surface_remap() starts from this one.  Returns (the map, the number of frames moved).
+        Limits: the frames of the LAST surface_map() call only (the pipeline keeps one step's disparities); blocks that empty stay claimed."""
+        st = getattr(self, "surface_frames", None)
+        assert st is not None, "surface_remap needs a surface_map() call before it: it re-integrates that call's frames"
+        tm = tsdf_map if tsdf_map is not None else st["tsdf_map"]
+        assert tm is st["tsdf_map"] and getattr(tm, "h", None), "surface_remap: tsdf_map is not the (open) map the last surface_map() filled"
+        self.vo.sync()
+        torch.cuda.synchronize(self.dev)
+        T_new, id_new = self.dense_map_inputs(poses)
+        T_old, id_old = st["T"], st["map_id"]
+        was, now = id_old >= 0, id_new >= 0
+        assert (id_old[was & now] == id_new[was & now]).all(), "surface_remap: a frame changed its segment"
+        R = lambda T: np.stack([np.asarray(synth.R_from_quat(q)) for q in T[:, :4]])
+        Ro, Rn = R(T_old), R(T_new)
+        centre = lambda Rm, T: -np.einsum("bji,bj->bi", Rm, T[:, 4:])
+        shift = np.linalg.norm(centre(Rn, T_new) - centre(Ro, T_old), axis=1)
+        turn = np.arccos(np.clip((np.einsum("bij,bij->b", Ro, Rn) - 1.0) / 2.0, -1.0, 1.0))
+        moved = (was != now) | (was & now & ((shift > float(min_shift)) | (turn > float(min_turn))))
+        n_moved = int(moved.sum())
+        if n_moved == 0:
+            return tm, 0
+        nan = np.full(7, np.nan)
+        call_old = np.where((moved & was)[:, None], T_old, nan)
+        call_new = np.where((moved & now)[:, None], T_new, nan)
+        call_id = np.where(moved, np.where(now, id_new, id_old), -1).astype(np.int32)
+        with torch.cuda.stream(self.stream):
+            d_old, d_new = torch.from_numpy(call_old).to(self.dev), torch.from_numpy(call_new).to(self.dev)
+            d_id, d_moved = torch.from_numpy(call_id).to(self.dev), torch.from_numpy(moved).to(self.dev)
+            d_reach = st["reach"].contiguous()
+            after = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        tm.reintegrate_dev(self.d_disp.data_ptr(), self.d_imgs.data_ptr(), self.img_bytes, self.pitch, self.w, self.h, self.B, d_old.data_ptr(), d_new.data_ptr(),
+                           d_id.data_ptr(), d_reach.data_ptr(), st["z_min"], st["z_max"], st["step"])
+        tm.reach_dev(after.data_ptr())
+        with torch.cuda.stream(self.stream):
+            st["reach"] = torch.where(d_moved, after.expand(self.B), d_reach)
+        st["T"] = np.where(moved[:, None], np.where(now[:, None], T_new, T_old), T_old)
+        st["map_id"] = np.where(moved, id_new, id_old).astype(np.int32)
+        self.surface_remap_buffers = (d_old, d_new, d_id, d_reach)   # (alive until the stream has run the call)
+        return tm, n_moved
 
     def surface_views(self, tsdf_map=None, poses=None, scale=1.0, march=0.5, min_weight=1, disparity=False):
         """What the surface map shows from every frame of dense_map_inputs(poses), each at its own pose and map id (TsdfMap.render): the carved,
