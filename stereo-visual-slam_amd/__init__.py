@@ -498,6 +498,7 @@ class VO:
     def __init__(self, params=None, device=0, stream=None, **kw):
         self.lib = load_library()
         self.params = params if params is not None else default_params(**kw)
+        self._owned = []   # the VoxelMaps, TsdfMaps and PlaceDBs created on this context and not yet closed, in creation order
         h = C.c_void_p()
         rc = self.lib.vslam_create(C.byref(self.params), device, stream or None, C.byref(h))
         if rc != VSLAM_OK:
@@ -506,8 +507,8 @@ class VO:
 
     def close(self):
         if getattr(self, "h", None):
-            for vm in list(getattr(self, "_voxel_maps", ())) + list(getattr(self, "_tsdf_maps", ())) + list(getattr(self, "_place_dbs", ())):   # (they belong to the context and go first)
-                vm.close()
+            for obj in list(self._owned):   # (they belong to the context and go first)
+                obj.close()
             self.lib.vslam_destroy(self.h)
             self.h = None
 
@@ -1156,35 +1157,80 @@ class VO:
         return st
 
 
-class VoxelMap:
-    """A sparse voxel grid in a device hash table (include/vslam_hip.h "dense map"): per voxel a point count, the sums of the points' sub-voxel
-    offsets and of their intensities, all integers, so the table does not depend on the order its points arrived in.  Filled through
-    VO.voxel_insert_points_dev / VO.voxel_fuse_disparity_dev (or KeyframePipeline.dense_map); belongs to the VO it was created on."""
+class _Owned:
+    """What VoxelMap, TsdfMap and PlaceDB share: an object that a VO creates, owns and closes with itself.  A subclass names its four entry points
+    in _CREATE, _DESTROY, _CLEAR and _STATS, its stats struct in _STATS_T, and hands _create() the arguments of its create call."""
 
-    def __init__(self, vo, voxel_size=0.2, log2_capacity=22):
-        self.vo, self.voxel_size, self.log2_capacity = vo, float(voxel_size), int(log2_capacity)
+    def _create(self, vo, *args):
+        self.vo = vo
         h = C.c_void_p()
-        vo._chk(vo.lib.vslam_voxel_create(vo.h, voxel_size, log2_capacity, C.byref(h)), "vslam_voxel_create")
+        vo._chk(getattr(vo.lib, self._CREATE)(vo.h, *args, C.byref(h)), self._CREATE)
         self.h = h
-        if not hasattr(vo, "_voxel_maps"):
-            vo._voxel_maps = []
-        vo._voxel_maps.append(self)
+        vo._owned.append(self)
 
     def close(self):
         if getattr(self, "h", None):
-            self.vo.lib.vslam_voxel_destroy(self.h)
+            getattr(self.vo.lib, self._DESTROY)(self.h)
             self.h = None
-            self.vo._voxel_maps.remove(self)
+            self.vo._owned.remove(self)
 
     def clear(self):
-        """empty table, zero counters; asynchronous on the context stream"""
-        self.vo._chk(self.vo.lib.vslam_voxel_clear(self.h), "vslam_voxel_clear")
+        """empty again, counters zeroed; the two maps clear asynchronously on the context stream"""
+        self.vo._chk(getattr(self.vo.lib, self._CLEAR)(self.h), self._CLEAR)
 
     def stats(self):
-        """{n_occupied, n_points, n_dropped_range, n_dropped_full, status}; synchronises"""
-        st = VoxelStats(); st.struct_size = C.sizeof(VoxelStats)
-        self.vo._chk(self.vo.lib.vslam_voxel_stats(self.h, C.byref(st)), "vslam_voxel_stats")
+        """the fields of the object's stats struct as a dict (see the class); the two maps synchronise"""
+        st = self._STATS_T(); st.struct_size = C.sizeof(self._STATS_T)
+        self.vo._chk(getattr(self.vo.lib, self._STATS)(self.h, C.byref(st)), self._STATS)
         return st.as_dict()
+
+
+def _read_lists(vo, call, lists, capacities=None):
+    """Reads back the counted, capacity-limited lists a device entry writes.  lists: per list its parallel arrays as (torch dtype, row shape, fill);
+    call(*args) runs the entry with, per list, its arrays' device pointers and its capacity, then the pointer to one uint64 count per list -- the
+    order the extract, blocks and mesh entries take them in.  capacities None: a first pass without arrays (null pointers, capacity 0) counts.
+    Returns (per list its arrays as numpy, cut to min(count, capacity) rows; the full counts)."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    d_n = torch.zeros(len(lists), dtype=torch.int64, device=dev)
+
+    def run(bufs, caps):
+        args = []
+        for arrays, cap in zip(bufs, caps):
+            args += [None if a is None else a.data_ptr() for a in arrays] + [cap]
+        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
+        call(*args, d_n.data_ptr())
+        vo.sync()
+        return [int(c) for c in d_n.cpu().tolist()]
+
+    if capacities is None:
+        capacities = [max(c, 1) for c in run([[None] * len(arrays) for arrays in lists], [0] * len(lists))]
+    bufs = [[torch.full((cap,) + tuple(shape), fill, dtype=dtype, device=dev) for dtype, shape, fill in arrays] for arrays, cap in zip(lists, capacities)]
+    counts = run(bufs, capacities)
+    return [[a[:min(n, cap)].cpu().numpy() for a in arrays] for arrays, n, cap in zip(bufs, counts, capacities)], counts
+
+
+def _rows_with_map(rows, maps, row_dtype, out_dtype, order=None):
+    """device rows (n, itemsize) uint8 of row_dtype and their map ids as one out_dtype array (`map` in front), sorted by the fields `order` (last
+    is the primary key, as np.lexsort takes them) when given"""
+    v = rows.reshape(-1).view(row_dtype)
+    out = np.zeros(len(v), out_dtype)
+    out["map"] = maps
+    for f in row_dtype.names:
+        out[f] = v[f]
+    return out[np.lexsort(tuple(out[f] for f in order))] if order else out
+
+
+class VoxelMap(_Owned):
+    """A sparse voxel grid in a device hash table (include/vslam_hip.h "dense map"): per voxel a point count, the sums of the points' sub-voxel
+    offsets and of their intensities, all integers, so the table does not depend on the order its points arrived in.  Filled through
+    VO.voxel_insert_points_dev / VO.voxel_fuse_disparity_dev (or KeyframePipeline.dense_map); belongs to the VO it was created on.
+    stats(): {n_occupied, n_points, n_dropped_range, n_dropped_full, status}."""
+    _CREATE, _DESTROY, _CLEAR, _STATS, _STATS_T = "vslam_voxel_create", "vslam_voxel_destroy", "vslam_voxel_clear", "vslam_voxel_stats", VoxelStats
+
+    def __init__(self, vo, voxel_size=0.2, log2_capacity=22):
+        self.voxel_size, self.log2_capacity = float(voxel_size), int(log2_capacity)
+        self._create(vo, voxel_size, log2_capacity)
 
     def extract(self, map_id=-1, min_count=1, capacity=None, sort=True):
         """the voxels with count >= min_count of map map_id (-1: every map) as a VOXEL_MAP_DTYPE array sorted by (map, ix, iy, iz) -- the canonical
@@ -1194,21 +1240,9 @@ class VoxelMap:
         vo = self.vo
         if capacity is None:
             capacity = max(self.stats()["n_occupied"], 1)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        d_out = torch.zeros((capacity, 32), dtype=torch.uint8, device=dev)
-        d_map = torch.zeros(capacity, dtype=torch.int32, device=dev)
-        d_n = torch.zeros(1, dtype=torch.int64, device=dev)
-        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
-        vo.voxel_extract_dev(self, map_id, min_count, d_out.data_ptr(), d_map.data_ptr(), capacity, d_n.data_ptr())
-        vo.sync()
-        self.last_count = int(d_n.cpu()[0])
-        n = min(self.last_count, capacity)
-        v = d_out[:n].cpu().numpy().reshape(-1).view(VOXEL_DTYPE)
-        out = np.zeros(n, VOXEL_MAP_DTYPE)
-        out["map"] = d_map[:n].cpu().numpy()
-        for f in VOXEL_DTYPE.names:
-            out[f] = v[f]
-        return out[np.lexsort((out["iz"], out["iy"], out["ix"], out["map"]))] if sort else out
+        ((rows, maps),), (self.last_count,) = _read_lists(vo, lambda *out: vo.voxel_extract_dev(self, map_id, min_count, *out),
+                                                          [[(torch.uint8, (32,), 0), (torch.int32, (), 0)]], [capacity])
+        return _rows_with_map(rows, maps, VOXEL_DTYPE, VOXEL_MAP_DTYPE, ("iz", "iy", "ix", "map") if sort else None)
 
 
 def canonical_mesh(vertices, triangles):
@@ -1224,36 +1258,17 @@ def canonical_mesh(vertices, triangles):
     return vertices[order], tris
 
 
-class TsdfMap:
+class TsdfMap(_Owned):
     """A truncated signed distance field over 8 x 8 x 8 voxel blocks in a device pool (include/vslam_hip.h "surface map"): per voxel the integer sums
     of the quantised distance to the surface, of the views that saw it and of their intensities.  Views that look through a voxel carve it.  Filled
     through integrate_dev (or KeyframePipeline.surface_map) or load_blocks; extract() reads the surface as surfels, mesh() as indexed triangles over
-    the same surfels; belongs to the VO it was created on."""
+    the same surfels; belongs to the VO it was created on.
+    stats(): {n_blocks, n_samples, n_dropped_range, n_dropped_full, n_frames_skipped, n_pairs_visited, n_pairs_kept, status}."""
+    _CREATE, _DESTROY, _CLEAR, _STATS, _STATS_T = "vslam_tsdf_create", "vslam_tsdf_destroy", "vslam_tsdf_clear", "vslam_tsdf_stats", TsdfStats
 
     def __init__(self, vo, voxel_size=0.2, trunc_voxels=4, log2_blocks=16):
-        self.vo, self.voxel_size, self.trunc_voxels, self.log2_blocks = vo, float(voxel_size), int(trunc_voxels), int(log2_blocks)
-        h = C.c_void_p()
-        vo._chk(vo.lib.vslam_tsdf_create(vo.h, voxel_size, trunc_voxels, log2_blocks, C.byref(h)), "vslam_tsdf_create")
-        self.h = h
-        if not hasattr(vo, "_tsdf_maps"):
-            vo._tsdf_maps = []
-        vo._tsdf_maps.append(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.vo.lib.vslam_tsdf_destroy(self.h)
-            self.h = None
-            self.vo._tsdf_maps.remove(self)
-
-    def clear(self):
-        """every block released, zero counters; asynchronous on the context stream"""
-        self.vo._chk(self.vo.lib.vslam_tsdf_clear(self.h), "vslam_tsdf_clear")
-
-    def stats(self):
-        """{n_blocks, n_samples, n_dropped_range, n_dropped_full, n_frames_skipped, n_pairs_visited, n_pairs_kept, status}; synchronises"""
-        st = TsdfStats(); st.struct_size = C.sizeof(TsdfStats)
-        self.vo._chk(self.vo.lib.vslam_tsdf_stats(self.h, C.byref(st)), "vslam_tsdf_stats")
-        return st.as_dict()
+        self.voxel_size, self.trunc_voxels, self.log2_blocks = float(voxel_size), int(trunc_voxels), int(log2_blocks)
+        self._create(vo, voxel_size, trunc_voxels, log2_blocks)
 
     def integrate_dev(self, d_disp, d_gray, img_bytes, pitch, w, h, B, d_T, d_map_id, z_min, z_max, step=1):
         """VO.tsdf_integrate_dev into this map"""
@@ -1313,53 +1328,24 @@ class TsdfMap:
                              d_ids.data_ptr(), d_reach.data_ptr(), float(z_min), float(z_max), int(step))
         return self.reach()
 
-    def _buffers(self, capacity, row_bytes):
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
-        d_out = torch.zeros((capacity, row_bytes), dtype=torch.uint8, device=dev)
-        d_n = torch.zeros(1, dtype=torch.int64, device=dev)
-        return dev, d_out, d_n
-
     def extract(self, map_id=-1, min_weight=1, capacity=None, sort=True):
         """the zero-crossing voxel edges of map map_id (-1: every map) between voxels of weight >= min_weight, as a SURFEL_MAP_DTYPE array sorted
         by (map, ix, iy, iz, axis) -- the canonical form for comparisons.  capacity: rows of the device buffer (None: counted by a first pass);
         the call returns at most that many (self.last_count holds the full count)."""
         import torch
         vo = self.vo
-        if capacity is None:
-            dev, d_out, d_n = self._buffers(1, 48)
-            torch.cuda.synchronize(dev)
-            vo._chk(vo.lib.vslam_tsdf_extract_dev(vo.h, self.h, map_id, min_weight, None, None, 0, d_n.data_ptr()), "vslam_tsdf_extract_dev")
-            vo.sync()
-            capacity = max(int(d_n.cpu()[0]), 1)
-        dev, d_out, d_n = self._buffers(capacity, 48)
-        d_map = torch.zeros(capacity, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
-        vo._chk(vo.lib.vslam_tsdf_extract_dev(vo.h, self.h, map_id, min_weight, d_out.data_ptr(), d_map.data_ptr(), capacity, d_n.data_ptr()), "vslam_tsdf_extract_dev")
-        vo.sync()
-        self.last_count = int(d_n.cpu()[0])
-        n = min(self.last_count, capacity)
-        v = d_out[:n].cpu().numpy().reshape(-1).view(SURFEL_DTYPE)
-        out = np.zeros(n, SURFEL_MAP_DTYPE)
-        out["map"] = d_map[:n].cpu().numpy()
-        for f in SURFEL_DTYPE.names:
-            out[f] = v[f]
-        return out[np.lexsort((out["axis"], out["iz"], out["iy"], out["ix"], out["map"]))] if sort else out
+        call = lambda *out: vo._chk(vo.lib.vslam_tsdf_extract_dev(vo.h, self.h, map_id, min_weight, *out), "vslam_tsdf_extract_dev")
+        ((rows, maps),), (self.last_count,) = _read_lists(vo, call, [[(torch.uint8, (48,), 0), (torch.int32, (), 0)]], None if capacity is None else [capacity])
+        return _rows_with_map(rows, maps, SURFEL_DTYPE, SURFEL_MAP_DTYPE, ("axis", "iz", "iy", "ix", "map") if sort else None)
 
     def blocks(self, map_id=-1):
         """the claimed blocks of map map_id (-1: every map), raw: (ids (n, 4) int32 of (map, bx, by, bz), voxels (n, 512, 4) uint32 of (W, Sq, Wc, I)
         with voxel (ix, iy, iz) at (iz & 7) << 6 | (iy & 7) << 3 | (ix & 7)), sorted by (map, bx, by, bz)"""
         import torch
         vo = self.vo
-        capacity = max(self.stats()["n_blocks"], 1)
-        dev, d_vox, d_n = self._buffers(capacity, 8192)
-        d_ids = torch.zeros((capacity, 4), dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)
-        vo._chk(vo.lib.vslam_tsdf_blocks_dev(vo.h, self.h, map_id, d_ids.data_ptr(), d_vox.data_ptr(), capacity, d_n.data_ptr()), "vslam_tsdf_blocks_dev")
-        vo.sync()
-        n = min(int(d_n.cpu()[0]), capacity)
-        ids = d_ids[:n].cpu().numpy()
-        vox = d_vox[:n].cpu().numpy().view(np.uint32).reshape(n, 512, 4)
+        call = lambda *out: vo._chk(vo.lib.vslam_tsdf_blocks_dev(vo.h, self.h, map_id, *out), "vslam_tsdf_blocks_dev")
+        ((ids, vox),), _ = _read_lists(vo, call, [[(torch.int32, (4,), 0), (torch.uint8, (8192,), 0)]], [max(self.stats()["n_blocks"], 1)])
+        vox = vox.view(np.uint32).reshape(len(ids), 512, 4)
         order = np.lexsort((ids[:, 3], ids[:, 2], ids[:, 1], ids[:, 0]))
         return ids[order], vox[order]
 
@@ -1389,27 +1375,10 @@ class TsdfMap:
         holds the device's two counts."""
         import torch
         vo = self.vo
-        dev = torch.device("cuda", torch.cuda.current_device())
-        d_n = torch.zeros(2, dtype=torch.int64, device=dev)
-        torch.cuda.synchronize(dev)
-        vo._chk(vo.lib.vslam_tsdf_mesh_dev(vo.h, self.h, map_id, min_weight, None, None, 0, None, 0, d_n.data_ptr()), "vslam_tsdf_mesh_dev")
-        vo.sync()
-        vcap, tcap = (int(c) for c in d_n.cpu().tolist())
-        d_v = torch.zeros((max(vcap, 1), 48), dtype=torch.uint8, device=dev)
-        d_map = torch.zeros(max(vcap, 1), dtype=torch.int32, device=dev)
-        d_t = torch.full((max(tcap, 1), 3), -1, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
-        vo._chk(vo.lib.vslam_tsdf_mesh_dev(vo.h, self.h, map_id, min_weight, d_v.data_ptr(), d_map.data_ptr(), vcap, d_t.data_ptr(), tcap, d_n.data_ptr()),
-                "vslam_tsdf_mesh_dev")
-        vo.sync()
-        self.last_counts = tuple(int(c) for c in d_n.cpu().tolist())
-        nv, nt = min(self.last_counts[0], vcap), min(self.last_counts[1], tcap)
-        v = d_v[:nv].cpu().numpy().reshape(-1).view(SURFEL_DTYPE)
-        verts = np.zeros(nv, SURFEL_MAP_DTYPE)
-        verts["map"] = d_map[:nv].cpu().numpy()
-        for f in SURFEL_DTYPE.names:
-            verts[f] = v[f]
-        tris = d_t[:nt].cpu().numpy().reshape(-1, 3)
+        call = lambda *out: vo._chk(vo.lib.vslam_tsdf_mesh_dev(vo.h, self.h, map_id, min_weight, *out), "vslam_tsdf_mesh_dev")
+        ((rows, maps), (tris,)), counts = _read_lists(vo, call, [[(torch.uint8, (48,), 0), (torch.int32, (), 0)], [(torch.int32, (3,), -1)]])
+        self.last_counts = tuple(counts)
+        verts = _rows_with_map(rows, maps, SURFEL_DTYPE, SURFEL_MAP_DTYPE)
         if not sort:
             return verts, tris
         return canonical_mesh(verts, tris)
@@ -1444,35 +1413,16 @@ class TsdfMap:
                     counts=tuple(int(c) for c in d_counts.cpu().tolist()))
 
 
-class PlaceDB:
+class PlaceDB(_Owned):
     """A database of keyframe descriptor blocks that outlives the steps (include/vslam_hip.h "place database"): entries are appended by
     VO.place_add_dev, scored against each other by brute force on the matrix cores (VO.place_score_dev), and the best candidates verified with the
-    matcher and the RANSAC pose stage (VO.place_verify_dev).  KeyframePipeline.loop_closures drives all of it; belongs to the VO it was created on."""
+    matcher and the RANSAC pose stage (VO.place_verify_dev).  KeyframePipeline.loop_closures drives all of it; belongs to the VO it was created on.
+    stats(): {n_entries, capacity, rows_per_entry, with_geometry, n_refused}; clear() forgets every entry and zeroes the refusal counter."""
+    _CREATE, _DESTROY, _CLEAR, _STATS, _STATS_T = "vslam_place_create", "vslam_place_destroy", "vslam_place_clear", "vslam_place_stats", PlaceStats
 
     def __init__(self, vo, rows, capacity=4096, with_geometry=True):
-        self.vo, self.rows, self.capacity, self.with_geometry = vo, int(rows), int(capacity), bool(with_geometry)
-        h = C.c_void_p()
-        vo._chk(vo.lib.vslam_place_create(vo.h, self.rows, self.capacity, int(self.with_geometry), C.byref(h)), "vslam_place_create")
-        self.h = h
-        if not hasattr(vo, "_place_dbs"):
-            vo._place_dbs = []
-        vo._place_dbs.append(self)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.vo.lib.vslam_place_destroy(self.h)
-            self.h = None
-            self.vo._place_dbs.remove(self)
-
-    def clear(self):
-        """forget every entry and zero the refusal counter"""
-        self.vo._chk(self.vo.lib.vslam_place_clear(self.h), "vslam_place_clear")
-
-    def stats(self):
-        """{n_entries, capacity, rows_per_entry, with_geometry, n_refused}"""
-        st = PlaceStats(); st.struct_size = C.sizeof(PlaceStats)
-        self.vo._chk(self.vo.lib.vslam_place_stats(self.h, C.byref(st)), "vslam_place_stats")
-        return st.as_dict()
+        self.rows, self.capacity, self.with_geometry = int(rows), int(capacity), bool(with_geometry)
+        self._create(vo, self.rows, self.capacity, int(self.with_geometry))
 
     def __len__(self):
         return self.stats()["n_entries"]

@@ -80,6 +80,27 @@ void DevBuf::release() {
     p = nullptr; bytes = 0;
 }
 
+int Owned::alloc(Ctx* c, size_t n, const char* who) {
+    ctx = c;
+    if (hipMalloc((void**)&base, n) != hipSuccess) { base = nullptr; set_error("%s: hipMalloc(%zu) failed", who, n); return VSLAM_ERR_HIP; }
+    bytes = n; c->dev_bytes += n;
+    return VSLAM_OK;
+}
+void Owned::free() {
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    hipFree(base);
+    ctx->dev_bytes -= bytes;
+    base = nullptr; bytes = 0;
+}
+// the object behind a handle (a VoxelMap, TsdfMap or PlaceDb), or null and a message when it is not one of context c
+template <typename T, typename H>
+static T* owned_by(const Ctx* c, H* handle, const char* who) {
+    T* m = reinterpret_cast<T*>(handle);
+    if (!c || !m || m->ctx != c) { set_error("%s: null context or %s, or a %s of another context", who, T::noun, T::noun); return nullptr; }
+    return m;
+}
+
 // Staging layout of one host-buffer call over the context's staging buffer: in() also queues the host -> device copy of its slot.
 struct Arena : Layout {
     struct Upload { void* d; const void* h; size_t bytes; };
@@ -1703,22 +1724,45 @@ int vslam_build_pnp_inputs_dev(vslam_ctx* ctx, const vslam_dmatch* d_f2f, const 
 constexpr int kVoxelFormDefault = 1;
 static int voxel_form(const Ctx* c) { return c->tune.voxel_form >= 0 ? c->tune.voxel_form : kVoxelFormDefault; }
 
+// ---- the checks and steps the entries of the dense map, the surface map and the place database share
+// a voxel size the kernels can use: positive and finite as a float, and so is its reciprocal
+static int voxel_size_check(const char* who, double voxel_size) {
+    const float vs = (float)voxel_size;
+    if (!std::isfinite(voxel_size) || !(voxel_size > 0) || !std::isfinite(vs) || !(vs > 0.f) || !std::isfinite(1.0f / vs)) {
+        set_error("%s: voxel_size %g is not a finite positive float", who, voxel_size); return VSLAM_ERR_ARG;
+    }
+    return VSLAM_OK;
+}
+// lo = 0: a map to write into; lo = -1: a map to read, or all of them
+static int map_id_check(const char* who, int map_id, int lo) {
+    if (map_id < lo || map_id > kVoxelMaxMap) { set_error("%s: map_id %d outside [%d, %d]", who, map_id, lo, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    return VSLAM_OK;
+}
+// a counted list: the count is always written, rows only where a capacity gives them room (`have_out`: every output array is there; `null_out`: the
+// message's words for one that is not)
+static int counted_output_check(const char* who, const void* d_n_out, size_t capacity, bool have_out, const char* null_out) {
+    if (!d_n_out || (capacity > 0 && !have_out)) { set_error("%s: null d_n_out, or %s with a capacity", who, null_out); return VSLAM_ERR_ARG; }
+    return VSLAM_OK;
+}
+// the first n counter words of a map as they stand after everything queued before the call; synchronises
+static int read_counters(const Ctx* c, const unsigned long long* d_counters, unsigned long long* host, int n) {
+    VS_HIP(hipMemcpyAsync(host, d_counters, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+    VS_HIP(hipStreamSynchronize(c->stream));
+    return VSLAM_OK;
+}
+
 int vslam_voxel_create(vslam_ctx* ctx, double voxel_size, int log2_capacity, vslam_voxel_map** out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !out) { set_error("vslam_voxel_create: null argument"); return VSLAM_ERR_ARG; }
     *out = nullptr;
-    const float vs = (float)voxel_size;
-    if (!std::isfinite(voxel_size) || !(voxel_size > 0) || !std::isfinite(vs) || !(vs > 0.f) || !std::isfinite(1.0f / vs)) {
-        set_error("vslam_voxel_create: voxel_size %g is not a finite positive float", voxel_size); return VSLAM_ERR_ARG;
-    }
+    if (int rc = voxel_size_check("vslam_voxel_create", voxel_size)) return rc;
     if (log2_capacity < 10 || log2_capacity > 28) { set_error("vslam_voxel_create: log2_capacity %d outside [10, 28]", log2_capacity); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     VoxelMap* m = new VoxelMap();
-    m->ctx = c; m->bytes = ((size_t)32 << log2_capacity) + sizeof(unsigned long long) * kVoxelCounters;
-    m->t.log2_capacity = log2_capacity; m->t.vs = vs; m->t.inv = 1.0f / vs;
-    if (hipMalloc((void**)&m->t.slots, m->bytes) != hipSuccess) { set_error("vslam_voxel_create: hipMalloc(%zu) failed", m->bytes); delete m; return VSLAM_ERR_HIP; }
+    m->t.log2_capacity = log2_capacity; m->t.vs = (float)voxel_size; m->t.inv = 1.0f / m->t.vs;
+    if (int rc = m->alloc(c, ((size_t)32 << log2_capacity) + sizeof(unsigned long long) * kVoxelCounters, "vslam_voxel_create")) { delete m; return rc; }
+    m->t.slots = m->base;
     m->t.counters = reinterpret_cast<unsigned long long*>(m->t.slots + ((size_t)32 << log2_capacity));
-    c->dev_bytes += m->bytes;
     int rc = launch_voxel_clear(m->t, c->stream);
     if (rc == VSLAM_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("vslam_voxel_create: clearing the table failed"); rc = VSLAM_ERR_HIP; }
     if (rc) { vslam_voxel_destroy(reinterpret_cast<vslam_voxel_map*>(m)); return rc; }
@@ -1729,10 +1773,7 @@ int vslam_voxel_create(vslam_ctx* ctx, double voxel_size, int log2_capacity, vsl
 void vslam_voxel_destroy(vslam_voxel_map* vm) {
     VoxelMap* m = reinterpret_cast<VoxelMap*>(vm);
     if (!m) return;
-    hipSetDevice(m->ctx->device);
-    hipStreamSynchronize(m->ctx->stream);
-    hipFree(m->t.slots);
-    m->ctx->dev_bytes -= m->bytes;
+    m->free();
     delete m;
 }
 
@@ -1748,8 +1789,7 @@ int vslam_voxel_stats(vslam_voxel_map* vm, struct vslam_voxel_stats* host) {
     if (!m || !host || host->struct_size != (int32_t)sizeof(struct vslam_voxel_stats)) { set_error("vslam_voxel_stats: null argument or struct_size mismatch"); return VSLAM_ERR_ARG; }
     VS_ENTER(m->ctx);
     unsigned long long w[kVoxelCounters];
-    VS_HIP(hipMemcpyAsync(w, m->t.counters, sizeof(w), hipMemcpyDeviceToHost, m->ctx->stream));
-    VS_HIP(hipStreamSynchronize(m->ctx->stream));
+    if (int rc = read_counters(m->ctx, m->t.counters, w, kVoxelCounters)) return rc;
     host->n_occupied = w[0]; host->n_points = w[1]; host->n_dropped_range = w[2]; host->n_dropped_full = w[3]; host->status = (uint32_t)w[4];
     return VSLAM_OK;
 }
@@ -1777,19 +1817,24 @@ int vslam_reproject_dev(vslam_ctx* ctx, const float* d_disparity, int w, int h, 
     return launch_reproject(a, d_xyz, d_valid, c->stream);
 }
 
-static VoxelMap* voxel_map_of(const Ctx* c, vslam_voxel_map* vm, const char* who) {
-    VoxelMap* m = reinterpret_cast<VoxelMap*>(vm);
-    if (!c || !m || m->ctx != c) { set_error("%s: null context or map, or a map of another context", who); return nullptr; }
-    return m;
+// the front of the entries that fuse disparity maps, by their map ids and with optional gray images, into a map: the checks, and `a` filled
+static int map_images(const Ctx* c, const char* who, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch, int w, int h, int B,
+                      const double* d_T_c_w, const int32_t* d_map_id, double z_min, double z_max, int step, VoxelImages& a) {
+    if (!d_map_id) { set_error("%s: null d_map_id", who); return VSLAM_ERR_ARG; }
+    if (int rc = voxel_images(c, who, d_disparity, w, h, B, d_T_c_w, z_min, z_max, step, a)) return rc;
+    if (d_gray && (pitch < w || img_bytes < (size_t)pitch * h)) {
+        set_error("%s: pitch %d / img_bytes %zu do not hold a %d x %d image", who, pitch, img_bytes, w, h); return VSLAM_ERR_ARG;
+    }
+    return VSLAM_OK;
 }
 
 int vslam_voxel_insert_points_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const float* d_xyz, const uint8_t* d_valid, const uint8_t* d_intensity, size_t n,
                                   int map_id) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    VoxelMap* m = voxel_map_of(c, vm, "vslam_voxel_insert_points_dev");
+    VoxelMap* m = owned_by<VoxelMap>(c, vm, "vslam_voxel_insert_points_dev");
     if (!m) return VSLAM_ERR_ARG;
     if (n > 0 && !d_xyz) { set_error("vslam_voxel_insert_points_dev: null d_xyz"); return VSLAM_ERR_ARG; }
-    if (map_id < 0 || map_id > kVoxelMaxMap) { set_error("vslam_voxel_insert_points_dev: map_id %d outside [0, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    if (int rc = map_id_check("vslam_voxel_insert_points_dev", map_id, 0)) return rc;
     VS_ENTER(c);
     return launch_voxel_insert_points(m->t, d_xyz, d_valid, d_intensity, n, map_id, c->stream);
 }
@@ -1797,14 +1842,10 @@ int vslam_voxel_insert_points_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const flo
 int vslam_voxel_fuse_disparity_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
                                    int w, int h, int B, const double* d_T_c_w, const int32_t* d_map_id, double z_min, double z_max, int step) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    VoxelMap* m = voxel_map_of(c, vm, "vslam_voxel_fuse_disparity_dev");
+    VoxelMap* m = owned_by<VoxelMap>(c, vm, "vslam_voxel_fuse_disparity_dev");
     if (!m) return VSLAM_ERR_ARG;
-    if (!d_map_id) { set_error("vslam_voxel_fuse_disparity_dev: null d_map_id"); return VSLAM_ERR_ARG; }
     VoxelImages a;
-    if (int rc = voxel_images(c, "vslam_voxel_fuse_disparity_dev", d_disparity, w, h, B, d_T_c_w, z_min, z_max, step, a)) return rc;
-    if (d_gray && (pitch < w || img_bytes < (size_t)pitch * h)) {
-        set_error("vslam_voxel_fuse_disparity_dev: pitch %d / img_bytes %zu do not hold a %d x %d image", pitch, img_bytes, w, h); return VSLAM_ERR_ARG;
-    }
+    if (int rc = map_images(c, "vslam_voxel_fuse_disparity_dev", d_disparity, d_gray, img_bytes, pitch, w, h, B, d_T_c_w, d_map_id, z_min, z_max, step, a)) return rc;
     VS_ENTER(c);
     return launch_voxel_fuse(m->t, a, d_gray, img_bytes, pitch, d_map_id, voxel_form(c), c->stream);
 }
@@ -1812,10 +1853,10 @@ int vslam_voxel_fuse_disparity_dev(vslam_ctx* ctx, vslam_voxel_map* vm, const fl
 int vslam_voxel_extract_dev(vslam_ctx* ctx, vslam_voxel_map* vm, int map_id, int min_count, vslam_voxel* d_out, int32_t* d_map_out, size_t capacity,
                             uint64_t* d_n_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    VoxelMap* m = voxel_map_of(c, vm, "vslam_voxel_extract_dev");
+    VoxelMap* m = owned_by<VoxelMap>(c, vm, "vslam_voxel_extract_dev");
     if (!m) return VSLAM_ERR_ARG;
-    if (!d_n_out || (capacity > 0 && !d_out)) { set_error("vslam_voxel_extract_dev: null d_n_out, or null d_out with a capacity"); return VSLAM_ERR_ARG; }
-    if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_voxel_extract_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    if (int rc = counted_output_check("vslam_voxel_extract_dev", d_n_out, capacity, d_out, "null d_out")) return rc;
+    if (int rc = map_id_check("vslam_voxel_extract_dev", map_id, -1)) return rc;
     VS_ENTER(c);
     return launch_voxel_extract(m->t, map_id, min_count, d_out, d_map_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
 }
@@ -1830,10 +1871,7 @@ int vslam_tsdf_create(vslam_ctx* ctx, double voxel_size, int trunc_voxels, int l
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     if (!c || !out) { set_error("vslam_tsdf_create: null argument"); return VSLAM_ERR_ARG; }
     *out = nullptr;
-    const float vs = (float)voxel_size;
-    if (!std::isfinite(voxel_size) || !(voxel_size > 0) || !std::isfinite(vs) || !(vs > 0.f) || !std::isfinite(1.0f / vs)) {
-        set_error("vslam_tsdf_create: voxel_size %g is not a finite positive float", voxel_size); return VSLAM_ERR_ARG;
-    }
+    if (int rc = voxel_size_check("vslam_tsdf_create", voxel_size)) return rc;
     if (trunc_voxels < 1 || trunc_voxels > 8) { set_error("vslam_tsdf_create: trunc_voxels %d outside [1, 8]", trunc_voxels); return VSLAM_ERR_ARG; }
     if (log2_blocks < 6 || log2_blocks > 22) { set_error("vslam_tsdf_create: log2_blocks %d outside [6, 22]", log2_blocks); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
@@ -1842,17 +1880,15 @@ int vslam_tsdf_create(vslam_ctx* ctx, double voxel_size, int trunc_voxels, int l
     const size_t n = (size_t)1 << log2_blocks, words = ((size_t)c->p.max_batch + 63) / 64;
     // one allocation: pool | keys | frame masks | frame table | counters | list (every part a multiple of 8 bytes, the pool 16-byte aligned)
     const size_t pool_b = n * 8192, keys_b = n * 8, pairs_b = n * words * 8, frames_b = (size_t)c->p.max_batch * kTsdfFrameDoubles * 8, cnt_b = 8 * kTsdfCounters;
-    m->ctx = c; m->bytes = pool_b + keys_b + pairs_b + frames_b + cnt_b + n * 4;
-    t.log2_blocks = log2_blocks; t.J = trunc_voxels; t.frame_words = (int)words; t.vs = vs; t.inv = 1.0f / vs;
-    if (hipMalloc(&m->base, m->bytes) != hipSuccess) { set_error("vslam_tsdf_create: hipMalloc(%zu) failed", m->bytes); delete m; return VSLAM_ERR_HIP; }
-    uint8_t* p = reinterpret_cast<uint8_t*>(m->base);
+    t.log2_blocks = log2_blocks; t.J = trunc_voxels; t.frame_words = (int)words; t.vs = (float)voxel_size; t.inv = 1.0f / t.vs;
+    if (int rc = m->alloc(c, pool_b + keys_b + pairs_b + frames_b + cnt_b + n * 4, "vslam_tsdf_create")) { delete m; return rc; }
+    uint8_t* p = m->base;
     t.pool = reinterpret_cast<uint4*>(p); p += pool_b;
     t.keys = reinterpret_cast<unsigned long long*>(p); p += keys_b;
     t.pairs = reinterpret_cast<unsigned long long*>(p); p += pairs_b;
     t.frames = reinterpret_cast<double*>(p); p += frames_b;
     t.counters = reinterpret_cast<unsigned long long*>(p); p += cnt_b;
     t.list = reinterpret_cast<uint32_t*>(p);
-    c->dev_bytes += m->bytes;
     int rc = launch_tsdf_clear(t, c->stream);
     if (rc == VSLAM_OK && hipStreamSynchronize(c->stream) != hipSuccess) { set_error("vslam_tsdf_create: clearing the pool failed"); rc = VSLAM_ERR_HIP; }
     if (rc) { vslam_tsdf_destroy(reinterpret_cast<vslam_tsdf_map*>(m)); return rc; }
@@ -1863,10 +1899,7 @@ int vslam_tsdf_create(vslam_ctx* ctx, double voxel_size, int trunc_voxels, int l
 void vslam_tsdf_destroy(vslam_tsdf_map* tm) {
     TsdfMap* m = reinterpret_cast<TsdfMap*>(tm);
     if (!m) return;
-    hipSetDevice(m->ctx->device);
-    hipStreamSynchronize(m->ctx->stream);
-    hipFree(m->base);
-    m->ctx->dev_bytes -= m->bytes;
+    m->free();
     m->mesh.release();
     m->render.release();
     m->reint.release();
@@ -1885,37 +1918,26 @@ int vslam_tsdf_stats(vslam_tsdf_map* tm, struct vslam_tsdf_stats* host) {
     if (!m || !host || host->struct_size != (int32_t)sizeof(struct vslam_tsdf_stats)) { set_error("vslam_tsdf_stats: null argument or struct_size mismatch"); return VSLAM_ERR_ARG; }
     VS_ENTER(m->ctx);
     unsigned long long w[kTsdfCounters];
-    VS_HIP(hipMemcpyAsync(w, m->t.counters, sizeof(w), hipMemcpyDeviceToHost, m->ctx->stream));
-    VS_HIP(hipStreamSynchronize(m->ctx->stream));
+    if (int rc = read_counters(m->ctx, m->t.counters, w, kTsdfCounters)) return rc;
     host->n_blocks = w[0]; host->n_samples = w[1]; host->n_dropped_range = w[2]; host->n_dropped_full = w[3]; host->status = (uint32_t)w[4];
     host->n_frames_skipped = w[5]; host->n_pairs_visited = w[6]; host->n_pairs_kept = w[7];
     return VSLAM_OK;
 }
 
-static TsdfMap* tsdf_map_of(const Ctx* c, vslam_tsdf_map* tm, const char* who) {
-    TsdfMap* m = reinterpret_cast<TsdfMap*>(tm);
-    if (!c || !m || m->ctx != c) { set_error("%s: null context or map, or a map of another context", who); return nullptr; }
-    return m;
-}
-
 int vslam_tsdf_integrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* d_disparity, const uint8_t* d_gray, size_t img_bytes, int pitch,
                              int w, int h, int B, const double* d_T_c_w, const int32_t* d_map_id, double z_min, double z_max, int step) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_integrate_dev");
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_integrate_dev");
     if (!m) return VSLAM_ERR_ARG;
-    if (!d_map_id) { set_error("vslam_tsdf_integrate_dev: null d_map_id"); return VSLAM_ERR_ARG; }
     VoxelImages a;
-    if (int rc = voxel_images(c, "vslam_tsdf_integrate_dev", d_disparity, w, h, B, d_T_c_w, z_min, z_max, step, a)) return rc;
-    if (d_gray && (pitch < w || img_bytes < (size_t)pitch * h)) {
-        set_error("vslam_tsdf_integrate_dev: pitch %d / img_bytes %zu do not hold a %d x %d image", pitch, img_bytes, w, h); return VSLAM_ERR_ARG;
-    }
+    if (int rc = map_images(c, "vslam_tsdf_integrate_dev", d_disparity, d_gray, img_bytes, pitch, w, h, B, d_T_c_w, d_map_id, z_min, z_max, step, a)) return rc;
     VS_ENTER(c);
     return launch_tsdf_integrate(m->t, a, d_gray, img_bytes, pitch, d_map_id, tsdf_form(c), c->stream);
 }
 
 int vslam_tsdf_reach_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, uint32_t* d_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_reach_dev");
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_reach_dev");
     if (!m) return VSLAM_ERR_ARG;
     if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 4) { set_error("vslam_tsdf_reach_dev: d_out is null or not 4-byte aligned"); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
@@ -1928,15 +1950,12 @@ int vslam_tsdf_reintegrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* 
                                int w, int h, int B, const double* d_T_old, const double* d_T_new, const int32_t* d_map_id,
                                const uint32_t* d_reach, double z_min, double z_max, int step) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_reintegrate_dev");
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_reintegrate_dev");
     if (!m) return VSLAM_ERR_ARG;
     if (B == 0) return VSLAM_OK;
     if (!d_map_id || !d_T_old || !d_T_new || !d_reach) { set_error("vslam_tsdf_reintegrate_dev: null d_map_id, d_T_old, d_T_new or d_reach"); return VSLAM_ERR_ARG; }
     VoxelImages a;
-    if (int rc = voxel_images(c, "vslam_tsdf_reintegrate_dev", d_disparity, w, h, B, d_T_new, z_min, z_max, step, a)) return rc;
-    if (d_gray && (pitch < w || img_bytes < (size_t)pitch * h)) {
-        set_error("vslam_tsdf_reintegrate_dev: pitch %d / img_bytes %zu do not hold a %d x %d image", pitch, img_bytes, w, h); return VSLAM_ERR_ARG;
-    }
+    if (int rc = map_images(c, "vslam_tsdf_reintegrate_dev", d_disparity, d_gray, img_bytes, pitch, w, h, B, d_T_new, d_map_id, z_min, z_max, step, a)) return rc;
     VS_ENTER(c);
     if (int rc = m->reint.reserve(tsdf_reint_table_bytes(m->t, c->p.max_batch), c->stream)) return rc;
     const TsdfReint r = tsdf_reint_tables(m->t, c->p.max_batch, m->reint.p, d_reach);
@@ -1946,10 +1965,10 @@ int vslam_tsdf_reintegrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* 
 int vslam_tsdf_extract_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_weight, vslam_surfel* d_out, int32_t* d_map_out, size_t capacity,
                            uint64_t* d_n_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_extract_dev");
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_extract_dev");
     if (!m) return VSLAM_ERR_ARG;
-    if (!d_n_out || (capacity > 0 && !d_out)) { set_error("vslam_tsdf_extract_dev: null d_n_out, or null d_out with a capacity"); return VSLAM_ERR_ARG; }
-    if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_tsdf_extract_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    if (int rc = counted_output_check("vslam_tsdf_extract_dev", d_n_out, capacity, d_out, "null d_out")) return rc;
+    if (int rc = map_id_check("vslam_tsdf_extract_dev", map_id, -1)) return rc;
     VS_ENTER(c);
     return launch_tsdf_extract(m->t, map_id, min_weight, d_out, d_map_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
 }
@@ -1957,10 +1976,10 @@ int vslam_tsdf_extract_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int m
 int vslam_tsdf_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int32_t* d_block_out, uint32_t* d_voxels_out, size_t capacity,
                           uint64_t* d_n_out) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_blocks_dev");
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_blocks_dev");
     if (!m) return VSLAM_ERR_ARG;
-    if (!d_n_out || (capacity > 0 && (!d_block_out || !d_voxels_out))) { set_error("vslam_tsdf_blocks_dev: null d_n_out, or a null output with a capacity"); return VSLAM_ERR_ARG; }
-    if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_tsdf_blocks_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    if (int rc = counted_output_check("vslam_tsdf_blocks_dev", d_n_out, capacity, d_block_out && d_voxels_out, "a null output")) return rc;
+    if (int rc = map_id_check("vslam_tsdf_blocks_dev", map_id, -1)) return rc;
     VS_ENTER(c);
     return launch_tsdf_blocks(m->t, map_id, d_block_out, d_voxels_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
 }
@@ -1968,7 +1987,7 @@ int vslam_tsdf_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int32_
 int vslam_tsdf_mesh_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_weight, vslam_surfel* d_vertices, int32_t* d_vertex_map, size_t vertex_capacity,
                         vslam_triangle* d_triangles, size_t triangle_capacity, uint64_t* d_counts) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_mesh_dev");
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_mesh_dev");
     if (!m) return VSLAM_ERR_ARG;
     if (!d_counts || (vertex_capacity > 0 && !d_vertices) || (triangle_capacity > 0 && !d_triangles)) {
         set_error("vslam_tsdf_mesh_dev: null d_counts, or a null output with a capacity"); return VSLAM_ERR_ARG;
@@ -1977,12 +1996,11 @@ int vslam_tsdf_mesh_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_
         reinterpret_cast<uintptr_t>(d_counts) % 8) {
         set_error("vslam_tsdf_mesh_dev: d_vertices must be 16-byte, d_counts 8-byte, d_vertex_map and d_triangles 4-byte aligned"); return VSLAM_ERR_ARG;
     }
-    if (map_id < -1 || map_id > kVoxelMaxMap) { set_error("vslam_tsdf_mesh_dev: map_id %d outside [-1, %d]", map_id, kVoxelMaxMap); return VSLAM_ERR_ARG; }
+    if (int rc = map_id_check("vslam_tsdf_mesh_dev", map_id, -1)) return rc;
     VS_ENTER(c);
     // the vertex-id table holds every block claimed so far: the count is read here, after everything queued before this call
     unsigned long long n_blocks = 0;
-    VS_HIP(hipMemcpyAsync(&n_blocks, m->t.counters, sizeof(n_blocks), hipMemcpyDeviceToHost, c->stream));
-    VS_HIP(hipStreamSynchronize(c->stream));
+    if (int rc = read_counters(c, m->t.counters, &n_blocks, 1)) return rc;
     const size_t n_slots = (size_t)1 << m->t.log2_blocks, blocks = std::max<size_t>(std::min<size_t>((size_t)n_blocks, n_slots), 1);
     const size_t have = m->mesh.bytes >= n_slots * 4 ? (m->mesh.bytes - n_slots * 4) / (1536 * 4) : 0;
     if (have < blocks) {
@@ -1997,7 +2015,7 @@ int vslam_tsdf_mesh_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int min_
 
 int vslam_tsdf_load_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const int32_t* d_block_ids, const uint32_t* d_voxels, size_t n) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_load_blocks_dev");
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_load_blocks_dev");
     if (!m) return VSLAM_ERR_ARG;
     if (n > 0 && (!d_block_ids || !d_voxels)) { set_error("vslam_tsdf_load_blocks_dev: a null input with n > 0"); return VSLAM_ERR_ARG; }
     if (reinterpret_cast<uintptr_t>(d_block_ids) % 16 || reinterpret_cast<uintptr_t>(d_voxels) % 16) {
@@ -2015,7 +2033,7 @@ constexpr int kTsdfRenderMaxSamples = 8192;
 int vslam_tsdf_render_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const struct vslam_tsdf_render_params* rp, int V, const double* d_T_c_w, const int32_t* d_map_id,
                           float* d_depth, float* d_attr, uint64_t* d_counts) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    TsdfMap* m = tsdf_map_of(c, tm, "vslam_tsdf_render_dev");
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_render_dev");
     if (!m) return VSLAM_ERR_ARG;
     if (!rp || rp->struct_size != (int32_t)sizeof(struct vslam_tsdf_render_params)) { set_error("vslam_tsdf_render_dev: null params or struct_size mismatch"); return VSLAM_ERR_ARG; }
     if (rp->w < 1 || rp->h < 1 || V < 0) { set_error("vslam_tsdf_render_dev: w %d, h %d below 1 or V %d below 0", rp->w, rp->h, V); return VSLAM_ERR_ARG; }
@@ -2058,7 +2076,7 @@ int vslam_place_create(vslam_ctx* ctx, int rows_per_entry, int capacity_entries,
     if (capacity_entries < 1) { set_error("vslam_place_create: capacity_entries %d must be >= 1", capacity_entries); return VSLAM_ERR_ARG; }
     VS_ENTER(c);
     PlaceDb* d = new PlaceDb(&c->dev_bytes);
-    d->ctx = c; d->n_refused = 0; d->block = nullptr;
+    d->n_refused = 0;
     const size_t R = (size_t)rows_per_entry, Rs = (R + 31) & ~(size_t)31, cap = (size_t)capacity_entries;
     d->v = PlaceView{};
     d->v.rows = rows_per_entry; d->v.stride_rows = (int)Rs; d->v.capacity = capacity_entries; d->v.n_entries = 0;
@@ -2072,10 +2090,8 @@ int vslam_place_create(vslam_ctx* ctx, int rows_per_entry, int capacity_entries,
     };
     Layout m(nullptr);
     layout(m);
-    d->bytes = m.off;
-    if (hipMalloc((void**)&d->block, d->bytes) != hipSuccess) { set_error("vslam_place_create: hipMalloc(%zu) failed", d->bytes); delete d; return VSLAM_ERR_HIP; }
-    c->dev_bytes += d->bytes;
-    Layout a(d->block);
+    if (int rc = d->alloc(c, m.off, "vslam_place_create")) { delete d; return rc; }
+    Layout a(d->base);
     layout(a);
     *out = reinterpret_cast<vslam_place_db*>(d);
     return VSLAM_OK;
@@ -2084,10 +2100,7 @@ int vslam_place_create(vslam_ctx* ctx, int rows_per_entry, int capacity_entries,
 void vslam_place_destroy(vslam_place_db* db) {
     PlaceDb* d = reinterpret_cast<PlaceDb*>(db);
     if (!d) return;
-    hipSetDevice(d->ctx->device);
-    hipStreamSynchronize(d->ctx->stream);
-    hipFree(d->block);
-    d->ctx->dev_bytes -= d->bytes;
+    d->free();
     d->dst.release(); d->work.release();
     delete d;
 }
@@ -2147,11 +2160,6 @@ int vslam_place_read_meta(vslam_place_db* db, int first, int count, int32_t* n, 
     return VSLAM_OK;
 }
 
-static PlaceDb* place_db_of(const Ctx* c, vslam_place_db* db, const char* who) {
-    PlaceDb* d = reinterpret_cast<PlaceDb*>(db);
-    if (!c || !d || d->ctx != c) { set_error("%s: null context or database, or a database of another context", who); return nullptr; }
-    return d;
-}
 // the query range of the score / select / verify entries
 static int place_range(const PlaceDb* d, const char* who, int q0, int nq, int nq_max) {
     if (nq < 1 || nq > nq_max) { set_error("%s: nq %d outside 1..%d", who, nq, nq_max); return VSLAM_ERR_ARG; }
@@ -2163,7 +2171,7 @@ int vslam_place_add_dev(vslam_ctx* ctx, vslam_place_db* db, const uint8_t* d_des
                         const int32_t* d_seq, const int32_t* d_frame, const vslam_keypoint* d_kps, const float* d_xyz, const uint8_t* d_valid, int kp_capacity,
                         int B, int* first_entry) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    PlaceDb* d = place_db_of(c, db, "vslam_place_add_dev");
+    PlaceDb* d = owned_by<PlaceDb>(c, db, "vslam_place_add_dev");
     if (!d) return VSLAM_ERR_ARG;
     if (!d_desc || !d_n || !d_seq || !d_frame) { set_error("vslam_place_add_dev: null d_desc, d_n, d_seq or d_frame"); return VSLAM_ERR_ARG; }
     if (B < 1) { set_error("vslam_place_add_dev: batch %d must be >= 1", B); return VSLAM_ERR_ARG; }
@@ -2197,7 +2205,7 @@ int vslam_place_add_dev(vslam_ctx* ctx, vslam_place_db* db, const uint8_t* d_des
 
 int vslam_place_score_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, int tau, int min_gap, int32_t* d_score, int ld) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    PlaceDb* d = place_db_of(c, db, "vslam_place_score_dev");
+    PlaceDb* d = owned_by<PlaceDb>(c, db, "vslam_place_score_dev");
     if (!d) return VSLAM_ERR_ARG;
     if (!d_score) { set_error("vslam_place_score_dev: null d_score"); return VSLAM_ERR_ARG; }
     if (int rc = place_range(d, "vslam_place_score_dev", q0, nq, 65535)) return rc;
@@ -2210,7 +2218,7 @@ int vslam_place_score_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, in
 int vslam_place_select_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, const int32_t* d_score, int ld, int K, int min_score, int32_t* d_cand,
                            int32_t* d_cand_score) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    PlaceDb* d = place_db_of(c, db, "vslam_place_select_dev");
+    PlaceDb* d = owned_by<PlaceDb>(c, db, "vslam_place_select_dev");
     if (!d) return VSLAM_ERR_ARG;
     if (!d_score || !d_cand || !d_cand_score) { set_error("vslam_place_select_dev: null d_score, d_cand or d_cand_score"); return VSLAM_ERR_ARG; }
     if (int rc = place_range(d, "vslam_place_select_dev", q0, nq, 1 << 30)) return rc;
@@ -2223,7 +2231,7 @@ int vslam_place_select_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, c
 int vslam_place_verify_dev(vslam_ctx* ctx, vslam_place_db* db, int q0, int nq, const int32_t* d_cand, int K, int rank, int min_inliers, double* d_T_q_c,
                            int32_t* d_n_matches, int32_t* d_n_inliers) {
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    PlaceDb* d = place_db_of(c, db, "vslam_place_verify_dev");
+    PlaceDb* d = owned_by<PlaceDb>(c, db, "vslam_place_verify_dev");
     if (!d) return VSLAM_ERR_ARG;
     if (!d_cand || !d_T_q_c || !d_n_matches || !d_n_inliers) { set_error("vslam_place_verify_dev: null d_cand, d_T_q_c, d_n_matches or d_n_inliers"); return VSLAM_ERR_ARG; }
     if (!d->v.xy) { set_error("vslam_place_verify_dev: the database was created without geometry"); return VSLAM_ERR_ARG; }

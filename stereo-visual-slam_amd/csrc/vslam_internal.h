@@ -482,7 +482,14 @@ struct RectifyState { uint2* d_map[2]; int4* d_tiles[2]; int src_w[2], src_h[2];
 constexpr int kVoxelMaxMap = 1022;       // map ids 0 .. 1022: the key's top ten bits, all-ones left to the empty slot
 constexpr int kVoxelCounters = 8;        // uint64 words behind a table: occupied, points, dropped for range, dropped full, status (the rest unused)
 struct VoxelTable { uint8_t* slots; unsigned long long* counters; int log2_capacity; float vs, inv; };
-struct VoxelMap { Ctx* ctx; VoxelTable t; size_t bytes; };
+// What a context hands out and takes back -- VoxelMap, TsdfMap, PlaceDb -- starts with this: the context, the object's one device allocation and its
+// size, counted in the context's dev_bytes.  `noun`: what the messages of owned_by() call the object.
+struct Owned {
+    Ctx* ctx = nullptr; uint8_t* base = nullptr; size_t bytes = 0;
+    int alloc(Ctx* c, size_t n, const char* who);   // on `who`'s behalf; a failure leaves nothing allocated and nothing counted
+    void free();                                    // after everything queued on the context's stream; the object's DevBufs are its own to release
+};
+struct VoxelMap : Owned { static constexpr const char* noun = "map"; VoxelTable t; };
 // B disparity maps (B x h x w f32, tightly packed), their poses (B x 7) and the pixels wanted: every step-th column and row, depth gate (z_min, z_max)
 struct VoxelImages { const float* disp; int w, h, B, step; const double* T; double z_min, z_max, fx, fy, cx, cy, b; };
 int launch_voxel_clear(const VoxelTable& t, hipStream_t stream);
@@ -502,7 +509,7 @@ constexpr int kTsdfCounters = 8;         // uint64 words: blocks, samples, dropp
 constexpr int kTsdfFrameDoubles = 16;    // a frame of the frame table: R (9), t (3), the inverse pose's translation (3), the map id (-1: takes no part)
 struct TsdfTable { unsigned long long* keys; uint32_t* list; uint4* pool; unsigned long long* counters; double* frames; unsigned long long* pairs;
                    int log2_blocks, J, frame_words; float vs, inv; };
-struct TsdfMap { Ctx* ctx; TsdfTable t; size_t bytes; void* base;
+struct TsdfMap : Owned { static constexpr const char* noun = "map"; TsdfTable t;
                  DevBuf mesh; // the vertex-id table of vslam_tsdf_mesh_dev: vid (3 x 512 int32 per claimed block) | pos_of_slot (one uint32 per slot); grown by the first mesh call
                  DevBuf render; // the tables of vslam_tsdf_render_dev: the view table (16 doubles per view) | (form 1) one (k_lo, k_hi) per view and 16 x 16 tile; grown on demand
                  DevBuf reint; // the old sides of vslam_tsdf_reintegrate_dev: a second frame table | a second frame mask per slot | n0; grown by the first such call
@@ -542,7 +549,7 @@ int launch_tsdf_render(const TsdfTable& t, const TsdfRenderCall& rc, uint8_t* d_
 // and, with geometry (xy non-null), `rows` slots of pixel, camera-frame point, valid flag and the ascending list qsel[0 .. nqsel) of the valid rows.
 struct PlaceView { uint8_t* desc; int32_t* n; int32_t* seq; int32_t* frame; float2* xy; float* xyz; uint8_t* valid; int32_t* qsel; int32_t* nqsel;
                    int rows, stride_rows, capacity, n_entries; };
-struct PlaceDb { Ctx* ctx; PlaceView v; uint8_t* block; size_t bytes; unsigned long long n_refused; DevBuf dst, work;
+struct PlaceDb : Owned { static constexpr const char* noun = "database"; PlaceView v; unsigned long long n_refused; DevBuf dst, work;
                  PlaceDb(size_t* acct) : dst("place add table", acct), work("place verify scratch", acct) {} };
 int launch_place_add(const PlaceView& v, const int32_t* d_dst, const uint8_t* d_desc, size_t desc_stride, const int32_t* d_n, const int32_t* d_seq,
                      const int32_t* d_frame, const vslam_keypoint* d_kps, const float* d_xyz, const uint8_t* d_valid, int kp_capacity, int B, hipStream_t stream);

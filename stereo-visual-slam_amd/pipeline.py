@@ -672,15 +672,17 @@ class KeyframePipeline:
             map_id[first[s_] + ids] = s_
         return T, map_id
 
-    def dense_map(self, voxel_size=0.2, log2_capacity=22, z_min=None, z_max=None, step=1, voxel_map=None, poses=None):
-        """The dense map of the last step (depth="sgbm", ba_windows="tracks"): the SGBM disparity and the left image of every frame trajectories()
-        returns, reprojected at that frame's BA-refined pose and fused into a VoxelMap (vslam_voxel_fuse_disparity_dev) -- map id = the segment index.
-        z_min / z_max default to the context's depth_min / depth_reliable (the reference trusts stereo depth below 40 m only); every step-th pixel.
-        voxel_map: a VoxelMap of this pipeline's context to accumulate into over several steps (voxel_size / log2_capacity then go unused); otherwise
-        a new one.  poses: the corrected trajectories close_loops() returned, in place of the BA poses (None: the BA poses).
-        Returns the map: .extract() / .stats() read it, write_ply(path, vm.extract()) writes it."""
-        assert self.depth == "sgbm", "dense_map needs depth='sgbm': it fuses the SGBM disparity maps"
-        assert self.with_ba and self.ba_windows == "tracks", "dense_map needs ba_windows='tracks': the poses are the BA windows'"
+    def _map_inputs(self, poses, z_min=None, z_max=None, fuse=None, **given):
+        """The front dense_map, surface_map, surface_views and surface_remap share -- which frames meet a map, at which poses, under which map ids,
+        between which depth gates: (T_c_w (B, 7), map_id (B,), z_min, z_max) of dense_map_inputs(poses), a gate left None standing for the
+        context's depth_min / depth_reliable.  given: the caller's voxel_map= or tsdf_map= argument, which, unless None, must be of this pipeline's
+        context.  fuse: the name of a caller that fuses the step's SGBM maps; it needs depth="sgbm" and the BA windows' poses, and finds T and map_id
+        on the device as self.dense_T / self.dense_map_id, uploaded on the pipeline's stream."""
+        if fuse is not None:
+            assert self.depth == "sgbm", "%s needs depth='sgbm': it fuses the SGBM disparity maps" % fuse
+            assert self.with_ba and self.ba_windows == "tracks", "%s needs ba_windows='tracks': the poses are the BA windows'" % fuse
+        for name, m in given.items():
+            assert m is None or m.vo is self.vo, "%s belongs to another context" % name
         if poses is not None:
             self.vo.sync()
             torch.cuda.synchronize(self.dev)
@@ -688,11 +690,21 @@ class KeyframePipeline:
         p = self.vo.params
         z_min = p.depth_min if z_min is None else float(z_min)
         z_max = p.depth_reliable if z_max is None else float(z_max)
+        if fuse is not None:
+            with torch.cuda.stream(self.stream):
+                self.dense_T = torch.from_numpy(T).to(self.dev)
+                self.dense_map_id = torch.from_numpy(map_id).to(self.dev)
+        return T, map_id, z_min, z_max
+
+    def dense_map(self, voxel_size=0.2, log2_capacity=22, z_min=None, z_max=None, step=1, voxel_map=None, poses=None):
+        """The dense map of the last step (depth="sgbm", ba_windows="tracks"): the SGBM disparity and the left image of every frame trajectories()
+        returns, reprojected at that frame's BA-refined pose and fused into a VoxelMap (vslam_voxel_fuse_disparity_dev) -- map id = the segment index.
+        z_min / z_max default to the context's depth_min / depth_reliable (the reference trusts stereo depth below 40 m only); every step-th pixel.
+        voxel_map: a VoxelMap of this pipeline's context to accumulate into over several steps (voxel_size / log2_capacity then go unused); otherwise
+        a new one.  poses: the corrected trajectories close_loops() returned, in place of the BA poses (None: the BA poses).
+        Returns the map: .extract() / .stats() read it, write_ply(path, vm.extract()) writes it."""
+        T, map_id, z_min, z_max = self._map_inputs(poses, z_min, z_max, fuse="dense_map", voxel_map=voxel_map)
         vm = voxel_map if voxel_map is not None else self.vo.voxel_map(voxel_size, log2_capacity)
-        assert vm.vo is self.vo, "voxel_map belongs to another context"
-        with torch.cuda.stream(self.stream):
-            self.dense_T = torch.from_numpy(T).to(self.dev)
-            self.dense_map_id = torch.from_numpy(map_id).to(self.dev)
         self.vo.voxel_fuse_disparity_dev(vm, self.d_disp.data_ptr(), self.d_imgs.data_ptr(), self.img_bytes, self.pitch, self.w, self.h, self.B,
                                          self.dense_T.data_ptr(), self.dense_map_id.data_ptr(), z_min, z_max, int(step))
         return vm
@@ -706,20 +718,8 @@ class KeyframePipeline:
         Returns the map: .extract() reads the surfels, write_surfel_ply(path, tm.extract()) writes them; .mesh() connects them into triangles,
         write_mesh_ply(path, *tm.mesh()) writes the mesh.  self.surface_frames remembers what was integrated (poses, map ids, gates, the call's
         reach) for surface_remap()."""
-        assert self.depth == "sgbm", "surface_map needs depth='sgbm': it fuses the SGBM disparity maps"
-        assert self.with_ba and self.ba_windows == "tracks", "surface_map needs ba_windows='tracks': the poses are the BA windows'"
-        if poses is not None:
-            self.vo.sync()
-            torch.cuda.synchronize(self.dev)
-        T, map_id = self.dense_map_inputs() if poses is None else self.dense_map_inputs(poses)   # (synchronises: the step is complete)
-        p = self.vo.params
-        z_min = p.depth_min if z_min is None else float(z_min)
-        z_max = p.depth_reliable if z_max is None else float(z_max)
+        T, map_id, z_min, z_max = self._map_inputs(poses, z_min, z_max, fuse="surface_map", tsdf_map=tsdf_map)
         tm = tsdf_map if tsdf_map is not None else self.vo.tsdf_map(voxel_size, trunc_voxels, log2_blocks)
-        assert tm.vo is self.vo, "tsdf_map belongs to another context"
-        with torch.cuda.stream(self.stream):
-            self.dense_T = torch.from_numpy(T).to(self.dev)
-            self.dense_map_id = torch.from_numpy(map_id).to(self.dev)
         tm.integrate_dev(self.d_disp.data_ptr(), self.d_imgs.data_ptr(), self.img_bytes, self.pitch, self.w, self.h, self.B,
                          self.dense_T.data_ptr(), self.dense_map_id.data_ptr(), z_min, z_max, int(step))
         self.last_surface_map = tm
@@ -743,9 +743,7 @@ class KeyframePipeline:
         assert st is not None, "surface_remap needs a surface_map() call before it: it re-integrates that call's frames"
         tm = tsdf_map if tsdf_map is not None else st["tsdf_map"]
         assert tm is st["tsdf_map"] and getattr(tm, "h", None), "surface_remap: tsdf_map is not the (open) map the last surface_map() filled"
-        self.vo.sync()
-        torch.cuda.synchronize(self.dev)
-        T_new, id_new = self.dense_map_inputs(poses)
+        T_new, id_new, _, _ = self._map_inputs(poses, tsdf_map=tm)
         T_old, id_old = st["T"], st["map_id"]
         was, now = id_old >= 0, id_new >= 0
         assert (id_old[was & now] == id_new[was & now]).all(), "surface_remap: a frame changed its segment"
@@ -786,12 +784,8 @@ class KeyframePipeline:
         disparity = fx * b / depth at the scaled fx (0 where the ray misses)."""
         tm = tsdf_map if tsdf_map is not None else getattr(self, "last_surface_map", None)
         assert tm is not None and getattr(tm, "h", None), "surface_views needs a TsdfMap: call surface_map() first or pass tsdf_map="
-        assert tm.vo is self.vo, "tsdf_map belongs to another context"
         assert scale > 0
-        if poses is not None:
-            self.vo.sync()
-            torch.cuda.synchronize(self.dev)
-        T, map_id = self.dense_map_inputs() if poses is None else self.dense_map_inputs(poses)
+        T, map_id, _, _ = self._map_inputs(poses, tsdf_map=tm)
         fx, fy, cx, cy, b = (float(v) for v in self.vo.params.cam)
         K4 = (fx * scale, fy * scale, cx * scale, cy * scale)
         size = (max(int(round(self.w * scale)), 1), max(int(round(self.h * scale)), 1))

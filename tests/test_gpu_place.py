@@ -1,6 +1,8 @@
 """GPU: the place database -- add, score, select, verify -- bit for bit against tests/place_ref.py (all integer), the refused arguments, and the
 verification against the three existing entries called by hand and against the oracle's matcher + RANSAC."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
@@ -13,6 +15,18 @@ pytestmark = pytest.mark.gpu
 def _dev():
     import torch
     return torch.device("cuda:0")
+
+
+def _refusals(lib, err, section):
+    """no(key, rc): the call returned `err` and left the message tests/golden/refused_messages.json holds under `key` -- the text the library gave
+    before its host tier was put in order, which every later library must reproduce"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refused_messages.json")) as f:
+        want = json.load(f)[section]
+
+    def no(key, rc):
+        assert rc == err, key
+        assert lib.vslam_last_error().decode() == want[key], key
+    return no
 
 
 def _add(vo, db, descs, seqs, frames, add=None, ns=None, geom=None, kp_cap=None):
@@ -232,6 +246,7 @@ def test_add_masks_clamp_refusal_and_valid_rows(vo, pkg):
 def test_refused_arguments(vo, pkg):
     import torch
     lib = vo.lib
+    no = _refusals(lib, pkg.VSLAM_ERR_ARG, "place")
     db = vo.place_db(rows=32, capacity=4, with_geometry=False)
     dbg = vo.place_db(rows=32, capacity=4, with_geometry=True)
     other = pkg.VO(device=0, max_batch=1)
@@ -242,59 +257,58 @@ def test_refused_arguments(vo, pkg):
         torch.cuda.synchronize()
         p, d, n = buf.data_ptr(), desc.data_ptr(), ints.data_ptr()
         h = C.c_void_p()
-        bad = lambda rc: rc == pkg.VSLAM_ERR_ARG and len(lib.vslam_last_error()) > 0
-        assert bad(lib.vslam_place_create(None, 32, 4, 0, C.byref(h)))
-        assert bad(lib.vslam_place_create(vo.h, 0, 4, 0, C.byref(h)))
-        assert bad(lib.vslam_place_create(vo.h, 4097, 4, 0, C.byref(h)))
-        assert bad(lib.vslam_place_create(vo.h, 32, 0, 0, C.byref(h)))
-        assert bad(lib.vslam_place_clear(None))
-        assert bad(lib.vslam_place_stats(db.h, None))
+        no("create null ctx", lib.vslam_place_create(None, 32, 4, 0, C.byref(h)))
+        no("create rows 0", lib.vslam_place_create(vo.h, 0, 4, 0, C.byref(h)))
+        no("create rows 4097", lib.vslam_place_create(vo.h, 4097, 4, 0, C.byref(h)))
+        no("create capacity 0", lib.vslam_place_create(vo.h, 32, 0, 0, C.byref(h)))
+        no("clear null database", lib.vslam_place_clear(None))
+        no("stats null host", lib.vslam_place_stats(db.h, None))
         st = pkg.PlaceStats(); st.struct_size = 4
-        assert bad(lib.vslam_place_stats(db.h, C.byref(st)))
-        assert bad(lib.vslam_place_read_entry(db.h, 3, np.zeros(4, np.int32), None, None, None, None, None))
+        no("stats struct_size", lib.vslam_place_stats(db.h, C.byref(st)))
+        no("read_entry 3 of 3", lib.vslam_place_read_entry(db.h, 3, np.zeros(4, np.int32), None, None, None, None, None))
         add = lambda *a: lib.vslam_place_add_dev(*a)
-        assert bad(add(other.h, db.h, d, 1024, n, None, n, n, None, None, None, 0, 2, None))            # a database of another context
-        assert bad(add(vo.h, None, d, 1024, n, None, n, n, None, None, None, 0, 2, None))
-        assert bad(add(vo.h, db.h, None, 1024, n, None, n, n, None, None, None, 0, 2, None))
-        assert bad(add(vo.h, db.h, d, 1024, None, None, n, n, None, None, None, 0, 2, None))
-        assert bad(add(vo.h, db.h, d, 1024, n, None, None, n, None, None, None, 0, 2, None))
-        assert bad(add(vo.h, db.h, d, 1024, n, None, n, None, None, None, None, 0, 2, None))
-        assert bad(add(vo.h, db.h, d, 1024, n, None, n, n, None, None, None, 0, 0, None))               # B < 1
-        assert bad(add(vo.h, db.h, d + 4, 1024, n, None, n, n, None, None, None, 0, 2, None))           # alignment
-        assert bad(add(vo.h, db.h, d, 1000, n, None, n, n, None, None, None, 0, 2, None))
-        assert bad(add(vo.h, dbg.h, d, 1024, n, None, n, n, None, None, None, 32, 2, None))             # geometry wanted, not given
+        no("add a database of another context", add(other.h, db.h, d, 1024, n, None, n, n, None, None, None, 0, 2, None))
+        no("add null database", add(vo.h, None, d, 1024, n, None, n, n, None, None, None, 0, 2, None))
+        no("add null d_desc", add(vo.h, db.h, None, 1024, n, None, n, n, None, None, None, 0, 2, None))
+        no("add null d_n", add(vo.h, db.h, d, 1024, None, None, n, n, None, None, None, 0, 2, None))
+        no("add null d_seq", add(vo.h, db.h, d, 1024, n, None, None, n, None, None, None, 0, 2, None))
+        no("add null d_frame", add(vo.h, db.h, d, 1024, n, None, n, None, None, None, None, 0, 2, None))
+        no("add B 0", add(vo.h, db.h, d, 1024, n, None, n, n, None, None, None, 0, 0, None))
+        no("add d_desc not aligned", add(vo.h, db.h, d + 4, 1024, n, None, n, n, None, None, None, 0, 2, None))
+        no("add stride not aligned", add(vo.h, db.h, d, 1000, n, None, n, n, None, None, None, 0, 2, None))
+        no("add geometry wanted, not given", add(vo.h, dbg.h, d, 1024, n, None, n, n, None, None, None, 32, 2, None))
         score = lambda *a: lib.vslam_place_score_dev(*a)
-        assert bad(score(other.h, db.h, 0, 3, 30, 1, p, 8))
-        assert bad(score(vo.h, db.h, 0, 3, 30, 1, None, 8))
-        assert bad(score(vo.h, db.h, 0, 0, 30, 1, p, 8))
-        assert bad(score(vo.h, db.h, -1, 2, 30, 1, p, 8))
-        assert bad(score(vo.h, db.h, 2, 2, 30, 1, p, 8))                                                # range past the entries
-        assert bad(score(vo.h, db.h, 0, 3, -1, 1, p, 8))
-        assert bad(score(vo.h, db.h, 0, 3, 256, 1, p, 8))
-        assert bad(score(vo.h, db.h, 0, 3, 30, 1, p, 2))                                                # ld < n_entries
+        no("score a database of another context", score(other.h, db.h, 0, 3, 30, 1, p, 8))
+        no("score null d_score", score(vo.h, db.h, 0, 3, 30, 1, None, 8))
+        no("score nq 0", score(vo.h, db.h, 0, 0, 30, 1, p, 8))
+        no("score q0 -1", score(vo.h, db.h, -1, 2, 30, 1, p, 8))
+        no("score range past the entries", score(vo.h, db.h, 2, 2, 30, 1, p, 8))
+        no("score tau -1", score(vo.h, db.h, 0, 3, -1, 1, p, 8))
+        no("score tau 256", score(vo.h, db.h, 0, 3, 256, 1, p, 8))
+        no("score ld below n_entries", score(vo.h, db.h, 0, 3, 30, 1, p, 2))
         sel = lambda *a: lib.vslam_place_select_dev(*a)
-        assert bad(sel(other.h, db.h, 0, 3, p, 8, 3, 1, p, p))
-        assert bad(sel(vo.h, db.h, 0, 3, None, 8, 3, 1, p, p))
-        assert bad(sel(vo.h, db.h, 0, 3, p, 8, 3, 1, None, p))
-        assert bad(sel(vo.h, db.h, 0, 3, p, 8, 3, 1, p, None))
-        assert bad(sel(vo.h, db.h, 0, 3, p, 8, 0, 1, p, p))
-        assert bad(sel(vo.h, db.h, 0, 3, p, 8, 9, 1, p, p))
-        assert bad(sel(vo.h, db.h, 0, 3, p, 2, 3, 1, p, p))
-        assert bad(sel(vo.h, db.h, 1, 3, p, 8, 3, 1, p, p))
+        no("select a database of another context", sel(other.h, db.h, 0, 3, p, 8, 3, 1, p, p))
+        no("select null d_score", sel(vo.h, db.h, 0, 3, None, 8, 3, 1, p, p))
+        no("select null d_cand", sel(vo.h, db.h, 0, 3, p, 8, 3, 1, None, p))
+        no("select null d_cand_score", sel(vo.h, db.h, 0, 3, p, 8, 3, 1, p, None))
+        no("select K 0", sel(vo.h, db.h, 0, 3, p, 8, 0, 1, p, p))
+        no("select K 9", sel(vo.h, db.h, 0, 3, p, 8, 9, 1, p, p))
+        no("select ld below n_entries", sel(vo.h, db.h, 0, 3, p, 2, 3, 1, p, p))
+        no("select range past the entries", sel(vo.h, db.h, 1, 3, p, 8, 3, 1, p, p))
         ver = lambda *a: lib.vslam_place_verify_dev(*a)
         t = T.data_ptr()
-        assert bad(ver(vo.h, db.h, 0, 3, p, 3, 0, 10, t, n, n))                                         # no geometry
+        no("verify no geometry", ver(vo.h, db.h, 0, 3, p, 3, 0, 10, t, n, n))
         _add(vo, dbg, [np.zeros((3, 32), np.uint8)] * 3, [0] * 3, [0, 1, 2], geom=([np.zeros((3, 2), np.float32)] * 3, [np.zeros((3, 3), np.float32)] * 3, [np.ones(3, np.uint8)] * 3))
-        assert bad(ver(other.h, dbg.h, 0, 1, p, 3, 0, 10, t, n, n))
-        assert bad(ver(vo.h, dbg.h, 0, 3, None, 3, 0, 10, t, n, n))
-        assert bad(ver(vo.h, dbg.h, 0, 3, p, 3, 0, 10, None, n, n))
-        assert bad(ver(vo.h, dbg.h, 0, 3, p, 3, 0, 10, t, None, n))
-        assert bad(ver(vo.h, dbg.h, 0, 3, p, 3, 0, 10, t, n, None))
-        assert bad(ver(vo.h, dbg.h, 0, 3, p, 3, 3, 10, t, n, n))                                        # rank outside [0, K)
-        assert bad(ver(vo.h, dbg.h, 0, 3, p, 9, 0, 10, t, n, n))
-        assert bad(ver(vo.h, dbg.h, 0, 3, p, 3, 0, -1, t, n, n))
-        assert bad(ver(vo.h, dbg.h, 1, 3, p, 3, 0, 10, t, n, n))
-        assert bad(ver(vo.h, dbg.h, 0, vo.params.max_batch + 1, p, 3, 0, 10, t, n, n))                  # nq > max_batch
+        no("verify a database of another context", ver(other.h, dbg.h, 0, 1, p, 3, 0, 10, t, n, n))
+        no("verify null d_cand", ver(vo.h, dbg.h, 0, 3, None, 3, 0, 10, t, n, n))
+        no("verify null d_T_q_c", ver(vo.h, dbg.h, 0, 3, p, 3, 0, 10, None, n, n))
+        no("verify null d_n_matches", ver(vo.h, dbg.h, 0, 3, p, 3, 0, 10, t, None, n))
+        no("verify null d_n_inliers", ver(vo.h, dbg.h, 0, 3, p, 3, 0, 10, t, n, None))
+        no("verify rank outside [0, K)", ver(vo.h, dbg.h, 0, 3, p, 3, 3, 10, t, n, n))
+        no("verify K 9", ver(vo.h, dbg.h, 0, 3, p, 9, 0, 10, t, n, n))
+        no("verify min_inliers -1", ver(vo.h, dbg.h, 0, 3, p, 3, 0, -1, t, n, n))
+        no("verify range past the entries", ver(vo.h, dbg.h, 1, 3, p, 3, 0, 10, t, n, n))
+        no("verify nq above max_batch", ver(vo.h, dbg.h, 0, vo.params.max_batch + 1, p, 3, 0, 10, t, n, n))
         assert db.stats()["n_entries"] == 3 and db.stats()["n_refused"] == 0
     finally:
         other.close(); db.close(); dbg.close()

@@ -3,6 +3,8 @@ blocks (the block set and all four sums of every voxel) and the surfels bit for 
 tests/tsdf_cases.py in both integration forms; frames permuted, split over calls, held apart by map id, skipped; a pool that overflows; every
 refused argument.  Shapes are small (160 x 48 and smaller, at most four frames)."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
@@ -19,6 +21,18 @@ def _dev(a):
     t = torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
     torch.cuda.synchronize()
     return t
+
+
+def _refusals(lib, err, section):
+    """no(key, rc): the call returned `err` and left the message tests/golden/refused_messages.json holds under `key` -- the text the library gave
+    before its host tier was put in order, which every later library must reproduce"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refused_messages.json")) as f:
+        want = json.load(f)[section]
+
+    def no(key, rc):
+        assert rc == err, key
+        assert lib.vslam_last_error().decode() == want[key], key
+    return no
 
 
 @pytest.fixture(scope="module")
@@ -210,25 +224,43 @@ def test_a_full_pool_drops_blocks_and_keeps_the_rest_exact(vos, form):
         tm.close()
 
 
-def test_the_pool_counts_in_device_bytes(vos):
+def test_the_pool_counts_in_device_bytes(vos, pkg):
     vo = vos(TC.cases()["scene"])
     before = vo.device_bytes
     tm = vo.tsdf_map(0.2, 4, 8)
     assert vo.device_bytes - before >= 8192 << 8
     tm.close()
     assert vo.device_bytes == before
+    # a context closes what was created on it: one object of each kind, each counted to the byte, closed by the context, closed again to no effect
+    ctx = pkg.VO(device=0, max_batch=1)
+    try:
+        base = ctx.device_bytes
+        vm, tm, db = ctx.voxel_map(0.2, 10), ctx.tsdf_map(0.2, 4, 6), ctx.place_db(rows=32, capacity=4, with_geometry=False)
+        table = (32 << 10) + 8 * 8                                            # slots | counters
+        pool = ((8192 + 8 + 8 + 4) << 6) + 16 * 8 + 8 * 8                     # per block: voxels, key, one mask word, list entry | one frame | counters
+        entries = 4 * 32 * 32 + 3 * 256                                       # descriptors | n, seq, frame, each padded to 256 bytes
+        assert ctx.device_bytes == base + table + pool + entries
+    finally:
+        ctx.close()
+    assert vm.h is None and tm.h is None and db.h is None and ctx.h is None
+    for obj in (vm, tm, db, ctx):
+        obj.close()
+    assert vm.h is None and tm.h is None and db.h is None
 
 
 def test_refused_arguments(vos, pkg):
     import torch
     vo = vos(TC.cases()["scene"])
     lib, ERR = vo.lib, pkg.VSLAM_ERR_ARG
+    no = _refusals(lib, ERR, "tsdf")
     buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
     p = buf.data_ptr()
     h = C.c_void_p()
     for size, J, log2 in ((0.0, 4, 8), (-0.2, 4, 8), (float("nan"), 4, 8), (float("inf"), 4, 8), (1e-60, 4, 8), (0.2, 0, 8), (0.2, 9, 8), (0.2, -1, 8), (0.2, 4, 5), (0.2, 4, 23)):
-        assert lib.vslam_tsdf_create(vo.h, size, J, log2, C.byref(h)) == ERR and not h.value, (size, J, log2)
-    assert lib.vslam_tsdf_create(None, 0.2, 4, 8, C.byref(h)) == ERR and lib.vslam_tsdf_create(vo.h, 0.2, 4, 8, None) == ERR
+        no("create %r %d %d" % (size, J, log2), lib.vslam_tsdf_create(vo.h, size, J, log2, C.byref(h)))
+        assert not h.value, (size, J, log2)
+    no("create null ctx", lib.vslam_tsdf_create(None, 0.2, 4, 8, C.byref(h)))
+    no("create null out", lib.vslam_tsdf_create(vo.h, 0.2, 4, 8, None))
     tm = vo.tsdf_map(0.2, 4, 6)
     other = pkg.VO(device=0, max_batch=1)
     zero = tm.stats()
@@ -237,24 +269,31 @@ def test_refused_arguments(vos, pkg):
         bad = [dict(B=0), dict(B=9), dict(step=0), dict(step=-1), dict(z0=50.0, z1=50.0), dict(z0=60.0), dict(z1=float("nan")), dict(d=None), dict(T=None), dict(w=0), dict(h=0)]
         for kw in bad:
             a = dict(good, **kw)
-            assert lib.vslam_tsdf_integrate_dev(vo.h, tm.h, a["d"], None, 0, 0, a["w"], a["h"], a["B"], a["T"], p, a["z0"], a["z1"], a["step"]) == ERR, kw
+            no("integrate %r" % kw, lib.vslam_tsdf_integrate_dev(vo.h, tm.h, a["d"], None, 0, 0, a["w"], a["h"], a["B"], a["T"], p, a["z0"], a["z1"], a["step"]))
         run = lambda ctx, m, ids, gray=None, img_bytes=0, pitch=0: lib.vslam_tsdf_integrate_dev(ctx, m, p, gray, img_bytes, pitch, 16, 8, 2, p, ids, 1.0, 50.0, 1)
-        assert run(vo.h, tm.h, None) == ERR and run(vo.h, None, p) == ERR and run(None, tm.h, p) == ERR
-        assert run(other.h, tm.h, p) == ERR, "a map of another context"
-        assert run(vo.h, tm.h, p, gray=p, img_bytes=16 * 8, pitch=15) == ERR and run(vo.h, tm.h, p, gray=p, img_bytes=16 * 7, pitch=16) == ERR
+        no("integrate null d_map_id", run(vo.h, tm.h, None))
+        no("integrate null map", run(vo.h, None, p))
+        no("integrate null ctx", run(None, tm.h, p))
+        no("integrate a map of another context", run(other.h, tm.h, p))
+        no("integrate pitch below w", run(vo.h, tm.h, p, gray=p, img_bytes=16 * 8, pitch=15))
+        no("integrate img_bytes below pitch * h", run(vo.h, tm.h, p, gray=p, img_bytes=16 * 7, pitch=16))
         for map_id in (-2, 1023):
-            assert lib.vslam_tsdf_extract_dev(vo.h, tm.h, map_id, 1, p, None, 4, p) == ERR, map_id
-            assert lib.vslam_tsdf_blocks_dev(vo.h, tm.h, map_id, p, p, 4, p) == ERR, map_id
-        assert lib.vslam_tsdf_extract_dev(vo.h, tm.h, -1, 1, p, None, 4, None) == ERR
-        assert lib.vslam_tsdf_extract_dev(vo.h, tm.h, -1, 1, None, None, 4, p) == ERR
-        assert lib.vslam_tsdf_extract_dev(vo.h, None, -1, 1, p, None, 4, p) == ERR and lib.vslam_tsdf_extract_dev(other.h, tm.h, -1, 1, p, None, 4, p) == ERR
-        assert lib.vslam_tsdf_blocks_dev(vo.h, tm.h, -1, p, p, 4, None) == ERR
-        assert lib.vslam_tsdf_blocks_dev(vo.h, tm.h, -1, None, p, 4, p) == ERR and lib.vslam_tsdf_blocks_dev(vo.h, tm.h, -1, p, None, 4, p) == ERR
-        assert lib.vslam_tsdf_blocks_dev(vo.h, None, -1, p, p, 4, p) == ERR
-        assert lib.vslam_tsdf_clear(None) == ERR and lib.vslam_tsdf_stats(tm.h, None) == ERR and lib.vslam_tsdf_stats(None, C.byref(pkg.TsdfStats())) == ERR
+            no("extract map_id %d" % map_id, lib.vslam_tsdf_extract_dev(vo.h, tm.h, map_id, 1, p, None, 4, p))
+            no("blocks map_id %d" % map_id, lib.vslam_tsdf_blocks_dev(vo.h, tm.h, map_id, p, p, 4, p))
+        no("extract null d_n_out", lib.vslam_tsdf_extract_dev(vo.h, tm.h, -1, 1, p, None, 4, None))
+        no("extract null d_out", lib.vslam_tsdf_extract_dev(vo.h, tm.h, -1, 1, None, None, 4, p))
+        no("extract null map", lib.vslam_tsdf_extract_dev(vo.h, None, -1, 1, p, None, 4, p))
+        no("extract a map of another context", lib.vslam_tsdf_extract_dev(other.h, tm.h, -1, 1, p, None, 4, p))
+        no("blocks null d_n_out", lib.vslam_tsdf_blocks_dev(vo.h, tm.h, -1, p, p, 4, None))
+        no("blocks null d_block_out", lib.vslam_tsdf_blocks_dev(vo.h, tm.h, -1, None, p, 4, p))
+        no("blocks null d_voxels_out", lib.vslam_tsdf_blocks_dev(vo.h, tm.h, -1, p, None, 4, p))
+        no("blocks null map", lib.vslam_tsdf_blocks_dev(vo.h, None, -1, p, p, 4, p))
+        no("clear null map", lib.vslam_tsdf_clear(None))
+        no("stats null host", lib.vslam_tsdf_stats(tm.h, None))
+        no("stats null map", lib.vslam_tsdf_stats(None, C.byref(pkg.TsdfStats())))
         st = pkg.TsdfStats(); st.struct_size = 8
-        assert lib.vslam_tsdf_stats(tm.h, C.byref(st)) == ERR
-        assert lib.vslam_set_tuning(vo.h, b"tsdf_form", 2) == ERR
+        no("stats struct_size", lib.vslam_tsdf_stats(tm.h, C.byref(st)))
+        no("set_tuning tsdf_form 2", lib.vslam_set_tuning(vo.h, b"tsdf_form", 2))
         vo.sync()
         assert tm.stats() == zero and zero["n_blocks"] == 0, "a refused call launches nothing"
     finally:

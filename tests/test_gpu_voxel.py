@@ -3,6 +3,8 @@ the numpy restatement tests/voxel_ref.py bit for bit (keys, counts and every flo
 insertion, a table that overflows, and every refused argument.  Shapes are small: 131 x 37 images are no multiple of the kernels' 64 x 16 tile
 and still span three tiles a row."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
@@ -20,6 +22,18 @@ def _dev(a):
     t = torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
     torch.cuda.synchronize()
     return t
+
+
+def _refusals(lib, err, section):
+    """no(key, rc): the call returned `err` and left the message tests/golden/refused_messages.json holds under `key` -- the text the library gave
+    before its host tier was put in order, which every later library must reproduce"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refused_messages.json")) as f:
+        want = json.load(f)[section]
+
+    def no(key, rc):
+        assert rc == err, key
+        assert lib.vslam_last_error().decode() == want[key], key
+    return no
 
 
 def _poses(synth, n, seed):
@@ -248,12 +262,15 @@ def test_overflow_drops_points_and_conserves_the_count(vo, synth, form):
 def test_refused_arguments(vo, pkg):
     import torch
     lib, ERR = vo.lib, pkg.VSLAM_ERR_ARG
+    no = _refusals(lib, ERR, "voxel")
     buf = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
     p = buf.data_ptr()
     h = C.c_void_p()
     for size, log2 in ((0.0, 12), (-0.2, 12), (float("nan"), 12), (float("inf"), 12), (1e-60, 12), (0.2, 9), (0.2, 29)):
-        assert lib.vslam_voxel_create(vo.h, size, log2, C.byref(h)) == ERR and not h.value, (size, log2)
-    assert lib.vslam_voxel_create(None, 0.2, 12, C.byref(h)) == ERR and lib.vslam_voxel_create(vo.h, 0.2, 12, None) == ERR
+        no("create %r %d" % (size, log2), lib.vslam_voxel_create(vo.h, size, log2, C.byref(h)))
+        assert not h.value, (size, log2)
+    no("create null ctx", lib.vslam_voxel_create(None, 0.2, 12, C.byref(h)))
+    no("create null out", lib.vslam_voxel_create(vo.h, 0.2, 12, None))
     vm = vo.voxel_map(0.2, 10)
     other = pkg.VO(device=0, max_batch=1)
     try:
@@ -262,28 +279,34 @@ def test_refused_arguments(vo, pkg):
         for kw in bad:
             a = dict(good, **kw)
             head = (a["d"], a["w"], a["h"], a["B"], a["T"], a["z0"], a["z1"], a["step"])
-            assert lib.vslam_reproject_dev(vo.h, *head, p, p) == ERR, kw
-            assert lib.vslam_voxel_fuse_disparity_dev(vo.h, vm.h, a["d"], None, 0, 0, a["w"], a["h"], a["B"], a["T"], p, a["z0"], a["z1"], a["step"]) == ERR, kw
+            no("reproject %r" % kw, lib.vslam_reproject_dev(vo.h, *head, p, p))
+            no("fuse %r" % kw, lib.vslam_voxel_fuse_disparity_dev(vo.h, vm.h, a["d"], None, 0, 0, a["w"], a["h"], a["B"], a["T"], p, a["z0"], a["z1"], a["step"]))
         head = (p, 16, 8, 2, p, 1.0, 50.0, 1)
-        assert lib.vslam_reproject_dev(vo.h, *head, None, p) == ERR and lib.vslam_reproject_dev(vo.h, *head, p, None) == ERR
-        assert lib.vslam_reproject_dev(None, *head, p, p) == ERR
+        no("reproject null d_xyz", lib.vslam_reproject_dev(vo.h, *head, None, p))
+        no("reproject null d_valid", lib.vslam_reproject_dev(vo.h, *head, p, None))
+        no("reproject null ctx", lib.vslam_reproject_dev(None, *head, p, p))
         fuse = lambda ctx, m, ids, gray=None, img_bytes=0, pitch=0: lib.vslam_voxel_fuse_disparity_dev(ctx, m, p, gray, img_bytes, pitch, 16, 8, 2, p, ids, 1.0, 50.0, 1)
-        assert fuse(vo.h, vm.h, None) == ERR and fuse(vo.h, None, p) == ERR and fuse(None, vm.h, p) == ERR
-        assert fuse(other.h, vm.h, p) == ERR, "a map of another context"
-        assert fuse(vo.h, vm.h, p, gray=p, img_bytes=16 * 8, pitch=15) == ERR and fuse(vo.h, vm.h, p, gray=p, img_bytes=16 * 7, pitch=16) == ERR
+        no("fuse null d_map_id", fuse(vo.h, vm.h, None))
+        no("fuse null map", fuse(vo.h, None, p))
+        no("fuse null ctx", fuse(None, vm.h, p))
+        no("fuse a map of another context", fuse(other.h, vm.h, p))
+        no("fuse pitch below w", fuse(vo.h, vm.h, p, gray=p, img_bytes=16 * 8, pitch=15))
+        no("fuse img_bytes below pitch * h", fuse(vo.h, vm.h, p, gray=p, img_bytes=16 * 7, pitch=16))
         for map_id in (-1, 1023, 1 << 20):
-            assert lib.vslam_voxel_insert_points_dev(vo.h, vm.h, p, None, None, 4, map_id) == ERR, map_id
-        assert lib.vslam_voxel_insert_points_dev(vo.h, vm.h, None, None, None, 4, 0) == ERR
-        assert lib.vslam_voxel_insert_points_dev(vo.h, None, p, None, None, 4, 0) == ERR
+            no("insert map_id %d" % map_id, lib.vslam_voxel_insert_points_dev(vo.h, vm.h, p, None, None, 4, map_id))
+        no("insert null d_xyz", lib.vslam_voxel_insert_points_dev(vo.h, vm.h, None, None, None, 4, 0))
+        no("insert null map", lib.vslam_voxel_insert_points_dev(vo.h, None, p, None, None, 4, 0))
         for map_id in (-2, 1023):
-            assert lib.vslam_voxel_extract_dev(vo.h, vm.h, map_id, 1, p, None, 4, p) == ERR, map_id
-        assert lib.vslam_voxel_extract_dev(vo.h, vm.h, -1, 1, p, None, 4, None) == ERR
-        assert lib.vslam_voxel_extract_dev(vo.h, vm.h, -1, 1, None, None, 4, p) == ERR
-        assert lib.vslam_voxel_extract_dev(vo.h, None, -1, 1, p, None, 4, p) == ERR
-        assert lib.vslam_voxel_clear(None) == ERR and lib.vslam_voxel_stats(vm.h, None) == ERR and lib.vslam_voxel_stats(None, C.byref(pkg.VoxelStats())) == ERR
+            no("extract map_id %d" % map_id, lib.vslam_voxel_extract_dev(vo.h, vm.h, map_id, 1, p, None, 4, p))
+        no("extract null d_n_out", lib.vslam_voxel_extract_dev(vo.h, vm.h, -1, 1, p, None, 4, None))
+        no("extract null d_out", lib.vslam_voxel_extract_dev(vo.h, vm.h, -1, 1, None, None, 4, p))
+        no("extract null map", lib.vslam_voxel_extract_dev(vo.h, None, -1, 1, p, None, 4, p))
+        no("clear null map", lib.vslam_voxel_clear(None))
+        no("stats null host", lib.vslam_voxel_stats(vm.h, None))
+        no("stats null map", lib.vslam_voxel_stats(None, C.byref(pkg.VoxelStats())))
         st = pkg.VoxelStats(); st.struct_size = 8
-        assert lib.vslam_voxel_stats(vm.h, C.byref(st)) == ERR
-        assert lib.vslam_set_tuning(vo.h, b"voxel_form", 2) == ERR
+        no("stats struct_size", lib.vslam_voxel_stats(vm.h, C.byref(st)))
+        no("set_tuning voxel_form 2", lib.vslam_set_tuning(vo.h, b"voxel_form", 2))
         vo.sync()
         assert vm.stats() == dict(n_occupied=0, n_points=0, n_dropped_range=0, n_dropped_full=0, status=0), "a refused call launches nothing"
     finally:
