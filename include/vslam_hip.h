@@ -1021,7 +1021,7 @@ struct vslam_tsdf_stats {
     uint64_t n_frames_skipped;  /* frames with a map id whose pose was not finite                     */
     uint64_t n_pairs_visited;   /* (block, frame) pairs of equal map id the integration has looked at */
     uint64_t n_pairs_kept;      /* ... of which the cull kept                                         */
-    uint32_t status;            /* bit 0: pool full; bit 1: a weight reached 2^20; bit 2: a frame was skipped for its pose; bit 3: a re-integration met a sum below what it was to take out */
+    uint32_t status;            /* bit 0: pool full; bit 1: a weight reached 2^20; bit 2: a frame was skipped for its pose; bit 3: a re-integration met a sum below what it was to take out; bit 4: a distance layer found no slot for a block and is void */
     int32_t struct_size;        /* sizeof(struct vslam_tsdf_stats) of the caller's header: set by the caller, checked */
 };
 typedef struct vslam_surfel {   /* one zero-crossing voxel edge (48 bytes) */
@@ -1123,6 +1123,61 @@ struct vslam_tsdf_render_params {
  * outside [1/8, 1], K > 8192, a null d_T_c_w, d_map_id or d_depth with V > 0, a misaligned pointer. */
 int vslam_tsdf_render_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const struct vslam_tsdf_render_params* params, int V, const double* d_T_c_w,
                           const int32_t* d_map_id, float* d_depth, float* d_attr, uint64_t* d_counts);
+/* DISTANCE.  How far a point is from the nearest surface of the map: a layer of squared Euclidean distances over the field, built on the device, and
+ * point queries against it.  All quantities are integers except the last step of a query, so the layer is exact, independent of the order the blocks
+ * arrived in and reproducible to the byte.
+ *   good(v) is EXTRACTION's predicate with the call's min_weight (below 1 counts as 1; a weight at 2^20 is not good), num(v) as there.
+ *   CLASS of a voxel: 0 UNKNOWN (not good, or in no claimed block), 1 FREE (good and num > 0), 2 OCCUPIED (good and num <= 0: an exact zero is not
+ *   positive, as in MESH and RENDER).
+ *   SITE: an OCCUPIED voxel with at least one of its six face neighbours, in whichever block of the same map, FREE -- the non-positive end of every
+ *   crossing edge of EXTRACTION, nothing else.
+ *   d2(v), for any voxel index v in [-2^17, 2^17)^3: the minimum over the sites s of the same map of |v - s|^2, an integer in voxel units; FAR if that
+ *   minimum exceeds R^2 or the map has no site.  R = radius_voxels in [1, 16], so d2 <= 256.  Sites of different maps never see each other.
+ *   CELL WORD (uint16): bits 0-11 d2, 0xFFF = FAR; bits 12-13 the class; bits 14-15 zero.
+ *   LAYER of a build call: every block with coordinates in [-2^14, 2^14) that (a) is claimed in the pool for a map the call covers, or (b) holds at
+ *   least one voxel with d2 != FAR.  Blocks of kind (b) are in general NOT claimed in the pool; their voxels are UNKNOWN.  A block is 512 cell words
+ *   in EXTRACTION's voxel order: 1 KiB.  A build with map_id >= 0 covers that map alone: no block of another map is in the layer.
+ *   QUERY of a world point Xw (three f64) in map m: i[a] = floor(Xw[a] / vs) in f64, in the written order, no contraction.  Class 3 INVALID with
+ *   dist = +INFINITY when m is outside 0 .. 1022, a coordinate is not finite or an index is outside [-2^17, 2^17).  Otherwise the cell word is the
+ *   voxel's; a block outside the layer reads as FAR | UNKNOWN.  dist = (float)(sqrt((double)d2) * vs), negated when the class is OCCUPIED and d2 > 0;
+ *   FAR gives +INFINITY, or -INFINITY when OCCUPIED.  The voxel is the NEAREST one: one sample per query, no interpolation, so the distance is that
+ *   between voxel centres and moves in steps.
+ * The layer lives in the map handle: a key table and cell pool of its own of 2^log2_layer_blocks blocks with the build's scratch, 2257 bytes per block
+ * and 64 more, counted in vslam_device_bytes and released by vslam_tsdf_destroy.  It is grown by the first build or by a larger request, which
+ * synchronises the context stream; the build itself is asynchronous on that stream and replaces any earlier layer of the handle.  The pool is not
+ * written.  Before anything is computed the build claims, in the layer's table, every claimed block of the covered maps and every block within
+ * ceil(R / 8) blocks per axis of a block that holds a site (coordinates outside [-2^14, 2^14) are dropped, never wrapped); one of these that finds no
+ * slot -- the table is full, or for tables of 128 slots or more no free slot lies within 128 probes -- makes the whole layer VOID: status bit 4 of
+ * vslam_tsdf_stats is set (it stays set until vslam_tsdf_clear), vslam_tsdf_distance_blocks_dev writes a count of 0, every valid query answers
+ * FAR | UNKNOWN and the build's counts are (sites, 0, 0).  Nothing is half-served.
+ * The layer is a snapshot: vslam_tsdf_integrate_dev, vslam_tsdf_reintegrate_dev (with B > 0), vslam_tsdf_load_blocks_dev and vslam_tsdf_clear make it
+ * stale, and the two readers below refuse a map whose layer is missing or stale (VSLAM_ERR_ARG, "distance layer not built or older than the map").
+ * Two forms, same bytes (vslam_set_tuning "tsdf_dist_form"): 0 = every voxel takes the minimum over the site masks of the blocks around it; 1 = the
+ * separable exact transform, three passes along x, y and z. */
+struct vslam_tsdf_distance_params {
+    int32_t struct_size;         /* sizeof(struct vslam_tsdf_distance_params) of the caller's header: set by the caller, checked */
+    int32_t map_id;              /* 0 .. 1022, or -1: every map */
+    int32_t min_weight;
+    int32_t radius_voxels;       /* [1, 16] */
+    int32_t log2_layer_blocks;   /* [6, 24] */
+    int32_t reserved;
+};
+/* Builds the layer by the DISTANCE rule.  d_counts: NULL, or three uint64 (device, 8-byte aligned): the sites, the layer's blocks, and those of them
+ * that the pool does not hold for a covered map (kind (b) only).  An empty map succeeds with an empty layer.  VSLAM_ERR_ARG: a null map or a map of
+ * another context, null params or a wrong struct_size, map_id outside [-1, 1022], radius_voxels outside [1, 16], log2_layer_blocks outside [6, 24], a
+ * misaligned d_counts. */
+int vslam_tsdf_distance_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const struct vslam_tsdf_distance_params* params, uint64_t* d_counts);
+/* The layer's blocks of map map_id (-1: every map the build covered): (map, bx, by, bz) into d_block_out (`capacity` x 4 int32) and the block's 512 cell
+ * words into d_cells_out (`capacity` x 512 uint16), both 16-byte aligned; *d_n_out (uint64, device) = the full count even when it exceeds `capacity`;
+ * nothing is stored at or beyond it; the order is unspecified.  A block the build claimed that ended all FAR and is not claimed in the pool is not
+ * emitted.  Asynchronous on the context stream.  VSLAM_ERR_ARG: a null or foreign map, a null d_n_out, a null output with a capacity, map_id outside
+ * [-1, 1022], a misaligned pointer, a missing or stale layer. */
+int vslam_tsdf_distance_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int32_t* d_block_out, uint16_t* d_cells_out, size_t capacity,
+                                   uint64_t* d_n_out);
+/* N point queries by the DISTANCE rule: d_xyz_w N x 3 f64 world points, d_map_id N map ids, d_dist N floats, d_class N bytes (0 .. 3).  Asynchronous on
+ * the context stream; N == 0 succeeds.  VSLAM_ERR_ARG: a null or foreign map, a null pointer with N > 0, a misaligned pointer, a missing or stale layer. */
+int vslam_tsdf_distance_query_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const double* d_xyz_w, const int32_t* d_map_id, size_t N, float* d_dist,
+                                  uint8_t* d_class);
 
 /* ------------------------------------------------------------------ place database: loop-closure candidates and verified edges --- */
 /* Noticing that the camera is back at a place it has seen: keyframe descriptor blocks are kept in a database that outlives the steps (loops close

@@ -124,6 +124,13 @@ class TsdfRenderParams(C.Structure):
                 ("z_min", C.c_double), ("z_max", C.c_double), ("march", C.c_double), ("min_weight", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TsdfDistanceParams(C.Structure):
+    """struct vslam_tsdf_distance_params: the maps covered, the weight gate, the radius in voxels and the size of the layer's table of one
+    vslam_tsdf_distance_dev call"""
+    _fields_ = [("struct_size", C.c_int32), ("map_id", C.c_int32), ("min_weight", C.c_int32), ("radius_voxels", C.c_int32),
+                ("log2_layer_blocks", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PlaceStats(C.Structure):
     """struct vslam_place_stats: entries held, capacity, rows per entry, geometry flag and the adds refused for lack of room"""
     _fields_ = [("n_entries", C.c_int32), ("capacity", C.c_int32), ("rows_per_entry", C.c_int32), ("with_geometry", C.c_int32),
@@ -306,6 +313,9 @@ SIGNATURES = {
     "vslam_tsdf_mesh_dev": (I, [P, P, I, I, P, P, Z, P, Z, P]),
     "vslam_tsdf_load_blocks_dev": (I, [P, P, P, P, Z]),
     "vslam_tsdf_render_dev": (I, [P, P, C.POINTER(TsdfRenderParams), I, P, P, P, P, P]),
+    "vslam_tsdf_distance_dev": (I, [P, P, C.POINTER(TsdfDistanceParams), P]),
+    "vslam_tsdf_distance_blocks_dev": (I, [P, P, I, P, P, Z, P]),
+    "vslam_tsdf_distance_query_dev": (I, [P, P, P, P, Z, P, P]),
     "vslam_place_create": (I, [P, I, I, I, C.POINTER(C.c_void_p)]), "vslam_place_destroy": (None, [P]), "vslam_place_clear": (I, [P]),
     "vslam_place_stats": (I, [P, C.POINTER(PlaceStats)]),
     "vslam_place_read_entry": (I, [P, I, P, P, P, P, P, P]),
@@ -1411,6 +1421,49 @@ class TsdfMap(_Owned):
         attr = d_attr.cpu().numpy() if attrs else None
         return dict(depth=d_depth.cpu().numpy(), normal=attr[..., :3] if attrs else None, intensity=attr[..., 3] if attrs else None,
                     counts=tuple(int(c) for c in d_counts.cpu().tolist()))
+
+    def distance(self, map_id=-1, min_weight=1, radius=8, log2_layer_blocks=None):
+        """builds the map's clearance layer (include/vslam_hip.h "DISTANCE") over map map_id (-1: every map) with radius `radius` voxels in [1, 16] and
+        reads it back: dict(ids (n, 4) int32 of (map, bx, by, bz), cells (n, 512) uint16 cell words -- bits 0-11 the squared distance to the nearest
+        site in voxel units (0xFFF: FAR), bits 12-13 the class (0 UNKNOWN, 1 FREE, 2 OCCUPIED) -- in blocks()' voxel order, counts = (sites, layer
+        blocks, layer blocks the pool does not hold)), sorted by (map, bx, by, bz).  log2_layer_blocks: the size of the layer's table (None: the
+        map's log2_blocks); a layer that does not fit is void (stats()["status"] bit 4, no blocks).  The layer stays in the handle for
+        distance_query() until the map changes."""
+        import torch
+        vo = self.vo
+        dp = TsdfDistanceParams(struct_size=C.sizeof(TsdfDistanceParams), map_id=int(map_id), min_weight=int(min_weight), radius_voxels=int(radius),
+                                log2_layer_blocks=int(self.log2_blocks if log2_layer_blocks is None else log2_layer_blocks))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_counts = torch.zeros(3, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)   # (the buffer is ready before the context stream writes it)
+        vo._chk(vo.lib.vslam_tsdf_distance_dev(vo.h, self.h, C.byref(dp), d_counts.data_ptr()), "vslam_tsdf_distance_dev")
+        vo.sync()
+        counts = tuple(int(c) for c in d_counts.cpu().tolist())
+        call = lambda *out: vo._chk(vo.lib.vslam_tsdf_distance_blocks_dev(vo.h, self.h, map_id, *out), "vslam_tsdf_distance_blocks_dev")
+        ((ids, cells),), (self.last_count,) = _read_lists(vo, call, [[(torch.int32, (4,), 0), (torch.uint8, (1024,), 0)]], [max(counts[1], 1)])
+        cells = cells.view(np.uint16).reshape(len(ids), 512)
+        order = np.lexsort((ids[:, 3], ids[:, 2], ids[:, 1], ids[:, 0]))
+        return dict(ids=ids[order], cells=cells[order], counts=counts)
+
+    def distance_query(self, xyz, map_id=0):
+        """the clearance of world points against the layer distance() built: xyz (N, 3) float64, map_id one id or (N,) -> (dist (N,) float32 in
+        metres -- negative inside occupied space, +-inf beyond the radius --, cls (N,) uint8: 0 UNKNOWN, 1 FREE, 2 OCCUPIED, 3 INVALID).  The
+        nearest voxel answers: no interpolation."""
+        import torch
+        vo = self.vo
+        xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        N = len(xyz)
+        ids = np.array(np.broadcast_to(np.asarray(map_id, np.int32), (N,)))                 # (a copy: the caller's array may be read-only)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        d_xyz = torch.from_numpy(xyz).to(dev)
+        d_ids = torch.from_numpy(ids).to(dev)
+        d_dist = torch.zeros(max(N, 1), dtype=torch.float32, device=dev)
+        d_cls = torch.zeros(max(N, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)   # (the buffers are ready before the context stream writes them)
+        vo._chk(vo.lib.vslam_tsdf_distance_query_dev(vo.h, self.h, d_xyz.data_ptr(), d_ids.data_ptr(), N, d_dist.data_ptr(), d_cls.data_ptr()),
+                "vslam_tsdf_distance_query_dev")
+        vo.sync()
+        return d_dist[:N].cpu().numpy(), d_cls[:N].cpu().numpy()
 
 
 class PlaceDB(_Owned):

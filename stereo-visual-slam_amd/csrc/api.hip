@@ -160,6 +160,7 @@ static const TuneKey kTuneKeys[] = {
     {"rectify_form", "VSLAM_RECTIFY_FORM", &Tuning::rectify_form, 0, 1},
     {"voxel_form", "VSLAM_VOXEL_FORM", &Tuning::voxel_form, 0, 1},
     {"tsdf_form", "VSLAM_TSDF_FORM", &Tuning::tsdf_form, 0, 1},
+    {"tsdf_dist_form", "VSLAM_TSDF_DIST_FORM", &Tuning::tsdf_dist_form, 0, 1},
     {"tsdf_render_form", "VSLAM_TSDF_RENDER_FORM", &Tuning::tsdf_render_form, 0, 1},
     {"pg_precond", "VSLAM_PG_PRECOND", &Tuning::pg_precond, 0, 1},
     {"fba_store", "VSLAM_FBA_STORE", &Tuning::fba_store, 0, 1},
@@ -317,6 +318,8 @@ const char* vslam_kernel_names(void) { // the ProfScope names of csrc/*.hip (tes
            "tsdf_clear_kernel tsdf_frames_kernel tsdf_alloc_kernel tsdf_cull_kernel tsdf_integrate_kernel tsdf_extract_kernel tsdf_blocks_kernel tsdf_mesh_vertex_kernel tsdf_mesh_tri_kernel tsdf_load_kernel "
            "tsdf_reint_frames_kernel tsdf_reint_cull_kernel tsdf_reint_kernel "
            "tsdf_views_kernel tsdf_range_init_kernel tsdf_ray_range_kernel tsdf_render_kernel "
+           "tsdf_dist_clear_kernel tsdf_dist_classify_kernel tsdf_dist_dilate_kernel tsdf_dist_brute_kernel tsdf_dist_row_kernel tsdf_dist_pass_kernel tsdf_dist_counts_kernel "
+           "tsdf_dist_blocks_kernel tsdf_dist_query_kernel "
            "place_add_kernel place_score_init_kernel place_score_kernel place_select_kernel place_verify_prep_kernel place_gather_kernel "
            "pose_graph_kernel full_ba_kernel project_match_kernel";
 }
@@ -1903,6 +1906,7 @@ void vslam_tsdf_destroy(vslam_tsdf_map* tm) {
     m->mesh.release();
     m->render.release();
     m->reint.release();
+    m->dist.release();
     delete m;
 }
 
@@ -1910,6 +1914,7 @@ int vslam_tsdf_clear(vslam_tsdf_map* tm) {
     TsdfMap* m = reinterpret_cast<TsdfMap*>(tm);
     if (!m) { set_error("vslam_tsdf_clear: null map"); return VSLAM_ERR_ARG; }
     VS_ENTER(m->ctx);
+    m->epoch += 1;
     return launch_tsdf_clear(m->t, m->ctx->stream);
 }
 
@@ -1932,6 +1937,7 @@ int vslam_tsdf_integrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* d_
     VoxelImages a;
     if (int rc = map_images(c, "vslam_tsdf_integrate_dev", d_disparity, d_gray, img_bytes, pitch, w, h, B, d_T_c_w, d_map_id, z_min, z_max, step, a)) return rc;
     VS_ENTER(c);
+    m->epoch += 1;
     return launch_tsdf_integrate(m->t, a, d_gray, img_bytes, pitch, d_map_id, tsdf_form(c), c->stream);
 }
 
@@ -1957,6 +1963,7 @@ int vslam_tsdf_reintegrate_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const float* 
     VoxelImages a;
     if (int rc = map_images(c, "vslam_tsdf_reintegrate_dev", d_disparity, d_gray, img_bytes, pitch, w, h, B, d_T_new, d_map_id, z_min, z_max, step, a)) return rc;
     VS_ENTER(c);
+    m->epoch += 1;
     if (int rc = m->reint.reserve(tsdf_reint_table_bytes(m->t, c->p.max_batch), c->stream)) return rc;
     const TsdfReint r = tsdf_reint_tables(m->t, c->p.max_batch, m->reint.p, d_reach);
     return launch_tsdf_reintegrate(m->t, r, a, d_gray, img_bytes, pitch, d_T_old, d_map_id, tsdf_form(c), c->stream);
@@ -2022,6 +2029,7 @@ int vslam_tsdf_load_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const int32_t
         set_error("vslam_tsdf_load_blocks_dev: d_block_ids and d_voxels must be 16-byte aligned"); return VSLAM_ERR_ARG;
     }
     VS_ENTER(c);
+    m->epoch += 1;
     return launch_tsdf_load(m->t, d_block_ids, d_voxels, n, c->stream);
 }
 
@@ -2065,6 +2073,66 @@ int vslam_tsdf_render_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const struct vslam
     call.fx = rp->fx; call.fy = rp->fy; call.cx = rp->cx; call.cy = rp->cy; call.z_min = rp->z_min; call.hs = hs;
     call.d_T = d_T_c_w; call.d_map_id = d_map_id; call.d_depth = d_depth; call.d_attr = d_attr; call.d_counts = reinterpret_cast<unsigned long long*>(d_counts);
     return launch_tsdf_render(m->t, call, m->render.p, form, c->stream);
+}
+
+// Form of the distance layer's build: 0 = every voxel walks the site masks of the blocks around it, 1 = the separable transform in three passes
+// (DESIGN.md 5.17); Tuning::tsdf_dist_form overrides it (tests and tools/bench_tsdf_distance.py run both)
+constexpr int kTsdfDistFormDefault = 1;
+
+int vslam_tsdf_distance_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const struct vslam_tsdf_distance_params* dp, uint64_t* d_counts) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_distance_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (!dp || dp->struct_size != (int32_t)sizeof(struct vslam_tsdf_distance_params)) { set_error("vslam_tsdf_distance_dev: null params or struct_size mismatch"); return VSLAM_ERR_ARG; }
+    if (int rc = map_id_check("vslam_tsdf_distance_dev", dp->map_id, -1)) return rc;
+    if (dp->radius_voxels < 1 || dp->radius_voxels > 16) { set_error("vslam_tsdf_distance_dev: radius_voxels %d outside [1, 16]", dp->radius_voxels); return VSLAM_ERR_ARG; }
+    if (dp->log2_layer_blocks < 6 || dp->log2_layer_blocks > 24) { set_error("vslam_tsdf_distance_dev: log2_layer_blocks %d outside [6, 24]", dp->log2_layer_blocks); return VSLAM_ERR_ARG; }
+    if (reinterpret_cast<uintptr_t>(d_counts) % 8) { set_error("vslam_tsdf_distance_dev: d_counts must be 8-byte aligned"); return VSLAM_ERR_ARG; }
+    VS_ENTER(c);
+    m->dist_built = false; // (a build that fails below leaves no layer)
+    if (int rc = m->dist.reserve(tsdf_dist_layer_bytes(dp->log2_layer_blocks), c->stream)) return rc;
+    const TsdfLayer L = tsdf_dist_layer(m->dist.p, dp->log2_layer_blocks);
+    const int form = c->tune.tsdf_dist_form >= 0 ? c->tune.tsdf_dist_form : kTsdfDistFormDefault;
+    if (int rc = launch_tsdf_distance(m->t, L, dp->map_id, dp->min_weight, dp->radius_voxels, form, reinterpret_cast<unsigned long long*>(d_counts), c->stream)) return rc;
+    m->dist_built = true; m->dist_epoch = m->epoch; m->dist_log2 = dp->log2_layer_blocks;
+    return VSLAM_OK;
+}
+
+// the layer of a map for a reader, or a refusal when none was built or the map changed since
+static int dist_layer_of(const TsdfMap* m, const char* who, TsdfLayer& L) {
+    if (!m->dist_built || m->dist_epoch != m->epoch) { set_error("%s: distance layer not built or older than the map", who); return VSLAM_ERR_ARG; }
+    L = tsdf_dist_layer(m->dist.p, m->dist_log2);
+    return VSLAM_OK;
+}
+
+int vslam_tsdf_distance_blocks_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, int map_id, int32_t* d_block_out, uint16_t* d_cells_out, size_t capacity, uint64_t* d_n_out) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_distance_blocks_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (int rc = counted_output_check("vslam_tsdf_distance_blocks_dev", d_n_out, capacity, d_block_out && d_cells_out, "a null output")) return rc;
+    if (int rc = map_id_check("vslam_tsdf_distance_blocks_dev", map_id, -1)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_block_out) % 16 || reinterpret_cast<uintptr_t>(d_cells_out) % 16 || reinterpret_cast<uintptr_t>(d_n_out) % 8) {
+        set_error("vslam_tsdf_distance_blocks_dev: d_block_out and d_cells_out must be 16-byte, d_n_out 8-byte aligned"); return VSLAM_ERR_ARG;
+    }
+    TsdfLayer L;
+    if (int rc = dist_layer_of(m, "vslam_tsdf_distance_blocks_dev", L)) return rc;
+    VS_ENTER(c);
+    return launch_tsdf_distance_blocks(L, map_id, d_block_out, d_cells_out, capacity, reinterpret_cast<unsigned long long*>(d_n_out), c->stream);
+}
+
+int vslam_tsdf_distance_query_dev(vslam_ctx* ctx, vslam_tsdf_map* tm, const double* d_xyz_w, const int32_t* d_map_id, size_t N, float* d_dist, uint8_t* d_class) {
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    TsdfMap* m = owned_by<TsdfMap>(c, tm, "vslam_tsdf_distance_query_dev");
+    if (!m) return VSLAM_ERR_ARG;
+    if (N > 0 && (!d_xyz_w || !d_map_id || !d_dist || !d_class)) { set_error("vslam_tsdf_distance_query_dev: a null pointer with N > 0"); return VSLAM_ERR_ARG; }
+    if (reinterpret_cast<uintptr_t>(d_xyz_w) % 8 || reinterpret_cast<uintptr_t>(d_map_id) % 4 || reinterpret_cast<uintptr_t>(d_dist) % 4) {
+        set_error("vslam_tsdf_distance_query_dev: d_xyz_w must be 8-byte, d_map_id and d_dist 4-byte aligned"); return VSLAM_ERR_ARG;
+    }
+    TsdfLayer L;
+    if (int rc = dist_layer_of(m, "vslam_tsdf_distance_query_dev", L)) return rc;
+    if (N == 0) return VSLAM_OK;
+    VS_ENTER(c);
+    return launch_tsdf_distance_query(m->t, L, d_xyz_w, d_map_id, N, d_dist, d_class, c->stream);
 }
 
 // ---------------------------------------------------------------------------------------------- place database

@@ -281,6 +281,7 @@ struct Tuning {
     int pg_precond = -1;      // VSLAM_PG_PRECOND: preconditioner of pose_graph_kernel's conjugate gradients -- 0 = block-Jacobi, 1 = chain (block-tridiagonal); default: the rule of DESIGN.md 5.10
     int voxel_form = -1;      // VSLAM_VOXEL_FORM: voxel_fuse_kernel -- 0 = every point straight into the global table, 1 = a workgroup sums its image tile in an LDS hash table first (same table either way)
     int tsdf_render_form = -1; // VSLAM_TSDF_RENDER_FORM: vslam_tsdf_render_dev -- 0 = every ray walks all K samples, 1 = tsdf_ray_range_kernel narrows each tile's sample range first (same bytes either way); default: DESIGN.md 5.15
+    int tsdf_dist_form = -1;  // VSLAM_TSDF_DIST_FORM: vslam_tsdf_distance_dev -- 0 = tsdf_dist_brute_kernel walks the site masks around every voxel, 1 = the separable transform in three passes (same bytes either way); default: DESIGN.md 5.17
     int tsdf_form = -1;       // VSLAM_TSDF_FORM: tsdf_integrate_kernel -- 0 = every block walks all frames of the call, 1 = tsdf_cull_kernel writes a frame mask per block first (same sums either way); default: DESIGN.md 5.13
     int ba_adaptive = -1;     // VSLAM_BA_ADAPTIVE: 0 = the BA schedule runs all three optimize_map passes for every window (default: a pass that flags nothing new is continued instead of repeated)
     int pm_stage = -1;        // VSLAM_PM_STAGE: project_match_kernel -- 1 = the target image's descriptors staged in LDS (where two workgroups per CU still fit), 0 = read from L2; default: DESIGN.md 5.12
@@ -513,7 +514,11 @@ struct TsdfMap : Owned { static constexpr const char* noun = "map"; TsdfTable t;
                  DevBuf mesh; // the vertex-id table of vslam_tsdf_mesh_dev: vid (3 x 512 int32 per claimed block) | pos_of_slot (one uint32 per slot); grown by the first mesh call
                  DevBuf render; // the tables of vslam_tsdf_render_dev: the view table (16 doubles per view) | (form 1) one (k_lo, k_hi) per view and 16 x 16 tile; grown on demand
                  DevBuf reint; // the old sides of vslam_tsdf_reintegrate_dev: a second frame table | a second frame mask per slot | n0; grown by the first such call
-                 TsdfMap(size_t* acct) : mesh("mesh vertex-id table", acct), render("render view and range tables", acct), reint("re-integration tables", acct) {} };
+                 DevBuf dist; // the clearance layer of vslam_tsdf_distance_dev (TsdfLayer below); grown by the first build or a larger request
+                 // epoch: bumped by integrate, reintegrate, load_blocks and clear; the layer serves readers only while dist_epoch == epoch
+                 unsigned long long epoch = 0, dist_epoch = 0; bool dist_built = false; int dist_log2 = 0;
+                 TsdfMap(size_t* acct) : mesh("mesh vertex-id table", acct), render("render view and range tables", acct), reint("re-integration tables", acct),
+                                         dist("distance layer", acct) {} };
 int launch_tsdf_clear(const TsdfTable& t, hipStream_t stream);
 int launch_tsdf_alloc(const TsdfTable& t, const VoxelImages& a, hipStream_t stream); // ALLOCATION of the frames of t.frames
 // form: 0 = every block walks all frames, 1 = a cull kernel writes a frame mask per block first
@@ -523,6 +528,25 @@ int launch_tsdf_extract(const TsdfTable& t, int map_id, int min_weight, vslam_su
                         hipStream_t stream);
 int launch_tsdf_blocks(const TsdfTable& t, int map_id, int32_t* d_block_out, uint32_t* d_voxels_out, size_t capacity, unsigned long long* d_n_out,
                        hipStream_t stream);
+// tsdf_dist_kernels.hip: the clearance layer (include/vslam_hip.h "DISTANCE").  A key table of its own of 2^log2_blocks slots, slot s owning block s of
+// `cells` (512 uint16 cell words in the pool's voxel order), of `tmp` (the separable form's second buffer), of `masks` (three 512-bit masks: site, free,
+// occupied) and of `kind` (bit 0: claimed in the pool for a map the build covered, bit 1: holds a voxel within R of a site; 0: not emitted).  `list`
+// holds the claimed slots, `site_list` those whose block holds a site.
+constexpr int kDistCounters = 8;         // uint64 words; the indices follow
+constexpr int kDistNList = 0, kDistSites = 1, kDistNSiteBlocks = 2, kDistVoid = 3, kDistNLayer = 4, kDistNKindB = 5;
+constexpr int kDistMaskWords = 24;
+constexpr size_t kDistBlockBytes = 8 + 8 * kDistMaskWords + 1024 + 1024 + 4 + 4 + 1;   // per slot: key, masks, cells, tmp, list, site_list, kind
+struct TsdfLayer { unsigned long long* counters; unsigned long long* keys; unsigned long long* masks; uint16_t* cells; uint16_t* tmp; uint32_t* list;
+                   uint32_t* site_list; uint8_t* kind; int log2_blocks; };
+size_t tsdf_dist_layer_bytes(int log2_layer_blocks);
+TsdfLayer tsdf_dist_layer(uint8_t* base, int log2_layer_blocks);
+// R = radius_voxels in [1, 16]; form: 0 = every voxel walks the site masks around it, 1 = the separable transform, three passes (same bytes);
+// d_counts null or 3 words: sites, layer blocks, layer blocks the pool does not hold
+int launch_tsdf_distance(const TsdfTable& t, const TsdfLayer& L, int map_id, int min_weight, int R, int form, unsigned long long* d_counts, hipStream_t stream);
+int launch_tsdf_distance_blocks(const TsdfLayer& L, int map_id, int32_t* d_block_out, uint16_t* d_cells_out, size_t capacity, unsigned long long* d_n_out,
+                                hipStream_t stream);
+int launch_tsdf_distance_query(const TsdfTable& t, const TsdfLayer& L, const double* d_xyz_w, const int32_t* d_map_id, size_t N, float* d_dist, uint8_t* d_class,
+                               hipStream_t stream);
 // tsdf_reint_kernels.hip: frames taken out at their old poses and put in at their new ones (include/vslam_hip.h "RE-INTEGRATION").  The new sides use
 // the map's own frame table and masks (t.frames, t.pairs); the old sides the tables of TsdfMap::reint, laid out alike.  n0 = the blocks claimed before the call.
 struct TsdfReint { double* frames_old; unsigned long long* pairs_old; uint32_t* n0; const uint32_t* reach; };

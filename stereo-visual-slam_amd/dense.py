@@ -111,6 +111,37 @@ def write_depth_pgm(path, depth, z_max):
         f.write(v.tobytes())
 
 
+def clearance_slice(ids, cells, voxel_size, axis=1, lo=0, hi=1, map_id=None):
+    """The costmap a ground planner reads off a clearance layer (TsdfMap.distance: ids (n, 4) of (map, bx, by, bz), cells (n, 512) uint16): over the
+    voxel indices [lo, hi) along `axis`, per column of the other two axes the minimum squared distance d2 (voxel units; 0xFFF where every voxel of
+    the column is FAR or outside the layer) and whether any voxel of the column is OCCUPIED.  map_id: the map to read (None: every block given).
+    Returns dict(d2 (na, nb) uint16, occupied (na, nb) bool, origin (ia, ib) -- the voxel indices of d2[0, 0] along the two remaining axes in
+    ascending axis order, so the column's corner in metres is origin * voxel_size --, axes (a, b), voxel_size); empty (0, 0) arrays when no block
+    meets the band."""
+    ids = np.asarray(ids, np.int64).reshape(-1, 4)
+    cells = np.asarray(cells, np.uint16).reshape(len(ids), 8, 8, 8)   # (z, y, x)
+    assert axis in (0, 1, 2) and hi > lo, (axis, lo, hi)
+    a, b = [k for k in range(3) if k != axis]
+    keep = (ids[:, 1 + axis] * 8 + 7 >= lo) & (ids[:, 1 + axis] * 8 < hi)
+    if map_id is not None:
+        keep &= ids[:, 0] == map_id
+    ids, cells = ids[keep], cells[keep]
+    if not len(ids):
+        return dict(d2=np.zeros((0, 0), np.uint16), occupied=np.zeros((0, 0), bool), origin=(0, 0), axes=(a, b), voxel_size=float(voxel_size))
+    a0, b0 = int(ids[:, 1 + a].min()) * 8, int(ids[:, 1 + b].min()) * 8
+    na, nb = int(ids[:, 1 + a].max()) * 8 + 8 - a0, int(ids[:, 1 + b].max()) * 8 + 8 - b0
+    d2 = np.full((na, nb), 0xFFF, np.uint16)
+    occ = np.zeros((na, nb), bool)
+    for bid, blk in zip(ids, cells):
+        blk = np.moveaxis(blk.transpose(2, 1, 0), axis, 2)           # (x, y, z) -> (a, b, axis)
+        k = np.arange(8) + bid[1 + axis] * 8
+        blk = blk[:, :, (k >= lo) & (k < hi)]
+        ia, ib = int(bid[1 + a]) * 8 - a0, int(bid[1 + b]) * 8 - b0
+        d2[ia:ia + 8, ib:ib + 8] = np.minimum(d2[ia:ia + 8, ib:ib + 8], (blk & 0xFFF).min(axis=2))
+        occ[ia:ia + 8, ib:ib + 8] |= (((blk >> 12) & 3) == 2).any(axis=2)
+    return dict(d2=d2, occupied=occ, origin=(a0, b0), axes=(a, b), voxel_size=float(voxel_size))
+
+
 def read_depth_pgm(path, z_max):
     """the (h, w) float64 depth of a file write_depth_pgm wrote with the same z_max: 0 where the ray missed, otherwise within z_max / 131070 of the
     depth written"""

@@ -797,6 +797,21 @@ class KeyframePipeline:
                 out["disparity"] = np.where(depth > 0, K4[0] * b / depth, 0.0).astype(np.float32)
         return out
 
+    def surface_clearance(self, radius_m, tsdf_map=None, min_weight=1):
+        """The clearance layer of the surface map (TsdfMap.distance, include/vslam_hip.h "DISTANCE") out to radius_m metres: per voxel the squared
+        distance in voxels to the nearest surface voxel of its map and the voxel's class.  The radius in voxels is ceil(radius_m / voxel size) and
+        must not exceed 16.  tsdf_map: a TsdfMap of this pipeline's context (None: the one the last surface_map() returned).  Returns
+        TsdfMap.distance's dict (ids, cells, counts) with radius (voxels) and voxel_size added; tm.distance_query(points, map_id) then answers
+        points until the map changes, and dense.clearance_slice(ids, cells, ...) flattens a height band into a costmap."""
+        tm = tsdf_map if tsdf_map is not None else getattr(self, "last_surface_map", None)
+        assert tm is not None and getattr(tm, "h", None), "surface_clearance needs a TsdfMap: call surface_map() first or pass tsdf_map="
+        vs = float(np.float32(tm.voxel_size))
+        radius = int(np.ceil(float(radius_m) / vs))
+        assert 1 <= radius <= 16, "surface_clearance: radius_m %g is %d voxels of %g m, outside [1, 16]" % (radius_m, radius, vs)
+        out = tm.distance(map_id=-1, min_weight=min_weight, radius=radius)
+        out.update(radius=radius, voxel_size=vs)
+        return out
+
     # ------------------------------------------------------------------ loop closure (nothing here runs unless loop_closures is called)
     def show_sequence(self, sequence):
         """lay another rendered sequence of the same length over the batch (an unsegmented pipeline without a rig): the next step() sees its frames.
